@@ -81,6 +81,8 @@ def main():
                     "are synthetic N(0, 1) bf16 rows written once (a step's time depends on how many rows it reads, not on their values), the decode state is set to the window's first position")
     ap.add_argument("--lean", action="store_true", help="only the timed decode and step_roofline (what the side legs run in their child processes)")
     ap.add_argument("--leg", default="", choices=["", "config3", "config4cpu"], help="run ONE side leg and print its JSON (child processes of the main run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, what they computed as DIR/<name>.npy: logits.npy = the last step's logits (float32), "
+                    "ids.npy = the greedy ids of the last min(steps, max_seq) timed steps in step order (float64), the last one the last step's pick; same arguments, same inputs")
     ap.add_argument("--side-legs", default="config3,config5,config4,qwen3_1p7b,qwen3_1p7b_launches,qwen3_4b", help="side objects beside the line, each measured in a child process after the main measurements "
                     "(never `value`): config3 = GPT2-1558M operator path of a training step (sum of separately timed forward+loss, backward, AdamW phases; no parameter update), config5 = 1-bit layers + 20 %% hot FFN rows, config4 = Qwen3-32B on ONE GPU; '' = none")
     args = ap.parse_args()
@@ -122,6 +124,8 @@ def main():
     if K < 1 or W < 0:
         raise SystemExit("steps >= 1, warmup >= 0")
     if (args.config == "qwen3-32b" and world > 1) or args.tp_virtual > 1:   # (--tp-virtual 8 --tp-xcd 1 also serves ONE sequence of Qwen3-4B / 8B: the eight TP ranks as the eight XCDs)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the single-model decode only, not the tensor-parallel runs")
         return tp_main(args, cfg, rank, world, dev)
     head_type = {"bf16": L.BF16, "q4": L.Q4, "nf4": L.NF4}[args.head]
     layer_type = {"q4": L.Q4, "bf16": L.BF16, "f8": L.F8E5M2, "ternary": L.T_SIGN, "1bit": L.BOOL1, "nf4": L.NF4}[args.layers]
@@ -209,6 +213,8 @@ def main():
     dev_ms = ctx.elapsed_ms(e0, e1)
     ms_per_step = dt * 1e3 / K
     value = world * K / dt
+    if args.dump_outputs and rank == 0:   # read back before anything below runs the model again
+        dump_outputs(args.dump_outputs, m, timed_positions)
 
     out = None
     if rank == 0:
@@ -349,6 +355,22 @@ def main():
         out["wall_s"] = round(time.perf_counter() - _T_START, 1)
         out["wall_laps_s"] = _LAPS
         emit(out)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, m, timed_positions):
+    """--dump-outputs: what a caller of the timed decode receives from it -- the bf16 logits of the last timed step widened to float32, and the greedy ids the
+    timed steps picked (the device keeps one per cache position: the last min(K, max_seq) of them, in step order), float64 so that every id is exact"""
+    import numpy as np
+    S = m.cfg["max_seq"]
+    arrays = {"logits": (m.logits().astype(np.uint32) << 16).view(np.float32),
+              "ids": m.tokens_out(S)[timed_positions[-S:]].astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _fill_kv_synthetic(hip, ctx_h, ptrs_bytes, seed=11):

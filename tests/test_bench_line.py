@@ -98,3 +98,26 @@ def test_compact_line_of_the_round_6_result():
     q = x["request_queue"]
     assert q["generated_tokens_per_s"] > 0 and q["prefill_batch"]["ms_per_prompt"] < 1.0
     assert d["side"]["config3_train_step"]["host_loop"].startswith("C++")
+
+
+def test_dump_outputs_writes_the_last_steps_logits_and_the_timed_ids(tmp_path):
+    """--dump-outputs: the last step's bf16 logits widened to float32, and the greedy ids of the timed positions in step order -- of the last max_seq of them when the
+    window wrapped round the cache (the device keeps one id per position)"""
+    import numpy as np
+    B = _bench()
+
+    class Model:   # the two read-backs dump_outputs uses, over an 8-position cache
+        cfg = {"max_seq": 8, "vocab": 5}
+
+        def logits(self):
+            return np.array([0x3F80, 0xBF80, 0x4000, 0x0000, 0x7F80], dtype=np.uint16)   # 1, -1, 2, 0, inf
+
+        def tokens_out(self, n):
+            return np.arange(100, 100 + n, dtype=np.int32)
+    B.dump_outputs(str(tmp_path / "a"), Model(), [5, 6, 7, 0, 1])
+    lg, ids = np.load(tmp_path / "a" / "logits.npy"), np.load(tmp_path / "a" / "ids.npy")
+    assert lg.dtype == np.float32 and lg.tolist() == [1.0, -1.0, 2.0, 0.0, float("inf")]
+    assert ids.dtype == np.float64 and ids.tolist() == [105, 106, 107, 100, 101]
+    B.dump_outputs(str(tmp_path / "b"), Model(), [(3 + i) % 8 for i in range(11)])
+    assert np.load(tmp_path / "b" / "ids.npy").tolist() == [106, 107, 100, 101, 102, 103, 104, 105]
+    assert sorted(os.listdir(tmp_path / "b")) == ["ids.npy", "logits.npy"]
