@@ -1355,9 +1355,14 @@ int kf_xengine_destroy(kf_xengine* e) {
     }
     return KF_OK;
 }
-int kfdbg_xengine_variant(kf_xengine* e, int nwv, int depth) {
-    if (!e || !e->h) return -1;
-    kf::xengine_set_variant(e->h, nwv, depth);
+int kfdbg_xengine_variant(kf_xengine* e, int nwv, int depth) { return (e && e->h) ? kf::xengine_set_variant(e->h, nwv, depth) : -1; }
+// the form the engines pick (kf::xengine_form, no HIP call) for a shape class (1 Qwen3-0.6B, 2 the 256-wide test shape, 3 1.7B, 4 4B, 5 8B, 6 the 8-on-1 test shape, 7 / 8 / 9
+// the TP ranks of 32B / 8B / 4B), a storage (kf::FMT_Q4P / FMT_Q1T / FMT_Q2T) and the hooks: out[5] = waves, ring depth, decoders per XCD, sequences per decoder, stamps;
+// -1: refused
+int kfdbg_xengine_form(int shape_class, int fmt, int n_seq, int n_layer, int stamps, int two_wpc, int* out) {
+    const kf::XForm* f = kf::xengine_form(shape_class, fmt, n_seq, n_layer, stamps != 0, two_wpc != 0);
+    if (!f || !out) return -1;
+    out[0] = f->nwv, out[1] = f->depth, out[2] = f->wpc, out[3] = f->nb, out[4] = f->dbg;
     return 0;
 }
 int kfdbg_xengine_stamps_enable(kf_xengine* e, int seq, int wg, int max_steps) { return (e && e->h) ? kf::xengine_debug_enable(e->h, seq, wg, max_steps) : -1; }

@@ -175,6 +175,16 @@ void engine_set_delays(EngineHost* E, const int* d6); /* tuning runs */
 
 // ---- XCD-confined decode engines: up to eight independent sequences per launch, one per XCD (kf_xengine.hip)
 struct XEngineHost;
+// one form an engine can launch (an xengine_kernel<XCfg<...>> instantiation, built from its XCfg by xe_form): what it serves, its shape, its LDS, its launcher
+struct XForm {
+    int shape_class, fmt;
+    int nwv, depth, wpc, nb;     /* waves per workgroup, ring depth, decoders per XCD, sequences per decoder */
+    bool dbg;                    /* the per-phase stamps */
+    size_t (*smem)(int n_layer); /* dynamic LDS of one workgroup at launch */
+    int (*go)(XEngineHost* E, hipStream_t st);
+};
+// THE choice of form, at create and at every launch (no HIP call): nullptr = refused (no form for this shape, storage and count, or none fits the LDS at this depth)
+const XForm* xengine_form(int shape_class, int fmt, int n_seq, int n_layer, bool stamps, bool two_wpc);
 size_t xengine_ws_bytes(const kf_engine_desc* d);
 int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why = nullptr, bool dry = false);
 int xengine_steps(XEngineHost* E, hipStream_t st, int32_t* d_state, uint16_t* x_out, int with_head, int n_steps);
@@ -186,7 +196,7 @@ int xengine_set_head(XEngineHost* E, const kf_weight* w, const uint16_t* norm_w,
 int xengine_error_word(XEngineHost* E, hipStream_t st, int* h_err);
 int xengine_reset(XEngineHost* E, hipStream_t st);
 void xengine_free(XEngineHost* E);
-void xengine_set_variant(XEngineHost* E, int nwv, int depth);             /* tuning runs: waves per workgroup x ring depth (instantiated pairs only) */
+int xengine_set_variant(XEngineHost* E, int nwv, int depth);              /* A/B hook: nwv -2 = two decoders per XCD for 9 .. 16 sequences (depth != 0); else -1 */
 int xengine_debug_enable(XEngineHost* E, int seq, int wg, int max_steps); /* per-phase stamps of one workgroup of one decoder (seq < 0: off) */
 int xengine_debug_read(XEngineHost* E, unsigned long long* h_out, int n_words);
 

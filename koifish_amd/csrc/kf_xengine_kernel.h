@@ -1591,21 +1591,23 @@ struct XEngineHost {
     XArgs args;
     int shape_class, fmt;
     int dim, q_dim, kv_dim, ffn, n_head, n_kv, hd;
-    size_t smem, loc_stride;
+    size_t loc_stride;
     void* ws;
     size_t ws_bytes;
-    int nwv, depth; /* the instantiation in use */
-    int deal_wl;    /* 0: the form's default (xengine_go) */
     size_t tp_bytes; /* TP: bytes of the receive + pick areas behind the exchange areas (reset with them) */
     int epoch;       /* the generation the next launch starts at (XArgs::epoch0) */
-    int batch;       /* sequences per decoder of the form in use (XCfg::NB): 1, 2 or 4 */
-    int variant_set; /* xengine_set_variant was called with a waves x depth pair (tuning runs) */
     int two_wpc;     /* n_seq 9 .. 16 through the round-5 form (two decoders per XCD, two workgroups per CU) instead of the batched one: A/B hook */
 };
 
 template <class C>
 static size_t xe_smem(int n_layer) {
     return XLay<C>::fixed_bytes + (((size_t)n_layer * sizeof(EngLayer) + 15) & ~(size_t)15);
+}
+// the dynamic LDS of one workgroup at launch: what create checks (xengine_form) and what xengine_go launches with
+template <class C>
+static size_t xe_launch_smem(int n_layer) {
+    const size_t smem = xe_smem<C>(n_layer);
+    return C::WPC == 2 && smem < 54 * 1024 ? 54 * 1024 : smem; /* two workgroups per CU, never three: a third would be a workgroup of some decoder queued behind its own peers */
 }
 template <class C>
 static int xengine_go(XEngineHost* E, hipStream_t st) {
@@ -1616,12 +1618,16 @@ static int xengine_go(XEngineHost* E, hipStream_t st) {
         if (hipFuncSetAttribute((const void*)xengine_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return KF_HIP_CHECK;
         if (dev >= 0 && dev < 64) ready |= 1ull << dev;
     }
-    size_t smem = xe_smem<C>(E->args.n_layer);
-    if (C::WPC == 2 && smem < 54 * 1024) smem = 54 * 1024; /* two workgroups per CU, never three: a third would be a workgroup of some decoder queued behind its own peers */
+    const size_t smem = xe_launch_smem<C>(E->args.n_layer);
     if (smem * C::WPC > 160 * 1024) return KF_UNSUPPORTED_DATATYPE;
-    E->args.deal_wl = E->deal_wl > 0 ? E->deal_wl : (C::WPC > 1 ? 14 : (C::NCW == 7 ? 11 : 16)); /* xe_deal: the share of the compute wave beside the poller (two decoders per XCD) */
+    E->args.deal_wl = C::WPC > 1 ? 14 : (C::NCW == 7 ? 11 : 16); /* xe_deal: the share of the compute wave beside the poller (two decoders per XCD) */
     hipLaunchKernelGGL((xengine_kernel<C>), dim3(XE_GRID * C::WPC), dim3(C::NWV * 64), smem, st, E->args);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+// the table entry of the form C (kf_kernels.h XForm) for the engines of shape class sc
+template <class C>
+constexpr XForm xe_form(int sc) {
+    return XForm{sc, C::FMT, C::NWV, C::DEPTH, C::WPC, C::NB, C::DBG, xe_launch_smem<C>, xengine_go<C>};
 }
 
 }  // namespace kf

@@ -757,8 +757,9 @@ class XcdReplicas:
         return self._d2h(self.host.kfh_xr_kcache(self.h, int(seq)), n).reshape(shp), self._d2h(self.host.kfh_xr_vcache(self.h, int(seq)), n).reshape(shp)
 
     def variant(self, nwv, depth):
-        """tuning runs: waves per workgroup x ring depth of the next launches (instantiated pairs only)"""
-        self.host.kfh_xr_variant(self.h, int(nwv), int(depth))
+        """A/B hook of the next launches: variant(-2, 1) runs 9 .. 16 sequences through the round-5 form (two decoders per XCD), variant(-2, 0) back; other codes are refused"""
+        if self.host.kfh_xr_variant(self.h, int(nwv), int(depth)) != 0:
+            raise ValueError("xengine variant (%d, %d): only (-2, 0 | 1) is served" % (nwv, depth))
 
     def stamps(self, seq, wg, steps, n_layer):
         """enable (steps > 0) / read the per-phase wall-clock stamps [step][layer][64] of one workgroup of one decoder (diagnostic instantiation)"""
@@ -840,10 +841,6 @@ class XcdTP:
         n = len(self.nt.ranks) * c["n_layer"] * c["max_seq"] * kvd
         shp = (len(self.nt.ranks), c["n_layer"], c["max_seq"], kvd)
         return self._d2h(self.host.kfh_xtp_kcache(self.h), n).reshape(shp), self._d2h(self.host.kfh_xtp_vcache(self.h), n).reshape(shp)
-
-    def variant(self, nwv, depth):
-        """tuning builds (-DXE_TP_VARIANTS): another instantiation for the next launches"""
-        self.host.kfh_xtp_variant(self.h, int(nwv), int(depth))
 
     def stamps(self, rank, wg, steps, n_layer):
         """enable (steps > 0) / read the per-phase wall-clock stamps [step][layer][64] of one workgroup of one rank (diagnostic instantiation)"""
