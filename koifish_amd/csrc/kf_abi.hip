@@ -1365,6 +1365,14 @@ int kfdbg_xengine_form(int shape_class, int fmt, int n_seq, int n_layer, int sta
     out[0] = f->nwv, out[1] = f->depth, out[2] = f->wpc, out[3] = f->nb, out[4] = f->dbg;
     return 0;
 }
+// the form the persistent engine picks (kf::engine_form, no HIP call) for a shape class (1 Qwen3-0.6B, 2 the 256-wide test shape, 3 1.7B), a storage (kf::FMT_Q4P /
+// FMT_Q1T / FMT_Q2T), an order and the stamps: out[5] = shape class, storage, canonical, stamps, launch LDS in bytes; -1: refused
+int kfdbg_engine_form(int shape_class, int fmt, int canon, int stamps, int n_layer, int* out) {
+    const kf::EngForm* f = kf::engine_form(shape_class, fmt, canon != 0, stamps != 0, n_layer);
+    if (!f || !out) return -1;
+    out[0] = f->shape_class, out[1] = f->fmt, out[2] = f->canon, out[3] = f->dbg, out[4] = (int)f->smem(n_layer);
+    return 0;
+}
 int kfdbg_xengine_stamps_enable(kf_xengine* e, int seq, int wg, int max_steps) { return (e && e->h) ? kf::xengine_debug_enable(e->h, seq, wg, max_steps) : -1; }
 int kfdbg_xengine_stamps(kf_xengine* e, unsigned long long* h_out, int n_words) { return (e && e->h) ? kf::xengine_debug_read(e->h, h_out, n_words) : -1; }
 // ---- diagnostics (NOT part of the ABI header; tests and scratch/ only)

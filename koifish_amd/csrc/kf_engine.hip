@@ -1271,11 +1271,9 @@ __global__ void __launch_bounds__(C::NWV * 64) engine_kernel(const EngArgs a) {
 // ------------------------------------------------------------------------------------------------ host side
 struct EngineHost {
     EngArgs args;
-    EngPlan plans[4];
-    int fmt, GQ, hd, nwv, shape_class, xmap;
-    int canon; /* 1: mat-vec phases in the canonical order (engine_set_canonical) */
+    const EngForm* form; /* what engine_step launches: engine_form of the model's shape, storage and depth, the order (form->canon) and the stamps */
+    int GQ, hd;
     int dim, q_dim, kv_dim, ffn, n_kv, n_head;
-    size_t smem;
     int n_cu;
     void* xmem;     /* the hand-off vectors every CU sweeps: device memory that is cached nowhere (hipDeviceMallocUncached), owned by the engine */
     size_t xbytes;
@@ -1286,54 +1284,123 @@ struct EngineHost {
     int delay_tab[KF_ATTN_MAX_SPLITS + 1][6];
     unsigned char tuned[KF_ATTN_MAX_SPLITS + 1];
 };
+static_assert(sizeof(EngLayer) == 224, "device table stride");
 
-// the instantiated model shapes: {GQA group, head_dim, dim, q_dim, ffn}
-static int engine_shape_class(int GQ, int hd, int dim, int q_dim, int ffn) { /* kv_dim = q_dim / GQ */
-    if (GQ == 2 && hd == 128 && dim == 1024 && q_dim == 2048 && ffn == 3072) return 1; /* Qwen3-0.6B (BASELINE config 2) */
-    if (GQ == 2 && hd == 64 && dim == 256 && q_dim == 256 && ffn == 512) return 2;     /* the small parity-test shape */
-    if (GQ == 2 && hd == 128 && dim == 2048 && q_dim == 2048 && ffn == 6144) return 3;  /* Qwen3-1.7B: the 0.6B head geometry on a 2048-wide stream (4-bit register-table storage only) */
-    return 0;
+// the dynamic LDS of a launch: engine_kernel's fixed buffers (the attention merge sized for 64 elements per workgroup, the most ME can be), the 1-bit / 2-bit selector
+// table, the layer table and the layers' hot bits
+template <class C>
+static size_t eng_smem(int n_layer) {
+    constexpr int maxK = C::DIM > C::QD ? (C::DIM > C::FFN ? C::DIM : C::FFN) : (C::QD > C::FFN ? C::QD : C::FFN);
+    constexpr size_t xs_bytes = ((size_t)maxK * 4 + 15) & ~(size_t)15;
+    size_t smem = (((size_t)n_layer * sizeof(EngLayer) + 15) & ~(size_t)15) + 2 * xs_bytes + 2 * (((size_t)C::DIM * 2 + 15) & ~(size_t)15);
+    smem += sizeof(uint16_t) * ((size_t)2 * C::GQ * C::HD + 3 * C::HD) + sizeof(double) * ((size_t)C::NWV * C::GQ * (C::HD + 2) + 64 * KF_ATTN_MAX_SPLITS + 64) + 4 * 16 + 4 * 64 + 32;
+    smem += (C::FMT == FMT_Q1T ? 4096 : (C::FMT == FMT_Q2T ? 2048 : 0)) + (size_t)n_layer * 4 + 64;
+    return (smem + 15) & ~(size_t)15;
 }
-static_assert(sizeof(EngPlan) == 80 && sizeof(EngLayer) == 224, "device table strides");
-static int eng_epb(int fmt) { return fmt == FMT_BF16 ? 8 : (fmt == FMT_F8 ? 16 : (fmt == FMT_Q4 || fmt == FMT_Q4P ? 32 : (32 /* 2-bit / 1-bit: the engine's lanes take a 32-weight piece of a block each (eng_vepb) */))); }
-
-// geometry of one phase; returns false when the shape is outside what the engine serves
-static bool eng_plan(EngPlan& P, int fmt, int K, int njobs, const kf_weight* const* w, bool paired, int n_wg, bool& q4p_ok) {
-    const int epb = eng_epb(fmt);
-    if (K % epb != 0 || K % 8 != 0 || K > ENG_MAXLD * 256) return false;
-    memset(&P, 0, sizeof(P));
-    P.K = K, P.nBlk = K / epb;
-    long rows = 0;
-    for (int j = 0; j < njobs; j++)
-        if (!(paired && j == 1)) rows += w[j]->ne0;
-    P.lpr_log2 = gemv_lpr_log2(P.nBlk, rows);
-    const int LPR = 1 << P.lpr_log2, RPS = 64 / LPR;
-    P.iters = (P.nBlk + LPR - 1) / LPR;
-    P.njobs = paired ? 1 : njobs;
-    int slots = 0;
-    for (int j = 0; j < njobs; j++) {
-        const kf_weight* wj = w[j];
-        if (gemv_fmt_of(wj) != (fmt == FMT_Q4P ? FMT_Q4 : fmt) || wj->ne1 != K || wj->qzeros || wj->qscales) return false;
-        if (((uintptr_t)wj->data & 15) != 0) return false;
-        if (fmt >= FMT_Q4) {
-            if (!wj->gama || wj->lGroup <= 0 || (wj->lGroup % epb) != 0 || ((long)wj->ne0 * wj->ne1) % wj->lGroup != 0) return false;
-            const int bpg = wj->lGroup / epb;
-            if (bpg < 1 || (bpg & (bpg - 1)) != 0) return false;
-            P.gshift = __builtin_ctz(bpg);
-            if (!(wj->lGroup == 128 && (K % 128) == 0 && P.lpr_log2 >= 2)) q4p_ok = false;
-        }
-        P.M[j] = wj->ne0, P.qBias[j] = wj->qBias;
-        if (paired && j == 1) {
-            if (wj->ne0 != w[0]->ne0) return false;
-            continue;
-        }
-        P.slot0[j] = slots;
-        slots += (wj->ne0 + RPS - 1) / RPS;
+template <class C>
+static int engine_go(EngineHost* E, hipStream_t st) {
+    static bool attr = false; /* the LDS ceiling of this instantiation, set at its first launch */
+    if (!attr) {
+        if (hipFuncSetAttribute((const void*)engine_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return KF_HIP_CHECK;
+        attr = true;
     }
-    for (int j = P.njobs; j < 3; j++) P.slot0[j] = 0x7fffffff;
-    P.total_slots = slots;
-    P.spg = (slots + n_wg - 1) / n_wg;
+    hipLaunchKernelGGL((engine_kernel<C>), dim3(C::NWG), dim3(C::NWV * 64), eng_smem<C>(E->args.n_layer), st, E->args);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+// the table entry of the form C (kf_kernels.h EngForm) for shape class sc
+template <class C>
+constexpr EngForm eng_form(int sc) {
+    using SH = typename C::SH;
+    return EngForm{sc, C::FMT, C::CANON, C::DBG, {SH::P1::plan(), SH::P4::plan(), SH::P5::plan(), SH::P6::plan()}, eng_smem<C>, engine_go<C>};
+}
+
+template <int FMT, bool DBG, bool CANON>
+using EC1 = EngCfg<FMT, 2, 128, ENG_NWV, 1024, 2048, 1024, 3072, ENG_NWG, true, DBG, CANON>; /* Qwen3-0.6B (BASELINE config 2): 8 kv-heads on 8 XCDs */
+template <int FMT, bool DBG, bool CANON>
+using EC2 = EngCfg<FMT, 2, 64, ENG_NWV, 256, 256, 128, 512, ENG_NWG, false, DBG, CANON>; /* the small parity-test shape */
+template <int FMT, bool DBG, bool CANON>
+using EC3 = EngCfg<FMT, 2, 128, ENG_NWV, 2048, 2048, 1024, 6144, ENG_NWG, true, DBG, CANON>; /* Qwen3-1.7B: the 0.6B head geometry on a 2048-wide stream; gate | up and
+                                                                                                 down_proj hold 8 and 6 blocks per lane, part of them dequantised behind the
+                                                                                                 hand-off (MvPhase::AH) */
+
+// ---- the table of shapes: one row per shape class, read off a form of the shape
+struct EngShapeRow {
+    int sc, hd, dim, q_dim, kv_dim, ffn;
+};
+template <class C>
+constexpr EngShapeRow eng_shape(int sc) {
+    return EngShapeRow{sc, C::HD, C::DIM, C::QD, C::KVD, C::FFN};
+}
+static const EngShapeRow eng_shapes[] = {eng_shape<EC1<FMT_Q4P, false, true>>(1), eng_shape<EC2<FMT_Q4P, false, true>>(2), eng_shape<EC3<FMT_Q4P, false, true>>(3)};
+static const EngShapeRow* eng_shape_of(const kf_engine_desc* d) { /* nullptr: not instantiated */
+    for (const EngShapeRow& s : eng_shapes)
+        if (d->head_dim == s.hd && d->dim == s.dim && d->n_head * d->head_dim == s.q_dim && d->n_kv * d->head_dim == s.kv_dim && d->ffn == s.ffn) return &s;
+    return nullptr;
+}
+
+// ---- the table of forms: every instantiation the engine launches.  Both orders of every shape and storage; the stamped (diagnostic) twins exist for the benchmark's
+// storage and shape only.  The 2048-wide shape is instantiated for the register-table 4-bit storage only.
+#define ENG_ORDERS(EC, FMT, DBG, sc) eng_form<EC<FMT, DBG, true>>(sc), eng_form<EC<FMT, DBG, false>>(sc)
+static const EngForm eng_forms[] = {ENG_ORDERS(EC1, FMT_Q4P, false, 1), ENG_ORDERS(EC1, FMT_Q4P, true, 1), ENG_ORDERS(EC1, FMT_Q1T, false, 1), ENG_ORDERS(EC1, FMT_Q2T, false, 1),
+                                    ENG_ORDERS(EC2, FMT_Q4P, false, 2), ENG_ORDERS(EC2, FMT_Q1T, false, 2), ENG_ORDERS(EC2, FMT_Q2T, false, 2),
+                                    ENG_ORDERS(EC3, FMT_Q4P, false, 3)};
+#undef ENG_ORDERS
+// the stamps where the shape and storage have a stamped twin, else the unstamped form; nullptr when there is no such form or its LDS does not fit at this depth
+const EngForm* engine_form(int sc, int fmt, bool canon, bool stamps, int n_layer) {
+    auto find = [&](bool dbg) -> const EngForm* {
+        for (const EngForm& f : eng_forms)
+            if (f.shape_class == sc && f.fmt == fmt && f.canon == canon && f.dbg == dbg) return &f;
+        return nullptr;
+    };
+    const EngForm* f = stamps ? find(true) : nullptr;
+    if (!f) f = find(false);
+    return f && f->smem(n_layer) <= 160 * 1024 ? f : nullptr;
+}
+// the invariant behind the engine's summation order: every phase's compile-time plan has the matrices of the model and the lanes per row the mat-vec launcher picks
+// for them (the engine walks every storage in 32-weight pieces, eng_vepb)
+static bool eng_plans_match(const EngForm* f, const kf_engine_desc* d) {
+    const int q_dim = d->n_head * d->head_dim, kv_dim = d->n_kv * d->head_dim;
+    const int K[4] = {d->dim, q_dim, d->dim, d->ffn}, M[4][3] = {{q_dim, kv_dim, kv_dim}, {d->dim, 0, 0}, {d->ffn, d->ffn, 0}, {d->dim, 0, 0}};
+    const long rows[4] = {(long)q_dim + 2 * kv_dim, d->dim, d->ffn, d->dim}; /* gate | up: the launcher's rows of one of the pair */
+    for (int i = 0; i < 4; i++) {
+        const CPlan& p = f->plan[i];
+        if (p.K != K[i] || p.nBlk != K[i] / 32 || p.lpr_log2 != gemv_lpr_log2(p.nBlk, rows[i])) return false;
+        for (int j = 0; j < 3; j++)
+            if (p.M[j] != M[i][j]) return false;
+    }
     return true;
+}
+
+// one model's (one TP rank's) layer table out of its descriptor, for both engine families; qbias: the seven matrices' zero points of layer 0 (every layer, every rank: the
+// same).  *fmt_io: the storage every matrix of the model carries (0 on entry = not known yet): FMT_Q4P, FMT_Q1T or FMT_Q2T; NULL: 4-bit only
+int eng_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool qbias_set, bool& q4p_ok, int* fmt_io, bool allow_hot) {
+    const int hd = d->head_dim, q_dim = d->n_head * hd, kv_dim = d->n_kv * hd;
+    const int Ks[7] = {d->dim, d->dim, d->dim, q_dim, d->dim, d->dim, d->ffn}, Ms[7] = {q_dim, kv_dim, kv_dim, d->dim, d->ffn, d->ffn, d->dim};
+    for (int l = 0; l < d->n_layer; l++) {
+        const kf_engine_layer& Ly = d->layers[l];
+        if (Ly.hot_ffn && !allow_hot) return KF_UNSUPPORTED_DATATYPE;
+        if (!Ly.norm_in || !Ly.norm_post || !Ly.kcache || !Ly.vcache || (((uintptr_t)Ly.kcache | (uintptr_t)Ly.vcache) & 15) != 0) return KF_UNSUPPORTED_DATATYPE;
+        for (int j = 0; j < 7; j++) {
+            const kf_weight& w = Ly.w[j];
+            const int wf = gemv_fmt_of(&w), ef = wf == FMT_Q4 ? FMT_Q4P : (wf == FMT_Q1 ? FMT_Q1T : (wf == FMT_Q2 ? FMT_Q2T : -1));
+            if (ef < 0 || (!fmt_io && ef != FMT_Q4P) || (fmt_io && *fmt_io != 0 && *fmt_io != ef)) return KF_UNSUPPORTED_DATATYPE;
+            if (fmt_io) *fmt_io = ef;
+            if (w.ne0 != Ms[j] || w.ne1 != Ks[j] || w.qzeros || w.qscales || !w.gama || w.lGroup != 128 || (Ks[j] % 128) != 0 || ((uintptr_t)w.data & 15) != 0)
+                return KF_UNSUPPORTED_DATATYPE;
+            const long rows = j < 3 ? (long)q_dim + 2 * kv_dim : (j == 4 || j == 5 ? (long)d->ffn : (long)Ms[j]);
+            if (gemv_lpr_log2(Ks[j] / 32, rows) < 2) q4p_ok = false; /* the register-table form needs a group's four blocks in one aligned lane quad (1-bit: the four dwords of a block in one) */
+            tab[l].m[j].w = (g_u32x4)(uintptr_t)w.data;
+            tab[l].m[j].zero = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1);
+            tab[l].m[j].step = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1 + (size_t)w.ne0 * w.ne1 / w.lGroup);
+            if (l == 0 && !qbias_set) qbias[j] = (float)w.qBias;
+            else if (qbias[j] != (float)w.qBias) return KF_UNSUPPORTED_DATATYPE;
+        }
+        tab[l].norm_in = (g_u16)(uintptr_t)Ly.norm_in, tab[l].norm_post = (g_u16)(uintptr_t)Ly.norm_post;
+        tab[l].norm_q = (g_u16)(uintptr_t)Ly.q_norm, tab[l].norm_k = (g_u16)(uintptr_t)Ly.k_norm;
+        tab[l].kcache = (g_u16w)(uintptr_t)Ly.kcache, tab[l].vcache = (g_u16w)(uintptr_t)Ly.vcache;
+        tab[l].hot = (g_i32)(uintptr_t)Ly.hot_ffn; /* sparse forward: CS_Picker's hot[ffn] on the device (kf_abi.h kf_engine_layer::hot_ffn); NULL: dense */
+    }
+    return KF_OK;
 }
 
 // caller's workspace (cached device memory): [ws words 256 B] [EngLayer table] [XCD-local area: tickets | lqkv | lpart] [room for the exchange vectors, used
@@ -1376,102 +1443,51 @@ int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t
     const int hd = d->head_dim;
     *why = "head_dim must be 64 or 128 and n_head a multiple of n_kv";
     if ((hd != 64 && hd != 128) || d->n_kv <= 0 || d->n_head % d->n_kv != 0) return KF_UNSUPPORTED_DATATYPE;
-    const int GQ = d->n_head / d->n_kv;
-    const int shape_class = engine_shape_class(GQ, hd, d->dim, d->n_head * hd, d->ffn);
+    const EngShapeRow* sh = eng_shape_of(d);
     *why = "model shape not instantiated: the engine's phase plans are compile-time types; built for Qwen3-0.6B (dim 1024, 16/8 heads of 128, ffn 3072), Qwen3-1.7B (dim 2048, same heads, ffn 6144; 4-bit layers) and the 256-wide test shape (dim 256, 4/2 heads of 64, ffn 512)";
-    if (!shape_class) return KF_UNSUPPORTED_DATATYPE; /* not one of the instantiated model shapes: the per-layer launches remain */
+    if (!sh) return KF_UNSUPPORTED_DATATYPE; /* not one of the instantiated model shapes: the per-layer launches remain */
     int dev = 0, n_cu = 0;
     *why = "HIP failure";
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) return KF_HIP_CHECK;
     *why = "the device has fewer than 256 compute units: one resident workgroup per CU is the engine's premise";
     if (n_cu < ENG_NWG) return KF_UNSUPPORTED_DATATYPE; /* one resident workgroup per CU is the engine's premise */
-    n_cu = ENG_NWG;
-    EngineHost* E = new EngineHost();
-    memset(E, 0, sizeof(*E));
-    EngArgs& a = E->args;
-    a.n_layer = d->n_layer;
-    E->dim = d->dim, E->n_head = d->n_head, E->n_kv = d->n_kv, E->q_dim = d->n_head * hd, E->kv_dim = d->n_kv * hd, E->ffn = d->ffn;
-    a.kv_stride = d->kv_stride;
-    a.max_seq = d->max_seq;
-    a.eps = d->rms_eps, a.qk_eps = d->qk_eps, a.rope_table = d->rope_table;
     *why = "rope_table missing, kv_stride not a multiple of 8, or max_seq < 1";
-    if (!a.rope_table || (a.kv_stride % 8) != 0 || a.max_seq < 1) {
-        delete E;
-        return KF_INVALID_ARGS;
-    }
-    // phases: every layer must have the same shapes and storage
-    const kf_engine_layer& L0 = d->layers[0];
-    int fmt = gemv_fmt_of(&L0.w[0]);
-    *why = "layer storage not served: the engine is instantiated for 4-bit (RTN), 2-bit and 1-bit PackedQ layers in groups of 128; other storages keep the per-layer launches";
-    if (fmt != FMT_Q4 && fmt != FMT_Q1 && fmt != FMT_Q2) { /* the engine is instantiated for the 4-bit PackedQ storage (BASELINE config 2); other storages keep the per-layer launches */
-        delete E;
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    *why = "a layer's matrices differ from layer 0's in shape, storage, grouping or alignment, or a norm weight / cache pointer is missing";
-    bool q4p_ok = fmt == FMT_Q4;
+    if (!d->rope_table || (d->kv_stride % 8) != 0 || d->max_seq < 1) return KF_INVALID_ARGS;
+    *why = "layer storage not served: the engine is instantiated for 4-bit (RTN), 2-bit and 1-bit PackedQ layers in groups of 128 with 16-byte aligned blocks, every matrix the "
+           "same storage, every layer the same shapes and zero points, norm weights and 16-byte aligned caches present; other storages keep the per-layer launches";
     std::vector<EngLayer> tab(d->n_layer);
-    for (int l = 0; l < d->n_layer; l++) {
-        const kf_engine_layer& L = d->layers[l];
-        const kf_weight* k1[3] = {&L.w[0], &L.w[1], &L.w[2]};
-        const kf_weight* k4[1] = {&L.w[3]};
-        const kf_weight* k5[2] = {&L.w[4], &L.w[5]};
-        const kf_weight* k6[1] = {&L.w[6]};
-        EngPlan p1, p4, p5, p6;
-        EngPlan* const pl = E->plans;
-        bool ok = eng_plan(p1, fmt, E->dim, 3, k1, false, n_cu, q4p_ok) && eng_plan(p4, fmt, E->q_dim, 1, k4, false, n_cu, q4p_ok) &&
-                  eng_plan(p5, fmt, E->dim, 2, k5, true, n_cu, q4p_ok) && eng_plan(p6, fmt, E->ffn, 1, k6, false, n_cu, q4p_ok);
-        ok = ok && L.w[0].ne0 == E->q_dim && L.w[1].ne0 == E->kv_dim && L.w[2].ne0 == E->kv_dim && L.w[3].ne0 == E->dim && L.w[4].ne0 == E->ffn && L.w[6].ne0 == E->dim;
-        ok = ok && L.norm_in && L.norm_post && L.kcache && L.vcache && (((uintptr_t)L.kcache | (uintptr_t)L.vcache) & 15) == 0;
-        if (l == 0) pl[0] = p1, pl[1] = p4, pl[2] = p5, pl[3] = p6;
-        if (ok && l > 0) ok = !memcmp(&p1, &pl[0], sizeof(p1)) && !memcmp(&p4, &pl[1], sizeof(p4)) && !memcmp(&p5, &pl[2], sizeof(p5)) && !memcmp(&p6, &pl[3], sizeof(p6));
-        if (!ok) {
-            delete E;
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        for (int j = 0; j < 7; j++) {
-            const kf_weight& w = L.w[j];
-            tab[l].m[j].w = (g_u32x4)(uintptr_t)w.data;
-            tab[l].m[j].zero = tab[l].m[j].step = nullptr;
-            if (fmt >= FMT_Q4) {
-                tab[l].m[j].zero = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1);
-                tab[l].m[j].step = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1 + (size_t)w.ne0 * w.ne1 / w.lGroup);
-            }
-        }
-        if (l == 0)
-            for (int j = 0; j < 7; j++) a.qbias[j] = (float)L.w[j].qBias;
-        else
-            for (int j = 0; j < 7; j++)
-                if (a.qbias[j] != (float)L.w[j].qBias) {
-                    delete E;
-                    return KF_UNSUPPORTED_DATATYPE;
-                }
-        tab[l].norm_in = (g_u16)(uintptr_t)L.norm_in, tab[l].norm_post = (g_u16)(uintptr_t)L.norm_post;
-        tab[l].norm_q = (g_u16)(uintptr_t)L.q_norm, tab[l].norm_k = (g_u16)(uintptr_t)L.k_norm;
-        tab[l].kcache = (g_u16w)(uintptr_t)L.kcache, tab[l].vcache = (g_u16w)(uintptr_t)L.vcache;
-        tab[l].hot = (g_i32)(uintptr_t)L.hot_ffn;
-    }
-    if (fmt == FMT_Q4 && q4p_ok) fmt = FMT_Q4P;
-    if (fmt == FMT_Q1) fmt = FMT_Q1T; /* the LDS selector-table forms (same bits as the per-bit select forms) */
-    if (fmt == FMT_Q2) fmt = FMT_Q2T;
-    if (shape_class == 3 && fmt != FMT_Q4P) { /* the 2048-wide shape is instantiated for the register-table 4-bit storage only */
-        delete E;
-        *why = "the Qwen3-1.7B shape is instantiated for 4-bit (RTN, groups of 128) layers only";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
+    float qbias[7] = {0};
+    bool q4p_ok = true;
+    int fmt = 0;
+    if (eng_fill_layers(d, tab.data(), qbias, false, q4p_ok, &fmt, true) != KF_OK || !q4p_ok) return KF_UNSUPPORTED_DATATYPE;
+    *why = "the Qwen3-1.7B shape is instantiated for 4-bit (RTN, groups of 128) layers only";
+    if (!engine_form(sh->sc, fmt, true, false, 1)) return KF_UNSUPPORTED_DATATYPE;
+    *why = "the layer table and the staging buffers exceed 160 KB of LDS (too many layers)";
+    const EngForm* f = engine_form(sh->sc, fmt, true, false, d->n_layer);
+    if (!f) return KF_UNSUPPORTED_DATATYPE;
+    *why = "the engine's compile-time phase plans are not the mat-vec launcher's for these matrices (its summation order would differ)";
+    if (!eng_plans_match(f, d)) return KF_UNSUPPORTED_DATATYPE;
     if (dry) {
-        delete E;
         *why = "";
         return KF_OK;
     }
-    E->fmt = fmt, E->GQ = GQ, E->hd = hd, E->n_cu = n_cu, E->nwv = ENG_NWV, E->shape_class = shape_class;
-    E->canon = 1;
-    E->xmap = shape_class == 1 || shape_class == 3 ? 1 : 0; /* 8 kv-heads on 8 XCDs (informational: the mapping is a template parameter of the instantiation) */
+    EngineHost* E = new EngineHost();
+    memset(E, 0, sizeof(*E));
+    EngArgs& a = E->args;
+    E->form = f;
+    E->GQ = d->n_head / d->n_kv, E->hd = hd, E->n_cu = ENG_NWG;
+    E->dim = d->dim, E->n_head = d->n_head, E->n_kv = d->n_kv, E->q_dim = d->n_head * hd, E->kv_dim = d->n_kv * hd, E->ffn = d->ffn;
+    a.n_layer = d->n_layer;
+    a.kv_stride = d->kv_stride;
+    a.max_seq = d->max_seq;
+    a.eps = d->rms_eps, a.qk_eps = d->qk_eps, a.rope_table = d->rope_table;
+    for (int j = 0; j < 7; j++) a.qbias[j] = qbias[j];
     // workspace carve
     char* p = reinterpret_cast<char*>(ws);
     E->ws = ws, E->ws_bytes = ws_bytes;
     a.ws = reinterpret_cast<int*>(p), p += 256;
     a.layers = reinterpret_cast<const EngLayer*>(p), p += ((size_t)d->n_layer * sizeof(EngLayer) + 255) & ~(size_t)255;
-    a.loc = p, p += (eng_loc_bytes(GQ, hd) + 255) & ~(size_t)255;
+    a.loc = p, p += (eng_loc_bytes(E->GQ, hd) + 255) & ~(size_t)255;
     {
         /* s_sleep units (one trip of the wait loop ~ 40 ns) behind the own publish: x, q|k|v, slice partials, ao, xB, act.  Tuned on the 0.6B shape at 2 k keys
            (scratch/eng_ab.py): after the drains were removed 12,8,12,12,12,12 0.455 ms/step, 16,8,12,16,16,16 0.452, 20,12,16,20,20,20 0.464, 24,12,16,24,24,24 0.474 */
@@ -1495,25 +1511,13 @@ int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t
         *why = "HIP failure while initialising the workspace";
         return KF_HIP_CHECK;
     }
-    // LDS
-    int maxK = E->dim > E->q_dim ? E->dim : E->q_dim;
-    if (E->ffn > maxK) maxK = E->ffn;
-    const size_t xs_bytes = ((size_t)maxK * 4 + 15) & ~(size_t)15;
-    size_t smem = (((size_t)d->n_layer * sizeof(EngLayer) + 15) & ~(size_t)15) + 2 * xs_bytes + 2 * (((size_t)E->dim * 2 + 15) & ~(size_t)15);
-    smem += sizeof(uint16_t) * ((size_t)2 * GQ * hd + 3 * hd) + sizeof(double) * ((size_t)ENG_NWV * GQ * (hd + 2) + 64 * KF_ATTN_MAX_SPLITS + 64) + 4 * 16 + 4 * 64 + 32;
-    smem += (fmt == FMT_Q1T ? 4096 : (fmt == FMT_Q2T ? 2048 : 0)) + (size_t)d->n_layer * 4 + 64; /* the 1-bit / 2-bit selector table; the layers' hot bits */
-    smem = (smem + 15) & ~(size_t)15;
-    if (smem > 160 * 1024) {
-        engine_release(E);
-        *why = "the layer table and the staging buffers exceed 160 KB of LDS (too many layers)";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    E->smem = smem;
     *out = E;
     *why = "";
     return KF_OK;
 }
 void engine_free(EngineHost* E) { engine_release(E); }
+// the form for another order or the stamps: the model's shape, storage and depth, which create found a form for (every twin has the same plans and LDS)
+static void engine_repick(EngineHost* E, bool canon) { E->form = engine_form(E->form->shape_class, E->form->fmt, canon, E->args.dbg != nullptr, E->args.n_layer); }
 // diagnostic runs: per-phase wall-clock stamps of one workgroup (the DBG instantiation of the kernel)
 int engine_debug_enable(EngineHost* E, int wg) {
     EngArgs& a = E->args;
@@ -1525,6 +1529,7 @@ int engine_debug_enable(EngineHost* E, int wg) {
     }
     (void)hipMemset(a.dbg, 0, (size_t)a.n_layer * 2 * 16 * 8);
     a.dbg_wg = wg;
+    engine_repick(E, E->form->canon);
     return KF_OK;
 }
 void engine_set_delays(EngineHost* E, const int* d6) { /* every slice count */
@@ -1537,58 +1542,6 @@ int engine_debug_read(EngineHost* E, unsigned long long* h_out, int n_words) {
     const int n = n_words < have ? n_words : have;
     if (hipMemcpy(h_out, E->args.dbg, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return n;
-}
-
-template <class C>
-static bool engine_plans_match(const EngineHost* E) {
-    using SH = typename C::SH;
-    const CPlan c[4] = {SH::P1::plan(), SH::P4::plan(), SH::P5::plan(), SH::P6::plan()};
-    for (int i = 0; i < 4; i++) {
-        const EngPlan& r = E->plans[i];
-        if (r.K != c[i].K || r.nBlk != c[i].nBlk || r.lpr_log2 != c[i].lpr_log2 || r.iters != c[i].iters || r.total_slots != c[i].total || r.spg != c[i].spg ||
-            r.njobs != c[i].njobs)
-            return false;
-        for (int j = 0; j < r.njobs; j++)
-            if (r.slot0[j] != c[i].slot0[j] || r.M[j] != c[i].M[j]) return false;
-    }
-    return true;
-}
-template <class C>
-static int engine_go(EngineHost* E, hipStream_t st) {
-    static int ready = 0; /* 1 ok, -1 the compile-time geometry is not the mat-vec launcher's */
-    if (!ready) {
-        if (!engine_plans_match<C>(E))
-            ready = -1;
-        else if (hipFuncSetAttribute((const void*)engine_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return KF_HIP_CHECK;
-        else
-            ready = 1;
-    }
-    if (ready < 0) return 1;
-    hipLaunchKernelGGL((engine_kernel<C>), dim3(C::NWG), dim3(C::NWV * 64), E->smem, st, E->args);
-    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
-}
-template <int FMT>
-static int engine_go_fmt(EngineHost* E, hipStream_t st) {
-    switch (E->shape_class) {
-        case 1: /* 8 kv-heads on 8 XCDs: the attention chain of a kv-head stays inside one XCD */
-            if constexpr (FMT == FMT_Q4P) { /* the diagnostic (stamped) instantiations exist for the benchmark's storage only */
-                if (E->args.dbg && E->canon) return engine_go<EngCfg<FMT_Q4P, 2, 128, ENG_NWV, 1024, 2048, 1024, 3072, ENG_NWG, true, true, true>>(E, st);
-                if (E->args.dbg) return engine_go<EngCfg<FMT_Q4P, 2, 128, ENG_NWV, 1024, 2048, 1024, 3072, ENG_NWG, true, true, false>>(E, st);
-            }
-            if (!E->canon) return engine_go<EngCfg<FMT, 2, 128, ENG_NWV, 1024, 2048, 1024, 3072, ENG_NWG, true, false, false>>(E, st);
-            return engine_go<EngCfg<FMT, 2, 128, ENG_NWV, 1024, 2048, 1024, 3072, ENG_NWG, true, false, true>>(E, st);
-        case 2:
-            if (!E->canon) return engine_go<EngCfg<FMT, 2, 64, ENG_NWV, 256, 256, 128, 512, ENG_NWG, false, false, false>>(E, st);
-            return engine_go<EngCfg<FMT, 2, 64, ENG_NWV, 256, 256, 128, 512, ENG_NWG, false, false, true>>(E, st);
-        case 3: /* gate | up and down_proj hold 8 and 6 blocks per lane: part of them is dequantised behind the hand-off (MvPhase::AH) */
-            if constexpr (FMT == FMT_Q4P) {
-                if (!E->canon) return engine_go<EngCfg<FMT_Q4P, 2, 128, ENG_NWV, 2048, 2048, 1024, 6144, ENG_NWG, true, false, false>>(E, st);
-                return engine_go<EngCfg<FMT_Q4P, 2, 128, ENG_NWV, 2048, 2048, 1024, 6144, ENG_NWG, true, false, true>>(E, st);
-            }
-            return 1;
-        default: return 1;
-    }
 }
 
 // 1: this position bound is outside what the engine serves (the caller runs the multi-launch path), < 0 error
@@ -1611,13 +1564,7 @@ int engine_step(EngineHost* E, hipStream_t st, const uint16_t* x_in, uint16_t* x
     if (me > E->hd || me > 64) return 1;
     a.merge_e = me; /* = EngCfg::ME of the instantiated shapes (whole workgroups: q_dim / n_cu) */
     a.x_in = x_in, a.x_out = x_out, a.d_state = d_state;
-    switch (E->fmt) {
-        case FMT_Q4P: return engine_go_fmt<FMT_Q4P>(E, st);
-        case FMT_Q4: return engine_go_fmt<FMT_Q4>(E, st);
-        case FMT_Q1T: return engine_go_fmt<FMT_Q1T>(E, st);
-        case FMT_Q2T: return engine_go_fmt<FMT_Q2T>(E, st);
-        default: return 1;
-    }
+    return E->form->go(E, st);
 }
 // bf16 embedding table for steps given x_in == NULL (the row is read inside the launch: one launch less per token)
 int engine_set_embedding(EngineHost* E, const kf_weight* w, const int32_t* d_forced) {
@@ -1650,7 +1597,7 @@ int engine_error_word(EngineHost* E, hipStream_t st, int* h_err) {
     *h_err = v[1];
     return KF_OK;
 }
-void engine_set_canonical(EngineHost* E, int on) { E->canon = on ? 1 : 0; }
+void engine_set_canonical(EngineHost* E, int on) { engine_repick(E, on != 0); }
 
 // ---- self-calibration of the first-sweep delays.  The hand-off protocol is correct for ANY delay -- a sweep that comes too early is repeated -- but a
 // repeated sweep costs its whole round trip on the critical path and a late one its lateness, and the best values depend on the device (clocks, fabric) and on how many

@@ -35,12 +35,8 @@ struct EngLayer {
     g_u16w kcache, vcache; /* layer base */
     g_i32 hot;             /* sparse forward: CS_Picker's hot[ffn] (1 = the gate / up row is computed, D_matmul_sparse); NULL: dense */
 };
-struct EngPlan { /* host copy of one mat-vec phase: the geometry gemv_launch would pick for the same matrices (checked against PlanT) */
-    int K, nBlk, lpr_log2, iters, gshift, njobs;
-    int M[3], slot0[3], qBias[3];
-    int total_slots, spg; /* slots per workgroup (contiguous) */
-    int pad_[3];
-};
+// one model's (one TP rank's) layer table out of its descriptor, validated for both engine families (kf_engine.hip)
+int eng_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool qbias_set, bool& q4p_ok, int* fmt_io = nullptr, bool allow_hot = false);
 
 constexpr int eng_gran_dw(int n) { return ((n * 4 + 255) & ~255) / 4; }
 constexpr int pow2_ceil(int v) {
@@ -293,9 +289,6 @@ constexpr int c_lpr_log2(int nBlk, long rows) { /* = gemv_lpr_log2 (kf_gemv.hip)
     while (l < 6 && nBlk > (1 << l) && (rows << l) / 64 < 1024 && (nBlk + (2 << l) - 1) / (2 << l) < (nBlk + (1 << l) - 1) / (1 << l)) l++;
     return l;
 }
-struct CPlan {
-    int K, nBlk, lpr_log2, iters, njobs, M[3], slot0[3], total, spg;
-};
 constexpr CPlan c_plan(int K, int epb, int m0, int m1, int m2, bool paired, int nwg) {
     CPlan P{};
     P.K = K, P.nBlk = K / epb;

@@ -137,8 +137,6 @@ int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t*
                        const int* d_pos, int n_head, int n_kv, int hd, float eps, int n_tok = 1, long long q_stride = 0, long long k_stride = 0, int seq_len = 0,
                        float* rstd_q = nullptr, float* rstd_k = nullptr);
 
-// ---- persistent decode engine (kf_engine.hip)
-struct EngineHost;
 // Development knobs (process-wide, default = the product's choice).  Not part of the ABI and never read from the environment: tests and the scripts under
 // scratch/ set them through kfdbg_set_knob (kf_abi.hip) to compare a kernel form with the form it replaces inside one process.
 struct Knobs {
@@ -158,6 +156,21 @@ struct Knobs {
     int gemm_min = 8;     /* token rows from which the MFMA tile kernels replace the per-token mat-vec loop */
 };
 extern Knobs g_knobs;
+// ---- the persistent decode engine: one sequence on every CU (kf_engine.hip)
+struct EngineHost;
+struct CPlan { /* one mat-vec phase of an engine, a compile-time figure of its model shape (kf_engine_common.h c_plan, PlanT) */
+    int K, nBlk, lpr_log2, iters, njobs, M[3], slot0[3], total, spg;
+};
+// one form the engine can launch (an engine_kernel<EngCfg<...>> instantiation, built from its EngCfg by eng_form): what it serves, its phase plans, its LDS, its launcher
+struct EngForm {
+    int shape_class, fmt;
+    bool canon, dbg;             /* the canonical order; the per-phase stamps */
+    CPlan plan[4];               /* q | k | v, o_proj, gate | up, down_proj */
+    size_t (*smem)(int n_layer); /* dynamic LDS of a launch */
+    int (*go)(EngineHost* E, hipStream_t st);
+};
+// THE choice of form, at create and when the order or the stamps change (no HIP call): nullptr = refused (no form for this shape and storage, or its LDS does not fit)
+const EngForm* engine_form(int shape_class, int fmt, bool canon, bool stamps, int n_layer);
 size_t engine_ws_bytes(const kf_engine_desc* d);
 int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t st, EngineHost** out, const char** why = nullptr, bool dry = false);
 int engine_tune(EngineHost* E, hipStream_t st, uint16_t* x_out, const int32_t* d_state, int pos_bound, int passes, float* us_before, float* us_after);

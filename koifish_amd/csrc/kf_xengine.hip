@@ -158,37 +158,6 @@ void xengine_free(XEngineHost* E) {
     if (E->args.dbg) (void)hipFree(E->args.dbg);
     delete E;
 }
-// one model's (one TP rank's) layer table out of its descriptor; qbias: the seven matrices' zero points of layer 0 (every layer, every rank: the same)
-// *fmt_io: the storage every matrix of the model carries (0 on entry = not known yet): FMT_Q4P (4-bit PackedQ) or FMT_Q1T (1-bit, round 6)
-static int xe_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool qbias_set, bool& q4p_ok, int* fmt_io = nullptr, bool allow_hot = false) {
-    const int hd = d->head_dim, q_dim = d->n_head * hd, kv_dim = d->n_kv * hd;
-    const int Ks[7] = {d->dim, d->dim, d->dim, q_dim, d->dim, d->dim, d->ffn}, Ms[7] = {q_dim, kv_dim, kv_dim, d->dim, d->ffn, d->ffn, d->dim};
-    for (int l = 0; l < d->n_layer; l++) {
-        const kf_engine_layer& Ly = d->layers[l];
-        if (Ly.hot_ffn && !allow_hot) return KF_UNSUPPORTED_DATATYPE;
-        if (!Ly.norm_in || !Ly.norm_post || !Ly.kcache || !Ly.vcache || (((uintptr_t)Ly.kcache | (uintptr_t)Ly.vcache) & 15) != 0) return KF_UNSUPPORTED_DATATYPE;
-        for (int j = 0; j < 7; j++) {
-            const kf_weight& w = Ly.w[j];
-            const int wf = gemv_fmt_of(&w), ef = wf == FMT_Q4 ? FMT_Q4P : (wf == FMT_Q1 ? FMT_Q1T : (wf == FMT_Q2 ? FMT_Q2T : -1));
-            if (ef < 0 || (!fmt_io && ef != FMT_Q4P) || (fmt_io && *fmt_io != 0 && *fmt_io != ef)) return KF_UNSUPPORTED_DATATYPE;
-            if (fmt_io) *fmt_io = ef;
-            if (w.ne0 != Ms[j] || w.ne1 != Ks[j] || w.qzeros || w.qscales || !w.gama || w.lGroup != 128 || (Ks[j] % 128) != 0 || ((uintptr_t)w.data & 15) != 0)
-                return KF_UNSUPPORTED_DATATYPE;
-            const long rows = j < 3 ? (long)q_dim + 2 * kv_dim : (j == 4 || j == 5 ? (long)d->ffn : (long)Ms[j]);
-            if (gemv_lpr_log2(Ks[j] / 32, rows) < 2) q4p_ok = false; /* the register-table form needs a group's four blocks in one aligned lane quad (1-bit: the four dwords of a block in one) */
-            tab[l].m[j].w = (g_u32x4)(uintptr_t)w.data;
-            tab[l].m[j].zero = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1);
-            tab[l].m[j].step = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1 + (size_t)w.ne0 * w.ne1 / w.lGroup);
-            if (l == 0 && !qbias_set) qbias[j] = (float)w.qBias;
-            else if (qbias[j] != (float)w.qBias) return KF_UNSUPPORTED_DATATYPE;
-        }
-        tab[l].norm_in = (g_u16)(uintptr_t)Ly.norm_in, tab[l].norm_post = (g_u16)(uintptr_t)Ly.norm_post;
-        tab[l].norm_q = (g_u16)(uintptr_t)Ly.q_norm, tab[l].norm_k = (g_u16)(uintptr_t)Ly.k_norm;
-        tab[l].kcache = (g_u16w)(uintptr_t)Ly.kcache, tab[l].vcache = (g_u16w)(uintptr_t)Ly.vcache;
-        tab[l].hot = (g_i32)(uintptr_t)Ly.hot_ffn; /* sparse forward: CS_Picker's hot[ffn] on the device (kf_abi.h kf_engine_layer::hot_ffn); NULL: dense */
-    }
-    return KF_OK;
-}
 // the engine over its validated, filled layer table (TP: the eight ranks' tables one after the other, ds[r] rank r's descriptor): the workspace carved, the fused q | k | v
 // copies made, the state initialised
 static int xe_make(const kf_engine_desc* const* ds, const XShape* sh, int fmt, int n_seq, long long kv_seq_stride, std::vector<EngLayer>& tab, const float* qbias, void* ws,
@@ -266,7 +235,7 @@ int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, v
     float qbias[7] = {0};
     bool q4p_ok = true;
     int fmt = 0;
-    if (xe_fill_layers(d, tab.data(), qbias, false, q4p_ok, &fmt, true) != KF_OK || !q4p_ok) return KF_UNSUPPORTED_DATATYPE;
+    if (eng_fill_layers(d, tab.data(), qbias, false, q4p_ok, &fmt, true) != KF_OK || !q4p_ok) return KF_UNSUPPORTED_DATATYPE;
     *why = "1-bit / 2-bit PackedQ layers are served for the Qwen3-0.6B shape and the 256-wide test shape";
     if (fmt != FMT_Q4P && !sh->lowbit) return KF_UNSUPPORTED_DATATYPE;
     *why = sh->sc == 3 && n_seq > XE_NXCD ? "two decoders per XCD (more than 8 sequences) do not fit this shape and depth: two workgroups per CU need 2 x the activations + the layer table in 160 KB of LDS"
@@ -312,7 +281,7 @@ int xengine_build_tp(const kf_engine_desc* const* ds, int world, void* ws, size_
     float qbias[7] = {0};
     bool q4p_ok = true;
     for (int r = 0; r < world; r++)
-        if (xe_fill_layers(ds[r], tab.data() + (size_t)r * d->n_layer, qbias, r > 0, q4p_ok) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
+        if (eng_fill_layers(ds[r], tab.data() + (size_t)r * d->n_layer, qbias, r > 0, q4p_ok) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
     if (!q4p_ok) return KF_UNSUPPORTED_DATATYPE;
     return xe_make(ds, sh, FMT_Q4P, XE_NXCD /* decoders = ranks */, 0, tab, qbias, ws, ws_bytes, st, out, why);
 }

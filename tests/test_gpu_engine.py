@@ -157,6 +157,26 @@ def test_engine_not_served_shapes_fall_back():
     m.close()
 
 
+def test_engine_refuses_4bit_groups_other_than_128():
+    """The engine kernel has 128-weight groups built in: a 4-bit model of an instantiated shape in groups of 64 is refused at create, with a reason, and decodes through
+    the per-layer launches (which read the group size at run time) -- the ids of the same model with the engine switched off, and the oracle's at that group size."""
+    cfg = _cfg("small", 64)
+    raw = synth.raw_weights_numpy(cfg, 77, w_std=0.1)
+    prompt = prompt_ids(cfg, 8)
+    ref_m = synth.build_from_raw(cfg, raw, L.Q4, L.BF16, lGroup=64)
+    ref_m.set_engine(False)
+    ref = ref_m.generate(prompt, 8, use_graph=True)
+    ref_m.close()
+    m = synth.build_from_raw(cfg, raw, L.Q4, L.BF16, lGroup=64)
+    assert "groups of 128" in m.engine_why(), m.engine_why()
+    got = m.generate(prompt, 8, use_graph=True)
+    assert m.engine_steps() == -1
+    m.close()
+    assert got == ref, "greedy ids %s differ from the per-layer launches' %s" % (got, ref)
+    om = oracle_model(cfg, raw, L.Q4, L.BF16, lGroup=64)
+    assert got == om.generate(prompt.tolist(), 8)
+
+
 def test_full_size_generations_repeat_bit_for_bit():
     """Soak of the engine inside the suite (round 3 kept it in scratch/): two full greedy decodes of Qwen3-0.6B per summation order (positions 0 .. 2046, runs of up to 16 steps per
     launch, every position bucket and slice count; every fourth id teacher-forced so that the sequence keeps moving) -- the second decode of an order reproduces the first one's
