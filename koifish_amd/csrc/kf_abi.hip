@@ -11,7 +11,7 @@
 
 #include <vector>
 
-#include "kf_kernels.h"
+#include "kf_gemm_plan.h"
 
 struct kf_ctx {
     int device;
@@ -34,7 +34,6 @@ struct kf_ctx {
     size_t arena_bytes, arena_used;
     std::vector<DeqCopy> copies;
 };
-enum { DEQ_STACK = 0, DEQ_ILV = 1 };
 struct kf_graph {
     hipGraph_t graph;
     hipGraphExec_t exec;
@@ -93,56 +92,56 @@ int kf_init(int device, void* stream, kf_ctx** out) {
     *out = c;
     return KF_OK;
 }
-// bf16 view of a weight: the data itself (bf16 storage) or its dequantisation into the caller's scratch (kf_set_scratch)
-static int lib_weight_bf16(kf_ctx* c, const kf_weight* w, const uint16_t** out) {
-    if (w->type == KF_BF16) {
-        *out = (const uint16_t*)w->data;
+static size_t up256z(size_t v) { return (v + 255) & ~(size_t)255; }
+// the resident copy of n_w matrices in `form` (kf_set_dequant_arena), or NULL: a lookup, nothing is launched or filled
+static const uint16_t* arena_find(const kf_ctx* c, int n_w, const kf_weight* const* w, int form) {
+    if (!c->arena) return nullptr;
+    for (const kf_ctx::DeqCopy& e : c->copies) {
+        bool same = e.form == form;
+        for (int i = 0; i < 3; i++) same = same && e.key[i] == (i < n_w ? w[i]->data : nullptr);
+        if (same) return (const uint16_t*)((const char*)c->arena + e.off);
+    }
+    return nullptr;
+}
+// The bf16 copies of a plan (p.deq, p.deq_form): resident in the arena, dequantised into it and kept, or dequantised into the scratch for this call.  KF_OK: *out holds
+// them; < 0 error.
+static int deq_copies(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight* const* w, const uint16_t** out) {
+    if (p.deq == kf::DQ_RESIDENT) {
+        *out = arena_find(c, n_w, w, p.deq_form);
         return KF_OK;
     }
-    const size_t need = (size_t)w->ne0 * w->ne1 * 2;
-    if (need > c->scratch_bytes || !c->scratch)
-        return fail(KF_INVALID_ARGS, "kf_linear: this weight needs %zu bytes of scratch (kf_linear_scratch_bytes), kf_set_scratch gave %zu", need, c->scratch_bytes);
-    const int r = kf::dequant_launch(c->stream, w, (uint16_t*)c->scratch);
-    *out = (const uint16_t*)c->scratch;
-    return r;
-}
-static size_t up256z(size_t v) { return (v + 255) & ~(size_t)255; }
-// The bf16 copies of n_w group-quantised matrices of one input width, laid out as `form` says: from the arena when the caller lent one (dequantised on first use and
-// kept), otherwise dequantised into the scratch for this call.  KF_OK: *out holds them; 1: no room in either; < 0 error.
-static int deq_copies(kf_ctx* c, int n_w, const kf_weight* const* w, int form, const uint16_t** out, bool* resident = nullptr, bool arena_only = false) {
-    size_t need = 0;
-    for (int i = 0; i < n_w; i++) need += up256z((size_t)w[i]->ne0 * w[i]->ne1 * 2);
-    if (resident) *resident = false;
-    if (c->arena) {
-        for (const kf_ctx::DeqCopy& e : c->copies) {
-            bool same = e.form == form;
-            for (int i = 0; i < 3; i++) same = same && e.key[i] == (i < n_w ? w[i]->data : nullptr);
-            if (same) {
-                *out = (const uint16_t*)((const char*)c->arena + e.off);
-                if (resident) *resident = true;
-                return KF_OK;
-            }
-        }
-    }
-    const bool keep = c->arena && !c->capturing && c->arena_used + need <= c->arena_bytes; /* a captured launch would replay the fill with every replay: those use the scratch */
-    char* dst = keep ? (char*)c->arena + c->arena_used : (char*)c->scratch;
-    if (!keep && (arena_only || !c->scratch || c->scratch_bytes < need)) return 1;
+    char* dst = p.deq == kf::DQ_ARENA ? (char*)c->arena + c->arena_used : (char*)c->scratch;
     size_t off = 0;
     for (int i = 0; i < n_w; i++) {
-        const int r = form == DEQ_ILV ? kf::dequant_launch(c->stream, w[i], (uint16_t*)dst, n_w, i) : kf::dequant_launch(c->stream, w[i], (uint16_t*)(dst + off));
+        const int r = p.deq_form == kf::DEQ_ILV ? kf::dequant_launch(c->stream, w[i], (uint16_t*)dst, n_w, i) : kf::dequant_launch(c->stream, w[i], (uint16_t*)(dst + off));
         if (r != KF_OK) return r < 0 ? r : KF_HIP_CHECK;
         off += up256z((size_t)w[i]->ne0 * w[i]->ne1 * 2);
     }
-    if (keep) {
+    if (p.deq == kf::DQ_ARENA) {
         kf_ctx::DeqCopy e;
         for (int i = 0; i < 3; i++) e.key[i] = i < n_w ? w[i]->data : nullptr;
-        e.form = form, e.off = c->arena_used;
+        e.form = p.deq_form, e.off = c->arena_used;
         c->copies.push_back(e);
-        c->arena_used += need;
-        if (resident) *resident = true;
+        c->arena_used += p.deq_bytes;
     }
     *out = (const uint16_t*)dst;
     return KF_OK;
+}
+static kf::GemmMat mat_of(const kf_weight* w) {
+    const bool tab_al = w->gama && al16(w->gama + w->ne0 + w->ne1);
+    return kf::GemmMat{w->type, w->quant, w->qzeros || w->qscales, w->ne0, w->ne1, w->lGroup, w->gama != nullptr, (al16(w->data) ? kf::GM_DATA_AL : 0) | (tab_al ? kf::GM_TAB_AL : 0)};
+}
+// what a token-batch entry knows before it launches anything (kf_gemm_plan.h)
+static kf::GemmProblem problem_of(const kf_ctx* c, int entry, int n_w, const kf_weight* const* w, int n, const void* x) {
+    kf::GemmProblem P;
+    memset(&P, 0, sizeof(P));
+    P.entry = entry, P.n_w = n_w, P.n = n, P.x_al = al16(x);
+    for (int i = 0; i < n_w; i++) P.w[i] = mat_of(w[i]);
+    P.scratch = c->scratch ? (long long)c->scratch_bytes : 0;
+    P.arena = c->arena != nullptr, P.capturing = c->capturing, P.arena_free = (long long)(c->arena_bytes - c->arena_used);
+    for (int f = kf::DEQ_STACK; f <= kf::DEQ_ILV; f++)
+        if (arena_find(c, n_w, w, f)) P.arena_hit |= 1 << f;
+    return P;
 }
 
 int kf_destroy(kf_ctx* c) {
@@ -314,14 +313,14 @@ int kf_quantize(kf_ctx* c, const kf_weight* w, const kf_bf16* src, int symmetric
 
 static void init_args(kf_ctx* c, kf::GemvLaunch& L) { memset(&L, 0, sizeof(L)); L.args.alpha = 1.0f; L.canon = c->canonical; }
 
-static const int KF_DEQ_GEMM_MIN = 2048; /* token rows from which a quantised weight is dequantised once and multiplied by the bf16 tile kernel (when scratch was handed over) */
+// Fish sizes its scratch from this answer, and the resident route lends that scratch to the split-K slots (kf_gemm_plan.h gemm_plan_linear): a smaller answer could
+// change a route and with it the bits.  So it stays what it always was -- the row forms' GetDataX copy (the 4-bit row codebook's too), and the large-batch dequantise
+// route's shape even where that route's tile-count test then declines.
 size_t kf_linear_scratch_bytes(const kf_weight* w, int nTok) {
     if (!w || nTok < 1) return 0;
     if (w->qzeros) return kf::awq_scratch_bytes(w);
-    if (w->quant != KF_QUANT_GROUP) return (size_t)w->ne0 * w->ne1 * 2; /* row forms: GetDataX into the scratch (the 4-bit row codebook only for token batches the tile kernels do not cover) */
-    // training-size batches of a quantised weight: one dequantise pass (a few % of the product at >= 2048 rows) buys the 256 x 256 bf16 tile kernel (kf_gemm3.hip)
-    if (w->type != KF_BF16 && nTok >= KF_DEQ_GEMM_MIN && w->ne0 >= 256 && (w->ne1 % 64) == 0) return (size_t)w->ne0 * w->ne1 * 2;
-    return 0;
+    const kf::GemmMat m = mat_of(w);
+    return m.quant != KF_QUANT_GROUP || kf::deq_tile_shape(m, nTok) ? (size_t)w->ne0 * w->ne1 * 2 : 0;
 }
 int kf_set_canonical(kf_ctx* c, int on) {
     CHKCTX(c);
@@ -348,6 +347,20 @@ int kf_set_scratch(kf_ctx* c, void* scratch, size_t bytes) {
     return KF_OK;
 }
 
+// one mat-vec launch per token row
+static int linear_rows(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta, const kf_bf16* residual) {
+    for (int t = 0; t < nTok; t++) {
+        kf::GemvLaunch L;
+        init_args(c, L);
+        L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN;
+        L.args.x = x + (size_t)t * w->ne1, L.args.job[0].y = y + (size_t)t * w->ne0;
+        L.args.bias = bias, L.args.alpha = alpha, L.args.beta = beta;
+        L.args.residual = residual ? residual + (size_t)t * w->ne0 : nullptr;
+        int rc = kf::gemv_launch(c->stream, L);
+        if (rc != KF_OK) return fail(rc, "kf_linear failed with %d", rc);
+    }
+    return KF_OK;
+}
 int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta, uint32_t epilogue,
               const kf_bf16* residual) {
     CHKCTX(c);
@@ -357,89 +370,41 @@ int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const
     if (!x || !y || !al16(x)) return fail(KF_BLAS_UNALIGN, "kf_linear: x/y null or x unaligned");
     if ((epilogue & KF_EPI_RESIDUAL) && !residual) return fail(KF_INVALID_ARGS, "kf_linear: residual epilogue without residual");
     if (nTok > 1 && ((w->ne1 * 2) % 16 != 0)) return fail(KF_BLAS_UNALIGN, "kf_linear: token rows of x are not 16-byte aligned");
-    // nTok > 1 (SLP::Forw with a batch of tokens: x [nTok, ne1] row-major, y [nTok, ne0]): the MFMA tile kernels of kf_gemm.hip from 8 rows
-    // up when the shape is covered (K a multiple of 128, 16-byte aligned rows), otherwise one mat-vec launch per token row.
-    if (w->qzeros) { /* AutoAWQ layout: its own transposed mat-vec */
+    // nTok > 1 (SLP::Forw with a batch of tokens: x [nTok, ne1] row-major, y [nTok, ne0]): the MFMA tile kernels from kf::GEMM_MIN rows up when the shape is covered,
+    // otherwise one mat-vec launch per token row; which kernel, on which operand, is kf::gemm_plan's choice
+    const kf_bf16* res = (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr;
+    const kf::GemmPlan p = kf::gemm_plan(problem_of(c, kf::GE_LINEAR, 1, &w, nTok, x));
+    if (p.route == kf::GR_AWQ) { /* AutoAWQ layout: its own transposed mat-vec */
         const size_t need = kf::awq_scratch_bytes(w);
         if (need > c->scratch_bytes || !c->scratch)
             return fail(KF_INVALID_ARGS, "kf_linear: the AWQ mat-vec needs %zu bytes of scratch (kf_linear_scratch_bytes), kf_set_scratch gave %zu", need, c->scratch_bytes);
         for (int t = 0; t < nTok; t++) {
-            int rc = kf::awq_linear_launch(c->stream, w, x + (size_t)t * w->ne1, y + (size_t)t * w->ne0, bias, alpha, beta,
-                                           (epilogue & KF_EPI_RESIDUAL) ? residual + (size_t)t * w->ne0 : nullptr, (float*)c->scratch);
+            int rc = kf::awq_linear_launch(c->stream, w, x + (size_t)t * w->ne1, y + (size_t)t * w->ne0, bias, alpha, beta, res ? res + (size_t)t * w->ne0 : nullptr,
+                                           (float*)c->scratch);
             if (rc != KF_OK) return fail(rc, "kf_linear (AWQ) failed with %d", rc);
         }
         return KF_OK;
     }
-    const int gemm_min = kf::g_knobs.gemm_min; /* token rows from which the MFMA tile kernel replaces the per-token mat-vec loop (8) */
-    if (w->quant != KF_QUANT_GROUP && w->type != KF_Q4) {
-        // 3- / 2-bit row forms: GetDataX into the scratch, then the bf16 product, whatever the batch (the reference's own order; no in-place mat-vec)
-        const uint16_t* Wd = nullptr;
-        r = lib_weight_bf16(c, w, &Wd);
-        if (r != KF_OK) return fail(r, "kf_linear (row-form dequant) failed with %d", r);
+    if (p.route == kf::GR_MATVEC) return linear_rows(c, w, x, y, bias, nTok, alpha, beta, res);
+    if (p.route == kf::GR_TILE) {
+        const int rc = p.status ? p.status : kf::gemm_launch(c->stream, p.k, kf::gm_operand(w, p.k), x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, res, w->ne0);
+        return rc ? fail(rc, "kf_linear (token-batch GEMM) failed with %d", rc) : KF_OK;
+    }
+    // on a bf16 copy: a row form's GetDataX into the scratch, the resident copy (kf_set_dequant_arena), a large batch's dequantise into the scratch
+    const bool row = p.route == kf::GR_ROWFORM, lut = row && w->type == KF_Q4, resident = p.route == kf::GR_RESIDENT;
+    const char* what = lut ? "row-LUT dequant" : row ? "row-form dequant" : (resident ? "resident dequantised copy" : "dequantise for the large-batch tile kernel");
+    if (row && (!c->scratch || (size_t)p.deq_bytes > c->scratch_bytes)) return fail(KF_INVALID_ARGS, "kf_linear (%s) failed with %d", what, KF_INVALID_ARGS);
+    const uint16_t* W = nullptr;
+    r = deq_copies(c, p, 1, &w, &W);
+    if (r != KF_OK) return fail(r, "kf_linear (%s) failed with %d", what, r);
+    if (!p.k.fam) { /* a row form below kf::GEMM_MIN rows, or a shape no tile kernel takes: the mat-vec on the copy */
         kf_weight wb;
         memset(&wb, 0, sizeof(wb));
-        wb.data = Wd, wb.type = KF_BF16, wb.ne0 = w->ne0, wb.ne1 = w->ne1;
-        return kf_linear(c, &wb, x, y, bias, nTok, alpha, beta, epilogue, residual);
+        wb.data = W, wb.type = KF_BF16, wb.ne0 = w->ne0, wb.ne1 = w->ne1;
+        return linear_rows(c, &wb, x, y, bias, nTok, alpha, beta, res);
     }
-    if (c->arena && nTok >= kf::g_knobs.resident_min && w->type != KF_BF16 && w->quant == KF_QUANT_GROUP && w->ne0 >= 128 && (w->ne1 % 64) == 0) {
-        // a resident copy (kf_set_dequant_arena): nothing to dequantise -- the bf16 tile kernels of kf_gemm3.hip from g_knobs.resident_min token rows (the 1024-row o_proj / down_proj of a
-        // long prompt as 256 tiles of 64 x 128 or 64 x 64)
-        const kf_weight* one[1] = {w};
-        const uint16_t* W = nullptr;
-        r = deq_copies(c, 1, one, DEQ_STACK, &W, nullptr, true);
-        if (r < 0) return fail(r, "kf_linear (resident dequantised copy) failed with %d", r);
-        if (r == KF_OK) {
-            kf_weight wb;
-            memset(&wb, 0, sizeof(wb));
-            wb.data = W, wb.type = KF_BF16, wb.ne0 = w->ne0, wb.ne1 = w->ne1;
-            const bool lend = c->scratch && c->scratch_bytes >= kf::gemm3_sk_ws_bytes() && al16(c->scratch); /* the scratch holds no copy on this route: split-K slots */
-            const int rc = kf::gemm_launch(c->stream, &wb, x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr, w->ne0, lend ? c->scratch : nullptr,
-                                           lend ? c->scratch_bytes : 0);
-            if (rc < 0) return fail(rc, "kf_linear (bf16 tile GEMM on the resident copy) failed with %d", rc);
-            if (rc == KF_OK) return KF_OK;
-        }
-    }
-    if (nTok >= KF_DEQ_GEMM_MIN && w->type != KF_BF16 && w->quant == KF_QUANT_GROUP && w->ne0 >= 256 && (w->ne1 % 64) == 0 && c->scratch &&
-        c->scratch_bytes >= (size_t)w->ne0 * w->ne1 * 2 &&
-        ((long)((w->ne0 + 255) / 256) * ((nTok + 255) / 256) >= 128 || (long)((w->ne0 + 127) / 128) * ((nTok + 127) / 128) >= 256 /* the 128 x 128 form: M 1024 from 4096 rows */)) {
-        // GetDataX into the caller's scratch, then the 256 x 256 bf16 tile kernel: the reference's own order, on our own kernels
-        r = kf::dequant_launch(c->stream, w, (uint16_t*)c->scratch);
-        if (r != KF_OK) return fail(r, "kf_linear (dequantise for the large-batch tile kernel) failed with %d", r);
-        kf_weight wb;
-        memset(&wb, 0, sizeof(wb));
-        wb.data = c->scratch, wb.type = KF_BF16, wb.ne0 = w->ne0, wb.ne1 = w->ne1;
-        const int rc = kf::gemm_launch(c->stream, &wb, x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr, w->ne0);
-        if (rc < 0) return fail(rc, "kf_linear (large-batch bf16 tile GEMM) failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
-    }
-    if (nTok >= gemm_min) {
-        const int rc = kf::gemm_launch(c->stream, w, x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr, w->ne0);
-        if (rc < 0) return fail(rc, "kf_linear (token-batch GEMM) failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
-    }
-    if (nTok >= gemm_min && w->quant == KF_QUANT_ROW_LUT && c->scratch && c->scratch_bytes >= (size_t)w->ne0 * w->ne1 * 2) {
-        // row-codebook storage whose shape the in-register-unpack tile kernels do not cover: the reference's own order -- GetDataX into the scratch,
-        // then the bf16 product on the dequantised copy.  Mat-vecs (below) read the nibble stream directly.
-        const uint16_t* Wd = nullptr;
-        r = lib_weight_bf16(c, w, &Wd);
-        if (r != KF_OK) return fail(r, "kf_linear (row-LUT dequant) failed with %d", r);
-        kf_weight wb;
-        memset(&wb, 0, sizeof(wb));
-        wb.data = Wd, wb.type = KF_BF16, wb.ne0 = w->ne0, wb.ne1 = w->ne1;
-        const int rc = kf::gemm_launch(c->stream, &wb, x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr, w->ne0);
-        if (rc < 0) return fail(rc, "kf_linear (row-LUT token-batch GEMM) failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
-    }
-    for (int t = 0; t < nTok; t++) {
-        kf::GemvLaunch L;
-        init_args(c, L);
-        L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN;
-        L.args.x = x + (size_t)t * w->ne1, L.args.job[0].y = y + (size_t)t * w->ne0;
-        L.args.bias = bias, L.args.alpha = alpha, L.args.beta = beta;
-        L.args.residual = (epilogue & KF_EPI_RESIDUAL) ? residual + (size_t)t * w->ne0 : nullptr;
-        int rc = kf::gemv_launch(c->stream, L);
-        if (rc != KF_OK) return fail(rc, "kf_linear failed with %d", rc);
-    }
+    const int rc = kf::gemm_launch(c->stream, p.k, kf::gm_bf16(W, w->ne0, w->ne1), x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, res, w->ne0, p.ws_bytes ? c->scratch : nullptr);
+    if (rc) return fail(rc, "kf_linear (%s) failed with %d", lut ? "row-LUT token-batch GEMM" : row ? "token-batch GEMM" : (resident ? "bf16 tile GEMM on the resident copy" : "large-batch bf16 tile GEMM"), rc);
     return KF_OK;
 }
 
@@ -741,38 +706,33 @@ int kf_embed_batch(kf_ctx* c, const kf_weight* w, const int32_t* d_tokens, int n
 // Large token batches of matrices that share their input (Q | K | V, gate | up): GetDataX of each into the caller's scratch, back to back, then ONE launch of the
 // 256 x 256 bf16 tile kernel over the stacked rows (each matrix a multiple of 256 rows; its rows go to its own output).  A 1024-row K or V projection alone is 4 x 8
 // tiles at 2048 tokens -- an eighth of the chip -- and took 32 us on the in-register-unpack kernels; stacked with Q it is 128 tiles.
-static const int KF_MULTI_DEQ_MIN = 1024; /* token rows from which the stacked route is taken (with a dequantise per call; resident copies: g_knobs.resident_min) */
-static int multi_min(const kf_ctx* c) { return c && c->arena && kf::g_knobs.resident_min < KF_MULTI_DEQ_MIN ? kf::g_knobs.resident_min : KF_MULTI_DEQ_MIN; }
-/* up256z: a no-op on these sizes (multiples of 256 rows x 64 columns): the stacked rows are contiguous */
-static bool multi_deq_ok(int n_w, const kf_weight* const* w, int nTok, size_t* need, const kf_ctx* c = nullptr) {
-    size_t tot = 0;
-    long rows = 0;
-    if (n_w < 2 || n_w > 3 || nTok < multi_min(c)) return false;
-    for (int i = 0; i < n_w; i++) {
-        if (w[i]->qzeros || w[i]->quant != KF_QUANT_GROUP || w[i]->ne0 < 256 || (w[i]->ne0 % 256) != 0 || (w[i]->ne1 % 64) != 0 || w[i]->ne1 != w[0]->ne1) return false;
-        tot += up256z((size_t)w[i]->ne0 * w[i]->ne1 * 2), rows += w[i]->ne0;
-    }
-    if ((rows / 256) * ((nTok + 255) / 256) < 64 && (rows / 128) * ((nTok + 127) / 128) < 64) return false; /* fewer tiles than that: the in-register-unpack kernels */
-    *need = tot;
-    return true;
-}
 size_t kf_linear_multi_scratch_bytes(int n_w, const kf_weight* const* w, int nTok) {
-    size_t need = 0;
-    if (!w) return 0;
-    for (int i = 0; i < n_w; i++)
+    if (!w || n_w < 2 || n_w > 3) return 0;
+    kf::GemmProblem P;
+    memset(&P, 0, sizeof(P));
+    P.n_w = n_w, P.n = nTok;
+    for (int i = 0; i < n_w; i++) {
         if (!w[i]) return 0;
-    return multi_deq_ok(n_w, w, nTok, &need) ? need : 0;
+        P.w[i] = mat_of(w[i]);
+    }
+    long long bytes = 0;
+    return kf::stack_shape(P, &bytes) ? (size_t)bytes : 0; /* the stacked route's copy without an arena */
 }
-// KF_OK done, 1 not this route, < 0 error
-static int multi_deq_route(kf_ctx* c, int n_w, const kf_weight* const* w, const kf_bf16* x, kf_bf16* const* y, int nTok, const kf::G3Rope* rope = nullptr) {
-    size_t need = 0;
-    if (!multi_deq_ok(n_w, w, nTok, &need, c) || !al16(x)) return 1;
+// GR_STACKED / GR_ROPE: the plan's copies back to back, one kf_gemm3.hip launch over the stacked rows
+static int stacked_launch(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight* const* w, const kf_bf16* x, kf_bf16* const* y, int nTok, const kf::G3Rope* rope = nullptr) {
     int M[3] = {0, 0, 0};
     for (int i = 0; i < n_w; i++) M[i] = w[i]->ne0;
     const uint16_t* W = nullptr;
-    const int r = deq_copies(c, n_w, w, DEQ_STACK, &W);
+    const int r = deq_copies(c, p, n_w, w, &W);
     if (r != KF_OK) return r;
-    return kf::gemm3_multi_launch(c->stream, n_w, W, M, w[0]->ne1, x, w[0]->ne1, nTok, y, rope);
+    return kf::gemm3_multi_launch(c->stream, p.k, n_w, W, M, w[0]->ne1, x, w[0]->ne1, nTok, y, rope);
+}
+// GR_FUSED: the direct kernel over the matrices as they are stored
+static int fused_launch(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight* const* w, const kf_bf16* x, int nTok, kf_bf16* const* y) {
+    if (p.status) return p.status;
+    kf::GmWeight g[3];
+    for (int i = 0; i < n_w; i++) g[i] = kf::gm_operand(w[i], p.k);
+    return kf::gemm_multi_launch(c->stream, p.k, n_w, g, x, w[0]->ne1, nTok, y);
 }
 int kf_qkv_rope_batch(kf_ctx* c, const kf_weight* wq, const kf_weight* wk, const kf_weight* wv, const kf_bf16* x, kf_bf16* q, kf_bf16* k, kf_bf16* v, int nTok, const kf_bf16* wq_norm,
                       const kf_bf16* wk_norm, const float* rope_table, int pos0, int n_head, int n_kv, int hd, float eps) {
@@ -785,15 +745,21 @@ int kf_qkv_rope_seqs(kf_ctx* c, const kf_weight* wq, const kf_weight* wk, const 
         return fail(KF_INVALID_ARGS, "kf_qkv_rope_batch / _seqs: bad args");
     const kf_weight* ws[3] = {wq, wk, wv};
     kf_bf16* ys[3] = {q, k, v};
-    if (hd == 128 && nTok >= multi_min(c) && wq->ne0 == n_head * hd && wk->ne0 == n_kv * hd) { /* one launch: the stacked tile GEMM with q/k-norm + RoPE in its epilogue */
+    kf::GemmProblem P = problem_of(c, kf::GE_QKV_ROPE, 3, ws, nTok, x);
+    P.rope_ok = hd == 128 && wq->ne0 == n_head * hd && wk->ne0 == n_kv * hd;
+    P.y_al = (((uintptr_t)q | (uintptr_t)k) & 7) == 0;
+    if (P.rope_ok && nTok >= kf::stack_min(P.arena)) {
         for (int i = 0; i < 3; i++) {
             const int r = check_weight(ws[i], "kf_qkv_rope_batch");
             if (r) return r;
         }
+    }
+    const kf::GemmPlan p = kf::gemm_plan(P);
+    if (p.route == kf::GR_ROPE) { /* one launch: the stacked tile GEMM with q/k-norm + RoPE in its epilogue */
         const kf::G3Rope rp = {wq_norm, wk_norm, rope_table, pos0, eps, seq_len};
-        const int rc = multi_deq_route(c, 3, ws, x, ys, nTok, &rp);
-        if (rc < 0) return fail(rc, "kf_qkv_rope_batch (stacked tile GEMM + RoPE epilogue) failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
+        const int rc = stacked_launch(c, p, 3, ws, x, ys, nTok, &rp);
+        if (rc) return fail(rc, "kf_qkv_rope_batch (stacked tile GEMM + RoPE epilogue) failed with %d", rc);
+        return KF_OK;
     }
     const int r = kf_linear_multi(c, 3, ws, x, ys, nTok);
     if (r) return r;
@@ -809,17 +775,14 @@ int kf_linear_multi(kf_ctx* c, int n_w, const kf_weight* const* w, const kf_bf16
         if (!y[i]) return fail(KF_INVALID_ARGS, "kf_linear_multi: y[%d] null", i);
         if (w[i]->ne1 != w[0]->ne1) return fail(KF_INVALID_ARGS, "kf_linear_multi: the matrices do not share the input width");
     }
-    if (n_w > 1 && nTok >= multi_min(c)) {
-        const int rc = multi_deq_route(c, n_w, w, x, y, nTok);
-        if (rc < 0) return fail(rc, "kf_linear_multi (dequantise + stacked tile GEMM) failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
+    const kf::GemmPlan p = kf::gemm_plan(problem_of(c, kf::GE_MULTI, n_w, w, nTok, x));
+    if (p.route == kf::GR_STACKED) {
+        const int rc = stacked_launch(c, p, n_w, w, x, y, nTok);
+        return rc ? fail(rc, "kf_linear_multi (dequantise + stacked tile GEMM) failed with %d", rc) : KF_OK;
     }
-    // (bf16 storage from g3_first rows: kf_linear multiplies each matrix on the kf_gemm3.hip tile kernels -- the stacked in-register launch would be another summation order)
-    const bool bf16_tiles = w[0]->type == KF_BF16 && nTok >= kf::g_knobs.g3_first;
-    if (n_w > 1 && nTok >= 8 && !bf16_tiles) {
-        const int rc = kf::gemm_multi_launch(c->stream, n_w, w, x, w[0]->ne1, nTok, y);
-        if (rc < 0) return fail(rc, "kf_linear_multi failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
+    if (p.route == kf::GR_FUSED) {
+        const int rc = fused_launch(c, p, n_w, w, x, nTok, y);
+        return rc ? fail(rc, "kf_linear_multi failed with %d", rc) : KF_OK;
     }
     for (int i = 0; i < n_w; i++) {
         int r = kf_linear(c, w[i], x, y[i], nullptr, nTok, 1.0f, 0.0f, KF_EPI_NONE, nullptr);
@@ -835,25 +798,26 @@ int kf_gateup_swiglu_batch(kf_ctx* c, const kf_weight* gate, const kf_weight* up
     if (r) return r;
     if (!x || !act || !up_scratch || nTok < 1) return fail(KF_INVALID_ARGS, "kf_gateup_swiglu_batch: bad args");
     if (gate->ne0 != up->ne0 || gate->ne1 != up->ne1) return fail(KF_INVALID_ARGS, "kf_gateup_swiglu_batch: gate and up shapes differ");
-    if (nTok >= multi_min(c)) { /* gate | up dequantised interleaved, ONE tile-GEMM launch with the SwiGLU expression in its epilogue (on the two bf16-rounded projections,
-                                       as the paired kernel and swiglu_kernel form it) */
-        const kf_weight* ws[2] = {gate, up};
-        size_t need = 0;
+    const kf_weight* ws[2] = {gate, up};
+    kf_bf16* ys[2] = {act, up_scratch};
+    kf::GemmProblem P = problem_of(c, kf::GE_GATEUP, 2, ws, nTok, x);
+    P.y_al = ((uintptr_t)act & 7) == 0;
+    const kf::GemmPlan p = kf::gemm_plan(P);
+    if (p.route == kf::GR_SWIGLU) { /* gate | up dequantised interleaved, ONE tile-GEMM launch with the SwiGLU expression in its epilogue (on the two bf16-rounded
+                                       projections, as the paired kernel and swiglu_kernel form it) */
         const uint16_t* W = nullptr;
-        if (multi_deq_ok(2, ws, nTok, &need, c) && al16(x) && gate->ne0 % 128 == 0 && deq_copies(c, 2, ws, DEQ_ILV, &W) == KF_OK) {
-            const int rc = kf::gemm3_swiglu_launch(c->stream, W, gate->ne0, gate->ne1, x, gate->ne1, nTok, act);
-            if (rc < 0) return fail(rc, "kf_gateup_swiglu_batch (interleaved dequantise + tile GEMM with SwiGLU epilogue) failed with %d", rc);
-            if (rc == KF_OK) return KF_OK;
-        }
-        kf_bf16* ys[2] = {act, up_scratch};
-        const int rc = multi_deq_route(c, 2, ws, x, ys, nTok);
-        if (rc < 0) return fail(rc, "kf_gateup_swiglu_batch (dequantise + stacked tile GEMM) failed with %d", rc);
-        if (rc == KF_OK) return kf_swiglu(c, act, up_scratch, act, (size_t)nTok * gate->ne0);
+        int rc = deq_copies(c, p, 2, ws, &W);
+        if (rc == KF_OK) rc = kf::gemm3_swiglu_launch(c->stream, p.k, W, gate->ne0, gate->ne1, x, gate->ne1, nTok, act);
+        return rc ? fail(rc, "kf_gateup_swiglu_batch (interleaved dequantise + tile GEMM with SwiGLU epilogue) failed with %d", rc) : KF_OK;
     }
-    if (nTok >= 8 && !(gate->type == KF_BF16 && nTok >= kf::g_knobs.g3_first)) { /* bf16 storage from g3_first rows: two kf_linear (tile kernels) + kf_swiglu, as kf_linear_multi */
-        const int rc = kf::gemm_paired_launch(c->stream, gate, up, x, gate->ne1, nTok, act);
-        if (rc < 0) return fail(rc, "kf_gateup_swiglu_batch failed with %d", rc);
-        if (rc == KF_OK) return KF_OK;
+    if (p.route == kf::GR_STACKED) {
+        const int rc = stacked_launch(c, p, 2, ws, x, ys, nTok);
+        if (rc) return fail(rc, "kf_gateup_swiglu_batch (dequantise + stacked tile GEMM) failed with %d", rc);
+        return kf_swiglu(c, act, up_scratch, act, (size_t)nTok * gate->ne0);
+    }
+    if (p.route == kf::GR_FUSED) { /* the paired direct kernel */
+        const int rc = fused_launch(c, p, 2, ws, x, nTok, ys);
+        return rc ? fail(rc, "kf_gateup_swiglu_batch failed with %d", rc) : KF_OK;
     }
     r = kf_linear(c, gate, x, act, nullptr, nTok, 1.0f, 0.0f, KF_EPI_NONE, nullptr);
     if (r) return r;
@@ -1018,39 +982,40 @@ int kf_linear_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, co
         r = kf::colsum_add_launch(c->stream, deltaIn, gBias, n, OC, slabs);
         if (r != KF_OK) return fail(r, "kf_linear_backward: bias column sums failed with %d", r);
     }
+    kf::GemmProblem P; /* the two products' plans (kf_gemm_plan.h gemm_plan_backward): the middle region lends the split-K slots */
+    memset(&P, 0, sizeof(P));
+    P.n_w = 1, P.w[0] = mat_of(w), P.n = n, P.x_al = 1, P.scratch = (long long)sk_bytes;
     if (delta) { /* delta [n, IC] (+)= deltaIn [n, OC] . W [OC, IC]: rows of W^T are contiguous in the contraction index OC */
+        P.entry = kf::GE_BWD_DX;
+        const kf::GemmPlan p = kf::gemm_plan(P);
         const uint16_t* Wsrc = (const uint16_t*)w->data;
         r = KF_OK;
         if (w->type != KF_BF16) r = kf::dequant_launch(c->stream, w, Wd), Wsrc = Wd;
         if (r != KF_OK) return fail(r, "kf_linear_backward: dequantise of the weight failed with %d", r);
-        // large shapes: the 256x256 tile kernel reads W as the K-MAJOR operand it already is (contraction over its OC rows): no transpose
-        r = kf::gemm3_km_launch(c->stream, Wsrc, IC, true, deltaIn, OC, false, n, IC, OC, delta, IC, nullptr, 1.0f, accumulate_delta ? 1.0f : 0.0f, sk_ws, sk_bytes);
-        if (r < 0) return fail(r, "kf_linear_backward: input-gradient GEMM failed with %d", r);
+        if (p.route == kf::GR_KMAJOR) { /* large shapes: the tile kernel reads W as the K-MAJOR operand it already is (contraction over its OC rows): no transpose */
+            r = kf::gemm3_km_launch(c->stream, p.k, Wsrc, IC, deltaIn, OC, n, IC, OC, delta, IC, 1.0f, accumulate_delta ? 1.0f : 0.0f, sk_ws);
+            if (r) return fail(r, "kf_linear_backward: input-gradient GEMM failed with %d", r);
+        } else {
+            r = w->type == KF_BF16 ? kf::dequant_launch(c->stream, w, Wd) : KF_OK;
+            if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, Wd, WdT, OC, IC);
+            if (r != KF_OK) return fail(r, "kf_linear_backward: dequantise / transpose of the weight failed with %d", r);
+            r = p.k.fam ? kf::gemm_launch(c->stream, p.k, kf::gm_bf16(WdT, IC, OC), deltaIn, OC, n, delta, IC, nullptr, 1.0f, accumulate_delta ? 1.0f : 0.0f, nullptr, IC) : 1;
+            if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: input-gradient GEMM not covered (%d)", r);
+        }
     }
-    if (delta && r == 1) {
-        r = w->type == KF_BF16 ? kf::dequant_launch(c->stream, w, Wd) : KF_OK;
-        if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, Wd, WdT, OC, IC);
-        if (r != KF_OK) return fail(r, "kf_linear_backward: dequantise / transpose of the weight failed with %d", r);
-        kf_weight wt;
-        memset(&wt, 0, sizeof(wt));
-        wt.data = WdT, wt.type = KF_BF16, wt.ne0 = IC, wt.ne1 = OC;
-        r = kf::gemm_launch(c->stream, &wt, deltaIn, OC, n, delta, IC, nullptr, 1.0f, accumulate_delta ? 1.0f : 0.0f, nullptr, IC);
-        if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: input-gradient GEMM not covered (%d)", r);
-    }
-    int rg = 1;
     if (gW) { /* both operands are k-major for the contraction over the n token rows: inp [n][IC] is the "weight" side, deltaIn [n][OC] the "token" side */
-        rg = kf::gemm3_km_launch(c->stream, inp, IC, true, deltaIn, OC, true, OC, IC, n, gW, IC, nullptr, 1.0f, 1.0f, sk_ws, sk_bytes);
-        if (rg < 0) return fail(rg, "kf_linear_backward: weight-gradient GEMM failed with %d", rg);
-    }
-    if (gW && rg == 1) { /* gW [OC, IC] += deltaIn^T [OC, n] . inp [n, IC]: "weight" = inp^T [IC, n], "tokens" = the OC rows of deltaIn^T, contraction over n */
-        r = kf::transpose_bf16_launch(c->stream, deltaIn, dInT, n, OC);
-        if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, inp, inpT, n, IC);
-        if (r != KF_OK) return fail(r, "kf_linear_backward: operand transposes failed with %d", r);
-        kf_weight xt;
-        memset(&xt, 0, sizeof(xt));
-        xt.data = inpT, xt.type = KF_BF16, xt.ne0 = IC, xt.ne1 = n;
-        r = kf::gemm_launch(c->stream, &xt, dInT, n, OC, gW, IC, nullptr, 1.0f, 1.0f, nullptr, IC);
-        if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: weight-gradient GEMM not covered (%d)", r);
+        P.entry = kf::GE_BWD_DW;
+        const kf::GemmPlan p = kf::gemm_plan(P);
+        if (p.route == kf::GR_KMAJOR) {
+            r = kf::gemm3_km_launch(c->stream, p.k, inp, IC, deltaIn, OC, OC, IC, n, gW, IC, 1.0f, 1.0f, sk_ws);
+            if (r) return fail(r, "kf_linear_backward: weight-gradient GEMM failed with %d", r);
+        } else { /* gW [OC, IC] += deltaIn^T [OC, n] . inp [n, IC]: "weight" = inp^T [IC, n], "tokens" = the OC rows of deltaIn^T, contraction over n */
+            r = kf::transpose_bf16_launch(c->stream, deltaIn, dInT, n, OC);
+            if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, inp, inpT, n, IC);
+            if (r != KF_OK) return fail(r, "kf_linear_backward: operand transposes failed with %d", r);
+            r = p.k.fam ? kf::gemm_launch(c->stream, p.k, kf::gm_bf16(inpT, IC, n), dInT, n, OC, gW, IC, nullptr, 1.0f, 1.0f, nullptr, IC) : 1;
+            if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: weight-gradient GEMM not covered (%d)", r);
+        }
     }
     return KF_OK;
 }
@@ -1384,7 +1349,13 @@ int kfdbg_engine_set_delays(kf_engine* e, const int* d6) {
     kf::engine_set_delays(e->h, d6);
     return 0;
 }
-// development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process
+// the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py
+int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::gemm_plan(*P);
+    return 0;
+}
+// development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process (the token-batch routes have none: kf_gemm_plan.h)
 int kfdbg_set_knob(const char* name, long value) {
     if (!name) return -1;
     kf::Knobs& k = kf::g_knobs;
@@ -1394,13 +1365,7 @@ int kfdbg_set_knob(const char* name, long value) {
     else if (!strcmp(name, "gemv_waves")) k.gemv_waves = value;
     else if (!strcmp(name, "gemv_stream")) k.gemv_stream = (int)value;
     else if (!strcmp(name, "gemv_xf2")) k.gemv_xf2 = (int)value;
-    else if (!strcmp(name, "gemm_min")) k.gemm_min = (int)value;
-    else if (!strcmp(name, "g3_tiles")) k.g3_tiles = (int)value;
-    else if (!strcmp(name, "g3_first")) k.g3_first = (int)value;
-    else if (!strcmp(name, "g3_wide")) k.g3_wide = (int)value;
     else if (!strcmp(name, "attn_gq_split")) k.attn_gq_split = (int)value;
-    else if (!strcmp(name, "g3_mid_min")) k.g3_mid_min = (int)value;
-    else if (!strcmp(name, "resident_min")) k.resident_min = (int)value;
     else if (!strcmp(name, "attn_pair_min")) k.attn_pair_min = (int)value;
     else return -1;
     return 0;

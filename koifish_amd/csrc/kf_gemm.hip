@@ -473,104 +473,61 @@ __global__ void __launch_bounds__(NW * 64) gemm_direct_kernel(const GemmArgs a0)
     }
 }
 
-static int gm_fmt_of(int type) {
-    switch (type) {
-        case KF_BF16: return FMT_BF16;
-        case KF_F8E5M2: return FMT_F8;
-        case KF_Q4: return FMT_Q4;
-        case KF_T_SIGN: return FMT_Q2;
-        case KF_BOOL1: case KF_T_BINARY: return FMT_Q1;
-        default: return -1;
-    }
-}
-
-constexpr int GD_NW = 8, GD_UPG = 2; /* direct kernel: 8 waves, groups of two 64-element units, 32-token tiles */
-
 template <int FMT>
-static void gm_launch(const GemmArgs& a, int KS, dim3 grid, size_t smem, hipStream_t st) {
-    if (KS == 0)
-        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 1, GD_UPG, GD_NW, false>), grid, dim3(GD_NW * 64), (size_t)GD_NW * 16 * 64 * 4, st, a);
-    else if (KS == -2) /* 64-token tiles: every weight block is unpacked for two token blocks */
-        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 2, GD_UPG, GD_NW, false>), grid, dim3(GD_NW * 64), (size_t)GD_NW * 2 * 16 * 64 * 4, st, a);
-    else if (KS == -1) /* paired SwiGLU */
-        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 1, GD_UPG, GD_NW, true>), grid, dim3(GD_NW * 64), (size_t)GD_NW * 2 * 16 * 64 * 4, st, a);
-    else if (KS == 2)
-        hipLaunchKernelGGL((gemm_kernel<FMT, 2>), grid, dim3(256), smem, st, a);
+static void gm_launch(const GemmKern& k, const GemmArgs& a, hipStream_t st) {
+    const dim3 grid(k.gx, k.gy), block(k.block);
+    if (k.fam == GK_PAIRED) /* paired SwiGLU */
+        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 1, GD_UPG, GD_NW, true>), grid, block, k.lds, st, a);
+    else if (k.fam == GK_DIRECT && k.form == 64) /* 64-token tiles: every weight block is unpacked for two token blocks */
+        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 2, GD_UPG, GD_NW, false>), grid, block, k.lds, st, a);
+    else if (k.fam == GK_DIRECT)
+        hipLaunchKernelGGL((gemm_direct_kernel<FMT, 1, GD_UPG, GD_NW, false>), grid, block, k.lds, st, a);
+    else if (k.form == 2)
+        hipLaunchKernelGGL((gemm_kernel<FMT, 2>), grid, block, k.lds, st, a);
     else
-        hipLaunchKernelGGL((gemm_kernel<FMT, 1>), grid, dim3(256), smem, st, a);
+        hipLaunchKernelGGL((gemm_kernel<FMT, 1>), grid, block, k.lds, st, a);
 }
-static void gm_dispatch(int fmt, const GemmArgs& a, int KS, dim3 grid, size_t smem, hipStream_t st) {
-    switch (fmt) {
-        case FMT_BF16: gm_launch<FMT_BF16>(a, KS, grid, smem, st); break;
-        case FMT_F8: gm_launch<FMT_F8>(a, KS, grid, smem, st); break;
-        case FMT_Q4: gm_launch<FMT_Q4>(a, KS, grid, smem, st); break;
-        case FMT_Q2: gm_launch<FMT_Q2>(a, KS, grid, smem, st); break;
-        case FMT_Q4R: gm_launch<FMT_Q4R>(a, KS, grid, smem, st); break;
-        default: gm_launch<FMT_Q1>(a, KS, grid, smem, st); break;
+// the executor of every family: kf_gemm3.hip, kf_gemm2.hip, or this file's direct / paired / staged kernels
+static int gemm_run(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* ws) {
+    if (k.fam == GK_G3) return gemm3_run(st, k, a, ws);
+    if (k.fam == GK_G2) return gemm2_run(st, k, a);
+    switch (k.fmt) {
+        case FMT_BF16: gm_launch<FMT_BF16>(k, a, st); break;
+        case FMT_F8: gm_launch<FMT_F8>(k, a, st); break;
+        case FMT_Q4: gm_launch<FMT_Q4>(k, a, st); break;
+        case FMT_Q2: gm_launch<FMT_Q2>(k, a, st); break;
+        case FMT_Q4R: gm_launch<FMT_Q4R>(k, a, st); break;
+        default: gm_launch<FMT_Q1>(k, a, st); break;
     }
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 
-static const int gm_epb[7] = {8, 16, 32, 64, 128, 32, 32};
-struct GmWeight {
-    const unsigned char* w;
-    const uint16_t *zero, *step;
-    float qBias;
-    int M, K, fmt, gshift;
-};
-// 0 ok, 1 not eligible for the tile kernels, < 0 error
-static int gm_weight(const kf_weight* w, GmWeight& o) {
-    o.fmt = gm_fmt_of(w->type);
-    if (is_row_lut(w)) { /* 4-bit row codebooks unpack in registers like the Packed128 form; the 3- / 2-bit row forms are dequantised by the caller */
-        if (w->type != KF_Q4 || w->quant != KF_QUANT_ROW_LUT) return 1;
-        o.fmt = FMT_Q4R;
+GmWeight gm_operand(const kf_weight* w, const GemmKern& k) {
+    GmWeight g = gm_bf16(w->data, w->ne0, w->ne1);
+    g.qBias = (float)w->qBias;
+    if (k.fmt == FMT_Q4R) {
+        g.zero = w->gama + w->ne0 + w->ne1; /* the rows' tables */
+    } else if (k.fmt >= FMT_Q4) {
+        g.zero = w->gama + w->ne0 + w->ne1;
+        g.step = g.zero + (size_t)g.M * g.K / w->lGroup;
     }
-    if (o.fmt < 0 || w->qzeros || w->qscales) return 1;
-    o.M = w->ne0, o.K = w->ne1;
-    // K a multiple of 128 for every kernel; a multiple of 64 is enough for the direct kernel on the formats whose 64-element unit is made of
-    // whole blocks (bf16, f8, 4-bit) -- GPT-2's n_embd = 1600
-    if (o.K % 64 != 0 || o.K < GM_KT || o.M < 1 || (reinterpret_cast<uintptr_t>(w->data) & 15) != 0) return 1;
-    if (o.K % GM_KT != 0 && o.fmt > FMT_Q4 && o.fmt != FMT_Q4R) return 1;
-    if ((unsigned long long)o.M * (unsigned long long)(o.K / gm_epb[o.fmt]) >= (1ull << 32)) return 1;
-    o.w = reinterpret_cast<const unsigned char*>(w->data);
-    o.zero = o.step = nullptr, o.qBias = (float)w->qBias, o.gshift = 0;
-    if (o.fmt == FMT_Q4R) {
-        if (!w->gama) return KF_QUANT_ERR;
-        o.zero = w->gama + w->ne0 + w->ne1; /* the rows' tables */
-        if ((reinterpret_cast<uintptr_t>(o.zero) & 15) != 0) return 1;
-    } else if (o.fmt >= FMT_Q4) {
-        if (!w->gama || w->lGroup <= 0 || (w->lGroup % gm_epb[o.fmt]) != 0 || ((long)o.M * o.K) % w->lGroup != 0) return KF_QUANT_ERR;
-        const int bpg = w->lGroup / gm_epb[o.fmt];
-        if (bpg < 1 || (bpg & (bpg - 1)) != 0) return KF_QUANT_ERR;
-        o.gshift = __builtin_ctz(bpg);
-        o.zero = w->gama + w->ne0 + w->ne1;
-        o.step = o.zero + (size_t)o.M * o.K / w->lGroup;
-    }
-    return 0;
+    return g;
 }
-static void gm_base(GemmArgs& a, const GmWeight& g, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy) {
+static void gm_base(GemmArgs& a, const GemmKern& k, const GmWeight& g, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy) {
     memset(&a, 0, sizeof(a));
     a.w = g.w, a.zero = g.zero, a.step = g.step, a.qBias = g.qBias;
-    a.M = g.M, a.K = g.K, a.nBlk = g.K / gm_epb[g.fmt], a.gshift = g.gshift;
+    a.M = g.M, a.K = g.K, a.nBlk = g.K / GM_EPB[k.fmt], a.gshift = k.gshift;
     a.x = x, a.ldx = ldx, a.n = n, a.y = y, a.ldy = ldy, a.alpha = 1.0f, a.njobs = 1;
     a.rb_end[0] = a.rb_end[1] = a.rb_end[2] = (g.M + 31) / 32;
 }
-static bool gm_x_ok(const uint16_t* x, long long ldx) { return (ldx & 7) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
-constexpr long GD_FUSED_MAX = 2048; /* workgroups up to which the fused direct launches beat separate (staged) ones */
 
-// up to three matrices sharing x (Q, K, V) in ONE direct launch: KF_OK, 1 = not eligible (the caller launches them one by one), < 0 error
-int gemm_multi_launch(hipStream_t st, int n_w, const kf_weight* const* w, const uint16_t* x, long long ldx, int n, uint16_t* const* y) {
-    if (n_w < 2 || n_w > 3 || !gm_x_ok(x, ldx)) return 1;
-    GmWeight g[3];
-    long rbs = 0;
-    for (int i = 0; i < n_w; i++) {
-        const int rc = gm_weight(w[i], g[i]);
-        if (rc) return rc;
-        if (g[i].fmt != g[0].fmt || g[i].K != g[0].K || g[i].gshift != g[0].gshift) return 1;
-        rbs += (g[i].M + 31) / 32;
-    }
-    if (rbs * ((n + 31) / 32) > GD_FUSED_MAX) return 1;
+int gemm_multi_launch(hipStream_t st, const GemmKern& k, int n_w, const GmWeight* g, const uint16_t* x, long long ldx, int n, uint16_t* const* y) {
     GemmArgs a;
-    gm_base(a, g[0], x, ldx, n, y[0], g[0].M);
+    gm_base(a, k, g[0], x, ldx, n, y[0], g[0].M);
+    if (k.fam == GK_PAIRED) {
+        a.xw[0] = g[1].w, a.xzero[0] = g[1].zero, a.xstep[0] = g[1].step, a.xqBias[0] = g[1].qBias;
+        return gemm_run(st, k, a, nullptr);
+    }
     a.njobs = n_w;
     int end = 0;
     for (int i = 0; i < 3; i++) {
@@ -580,66 +537,15 @@ int gemm_multi_launch(hipStream_t st, int n_w, const kf_weight* const* w, const 
             a.xw[i - 1] = g[i].w, a.xzero[i - 1] = g[i].zero, a.xstep[i - 1] = g[i].step, a.xqBias[i - 1] = g[i].qBias, a.xM[i - 1] = g[i].M, a.xy[i - 1] = y[i],
                      a.xldy[i - 1] = g[i].M;
     }
-    if (n >= 64 && (long)end * ((n + 63) / 64) >= 256)
-        gm_dispatch(g[0].fmt, a, -2, dim3(end, (n + 63) / 64), 0, st);
-    else
-        gm_dispatch(g[0].fmt, a, 0, dim3(end, (n + 31) / 32), 0, st);
-    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+    return gemm_run(st, k, a, nullptr);
 }
 
-// act[n, M] = silu(x . gate^T) * (x . up^T) in one direct launch: KF_OK, 1 = not eligible, < 0 error
-int gemm_paired_launch(hipStream_t st, const kf_weight* gate, const kf_weight* up, const uint16_t* x, long long ldx, int n, uint16_t* act) {
-    if (!gm_x_ok(x, ldx)) return 1;
-    GmWeight g, u;
-    int rc = gm_weight(gate, g);
-    if (rc) return rc;
-    rc = gm_weight(up, u);
-    if (rc) return rc;
-    if (g.fmt != u.fmt || g.K != u.K || g.M != u.M || g.gshift != u.gshift) return 1;
-    if ((long)((g.M + 31) / 32) * ((n + 31) / 32) > GD_FUSED_MAX) return 1;
+int gemm_launch(hipStream_t st, const GemmKern& k, const GmWeight& g, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy, const uint16_t* bias, float alpha,
+                float beta, const uint16_t* residual, long long ldr, void* ws) {
     GemmArgs a;
-    gm_base(a, g, x, ldx, n, act, g.M);
-    a.xw[0] = u.w, a.xzero[0] = u.zero, a.xstep[0] = u.step, a.xqBias[0] = u.qBias;
-    gm_dispatch(g.fmt, a, -1, dim3((g.M + 31) / 32, (n + 31) / 32), 0, st);
-    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
-}
-
-// Returns KF_OK when launched, 1 when the shape is not eligible (the caller then loops the mat-vec), < 0 on error.
-int gemm_launch(hipStream_t st, const kf_weight* w, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy, const uint16_t* bias, float alpha,
-                float beta, const uint16_t* residual, long long ldr, void* ws, size_t ws_bytes) {
-    GmWeight g;
-    const int rc = gm_weight(w, g);
-    if (rc) return rc;
-    if (!gm_x_ok(x, ldx)) return 1;
-    const int M = g.M;
-    GemmArgs a;
-    gm_base(a, g, x, ldx, n, y, ldy);
+    gm_base(a, k, g, x, ldx, n, y, ldy);
     a.bias = bias, a.residual = residual, a.ldr = ldr, a.alpha = alpha, a.beta = beta;
-    const int ttiles = (n + GM_TOK - 1) / GM_TOK;
-    // prompt-sized batches on small matrices: the wave-independent kernel while its 32 x 32 workgroups fit ~2-3 rounds of the chip
-    // (measured crossover against the staged tiles, scratch/ub_gemm.py: 1024 rows up to n ~ 1024, 2048 up to ~ 600, 3072 up to ~ 400)
-    constexpr int direct_max = 1280;
-    int KS = ((long)((M + 127) / 128) * ttiles < 512) ? 2 : 1;
-    dim3 grid;
-    // bf16 operands (weights stored as bf16, or the resident dequantised copies of a long prompt): the global_load_lds tile kernels first from g3_first token rows --
-    // the crossover above was measured on the 4-bit in-register unpack; on bf16 the direct kernel took 64 us for 1024 x 2048 at 1024 rows
-    if (g.fmt == FMT_BF16 && n >= g_knobs.g3_first) {
-        const int rc3 = gemm3_launch(st, g.fmt, a, ws, ws_bytes);
-        if (rc3 != 1) return rc3;
-    }
-    if ((long)((M + 31) / 32) * ((n + 31) / 32) <= direct_max) {
-        KS = 0;
-        grid = dim3((M + 31) / 32, (n + 31) / 32);
-    } else {
-        const int rc3 = gemm3_launch(st, g.fmt, a); /* bf16 operands, >= 128 tiles of 256 x 256: the global_load_lds tile kernel (kf_gemm3.hip) */
-        if (rc3 != 1) return rc3;
-        const int rc2 = gemm2_launch(st, g.fmt, a); /* large batches: the producer / consumer tile kernel when it applies */
-        if (rc2 != 1) return rc2;
-        const int rows_per_wg = 32 * (4 / KS);
-        grid = dim3((M + rows_per_wg - 1) / rows_per_wg, ttiles);
-    }
-    gm_dispatch(g.fmt, a, KS, grid, (size_t)2 * GM_TOK * GM_XS * sizeof(uint16_t), st);
-    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+    return gemm_run(st, k, a, ws);
 }
 
 }  // namespace kf

@@ -20,10 +20,6 @@
 
 namespace kf {
 
-constexpr int G2_BM = 128, G2_BN = 256, G2_BK = 64;
-constexpr int G2_LS = G2_BK + 8; /* LDS row, bf16 elements */
-constexpr size_t G2_STAGE = (size_t)(G2_BM + G2_BN) * G2_LS * sizeof(uint16_t);
-
 template <int FMT>
 __global__ void __launch_bounds__(512) gemm2_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -155,15 +151,12 @@ __global__ void __launch_bounds__(512) gemm2_kernel(const GemmArgs a) {
     for (int rb = 0; rb < 2; rb++) gemm_epilogue<4>(acc[rb], a, tok0 + th * 128, row0 + rh * 64 + rb * 32, r, h);
 }
 
-// KF_OK launched, 1 = not for this kernel
-int gemm2_launch(hipStream_t st, int fmt, const GemmArgs& a) {
-    constexpr int min_wg = 128; /* fewer workgroups than this: the staged / direct tiles of kf_gemm.hip fill the chip better */
-    if ((fmt != FMT_Q4 && fmt != FMT_BF16 && fmt != FMT_F8) || a.K % G2_BK != 0 || a.n < G2_BN) return 1;
-    const dim3 grid((a.M + G2_BM - 1) / G2_BM, (a.n + G2_BN - 1) / G2_BN);
-    if ((long)grid.x * grid.y < min_wg) return 1;
-    const size_t smem = 2 * G2_STAGE;
+// tiles of G2_BM rows x G2_BN tokens (kf_gemm_plan.h tile_plan: 4-bit, bf16, f8; K a multiple of G2_BK, >= G2_BN rows)
+int gemm2_run(hipStream_t st, const GemmKern& k, const GemmArgs& a) {
+    const dim3 grid(k.gx, k.gy);
+    const size_t smem = k.lds;
     static bool raised[3] = {false, false, false};
-    switch (fmt) {
+    switch (k.fmt) {
         case FMT_Q4:
             if (!raised[0]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<FMT_Q4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), raised[0] = true;
             hipLaunchKernelGGL(gemm2_kernel<FMT_Q4>, grid, dim3(512), smem, st, a);

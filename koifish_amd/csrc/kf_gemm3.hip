@@ -25,24 +25,7 @@
 
 namespace kf {
 
-constexpr int G3_BM = 256, G3_BN = 256, G3_BK = 64;
-// the workgroup tile: BM rows x BN tokens, NW waves as 2 (rows) x NW / 2 (tokens).  Big = the 256 x 256 tile of the header (8 waves, 128 x 64 outputs each, 128 KiB of
-// LDS: one workgroup per CU); Small = 128 x 128 on 4 waves (64 x 64 outputs each, 64 KiB: two workgroups per CU) for products with too few 256 x 256 tiles to fill the
-// chip -- the o_proj / down projections of a 1-2 k token prompt (M = 1024: 32 big tiles), with the split-K form below on top.  K-contiguous operands only.
-template <int BM_, int BN_, int NW_>
-struct G3Cfg {
-    static constexpr int BM = BM_, BN = BN_, NW = NW_, WN = NW_ / 2, MT = BM_ / 32, NT = BN_ / (16 * (NW_ / 2));
-    static constexpr int NIA = BM_ / (8 * NW_), NIB = BN_ / (8 * NW_); /* global_load_lds instructions per wave, operand and k-step (8 rows of 128 bytes each) */
-    static constexpr int STAGE = (BM_ + BN_) * G3_BK * 2, NTH = 64 * NW_, WGS_PER_CU = (160 * 1024) / (2 * STAGE);
-};
-using G3Big = G3Cfg<256, 256, 8>;
-using G3Small = G3Cfg<128, 128, 4>;
-// round 4: products whose 128 x 128 tiles do not fill the chip either (M = 1024 at 1-2 k tokens: 64-128 of them; split-K S = 4 measured 37.8 us against 27 plain: three
-// 64 KiB partials per tile through memory) get MORE, SMALLER tiles instead of k-pieces: 64 x 128 (48 KiB of LDS: three workgroups per CU) and 64 x 64 (32 KiB: five)
-using G3Mid = G3Cfg<64, 128, 4>;
-using G3Tiny = G3Cfg<64, 64, 4>;
-// 192 x 256: a product whose 256 x 256 tiles number 160-255 (gate | up of a 0.6B model at 2047 tokens: 24 x 8 = 192 tiles on 256 CUs) becomes 32 x 8 = 256 tiles of 3/4 the work
-using G3Wide = G3Cfg<192, 256, 8>;
+// G3Cfg (kf_gemm_plan.h): the workgroup tiles -- 256 x 256 (Big), 128 x 128 (Small), 64 x 128 (Mid), 64 x 64 (Tiny), 192 x 256 (Wide)
 
 // one operand tile (256 rows x 2 BK bytes) = BK / 2 wave instructions of 1 KiB; wave `wid` issues BK / 16 of them.  BK = 64: 8 rows per instruction, chunk c of row r
 // at position c ^ ((r >> 1) & 7); BK = 32: 16 rows per instruction (64-byte rows), chunk c at position c ^ ((r >> 2) & 3) -- either way a fragment read
@@ -94,7 +77,7 @@ __device__ __forceinline__ bf16x8 g3_frag_km(const unsigned char* tile, int rowb
 
 // k-steps kt0 .. kt1 - 1 (of BK) of the output tile at (m0, t0) accumulated into acc (the caller zeroes it).  NST = 128 KiB / stage LDS buffers: the loads of step
 // kt + NST - 1 are issued while step kt is multiplied and drained with a COUNTED s_waitcnt vmcnt + one raw s_barrier per step (a __syncthreads() would drain the loads
-// in flight): BK = 64 -> 2 buffers; BK = 32 -> 4 buffers, three steps in flight (measured slower, see g3_go).  Also measured and dropped: the barrier moved into
+// in flight): BK = 64 -> 2 buffers; BK = 32 -> 4 buffers, three steps in flight (measured slower, see g3_run_c).  Also measured and dropped: the barrier moved into
 // the middle of the step's MFMA stream (the last 16 MFMAs of a step held back behind it, the first fragments of the next step read under them): 979 TFLOP/s against
 // 1000 on the forward shapes at 246 VGPRs, and the k-major forms spill; four waves of 128 x 128 outputs each (256 accumulator AGPRs, a third less LDS traffic per MFMA,
 // the vendor library's shape): the compiler fills all 512 registers and still spills inside the loop, 228 TFLOP/s -- that form needs a hand-scheduled loop.
@@ -463,7 +446,6 @@ __global__ void __launch_bounds__(C::NTH, C::WGS_PER_CU * C::NW / 4) gemm3_sk_ke
 // The flag value of one split-K launch.  Launches outside a capture take a fresh value each (a process-wide counter from 2 up), so the flags of the launch before need
 // no clearing -- the memset was a dependent 2-3 us node in front of every such product; a flag area seen for the first time is cleared once.  A launch that is being
 // CAPTURED is replayed with the arguments it was recorded with: it keeps the clearing node and the value 1.
-constexpr size_t G3_SK_FLAG_BYTES = 8192; /* up to 2048 resident workgroups (64 x 64 tiles, eight per CU) */
 static std::mutex g_sk_mu;
 static uint32_t g_sk_epoch = 1;
 static const void* g_sk_seen[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -489,11 +471,11 @@ static int g3_sk_epoch(hipStream_t st, uint32_t* flags, int n, uint32_t* epoch) 
     return KF_OK;
 }
 
-// KF_OK launched, 1 = not for this kernel (the caller's other tile kernels take the shape), < 0 error.  bf16 "weights" only: quantised ones are dequantised first.
+// One plan's launch (kf_gemm_plan.h g3_kern: plain, or the split-K form with the plan's P, S, kp, R).  bf16 "weights" only: quantised ones are dequantised first.
 // BK = 32 (4 LDS buffers, three steps in flight) was measured 8-10 % slower than BK = 64 (2 buffers) on every shape, forward and backward: the per-step costs
 // (barrier, counted wait, loop) double, and the loop is not waiting for memory.  Only BK = 64 is instantiated.
 template <bool AKM, bool BKM, class C>
-static int g3_go_c(hipStream_t st, const GemmArgs& a, long nwg, void* ws, size_t ws_bytes, long min_plain) {
+static int g3_run_c(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* ws) {
     constexpr int BK = G3_BK, SMEM = 2 * C::STAGE;
     static int attr_set = 0;
     if (!attr_set && SMEM > 64 * 1024) {
@@ -501,141 +483,72 @@ static int g3_go_c(hipStream_t st, const GemmArgs& a, long nwg, void* ws, size_t
         if (hipFuncSetAttribute((const void*)gemm3_sk_kernel<AKM, BKM, BK, C>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess) return KF_HIP_CHECK;
         attr_set = 1;
     }
-    // split-K when the tiles are fewer than 4/5 of the resident workgroups, the caller lent the workspace, and the pieces stay >= 512 deep in k
-    const int G = 256 * C::WGS_PER_CU, nkt = a.K / BK, min_steps = 512 / BK;
-    if (ws && ws_bytes >= gemm3_sk_ws_bytes() && 5 * nwg < 4 * G) {
+    if (k.sk) {
         G3SkArgs s;
         // the flags live in the LAST 8 KiB of the lent workspace whatever the tile configuration (behind the partial tiles of THIS configuration they moved with it,
         // and another configuration's fp32 partials could overwrite words already marked "seen" with values that pass for an epoch)
         static_assert((size_t)256 * C::WGS_PER_CU * C::BM * C::BN * 4 <= (size_t)256 * G3_BM * G3_BN * 4 && 256 * C::WGS_PER_CU * 4 <= G3_SK_FLAG_BYTES, "partials and flags fit the lent workspace");
         s.ws = (float*)ws, s.flags = (uint32_t*)((char*)ws + gemm3_sk_ws_bytes() - G3_SK_FLAG_BYTES);
-        s.P = (int)nwg, s.S = G / s.P, s.kp = 0, s.R = 1;
-        int nlaunch;
-        if (s.S >= 2) {
-            while (s.S > 1 && nkt / s.S < min_steps) s.S--;
-            nlaunch = s.P * s.S;
-        } else {
-            s.kp = (int)(((long long)nkt * s.P + G / 2) / G);
-            nlaunch = G;
-            const long long T = (long long)s.P * (nkt - s.kp);
-            s.R = (int)((T + (G - s.P) - 1) / (G - s.P));
-            if (nkt - s.kp < 1 || nkt < 4 * min_steps || T * 2 >= (1LL << 31)) s.S = 0;
-        }
-        if (s.S >= 1 && (s.S >= 2 || s.kp > 0)) {
-            if (g3_sk_epoch(st, s.flags, G, &s.epoch) != KF_OK) return KF_HIP_CHECK;
-            hipLaunchKernelGGL((gemm3_sk_kernel<AKM, BKM, BK, C>), dim3(nlaunch), dim3(C::NTH), SMEM, st, a, s);
-            return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
-        }
+        s.P = k.P, s.S = k.S, s.kp = k.kp, s.R = k.R;
+        if (g3_sk_epoch(st, s.flags, 256 * C::WGS_PER_CU, &s.epoch) != KF_OK) return KF_HIP_CHECK;
+        hipLaunchKernelGGL((gemm3_sk_kernel<AKM, BKM, BK, C>), dim3(k.gx), dim3(C::NTH), SMEM, st, a, s);
+    } else {
+        hipLaunchKernelGGL((gemm3_kernel<AKM, BKM, BK, C>), dim3(k.gx), dim3(C::NTH), SMEM, st, a);
     }
-    if (nwg < min_plain) return 1;
-    hipLaunchKernelGGL((gemm3_kernel<AKM, BKM, BK, C>), dim3((unsigned)nwg), dim3(C::NTH), SMEM, st, a);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
-template <bool AKM, bool BKM>
-static int g3_go(hipStream_t st, const GemmArgs& a, long nwg, void* ws, size_t ws_bytes) {
-    return g3_go_c<AKM, BKM, G3Big>(st, a, nwg, ws, ws_bytes, 64);
-}
-size_t gemm3_sk_ws_bytes() { return (size_t)256 * G3_BM * G3_BN * 4 + G3_SK_FLAG_BYTES; }
-int gemm3_launch(hipStream_t st, int fmt, const GemmArgs& a, void* ws, size_t ws_bytes) {
-    if (fmt != FMT_BF16 || a.K % G3_BK != 0 || a.K < G3_BK) return 1;
-    if ((a.ldx & 7) != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.w) & 15) != 0 || (a.K & 7) != 0) return 1;
-    if (a.n >= G3_BN && a.M >= G3_BM) {
-        const long nwg = (long)((a.M + G3_BM - 1) / G3_BM) * ((a.n + G3_BN - 1) / G3_BN);
-        // (M 1024 x K 3072 at 8192 rows, 128 big tiles: 83 -> 57 us = 890 TFLOP/s on the small ones; from 400 big tiles up the big tile is 8-12 % faster)
-        if (nwg >= 160) return g3_go<false, false>(st, a, nwg, nullptr, 0); /* fewer big tiles than that: four times as many small ones fill the chip better */
+int gemm3_run(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* ws) {
+    if (k.akm) { /* the backward's k-major forms (kf_gemm_plan.h gemm_plan_backward: A always k-major) */
+        if (k.bkm) return k.form == G3_SMALL ? g3_run_c<true, true, G3Small>(st, k, a, ws) : g3_run_c<true, true, G3Big>(st, k, a, ws);
+        return k.form == G3_SMALL ? g3_run_c<true, false, G3Small>(st, k, a, ws) : g3_run_c<true, false, G3Big>(st, k, a, ws);
     }
-    // 128 x 128 tiles, two workgroups per CU: bf16 products of 1-4 k rows whose M is 1024-3072 (M 1024 x K 2048 at 2048 rows: 36.9 -> 27.4 us, 3072 x 1024: 35.6 -> 23.9;
-    // 4096 rows: 583-656 TFLOP/s).  For QUANTISED weights of that size dequantise + this kernel only ties with the in-register-unpack kernels (the 5 us dequantise pass
-    // and, with split-K, the flag memset eat the gain): kf_linear keeps those on kf_gemm.hip.
-    if (a.n < 128 || a.M < 128) return 1;
-    const long nwg = (long)((a.M + 127) / 128) * ((a.n + 127) / 128);
-    if (nwg < 32 && (g_knobs.g3_tiles < 3 || (long)((a.M + 63) / 64) * ((a.n + 63) / 64) < 64)) return 1;
-    if (nwg < 256 && g_knobs.g3_tiles >= 1 && !a.swiglu && !a.qkrope) { /* fewer 128 x 128 tiles than CUs: twice or four times as many smaller ones, no k-pieces */
-        // with the caller's workspace these go in k-pieces when even the small tiles leave CUs idle (1024 rows x K 2048-3072 at 512 tokens: 128 tiles of 64 x 64, each a
-        // 32-48 step k-loop of ~0.7 us per step on its own CU: 31 us; a 16 KiB partial per piece is cheap where the 64 KiB ones of the 128 x 128 tile were not)
-        const long nmid = (long)((a.M + 63) / 64) * ((a.n + 127) / 128);
-        if (nmid >= g_knobs.g3_mid_min || g_knobs.g3_tiles < 3) return nmid >= 64 ? g3_go_c<false, false, G3Mid>(st, a, nmid, ws, ws_bytes, 64) : 1;
-        return g3_go_c<false, false, G3Tiny>(st, a, (long)((a.M + 63) / 64) * ((a.n + 63) / 64), ws, ws_bytes, 64);
+    switch (k.form) {
+        case G3_SMALL: return g3_run_c<false, false, G3Small>(st, k, a, ws);
+        case G3_MID: return g3_run_c<false, false, G3Mid>(st, k, a, ws);
+        case G3_TINY: return g3_run_c<false, false, G3Tiny>(st, k, a, ws);
+        case G3_WIDE: return g3_run_c<false, false, G3Wide>(st, k, a, ws);
+        default: return g3_run_c<false, false, G3Big>(st, k, a, ws);
     }
-    return g3_go_c<false, false, G3Small>(st, a, nwg, nullptr, 0, 128);
 }
-// y[n, M] = alpha * sum_k B(k, tok) A(k, m) + beta * y (+ bias) with either operand stored K-MAJOR: akm: A = w[K][lda] (element (k, m) at k * lda + m), else w[M][K];
-// bkm: B = x[K][ldb], else x[n][ldb].  The two GEMMs of SLP::Back without a transpose of anything:  delta[n, IC] = deltaIn[n, OC] . W[OC, IC]  (A = W k-major),
-// gW[OC, IC] += deltaIn^T . inp  (A = inp[n][IC] k-major, B = deltaIn[n][OC] k-major, contraction over the n token rows).  1 = shape not served.
-// ws (gemm3_sk_ws_bytes() bytes, 16-byte aligned) lends the stream-K form its partial-tile slots; NULL = one workgroup per tile only.
-int gemm3_km_launch(hipStream_t st, const uint16_t* A, long long lda, bool akm, const uint16_t* B, long long ldb, bool bkm, int n, int M, int K, uint16_t* y, long long ldy,
-                    const uint16_t* bias, float alpha, float beta, void* ws, size_t ws_bytes) {
-    if (K % G3_BK != 0 || K < G3_BK || n < G3_BN || M < G3_BM || (M & 7) || (n & 7) || (lda & 7) || (ldb & 7)) return 1;
-    if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15)) return 1;
-    const long nwg = (long)((M + G3_BM - 1) / G3_BM) * ((n + G3_BN - 1) / G3_BN);
+// y[n, M] = alpha * sum_k B(k, tok) A(k, m) + beta * y with A = w[K][lda] (element (k, m) at k * lda + m) and B = x[K][ldb] (k.bkm) or x[n][ldb].  The two GEMMs of
+// SLP::Back without a transpose of anything:  delta[n, IC] = deltaIn[n, OC] . W[OC, IC]  (A = W k-major), gW[OC, IC] += deltaIn^T . inp  (A = inp[n][IC] k-major,
+// B = deltaIn[n][OC] k-major, contraction over the n token rows).  ws (gemm3_sk_ws_bytes() bytes, 16-byte aligned) lends the split-K form its partial-tile slots.
+int gemm3_km_launch(hipStream_t st, const GemmKern& k, const uint16_t* A, long long lda, const uint16_t* B, long long ldb, int n, int M, int K, uint16_t* y, long long ldy,
+                    float alpha, float beta, void* ws) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.w = reinterpret_cast<const unsigned char*>(A), a.M = M, a.K = K, a.x = B, a.ldx = ldb, a.n = n, a.y = y, a.ldy = ldy, a.bias = bias, a.alpha = alpha, a.beta = beta;
+    a.w = reinterpret_cast<const unsigned char*>(A), a.M = M, a.K = K, a.x = B, a.ldx = ldb, a.n = n, a.y = y, a.ldy = ldy, a.alpha = alpha, a.beta = beta;
     a.ldr = lda; /* the k-major A operand's row stride */
-    if (!akm && lda != K) return 1; /* the row-major A form reads rows of K */
-    // big tiles that fill less than 4/5 of the CUs: 128 x 128 tiles instead when they make (nearly) whole rounds of the 512 resident workgroups, or -- with the
-    // workspace -- their split-K form (partials of 64 KiB instead of 256 KiB, twice the workgroups)
-    // (measured: Qwen3-0.6B training step 99.3 -> 95.7 ms with the first rule alone, -> 87.2 ms with both; GPT2-1558M 166.0 -> 163.7 -> 161.2 ms)
-    const long nws = (long)((M + 127) / 128) * ((n + 127) / 128), rounds = (nws + 511) / 512;
-    const bool small = 5 * nwg < 4 * 256 && akm && (20 * nws >= 17 * rounds * 512 || (ws && ws_bytes >= gemm3_sk_ws_bytes() && 5 * nws < 4 * 512));
-    if (small) return bkm ? g3_go_c<true, true, G3Small>(st, a, nws, ws, ws_bytes, 1) : g3_go_c<true, false, G3Small>(st, a, nws, ws, ws_bytes, 1);
-    if (akm && bkm) return g3_go<true, true>(st, a, nwg, ws, ws_bytes);
-    if (akm) return g3_go<true, false>(st, a, nwg, ws, ws_bytes);
-    if (bkm) return g3_go<false, true>(st, a, nwg, ws, ws_bytes);
-    return g3_go<false, false>(st, a, nwg, ws, ws_bytes);
+    return gemm3_run(st, k, a, ws);
 }
 
 // up to three bf16 matrices stacked along M in ONE contiguous buffer (the caller dequantised them back to back: Q | K | V, or gate | up), each a multiple of 256
-// rows, multiplied by the same x in one launch; matrix j's rows go to y[j] (row stride M[j]).  1 = shape not served.
-// rope != NULL (n_w == 3: Q | K | V, head_dim 128): q/k-norm + RoPE in the epilogue (GemmArgs::qkrope); served on the 128 x 128 tile only -- 1 otherwise, the caller then
-// runs the plain stacked launch and qknorm_rope_launch
-int gemm3_multi_launch(hipStream_t st, int n_w, const uint16_t* Wcat, const int* M, int K, const uint16_t* x, long long ldx, int n, uint16_t* const* y, const G3Rope* rope) {
-    if (n_w < 2 || n_w > 3 || K % G3_BK != 0 || K < G3_BK || n < G3_BN || (ldx & 7) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(Wcat) & 15)) return 1;
+// rows, multiplied by the same x in one launch; matrix j's rows go to y[j] (row stride M[j]).  rope (Q | K | V, head_dim 128, the 128 x 128 tile): q/k-norm + RoPE in the
+// epilogue (GemmArgs::qkrope)
+int gemm3_multi_launch(hipStream_t st, const GemmKern& k, int n_w, const uint16_t* Wcat, const int* M, int K, const uint16_t* x, long long ldx, int n, uint16_t* const* y,
+                       const G3Rope* rope) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     int tot = 0;
     for (int j = 0; j < 3; j++) {
-        if (j < n_w) {
-            if (M[j] < G3_BM || M[j] % G3_BM != 0) return 1;
-            tot += M[j];
-        }
+        if (j < n_w) tot += M[j];
         a.rb_end[j] = tot / 32;
         if (j >= 1 && j < n_w) a.xy[j - 1] = y[j], a.xldy[j - 1] = M[j];
     }
     a.njobs = n_w;
     a.w = reinterpret_cast<const unsigned char*>(Wcat), a.M = tot, a.K = K, a.x = x, a.ldx = ldx, a.n = n, a.y = y[0], a.ldy = M[0], a.alpha = 1.0f, a.beta = 0.0f;
-    const long nwg = (long)(tot / G3_BM) * ((n + G3_BN - 1) / G3_BN);
-    if (nwg < 64 && (long)(tot / 128) * ((n + 127) / 128) < 64) return 1;
-    // fewer than 160 big tiles (Q | K | V of a 0.6B model at 2047 tokens: 128): four times as many 128 x 128 tiles fill the chip better (2047-token prompt 8.20 -> 7.84 ms;
-    // gate | up, 192 big tiles, is better left on them: 7.93 ms with both small)
-    if (rope) {
-        if (n_w != 3 || M[0] % 128 != 0 || M[1] % 128 != 0 || ((M[0] | M[1] | M[2]) & 3) || (reinterpret_cast<uintptr_t>(y[0]) & 7) || (reinterpret_cast<uintptr_t>(y[1]) & 7)) return 1;
-        a.qkrope = 1, a.qk_norm[0] = rope->wq, a.qk_norm[1] = rope->wk, a.rope_table = rope->table, a.rope_pos0 = rope->pos0, a.rope_seq = rope->seq_len, a.qk_eps = rope->eps;
-        return g3_go_c<false, false, G3Small>(st, a, (long)(tot / 128) * ((n + 127) / 128), nullptr, 0, 1); /* always the head-sized tile */
-    }
-    if (nwg < 160) return g3_go_c<false, false, G3Small>(st, a, (long)(tot / 128) * ((n + 127) / 128), nullptr, 0, 1);
-    return g3_go<false, false>(st, a, nwg, nullptr, 0);
+    if (rope) a.qkrope = 1, a.qk_norm[0] = rope->wq, a.qk_norm[1] = rope->wk, a.rope_table = rope->table, a.rope_pos0 = rope->pos0, a.rope_seq = rope->seq_len, a.qk_eps = rope->eps;
+    return gemm3_run(st, k, a, nullptr);
 }
 
 // gate | up dequantised INTERLEAVED in blocks of 16 rows (dequant_launch ilv_n = 2) x the same x, SwiGLU in the epilogue: act[n, ffn] in one launch (the stacked route
-// wrote both projections and ran swiglu_kernel over them: 12 us and 38 MB of traffic per layer of a 2047-token prompt).  1 = shape not served.
-int gemm3_swiglu_launch(hipStream_t st, const uint16_t* Wilv, int ffn, int K, const uint16_t* x, long long ldx, int n, uint16_t* act) {
-    const int M = 2 * ffn;
-    if (ffn % 16 != 0 || M % G3_BM != 0 || K % G3_BK != 0 || K < G3_BK || n < G3_BN || (ldx & 7) || (ffn & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(Wilv) & 15) ||
-        (reinterpret_cast<uintptr_t>(act) & 7))
-        return 1;
+// wrote both projections and ran swiglu_kernel over them: 12 us and 38 MB of traffic per layer of a 2047-token prompt)
+int gemm3_swiglu_launch(hipStream_t st, const GemmKern& k, const uint16_t* Wilv, int ffn, int K, const uint16_t* x, long long ldx, int n, uint16_t* act) {
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.njobs = 1, a.swiglu = 1;
-    a.w = reinterpret_cast<const unsigned char*>(Wilv), a.M = M, a.K = K, a.x = x, a.ldx = ldx, a.n = n, a.y = act, a.ldy = ffn, a.alpha = 1.0f, a.beta = 0.0f;
-    const long nwg = (long)(M / G3_BM) * ((n + G3_BN - 1) / G3_BN);
-    if (nwg < 64 && (long)(M / 128) * ((n + 127) / 128) < 64) return 1;
-    const long nws = (long)(M / 128) * ((n + 127) / 128), nww = (long)(M / 192) * ((n + G3_BN - 1) / G3_BN);
-    const bool wide_ok = g_knobs.g3_wide && M % 192 == 0 && nww <= 256;
-    // fewer than 160 big tiles: four times as many 128 x 128 ones -- unless those spill into a second round of the 512 resident workgroups and the 192 x 256 ones make one round
-    if (nwg < 160 && !(wide_ok && nws > 512 && nww >= 160)) return g3_go_c<false, false, G3Small>(st, a, nws, nullptr, 0, 1);
-    if (wide_ok && nwg < 256) return g3_go_c<false, false, G3Wide>(st, a, nww, nullptr, 0, 1);
-    return g3_go<false, false>(st, a, nwg, nullptr, 0);
+    a.w = reinterpret_cast<const unsigned char*>(Wilv), a.M = 2 * ffn, a.K = K, a.x = x, a.ldx = ldx, a.n = n, a.y = act, a.ldy = ffn, a.alpha = 1.0f, a.beta = 0.0f;
+    return gemm3_run(st, k, a, nullptr);
 }
 
 }  // namespace kf

@@ -1,15 +1,11 @@
-// kf_gemm_common.h -- pieces shared by the token-batch GEMM kernels (kf_gemm.hip, kf_gemm2.hip)
+// kf_gemm_common.h -- pieces shared by the token-batch GEMM kernels (kf_gemm.hip, kf_gemm2.hip, kf_gemm3.hip)
 #pragma once
-#include "kf_kernels.h"
+#include "kf_gemm_plan.h"
 
 namespace kf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int GM_TOK = 128;         /* tokens per workgroup tile (4 MFMA column blocks) */
-constexpr int GM_KT = 128;          /* k per staged x tile */
-constexpr int GM_XS = GM_KT + 8;    /* padded LDS row in bf16 elements: 272 B, ds_read_b128 of 32 rows is conflict-free */
 
 struct GemmArgs {
     const unsigned char* w;
@@ -151,9 +147,8 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TB], const Gem
     }
 }
 
-// kf_gemm2.hip: large-batch tile kernel; KF_OK launched, 1 = not for this kernel
-int gemm2_launch(hipStream_t st, int fmt, const GemmArgs& a);
-// kf_gemm3.hip: 256 x 256 x 64 bf16 tiles staged by global_load_lds; KF_OK launched, 1 = not for this kernel
-int gemm3_launch(hipStream_t st, int fmt, const GemmArgs& a, void* ws = nullptr, size_t ws_bytes = 0); /* ws: lends the 128 x 128 form its split-K slots (gemm3_sk_ws_bytes) */
+// the executors of a plan's kernel family (GemmKern): kf_gemm2.hip's producer / consumer tiles, kf_gemm3.hip's global_load_lds tiles (ws: the split-K slots)
+int gemm2_run(hipStream_t st, const GemmKern& k, const GemmArgs& a);
+int gemm3_run(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* ws);
 
 }  // namespace kf

@@ -85,25 +85,7 @@ int gemv_lpr_log2_fmt(int fmt, int K, long rows); /* the same per storage (1-bit
 int gemv_fmt_of(const kf_weight* w);    /* FMT_* of a weight, < 0: not served by the mat-vec kernel */
 void argmax_finish_launch(hipStream_t st, const float* val, const int* idx, int n, int32_t* d_argmax, int32_t* d_state, int32_t* d_tokens_out);
 
-// ---- token-batch GEMM on MFMA (kf_gemm.hip): KF_OK launched, 1 = shape not eligible (caller loops the mat-vec), < 0 error
-// the 256 x 256 tile kernel on K-MAJOR operands (kf_gemm3.hip): the two GEMMs of SLP::Back without transposes.  1 = shape not served
-int gemm3_km_launch(hipStream_t st, const uint16_t* A, long long lda, bool akm, const uint16_t* B, long long ldb, bool bkm, int n, int M, int K, uint16_t* y, long long ldy,
-                    const uint16_t* bias, float alpha, float beta, void* ws, size_t ws_bytes);
-size_t gemm3_sk_ws_bytes();
-struct G3Rope { /* ROPE::cuInfer folded into the stacked Q | K | V launch's epilogue (kf_gemm3.hip g3_epilogue_qkrope) */
-    const uint16_t *wq, *wk; /* q / k norm weights [128] or NULL */
-    const float* table;      /* RoPE (cos, sin) table or NULL */
-    int pos0;
-    float eps;
-    int seq_len; /* > 0: rows are sequences of seq_len tokens back to back, positions pos0 .. pos0 + seq_len - 1 in each */
-};
-int gemm3_multi_launch(hipStream_t st, int n_w, const uint16_t* Wcat, const int* M, int K, const uint16_t* x, long long ldx, int n, uint16_t* const* y, const G3Rope* rope = nullptr);
-int gemm3_swiglu_launch(hipStream_t st, const uint16_t* Wilv, int ffn, int K, const uint16_t* x, long long ldx, int n, uint16_t* act); /* kf_gemm3.hip */
-int gemm_launch(hipStream_t st, const kf_weight* w, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy, const uint16_t* bias, float alpha,
-                float beta, const uint16_t* residual, long long ldr, void* ws = nullptr, size_t ws_bytes = 0); /* ws: split-K slots of the small bf16 tiles (gemm3_sk_ws_bytes) */
-
-int gemm_multi_launch(hipStream_t st, int n_w, const kf_weight* const* w, const uint16_t* x, long long ldx, int n, uint16_t* const* y);
-int gemm_paired_launch(hipStream_t st, const kf_weight* gate, const kf_weight* up, const uint16_t* x, long long ldx, int n, uint16_t* act);
+// ---- token-batch GEMM on MFMA: kf_gemm_plan.h (the rule and the launchers)
 
 // ---- attention (kf_attn.hip)
 struct AttnArgs {
@@ -142,18 +124,12 @@ int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t*
 struct Knobs {
     int q4_perm = 1;      /* 4-bit mat-vec through the register-table lookup (0: the arithmetic form; same bits) */
     int q2_tab = 1;       /* 2-bit mat-vec through the LDS selector table (0: the arithmetic form; same bits) */
-    int g3_tiles = 3;     /* smallest bf16 tile gemm3_launch may pick: 0 = 128 x 128 only (round 3), 1 = + 64 x 128, 3 = + 64 x 64 (kf_gemm3.hip) */
-    int resident_min = 320;  /* token rows from which the token-batch routes use RESIDENT dequantised copies (kf_set_dequant_arena) + the bf16 tile kernels; without an arena: 1024 */
     int attn_pair_min = 256;  /* prompt tokens from which kf_attn_prefill takes its paired two-key-half form (when there is about one workgroup per CU or fewer) */
-    int g3_wide = 1;      /* gate | up + SwiGLU on 192 x 256 tiles when the 256 x 256 ones would leave CUs idle */
-    int g3_mid_min = 192; /* 64 x 128 tiles from this many of them, 64 x 64 below */
     int attn_gq_split = 4; /* canonical decode attention of a GQA-8 model: workgroups per (kv-head, slice), 2 or 4 */
-    int g3_first = 256;   /* token rows from which bf16 operands try the kf_gemm3.hip tile kernels before the 32 x 32 direct kernel */
     int q1_tab = 1;       /* 1-bit mat-vec through the LDS selector table (0: the per-bit select form; same bits) */
     long gemv_waves = 0;  /* > 0: waves a mat-vec launch aims for (0: the launcher's rule) */
     int gemv_stream = 1;  /* buffer-load form of the long mat-vec launches (0: off) */
     int gemv_xf2 = 1;     /* canonical 4-bit rows too long for fp32 activations in 48 KiB of LDS: two windows of half the block columns (0: bf16 activations, widened per product) */
-    int gemm_min = 8;     /* token rows from which the MFMA tile kernels replace the per-token mat-vec loop */
 };
 extern Knobs g_knobs;
 // ---- the persistent decode engine: one sequence on every CU (kf_engine.hip)

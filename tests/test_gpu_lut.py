@@ -150,6 +150,10 @@ def test_rejects_malformed(ctx, O):
     d.ne1 = 48                              # rows must be whole 16-byte blocks
     assert ctx.hip.kf_linear(ctx.h, C.byref(d), x.data_ptr(), y.data_ptr(), None, 1, 1.0, 0.0, 0, None) == -2000
     d = dw.desc()
+    d.gama += 2                             # the rows' tables (gama + ne0 + ne1) must be 16-byte aligned, whatever the batch
+    for n in (1, 64):
+        assert ctx.hip.kf_linear(ctx.h, C.byref(d), x.data_ptr(), y.data_ptr(), None, n, 1.0, 0.0, 0, None) == -2000
+    d = dw.desc()
     d.gama = None
     assert ctx.hip.kf_dequant(ctx.h, C.byref(d), y.data_ptr()) == -701
 
