@@ -205,9 +205,12 @@ int kf_tp_pick(kf_ctx* ctx, const kf_tp_comm* comm, int32_t* d_state, int32_t* d
  * (src/Manifold/SparseNeuron.cpp:20-29; Neuron.hpp:265-285: one int per FFN row, 1 = hot):  y[i] = (hot[i] == 1 ? W[i,:].x : 0) (+ bias[i]).
  * The mask is turned into a list of hot rows once (kf_hot_rows: ascending indices, their number to *d_count) and the products walk that list, so
  * cold rows cost no HBM traffic: algorithmic bytes = n_hot / ne0 of the dense product's.  Hot rows carry every bit of kf_linear's rows.
- * kf_norm_gateup_swiglu_masked is the FFN form (FFN::cuInfer with the mask on the gate / up rows): cold rows of `act` are SwiGLU(0, 0) = 0. */
+ * kf_norm_gateup_swiglu_masked is the FFN form (FFN::cuInfer with the mask on the gate / up rows): cold rows of `act` are SwiGLU(0, 0) = 0.
+ * kf_zero_cold_columns is the token-batch form (FFN::cuFlow, after kf_gateup_swiglu_batch): y[r][i] = 0 for every row r < rows where d_hot[i] != 1, the
+ * hot columns untouched -- so they keep every bit of the dense batched product. */
 int kf_hot_rows(kf_ctx* ctx, const int32_t* d_hot, int n, int32_t* d_rows, int32_t* d_count);
 int kf_linear_masked(kf_ctx* ctx, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias_or_null, const int32_t* d_rows, int n_hot);
+int kf_zero_cold_columns(kf_ctx* ctx, kf_bf16* y, const int32_t* d_hot, int rows, int cols);
 int kf_norm_gateup_swiglu_masked(kf_ctx* ctx, const kf_bf16* x, const kf_bf16* norm_w_or_null, float eps, const kf_weight* gate, const kf_weight* up,
                                  kf_bf16* act, const int32_t* d_rows, int n_hot);
 

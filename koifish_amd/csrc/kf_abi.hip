@@ -580,6 +580,11 @@ int kf_hot_rows(kf_ctx* c, const int32_t* d_hot, int n, int32_t* d_rows, int32_t
     if (!d_hot || !d_rows || !d_count || n < 1) return fail(KF_INVALID_ARGS, "kf_hot_rows: null pointer or n < 1");
     RET(kf::hot_rows_launch(c->stream, d_hot, n, d_rows, d_count));
 }
+int kf_zero_cold_columns(kf_ctx* c, kf_bf16* y, const int32_t* d_hot, int rows, int cols) {
+    CHKCTX(c);
+    if (!y || !d_hot || rows < 1 || cols < 1) return fail(KF_INVALID_ARGS, "kf_zero_cold_columns: null pointer or rows / cols < 1");
+    RET(kf::cold_cols_launch(c->stream, y, d_hot, rows, cols));
+}
 int kf_linear_masked(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, const int32_t* d_rows, int n_hot) {
     CHKCTX(c);
     int r = check_weight(w, "kf_linear_masked");

@@ -239,6 +239,7 @@ int awq_dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out);
 int set_state_launch(hipStream_t st, int32_t* d_state, int token, int pos);
 int hot_rows_launch(hipStream_t st, const int32_t* hot, int n, int32_t* rows, int32_t* count);
 int cold_fill_launch(hipStream_t st, uint16_t* y, const uint16_t* bias, int n);
+int cold_cols_launch(hipStream_t st, uint16_t* y, const int32_t* hot, int rows, int cols);
 int tp_reduce_launch(hipStream_t st, const float* partials, int R, int n, const uint16_t* residual, uint16_t* out);
 
 }  // namespace kf

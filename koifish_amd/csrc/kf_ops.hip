@@ -1008,5 +1008,16 @@ int cold_fill_launch(hipStream_t st, uint16_t* y, const uint16_t* bias, int n) {
     hipLaunchKernelGGL(cold_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, bias, n);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
+// cold columns of a token batch's SwiGLU output y [rows][cols]: y[r][i] = 0 where hot[i] != 1 (SwiGLU(0, 0) = 0: D_matmul_sparse on gate / up for every token);
+// hot columns are not touched.  A thread owns one column, reads its mask entry once and walks the rows of its grid row.
+__global__ void cold_cols_kernel(uint16_t* y, const int32_t* hot, int rows, int cols) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cols || hot[i] == 1) return;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) y[(size_t)r * cols + i] = 0;
+}
+int cold_cols_launch(hipStream_t st, uint16_t* y, const int32_t* hot, int rows, int cols) {
+    hipLaunchKernelGGL(cold_cols_kernel, dim3((cols + 255) / 256, rows < 1024 ? rows : 1024), dim3(256), 0, st, y, hot, rows, cols);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
 
 }  // namespace kf

@@ -183,6 +183,7 @@ int FFN::cuFlow(floatX* bx, int n) {
     kf_weight wg = gate.w->desc(), wu = up.w->desc(), wd = down.w->desc();
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_gateup_swiglu_batch(c, &wg, &wu, bn, bg, bu, n));
+    if (n_hot >= 0) KF_TRY(kf_zero_cold_columns(c, bg, reinterpret_cast<const int32_t*>(hot_mask->data), n, wg.ne0));  // D_matmul_sparse for every token row, as cuInfer
     return kf_linear(c, &wd, bg, bx, nullptr, n, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx);
 }
 

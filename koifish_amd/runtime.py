@@ -636,7 +636,8 @@ class XcdReplicas:
 
     def close(self):
         if getattr(self, "h", None):
-            self.host.kfh_xr_destroy(self.h)
+            if getattr(self.m, "h", None):   # a garbage cycle (a failed test's frame) finalises in any order: a model that went first took the context with it
+                self.host.kfh_xr_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -791,7 +792,8 @@ class XcdTP:
 
     def close(self):
         if getattr(self, "h", None):
-            self.host.kfh_xtp_destroy(self.h)
+            if all(getattr(m, "h", None) for m in self.nt.ranks):   # (as XcdReplicas.close)
+                self.host.kfh_xtp_destroy(self.h)
             self.h = None
 
     def __del__(self):

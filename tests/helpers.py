@@ -42,3 +42,23 @@ def ids_agree_up_to_a_near_tie(om, prompt, got, ref, ulps=2):
     margin = float(top[1] - top[0])
     tol = ulps * 2.0 ** -7 * max(abs(float(top[1])), 1e-9)   # a bf16 ulp is 2^-8 .. 2^-7 of the value
     return margin <= tol, "first difference at generated id %d (%d vs %d): the oracle's top-2 margin there is %g, %d bf16 ulps are %g" % (i, got[i], ref[i], margin, ulps, tol)
+
+
+def ids_agree_up_to_a_token_batch_near_tie(om, prompt, got, ref, tol=2.0 ** -6):
+    """The same question for ids behind a TOKEN-BATCH prefill (MFMA summation order; logits within `tol` of max|logit| of the oracle's, tests/test_gpu_prefill.py): equal
+    to `ref`, or first different at a step where both ids' oracle logits lie within 2 * tol * max|logit| of the oracle's best -- the rule tests/test_gpu_full_size.py applies
+    to prefill ids (two logit vectors each within tol of the oracle's can pick ids that far apart, no further).  The oracle is teacher-forced along `ref` (the common prefix)."""
+    if list(got) == list(ref):
+        return True, "equal"
+    i = next((k for k, (a, b) in enumerate(zip(got, ref)) if a != b), None)
+    if i is None:
+        return False, "%d ids against %d, equal as far as both go" % (len(got), len(ref))
+    seq = list(prompt) + list(ref)
+    logits = None
+    for p in range(len(prompt) + i):
+        _, logits, _ = om.decode(int(seq[p]), p)
+    f = O.bf16_to_f32(logits)
+    bar = 2 * tol * float(np.abs(f).max())
+    gap = float(f.max() - min(f[int(got[i])], f[int(ref[i])]))
+    return gap <= bar, "first difference at generated id %d (%d vs %d): the oracle's logits there lie %g below its best, the bar is %g (%.2f of it)" % (
+        i, got[i], ref[i], gap, bar, gap / bar)

@@ -252,8 +252,9 @@ def test_fused_qkv_rope_epilogue_equals_the_two_launch_route(ctx, O, nt, seq):
     ctx.sync()
     ctx._lin_ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
     L.check(ctx.hip.kf_set_scratch(ctx.h, C.c_void_p(ctx._lin_ws.data_ptr()), C.c_size_t(ctx._lin_ws.numel())), "kf_set_scratch")
-    wq = bf16_t(O.f32_to_bf16((1 + rng.normal(0, 0.1, size=hd)).astype(np.float32)), ctx.device)
-    wk = bf16_t(O.f32_to_bf16((1 + rng.normal(0, 0.1, size=hd)).astype(np.float32)), ctx.device)
+    wq_h = O.f32_to_bf16((1 + rng.normal(0, 0.1, size=hd)).astype(np.float32))
+    wk_h = O.f32_to_bf16((1 + rng.normal(0, 0.1, size=hd)).astype(np.float32))
+    wq, wk = bf16_t(wq_h, ctx.device), bf16_t(wk_h, ctx.device)
     table = ctx.rope_table(pos0 + nt + 1, hd, 1e6)
     outs = {}
     for fused in (True, False):
@@ -281,6 +282,14 @@ def test_fused_qkv_rope_epilogue_equals_the_two_launch_route(ctx, O, nt, seq):
     v_ref = f(x) @ f(O.dequant(ows[2])).reshape(ms[2], k).T
     assert np.abs(f(outs[True][2]) - v_ref).max() <= 2.0 ** -7 * np.abs(v_ref).max()
     assert np.abs(f(outs[True][0])).max() > 0.1   # q really went through the norm (values of order one)
+    if seq:   # q and k straight against the oracle's linear + head norm + RoPE at position row % seq, on both sides of every prompt boundary: per head within 2^-6 of its scale
+        rows = sorted({0, nt - 1} | {r for b in range(seq, nt, seq) for r in (b - 1, b)})
+        for r in rows:
+            for i, (w_norm, nh) in enumerate(((wq_h, n_head), (wk_h, n_kv))):
+                ref = O.rope(O.headnorm(O.linear(ows[i], x[r]), w_norm, nh, hd, eps), nh, hd, r % seq, 1e6)
+                a, b = O.bf16_to_f32(outs[True][i][r]).reshape(nh, hd), O.bf16_to_f32(ref).reshape(nh, hd)
+                err = np.abs(a - b).max(axis=1) / np.abs(b).max(axis=1)
+                assert err.max() <= 2.0 ** -6, "%s row %d (position %d): head %d off by %.3g of its scale" % ("qk"[i], r, r % seq, int(err.argmax()), err.max())
     if seq:   # the positions restart: sequence 3's rows equal ... only if its inputs did; instead: a call with mismatched nTok / seq_len is refused
         assert ctx.hip.kf_qkv_rope_seqs(ctx.h, C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), xd.data_ptr(), ys[0].data_ptr(), ys[1].data_ptr(), ys[2].data_ptr(), nt, seq + 1,
                                         wq.data_ptr(), wk.data_ptr(), table.data_ptr(), 0, n_head, n_kv, hd, eps) != 0

@@ -8,12 +8,14 @@ import pytest
 import torch
 
 from conftest import bf16_t, u16, ulp_diff_bf16, close_bf16
-from helpers import oracle_model, prompt_ids
+from helpers import ids_agree_up_to_a_token_batch_near_tie, oracle_model, prompt_ids
 from koifish_amd import lib as L
 from koifish_amd import synth
+from koifish_amd.runtime import XcdReplicas
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
+LOGIT_TOL = 2.0 ** -6   # the token-batch bar of tests/test_gpu_prefill.py (MFMA summation order against the oracle's token-serial one)
 
 
 def hot_mask(n, frac=0.2, seed=5):
@@ -64,6 +66,179 @@ def test_linear_masked_vs_oracle_and_dense(ctx, type_, shape):
         assert np.array_equal(got[hot == 1], dense[hot == 1]), "a hot row must carry every bit of the dense product's row"
         cold = got[hot != 1]
         assert np.array_equal(cold, (bias if b is not None else np.zeros(m, dtype=np.uint16))[hot != 1]), "a cold row is 0 (+ bias)"
+
+
+@pytest.mark.parametrize("rows,cols,kind", [(1, 3072, "random"), (7, 1000, "random"), (130, 3072, "random"), (2048, 1029, "random"), (33, 300, "hot"), (33, 300, "cold"),
+                                             (1, 255, "cold"), (1100, 257, "hot")])
+def test_zero_cold_columns(ctx, rows, cols, kind):
+    """kf_zero_cold_columns (FFN::cuFlow's mask on a token batch's SwiGLU output): a cold column (hot[i] != 1) is exactly 0 in every row, a hot column keeps every bit"""
+    rng = np.random.default_rng(rows * 7919 + cols)
+    hot = {"hot": np.ones(cols, dtype=np.int32), "cold": np.zeros(cols, dtype=np.int32), "random": hot_mask(cols, 0.2, seed=cols)}[kind]
+    if kind == "random":
+        hot[::5] *= 3            # values other than 1 are cold, as in kf_hot_rows
+    y0 = O.f32_to_bf16(rng.normal(0, 1.0, size=(rows, cols)).astype(np.float32))
+    y0[y0 == 0] = 0x3f80     # no zero among the inputs: a cold entry left alone would show
+    pad = 512                # guard elements behind the buffer: nothing is written past rows * cols
+    buf = torch.from_numpy(np.concatenate([y0.ravel(), np.full(pad, 0x7777, dtype=np.uint16)]).view(np.int16)).to(ctx.device)
+    d_hot = torch.from_numpy(hot).to(ctx.device)
+    L.check(ctx.hip.kf_zero_cold_columns(ctx.h, buf.data_ptr(), d_hot.data_ptr(), rows, cols), "kf_zero_cold_columns")
+    ctx.sync()
+    out = buf.cpu().numpy().view(np.uint16)
+    got = out[:rows * cols].reshape(rows, cols)
+    assert np.array_equal(got[:, hot == 1], y0[:, hot == 1]), "a hot column must keep every bit"
+    assert not got[:, hot != 1].any(), "a cold column must be exactly 0 in every row"
+    assert (out[rows * cols:] == 0x7777).all()
+    assert ctx.hip.kf_zero_cold_columns(ctx.h, buf.data_ptr(), d_hot.data_ptr(), 0, cols) != 0
+    assert ctx.hip.kf_zero_cold_columns(ctx.h, None, d_hot.data_ptr(), rows, cols) != 0
+
+
+def _masked_pair(layer_type, max_seq=None):
+    """test_sparse_decode_vs_oracle's setup: the small shape, w_std 0.1, the seed-(5 + layer) 20 % mask on every layer, on the device model and the oracle"""
+    cfg = dict(synth.CONFIGS["small"], **({} if max_seq is None else dict(max_seq=max_seq)))
+    raw = synth.raw_weights_numpy(cfg, 77, w_std=0.1)
+    m = synth.build_from_raw(cfg, raw, layer_type, L.BF16)
+    om = oracle_model(cfg, raw, layer_type, L.BF16)
+    for l in range(cfg["n_layer"]):
+        hot = hot_mask(cfg["ffn"], 0.2, seed=5 + l)
+        m.set_hot(l, hot)
+        om.set_hot(l, hot)
+    return cfg, m, om
+
+
+def _oracle_prompt(om, prompt):
+    nxt = lg = None
+    for pos, tok in enumerate(prompt):
+        nxt, lg, _ = om.decode(int(tok), pos)
+    return nxt, lg
+
+
+def _within(g, o, what):
+    a, b = O.bf16_to_f32(g), O.bf16_to_f32(o)
+    err = np.abs(a - b).max() / np.abs(b).max()
+    assert err <= LOGIT_TOL, "%s: off by %.3g of scale, %.1f x the bar" % (what, err, err / LOGIT_TOL)
+
+
+def _kv_within(gk, gv, om, n, n_layer, what):
+    ok, ov = om.kv()
+    for name, g, o in (("K", gk, ok), ("V", gv, ov)):
+        for l in range(n_layer):
+            _within(g[l, :n], o[l, :n], "%s: layer %d %s rows" % (what, l, name))
+
+
+@pytest.mark.parametrize("layer_type", [L.Q4, L.BOOL1])
+def test_sparse_prefill_vs_oracle(layer_type):
+    """Qwen3.prefill on a masked model (Fish::Prefill, FFN::cuFlow on token batches) against the oracle's token-serial sparse forward: the last logits and every layer's
+    K / V rows within the token-batch bar, the next id equal; the mask is really applied (the same prompt without it gives other logits)"""
+    cfg, m, om = _masked_pair(layer_type)
+    prompt = prompt_ids(cfg, 41)
+    n = len(prompt)
+    g_next, g_logits = m.prefill(prompt)
+    o_next, o_logits = _oracle_prompt(om, prompt)
+    _within(g_logits, o_logits, "last logits")
+    gk, gv = m.kv_to_host()
+    _kv_within(gk, gv, om, n, cfg["n_layer"], "prompt")
+    assert g_next == O.argmax_bf16(g_logits)
+    assert g_next == o_next, "next id %d, the oracle's %d" % (g_next, o_next)
+    for l in range(cfg["n_layer"]):
+        m.set_hot(l, None)
+    _, dense = m.prefill(prompt)
+    assert not np.array_equal(dense, g_logits), "the masks changed nothing"
+    om.close()
+    m.close()
+
+
+@pytest.mark.parametrize("layer_type", [L.Q4, L.BOOL1])
+def test_sparse_generate_with_batched_prefill_vs_oracle(layer_type):
+    """generate with set_prefill_mode(1) on a masked model: the ids equal the oracle's sparse generate, or first differ at a near-tie of the token-batch bar"""
+    cfg, m, om = _masked_pair(layer_type)
+    prompt = prompt_ids(cfg, 24)
+    m.set_prefill_mode(1)
+    got = m.generate(prompt, 12, use_graph=True)
+    ref = om.generate(prompt.tolist(), 12)
+    ok, msg = ids_agree_up_to_a_token_batch_near_tie(om, prompt, got, ref)
+    assert ok, msg
+    om.close()
+    m.close()
+
+
+@pytest.mark.parametrize("layer_type", [L.Q4, L.BOOL1])
+def test_sparse_replicas_prefill_and_prefill_batch_vs_oracle(layer_type):
+    """XcdReplicas.prefill_batch (ragged prompts as one token batch) and XcdReplicas.prefill (one prompt through Fish::Prefill) on a masked model, structured as
+    tests/test_gpu_xengine.py::test_prefill_batch_vs_the_oracle: per slot the K / V rows and the last logits within the token-batch bar of the oracle's sparse forward, the
+    picked id equal or a near-tie of that bar (helpers.ids_agree_up_to_a_token_batch_near_tie's rule); then every slot decodes on (the sparse XCD engine), teacher-forced along the oracle's continuation, and the logits six steps behind meet the same bar.
+    Slots that took no prompt keep their state."""
+    cfg, m, om = _masked_pair(layer_type, max_seq=128)
+    xr = XcdReplicas(m, 8)
+    batch_lens, batch_slots = (5, 40, 17, 64), (3, 0, 6, 5)
+    single_lens, single_slots = (33, 2), (1, 7)
+    idle = [s for s in range(8) if s not in batch_slots + single_slots]
+    for s in idle:
+        xr.set_state(s, 7, 0)
+        xr.park(s)
+    prompts = {s: prompt_ids(cfg, n, seed=40 + i) for i, (n, s) in enumerate(zip(batch_lens + single_lens, batch_slots + single_slots))}
+    xr.prefill_batch(batch_slots, [prompts[s] for s in batch_slots])
+    for s in single_slots:
+        xr.prefill(s, prompts[s])
+    m.sync()
+    n_new = 6
+    want = {}
+    for s, p in prompts.items():
+        n = len(p)
+        nxt, lg = _oracle_prompt(om, p)
+        gk, gv = xr.kv_to_host(s)
+        _kv_within(gk, gv, om, n, cfg["n_layer"], "slot %d" % s)
+        _within(xr.logits(s), lg, "slot %d logits" % s)
+        got = xr.state(s)[0]
+        assert xr.state(s) == (O.argmax_bf16(xr.logits(s)), n), "slot %d: state %s" % (s, xr.state(s))
+        assert int(xr.tokens_out(s, n)[n - 1]) == got
+        ol = O.bf16_to_f32(lg)
+        assert got == nxt or ol.max() - min(ol[got], ol[nxt]) <= 2 * LOGIT_TOL * np.abs(ol).max(), "slot %d: picked %d, the oracle %d, not a near-tie" % (s, got, nxt)
+        f = np.full(cfg["max_seq"], -1, dtype=np.int32)
+        tok = nxt
+        for k in range(n_new):
+            f[n + k] = tok
+            tok, lg, _ = om.decode(int(tok), n + k)
+        xr.set_forced(s, f)
+        want[s] = np.array(lg, copy=True)
+    xr.run_steps(n_new)
+    m.sync()
+    xr.check()
+    for s, p in prompts.items():
+        _within(xr.logits(s), want[s], "slot %d: logits %d steps behind the prompt" % (s, n_new))
+        assert xr.state(s)[1] == len(p) + n_new
+    for s in idle:
+        assert xr.status(s)[:3] == [7, 0, 1]
+    om.close()
+    xr.close()
+    m.close()
+
+
+@pytest.mark.parametrize("layer_type", [L.Q4, L.BOOL1])
+def test_sparse_chat_vs_the_model_alone_and_the_oracle(layer_type):
+    """XcdReplicas.chat on a masked model, prompts one by one and in batches of up to 8 (set_prefill_batch): the one-by-one answers equal the model alone generating with
+    prefill mode 1 bit for bit (the existing contract); every answer -- one by one and batched -- equals the oracle's sparse generate up to a token-batch near-tie"""
+    cfg, m, om = _masked_pair(layer_type, max_seq=96)
+    rng = np.random.default_rng(5)
+    prompts = [prompt_ids(cfg, int(rng.integers(2, 41)), seed=300 + r) for r in range(12)]
+    max_new = 8
+    m.set_prefill_mode(1)
+    ref = [m.generate(p, max_new, use_graph=False) for p in prompts]
+    xr = XcdReplicas(m, 8)
+    xr.set_steps_per_launch(4)
+    got, st = xr.chat(prompts, max_new)
+    assert got == ref
+    assert st["prefills"] == len(prompts) and st["dropped"] == 0
+    xr.set_prefill_batch(8)
+    batched, st = xr.chat(prompts, max_new)
+    assert st["prefills"] == len(prompts)
+    for r, p in enumerate(prompts):
+        o_ids = om.generate(p.tolist(), max_new)
+        for name, ids in (("one by one", got[r]), ("batched", batched[r])):
+            ok, msg = ids_agree_up_to_a_token_batch_near_tie(om, p, ids, o_ids)
+            assert ok, "request %d (%s): %s" % (r, name, msg)
+    om.close()
+    xr.close()
+    m.close()
 
 
 @pytest.mark.parametrize("layer_type", [L.BOOL1, L.Q4])

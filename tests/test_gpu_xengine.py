@@ -6,7 +6,7 @@ oracle produce."""
 import numpy as np
 import pytest
 
-from helpers import oracle_model, prompt_ids
+from helpers import ids_agree_up_to_a_token_batch_near_tie, oracle_model, prompt_ids
 from koifish_amd import lib as L
 from koifish_amd import synth
 from koifish_amd.runtime import XcdReplicas
@@ -225,13 +225,13 @@ def test_full_size_eight_sequences(canon, n_seq):
     """(n_seq 32: the form bench.py's `xcd_replicas` headlines -- four sequences per decoder; 16: two.)
     Qwen3-0.6B at the benchmark's positions: eight sequences with different histories (each prefilled with its own 2028-token prompt through the batched prefill, whose
     K / V rows are copied into the sequence's cache) decode 2028 .. 2043 in one 16-step launch.  Sequence by sequence: the 16 ids, the last logits and the 16 new K / V rows
-    equal the single-sequence engine's on the same history; sequences 0 and 5 also equal the oracle's."""
+    equal the single-sequence engine's on the same history; sequences 0 and 5 (n_seq 32: one in each of a decoder's four places) also equal the oracle's."""
     import torch
     cfg = dict(synth.CONFIGS["qwen3-0.6b"])
     m = synth.build_on_gpu(cfg, seed=1234, layer_type=L.Q4, head_type=L.BF16, head_std=0.1)
     m.set_canonical(True)
     P, n = 2028, 16
-    osel = (0, 5) if n_seq <= 16 else (0, 21)   # the sequences also compared with the oracle itself (21: the third of its decoder's four)
+    osel = (0, 5) if n_seq <= 16 else (0, 9, 21, 30)   # the sequences also compared with the oracle itself (s = XCD + 8 * place: 0, 9, 21, 30 are places 0 .. 3 of their decoders)
     kvd = cfg["n_kv"] * cfg["head_dim"]
     xr = XcdReplicas(m, n_seq)
     ref = []
@@ -270,7 +270,7 @@ def test_full_size_eight_sequences(canon, n_seq):
         assert np.array_equal(xr.logits(s), logits), "sequence %d: logits" % s
         gk, gv = xr.kv_to_host(s)
         assert np.array_equal(gk[:, P:P + n], rk) and np.array_equal(gv[:, P:P + n], rv), "sequence %d: K / V rows" % s
-    # two of them against the oracle itself
+    # some of them against the oracle itself
     om = O.from_device_model(m, attn_mode=O.ATTN_CANON)
     om.prepare_fast()
     for s in osel:
@@ -622,12 +622,16 @@ def test_a_queue_of_prompts_through_the_slots(canon, n_seq, n_req):
     got, _ = xr.chat(prompts[:5], max_new)
     assert got == ref[:5]
     # prompts prefilled together when several slots are free (set_prefill_batch): one token batch per refill -- the batch sums in MFMA order over more rows, so the bar is
-    # tests/test_gpu_prefill.py's (ids identical on the committed seeds), not bits
+    # tests/test_gpu_prefill.py's, not bits: an answer that differs from the one-by-one prefill's first differs at a near-tie of the token-batch bar (the oracle teacher-forced
+    # along the one-by-one answer)
     xr.set_prefill_batch(8)
     got, st = xr.chat(prompts, max_new)
     assert st["prefills"] == n_req and [len(a) for a in got] == [len(a) for a in ref]
-    same = sum(a == b for a, b in zip(got, ref))
-    assert same >= 0.8 * n_req, "%d of %d answers equal the one-by-one prefill's" % (same, n_req)   # a near-tie may flip under the other summation order (w_std 0.1: spiky logits)
+    om = oracle_model(cfg, raw, L.Q4, L.BF16, attn_mode=O.ATTN_CANON)
+    for r, (a, b) in enumerate(zip(got, ref)):
+        ok, msg = ids_agree_up_to_a_token_batch_near_tie(om, prompts[r], a, b)
+        assert ok, "request %d: %s" % (r, msg)
+    om.close()
     again, _ = xr.chat(prompts, max_new)
     assert again == got                                                                             # the same batches, the same bits
     xr.set_prefill_batch(1)
@@ -697,5 +701,65 @@ def test_prefill_batch_vs_the_oracle(lens, slots):
         xr.prefill_batch((1, 1), prompts[:2])          # one slot twice
     with pytest.raises(Exception):
         xr.prefill_batch((0,), [prompt_ids(cfg, cfg["max_seq"], seed=1)])   # no row left behind the prompt
+    xr.close()
+    m.close()
+
+
+def test_full_size_prefill_batch_vs_the_oracle():
+    """XcdReplicas.prefill_batch as bench.py times it: Qwen3-0.6B, 4-bit layers, canonical order, resident bf16 copies, 32 slots, 16 ragged prompts of 97 .. 128 tokens in ONE
+    call (the slots cover all four places of decoders 0 .. 7).  The longest and the shortest prompt against the oracle's token-serial forward on the same device weights:
+    layer 0's K / V rows within 2^-6 of scale; deeper, test_gpu_full_size.py's 28-layer rules: every layer's K / V rows within rms 2^-8 and max 2^-5 of scale, the last
+    logits within 1.25 x 2^-6; the picked id equal or a token-batch near-tie.  All 16 picked ids are the first argmax of their slot's
+    logits (the one-read head at vocab 151936); the slots outside the batch keep their state."""
+    cfg = dict(synth.CONFIGS["qwen3-0.6b"])
+    m = synth.build_on_gpu(cfg, seed=1234, layer_type=L.Q4, head_type=L.BF16)
+    m.set_canonical(True)
+    m.set_prefill_resident(True)
+    xr = XcdReplicas(m, 32)
+    slots = tuple(range(0, 32, 2))          # s = XCD + 8 * place: 0, 8, 16, 24 are decoder 0's four places, and so on
+    idle = [s for s in range(32) if s not in slots]
+    for s in idle:
+        xr.set_state(s, 7, 0)
+        xr.park(s)
+    lens = np.random.default_rng(31).integers(97, 129, size=len(slots))
+    lens[3], lens[11] = 128, 97
+    prompts = [np.random.default_rng(600 + i).integers(0, cfg["vocab"], size=int(n)).astype(np.int32) for i, n in enumerate(lens)]
+    xr.prefill_batch(slots, prompts)
+    m.sync()
+    TOL = 2.0 ** -6
+    for s, p in zip(slots, prompts):
+        assert xr.state(s) == (O.argmax_bf16(xr.logits(s)), len(p)), "slot %d" % s
+    om = O.from_device_model(m)
+    om.prepare_fast()
+    for i in (int(np.argmax(lens)), int(np.argmin(lens))):
+        s, p, n = slots[i], prompts[i], int(lens[i])
+        nxt = lg = None
+        for pos, tok in enumerate(p):
+            nxt, lg, _ = om.decode(int(tok), pos, want_logits=(pos == n - 1))
+        ok, ov = om.kv()
+        gk, gv = xr.kv_to_host(s)
+        gl, ol = O.bf16_to_f32(xr.logits(s)), O.bf16_to_f32(lg)
+        err = np.abs(gl - ol).max() / np.abs(ol).max()
+        print("slot %d (%d tokens): logits off by %.3g of scale" % (s, n, err))
+        for name, g, o in (("K", gk, ok), ("V", gv, ov)):
+            for l in range(cfg["n_layer"]):
+                a, b = O.bf16_to_f32(g[l, :n]), O.bf16_to_f32(o[l, :n])
+                d, scale = np.abs(a - b), np.abs(b).max()
+                print("  %s layer %2d: max %.3g rms %.3g of scale" % (name, l, d.max() / scale, np.sqrt((d ** 2).mean()) / scale))
+                # the rows of layer 0 come from one token-batch layer: the bar itself.  Deeper, two fp32 summation orders' one-ulp roundings are amplified layer by layer
+                # (28 layers of random weights; measured: max up to 0.021 of scale by layer 24, rms below 2^-8): the rule test_gpu_full_size.py applies to these rows
+                if l == 0:
+                    assert d.max() <= TOL * scale, "slot %d layer 0 %s rows" % (s, name)
+                assert np.sqrt((d ** 2).mean()) <= 2.0 ** -8 * scale, "slot %d layer %d %s rows: rms" % (s, l, name)
+                assert d.max() <= 2.0 ** -5 * scale, "slot %d layer %d %s rows: max" % (s, l, name)
+        # 28 layers deep the last logits get the bound test_gpu_full_size.py's every-bucket test applies behind a batched prefill (measured there 0.011 - 0.016 of scale;
+        # here 0.013 for the 128-token prompt, 0.0165 for the 97-token one)
+        assert err <= 1.25 * TOL, "slot %d logits: off by %.3g of scale" % (s, err)
+        got = xr.state(s)[0]
+        if got != nxt:   # a near-tie of the token-batch bar (helpers.ids_agree_up_to_a_token_batch_near_tie's rule at the prompt's last row)
+            assert ol.max() - min(ol[got], ol[nxt]) <= 2 * TOL * np.abs(ol).max(), "slot %d: picked %d, the oracle %d" % (s, got, nxt)
+    om.close()
+    for s in idle:
+        assert xr.status(s)[:3] == [7, 0, 1]
     xr.close()
     m.close()
