@@ -9,7 +9,10 @@ last K are timed (default W=128 = the prompt, K=1920 = decode to position 2047).
 
   python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run; independent replicas,
                                                        no data-path collective -- "scaling": "weak")
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  --full adds everything else, after the timed steps and never inside `value`: the other summation
+order, prefill rates, per-kernel rooflines, the CPU baselines, the batched XCD decoders, the side legs of the other
+BASELINE configurations and shapes (child processes), and for --gpus N > 1 the tensor-parallel Qwen3-32B job.
 """
 import argparse
 import json
@@ -49,6 +52,8 @@ def main():
     ap.add_argument("--head", default="bf16", choices=["bf16", "q4", "nf4"])
     ap.add_argument("--layers", default="q4", choices=["q4", "bf16", "f8", "ternary", "1bit", "nf4"],
                     help="weight type of the transformer layers (default: the metric's 4-bit PackedQ; the others are side measurements)")
+    ap.add_argument("--full", action="store_true", help="also every measurement and check beside the headline (never `value`): the options below that name a side "
+                    "measurement act with --full only")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-fp16-steps", type=int, default=64, help="BASELINE config 1 beside the line (never `value`): Qwen3-0.6B with IEEE-half weights decoded on the host cores -- a 128-token "
                     "prompt fed token by token, then this many greedy steps (0 = skip)")
@@ -79,7 +84,8 @@ def main():
     ap.add_argument("--lean-xcd", type=int, default=0, help="with --lean: also the XCD-confined engines on this many independent sequences of the model being run (xcd_replicas)")
     ap.add_argument("--jump", action="store_true", help="side legs only (never the run behind `value`): no token-serial run-up to the timed window -- the K / V rows of the positions in front of it "
                     "are synthetic N(0, 1) bf16 rows written once (a step's time depends on how many rows it reads, not on their values), the decode state is set to the window's first position")
-    ap.add_argument("--lean", action="store_true", help="only the timed decode and step_roofline (what the side legs run in their child processes)")
+    ap.add_argument("--lean", action="store_true", help="with --full: of the side measurements only the other summation order, the engine's hand-offs and the --lean-* legs; "
+                    "prints the whole result as one JSON line (what the side legs run in their child processes)")
     ap.add_argument("--leg", default="", choices=["", "config3", "config4cpu"], help="run ONE side leg and print its JSON (child processes of the main run)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, what they computed as DIR/<name>.npy: logits.npy = the last step's logits (float32), "
                     "ids.npy = the greedy ids of the last min(steps, max_seq) timed steps in step order (float64), the last one the last step's pick; same arguments, same inputs")
@@ -238,6 +244,10 @@ def main():
         # `value` was timed in the library's default summation order: the CANONICAL one (kf_abi.h kf_set_canonical; round 4), every logit, greedy id and KV row bit-exact against
         # the CPU oracle (cpu_baseline.parity_timed_order).  Beside it, never `value`: the same positions in the v_dot2c / fp32 order (kf_set_canonical(ctx, 0)).
         out["config"]["summation_order"] = "canonical (the library default): two v_pk_fma_f32 chains per lane + tree, exact power-of-two softmax with fp64 sums -- bit-exact against the CPU oracle"
+        out["config"]["decode_path"] = "persistent engine, one launch per token" if m.engine_steps() > 0 else "per-layer launches: 5 per layer (%s)" % (m.engine_why() or "engine off")
+        m.engine_check()   # a hand-off poll that timed out in the timed steps voids `value`
+    _lap("timed")
+    if rank == 0 and args.full:   # everything beside the headline: it runs the model again, so the read-backs of the timed steps are done above
         ids_timed_run = m.tokens_out(S).copy()   # the greedy ids of the timed (canonical) run at every position: what sequence 0 of the xcd_replicas leg must reproduce
         try:
             ids0 = m.tokens_out(S)
@@ -272,7 +282,6 @@ def main():
             out["engine_handoffs"] = {"error": repr(e)[:160]}
         if args.lean:
             m.engine_check()
-            out["config"]["decode_path"] = "persistent engine, one launch per token" if m.engine_steps() > 0 else "per-layer launches: 5 per layer (%s)" % (m.engine_why() or "engine off")
             if args.lean_cpu > 0 and world == 1:
                 try:   # the oracle with the same weights (and the same hot-row masks) on this host's cores: parity passes + a bounded timed sample
                     out["cpu_baseline"] = cpu_baseline(m, cfg, forced, args.lean_cpu, min_steps=16, max_steps=96, canon_steps=24, hots=hots)
@@ -291,7 +300,7 @@ def main():
                     out["prefill"] = {"error": repr(e)[:200]}
             print(json.dumps(out))
             return
-        _lap("timed + fast order")
+        _lap("fast order")
         out["prefill"] = prefill_rate(m, forced[:n_prompt], ms_per_step)
         if world == 1 and args.streams > 1 and args.config == "qwen3-0.6b":
             try:
@@ -351,7 +360,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        _lap("side legs")
+        if args.full:
+            _lap("side legs")
         out["wall_s"] = round(time.perf_counter() - _T_START, 1)
         out["wall_laps_s"] = _LAPS
         emit(out)
@@ -413,8 +423,8 @@ def _run_ranks(n, argv, timeout_s):
 
 
 def launch_ranks(args):
-    """The parent of a bare `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment).  It never imports torch and never touches a GPU.  Two child jobs, each N
-    fresh rank processes: (1) the command line as given -- for the default config the 0.6B decode as N independent replicas (`value`, "scaling": "weak"); (2) when (1) was the
+    """The parent of a bare `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment).  It never imports torch and never touches a GPU.  One or two child jobs, each N
+    fresh rank processes: (1) the command line as given -- for the default config the 0.6B decode as N independent replicas (`value`, "scaling": "weak"); (2) with --full, when (1) was the
     default config, BASELINE config 4 -- Qwen3-32B tensor parallel TP = N over the kernel-side exchange ("scaling": "strong") -- whose line rides inside (1)'s as
     `config4_tp`, so that ONE driver command per N yields both curves north_star asks for.  A failure of (1) is this process's exit code; a failure of (2) costs only its object."""
     argv = [a for a in sys.argv[1:]]
@@ -423,7 +433,7 @@ def launch_ranks(args):
         sys.stderr.write(err + "\n")
         return rc if rc != 0 else 1
     out = json.loads(line)   # rank 0's COMPACT line (its detail file: bench_detail.json)
-    if args.config == "qwen3-0.6b" and not args.x_no_tp_leg:
+    if args.full and args.config == "qwen3-0.6b" and not args.x_no_tp_leg:
         tp_argv = ["--gpus", str(args.gpus), "--config", "qwen3-32b", "--steps", "64", "--warmup", "16", "--tp-exchange", args.tp_exchange, "--x-backend", args.x_backend,
                    "--x-device", str(args.x_device), "--x-tp-layers", str(args.x_tp_layers), "--x-tp-vocab", str(args.x_tp_vocab)]
         rc2, line2, err2 = _run_ranks(args.gpus, tp_argv, 1500)
@@ -440,14 +450,15 @@ def launch_ranks(args):
 
 
 def _child(argv, timeout_s):
-    """one side leg in a child process (its own HIP context and memory; a failure or a timeout costs only that object): the last JSON line it prints"""
+    """one side leg in a child process (its own HIP context and memory; a failure or a timeout costs only that object): the last JSON line it prints.  The child runs with
+    --full: its side measurements are what the leg reports"""
     import subprocess
     t0 = time.perf_counter()
     try:
         def unpin():   # the parent's OpenMP runtime bound this thread to one core (2 hardware threads): the child's CPU legs would see 2 "cores"
             if _ALL_CPUS:
                 os.sched_setaffinity(0, _ALL_CPUS)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=timeout_s, preexec_fn=unpin)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + argv, capture_output=True, text=True, timeout=timeout_s, preexec_fn=unpin)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not lines:
             return {"error": (r.stderr or r.stdout)[-300:]}

@@ -26,9 +26,10 @@ HOOKS = ["--x-backend", "gloo", "--x-device", "0"]   # two ranks share GPU 0 ove
 
 
 def test_two_ranks_one_json_line():
+    """--full: the line also carries the per-kernel `roofline` of rank 0"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "96", "--warmup", "16", "--cpu-seconds", "0", "--streams", "0", "--config", "small"] + HOOKS
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "96", "--warmup", "16", "--full", "--cpu-seconds", "0", "--streams", "0", "--config", "small"] + HOOKS
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
