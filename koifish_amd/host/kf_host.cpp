@@ -57,6 +57,35 @@ void* KVCache::Get(CTYPE type, int layer, int pos) const {
     return base + ((size_t)layer * max_seq_len + pos) * kv_dim;
 }
 
+// ------------------------------------------------------------------------------------------------ sampler, sequence buffers
+bool CHAT_SAMPLER::Valid(int vocab) const {
+    if (greedy()) return true;
+    const int k = top_k < vocab ? top_k : vocab;
+    return !(k < 2 || k >= vocab / 2 || k > 1024 || !(temperature > 0.0f) || !(top_p > 0.0f));
+}
+CHAT_SAMPLER CHAT_SAMPLER::FromArgs(float temperature, float top_p, int top_k, uint64_t seed) {
+    CHAT_SAMPLER s;
+    s.temperature = temperature, s.top_p = top_p, s.top_k = top_k & 0xFFFF, s.seed = seed;
+    s.true_topk = (top_k & 0x10000) != 0;  // bit 16 of top_k: candidates = the k largest logits (kf_sample_topk)
+    return s;
+}
+int CHAT_SAMPLER::Draw(kf_ctx* c, const floatX* logits, int vocab, uint64_t* rng, int32_t* state, int32_t* ids, const int32_t* forced, int n_ctx) const {
+    return (true_topk ? kf_sample_topk : kf_sample)(c, logits, vocab, top_k, temperature, top_p, rng, nullptr, state, ids, forced, n_ctx);
+}
+
+int SeqBuffers::AllocSeqs(kf_ctx* c, int n, int n_ctx, int tokens_fill) {
+    KF_TRY(kf_malloc(c, (size_t)n * 16, (void**)&d_state));
+    KF_TRY(kf_malloc(c, (size_t)n * n_ctx * 4, (void**)&d_forced));
+    KF_TRY(kf_malloc(c, (size_t)n * n_ctx * 4, (void**)&d_tokens_out));
+    KF_TRY(kf_memset(c, d_state, 0, (size_t)n * 16));
+    KF_TRY(kf_memset(c, d_forced, 0xff, (size_t)n * n_ctx * 4));
+    return kf_memset(c, d_tokens_out, tokens_fill, (size_t)n * n_ctx * 4);
+}
+void SeqBuffers::FreeSeqs(kf_ctx* c) {
+    kf_free(c, d_state), kf_free(c, d_forced), kf_free(c, d_tokens_out);
+    d_state = d_forced = d_tokens_out = nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------ neurons
 hGTensor LayerNormal::cuFlow(hGTensor inp, int) {
     // P_CHAT_1 && nHead == 0  ->  CU_rms_infer (T.cu:569-573)
@@ -166,9 +195,6 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
     floatX *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn);
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
-    const kf_weight* ws[3] = {&wq, &wk, &wv};
-    kf_bf16* ys[3] = {bq, krows, vrows};  // K.out / V.out alias the cache rows (_devQKV)
-    (void)ws, (void)ys;
     KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, krows, vrows, n, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv,
                              head_dim, normQ.rms_eps));
     KF_TRY(kf_attn_prefill(c, bq, key_cache, val_cache, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
@@ -223,9 +249,7 @@ Fish::~Fish() {
     if (ctx && engine_ws) kf_free(ctx, engine_ws);
     if (ctx) {
         if (rope_table) kf_free(ctx, rope_table);
-        if (d_state) kf_free(ctx, d_state);
-        if (d_forced) kf_free(ctx, d_forced);
-        if (d_tokens_out) kf_free(ctx, d_tokens_out);
+        FreeSeqs(ctx);
         if (gBUFF.d_ptok) kf_free(ctx, gBUFF.d_ptok);
         if (d_rng) kf_free(ctx, d_rng);
     }
@@ -279,12 +303,7 @@ int Fish::Build(const MODEL_CARD& card, int device, void* stream) {
         KF_TRY(kf_malloc(ctx, tab.size() * 4, (void**)&rope_table));
         KF_TRY(kf_h2d(ctx, rope_table, tab.data(), tab.size() * 4));
     }
-    KF_TRY(kf_malloc(ctx, 16, (void**)&d_state));
-    KF_TRY(kf_memset(ctx, d_state, 0, 16));
-    KF_TRY(kf_malloc(ctx, (size_t)card.n_ctx * 4, (void**)&d_forced));
-    KF_TRY(kf_memset(ctx, d_forced, 0xff, (size_t)card.n_ctx * 4));
-    KF_TRY(kf_malloc(ctx, (size_t)card.n_ctx * 4, (void**)&d_tokens_out));
-    KF_TRY(kf_memset(ctx, d_tokens_out, 0xff, (size_t)card.n_ctx * 4));
+    KF_TRY(AllocSeqs(ctx, 1, card.n_ctx, 0xff));
 
     embed.hFish = this, embed.name = "embed_tokens", embed.out = x;
     for (int l = 0; l < card.nLayer; l++) {
@@ -325,8 +344,7 @@ int Fish::pos_bound() const {
     return b < config.n_ctx - 1 ? b : config.n_ctx - 1;
 }
 
-int Fish::EnsureLinearScratch(const kf_weight& w, int nTok) {
-    const size_t need = kf_linear_scratch_bytes(&w, nTok);
+int Fish::GrowScratch(size_t need) {
     if (need <= lin_scratch_bytes) return KF_OK;
     KF_TRY(kf_sync(ctx));
     void* p = nullptr;
@@ -337,38 +355,44 @@ int Fish::EnsureLinearScratch(const kf_weight& w, int nTok) {
     return KF_OK;
 }
 
-// The persistent decode engine over this model's layers: built on first use (every weight must be set), not while capturing.
-int Fish::EnsureEngine() {
-    if (engine_state != 0) return engine_state > 0 ? KF_OK : KF_ENGINE_NOT_SERVED;
-    engine_state = -1;
-    std::vector<kf_engine_layer> L(config.nLayer);
+int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why, std::vector<kf_engine_layer>& L, kf_engine_desc& d) const {
+    const size_t layer_rows = (size_t)config.n_ctx * config.n_head_kv * config.head_dim;
+    L.assign(config.nLayer, kf_engine_layer{});
     for (int l = 0; l < config.nLayer; l++) {
         SelfAttention* a = attn[l].get();
         FFN* m = ffn[l].get();
         SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
         for (int j = 0; j < 7; j++) {
             if (!s[j]->w || s[j]->b) {
-                engine_why = "a layer matrix is missing or carries a bias";
+                why = "a layer matrix is missing or carries a bias";
                 return KF_ENGINE_NOT_SERVED;
             }
             L[l].w[j] = s[j]->w->desc();
         }
-        if (!a->norm.w || !m->norm.w) {
-            engine_why = "a norm weight is missing";
+        if (!a->norm.w || !m->norm.w || (!masks && m->n_hot >= 0)) {
+            why = masks ? "a norm weight is missing" : "a norm weight is missing or a hot-row mask is set";
             return KF_ENGINE_NOT_SERVED;
         }
         L[l].hot_ffn = m->n_hot >= 0 ? reinterpret_cast<const int32_t*>(m->hot_mask->data) : nullptr; /* the sparse forward inside the launch: cold gate / up rows never read, zeros published */
         L[l].norm_in = ToX(a->norm.w), L[l].norm_post = ToX(m->norm.w);
         L[l].q_norm = a->normQ.w ? ToX(a->normQ.w) : nullptr, L[l].k_norm = a->normK.w ? ToX(a->normK.w) : nullptr;
-        L[l].kcache = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_KEY, l, 0));
-        L[l].vcache = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_VAL, l, 0));
+        L[l].kcache = kbase + l * layer_rows, L[l].vcache = vbase + l * layer_rows;
     }
-    kf_engine_desc d;
     std::memset(&d, 0, sizeof(d));
     d.n_layer = config.nLayer, d.dim = config.nEmbed, d.n_head = config.n_head, d.n_kv = config.n_head_kv, d.head_dim = config.head_dim, d.ffn = config.n_ff;
     d.kv_stride = config.n_head_kv * config.head_dim;
     d.max_seq = config.n_ctx;
     d.rms_eps = config.rms_eps, d.qk_eps = config.qk_eps, d.rope_table = rope_table, d.layers = L.data();
+    return KF_OK;
+}
+
+// The persistent decode engine over this model's layers: built on first use (every weight must be set), not while capturing.
+int Fish::EnsureEngine() {
+    if (engine_state != 0) return engine_state > 0 ? KF_OK : KF_ENGINE_NOT_SERVED;
+    engine_state = -1;
+    std::vector<kf_engine_layer> L;
+    kf_engine_desc d;
+    KF_TRY(EngineTable(ToX(cache.key), ToX(cache.val), true, engine_why, L, d));
     {
         char why[320];
         why[0] = 0;
@@ -439,15 +463,7 @@ int Fish::EnsureResident(int PC) {
     if (kf_malloc(ctx, total, &p) != KF_OK) return KF_OK; /* no room: not an error, the scratch route serves */
     deq_arena = p, deq_arena_bytes = total;
     KF_TRY(kf_set_dequant_arena(ctx, p, total));
-    const size_t need = kf_resident_scratch_bytes(); /* the scratch holds no dequantised copy any more: it lends the small tile kernels their split-K slots */
-    if (need > lin_scratch_bytes) {
-        void* q = nullptr;
-        KF_TRY(kf_malloc(ctx, need, &q));
-        KF_TRY(kf_set_scratch(ctx, q, need));
-        if (lin_scratch) kf_free(ctx, lin_scratch);
-        lin_scratch = q, lin_scratch_bytes = need;
-    }
-    return KF_OK;
+    return GrowScratch(kf_resident_scratch_bytes()); /* the scratch holds no dequantised copy any more: it lends the small tile kernels their split-K slots */
 }
 int Fish::EngineCheck() {
     if (!engine || engine_steps == 0) return KF_OK;
@@ -554,8 +570,7 @@ int Fish::EnqueueStep(int bound) {
             if (rc == KF_OK) {
                 engine_steps++;
                 if (samp_params.greedy()) return KF_OK;
-                return (samp_params.true_topk ? kf_sample_topk : kf_sample)(ctx, ToX(head.preLogits), config.vocab, samp_params.top_k, samp_params.temperature, samp_params.top_p,
-                                                                             d_rng, nullptr, d_state, d_tokens_out, d_forced, config.n_ctx);
+                return samp_params.Draw(ctx, ToX(head.preLogits), config.vocab, d_rng, d_state, d_tokens_out, d_forced, config.n_ctx);
             }
         } else {
             const int rc = kf_engine_step(ctx, engine, nullptr, ToX(x), d_state, bound);
@@ -744,16 +759,8 @@ int Fish::PrefillReady(int min_rows) {
             kf_weight wq = attn[l]->Q.w->desc(), wk = attn[l]->K.w->desc(), wv = attn[l]->V.w->desc(), wg = ffn[l]->gate.w->desc(), wu = ffn[l]->up.w->desc();
             const kf_weight* qkv[3] = {&wq, &wk, &wv};
             const kf_weight* gu[2] = {&wg, &wu};
-            size_t need = kf_linear_multi_scratch_bytes(3, qkv, PC), need2 = kf_linear_multi_scratch_bytes(2, gu, PC);
-            need = need > need2 ? need : need2;
-            if (need > lin_scratch_bytes) {
-                KF_TRY(kf_sync(ctx));
-                void* p = nullptr;
-                KF_TRY(kf_malloc(ctx, need, &p));
-                KF_TRY(kf_set_scratch(ctx, p, need));
-                if (lin_scratch) kf_free(ctx, lin_scratch);
-                lin_scratch = p, lin_scratch_bytes = need;
-            }
+            const size_t need = kf_linear_multi_scratch_bytes(3, qkv, PC), need2 = kf_linear_multi_scratch_bytes(2, gu, PC);
+            KF_TRY(GrowScratch(need > need2 ? need : need2));
         }
     }
     return EnsureResident(gBUFF.rows);
@@ -764,15 +771,11 @@ int Fish::HeadAndPick(const floatX* x_last) {
     if (samp_params.greedy())
         return kf_norm_lm_head(ctx, x_last, ToX(final_norm.w), final_norm.rms_eps, &wh, ToX(head.preLogits), d_state, d_tokens_out, gBUFF.head_ws->data);
     KF_TRY(kf_norm_lm_head(ctx, x_last, ToX(final_norm.w), final_norm.rms_eps, &wh, ToX(head.preLogits), nullptr, nullptr, gBUFF.head_ws->data));
-    return (samp_params.true_topk ? kf_sample_topk : kf_sample)(ctx, ToX(head.preLogits), config.vocab, samp_params.top_k, samp_params.temperature, samp_params.top_p,
-                                                                 d_rng, nullptr, d_state, d_tokens_out, d_forced, config.n_ctx);
+    return samp_params.Draw(ctx, ToX(head.preLogits), config.vocab, d_rng, d_state, d_tokens_out, d_forced, config.n_ctx);
 }
 
 int Fish::SetSampler(const CHAT_SAMPLER& s) {
-    if (!s.greedy()) {
-        const int k = s.top_k < config.vocab ? s.top_k : config.vocab;
-        if (k < 2 || k >= config.vocab / 2 || k > 1024 || !(s.temperature > 0.0f) || !(s.top_p > 0.0f)) return KF_INVALID_ARGS;
-    }
+    if (!s.Valid(config.vocab)) return KF_INVALID_ARGS;
     const bool was_greedy = samp_params.greedy();
     samp_params = s;
     if (!was_greedy || !s.greedy()) { /* the captured step graphs end in a different pick, or hold the old sampler arguments */
@@ -803,20 +806,46 @@ int Fish::Generate(const int* prompt, int n_prompt, int n_new, int* out, bool us
     return KF_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ XCD-confined replicas
-XcdReplicas::~XcdReplicas() {
-    if (!hFish) return;
-    kf_ctx* ctx = hFish->ctx;
-    if (engine) {
-        kf_sync(ctx);
-        kf_xengine_destroy(engine);
+// ------------------------------------------------------------------------------------------------ XCD engines
+XcdEngine::~XcdEngine() {
+    if (!ctx) return;
+    kf_sync(ctx);
+    if (engine) kf_xengine_destroy(engine);
+    kf_free(ctx, engine_ws);
+    FreeSeqs(ctx);
+}
+int XcdEngine::EnsureWorkspace(size_t bytes) {
+    if (engine_ws && bytes <= engine_ws_bytes) return KF_OK;
+    if (engine_ws) kf_free(ctx, engine_ws), engine_ws = nullptr;
+    KF_TRY(kf_malloc(ctx, bytes, &engine_ws));
+    engine_ws_bytes = bytes;
+    return KF_OK;
+}
+int XcdEngine::LaunchSteps(int n) {
+    for (int i = 0; i < n;) {
+        const int m = n - i < steps_per_launch ? n - i : steps_per_launch;
+        KF_TRY(kf_xengine_steps(ctx, engine, ToX(x), d_state, m, 1));
+        i += m;
     }
-    if (engine_ws) kf_free(ctx, engine_ws);
-    if (d_state) kf_free(ctx, d_state);
-    if (d_forced) kf_free(ctx, d_forced);
-    if (d_tokens_out) kf_free(ctx, d_tokens_out);
-    if (d_rng) kf_free(ctx, d_rng);
-    if (d_dst) kf_free(ctx, d_dst);
+    return KF_OK;
+}
+int XcdEngine::SetStepsPerLaunch(int n) {
+    if (n < 1 || n > 4096) return KF_INVALID_ARGS;
+    steps_per_launch = n;
+    return KF_OK;
+}
+int XcdEngine::Check() {
+    if (!engine) return KF_OK;
+    const int rc = kf_xengine_check(ctx, engine);
+    if (rc == KF_INTERNAL_ERR) kf_xengine_reset(ctx, engine);
+    return rc;
+}
+
+// ---- XCD-confined replicas
+XcdReplicas::~XcdReplicas() {
+    if (!ctx) return;
+    kf_free(ctx, d_rng);
+    kf_free(ctx, d_dst);
 }
 size_t XcdReplicas::kv_seq_elems() const {
     const MODEL_CARD& c = hFish->config;
@@ -826,35 +855,11 @@ size_t XcdReplicas::kv_seq_elems() const {
 // the first use after the Fish's weights changed (kfh_weights_changed / a weight set again: Fish::weights_gen) -- a decode through this object never reads stale weights
 int XcdReplicas::MakeEngine(bool allocate) {
     Fish* f = hFish;
-    kf_ctx* ctx = f->ctx;
     const MODEL_CARD& c = f->config;
     const int kvd = c.n_head_kv * c.head_dim;
-    std::vector<kf_engine_layer> L(c.nLayer);
-    for (int l = 0; l < c.nLayer; l++) {
-        SelfAttention* a = f->attn[l].get();
-        FFN* m = f->ffn[l].get();
-        SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
-        for (int j = 0; j < 7; j++) {
-            if (!s[j]->w || s[j]->b) {
-                why = "a layer matrix is missing or carries a bias";
-                return KF_ENGINE_NOT_SERVED;
-            }
-            L[l].w[j] = s[j]->w->desc();
-        }
-        if (!a->norm.w || !m->norm.w) {
-            why = "a norm weight is missing";
-            return KF_ENGINE_NOT_SERVED;
-        }
-        L[l].hot_ffn = m->n_hot >= 0 ? reinterpret_cast<const int32_t*>(m->hot_mask->data) : nullptr; /* the sparse forward (round 6): cold gate / up rows publish zeros */
-        L[l].norm_in = ToX(a->norm.w), L[l].norm_post = ToX(m->norm.w);
-        L[l].q_norm = a->normQ.w ? ToX(a->normQ.w) : nullptr, L[l].k_norm = a->normK.w ? ToX(a->normK.w) : nullptr;
-        L[l].kcache = L[l].vcache = reinterpret_cast<floatX*>(f->cache.Get(KVCache::KV_KEY, l, 0)); /* stand-ins for the validation call below; set after the allocation */
-    }
+    std::vector<kf_engine_layer> L;
     kf_engine_desc d;
-    std::memset(&d, 0, sizeof(d));
-    d.n_layer = c.nLayer, d.dim = c.nEmbed, d.n_head = c.n_head, d.n_kv = c.n_head_kv, d.head_dim = c.head_dim, d.ffn = c.n_ff;
-    d.kv_stride = kvd, d.max_seq = c.n_ctx;
-    d.rms_eps = c.rms_eps, d.qk_eps = c.qk_eps, d.rope_table = f->rope_table, d.layers = L.data();
+    KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
     {
         char w[320];
         w[0] = 0;
@@ -875,23 +880,10 @@ int XcdReplicas::MakeEngine(bool allocate) {
         if (!key || !val || !logits || !x) return KF_OUTOF_GPUMEMORY;
         KF_TRY(kf_memset(ctx, key->data, 0, seq_elems * n_seq * 2));
         KF_TRY(kf_memset(ctx, val->data, 0, seq_elems * n_seq * 2));
-        KF_TRY(kf_malloc(ctx, (size_t)n_seq * 16, (void**)&d_state));
-        KF_TRY(kf_malloc(ctx, (size_t)n_seq * c.n_ctx * 4, (void**)&d_forced));
-        KF_TRY(kf_malloc(ctx, (size_t)n_seq * c.n_ctx * 4, (void**)&d_tokens_out));
-        KF_TRY(kf_memset(ctx, d_state, 0, (size_t)n_seq * 16));
-        KF_TRY(kf_memset(ctx, d_forced, 0xff, (size_t)n_seq * c.n_ctx * 4));
-        KF_TRY(kf_memset(ctx, d_tokens_out, 0, (size_t)n_seq * c.n_ctx * 4));
+        KF_TRY(AllocSeqs(ctx, n_seq, c.n_ctx, 0));
     }
-    for (int l = 0; l < c.nLayer; l++) {
-        L[l].kcache = ToX(key) + (size_t)l * c.n_ctx * kvd;
-        L[l].vcache = ToX(val) + (size_t)l * c.n_ctx * kvd;
-    }
-    const size_t bytes = kf_xengine_workspace_bytes(&d);
-    if (!engine_ws || bytes > engine_ws_bytes) {
-        if (engine_ws) kf_free(ctx, engine_ws), engine_ws = nullptr;
-        KF_TRY(kf_malloc(ctx, bytes, &engine_ws));
-        engine_ws_bytes = bytes;
-    }
+    KF_TRY(f->EngineTable(ToX(key), ToX(val), true, why, L, d)); /* the table again, on this object's rows */
+    KF_TRY(EnsureWorkspace(kf_xengine_workspace_bytes(&d)));
     int rc = kf_xengine_create(ctx, &d, n_seq, (int64_t)seq_elems, engine_ws, engine_ws_bytes, &engine);
     if (rc != KF_OK) {
         why = kf_last_error();
@@ -909,12 +901,11 @@ int XcdReplicas::MakeEngine(bool allocate) {
 }
 int XcdReplicas::Build(Fish* f, int n_seq_) {
     if (!f || n_seq_ < 1 || n_seq_ > KF_XENGINE_MAX_SEQ) return KF_INVALID_ARGS;
-    hFish = f, n_seq = n_seq_;
+    hFish = f, ctx = f->ctx, n_seq = n_seq_;
     return MakeEngine(true);
 }
 int XcdReplicas::Fresh() {
     if (engine && built_gen == hFish->weights_gen) return KF_OK;
-    kf_ctx* ctx = hFish->ctx;
     if (engine) {
         KF_TRY(kf_sync(ctx));
         kf_xengine_destroy(engine), engine = nullptr;
@@ -925,20 +916,17 @@ int XcdReplicas::SetForced(int seq, const int32_t* ids, int n) {
     if (seq < 0 || seq >= n_seq || n < 0 || n > hFish->config.n_ctx) return KF_INVALID_ARGS;
     std::vector<int32_t> row(hFish->config.n_ctx, -1);
     for (int i = 0; i < n; i++) row[i] = ids[i];
-    return kf_h2d(hFish->ctx, d_forced + (size_t)seq * hFish->config.n_ctx, row.data(), row.size() * 4);
+    return kf_h2d(ctx, d_forced + (size_t)seq * hFish->config.n_ctx, row.data(), row.size() * 4);
 }
 int XcdReplicas::SetState(int seq, int token, int pos) {
     if (seq < 0 || seq >= n_seq || pos < 0 || pos >= hFish->config.n_ctx || token < 0 || token >= hFish->config.vocab) return KF_INVALID_ARGS;
-    KF_TRY(kf_memset32(hFish->ctx, d_state + 4 * seq + 3, 0, 1)); /* the status word of the re-aimed sequence */
-    return kf_set_state(hFish->ctx, d_state + 4 * seq, token, pos);
+    KF_TRY(kf_memset32(ctx, d_state + 4 * seq + 3, 0, 1)); /* the status word of the re-aimed sequence */
+    return kf_set_state(ctx, d_state + 4 * seq, token, pos);
 }
 // CHAT_SAMPLER for Chat (greedy by default): one rng word per sequence, seeded per request
 int XcdReplicas::SetSampler(const CHAT_SAMPLER& sp) {
-    if (!sp.greedy()) {
-        const int k = sp.top_k < hFish->config.vocab ? sp.top_k : hFish->config.vocab;
-        if (k < 2 || k >= hFish->config.vocab / 2 || k > 1024 || !(sp.temperature > 0.0f) || !(sp.top_p > 0.0f)) return KF_INVALID_ARGS;
-        if (!d_rng) KF_TRY(kf_malloc(hFish->ctx, (size_t)n_seq * 8, (void**)&d_rng));
-    }
+    if (!sp.Valid(hFish->config.vocab)) return KF_INVALID_ARGS;
+    if (!sp.greedy() && !d_rng) KF_TRY(kf_malloc(ctx, (size_t)n_seq * 8, (void**)&d_rng));
     samp_params = sp;
     return KF_OK;
 }
@@ -946,18 +934,17 @@ int XcdReplicas::SetSampler(const CHAT_SAMPLER& sp) {
 // sequence's cache rows and skipped it (kf_abi.h: d_state [n_seq][4] = {token, pos, parked, status}).
 int XcdReplicas::Park(int seq, bool on) {
     if (seq < 0 || seq >= n_seq) return KF_INVALID_ARGS;
-    return kf_memset32(hFish->ctx, d_state + 4 * seq + 2, on ? 1 : 0, 1); /* on the stream, no host sync: the queue flips these between launches */
+    return kf_memset32(ctx, d_state + 4 * seq + 2, on ? 1 : 0, 1); /* on the stream, no host sync: the queue flips these between launches */
 }
 int XcdReplicas::Status(int seq, int32_t* out4) {
     if (seq < 0 || seq >= n_seq || !out4) return KF_INVALID_ARGS;
-    return kf_d2h(hFish->ctx, out4, d_state + 4 * seq, 16);
+    return kf_d2h(ctx, out4, d_state + 4 * seq, 16);
 }
 // The prompt half of "prefill + decode" for one of the sequences: the model's own batched prefill (Fish::Prefill: the reference prefills token by token through the decode
 // path, GoPT.cpp:1139-1146), then the prompt's K / V rows of every layer move into the sequence's cache and the sequence stands at {first generated id, n}.
 int XcdReplicas::Prefill(int seq, const int* tokens, int n) {
     const MODEL_CARD& c = hFish->config;
     if (seq < 0 || seq >= n_seq || !tokens || n < 1 || n >= c.n_ctx) return KF_INVALID_ARGS;
-    kf_ctx* ctx = hFish->ctx;
     KF_TRY(Fresh());
     {   /* the sequence's cache has the model's own layout ([layer][row][kv_dim]): for the length of the call the model's cache IS the sequence's, the rows land where they stay */
         struct Aim {
@@ -977,7 +964,6 @@ int XcdReplicas::Prefill(int seq, const int* tokens, int n) {
 int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int* lens, int S, int stride) {
     Fish* f = hFish;
     const MODEL_CARD& c = f->config;
-    kf_ctx* ctx = f->ctx;
     if (!slots || !tokens || !lens || S < 1 || S > n_seq || stride < 1) return KF_INVALID_ARGS;
     int T = 0;
     for (int i = 0; i < S; i++) {
@@ -1055,11 +1041,8 @@ int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int
 int XcdReplicas::RunSteps(int n) {
     if (n < 1) return KF_INVALID_ARGS;
     KF_TRY(Fresh());
-    for (int i = 0; i < n;) {
-        const int m = n - i < steps_per_launch ? n - i : steps_per_launch;
-        KF_TRY(kf_xengine_steps(hFish->ctx, engine, ToX(x), d_state, m, 1));
-        i += m, steps_run += m;
-    }
+    KF_TRY(LaunchSteps(n));
+    steps_run += n;
     return KF_OK;
 }
 // A queue of prompts answered through the sequences' slots: what Fish::Chat does round by round over DEBUG.prompts (GoPT.cpp:1111-1180: prefill the prompt, then sample
@@ -1080,14 +1063,11 @@ int XcdReplicas::Chat(const int32_t* prompts, const int32_t* prompt_len, int n_r
         for (int r = 0; r < n_req; r++)
             if (max_new_each[r] < 1 || max_new_each[r] > max_new) return KF_INVALID_ARGS;
     const bool sampled = !samp_params.greedy();
-    auto draw = [&](int s) -> int {  // the slot's next id from its logits: state {token, pos} -> {id, pos + 1}, ids out [pos] = id
-        return (samp_params.true_topk ? kf_sample_topk : kf_sample)(hFish->ctx, ToX(logits) + (size_t)s * c.vocab, c.vocab, samp_params.top_k, samp_params.temperature,
-                                                                     samp_params.top_p, d_rng + s, nullptr, d_state + 4 * s, d_tokens_out + (size_t)s * c.n_ctx,
-                                                                     d_forced + (size_t)s * c.n_ctx, c.n_ctx);
+    auto draw = [&](int s) -> int {  // the slot's next id from its logits
+        return samp_params.Draw(ctx, ToX(logits) + (size_t)s * c.vocab, c.vocab, d_rng + s, d_state + 4 * s, d_tokens_out + (size_t)s * c.n_ctx, d_forced + (size_t)s * c.n_ctx, c.n_ctx);
     };
     for (int r = 0; r < n_req; r++)
         if (prompt_len[r] < 1 || prompt_len[r] > stride || prompt_len[r] >= c.n_ctx) return KF_INVALID_ARGS;
-    kf_ctx* ctx = hFish->ctx;
     KF_TRY(Fresh());
     struct Slot { int req = -1, len = 0, want = 0, have = 0; };
     std::vector<Slot> slot(n_seq);
@@ -1184,31 +1164,15 @@ int XcdReplicas::Chat(const int32_t* prompts, const int32_t* prompt_len, int n_r
     if (stats) for (int i = 0; i < 4; i++) stats[i] = st[i];
     return rc != KF_OK ? rc : Check();
 }
-int XcdReplicas::Check() {
-    if (!engine) return KF_OK;
-    const int rc = kf_xengine_check(hFish->ctx, engine);
-    if (rc == KF_INTERNAL_ERR) kf_xengine_reset(hFish->ctx, engine);
-    return rc;
-}
 
 // ---- tensor parallel over the XCDs
-XcdTP::~XcdTP() {
-    if (ranks.empty()) return;
-    kf_ctx* ctx = ranks[0]->ctx;
-    kf_sync(ctx);
-    if (engine) kf_xengine_destroy(engine);
-    if (engine_ws) kf_free(ctx, engine_ws);
-    if (d_state) kf_free(ctx, d_state);
-    if (d_forced) kf_free(ctx, d_forced);
-    if (d_tokens_out) kf_free(ctx, d_tokens_out);
-}
 int XcdTP::Build(Fish** fs, int world) {
     if (!fs || world < 1) return KF_INVALID_ARGS;
     for (int r = 0; r < world; r++)
         if (!fs[r]) return KF_INVALID_ARGS;
     ranks.assign(fs, fs + world);
     Fish* f0 = fs[0];
-    kf_ctx* ctx = f0->ctx;
+    ctx = f0->ctx;
     const MODEL_CARD& c = f0->config;
     const int kvd = c.n_head_kv * c.head_dim;
     const size_t rank_elems = (size_t)c.nLayer * c.n_ctx * kvd;
@@ -1231,34 +1195,9 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "the ranks' cards disagree";
             return KF_INVALID_ARGS;
         }
-        Ls[r].resize(c.nLayer);
-        for (int l = 0; l < c.nLayer; l++) {
-            SelfAttention* a = f->attn[l].get();
-            FFN* m = f->ffn[l].get();
-            SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
-            for (int j = 0; j < 7; j++) {
-                if (!s[j]->w || s[j]->b) {
-                    why = "a layer matrix is missing or carries a bias";
-                    return KF_ENGINE_NOT_SERVED;
-                }
-                Ls[r][l].w[j] = s[j]->w->desc();
-            }
-            if (!a->norm.w || !m->norm.w || m->n_hot >= 0) {
-                why = "a norm weight is missing or a hot-row mask is set";
-                return KF_ENGINE_NOT_SERVED;
-            }
-            Ls[r][l].hot_ffn = nullptr;
-            Ls[r][l].norm_in = ToX(a->norm.w), Ls[r][l].norm_post = ToX(m->norm.w);
-            Ls[r][l].q_norm = a->normQ.w ? ToX(a->normQ.w) : nullptr, Ls[r][l].k_norm = a->normK.w ? ToX(a->normK.w) : nullptr;
-            Ls[r][l].kcache = ToX(key) + (size_t)r * rank_elems + (size_t)l * c.n_ctx * kvd;
-            Ls[r][l].vcache = ToX(val) + (size_t)r * rank_elems + (size_t)l * c.n_ctx * kvd;
-        }
-        kf_engine_desc& d = ds[r];
-        std::memset(&d, 0, sizeof(d));
-        d.n_layer = c.nLayer, d.dim = cr.nEmbed, d.n_head = cr.n_head, d.n_kv = cr.n_head_kv, d.head_dim = cr.head_dim, d.ffn = cr.n_ff;
-        d.kv_stride = kvd, d.max_seq = c.n_ctx;
-        d.rms_eps = cr.rms_eps, d.qk_eps = cr.qk_eps, d.rope_table = f0->rope_table, d.layers = Ls[r].data();
-        dp[r] = &d;
+        KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
+        ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
+        dp[r] = &ds[r];
         if (!f->embed.w || !f->head.proj.w || !f->final_norm.w) {
             why = "embedding / head / final norm missing";
             return KF_ENGINE_NOT_SERVED;
@@ -1269,15 +1208,9 @@ int XcdTP::Build(Fish** fs, int world) {
     logits = GT(ctx, "xtp.logits", typNUMBER::BF16, vocab, 1);
     x = GT(ctx, "xtp.x", typNUMBER::BF16, c.nEmbed, 1);
     if (!logits || !x) return KF_OUTOF_GPUMEMORY;
-    KF_TRY(kf_malloc(ctx, 16, (void**)&d_state));
-    KF_TRY(kf_malloc(ctx, (size_t)c.n_ctx * 4, (void**)&d_forced));
-    KF_TRY(kf_malloc(ctx, (size_t)c.n_ctx * 4, (void**)&d_tokens_out));
-    KF_TRY(kf_memset(ctx, d_state, 0, 16));
-    KF_TRY(kf_memset(ctx, d_forced, 0xff, (size_t)c.n_ctx * 4));
-    KF_TRY(kf_memset(ctx, d_tokens_out, 0, (size_t)c.n_ctx * 4));
-    const size_t bytes = kf_xengine_workspace_bytes_tp(dp[0]);
-    KF_TRY(kf_malloc(ctx, bytes, &engine_ws));
-    int rc = kf_xengine_create_tp(ctx, dp.data(), world, engine_ws, bytes, &engine);
+    KF_TRY(AllocSeqs(ctx, 1, c.n_ctx, 0));
+    KF_TRY(EnsureWorkspace(kf_xengine_workspace_bytes_tp(dp[0])));
+    int rc = kf_xengine_create_tp(ctx, dp.data(), world, engine_ws, engine_ws_bytes, &engine);
     if (rc != KF_OK) {
         why = kf_last_error();
         return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : rc;
@@ -1298,11 +1231,11 @@ int XcdTP::SetForced(const int32_t* ids, int n) {
     if (n < 0 || n > n_ctx) return KF_INVALID_ARGS;
     std::vector<int32_t> row(n_ctx, -1);
     for (int i = 0; i < n; i++) row[i] = ids[i];
-    return kf_h2d(ranks[0]->ctx, d_forced, row.data(), row.size() * 4);
+    return kf_h2d(ctx, d_forced, row.data(), row.size() * 4);
 }
 int XcdTP::SetState(int token, int pos) {
     if (pos < 0 || pos >= ranks[0]->config.n_ctx || token < 0 || token >= vocab) return KF_INVALID_ARGS;
-    return kf_set_state(ranks[0]->ctx, d_state, token, pos);
+    return kf_set_state(ctx, d_state, token, pos);
 }
 int XcdTP::RunSteps(int n) {
     if (!engine || n < 1) return KF_INVALID_ARGS;
@@ -1311,18 +1244,20 @@ int XcdTP::RunSteps(int n) {
             why = "a rank's weights changed since this engine was built (kfh_weights_changed / a weight set again): destroy it and create it again";
             return KF_INVALID_ARGS;
         }
-    for (int i = 0; i < n;) {
-        const int m = n - i < steps_per_launch ? n - i : steps_per_launch;
-        KF_TRY(kf_xengine_steps(ranks[0]->ctx, engine, ToX(x), d_state, m, 1));
-        i += m;
-    }
-    return KF_OK;
+    return LaunchSteps(n);
 }
-int XcdTP::Check() {
-    if (!engine) return KF_OK;
-    const int rc = kf_xengine_check(ranks[0]->ctx, engine);
-    if (rc == KF_INTERNAL_ERR) kf_xengine_reset(ranks[0]->ctx, engine);
-    return rc;
+// the C entry points' create: a built object, or NULL with its refusal in kfh_host_error
+template <class T, class... A>
+static void* xcd_create(int* rc_out, A... args) {
+    T* t = new T();
+    const int rc = t->Build(args...);
+    if (rc_out) *rc_out = rc;
+    if (rc != KF_OK) {
+        g_host_err = t->why;
+        delete t;
+        return nullptr;
+    }
+    return t;
 }
 
 }  // namespace koifish
@@ -1617,10 +1552,7 @@ int kfh_set_prefill_mode(void* h, int mode, int chunk) {
     return KF_OK;
 }
 int kfh_set_sampler(void* h, float temperature, float top_p, int top_k, uint64_t seed) {
-    CHAT_SAMPLER s;
-    s.temperature = temperature, s.top_p = top_p, s.top_k = top_k & 0xFFFF, s.seed = seed;
-    s.true_topk = (top_k & 0x10000) != 0;  // bit 16 of top_k: candidates = the k largest logits (kf_sample_topk)
-    return reinterpret_cast<Fish*>(h)->SetSampler(s);
+    return reinterpret_cast<Fish*>(h)->SetSampler(CHAT_SAMPLER::FromArgs(temperature, top_p, top_k, seed));
 }
 int kfh_set_state(void* h, int token, int pos) { return reinterpret_cast<Fish*>(h)->SetState(token, pos); }
 int kfh_run_steps(void* h, int pos, int n, int use_graph) { return reinterpret_cast<Fish*>(h)->RunSteps(pos, n, use_graph != 0); }
@@ -1696,18 +1628,8 @@ int kfh_tp_group_run(void** hs, int R, int pos, int n, int use_graph) {
     return KF_OK;
 }
 
-// ---- XCD-confined replicas: handles are koifish::XcdReplicas*
-void* kfh_xr_create(void* fish, int n_seq, int* rc_out) {
-    XcdReplicas* r = new XcdReplicas();
-    const int rc = r->Build(reinterpret_cast<Fish*>(fish), n_seq);
-    if (rc_out) *rc_out = rc;
-    if (rc != KF_OK) {
-        g_host_err = r->why;
-        delete r;
-        return nullptr;
-    }
-    return r;
-}
+// ---- XCD engines: handles are koifish::XcdReplicas* / koifish::XcdTP*
+void* kfh_xr_create(void* fish, int n_seq, int* rc_out) { return xcd_create<XcdReplicas>(rc_out, reinterpret_cast<Fish*>(fish), n_seq); }
 void kfh_xr_destroy(void* h) { delete reinterpret_cast<XcdReplicas*>(h); }
 int kfh_xr_set_forced(void* h, int seq, const int32_t* ids, int n) { return reinterpret_cast<XcdReplicas*>(h)->SetForced(seq, ids, n); }
 int kfh_xr_set_state(void* h, int seq, int token, int pos) { return reinterpret_cast<XcdReplicas*>(h)->SetState(seq, token, pos); }
@@ -1725,10 +1647,7 @@ int kfh_xr_set_prefill_batch(void* h, int n) {
     return KF_OK;
 }
 int kfh_xr_set_sampler(void* h, float temperature, float top_p, int top_k, uint64_t seed) {
-    CHAT_SAMPLER s;
-    s.temperature = temperature, s.top_p = top_p, s.top_k = top_k & 0xFFFF, s.seed = seed;
-    s.true_topk = (top_k & 0x10000) != 0;
-    return reinterpret_cast<XcdReplicas*>(h)->SetSampler(s);
+    return reinterpret_cast<XcdReplicas*>(h)->SetSampler(CHAT_SAMPLER::FromArgs(temperature, top_p, top_k, seed));
 }
 int kfh_xr_chat(void* h, const int32_t* prompts, const int32_t* prompt_len, int n_req, int stride, int max_new, int eos, int32_t* out, int32_t* out_len, long long* stats) {
     return reinterpret_cast<XcdReplicas*>(h)->Chat(prompts, prompt_len, n_req, stride, max_new, eos, out, out_len, stats);
@@ -1739,20 +1658,16 @@ int kfh_xr_chat_each(void* h, const int32_t* prompts, const int32_t* prompt_len,
     return reinterpret_cast<XcdReplicas*>(h)->Chat(prompts, prompt_len, n_req, stride, max_new, eos, out, out_len, stats, max_new_each);
 }
 int kfh_xr_status(void* h, int seq, int32_t* out4) { return reinterpret_cast<XcdReplicas*>(h)->Status(seq, out4); }
-int kfh_xr_set_steps_per_launch(void* h, int n) {
-    if (n < 1 || n > 4096) return KF_INVALID_ARGS;
-    reinterpret_cast<XcdReplicas*>(h)->steps_per_launch = n;
-    return KF_OK;
-}
+int kfh_xr_set_steps_per_launch(void* h, int n) { return reinterpret_cast<XcdReplicas*>(h)->SetStepsPerLaunch(n); }
 int kfh_xr_get_tokens(void* h, int seq, int32_t* out, int n) {
     XcdReplicas* r = reinterpret_cast<XcdReplicas*>(h);
     if (seq < 0 || seq >= r->n_seq || n < 0 || n > r->hFish->config.n_ctx) return KF_INVALID_ARGS;
-    return kf_d2h(r->hFish->ctx, out, r->d_tokens_out + (size_t)seq * r->hFish->config.n_ctx, (size_t)n * 4);
+    return kf_d2h(r->ctx, out, r->d_tokens_out + (size_t)seq * r->hFish->config.n_ctx, (size_t)n * 4);
 }
 int kfh_xr_get_state(void* h, int seq, int32_t* out2) {
     XcdReplicas* r = reinterpret_cast<XcdReplicas*>(h);
     if (seq < 0 || seq >= r->n_seq) return KF_INVALID_ARGS;
-    return kf_d2h(r->hFish->ctx, out2, r->d_state + 4 * seq, 8);
+    return kf_d2h(r->ctx, out2, r->d_state + 4 * seq, 8);
 }
 void* kfh_xr_logits(void* h, int seq) {
     XcdReplicas* r = reinterpret_cast<XcdReplicas*>(h);
@@ -1770,31 +1685,17 @@ void* kfh_xr_vcache(void* h, int seq) {
     XcdReplicas* r = reinterpret_cast<XcdReplicas*>(h);
     return ToX(r->val) + (size_t)seq * r->kv_seq_elems();
 }
-void* kfh_xtp_create(void** fishes, int world, int* rc_out) {
-    XcdTP* t = new XcdTP();
-    const int rc = t->Build(reinterpret_cast<Fish**>(fishes), world);
-    if (rc_out) *rc_out = rc;
-    if (rc != KF_OK) {
-        g_host_err = t->why;
-        delete t;
-        return nullptr;
-    }
-    return t;
-}
+void* kfh_xtp_create(void** fishes, int world, int* rc_out) { return xcd_create<XcdTP>(rc_out, reinterpret_cast<Fish**>(fishes), world); }
 void kfh_xtp_destroy(void* h) { delete reinterpret_cast<XcdTP*>(h); }
 int kfh_xtp_set_forced(void* h, const int32_t* ids, int n) { return reinterpret_cast<XcdTP*>(h)->SetForced(ids, n); }
 int kfh_xtp_set_state(void* h, int token, int pos) { return reinterpret_cast<XcdTP*>(h)->SetState(token, pos); }
 int kfh_xtp_run_steps(void* h, int n) { return reinterpret_cast<XcdTP*>(h)->RunSteps(n); }
 int kfh_xtp_check(void* h) { return reinterpret_cast<XcdTP*>(h)->Check(); }
-int kfh_xtp_set_steps_per_launch(void* h, int n) {
-    if (n < 1 || n > 4096) return KF_INVALID_ARGS;
-    reinterpret_cast<XcdTP*>(h)->steps_per_launch = n;
-    return KF_OK;
-}
+int kfh_xtp_set_steps_per_launch(void* h, int n) { return reinterpret_cast<XcdTP*>(h)->SetStepsPerLaunch(n); }
 int kfh_xtp_get_tokens(void* h, int32_t* out, int n) {
     XcdTP* t = reinterpret_cast<XcdTP*>(h);
     if (n < 0 || n > t->ranks[0]->config.n_ctx) return KF_INVALID_ARGS;
-    return kf_d2h(t->ranks[0]->ctx, out, t->d_tokens_out, (size_t)n * 4);
+    return kf_d2h(t->ctx, out, t->d_tokens_out, (size_t)n * 4);
 }
 int kfh_xtp_vocab(void* h) { return reinterpret_cast<XcdTP*>(h)->vocab; }
 void* kfh_xtp_logits(void* h) { return ToX(reinterpret_cast<XcdTP*>(h)->logits); }

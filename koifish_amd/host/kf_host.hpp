@@ -177,6 +177,19 @@ struct CHAT_SAMPLER {
     uint64_t seed = 42;
     bool true_topk = false;  // false: the candidate set the reference's TOPK_heap keeps (kf_sample); true: the k largest logits (kf_sample_topk)
     bool greedy() const { return temperature == 0.0f || top_k == 1; }
+    bool Valid(int vocab) const;  // what kf_sample accepts (greedy: always)
+    static CHAT_SAMPLER FromArgs(float temperature, float top_p, int top_k, uint64_t seed);  // the C arguments: bit 16 of top_k = true_topk
+    // the next id drawn from `logits` with rng state `rng`: state {token, pos} -> {id, pos + 1}, ids [pos] = id (nothing drawn where forced [pos + 1] >= 0)
+    int Draw(kf_ctx* c, const floatX* logits, int vocab, uint64_t* rng, int32_t* state, int32_t* ids, const int32_t* forced, int n_ctx) const;
+};
+
+// The decode buffers of n sequences, allocated and filled together (Fish: one sequence; XcdReplicas: n_seq; XcdTP: its one sequence)
+struct SeqBuffers {
+    int32_t* d_state = nullptr;       // [n][4]: {token, pos, 0, 0} (XcdReplicas: {token, pos, parked, status})
+    int32_t* d_forced = nullptr;      // [n][n_ctx] teacher-forced ids, -1 = free running
+    int32_t* d_tokens_out = nullptr;  // [n][n_ctx] the id produced at each position
+    int AllocSeqs(kf_ctx* c, int n, int n_ctx, int tokens_fill);  // tokens_fill: the byte d_tokens_out starts as
+    void FreeSeqs(kf_ctx* c);
 };
 
 // Tensor-parallel decode (no counterpart in the single-GPU reference, QKV.cu:503): this Fish holds ONE rank's shard -- the
@@ -191,7 +204,7 @@ struct TPState {
     std::vector<kf_graph*> group_graphs;  // ranks of ONE process stepped in lock-step on one stream: rank 0 keeps the group's graphs, one per bucket
 };
 
-struct Fish {
+struct Fish : SeqBuffers {
     MODEL_CARD config;
     TPState tp;
     int TPInit(int rank, int world, int vocab_row0);  // allocates this rank's receive area; peers are set afterwards
@@ -221,7 +234,8 @@ struct Fish {
     bool resident_tried = false;
     int EnsureResident(int PC);
     void DropResident();
-    int EnsureLinearScratch(const kf_weight& w, int nTok);
+    int GrowScratch(size_t need);  // the kf_set_scratch workspace grown to `need` bytes (synchronises first; never shrinks)
+    int EnsureLinearScratch(const kf_weight& w, int nTok) { return GrowScratch(kf_linear_scratch_bytes(&w, nTok)); }
     bool use_engine = true;
     kf_engine* engine = nullptr;
     void* engine_ws = nullptr;
@@ -231,6 +245,9 @@ struct Fish {
     bool engine_head = false;   // ... and runs the final norm, the (bf16) LM head and the greedy pick as trailing phases of its launch
     int masked_layers = 0;      // layers with a hot-row mask (kfh_set_hot): the engine walks dense FFNs only
     int EnsureEngine();
+    // what the decode engines read of this model: one kf_engine_layer per layer -- the seven matrices (none with a bias), both norms, the q / k norms, the hot-row mask
+    // (refused unless `masks`), K / V rows of layer l at kbase / vbase + l * n_ctx * kv_dim -- and the descriptor over them; KF_ENGINE_NOT_SERVED with `why` otherwise
+    int EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why, std::vector<kf_engine_layer>& L, kf_engine_desc& d) const;
     void DropEngineTable();     // the engine's device table and the captured graphs only (a hot-row mask changed)
     void DropEngine();          // weights / norms / caches changed: the engine's device table and the captured graphs hold stale pointers
     int EngineCheck();          // synchronises; a timed-out hand-off is reported ONCE (KF_INTERNAL_ERR), the engine reset so that later steps run again
@@ -247,9 +264,6 @@ struct Fish {
     LayerNormal final_norm;
     Head4Token head;
     float* rope_table = nullptr;  // device [n_ctx][hd/2][2]
-    int32_t* d_state = nullptr;   // {token, pos, 0, 0}
-    int32_t* d_forced = nullptr;  // [n_ctx] teacher-forced ids, -1 = free running
-    int32_t* d_tokens_out = nullptr;  // [n_ctx] greedy id produced at each position
     int tok_pos = 0;              // hBatch->tok_pos
     bool graph_mode = false;      // launches take position/token from d_state
     bool state_tokens = false;    // eager per-kernel steps (fuse_level 0, e.g. AutoAWQ weights): position from the host, token from d_state
@@ -283,25 +297,35 @@ struct Fish {
     int prefill_mode = 0;  // Generate: 0 token-serial prefill like the reference, 1 batched
 };
 
+// What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their
+// sequences, the sequences' buffers, the launches in runs of steps_per_launch, the check and the teardown.
+struct XcdEngine : SeqBuffers {
+    kf_ctx* ctx = nullptr;  // the (first) Fish's, not owned; set by Build
+    kf_xengine* engine = nullptr;
+    void* engine_ws = nullptr;
+    size_t engine_ws_bytes = 0;
+    hGTensor key, val;      // [sequence or rank][n_layer][n_ctx][kv_dim] bf16
+    hGTensor logits, x;     // [sequence][vocab], [sequence][nEmbed]
+    std::string why;        // why the model is not served, "" when it is
+    int steps_per_launch;
+    explicit XcdEngine(int steps) : steps_per_launch(steps) {}
+    ~XcdEngine();
+    int EnsureWorkspace(size_t bytes);  // engine_ws of at least `bytes` (kept when large enough)
+    int LaunchSteps(int n);  // n greedy steps of every sequence, kf_xengine_steps in runs of at most steps_per_launch; no host sync
+    int SetStepsPerLaunch(int n);
+    int Check();          // synchronises; a timed-out hand-off is reported once (KF_INTERNAL_ERR) and the engine reset
+};
+
 // Eight independent decoders on ONE GPU, one per XCD, sharing a Fish's weights (kf_xengine_* of the ABI; round 5).  The reference decodes one sequence per process
 // (Fish::Chat, GoPT.cpp:1139-1180) and scales a small model by running more processes; here the "processes" are the 32-workgroup halves of one launch: sequence s has its own
 // KVCache (Cache.cpp:14-57, one per sequence), decode state, forced ids, ids out and logits -- everything the reference's per-process Fish owns except the weights.
 // Every sequence's ids / logits / K / V rows are those Fish::RunSteps produces for it alone (canonical order), bit for bit.
-struct XcdReplicas {
+struct XcdReplicas : XcdEngine {
     Fish* hFish = nullptr;  // the weights (not owned)
     int n_seq = 0;
-    kf_xengine* engine = nullptr;
-    void* engine_ws = nullptr;
-    hGTensor key, val;      // [n_seq][n_layer][n_ctx][kv_dim] bf16
-    hGTensor logits, x;     // [n_seq][vocab], [n_seq][nEmbed]
-    int32_t* d_state = nullptr;       // [n_seq][4]: {token, pos, parked, status}
-    int32_t* d_forced = nullptr;      // [n_seq][n_ctx], -1 = free running
-    int32_t* d_tokens_out = nullptr;  // [n_seq][n_ctx]
-    std::string why;        // why the model is not served, "" when it is
-    int steps_per_launch = 32;
     long long steps_run = 0;
-    size_t engine_ws_bytes = 0;
     unsigned built_gen = 0;  // Fish::weights_gen the engine was built on
+    XcdReplicas() : XcdEngine(32) {}
     ~XcdReplicas();
     int Build(Fish* f, int n_seq_);
     int MakeEngine(bool allocate);
@@ -325,31 +349,21 @@ struct XcdReplicas {
     CHAT_SAMPLER samp_params;     // Chat's sampler (greedy by default); non-greedy: one launch per token, kf_sample per occupied slot
     uint64_t* d_rng = nullptr;    // [n_seq] xorshift states, seeded per request (seed + request index)
     int SetSampler(const CHAT_SAMPLER& s);
-    int Check();          // synchronises; a timed-out hand-off is reported once (KF_INTERNAL_ERR) and the engine reset
     size_t kv_seq_elems() const;
 };
 
 // ONE sequence of a model split over eight tensor-parallel ranks, the ranks as the eight XCDs of ONE launch (kf_xengine_create_tp): the Fish of every rank holds its shards
 // (koifish_amd/tp.py build_native_rank); this object owns the ranks' K / V rows, the sequence's state / forced ids / ids out, the full logits vector.
-struct XcdTP {
+// key / val: [rank][n_layer][n_ctx][kv_dim of a rank]; logits: [vocab] (the shards in rank order); x: [nEmbed].
+struct XcdTP : XcdEngine {
     std::vector<Fish*> ranks;  // not owned
-    kf_xengine* engine = nullptr;
-    void* engine_ws = nullptr;
-    hGTensor key, val;         // [rank][n_layer][n_ctx][kv_dim of a rank] bf16
-    hGTensor logits, x;        // [vocab] (the shards in rank order), [nEmbed]
-    int32_t* d_state = nullptr;
-    int32_t* d_forced = nullptr;
-    int32_t* d_tokens_out = nullptr;
     int vocab = 0;
-    std::string why;
-    int steps_per_launch = 16;
     std::vector<unsigned> built_gen;  // the ranks' Fish::weights_gen at Build: a rank whose weights changed since makes RunSteps refuse (the engine holds a fused copy of q | k | v)
-    ~XcdTP();
+    XcdTP() : XcdEngine(16) {}
     int Build(Fish** fs, int world);
     int SetForced(const int32_t* ids, int n);
     int SetState(int token, int pos);
     int RunSteps(int n);
-    int Check();
 };
 
 }  // namespace koifish
