@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kf_gemm_plan.h"
+#include "kf_gemv_plan.h"
 
 struct kf_ctx {
     int device;
@@ -127,16 +128,12 @@ static int deq_copies(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight
     *out = (const uint16_t*)dst;
     return KF_OK;
 }
-static kf::GemmMat mat_of(const kf_weight* w) {
-    const bool tab_al = w->gama && al16(w->gama + w->ne0 + w->ne1);
-    return kf::GemmMat{w->type, w->quant, w->qzeros || w->qscales, w->ne0, w->ne1, w->lGroup, w->gama != nullptr, (al16(w->data) ? kf::GM_DATA_AL : 0) | (tab_al ? kf::GM_TAB_AL : 0)};
-}
 // what a token-batch entry knows before it launches anything (kf_gemm_plan.h)
 static kf::GemmProblem problem_of(const kf_ctx* c, int entry, int n_w, const kf_weight* const* w, int n, const void* x) {
     kf::GemmProblem P;
     memset(&P, 0, sizeof(P));
     P.entry = entry, P.n_w = n_w, P.n = n, P.x_al = al16(x);
-    for (int i = 0; i < n_w; i++) P.w[i] = mat_of(w[i]);
+    for (int i = 0; i < n_w; i++) P.w[i] = kf::mat_of(w[i]);
     P.scratch = c->scratch ? (long long)c->scratch_bytes : 0;
     P.arena = c->arena != nullptr, P.capturing = c->capturing, P.arena_free = (long long)(c->arena_bytes - c->arena_used);
     for (int f = kf::DEQ_STACK; f <= kf::DEQ_ILV; f++)
@@ -319,7 +316,7 @@ static void init_args(kf_ctx* c, kf::GemvLaunch& L) { memset(&L, 0, sizeof(L)); 
 size_t kf_linear_scratch_bytes(const kf_weight* w, int nTok) {
     if (!w || nTok < 1) return 0;
     if (w->qzeros) return kf::awq_scratch_bytes(w);
-    const kf::GemmMat m = mat_of(w);
+    const kf::GemmMat m = kf::mat_of(w);
     return m.quant != KF_QUANT_GROUP || kf::deq_tile_shape(m, nTok) ? (size_t)w->ne0 * w->ne1 * 2 : 0;
 }
 int kf_set_canonical(kf_ctx* c, int on) {
@@ -347,16 +344,17 @@ int kf_set_scratch(kf_ctx* c, void* scratch, size_t bytes) {
     return KF_OK;
 }
 
-// one mat-vec launch per token row
+// one mat-vec launch per token row, all of one plan
 static int linear_rows(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta, const kf_bf16* residual) {
+    kf::GemvLaunch L;
+    init_args(c, L);
+    L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN;
+    L.args.bias = bias, L.args.alpha = alpha, L.args.beta = beta;
+    const kf::GemvPlan p = kf::gemv_plan(kf::gemv_problem(L));
     for (int t = 0; t < nTok; t++) {
-        kf::GemvLaunch L;
-        init_args(c, L);
-        L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN;
         L.args.x = x + (size_t)t * w->ne1, L.args.job[0].y = y + (size_t)t * w->ne0;
-        L.args.bias = bias, L.args.alpha = alpha, L.args.beta = beta;
         L.args.residual = residual ? residual + (size_t)t * w->ne0 : nullptr;
-        int rc = kf::gemv_launch(c->stream, L);
+        int rc = kf::gemv_launch(c->stream, L, p);
         if (rc != KF_OK) return fail(rc, "kf_linear failed with %d", rc);
     }
     return KF_OK;
@@ -718,7 +716,7 @@ size_t kf_linear_multi_scratch_bytes(int n_w, const kf_weight* const* w, int nTo
     P.n_w = n_w, P.n = nTok;
     for (int i = 0; i < n_w; i++) {
         if (!w[i]) return 0;
-        P.w[i] = mat_of(w[i]);
+        P.w[i] = kf::mat_of(w[i]);
     }
     long long bytes = 0;
     return kf::stack_shape(P, &bytes) ? (size_t)bytes : 0; /* the stacked route's copy without an arena */
@@ -989,7 +987,7 @@ int kf_linear_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, co
     }
     kf::GemmProblem P; /* the two products' plans (kf_gemm_plan.h gemm_plan_backward): the middle region lends the split-K slots */
     memset(&P, 0, sizeof(P));
-    P.n_w = 1, P.w[0] = mat_of(w), P.n = n, P.x_al = 1, P.scratch = (long long)sk_bytes;
+    P.n_w = 1, P.w[0] = kf::mat_of(w), P.n = n, P.x_al = 1, P.scratch = (long long)sk_bytes;
     if (delta) { /* delta [n, IC] (+)= deltaIn [n, OC] . W [OC, IC]: rows of W^T are contiguous in the contraction index OC */
         P.entry = kf::GE_BWD_DX;
         const kf::GemmPlan p = kf::gemm_plan(P);
@@ -1360,15 +1358,20 @@ int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
     *out = kf::gemm_plan(*P);
     return 0;
 }
-// development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process (the token-batch routes have none: kf_gemm_plan.h)
+// the plan kf::gemv_plan makes for a one-token mat-vec problem (no HIP call): tests/test_gemv_plan_cpu.py
+int kfdbg_gemv_plan(const kf::GemvProblem* P, kf::GemvPlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::gemv_plan(*P);
+    return 0;
+}
+// development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process (the token-batch routes have none: kf_gemm_plan.h; the mat-vec's
+// slots per wave and load form none either: kf_gemv_plan.h)
 int kfdbg_set_knob(const char* name, long value) {
     if (!name) return -1;
     kf::Knobs& k = kf::g_knobs;
     if (!strcmp(name, "q4_perm")) k.q4_perm = (int)value;
     else if (!strcmp(name, "q2_tab")) k.q2_tab = (int)value;
     else if (!strcmp(name, "q1_tab")) k.q1_tab = (int)value;
-    else if (!strcmp(name, "gemv_waves")) k.gemv_waves = value;
-    else if (!strcmp(name, "gemv_stream")) k.gemv_stream = (int)value;
     else if (!strcmp(name, "gemv_xf2")) k.gemv_xf2 = (int)value;
     else if (!strcmp(name, "attn_gq_split")) k.attn_gq_split = (int)value;
     else if (!strcmp(name, "attn_pair_min")) k.attn_pair_min = (int)value;

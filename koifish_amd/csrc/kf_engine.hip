@@ -367,8 +367,8 @@ struct EngCfg {
     static constexpr int xA = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).xA, qkv = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).qkv, ao = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).ao,
                          xB = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).xB, act = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).act, part = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).part,
                          hbest = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).hbest, tokg = eng_xoff(DIM_, QD_, KVD_, FFN_, HD_).tokg;
-    // the LM head (bf16 [vocab, DIM]) as trailing phases of the same launch: the geometry gemv_launch picks for a many-row bf16 matrix of this width
-    static constexpr int HnBlk = DIM_ / 8, Hlpr_log2 = c_lpr_log2(DIM_ / 8, 1L << 20), HLPR = 1 << Hlpr_log2, HRPS = 64 >> Hlpr_log2, Hiters = (HnBlk + HLPR - 1) / HLPR;
+    // the LM head (bf16 [vocab, DIM]) as trailing phases of the same launch: the geometry of the mat-vec rule for a many-row bf16 matrix of this width
+    static constexpr int HnBlk = DIM_ / 8, Hlpr_log2 = gemv_lpr_log2(8, DIM_, 1L << 20), HLPR = 1 << Hlpr_log2, HRPS = 64 >> Hlpr_log2, Hiters = (HnBlk + HLPR - 1) / HLPR;
     static constexpr int lq_stride = eng_lq_stride(GQ_, HD_), lp_stride = eng_lp_stride(GQ_, HD_);
     // slice merge: every workgroup merges ME consecutive elements of one head (ME = the power of two >= q_dim / NWG).  A head's slice partials (fp64 sums of the
     // canonical softmax, kf_attn_common.h) lie as [hd / ME element groups][KF_ATTN_MAX_SPLITS slices][ME] values, a value = two 8-byte {32 bits, generation}
@@ -1356,15 +1356,14 @@ const EngForm* engine_form(int sc, int fmt, bool canon, bool stamps, int n_layer
     if (!f) f = find(false);
     return f && f->smem(n_layer) <= 160 * 1024 ? f : nullptr;
 }
-// the invariant behind the engine's summation order: every phase's compile-time plan has the matrices of the model and the lanes per row the mat-vec launcher picks
-// for them (the engine walks every storage in 32-weight pieces, eng_vepb)
+// the invariant behind the engine's summation order: every phase's compile-time plan has the matrices of the model (the engine walks every storage in 32-weight
+// pieces, eng_vepb); its lanes per row are then those of the mat-vec rule, gemv_lpr_log2, which c_plan calls for the same matrices
 static bool eng_plans_match(const EngForm* f, const kf_engine_desc* d) {
     const int q_dim = d->n_head * d->head_dim, kv_dim = d->n_kv * d->head_dim;
     const int K[4] = {d->dim, q_dim, d->dim, d->ffn}, M[4][3] = {{q_dim, kv_dim, kv_dim}, {d->dim, 0, 0}, {d->ffn, d->ffn, 0}, {d->dim, 0, 0}};
-    const long rows[4] = {(long)q_dim + 2 * kv_dim, d->dim, d->ffn, d->dim}; /* gate | up: the launcher's rows of one of the pair */
     for (int i = 0; i < 4; i++) {
         const CPlan& p = f->plan[i];
-        if (p.K != K[i] || p.nBlk != K[i] / 32 || p.lpr_log2 != gemv_lpr_log2(p.nBlk, rows[i])) return false;
+        if (p.K != K[i] || p.nBlk != K[i] / 32) return false;
         for (int j = 0; j < 3; j++)
             if (p.M[j] != M[i][j]) return false;
     }
@@ -1382,13 +1381,13 @@ int eng_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool q
         if (!Ly.norm_in || !Ly.norm_post || !Ly.kcache || !Ly.vcache || (((uintptr_t)Ly.kcache | (uintptr_t)Ly.vcache) & 15) != 0) return KF_UNSUPPORTED_DATATYPE;
         for (int j = 0; j < 7; j++) {
             const kf_weight& w = Ly.w[j];
-            const int wf = gemv_fmt_of(&w), ef = wf == FMT_Q4 ? FMT_Q4P : (wf == FMT_Q1 ? FMT_Q1T : (wf == FMT_Q2 ? FMT_Q2T : -1));
+            const int wf = gemv_fmt(mat_of(&w)), ef = wf == FMT_Q4 ? FMT_Q4P : (wf == FMT_Q1 ? FMT_Q1T : (wf == FMT_Q2 ? FMT_Q2T : -1));
             if (ef < 0 || (!fmt_io && ef != FMT_Q4P) || (fmt_io && *fmt_io != 0 && *fmt_io != ef)) return KF_UNSUPPORTED_DATATYPE;
             if (fmt_io) *fmt_io = ef;
             if (w.ne0 != Ms[j] || w.ne1 != Ks[j] || w.qzeros || w.qscales || !w.gama || w.lGroup != 128 || (Ks[j] % 128) != 0 || ((uintptr_t)w.data & 15) != 0)
                 return KF_UNSUPPORTED_DATATYPE;
             const long rows = j < 3 ? (long)q_dim + 2 * kv_dim : (j == 4 || j == 5 ? (long)d->ffn : (long)Ms[j]);
-            if (gemv_lpr_log2(Ks[j] / 32, rows) < 2) q4p_ok = false; /* the register-table form needs a group's four blocks in one aligned lane quad (1-bit: the four dwords of a block in one) */
+            if (gemv_lpr_log2(32, Ks[j], rows) < 2) q4p_ok = false; /* the register-table form needs a group's four blocks in one aligned lane quad (1-bit: the four dwords of a block in one) */
             tab[l].m[j].w = (g_u32x4)(uintptr_t)w.data;
             tab[l].m[j].zero = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1);
             tab[l].m[j].step = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1 + (size_t)w.ne0 * w.ne1 / w.lGroup);
@@ -1586,8 +1585,7 @@ int engine_set_head(EngineHost* E, const kf_weight* w, const uint16_t* norm_w, u
     if (w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || !norm_w || !logits || w->ne0 < 64)
         return KF_UNSUPPORTED_DATATYPE;
     // the compile-time geometry of the head phases must be the mat-vec launcher's for this matrix (same lanes per row: same summation order)
-    const int nBlk = E->dim / 8;
-    if (gemv_lpr_log2(nBlk, w->ne0) != c_lpr_log2(nBlk, 1L << 20)) return KF_UNSUPPORTED_DATATYPE;
+    if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE;
     a.head_w = (g_u32x4)(uintptr_t)w->data, a.head_norm = (g_u16)(uintptr_t)norm_w, a.logits = logits, a.d_tokens_out = d_tokens_out, a.vocab = w->ne0;
     return KF_OK;
 }

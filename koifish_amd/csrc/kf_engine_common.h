@@ -1,12 +1,13 @@
 // kf_engine_common.h -- what the two persistent decode engines share: kf_engine.hip (one sequence on all 256 CUs, weights in registers ahead of every hand-off) and
 // kf_xengine.hip (round 5: eight independent sequences, one per XCD, every hand-off through that XCD's L2, weights streamed): the device tables, the tagged-granule
-// accessors, and the mat-vec phase geometry as compile-time types (the lanes per row, rows per wave step and steps per row gemv_launch picks for the same matrices: the
-// canonical summation order is a property of the matrix shape, not of how many workgroups share the rows).
+// accessors, and the mat-vec phase geometry as compile-time types (the lanes per row of the mat-vec rule, gemv_lpr_log2, for the same matrices, and the rows per wave step and
+// steps per row that follow: the canonical summation order is a property of the matrix shape, not of how many workgroups share the rows).
 #pragma once
 #include <stdint.h>
 
 #include "kf_attn_common.h"
 #include "kf_gemv_blocks.h"
+#include "kf_gemv_plan.h"
 
 namespace kf {
 
@@ -276,24 +277,13 @@ struct MvAt {
     int row, col;
     bool ok;
 };
-// ---- mat-vec phase geometry: compile-time constants of the model shape (the same lanes per row, rows per wave step and steps per row
-// gemv_launch picks for these matrices: engine_build checks the two against each other), so a wave's loads are unconditional, their number
-// is static and the compiler can wait with counted vmcnt(N) instead of draining.
-constexpr int c_lpr_log2(int nBlk, long rows) { /* = gemv_lpr_log2 (kf_gemv.hip) */
-    int l = 6;
-    while (l > 0 && (nBlk % (1 << l)) != 0) l--;
-    if ((1 << l) < 16) {
-        l = 6;
-        while ((1 << l) > nBlk) l--;
-    }
-    while (l < 6 && nBlk > (1 << l) && (rows << l) / 64 < 1024 && (nBlk + (2 << l) - 1) / (2 << l) < (nBlk + (1 << l) - 1) / (1 << l)) l++;
-    return l;
-}
+// ---- mat-vec phase geometry: compile-time constants of the model shape (the lanes per row of the one rule, gemv_lpr_log2 in kf_gemv_plan.h, and the rows per wave step
+// and steps per row that follow from it), so a wave's loads are unconditional, their number is static and the compiler can wait with counted vmcnt(N) instead of draining.
 constexpr CPlan c_plan(int K, int epb, int m0, int m1, int m2, bool paired, int nwg) {
     CPlan P{};
     P.K = K, P.nBlk = K / epb;
     const long rows = (long)m0 + (paired ? 0 : m1 + m2);
-    P.lpr_log2 = c_lpr_log2(P.nBlk, rows);
+    P.lpr_log2 = gemv_lpr_log2(epb, K, rows);
     const int LPR = 1 << P.lpr_log2, RPS = 64 / LPR;
     P.iters = (P.nBlk + LPR - 1) / LPR;
     P.njobs = paired ? 1 : (m2 > 0 ? 3 : (m1 > 0 ? 2 : 1));

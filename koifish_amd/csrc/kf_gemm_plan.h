@@ -61,13 +61,6 @@ enum { DEQ_STACK = 0, DEQ_ILV = 1 }; /* dequantised copies: back to back, or gat
 
 // ---- the problem: what an entry knows before it launches anything
 enum GemmEntry { GE_LINEAR = 0, GE_MULTI = 1, GE_GATEUP = 2, GE_QKV_ROPE = 3, GE_BWD_DX = 4, GE_BWD_DW = 5 };
-enum { GM_DATA_AL = 1, GM_TAB_AL = 2 };
-struct GemmMat {
-    int type, quant, awq; /* kf_weight type and quant form; AutoAWQ layout (qzeros / qscales) */
-    int M, K;             /* ne0, ne1 */
-    int lgroup, gama;     /* group size; gama present */
-    int al;               /* GM_DATA_AL: data 16-byte aligned; GM_TAB_AL: the row tables (gama + ne0 + ne1) 16-byte aligned */
-};
 struct GemmProblem {
     int entry;              /* GemmEntry */
     int n_w;                /* matrices: 1 (linear, backward), 2-3 (multi), 2 (gate | up), 3 (Q | K | V) */

@@ -29,6 +29,19 @@ struct GemvJob {
     int slot0;
 };
 
+// a weight as the launch plans see it (kf_gemm_plan.h, kf_gemv_plan.h)
+enum { GM_DATA_AL = 1, GM_TAB_AL = 2 };
+struct GemmMat {
+    int type, quant, awq; /* kf_weight type and quant form; AutoAWQ layout (qzeros / qscales) */
+    int M, K;             /* ne0, ne1 */
+    int lgroup, gama;     /* group size; gama present */
+    int al;               /* GM_DATA_AL: data 16-byte aligned; GM_TAB_AL: the row tables (gama + ne0 + ne1) 16-byte aligned */
+};
+inline GemmMat mat_of(const kf_weight* w) {
+    const bool tab_al = w->gama && ((uintptr_t)(w->gama + w->ne0 + w->ne1) & 15) == 0;
+    return GemmMat{w->type, w->quant, w->qzeros || w->qscales, w->ne0, w->ne1, w->lGroup, w->gama != nullptr, (((uintptr_t)w->data & 15) == 0 ? GM_DATA_AL : 0) | (tab_al ? GM_TAB_AL : 0)};
+}
+
 struct TpPushDev { /* one per (rank, exchange index), written once by kf_tp_commit */
     unsigned long long* peer[8]; /* this rank's slot of the exchange's buffer in every rank's receive area */
     const unsigned* step;        /* device word: generation */
@@ -59,20 +72,6 @@ struct GemvArgs {
     const int32_t* row_map; /* non-NULL: the sparse forward -- slot rows index this list of hot rows (job.M = their number); weights and outputs use row_map[row] */
 };
 
-struct GemvLaunch {
-    GemvArgs args;
-    const kf_weight* w[3];
-    int n;
-    int mode;
-    long target_waves; /* 0: default */
-    int n_hot;         /* args.row_map != NULL: number of entries */
-    int canon;         /* the canonical summation order (one v_pk_fma_f32 per weight pair: an even and an odd chain per lane; oracle/kf_oracle.c section 4c) instead of v_dot2c_f32_bf16 */
-    int blocks;        /* out */
-};
-
-int gemv_launch(hipStream_t st, GemvLaunch& L);
-int gemv_launch_dot2(hipStream_t st, GemvLaunch& L);  /* kf_gemv.hip */
-int gemv_launch_canon(hipStream_t st, GemvLaunch& L); /* kf_gemv_canon.hip: the same file, canonical instantiation */
 // tensor-parallel exchange (kf_tp.hip)
 int tp_reduce_recv_launch(hipStream_t st, const unsigned long long* slots, int R, int n_max, int n, const unsigned* d_step, unsigned per_step, unsigned index,
                           const uint16_t* residual, uint16_t* out, int* d_err);
@@ -80,9 +79,6 @@ int tp_argmax_push_launch(hipStream_t st, const float* val, const int* idx, int 
                           unsigned per_step, unsigned index);
 int tp_pick_launch(hipStream_t st, const unsigned long long* pairs, int R, unsigned* d_step, unsigned per_step, unsigned index, int32_t* d_state, int32_t* d_tokens_out,
                    int* d_err, int vocab);
-int gemv_lpr_log2(int nBlk, long rows); /* lanes per row of a mat-vec launch (kf_gemv.hip) */
-int gemv_lpr_log2_fmt(int fmt, int K, long rows); /* the same per storage (1-bit: K / 32 virtual blocks, divided by four) */
-int gemv_fmt_of(const kf_weight* w);    /* FMT_* of a weight, < 0: not served by the mat-vec kernel */
 void argmax_finish_launch(hipStream_t st, const float* val, const int* idx, int n, int32_t* d_argmax, int32_t* d_state, int32_t* d_tokens_out);
 
 // ---- token-batch GEMM on MFMA: kf_gemm_plan.h (the rule and the launchers)
@@ -127,8 +123,6 @@ struct Knobs {
     int attn_pair_min = 256;  /* prompt tokens from which kf_attn_prefill takes its paired two-key-half form (when there is about one workgroup per CU or fewer) */
     int attn_gq_split = 4; /* canonical decode attention of a GQA-8 model: workgroups per (kv-head, slice), 2 or 4 */
     int q1_tab = 1;       /* 1-bit mat-vec through the LDS selector table (0: the per-bit select form; same bits) */
-    long gemv_waves = 0;  /* > 0: waves a mat-vec launch aims for (0: the launcher's rule) */
-    int gemv_stream = 1;  /* buffer-load form of the long mat-vec launches (0: off) */
     int gemv_xf2 = 1;     /* canonical 4-bit rows too long for fp32 activations in 48 KiB of LDS: two windows of half the block columns (0: bf16 activations, widened per product) */
 };
 extern Knobs g_knobs;

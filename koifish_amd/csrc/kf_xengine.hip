@@ -289,12 +289,11 @@ int xengine_build_tp(const kf_engine_desc* const* ds, int world, void* ws, size_
 int xengine_set_head_tp(XEngineHost* E, const kf_weight* const* ws, const int* row0, const uint16_t* norm_w, uint16_t* logits, int32_t* d_tokens_out, int tokens_stride) {
     XArgs& a = E->args;
     if (!E->tp_bytes || !ws || !row0 || !norm_w || !logits) return KF_INVALID_ARGS;
-    const int nBlk = E->dim / 8;
     long at = 0;
     for (int r = 0; r < XE_NXCD; r++) {
         const kf_weight* w = ws[r];
         if (!w || w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || w->ne0 < 64 || row0[r] != at) return KF_UNSUPPORTED_DATATYPE;
-        if (gemv_lpr_log2(nBlk, w->ne0) != c_lpr_log2(nBlk, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
+        if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
         a.head_w_r[r] = (g_u32x4)(uintptr_t)w->data, a.logits_r[r] = logits + at, a.vocab_r[r] = w->ne0, a.row0_r[r] = row0[r];
         at += w->ne0;
     }
@@ -331,8 +330,7 @@ int xengine_set_head(XEngineHost* E, const kf_weight* w, const uint16_t* norm_w,
     }
     if (w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || !norm_w || !logits || w->ne0 < 64)
         return KF_UNSUPPORTED_DATATYPE;
-    const int nBlk = E->dim / 8;
-    if (gemv_lpr_log2(nBlk, w->ne0) != c_lpr_log2(nBlk, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
+    if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
     a.head_w = (g_u32x4)(uintptr_t)w->data, a.head_norm = (g_u16)(uintptr_t)norm_w, a.logits = logits, a.d_tokens_out = d_tokens_out, a.tokens_stride = tokens_stride, a.vocab = w->ne0;
     return KF_OK;
 }

@@ -153,8 +153,8 @@ struct XCfg {
     // the XCD-local exchange area (dwords)
     static constexpr int xA = 0, qkv = xA + eng_gran_dw(DIM_), ao = qkv + eng_gran_dw(QD_ + 2 * KVD_), xB = ao + eng_gran_dw(QD_), act = xB + eng_gran_dw(DIM_),
                          part = act + eng_gran_dw(FFNP), hbest = part + eng_gran_dw(2 * n_head * PSH), tokg = hbest + eng_gran_dw(2 * XE_NWG), loc_dw = tokg + eng_gran_dw(2);
-    // LM head (bf16 [vocab, DIM]): the geometry gemv_launch picks for a many-row bf16 matrix of this width
-    static constexpr int HnBlk = DIM_ / 8, Hlpr_log2 = c_lpr_log2(DIM_ / 8, 1L << 20), HLPR = 1 << Hlpr_log2, HRPS = 64 >> Hlpr_log2, Hiters = (HnBlk + HLPR - 1) / HLPR;
+    // LM head (bf16 [vocab, DIM]): the geometry of the mat-vec rule for a many-row bf16 matrix of this width
+    static constexpr int HnBlk = DIM_ / 8, Hlpr_log2 = gemv_lpr_log2(8, DIM_, 1L << 20), HLPR = 1 << Hlpr_log2, HRPS = 64 >> Hlpr_log2, Hiters = (HnBlk + HLPR - 1) / HLPR;
     static constexpr int XCH = 8; /* fp32 activations: 16-byte chunks per 32-weight block */
     static constexpr int maxKc = DIM_ > QD_ ? (DIM_ > FFN_ ? DIM_ : FFN_) : (QD_ > FFN_ ? QD_ : FFN_);
     // the waves' attention sums (fp64, [NCW][GQ][hd + 2]) in the second activation buffer when the two would not fit side by side (Qwen3-8B: 2 x 48 KB of activations): the
@@ -247,7 +247,7 @@ struct XRing {
     uint16_t st[D], ze[D];
 };
 // One mat-vec phase as RUN-TIME parameters of one wave (all wave-uniform: scalar registers).  The geometry figures are the compile-time constants of PlanT (the lanes per row,
-// rows per wave step and steps per row gemv_launch picks for the matrices: the canonical summation order), handed to ONE copy of the streaming loop: four typed copies of the
+// rows per wave step and steps per row of the mat-vec rule for the matrices: the canonical summation order), handed to ONE copy of the streaming loop: four typed copies of the
 // DEPTH-times unrolled block code were 150 KB of instructions.
 struct XPhase {
     EngMat m, m2;    /* m2: up_proj beside gate_proj (paired) */

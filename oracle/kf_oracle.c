@@ -509,7 +509,7 @@ static float dot16(const float* w, const float* x, int n) {
  *         dependent chain each); the mat-vec kernel keeps them as register pairs.  The lanes-per-row figure of such a row is the rule's value for K / 32 "virtual" blocks
  *         divided by the sub-blocks per block (kfo_lpr_log2_epb);
  *       - the LPR lane values are added by a balanced binary tree (lanes 2j + 2j+1, then pairs of pairs, ...).
- *     lpr_log2 = kfo_lpr_log2(blocks per row, rows of the launch): the rule of kf::gemv_lpr_log2 (koifish_amd/csrc/kf_gemv.hip), restated.
+ *     lpr_log2 = kfo_lpr_log2(blocks per row, rows of the launch): the rule of kf::gemv_lpr_log2 (koifish_amd/csrc/kf_gemv_plan.h), restated.
  *     `rows` = the rows of ALL matrices a launch multiplies (Q | K | V together; gate alone for the paired gate / up launch).
  * ---------------------------------------------------------------------------------------------- */
 static int g_order = 0; /* 0: the dot16 order of sections 4 / 4b; 1: canonical */

@@ -1,4 +1,5 @@
-"""Large 4-bit mat-vec shapes of Qwen3-32B, timed alone with cold weights (6 rotating copies): KF_GEMV_WAVES / KF_GEMV_G / KF_GEMV_STREAM sweeps."""
+"""Large 4-bit mat-vec shapes of Qwen3-32B, timed alone with cold weights (6 rotating copies); once for KF_GEMV_WAVES / KF_GEMV_G /
+KF_GEMV_STREAM sweeps, now constants of koifish_amd/csrc/kf_gemv_plan.h."""
 import sys, os, ctypes as C, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from koifish_amd.runtime import Context, _ptr

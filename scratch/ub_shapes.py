@@ -1,6 +1,6 @@
 """4-bit mat-vec launches timed alone in the canonical order, cold weights (rotating copies), per knob setting inside ONE process:
     python scratch/ub_shapes.py [tp|big|all]     tp: the TP = 8 rank shards of Qwen3-32B (the launches of Fish::TPPhase); big: the whole matrices on one GPU
-Knob sweeps: gemv_waves (0 = the launcher's rule), gemv_xf2 (the two-window fp32 staging of the 25600-wide rows)."""
+Knob sweep: gemv_xf2 (the two-window fp32 staging of the 25600-wide rows); the waves per launch are constants of koifish_amd/csrc/kf_gemv_plan.h."""
 import ctypes as C
 import os
 import sys
@@ -45,12 +45,11 @@ def bench(name, M, K, settings, reps=200):
         us = ctx.elapsed_ms(e0, e1) * 1e3 / reps
         out.append("%s %.1f us (%.0f GB/s)" % (",".join("%s=%s" % kv for kv in st.items()), us, b / us / 1e3))
     print("%-22s %6d x %-6d %5.1f MB: %s" % (name, M, K, b / 1e6, "   ".join(out)), flush=True)
-    knob("gemv_waves", 0)
     knob("gemv_xf2", 1)
 
 
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
-W = [{"gemv_waves": w} for w in (0, 1024, 2048, 4096, 8192)]
+W = [{}]   # the plan's own choice
 if which in ("tp", "all"):
     bench("o_proj shard", 5120, 1024, W)
     bench("down_proj shard", 5120, 3200, W)
@@ -58,5 +57,5 @@ if which in ("tp", "all"):
     bench("gate rows shard", 3200, 5120, W)
 if which in ("big", "all"):
     bench("down_proj 32B", 5120, 25600, [{"gemv_xf2": 1}, {"gemv_xf2": 0}], reps=60)
-    bench("gate_proj 32B", 25600, 5120, [{"gemv_waves": 0}], reps=60)
-    bench("o_proj 32B", 5120, 8192, [{"gemv_waves": 0}], reps=60)
+    bench("gate_proj 32B", 25600, 5120, W, reps=60)
+    bench("o_proj 32B", 5120, 8192, W, reps=60)
