@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
 
@@ -640,8 +641,11 @@ int kf_qknorm_rope(kf_ctx* c, kf_bf16* q, kf_bf16* k, const kf_bf16* wq, const k
     RET(kf::qknorm_rope_launch(c->stream, q, k, wq, wk, table, pos, d_pos, n_head, n_kv, hd, eps));
 }
 
-static size_t attn_part_bytes(int n_head, int hd) { return sizeof(double) * (size_t)n_head * kf::KF_ATTN_MAX_SPLITS * (hd + 2); } /* {O[hd], L, m} fp64 per (head, slice) */
-size_t kf_attn_scratch_bytes(int n_head, int hd) { return attn_part_bytes(n_head, hd) + kf::KF_ATTN_CNT_BYTES; /* + arrival counters */ }
+size_t kf_attn_scratch_bytes(int n_head, int hd) { return kf::attn_decode_scratch_bytes(n_head, hd); }
+static kf::AttnProblem attn_problem(int entry, kf_ctx* c, int n_head, int n_kv, int hd, int pos, int n_tok, int n_seq, const void* q, const void* out, long long q_stride,
+                                    long long out_stride, long long kv_stride) { /* q 16-byte and out 8-byte aligned: the tile kernel's rows */
+    return kf::AttnProblem{entry, n_head, n_kv, hd, pos, n_tok, n_seq, c->canonical, (al16(q) ? kf::ATTN_Q_AL : 0) | (((uintptr_t)out & 7) == 0 ? kf::ATTN_OUT_AL : 0), q_stride, out_stride, kv_stride};
+}
 
 int kf_attn_decode(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, int pos, const int32_t* d_pos, int n_head, int n_kv, int hd,
                    int kv_stride, void* scratch) {
@@ -654,7 +658,7 @@ int kf_attn_decode(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf16
     a.q = q, a.kcache = const_cast<kf_bf16*>(kc), a.vcache = vc, a.out = out, a.part = (float*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
     a.pos = pos, a.d_pos = d_pos, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
     a.counters = (int*)scratch; /* the first KF_ATTN_CNT_BYTES: arrival counters (fixed place whatever the shape) */
-    RET(kf::attn_launch(c->stream, a));
+    RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q, out, 0, 0, 0))));
 }
 
 int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, const kf_bf16* wq, const kf_bf16* wk,
@@ -669,7 +673,7 @@ int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16
     a.wq_norm = wq, a.wk_norm = wk, a.rope_table = table, a.eps = eps;
     a.pos = pos, a.d_pos = d_pos, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
     a.counters = (int*)scratch;
-    RET(kf::attn_launch(c->stream, a));
+    RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q_raw, out, 0, 0, 0))));
 }
 
 int kf_swiglu(kf_ctx* c, const kf_bf16* gate, const kf_bf16* up, kf_bf16* out, int n) {
@@ -847,18 +851,19 @@ int kf_attn_prefill(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf1
     CHKCTX(c);
     if (!q || !kc || !vc || !out || n_tok < 1 || pos0 < 0) return fail(KF_INVALID_ARGS, "kf_attn_prefill: bad args");
     if (!al16(kc) || !al16(vc) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill: cache not 16-byte aligned");
-    if (n_tok >= 8) { /* fewer tokens: the per-token form of the decode kernel */
-        const int rc = kf::attn_prefill_mfma_launch(c->stream, q, kc, vc, out, pos0, n_tok, q_stride, n_head, n_kv, hd, kv_stride);
-        if (rc < 0) return fail(rc, "kf_attn_prefill: launch failed (%d)", rc);
-        if (rc == KF_OK) return KF_OK;
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_PROMPT, c, n_head, n_kv, hd, pos0, n_tok, 1, q, out, q_stride, 0, kv_stride));
+    if (p.route != kf::ATTN_PER_TOKEN) {
+        const int rc = kf::attn_prefill_mfma_launch(c->stream, p, q, kc, vc, out, pos0, n_tok, q_stride, n_kv, kv_stride, 1, 0);
+        if (rc != KF_OK) return fail(rc, "kf_attn_prefill: launch failed (%d)", rc);
+        return KF_OK;
     }
     kf::AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.canon = c->canonical;
     a.q = q, a.kcache = const_cast<kf_bf16*>(kc), a.vcache = vc, a.out = out;
     a.pos = pos0, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
-    a.n_tok = n_tok, a.q_stride = q_stride, a.one_slice = 1;
-    RET(kf::attn_launch(c->stream, a));
+    a.q_stride = q_stride, a.one_slice = 1;
+    RET(kf::attn_launch(c->stream, a, p));
 }
 
 int kf_attn_prefill_batch(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, kf_bf16* out, int n_tok, int64_t q_stride, int n_head, int n_kv, int hd,
@@ -866,18 +871,18 @@ int kf_attn_prefill_batch(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const k
     CHKCTX(c);
     if (!q || !k || !v || !out || n_tok < 1 || n_seq < 1) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch: bad args");
     if (!al16(k) || !al16(v) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill_batch: k / v rows not 16-byte aligned");
-    const int rc = kf::attn_prefill_mfma_launch(c->stream, q, k, v, out, 0, n_tok, q_stride, n_head, n_kv, hd, kv_stride, n_seq);
-    if (rc == 1) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch: shape not covered by the tile kernel (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8, 16-byte aligned rows)");
-    RET(rc);
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_BATCH, c, n_head, n_kv, hd, 0, n_tok, n_seq, q, out, q_stride, 0, kv_stride));
+    if (p.status != KF_OK) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch: shape not covered by the tile kernel (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8, 16-byte aligned rows)");
+    RET(kf::attn_prefill_mfma_launch(c->stream, p, q, k, v, out, 0, n_tok, q_stride, n_kv, kv_stride, n_seq, 0));
 }
 int kf_attn_prefill_batch_strided(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, kf_bf16* out, int n_tok, int64_t q_stride, int64_t out_stride, int n_head,
                                   int n_kv, int hd, int kv_stride, int n_seq) {
     CHKCTX(c);
     if (!q || !k || !v || !out || n_tok < 1 || n_seq < 1 || out_stride < (int64_t)n_head * hd) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch_strided: bad args");
     if (!al16(k) || !al16(v) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill_batch_strided: k / v rows not 16-byte aligned");
-    const int rc = kf::attn_prefill_mfma_launch(c->stream, q, k, v, out, 0, n_tok, q_stride, n_head, n_kv, hd, kv_stride, n_seq, out_stride);
-    if (rc == 1) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch_strided: shape not covered by the tile kernel (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8, 16-byte aligned rows)");
-    RET(rc);
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_BATCH, c, n_head, n_kv, hd, 0, n_tok, n_seq, q, out, q_stride, out_stride, kv_stride));
+    if (p.status != KF_OK) return fail(KF_INVALID_ARGS, "kf_attn_prefill_batch_strided: shape not covered by the tile kernel (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8, 16-byte aligned rows)");
+    RET(kf::attn_prefill_mfma_launch(c->stream, p, q, k, v, out, 0, n_tok, q_stride, n_kv, kv_stride, n_seq, out_stride));
 }
 
 int kf_set_state(kf_ctx* c, int32_t* d_state, int token, int pos) {
@@ -1022,7 +1027,7 @@ int kf_linear_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, co
     }
     return KF_OK;
 }
-size_t kf_attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return (T < 1 || n_head < 1 || n_seq < 1) ? 0 : sizeof(float) * 2 * (size_t)T * n_head * n_seq; }
+size_t kf_attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return kf::attn_backward_scratch_bytes(T, n_head, n_seq); }
 int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,
                      kf_bf16* dk, kf_bf16* dv, long long ld_d, int T, int n_head, int n_kv, int hd, int n_seq, void* scratch) {
     CHKCTX(c);
@@ -1031,10 +1036,9 @@ int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf1
         return fail(KF_BLAS_UNALIGN, "kf_attn_backward: rows must be 16-byte aligned");
     if (ld_qkv < (long long)n_head * hd || ld_o < (long long)n_head * hd || ld_d < (long long)n_head * hd) return fail(KF_INVALID_ARGS, "kf_attn_backward: row stride below n_head * head_dim");
     if (T < 1 || n_head < 1) return fail(KF_INVALID_ARGS, "kf_attn_backward: T / n_head < 1");
-    int r = kf::attn_backward_mfma_launch(c->stream, q, k, v, ld_qkv, o, dO, ld_o, dq, dk, dv, ld_d, T, n_head, hd, n_seq, (float*)scratch, n_kv, ld_qkv, ld_d);
-    if (r == 1) r = KF_UNSUPPORTED_DATATYPE; /* shape outside the MFMA tile kernels */
-    if (r == KF_UNSUPPORTED_DATATYPE) return fail(r, "kf_attn_backward: head_dim %d not covered (64, 128)", hd);
-    RET(r);
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_BACKWARD, c, n_head, n_kv, hd, 0, T, n_seq, q, dq, 0, 0, 0));
+    if (p.status != KF_OK) return fail(p.status, "kf_attn_backward: head_dim %d not covered (64, 128)", hd);
+    RET(kf::attn_backward_mfma_launch(c->stream, p, q, k, v, ld_qkv, o, dO, ld_o, dq, dk, dv, ld_d, T, (float*)scratch, ld_qkv, ld_d));
 }
 int kf_embed_pos(kf_ctx* c, const kf_bf16* wte, long long ldw, const kf_bf16* wpe, const int32_t* tokens, int B, int T, int C, int V, kf_bf16* out) {
     CHKCTX(c);
@@ -1364,8 +1368,14 @@ int kfdbg_gemv_plan(const kf::GemvProblem* P, kf::GemvPlan* out) {
     *out = kf::gemv_plan(*P);
     return 0;
 }
+// the plan kf::attn_plan makes for an attention problem (no HIP call): tests/test_attn_plan_cpu.py
+int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::attn_plan(*P);
+    return 0;
+}
 // development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process (the token-batch routes have none: kf_gemm_plan.h; the mat-vec's
-// slots per wave and load form none either: kf_gemv_plan.h)
+// slots per wave and load form none either: kf_gemv_plan.h; nor the attention routes and forms: kf_attn_plan.h)
 int kfdbg_set_knob(const char* name, long value) {
     if (!name) return -1;
     kf::Knobs& k = kf::g_knobs;
@@ -1373,8 +1383,6 @@ int kfdbg_set_knob(const char* name, long value) {
     else if (!strcmp(name, "q2_tab")) k.q2_tab = (int)value;
     else if (!strcmp(name, "q1_tab")) k.q1_tab = (int)value;
     else if (!strcmp(name, "gemv_xf2")) k.gemv_xf2 = (int)value;
-    else if (!strcmp(name, "attn_gq_split")) k.attn_gq_split = (int)value;
-    else if (!strcmp(name, "attn_pair_min")) k.attn_pair_min = (int)value;
     else return -1;
     return 0;
 }

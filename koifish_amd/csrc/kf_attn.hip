@@ -20,7 +20,11 @@
 // nsp-1 reads every partial with agent-scope relaxed atomic loads (`sc1`) after a barrier, and re-zeroes the counter.
 #include <stdlib.h>
 
+#include <array>
+#include <utility>
+
 #include "kf_attn_common.h"
+#include "kf_attn_plan.h"
 
 namespace kf {
 
@@ -471,73 +475,32 @@ __global__ void __launch_bounds__(64) qknorm_rope_kernel(uint16_t* q, uint16_t* 
     for (int i = threadIdx.x; i < hd; i += 64) src[i] = buf[i];
 }
 
-// slices: ~64 keys each, enough workgroups to cover the chip, bounded by the scratch layout
-int attn_splits(int pos_bound, int n_kv) {
-    // keys per slice: one workgroup streams a slice in batches of 64 keys (hd 128, 4 waves); short contexts stay in ONE slice per
-    // kv-head (no cross-workgroup hand-off at all), long ones are cut so that the chip is covered.
-    constexpr int slice = 64, single = 192; /* keys per slice / longest context served by one slice (settled by the round-1 sweeps) */
-    const int len = pos_bound + 1;
-    if (len <= single) return 1;
-    int nsp = (len + slice - 1) / slice;
-    int cap = 512 / n_kv;
-    if (cap < 1) cap = 1;
-    if (nsp > cap) nsp = cap;
-    if (nsp > KF_ATTN_MAX_SPLITS) nsp = KF_ATTN_MAX_SPLITS;
-    if (nsp < 1) nsp = 1;
-    return nsp;
+// the instantiations attn_plan can name, by (order, query heads per workgroup, waves, hd): 8 waves only at ATTN_NW8_GQ heads or fewer, the canonical order only with
+// its ATTN_CANON_GQ_WG heads per workgroup or fewer
+constexpr int AF_HD = 1, AF_NW = 2, AF_GQ = 4, AF_CANON = 16, ATTN_FORMS = 2 * AF_CANON;
+constexpr int attn_form_index(bool canon, int gq, int nw, int hd) { return canon * AF_CANON + __builtin_ctz(gq) * AF_GQ + (nw == 8) * AF_NW + (hd == 128) * AF_HD; }
+using AttnKernel = void (*)(AttnArgs);
+template <int I, bool CANON = I / AF_CANON, int GQ = 1 << (I / AF_GQ % 4), int NW = I / AF_NW % 2 ? 8 : 4, int HD = I % 2 ? 128 : 64>
+constexpr AttnKernel attn_form() {
+    static_assert(attn_form_index(CANON, GQ, NW, HD) == I, "attn_form_index");
+    if constexpr ((NW == 8 && GQ > ATTN_NW8_GQ) || (CANON && GQ > ATTN_CANON_GQ_WG)) return nullptr;
+    else if constexpr (CANON) return attn_kernel<GQ, NW, HD>;
+    else return attn_fast_kernel<GQ, NW, HD>;
+}
+template <int... I>
+constexpr std::array<AttnKernel, ATTN_FORMS> attn_forms(std::integer_sequence<int, I...>) {
+    return {{attn_form<I>()...}};
 }
 
-int attn_launch(hipStream_t st, AttnArgs& a) {
-    const int hd = a.hd;
-    if (hd < 64 || hd > 128 || (hd & (hd - 1)) != 0) return KF_INVALID_ARGS; /* 8 dims per lane, one RoPE trip per wave */
-    if (a.n_kv <= 0 || a.n_head % a.n_kv != 0) return KF_INVALID_ARGS;
-    const int GQ = a.n_head / a.n_kv;
-    const bool batch = a.one_slice != 0;
-    if (a.n_tok < 1) a.n_tok = 1;
-    if (!batch) a.n_tok = 1, a.q_stride = 0;
-    const int pos_max = a.pos + a.n_tok - 1;
-    const int nsp = batch ? 1 : attn_splits(a.pos, a.n_kv);
-    a.n_splits = nsp;
-    a.chunk = (pos_max + 1 + nsp - 1) / nsp;
-    a.inv_sqrt_hd_den = sqrtf((float)hd);
-    a.gq_split = (a.canon && GQ == 8) ? (g_knobs.attn_gq_split == 8 ? 8 : (g_knobs.attn_gq_split == 4 ? 4 : 2)) : ((a.canon && GQ == 4 && g_knobs.attn_gq_split >= 4) ? 2 : 1);
-    a.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (a.n_kv * a.gq_split); /* arrival counters of different kv-heads in different cache lines: atomics on one line serialise */
-    if (a.cnt_stride > 64) a.cnt_stride = 64;
-    if (a.cnt_stride < 1) return KF_INVALID_ARGS;
-    // one 64-key batch per 4-wave workgroup (one wave per SIMD: the kernel is bound by VALU issue inside a latency chain, so
-    // spreading the keys over more CUs beats more waves per CU); 8 waves once the slices have to grow past 128 keys
-    int NW = (GQ <= 2 && a.chunk > 128) ? 8 : 4;
-    const int gq_wg = GQ / a.gq_split; /* query heads per workgroup */
-    size_t smem = sizeof(double) * ((size_t)NW * gq_wg * (hd + 2)) + sizeof(uint16_t) * ((size_t)gq_wg * hd + hd) + 16;
-    const size_t smem_fast = sizeof(uint16_t) * ((size_t)GQ * hd + hd) + sizeof(float) * (NW * GQ + 4 + (size_t)NW * GQ * (hd + 4));
-    if (!a.canon) smem = smem_fast;
-    dim3 grid(nsp, a.n_kv * a.gq_split, a.n_tok);
-#define KF_ATTN_GO(gq, nw)                                                                                       \
-    do {                                                                                                        \
-        if (a.canon) {                                                                                          \
-            if (hd == 128) hipLaunchKernelGGL((attn_kernel<gq, nw, 128>), grid, dim3(nw * 64), smem, st, a);      \
-            else hipLaunchKernelGGL((attn_kernel<gq, nw, 64>), grid, dim3(nw * 64), smem, st, a);                 \
-        } else {                                                                                                \
-            if (hd == 128) hipLaunchKernelGGL((attn_fast_kernel<gq, nw, 128>), grid, dim3(nw * 64), smem, st, a); \
-            else hipLaunchKernelGGL((attn_fast_kernel<gq, nw, 64>), grid, dim3(nw * 64), smem, st, a);            \
-        }                                                                                                       \
-    } while (0)
-    switch (GQ) {
-        case 1: if (NW == 8) KF_ATTN_GO(1, 8); else KF_ATTN_GO(1, 4); break;
-        case 2: if (NW == 8) KF_ATTN_GO(2, 8); else KF_ATTN_GO(2, 4); break;
-        case 4:
-            if (a.gq_split == 2) KF_ATTN_GO(2, 4); /* canonical order: two workgroups of two heads each, as for GQA-8 */
-            else KF_ATTN_GO(4, 4);
-            break;
-        case 8:
-            if (a.gq_split == 8) KF_ATTN_GO(1, 4); /* one head per workgroup */
-            else if (a.gq_split == 4) KF_ATTN_GO(2, 4); /* four workgroups of two heads each */
-            else if (a.gq_split == 2) KF_ATTN_GO(4, 4); /* two workgroups of four heads each (canonical order) */
-            else KF_ATTN_GO(8, 4);
-            break;
-        default: return KF_INVALID_ARGS;
-    }
-#undef KF_ATTN_GO
+int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p) {
+    static constexpr std::array<AttnKernel, ATTN_FORMS> forms = attn_forms(std::make_integer_sequence<int, ATTN_FORMS>());
+    if (p.status != KF_OK) return p.status;
+    const AttnKernel k = forms[attn_form_index(p.canon, p.gq, p.nw, p.hd)];
+    if (!k) return KF_INTERNAL_ERR; /* a form attn_plan never names */
+    a.n_tok = p.grid[2], a.n_splits = p.n_splits, a.chunk = p.chunk, a.gq_split = p.gq_split, a.cnt_stride = p.cnt_stride;
+    a.inv_sqrt_hd_den = sqrtf((float)p.hd);
+    void* args[] = {&a};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(k), dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.threads), args, (size_t)p.lds, st);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

@@ -11,7 +11,7 @@
 //              P = exp(scale S - L_q), dS = P o (dP - D_q)  L, D per accumulator ROW: four ds_read_b128 each
 //              dV^T[d][key] += dO^T[d][q] . P[q][key],  dK^T[d][key] += Q^T[d][q] . dS[q][key]
 // P and dS enter their products as single bf16 values (gradients are compared at 2^-7 of scale); everything else fp32.
-#include "kf_kernels.h"
+#include "kf_attn_plan.h"
 
 namespace kf {
 
@@ -316,22 +316,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_mfma_kernel(const uint16_t* 
         }
 }
 
-// KF_OK launched; 1 = shape not covered by the MFMA form
-int attn_backward_mfma_launch(hipStream_t st, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o, const uint16_t* dO, long long ld_o,
-                              uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, int T, int n_head, int hd, int n_seq, float* scratch, int n_kv, long long ld_kv, long long ld_dkv) {
-    if ((hd != 64 && hd != 128) || n_kv < 1 || n_head % n_kv != 0) return 1;
-    const int gq = n_head / n_kv;
-    const float scale = 1.0f / sqrtf((float)hd);
+int attn_backward_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o,
+                              const uint16_t* dO, long long ld_o, uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, int T, float* scratch, long long ld_kv,
+                              long long ld_dkv) {
+    const float scale = 1.0f / sqrtf((float)p.hd);
     float* Lb = scratch;
-    float* Db = scratch + (size_t)n_seq * n_head * T;
-    const dim3 grid((T + 127) / 128, n_head, n_seq), grid_kv((T + 127) / 128, n_kv, n_seq);
-    if (hd == 64) {
-        hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<64>), grid, dim3(256), 0, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, T, scale, gq, ld_kv);
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<64>), grid_kv, dim3(256), 0, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, T, scale, gq, ld_kv, ld_dkv);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<128>), grid, dim3(256), 0, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, T, scale, gq, ld_kv);
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<128>), grid_kv, dim3(256), 0, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, T, scale, gq, ld_kv, ld_dkv);
-    }
+    float* Db = scratch + (size_t)p.grid[2] * p.grid[1] * T;
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), grid_kv(p.grid_kv[0], p.grid_kv[1], p.grid_kv[2]);
+    const auto dq_k = p.hd == 128 ? attn_bwd_dq_mfma_kernel<128> : attn_bwd_dq_mfma_kernel<64>;
+    const auto dkv_k = p.hd == 128 ? attn_bwd_dkv_mfma_kernel<128> : attn_bwd_dkv_mfma_kernel<64>;
+    hipLaunchKernelGGL(dq_k, grid, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, T, scale, p.gq, ld_kv);
+    hipLaunchKernelGGL(dkv_k, grid_kv, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, T, scale, p.gq, ld_kv, ld_dkv);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

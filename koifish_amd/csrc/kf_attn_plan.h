@@ -1,0 +1,125 @@
+// kf_attn_plan.h -- how attention is launched: kf::attn_plan, one pure host function, picks the route, kernel form, slices, grid, threads, LDS and scratch of every
+// attention launch (kf_attn_decode / kf_attn_block, kf_attn_prefill, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
+// kf_attn_prefill.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
+#pragma once
+#include "kf_kernels.h"
+
+namespace kf {
+
+// ---- the thresholds
+// ~64 keys per slice: short contexts in ONE slice per kv-head (no cross-workgroup hand-off), long ones cut so that the chip is covered, at most 512 / n_kv and
+// KF_ATTN_MAX_SPLITS (the scratch layout) slices (the round-1 sweeps)
+constexpr int ATTN_SLICE_KEYS = 64, ATTN_ONE_SLICE_KEYS = 192, ATTN_SLICE_WGS = 512;
+// one 64-key batch per 4-wave workgroup (one wave per SIMD: the kernel is bound by VALU issue inside a latency chain, so spreading the keys over more CUs beats more
+// waves per CU); 8 waves once the slices of a kv-head with at most ATTN_NW8_GQ query heads grow past ATTN_NW8_KEYS keys
+constexpr int ATTN_NW8_KEYS = 128, ATTN_NW8_GQ = 2;
+// the canonical order deals the query heads of GQA-4 / GQA-8 to workgroups of two: 8 heads in one workgroup need 411 registers (one wave per SIMD), 2 need 224
+constexpr int ATTN_CANON_GQ_WG = 2;
+// arrival counters at the head of the decode scratch, at most 64 ints apart: the counters of two (kv-head, part) on different cache lines (atomics on one line serialise)
+constexpr int KF_ATTN_CNT_BYTES = 16384, ATTN_CNT_STRIDE_MAX = 64;
+// prompts: the MFMA tile kernel (128 (token, query head) columns per workgroup, as in the backward) from 8 tokens; fewer: one slice of the decode kernel per token
+constexpr int ATTN_TILE_MIN_TOK = 8, ATTN_TILE_COLS = 128;
+// the paired form (two key halves per workgroup) at about one workgroup per CU or fewer: the launch lasts as long as its last query block (2047 tokens, 16 / 8 heads
+// x 128: 81 -> 67 us); with more workgroups the halves only compete for the CU (8 x 1024 x 25 x 64: 130 vs 143 us); short prompts take a few us either way
+constexpr long ATTN_PAIR_MAX_WGS = 320;
+constexpr int ATTN_PAIR_MIN_TOK = 256;
+constexpr int AP_KT = 32, AP_KT_LONG = 64; /* keys per staged tile: tile kernel, paired form */
+constexpr int AP_VPAD = 32;                /* V row padding, elements (64 B): rows 4 apart in a transposing read land on distinct 16-bank groups (K rows: 8) */
+
+// ---- the slice rule: slices, keys per slice and waves of the decode kernel for keys 0 .. pos_bound (one_slice: the per-token form)
+struct AttnSlices {
+    int n_splits, chunk, nw;
+};
+constexpr AttnSlices attn_slices(int pos_bound, int n_kv, int gq, bool one_slice = false) {
+    const int len = pos_bound + 1, cap = ATTN_SLICE_WGS / n_kv;
+    int nsp = 1;
+    if (!one_slice && len > ATTN_ONE_SLICE_KEYS) {
+        nsp = (len + ATTN_SLICE_KEYS - 1) / ATTN_SLICE_KEYS;
+        if (nsp > cap) nsp = cap < 1 ? 1 : cap;
+        if (nsp > KF_ATTN_MAX_SPLITS) nsp = KF_ATTN_MAX_SPLITS;
+    }
+    const int chunk = (len + nsp - 1) / nsp;
+    return AttnSlices{nsp, chunk, gq <= ATTN_NW8_GQ && chunk > ATTN_NW8_KEYS ? 8 : 4};
+}
+// scratch: the decode kernel's {O[hd], L, m} fp64 partials per (head, slice) behind the counters; the backward's L and D per (sequence, head, row)
+constexpr size_t attn_decode_scratch_bytes(int n_head, int hd) { return sizeof(double) * (size_t)n_head * KF_ATTN_MAX_SPLITS * (hd + 2) + KF_ATTN_CNT_BYTES; }
+constexpr size_t attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return (T < 1 || n_head < 1 || n_seq < 1) ? 0 : sizeof(float) * 2 * (size_t)T * n_head * n_seq; }
+
+// ---- the problem
+enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3 };
+enum { ATTN_Q_AL = 1, ATTN_OUT_AL = 2 }; /* q 16-byte aligned, out 8-byte aligned */
+struct AttnProblem {
+    int entry, n_head, n_kv, hd;
+    int pos;                                   /* ATTN_DECODE: the position bound; ATTN_PROMPT: the first token's */
+    int n_tok, n_seq, canon, al;               /* tokens per sequence (the backward's T), sequences, the canonical order, ATTN_Q_AL | ATTN_OUT_AL */
+    long long q_stride, out_stride, kv_stride; /* elements between rows; out_stride 0: q_stride */
+};
+// ---- the plan, by route:
+//   ATTN_SLICED     attn_kernel (canon) / attn_fast_kernel <gq, nw, hd> on (n_splits, n_kv * gq_split, 1); the last workgroup of a (kv-head, part) merges the slices
+//   ATTN_PER_TOKEN  the same kernels on (1, n_kv * gq_split, n_tok), no scratch
+//   ATTN_TILE / ATTN_PAIRED  attn_prefill_kernel<hd, gq, kh, kt> on (blocks, n_kv, n_seq); kh = 2: a block from the front and one from the back per workgroup
+//   ATTN_BWD        attn_bwd_dq_mfma_kernel<hd> on grid, then attn_bwd_dkv_mfma_kernel<hd> on grid_kv
+enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4 };
+struct AttnPlan {
+    int status, route;             /* KF_OK or the refusal; the route (of a refusal: the one that refused) */
+    int canon, gq, nw, hd, kh, kt; /* the kernel form; gq = query heads per workgroup */
+    int gq_split, n_splits, chunk, cnt_stride;
+    int grid[3], grid_kv[3], threads, lds;
+    long long scratch; /* bytes the route needs */
+};
+
+inline AttnPlan attn_plan(const AttnProblem& P) {
+    AttnPlan p = {};
+    auto refuse = [&p](int status) { return p.status = status, p; };
+    const bool kv_ok = P.n_kv > 0 && P.n_head % P.n_kv == 0, hd_ok = P.hd == 64 || P.hd == 128;
+    const int GQ = kv_ok ? P.n_head / P.n_kv : 0;
+    const bool gq_ok = GQ == 1 || GQ == 2 || GQ == 4 || GQ == 8;
+    p.hd = P.hd, p.gq = GQ;
+    if (P.entry == ATTN_BACKWARD) {
+        p.route = ATTN_BWD;
+        if (!hd_ok || !kv_ok) return refuse(KF_UNSUPPORTED_DATATYPE);
+        p.grid[0] = p.grid_kv[0] = (P.n_tok + ATTN_TILE_COLS - 1) / ATTN_TILE_COLS, p.grid[1] = P.n_head, p.grid_kv[1] = P.n_kv, p.grid[2] = p.grid_kv[2] = P.n_seq;
+        p.threads = 256, p.scratch = (long long)attn_backward_scratch_bytes(P.n_tok, P.n_head, P.n_seq);
+        return p;
+    }
+    // the tile kernel: 16-byte q and K / V rows, 8-byte out rows
+    const long long out_stride = P.out_stride > 0 ? P.out_stride : P.q_stride;
+    const bool tile_ok = !(out_stride & 3) && hd_ok && kv_ok && !(P.q_stride & 7) && !(P.kv_stride & 7) && (P.al & ATTN_Q_AL) && (P.al & ATTN_OUT_AL) && gq_ok;
+    if (P.entry == ATTN_BATCH || (P.entry == ATTN_PROMPT && P.n_tok >= ATTN_TILE_MIN_TOK && tile_ok)) {
+        p.route = ATTN_TILE;
+        if (!tile_ok) return refuse(KF_INVALID_ARGS);
+        const int TQ = ATTN_TILE_COLS / GQ; /* tokens per workgroup */
+        p.grid[0] = (P.n_tok + TQ - 1) / TQ, p.grid[1] = P.n_kv, p.grid[2] = P.n_seq;
+        if ((long)p.grid[0] * P.n_kv * P.n_seq <= ATTN_PAIR_MAX_WGS && P.n_tok >= ATTN_PAIR_MIN_TOK)
+            p.route = ATTN_PAIRED, p.grid[0] = ((P.n_tok + TQ / 2 - 1) / (TQ / 2) + 1) / 2; /* half blocks of TQ / 2 tokens, two per workgroup */
+        p.kh = p.route == ATTN_PAIRED ? 2 : 1, p.kt = p.kh == 2 ? AP_KT_LONG : AP_KT, p.threads = 256 * p.kh;
+        p.lds = (int)sizeof(uint16_t) * p.kh * (2 * p.kt * (P.hd + 8) + 2 * p.kt * (P.hd + AP_VPAD));
+        return p;
+    }
+    // the decode kernel: sliced (one token), or one slice per token (a prompt the tile kernel does not take)
+    const bool per_token = P.entry == ATTN_PROMPT;
+    p.route = per_token ? ATTN_PER_TOKEN : ATTN_SLICED;
+    if (!hd_ok || !kv_ok || !gq_ok) return refuse(KF_INVALID_ARGS);
+    const int n_tok = per_token ? P.n_tok : 1;
+    const AttnSlices s = attn_slices(P.pos + n_tok - 1, P.n_kv, GQ, per_token);
+    p.canon = P.canon != 0, p.gq_split = p.canon && GQ > ATTN_CANON_GQ_WG ? GQ / ATTN_CANON_GQ_WG : 1;
+    p.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (P.n_kv * p.gq_split);
+    if (p.cnt_stride > ATTN_CNT_STRIDE_MAX) p.cnt_stride = ATTN_CNT_STRIDE_MAX;
+    if (p.cnt_stride < 1) return refuse(KF_INVALID_ARGS);
+    p.gq = GQ / p.gq_split, p.nw = s.nw, p.n_splits = s.n_splits, p.chunk = s.chunk, p.threads = 64 * s.nw;
+    p.grid[0] = s.n_splits, p.grid[1] = P.n_kv * p.gq_split, p.grid[2] = n_tok;
+    const size_t q_lds = sizeof(uint16_t) * ((size_t)p.gq * P.hd + P.hd); /* prepared q heads + the new key */
+    p.lds = (int)(p.canon ? sizeof(double) * ((size_t)s.nw * p.gq * (P.hd + 2)) + q_lds + 16 : q_lds + sizeof(float) * (s.nw * p.gq + 4 + (size_t)s.nw * p.gq * (P.hd + 4)));
+    p.scratch = per_token ? 0 : (long long)attn_decode_scratch_bytes(P.n_head, P.hd);
+    return p;
+}
+
+// ---- the launchers carry out a plan with status KF_OK: KF_OK, KF_INTERNAL_ERR (a form the plan never names) or KF_HIP_CHECK
+int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p); /* kf_attn.hip, ATTN_SLICED / ATTN_PER_TOKEN (returns p.status when not KF_OK); a's geometry from p */
+int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, int pos0, int n_tok,
+                             long long q_stride, int n_kv, int kv_stride, int n_seq, long long out_stride); /* kf_attn_prefill.hip, ATTN_TILE / ATTN_PAIRED */
+int attn_backward_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o,
+                              const uint16_t* dO, long long ld_o, uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, int T, float* scratch, long long ld_kv,
+                              long long ld_dkv); /* kf_attn_bwd_mfma.hip, ATTN_BWD */
+
+}  // namespace kf

@@ -17,9 +17,11 @@
 //      fragments read straight from the row-major V tile with two transposing ds_read_b64_tr_b16 (4 keys x 16 d per 16 lanes; the 192- / 320-byte row
 //      stride puts the 4 rows of a 32-lane pass on different banks) -- no transposed copy, no 16-bit scatter stores.
 // Online softmax: running maximum per column, O and l rescaled when it moves.  HBM/L2 bytes: K and V once per 128 columns.
+#include <array>
 #include <type_traits>
+#include <utility>
 
-#include "kf_kernels.h"
+#include "kf_attn_plan.h"
 
 namespace kf {
 #ifdef AP_STAMP /* scratch/build_variant.py ... -DAP_STAMP: cycles per segment of the key walk, summed by wave 2 of workgroup (0, 0) -- a long walk of the even key half */
@@ -38,8 +40,6 @@ __device__ unsigned long long g_ap_stamp[8];
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int AP_VPAD = 32;      /* V row padding, elements (64 B): rows 4 apart in a transposing read land on distinct 16-bank groups */
 
 struct AttnPrefillArgs {
     const uint16_t* q;
@@ -339,53 +339,38 @@ __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefil
         }
 }
 
-constexpr int AP_KT_LONG = 64; /* keys per staged tile of the long-prompt form (KH = 2); 32 otherwise */
-template <int HD, int GQ, int KH>
-static int ap_go(hipStream_t st, const AttnPrefillArgs& a, dim3 grid) {
-    constexpr int KT = KH == 2 ? AP_KT_LONG : 32;
-    constexpr size_t smem = sizeof(uint16_t) * KH * (2 * (size_t)KT * (HD + 8) + 2 * (size_t)KT * (HD + AP_VPAD));
-    static_assert(smem <= 160 * 1024, "LDS");
-    static int attr_set = 0;
-    if (!attr_set && smem > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)attn_prefill_kernel<HD, GQ, KH, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return KF_HIP_CHECK;
-        attr_set = 1;
-    }
-    hipLaunchKernelGGL((attn_prefill_kernel<HD, GQ, KH, KT>), grid, dim3(256 * KH), smem, st, a);
-    return 0;
+// the instantiations attn_plan names, by (hd, query heads per workgroup, key halves); the tile follows the halves
+constexpr int APF_KH = 1, APF_GQ = 2, APF_HD = 8, AP_FORMS = 2 * APF_HD;
+constexpr int ap_form_index(int hd, int gq, int kh) { return (hd == 128) * APF_HD + __builtin_ctz(gq) * APF_GQ + (kh == 2) * APF_KH; }
+using ApKernel = void (*)(AttnPrefillArgs);
+template <int I, int HD = I / APF_HD ? 128 : 64, int GQ = 1 << (I / APF_GQ % 4), int KH = I % 2 ? 2 : 1>
+constexpr ApKernel ap_form() {
+    static_assert(ap_form_index(HD, GQ, KH) == I, "ap_form_index");
+    constexpr int KT = KH == 2 ? AP_KT_LONG : AP_KT;
+    static_assert(sizeof(uint16_t) * KH * (2 * KT * (HD + 8) + 2 * KT * (HD + AP_VPAD)) <= 160 * 1024, "LDS");
+    return attn_prefill_kernel<HD, GQ, KH, KT>;
 }
-template <int HD>
-static int ap_launch_gq(hipStream_t st, const AttnPrefillArgs& a, int GQ, dim3 grid, int kh) {
-    switch (GQ) {
-        case 1: return kh == 2 ? ap_go<HD, 1, 2>(st, a, grid) : ap_go<HD, 1, 1>(st, a, grid);
-        case 2: return kh == 2 ? ap_go<HD, 2, 2>(st, a, grid) : ap_go<HD, 2, 1>(st, a, grid);
-        case 4: return kh == 2 ? ap_go<HD, 4, 2>(st, a, grid) : ap_go<HD, 4, 1>(st, a, grid);
-        case 8: return kh == 2 ? ap_go<HD, 8, 2>(st, a, grid) : ap_go<HD, 8, 1>(st, a, grid);
-        default: return 1;
-    }
+template <int... I>
+constexpr std::array<ApKernel, AP_FORMS> ap_forms(std::integer_sequence<int, I...>) {
+    return {{ap_form<I>()...}};
 }
 
-// KF_OK launched; 1 = shape not covered (the caller falls back to the per-token kernel)
-int attn_prefill_mfma_launch(hipStream_t st, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, int pos0, int n_tok, long long q_stride,
-                             int n_head, int n_kv, int hd, int kv_stride, int n_seq, long long out_stride) {
-    if (out_stride <= 0) out_stride = q_stride;
-    if (out_stride & 3) return 1;
-    if ((hd != 64 && hd != 128) || n_kv <= 0 || n_head % n_kv != 0) return 1;
-    if ((q_stride & 7) != 0 || (kv_stride & 7) != 0 || (reinterpret_cast<uintptr_t>(q) & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 7) != 0) return 1;
-    const int GQ = n_head / n_kv;
-    if (GQ != 1 && GQ != 2 && GQ != 4 && GQ != 8) return 1;
+int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, int pos0, int n_tok,
+                             long long q_stride, int n_kv, int kv_stride, int n_seq, long long out_stride) {
+    static constexpr std::array<ApKernel, AP_FORMS> forms = ap_forms(std::make_integer_sequence<int, AP_FORMS>());
+    static bool lds_set[AP_FORMS] = {};
+    const int f = ap_form_index(p.hd, p.gq, p.kh);
+    if (!lds_set[f] && p.lds > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(forms[f]), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds) != hipSuccess) return KF_HIP_CHECK;
+        lds_set[f] = true;
+    }
     AttnPrefillArgs a;
-    a.q = q, a.kcache = kc, a.vcache = vc, a.out = out, a.pos0 = pos0, a.n_tok = n_tok, a.n_kv = n_kv, a.kv_stride = kv_stride, a.q_stride = q_stride, a.out_stride = out_stride;
-    a.rden = 1.0f / sqrtf((float)hd);
+    a.q = q, a.kcache = kc, a.vcache = vc, a.out = out, a.pos0 = pos0, a.n_tok = n_tok, a.n_kv = n_kv, a.kv_stride = kv_stride, a.q_stride = q_stride;
+    a.out_stride = out_stride > 0 ? out_stride : q_stride;
+    a.rden = 1.0f / sqrtf((float)p.hd);
     a.n_seq = n_seq;
-    const int TQ = 128 / GQ;
-    dim3 grid((n_tok + TQ - 1) / TQ, n_kv, n_seq);
-    const int nsb = (n_tok + TQ / 2 - 1) / (TQ / 2); /* the paired form (kh = 2): half blocks of TQ / 2 tokens, one from the front and one from the back per workgroup */
-    // about one workgroup per CU or fewer: the launch lasts as long as its last query block -- two key halves per workgroup (2047 tokens, 16 / 8 heads x 128:
-    // 81 -> 67 us); with more workgroups than that the halves only compete for the CU (8 x 1024 x 25 x 64: 130 vs 143 us; 4095 tokens: 15.9 vs 16.4 ms per prompt)
-    const int kh = ((long)grid.x * grid.y * grid.z <= 320 && n_tok >= g_knobs.attn_pair_min) ? 2 : 1; /* short prompts: the launch is a few microseconds either way */
-    if (kh == 2) grid.x = (nsb + 1) / 2;
-    const int rc = hd == 128 ? ap_launch_gq<128>(st, a, GQ, grid, kh) : ap_launch_gq<64>(st, a, GQ, grid, kh);
-    if (rc) return rc;
+    void* args[] = {&a};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(forms[f]), dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.threads), args, (size_t)p.lds, st);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

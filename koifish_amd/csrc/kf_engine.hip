@@ -38,6 +38,7 @@
 
 #include <type_traits>
 
+#include "kf_attn_plan.h"
 #include "kf_engine_common.h"
 
 namespace kf {
@@ -1552,11 +1553,10 @@ int engine_step(EngineHost* E, hipStream_t st, const uint16_t* x_in, uint16_t* x
     a.n_steps = n_steps;
     a.head_on = with_head ? 1 : 0;
     a.d_state_w = with_head == 2 ? const_cast<int32_t*>(d_state) : nullptr; /* 2: head + greedy pick + state update; 1: logits only */
-    const int nsp = attn_splits(pos_bound, E->n_kv);
-    const int chunk = (pos_bound + 1 + nsp - 1) / nsp;
-    const int NW = (E->GQ <= 2 && chunk > 128) ? 8 : 4;
-    if (NW != 4 || E->n_kv * nsp > E->n_cu) return 1; /* the 8-wave slice form and more slices than workgroups are not restated here */
-    a.nsp = nsp, a.chunk = chunk;
+    const AttnSlices sl = attn_slices(pos_bound, E->n_kv, E->GQ);
+    const int nsp = sl.n_splits;
+    if (sl.nw != 4 || E->n_kv * nsp > E->n_cu) return 1; /* the 8-wave slice form and more slices than workgroups are not restated here */
+    a.nsp = nsp, a.chunk = sl.chunk;
     for (int i = 0; i < 6; i++) a.delay[i] = E->delay_tab[nsp][i];
     int e = (E->n_head * E->hd + E->n_cu - 1) / E->n_cu, me = 1;
     while (me < e) me <<= 1;
@@ -1611,8 +1611,7 @@ static float eng_time_launches(EngineHost* E, hipStream_t st, uint16_t* x_out, c
 }
 int engine_tune(EngineHost* E, hipStream_t st, uint16_t* x_out, const int32_t* d_state, int pos_bound, int passes, float* us_before, float* us_after) {
     if (!E->args.emb || !x_out || !d_state || pos_bound < 0 || pos_bound >= E->args.max_seq) return KF_INVALID_ARGS;
-    const int nsp = attn_splits(pos_bound, E->n_kv);
-    if (nsp < 1 || nsp > KF_ATTN_MAX_SPLITS) return KF_INVALID_ARGS;
+    const int nsp = attn_slices(pos_bound, E->n_kv, E->GQ).n_splits; /* 1 .. KF_ATTN_MAX_SPLITS */
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess) return KF_HIP_CHECK;
     if (hipEventCreate(&e1) != hipSuccess) {
@@ -1669,8 +1668,7 @@ int engine_stats(EngineHost* E, hipStream_t st, int pos_bound, int* out14) {
     int w[16];
     if (hipMemcpyAsync(w, E->args.ws, sizeof(w), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KF_HIP_CHECK;
     for (int i = 0; i < 7; i++) out14[i] = w[8 + i];
-    int nsp = attn_splits(pos_bound < 0 ? 0 : pos_bound, E->n_kv);
-    if (nsp < 1 || nsp > KF_ATTN_MAX_SPLITS) nsp = 1;
+    const int nsp = attn_slices(pos_bound < 0 ? 0 : pos_bound, E->n_kv, E->GQ).n_splits;
     for (int i = 0; i < 6; i++) out14[7 + i] = E->delay_tab[nsp][i];
     out14[13] = E->tuned[nsp];
     return KF_OK;

@@ -16,7 +16,6 @@ inline bool is_row_lut(const kf_weight* w) { return w->quant != KF_QUANT_GROUP; 
 enum { GEMV_PLAIN = 0, GEMV_PAIRED = 1, GEMV_ARGMAX = 2 };
 constexpr int KF_MAX_ARGMAX_PARTIALS = 4096;
 constexpr int KF_ATTN_MAX_SPLITS = 32;
-constexpr int KF_ATTN_CNT_BYTES = 16384; /* arrival counters at the head of the attention scratch */
 
 struct GemvJob {
     const void* w;
@@ -103,14 +102,10 @@ struct AttnArgs {
     int one_slice;      /* every (kv-head, token) is handled by one workgroup: no scratch, no hand-off */
     long long q_stride; /* elements between the q (and out) rows of consecutive tokens */
     int canon;          /* the canonical softmax (fp64 sums, exact rescales; bit-exact against the oracle's CANON mode) instead of the fp32 form */
-    int gq_split;       /* set by attn_launch: the query heads of a kv-head are dealt to this many workgroups (blockIdx.y = kv-head * gq_split + part), each with GQ / gq_split heads:
-                           the canonical form at 8 query heads per kv-head needs 411 registers in one workgroup (one wave per SIMD, accumulators in AGPRs), 224 in two */
+    int gq_split;       /* the query heads of a kv-head are dealt to this many workgroups (blockIdx.y = kv-head * gq_split + part), each with GQ / gq_split heads
+                           (kf_attn_plan.h ATTN_CANON_GQ_WG) */
 };
-int attn_launch(hipStream_t st, AttnArgs& a);
-int attn_splits(int pos_bound, int n_kv);
-// token-batch causal attention on MFMA (kf_attn_prefill.hip): KF_OK launched, 1 = shape not covered, < 0 error
-int attn_prefill_mfma_launch(hipStream_t st, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, int pos0, int n_tok, long long q_stride,
-                             int n_head, int n_kv, int hd, int kv_stride, int n_seq = 1, long long out_stride = 0 /* 0: q_stride */);
+// the attention launchers: kf_attn_plan.h (the rule and the launchers)
 int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, int pos,
                        const int* d_pos, int n_head, int n_kv, int hd, float eps, int n_tok = 1, long long q_stride = 0, long long k_stride = 0, int seq_len = 0,
                        float* rstd_q = nullptr, float* rstd_k = nullptr);
@@ -120,8 +115,6 @@ int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t*
 struct Knobs {
     int q4_perm = 1;      /* 4-bit mat-vec through the register-table lookup (0: the arithmetic form; same bits) */
     int q2_tab = 1;       /* 2-bit mat-vec through the LDS selector table (0: the arithmetic form; same bits) */
-    int attn_pair_min = 256;  /* prompt tokens from which kf_attn_prefill takes its paired two-key-half form (when there is about one workgroup per CU or fewer) */
-    int attn_gq_split = 4; /* canonical decode attention of a GQA-8 model: workgroups per (kv-head, slice), 2 or 4 */
     int q1_tab = 1;       /* 1-bit mat-vec through the LDS selector table (0: the per-bit select form; same bits) */
     int gemv_xf2 = 1;     /* canonical 4-bit rows too long for fp32 activations in 48 KiB of LDS: two windows of half the block columns (0: bf16 activations, widened per product) */
 };
@@ -198,10 +191,6 @@ int bias_residual_launch(hipStream_t st, uint16_t* y, const uint16_t* bias, cons
 // linear backward helpers (kf_linear_bwd.hip)
 int transpose_bf16_launch(hipStream_t st, const uint16_t* in, uint16_t* out, int R, int C);
 int colsum_add_launch(hipStream_t st, const uint16_t* x, uint16_t* dst, int n, int C, double* scratch); /* scratch: ceil(n / 256) * C doubles */
-// causal MHA backward on MFMA tiles (kf_attn_bwd_mfma.hip); scratch: 2 * n_seq * n_head * T floats; 1 = shape not covered
-int attn_backward_mfma_launch(hipStream_t st, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o, const uint16_t* dO, long long ld_o,
-                              uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, int T, int n_head, int hd, int n_seq, float* scratch, int n_kv, long long ld_kv,
-                              long long ld_dkv); /* kf_attn_bwd_mfma.hip: 1 = not covered */
 // embedding backward (kf_embed_bwd.hip)
 int argmax_rows_state_launch(hipStream_t st, const uint16_t* logits, long long ld, int n, int n_rows, const int* d_seq, int32_t* states, int32_t* tokens_out, int tokens_stride);
 int copy_blocks_launch(hipStream_t st, void* const* dst_table, size_t dst_offset, const void* src, size_t src_stride, size_t block_bytes, int n_blocks);

@@ -8,8 +8,6 @@ from koifish_amd import lib as L, synth
 cfg = dict(synth.CONFIGS["qwen3-0.6b"])
 m = synth.build_on_gpu(cfg, seed=1234, layer_type=L.Q4, head_type=L.BF16)
 rng = np.random.default_rng(5)
-import _knobs
-_knobs.apply(m.hip)   # KF_ATTN_PAIR_MIN ... (scratch/_knobs.py)
 SIZES = [int(a) for a in sys.argv[1].split(',')] if len(sys.argv) > 1 else (32, 128, 512, 1024, 2047)
 SERIAL = len(sys.argv) <= 2
 
