@@ -243,6 +243,20 @@ int kf_embed(kf_ctx* ctx, const kf_weight* w, int token, const int32_t* d_token,
  * the greedy id (first maximum) to d_argmax_out (device int32; NULL: logits only, no pick).  scratch: kf_head_scratch_bytes(). */
 int kf_lm_head(kf_ctx* ctx, const kf_weight* w, const kf_bf16* x, kf_bf16* logits, int32_t* d_argmax_out, void* scratch_or_null);
 size_t kf_head_scratch_bytes(void);
+/* The LM head scored against target ids: what Fish_ppl / Fish::Eval_ppl compute token by token as log(P_softmax(tokens[i + 1], logits, nVocab))
+ * (Evaluate.cpp:19-94, CLI_params.cpp:1692-1705), for n_rows rows at once and without the [n_rows x ne0] logit matrix being written.
+ * x [n_rows][ldx] bf16 is the hidden state AFTER the final RMSNorm (kf_rmsnorm over the rows), 16-byte aligned, ldx >= ne1 a multiple of 8.  Per row t:
+ *   logit[v]   = bf16(fp32 dot(x[t], W[v])), rounded exactly as kf_lm_head / kf_linear store it (token-batch products sum in MFMA order);
+ *   logprob[t] = (logit[target] - m) - log(sum_v exp(logit[v] - m)), m the row maximum, fp32, the fixed exp / log of kf_fused_classifier.  The same number as
+ *                log(P_softmax(..)) of the reference WITHOUT its underflow to log(0) = -inf for a token the model finds unlikely;
+ *   lse[t]     = m + log(sum);   top1[t] = the FIRST maximum of the bf16 logits (sample_argmax, GoPT.cpp:602-612), ties to the lower id.
+ * d_targets[t] < 0: the row is not scored, logprob[t] = 0, lse / top1 are still written.  d_targets[t] >= ne0 (ids the host never saw) gives NaN and reads nothing;
+ * callers with host-side ids refuse them with KF_INVALID_ARGS (kfh_score).  Every storage type is served: a bf16 head with ne1 % 64 == 0 by MFMA tiles whose epilogue
+ * keeps three numbers per row and vocabulary tile, the rest through kf_linear on panels of rows (its kf_set_scratch workspace as for kf_linear).
+ * scratch: kf_head_logprob_scratch_bytes(head, n_rows) bytes, 16-byte aligned -- for a bf16 head at most 1/16 of the logit matrix's bytes. */
+size_t kf_head_logprob_scratch_bytes(const kf_weight* head, int n_rows);
+int kf_head_logprob(kf_ctx* ctx, const kf_weight* head, const kf_bf16* x, int64_t ldx, int n_rows, const int32_t* d_targets, float* d_logprob,
+                    float* d_lse_or_null, int32_t* d_top1_or_null, void* scratch);
 
 /* ---- fused forms used by the decode step (same arithmetic as the calls above, fewer launches) ---- */
 /* [RMSNorm(x, norm_w)] -> up to 3 projections sharing the normed input.  y[i] rows go to y[i], or, when

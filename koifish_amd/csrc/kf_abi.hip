@@ -14,6 +14,7 @@
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
+#include "kf_score_plan.h"
 
 struct kf_ctx {
     int device;
@@ -404,6 +405,50 @@ int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const
     }
     const int rc = kf::gemm_launch(c->stream, p.k, kf::gm_bf16(W, w->ne0, w->ne1), x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, res, w->ne0, p.ws_bytes ? c->scratch : nullptr);
     if (rc) return fail(rc, "kf_linear (%s) failed with %d", lut ? "row-LUT token-batch GEMM" : row ? "token-batch GEMM" : (resident ? "bf16 tile GEMM on the resident copy" : "large-batch bf16 tile GEMM"), rc);
+    return KF_OK;
+}
+
+// ---- the LM head scored against target ids (kf_head_score.hip; the route: kf_score_plan.h)
+static kf::ScoreProblem score_problem(const kf_weight* head, int n_rows, bool x_al) {
+    kf::ScoreProblem P = {};
+    P.w = kf::mat_of(head), P.n = n_rows, P.x_al = x_al, P.force = kf::g_knobs.score_route, P.form = kf::g_knobs.score_form;
+    return P;
+}
+size_t kf_head_logprob_scratch_bytes(const kf_weight* head, int n_rows) {
+    if (!head || n_rows < 1) return 0;
+    return (size_t)kf::score_plan(score_problem(head, n_rows, true)).scratch; /* kf_head_logprob refuses an x that is not aligned: the plan is the call's */
+}
+int kf_head_logprob(kf_ctx* c, const kf_weight* head, const kf_bf16* x, int64_t ldx, int n_rows, const int32_t* d_targets, float* d_logprob, float* d_lse_or_null,
+                    int32_t* d_top1_or_null, void* scratch) {
+    CHKCTX(c);
+    int r = check_weight(head, "kf_head_logprob");
+    if (r) return r;
+    if (n_rows < 1 || !d_targets || !d_logprob || !scratch) return fail(KF_INVALID_ARGS, "kf_head_logprob: n_rows=%d, or targets / logprob / scratch null", n_rows);
+    if (ldx < head->ne1) return fail(KF_INVALID_ARGS, "kf_head_logprob: ldx=%lld below dim=%d", (long long)ldx, head->ne1);
+    if (!x || !al16(x) || (ldx & 7) || !al16(scratch)) return fail(KF_BLAS_UNALIGN, "kf_head_logprob: x / scratch null or not 16-byte aligned, or ldx not a multiple of 8");
+    const kf::ScorePlan p = kf::score_plan(score_problem(head, n_rows, true));
+    if (p.status) return fail(p.status, "kf_head_logprob: bad shape");
+    const int V = head->ne0, K = head->ne1;
+    if (p.route == kf::SR_FUSED) {
+        const int rc = kf::score_fused_launch(c->stream, p, (const uint16_t*)head->data, V, K, x, ldx, n_rows, d_targets, d_logprob, d_lse_or_null, d_top1_or_null, scratch);
+        return rc ? fail(rc, "kf_head_logprob (fused tiles) failed with %d", rc) : KF_OK;
+    }
+    kf_bf16* logits = (kf_bf16*)scratch; /* [panel_rows][V] */
+    for (int r0 = 0; r0 < n_rows; r0 += p.panel_rows) {
+        const int m = n_rows - r0 < p.panel_rows ? n_rows - r0 : p.panel_rows;
+        if (ldx == K) {
+            r = kf_linear(c, head, x + (size_t)r0 * ldx, logits, nullptr, m, 1.0f, 0.0f, 0, nullptr);
+            if (r) return r;
+        } else { /* padded rows: kf_linear's batch form wants them dense */
+            for (int t = 0; t < m; t++) {
+                r = kf_linear(c, head, x + (size_t)(r0 + t) * ldx, logits + (size_t)t * V, nullptr, 1, 1.0f, 0.0f, 0, nullptr);
+                if (r) return r;
+            }
+        }
+        const int rc = kf::score_rows_launch(c->stream, logits, V, V, m, d_targets + r0, d_logprob + r0, d_lse_or_null ? d_lse_or_null + r0 : nullptr,
+                                             d_top1_or_null ? d_top1_or_null + r0 : nullptr);
+        if (rc) return fail(rc, "kf_head_logprob (panel fold) failed with %d", rc);
+    }
     return KF_OK;
 }
 
@@ -1374,6 +1419,12 @@ int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
     *out = kf::attn_plan(*P);
     return 0;
 }
+// the plan kf::score_plan makes for a scoring problem (no HIP call): tests/test_score_cpu.py
+int kfdbg_score_plan(const kf::ScoreProblem* P, kf::ScorePlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::score_plan(*P);
+    return 0;
+}
 // development knobs (kf::Knobs): a kernel form against the form it replaces, inside one process (the token-batch routes have none: kf_gemm_plan.h; the mat-vec's
 // slots per wave and load form none either: kf_gemv_plan.h; nor the attention routes and forms: kf_attn_plan.h)
 int kfdbg_set_knob(const char* name, long value) {
@@ -1383,6 +1434,8 @@ int kfdbg_set_knob(const char* name, long value) {
     else if (!strcmp(name, "q2_tab")) k.q2_tab = (int)value;
     else if (!strcmp(name, "q1_tab")) k.q1_tab = (int)value;
     else if (!strcmp(name, "gemv_xf2")) k.gemv_xf2 = (int)value;
+    else if (!strcmp(name, "score_route")) k.score_route = (int)value;
+    else if (!strcmp(name, "score_form")) k.score_form = (int)value;
     else return -1;
     return 0;
 }

@@ -117,6 +117,8 @@ struct Knobs {
     int q2_tab = 1;       /* 2-bit mat-vec through the LDS selector table (0: the arithmetic form; same bits) */
     int q1_tab = 1;       /* 1-bit mat-vec through the LDS selector table (0: the per-bit select form; same bits) */
     int gemv_xf2 = 1;     /* canonical 4-bit rows too long for fp32 activations in 48 KiB of LDS: two windows of half the block columns (0: bf16 activations, widened per product) */
+    int score_route = 0;  /* kf_head_logprob: 1 sends a head the fused route would take down the panel route (kf_score_plan.h; the two are compared by tests/test_gpu_score.py) */
+    int score_form = -1;  /* kf_head_logprob's fused route: >= 0 the tile form (G3_BIG / G3_SMALL) instead of the rule's (scratch/ub_score.py measures both) */
 };
 extern Knobs g_knobs;
 // ---- the persistent decode engine: one sequence on every CU (kf_engine.hip)

@@ -2,6 +2,7 @@
 #include "kf_host.hpp"
 
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -251,6 +252,7 @@ Fish::~Fish() {
         if (rope_table) kf_free(ctx, rope_table);
         FreeSeqs(ctx);
         if (gBUFF.d_ptok) kf_free(ctx, gBUFF.d_ptok);
+        FreeScore();
         if (d_rng) kf_free(ctx, d_rng);
     }
     attn.clear(), ffn.clear();
@@ -729,6 +731,81 @@ int Fish::Prefill(const int* tokens, int n, int pos0) {
     KF_TRY(SetState(tokens[n - 1], pos0 + n - 1));
     tok_pos = pos0 + n - 1;
     return HeadAndPick(ToX(x));
+}
+
+void Fish::FreeScore() {
+    if (gBUFF.d_stgt) kf_free(ctx, gBUFF.d_stgt), gBUFF.d_stgt = nullptr;
+    if (gBUFF.d_slp) kf_free(ctx, gBUFF.d_slp), gBUFF.d_slp = nullptr;
+    if (gBUFF.d_stop1) kf_free(ctx, gBUFF.d_stop1), gBUFF.d_stop1 = nullptr;
+    if (gBUFF.score_ws) kf_free(ctx, gBUFF.score_ws), gBUFF.score_ws = nullptr;
+    gBUFF.score_rows = 0;
+}
+int Fish::ScoreReady() {
+    KF_TRY(PrefillReady());
+    const int R = gBUFF.rows;
+    if (gBUFF.score_rows >= R) return KF_OK;
+    KF_TRY(kf_sync(ctx));
+    FreeScore();
+    kf_weight wh = head.proj.w->desc();
+    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_stgt));
+    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_slp));
+    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_stop1));
+    KF_TRY(kf_malloc(ctx, kf_head_logprob_scratch_bytes(&wh, R), &gBUFF.score_ws));
+    gBUFF.score_rows = R;
+    return KF_OK;
+}
+
+int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) {
+    if (n < 2 || pos0 < 0 || pos0 + n > config.n_ctx || !tokens || !logprob_out) return KF_INVALID_ARGS;
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= config.vocab) return KF_INVALID_ARGS;
+    const int PC = prefill_chunk < config.n_ctx ? prefill_chunk : config.n_ctx, C = config.nEmbed;
+    KF_TRY(ScoreReady());
+    floatX* bx = ToX(gBUFF.bX);
+    kf_weight we = embed.w->desc(), wh = head.proj.w->desc();
+    std::vector<int32_t> tgt(PC);
+    int m = 0;
+    for (int c0 = 0; c0 < n; c0 += PC) {
+        m = n - c0 < PC ? n - c0 : PC;
+        KF_TRY(kf_h2d(ctx, gBUFF.d_ptok, tokens + c0, (size_t)m * 4));
+        KF_TRY(kf_embed_batch(ctx, &we, gBUFF.d_ptok, m, bx));
+        for (int l = 0; l < config.nLayer; l++) {
+            KF_TRY(attn[l]->cuFlow(bx, pos0 + c0, m));
+            KF_TRY(ffn[l]->cuFlow(bx, m));
+        }
+        // row i of the chunk predicts token c0 + i + 1: the first token of the next chunk for the chunk's last row, nothing for the last row of all
+        const int ns = c0 + m < n ? m : m - 1;
+        if (ns < 1) continue;
+        for (int i = 0; i < m; i++) tgt[i] = i < ns ? tokens[c0 + i + 1] : -1;
+        KF_TRY(kf_h2d(ctx, gBUFF.d_stgt, tgt.data(), (size_t)m * 4));
+        KF_TRY(kf_rmsnorm(ctx, bx, ToX(final_norm.w), ToX(gBUFF.bNorm), ns, C, final_norm.rms_eps, nullptr));
+        KF_TRY(kf_head_logprob(ctx, &wh, ToX(gBUFF.bNorm), C, ns, gBUFF.d_stgt, gBUFF.d_slp, nullptr, top1_out ? gBUFF.d_stop1 : nullptr, gBUFF.score_ws));
+        KF_TRY(kf_d2h(ctx, logprob_out + c0, gBUFF.d_slp, (size_t)ns * 4));
+        if (top1_out) KF_TRY(kf_d2h(ctx, top1_out + c0, gBUFF.d_stop1, (size_t)ns * 4));
+    }
+    // from here on Prefill's own ending: the head on the last token, the state update leaves {next token, pos0 + n}
+    KF_TRY(kf_d2d(ctx, x->data, bx + (size_t)(m - 1) * C, (size_t)C * 2));
+    KF_TRY(SetState(tokens[n - 1], pos0 + n - 1));
+    tok_pos = pos0 + n - 1;
+    return HeadAndPick(ToX(x));
+}
+
+int Fish::EvalPPL(const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored) {
+    if (!tokens || n < 2 || !ppl) return KF_INVALID_ARGS;
+    const int W = window <= 0 || window > config.n_ctx ? config.n_ctx : window;
+    if (W < 2) return KF_INVALID_ARGS;
+    std::vector<float> lp(W);
+    double sum = 0.0, ss = 0.0;
+    long long nz = 0;
+    for (long long w0 = 0; w0 + 1 < n; w0 += W) {
+        const int m = (int)(n - w0 < W ? n - w0 : W);
+        KF_TRY(Score(tokens + w0, m, 0, lp.data(), nullptr));
+        for (int i = 0; i < m - 1; i++) sum += (double)lp[i], ss += (double)lp[i] * (double)lp[i], nz++;
+    }
+    *ppl = exp(-sum / (double)nz);
+    if (pplerr) *pplerr = *ppl * sqrt((ss - sum * sum / (double)nz) / (double)nz / (double)nz);
+    if (n_scored) *n_scored = nz;
+    return KF_OK;
 }
 
 // the token-batch buffers ([prefill_chunk rows]) and the tile kernels' scratch / resident copies: allocated by the first prefill, never inside a later one
@@ -1545,6 +1622,11 @@ int kfh_set_forced(void* h, const int32_t* forced, int n) {
     return kf_h2d(f->ctx, f->d_forced, forced, (size_t)n * 4);
 }
 int kfh_prefill(void* h, const int* tokens, int n, int pos0) { return reinterpret_cast<Fish*>(h)->Prefill(tokens, n, pos0); }
+// Fish_ppl / Fish::Eval_ppl as a batch (Fish::Score, Fish::EvalPPL): logprob_out [n - 1] fp32, top1_out [n - 1] int32 or NULL
+int kfh_score(void* h, const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) { return reinterpret_cast<Fish*>(h)->Score(tokens, n, pos0, logprob_out, top1_out); }
+int kfh_eval_ppl(void* h, const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored) {
+    return reinterpret_cast<Fish*>(h)->EvalPPL(tokens, n, window, ppl, pplerr, n_scored);
+}
 int kfh_set_prefill_mode(void* h, int mode, int chunk) {
     Fish* f = reinterpret_cast<Fish*>(h);
     f->prefill_mode = mode;

@@ -166,6 +166,12 @@ struct MemBuffer {
     hGTensor bX, bNorm, bQ, bAttn, bGate, bUp;
     int32_t* d_ptok = nullptr;
     int rows = 0;       // rows of the token-batch buffers
+    // Fish::Score: a chunk's target ids, log-probs and greedy ids [score_rows], and kf_head_logprob's workspace; allocated by the first Score (ScoreReady)
+    int32_t* d_stgt = nullptr;
+    float* d_slp = nullptr;
+    int32_t* d_stop1 = nullptr;
+    void* score_ws = nullptr;
+    int score_rows = 0;
 };
 
 // CHAT_SAMPLER (CLI_params.hpp:663-683): the fields GeneratOnPrompt::Sample reads.  temperature == 0 or top_k == 1 -> sample_argmax.
@@ -290,6 +296,16 @@ struct Fish : SeqBuffers {
     // afterwards the KV cache holds rows pos0..pos0+n-1, d_state = {greedy next token, pos0+n}, d_tokens_out[pos0+n-1] = that token.
     // The reference prefills token by token (Fish::Chat, GoPT.cpp:1139-1146); same arithmetic per token, fp32 sums in MFMA order.
     int Prefill(const int* tokens, int n, int pos0);
+    // Fish_ppl / Fish::Eval_ppl (Evaluate.cpp:19-94) as a batch: the n tokens at positions pos0.. through every layer exactly as Prefill runs them (hot-row masks included),
+    // then per chunk the final RMSNorm over the chunk's rows and kf_head_logprob against the NEXT token: logprob_out[i] = log P(tokens[i + 1] | tokens[0 .. i]) for
+    // i < n - 1 -- the pair across a chunk boundary included -- and top1_out[i] (or NULL) the greedy id after token i.  K / V rows, d_state, d_tokens_out, logits and the
+    // residual row are left exactly as Prefill(tokens, n, pos0) leaves them.  Argument checks and codes as Prefill's; n >= 2.
+    int Score(const int* tokens, int n, int pos0, float* logprob_out, int* top1_out);
+    int ScoreReady();  // PrefillReady + the scoring buffers, sized to the token-batch rows: allocated by the first Score, never inside a later one
+    void FreeScore();
+    // the reference's perplexity loop: windows of at most `window` tokens (<= 0: n_ctx), each scored from position 0; sum, sum of squares and count of the log-probs in
+    // fp64, ppl = exp(-sum / nz), pplerr = ppl * sqrt((ss - sum * sum / nz) / nz / nz) (Evaluate.cpp:64-80).  A trailing window of one token has no pair and is left out.
+    int EvalPPL(const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored);
     int PrefillReady(int min_rows = 0);  // the token-batch buffers ([rows >= min_rows]), scratch and resident copies: allocated by the first prefill, grown by a larger batch
     // rows per token batch (clamped to n_ctx).  Measured, Qwen3-0.6B 4-bit, prompt filling the context: 2047 tokens 20.9 / 15.5 / 9.8 ms at 512 / 1024 / 2048 rows,
     // 8191 tokens 92.3 / 53.9 / 42.7 / 36.6 ms at 1024 / 2048 / 4096 / 8192 (scratch/prefill_chunk.py): the tile kernels want many rows per launch.

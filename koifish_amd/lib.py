@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "kf_hot_rows", "kf_linear_masked", "kf_zero_cold_columns", "kf_norm_gateup_swiglu_masked", "kf_linear_scratch_bytes", "kf_set_scratch", "kf_engine_workspace_bytes", "kf_engine_create", "kf_engine_step", "kf_engine_check", "kf_engine_destroy", "kf_engine_set_embedding", "kf_engine_set_head", "kf_engine_step_head", "kf_engine_steps_head", "kf_engine_reset", "kf_set_canonical", "kf_get_canonical", "kf_engine_served", "kf_engine_tune", "kf_engine_stats", "kf_qkv_rope_batch", "kf_qkv_rope_seqs", "kf_set_dequant_arena", "kf_dequant_arena_used", "kf_resident_scratch_bytes",
     "kf_xengine_workspace_bytes", "kf_xengine_create", "kf_xengine_served", "kf_xengine_set_embedding", "kf_xengine_set_head", "kf_xengine_steps", "kf_xengine_check", "kf_xengine_reset", "kf_xengine_destroy", "kf_xengine_workspace_bytes_tp", "kf_xengine_create_tp", "kf_xengine_set_head_tp",
     "kf_tp_recv_bytes", "kf_tp_push_bytes", "kf_tp_commit", "kf_tp_alloc", "kf_tp_ipc_export", "kf_tp_ipc_open", "kf_tp_ipc_close", "kf_linear_f32_push", "kf_tp_reduce_recv", "kf_tp_lm_head", "kf_tp_pick",
+    "kf_head_logprob", "kf_head_logprob_scratch_bytes",
 ]
 
 
@@ -98,6 +99,8 @@ def load():
         hip.kf_norm_gateup_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Weight), C.POINTER(Weight), C.c_void_p]
         hip.kf_norm_lm_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_lm_head.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        hip.kf_head_logprob.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        hip.kf_head_logprob_scratch_bytes.argtypes, hip.kf_head_logprob_scratch_bytes.restype = [C.POINTER(Weight), C.c_int], C.c_size_t
         hip.kf_embed.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_int, C.c_void_p, C.c_void_p]
         hip.kf_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -158,6 +161,8 @@ def load():
         host.kfh_msgpack_to_json.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64]
         host.kfh_set_sampler.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_uint64]
         host.kfh_prefill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        host.kfh_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        host.kfh_eval_ppl.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         host.kfh_set_prefill_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
         host.kfh_run_steps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         host.kfh_sync.argtypes = [C.c_void_p]

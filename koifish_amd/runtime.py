@@ -26,6 +26,18 @@ def quant_range(type_, symmetric=False):
     return 0, 0, 0
 
 
+def perplexity_from_logprobs(logprobs):
+    """The reference's perplexity figures (Fish::Eval_ppl, Evaluate.cpp:64-80) from per-token log-probabilities, in fp64, no device needed:
+    sum = sum(lp), ss = sum(lp^2), nz = their number; ppl = exp(-sum / nz), pplerr = ppl * sqrt((ss - sum * sum / nz) / nz / nz).  Returns (ppl, pplerr, nz)."""
+    lp = np.asarray(logprobs, dtype=np.float64).reshape(-1)
+    nz = int(lp.size)
+    if nz < 1:
+        raise ValueError("perplexity_from_logprobs: no log-probabilities")
+    s, ss = float(lp.sum()), float((lp * lp).sum())
+    ppl = float(np.exp(-s / nz))
+    return ppl, ppl * float(np.sqrt(max(ss - s * s / nz, 0.0) / nz / nz)), nz
+
+
 class DevWeight:
     """A weight resident in HBM: blob = torch.uint8 [szData + szGama]."""
 
@@ -557,6 +569,25 @@ class Qwen3:
             ctx = C.c_void_p(self.host.kfh_ctx(self.h))
             L.check(self.hip.kf_d2h(ctx, logits.ctypes.data_as(C.c_void_p), C.c_void_p(self.host.kfh_logits(self.h)), C.c_size_t(logits.size * 2)), "kf_d2h")
         return nxt, logits
+
+    def score(self, tokens, pos0=0, want_top1=False):
+        """log P(tokens[i + 1] | tokens[.. i]) for every i < n - 1 as np.float32 [n - 1] (and, with want_top1, the greedy id after each of those tokens as
+        np.int32 [n - 1]): the prompt through the batched prefill and the LM head with the log-softmax in its epilogue (Fish::Score).  K / V rows, logits,
+        next id and decode state are left as prefill(tokens, pos0) leaves them."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        lp = np.zeros(max(t.size - 1, 0), dtype=np.float32)
+        top1 = np.zeros(max(t.size - 1, 0), dtype=np.int32) if want_top1 else None
+        L.check(self.host.kfh_score(self.h, t.ctypes.data_as(C.c_void_p), t.size, int(pos0), lp.ctypes.data_as(C.c_void_p),
+                                    None if top1 is None else top1.ctypes.data_as(C.c_void_p)), "kfh_score")
+        return (lp, top1) if want_top1 else lp
+
+    def perplexity(self, tokens, window=None):
+        """(ppl, pplerr, n_scored) of a token sequence as Fish::Eval_ppl reports them: windows of at most `window` tokens (default: the context), each scored
+        from position 0; the sums in fp64 on the host (Fish::EvalPPL).  perplexity_from_logprobs is the same arithmetic on given log-probs."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        ppl, err, nz = C.c_double(0.0), C.c_double(0.0), C.c_longlong(0)
+        L.check(self.host.kfh_eval_ppl(self.h, t.ctypes.data_as(C.c_void_p), t.size, int(window or 0), C.byref(ppl), C.byref(err), C.byref(nz)), "kfh_eval_ppl")
+        return ppl.value, err.value, int(nz.value)
 
     def logits(self):
         """the last step's logits (bf16 bit patterns as uint16 [vocab])"""
