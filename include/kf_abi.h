@@ -554,6 +554,31 @@ size_t kf_xengine_workspace_bytes_tp(const kf_engine_desc* rank0_desc);
 int kf_xengine_create_tp(kf_ctx* ctx, const kf_engine_desc* const* rank_descs, int world, void* workspace, size_t workspace_bytes, kf_xengine** out);
 int kf_xengine_set_head_tp(kf_ctx* ctx, kf_xengine* e, const kf_weight* const* head_shards, const int32_t* row0, const kf_bf16* final_norm_w, kf_bf16* logits, int32_t* d_tokens_out_or_null, int tokens_stride);
 
+/* ---- int8 activations for 1-bit and ternary layers: W1.58 . A8 as the reference runs its BitNet family (Bitnet::Bitnet sets DEBUG.tpActi = I8, QWen.cpp:146-153;
+ * SelfAttention::cuInfer calls inpQ->Quant4A(DEBUG.tpActi) in front of Q / K / V, QKV.cu:647; huTensor::Quant4A -> CU_X2A8_, T.cu:24-102).  Off unless called.
+ * THE DEFINITION (DESIGN.md "Int8 activations"; restated in numpy by tests/test_a8_cpu.py and tests/test_gpu_a8.py):
+ *   quantiser, per token row x[dim] (bf16 read as fp32; with norm_w first normed and rounded to bf16 exactly as kf_rmsnorm stores it):
+ *     amax = max_i |x_i|;  step_x = amax / 127.0f  (correctly rounded fp32 division);
+ *     q_i = clamp(round_half_away(x_i / step_x), -127, 127)  (correctly rounded fp32 division, std::round as T.cu:60);  amax == 0: step_x = 0 and every q_i = 0.
+ *     DEVIATION from CU_X2A8_: it takes the SIGNED row maximum (step = wMax / qMax, T.cu:41-43) and asserts step > 0 -- a row whose largest element is negative trips
+ *     the assert, a row with |min| > max clips.  Here: the absolute maximum, as BitNet b1.58 defines it.
+ *   product, per output row r and token t, groups g of 128 consecutive weights:
+ *     I_g = sum_{c in g} (code[c] - qBias) * q[t][c]  as int32 (ternary KF_T_SIGN: {-1, 0, 1}; KF_BOOL1 / KF_T_BINARY: {0, 1}); |I_g| <= 128 * 127 = 16256;
+ *     acc = 0;  acc = acc + fp32(step_w[g]) * fp32(I_g)  for g = 0, 1, .. K/128 - 1: ONE ascending fp32 chain; every product is exact (8 + 14 significant bits).
+ *     The order depends on K and g only -- never on lanes per row, grid, plan form or nTok;
+ *     y = bf16_rn(step_x[t] * acc);  with bias: bf16_rn(step_x[t] * acc + bias[r]);  with residual: y = bf16(residual + bf16(..)), kf_linear's epilogue.
+ *   The group ZERO is not part of this arithmetic: YinYang and the symmetric quantiser write zero = 0 (GeQuant.cpp:536-628); callers check it (Fish, at switch-on).
+ * kf_act_quant_i8: x rows of dim bf16, ldx elements apart (ldx >= dim) -> q int8 [rows][dim], step fp32 [rows].
+ * kf_linear_a8: y [nTok][ne0] as kf_linear writes it; residual [nTok][ne0] may alias y.  Refusals (kf::a8_plan, csrc/kf_a8_plan.h): any storage other than KF_T_SIGN /
+ * KF_BOOL1 / KF_T_BINARY in KF_QUANT_GROUP form KF_UNSUPPORTED_DATATYPE; lGroup != 128 or no gama KF_QUANT_ERR; ne1 % 128 != 0, ne0 < 1, nTok < 1 KF_INVALID_ARGS; data not
+ * 16-byte aligned KF_BLAS_UNALIGN.  nTok > 1 runs the same kernel on tiles of token rows: the bits of nTok = 1.
+ * With norm_w the prologue refuses what kf_rmsnorm refuses (an odd dim: KF_RMS_PARAMS).
+ * kf_linear_a8_status: what kf_linear_a8 would answer for this weight and nTok -- KF_OK or the refusal -- without a launch: THE served-storage rule for callers that route
+ * matrices (Fish asks it per layer matrix: KF_UNSUPPORTED_DATATYPE = "keep the bf16-activation route"). */
+int kf_linear_a8_status(const kf_weight* w, int nTok);
+int kf_act_quant_i8(kf_ctx* ctx, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w_or_null, float eps, int rows, int dim, int8_t* q, float* step);
+int kf_linear_a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
+
 #ifdef __cplusplus
 }
 #endif

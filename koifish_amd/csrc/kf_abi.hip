@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "kf_a8_plan.h"
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
@@ -1401,6 +1402,29 @@ int kfdbg_engine_set_delays(kf_engine* e, const int* d6) {
     kf::engine_set_delays(e->h, d6);
     return 0;
 }
+// ---- int8 activations for 1-bit / ternary weights (include/kf_abi.h): the quantiser and the integer mat-vec; every launch decision is kf::a8_plan's
+int kf_act_quant_i8(kf_ctx* c, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w, float eps, int rows, int dim, int8_t* q, float* step) {
+    CHKCTX(c);
+    if (!x || !q || !step) return fail(KF_INVALID_ARGS, "kf_act_quant_i8: null pointer");
+    if (rows < 1 || dim < 1 || ldx < dim) return fail(KF_INVALID_ARGS, "kf_act_quant_i8: rows=%d dim=%d ldx=%lld", rows, dim, (long long)ldx);
+    if (norm_w && dim % 2 != 0) return fail(KF_RMS_PARAMS, "kf_act_quant_i8: rmsnorm dim %d is not divisible by 2", dim); /* what kf_rmsnorm refuses, the prologue refuses */
+    RET(kf::act_quant_launch(c->stream, x, ldx, norm_w, eps, rows, dim, q, step));
+}
+int kf_linear_a8_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::a8_plan(kf::A8Problem{kf::mat_of(w), nTok}).status : KF_INVALID_ARGS; }
+int kf_linear_a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_a8: null weight");
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_a8: null pointer");
+    const kf::A8Plan p = kf::a8_plan(kf::A8Problem{kf::mat_of(w), nTok});
+    if (p.status == KF_UNSUPPORTED_DATATYPE)
+        return fail(p.status, "kf_linear_a8: weight type %d (quant mode %d%s) has no integer form: served are KF_T_SIGN (%d), KF_BOOL1 (%d), KF_T_BINARY (%d) in group storage", w->type,
+                    w->quant, (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_T_SIGN, KF_BOOL1, KF_T_BINARY);
+    if (p.status == KF_QUANT_ERR) return fail(p.status, "kf_linear_a8: group size %d (must be 128) or gama missing", w->lGroup);
+    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_a8: weight data not 16-byte aligned");
+    if (p.status != KF_OK) return fail(p.status, "kf_linear_a8: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
+    RET(kf::a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+
 // the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py
 int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
     if (!P || !out) return -1;
@@ -1417,6 +1441,12 @@ int kfdbg_gemv_plan(const kf::GemvProblem* P, kf::GemvPlan* out) {
 int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
     if (!P || !out) return -1;
     *out = kf::attn_plan(*P);
+    return 0;
+}
+// the plan kf::a8_plan makes for an integer mat-vec (no HIP call): tests/test_a8_plan_cpu.py
+int kfdbg_a8_plan(const kf::A8Problem* P, kf::A8Plan* out) {
+    if (!P || !out) return -1;
+    *out = kf::a8_plan(*P);
     return 0;
 }
 // the plan kf::score_plan makes for a scoring problem (no HIP call): tests/test_score_cpu.py

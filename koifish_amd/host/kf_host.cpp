@@ -125,6 +125,20 @@ hGTensor SelfAttention::cuInfer(hGTensor inpL, int) {
     f->gBUFF.residual = inpL;
     const int32_t* d_pos = f->graph_mode ? f->d_state + 1 : nullptr;
     const int bound = f->graph_mode ? f->pos_bound() : pos;
+    if (f->act_int8) {  // int8 activations: [norm + quantise] -> Q, K, V -> [q/k-norm + RoPE + attention] -> [quantise] -> proj_cat + residual; 7 launches
+        if (f->graph_mode) return nullptr;  // cache rows are resolved on the host
+        SLP* qkv[3] = {&Q, &K, &V};
+        floatX* ys[3] = {ToX(Q.out), ToX(f->gBUFF.kraw), val_cache + (size_t)pos * kv_dim};
+        if (f->A8Group(ToX(inpL), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 3, qkv, ys, nullptr) != KF_OK) return nullptr;
+        if (kf_attn_block(c, ToX(Q.out), ToX(f->gBUFF.kraw), key_cache, val_cache, ToX(f->gBUFF.scratch), normQ.w ? ToX(normQ.w) : nullptr,
+                          normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos, nullptr, n_head, n_head_kv, head_dim, kv_dim, normQ.rms_eps,
+                          f->gBUFF.attn_ws->data) != KF_OK)
+            return nullptr;
+        SLP* o[1] = {&proj_cat};
+        floatX* yo[1] = {ToX(out)};
+        if (f->A8Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, q_dim, nullptr, 1, o, yo, ToX(inpL)) != KF_OK) return nullptr;
+        return out;
+    }
     if (f->fuse_level == 0) {
         if (f->graph_mode) return nullptr;  // the per-kernel path resolves cache rows on the host
         hGTensor inpQ = norm.cuFlow(inpL);
@@ -157,6 +171,16 @@ hGTensor FFN::cuInfer(hGTensor hIn, int) {
     Fish* f = hFish;
     kf_ctx* c = f->ctx;
     f->gBUFF.residual = hIn;
+    if (f->act_int8) {  // int8 activations: [norm + quantise] -> gate, up -> SwiGLU -> [quantise] -> down + residual; 6 launches (no hot-row masks: refused at switch-on)
+        SLP* gu[2] = {&gate, &up};
+        floatX* ys[2] = {ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut)};
+        if (f->A8Group(ToX(hIn), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 2, gu, ys, nullptr) != KF_OK) return nullptr;
+        if (kf_swiglu(c, ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut), ToX(f->gBUFF.scratch), latent) != KF_OK) return nullptr;
+        SLP* d[1] = {&down};
+        floatX* yd[1] = {ToX(out)};
+        if (f->A8Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, latent, nullptr, 1, d, yd, ToX(hIn)) != KF_OK) return nullptr;
+        return out;
+    }
     if (f->fuse_level == 0) {
         hGTensor xn = norm.cuFlow(hIn);
         if (!xn) return nullptr;
@@ -195,6 +219,18 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
     floatX* vrows = val_cache + (size_t)pos0 * kv_dim;
     floatX *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn);
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
+    if (f->act_int8) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
+        KF_TRY(f->A8Ready(n));
+        SLP* qkv[3] = {&Q, &K, &V};
+        floatX* ys[3] = {bq, krows, vrows};
+        KF_TRY(f->A8Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 3, qkv, ys, nullptr));
+        KF_TRY(kf_qknorm_rope_batch(c, bq, krows, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n, q_dim, kv_dim, n_head, n_head_kv,
+                                    head_dim, normQ.rms_eps));
+        KF_TRY(kf_attn_prefill(c, bq, key_cache, val_cache, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
+        SLP* o[1] = {&proj_cat};
+        floatX* yo[1] = {bx};
+        return f->A8Group(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
+    }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, krows, vrows, n, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv,
                              head_dim, normQ.rms_eps));
@@ -208,6 +244,16 @@ int FFN::cuFlow(floatX* bx, int n) {
     const int C = f->config.nEmbed;
     floatX *bn = ToX(f->gBUFF.bNorm), *bg = ToX(f->gBUFF.bGate), *bu = ToX(f->gBUFF.bUp);
     kf_weight wg = gate.w->desc(), wu = up.w->desc(), wd = down.w->desc();
+    if (f->act_int8) {
+        KF_TRY(f->A8Ready(n));
+        SLP* gu[2] = {&gate, &up};
+        floatX* ys[2] = {bg, bu};
+        KF_TRY(f->A8Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
+        KF_TRY(kf_swiglu(c, bg, bu, bg, n * latent));
+        SLP* d[1] = {&down};
+        floatX* yd[1] = {bx};
+        return f->A8Group(bg, nullptr, 0.0f, n, latent, nullptr, 1, d, yd, bx);
+    }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_gateup_swiglu_batch(c, &wg, &wu, bn, bg, bu, n));
     if (n_hot >= 0) KF_TRY(kf_zero_cold_columns(c, bg, reinterpret_cast<const int32_t*>(hot_mask->data), n, wg.ne0));  // D_matmul_sparse for every token row, as cuInfer
@@ -245,6 +291,8 @@ Fish::~Fish() {
         if (tp.area) kf_free(ctx, tp.area);
     }
     if (ctx && lin_scratch) kf_free(ctx, lin_scratch);
+    if (ctx && a8_q) kf_free(ctx, a8_q);
+    if (ctx && a8_step) kf_free(ctx, a8_step);
     if (ctx && deq_arena) kf_free(ctx, deq_arena);
     if (engine) kf_engine_destroy(engine);
     if (ctx && engine_ws) kf_free(ctx, engine_ws);
@@ -334,6 +382,92 @@ int Fish::Build(const MODEL_CARD& card, int device, void* stream) {
     return head.preLogits ? KF_OK : KF_OUTOF_GPUMEMORY;
 }
 
+// ---- int8 activations (kfh_set_act_int8)
+static const char* kf_last_error_hint(int st) {
+    return st == KF_QUANT_ERR ? "groups of 128 weights with their gama are required" : st == KF_BLAS_UNALIGN ? "data not 16-byte aligned" : "rows must be whole 128-weight groups";
+}
+// a matrix takes int8 activations unless kf::a8_plan (asked through kf_linear_a8_status: the one served-storage rule) says its storage has no integer form
+static bool a8_type(const kf_weight& w) { return kf_linear_a8_status(&w, 1) != KF_UNSUPPORTED_DATATYPE; }
+int Fish::A8Ready(int rows) {
+    if (a8_q && a8_rows >= rows) return KF_OK;
+    KF_TRY(kf_sync(ctx));
+    if (a8_q) kf_free(ctx, a8_q), a8_q = nullptr;
+    if (a8_step) kf_free(ctx, a8_step), a8_step = nullptr;
+    const size_t wide = (size_t)std::max(std::max(config.n_head * config.head_dim, config.nEmbed), config.n_ff);
+    KF_TRY(kf_malloc(ctx, wide * rows, (void**)&a8_q));
+    KF_TRY(kf_malloc(ctx, (size_t)rows * 4, (void**)&a8_step));
+    a8_rows = rows;
+    return KF_OK;
+}
+int Fish::A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
+    bool any8 = false, other = false;
+    kf_weight wd[3];
+    for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), (a8_type(wd[i]) ? any8 : other) = true;
+    if (any8) KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8_q, a8_step));
+    const floatX* xb = x;
+    if (other && norm_w) {
+        KF_TRY(kf_rmsnorm(ctx, x, norm_w, normed, n, dim, eps, nullptr));
+        xb = normed;
+    }
+    for (int i = 0; i < n_w; i++) {
+        const floatX* b = s[i]->b ? ToX(s[i]->b) : nullptr;
+        if (a8_type(wd[i]))
+            KF_TRY(kf_linear_a8(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
+        else
+            KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], b, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
+    }
+    return KF_OK;
+}
+int Fish::SetActInt8(bool on, std::string& why) {
+    if (on) {
+        if (tp.world > 1) {
+            why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
+        int n8 = 0;
+        std::vector<uint16_t> zero;
+        for (int l = 0; l < config.nLayer; l++) {
+            SelfAttention* a = attn[l].get();
+            FFN* m = ffn[l].get();
+            if (m->n_hot >= 0) {
+                why = "a hot-row mask is set on layer " + std::to_string(l) + ": the sparse forward has no int8-activation form";
+                return KF_INVALID_ARGS;
+            }
+            for (SLP* s : {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down}) {
+                if (!s->w) {
+                    why = "a layer matrix is missing";
+                    return KF_INVALID_ARGS;
+                }
+                const kf_weight w = s->w->desc();
+                if (!a8_type(w)) continue;
+                if (const int st = kf_linear_a8_status(&w, 1)) {
+                    why = "layer " + std::to_string(l) + ": kf_linear_a8 refuses a ternary / 1-bit matrix with " + std::to_string(st) + " (" + kf_last_error_hint(st) + ")";
+                    return st;
+                }
+                zero.resize(w.nGroup);
+                KF_TRY(kf_d2h(ctx, zero.data(), w.gama + w.ne0 + w.ne1, (size_t)w.nGroup * 2)); /* gama_T(ZERO) */
+                for (uint16_t z : zero)
+                    if (z & 0x7fff) {
+                        why = "layer " + std::to_string(l) + ": a group zero is not 0 -- the integer product has no zero point (YinYang and the symmetric quantiser write 0)";
+                        return KF_QUANT_ERR;
+                    }
+                n8++;
+            }
+        }
+        if (!n8) {
+            why = "no layer matrix is ternary (KF_T_SIGN) or 1-bit (KF_BOOL1 / KF_T_BINARY): nothing would take int8 activations";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
+        KF_TRY(A8Ready(1));
+    }
+    if (on != act_int8) {
+        DropEngineTable(); /* the captured graphs and the engine belong to the other arithmetic */
+        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use */
+        act_int8 = on;
+    }
+    return KF_OK;
+}
+
 // position buckets: one captured graph each; the bound fixes the attention slice count of that graph
 static const int kBuckets[] = {64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072};
 static int bucket_of(int pos) {
@@ -392,6 +526,10 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
 int Fish::EnsureEngine() {
     if (engine_state != 0) return engine_state > 0 ? KF_OK : KF_ENGINE_NOT_SERVED;
     engine_state = -1;
+    if (act_int8) {
+        engine_why = "int8 activations run on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
     KF_TRY(EngineTable(ToX(cache.key), ToX(cache.val), true, engine_why, L, d));
@@ -481,6 +619,10 @@ int Fish::EngineCheck() {
 // ------------------------------------------------------------------------------------------------ tensor parallel
 int Fish::TPInit(int rank, int world, int vocab_row0) {
     if (world < 2 || world > 8 || rank < 0 || rank >= world) return KF_INVALID_ARGS;
+    if (act_int8) { /* the TP step has no int8-activation form: switch it off first */
+        g_host_err = "kfh_tp_init: int8 activations are on and the tensor-parallel step has no int8-activation form: switch kfh_set_act_int8 off first";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
     std::memset(&tp.comm, 0, sizeof(tp.comm));
     tp.rank = rank, tp.world = world, tp.vocab_row0 = vocab_row0;
     tp.comm.rank = rank, tp.comm.world = world, tp.comm.n_max = config.nEmbed, tp.comm.per_step = 2u * (uint32_t)config.nLayer + 1u;
@@ -564,7 +706,8 @@ static int tp_group_enqueue(Fish** fs, int R) {
 }
 
 int Fish::EnqueueStep(int bound) {
-    if (tp.world > 1) return EnqueueStepTP();
+    if (tp.world > 1) return EnqueueStepTP(); /* never with int8 activations: SetActInt8 refuses a TP rank, TPInit refuses while the switch is on */
+    if (act_int8 && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
     if (use_engine && fuse_level >= 1 && engine_state > 0 && engine_embed && (graph_mode || state_tokens)) { /* embedding row read inside the launch */
         if (engine_head) { /* ... and the final norm, the LM head and the greedy pick: ONE launch per token */
             const int rc = kf_engine_step_head(ctx, engine, nullptr, ToX(x), d_state, bound, samp_params.greedy() ? 1 : 0);
@@ -652,7 +795,7 @@ bool Fish::OneLaunchStep() {
 int Fish::RunSteps(int pos, int n, bool use_graph) {
     if (pos < 0 || pos + n > config.n_ctx) return KF_INVALID_ARGS;
     KF_TRY(TPCommit());
-    if (use_graph && n > 1 && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
+    if (use_graph && n > 1 && !act_int8 && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
         constexpr int kStepsPerLaunch = 16;
         int i = 0;
         while (i < n) {
@@ -683,7 +826,7 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
     }
     for (int i = 0; i < n; i++) {
         const int p = pos + i;
-        if (fuse_level == 0) {  // per-kernel launches only (AutoAWQ weights): eager, position from the host, token from the device state
+        if (fuse_level == 0 || act_int8) {  // per-kernel launches only (AutoAWQ weights; int8 activations): eager, position from the host, token from the device state
             tok_pos = p;
             graph_mode = false, state_tokens = true;
             int rc = EnqueueStep(pos_bound());
@@ -936,6 +1079,10 @@ int XcdReplicas::MakeEngine(bool allocate) {
     const int kvd = c.n_head_kv * c.head_dim;
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
+    if (f->act_int8) {
+        why = "int8 activations run on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
     KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
     {
         char w[320];
@@ -1272,6 +1419,10 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "the ranks' cards disagree";
             return KF_INVALID_ARGS;
         }
+        if (f->act_int8) {
+            why = "int8 activations run on the per-layer launches";
+            return KF_ENGINE_NOT_SERVED;
+        }
         KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
         ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
         dp[r] = &ds[r];
@@ -1372,6 +1523,10 @@ int kfh_set_hot(void* h, int layer, const int32_t* h_hot, int n) {
     if (layer < 0 || layer >= f->config.nLayer) return KF_INVALID_ARGS;
     FFN* m = f->ffn[layer].get();
     if (h_hot && n != f->config.n_ff) return KF_INVALID_ARGS; /* arguments first: a rejected call changes nothing */
+    if (h_hot && f->act_int8) { /* the sparse forward has no int8-activation form */
+        g_host_err = "kfh_set_hot: int8 activations are on and the sparse forward has no int8-activation form: switch kfh_set_act_int8 off first";
+        return KF_INVALID_ARGS;
+    }
     f->DropEngineTable(); /* the engine's layer table (and the captured graphs) hold the masks: rebuilt on the next step; the resident bf16 copies and the measured delays do not
                              depend on them and stay */
     f->weights_gen++;     /* an XcdReplicas built on this Fish holds the masks' addresses in its layer table too: its next use re-creates the engine */
@@ -1402,6 +1557,12 @@ int kfh_set_engine(void* h, int on) {
     for (auto& g : f->graphs)
         if (g) kf_graph_destroy(g), g = nullptr;
     return KF_OK;
+}
+// int8 activations for the ternary / 1-bit layer matrices: on / off (off: today's routes, bit for bit).  A refusal leaves the switch as it was; kfh_host_error says why.
+int kfh_set_act_int8(void* h, int on) {
+    const int rc = reinterpret_cast<Fish*>(h)->SetActInt8(on != 0, g_host_err);
+    if (rc != KF_OK) g_host_err = "kfh_set_act_int8: " + g_host_err;
+    return rc;
 }
 // summation order of the decode kernels (kf_set_canonical): 1 (default) the canonical order shared with the CPU oracle, 0 the v_dot2c forms; captured graphs are dropped
 int kfh_set_canonical(void* h, int on) {

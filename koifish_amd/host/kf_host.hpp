@@ -311,6 +311,19 @@ struct Fish : SeqBuffers {
     // 8191 tokens 92.3 / 53.9 / 42.7 / 36.6 ms at 1024 / 2048 / 4096 / 8192 (scratch/prefill_chunk.py): the tile kernels want many rows per launch.
     int prefill_chunk = 8192;
     int prefill_mode = 0;  // Generate: 0 token-serial prefill like the reference, 1 batched
+    // int8 activations (kfh_set_act_int8; include/kf_abi.h "int8 activations"): every layer matrix stored ternary or 1-bit takes its input through kf_act_quant_i8 and
+    // kf_linear_a8 -- q | k | v share one quantisation of the normed row (the norm prologue), gate | up one, o_proj and down_proj quantise their own inputs; matrices of
+    // any other storage keep kf_rmsnorm + kf_linear; embedding, final norm and LM head are untouched.  Token-serial steps and token batches alike, on per-layer launches
+    // with the position from the host: the persistent engines and the captured graphs are not used while it is on.
+    bool act_int8 = false;
+    int8_t* a8_q = nullptr;     // [a8_rows][max(q_dim, nEmbed, n_ff)]
+    float* a8_step = nullptr;   // [a8_rows]
+    int a8_rows = 0;
+    int SetActInt8(bool on, std::string& why);  // the switch-on checks: a ternary / 1-bit layer matrix exists, every ZERO section of those is zero, no hot-row mask
+    int A8Ready(int rows);
+    // the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual` (may alias y[0]; n_w == 1) kf_linear's
+    // residual epilogue.  normed: [n][dim] for the bf16 route of matrices that have no integer form.
+    int A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
 };
 
 // What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their

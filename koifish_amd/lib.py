@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "kf_xengine_workspace_bytes", "kf_xengine_create", "kf_xengine_served", "kf_xengine_set_embedding", "kf_xengine_set_head", "kf_xengine_steps", "kf_xengine_check", "kf_xengine_reset", "kf_xengine_destroy", "kf_xengine_workspace_bytes_tp", "kf_xengine_create_tp", "kf_xengine_set_head_tp",
     "kf_tp_recv_bytes", "kf_tp_push_bytes", "kf_tp_commit", "kf_tp_alloc", "kf_tp_ipc_export", "kf_tp_ipc_open", "kf_tp_ipc_close", "kf_linear_f32_push", "kf_tp_reduce_recv", "kf_tp_lm_head", "kf_tp_pick",
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
+    "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status",
 ]
 
 
@@ -101,6 +102,9 @@ def load():
         hip.kf_lm_head.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_head_logprob.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_head_logprob_scratch_bytes.argtypes, hip.kf_head_logprob_scratch_bytes.restype = [C.POINTER(Weight), C.c_int], C.c_size_t
+        hip.kf_act_quant_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        hip.kf_linear_a8_status.argtypes = [C.POINTER(Weight), C.c_int]
+        hip.kf_linear_a8.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_embed.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_int, C.c_void_p, C.c_void_p]
         hip.kf_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -172,6 +176,7 @@ def load():
             getattr(host, f).argtypes = [C.c_void_p]
         host.kfh_num_graphs.argtypes = [C.c_void_p]
         host.kfh_set_engine.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_set_act_int8.argtypes = [C.c_void_p, C.c_int]
         host.kfh_engine_steps.argtypes = [C.c_void_p]
         host.kfh_engine_check.argtypes = [C.c_void_p]
         host.kfh_set_hot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]

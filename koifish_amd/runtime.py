@@ -244,6 +244,26 @@ class Context:
         L.check(self.hip.kf_linear(self.h, C.byref(d), _ptr(x), _ptr(y), _ptr(bias), 1, alpha, beta, epi, _ptr(residual)), "kf_linear")
         return y
 
+    def act_quant_i8(self, x, norm_w=None, eps=1e-6):
+        """kf_act_quant_i8: x bf16 [dim] or [rows, dim] (a row stride larger than dim is honoured) -> (q int8 of x's shape, step fp32 [rows]); with norm_w the rows are
+        first RMS-normed and rounded to bf16 as kf_rmsnorm stores them"""
+        rows, dim = (1, x.shape[0]) if x.dim() == 1 else x.shape
+        ldx = dim if x.dim() == 1 else x.stride(0)
+        assert x.stride(-1) == 1 and x.dtype == torch.bfloat16
+        q = torch.empty((rows, dim) if x.dim() == 2 else (dim,), dtype=torch.int8, device=self.device)
+        step = torch.empty(rows, dtype=torch.float32, device=self.device)
+        L.check(self.hip.kf_act_quant_i8(self.h, _ptr(x), ldx, _ptr(norm_w), eps, rows, dim, _ptr(q), _ptr(step)), "kf_act_quant_i8")
+        return q, step
+
+    def linear_a8(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_a8: a ternary / 1-bit weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
+        n = 1 if q.dim() == 1 else q.shape[0]
+        if y is None:
+            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
+        d = w.desc()
+        L.check(self.hip.kf_linear_a8(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8")
+        return y
+
     def rmsnorm(self, x, w, eps=1e-6):
         y = torch.empty_like(x)
         rows = 1 if x.dim() == 1 else x.shape[0]
@@ -470,7 +490,10 @@ class Qwen3:
             self._hot.pop(layer, None) if hasattr(self, "_hot") else None
             return
         a = np.ascontiguousarray(hot, dtype=np.int32)
-        L.check(self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size), "kfh_set_hot")
+        rc = self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size)
+        if rc != 0 and getattr(self, "_act_int8", False):   # the one refusal the host explains: a mask while int8 activations are on (the text is set on that path only)
+            raise L.KFError("kfh_set_hot failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+        L.check(rc, "kfh_set_hot")
         if not hasattr(self, "_hot"):
             self._hot = {}
         self._hot[layer] = int(self.host.kfh_n_hot(self.h, int(layer)))
@@ -479,6 +502,15 @@ class Qwen3:
         """The persistent decode engine (kf_engine_*: all layers of a step in one launch) on / off; off = the five launches per layer.
         Same arithmetic either way, bit for bit, in the canonical order (the default); in the v_dot2c order the engine's fp32 attention sums are its own (tolerances)."""
         L.check(self.host.kfh_set_engine(self.h, int(bool(on))), "kfh_set_engine")
+
+    def set_act_int8(self, on):
+        """int8 activations for every ternary / 1-bit layer matrix (kf_act_quant_i8 + kf_linear_a8; embedding, final norm and head untouched), in forward, run_steps,
+        generate, prefill, score and perplexity, on per-layer launches (engine_why() then says so).  Raises with the reason when no layer matrix is ternary / 1-bit, a group
+        zero is not 0 or a hot-row mask is set.  step_bytes is unchanged: the weights read are the same."""
+        rc = self.host.kfh_set_act_int8(self.h, int(bool(on)))
+        if rc != 0:
+            raise L.KFError("set_act_int8 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+        self._act_int8 = bool(on)
 
     def set_canonical(self, on):
         """1 (the library default): the decode kernels sum in the canonical order the CPU oracle shares (bit-exact logits, ids and KV rows); 0: the v_dot2c_f32_bf16 / fp32 forms"""
