@@ -408,6 +408,36 @@ int kf_fused_classifier(kf_ctx* ctx, kf_bf16* logits, float* losses, kf_bf16* pr
 int kf_adamw(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, size_t n, int mv_type, float learning_rate, float beta1, float beta2,
              float beta1_correction, float beta2_correction, float eps, float weight_decay, float grad_scale, uint32_t seed, int32_t* d_status);
 
+/* ---- Muon, the reference's default optimiser (CLI_params.hpp:627), for a hidden matrix W [ne0 = out][ne1 = in] with ne0 >= ne1: PIPE_Muon::CU_core
+ * (src/Device/CUDA/Optimizer.cu:498-583; set up by PIPE_Muon::Update, src/Device/Pipe.cpp:16-57).  The reference's column-major X (m = ne1, n = ne0) is W^T, its
+ * A = X X^T is W^T W [ne1, ne1]; isTrans is forced off there and is not built here.  grad_scale is NOT applied on this path, as in the reference (CU_muon_mG reads
+ * grads0 as they are).  No entry allocates or synchronises with the host: the sums of squares stay on the device (the reference's D2e read-backs are not restated).
+ * Sums of squares are deterministic: one fp64 partial per workgroup, added in workgroup order by a one-workgroup follow-up launch (the reference: atomicAdd).
+ * Refusals are KF_INVALID_ARGS and launch nothing: ne0 < ne1, a dimension that is no multiple of 64, n_iter outside [0, 16], a tensor that is not 16-byte aligned,
+ * a scratch that is missing, not 256-byte aligned or shorter than kf_muon_scratch_bytes(ne0, ne1) (0 for a shape the entries refuse).
+ *
+ * scratch layout (every offset a multiple of 256; up = round up to 256):  A [ne1][ne1] bf16 at 0;  B [ne1][ne1] bf16 at up(2 ne1^2);  X [ne0][ne1] bf16 at
+ * 2 up(2 ne1^2) (kf_muon: the momentum kernel's output, orthogonalised in place);  X' (the ping-pong buffer) at + up(2 ne0 ne1);  ceil(ne0 ne1 / 4096) fp64 partial
+ * sums;  two doubles: sum X^2, and kf_muon's wnorm^2 when the caller passes no destination.  Contents need not be initialised; after a call A and B hold the last
+ * iteration's matrices. */
+size_t kf_muon_scratch_bytes(int ne0, int ne1);
+/* CU_muon_mG (Optimizer.cu:93-109) in TASKA_1p1 geometry (512 threads x 8 bf16, as kf_adamw):  mG <- sr(mG + (1 - mui)(g - mG)), then X <- sr(g + mui (mG' - g)) with
+ * mG' the bf16 value just stored; sr = the seeded stochastic bf16 store of kf_adamw, one threshold per thread.  *d_sumsq (device) = sum of X^2 over the stored X.
+ * n a multiple of 8, at most 2^28. */
+int kf_muon_momentum(kf_ctx* ctx, kf_bf16* mG, const kf_bf16* grads, kf_bf16* X, size_t n, float mui, uint32_t seed, double* d_sumsq);
+/* The orthogonalisation of CU_core (Optimizer.cu:522-570), X [ne0, ne1] in place:  alpha = 1 / (sqrt(sum X^2) + eps_muon) in fp64 on the device, narrowed to float;
+ * X <- bf16(X + (alpha - 1) X);  n_iter times:  A = bf16(X^T X),  B = bf16(b A + bf16(c A A)),  X <- bf16(a X + bf16(X B))  (the bf16 stores of cublasGemmEx and
+ * cublasAxpyEx; fp32 accumulation);  X <- bf16(X + beta X), beta = sqrt(max(1, ne1 / ne0)) - 1, which is 0 for every shape this entry takes.  A, A A and B are
+ * computed on and above the diagonal only and mirrored: symmetric bit for bit.  d_sumsq NULL: the entry sums X itself. */
+int kf_newton_schulz(kf_ctx* ctx, kf_bf16* X, int ne0, int ne1, const double* d_sumsq_or_null, float eps_muon, int n_iter, float a, float b, float c, void* scratch,
+                     size_t scratch_bytes);
+/* CU_muon_update (Optimizer.cu:111-131), same geometry and threshold rule:  p <- sr((1 - lr weight_decay) p + (-lr) X);  grads are zeroed;  *d_wnormsq (device,
+ * optional) = sum of the stored p^2, the reference's wnorm^2. */
+int kf_muon_apply(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, const kf_bf16* X, size_t n, float lr, float weight_decay, uint32_t seed, double* d_wnormsq_or_null);
+/* The three in order, as CU_core runs them, with a / b / c = 3.4445 / -4.7750 / 2.0315 (Pipe.hpp:131) and one seed for both elementwise kernels (task_11.config.seed). */
+int kf_muon(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, kf_bf16* mG, int ne0, int ne1, float lr, float weight_decay, float mui, float eps_muon, int n_iter,
+            uint32_t seed, void* scratch, size_t scratch_bytes, double* d_wnormsq_or_null);
+
 /* ---- token batch (prompt prefill).  The reference feeds the prompt one token at a time through the decode path (Fish::Chat,
  * GoPT.cpp:1139-1146); its batched forward exists only on the training side (SelfAttention::cuFlow / ROPE::cuFlow,
  * NeuronFuse.cu:692-731, rope.cu).  These entries run the same per-token arithmetic for n_tok consecutive positions at once;

@@ -24,6 +24,7 @@ struct kf_ctx {
     bool capturing;
     float* amax_val; /* per-workgroup partial maxima for kf_lm_head when the caller passes no scratch */
     int* amax_idx;
+    double* muon_part; /* per-workgroup partial sums of squares of kf_muon_momentum / kf_muon_apply (those entries take no scratch) */
     int canonical;    /* 1: the decode kernels sum in the canonical order of oracle/kf_oracle.c sections 4c / 6 (bit-exact against the oracle; the default); 0: v_dot2c / fp32 forms */
     void* scratch;    /* caller-owned workspace of kf_linear (kf_set_scratch): AWQ slice partials, or a weight dequantised to bf16 */
     size_t scratch_bytes;
@@ -90,6 +91,7 @@ int kf_init(int device, void* stream, kf_ctx** out) {
     }
     HIPCHK(hipMalloc(&c->amax_val, sizeof(float) * kf::KF_MAX_ARGMAX_PARTIALS));
     HIPCHK(hipMalloc(&c->amax_idx, sizeof(int) * kf::KF_MAX_ARGMAX_PARTIALS));
+    HIPCHK(hipMalloc(&c->muon_part, sizeof(double) * kf::KF_MUON_MAX_PARTIALS));
     c->scratch = nullptr, c->scratch_bytes = 0;
     c->arena = nullptr, c->arena_bytes = c->arena_used = 0;
     c->canonical = 1;
@@ -148,7 +150,7 @@ int kf_destroy(kf_ctx* c) {
     if (!c) return KF_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->amax_val), (void)hipFree(c->amax_idx);
+    (void)hipFree(c->amax_val), (void)hipFree(c->amax_idx), (void)hipFree(c->muon_part);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return KF_OK;
@@ -1167,6 +1169,57 @@ int kf_adamw(kf_ctx* c, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, siz
     if (!al16(params) || !al16(grads) || !al16(gm) || !al16(gv)) return fail(KF_BLAS_UNALIGN, "kf_adamw: tensors must be 16-byte aligned");
     RET(kf::adamw_launch(c->stream, params, grads, gm, gv, n, mv_type == KF_BF16, learning_rate, beta1, beta2, beta1_correction, beta2_correction, eps,
                          weight_decay, grad_scale, seed, d_status));
+}
+
+
+// ---- Muon (PIPE_Muon::CU_core, Optimizer.cu:498-583): kf_muon.hip
+static bool muon_dims_ok(int ne0, int ne1) { return ne1 >= 64 && ne0 >= ne1 && !(ne0 % 64) && !(ne1 % 64); }
+static int muon_scratch_ok(const char* who, int ne0, int ne1, const void* scratch, size_t scratch_bytes) {
+    if (!scratch || (((uintptr_t)scratch) & 255)) return fail(KF_INVALID_ARGS, "%s: scratch is missing or not 256-byte aligned", who);
+    const size_t need = kf::muon_layout(ne0, ne1).bytes;
+    if (scratch_bytes < need) return fail(KF_INVALID_ARGS, "%s: scratch of %zu bytes, kf_muon_scratch_bytes(%d, %d) = %zu", who, scratch_bytes, ne0, ne1, need);
+    return KF_OK;
+}
+size_t kf_muon_scratch_bytes(int ne0, int ne1) { return muon_dims_ok(ne0, ne1) ? kf::muon_layout(ne0, ne1).bytes : 0; }
+int kf_muon_momentum(kf_ctx* c, kf_bf16* mG, const kf_bf16* grads, kf_bf16* X, size_t n, float mui, uint32_t seed, double* d_sumsq) {
+    CHKCTX(c);
+    if (!mG || !grads || !X || !d_sumsq) return fail(KF_INVALID_ARGS, "kf_muon_momentum: null pointer");
+    if (n == 0 || n % 8 || n > (size_t)kf::KF_MUON_MAX_PARTIALS * 4096) return fail(KF_INVALID_ARGS, "kf_muon_momentum: n = %zu is not a multiple of 8 in (0, 2^28]", n);
+    if (!al16(mG) || !al16(grads) || !al16(X) || (((uintptr_t)d_sumsq) & 7)) return fail(KF_INVALID_ARGS, "kf_muon_momentum: tensors must be 16-byte aligned");
+    RET(kf::muon_momentum_launch(c->stream, mG, grads, X, n, mui, seed, c->muon_part, d_sumsq));
+}
+int kf_muon_apply(kf_ctx* c, kf_bf16* params, kf_bf16* grads, const kf_bf16* X, size_t n, float lr, float weight_decay, uint32_t seed, double* d_wnormsq) {
+    CHKCTX(c);
+    if (!params || !grads || !X) return fail(KF_INVALID_ARGS, "kf_muon_apply: null pointer");
+    if (n == 0 || n % 8 || n > (size_t)kf::KF_MUON_MAX_PARTIALS * 4096) return fail(KF_INVALID_ARGS, "kf_muon_apply: n = %zu is not a multiple of 8 in (0, 2^28]", n);
+    if (!al16(params) || !al16(grads) || !al16(X) || (((uintptr_t)d_wnormsq) & 7)) return fail(KF_INVALID_ARGS, "kf_muon_apply: tensors must be 16-byte aligned");
+    RET(kf::muon_apply_launch(c->stream, params, grads, X, n, lr, weight_decay, seed, c->muon_part, d_wnormsq));
+}
+int kf_newton_schulz(kf_ctx* c, kf_bf16* X, int ne0, int ne1, const double* d_sumsq, float eps_muon, int n_iter, float a, float b, float cc, void* scratch, size_t scratch_bytes) {
+    CHKCTX(c);
+    if (!X || !al16(X) || (((uintptr_t)d_sumsq) & 7)) return fail(KF_INVALID_ARGS, "kf_newton_schulz: X is null or not 16-byte aligned");
+    if (!muon_dims_ok(ne0, ne1)) return fail(KF_INVALID_ARGS, "kf_newton_schulz: needs ne0 >= ne1, both multiples of 64 (got %d x %d)", ne0, ne1);
+    if (n_iter < 0 || n_iter > 16) return fail(KF_INVALID_ARGS, "kf_newton_schulz: n_iter = %d outside [0, 16]", n_iter);
+    const int r = muon_scratch_ok("kf_newton_schulz", ne0, ne1, scratch, scratch_bytes);
+    if (r) return r;
+    RET(kf::newton_schulz_launch(c->stream, X, ne0, ne1, d_sumsq, eps_muon, n_iter, a, b, cc, scratch));
+}
+int kf_muon(kf_ctx* c, kf_bf16* params, kf_bf16* grads, kf_bf16* mG, int ne0, int ne1, float lr, float weight_decay, float mui, float eps_muon, int n_iter, uint32_t seed,
+            void* scratch, size_t scratch_bytes, double* d_wnormsq) {
+    CHKCTX(c);
+    if (!params || !grads || !mG || !al16(params) || !al16(grads) || !al16(mG) || (((uintptr_t)d_wnormsq) & 7)) return fail(KF_INVALID_ARGS, "kf_muon: a tensor is null or not 16-byte aligned");
+    if (!muon_dims_ok(ne0, ne1)) return fail(KF_INVALID_ARGS, "kf_muon: needs ne0 >= ne1, both multiples of 64 (got %d x %d)", ne0, ne1);
+    if (n_iter < 0 || n_iter > 16) return fail(KF_INVALID_ARGS, "kf_muon: n_iter = %d outside [0, 16]", n_iter);
+    int r = muon_scratch_ok("kf_muon", ne0, ne1, scratch, scratch_bytes);
+    if (r) return r;
+    const kf::MuonLayout L = kf::muon_layout(ne0, ne1);
+    char* const sc = (char*)scratch;
+    uint16_t* const X = (uint16_t*)(sc + L.X0);
+    double *const part = (double*)(sc + L.part), *const dbl = (double*)(sc + L.dbl);
+    const size_t n = (size_t)ne0 * ne1;
+    if ((r = kf::muon_momentum_launch(c->stream, mG, grads, X, n, mui, seed, part, dbl)) != KF_OK) return fail(r, "kf_muon: momentum failed with %d", r);
+    if ((r = kf::newton_schulz_launch(c->stream, X, ne0, ne1, dbl, eps_muon, n_iter, 3.4445f, -4.7750f, 2.0315f, scratch)) != KF_OK) return fail(r, "kf_muon: Newton-Schulz failed with %d", r);
+    RET(kf::muon_apply_launch(c->stream, params, grads, X, n, lr, weight_decay, seed, part, d_wnormsq ? d_wnormsq : dbl + 1));
 }
 
 // ---- persistent decode engine

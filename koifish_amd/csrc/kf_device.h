@@ -196,6 +196,29 @@ __device__ __forceinline__ double block_sumsq_bf16(const uint16_t* __restrict__ 
     return tot;
 }
 
+// SquirrelNoise5 (utils.cuh:296-326) and the seeded stochastic bf16 store CU_Float2T<bf16> (packedN.cuh:62-72) of the optimiser kernels (kf_ops.hip adamw_kernel,
+// kf_muon.hip): one 16-bit threshold per thread, the low 16 bits of the fp32 compared with it, then round-to-nearest of the all-ones / all-zeros padded value
+__device__ __forceinline__ unsigned int squirrel5(unsigned int pos, unsigned int seed) {
+    unsigned int b = pos;
+    b *= 0xd2a80a3fu;
+    b += seed;
+    b ^= (b >> 9);
+    b += 0xa884f197u;
+    b ^= (b >> 11);
+    b *= 0x6C736F4Bu;
+    b ^= (b >> 13);
+    b += 0xB79F3ABBu;
+    b ^= (b >> 15);
+    b *= 0x1b56c4f5u;
+    b ^= (b >> 17);
+    return b;
+}
+__device__ __forceinline__ uint16_t stochastic_bf16(float a, unsigned int threshold) {
+    unsigned int u = __float_as_uint(a);
+    u = ((u & 0xFFFFu) > threshold) ? (u | 0xFFFFu) : (u & ~0xFFFFu);
+    return f2bf(__uint_as_float(u));
+}
+
 // ---- 16-entry bf16 table in registers, looked up with v_perm_b32 (4-bit weights; see kf_gemv_lut.hip / kf_gemv.hip)
 struct PermLut {
     uint32_t tl[4], th[4];

@@ -208,6 +208,15 @@ int embed_launch(hipStream_t st, const kf_weight* w, int token, const int32_t* d
 int dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out, int ilv_n = 1, int ilv_i = 0); /* ilv_n > 1: rows interleaved with ilv_n - 1 other matrices in blocks of 16 (kf_ops.hip) */
 int adamw_launch(hipStream_t st, uint16_t* params, uint16_t* grads, void* gm, void* gv, size_t n, int mv_bf16, float lr, float beta1, float beta2, float b1c,
                  float b2c, float eps, float wd, float grad_scale, unsigned int seed, int* status);
+// ---- Muon (kf_muon.hip): PIPE_Muon::CU_core.  One scratch per tensor shape: A, B [ne1][ne1] bf16, two X buffers [ne0][ne1] bf16, one fp64 partial per 4096 elements, two doubles
+struct MuonLayout {
+    size_t A, B, X0, X1, part, dbl, bytes; /* byte offsets, each a multiple of 256 */
+};
+constexpr int KF_MUON_MAX_PARTIALS = 1 << 16; /* the context's own partial sums for kf_muon_momentum / kf_muon_apply: n <= 2^28 elements */
+MuonLayout muon_layout(int ne0, int ne1);
+int muon_momentum_launch(hipStream_t st, uint16_t* mG, const uint16_t* grads, uint16_t* X, size_t n, float mui, unsigned int seed, double* partials, double* d_sumsq);
+int muon_apply_launch(hipStream_t st, uint16_t* params, uint16_t* grads, const uint16_t* X, size_t n, float lr, float wd, unsigned int seed, double* partials, double* d_wnormsq);
+int newton_schulz_launch(hipStream_t st, uint16_t* X, int ne0, int ne1, const double* d_sumsq, float eps, int n_iter, float a, float b, float c, void* scratch);
 int sample_launch(hipStream_t st, const uint16_t* logits, int n, int top_k, float temperature, float top_p, unsigned long long* rng, int32_t* d_token,
                   int32_t* d_state, int32_t* d_tokens_out, const int32_t* d_forced, int n_forced, int true_topk = 0);
 int quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src, int symmetric);

@@ -855,26 +855,7 @@ int quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src, int
 // 16-bit threshold per thread from SquirrelNoise5(threadIdx.x + PRIME * (blockIdx.x * blockDim.x), seed) (utils.cuh:296-326): with the
 // same geometry the update is bit-identical to the oracle's restatement.  HBM-bound: 16 B per parameter with bf16 moments
 // (p, g, m, v read and written), 24 B with fp32 moments.
-__device__ __forceinline__ unsigned int squirrel5(unsigned int pos, unsigned int seed) {
-    unsigned int b = pos;
-    b *= 0xd2a80a3fu;
-    b += seed;
-    b ^= (b >> 9);
-    b += 0xa884f197u;
-    b ^= (b >> 11);
-    b *= 0x6C736F4Bu;
-    b ^= (b >> 13);
-    b += 0xB79F3ABBu;
-    b ^= (b >> 15);
-    b *= 0x1b56c4f5u;
-    b ^= (b >> 17);
-    return b;
-}
-__device__ __forceinline__ uint16_t stochastic_bf16(float a, unsigned int threshold) {
-    unsigned int u = __float_as_uint(a);
-    u = ((u & 0xFFFFu) > threshold) ? (u | 0xFFFFu) : (u & ~0xFFFFu);
-    return f2bf(__uint_as_float(u));
-}
+// squirrel5 / stochastic_bf16: kf_device.h (shared with the Muon kernels of kf_muon.hip)
 template <bool MV_BF16>
 __global__ void __launch_bounds__(512) adamw_kernel(uint16_t* __restrict__ params, uint16_t* __restrict__ grads, void* __restrict__ gm_, void* __restrict__ gv_, size_t n,
                                                     float lr, float beta1, float beta2, float b1c, float b2c, float eps, float wd, float grad_scale, unsigned int seed,

@@ -9,6 +9,9 @@
 // Order of the registered tensors (kfh_gpt2_set_param index):  per block l, 12 in a row: qkv.w qkv.b proj.w proj.b fc.w fc.b proj2.w proj2.b ln1.w ln1.b ln2.w
 // ln2.b;  then wte, wpe, lnf.w, lnf.b.   The AdamW seed of tensor i at optimizer step t is seed + 7919 t + i (one seed per launch, as the reference draws one per
 // tensor update).
+//
+// The optimiser is a switch (kfh_gpt2_set_optimizer): AdamW on everything (the default), or the reference's default "muon" (OPT_Muon, Optimizer.cpp:1014-1056;
+// PIPE_Muon::Update, Pipe.cpp:16-57): MUON_params_::isAdamW restated -- a block's weight matrix with ne0 >= ne1 goes through kf_muon, everything else keeps kf_adamw.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -42,6 +45,12 @@ struct GPT2Trainer {
     void *sc_lin = nullptr, *sc_ln = nullptr, *sc_at = nullptr;
     const int32_t* ids = nullptr;  // of the last Forward (the embedding backward scatters by them)
     long long t = 0;               // optimizer steps taken
+    // Muon (kfh_gpt2_set_optimizer): lr_scale, mui, eps_muon, tpDecay of MUON_params_; the caller owns the scratch (sized for the largest Muon tensor)
+    enum { OPT_ADAMW = 0, OPT_MUON = 1 };
+    int method = OPT_ADAMW, tp_decay = 1;
+    float lr_scale = 1.0f, mui = 0.95f, eps_muon = 1e-7f;
+    void* sc_muon = nullptr;
+    size_t sc_muon_bytes = 0;
 
     enum { QKV_W = 0, QKV_B, PROJ_W, PROJ_B, FC_W, FC_B, PROJ2_W, PROJ2_B, LN1_W, LN1_B, LN2_W, LN2_B, PER_BLOCK };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_BLOCK + k]; }
@@ -50,6 +59,34 @@ struct GPT2Trainer {
     TrainTensor& LnfW() { return params[(size_t)NL * PER_BLOCK + 2]; }
     TrainTensor& LnfB() { return params[(size_t)NL * PER_BLOCK + 3]; }
 
+    // MUON_params_::isAdamW restated: a Muon tensor is one of a block's four weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape);
+    // wte, wpe, biases, norms and matrices with ne0 < ne1 (proj2) stay on AdamW
+    bool IsMuon(size_t i) const {
+        if (method != OPT_MUON || i >= (size_t)NL * PER_BLOCK) return false;
+        const int k = (int)(i % PER_BLOCK);
+        const TrainTensor& e = params[i];
+        return (k == QKV_W || k == PROJ_W || k == FC_W || k == PROJ2_W) && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
+    }
+    int SetOptimizer(int method_, float lr_scale_, float mui_, float eps_muon_, int tp_decay_, void* scratch, size_t scratch_bytes) {
+        if (method_ != OPT_ADAMW && method_ != OPT_MUON) return KF_INVALID_ARGS;
+        if (method_ == OPT_MUON) {
+            if (!(lr_scale_ > 0.0f) || !scratch) return KF_INVALID_ARGS;
+            const int keep = method;
+            method = OPT_MUON;
+            size_t need = 0;
+            bool ok = true;
+            for (size_t i = 0; i < params.size(); i++)
+                if (IsMuon(i)) {
+                    const size_t b = kf_muon_scratch_bytes(params[i].blob.ne0, params[i].blob.ne1);
+                    ok = ok && b > 0;
+                    need = b > need ? b : need;
+                }
+            method = keep;
+            if (!ok || scratch_bytes < need) return KF_INVALID_ARGS;
+        }
+        method = method_, lr_scale = lr_scale_, mui = mui_, eps_muon = eps_muon_, tp_decay = tp_decay_, sc_muon = scratch, sc_muon_bytes = scratch_bytes;
+        return KF_OK;
+    }
     int Ready() const {
         for (const TrainTensor& e : params)
             if (!e.p || !e.g || !e.m || !e.v || e.n < 8 || (e.n & 7)) return KF_INVALID_ARGS;
@@ -120,15 +157,23 @@ struct GPT2Trainer {
         return kf_embed_backward(ctx, Wte().g, C, Wpe().g, dx, ids, B, T, C, Vp);
     }
     // CU_adamw_ on every tensor (its own master, moments and gradient; seeded stochastic rounding), then the re-quantisation of every quantised matrix from its
-    // updated master.  kf_adamw zeroes the gradients it has consumed.
+    // updated master.  kf_adamw zeroes the gradients it has consumed.  With the Muon switch a Muon tensor takes PIPE_Muon::CU_core instead (kf_muon: mG is its m
+    // buffer, v is not touched; lr x lr_scale, the weight decay by tpDecay, Pipe.cpp:23-37; the same seed as its AdamW launch would have had).
     int Update(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
         KF_TRY(Ready());
         t++;
         const float b1c = (float)(1.0 - std::pow(beta1, (double)t)), b2c = (float)(1.0 - std::pow(beta2, (double)t)); /* the bias corrections, in double like the host side of the reference */
         for (size_t i = 0; i < params.size(); i++) {
             TrainTensor& e = params[i];
+            const uint32_t sd = (uint32_t)((seed + 7919ull * (unsigned long long)t + i) & 0xFFFFFFFFull);
+            if (IsMuon(i)) {
+                const float wd0 = e.decay ? wd : 0.0f, wd_muon = tp_decay == 0 ? 0.0f : (tp_decay == 1 ? wd0 / lr_scale : wd0);
+                KF_TRY(kf_muon(ctx, e.p, e.g, (kf_bf16*)e.m, e.blob.ne0, e.blob.ne1, lr * lr_scale, wd_muon, mui, eps_muon, 5, sd, sc_muon, sc_muon_bytes, nullptr));
+                if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
+                continue;
+            }
             KF_TRY(kf_adamw(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f, 1.0f,
-                            (uint32_t)((seed + 7919ull * (unsigned long long)t + i) & 0xFFFFFFFFull), nullptr));
+                            sd, nullptr));
             if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
         }
         return KF_OK;
@@ -188,6 +233,11 @@ int kfh_gpt2_step(void* h, const int32_t* d_ids, const int32_t* d_tgt, float lr,
     KF_TRY(t->Forward(d_ids, d_tgt));
     KF_TRY(t->Backward());
     return t->Update(lr, beta1, beta2, eps, wd, seed);
+}
+// method 0: AdamW on every tensor (the default); 1: Muon (the reference's default) on the Muon tensors, AdamW on the rest.  Call after every kfh_gpt2_set_param:
+// scratch (device memory, 256-byte aligned, the caller's) must hold kf_muon_scratch_bytes of the largest Muon tensor; KF_INVALID_ARGS otherwise, nothing changes.
+int kfh_gpt2_set_optimizer(void* h, int method, float lr_scale, float mui, float eps_muon, int tp_decay, void* scratch, size_t scratch_bytes) {
+    return reinterpret_cast<GPT2Trainer*>(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
 }
 long long kfh_gpt2_steps_taken(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->t; }
 }

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "kf_tp_recv_bytes", "kf_tp_push_bytes", "kf_tp_commit", "kf_tp_alloc", "kf_tp_ipc_export", "kf_tp_ipc_open", "kf_tp_ipc_close", "kf_linear_f32_push", "kf_tp_reduce_recv", "kf_tp_lm_head", "kf_tp_pick",
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
     "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status",
+    "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
 ]
 
 
@@ -69,6 +70,11 @@ def load():
         hip.kf_linear_multi_scratch_bytes.argtypes, hip.kf_linear_multi_scratch_bytes.restype = [C.c_int, C.c_void_p, C.c_int], C.c_size_t
         hip.kf_gateup_swiglu_batch.argtypes = [C.c_void_p, C.POINTER(Weight), C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_adamw.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_int] + [C.c_float] * 8 + [C.c_uint32, C.c_void_p]
+        hip.kf_muon_scratch_bytes.argtypes, hip.kf_muon_scratch_bytes.restype = [C.c_int, C.c_int], C.c_size_t
+        hip.kf_muon_momentum.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_float, C.c_uint32, C.c_void_p]
+        hip.kf_newton_schulz.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
+        hip.kf_muon_apply.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_float, C.c_float, C.c_uint32, C.c_void_p]
+        hip.kf_muon.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         hip.kf_sample_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_layernorm.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         hip.kf_qknorm_rope_train.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
@@ -217,6 +223,7 @@ def load():
         host.kfh_gpt2_backward.argtypes = [C.c_void_p]
         host.kfh_gpt2_update.argtypes = [C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
         host.kfh_gpt2_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
+        host.kfh_gpt2_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
         host.kfh_gpt2_steps_taken.restype = C.c_longlong
         host.kfh_gpt2_steps_taken.argtypes = [C.c_void_p]
         # eight decoders, one per XCD (kf_xengine_*): handles are koifish::XcdReplicas* of the host library

@@ -94,6 +94,23 @@ class GPT2Step:
                                   + [self._sp_lin, self._sc_ln.data_ptr(), self._sc_at.data_ptr()]))
         L.check(host.kfh_gpt2_set_buffers(self.h, arr), "kfh_gpt2_set_buffers")
 
+    def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
+        """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a block's weight matrices with ne0 >= ne1 (qkv, proj, fc) take SGD-momentum +
+        five Newton-Schulz steps (kf_muon: lr x lr_scale, weight decay by tp_decay as Pipe.cpp:23-37, mG = the tensor's m buffer); proj2, the embeddings, biases and norms
+        keep kf_adamw.  Owns the scratch, sized for the largest Muon tensor."""
+        if method not in ("adamw", "muon"):
+            raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
+        sp, nb = None, 0
+        if method == "muon":
+            shapes = [tuple(e["p"].shape) for e in self.params if e["blob"] is not None and e["name"].startswith("h") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
+            nb = max(self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes)
+            if nb == 0:
+                raise L.KFError("muon: a hidden matrix has a dimension that is no multiple of 64")
+            self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
+            sp = (self._sc_muon.data_ptr() + 255) & ~255
+        L.check(self.ctx.host.kfh_gpt2_set_optimizer(self.h, int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb), "kfh_gpt2_set_optimizer")
+        self.optimizer = method
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.host.kfh_gpt2_destroy(self.h)
