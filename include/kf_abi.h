@@ -157,6 +157,7 @@ int kf_set_scratch(kf_ctx* ctx, void* scratch, size_t bytes);
  * full, further weights go through the scratch as before.  kf_dequant_arena_used: bytes filled so far.  Not while capturing. */
 int kf_set_dequant_arena(kf_ctx* ctx, void* arena, size_t bytes);
 size_t kf_dequant_arena_used(kf_ctx* ctx);
+size_t kf_dequant_arena_bytes(kf_ctx* ctx); /* the size of the arena set, 0: none -- a trainer that changes quantised weights in place asks before it multiplies them */
 size_t kf_resident_scratch_bytes(void); /* a kf_set_scratch workspace of at least this size lets kf_linear's resident-copy route cut short token batches into k-pieces */
 int kf_linear(kf_ctx* ctx, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta,
               uint32_t epilogue, const kf_bf16* residual);
@@ -367,6 +368,22 @@ int kf_embed_backward(kf_ctx* ctx, kf_bf16* dwte_or_null, long long ldw, kf_bf16
 size_t kf_linear_backward_scratch_bytes(int OC, int IC, int n);
 int kf_linear_backward(kf_ctx* ctx, const kf_weight* w, const kf_bf16* deltaIn, const kf_bf16* inp_or_null, kf_bf16* delta_or_null, kf_bf16* gW_or_null,
                        kf_bf16* gBias_or_null, int n, int accumulate_delta, void* scratch);
+
+/* The other way to train a quantised layer, "train_target": "gama" (SLP::Back with w->gama_param, NeuronFuse.cu:538-549 -> GamaBack_v0 -> CU_GamaBack_2,
+ * kernel/quantizer.cu:66-94; GTensor::InitGamaParam, GTensor.cpp:903-945): the packed integers stay frozen and each group's (zero, step) pair is the parameter.
+ * With w = step (q - qBias) - zero and dW = deltaIn^T . inp (the gW of kf_linear_backward, never written here), per 128-column group g of row r:
+ *   gGama[g]          = bf16(gGama[g]          + scale * (- sum_{c in g} dW[r, c]))                      (zero)
+ *   gGama[nGroup + g] = bf16(gGama[nGroup + g] + scale * (+ sum_{c in g} dW[r, c] (q[r, c] - qBias)))     (step)
+ * -- the order of the blob's [ZERO nGroup][STEP nGroup] and of the reference's gW[idG], gW[idG + nG].  q - qBias is the integer read from the Packed128 stream; the
+ * weight is never dequantised.  Sums in fp32 (MFMA accumulation over the n token rows, then the 128 columns), accumulating into gGama as gW / gBias do (kf_adamw zeroes
+ * what it consumed).  scale: CU_GamaBack_2 divides by nSample (SLP::Back passes B, not B * T); 1.0f is the chain rule's value and what this project's trainer passes.
+ * Deterministic: no atomics; a cut over n leaves fp32 partials in the scratch that a second launch adds in slab order; results do not depend on the scratch's contents.
+ * Served: KF_QUANT_GROUP storage with lGroup 128 of KF_Q4 (qBias 0 or 8), KF_T_SIGN, KF_BOOL1.  Refusals launch nothing: IC % 128, OC % 64, OC < 128 or n % 64 violated,
+ * a null pointer or a missing scratch: KF_INVALID_ARGS; AutoAWQ layout, row-LUT / row-RTN modes, any other type: KF_UNSUPPORTED_DATATYPE; deltaIn / inp / gGama not
+ * 16-byte aligned or scratch not 256-byte aligned: KF_BLAS_UNALIGN.  scratch: kf_gama_backward_scratch_bytes(OC, IC, n) bytes (0 for a refused shape); the entry is not
+ * told its size -- the caller sizes it with that function.  The input gradient stays with kf_linear_backward(..., gW = NULL). */
+size_t kf_gama_backward_scratch_bytes(int OC, int IC, int n);
+int kf_gama_backward(kf_ctx* ctx, const kf_weight* w, const kf_bf16* deltaIn, const kf_bf16* inp, kf_bf16* gGama, int n, float scale, void* scratch);
 
 /* LayerNorm / RMSNorm backward (LayerNormal::cuFlow, backward branch, T.cu:605-646: layernorm_backward -> layernorm_backward_kernel10, layernorm.cuh:311-503;
  * RMS: CU_rms_back_llmc, layernorm.cuh:863-1051).  mean == NULL selects RMSNorm.  dinp (the residual-path gradient on entry) becomes

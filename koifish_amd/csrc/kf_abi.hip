@@ -16,6 +16,7 @@
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
 #include "kf_score_plan.h"
+#include "kf_gama_plan.h"
 
 struct kf_ctx {
     int device;
@@ -340,6 +341,7 @@ int kf_set_dequant_arena(kf_ctx* c, void* arena, size_t bytes) {
     return KF_OK;
 }
 size_t kf_dequant_arena_used(kf_ctx* c) { return c ? c->arena_used : 0; }
+size_t kf_dequant_arena_bytes(kf_ctx* c) { return c && c->arena ? c->arena_bytes : 0; }
 size_t kf_resident_scratch_bytes(void) { return kf::gemm3_sk_ws_bytes(); }
 int kf_set_scratch(kf_ctx* c, void* scratch, size_t bytes) {
     CHKCTX(c);
@@ -1074,6 +1076,34 @@ int kf_linear_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, co
         }
     }
     return KF_OK;
+}
+// ---- "train_target": "gama" (SLP::Back's gama branch -> CU_GamaBack_2): the (zero, step) gradients of a group-quantised weight (kf_gama_bwd.hip; the launch: kf_gama_plan.h)
+size_t kf_gama_backward_scratch_bytes(int OC, int IC, int n) {
+    const kf::GamaPlan p = kf::gama_plan(OC, IC, n);
+    return p.status == KF_OK ? (size_t)p.scratch : 0;
+}
+int kf_gama_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, const kf_bf16* inp, kf_bf16* gGama, int n, float scale, void* scratch) {
+    CHKCTX(c);
+    int r = check_weight(w, "kf_gama_backward");
+    if (r) return r;
+    if (w->qzeros || w->qscales) return fail(KF_UNSUPPORTED_DATATYPE, "kf_gama_backward: AutoAWQ-layout weights are inference-only");
+    if (w->quant != KF_QUANT_GROUP) return fail(KF_UNSUPPORTED_DATATYPE, "kf_gama_backward: row-quantised storage (quant mode %d) has no (zero, step) per group", w->quant);
+    int fmt;
+    switch (w->type) {
+        case KF_Q4: fmt = kf::FMT_Q4; break;
+        case KF_T_SIGN: fmt = kf::FMT_Q2; break;
+        case KF_BOOL1: fmt = kf::FMT_Q1; break;
+        default: return fail(KF_UNSUPPORTED_DATATYPE, "kf_gama_backward: type %d is not a PackedQ group storage (KF_Q4, KF_T_SIGN, KF_BOOL1)", w->type);
+    }
+    if (!deltaIn || !inp || !gGama || !scratch) return fail(KF_INVALID_ARGS, "kf_gama_backward: null deltaIn / inp / gGama / scratch");
+    const int OC = w->ne0, IC = w->ne1;
+    const kf::GamaPlan p = kf::gama_plan(OC, IC, n);
+    if (p.status != KF_OK || w->lGroup != kf::GAMA_GROUP || (long long)w->nGroup * kf::GAMA_GROUP != (long long)OC * IC)
+        return fail(KF_INVALID_ARGS, "kf_gama_backward: needs groups of 128, IC a multiple of 128, OC and n multiples of 64, OC >= 128 (got %d x %d, n %d, group %d)", OC, IC, n, w->lGroup);
+    if (!al16(deltaIn) || !al16(inp) || !al16(gGama) || ((uintptr_t)scratch & 255))
+        return fail(KF_BLAS_UNALIGN, "kf_gama_backward: tensors must be 16-byte aligned, scratch 256-byte aligned");
+    r = kf::gama_backward_launch(c->stream, p, (const unsigned char*)w->data, fmt, w->qBias, OC, IC, deltaIn, inp, n, gGama, scale, (float*)scratch);
+    RET(r);
 }
 size_t kf_attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return kf::attn_backward_scratch_bytes(T, n_head, n_seq); }
 int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,

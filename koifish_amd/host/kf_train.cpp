@@ -10,6 +10,13 @@
 // ln2.b;  then wte, wpe, lnf.w, lnf.b.   The AdamW seed of tensor i at optimizer step t is seed + 7919 t + i (one seed per launch, as the reference draws one per
 // tensor update).
 //
+// What is trained of a quantised matrix is a choice per tensor.  kfh_gpt2_set_param registers the SHADOW-WEIGHT form: a bf16 master, its [OC, IC] gradient and moments, the
+// blob re-quantised after every update.  kfh_gpt2_set_param_gama registers the reference's "train_target": "gama" (SLP::Back with w->gama_param, NeuronFuse.cu:538-549;
+// GTensor::InitGamaParam, GTensor.cpp:903-945; PIPE_Adamw on the slice, Optimizer.cu:646-662): the packed integers stay frozen, the parameter is the blob's own
+// [ZERO nGroup][STEP nGroup] slice, its gradient and moments are 2 nGroup long, LinBack is kf_linear_backward(gW = NULL) + kf_gama_backward(scale 1: the chain rule's value,
+// not the reference's 1 / nSample), the update is the same kf_adamw launch on the slice -- no weight decay (a decayed step shrinks every weight of its group), no
+// re-quantisation, never Muon.  Resident dequantised copies (kf_set_dequant_arena) would go stale with every update: a trainer with a gama tensor refuses a context that has an arena.
+//
 // The optimiser is a switch (kfh_gpt2_set_optimizer): AdamW on everything (the default), or the reference's default "muon" (OPT_Muon, Optimizer.cpp:1014-1056;
 // PIPE_Muon::Update, Pipe.cpp:16-57): MUON_params_::isAdamW restated -- a block's weight matrix with ne0 >= ne1 goes through kf_muon, everything else keeps kf_adamw.
 #include <cmath>
@@ -26,6 +33,7 @@ struct TrainTensor {
     void *m = nullptr, *v = nullptr;
     long long n = 0;
     bool decay = false, has_blob = false, requant = false;
+    bool gama = false;  // p is the blob's [ZERO][STEP] slice (n = 2 nGroup): kfh_gpt2_set_param_gama
     kf_weight blob;  // what the forward multiplies (f8e5m2 / 4-bit PackedQ / the bf16 master itself for the tied head)
 };
 
@@ -51,6 +59,8 @@ struct GPT2Trainer {
     float lr_scale = 1.0f, mui = 0.95f, eps_muon = 1e-7f;
     void* sc_muon = nullptr;
     size_t sc_muon_bytes = 0;
+    void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (kfh_gpt2_set_gama_scratch)
+    size_t sc_gama_bytes = 0;
 
     enum { QKV_W = 0, QKV_B, PROJ_W, PROJ_B, FC_W, FC_B, PROJ2_W, PROJ2_B, LN1_W, LN1_B, LN2_W, LN2_B, PER_BLOCK };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_BLOCK + k]; }
@@ -65,7 +75,7 @@ struct GPT2Trainer {
         if (method != OPT_MUON || i >= (size_t)NL * PER_BLOCK) return false;
         const int k = (int)(i % PER_BLOCK);
         const TrainTensor& e = params[i];
-        return (k == QKV_W || k == PROJ_W || k == FC_W || k == PROJ2_W) && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
+        return (k == QKV_W || k == PROJ_W || k == FC_W || k == PROJ2_W) && !e.gama && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
     }
     int SetOptimizer(int method_, float lr_scale_, float mui_, float eps_muon_, int tp_decay_, void* scratch, size_t scratch_bytes) {
         if (method_ != OPT_ADAMW && method_ != OPT_MUON) return KF_INVALID_ARGS;
@@ -96,6 +106,14 @@ struct GPT2Trainer {
         for (int l = 0; l < NL; l++)
             for (int k : {QKV_W, PROJ_W, FC_W, PROJ2_W})
                 if (!params[(size_t)l * PER_BLOCK + k].has_blob) return KF_INVALID_ARGS;
+        bool any_gama = false;
+        for (const TrainTensor& e : params)
+            if (e.gama) {
+                const size_t b = kf_gama_backward_scratch_bytes(e.blob.ne0, e.blob.ne1, N);
+                if (b == 0 || !sc_gama || sc_gama_bytes < b) return KF_INVALID_ARGS; /* a shape the entry refuses, or no / too small a scratch */
+                any_gama = true;
+            }
+        if (any_gama && kf_dequant_arena_bytes(ctx) > 0) return KF_INVALID_ARGS; /* resident dequantised copies would go stale with the first update */
         return params[(size_t)NL * PER_BLOCK].has_blob ? KF_OK : KF_INVALID_ARGS;
     }
     // SLP::Forw (NeuronFuse.cu:305-381): y = x . W^T + b (+ residual)
@@ -105,6 +123,10 @@ struct GPT2Trainer {
     int LN(const kf_bf16* x, TrainTensor& w, TrainTensor& b, kf_bf16* y, float* mean, float* rstd) { return kf_layernorm(ctx, x, w.p, b.p, y, N, C, 1e-5f, mean, rstd); }
     // SLP::Back (NeuronFuse.cu:495-563): weight / bias gradients into the tensors' own buffers, delta to the layer below
     int LinBack(TrainTensor& w, const kf_bf16* dIn, const kf_bf16* inp, kf_bf16* delta, TrainTensor* bias) {
+        if (w.gama) { /* the gama branch of SLP::Back: delta and the bias gradient as ever, no gW; then the (zero, step) gradients from the same two operands */
+            KF_TRY(kf_linear_backward(ctx, &w.blob, dIn, inp, delta, nullptr, bias ? bias->g : nullptr, N, 0, sc_lin));
+            return kf_gama_backward(ctx, &w.blob, dIn, inp, w.g, N, 1.0f, sc_gama);
+        }
         return kf_linear_backward(ctx, &w.blob, dIn, inp, delta, w.g, bias ? bias->g : nullptr, N, 0, sc_lin);
     }
     // kf_norm_backward ADDS into dweight / dbias: the per-tensor gradients are zero here (kf_adamw zeroes what it consumed)
@@ -201,8 +223,30 @@ int kfh_gpt2_set_param(void* h, int index, void* p, void* g, void* m, void* v, l
     GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
     if (index < 0 || index >= (int)t->params.size() || !p || !g || !m || !v || n < 8 || (n & 7)) return KF_INVALID_ARGS;
     koifish::TrainTensor& e = t->params[index];
-    e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant;
+    e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false;
     if (blob) e.blob = *blob;
+    return KF_OK;
+}
+// "train_target": "gama" for one of a block's four weight matrices (index as kfh_gpt2_set_param): blob a PackedQ group storage; the parameter is ITS [ZERO nGroup][STEP nGroup]
+// slice (gama + ne0 + ne1), g / m / v are 2 nGroup bf16 each.  No weight decay, no re-quantisation, AdamW whatever the optimiser switch says.
+int kfh_gpt2_set_param_gama(void* h, int index, void* g, void* m, void* v, const kf_weight* blob) {
+    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
+    if (index < 0 || index >= t->NL * GPT2Trainer::PER_BLOCK || !g || !m || !v || !blob) return KF_INVALID_ARGS;
+    const int k = index % GPT2Trainer::PER_BLOCK;
+    if (k != GPT2Trainer::QKV_W && k != GPT2Trainer::PROJ_W && k != GPT2Trainer::FC_W && k != GPT2Trainer::PROJ2_W) return KF_INVALID_ARGS;
+    if (!blob->gama || blob->qzeros || blob->qscales || blob->quant != KF_QUANT_GROUP || (blob->type != KF_Q4 && blob->type != KF_T_SIGN && blob->type != KF_BOOL1)) return KF_UNSUPPORTED_DATATYPE;
+    if (blob->nGroup < 4 || (blob->nGroup & 3) || (long long)blob->nGroup * blob->lGroup != (long long)blob->ne0 * blob->ne1) return KF_INVALID_ARGS;
+    koifish::TrainTensor& e = t->params[index];
+    e.blob = *blob;
+    e.p = const_cast<kf_bf16*>(blob->gama) + blob->ne0 + blob->ne1, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = 2LL * blob->nGroup;
+    e.decay = false, e.has_blob = true, e.requant = false, e.gama = true;
+    return KF_OK;
+}
+// kf_gama_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_gama_backward_scratch_bytes of every gama tensor at the step's B * T rows
+int kfh_gpt2_set_gama_scratch(void* h, void* scratch, size_t bytes) {
+    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
+    if (!scratch || ((uintptr_t)scratch & 255)) return KF_INVALID_ARGS;
+    t->sc_gama = scratch, t->sc_gama_bytes = bytes;
     return KF_OK;
 }
 // ptrs: x h1 m1 r1 qkv att x2 h2 m2 r2 f g

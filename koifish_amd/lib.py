@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
     "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
+    "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
 ]
 
 
@@ -90,6 +91,8 @@ def load():
         hip.kf_embed_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         hip.kf_linear_backward.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]
         hip.kf_linear_backward_scratch_bytes.argtypes, hip.kf_linear_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
+        hip.kf_gama_backward.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+        hip.kf_gama_backward_scratch_bytes.argtypes, hip.kf_gama_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_norm_backward.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p]
         hip.kf_norm_backward_scratch_bytes.argtypes, hip.kf_norm_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_rope_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]
@@ -196,6 +199,7 @@ def load():
         hip.kf_set_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         hip.kf_set_dequant_arena.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         hip.kf_dequant_arena_used.argtypes, hip.kf_dequant_arena_used.restype = [C.c_void_p], C.c_size_t
+        hip.kf_dequant_arena_bytes.argtypes, hip.kf_dequant_arena_bytes.restype = [C.c_void_p], C.c_size_t
         hip.kf_resident_scratch_bytes.argtypes, hip.kf_resident_scratch_bytes.restype = [], C.c_size_t
         host.kfh_set_prefill_resident.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
         host.kfh_weights_changed.argtypes = [C.c_void_p]
@@ -217,6 +221,8 @@ def load():
         host.kfh_gpt2_destroy.argtypes = [C.c_void_p]
         host.kfh_gpt2_n_params.argtypes = [C.c_void_p]
         host.kfh_gpt2_set_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int]
+        host.kfh_gpt2_set_param_gama.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        host.kfh_gpt2_set_gama_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         host.kfh_gpt2_set_block_acts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         host.kfh_gpt2_set_buffers.argtypes = [C.c_void_p, C.c_void_p]
         host.kfh_gpt2_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

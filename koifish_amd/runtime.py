@@ -74,6 +74,16 @@ class DevWeight:
         return g[z0:z0 + self.nGroup], g[z0 + self.nGroup:z0 + 2 * self.nGroup]
 
 
+    def gama_slice(self):
+        """the blob's [ZERO nGroup][STEP nGroup] region as a bf16 view, 2 nGroup long (element offset ne0 + ne1 of gama): the parameter of "train_target": "gama"
+        (GTensor::InitGamaParam) -- what kf_adamw is pointed at, in place inside the blob"""
+        if not self.quantised:
+            raise L.KFError("gama_slice: type %d has no (zero, step) groups" % self.type)
+        g = self.blob[self.szData:].view(torch.bfloat16)
+        z0 = self.ne0 + self.ne1
+        return g[z0:z0 + 2 * self.nGroup]
+
+
 class LutDevWeight:
     """Row-codebook weight in HBM (KF_QUANT_ROW_LUT; GeQuant::RT_NormalF): blob = MSB-first `bits`-wide stream [ne0*ne1*bits/8] ‖ bf16 gama
     [ne0 + ne1 + (2^bits)*ne0]; bits 4 (the mat-vec format), 3 or 2 (dequant-only); rtn=True (bits 2): (zero, step) per row, KF_QUANT_ROW_RTN."""
@@ -243,6 +253,21 @@ class Context:
         epi = L.KF_EPI_RESIDUAL if residual is not None else 0
         L.check(self.hip.kf_linear(self.h, C.byref(d), _ptr(x), _ptr(y), _ptr(bias), 1, alpha, beta, epi, _ptr(residual)), "kf_linear")
         return y
+
+    def gama_backward(self, w, dIn, inp, g, scale=1.0):
+        """kf_gama_backward: g [2 nGroup] bf16 (zero gradients, then step gradients) += scale x the (zero, step) gradients of the group-quantised w [OC, IC] from
+        dIn [n, OC] and inp [n, IC].  Owns the scratch (kernels never allocate) and sizes it with kf_gama_backward_scratch_bytes: the entry itself is not told the size."""
+        n = dIn.shape[0]
+        need = self.hip.kf_gama_backward_scratch_bytes(w.ne0, w.ne1, n)
+        if dIn.shape != (n, w.ne0) or inp.shape != (n, w.ne1) or g.numel() != 2 * w.nGroup:
+            raise L.KFError("gama_backward: dIn %s, inp %s, g %d for a [%d, %d] weight of %d groups" % (tuple(dIn.shape), tuple(inp.shape), g.numel(), w.ne0, w.ne1, w.nGroup))
+        ws = getattr(self, "_gama_ws", None)
+        if ws is None or ws.numel() < need + 256:
+            self.sync()   # earlier launches may still read the old buffer
+            ws = self._gama_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        d = w.desc()
+        L.check(self.hip.kf_gama_backward(self.h, C.byref(d), _ptr(dIn), _ptr(inp), _ptr(g), n, scale, C.c_void_p((ws.data_ptr() + 255) & ~255)), "kf_gama_backward")
+        return g
 
     def act_quant_i8(self, x, norm_w=None, eps=1e-6):
         """kf_act_quant_i8: x bf16 [dim] or [rows, dim] (a row stride larger than dim is honoured) -> (q int8 of x's shape, step fp32 [rows]); with norm_w the rows are

@@ -7,6 +7,10 @@
   update   CU_adamw_ (Optimizer.cu:135-160: seeded stochastic rounding) on the model's OWN bf16 master weights and bf16 moments
   requant  CU_XtoQ128_ / Float2T<f8e5> (T.cu:105-175) of every updated matrix back into its blob, which the next forward reads
 
+train_target="gama" is the reference's other way to train a quantised layer ("train_target": "gama"; SLP::Back's gama branch, GTensor::InitGamaParam): a block matrix stored
+as a PackedQ group type keeps its packed integers frozen and trains each group's (zero, step) pair in place inside the blob -- no bf16 master, no [OC, IC] gradient, no
+moments of that size, no re-quantisation: per 128 weights two bf16 parameters, two gradients, four moments (kf_gama_backward + kf_adamw on the blob's gama slice).
+
 The step keeps every activation (no recomputation).  Python here OWNS the device buffers (torch tensors: setup, outside any timed region) and registers them with
 koifish::GPT2Trainer (koifish_amd/host/kf_train.cpp, libkf_host.so), which sequences the step: forward / backward / update are one C call each, step() is ONE call,
 and nothing in them is a torch op (the embedding gather + add is kf_embed_pos, the attention reads q out of the fused rows, the zero fills are kf_memset / kf_memset2d).
@@ -18,12 +22,20 @@ import torch
 from . import lib as L
 
 MATS = ("qkv", "proj", "fc", "proj2")
+GAMA_TYPES = (L.Q4, L.T_SIGN, L.BOOL1)   # the PackedQ group storages kf_gama_backward serves
 
 
 class GPT2Step:
-    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None):
+    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None, train_target="weights"):
         """masters: optional dict of host-provided bf16 torch tensors (tests hand the same numbers to the reference): 'wte' [Vp, C], 'wpe' [T, C], 'lnf' (w, b), 'blocks':
-        list of dicts {mat: (W [out, in], b [out])} + 'ln' (w1, b1, w2, b2).  Otherwise N(0, w_std) draws on the device."""
+        list of dicts {mat: (W [out, in], b [out])} + 'ln' (w1, b1, w2, b2).  Otherwise N(0, w_std) draws on the device.
+        train_target: "weights" (the default: bf16 masters, re-quantised after every update) or "gama": every block matrix whose storage is a PackedQ group type (GAMA_TYPES)
+        is quantised once from its initial draw, which is then dropped; its entry of self.params has p = the blob's [ZERO][STEP] slice and g, m, v of 2 nGroup elements, no
+        weight decay.  f8e5m2 / bf16 matrices, biases, norms and embeddings train as under "weights".  Refused with a reason: a matrix kf_gama_backward does not take
+        (in-features no multiple of 128), and a context that holds a dequant arena (kf_set_dequant_arena: its resident copies would go stale with every update)."""
+        if train_target not in ("weights", "gama"):
+            raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
+        self.train_target = train_target
         self.ctx, self.C, self.H, self.NL, self.V, self.Vp, self.B, self.T = ctx, C_, H, NL, V, Vp, B, T
         self.hd, self.N = C_ // H, B * T
         self.types = dict(qkv=L.F8E5M2, proj=L.F8E5M2, fc=L.Q4, proj2=L.Q4) if types is None else dict(types)
@@ -44,13 +56,23 @@ class GPT2Step:
                     e["p"] = e["blob"].blob.view(bf).view(p.shape)   # a bf16 "blob" IS the master (the tied head): updated in place, nothing to re-quantise
             self.params.append(e)
             return e
+
+        def reg_gama(name, W, type_):
+            blob = ctx.quantize(W.contiguous(), type_)   # the draw is dropped: the packed integers are the weight from here on
+            p = blob.gama_slice()
+            e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=False, blob=blob, type=type_, gama=True)
+            self.params.append(e)
+            return e
         for l in range(NL):
             mb = masters["blocks"][l] if masters else None
             blk = {}
             for k in MATS:
                 W = mb[k][0].to(dev) if mb else rnd(*shapes[k])
                 b = mb[k][1].to(dev) if mb else z(shapes[k][0])
-                blk[k] = reg("h%d.%s.w" % (l, k), W, True, self.types[k])
+                if train_target == "gama" and self.types[k] in GAMA_TYPES:
+                    blk[k] = reg_gama("h%d.%s.w" % (l, k), W, self.types[k])
+                else:
+                    blk[k] = reg("h%d.%s.w" % (l, k), W, True, self.types[k])
                 blk[k + "_b"] = reg("h%d.%s.b" % (l, k), b, False)
             ln = [t.to(dev) for t in mb["ln"]] if mb else [torch.ones(C_, device=dev, dtype=bf), z(C_), torch.ones(C_, device=dev, dtype=bf), z(C_)]
             for i, nm in enumerate(("ln1.w", "ln1.b", "ln2.w", "ln2.b")):
@@ -83,8 +105,21 @@ class GPT2Step:
         if not self.h:
             raise RuntimeError("kfh_gpt2_create refused the shape")
         assert host.kfh_gpt2_n_params(self.h) == len(self.params)
+        gama = [e for e in self.params if e.get("gama")]
+        if gama:
+            self._check_arena()
+            need = [hip.kf_gama_backward_scratch_bytes(e["blob"].ne0, e["blob"].ne1, N) for e in gama]
+            if not all(need):
+                bad = gama[need.index(0)]
+                raise L.KFError("train_target='gama': kf_gama_backward does not take %s [%d, %d] at %d rows (in-features a multiple of 128, out-features and rows multiples of 64)"
+                                % (bad["name"], bad["blob"].ne0, bad["blob"].ne1, N))
+            self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=dev)
+            L.check(host.kfh_gpt2_set_gama_scratch(self.h, (self._sc_gama.data_ptr() + 255) & ~255, max(need)), "kfh_gpt2_set_gama_scratch")
         for i, e in enumerate(self.params):
             d = e["blob"].desc() if e["blob"] is not None else None
+            if e.get("gama"):
+                L.check(host.kfh_gpt2_set_param_gama(self.h, i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d)), "kfh_gpt2_set_param_gama")
+                continue
             L.check(host.kfh_gpt2_set_param(self.h, i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["p"].numel(), int(e["wd"]),
                                             C.byref(d) if d is not None else None, int(e["type"] is not None and e["type"] != L.BF16)), "kfh_gpt2_set_param")
         for l, a in enumerate(self.A):
@@ -94,16 +129,24 @@ class GPT2Step:
                                   + [self._sp_lin, self._sc_ln.data_ptr(), self._sc_at.data_ptr()]))
         L.check(host.kfh_gpt2_set_buffers(self.h, arr), "kfh_gpt2_set_buffers")
 
+    def _check_arena(self):
+        """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
+        if self.train_target == "gama" and self.ctx.hip.kf_dequant_arena_bytes(self.ctx.h):
+            raise L.KFError("train_target='gama' on a context with a dequant arena (kf_set_dequant_arena): the resident bf16 copies of the trained matrices would go stale "
+                            "with every update -- switch the arena off (kf_set_dequant_arena(ctx, NULL, 0)) for training")
+
     def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
         """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a block's weight matrices with ne0 >= ne1 (qkv, proj, fc) take SGD-momentum +
         five Newton-Schulz steps (kf_muon: lr x lr_scale, weight decay by tp_decay as Pipe.cpp:23-37, mG = the tensor's m buffer); proj2, the embeddings, biases and norms
-        keep kf_adamw.  Owns the scratch, sized for the largest Muon tensor."""
+        keep kf_adamw -- and so does every gama-trained tensor (train_target="gama"): its parameter is a [2 nGroup] slice, never a matrix for kf_muon.  Owns the scratch,
+        sized for the largest Muon tensor."""
         if method not in ("adamw", "muon"):
             raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
         sp, nb = None, 0
         if method == "muon":
-            shapes = [tuple(e["p"].shape) for e in self.params if e["blob"] is not None and e["name"].startswith("h") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
-            nb = max(self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes)
+            shapes = [tuple(e["p"].shape) for e in self.params
+                      if e["blob"] is not None and not e.get("gama") and e["name"].startswith("h") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
+            nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
             if nb == 0:
                 raise L.KFError("muon: a hidden matrix has a dimension that is no multiple of 64")
             self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
@@ -127,6 +170,7 @@ class GPT2Step:
     def forward(self, ids, tgt):
         """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
         self._ids = ids   # kept alive: the backward reads them
+        self._check_arena()
         L.check(self.ctx.host.kfh_gpt2_forward(self.h, ids.data_ptr(), tgt.data_ptr()), "kfh_gpt2_forward")
 
     def backward(self):
@@ -140,6 +184,7 @@ class GPT2Step:
     def step(self, ids, tgt, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
         """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
         self._ids = ids
+        self._check_arena()
         L.check(self.ctx.host.kfh_gpt2_step(self.h, ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_gpt2_step")
 
     def n_params(self):
