@@ -455,6 +455,28 @@ int kf_muon_apply(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, const kf_bf16* X
 int kf_muon(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, kf_bf16* mG, int ne0, int ne1, float lr, float weight_decay, float mui, float eps_muon, int n_iter,
             uint32_t seed, void* scratch, size_t scratch_bytes, double* d_wnormsq_or_null);
 
+/* ---- EOE, "Evolutionary Optimization of Experts": Fuyou::Exploitation (src/Device/CUDA/Optimizer.cu:439-484) of ONE follower matrix towards the head's, one pass.
+ * x [ne0, ne1] bf16: the follower's master, updated in place; head [ne0, ne1] bf16: read only.  n = ne0 ne1.  The algorithms carry the values of the three live
+ * members of Fuyou_params::ALGORITHM (CLI_params.hpp:194-204; GENE_MUTATION is commented out in the reference and not built).
+ * The draw is this project's own (the reference's per-row curand XORWOW streams cannot be restated): counter-based, one hash per element, for flat row-major index i
+ *     h = SquirrelNoise5(i, seed) (the noise of kf_adamw);  b0 .. b3 = the bytes of h, low to high;  r = float(b0 + b1 + b2) * (1.0f / 765.0f)
+ * r stands for the reference's clip((N(0,1) + 3) / 6, 0, 1]: support [0, 1], mean 0.5, standard deviation 0.1673 (there: 1/6).  r == 0 leaves x[i] as it is.
+ *   KF_EVO_PSO     (CU_PSO_2D)   xf = f32(x[i]), gf = f32(head[i]);  t = social * r;  d = gf - xf;  x[i] = bf16(xf + t * d) -- every operation rounded on its own, no
+ *                                fma.  The reference passes alpha to CU_PSO_2D and never reads it: alpha is ignored here.
+ *   KF_EVO_PSO_GA  (+ CU_crossover_, the same pass)  the PSO value, then where b3 < thr the 16 bits of head[i] verbatim;  thr = clamp(floor(t_cross * 256 + 0.5), 0, 256),
+ *                                computed on the host (t_cross = 0: exactly KF_EVO_PSO; t_cross = 1: x == head bit for bit).
+ *   KF_EVO_MIX     (CU_mix_)     x[i] = bf16(alpha * xf + beta * gf),  beta = (float)(1.0 - (double)alpha): two rounded products, one add.  No draw.
+ * Stores round to nearest even (the reference's (T) cast), not the optimiser's stochastic store.  The bits do not depend on the launch geometry.
+ * Refusals are KF_INVALID_ARGS, launch nothing, and kf_last_error says which: a null pointer; x == head or overlapping ranges; ne0 or ne1 < 1, n < 8, n % 8 != 0 or
+ * n >= 2^32; a pointer that is not 16-byte aligned; an unknown algorithm; social, alpha or t_cross not finite. */
+enum kf_evo_algorithm { KF_EVO_PSO = 1, KF_EVO_MIX = 2, KF_EVO_PSO_GA = 4 };
+int kf_evolve(kf_ctx* ctx, kf_bf16* x, const kf_bf16* head, int ne0, int ne1, int algorithm, float alpha, float social, float t_cross, uint32_t seed);
+/* The ensemble mean of per-row losses (Fish::ForwardOnRLS, gLLM.cpp:722-787: tmpLoss[i] / curB), one member at a time -- the trainer's one losses buffer is
+ * overwritten by the next member's forward:  index 0: acc[i] = losses[i];  0 < index: acc[i] = acc[i] + losses[i];  and at index == count - 1 also acc[i] = acc[i] / count.
+ * fp32, in index order; acc and losses fp32 [n] on the device, acc != losses.  KF_INVALID_ARGS: a null pointer, acc == losses, n = 0 or n >= 2^31, count < 1, index
+ * outside [0, count). */
+int kf_loss_mean(kf_ctx* ctx, float* acc, const float* losses, size_t n, int index, int count);
+
 /* ---- token batch (prompt prefill).  The reference feeds the prompt one token at a time through the decode path (Fish::Chat,
  * GoPT.cpp:1139-1146); its batched forward exists only on the training side (SelfAttention::cuFlow / ROPE::cuFlow,
  * NeuronFuse.cu:692-731, rope.cu).  These entries run the same per-token arithmetic for n_tok consecutive positions at once;

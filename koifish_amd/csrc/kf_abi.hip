@@ -1252,6 +1252,30 @@ int kf_muon(kf_ctx* c, kf_bf16* params, kf_bf16* grads, kf_bf16* mG, int ne0, in
     RET(kf::muon_apply_launch(c->stream, params, grads, X, n, lr, weight_decay, seed, part, d_wnormsq ? d_wnormsq : dbl + 1));
 }
 
+// ---- EOE (Fuyou::Exploitation, Optimizer.cu:439-484): kf_evo.hip
+int kf_evolve(kf_ctx* c, kf_bf16* x, const kf_bf16* head, int ne0, int ne1, int algorithm, float alpha, float social, float t_cross, uint32_t seed) {
+    CHKCTX(c);
+    if (!x || !head) return fail(KF_INVALID_ARGS, "kf_evolve: null pointer");
+    if (ne0 < 1 || ne1 < 1) return fail(KF_INVALID_ARGS, "kf_evolve: shape %d x %d", ne0, ne1);
+    const unsigned long long n = (unsigned long long)ne0 * (unsigned long long)ne1;
+    if (n < 8 || n % 8 || n >= (1ull << 32)) return fail(KF_INVALID_ARGS, "kf_evolve: n = %llu is not a multiple of 8 in [8, 2^32)", n);
+    const uintptr_t xa = (uintptr_t)x, ha = (uintptr_t)head;
+    if (xa < ha + 2 * n && ha < xa + 2 * n) return fail(KF_INVALID_ARGS, "kf_evolve: x and head %s", xa == ha ? "are the same tensor" : "overlap");
+    if (!al16(x) || !al16(head)) return fail(KF_INVALID_ARGS, "kf_evolve: tensors must be 16-byte aligned");
+    if (algorithm != KF_EVO_PSO && algorithm != KF_EVO_PSO_GA && algorithm != KF_EVO_MIX)
+        return fail(KF_INVALID_ARGS, "kf_evolve: unknown algorithm %d (KF_EVO_PSO = 1, KF_EVO_MIX = 2, KF_EVO_PSO_GA = 4)", algorithm);
+    if (!isfinite(social) || !isfinite(alpha) || !isfinite(t_cross)) return fail(KF_INVALID_ARGS, "kf_evolve: social, alpha or t_cross is not finite");
+    const double th = floor((double)t_cross * 256.0 + 0.5);
+    const unsigned thr = th < 0.0 ? 0u : (th > 256.0 ? 256u : (unsigned)th);
+    RET(kf::evolve_launch(c->stream, x, head, (size_t)n, algorithm, alpha, (float)(1.0 - (double)alpha), social, thr, seed));
+}
+int kf_loss_mean(kf_ctx* c, float* acc, const float* losses, size_t n, int index, int count) {
+    CHKCTX(c);
+    if (!acc || !losses || acc == losses) return fail(KF_INVALID_ARGS, "kf_loss_mean: acc / losses null or the same buffer");
+    if (n == 0 || n >= ((size_t)1 << 31) || count < 1 || index < 0 || index >= count) return fail(KF_INVALID_ARGS, "kf_loss_mean: n = %zu, index %d of %d", n, index, count);
+    RET(kf::loss_mean_launch(c->stream, acc, losses, n, index, count));
+}
+
 // ---- persistent decode engine
 struct kf_engine {
     kf::EngineHost* h;

@@ -217,6 +217,9 @@ MuonLayout muon_layout(int ne0, int ne1);
 int muon_momentum_launch(hipStream_t st, uint16_t* mG, const uint16_t* grads, uint16_t* X, size_t n, float mui, unsigned int seed, double* partials, double* d_sumsq);
 int muon_apply_launch(hipStream_t st, uint16_t* params, uint16_t* grads, const uint16_t* X, size_t n, float lr, float wd, unsigned int seed, double* partials, double* d_wnormsq);
 int newton_schulz_launch(hipStream_t st, uint16_t* X, int ne0, int ne1, const double* d_sumsq, float eps, int n_iter, float a, float b, float c, void* scratch);
+// ---- EOE (kf_evo.hip): Fuyou::Exploitation over one follower matrix (thr: the crossover threshold out of 256, beta = 1 - alpha), and the ensemble mean of losses
+int evolve_launch(hipStream_t st, uint16_t* x, const uint16_t* head, size_t n, int algorithm, float alpha, float beta, float social, unsigned int thr, unsigned int seed);
+int loss_mean_launch(hipStream_t st, float* acc, const float* losses, size_t n, int index, int count);
 int sample_launch(hipStream_t st, const uint16_t* logits, int n, int top_k, float temperature, float top_p, unsigned long long* rng, int32_t* d_token,
                   int32_t* d_state, int32_t* d_tokens_out, const int32_t* d_forced, int n_forced, int true_topk = 0);
 int quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src, int symmetric);

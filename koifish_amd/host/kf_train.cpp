@@ -19,14 +19,25 @@
 //
 // The optimiser is a switch (kfh_gpt2_set_optimizer): AdamW on everything (the default), or the reference's default "muon" (OPT_Muon, Optimizer.cpp:1014-1056;
 // PIPE_Muon::Update, Pipe.cpp:16-57): MUON_params_::isAdamW restated -- a block's weight matrix with ne0 >= ne1 goes through kf_muon, everything else keeps kf_adamw.
+//
+// EOE, "Evolutionary Optimization of Experts" (kfh_gpt2_set_branches / _set_active_branch / _evolve / _eval): the NL layers are cut into NL / layers_in_branch sections
+// (RLSchedule::InitBranch / UpdateBackbone, Scheduler.cpp:522-656); a section together with the shared embedding, final norm and head is a shallow model of its own, a
+// "Fuyou".  Forward / Backward / Update walk the ACTIVE section only: the 0 .. NL loops are l0 .. l1, the embedding writes acts[l0].x, Update leaves every tensor of
+// another section alone (no momentum, no weight decay; its seed index is skipped, not renumbered).  Evolve is Fuyou::UpdateFollower over the swarm
+// (ExploreOptimization, Scheduler.cpp:430-486): the head branch pulls the four weight matrices (isWMAT) of every layer of every other branch towards its own with
+// kf_evolve, and every follower blob is re-quantised.  Eval is the evaluation half of Fish::ForwardOnRLS (gLLM.cpp:722-787): one branch, or the mean over all of
+// them.  Which branch trains when, and which one is the head, is the caller's loop.  One branch (the default) is the code above, bit for bit.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "kf_host.hpp"
 
 namespace koifish {
+
+static thread_local std::string g_train_err;  // why the last kfh_gpt2_evolve / _set_branches / _set_active_branch / _eval refused (kfh_gpt2_last_error)
 
 struct TrainTensor {
     kf_bf16 *p = nullptr, *g = nullptr;
@@ -61,6 +72,11 @@ struct GPT2Trainer {
     size_t sc_muon_bytes = 0;
     void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (kfh_gpt2_set_gama_scratch)
     size_t sc_gama_bytes = 0;
+    // EOE: sections of LIS layers; branch b owns layers [b LIS, (b + 1) LIS); [l0, l1) is the active one.  One branch (LIS = NL): the whole depth
+    int LIS = 0, branch = 0, l0 = 0, l1 = 0;
+    enum { ENSEMBLE_AGGREGATION = 0, ENSEMBLE_BRANCH = 1 };  // Fuyou_params::ENSEMBLE: AGGREGATION; FUYOU_BEST and RANDOM_1 are BRANCH with the caller's choice of branch
+    int NBranch() const { return NL / LIS; }
+    bool InSection(size_t i) const { return i >= (size_t)NL * PER_BLOCK || ((int)(i / PER_BLOCK) >= l0 && (int)(i / PER_BLOCK) < l1); }
 
     enum { QKV_W = 0, QKV_B, PROJ_W, PROJ_B, FC_W, FC_B, PROJ2_W, PROJ2_B, LN1_W, LN1_B, LN2_W, LN2_B, PER_BLOCK };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_BLOCK + k]; }
@@ -139,8 +155,8 @@ struct GPT2Trainer {
     int Forward(const int32_t* d_ids, const int32_t* d_tgt) {
         KF_TRY(Ready());
         if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
-        KF_TRY(kf_embed_pos(ctx, Wte().p, C, Wpe().p, d_ids, B, T, C, Vp, acts[0].x));
-        for (int l = 0; l < NL; l++) {
+        KF_TRY(kf_embed_pos(ctx, Wte().p, C, Wpe().p, d_ids, B, T, C, Vp, acts[l0].x));
+        for (int l = l0; l < l1; l++) {
             BlockActs& a = acts[l];
             KF_TRY(LN(a.x, P(l, LN1_W), P(l, LN1_B), a.h1, a.m1, a.r1));
             KF_TRY(Lin(P(l, QKV_W), a.h1, a.qkv, &P(l, QKV_B), nullptr));
@@ -149,7 +165,7 @@ struct GPT2Trainer {
             KF_TRY(LN(a.x2, P(l, LN2_W), P(l, LN2_B), a.h2, a.m2, a.r2));
             KF_TRY(Lin(P(l, FC_W), a.h2, a.f, &P(l, FC_B), nullptr));
             KF_TRY(kf_gelu(ctx, a.f, a.g, (size_t)N * 4 * C));
-            KF_TRY(Lin(P(l, PROJ2_W), a.g, l + 1 < NL ? acts[l + 1].x : xf, &P(l, PROJ2_B), a.x2));
+            KF_TRY(Lin(P(l, PROJ2_W), a.g, l + 1 < l1 ? acts[l + 1].x : xf, &P(l, PROJ2_B), a.x2));
         }
         KF_TRY(LN(xf, LnfW(), LnfB(), hf, mf, rf));
         KF_TRY(Lin(Wte(), hf, logits, nullptr, nullptr));
@@ -165,7 +181,7 @@ struct GPT2Trainer {
         KF_TRY(LinBack(Wte(), logits, hf, dh, nullptr));
         KF_TRY(kf_memset(ctx, dx, 0, (size_t)N * C * 2));
         KF_TRY(LNBack(dx, dh, xf, LnfW(), LnfB(), mf, rf));
-        for (int l = NL - 1; l >= 0; l--) {
+        for (int l = l1 - 1; l >= l0; l--) {
             BlockActs& a = acts[l];
             KF_TRY(LinBack(P(l, PROJ2_W), dx, a.g, d4, &P(l, PROJ2_B)));
             KF_TRY(kf_gelu_backward(ctx, d4, a.f, (size_t)N * 4 * C));
@@ -186,6 +202,7 @@ struct GPT2Trainer {
         t++;
         const float b1c = (float)(1.0 - std::pow(beta1, (double)t)), b2c = (float)(1.0 - std::pow(beta2, (double)t)); /* the bias corrections, in double like the host side of the reference */
         for (size_t i = 0; i < params.size(); i++) {
+            if (!InSection(i)) continue; /* a tensor of another branch: not touched, its seed index skipped */
             TrainTensor& e = params[i];
             const uint32_t sd = (uint32_t)((seed + 7919ull * (unsigned long long)t + i) & 0xFFFFFFFFull);
             if (IsMuon(i)) {
@@ -200,6 +217,87 @@ struct GPT2Trainer {
         }
         return KF_OK;
     }
+
+    int SetBranches(int layers_in_branch) {
+        if (layers_in_branch == 0) layers_in_branch = NL;
+        if (layers_in_branch < 0 || layers_in_branch > NL || NL % layers_in_branch) {
+            g_train_err = "kfh_gpt2_set_branches: " + std::to_string(NL) + " layers do not divide into sections of " + std::to_string(layers_in_branch);
+            return KF_INVALID_ARGS;
+        }
+        LIS = layers_in_branch;
+        return SetActive(0);
+    }
+    int SetActive(int b) {
+        if (b < 0 || b >= NBranch()) {
+            g_train_err = "kfh_gpt2_set_active_branch: branch " + std::to_string(b) + " of " + std::to_string(NBranch());
+            return KF_INVALID_ARGS;
+        }
+        branch = b, l0 = b * LIS, l1 = l0 + LIS;
+        ids = nullptr; /* the kept activations belong to the branch that ran: a Backward needs a Forward of this one first */
+        return KF_OK;
+    }
+    // Fuyou::UpdateFollower for every follower of `head` (RLSchedule::ExploreOptimization): launches only -- no allocation, no host sync
+    int Evolve(int head, int algorithm, float alpha, float social, float t_cross, uint32_t seed) {
+        KF_TRY(Ready());
+        if (head < 0 || head >= NBranch()) {
+            g_train_err = "kfh_gpt2_evolve: head branch " + std::to_string(head) + " of " + std::to_string(NBranch());
+            return KF_INVALID_ARGS;
+        }
+        if (algorithm != KF_EVO_PSO && algorithm != KF_EVO_PSO_GA && algorithm != KF_EVO_MIX) {
+            g_train_err = "kfh_gpt2_evolve: unknown algorithm " + std::to_string(algorithm);
+            return KF_INVALID_ARGS;
+        }
+        if (NBranch() == 1) return KF_OK; /* fuyouSwarm.size() <= 1: ExploreOptimization returns early */
+        for (int l = 0; l < NL; l++)
+            for (int k : {QKV_W, PROJ_W, FC_W, PROJ2_W})
+                if (P(l, k).gama) {
+                    g_train_err = "kfh_gpt2_evolve: layer " + std::to_string(l) + " matrix " + std::to_string(k) + " is gama-trained (train_target \"gama\"): its parameter is " +
+                                  "the blob's (zero, step) slice over frozen packed integers, not a matrix kf_evolve could move towards another branch's -- nothing was changed";
+                    return KF_UNSUPPORTED_DATATYPE;
+                }
+        for (int l = 0; l < NL; l++)
+            for (int k : {QKV_W, PROJ_W, FC_W, PROJ2_W}) {
+                const TrainTensor &e = P(l, k), &h = P(head * LIS + l % LIS, k);
+                if (!e.has_blob || (long long)e.blob.ne0 * e.blob.ne1 != e.n || e.n != h.n || e.blob.ne0 != h.blob.ne0) {
+                    g_train_err = "kfh_gpt2_evolve: layer " + std::to_string(l) + " matrix " + std::to_string(k) + " has no [ne0, ne1] master of its head's shape -- nothing was changed";
+                    return KF_INVALID_ARGS;
+                }
+            }
+        for (int f = 0; f < NBranch(); f++) {
+            if (f == head) continue;
+            for (int j = 0; j < LIS; j++)
+                for (int k : {QKV_W, PROJ_W, FC_W, PROJ2_W}) {
+                    const size_t i = (size_t)(f * LIS + j) * PER_BLOCK + k;
+                    TrainTensor& e = params[i];
+                    KF_TRY(kf_evolve(ctx, e.p, P(head * LIS + j, k).p, e.blob.ne0, e.blob.ne1, algorithm, alpha, social, t_cross, (uint32_t)((seed + (unsigned long long)i) & 0xFFFFFFFFull)));
+                    if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
+                }
+        }
+        return KF_OK;
+    }
+    // the evaluation half of Fish::ForwardOnRLS: per-row losses of one branch, or their mean over all branches (added in branch order in fp32, divided by nBranch), into the
+    // caller's fp32 [B T] device buffer; the active branch is put back.  The kept activations are those of the last branch run: a Backward needs a new Forward.
+    int Eval(const int32_t* d_ids, const int32_t* d_tgt, int mode, int b, float* d_out) {
+        KF_TRY(Ready());
+        if (!d_out || d_out == losses) return KF_INVALID_ARGS;
+        if (mode != ENSEMBLE_AGGREGATION && mode != ENSEMBLE_BRANCH) {
+            g_train_err = "kfh_gpt2_eval: unknown ensemble mode " + std::to_string(mode);
+            return KF_INVALID_ARGS;
+        }
+        if (mode == ENSEMBLE_BRANCH && (b < 0 || b >= NBranch())) {
+            g_train_err = "kfh_gpt2_eval: branch " + std::to_string(b) + " of " + std::to_string(NBranch());
+            return KF_INVALID_ARGS;
+        }
+        const int keep = branch, b0 = mode == ENSEMBLE_BRANCH ? b : 0, nb = mode == ENSEMBLE_BRANCH ? 1 : NBranch();
+        int rc = KF_OK;
+        for (int k = 0; k < nb && rc == KF_OK; k++) {
+            SetActive(b0 + k);
+            rc = Forward(d_ids, d_tgt);
+            if (rc == KF_OK) rc = kf_loss_mean(ctx, d_out, losses, (size_t)N, k, nb);
+        }
+        SetActive(keep);
+        return rc;
+    }
 };
 
 }  // namespace koifish
@@ -213,6 +311,7 @@ void* kfh_gpt2_create(kf_ctx* ctx, int C, int H, int NL, int V, int Vp, int B, i
     g->ctx = ctx, g->C = C, g->H = H, g->NL = NL, g->V = V, g->Vp = Vp, g->B = B, g->T = T, g->N = B * T, g->hd = C / H;
     g->params.resize((size_t)NL * GPT2Trainer::PER_BLOCK + 4);
     g->acts.resize(NL);
+    g->LIS = NL, g->l1 = NL;
     memset(g->acts.data(), 0, sizeof(koifish::BlockActs) * NL);
     return g;
 }
@@ -284,4 +383,30 @@ int kfh_gpt2_set_optimizer(void* h, int method, float lr_scale, float mui, float
     return reinterpret_cast<GPT2Trainer*>(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
 }
 long long kfh_gpt2_steps_taken(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->t; }
+// ---- EOE.  Every refusal leaves the trainer as it was; kfh_gpt2_last_error says why (a refusal of a kf_* entry underneath: kf_last_error).
+// layers_in_branch must divide NL (KF_INVALID_ARGS otherwise); 0 or NL: one branch, the whole depth -- the default.  Branch 0 becomes the active one.
+int kfh_gpt2_set_branches(void* h, int layers_in_branch) {
+    koifish::g_train_err.clear();
+    return reinterpret_cast<GPT2Trainer*>(h)->SetBranches(layers_in_branch);
+}
+int kfh_gpt2_n_branches(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->NBranch(); }
+// forward / backward / update / step from here on run embed -> the layers of branch b -> lnf -> tied head and touch the shared tensors and that section's only
+int kfh_gpt2_set_active_branch(void* h, int b) {
+    koifish::g_train_err.clear();
+    return reinterpret_cast<GPT2Trainer*>(h)->SetActive(b);
+}
+int kfh_gpt2_active_branch(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->branch; }
+// for every branch f != head_branch, every layer offset j, each of qkv.w proj.w fc.w proj2.w: kf_evolve(follower master, head master, ..., seed + the follower tensor's
+// index in the registered order), then kf_quantize of the follower's blob.  Biases and norms are not touched (isWMAT).  A gama-trained matrix in ANY section:
+// KF_UNSUPPORTED_DATATYPE before anything is launched.  One branch: KF_OK, nothing is done.  algorithm: enum kf_evo_algorithm.
+int kfh_gpt2_evolve(void* h, int head_branch, int algorithm, float alpha, float social, float t_cross, uint32_t seed) {
+    koifish::g_train_err.clear();
+    return reinterpret_cast<GPT2Trainer*>(h)->Evolve(head_branch, algorithm, alpha, social, t_cross, seed);
+}
+// mode 0 (AGGREGATION): every branch forward in index order, d_loss_out = their mean; mode 1 (BRANCH): the given branch alone.  d_loss_out: fp32 [B T], the caller's.
+int kfh_gpt2_eval(void* h, const int32_t* d_ids, const int32_t* d_tgt, int mode, int branch, float* d_loss_out) {
+    koifish::g_train_err.clear();
+    return reinterpret_cast<GPT2Trainer*>(h)->Eval(d_ids, d_tgt, mode, branch, d_loss_out);
+}
+const char* kfh_gpt2_last_error(void) { return koifish::g_train_err.c_str(); }
 }

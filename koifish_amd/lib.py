@@ -11,6 +11,9 @@ LIB_HOST = os.path.join(os.environ.get("KF_LIB_DIR", HERE), "libkf_host.so")
 F32, F64, F16, BF16, F8E5M2, F8E4M3, U8, I8, U16, I16, U32, I32, U64, I64, Q4, Q3, Q2, T_SIGN, T_SEQ, BOOL1, T_BINARY, T_BINARY_3, T_BINARY_TILE = range(23)
 BITS = {BF16: 16, F8E5M2: 8, Q4: 4, T_SIGN: 2, BOOL1: 1, T_BINARY: 1}
 KF_EPI_RESIDUAL = 1
+EVO_PSO, EVO_MIX, EVO_PSO_GA = 1, 2, 4   # enum kf_evo_algorithm = the live members of Fuyou_params::ALGORITHM
+EVO_ALGORITHMS = {"pso": EVO_PSO, "mix": EVO_MIX, "pso_ga": EVO_PSO_GA}   # Fuyou_params::Algo2Name
+ENSEMBLE_AGGREGATION, ENSEMBLE_BRANCH = 0, 1   # kfh_gpt2_eval's mode
 QUANT_GROUP, QUANT_ROW_LUT, QUANT_ROW_RTN = 0, 1, 2  # kf_weight.quant
 NF4 = 1000  # not a typNUMBER: "Q4 with the normal-float quant card" (QUANT_MODE::RTNf) for the helpers that take a storage type
 
@@ -28,6 +31,7 @@ ABI_SYMBOLS = [
     "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
+    "kf_evolve", "kf_loss_mean",
 ]
 
 
@@ -76,6 +80,8 @@ def load():
         hip.kf_newton_schulz.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
         hip.kf_muon_apply.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_float, C.c_float, C.c_uint32, C.c_void_p]
         hip.kf_muon.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        hip.kf_evolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32]
+        hip.kf_loss_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
         hip.kf_sample_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_layernorm.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         hip.kf_qknorm_rope_train.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
@@ -232,6 +238,14 @@ def load():
         host.kfh_gpt2_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
         host.kfh_gpt2_steps_taken.restype = C.c_longlong
         host.kfh_gpt2_steps_taken.argtypes = [C.c_void_p]
+        # EOE: layer-section branches, the evolve step over the swarm, the ensemble evaluation
+        host.kfh_gpt2_set_branches.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_gpt2_n_branches.argtypes = [C.c_void_p]
+        host.kfh_gpt2_set_active_branch.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_gpt2_active_branch.argtypes = [C.c_void_p]
+        host.kfh_gpt2_evolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32]
+        host.kfh_gpt2_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        host.kfh_gpt2_last_error.restype = C.c_char_p
         # eight decoders, one per XCD (kf_xengine_*): handles are koifish::XcdReplicas* of the host library
         host.kfh_xr_create.restype = C.c_void_p
         host.kfh_xr_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]

@@ -269,6 +269,25 @@ class Context:
         L.check(self.hip.kf_gama_backward(self.h, C.byref(d), _ptr(dIn), _ptr(inp), _ptr(g), n, scale, C.c_void_p((ws.data_ptr() + 255) & ~255)), "kf_gama_backward")
         return g
 
+    def evolve(self, x, head, algorithm, alpha=0.9, social=2.0, t_crossover=0.6, seed=0):
+        """kf_evolve (Fuyou::Exploitation): the follower matrix x [ne0, ne1] bf16 moves towards head [ne0, ne1] bf16, in place; algorithm "pso" | "pso_ga" | "mix"
+        (Fuyou_params::Algo2Name) or a kf_evo_algorithm value; the defaults are Fuyou_params' (alpha 0.9, social 2, T_crossover 0.6).  Returns x."""
+        if isinstance(algorithm, str):
+            if algorithm not in L.EVO_ALGORITHMS:
+                raise ValueError("evolve algorithm %r: one of %s" % (algorithm, sorted(L.EVO_ALGORITHMS)))
+            algorithm = L.EVO_ALGORITHMS[algorithm]
+        if x.dtype != torch.bfloat16 or head.dtype != torch.bfloat16 or x.dim() != 2 or x.shape != head.shape or not x.is_contiguous() or not head.is_contiguous():
+            raise L.KFError("evolve: x %s %s and head %s %s must be contiguous bf16 matrices of one shape" % (tuple(x.shape), x.dtype, tuple(head.shape), head.dtype))
+        L.check(self.hip.kf_evolve(self.h, _ptr(x), _ptr(head), x.shape[0], x.shape[1], int(algorithm), alpha, social, t_crossover, seed & 0xFFFFFFFF), "kf_evolve")
+        return x
+
+    def loss_mean(self, members):
+        """kf_loss_mean over a list of fp32 [n] device tensors: ((m0 + m1) + m2 ...) / len(members) in fp32, one launch per member"""
+        out = torch.empty_like(members[0])
+        for k, m in enumerate(members):
+            L.check(self.hip.kf_loss_mean(self.h, _ptr(out), _ptr(m), out.numel(), k, len(members)), "kf_loss_mean")
+        return out
+
     def act_quant_i8(self, x, norm_w=None, eps=1e-6):
         """kf_act_quant_i8: x bf16 [dim] or [rows, dim] (a row stride larger than dim is honoured) -> (q int8 of x's shape, step fp32 [rows]); with norm_w the rows are
         first RMS-normed and rounded to bf16 as kf_rmsnorm stores them"""

@@ -11,6 +11,12 @@ train_target="gama" is the reference's other way to train a quantised layer ("tr
 as a PackedQ group type keeps its packed integers frozen and trains each group's (zero, step) pair in place inside the blob -- no bf16 master, no [OC, IC] gradient, no
 moments of that size, no re-quantisation: per 128 weights two bf16 parameters, two gradients, four moments (kf_gama_backward + kf_adamw on the blob's gama slice).
 
+layers_in_branch is the reference's EOE, "Evolutionary Optimization of Experts" (Fuyou_params::nLayerInBranch; RLSchedule::InitBranch, Fuyou::UpdateFollower,
+Fish::ForwardOnRLS): the NL layers are cut into NL / layers_in_branch sections; a section plus the shared embedding, final norm and head is a shallow model of its own
+(a "Fuyou").  set_branch(b) picks the one that forward / backward / update / step run; evolve(head) pulls the weight matrices of every other branch towards the head
+branch's (kf_evolve: particle swarm, particle swarm + genetic crossover, or a fixed mix) and re-quantises them; eval_loss scores one branch or the mean of all.  The
+schedule -- which branch trains when, which one is the head -- is the caller's loop over set_branch / step / evolve.
+
 The step keeps every activation (no recomputation).  Python here OWNS the device buffers (torch tensors: setup, outside any timed region) and registers them with
 koifish::GPT2Trainer (koifish_amd/host/kf_train.cpp, libkf_host.so), which sequences the step: forward / backward / update are one C call each, step() is ONE call,
 and nothing in them is a torch op (the embedding gather + add is kf_embed_pos, the attention reads q out of the fused rows, the zero fills are kf_memset / kf_memset2d).
@@ -26,13 +32,14 @@ GAMA_TYPES = (L.Q4, L.T_SIGN, L.BOOL1)   # the PackedQ group storages kf_gama_ba
 
 
 class GPT2Step:
-    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None, train_target="weights"):
+    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None, train_target="weights", layers_in_branch=None):
         """masters: optional dict of host-provided bf16 torch tensors (tests hand the same numbers to the reference): 'wte' [Vp, C], 'wpe' [T, C], 'lnf' (w, b), 'blocks':
         list of dicts {mat: (W [out, in], b [out])} + 'ln' (w1, b1, w2, b2).  Otherwise N(0, w_std) draws on the device.
         train_target: "weights" (the default: bf16 masters, re-quantised after every update) or "gama": every block matrix whose storage is a PackedQ group type (GAMA_TYPES)
         is quantised once from its initial draw, which is then dropped; its entry of self.params has p = the blob's [ZERO][STEP] slice and g, m, v of 2 nGroup elements, no
         weight decay.  f8e5m2 / bf16 matrices, biases, norms and embeddings train as under "weights".  Refused with a reason: a matrix kf_gama_backward does not take
-        (in-features no multiple of 128), and a context that holds a dequant arena (kf_set_dequant_arena: its resident copies would go stale with every update)."""
+        (in-features no multiple of 128), and a context that holds a dequant arena (kf_set_dequant_arena: its resident copies would go stale with every update).
+        layers_in_branch: None, 0 or NL: one branch, the whole depth (the default); otherwise a divisor of NL: NL / layers_in_branch branches, branch 0 active."""
         if train_target not in ("weights", "gama"):
             raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
         self.train_target = train_target
@@ -128,6 +135,48 @@ class GPT2Step:
         arr = (C.c_void_p * 14)(*([t_.data_ptr() for t_ in (self.xf, self.hf, self.mf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.d4)]
                                   + [self._sp_lin, self._sc_ln.data_ptr(), self._sc_at.data_ptr()]))
         L.check(host.kfh_gpt2_set_buffers(self.h, arr), "kfh_gpt2_set_buffers")
+        if layers_in_branch:
+            self._check_host(host.kfh_gpt2_set_branches(self.h, int(layers_in_branch)), "kfh_gpt2_set_branches")
+
+    def _check_host(self, rc, what):
+        """a refusal of the trainer itself carries its reason in kfh_gpt2_last_error; one of a kf_* entry underneath in kf_last_error"""
+        if rc != 0:
+            why = self.ctx.host.kfh_gpt2_last_error().decode() if rc in (-20, -1000) else ""
+            raise L.KFError("%s failed: code %d: %s" % (what, rc, why or self.ctx.hip.kf_last_error().decode()))
+
+    # ---- EOE: layer-section branches
+    @property
+    def n_branches(self):
+        return int(self.ctx.host.kfh_gpt2_n_branches(self.h))
+
+    @property
+    def branch(self):
+        """the active branch"""
+        return int(self.ctx.host.kfh_gpt2_active_branch(self.h))
+
+    def set_branch(self, b):
+        """forward / backward / update / step from here on run embed -> the layers of branch b -> lnf -> tied head, and update the shared tensors and that section's only"""
+        self._check_host(self.ctx.host.kfh_gpt2_set_active_branch(self.h, int(b)), "kfh_gpt2_set_active_branch")
+
+    def evolve(self, head, algorithm="pso_ga", alpha=0.9, social=2.0, t_crossover=0.6, seed=0):
+        """Fuyou::UpdateFollower over the swarm: every branch but `head` has its qkv / proj / fc / proj2 masters moved towards the head branch's (kf_evolve, seed + the
+        follower tensor's index in self.params) and its blobs re-quantised; biases, norms, embeddings and the head branch are not touched.  Refused, with nothing
+        changed, while any block matrix is gama-trained.  One branch: nothing to do."""
+        if algorithm not in L.EVO_ALGORITHMS:
+            raise ValueError("evolve algorithm %r: one of %s" % (algorithm, sorted(L.EVO_ALGORITHMS)))
+        self._check_host(self.ctx.host.kfh_gpt2_evolve(self.h, int(head), L.EVO_ALGORITHMS[algorithm], alpha, social, t_crossover, seed & 0xFFFFFFFF), "kfh_gpt2_evolve")
+
+    def eval_loss(self, ids, tgt, ensemble="aggregation", branch=None):
+        """per-row losses fp32 [B * T] without a backward or an update: "aggregation": the mean over all branches (Fuyou_params::AGGREGATION); "branch": of the given branch
+        (FUYOU_BEST / RANDOM_1: the choice is the caller's; None: the active one).  The active branch is the same afterwards; a backward needs a new forward."""
+        if ensemble not in ("aggregation", "branch"):
+            raise ValueError("ensemble %r: 'aggregation' or 'branch'" % (ensemble,))
+        self._check_arena()
+        out = torch.empty(self.N, dtype=torch.float32, device=self.ctx.device)
+        b = self.branch if branch is None else int(branch)
+        self._check_host(self.ctx.host.kfh_gpt2_eval(self.h, ids.data_ptr(), tgt.data_ptr(), L.ENSEMBLE_BRANCH if ensemble == "branch" else L.ENSEMBLE_AGGREGATION, b,
+                                                     out.data_ptr()), "kfh_gpt2_eval")
+        return out
 
     def _check_arena(self):
         """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
