@@ -99,6 +99,8 @@ int kf_memset32(kf_ctx* ctx, void* p, int32_t value, size_t count);
 int kf_h2d(kf_ctx* ctx, void* dst, const void* h_src, size_t bytes);
 int kf_d2h(kf_ctx* ctx, void* h_dst, const void* src, size_t bytes);
 int kf_d2d(kf_ctx* ctx, void* dst, const void* src, size_t bytes);
+/* `rows` rows of `width` bytes between two pitched device buffers, on the context's stream (a dense [rows, width] block into / out of a column block of wider rows) */
+int kf_d2d_rows(kf_ctx* ctx, void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows);
 /* hipGraph capture of whatever is launched between begin/end on the ctx stream; replay with kf_graph_launch */
 int kf_graph_begin(kf_ctx* ctx);
 int kf_graph_end(kf_ctx* ctx, kf_graph** out);
@@ -398,6 +400,24 @@ int kf_norm_backward(kf_ctx* ctx, kf_bf16* dinp, kf_bf16* dweight, kf_bf16* dbia
  * passes its sequence length).  The q/k-norm that precedes RoPE in the forward is an RMSNorm over head_dim: its backward is kf_norm_backward with
  * rows = n_tok * n_head and dim = head_dim. */
 int kf_rope_backward(kf_ctx* ctx, kf_bf16* d, const float* rope_table, int pos0, int n_tok, int seq_len, long long stride, int n_head, int head_dim);
+
+/* The backward of kf_qknorm_rope_train in ONE entry (the backward branches of ROPE::cuFlow, kernel/rope.cu, and of LayerNormal::cuFlow, T.cu:605-646, over
+ * n_tok * n_head rows of head_dim), fed by kf_attn_backward's dq | dk | dv -- column blocks of fused rows with the common row stride ld_d:
+ *   per head row: g = R^T d  (the transpose of the rotate-half rotation, as kf_rope_backward; row t at position t % seq_len), kept in fp32;
+ *   then kf_norm_backward's RMS branch with the forward's rstd: d_raw = bf16((w g - norm (sum_i w_i g_i raw_i / head_dim) rstd) rstd), norm = raw rstd.
+ * One bf16 rounding fewer than kf_rope_backward + kf_norm_backward.  q_raw / k_raw: the PRE-norm q and k of the forward, row strides ld_qraw / ld_kraw; rstd_q
+ * [n_tok * n_head] / rstd_k [n_tok * n_kv]: what kf_qknorm_rope_train wrote.  Outputs, all dense: dq_raw [n_tok, n_head * head_dim], dk_raw [n_tok, n_kv * head_dim]
+ * (written, not accumulated: they feed kf_linear_backward as they are), dv_out [n_tok, n_kv * head_dim] = a plain copy of dv (dv and dv_out both NULL: skipped);
+ * dwq / dwk [head_dim] ACCUMULATE bf16(sum over the rows + old), as kf_norm_backward's dweight.  Deterministic: no atomics, the row sums go through the scratch in a
+ * fixed order, and nothing depends on the scratch's contents.  Served: head_dim 64 or 128 (otherwise KF_UNSUPPORTED_DATATYPE), n_head a multiple of n_kv, any
+ * n_tok >= 1 a multiple of seq_len, strides multiples of 8 no smaller than their rows.  Refusals launch nothing: a null pointer (one of dv / dv_out alone included), a
+ * bad shape or stride: KF_INVALID_ARGS; a tensor or the table not 16-byte aligned, the scratch not 8-byte aligned: KF_BLAS_UNALIGN.
+ * scratch: kf_qknorm_rope_backward_scratch_bytes(n_tok, n_head, n_kv, head_dim) bytes (0 for a refused shape). */
+size_t kf_qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int head_dim);
+int kf_qknorm_rope_backward(kf_ctx* ctx, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv_or_null, long long ld_d, const kf_bf16* q_raw, long long ld_qraw,
+                            const kf_bf16* k_raw, long long ld_kraw, const kf_bf16* wq_norm, const kf_bf16* wk_norm, const float* rstd_q, const float* rstd_k,
+                            const float* rope_table, int n_tok, int seq_len, int n_head, int n_kv, int head_dim, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out_or_null,
+                            kf_bf16* dwq, kf_bf16* dwk, void* scratch);
 
 /* Activation backward (Relu::Back, Activation.cu:283-320).  GELU, in place on the incoming gradient (Activation_backward_inplace ->
  * gelu_backward_inplace_kernel, Activation.cu:42-78): d = bf16(gelu'(x) * d) with x the pre-activation.  SwiGLU (CU_swiglu_back_v0,

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(HERE, "host")
-HIP_SOURCES = ["kf_gemv.hip", "kf_gemv_canon.hip", "kf_gemv_a8.hip", "kf_act_quant.hip", "kf_gemm.hip", "kf_gemm2.hip", "kf_gemm3.hip", "kf_head_score.hip", "kf_attn.hip", "kf_engine.hip", "kf_xengine.hip", "kf_xengine_q1.hip", "kf_attn_prefill.hip", "kf_ops.hip", "kf_muon.hip", "kf_evo.hip", "kf_lut.hip", "kf_loss.hip", "kf_norm_bwd.hip", "kf_linear_bwd.hip", "kf_gama_bwd.hip", "kf_embed_bwd.hip", "kf_attn_bwd_mfma.hip", "kf_awq.hip", "kf_tp.hip", "kf_abi.hip"]
+HIP_SOURCES = ["kf_gemv.hip", "kf_gemv_canon.hip", "kf_gemv_a8.hip", "kf_act_quant.hip", "kf_gemm.hip", "kf_gemm2.hip", "kf_gemm3.hip", "kf_head_score.hip", "kf_attn.hip", "kf_engine.hip", "kf_xengine.hip", "kf_xengine_q1.hip", "kf_attn_prefill.hip", "kf_ops.hip", "kf_muon.hip", "kf_evo.hip", "kf_lut.hip", "kf_loss.hip", "kf_norm_bwd.hip", "kf_qknorm_rope_bwd.hip", "kf_linear_bwd.hip", "kf_gama_bwd.hip", "kf_embed_bwd.hip", "kf_attn_bwd_mfma.hip", "kf_awq.hip", "kf_tp.hip", "kf_abi.hip"]
 HIP_DEPS = ["kf_device.h", "kf_kernels.h", "kf_gemm_common.h", "kf_gemm_plan.h", "kf_gemm3_tile.h", "kf_score_plan.h", "kf_gama_plan.h", "kf_gemv_plan.h", "kf_a8_plan.h", "kf_attn_plan.h", "kf_gemv_kernel.h", "kf_gemv_blocks.h", "kf_attn_common.h", "kf_engine_common.h", "kf_xengine_kernel.h"]
 LIB_HIP = os.path.join(HERE, "libkf_hip.so")
 LIB_HOST = os.path.join(HERE, "libkf_host.so")
@@ -65,9 +65,11 @@ def build_host(force=False, verbose=False):
     src = os.path.join(HOST, "kf_host.cpp")
     src2 = os.path.join(HOST, "kf_safetensors.cpp")
     src3 = os.path.join(HOST, "kf_train.cpp")
-    deps = [src, src2, src3, os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"), os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+    src4 = os.path.join(HOST, "kf_train_qwen3.cpp")
+    deps = [src, src2, src3, src4, os.path.join(HOST, "kf_train_common.hpp"), os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"),
+            os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
     if force or _stale(LIB_HOST, deps):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", LIB_HOST, src, src2, src3, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", LIB_HOST, src, src2, src3, src4, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -82,10 +84,12 @@ def build_host_asan(verbose=False):
     src = os.path.join(HOST, "kf_host.cpp")
     src2 = os.path.join(HOST, "kf_safetensors.cpp")
     src3 = os.path.join(HOST, "kf_train.cpp")
-    deps = [src, src2, src3, os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"), os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+    src4 = os.path.join(HOST, "kf_train_qwen3.cpp")
+    deps = [src, src2, src3, src4, os.path.join(HOST, "kf_train_common.hpp"), os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"),
+            os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
     if _stale(out, deps):
         cmd = ["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17", "-fPIC", "-shared", "-Wall",
-               "-o", out, src, src2, src3, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
+               "-o", out, src, src2, src3, src4, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -201,6 +201,13 @@ int kf_d2d(kf_ctx* c, void* dst, const void* src, size_t bytes) {
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
     return KF_OK;
 }
+int kf_d2d_rows(kf_ctx* c, void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows) {
+    CHKCTX(c);
+    if (!dst || !src || width > dst_pitch || width > src_pitch) return fail(KF_INVALID_ARGS, "kf_d2d_rows: null pointer or width above a pitch");
+    if (!width || !rows) return KF_OK;
+    HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, width, rows, hipMemcpyDeviceToDevice, c->stream));
+    return KF_OK;
+}
 
 int kf_graph_begin(kf_ctx* c) {
     CHKCTX(c);
@@ -1170,6 +1177,24 @@ int kf_rope_backward(kf_ctx* c, kf_bf16* d, const float* rope_table, int pos0, i
     CHKCTX(c);
     if (!d || !rope_table || pos0 < 0) return fail(KF_INVALID_ARGS, "kf_rope_backward: bad args");
     RET(kf::rope_backward_launch(c->stream, d, rope_table, pos0, n_tok, seq_len, stride, n_head, hd));
+}
+size_t kf_qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int hd) { return kf::qknorm_rope_backward_scratch_bytes(n_tok, n_head, n_kv, hd); }
+int kf_qknorm_rope_backward(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv, long long ld_d, const kf_bf16* q_raw, long long ld_qraw, const kf_bf16* k_raw,
+                            long long ld_kraw, const kf_bf16* wq, const kf_bf16* wk, const float* rstd_q, const float* rstd_k, const float* table, int n_tok, int seq_len,
+                            int n_head, int n_kv, int hd, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out, kf_bf16* dwq, kf_bf16* dwk, void* scratch) {
+    CHKCTX(c);
+    if (!dq || !dk || !q_raw || !k_raw || !wq || !wk || !rstd_q || !rstd_k || !table || !dq_raw || !dk_raw || !dwq || !dwk || !scratch || (!dv) != (!dv_out))
+        return fail(KF_INVALID_ARGS, "kf_qknorm_rope_backward: null pointer (dv and dv_out go together)");
+    if (n_tok < 1 || seq_len < 1 || n_tok % seq_len || n_head < 1 || n_kv < 1 || n_head % n_kv)
+        return fail(KF_INVALID_ARGS, "kf_qknorm_rope_backward: needs n_tok >= 1 a multiple of seq_len and n_head a multiple of n_kv (got %d, %d, %d, %d)", n_tok, seq_len, n_head, n_kv);
+    if (hd != 64 && hd != 128) return fail(KF_UNSUPPORTED_DATATYPE, "kf_qknorm_rope_backward: head_dim %d not covered (64, 128)", hd);
+    if (ld_d < (long long)n_head * hd || ld_qraw < (long long)n_head * hd || ld_kraw < (long long)n_kv * hd || (ld_d % 8) || (ld_qraw % 8) || (ld_kraw % 8))
+        return fail(KF_INVALID_ARGS, "kf_qknorm_rope_backward: a row stride is below its row or no multiple of 8 (%lld, %lld, %lld)", ld_d, ld_qraw, ld_kraw);
+    if (!al16(dq) || !al16(dk) || (dv && !al16(dv)) || !al16(q_raw) || !al16(k_raw) || !al16(wq) || !al16(wk) || !al16(table) || !al16(dq_raw) || !al16(dk_raw) ||
+        (dv_out && !al16(dv_out)) || ((uintptr_t)rstd_q & 3) || ((uintptr_t)rstd_k & 3) || ((uintptr_t)dwq & 1) || ((uintptr_t)dwk & 1) || ((uintptr_t)scratch & 7))
+        return fail(KF_BLAS_UNALIGN, "kf_qknorm_rope_backward: tensors and the table must be 16-byte aligned, the scratch 8-byte aligned");
+    RET(kf::qknorm_rope_backward_launch(c->stream, dq, dk, dv, ld_d, q_raw, ld_qraw, k_raw, ld_kraw, wq, wk, rstd_q, rstd_k, table, n_tok, seq_len, n_head, n_kv, hd, dq_raw, dk_raw,
+                                        dv_out, dwq, dwk, (double*)scratch));
 }
 int kf_gelu_backward(kf_ctx* c, kf_bf16* d_in_out, const kf_bf16* x, size_t n) {
     CHKCTX(c);

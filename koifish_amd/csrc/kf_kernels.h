@@ -189,6 +189,13 @@ int swiglu_backward_launch(hipStream_t st, uint16_t* delta_in_out, uint16_t* del
 int norm_backward_groups(int rows);
 int norm_backward_launch(hipStream_t st, uint16_t* dinp, uint16_t* dweight, uint16_t* dbias, const uint16_t* dout, const uint16_t* inp, const uint16_t* weight,
                          const float* mean, const float* rstd, int rows, int C, double* scratch);
+int norm_backward_reduce_launch(hipStream_t st, uint16_t* dweight, const double* part, int G, int C); /* dweight[c] = bf16(sum_g part[g][c] + dweight[c]) */
+// q/k-norm + RoPE backward in one pass (kf_qknorm_rope_bwd.hip); scratch: qknorm_rope_backward_scratch_bytes (0: a shape the launch refuses)
+size_t qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int hd);
+int qknorm_rope_backward_launch(hipStream_t st, const uint16_t* dq, const uint16_t* dk, const uint16_t* dv, long long ld_d, const uint16_t* q_raw, long long ld_qraw,
+                                const uint16_t* k_raw, long long ld_kraw, const uint16_t* wq, const uint16_t* wk, const float* rstd_q, const float* rstd_k, const float* table,
+                                int n_tok, int seq_len, int n_head, int n_kv, int hd, uint16_t* dq_raw, uint16_t* dk_raw, uint16_t* dv_out, uint16_t* dwq, uint16_t* dwk,
+                                double* scratch);
 int bias_residual_launch(hipStream_t st, uint16_t* y, const uint16_t* bias, const uint16_t* residual, size_t n, int M); /* kf_ops.hip */
 // linear backward helpers (kf_linear_bwd.hip)
 int transpose_bf16_launch(hipStream_t st, const uint16_t* in, uint16_t* out, int R, int C);

@@ -248,6 +248,12 @@ __global__ void __launch_bounds__(256) norm_backward_reduce_kernel(uint16_t* __r
 
 int norm_backward_groups(int rows) { return rows < 512 ? rows : 512; }
 
+// the reduce launch alone, RMS form, for another kernel's [G][C] fp64 column partials (kf_qknorm_rope_bwd.hip)
+int norm_backward_reduce_launch(hipStream_t st, uint16_t* dweight, const double* part, int G, int C) {
+    hipLaunchKernelGGL(norm_backward_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, st, dweight, (uint16_t*)nullptr, part, G, C, 0);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
 int norm_backward_launch(hipStream_t st, uint16_t* dinp, uint16_t* dweight, uint16_t* dbias, const uint16_t* dout, const uint16_t* inp, const uint16_t* weight,
                          const float* mean, const float* rstd, int rows, int C, double* scratch) {
     if (rows < 1 || C < 8 || (C % 8) != 0 || C > NB_MAXV * 2048) return KF_INVALID_ARGS;

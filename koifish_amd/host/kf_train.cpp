@@ -33,20 +33,11 @@
 #include <string>
 #include <vector>
 
-#include "kf_host.hpp"
+#include "kf_train_common.hpp"
 
 namespace koifish {
 
 static thread_local std::string g_train_err;  // why the last kfh_gpt2_evolve / _set_branches / _set_active_branch / _eval refused (kfh_gpt2_last_error)
-
-struct TrainTensor {
-    kf_bf16 *p = nullptr, *g = nullptr;
-    void *m = nullptr, *v = nullptr;
-    long long n = 0;
-    bool decay = false, has_blob = false, requant = false;
-    bool gama = false;  // p is the blob's [ZERO][STEP] slice (n = 2 nGroup): kfh_gpt2_set_param_gama
-    kf_weight blob;  // what the forward multiplies (f8e5m2 / 4-bit PackedQ / the bf16 master itself for the tied head)
-};
 
 // the activations one block keeps for its backward (nothing is recomputed)
 struct BlockActs {
@@ -54,29 +45,19 @@ struct BlockActs {
     float *m1, *r1, *m2, *r2;
 };
 
-struct GPT2Trainer {
-    kf_ctx* ctx = nullptr;
-    int C = 0, H = 0, NL = 0, V = 0, Vp = 0, B = 0, T = 0, N = 0, hd = 0;
-    std::vector<TrainTensor> params;
+// TrainTensor, the registration, LinBack, the optimiser switch and the update loop are TrainerCore's (kf_train_common.hpp), shared with koifish::Qwen3Trainer
+struct GPT2Trainer : TrainerCore {
+    int C = 0, H = 0, NL = 0, V = 0, Vp = 0, B = 0, T = 0, hd = 0;
     std::vector<BlockActs> acts;
     kf_bf16 *xf = nullptr, *hf = nullptr, *logits = nullptr, *dx = nullptr, *dh = nullptr, *dqkv = nullptr, *datt = nullptr, *d4 = nullptr;
     float *mf = nullptr, *rf = nullptr, *losses = nullptr;
-    void *sc_lin = nullptr, *sc_ln = nullptr, *sc_at = nullptr;
+    void *sc_ln = nullptr, *sc_at = nullptr;
     const int32_t* ids = nullptr;  // of the last Forward (the embedding backward scatters by them)
-    long long t = 0;               // optimizer steps taken
-    // Muon (kfh_gpt2_set_optimizer): lr_scale, mui, eps_muon, tpDecay of MUON_params_; the caller owns the scratch (sized for the largest Muon tensor)
-    enum { OPT_ADAMW = 0, OPT_MUON = 1 };
-    int method = OPT_ADAMW, tp_decay = 1;
-    float lr_scale = 1.0f, mui = 0.95f, eps_muon = 1e-7f;
-    void* sc_muon = nullptr;
-    size_t sc_muon_bytes = 0;
-    void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (kfh_gpt2_set_gama_scratch)
-    size_t sc_gama_bytes = 0;
     // EOE: sections of LIS layers; branch b owns layers [b LIS, (b + 1) LIS); [l0, l1) is the active one.  One branch (LIS = NL): the whole depth
     int LIS = 0, branch = 0, l0 = 0, l1 = 0;
     enum { ENSEMBLE_AGGREGATION = 0, ENSEMBLE_BRANCH = 1 };  // Fuyou_params::ENSEMBLE: AGGREGATION; FUYOU_BEST and RANDOM_1 are BRANCH with the caller's choice of branch
     int NBranch() const { return NL / LIS; }
-    bool InSection(size_t i) const { return i >= (size_t)NL * PER_BLOCK || ((int)(i / PER_BLOCK) >= l0 && (int)(i / PER_BLOCK) < l1); }
+    bool InSection(size_t i) const override { return i >= (size_t)NL * PER_BLOCK || ((int)(i / PER_BLOCK) >= l0 && (int)(i / PER_BLOCK) < l1); }
 
     enum { QKV_W = 0, QKV_B, PROJ_W, PROJ_B, FC_W, FC_B, PROJ2_W, PROJ2_B, LN1_W, LN1_B, LN2_W, LN2_B, PER_BLOCK };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_BLOCK + k]; }
@@ -85,51 +66,11 @@ struct GPT2Trainer {
     TrainTensor& LnfW() { return params[(size_t)NL * PER_BLOCK + 2]; }
     TrainTensor& LnfB() { return params[(size_t)NL * PER_BLOCK + 3]; }
 
-    // MUON_params_::isAdamW restated: a Muon tensor is one of a block's four weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape);
-    // wte, wpe, biases, norms and matrices with ne0 < ne1 (proj2) stay on AdamW
-    bool IsMuon(size_t i) const {
-        if (method != OPT_MUON || i >= (size_t)NL * PER_BLOCK) return false;
-        const int k = (int)(i % PER_BLOCK);
-        const TrainTensor& e = params[i];
-        return (k == QKV_W || k == PROJ_W || k == FC_W || k == PROJ2_W) && !e.gama && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
-    }
-    int SetOptimizer(int method_, float lr_scale_, float mui_, float eps_muon_, int tp_decay_, void* scratch, size_t scratch_bytes) {
-        if (method_ != OPT_ADAMW && method_ != OPT_MUON) return KF_INVALID_ARGS;
-        if (method_ == OPT_MUON) {
-            if (!(lr_scale_ > 0.0f) || !scratch) return KF_INVALID_ARGS;
-            const int keep = method;
-            method = OPT_MUON;
-            size_t need = 0;
-            bool ok = true;
-            for (size_t i = 0; i < params.size(); i++)
-                if (IsMuon(i)) {
-                    const size_t b = kf_muon_scratch_bytes(params[i].blob.ne0, params[i].blob.ne1);
-                    ok = ok && b > 0;
-                    need = b > need ? b : need;
-                }
-            method = keep;
-            if (!ok || scratch_bytes < need) return KF_INVALID_ARGS;
-        }
-        method = method_, lr_scale = lr_scale_, mui = mui_, eps_muon = eps_muon_, tp_decay = tp_decay_, sc_muon = scratch, sc_muon_bytes = scratch_bytes;
-        return KF_OK;
-    }
     int Ready() const {
-        for (const TrainTensor& e : params)
-            if (!e.p || !e.g || !e.m || !e.v || e.n < 8 || (e.n & 7)) return KF_INVALID_ARGS;
+        KF_TRY(ParamsReady());
         for (const BlockActs& a : acts)
             if (!a.x || !a.h1 || !a.qkv || !a.att || !a.x2 || !a.h2 || !a.f || !a.g || !a.m1 || !a.r1 || !a.m2 || !a.r2) return KF_INVALID_ARGS;
         if (!xf || !hf || !logits || !dx || !dh || !dqkv || !datt || !d4 || !mf || !rf || !losses || !sc_lin || !sc_ln || !sc_at) return KF_INVALID_ARGS;
-        for (int l = 0; l < NL; l++)
-            for (int k : {QKV_W, PROJ_W, FC_W, PROJ2_W})
-                if (!params[(size_t)l * PER_BLOCK + k].has_blob) return KF_INVALID_ARGS;
-        bool any_gama = false;
-        for (const TrainTensor& e : params)
-            if (e.gama) {
-                const size_t b = kf_gama_backward_scratch_bytes(e.blob.ne0, e.blob.ne1, N);
-                if (b == 0 || !sc_gama || sc_gama_bytes < b) return KF_INVALID_ARGS; /* a shape the entry refuses, or no / too small a scratch */
-                any_gama = true;
-            }
-        if (any_gama && kf_dequant_arena_bytes(ctx) > 0) return KF_INVALID_ARGS; /* resident dequantised copies would go stale with the first update */
         return params[(size_t)NL * PER_BLOCK].has_blob ? KF_OK : KF_INVALID_ARGS;
     }
     // SLP::Forw (NeuronFuse.cu:305-381): y = x . W^T + b (+ residual)
@@ -137,14 +78,6 @@ struct GPT2Trainer {
         return kf_linear(ctx, &w.blob, x, y, bias ? bias->p : nullptr, N, 1.0f, 0.0f, res ? 1u : 0u, res);
     }
     int LN(const kf_bf16* x, TrainTensor& w, TrainTensor& b, kf_bf16* y, float* mean, float* rstd) { return kf_layernorm(ctx, x, w.p, b.p, y, N, C, 1e-5f, mean, rstd); }
-    // SLP::Back (NeuronFuse.cu:495-563): weight / bias gradients into the tensors' own buffers, delta to the layer below
-    int LinBack(TrainTensor& w, const kf_bf16* dIn, const kf_bf16* inp, kf_bf16* delta, TrainTensor* bias) {
-        if (w.gama) { /* the gama branch of SLP::Back: delta and the bias gradient as ever, no gW; then the (zero, step) gradients from the same two operands */
-            KF_TRY(kf_linear_backward(ctx, &w.blob, dIn, inp, delta, nullptr, bias ? bias->g : nullptr, N, 0, sc_lin));
-            return kf_gama_backward(ctx, &w.blob, dIn, inp, w.g, N, 1.0f, sc_gama);
-        }
-        return kf_linear_backward(ctx, &w.blob, dIn, inp, delta, w.g, bias ? bias->g : nullptr, N, 0, sc_lin);
-    }
     // kf_norm_backward ADDS into dweight / dbias: the per-tensor gradients are zero here (kf_adamw zeroes what it consumed)
     int LNBack(kf_bf16* dxx, const kf_bf16* dout, const kf_bf16* inp, TrainTensor& w, TrainTensor& b, const float* mean, const float* rstd) {
         return kf_norm_backward(ctx, dxx, w.g, b.g, dout, inp, w.p, mean, rstd, N, C, sc_ln);
@@ -194,28 +127,9 @@ struct GPT2Trainer {
         }
         return kf_embed_backward(ctx, Wte().g, C, Wpe().g, dx, ids, B, T, C, Vp);
     }
-    // CU_adamw_ on every tensor (its own master, moments and gradient; seeded stochastic rounding), then the re-quantisation of every quantised matrix from its
-    // updated master.  kf_adamw zeroes the gradients it has consumed.  With the Muon switch a Muon tensor takes PIPE_Muon::CU_core instead (kf_muon: mG is its m
-    // buffer, v is not touched; lr x lr_scale, the weight decay by tpDecay, Pipe.cpp:23-37; the same seed as its AdamW launch would have had).
     int Update(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
         KF_TRY(Ready());
-        t++;
-        const float b1c = (float)(1.0 - std::pow(beta1, (double)t)), b2c = (float)(1.0 - std::pow(beta2, (double)t)); /* the bias corrections, in double like the host side of the reference */
-        for (size_t i = 0; i < params.size(); i++) {
-            if (!InSection(i)) continue; /* a tensor of another branch: not touched, its seed index skipped */
-            TrainTensor& e = params[i];
-            const uint32_t sd = (uint32_t)((seed + 7919ull * (unsigned long long)t + i) & 0xFFFFFFFFull);
-            if (IsMuon(i)) {
-                const float wd0 = e.decay ? wd : 0.0f, wd_muon = tp_decay == 0 ? 0.0f : (tp_decay == 1 ? wd0 / lr_scale : wd0);
-                KF_TRY(kf_muon(ctx, e.p, e.g, (kf_bf16*)e.m, e.blob.ne0, e.blob.ne1, lr * lr_scale, wd_muon, mui, eps_muon, 5, sd, sc_muon, sc_muon_bytes, nullptr));
-                if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
-                continue;
-            }
-            KF_TRY(kf_adamw(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f, 1.0f,
-                            sd, nullptr));
-            if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
-        }
-        return KF_OK;
+        return UpdateParams(lr, beta1, beta2, eps, wd, seed);
     }
 
     int SetBranches(int layers_in_branch) {
@@ -310,6 +224,9 @@ void* kfh_gpt2_create(kf_ctx* ctx, int C, int H, int NL, int V, int Vp, int B, i
     GPT2Trainer* g = new GPT2Trainer;
     g->ctx = ctx, g->C = C, g->H = H, g->NL = NL, g->V = V, g->Vp = Vp, g->B = B, g->T = T, g->N = B * T, g->hd = C / H;
     g->params.resize((size_t)NL * GPT2Trainer::PER_BLOCK + 4);
+    g->wmat.assign(g->params.size(), 0);
+    for (int l = 0; l < NL; l++)
+        for (int k : {GPT2Trainer::QKV_W, GPT2Trainer::PROJ_W, GPT2Trainer::FC_W, GPT2Trainer::PROJ2_W}) g->wmat[(size_t)l * GPT2Trainer::PER_BLOCK + k] = 1;
     g->acts.resize(NL);
     g->LIS = NL, g->l1 = NL;
     memset(g->acts.data(), 0, sizeof(koifish::BlockActs) * NL);
@@ -319,34 +236,16 @@ void kfh_gpt2_destroy(void* h) { delete reinterpret_cast<GPT2Trainer*>(h); }
 int kfh_gpt2_n_params(void* h) { return (int)reinterpret_cast<GPT2Trainer*>(h)->params.size(); }
 // blob: the descriptor of what the forward reads (null: the tensor is not multiplied as a weight); requant != 0: kf_quantize(blob, master) after every update
 int kfh_gpt2_set_param(void* h, int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
-    if (index < 0 || index >= (int)t->params.size() || !p || !g || !m || !v || n < 8 || (n & 7)) return KF_INVALID_ARGS;
-    koifish::TrainTensor& e = t->params[index];
-    e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false;
-    if (blob) e.blob = *blob;
-    return KF_OK;
+    return reinterpret_cast<GPT2Trainer*>(h)->SetParam(index, p, g, m, v, n, decay, blob, requant);
 }
 // "train_target": "gama" for one of a block's four weight matrices (index as kfh_gpt2_set_param): blob a PackedQ group storage; the parameter is ITS [ZERO nGroup][STEP nGroup]
 // slice (gama + ne0 + ne1), g / m / v are 2 nGroup bf16 each.  No weight decay, no re-quantisation, AdamW whatever the optimiser switch says.
 int kfh_gpt2_set_param_gama(void* h, int index, void* g, void* m, void* v, const kf_weight* blob) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
-    if (index < 0 || index >= t->NL * GPT2Trainer::PER_BLOCK || !g || !m || !v || !blob) return KF_INVALID_ARGS;
-    const int k = index % GPT2Trainer::PER_BLOCK;
-    if (k != GPT2Trainer::QKV_W && k != GPT2Trainer::PROJ_W && k != GPT2Trainer::FC_W && k != GPT2Trainer::PROJ2_W) return KF_INVALID_ARGS;
-    if (!blob->gama || blob->qzeros || blob->qscales || blob->quant != KF_QUANT_GROUP || (blob->type != KF_Q4 && blob->type != KF_T_SIGN && blob->type != KF_BOOL1)) return KF_UNSUPPORTED_DATATYPE;
-    if (blob->nGroup < 4 || (blob->nGroup & 3) || (long long)blob->nGroup * blob->lGroup != (long long)blob->ne0 * blob->ne1) return KF_INVALID_ARGS;
-    koifish::TrainTensor& e = t->params[index];
-    e.blob = *blob;
-    e.p = const_cast<kf_bf16*>(blob->gama) + blob->ne0 + blob->ne1, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = 2LL * blob->nGroup;
-    e.decay = false, e.has_blob = true, e.requant = false, e.gama = true;
-    return KF_OK;
+    return reinterpret_cast<GPT2Trainer*>(h)->SetParamGama(index, g, m, v, blob);
 }
 // kf_gama_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_gama_backward_scratch_bytes of every gama tensor at the step's B * T rows
 int kfh_gpt2_set_gama_scratch(void* h, void* scratch, size_t bytes) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
-    if (!scratch || ((uintptr_t)scratch & 255)) return KF_INVALID_ARGS;
-    t->sc_gama = scratch, t->sc_gama_bytes = bytes;
-    return KF_OK;
+    return reinterpret_cast<GPT2Trainer*>(h)->SetGamaScratch(scratch, bytes);
 }
 // ptrs: x h1 m1 r1 qkv att x2 h2 m2 r2 f g
 int kfh_gpt2_set_block_acts(void* h, int layer, void* const* ptrs) {

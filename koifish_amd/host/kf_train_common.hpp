@@ -1,0 +1,143 @@
+// kf_train_common.hpp -- what the training-step sequencers of libkf_host.so share (koifish::GPT2Trainer, kf_train.cpp; koifish::Qwen3Trainer, kf_train_qwen3.cpp): the
+// table of trained tensors, its registration in both forms (shadow weights / "train_target": "gama"), SLP::Back for one matrix, the optimiser switch and the update loop
+// with its seed rule.  A trainer adds its own activations, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "kf_host.hpp"
+
+namespace koifish {
+
+struct TrainTensor {
+    kf_bf16 *p = nullptr, *g = nullptr;
+    void *m = nullptr, *v = nullptr;
+    long long n = 0;
+    bool decay = false, has_blob = false, requant = false;
+    bool gama = false;  // p is the blob's [ZERO][STEP] slice (n = 2 nGroup): SetParamGama
+    kf_weight blob;  // what the forward multiplies (f8e5m2 / 4-bit PackedQ / the bf16 master itself for a bf16 head)
+};
+
+struct TrainerCore {
+    kf_ctx* ctx = nullptr;
+    int N = 0;  // token rows of a step
+    std::vector<TrainTensor> params;
+    std::vector<char> wmat;  // per registered index: one of a layer's weight matrices (a Muon / gama candidate)
+    void* sc_lin = nullptr;  // kf_linear_backward's scratch
+    long long t = 0;         // optimizer steps taken
+    // Muon (SetOptimizer): lr_scale, mui, eps_muon, tpDecay of MUON_params_; the caller owns the scratch (sized for the largest Muon tensor)
+    enum { OPT_ADAMW = 0, OPT_MUON = 1 };
+    int method = OPT_ADAMW, tp_decay = 1;
+    float lr_scale = 1.0f, mui = 0.95f, eps_muon = 1e-7f;
+    void* sc_muon = nullptr;
+    size_t sc_muon_bytes = 0;
+    void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (SetGamaScratch)
+    size_t sc_gama_bytes = 0;
+
+    virtual ~TrainerCore() {}
+    virtual bool InSection(size_t) const { return true; }  // Update leaves a tensor outside the active section alone (EOE)
+
+    // MUON_params_::isAdamW restated: a Muon tensor is one of a layer's weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape) and a
+    // [ne0, ne1] bf16 master; embeddings, biases, norms, matrices with ne0 < ne1 and gama-trained tensors stay on AdamW
+    bool IsMuon(size_t i) const {
+        if (method != OPT_MUON || i >= wmat.size() || !wmat[i]) return false;
+        const TrainTensor& e = params[i];
+        return !e.gama && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
+    }
+    int SetOptimizer(int method_, float lr_scale_, float mui_, float eps_muon_, int tp_decay_, void* scratch, size_t scratch_bytes) {
+        if (method_ != OPT_ADAMW && method_ != OPT_MUON) return KF_INVALID_ARGS;
+        if (method_ == OPT_MUON) {
+            if (!(lr_scale_ > 0.0f) || !scratch) return KF_INVALID_ARGS;
+            const int keep = method;
+            method = OPT_MUON;
+            size_t need = 0;
+            bool ok = true;
+            for (size_t i = 0; i < params.size(); i++)
+                if (IsMuon(i)) {
+                    const size_t b = kf_muon_scratch_bytes(params[i].blob.ne0, params[i].blob.ne1);
+                    ok = ok && b > 0;
+                    need = b > need ? b : need;
+                }
+            method = keep;
+            if (!ok || scratch_bytes < need) return KF_INVALID_ARGS;
+        }
+        method = method_, lr_scale = lr_scale_, mui = mui_, eps_muon = eps_muon_, tp_decay = tp_decay_, sc_muon = scratch, sc_muon_bytes = scratch_bytes;
+        return KF_OK;
+    }
+    // blob: the descriptor of what the forward reads (null: the tensor is not multiplied as a weight); requant != 0: kf_quantize(blob, master) after every update
+    int SetParam(int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
+        if (index < 0 || index >= (int)params.size() || !p || !g || !m || !v || n < 8 || (n & 7)) return KF_INVALID_ARGS;
+        TrainTensor& e = params[index];
+        e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false;
+        if (blob) e.blob = *blob;
+        return KF_OK;
+    }
+    // "train_target": "gama" for one of a layer's weight matrices: blob a PackedQ group storage; the parameter is ITS [ZERO nGroup][STEP nGroup] slice
+    // (gama + ne0 + ne1), g / m / v are 2 nGroup bf16 each.  No weight decay, no re-quantisation, AdamW whatever the optimiser switch says.
+    int SetParamGama(int index, void* g, void* m, void* v, const kf_weight* blob) {
+        if (index < 0 || index >= (int)params.size() || !wmat[index] || !g || !m || !v || !blob) return KF_INVALID_ARGS;
+        if (!blob->gama || blob->qzeros || blob->qscales || blob->quant != KF_QUANT_GROUP || (blob->type != KF_Q4 && blob->type != KF_T_SIGN && blob->type != KF_BOOL1)) return KF_UNSUPPORTED_DATATYPE;
+        if (blob->nGroup < 4 || (blob->nGroup & 3) || (long long)blob->nGroup * blob->lGroup != (long long)blob->ne0 * blob->ne1) return KF_INVALID_ARGS;
+        TrainTensor& e = params[index];
+        e.blob = *blob;
+        e.p = const_cast<kf_bf16*>(blob->gama) + blob->ne0 + blob->ne1, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = 2LL * blob->nGroup;
+        e.decay = false, e.has_blob = true, e.requant = false, e.gama = true;
+        return KF_OK;
+    }
+    // kf_gama_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_gama_backward_scratch_bytes of every gama tensor at the step's rows
+    int SetGamaScratch(void* scratch, size_t bytes) {
+        if (!scratch || ((uintptr_t)scratch & 255)) return KF_INVALID_ARGS;
+        sc_gama = scratch, sc_gama_bytes = bytes;
+        return KF_OK;
+    }
+    // every tensor registered; every gama tensor a shape the entry takes, with scratch; no dequant arena beside a gama tensor
+    int ParamsReady() const {
+        for (const TrainTensor& e : params)
+            if (!e.p || !e.g || !e.m || !e.v || e.n < 8 || (e.n & 7)) return KF_INVALID_ARGS;
+        for (size_t i = 0; i < params.size(); i++)
+            if (wmat[i] && !params[i].has_blob) return KF_INVALID_ARGS;
+        bool any_gama = false;
+        for (const TrainTensor& e : params)
+            if (e.gama) {
+                const size_t b = kf_gama_backward_scratch_bytes(e.blob.ne0, e.blob.ne1, N);
+                if (b == 0 || !sc_gama || sc_gama_bytes < b) return KF_INVALID_ARGS; /* a shape the entry refuses, or no / too small a scratch */
+                any_gama = true;
+            }
+        if (any_gama && kf_dequant_arena_bytes(ctx) > 0) return KF_INVALID_ARGS; /* resident dequantised copies would go stale with the first update */
+        return KF_OK;
+    }
+    // SLP::Back (NeuronFuse.cu:495-563): weight / bias gradients into the tensors' own buffers, delta (accumulate: on top of what it holds) to the layer below
+    int LinBack(TrainTensor& w, const kf_bf16* dIn, const kf_bf16* inp, kf_bf16* delta, TrainTensor* bias, int accumulate = 0) {
+        if (w.gama) { /* the gama branch of SLP::Back: delta and the bias gradient as ever, no gW; then the (zero, step) gradients from the same two operands */
+            KF_TRY(kf_linear_backward(ctx, &w.blob, dIn, inp, delta, nullptr, bias ? bias->g : nullptr, N, accumulate, sc_lin));
+            return kf_gama_backward(ctx, &w.blob, dIn, inp, w.g, N, 1.0f, sc_gama);
+        }
+        return kf_linear_backward(ctx, &w.blob, dIn, inp, delta, w.g, bias ? bias->g : nullptr, N, accumulate, sc_lin);
+    }
+    // CU_adamw_ on every tensor (its own master, moments and gradient; seeded stochastic rounding: seed + 7919 t + the tensor's index, one seed per launch as the
+    // reference draws one per tensor update), then the re-quantisation of every quantised matrix from its updated master.  kf_adamw zeroes the gradients it has
+    // consumed.  With the Muon switch a Muon tensor takes PIPE_Muon::CU_core instead (kf_muon: mG is its m buffer, v is not touched; lr x lr_scale, the weight decay
+    // by tpDecay, Pipe.cpp:23-37; the same seed as its AdamW launch would have had).
+    int UpdateParams(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
+        t++;
+        const float b1c = (float)(1.0 - std::pow(beta1, (double)t)), b2c = (float)(1.0 - std::pow(beta2, (double)t)); /* the bias corrections, in double like the host side of the reference */
+        for (size_t i = 0; i < params.size(); i++) {
+            if (!InSection(i)) continue; /* a tensor of another branch: not touched, its seed index skipped */
+            TrainTensor& e = params[i];
+            const uint32_t sd = (uint32_t)((seed + 7919ull * (unsigned long long)t + i) & 0xFFFFFFFFull);
+            if (IsMuon(i)) {
+                const float wd0 = e.decay ? wd : 0.0f, wd_muon = tp_decay == 0 ? 0.0f : (tp_decay == 1 ? wd0 / lr_scale : wd0);
+                KF_TRY(kf_muon(ctx, e.p, e.g, (kf_bf16*)e.m, e.blob.ne0, e.blob.ne1, lr * lr_scale, wd_muon, mui, eps_muon, 5, sd, sc_muon, sc_muon_bytes, nullptr));
+                if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
+                continue;
+            }
+            KF_TRY(kf_adamw(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f, 1.0f,
+                            sd, nullptr));
+            if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
+        }
+        return KF_OK;
+    }
+};
+
+}  // namespace koifish

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
     "kf_evolve", "kf_loss_mean",
+    "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
 ]
 
 
@@ -102,6 +103,9 @@ def load():
         hip.kf_norm_backward.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p]
         hip.kf_norm_backward_scratch_bytes.argtypes, hip.kf_norm_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_rope_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]
+        hip.kf_qknorm_rope_backward.argtypes = [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 6
+        hip.kf_qknorm_rope_backward_scratch_bytes.argtypes, hip.kf_qknorm_rope_backward_scratch_bytes.restype = [C.c_int] * 4, C.c_size_t
+        hip.kf_d2d_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]
         hip.kf_gelu_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         hip.kf_swiglu_backward.argtypes = [C.c_void_p] * 5 + [C.c_size_t]
         hip.kf_fused_classifier.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
@@ -246,6 +250,25 @@ def load():
         host.kfh_gpt2_evolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32]
         host.kfh_gpt2_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         host.kfh_gpt2_last_error.restype = C.c_char_p
+        # the Qwen3 training step's sequencer (koifish::Qwen3Trainer, host/kf_train_qwen3.cpp)
+        host.kfh_qwen3t_create.restype = C.c_void_p
+        host.kfh_qwen3t_create.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_float, C.c_int]
+        host.kfh_qwen3t_destroy.restype = None
+        host.kfh_qwen3t_destroy.argtypes = [C.c_void_p]
+        host.kfh_qwen3t_n_params.argtypes = [C.c_void_p]
+        host.kfh_qwen3t_set_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int]
+        host.kfh_qwen3t_set_param_gama.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        host.kfh_qwen3t_set_gama_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        host.kfh_qwen3t_set_layer_acts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        host.kfh_qwen3t_set_buffers.argtypes = [C.c_void_p, C.c_void_p]
+        host.kfh_qwen3t_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        host.kfh_qwen3t_backward.argtypes = [C.c_void_p]
+        host.kfh_qwen3t_update.argtypes = [C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
+        host.kfh_qwen3t_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
+        host.kfh_qwen3t_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
+        host.kfh_qwen3t_steps_taken.restype = C.c_longlong
+        host.kfh_qwen3t_steps_taken.argtypes = [C.c_void_p]
+        host.kfh_qwen3t_last_error.restype = C.c_char_p
         # eight decoders, one per XCD (kf_xengine_*): handles are koifish::XcdReplicas* of the host library
         host.kfh_xr_create.restype = C.c_void_p
         host.kfh_xr_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]

@@ -20,7 +20,10 @@ schedule -- which branch trains when, which one is the head -- is the caller's l
 The step keeps every activation (no recomputation).  Python here OWNS the device buffers (torch tensors: setup, outside any timed region) and registers them with
 koifish::GPT2Trainer (koifish_amd/host/kf_train.cpp, libkf_host.so), which sequences the step: forward / backward / update are one C call each, step() is ONE call,
 and nothing in them is a torch op (the embedding gather + add is kf_embed_pos, the attention reads q out of the fused rows, the zero fills are kf_memset / kf_memset2d).
-Used by tests/test_gpu_train_step.py (a 2-layer toy, two consecutive steps against the oracle) and by bench.py's config3 leg (full size)."""
+Used by tests/test_gpu_train_step.py (a 2-layer toy, two consecutive steps against the oracle) and by bench.py's config3 leg (full size).
+
+Qwen3Step, further down, is the same for the Qwen3 family (koifish::Qwen3Trainer, koifish_amd/host/kf_train_qwen3.cpp); the two trainers share the tensor table, SLP::Back,
+the optimiser switch and the update loop (koifish_amd/host/kf_train_common.hpp)."""
 import ctypes as C
 
 import torch
@@ -235,6 +238,238 @@ class GPT2Step:
         self._ids = ids
         self._check_arena()
         L.check(self.ctx.host.kfh_gpt2_step(self.h, ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_gpt2_step")
+
+    def n_params(self):
+        return sum(e["p"].numel() for e in self.params)
+
+
+Q3_MATS = ("q", "k", "v", "o", "gate", "up", "down")   # the slot order of Qwen3.set_weight
+Q3_NORMS = ("n1", "n2", "qn", "kn")                    # the slot order of Qwen3.set_norm
+
+
+class Qwen3Step:
+    """One WHOLE training step of the Qwen3 family, GPT2Step's counterpart: the model everything else in this package serves (decode engines, prefill, score, .kun), and
+    the one the reference's own training goldens run (cases/test_lite.py, tutorial_qwen3.md: Qwen3-596M plain and 4-bit with "train_target": "gama").
+
+      forward  kf_embed_batch, n_layer x [RMSNorm, q / k / v, per-head q/k RMSNorm + RoPE (kf_qknorm_rope_train), GQA causal attention, o_proj + residual, RMSNorm,
+               gate / up / SwiGLU / down + residual], RMSNorm, head, fused classifier -- on the QUANTISED blobs
+      backward the reverse; dq | dk | dv of the attention backward through ONE kf_qknorm_rope_backward; weight gradients into per-tensor buffers
+      update   kf_adamw (or kf_muon under set_optimizer("muon"): q, k, v, gate, up at the Qwen3 shapes) on the bf16 masters, every blob re-quantised
+
+    Python owns the torch buffers and registers them once with koifish::Qwen3Trainer (host/kf_train_qwen3.cpp); forward / backward / update are one C call each, step()
+    is ONE call, and nothing in them is a torch op.  self.params holds the same dicts as GPT2Step.params, in the trainer's order: per layer q.w k.w v.w o.w gate.w up.w
+    down.w n1 n2 qn kn, then wte, nf, and head when untied.
+
+    as_model(max_seq) hands out a Qwen3 decoder built ON these blobs and norm tensors (no copy): score, perplexity, generate, save_kun and the engines then work on the
+    trained weights; every update() calls weights_changed() on each model still alive.
+
+    Not offered on this trainer: EOE layer-section branches (GPT2Step's layers_in_branch)."""
+
+    def __init__(self, ctx, cfg, B, T, types=None, tied=True, seed=0, w_std=0.02, masters=None, train_target="weights"):
+        """cfg: the dict Qwen3 takes (dim, n_layer, n_head, n_kv, head_dim, ffn, vocab, theta, rms_eps).  types: storage per matrix name of Q3_MATS (default: 4-bit for
+        all seven); the embedding / head are bf16.  The vocabulary is padded to a multiple of 64 rows (kf_linear_backward); the padded rows stay zero.
+        masters: optional dict of host-provided bf16 torch tensors: 'wte' [V or Vp, dim], 'nf' [dim], 'head' [V or Vp, dim] (untied), 'layers': list of dicts
+        {q .. down: W [out, in], n1, n2: [dim], qn, kn: [head_dim]}.  Otherwise N(0, w_std) draws on the device and unit norms.
+        train_target: "weights" or "gama" (every layer matrix stored as a PackedQ group type trains its (zero, step) pairs in place, as GPT2Step); a context that holds a
+        dequant arena is refused."""
+        if train_target not in ("weights", "gama"):
+            raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
+        self.train_target, self.tied = train_target, bool(tied)
+        self.ctx, self.cfg, self.B, self.T, self.N = ctx, dict(cfg), B, T, B * T
+        dim, NL, H, KV, hd, ffn, V = (cfg[k] for k in ("dim", "n_layer", "n_head", "n_kv", "head_dim", "ffn", "vocab"))
+        self.V, self.Vp = V, (V + 63) // 64 * 64
+        self.eps, self.theta = float(cfg.get("rms_eps", 1e-6)), float(cfg.get("theta", 1e6))
+        Vp, N, Cq, Ck = self.Vp, self.N, H * hd, KV * hd
+        W_ = Cq + 2 * Ck
+        self.types = dict({k: L.Q4 for k in Q3_MATS}, **(types or {}))
+        dev, bf, f32 = ctx.device, torch.bfloat16, torch.float32
+        g = torch.Generator(device=dev)
+        g.manual_seed(seed)
+        z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
+        rnd = lambda *s: (torch.randn(*s, device=dev, generator=g) * w_std).to(bf)
+        ones = lambda n: torch.ones(n, device=dev, dtype=bf)
+        self.shapes = dict(q=(Cq, dim), k=(Ck, dim), v=(Ck, dim), o=(dim, Cq), gate=(ffn, dim), up=(ffn, dim), down=(dim, ffn))
+        self.params, self.layers, self._models = [], [], []
+        self._check_arena()
+
+        def reg(name, p, wd, type_=None):
+            e = dict(name=name, p=p.contiguous(), g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=wd, blob=None, type=type_)
+            if type_ is not None:
+                e["blob"] = ctx.quantize(e["p"], type_)
+                if type_ == L.BF16:
+                    e["p"] = e["blob"].blob.view(bf).view(p.shape)   # a bf16 "blob" IS the master: updated in place, nothing to re-quantise
+            self.params.append(e)
+            return e
+
+        def reg_gama(name, Wm, type_):
+            blob = ctx.quantize(Wm.contiguous(), type_)   # the draw is dropped: the packed integers are the weight from here on
+            p = blob.gama_slice()
+            e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=False, blob=blob, type=type_, gama=True)
+            self.params.append(e)
+            return e
+
+        def vocab_rows(t_):
+            t_ = t_.to(dev)
+            return t_ if t_.shape[0] == Vp else torch.cat([t_, z(Vp - t_.shape[0], dim)])
+        for l in range(NL):
+            ml = masters["layers"][l] if masters else None
+            ly = {}
+            for k in Q3_MATS:
+                Wm = ml[k].to(dev) if ml else rnd(*self.shapes[k])
+                if train_target == "gama" and self.types[k] in GAMA_TYPES:
+                    ly[k] = reg_gama("l%d.%s.w" % (l, k), Wm, self.types[k])
+                else:
+                    ly[k] = reg("l%d.%s.w" % (l, k), Wm, True, self.types[k])
+            for k in Q3_NORMS:
+                n_ = hd if k in ("qn", "kn") else dim
+                ly[k] = reg("l%d.%s" % (l, k), ml[k].to(dev) if ml else ones(n_), False)
+            self.layers.append(ly)
+        self.wte = reg("wte", vocab_rows(masters["wte"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
+        self.nf = reg("nf", masters["nf"].to(dev) if masters else ones(dim), False)
+        self.head = self.wte if self.tied else reg("head", vocab_rows(masters["head"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
+        # activations of one step, all kept
+        self.A = [dict(x=z(N, dim), h1=z(N, dim), r1=z(N, dt=f32), qraw=z(N, Cq), kraw=z(N, Ck), qkv=z(N, W_), rq=z(N * H, dt=f32), rk=z(N * KV, dt=f32), att=z(N, Cq),
+                       x2=z(N, dim), h2=z(N, dim), r2=z(N, dt=f32), gate=z(N, ffn), up=z(N, ffn), act=z(N, ffn)) for _ in range(NL)]
+        self.xf, self.hf, self.rf, self.logits, self.losses = z(N, dim), z(N, dim), z(N, dt=f32), z(N, Vp), z(N, dt=f32)
+        self.dx, self.dh, self.dqkv, self.datt, self.dact, self.dgate = z(N, dim), z(N, dim), z(N, W_), z(N, Cq), z(N, ffn), z(N, ffn)
+        self.vtmp, self.dqr, self.dkr, self.dvd = z(N, Ck), z(N, Cq), z(N, Ck), z(N, Ck)
+        self.table = ctx.rope_table(T, hd, self.theta)
+        hip, host = ctx.hip, ctx.host
+        for k in Q3_MATS:
+            ctx.linear_scratch(self.layers[0][k]["blob"], N)
+        nb = max(hip.kf_linear_backward_scratch_bytes(oc, ic, N) for oc, ic in list(self.shapes.values()) + [(Vp, dim)])
+        self._sc_lin = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+        self._sc_ln = torch.empty(hip.kf_norm_backward_scratch_bytes(N, dim, 0) // 8 + 1, dtype=torch.float64, device=dev)
+        self._sc_at = torch.empty(hip.kf_attn_backward_scratch_bytes(T, H, B) // 4 + 1, dtype=torch.float32, device=dev)
+        nqk = hip.kf_qknorm_rope_backward_scratch_bytes(N, H, KV, hd)
+        if not nqk:
+            raise L.KFError("Qwen3Step: kf_qknorm_rope_backward does not take %d / %d heads of %d (head_dim 64 or 128, n_head a multiple of n_kv)" % (H, KV, hd))
+        self._sc_qk = torch.empty(nqk // 8 + 1, dtype=torch.float64, device=dev)
+
+        # the step's sequencer: koifish::Qwen3Trainer of libkf_host.so over the buffers above -- every tensor registered once
+        self.h = host.kfh_qwen3t_create(ctx.h, dim, NL, H, KV, hd, ffn, V, Vp, B, T, self.eps, int(self.tied))
+        if not self.h:
+            raise L.KFError("kfh_qwen3t_create refused the shape: %s" % host.kfh_qwen3t_last_error().decode())
+        assert host.kfh_qwen3t_n_params(self.h) == len(self.params)
+        gama = [e for e in self.params if e.get("gama")]
+        if gama:
+            need = [hip.kf_gama_backward_scratch_bytes(e["blob"].ne0, e["blob"].ne1, N) for e in gama]
+            if not all(need):
+                bad = gama[need.index(0)]
+                raise L.KFError("train_target='gama': kf_gama_backward does not take %s [%d, %d] at %d rows (in-features a multiple of 128, out-features and rows multiples of 64)"
+                                % (bad["name"], bad["blob"].ne0, bad["blob"].ne1, N))
+            self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=dev)
+            L.check(host.kfh_qwen3t_set_gama_scratch(self.h, (self._sc_gama.data_ptr() + 255) & ~255, max(need)), "kfh_qwen3t_set_gama_scratch")
+        for i, e in enumerate(self.params):
+            d = e["blob"].desc() if e["blob"] is not None else None
+            if e.get("gama"):
+                self._check_host(host.kfh_qwen3t_set_param_gama(self.h, i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d)), "kfh_qwen3t_set_param_gama")
+                continue
+            L.check(host.kfh_qwen3t_set_param(self.h, i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["p"].numel(), int(e["wd"]),
+                                              C.byref(d) if d is not None else None, int(e["type"] is not None and e["type"] != L.BF16)), "kfh_qwen3t_set_param")
+        for l, a in enumerate(self.A):
+            arr = (C.c_void_p * 15)(*[a[k].data_ptr() for k in ("x", "h1", "r1", "qraw", "kraw", "qkv", "rq", "rk", "att", "x2", "h2", "r2", "gate", "up", "act")])
+            L.check(host.kfh_qwen3t_set_layer_acts(self.h, l, arr), "kfh_qwen3t_set_layer_acts")
+        bufs = (self.xf, self.hf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.dact, self.dgate, self.vtmp, self.dqr, self.dkr, self.dvd, self.table)
+        arr = (C.c_void_p * 20)(*([t_.data_ptr() for t_ in bufs] + [(self._sc_lin.data_ptr() + 255) & ~255, self._sc_ln.data_ptr(), self._sc_at.data_ptr(), self._sc_qk.data_ptr()]))
+        L.check(host.kfh_qwen3t_set_buffers(self.h, arr), "kfh_qwen3t_set_buffers")
+        self.optimizer = "adamw"
+
+    def _check_host(self, rc, what):
+        """a refusal of the trainer itself carries its reason in kfh_qwen3t_last_error; one of a kf_* entry underneath in kf_last_error"""
+        if rc != 0:
+            why = self.ctx.host.kfh_qwen3t_last_error().decode()
+            raise L.KFError("%s failed: code %d: %s" % (what, rc, why or self.ctx.hip.kf_last_error().decode()))
+
+    def _check_arena(self):
+        """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
+        if self.train_target == "gama" and self.ctx.hip.kf_dequant_arena_bytes(self.ctx.h):
+            raise L.KFError("train_target='gama' on a context with a dequant arena (kf_set_dequant_arena): the resident bf16 copies of the trained matrices would go stale "
+                            "with every update -- switch the arena off (kf_set_dequant_arena(ctx, NULL, 0)) for training")
+
+    def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
+        """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a layer's weight matrices with ne0 >= ne1 and a bf16 master (q, k, v, gate,
+        up at the Qwen3 shapes) take kf_muon; o, down, the norms, the embedding and the head keep kf_adamw -- and so does every gama-trained tensor.  Owns the scratch,
+        sized for the largest Muon tensor."""
+        if method not in ("adamw", "muon"):
+            raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
+        sp, nb = None, 0
+        if method == "muon":
+            shapes = [tuple(e["p"].shape) for e in self.params
+                      if e["blob"] is not None and not e.get("gama") and e["name"].startswith("l") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
+            nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
+            if nb == 0:
+                raise L.KFError("muon: a layer matrix has a dimension that is no multiple of 64")
+            self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
+            sp = (self._sc_muon.data_ptr() + 255) & ~255
+        L.check(self.ctx.host.kfh_qwen3t_set_optimizer(self.h, int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb), "kfh_qwen3t_set_optimizer")
+        self.optimizer = method
+
+    def as_model(self, max_seq):
+        """a Qwen3 decoder on the trainer's OWN blobs and norm tensors (set_weight / set_norm / tie_head with device pointers: no copy), vocabulary = the unpadded one.
+        The step keeps a weak reference and calls weights_changed() on it after every update; the model must not outlive this object's buffers."""
+        import weakref
+        from .runtime import DevWeight, Qwen3
+        dim, V = self.cfg["dim"], self.V
+        m = Qwen3(dict(self.cfg, max_seq=int(max_seq), rms_eps=self.eps, qk_eps=self.eps, theta=self.theta, tied=self.tied), device=self.ctx.device.index or 0)
+        rows = lambda e: DevWeight(L.BF16, V, dim, e["blob"].blob[:V * dim * 2])   # the first V rows of the [Vp, dim] bf16 blob, the same memory
+        m.set_weight(-1, 0, rows(self.wte))
+        if self.tied:
+            m.tie_head()
+        else:
+            m.set_weight(-1, 1, rows(self.head))
+        m.set_norm(-1, 0, self.nf["p"])
+        for li, ly in enumerate(self.layers):
+            for si, k in enumerate(Q3_MATS):
+                m.set_weight(li, si, ly[k]["blob"])
+            for si, k in enumerate(Q3_NORMS):
+                m.set_norm(li, si, ly[k]["p"])
+        m._trainer = self   # the buffers live as long as the model does
+        self._models.append(weakref.ref(m))
+        return m
+
+    def _weights_changed(self):
+        live = []
+        for r in self._models:
+            m = r()
+            if m is not None and getattr(m, "h", None):
+                m.weights_changed()
+                live.append(r)
+        self._models = live
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.host.kfh_qwen3t_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def t(self):
+        """optimizer steps taken"""
+        return int(self.ctx.host.kfh_qwen3t_steps_taken(self.h))
+
+    # ---- the step: sequenced by the host library; Python passes two device pointers and the hyper-parameters
+    def forward(self, ids, tgt):
+        """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
+        self._ids = ids   # kept alive: the backward reads them
+        self._check_arena()
+        L.check(self.ctx.host.kfh_qwen3t_forward(self.h, ids.data_ptr(), tgt.data_ptr()), "kfh_qwen3t_forward")
+
+    def backward(self):
+        L.check(self.ctx.host.kfh_qwen3t_backward(self.h), "kfh_qwen3t_backward")
+
+    def update(self, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
+        """as GPT2Step.update (seed + 7919 t + the tensor's index); then weights_changed() on every model handed out by as_model"""
+        L.check(self.ctx.host.kfh_qwen3t_update(self.h, lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_qwen3t_update")
+        self._weights_changed()
+
+    def step(self, ids, tgt, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
+        """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
+        self._ids = ids
+        self._check_arena()
+        L.check(self.ctx.host.kfh_qwen3t_step(self.h, ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_qwen3t_step")
+        self._weights_changed()
 
     def n_params(self):
         return sum(e["p"].numel() for e in self.params)
