@@ -667,6 +667,17 @@ int kf_xengine_set_head_tp(kf_ctx* ctx, kf_xengine* e, const kf_weight* const* h
 int kf_linear_a8_status(const kf_weight* w, int nTok);
 int kf_act_quant_i8(kf_ctx* ctx, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w_or_null, float eps, int rows, int dim, int8_t* q, float* step);
 int kf_linear_a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
+/* kf_linear_a8_tiles: kf_linear_a8's contract and kf_linear_a8's bits on the int8 MFMA (v_mfma_i32_16x16x64_i8), for token batches: q int8 [nTok][ne1] and step fp32
+ * [nTok] as kf_act_quant_i8 writes them, y bf16 [nTok][ne0], y = bf16(step_x * acc [+ bias]) then bf16(residual + bf16(y)); residual [nTok][ne0] may alias y (every
+ * output element is read and written by one lane).  Any nTok >= 1 is served; token and row tails are masked.  Per 128-weight group an int32 accumulator starts from
+ * zero and takes exactly that group (two MFMA steps); the lane that holds an output element folds I_g into its fp32 chain in ascending g: the definition above, so the
+ * result equals kf_linear_a8's bit for bit whatever the tile, the grid or nTok.  The launch is kf::a8_tile_plan's (csrc/kf_a8_tile_plan.h); its refusals are
+ * kf::a8_plan's, the ones listed above.
+ * kf_linear_a8_tiles_status: what kf_linear_a8_tiles would answer for this weight and nTok, without a launch.
+ * KF_A8_TILE_MIN: the token count from which callers that route (Fish::A8Group) send a batch to the tiles by default; below it, and for nTok = 1 always, kf_linear_a8. */
+enum { KF_A8_TILE_MIN = 32 };
+int kf_linear_a8_tiles_status(const kf_weight* w, int nTok);
+int kf_linear_a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
 
 #ifdef __cplusplus
 }

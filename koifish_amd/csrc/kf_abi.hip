@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kf_a8_plan.h"
+#include "kf_a8_tile_plan.h"
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
@@ -1556,6 +1557,21 @@ int kf_linear_a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* st
     if (p.status != KF_OK) return fail(p.status, "kf_linear_a8: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
     RET(kf::a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
 }
+// the same product on int8 MFMA tiles: every launch decision is kf::a8_tile_plan's, whose refusals are kf::a8_plan's
+int kf_linear_a8_tiles_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::a8_tile_plan(kf::A8Problem{kf::mat_of(w), nTok}).status : KF_INVALID_ARGS; }
+int kf_linear_a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_a8_tiles: null weight");
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_a8_tiles: null pointer");
+    const kf::A8TilePlan p = kf::a8_tile_plan(kf::A8Problem{kf::mat_of(w), nTok});
+    if (p.status == KF_UNSUPPORTED_DATATYPE)
+        return fail(p.status, "kf_linear_a8_tiles: weight type %d (quant mode %d%s) has no integer form: served are KF_T_SIGN (%d), KF_BOOL1 (%d), KF_T_BINARY (%d) in group storage",
+                    w->type, w->quant, (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_T_SIGN, KF_BOOL1, KF_T_BINARY);
+    if (p.status == KF_QUANT_ERR) return fail(p.status, "kf_linear_a8_tiles: group size %d (must be 128) or gama missing", w->lGroup);
+    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_a8_tiles: weight data not 16-byte aligned");
+    if (p.status != KF_OK) return fail(p.status, "kf_linear_a8_tiles: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
+    RET(kf::a8_tiles_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
 
 // the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py
 int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
@@ -1579,6 +1595,12 @@ int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
 int kfdbg_a8_plan(const kf::A8Problem* P, kf::A8Plan* out) {
     if (!P || !out) return -1;
     *out = kf::a8_plan(*P);
+    return 0;
+}
+// the plan kf::a8_tile_plan makes for the same product on MFMA tiles (no HIP call): tests/test_a8_tiles_cpu.py
+int kfdbg_a8_tile_plan(const kf::A8Problem* P, kf::A8TilePlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::a8_tile_plan(*P);
     return 0;
 }
 // the plan kf::score_plan makes for a scoring problem (no HIP call): tests/test_score_cpu.py

@@ -411,9 +411,14 @@ int Fish::A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int d
     }
     for (int i = 0; i < n_w; i++) {
         const floatX* b = s[i]->b ? ToX(s[i]->b) : nullptr;
-        if (a8_type(wd[i]))
-            KF_TRY(kf_linear_a8(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
-        else
+        if (a8_type(wd[i])) {
+            const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
+            if (tiles)
+                KF_TRY(kf_linear_a8_tiles(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
+            else
+                KF_TRY(kf_linear_a8(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
+            a8_count[tiles ? 0 : 1]++;
+        } else
             KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], b, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
     }
     return KF_OK;
@@ -459,6 +464,7 @@ int Fish::SetActInt8(bool on, std::string& why) {
             return KF_UNSUPPORTED_DATATYPE;
         }
         KF_TRY(A8Ready(1));
+        a8_count[0] = a8_count[1] = 0;
     }
     if (on != act_int8) {
         DropEngineTable(); /* the captured graphs and the engine belong to the other arithmetic */
@@ -1563,6 +1569,19 @@ int kfh_set_act_int8(void* h, int on) {
     const int rc = reinterpret_cast<Fish*>(h)->SetActInt8(on != 0, g_host_err);
     if (rc != KF_OK) g_host_err = "kfh_set_act_int8: " + g_host_err;
     return rc;
+}
+// the token count from which a token batch's ternary / 1-bit matrices take the int8 MFMA tiles (kf_linear_a8_tiles) instead of the mat-vec (kf_linear_a8): n >= 2 sets it,
+// 1 is treated as 2 (a single token always takes the mat-vec), 0 restores the default (KF_A8_TILE_MIN), n < 0 = never.  Both routes give the same bits.
+int kfh_set_a8_tile_min(void* h, int n) {
+    reinterpret_cast<Fish*>(h)->a8_tile_min = n == 0 ? (int)KF_A8_TILE_MIN : n == 1 ? 2 : n < 0 ? -1 : n;
+    return KF_OK;
+}
+// (kf_linear_a8_tiles launches, kf_linear_a8 launches) since the last switch-on of kfh_set_act_int8
+int kfh_a8_route_counts(void* h, int64_t* out2) {
+    if (!h || !out2) return KF_INVALID_ARGS;
+    const Fish* f = reinterpret_cast<Fish*>(h);
+    out2[0] = f->a8_count[0], out2[1] = f->a8_count[1];
+    return KF_OK;
 }
 // summation order of the decode kernels (kf_set_canonical): 1 (default) the canonical order shared with the CPU oracle, 0 the v_dot2c forms; captured graphs are dropped
 int kfh_set_canonical(void* h, int on) {

@@ -319,6 +319,10 @@ struct Fish : SeqBuffers {
     int8_t* a8_q = nullptr;     // [a8_rows][max(q_dim, nEmbed, n_ff)]
     float* a8_step = nullptr;   // [a8_rows]
     int a8_rows = 0;
+    // token batches of at least a8_tile_min rows send those matrices to kf_linear_a8_tiles (int8 MFMA tiles; the same bits), smaller ones and every single token to
+    // kf_linear_a8; < 0: never.  kfh_set_a8_tile_min; the default is the tile plan's KF_A8_TILE_MIN.  a8_count: (tile, mat-vec) launches since the last switch-on.
+    int a8_tile_min = KF_A8_TILE_MIN;
+    int64_t a8_count[2] = {0, 0};
     int SetActInt8(bool on, std::string& why);  // the switch-on checks: a ternary / 1-bit layer matrix exists, every ZERO section of those is zero, no hot-row mask
     int A8Ready(int rows);
     // the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual` (may alias y[0]; n_w == 1) kf_linear's

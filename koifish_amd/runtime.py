@@ -308,6 +308,15 @@ class Context:
         L.check(self.hip.kf_linear_a8(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8")
         return y
 
+    def linear_a8_tiles(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_a8_tiles: linear_a8's contract and bits on int8 MFMA tiles, for token batches (any nTok >= 1 is served); residual may be y"""
+        n = 1 if q.dim() == 1 else q.shape[0]
+        if y is None:
+            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
+        d = w.desc()
+        L.check(self.hip.kf_linear_a8_tiles(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8_tiles")
+        return y
+
     def rmsnorm(self, x, w, eps=1e-6):
         y = torch.empty_like(x)
         rows = 1 if x.dim() == 1 else x.shape[0]
@@ -555,6 +564,17 @@ class Qwen3:
         if rc != 0:
             raise L.KFError("set_act_int8 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         self._act_int8 = bool(on)
+
+    def set_a8_tile_min(self, n):
+        """token batches of at least n rows send their ternary / 1-bit matrices to the int8 MFMA tiles (kf_linear_a8_tiles) while int8 activations are on, smaller ones and
+        single tokens to the mat-vec (kf_linear_a8): n >= 2 sets the threshold (1 is treated as 2), 0 restores the default (32), n < 0 = never.  The bits are the same."""
+        L.check(self.host.kfh_set_a8_tile_min(self.h, int(n)), "kfh_set_a8_tile_min")
+
+    def a8_route_counts(self):
+        """(kf_linear_a8_tiles launches, kf_linear_a8 launches) since the last set_act_int8(True)"""
+        out = (C.c_int64 * 2)()
+        L.check(self.host.kfh_a8_route_counts(self.h, out), "kfh_a8_route_counts")
+        return int(out[0]), int(out[1])
 
     def set_canonical(self, on):
         """1 (the library default): the decode kernels sum in the canonical order the CPU oracle shares (bit-exact logits, ids and KV rows); 0: the v_dot2c_f32_bf16 / fp32 forms"""
