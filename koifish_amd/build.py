@@ -14,6 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(HERE, "host")
 HIP_SOURCES = ["kf_gemv.hip", "kf_gemv_canon.hip", "kf_gemv_a8.hip", "kf_gemm_a8.hip", "kf_act_quant.hip", "kf_gemm.hip", "kf_gemm2.hip", "kf_gemm3.hip", "kf_head_score.hip", "kf_attn.hip", "kf_engine.hip", "kf_xengine.hip", "kf_xengine_q1.hip", "kf_attn_prefill.hip", "kf_ops.hip", "kf_muon.hip", "kf_evo.hip", "kf_lut.hip", "kf_loss.hip", "kf_norm_bwd.hip", "kf_qknorm_rope_bwd.hip", "kf_linear_bwd.hip", "kf_gama_bwd.hip", "kf_embed_bwd.hip", "kf_attn_bwd_mfma.hip", "kf_awq.hip", "kf_tp.hip", "kf_abi.hip"]
 HIP_DEPS = ["kf_device.h", "kf_kernels.h", "kf_gemm_common.h", "kf_gemm_plan.h", "kf_gemm3_tile.h", "kf_score_plan.h", "kf_gama_plan.h", "kf_gemv_plan.h", "kf_a8_plan.h", "kf_a8_tile_plan.h", "kf_attn_plan.h", "kf_gemv_kernel.h", "kf_gemv_blocks.h", "kf_attn_common.h", "kf_engine_common.h", "kf_xengine_kernel.h"]
+HOST_SOURCES = ["kf_host.cpp", "kf_safetensors.cpp", "kf_train.cpp", "kf_train_qwen3.cpp"]
+HOST_DEPS = ["kf_train_common.hpp", "kf_safetensors.hpp", "kf_host.hpp"]
 LIB_HIP = os.path.join(HERE, "libkf_hip.so")
 LIB_HOST = os.path.join(HERE, "libkf_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -61,15 +63,16 @@ def build_hip(force=False, verbose=False):
     return LIB_HIP
 
 
+def _host_inputs():
+    """the host library's translation units, and everything a change to which makes it stale"""
+    srcs = [os.path.join(HOST, s) for s in HOST_SOURCES]
+    return srcs, srcs + [os.path.join(HOST, d) for d in HOST_DEPS] + [os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+
+
 def build_host(force=False, verbose=False):
-    src = os.path.join(HOST, "kf_host.cpp")
-    src2 = os.path.join(HOST, "kf_safetensors.cpp")
-    src3 = os.path.join(HOST, "kf_train.cpp")
-    src4 = os.path.join(HOST, "kf_train_qwen3.cpp")
-    deps = [src, src2, src3, src4, os.path.join(HOST, "kf_train_common.hpp"), os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"),
-            os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+    srcs, deps = _host_inputs()
     if force or _stale(LIB_HOST, deps):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", LIB_HOST, src, src2, src3, src4, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", LIB_HOST] + srcs + ["-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -81,15 +84,10 @@ def build_host_asan(verbose=False):
     files.  Written to libkf_host_asan.so; tests/test_host_asan_cpu.py runs the checkpoint tests under it (LD_PRELOAD of libasan, KF_HOST_LIB).
     Never for the GPU box: sanitizers run on the CPU build only."""
     out = os.path.join(HERE, "libkf_host_asan.so")
-    src = os.path.join(HOST, "kf_host.cpp")
-    src2 = os.path.join(HOST, "kf_safetensors.cpp")
-    src3 = os.path.join(HOST, "kf_train.cpp")
-    src4 = os.path.join(HOST, "kf_train_qwen3.cpp")
-    deps = [src, src2, src3, src4, os.path.join(HOST, "kf_train_common.hpp"), os.path.join(HOST, "kf_safetensors.hpp"), os.path.join(HOST, "kf_host.hpp"),
-            os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+    srcs, deps = _host_inputs()
     if _stale(out, deps):
         cmd = ["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17", "-fPIC", "-shared", "-Wall",
-               "-o", out, src, src2, src3, src4, "-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
+               "-o", out] + srcs + ["-L" + HERE, "-lkf_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -45,14 +45,14 @@ struct BlockActs {
     float *m1, *r1, *m2, *r2;
 };
 
-// TrainTensor, the registration, LinBack, the optimiser switch and the update loop are TrainerCore's (kf_train_common.hpp), shared with koifish::Qwen3Trainer
+// TrainTensor, the registration, LinBack, the optimiser switch, Update, Step and the head's forward / backward are TrainerCore's (kf_train_common.hpp), shared with
+// koifish::Qwen3Trainer
 struct GPT2Trainer : TrainerCore {
-    int C = 0, H = 0, NL = 0, V = 0, Vp = 0, B = 0, T = 0, hd = 0;
+    int C = 0, H = 0, NL = 0, hd = 0;
     std::vector<BlockActs> acts;
-    kf_bf16 *xf = nullptr, *hf = nullptr, *logits = nullptr, *dx = nullptr, *dh = nullptr, *dqkv = nullptr, *datt = nullptr, *d4 = nullptr;
-    float *mf = nullptr, *rf = nullptr, *losses = nullptr;
+    kf_bf16 *xf = nullptr, *dx = nullptr, *dqkv = nullptr, *datt = nullptr, *d4 = nullptr;
+    float *mf = nullptr, *rf = nullptr;
     void *sc_ln = nullptr, *sc_at = nullptr;
-    const int32_t* ids = nullptr;  // of the last Forward (the embedding backward scatters by them)
     // EOE: sections of LIS layers; branch b owns layers [b LIS, (b + 1) LIS); [l0, l1) is the active one.  One branch (LIS = NL): the whole depth
     int LIS = 0, branch = 0, l0 = 0, l1 = 0;
     enum { ENSEMBLE_AGGREGATION = 0, ENSEMBLE_BRANCH = 1 };  // Fuyou_params::ENSEMBLE: AGGREGATION; FUYOU_BEST and RANDOM_1 are BRANCH with the caller's choice of branch
@@ -66,7 +66,7 @@ struct GPT2Trainer : TrainerCore {
     TrainTensor& LnfW() { return params[(size_t)NL * PER_BLOCK + 2]; }
     TrainTensor& LnfB() { return params[(size_t)NL * PER_BLOCK + 3]; }
 
-    int Ready() const {
+    int Ready() const override {
         KF_TRY(ParamsReady());
         for (const BlockActs& a : acts)
             if (!a.x || !a.h1 || !a.qkv || !a.att || !a.x2 || !a.h2 || !a.f || !a.g || !a.m1 || !a.r1 || !a.m2 || !a.r2) return KF_INVALID_ARGS;
@@ -85,7 +85,7 @@ struct GPT2Trainer : TrainerCore {
 
     // TokenEmbed, NL x [LayerNorm, qkv, causal attention, proj + residual, LayerNorm, fc, GELU, proj2 + residual], LayerNorm, tied head, fused classifier:
     // per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
-    int Forward(const int32_t* d_ids, const int32_t* d_tgt) {
+    int Forward(const int32_t* d_ids, const int32_t* d_tgt) override {
         KF_TRY(Ready());
         if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
         KF_TRY(kf_embed_pos(ctx, Wte().p, C, Wpe().p, d_ids, B, T, C, Vp, acts[l0].x));
@@ -101,17 +101,11 @@ struct GPT2Trainer : TrainerCore {
             KF_TRY(Lin(P(l, PROJ2_W), a.g, l + 1 < l1 ? acts[l + 1].x : xf, &P(l, PROJ2_B), a.x2));
         }
         KF_TRY(LN(xf, LnfW(), LnfB(), hf, mf, rf));
-        KF_TRY(Lin(Wte(), hf, logits, nullptr, nullptr));
-        KF_TRY(kf_memset(ctx, losses, 0, (size_t)N * 4));
-        KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
-        ids = d_ids;
-        return KF_OK;
+        return HeadLoss(Wte(), d_ids, d_tgt);
     }
-    int Backward() {
+    int Backward() override {
         KF_TRY(Ready());
-        if (!ids) return KF_INVALID_ARGS;
-        if (Vp > V) KF_TRY(kf_memset2d(ctx, logits + V, (size_t)Vp * 2, 0, (size_t)(Vp - V) * 2, (size_t)N)); /* the padded vocabulary columns carry no gradient */
-        KF_TRY(LinBack(Wte(), logits, hf, dh, nullptr));
+        KF_TRY(HeadBack(Wte()));
         KF_TRY(kf_memset(ctx, dx, 0, (size_t)N * C * 2));
         KF_TRY(LNBack(dx, dh, xf, LnfW(), LnfB(), mf, rf));
         for (int l = l1 - 1; l >= l0; l--) {
@@ -127,11 +121,6 @@ struct GPT2Trainer : TrainerCore {
         }
         return kf_embed_backward(ctx, Wte().g, C, Wpe().g, dx, ids, B, T, C, Vp);
     }
-    int Update(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
-        KF_TRY(Ready());
-        return UpdateParams(lr, beta1, beta2, eps, wd, seed);
-    }
-
     int SetBranches(int layers_in_branch) {
         if (layers_in_branch == 0) layers_in_branch = NL;
         if (layers_in_branch < 0 || layers_in_branch > NL || NL % layers_in_branch) {
@@ -216,7 +205,9 @@ struct GPT2Trainer : TrainerCore {
 
 }  // namespace koifish
 
+using koifish::Core;
 using koifish::GPT2Trainer;
+static GPT2Trainer* Gpt2(void* h) { return static_cast<GPT2Trainer*>(Core(h)); }  // for the entries only this family has
 
 extern "C" {
 void* kfh_gpt2_create(kf_ctx* ctx, int C, int H, int NL, int V, int Vp, int B, int T) {
@@ -230,26 +221,26 @@ void* kfh_gpt2_create(kf_ctx* ctx, int C, int H, int NL, int V, int Vp, int B, i
     g->acts.resize(NL);
     g->LIS = NL, g->l1 = NL;
     memset(g->acts.data(), 0, sizeof(koifish::BlockActs) * NL);
-    return g;
+    return static_cast<koifish::TrainerCore*>(g);
 }
-void kfh_gpt2_destroy(void* h) { delete reinterpret_cast<GPT2Trainer*>(h); }
-int kfh_gpt2_n_params(void* h) { return (int)reinterpret_cast<GPT2Trainer*>(h)->params.size(); }
+void kfh_gpt2_destroy(void* h) { delete Core(h); }
+int kfh_gpt2_n_params(void* h) { return (int)Core(h)->params.size(); }
 // blob: the descriptor of what the forward reads (null: the tensor is not multiplied as a weight); requant != 0: kf_quantize(blob, master) after every update
 int kfh_gpt2_set_param(void* h, int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
-    return reinterpret_cast<GPT2Trainer*>(h)->SetParam(index, p, g, m, v, n, decay, blob, requant);
+    return Core(h)->SetParam(index, p, g, m, v, n, decay, blob, requant);
 }
 // "train_target": "gama" for one of a block's four weight matrices (index as kfh_gpt2_set_param): blob a PackedQ group storage; the parameter is ITS [ZERO nGroup][STEP nGroup]
 // slice (gama + ne0 + ne1), g / m / v are 2 nGroup bf16 each.  No weight decay, no re-quantisation, AdamW whatever the optimiser switch says.
 int kfh_gpt2_set_param_gama(void* h, int index, void* g, void* m, void* v, const kf_weight* blob) {
-    return reinterpret_cast<GPT2Trainer*>(h)->SetParamGama(index, g, m, v, blob);
+    return Core(h)->SetParamGama(index, g, m, v, blob);
 }
 // kf_gama_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_gama_backward_scratch_bytes of every gama tensor at the step's B * T rows
 int kfh_gpt2_set_gama_scratch(void* h, void* scratch, size_t bytes) {
-    return reinterpret_cast<GPT2Trainer*>(h)->SetGamaScratch(scratch, bytes);
+    return Core(h)->SetGamaScratch(scratch, bytes);
 }
 // ptrs: x h1 m1 r1 qkv att x2 h2 m2 r2 f g
 int kfh_gpt2_set_block_acts(void* h, int layer, void* const* ptrs) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
+    GPT2Trainer* t = Gpt2(h);
     if (layer < 0 || layer >= t->NL || !ptrs) return KF_INVALID_ARGS;
     koifish::BlockActs& a = t->acts[layer];
     a.x = (kf_bf16*)ptrs[0], a.h1 = (kf_bf16*)ptrs[1], a.m1 = (float*)ptrs[2], a.r1 = (float*)ptrs[3], a.qkv = (kf_bf16*)ptrs[4], a.att = (kf_bf16*)ptrs[5];
@@ -258,54 +249,51 @@ int kfh_gpt2_set_block_acts(void* h, int layer, void* const* ptrs) {
 }
 // ptrs: xf hf mf rf logits losses dx dh dqkv datt d4 scratch_linear_backward scratch_norm_backward scratch_attn_backward
 int kfh_gpt2_set_buffers(void* h, void* const* ptrs) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
+    GPT2Trainer* t = Gpt2(h);
     if (!ptrs) return KF_INVALID_ARGS;
     t->xf = (kf_bf16*)ptrs[0], t->hf = (kf_bf16*)ptrs[1], t->mf = (float*)ptrs[2], t->rf = (float*)ptrs[3], t->logits = (kf_bf16*)ptrs[4], t->losses = (float*)ptrs[5];
     t->dx = (kf_bf16*)ptrs[6], t->dh = (kf_bf16*)ptrs[7], t->dqkv = (kf_bf16*)ptrs[8], t->datt = (kf_bf16*)ptrs[9], t->d4 = (kf_bf16*)ptrs[10];
     t->sc_lin = ptrs[11], t->sc_ln = ptrs[12], t->sc_at = ptrs[13];
     return KF_OK;
 }
-int kfh_gpt2_forward(void* h, const int32_t* d_ids, const int32_t* d_tgt) { return reinterpret_cast<GPT2Trainer*>(h)->Forward(d_ids, d_tgt); }
-int kfh_gpt2_backward(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->Backward(); }
+int kfh_gpt2_forward(void* h, const int32_t* d_ids, const int32_t* d_tgt) { return Core(h)->Forward(d_ids, d_tgt); }
+int kfh_gpt2_backward(void* h) { return Core(h)->Backward(); }
 int kfh_gpt2_update(void* h, float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
-    return reinterpret_cast<GPT2Trainer*>(h)->Update(lr, beta1, beta2, eps, wd, seed);
+    return Core(h)->Update(lr, beta1, beta2, eps, wd, seed);
 }
 int kfh_gpt2_step(void* h, const int32_t* d_ids, const int32_t* d_tgt, float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
-    GPT2Trainer* t = reinterpret_cast<GPT2Trainer*>(h);
-    KF_TRY(t->Forward(d_ids, d_tgt));
-    KF_TRY(t->Backward());
-    return t->Update(lr, beta1, beta2, eps, wd, seed);
+    return Core(h)->Step(d_ids, d_tgt, lr, beta1, beta2, eps, wd, seed);
 }
 // method 0: AdamW on every tensor (the default); 1: Muon (the reference's default) on the Muon tensors, AdamW on the rest.  Call after every kfh_gpt2_set_param:
 // scratch (device memory, 256-byte aligned, the caller's) must hold kf_muon_scratch_bytes of the largest Muon tensor; KF_INVALID_ARGS otherwise, nothing changes.
 int kfh_gpt2_set_optimizer(void* h, int method, float lr_scale, float mui, float eps_muon, int tp_decay, void* scratch, size_t scratch_bytes) {
-    return reinterpret_cast<GPT2Trainer*>(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
+    return Core(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
 }
-long long kfh_gpt2_steps_taken(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->t; }
+long long kfh_gpt2_steps_taken(void* h) { return Core(h)->t; }
 // ---- EOE.  Every refusal leaves the trainer as it was; kfh_gpt2_last_error says why (a refusal of a kf_* entry underneath: kf_last_error).
 // layers_in_branch must divide NL (KF_INVALID_ARGS otherwise); 0 or NL: one branch, the whole depth -- the default.  Branch 0 becomes the active one.
 int kfh_gpt2_set_branches(void* h, int layers_in_branch) {
     koifish::g_train_err.clear();
-    return reinterpret_cast<GPT2Trainer*>(h)->SetBranches(layers_in_branch);
+    return Gpt2(h)->SetBranches(layers_in_branch);
 }
-int kfh_gpt2_n_branches(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->NBranch(); }
+int kfh_gpt2_n_branches(void* h) { return Gpt2(h)->NBranch(); }
 // forward / backward / update / step from here on run embed -> the layers of branch b -> lnf -> tied head and touch the shared tensors and that section's only
 int kfh_gpt2_set_active_branch(void* h, int b) {
     koifish::g_train_err.clear();
-    return reinterpret_cast<GPT2Trainer*>(h)->SetActive(b);
+    return Gpt2(h)->SetActive(b);
 }
-int kfh_gpt2_active_branch(void* h) { return reinterpret_cast<GPT2Trainer*>(h)->branch; }
+int kfh_gpt2_active_branch(void* h) { return Gpt2(h)->branch; }
 // for every branch f != head_branch, every layer offset j, each of qkv.w proj.w fc.w proj2.w: kf_evolve(follower master, head master, ..., seed + the follower tensor's
 // index in the registered order), then kf_quantize of the follower's blob.  Biases and norms are not touched (isWMAT).  A gama-trained matrix in ANY section:
 // KF_UNSUPPORTED_DATATYPE before anything is launched.  One branch: KF_OK, nothing is done.  algorithm: enum kf_evo_algorithm.
 int kfh_gpt2_evolve(void* h, int head_branch, int algorithm, float alpha, float social, float t_cross, uint32_t seed) {
     koifish::g_train_err.clear();
-    return reinterpret_cast<GPT2Trainer*>(h)->Evolve(head_branch, algorithm, alpha, social, t_cross, seed);
+    return Gpt2(h)->Evolve(head_branch, algorithm, alpha, social, t_cross, seed);
 }
 // mode 0 (AGGREGATION): every branch forward in index order, d_loss_out = their mean; mode 1 (BRANCH): the given branch alone.  d_loss_out: fp32 [B T], the caller's.
 int kfh_gpt2_eval(void* h, const int32_t* d_ids, const int32_t* d_tgt, int mode, int branch, float* d_loss_out) {
     koifish::g_train_err.clear();
-    return reinterpret_cast<GPT2Trainer*>(h)->Eval(d_ids, d_tgt, mode, branch, d_loss_out);
+    return Gpt2(h)->Eval(d_ids, d_tgt, mode, branch, d_loss_out);
 }
 const char* kfh_gpt2_last_error(void) { return koifish::g_train_err.c_str(); }
 }

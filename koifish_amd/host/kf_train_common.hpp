@@ -1,6 +1,8 @@
 // kf_train_common.hpp -- what the training-step sequencers of libkf_host.so share (koifish::GPT2Trainer, kf_train.cpp; koifish::Qwen3Trainer, kf_train_qwen3.cpp): the
 // table of trained tensors, its registration in both forms (shadow weights / "train_target": "gama"), SLP::Back for one matrix, the optimiser switch and the update loop
-// with its seed rule.  A trainer adds its own activations, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
+// with its seed rule -- and the step around them: Update, Step, the head product + fused classifier that ends every Forward (HeadLoss), the head's backward that starts
+// every Backward (HeadBack).  A trainer adds its own activations, Ready, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
+// The handle behind the C ABI of both families is the TrainerCore*: the entries the families share call through it (Core), a family's own cast down from it.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -21,7 +23,11 @@ struct TrainTensor {
 
 struct TrainerCore {
     kf_ctx* ctx = nullptr;
-    int N = 0;  // token rows of a step
+    int N = 0;  // token rows of a step: B sequences of T tokens
+    int V = 0, Vp = 0, B = 0, T = 0;  // the vocabulary and its padded row count
+    kf_bf16 *hf = nullptr, *logits = nullptr, *dh = nullptr;  // the final norm's output, the logits (their gradient after the classifier), the gradient of a norm's output
+    float* losses = nullptr;
+    const int32_t* ids = nullptr;  // of the last Forward (the embedding backward scatters by them)
     std::vector<TrainTensor> params;
     std::vector<char> wmat;  // per registered index: one of a layer's weight matrices (a Muon / gama candidate)
     void* sc_lin = nullptr;  // kf_linear_backward's scratch
@@ -37,6 +43,9 @@ struct TrainerCore {
 
     virtual ~TrainerCore() {}
     virtual bool InSection(size_t) const { return true; }  // Update leaves a tensor outside the active section alone (EOE)
+    virtual int Ready() const = 0;  // everything registered that a step reads (ParamsReady + the trainer's own activations and buffers)
+    virtual int Forward(const int32_t* d_ids, const int32_t* d_tgt) = 0;
+    virtual int Backward() = 0;
 
     // MUON_params_::isAdamW restated: a Muon tensor is one of a layer's weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape) and a
     // [ne0, ne1] bf16 master; embeddings, biases, norms, matrices with ne0 < ne1 and gama-trained tensors stay on AdamW
@@ -138,6 +147,31 @@ struct TrainerCore {
         }
         return KF_OK;
     }
+    int Update(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
+        KF_TRY(Ready());
+        return UpdateParams(lr, beta1, beta2, eps, wd, seed);
+    }
+    int Step(const int32_t* d_ids, const int32_t* d_tgt, float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
+        KF_TRY(Forward(d_ids, d_tgt));
+        KF_TRY(Backward());
+        return Update(lr, beta1, beta2, eps, wd, seed);
+    }
+    // the end of every Forward: logits = hf . head^T, then the fused classifier: per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
+    int HeadLoss(TrainTensor& head, const int32_t* d_ids, const int32_t* d_tgt) {
+        KF_TRY(kf_linear(ctx, &head.blob, hf, logits, nullptr, N, 1.0f, 0.0f, 0u, nullptr));
+        KF_TRY(kf_memset(ctx, losses, 0, (size_t)N * 4));
+        KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
+        ids = d_ids;
+        return KF_OK;
+    }
+    // the start of every Backward (after Ready): refused without a Forward; the head's weight gradient, and dh = the gradient of hf
+    int HeadBack(TrainTensor& head) {
+        if (!ids) return KF_INVALID_ARGS;
+        if (Vp > V) KF_TRY(kf_memset2d(ctx, logits + V, (size_t)Vp * 2, 0, (size_t)(Vp - V) * 2, (size_t)N)); /* the padded vocabulary columns carry no gradient */
+        return LinBack(head, logits, hf, dh, nullptr);
+    }
 };
+
+inline TrainerCore* Core(void* h) { return static_cast<TrainerCore*>(h); }  // the handle of kfh_gpt2_* / kfh_qwen3t_*
 
 }  // namespace koifish

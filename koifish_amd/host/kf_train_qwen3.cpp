@@ -35,16 +35,14 @@ struct Q3Acts {
 };
 
 struct Qwen3Trainer : TrainerCore {
-    int dim = 0, H = 0, KV = 0, hd = 0, ffn = 0, NL = 0, V = 0, Vp = 0, B = 0, T = 0, Cq = 0, Ck = 0, W = 0;
+    int dim = 0, H = 0, KV = 0, hd = 0, ffn = 0, NL = 0, Cq = 0, Ck = 0, W = 0;
     bool tied = true;
     float eps = 1e-6f;
     std::vector<Q3Acts> acts;
-    kf_bf16 *xf = nullptr, *hf = nullptr, *logits = nullptr, *dx = nullptr, *dh = nullptr, *dqkv = nullptr, *datt = nullptr, *dact = nullptr, *dgate = nullptr, *vtmp = nullptr,
-            *dqr = nullptr, *dkr = nullptr, *dvd = nullptr;
-    float *rf = nullptr, *losses = nullptr;
+    kf_bf16 *xf = nullptr, *dx = nullptr, *dqkv = nullptr, *datt = nullptr, *dact = nullptr, *dgate = nullptr, *vtmp = nullptr, *dqr = nullptr, *dkr = nullptr, *dvd = nullptr;
+    float* rf = nullptr;
     const float* table = nullptr;  // kf_rope_table_host layout, T positions
     void *sc_ln = nullptr, *sc_at = nullptr, *sc_qk = nullptr;
-    const int32_t* ids = nullptr;  // of the last Forward (the embedding backward scatters by them)
 
     enum { Q_W = 0, K_W, V_W, O_W, GATE_W, UP_W, DOWN_W, N1, N2, QN, KN, PER_LAYER };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_LAYER + k]; }
@@ -52,7 +50,7 @@ struct Qwen3Trainer : TrainerCore {
     TrainTensor& Nf() { return params[(size_t)NL * PER_LAYER + 1]; }
     TrainTensor& Head() { return params[(size_t)NL * PER_LAYER + (tied ? 0 : 2)]; }
 
-    int Ready() const {
+    int Ready() const override {
         KF_TRY(ParamsReady());
         for (const Q3Acts& a : acts)
             if (!a.x || !a.h1 || !a.qraw || !a.kraw || !a.qkv || !a.att || !a.x2 || !a.h2 || !a.gate || !a.up || !a.act || !a.r1 || !a.rq || !a.rk || !a.r2) return KF_INVALID_ARGS;
@@ -69,7 +67,7 @@ struct Qwen3Trainer : TrainerCore {
     }
 
     // per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
-    int Forward(const int32_t* d_ids, const int32_t* d_tgt) {
+    int Forward(const int32_t* d_ids, const int32_t* d_tgt) override {
         KF_TRY(Ready());
         if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
         KF_TRY(kf_embed_batch(ctx, &Wte().blob, d_ids, N, acts[0].x));
@@ -92,17 +90,11 @@ struct Qwen3Trainer : TrainerCore {
             KF_TRY(Lin(P(l, DOWN_W), a.act, l + 1 < NL ? acts[l + 1].x : xf, a.x2));
         }
         KF_TRY(Rms(xf, Nf(), hf, rf));
-        KF_TRY(Lin(Head(), hf, logits, nullptr));
-        KF_TRY(kf_memset(ctx, losses, 0, (size_t)N * 4));
-        KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
-        ids = d_ids;
-        return KF_OK;
+        return HeadLoss(Head(), d_ids, d_tgt);
     }
-    int Backward() {
+    int Backward() override {
         KF_TRY(Ready());
-        if (!ids) return KF_INVALID_ARGS;
-        if (Vp > V) KF_TRY(kf_memset2d(ctx, logits + V, (size_t)Vp * 2, 0, (size_t)(Vp - V) * 2, (size_t)N)); /* the padded vocabulary columns carry no gradient */
-        KF_TRY(LinBack(Head(), logits, hf, dh, nullptr));
+        KF_TRY(HeadBack(Head()));
         KF_TRY(kf_memset(ctx, dx, 0, (size_t)N * dim * 2));
         KF_TRY(RmsBack(dx, dh, xf, Nf(), rf));
         for (int l = NL - 1; l >= 0; l--) {
@@ -123,15 +115,13 @@ struct Qwen3Trainer : TrainerCore {
         }
         return kf_embed_backward(ctx, Wte().g, dim, nullptr, dx, ids, B, T, dim, Vp);
     }
-    int Update(float lr, double beta1, double beta2, float eps_, float wd, uint32_t seed) {
-        KF_TRY(Ready());
-        return UpdateParams(lr, beta1, beta2, eps_, wd, seed);
-    }
 };
 
 }  // namespace koifish
 
+using koifish::Core;
 using koifish::Qwen3Trainer;
+static Qwen3Trainer* Q3(void* h) { return static_cast<Qwen3Trainer*>(Core(h)); }  // for the entries only this family has
 
 extern "C" {
 // V: the vocabulary; Vp >= V its padded row count (a multiple of 64 for kf_linear_backward); B sequences of T tokens per step; tied != 0: the head is wte
@@ -151,17 +141,17 @@ void* kfh_qwen3t_create(kf_ctx* ctx, int dim, int n_layer, int n_head, int n_kv,
         for (int k = Qwen3Trainer::Q_W; k <= Qwen3Trainer::DOWN_W; k++) g->wmat[(size_t)l * Qwen3Trainer::PER_LAYER + k] = 1;
     g->acts.resize(n_layer);
     memset(g->acts.data(), 0, sizeof(koifish::Q3Acts) * n_layer);
-    return g;
+    return static_cast<koifish::TrainerCore*>(g);
 }
-void kfh_qwen3t_destroy(void* h) { delete reinterpret_cast<Qwen3Trainer*>(h); }
-int kfh_qwen3t_n_params(void* h) { return (int)reinterpret_cast<Qwen3Trainer*>(h)->params.size(); }
+void kfh_qwen3t_destroy(void* h) { delete Core(h); }
+int kfh_qwen3t_n_params(void* h) { return (int)Core(h)->params.size(); }
 // as kfh_gpt2_set_param
 int kfh_qwen3t_set_param(void* h, int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
-    return reinterpret_cast<Qwen3Trainer*>(h)->SetParam(index, p, g, m, v, n, decay, blob, requant);
+    return Core(h)->SetParam(index, p, g, m, v, n, decay, blob, requant);
 }
 // "train_target": "gama" for one of a layer's seven matrices, with the refusals of kfh_gpt2_set_param_gama; a context that holds a dequant arena is refused here already
 int kfh_qwen3t_set_param_gama(void* h, int index, void* g, void* m, void* v, const kf_weight* blob) {
-    Qwen3Trainer* t = reinterpret_cast<Qwen3Trainer*>(h);
+    Qwen3Trainer* t = Q3(h);
     koifish::g_q3t_err.clear();
     if (kf_dequant_arena_bytes(t->ctx) > 0) {
         koifish::g_q3t_err = "kfh_qwen3t_set_param_gama: the context holds a dequant arena (kf_set_dequant_arena): its resident bf16 copies of a gama-trained matrix would go stale "
@@ -172,10 +162,10 @@ int kfh_qwen3t_set_param_gama(void* h, int index, void* g, void* m, void* v, con
     if (rc != KF_OK) koifish::g_q3t_err = "kfh_qwen3t_set_param_gama: index " + std::to_string(index) + " is no layer matrix, a null pointer, or a blob that is no KF_Q4 / KF_T_SIGN / KF_BOOL1 group storage";
     return rc;
 }
-int kfh_qwen3t_set_gama_scratch(void* h, void* scratch, size_t bytes) { return reinterpret_cast<Qwen3Trainer*>(h)->SetGamaScratch(scratch, bytes); }
+int kfh_qwen3t_set_gama_scratch(void* h, void* scratch, size_t bytes) { return Core(h)->SetGamaScratch(scratch, bytes); }
 // ptrs: x h1 r1 qraw kraw qkv rq rk att x2 h2 r2 gate up act
 int kfh_qwen3t_set_layer_acts(void* h, int layer, void* const* ptrs) {
-    Qwen3Trainer* t = reinterpret_cast<Qwen3Trainer*>(h);
+    Qwen3Trainer* t = Q3(h);
     if (layer < 0 || layer >= t->NL || !ptrs) return KF_INVALID_ARGS;
     koifish::Q3Acts& a = t->acts[layer];
     a.x = (kf_bf16*)ptrs[0], a.h1 = (kf_bf16*)ptrs[1], a.r1 = (float*)ptrs[2], a.qraw = (kf_bf16*)ptrs[3], a.kraw = (kf_bf16*)ptrs[4], a.qkv = (kf_bf16*)ptrs[5];
@@ -186,7 +176,7 @@ int kfh_qwen3t_set_layer_acts(void* h, int layer, void* const* ptrs) {
 // ptrs: xf hf rf logits losses dx dh dqkv datt dact dgate vtmp dq_raw dk_raw dv_dense rope_table scratch_linear_backward scratch_norm_backward scratch_attn_backward
 // scratch_qknorm_rope_backward
 int kfh_qwen3t_set_buffers(void* h, void* const* ptrs) {
-    Qwen3Trainer* t = reinterpret_cast<Qwen3Trainer*>(h);
+    Qwen3Trainer* t = Q3(h);
     if (!ptrs) return KF_INVALID_ARGS;
     t->xf = (kf_bf16*)ptrs[0], t->hf = (kf_bf16*)ptrs[1], t->rf = (float*)ptrs[2], t->logits = (kf_bf16*)ptrs[3], t->losses = (float*)ptrs[4];
     t->dx = (kf_bf16*)ptrs[5], t->dh = (kf_bf16*)ptrs[6], t->dqkv = (kf_bf16*)ptrs[7], t->datt = (kf_bf16*)ptrs[8], t->dact = (kf_bf16*)ptrs[9], t->dgate = (kf_bf16*)ptrs[10];
@@ -194,21 +184,18 @@ int kfh_qwen3t_set_buffers(void* h, void* const* ptrs) {
     t->sc_lin = ptrs[16], t->sc_ln = ptrs[17], t->sc_at = ptrs[18], t->sc_qk = ptrs[19];
     return KF_OK;
 }
-int kfh_qwen3t_forward(void* h, const int32_t* d_ids, const int32_t* d_tgt) { return reinterpret_cast<Qwen3Trainer*>(h)->Forward(d_ids, d_tgt); }
-int kfh_qwen3t_backward(void* h) { return reinterpret_cast<Qwen3Trainer*>(h)->Backward(); }
+int kfh_qwen3t_forward(void* h, const int32_t* d_ids, const int32_t* d_tgt) { return Core(h)->Forward(d_ids, d_tgt); }
+int kfh_qwen3t_backward(void* h) { return Core(h)->Backward(); }
 int kfh_qwen3t_update(void* h, float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
-    return reinterpret_cast<Qwen3Trainer*>(h)->Update(lr, beta1, beta2, eps, wd, seed);
+    return Core(h)->Update(lr, beta1, beta2, eps, wd, seed);
 }
 int kfh_qwen3t_step(void* h, const int32_t* d_ids, const int32_t* d_tgt, float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
-    Qwen3Trainer* t = reinterpret_cast<Qwen3Trainer*>(h);
-    KF_TRY(t->Forward(d_ids, d_tgt));
-    KF_TRY(t->Backward());
-    return t->Update(lr, beta1, beta2, eps, wd, seed);
+    return Core(h)->Step(d_ids, d_tgt, lr, beta1, beta2, eps, wd, seed);
 }
 // as kfh_gpt2_set_optimizer
 int kfh_qwen3t_set_optimizer(void* h, int method, float lr_scale, float mui, float eps_muon, int tp_decay, void* scratch, size_t scratch_bytes) {
-    return reinterpret_cast<Qwen3Trainer*>(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
+    return Core(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
 }
-long long kfh_qwen3t_steps_taken(void* h) { return reinterpret_cast<Qwen3Trainer*>(h)->t; }
+long long kfh_qwen3t_steps_taken(void* h) { return Core(h)->t; }
 const char* kfh_qwen3t_last_error(void) { return koifish::g_q3t_err.c_str(); }
 }

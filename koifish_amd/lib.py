@@ -46,6 +46,21 @@ class Weight(C.Structure):
                 ("lGroup", C.c_int32), ("qMin", C.c_int32), ("qMax", C.c_int32), ("qBias", C.c_int32), ("qzeros", C.c_void_p), ("qscales", C.c_void_p), ("quant", C.c_int32), ("reserved_", C.c_int32)]
 
 
+# the entries of libkf_host.so that kfh_gpt2_* and kfh_qwen3t_* have with one signature: (name, argtypes, restype)
+_TRAINER_ENTRIES = [
+    ("destroy", [C.c_void_p], None),
+    ("n_params", [C.c_void_p], C.c_int),
+    ("set_param", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int], C.c_int),
+    ("set_param_gama", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("set_gama_scratch", [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int),
+    ("set_buffers", [C.c_void_p, C.c_void_p], C.c_int),
+    ("forward", [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    ("backward", [C.c_void_p], C.c_int),
+    ("update", [C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32], C.c_int),
+    ("step", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32], C.c_int),
+    ("set_optimizer", [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
+    ("steps_taken", [C.c_void_p], C.c_longlong),
+]
 _libs = None
 
 
@@ -228,24 +243,18 @@ def load():
         hip.kf_set_canonical.argtypes = [C.c_void_p, C.c_int]
         hip.kf_get_canonical.argtypes = [C.c_void_p]
         hip.kf_engine_destroy.argtypes = [C.c_void_p]
-        # the config-3 training step's sequencer (koifish::GPT2Trainer, host/kf_train.cpp)
+        # the training steps' sequencers: koifish::GPT2Trainer (host/kf_train.cpp, kfh_gpt2_*) and koifish::Qwen3Trainer (host/kf_train_qwen3.cpp, kfh_qwen3t_*), the
+        # entries both families have from one table (_TRAINER_ENTRIES); getattr raises on a name the library lacks
+        for fam, acts in (("gpt2", "set_block_acts"), ("qwen3t", "set_layer_acts")):
+            for name, argtypes, restype in _TRAINER_ENTRIES + [(acts, [C.c_void_p, C.c_int, C.c_void_p], C.c_int)]:
+                f = getattr(host, "kfh_%s_%s" % (fam, name))
+                f.argtypes, f.restype = argtypes, restype
         host.kfh_gpt2_create.restype = C.c_void_p
         host.kfh_gpt2_create.argtypes = [C.c_void_p] + [C.c_int] * 7
-        host.kfh_gpt2_destroy.restype = None
-        host.kfh_gpt2_destroy.argtypes = [C.c_void_p]
-        host.kfh_gpt2_n_params.argtypes = [C.c_void_p]
-        host.kfh_gpt2_set_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int]
-        host.kfh_gpt2_set_param_gama.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        host.kfh_gpt2_set_gama_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        host.kfh_gpt2_set_block_acts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        host.kfh_gpt2_set_buffers.argtypes = [C.c_void_p, C.c_void_p]
-        host.kfh_gpt2_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        host.kfh_gpt2_backward.argtypes = [C.c_void_p]
-        host.kfh_gpt2_update.argtypes = [C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
-        host.kfh_gpt2_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
-        host.kfh_gpt2_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
-        host.kfh_gpt2_steps_taken.restype = C.c_longlong
-        host.kfh_gpt2_steps_taken.argtypes = [C.c_void_p]
+        host.kfh_gpt2_last_error.restype = C.c_char_p
+        host.kfh_qwen3t_create.restype = C.c_void_p
+        host.kfh_qwen3t_create.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_float, C.c_int]
+        host.kfh_qwen3t_last_error.restype = C.c_char_p
         # EOE: layer-section branches, the evolve step over the swarm, the ensemble evaluation
         host.kfh_gpt2_set_branches.argtypes = [C.c_void_p, C.c_int]
         host.kfh_gpt2_n_branches.argtypes = [C.c_void_p]
@@ -253,26 +262,6 @@ def load():
         host.kfh_gpt2_active_branch.argtypes = [C.c_void_p]
         host.kfh_gpt2_evolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32]
         host.kfh_gpt2_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        host.kfh_gpt2_last_error.restype = C.c_char_p
-        # the Qwen3 training step's sequencer (koifish::Qwen3Trainer, host/kf_train_qwen3.cpp)
-        host.kfh_qwen3t_create.restype = C.c_void_p
-        host.kfh_qwen3t_create.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_float, C.c_int]
-        host.kfh_qwen3t_destroy.restype = None
-        host.kfh_qwen3t_destroy.argtypes = [C.c_void_p]
-        host.kfh_qwen3t_n_params.argtypes = [C.c_void_p]
-        host.kfh_qwen3t_set_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int]
-        host.kfh_qwen3t_set_param_gama.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        host.kfh_qwen3t_set_gama_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        host.kfh_qwen3t_set_layer_acts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        host.kfh_qwen3t_set_buffers.argtypes = [C.c_void_p, C.c_void_p]
-        host.kfh_qwen3t_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        host.kfh_qwen3t_backward.argtypes = [C.c_void_p]
-        host.kfh_qwen3t_update.argtypes = [C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
-        host.kfh_qwen3t_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32]
-        host.kfh_qwen3t_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]
-        host.kfh_qwen3t_steps_taken.restype = C.c_longlong
-        host.kfh_qwen3t_steps_taken.argtypes = [C.c_void_p]
-        host.kfh_qwen3t_last_error.restype = C.c_char_p
         # eight decoders, one per XCD (kf_xengine_*): handles are koifish::XcdReplicas* of the host library
         host.kfh_xr_create.restype = C.c_void_p
         host.kfh_xr_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]

@@ -23,7 +23,8 @@ and nothing in them is a torch op (the embedding gather + add is kf_embed_pos, t
 Used by tests/test_gpu_train_step.py (a 2-layer toy, two consecutive steps against the oracle) and by bench.py's config3 leg (full size).
 
 Qwen3Step, further down, is the same for the Qwen3 family (koifish::Qwen3Trainer, koifish_amd/host/kf_train_qwen3.cpp); the two trainers share the tensor table, SLP::Back,
-the optimiser switch and the update loop (koifish_amd/host/kf_train_common.hpp)."""
+the optimiser switch, the update loop and the step around them (koifish_amd/host/kf_train_common.hpp), and the two classes here share _TrainStep: the registration of
+tensors and buffers with the trainer and every method that is one call into it."""
 import ctypes as C
 
 import torch
@@ -34,87 +35,88 @@ MATS = ("qkv", "proj", "fc", "proj2")
 GAMA_TYPES = (L.Q4, L.T_SIGN, L.BOOL1)   # the PackedQ group storages kf_gama_backward serves
 
 
-class GPT2Step:
-    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None, train_target="weights", layers_in_branch=None):
-        """masters: optional dict of host-provided bf16 torch tensors (tests hand the same numbers to the reference): 'wte' [Vp, C], 'wpe' [T, C], 'lnf' (w, b), 'blocks':
-        list of dicts {mat: (W [out, in], b [out])} + 'ln' (w1, b1, w2, b2).  Otherwise N(0, w_std) draws on the device.
-        train_target: "weights" (the default: bf16 masters, re-quantised after every update) or "gama": every block matrix whose storage is a PackedQ group type (GAMA_TYPES)
-        is quantised once from its initial draw, which is then dropped; its entry of self.params has p = the blob's [ZERO][STEP] slice and g, m, v of 2 nGroup elements, no
-        weight decay.  f8e5m2 / bf16 matrices, biases, norms and embeddings train as under "weights".  Refused with a reason: a matrix kf_gama_backward does not take
-        (in-features no multiple of 128), and a context that holds a dequant arena (kf_set_dequant_arena: its resident copies would go stale with every update).
-        layers_in_branch: None, 0 or NL: one branch, the whole depth (the default); otherwise a divisor of NL: NL / layers_in_branch branches, branch 0 active."""
+def _align256(ptr):
+    """a scratch the ABI wants 256-byte aligned is allocated 256 bytes longer and handed over from here"""
+    return (ptr + 255) & ~255
+
+
+class _TrainStep:
+    """What GPT2Step and Qwen3Step share.  A subclass's constructor draws or takes the tensors in its trainer's order (_reg / _reg_matrix), allocates the activations
+    (self.A) and buffers, creates its trainer (self.h) and hands everything over with _attach; the step itself is the entries kfh_<_family>_* of libkf_host.so."""
+    _family = None         # "gpt2" / "qwen3t": the entries are kfh_<_family>_<name>
+    _acts_entry = None     # the entry that takes one layer's kept activations, and the keys of a self.A dict in the order it takes them
+    _act_keys = ()
+    _layer_prefix = None   # what the name of a layer's tensor starts with ("h3.fc.w", "l3.gate.w")
+    _layer_noun = None     # what set_optimizer's refusal calls a layer matrix
+    _reason_codes = None   # the return codes whose reason is in kfh_<_family>_last_error; None: every code
+    optimizer = "adamw"
+
+    def _begin(self, ctx, train_target, seed):
+        """checks train_target before anything touches ctx; returns the device generator of the initial draws"""
         if train_target not in ("weights", "gama"):
             raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
-        self.train_target = train_target
-        self.ctx, self.C, self.H, self.NL, self.V, self.Vp, self.B, self.T = ctx, C_, H, NL, V, Vp, B, T
-        self.hd, self.N = C_ // H, B * T
-        self.types = dict(qkv=L.F8E5M2, proj=L.F8E5M2, fc=L.Q4, proj2=L.Q4) if types is None else dict(types)
-        dev, bf = ctx.device, torch.bfloat16
-        g = torch.Generator(device=dev)
-        g.manual_seed(seed)
-        z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
-        rnd = lambda *s, std=w_std: (torch.randn(*s, device=dev, generator=g) * std).to(bf)
-        shapes = dict(qkv=(3 * C_, C_), proj=(C_, C_), fc=(4 * C_, C_), proj2=(C_, 4 * C_))
+        self.train_target, self.ctx = train_target, ctx
         self.params = []   # every trained tensor: dict(name, p (bf16 master), g (bf16 gradient), m, v (bf16 moments), wd (bool), blob (DevWeight or None), type)
-        self.blocks = []
+        g = torch.Generator(device=ctx.device)
+        g.manual_seed(seed)
+        return g
 
-        def reg(name, p, wd, type_=None):
-            e = dict(name=name, p=p.contiguous(), g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=wd, blob=None, type=type_)
-            if type_ is not None:
-                e["blob"] = ctx.quantize(e["p"], type_)
-                if type_ == L.BF16:
-                    e["p"] = e["blob"].blob.view(bf).view(p.shape)   # a bf16 "blob" IS the master (the tied head): updated in place, nothing to re-quantise
-            self.params.append(e)
-            return e
+    def _entry(self, name):
+        return getattr(self.ctx.host, "kfh_%s_%s" % (self._family, name))
 
-        def reg_gama(name, W, type_):
-            blob = ctx.quantize(W.contiguous(), type_)   # the draw is dropped: the packed integers are the weight from here on
-            p = blob.gama_slice()
-            e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=False, blob=blob, type=type_, gama=True)
-            self.params.append(e)
-            return e
-        for l in range(NL):
-            mb = masters["blocks"][l] if masters else None
-            blk = {}
-            for k in MATS:
-                W = mb[k][0].to(dev) if mb else rnd(*shapes[k])
-                b = mb[k][1].to(dev) if mb else z(shapes[k][0])
-                if train_target == "gama" and self.types[k] in GAMA_TYPES:
-                    blk[k] = reg_gama("h%d.%s.w" % (l, k), W, self.types[k])
-                else:
-                    blk[k] = reg("h%d.%s.w" % (l, k), W, True, self.types[k])
-                blk[k + "_b"] = reg("h%d.%s.b" % (l, k), b, False)
-            ln = [t.to(dev) for t in mb["ln"]] if mb else [torch.ones(C_, device=dev, dtype=bf), z(C_), torch.ones(C_, device=dev, dtype=bf), z(C_)]
-            for i, nm in enumerate(("ln1.w", "ln1.b", "ln2.w", "ln2.b")):
-                blk[nm] = reg("h%d.%s" % (l, nm), ln[i], False)
-            self.blocks.append(blk)
-        wte = masters["wte"].to(dev) if masters else torch.cat([rnd(V, C_), z(Vp - V, C_)])
-        self.wte = reg("wte", wte, True, L.BF16)
-        self.wpe = reg("wpe", masters["wpe"].to(dev) if masters else rnd(T, C_, std=w_std / 2), False)
-        lnf = [t.to(dev) for t in masters["lnf"]] if masters else [torch.ones(C_, device=dev, dtype=bf), z(C_)]
-        self.lnf_w, self.lnf_b = reg("lnf.w", lnf[0], False), reg("lnf.b", lnf[1], False)
-        # activations of one step, all kept
-        N = self.N
-        self.A = [dict(x=z(N, C_), h1=z(N, C_), m1=z(N, dt=torch.float32), r1=z(N, dt=torch.float32), qkv=z(N, 3 * C_), att=z(N, C_), x2=z(N, C_), h2=z(N, C_),
-                       m2=z(N, dt=torch.float32), r2=z(N, dt=torch.float32), f=z(N, 4 * C_), g=z(N, 4 * C_)) for _ in range(NL)]
-        self.xf, self.hf, self.mf, self.rf = z(N, C_), z(N, C_), z(N, dt=torch.float32), z(N, dt=torch.float32)
-        self.qc, self.logits, self.losses = z(N, C_), z(N, Vp), z(N, dt=torch.float32)
-        self.dx, self.dh, self.dqkv, self.datt, self.d4 = z(N, C_), z(N, C_), z(N, 3 * C_), z(N, C_), z(N, 4 * C_)
-        hip = ctx.hip
-        for k in MATS:
-            ctx.linear_scratch(self.blocks[0][k]["blob"], N)
-        nb = max(hip.kf_linear_backward_scratch_bytes(oc, ic, N) for oc, ic in list(shapes.values()) + [(Vp, C_)])
-        self._sc_lin = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-        self._sp_lin = (self._sc_lin.data_ptr() + 255) & ~255
-        self._sc_ln = torch.empty(hip.kf_norm_backward_scratch_bytes(N, C_, 1) // 8 + 1, dtype=torch.float64, device=dev)
-        self._sc_at = torch.empty(hip.kf_attn_backward_scratch_bytes(T, H, B) // 4 + 1, dtype=torch.float32, device=dev)
+    def _call(self, name, *args, check=L.check):
+        """kfh_<family>_<name>(self.h, ...), its return code through check"""
+        check(self._entry(name)(self.h, *args), "kfh_%s_%s" % (self._family, name))
 
-        # the step's sequencer: koifish::GPT2Trainer of libkf_host.so (koifish_amd/host/kf_train.cpp) over the buffers above -- every tensor registered once
-        host = ctx.host
-        self.h = host.kfh_gpt2_create(ctx.h, C_, H, NL, V, Vp, B, T)
-        if not self.h:
-            raise RuntimeError("kfh_gpt2_create refused the shape")
-        assert host.kfh_gpt2_n_params(self.h) == len(self.params)
+    def _check_host(self, rc, what):
+        """a refusal of the trainer itself carries its reason in kfh_<family>_last_error; one of a kf_* entry underneath in kf_last_error"""
+        if rc != 0:
+            own = self._reason_codes is None or rc in self._reason_codes
+            why = self._entry("last_error")().decode() if own else ""
+            raise L.KFError("%s failed: code %d: %s" % (what, rc, why or self.ctx.hip.kf_last_error().decode()))
+
+    def _check_arena(self):
+        """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
+        if self.train_target == "gama" and self.ctx.hip.kf_dequant_arena_bytes(self.ctx.h):
+            raise L.KFError("train_target='gama' on a context with a dequant arena (kf_set_dequant_arena): the resident bf16 copies of the trained matrices would go stale "
+                            "with every update -- switch the arena off (kf_set_dequant_arena(ctx, NULL, 0)) for training")
+
+    # ---- the tensors, appended to self.params in the trainer's order
+    def _reg(self, name, p, wd, type_=None):
+        e = dict(name=name, p=p.contiguous(), g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=wd, blob=None, type=type_)
+        if type_ is not None:
+            e["blob"] = self.ctx.quantize(e["p"], type_)
+            if type_ == L.BF16:
+                e["p"] = e["blob"].blob.view(torch.bfloat16).view(p.shape)   # a bf16 "blob" IS the master (the tied head): updated in place, nothing to re-quantise
+        self.params.append(e)
+        return e
+
+    def _reg_gama(self, name, W, type_):
+        blob = self.ctx.quantize(W.contiguous(), type_)   # the draw is dropped: the packed integers are the weight from here on
+        p = blob.gama_slice()
+        e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=False, blob=blob, type=type_, gama=True)
+        self.params.append(e)
+        return e
+
+    def _reg_matrix(self, name, W, type_):
+        """one of a layer's weight matrices: its (zero, step) pairs under train_target="gama" when its storage is a PackedQ group type, its weights (decayed) otherwise"""
+        if self.train_target == "gama" and type_ in GAMA_TYPES:
+            return self._reg_gama(name, W, type_)
+        return self._reg(name, W, True, type_)
+
+    def _alloc_linear_scratch(self, layer, shapes, dim):
+        """kf_linear's scratch for one layer's matrices (the context's), kf_linear_backward's for the largest of the matrix shapes and the [Vp, dim] head"""
+        for k in shapes:
+            self.ctx.linear_scratch(layer[k]["blob"], self.N)
+        nb = max(self.ctx.hip.kf_linear_backward_scratch_bytes(oc, ic, self.N) for oc, ic in list(shapes.values()) + [(self.Vp, dim)])
+        self._sc_lin = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
+        self._sp_lin = _align256(self._sc_lin.data_ptr())
+
+    def _attach(self, bufs, scratch):
+        """every tensor registered once with the trainer just created: self.params in order, the activations of every layer (self.A), then the buffer table: bufs (torch
+        tensors, in the order kfh_<family>_set_buffers takes them), kf_linear_backward's scratch, the other scratch tensors"""
+        hip, N = self.ctx.hip, self.N
+        assert self._entry("n_params")(self.h) == len(self.params)
         gama = [e for e in self.params if e.get("gama")]
         if gama:
             self._check_arena()
@@ -123,29 +125,139 @@ class GPT2Step:
                 bad = gama[need.index(0)]
                 raise L.KFError("train_target='gama': kf_gama_backward does not take %s [%d, %d] at %d rows (in-features a multiple of 128, out-features and rows multiples of 64)"
                                 % (bad["name"], bad["blob"].ne0, bad["blob"].ne1, N))
-            self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=dev)
-            L.check(host.kfh_gpt2_set_gama_scratch(self.h, (self._sc_gama.data_ptr() + 255) & ~255, max(need)), "kfh_gpt2_set_gama_scratch")
+            self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=self.ctx.device)
+            self._call("set_gama_scratch", _align256(self._sc_gama.data_ptr()), max(need))
         for i, e in enumerate(self.params):
             d = e["blob"].desc() if e["blob"] is not None else None
             if e.get("gama"):
-                L.check(host.kfh_gpt2_set_param_gama(self.h, i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d)), "kfh_gpt2_set_param_gama")
+                self._call("set_param_gama", i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d), check=self._check_host)
                 continue
-            L.check(host.kfh_gpt2_set_param(self.h, i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["p"].numel(), int(e["wd"]),
-                                            C.byref(d) if d is not None else None, int(e["type"] is not None and e["type"] != L.BF16)), "kfh_gpt2_set_param")
+            self._call("set_param", i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["p"].numel(), int(e["wd"]),
+                       C.byref(d) if d is not None else None, int(e["type"] is not None and e["type"] != L.BF16))
         for l, a in enumerate(self.A):
-            arr = (C.c_void_p * 12)(*[a[k].data_ptr() for k in ("x", "h1", "m1", "r1", "qkv", "att", "x2", "h2", "m2", "r2", "f", "g")])
-            L.check(host.kfh_gpt2_set_block_acts(self.h, l, arr), "kfh_gpt2_set_block_acts")
-        arr = (C.c_void_p * 14)(*([t_.data_ptr() for t_ in (self.xf, self.hf, self.mf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.d4)]
-                                  + [self._sp_lin, self._sc_ln.data_ptr(), self._sc_at.data_ptr()]))
-        L.check(host.kfh_gpt2_set_buffers(self.h, arr), "kfh_gpt2_set_buffers")
-        if layers_in_branch:
-            self._check_host(host.kfh_gpt2_set_branches(self.h, int(layers_in_branch)), "kfh_gpt2_set_branches")
+            self._call(self._acts_entry, l, (C.c_void_p * len(self._act_keys))(*[a[k].data_ptr() for k in self._act_keys]))
+        ptrs = [t_.data_ptr() for t_ in bufs] + [self._sp_lin] + [t_.data_ptr() for t_ in scratch]
+        self._call("set_buffers", (C.c_void_p * len(ptrs))(*ptrs))
 
-    def _check_host(self, rc, what):
-        """a refusal of the trainer itself carries its reason in kfh_gpt2_last_error; one of a kf_* entry underneath in kf_last_error"""
-        if rc != 0:
-            why = self.ctx.host.kfh_gpt2_last_error().decode() if rc in (-20, -1000) else ""
-            raise L.KFError("%s failed: code %d: %s" % (what, rc, why or self.ctx.hip.kf_last_error().decode()))
+    def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
+        """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a layer's weight matrices with ne0 >= ne1 and a bf16 master (GPT-2: qkv, proj,
+        fc; Qwen3 at its shapes: q, k, v, gate, up) take SGD-momentum + five Newton-Schulz steps (kf_muon: lr x lr_scale, weight decay by tp_decay as Pipe.cpp:23-37, mG =
+        the tensor's m buffer); the other matrices (proj2; o, down), the embeddings, the head, biases and norms keep kf_adamw -- and so does every gama-trained tensor
+        (train_target="gama"): its parameter is a [2 nGroup] slice, never a matrix for kf_muon.  Owns the scratch, sized for the largest Muon tensor."""
+        if method not in ("adamw", "muon"):
+            raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
+        sp, nb = None, 0
+        if method == "muon":
+            shapes = [tuple(e["p"].shape) for e in self.params if e["blob"] is not None and not e.get("gama") and e["name"].startswith(self._layer_prefix)
+                      and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
+            nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
+            if nb == 0:
+                raise L.KFError("muon: a %s matrix has a dimension that is no multiple of 64" % self._layer_noun)
+            self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
+            sp = _align256(self._sc_muon.data_ptr())
+        self._call("set_optimizer", int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb)
+        self.optimizer = method
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._entry("destroy")(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @property
+    def t(self):
+        """optimizer steps taken"""
+        return int(self._entry("steps_taken")(self.h))
+
+    # ---- the step: sequenced by the host library; Python passes two device pointers and the hyper-parameters
+    def forward(self, ids, tgt):
+        """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
+        self._ids = ids   # kept alive: the backward reads them
+        self._check_arena()
+        self._call("forward", ids.data_ptr(), tgt.data_ptr())
+
+    def backward(self):
+        self._call("backward")
+
+    def _after_update(self):
+        """what a subclass does once the weights have changed"""
+
+    def update(self, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
+        """AdamW on every tensor (its own master, moments and gradient; seeded stochastic rounding: seed + 7919 t + the tensor's index, as one seed per launch in the
+        reference), then the re-quantisation of every quantised matrix from its updated master.  kf_adamw zeroes the gradients it has consumed."""
+        self._call("update", lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF)
+        self._after_update()
+
+    def step(self, ids, tgt, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
+        """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
+        self._ids = ids
+        self._check_arena()
+        self._call("step", ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF)
+        self._after_update()
+
+    def n_params(self):
+        return sum(e["p"].numel() for e in self.params)
+
+
+class GPT2Step(_TrainStep):
+    _family, _acts_entry, _layer_prefix, _layer_noun = "gpt2", "set_block_acts", "h", "hidden"
+    _act_keys = ("x", "h1", "m1", "r1", "qkv", "att", "x2", "h2", "m2", "r2", "f", "g")
+    _reason_codes = (-20, -1000)   # kfh_gpt2_last_error is cleared by the EOE entries only: for any other code it could hold a stale reason
+
+    def __init__(self, ctx, C_, H, NL, V, Vp, B, T, types=None, seed=0, w_std=0.02, masters=None, train_target="weights", layers_in_branch=None):
+        """masters: optional dict of host-provided bf16 torch tensors (tests hand the same numbers to the reference): 'wte' [Vp, C], 'wpe' [T, C], 'lnf' (w, b), 'blocks':
+        list of dicts {mat: (W [out, in], b [out])} + 'ln' (w1, b1, w2, b2).  Otherwise N(0, w_std) draws on the device.
+        train_target: "weights" (the default: bf16 masters, re-quantised after every update) or "gama": every block matrix whose storage is a PackedQ group type (GAMA_TYPES)
+        is quantised once from its initial draw, which is then dropped; its entry of self.params has p = the blob's [ZERO][STEP] slice and g, m, v of 2 nGroup elements, no
+        weight decay.  f8e5m2 / bf16 matrices, biases, norms and embeddings train as under "weights".  Refused with a reason: a matrix kf_gama_backward does not take
+        (in-features no multiple of 128), and a context that holds a dequant arena (kf_set_dequant_arena: its resident copies would go stale with every update).
+        layers_in_branch: None, 0 or NL: one branch, the whole depth (the default); otherwise a divisor of NL: NL / layers_in_branch branches, branch 0 active."""
+        g = self._begin(ctx, train_target, seed)
+        self.C, self.H, self.NL, self.V, self.Vp, self.B, self.T = C_, H, NL, V, Vp, B, T
+        self.hd, self.N = C_ // H, B * T
+        self.types = dict(qkv=L.F8E5M2, proj=L.F8E5M2, fc=L.Q4, proj2=L.Q4) if types is None else dict(types)
+        dev, bf = ctx.device, torch.bfloat16
+        z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
+        rnd = lambda *s, std=w_std: (torch.randn(*s, device=dev, generator=g) * std).to(bf)
+        shapes = dict(qkv=(3 * C_, C_), proj=(C_, C_), fc=(4 * C_, C_), proj2=(C_, 4 * C_))
+        self.blocks = []
+        for l in range(NL):
+            mb = masters["blocks"][l] if masters else None
+            blk = {}
+            for k in MATS:
+                W = mb[k][0].to(dev) if mb else rnd(*shapes[k])
+                b = mb[k][1].to(dev) if mb else z(shapes[k][0])
+                blk[k] = self._reg_matrix("h%d.%s.w" % (l, k), W, self.types[k])
+                blk[k + "_b"] = self._reg("h%d.%s.b" % (l, k), b, False)
+            ln = [t.to(dev) for t in mb["ln"]] if mb else [torch.ones(C_, device=dev, dtype=bf), z(C_), torch.ones(C_, device=dev, dtype=bf), z(C_)]
+            for i, nm in enumerate(("ln1.w", "ln1.b", "ln2.w", "ln2.b")):
+                blk[nm] = self._reg("h%d.%s" % (l, nm), ln[i], False)
+            self.blocks.append(blk)
+        wte = masters["wte"].to(dev) if masters else torch.cat([rnd(V, C_), z(Vp - V, C_)])
+        self.wte = self._reg("wte", wte, True, L.BF16)
+        self.wpe = self._reg("wpe", masters["wpe"].to(dev) if masters else rnd(T, C_, std=w_std / 2), False)
+        lnf = [t.to(dev) for t in masters["lnf"]] if masters else [torch.ones(C_, device=dev, dtype=bf), z(C_)]
+        self.lnf_w, self.lnf_b = self._reg("lnf.w", lnf[0], False), self._reg("lnf.b", lnf[1], False)
+        # activations of one step, all kept
+        N = self.N
+        self.A = [dict(x=z(N, C_), h1=z(N, C_), m1=z(N, dt=torch.float32), r1=z(N, dt=torch.float32), qkv=z(N, 3 * C_), att=z(N, C_), x2=z(N, C_), h2=z(N, C_),
+                       m2=z(N, dt=torch.float32), r2=z(N, dt=torch.float32), f=z(N, 4 * C_), g=z(N, 4 * C_)) for _ in range(NL)]
+        self.xf, self.hf, self.mf, self.rf = z(N, C_), z(N, C_), z(N, dt=torch.float32), z(N, dt=torch.float32)
+        self.qc, self.logits, self.losses = z(N, C_), z(N, Vp), z(N, dt=torch.float32)
+        self.dx, self.dh, self.dqkv, self.datt, self.d4 = z(N, C_), z(N, C_), z(N, 3 * C_), z(N, C_), z(N, 4 * C_)
+        hip = ctx.hip
+        self._alloc_linear_scratch(self.blocks[0], shapes, C_)
+        self._sc_ln = torch.empty(hip.kf_norm_backward_scratch_bytes(N, C_, 1) // 8 + 1, dtype=torch.float64, device=dev)
+        self._sc_at = torch.empty(hip.kf_attn_backward_scratch_bytes(T, H, B) // 4 + 1, dtype=torch.float32, device=dev)
+
+        # the step's sequencer: koifish::GPT2Trainer of libkf_host.so (koifish_amd/host/kf_train.cpp) over the buffers above -- every tensor registered once
+        self.h = ctx.host.kfh_gpt2_create(ctx.h, C_, H, NL, V, Vp, B, T)
+        if not self.h:
+            raise RuntimeError("kfh_gpt2_create refused the shape")
+        self._attach((self.xf, self.hf, self.mf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.d4), (self._sc_ln, self._sc_at))
+        if layers_in_branch:
+            self._check_host(ctx.host.kfh_gpt2_set_branches(self.h, int(layers_in_branch)), "kfh_gpt2_set_branches")
 
     # ---- EOE: layer-section branches
     @property
@@ -181,73 +293,12 @@ class GPT2Step:
                                                      out.data_ptr()), "kfh_gpt2_eval")
         return out
 
-    def _check_arena(self):
-        """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
-        if self.train_target == "gama" and self.ctx.hip.kf_dequant_arena_bytes(self.ctx.h):
-            raise L.KFError("train_target='gama' on a context with a dequant arena (kf_set_dequant_arena): the resident bf16 copies of the trained matrices would go stale "
-                            "with every update -- switch the arena off (kf_set_dequant_arena(ctx, NULL, 0)) for training")
-
-    def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
-        """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a block's weight matrices with ne0 >= ne1 (qkv, proj, fc) take SGD-momentum +
-        five Newton-Schulz steps (kf_muon: lr x lr_scale, weight decay by tp_decay as Pipe.cpp:23-37, mG = the tensor's m buffer); proj2, the embeddings, biases and norms
-        keep kf_adamw -- and so does every gama-trained tensor (train_target="gama"): its parameter is a [2 nGroup] slice, never a matrix for kf_muon.  Owns the scratch,
-        sized for the largest Muon tensor."""
-        if method not in ("adamw", "muon"):
-            raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
-        sp, nb = None, 0
-        if method == "muon":
-            shapes = [tuple(e["p"].shape) for e in self.params
-                      if e["blob"] is not None and not e.get("gama") and e["name"].startswith("h") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
-            nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
-            if nb == 0:
-                raise L.KFError("muon: a hidden matrix has a dimension that is no multiple of 64")
-            self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
-            sp = (self._sc_muon.data_ptr() + 255) & ~255
-        L.check(self.ctx.host.kfh_gpt2_set_optimizer(self.h, int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb), "kfh_gpt2_set_optimizer")
-        self.optimizer = method
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.host.kfh_gpt2_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    @property
-    def t(self):
-        """optimizer steps taken"""
-        return int(self.ctx.host.kfh_gpt2_steps_taken(self.h))
-
-    # ---- the step: sequenced by the host library; Python passes two device pointers and the hyper-parameters
-    def forward(self, ids, tgt):
-        """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
-        self._ids = ids   # kept alive: the backward reads them
-        self._check_arena()
-        L.check(self.ctx.host.kfh_gpt2_forward(self.h, ids.data_ptr(), tgt.data_ptr()), "kfh_gpt2_forward")
-
-    def backward(self):
-        L.check(self.ctx.host.kfh_gpt2_backward(self.h), "kfh_gpt2_backward")
-
-    def update(self, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
-        """AdamW on every tensor (its own master, moments and gradient; seeded stochastic rounding: seed + 7919 t + the tensor's index, as one seed per launch in the
-        reference), then the re-quantisation of every quantised matrix from its updated master.  kf_adamw zeroes the gradients it has consumed."""
-        L.check(self.ctx.host.kfh_gpt2_update(self.h, lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_gpt2_update")
-
-    def step(self, ids, tgt, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
-        """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
-        self._ids = ids
-        self._check_arena()
-        L.check(self.ctx.host.kfh_gpt2_step(self.h, ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_gpt2_step")
-
-    def n_params(self):
-        return sum(e["p"].numel() for e in self.params)
-
 
 Q3_MATS = ("q", "k", "v", "o", "gate", "up", "down")   # the slot order of Qwen3.set_weight
 Q3_NORMS = ("n1", "n2", "qn", "kn")                    # the slot order of Qwen3.set_norm
 
 
-class Qwen3Step:
+class Qwen3Step(_TrainStep):
     """One WHOLE training step of the Qwen3 family, GPT2Step's counterpart: the model everything else in this package serves (decode engines, prefill, score, .kun), and
     the one the reference's own training goldens run (cases/test_lite.py, tutorial_qwen3.md: Qwen3-596M plain and 4-bit with "train_target": "gama").
 
@@ -265,6 +316,9 @@ class Qwen3Step:
 
     Not offered on this trainer: EOE layer-section branches (GPT2Step's layers_in_branch)."""
 
+    _family, _acts_entry, _layer_prefix, _layer_noun = "qwen3t", "set_layer_acts", "l", "layer"
+    _act_keys = ("x", "h1", "r1", "qraw", "kraw", "qkv", "rq", "rk", "att", "x2", "h2", "r2", "gate", "up", "act")
+
     def __init__(self, ctx, cfg, B, T, types=None, tied=True, seed=0, w_std=0.02, masters=None, train_target="weights"):
         """cfg: the dict Qwen3 takes (dim, n_layer, n_head, n_kv, head_dim, ffn, vocab, theta, rms_eps).  types: storage per matrix name of Q3_MATS (default: 4-bit for
         all seven); the embedding / head are bf16.  The vocabulary is padded to a multiple of 64 rows (kf_linear_backward); the padded rows stay zero.
@@ -272,10 +326,8 @@ class Qwen3Step:
         {q .. down: W [out, in], n1, n2: [dim], qn, kn: [head_dim]}.  Otherwise N(0, w_std) draws on the device and unit norms.
         train_target: "weights" or "gama" (every layer matrix stored as a PackedQ group type trains its (zero, step) pairs in place, as GPT2Step); a context that holds a
         dequant arena is refused."""
-        if train_target not in ("weights", "gama"):
-            raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
-        self.train_target, self.tied = train_target, bool(tied)
-        self.ctx, self.cfg, self.B, self.T, self.N = ctx, dict(cfg), B, T, B * T
+        g = self._begin(ctx, train_target, seed)
+        self.tied, self.cfg, self.B, self.T, self.N = bool(tied), dict(cfg), B, T, B * T
         dim, NL, H, KV, hd, ffn, V = (cfg[k] for k in ("dim", "n_layer", "n_head", "n_kv", "head_dim", "ffn", "vocab"))
         self.V, self.Vp = V, (V + 63) // 64 * 64
         self.eps, self.theta = float(cfg.get("rms_eps", 1e-6)), float(cfg.get("theta", 1e6))
@@ -283,30 +335,12 @@ class Qwen3Step:
         W_ = Cq + 2 * Ck
         self.types = dict({k: L.Q4 for k in Q3_MATS}, **(types or {}))
         dev, bf, f32 = ctx.device, torch.bfloat16, torch.float32
-        g = torch.Generator(device=dev)
-        g.manual_seed(seed)
         z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
         rnd = lambda *s: (torch.randn(*s, device=dev, generator=g) * w_std).to(bf)
         ones = lambda n: torch.ones(n, device=dev, dtype=bf)
         self.shapes = dict(q=(Cq, dim), k=(Ck, dim), v=(Ck, dim), o=(dim, Cq), gate=(ffn, dim), up=(ffn, dim), down=(dim, ffn))
-        self.params, self.layers, self._models = [], [], []
+        self.layers, self._models = [], []
         self._check_arena()
-
-        def reg(name, p, wd, type_=None):
-            e = dict(name=name, p=p.contiguous(), g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=wd, blob=None, type=type_)
-            if type_ is not None:
-                e["blob"] = ctx.quantize(e["p"], type_)
-                if type_ == L.BF16:
-                    e["p"] = e["blob"].blob.view(bf).view(p.shape)   # a bf16 "blob" IS the master: updated in place, nothing to re-quantise
-            self.params.append(e)
-            return e
-
-        def reg_gama(name, Wm, type_):
-            blob = ctx.quantize(Wm.contiguous(), type_)   # the draw is dropped: the packed integers are the weight from here on
-            p = blob.gama_slice()
-            e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=False, blob=blob, type=type_, gama=True)
-            self.params.append(e)
-            return e
 
         def vocab_rows(t_):
             t_ = t_.to(dev)
@@ -316,17 +350,14 @@ class Qwen3Step:
             ly = {}
             for k in Q3_MATS:
                 Wm = ml[k].to(dev) if ml else rnd(*self.shapes[k])
-                if train_target == "gama" and self.types[k] in GAMA_TYPES:
-                    ly[k] = reg_gama("l%d.%s.w" % (l, k), Wm, self.types[k])
-                else:
-                    ly[k] = reg("l%d.%s.w" % (l, k), Wm, True, self.types[k])
+                ly[k] = self._reg_matrix("l%d.%s.w" % (l, k), Wm, self.types[k])
             for k in Q3_NORMS:
                 n_ = hd if k in ("qn", "kn") else dim
-                ly[k] = reg("l%d.%s" % (l, k), ml[k].to(dev) if ml else ones(n_), False)
+                ly[k] = self._reg("l%d.%s" % (l, k), ml[k].to(dev) if ml else ones(n_), False)
             self.layers.append(ly)
-        self.wte = reg("wte", vocab_rows(masters["wte"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
-        self.nf = reg("nf", masters["nf"].to(dev) if masters else ones(dim), False)
-        self.head = self.wte if self.tied else reg("head", vocab_rows(masters["head"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
+        self.wte = self._reg("wte", vocab_rows(masters["wte"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
+        self.nf = self._reg("nf", masters["nf"].to(dev) if masters else ones(dim), False)
+        self.head = self.wte if self.tied else self._reg("head", vocab_rows(masters["head"]) if masters else torch.cat([rnd(V, dim), z(Vp - V, dim)]), True, L.BF16)
         # activations of one step, all kept
         self.A = [dict(x=z(N, dim), h1=z(N, dim), r1=z(N, dt=f32), qraw=z(N, Cq), kraw=z(N, Ck), qkv=z(N, W_), rq=z(N * H, dt=f32), rk=z(N * KV, dt=f32), att=z(N, Cq),
                        x2=z(N, dim), h2=z(N, dim), r2=z(N, dt=f32), gate=z(N, ffn), up=z(N, ffn), act=z(N, ffn)) for _ in range(NL)]
@@ -335,10 +366,7 @@ class Qwen3Step:
         self.vtmp, self.dqr, self.dkr, self.dvd = z(N, Ck), z(N, Cq), z(N, Ck), z(N, Ck)
         self.table = ctx.rope_table(T, hd, self.theta)
         hip, host = ctx.hip, ctx.host
-        for k in Q3_MATS:
-            ctx.linear_scratch(self.layers[0][k]["blob"], N)
-        nb = max(hip.kf_linear_backward_scratch_bytes(oc, ic, N) for oc, ic in list(self.shapes.values()) + [(Vp, dim)])
-        self._sc_lin = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
+        self._alloc_linear_scratch(self.layers[0], self.shapes, dim)
         self._sc_ln = torch.empty(hip.kf_norm_backward_scratch_bytes(N, dim, 0) // 8 + 1, dtype=torch.float64, device=dev)
         self._sc_at = torch.empty(hip.kf_attn_backward_scratch_bytes(T, H, B) // 4 + 1, dtype=torch.float32, device=dev)
         nqk = hip.kf_qknorm_rope_backward_scratch_bytes(N, H, KV, hd)
@@ -350,60 +378,8 @@ class Qwen3Step:
         self.h = host.kfh_qwen3t_create(ctx.h, dim, NL, H, KV, hd, ffn, V, Vp, B, T, self.eps, int(self.tied))
         if not self.h:
             raise L.KFError("kfh_qwen3t_create refused the shape: %s" % host.kfh_qwen3t_last_error().decode())
-        assert host.kfh_qwen3t_n_params(self.h) == len(self.params)
-        gama = [e for e in self.params if e.get("gama")]
-        if gama:
-            need = [hip.kf_gama_backward_scratch_bytes(e["blob"].ne0, e["blob"].ne1, N) for e in gama]
-            if not all(need):
-                bad = gama[need.index(0)]
-                raise L.KFError("train_target='gama': kf_gama_backward does not take %s [%d, %d] at %d rows (in-features a multiple of 128, out-features and rows multiples of 64)"
-                                % (bad["name"], bad["blob"].ne0, bad["blob"].ne1, N))
-            self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=dev)
-            L.check(host.kfh_qwen3t_set_gama_scratch(self.h, (self._sc_gama.data_ptr() + 255) & ~255, max(need)), "kfh_qwen3t_set_gama_scratch")
-        for i, e in enumerate(self.params):
-            d = e["blob"].desc() if e["blob"] is not None else None
-            if e.get("gama"):
-                self._check_host(host.kfh_qwen3t_set_param_gama(self.h, i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d)), "kfh_qwen3t_set_param_gama")
-                continue
-            L.check(host.kfh_qwen3t_set_param(self.h, i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["p"].numel(), int(e["wd"]),
-                                              C.byref(d) if d is not None else None, int(e["type"] is not None and e["type"] != L.BF16)), "kfh_qwen3t_set_param")
-        for l, a in enumerate(self.A):
-            arr = (C.c_void_p * 15)(*[a[k].data_ptr() for k in ("x", "h1", "r1", "qraw", "kraw", "qkv", "rq", "rk", "att", "x2", "h2", "r2", "gate", "up", "act")])
-            L.check(host.kfh_qwen3t_set_layer_acts(self.h, l, arr), "kfh_qwen3t_set_layer_acts")
         bufs = (self.xf, self.hf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.dact, self.dgate, self.vtmp, self.dqr, self.dkr, self.dvd, self.table)
-        arr = (C.c_void_p * 20)(*([t_.data_ptr() for t_ in bufs] + [(self._sc_lin.data_ptr() + 255) & ~255, self._sc_ln.data_ptr(), self._sc_at.data_ptr(), self._sc_qk.data_ptr()]))
-        L.check(host.kfh_qwen3t_set_buffers(self.h, arr), "kfh_qwen3t_set_buffers")
-        self.optimizer = "adamw"
-
-    def _check_host(self, rc, what):
-        """a refusal of the trainer itself carries its reason in kfh_qwen3t_last_error; one of a kf_* entry underneath in kf_last_error"""
-        if rc != 0:
-            why = self.ctx.host.kfh_qwen3t_last_error().decode()
-            raise L.KFError("%s failed: code %d: %s" % (what, rc, why or self.ctx.hip.kf_last_error().decode()))
-
-    def _check_arena(self):
-        """train_target="gama" changes the (zero, step) a resident dequantised copy was made from: refused while the context holds a dequant arena"""
-        if self.train_target == "gama" and self.ctx.hip.kf_dequant_arena_bytes(self.ctx.h):
-            raise L.KFError("train_target='gama' on a context with a dequant arena (kf_set_dequant_arena): the resident bf16 copies of the trained matrices would go stale "
-                            "with every update -- switch the arena off (kf_set_dequant_arena(ctx, NULL, 0)) for training")
-
-    def set_optimizer(self, method="adamw", lr_scale=50.0, mui=0.95, eps=1e-7, tp_decay=1):
-        """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a layer's weight matrices with ne0 >= ne1 and a bf16 master (q, k, v, gate,
-        up at the Qwen3 shapes) take kf_muon; o, down, the norms, the embedding and the head keep kf_adamw -- and so does every gama-trained tensor.  Owns the scratch,
-        sized for the largest Muon tensor."""
-        if method not in ("adamw", "muon"):
-            raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
-        sp, nb = None, 0
-        if method == "muon":
-            shapes = [tuple(e["p"].shape) for e in self.params
-                      if e["blob"] is not None and not e.get("gama") and e["name"].startswith("l") and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
-            nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
-            if nb == 0:
-                raise L.KFError("muon: a layer matrix has a dimension that is no multiple of 64")
-            self._sc_muon = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
-            sp = (self._sc_muon.data_ptr() + 255) & ~255
-        L.check(self.ctx.host.kfh_qwen3t_set_optimizer(self.h, int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb), "kfh_qwen3t_set_optimizer")
-        self.optimizer = method
+        self._attach(bufs, (self._sc_ln, self._sc_at, self._sc_qk))
 
     def as_model(self, max_seq):
         """a Qwen3 decoder on the trainer's OWN blobs and norm tensors (set_weight / set_norm / tie_head with device pointers: no copy), vocabulary = the unpadded one.
@@ -437,39 +413,6 @@ class Qwen3Step:
                 live.append(r)
         self._models = live
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.host.kfh_qwen3t_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    @property
-    def t(self):
-        """optimizer steps taken"""
-        return int(self.ctx.host.kfh_qwen3t_steps_taken(self.h))
-
-    # ---- the step: sequenced by the host library; Python passes two device pointers and the hyper-parameters
-    def forward(self, ids, tgt):
-        """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
-        self._ids = ids   # kept alive: the backward reads them
-        self._check_arena()
-        L.check(self.ctx.host.kfh_qwen3t_forward(self.h, ids.data_ptr(), tgt.data_ptr()), "kfh_qwen3t_forward")
-
-    def backward(self):
-        L.check(self.ctx.host.kfh_qwen3t_backward(self.h), "kfh_qwen3t_backward")
-
-    def update(self, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
-        """as GPT2Step.update (seed + 7919 t + the tensor's index); then weights_changed() on every model handed out by as_model"""
-        L.check(self.ctx.host.kfh_qwen3t_update(self.h, lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_qwen3t_update")
+    def _after_update(self):
+        """update() and step(): weights_changed() on every model handed out by as_model"""
         self._weights_changed()
-
-    def step(self, ids, tgt, lr=3e-4, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.1, seed=1234):
-        """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
-        self._ids = ids
-        self._check_arena()
-        L.check(self.ctx.host.kfh_qwen3t_step(self.h, ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF), "kfh_qwen3t_step")
-        self._weights_changed()
-
-    def n_params(self):
-        return sum(e["p"].numel() for e in self.params)
