@@ -1,0 +1,461 @@
+"""Inputs whose arithmetic is EXACT in fp32 under every summation order, and their fp64 references (plain numpy, no GPU).
+
+A bar scaled by a tensor's largest element cannot see one wrong term of a long contraction.  With operands made of small integers (and halves) every
+product and every partial sum of a kernel's fp32 accumulation is representable, whatever the route, tile form, split-K cut or order, so the expected
+output is bf16(exact) BIT FOR BIT and nothing is measured.  Two groups:
+
+  integer GEMM operands   entries in {-1, 0, 1} (optionally +-2) with the density chosen per contraction length, or a dense +-1 block of 128 consecutive
+                          contraction indices placed on a seam of the form under test; small-integer prior values for the beta = 1 epilogues
+  one-hot / two-hot attention   q, k built so that each row's softmax is exactly {1} or {1/2, 1/2} on chosen keys and exactly 0 elsewhere after the
+                          kernels' own fp32 arithmetic (tests/test_exact_inputs_cpu.py emulates that arithmetic and asserts it)
+
+Every helper ASSERTS its precondition on the fp64 values it returns, so a badly chosen density or target pattern fails on the CPU, not on the GPU."""
+import ctypes as C
+
+import numpy as np
+
+from oracle import oracle as O
+
+BOUND = 256.0   # every integer of magnitude <= 256 is a bf16 value: the bf16 store of an exact result within the bound is that result
+
+
+def bits(x):
+    """fp64 / fp32 values -> bf16 bit patterns (round to nearest even)"""
+    return O.f32_to_bf16(np.asarray(x, dtype=np.float32))
+
+
+def exact_bits(x):
+    """bf16 bit patterns of values that must BE bf16 values (operands, prior values)"""
+    b = bits(x)
+    assert np.array_equal(O.bf16_to_f32(b).astype(np.float64), np.asarray(x, dtype=np.float64)), "not representable in bf16"
+    return b
+
+
+def f64(b):
+    return O.bf16_to_f32(b).astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- integer GEMM operands
+def density(K, second_moment=1.0):
+    """non-zero fraction per operand for a contraction of length K: the sum of K products of two such entries has variance K d^2 m <= 400, so its maximum over
+    a few million outputs (~5.5 sigma = 110) plus a prior value stays inside BOUND; at most 1/2"""
+    return min(0.5, 20.0 / np.sqrt(K * second_moment))
+
+
+def ternary(rng, shape, d, twos=False):
+    """entries 0 with probability 1 - d, otherwise +-1 (twos: +-1 or +-2)"""
+    mag = rng.integers(1, 3 if twos else 2, size=shape)
+    return (np.where(rng.random(shape) < d, mag, 0) * rng.choice([-1, 1], size=shape)).astype(np.float64)
+
+
+def small_ints(rng, shape, lim=8):
+    return rng.integers(-lim, lim + 1, size=shape).astype(np.float64)
+
+
+def exact_product(a, b, prior=None, bound=BOUND):
+    """fp64 a . b (+ prior): asserted to be integers within the bound, and with sum |terms| far below 2^24 -- so every partial sum in every order is an fp32 value"""
+    y = a @ b
+    if prior is not None:
+        y = y + prior
+    assert np.array_equal(y, np.rint(y)), "not an integer result"
+    assert np.abs(y).max() <= bound, "exact result %g outside +-%g: lower the density" % (np.abs(y).max(), bound)
+    assert a.shape[1] * np.abs(a).max() * np.abs(b).max() + (0 if prior is None else np.abs(prior).max()) < 2.0 ** 23
+    return y
+
+
+def block_rows(K, at, width=128):
+    """the contraction indices of a dense block placed astride index `at` (first / last tile: clipped into [0, K))"""
+    lo = min(max(at - width // 2, 0), K - width)
+    return np.arange(lo, lo + width)
+
+
+def linear_backward_case(OC, IC, n, family, seed, oc_blocks=(), n_blocks=(), twos=False, w=None):
+    """operands and exact results of kf_linear_backward for W [OC, IC], deltaIn [n, OC], inp [n, IC]:
+         delta [n, IC] = (prior) + deltaIn . W    (contraction over OC)        gW [OC, IC] = prior + deltaIn^T . inp   (contraction over n)
+         gBias [OC] = prior + column sums of deltaIn
+    family "sparse": random {-1, 0, 1} entries at density(K) of each contraction.
+    family "block":  dense +-1 blocks of 128 contraction indices, zero elsewhere.  oc_blocks / n_blocks: the positions `at` (block_rows) along OC / n.  Token row t
+                     multiplies block t mod len(oc_blocks) in the input gradient, output column o block o mod len(n_blocks) in the weight gradient, so one call
+                     puts a 128-term dense sum on every listed seam.
+    w: a given weight (fp64 integers [OC, IC]) instead of the family's."""
+    rng = np.random.default_rng(seed)
+    if family == "sparse":
+        W = ternary(rng, (OC, IC), density(OC, 2.5 if twos else 1.0), twos) if w is None else w
+        dIn = ternary(rng, (n, OC), min(density(OC), density(n)))
+        inp = ternary(rng, (n, IC), density(n))
+        kx, kw = slice(None), slice(None)
+    else:
+        assert family == "block" and len(oc_blocks) and len(n_blocks) and w is None
+        ocb = [block_rows(OC, a) for a in oc_blocks]
+        nb = [block_rows(n, a) for a in n_blocks]
+        u_oc, u_n = np.unique(np.concatenate(ocb)), np.unique(np.concatenate(nb))
+        A = np.zeros((n, OC), bool)   # row t: its block along OC
+        for j, blk in enumerate(ocb):
+            A[j::len(ocb), blk[0]:blk[-1] + 1] = True
+        B = np.zeros((n, OC), bool)   # column o: its block along n
+        for j, blk in enumerate(nb):
+            B[blk[0]:blk[-1] + 1, j::len(nb)] = True
+        both = np.zeros((n, OC), bool)
+        both[np.ix_(u_n, u_oc)] = True
+        mask = np.where(both, A, A | B)   # where the two unions cross, the row's rule alone: a token row never multiplies more than its own block
+        dIn = np.where(mask, rng.choice([-1.0, 1.0], size=(n, OC)), 0.0)
+        W = np.zeros((OC, IC))
+        W[u_oc] = rng.choice([-1.0, 1.0], size=(len(u_oc), IC))
+        inp = np.zeros((n, IC))
+        inp[u_n] = rng.choice([-1.0, 1.0], size=(len(u_n), IC))
+        kx, kw = u_oc, u_n   # the only contraction indices with a non-zero factor: the fp64 products below need no more
+    delta0, gW0, gb0 = small_ints(rng, (n, IC)), small_ints(rng, (OC, IC)), small_ints(rng, OC)
+    delta = exact_product(dIn[:, kx], W[kx], None)
+    delta_acc = exact_product(dIn[:, kx], W[kx], delta0)
+    gW = exact_product(np.ascontiguousarray(dIn[kw].T), inp[kw], gW0)
+    gb = dIn.sum(axis=0) + gb0
+    assert np.abs(gb).max() <= BOUND
+    return dict(OC=OC, IC=IC, n=n, W=exact_bits(W), dIn=exact_bits(dIn), inp=exact_bits(inp), delta0=exact_bits(delta0), gW0=exact_bits(gW0), gb0=exact_bits(gb0),
+                delta=exact_bits(delta), delta_acc=exact_bits(delta_acc), gW=exact_bits(gW), gb=exact_bits(gb),
+                f64=dict(W=W, dIn=dIn, inp=inp, delta0=delta0, gW0=gW0, kx=kx, kw=kw))
+
+
+def q4_grid_weight(OC, IC, seed):
+    """a 4-bit weight that its own storage holds exactly: every 128-element group contains one -7 and one 8, so RTN's step is (8 - -7) / 15 = 1 and its zero -7, and the
+    other entries are integers of the grid ({-1, 0, 1} mostly, so that the products stay inside BOUND).  Asserted against the oracle: dequant(quantize(w)) == w."""
+    rng = np.random.default_rng(seed)
+    w = ternary(rng, (OC * IC // 128, 128), density(OC, 2.0))
+    at = np.argsort(rng.random(w.shape), axis=1)[:, :2]   # two distinct places per group (a fixed column would line the -7s up in one output)
+    np.put_along_axis(w, at[:, :1], -7.0, axis=1)
+    np.put_along_axis(w, at[:, 1:], 8.0, axis=1)
+    w = w.reshape(OC, IC)
+    ow = O.quantize(exact_bits(w), OC, IC, O.Q4)
+    assert np.array_equal(O.dequant(ow), exact_bits(w)), "the 4-bit grid does not hold the weight exactly"
+    return w, ow
+
+
+# ---- the plan behind kf_linear_backward (kf_gemm_plan.h gemm_plan_backward through kfdbg_gemm_plan): which form a case runs, and where its k pieces meet
+BF16_T, BWD_DX, BWD_DW = 3, 4, 5
+ROUTES = {11: "KMAJOR", 12: "TRANSPOSE"}
+FAMILIES = {0: "NONE", 1: "DIRECT", 2: "PAIRED", 3: "STAGED", 4: "G2", 5: "G3"}
+G3_FORMS = {0: "BIG", 1: "SMALL", 2: "MID", 3: "TINY", 4: "WIDE"}
+
+
+class _Mat(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
+
+
+class _Problem(C.Structure):
+    _fields_ = [("entry", C.c_int), ("n_w", C.c_int), ("w", _Mat * 3), ("n", C.c_int), ("x_al", C.c_int), ("y_al", C.c_int), ("rope_ok", C.c_int), ("arena", C.c_int),
+                ("capturing", C.c_int), ("arena_hit", C.c_int), ("arena_free", C.c_longlong), ("scratch", C.c_longlong)]
+
+
+class _Kern(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("fam", "fmt", "gshift", "form", "akm", "bkm", "gx", "gy", "block", "lds", "sk", "P", "S", "kp", "R")]
+
+
+class _Plan(C.Structure):
+    _fields_ = [("route", C.c_int), ("status", C.c_int), ("deq", C.c_int), ("deq_form", C.c_int), ("deq_bytes", C.c_longlong), ("ws_bytes", C.c_longlong), ("k", _Kern)]
+
+
+def _up256(v):
+    return (v + 255) & ~255
+
+
+def backward_plan(hip, entry, OC, IC, n):
+    """the plan kf_linear_backward makes for this product: the scratch it lends is the middle region of kf_linear_backward_scratch_bytes"""
+    hip.kfdbg_gemm_plan.argtypes = [C.POINTER(_Problem), C.POINTER(_Plan)]
+    hip.kf_linear_backward_scratch_bytes.argtypes, hip.kf_linear_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
+    mid = hip.kf_linear_backward_scratch_bytes(OC, IC, n) - _up256(OC * IC * 2) - _up256((n + 255) // 256 * OC * 8)
+    P = _Problem(entry=entry, n_w=1, n=n, x_al=1, scratch=mid)
+    P.w[0] = _Mat(BF16_T, 0, 0, OC, IC, 0, 0, 3)
+    out = _Plan()
+    assert hip.kfdbg_gemm_plan(C.byref(P), C.byref(out)) == 0
+    return out
+
+
+def form_name(p):
+    """"KMAJOR/BIG/plain", "KMAJOR/SMALL/split" (S >= 2 pieces), "KMAJOR/BIG/tails" (kp > 0: owners + helpers), "TRANSPOSE/DIRECT", "TRANSPOSE/G3_TINY", ..."""
+    route, k = ROUTES[p.route], p.k
+    if route == "KMAJOR":
+        cut = "plain" if not k.sk else ("split" if k.S >= 2 else "tails")
+        return "KMAJOR/%s/%s" % (G3_FORMS[k.form], cut)
+    fam = FAMILIES[k.fam]
+    return "TRANSPOSE/" + (fam if fam != "G3" else "G3_%s%s" % (G3_FORMS[k.form], "/split" if k.sk else ""))
+
+
+def seams(p, K):
+    """the contraction indices at which two workgroups' k pieces of one output tile meet (kf_gemm3.hip gemm3_sk_kernel): between the S equal pieces; or the
+    owner / helper hand-over 64 kp and the cuts between two helpers' ranges of R steps inside the first tiles' tails.  Always with the first and the last k tile."""
+    at = [0, K]
+    k = p.k
+    if k.sk:
+        nkt = K // 64
+        if k.S >= 2:
+            at += [64 * (nkt * sp // k.S) for sp in range(1, k.S)]
+        else:
+            at.append(64 * k.kp)
+            L = nkt - k.kp   # the tails [kp, nkt) of all tiles laid end to end are cut every R steps: the cuts that fall inside the first four tiles' tails
+            at += [64 * (k.kp + b - t * L) for t in range(min(k.P, 4)) for b in range(0, k.P * L, k.R) if t * L < b < (t + 1) * L]
+    return sorted(set(at))
+
+
+# ---- the plan behind the attention entries (kf_attn_plan.h attn_plan through kfdbg_attn_plan): the forward's tile form or its paired form
+ATTN_PROMPT, ATTN_BATCH = 1, 2          # AttnProblem::entry: kf_attn_prefill, kf_attn_prefill_batch(_strided)
+ATTN_TILE, ATTN_PAIRED = 2, 3           # AttnPlan::route
+
+
+class _AttnProblem(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("entry", "n_head", "n_kv", "hd", "pos", "n_tok", "n_seq", "canon", "al")]
+                + [(f, C.c_longlong) for f in ("q_stride", "out_stride", "kv_stride")])
+
+
+class _AttnPlan(C.Structure):
+    _fields_ = ([(f, C.c_int) for f in ("status", "route", "canon", "gq", "nw", "hd", "kh", "kt", "gq_split", "n_splits", "chunk", "cnt_stride")]
+                + [("grid", C.c_int * 3), ("grid_kv", C.c_int * 3), ("threads", C.c_int), ("lds", C.c_int), ("scratch", C.c_longlong)])
+
+
+def forward_route(hip, entry, nh, nkv, hd, n, n_seq=1, pos0=0):
+    """the route of a forward launch with aligned, dense rows"""
+    hip.kfdbg_attn_plan.argtypes = [C.POINTER(_AttnProblem), C.POINTER(_AttnPlan)]
+    out = _AttnPlan()
+    assert hip.kfdbg_attn_plan(C.byref(_AttnProblem(entry, nh, nkv, hd, pos0, n, n_seq, 0, 3, nh * hd, 0, nkv * hd)), C.byref(out)) == 0 and out.status == 0
+    return out.route
+
+
+# ---------------------------------------------------------------------------------------------------------------- one-hot / two-hot attention
+NBITS = 9   # code words for up to 512 keys
+GAP_LOG2 = 160.0   # two scores that differ differ by at least this many powers of two: exp2 of the difference is exactly 0.0f (fp32's smallest subnormal is 2^-149)
+RAMP_G = 2048.0
+
+
+def code_gains(hd):
+    """(gq, gk, rep): q = gq x code, k = gk x code, every code bit repeated rep times.  Two distinct keys differ in >= 1 bit, i.e. by >= 2 rep gq gk in the raw score,
+    times scale log2(e) in the exponent: gq gk is the smallest power of two that makes that >= GAP_LOG2.  The gain sits mostly in k so that dk's accumulators (sums of
+    dS x q over many rows) stay small."""
+    rep = hd // NBITS
+    need = GAP_LOG2 / (2 * rep * np.log2(np.e) / np.sqrt(hd))
+    g = 2.0 ** np.ceil(np.log2(need))
+    assert g <= 64
+    return 2.0, g / 2.0, rep
+
+
+def codes(keys, hd, mask):
+    """+-1 code words of (key ^ mask), each of the NBITS bits repeated rep times, the remaining head_dim - NBITS rep entries 0"""
+    rep = hd // NBITS
+    b = ((np.asarray(keys)[:, None] ^ mask) >> np.arange(NBITS)[None, :]) & 1
+    c = np.zeros((len(keys), hd))
+    c[:, :NBITS * rep] = np.repeat(2.0 * b - 1.0, rep, axis=1)
+    return c
+
+
+def code_targets(T, pos0, nh, seq):
+    """the key(s) each (row, head) puts its whole probability on: ta [T, nh], tb [T, nh] (-1: one-hot).  Kinds, dealt over rows and heads: the diagonal; key 0 (one
+    row in four of its turn: every row that names key 0 adds to dk[0]); key p - 1; the first key of p's 32-key tile, the last and the first key of the tile before
+    it; the keys on either side of a multiple of 128; and two-hot {a, a - lowest set bit of a} on the next kind's key a.  A kind that does not exist for a row (no
+    earlier tile, p < 128, ...) falls back to the diagonal, which also covers the last key of the row's own tile (rows with p % 32 == 31) and the ragged last rows."""
+    ta = np.zeros((T, nh), np.int64)
+    tb = np.full((T, nh), -1, np.int64)
+
+    def one(kind, i, p):
+        t32 = p // 32 * 32
+        if kind == 1:
+            return 0 if i % 4 == 0 else p
+        if kind == 2:
+            return p - 1
+        if kind == 3:
+            return t32
+        if kind == 4:
+            return t32 - 1
+        if kind == 5:
+            return t32 - 32
+        if kind in (6, 7) and p >= 128:
+            return 128 * (1 + i % (p // 128)) - (kind == 6)
+        return p
+    for i in range(T):
+        p = pos0 + i
+        for h in range(nh):
+            kind = (i + 3 * h + seq) % 9
+            a = one(kind if kind < 8 else (i // 9 + h) % 8, i, p)
+            a = a if 0 <= a <= p else p
+            ta[i, h] = a
+            if kind == 8 and a > 0:
+                tb[i, h] = a - (a & -a)
+    return ta, tb
+
+
+def attn_case(family, T, nh, nkv, hd, n_seq=1, pos0=0, seed=0, vmax=1):
+    """q [n_seq T, nh hd], k / v [n_seq (pos0 + T), nkv hd], o / dO [n_seq T, nh hd] as fp64 small integers (each a bf16 value), and the targets ta / tb [n_seq, T, nh].
+    family "code": k_j = gk x the code word of j (a different bit mask per kv head and sequence), q_i = gq x the code of the target, or gq / 2 x the sum of two codes
+                   one bit apart -- the two scores are then equal and every other key's is lower by >= the gap.
+    family "ramp": score(i, j) = RAMP_G (j - p_i): k_j = (hi, lo, 1, 1, 0 ...) with j = 16 hi + lo, q_i = RAMP_G (16, 1, -16 hi_p, -lo_p, 0 ...).  The diagonal scores 0 and
+                   is the visible maximum; EVERY masked future key scores higher than any visible one, so one future key admitted takes the whole row.
+    o is NOT the forward's output: the backward takes it as an input, D = dO . o is an arbitrary integer."""
+    assert family in ("code", "ramp") and pos0 + T <= 1 << NBITS and nh % nkv == 0
+    rng = np.random.default_rng(seed)
+    GQ, tot = nh // nkv, pos0 + T
+    q, k = np.zeros((n_seq * T, nh * hd)), np.zeros((n_seq * tot, nkv * hd))
+    ta, tb = np.zeros((n_seq, T, nh), np.int64), np.full((n_seq, T, nh), -1, np.int64)
+    gq, gk, _ = code_gains(hd)
+    for s in range(n_seq):
+        if family == "code":
+            ta[s], tb[s] = code_targets(T, pos0, nh, s)
+        else:
+            ta[s] = (pos0 + np.arange(T))[:, None]
+        for g in range(nkv):
+            cols = slice(g * hd, (g + 1) * hd)
+            if family == "code":
+                mask = (37 * g + 73 * s + 11) & ((1 << NBITS) - 1)
+                k[s * tot:(s + 1) * tot, cols] = gk * codes(np.arange(tot), hd, mask)
+            else:
+                j = np.arange(tot)
+                k[s * tot:(s + 1) * tot, g * hd + 0], k[s * tot:(s + 1) * tot, g * hd + 1] = j // 16, j % 16
+                k[s * tot:(s + 1) * tot, g * hd + 2], k[s * tot:(s + 1) * tot, g * hd + 3] = 1.0, 1.0
+            for h in range(g * GQ, (g + 1) * GQ):
+                hc = slice(h * hd, (h + 1) * hd)
+                if family == "code":
+                    ca = codes(ta[s, :, h], hd, mask)
+                    two = tb[s, :, h] >= 0
+                    cb = codes(np.where(two, tb[s, :, h], 0), hd, mask)
+                    q[s * T:(s + 1) * T, hc] = np.where(two[:, None], gq / 2 * (ca + cb), gq * ca)
+                else:
+                    p = pos0 + np.arange(T)
+                    q[s * T:(s + 1) * T, h * hd + 0], q[s * T:(s + 1) * T, h * hd + 1] = 16 * RAMP_G, RAMP_G
+                    q[s * T:(s + 1) * T, h * hd + 2], q[s * T:(s + 1) * T, h * hd + 3] = -16 * RAMP_G * (p // 16), -RAMP_G * (p % 16)
+    v = rng.integers(-vmax, vmax + 1, size=(n_seq * tot, nkv * hd)).astype(np.float64)
+    o = rng.integers(-1, 2, size=(n_seq * T, nh * hd)).astype(np.float64)
+    dO = np.zeros((n_seq * T, nh, hd))
+    for _ in range(2):   # two +-1 entries per (row, head) (where the two places coincide the row has one)
+        idx = rng.integers(0, hd, size=(n_seq * T, nh))
+        np.put_along_axis(dO, idx[:, :, None], rng.choice([-1.0, 1.0], size=(n_seq * T, nh, 1)), axis=2)
+    dO = dO.reshape(n_seq * T, nh * hd)
+    for a in (q, k, v, o, dO):
+        exact_bits(a)
+    return dict(family=family, T=T, nh=nh, nkv=nkv, hd=hd, n_seq=n_seq, pos0=pos0, tot=tot, q=q, k=k, v=v, o=o, dO=dO, ta=ta, tb=tb)
+
+
+def kernel_scale(hd):
+    """1.0f / sqrtf((float)hd), as the launchers compute it"""
+    return np.float32(1.0) / np.sqrt(np.float32(hd))
+
+
+def closed_forward(c):
+    """out_i = bf16(v_a) or bf16((v_a + v_b) / 2): fp64 [n_seq T, nh hd]"""
+    T, nh, nkv, hd, tot = c["T"], c["nh"], c["nkv"], c["hd"], c["tot"]
+    GQ = nh // nkv
+    out = np.zeros((c["n_seq"] * T, nh * hd))
+    for s in range(c["n_seq"]):
+        for h in range(nh):
+            vg = c["v"][s * tot:(s + 1) * tot, (h // GQ) * hd:(h // GQ + 1) * hd]
+            a, b = c["ta"][s, :, h], c["tb"][s, :, h]
+            out[s * T:(s + 1) * T, h * hd:(h + 1) * hd] = np.where((b >= 0)[:, None], (vg[a] + vg[np.maximum(b, 0)]) / 2, vg[a])
+    return out
+
+
+def closed_backward(c, ta=None, tb=None, check=True):
+    """the backward in closed form: per (row i, head h) the probability w = 1 or 1/2 sits on the target key(s) x; dP_x = dO_i . v_x, D = dO_i . o_i,
+         dS_x = w (dP_x - D)       dq_i = sum_x dS_x k_x       dk_x += dS_x q_i       dv_x += w dO_i        (dk, dv: summed over the rows AND the group's heads)
+    -> bit patterns of dq = bf16(fl32(acc) fl32(scale)), dk likewise, dv = bf16(acc), and the fp64 accumulators.  check: every accumulator is a multiple of 1/2 of magnitude
+    <= BOUND, and its terms' magnitudes sum to < 2^23 halves, so every partial sum in every order is an fp32 value.  One exception, by construction: the ramp's q is
+    RAMP_G times integers up to 16 x 31 (nothing smaller separates neighbouring keys by the gap), so ITS dk accumulators are multiples of RAMP_G, held to the same
+    count of units; each has one term per head of the group."""
+    assert c["pos0"] == 0
+    T, nh, nkv, hd = c["T"], c["nh"], c["nkv"], c["hd"]
+    GQ = nh // nkv
+    ta = c["ta"] if ta is None else ta
+    tb = c["tb"] if tb is None else tb
+    rows = c["n_seq"] * T
+    dq, dk, dv = np.zeros((rows, nh * hd)), np.zeros((rows, nkv * hd)), np.zeros((rows, nkv * hd))
+    adq, adk, adv = np.zeros_like(dq), np.zeros_like(dk), np.zeros_like(dv)   # sums of |terms|
+    for s in range(c["n_seq"]):
+        r0 = s * T
+        for h in range(nh):
+            hc, gc = slice(h * hd, (h + 1) * hd), slice((h // GQ) * hd, (h // GQ + 1) * hd)
+            qh, dOh, oh = c["q"][r0:r0 + T, hc], c["dO"][r0:r0 + T, hc], c["o"][r0:r0 + T, hc]
+            kg, vg = c["k"][r0:r0 + T, gc], c["v"][r0:r0 + T, gc]
+            D = (dOh * oh).sum(axis=1)
+            two = tb[s, :, h] >= 0
+            for x, on in ((ta[s, :, h], np.ones(T, bool)), (np.maximum(tb[s, :, h], 0), two)):
+                w = np.where(two, 0.5, 1.0) * on
+                dS = w * ((dOh * vg[x]).sum(axis=1) - D)
+                dq[r0:r0 + T, hc] += dS[:, None] * kg[x]
+                adq[r0:r0 + T, hc] += np.abs(dS[:, None] * kg[x])
+                np.add.at(dk[r0:r0 + T, gc], x, dS[:, None] * qh)
+                np.add.at(adk[r0:r0 + T, gc], x, np.abs(dS[:, None] * qh))
+                np.add.at(dv[r0:r0 + T, gc], x, w[:, None] * dOh)
+                np.add.at(adv[r0:r0 + T, gc], x, np.abs(w[:, None] * dOh))
+    if check:
+        for name, a, aa in (("dq", dq, adq), ("dk", dk, adk), ("dv", dv, adv)):
+            unit = RAMP_G if (c["family"], name) == ("ramp", "dk") else 0.5
+            assert np.array_equal(a / unit, np.rint(a / unit)), name
+            assert aa.max() / unit < 2.0 ** 23, name
+            if unit == 0.5:
+                assert np.abs(a).max() <= BOUND, "%s accumulator %g outside +-%g" % (name, np.abs(a).max(), BOUND)
+    sc = kernel_scale(hd)
+    return dict(dq=bits(dq.astype(np.float32) * sc), dk=bits(dk.astype(np.float32) * sc), dv=bits(dv), acc=dict(dq=dq, dk=dk, dv=dv))
+
+
+# ---- plain fp64 references of the same operations (one sequence): the closed forms are compared with them on the CPU, and attn_backward_ref with the oracle
+def attn_forward_ref(q, k, v, nh, nkv, hd, pos0=0):
+    """causal softmax attention in fp64: q [T, nh hd], k / v [pos0 + T, nkv hd] -> out fp64 [T, nh hd]"""
+    T, GQ = q.shape[0], nh // nkv
+    vis = np.arange(pos0 + T)[None, :] <= (pos0 + np.arange(T))[:, None]
+    out = np.zeros((T, nh * hd))
+    for h in range(nh):
+        gc = slice((h // GQ) * hd, (h // GQ + 1) * hd)
+        s = np.where(vis, q[:, h * hd:(h + 1) * hd] @ k[:, gc].T / np.sqrt(float(hd)), -np.inf)
+        p = np.exp(s - s.max(axis=1, keepdims=True))
+        out[:, h * hd:(h + 1) * hd] = (p / p.sum(axis=1, keepdims=True)) @ v[:, gc]
+    return out
+
+
+def attn_backward_ref(q, k, v, o, dO, nh, nkv, hd, vis=None, round_p=False):
+    """causal attention backward in fp64 from fp64 copies of the bf16 inputs; the one fp32 multiply by fl32(1 / sqrt(hd)) and the bf16 stores as the kernels make them:
+    dq = bf16(fl32(sum dS k) fl32(scale)), dk likewise with the sum over the group's heads, dv = bf16(sum P dO).  vis [T, T]: the mask (default: causal) -- the
+    mutation checks pass a wrong one.  round_p: P and dS rounded to bf16 before their products, the kernels' two rounding points.  -> bit patterns + accumulators"""
+    T, GQ = q.shape[0], nh // nkv
+    vis = np.tril(np.ones((T, T), bool)) if vis is None else vis
+    rb = (lambda a: f64(bits(a))) if round_p else (lambda a: a)
+    dq, dk, dv = np.zeros((T, nh * hd)), np.zeros((T, nkv * hd)), np.zeros((T, nkv * hd))
+    for h in range(nh):
+        hc, gc = slice(h * hd, (h + 1) * hd), slice((h // GQ) * hd, (h // GQ + 1) * hd)
+        s = np.where(vis, q[:, hc] @ k[:, gc].T / np.sqrt(float(hd)), -np.inf)
+        p = np.exp(s - s.max(axis=1, keepdims=True))
+        p /= p.sum(axis=1, keepdims=True)
+        dS = p * (dO[:, hc] @ v[:, gc].T - (dO[:, hc] * o[:, hc]).sum(axis=1, keepdims=True))
+        dq[:, hc] = rb(dS) @ k[:, gc]
+        dk[:, gc] += rb(dS).T @ q[:, hc]
+        dv[:, gc] += rb(p).T @ dO[:, hc]
+    sc = kernel_scale(hd)
+    return dict(dq=bits(dq.astype(np.float32) * sc), dk=bits(dk.astype(np.float32) * sc), dv=bits(dv), acc=dict(dq=dq, dk=dk, dv=dv))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the cases the GPU modules run
+# kf_linear_backward (OC, IC, n) -> the forms of its two products (input gradient, weight gradient), as kf_gemm_plan.h plans them; pinned by
+# tests/test_exact_inputs_cpu.py.  The smallest shapes that reach each form: K-major needs IC and the token side >= 256, a split needs a contraction >= 1024.  No
+# shape with every side <= 2048 reaches a 256 x 256 (BIG) tile or an owner / helper cut (the CPU module enumerates them all), so those six go past it.
+LINEAR_CASES = {
+    (128, 128, 128): ("TRANSPOSE/DIRECT", "TRANSPOSE/DIRECT"),
+    (256, 256, 256): ("KMAJOR/SMALL/plain", "KMAJOR/SMALL/plain"),
+    (1024, 256, 1024): ("KMAJOR/SMALL/split", "KMAJOR/SMALL/split"),
+    (2048, 136, 2048): ("TRANSPOSE/G3_TINY", "TRANSPOSE/G3_TINY"),          # IC 136: a ragged last tile of 8 rows
+    (2048, 2176, 2048): ("KMAJOR/SMALL/tails", "KMAJOR/SMALL/tails"),
+    (512, 4096, 1600): ("KMAJOR/BIG/plain", "KMAJOR/SMALL/split"),          # 1600 = 6.25 big tiles; a 512-deep contraction is not cut
+    (1600, 4096, 512): ("KMAJOR/SMALL/split", "KMAJOR/BIG/plain"),
+    (1408, 4800, 1408): ("KMAJOR/BIG/split", "KMAJOR/BIG/split"),           # 19 x 6 = 114 ragged big tiles in two pieces
+    (2176, 3968, 2176): ("KMAJOR/BIG/tails", "KMAJOR/BIG/tails"),           # 16 x 9 = 144 tiles: owners + 112 helpers
+}
+Q4_CASE = (1024, 256, 1024)
+
+
+def linear_case(hip, shape, family, **kw):
+    """the case of LINEAR_CASES[shape]: the block family's blocks sit on the seams of the two plans"""
+    OC, IC, n = shape
+    if family == "block":
+        kw.update(oc_blocks=seams(backward_plan(hip, BWD_DX, OC, IC, n), OC), n_blocks=seams(backward_plan(hip, BWD_DW, OC, IC, n), n))
+    return linear_backward_case(OC, IC, n, family, seed=OC + 3 * IC + 7 * n + len(family), **kw)
+
+
+# attention: (n_head, n_kv) for GQ 1, 2, 4, 8
+HEADS = [(2, 2), (4, 2), (4, 1), (8, 1)]
+HEAD_DIMS = [64, 128]
+FWD_N = [8, 31, 32, 33, 127, 128, 129, 160, 257]   # 257 tokens of these head counts make few workgroups: the plan pairs them (ATTN_PAIRED)
+FWD_TILE_LONG = dict(n=257, nh=64, nkv=8, hd=64, n_seq=3)   # and the unpaired tile form past 256 tokens: 17 x 8 x 3 = 408 workgroups > 320
+FWD_POS0 = 37       # kf_attn_prefill behind a prefix of cache rows
+BWD_T = [8, 31, 33, 64, 129, 257, 300]
+N_SEQ = [1, 3]

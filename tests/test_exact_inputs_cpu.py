@@ -1,0 +1,385 @@
+"""Everything about the exact-arithmetic inputs (tests/exact_inputs.py) that can be settled without a GPU, for every case tests/test_gpu_exact_linear_backward.py and
+tests/test_gpu_exact_attention.py run:
+
+  preconditions   every operand is a bf16 value, every expected accumulator an integer (or half) inside the bound -- asserted by the helpers as the cases are built
+  probabilities   an fp32 emulation of the softmax statistics AS THE KERNELS COMPUTE THEM (running maximum per key tile, exp2 of score x scale x log2 e - M,
+                  L = (M + log2 l) ln 2, the forward's bf16 score store, the paired form's merge) gives exactly 0, 1/2 or 1 after the bf16 store and leaks exactly 0.0f
+  references      the closed forms equal a plain fp64 softmax reference; that reference agrees with the oracle's attn_backward to a bf16 unit, bit for bit off the ties
+  form coverage   the plan (kfdbg_gemm_plan / kfdbg_attn_plan) sends the case tables down every form the entry points have; what no small shape reaches is listed
+  power           one term removed, doubled or moved, one key admitted or dropped, changes the expected BITS -- and passes the global-max bars used so far"""
+import numpy as np
+import pytest
+
+from koifish_amd import lib as L
+from oracle import oracle as O
+from tests import exact_inputs as E
+
+LOG2E = np.float32(1.44269502162933349609375)
+LN2 = np.float32(0.693147182464599609375)
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def hip():
+    return L.load()[0]
+
+
+def same_values(a_bits, b_bits):
+    """bf16 arrays equal as numbers (an fp64 reference may reach a zero as -1e-50: -0.0 after the stores)"""
+    return np.array_equal(E.f64(a_bits), E.f64(b_bits))
+
+
+# ---------------------------------------------------------------------------------------------------------------- linear backward: preconditions, forms
+@pytest.mark.parametrize("family", ["sparse", "block"])
+@pytest.mark.parametrize("shape", list(E.LINEAR_CASES))
+def test_linear_case_preconditions(hip, shape, family):
+    c = E.linear_case(hip, shape, family)   # asserts integers inside the bound on every fp64 product it returns
+    for name in ("delta", "delta_acc", "gW", "gb"):
+        v = E.f64(c[name])
+        assert np.array_equal(v, np.rint(v)) and np.abs(v).max() <= E.BOUND
+    if family == "block":   # every output of the input gradient is a dense sum: 128 terms of +-1, an even integer
+        d = E.f64(c["delta"])
+        assert np.array_equal(d % 2, np.zeros_like(d)) and np.abs(d).max() > 16
+
+
+def test_linear_twos_and_q4_grid(hip):
+    c = E.linear_case(hip, (1024, 256, 1024), "sparse", twos=True)
+    assert np.abs(c["f64"]["W"]).max() == 2
+    w, ow = E.q4_grid_weight(*E.Q4_CASE[:2], seed=3)   # asserts dequant(quantize(w)) == w against the oracle
+    assert w.min() == -7 and w.max() == 8
+    E.linear_case(hip, E.Q4_CASE, "sparse", w=w)
+
+
+# forms of kf_gemm_plan.h gemm_plan_backward that NO legal shape with every side <= 2048 reaches (test_linear_forms_below_2048 enumerates them), and why
+BEYOND_2048 = {
+    "KMAJOR/BIG/plain": "a 256 x 256 tile is chosen only when the 128 x 128 tiles number >= 410 (else those, or their split, are taken): at most 16 x 16 = 256 here",
+    "KMAJOR/BIG/split": "as KMAJOR/BIG/plain",
+    "KMAJOR/BIG/tails": "as KMAJOR/BIG/plain",
+    "KMAJOR/SMALL/tails": "needs 257 .. 409 tiles of 128 x 128: at most 256 here",
+}
+# token-batch families tile_plan never returns for the transposed copies at ANY side <= 2048: the route is taken only when IC < 256 or the token side < 256
+NEVER_TRANSPOSED = {
+    "TRANSPOSE/G2": "ceil(M / 32) ceil(n / 32) <= 8 x 64 = 512 <= 1280: the direct kernel takes whatever the 64 x 64 tiles decline",
+    "TRANSPOSE/STAGED": "as TRANSPOSE/G2",
+    "TRANSPOSE/G3_MID": "needs >= 192 tiles of 64 x 128 with a side < 256: at most 4 x 16 = 64",
+    "TRANSPOSE/G3_SMALL": "needs >= 256 tiles of 128 x 128 with a side < 256: at most 2 x 16 = 32",
+    "TRANSPOSE/G3_BIG": "needs both sides >= 256: the K-major route has taken those",
+}
+WANTED = ["KMAJOR/BIG/plain", "KMAJOR/BIG/split", "KMAJOR/BIG/tails", "KMAJOR/SMALL/plain", "KMAJOR/SMALL/split"]
+
+
+def test_linear_case_forms(hip):
+    """the table names the form each case runs, and between them the cases run every wanted form in BOTH products"""
+    got = {e: set() for e in (E.BWD_DX, E.BWD_DW)}
+    for shape, want in E.LINEAR_CASES.items():
+        for e, w in zip((E.BWD_DX, E.BWD_DW), want):
+            p = E.backward_plan(hip, e, *shape)
+            assert E.form_name(p) == w, (shape, e)
+            got[e].add(w)
+            K = shape[0] if e == E.BWD_DX else shape[2]
+            if "split" in w:
+                assert p.k.S >= 2 and K // p.k.S >= 512 and len(E.seams(p, K)) == p.k.S + 1   # pieces stay >= 512 deep
+            if "tails" in w:
+                assert p.k.kp > 0 and 64 * p.k.kp in E.seams(p, K) and len(E.seams(p, K)) > 3   # the hand-over and helper-to-helper cuts
+    for e in got:
+        assert set(WANTED) <= got[e] and "KMAJOR/SMALL/tails" in got[e]
+
+
+def test_linear_forms_below_2048(hip):
+    """every legal shape on a grid of 64 (and two ragged input widths) with every side <= 2048: the forms reached are exactly those of the case table minus
+    BEYOND_2048, once per family tile_plan can return for the transposed copies; nothing in NEVER_TRANSPOSED is reached"""
+    reached = {e: set() for e in (E.BWD_DX, E.BWD_DW)}
+    sides = list(range(128, 2049, 64))
+    for OC in sides:
+        for IC in sides + [136, 200]:
+            for n in sides:
+                for e in reached:
+                    reached[e].add(E.form_name(E.backward_plan(hip, e, OC, IC, n)))
+    table = {e: {w[i] for w in E.LINEAR_CASES.values()} for i, e in enumerate((E.BWD_DX, E.BWD_DW))}
+    for e in reached:
+        assert reached[e] == table[e] - set(BEYOND_2048), (e, reached[e] ^ (table[e] - set(BEYOND_2048)))
+        assert not reached[e] & set(NEVER_TRANSPOSED)
+    assert all(max(s) > 2048 for s, w in E.LINEAR_CASES.items() if set(w) & set(BEYOND_2048))   # only those cases go past 2048
+
+
+# ---------------------------------------------------------------------------------------------------------------- attention: forms
+def test_attention_forward_forms(hip):
+    """every forward case runs the MFMA tile kernel; 257 tokens of the small head counts run its paired form, FWD_TILE_LONG the unpaired one past 256 tokens"""
+    routes = set()
+    for nh, nkv in E.HEADS:
+        for hd in E.HEAD_DIMS:
+            for n in E.FWD_N:
+                for n_seq in E.N_SEQ:
+                    r = E.forward_route(hip, E.ATTN_BATCH, nh, nkv, hd, n, n_seq)
+                    assert r == (E.ATTN_PAIRED if n >= 256 else E.ATTN_TILE)
+                    routes.add(r)
+                for pos0 in (0, E.FWD_POS0):
+                    assert E.forward_route(hip, E.ATTN_PROMPT, nh, nkv, hd, n, 1, pos0) == (E.ATTN_PAIRED if n >= 256 else E.ATTN_TILE)
+    assert routes == {E.ATTN_TILE, E.ATTN_PAIRED}
+    t = E.FWD_TILE_LONG
+    assert t["n"] >= 256 and E.forward_route(hip, E.ATTN_BATCH, t["nh"], t["nkv"], t["hd"], t["n"], t["n_seq"]) == E.ATTN_TILE
+
+
+# ---------------------------------------------------------------------------------------------------------------- attention: the kernels' fp32 softmax statistics
+def exp2f(x):
+    """v_exp_f32 on fp32 x: 2^x rounded to fp32 (2^-160 and below: 0.0f, 2^(-inf) = 0)"""
+    with np.errstate(over="ignore", under="ignore"):
+        return np.exp2(x.astype(np.float64)).astype(F32)
+
+
+def raw_scores(c, s, h):
+    """q . k of sequence s, head h: exact integers, every partial sum an fp32 value -> fp32 [T, tot]"""
+    T, tot, hd, GQ = c["T"], c["tot"], c["hd"], c["nh"] // c["nkv"]
+    q = c["q"][s * T:(s + 1) * T, h * hd:(h + 1) * hd]
+    k = c["k"][s * tot:(s + 1) * tot, (h // GQ) * hd:(h // GQ + 1) * hd]
+    assert (np.abs(q) @ np.abs(k).T).max() < 2.0 ** 24
+    return (q @ k.T).astype(F32)
+
+
+def walk(sc, tiles, kt, to_log2):
+    """online softmax over the key tiles `tiles` of kt keys: (M, l, P) with P[i, j] = the probability key j entered its tile's products with (before any later rescale).
+    sc [T, keys]: masked scores (-inf); to_log2: the exponent's unit -- the backward keeps scores in log2 units (1), the forward multiplies (s - M) by log2 e"""
+    T = sc.shape[0]
+    M, l, P = np.full(T, -np.inf, F32), np.zeros(T, F32), np.zeros(sc.shape, F32)
+    for t in tiles:
+        s = sc[:, t * kt:(t + 1) * kt]
+        if s.shape[1] == 0:
+            continue
+        mt = s.max(axis=1)
+        up = mt > M
+        with np.errstate(invalid="ignore"):
+            alpha = exp2f(((M - mt) * to_log2).astype(F32))
+        l = np.where(up, l * np.where(up, alpha, F32(1)), l).astype(F32)
+        rescaled = np.where(up[:, None], P * np.where(up, alpha, F32(1))[:, None], P)   # what earlier tiles contributed, as the kernel rescales O
+        M = np.where(up, mt, M)
+        Mref = np.where(np.isinf(M), F32(0), M)
+        p = exp2f(((s - Mref[:, None]) * to_log2).astype(F32))
+        for j in range(p.shape[1]):   # the kernel's adds, one probability at a time
+            l = (l + p[:, j]).astype(F32)
+        P = rescaled
+        P[:, t * kt:(t + 1) * kt] = p
+    return M, l, P
+
+
+def expected_probs(c, s, h):
+    T, tot = c["T"], c["tot"]
+    w = np.zeros((T, tot))
+    two = c["tb"][s, :, h] >= 0
+    w[np.arange(T), c["ta"][s, :, h]] = np.where(two, 0.5, 1.0)
+    w[np.arange(T)[two], c["tb"][s, two, h]] = 0.5
+    return w
+
+
+FWD_CASES = [(fam, n, nh, nkv, hd, n_seq, pos0) for fam in ("code", "ramp") for n in E.FWD_N for nh, nkv in E.HEADS for hd in E.HEAD_DIMS
+             for n_seq, pos0 in ((1, 0), (1, E.FWD_POS0), (3, 0))]
+
+
+def test_forward_probabilities_are_exact():
+    """kf_attn_prefill.hip: score = bf16(fl32(q . k x fl32(1 / sqrt(hd)))), mask, running maximum per tile, p = exp2((s - M) log2 e), l += p, out = O / l.  Both walks: 32-key
+    tiles in one pass, and the paired form's 64-key tiles in two halves (even / odd) merged at the end.  Every target enters with p == 1.0f, every other key with 0.0f,
+    l == the number of targets: out = (sum of the targets' v) / l exactly."""
+    t = E.FWD_TILE_LONG
+    for fam, n, nh, nkv, hd, n_seq, pos0 in FWD_CASES + [(f, t["n"], t["nh"], t["nkv"], t["hd"], t["n_seq"], 0) for f in ("code", "ramp")]:
+        c = E.attn_case(fam, n, nh, nkv, hd, n_seq, pos0, seed=n + nh + hd, vmax=2)
+        rden = E.kernel_scale(hd)
+        vis = np.arange(c["tot"])[None, :] <= (pos0 + np.arange(n))[:, None]
+        for s in range(n_seq):
+            for h in range(0, nh, max(1, nh // 8)):
+                st = raw_scores(c, s, h)
+                sc = np.where(vis, E.f64(E.bits(st * rden)).astype(F32), F32(-np.inf))
+                want = expected_probs(c, s, h)
+                cnt = (want > 0).sum(axis=1).astype(F32)
+                nt32, nt64 = (c["tot"] + 31) // 32, (c["tot"] + 63) // 64
+                M, l, P = walk(sc, range(nt32), 32, LOG2E)
+                assert np.array_equal(P, (want > 0).astype(F32)) and np.array_equal(l, cnt), (fam, n, nh, hd, pos0)
+                # paired: two partial softmaxes merged with a = exp2((M_half - max) log2 e)
+                M0, l0, P0 = walk(sc, range(0, nt64, 2), 64, LOG2E)
+                M1, l1, P1 = walk(sc, range(1, nt64, 2), 64, LOG2E)
+                Mm = np.maximum(M0, M1)
+                with np.errstate(invalid="ignore"):
+                    a0, a1 = exp2f(((M0 - Mm) * LOG2E).astype(F32)), exp2f(((M1 - Mm) * LOG2E).astype(F32))
+                assert np.isfinite(M0).all()   # the even half has seen key 0
+                assert np.array_equal((l0 * a0 + l1 * a1).astype(F32), cnt)
+                assert np.array_equal(P0 * a0[:, None] + P1 * a1[:, None], (want > 0).astype(F32))
+
+
+BWD_CASES = [(fam, T, nh, nkv, hd, n_seq) for fam in ("code", "ramp") for T in E.BWD_T for nh, nkv in E.HEADS for hd in E.HEAD_DIMS for n_seq in E.N_SEQ]
+
+
+def test_backward_probabilities_are_exact():
+    """kf_attn_bwd_mfma.hip: pass A keeps scores in log2 units, sc = fl32(q . k x c1), c1 = fl32(scale x log2 e); running maximum M and l = sum exp2(sc - M) per 32-key tile;
+    L = fl32(fl32(M + log2 l) x ln 2).  Both launches then recompute p = exp2(fma(q . k, c1, -fl32(L x log2 e))): NOT exactly 1 or 1/2 (L went through two roundings),
+    but within 2^-12 of it, so that the bf16 P operand IS 1 or 1/2 and the bf16 dS operand IS w (dP - D) -- with a margin of 2^3 over what the stores need for the
+    last bit of the hardware's exp2.  Every other visible key: exp2 of <= -160, exactly 0.0f; the leaked mass l - (number of targets) is exactly 0.0f."""
+    for fam, T, nh, nkv, hd, n_seq in BWD_CASES:
+        c = E.attn_case(fam, T, nh, nkv, hd, n_seq, seed=T + nh + hd)
+        GQ = nh // nkv
+        c1 = (E.kernel_scale(hd) * LOG2E).astype(F32)
+        vis = np.tril(np.ones((T, T), bool))
+        for s in range(n_seq):
+            for h in range(nh):
+                st = raw_scores(c, s, h)
+                sc = np.where(vis, (st * c1).astype(F32), F32(-np.inf))
+                want = expected_probs(c, s, h)
+                M, l, P = walk(sc, range((T + 31) // 32), 32, F32(1))
+                assert np.array_equal(l, (want > 0).sum(axis=1).astype(F32)), (fam, T, nh, hd)   # leaked mass 0.0f
+                assert np.array_equal(P > 0, want > 0)
+                Lrow = ((M + np.log2(l.astype(np.float64)).astype(F32)).astype(F32) * LN2).astype(F32)
+                L2 = (Lrow * LOG2E).astype(F32)
+                with np.errstate(over="ignore", invalid="ignore"):
+                    arg = (st.astype(np.float64) * np.float64(c1) - L2[:, None].astype(np.float64)).astype(F32)   # the fma: one rounding
+                    p = np.where(vis, exp2f(arg), F32(0))   # future keys may be +inf before the mask: selected away, never multiplied
+                assert np.array_equal(p[want == 0], np.zeros((want == 0).sum(), F32))
+                on = want > 0
+                assert (np.abs(p[on].astype(np.float64) / want[on] - 1.0) <= 2.0 ** -12).all(), (fam, T, nh, hd)
+                assert np.array_equal(E.f64(E.bits(p)), want)   # the P operand of dV
+                # dS = p (dP - D), packed to bf16: the exact w (dP - D)
+                hc, gc = slice(h * hd, (h + 1) * hd), slice((h // GQ) * hd, (h // GQ + 1) * hd)
+                dOh = c["dO"][s * T:(s + 1) * T, hc]
+                x = dOh @ c["v"][s * T:(s + 1) * T, gc].T - (dOh * c["o"][s * T:(s + 1) * T, hc]).sum(axis=1, keepdims=True)
+                assert np.abs(x).max() <= 16
+                dS = (p * x.astype(F32)).astype(F32)
+                assert np.array_equal(E.f64(E.bits(dS)), want * x)
+
+
+# ---------------------------------------------------------------------------------------------------------------- attention: closed forms, references, the oracle
+def split_seq(c, s):
+    T, tot = c["T"], c["tot"]
+    return [c[k][s * T:(s + 1) * T] for k in ("q",)] + [c[k][s * tot:(s + 1) * tot] for k in ("k", "v")] + [c[k][s * T:(s + 1) * T] for k in ("o", "dO")]
+
+
+def test_closed_forms_equal_the_fp64_reference():
+    """every case of the GPU module: the closed-form expectation (which also asserts the accumulator bounds) against the plain fp64 softmax reference"""
+    for fam, T, nh, nkv, hd, n_seq in BWD_CASES:
+        c = E.attn_case(fam, T, nh, nkv, hd, n_seq, seed=T + nh + hd)
+        want = E.closed_backward(c)
+        for s in range(n_seq):
+            q, k, v, o, dO = split_seq(c, s)
+            for round_p in (False, True):
+                ref = E.attn_backward_ref(q, k, v, o, dO, nh, nkv, hd, round_p=round_p)
+                for name in ("dq", "dk", "dv"):
+                    assert same_values(ref[name], want[name][s * T:(s + 1) * T]), (fam, T, nh, hd, name)
+    for fam, n, nh, nkv, hd, n_seq, pos0 in FWD_CASES:
+        c = E.attn_case(fam, n, nh, nkv, hd, n_seq, pos0, seed=n + nh + hd, vmax=2)
+        want = E.closed_forward(c)
+        assert np.array_equal(4 * want, np.rint(4 * want)) and np.abs(want).max() <= 2   # halves of sums of two small integers: bf16 values
+        for s in range(n_seq):
+            q, k, v, _, _ = split_seq(c, s)
+            assert same_values(E.bits(E.attn_forward_ref(q, k, v, nh, nkv, hd, pos0)), E.bits(want[s * n:(s + 1) * n]))
+
+
+def near_tie(x):
+    """fp64 x within 2^-20 (relative) of the midpoint of two neighbouring bf16 values: where a last-bit difference before the store may round the other way"""
+    with np.errstate(divide="ignore"):
+        ulp = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(x), 2.0 ** -126))) - 7)
+    r = np.abs(x) / ulp
+    return np.abs(r - np.floor(r) - 0.5) <= 2.0 ** -20 * r
+
+
+@pytest.mark.parametrize("T,nh,nkv,hd", [(19, 2, 2, 64), (40, 4, 2, 128), (33, 8, 1, 64), (70, 4, 1, 128)])
+def test_reference_agrees_with_the_oracle(T, nh, nkv, hd):
+    """attn_backward_ref against oracle.attn_backward (all fp64, one bf16 store): the only difference is the reference's fp32 multiply by fl32(scale), as the kernels make
+    it -- so at most one bf16 unit, and bit-equal wherever the fp64 value is not at a rounding tie.  Random inputs and the exact families."""
+    rng = np.random.default_rng(T)
+    cases = [[E.f64(O.f32_to_bf16(rng.normal(0, 1.0, (T, w * hd)).astype(np.float32))) for w in (nh, nkv, nkv, nh, nh)]]
+    cases += [split_seq(E.attn_case(fam, T, nh, nkv, hd, 1, seed=T), 0) for fam in ("code", "ramp")]
+    from tests.conftest import ulp_diff_bf16
+    for q, k, v, o, dO in cases:
+        ref = E.attn_backward_ref(q, k, v, o, dO, nh, nkv, hd)
+        odq, odk, odv = O.attn_backward(*(E.exact_bits(a) for a in (q, k, v, o, dO)), nh, hd, n_kv=nkv)
+        for name, got in (("dq", odq), ("dk", odk), ("dv", odv)):
+            d = ulp_diff_bf16(ref[name], got) * (E.f64(ref[name]) != E.f64(got))   # (+-0 are equal)
+            assert d.max() <= 1, name
+            x = ref["acc"][name] * (1.0 if name == "dv" else 1.0 / np.sqrt(float(hd)))
+            assert near_tie(x[d > 0]).all(), name
+            assert (d > 0).mean() <= 1e-3, name
+
+
+# ---------------------------------------------------------------------------------------------------------------- power
+def bar_accepts(got, ref, rel_max, rel_rms=None):
+    """the criteria of tests/test_gpu_linear_backward.py (2^-8 of max|ref|) and tests/test_gpu_gpt2_ops.py's attention backward (2^-7 max, 2^-9 rms)"""
+    ok = np.abs(got - ref).max() <= rel_max * np.abs(ref).max() + 1e-6
+    return ok and (rel_rms is None or np.sqrt(((got - ref) ** 2).mean()) <= rel_rms * np.abs(ref).max())
+
+
+@pytest.mark.parametrize("family", ["sparse", "block"])
+@pytest.mark.parametrize("shape", [(1024, 256, 1024), (2048, 2176, 2048)])
+def test_one_wrong_term_changes_the_bits(hip, shape, family):
+    """the fp64 reference of each product (input gradient delta = deltaIn . W, weight gradient gW = prior + deltaIn^T . inp) with one non-zero term removed, doubled, or
+    added to the neighbouring output column instead -- at sampled contraction indices and on both sides of every seam of the form: the expected bits change every time"""
+    c = E.linear_case(hip, shape, family)
+    f = c["f64"]
+    rng = np.random.default_rng(1)
+    for entry, a, b, name, K in ((E.BWD_DX, f["dIn"], f["W"], "delta", shape[0]), (E.BWD_DW, f["dIn"].T, f["inp"], "gW", shape[2])):   # y [r, col] = sum_k a[r, k] b[k, col]
+        y = E.f64(c[name])
+        assert np.abs(y).max() + 2 <= E.BOUND   # a result one term away is still an integer bf16 holds
+        ks = [k for s in E.seams(E.backward_plan(hip, entry, *shape), K) for k in (s - 1, s) if 0 <= k < K] + list(rng.integers(0, K, 16))
+        n_checked = 0
+        for k in ks:
+            rows, cols = np.nonzero(a[:, k])[0], np.nonzero(b[k])[0]
+            if not len(rows) or not len(cols):
+                continue
+            r, col = rows[rng.integers(len(rows))], cols[rng.integers(len(cols))]
+            term = a[r, k] * b[k, col]
+            nb = col + 1 if col + 1 < y.shape[1] else col - 1
+            for mut in ("removed", "doubled", "moved"):
+                m = y[r].copy()
+                m[col] += term if mut == "doubled" else -term
+                if mut == "moved":
+                    m[nb] += term
+                assert E.bits(m)[col] != c[name][r, col], (name, k, mut)
+                assert mut != "moved" or E.bits(m)[nb] != c[name][r, nb]
+            n_checked += 1
+        assert n_checked >= 8, name
+
+
+def test_the_global_max_bar_accepts_one_wrong_term():
+    """the record of why these tests exist: N(0, 1) operands, a contraction of 3072 (the GPT-2 shapes of tests/test_gpu_linear_backward.py) -- one product of typical
+    size dropped from one output passes max|got - ref| <= 2^-8 max|ref|"""
+    rng = np.random.default_rng(0)
+    a = E.f64(O.f32_to_bf16(rng.normal(0, 1.0, (256, 3072)).astype(np.float32)))
+    b = E.f64(O.f32_to_bf16(rng.normal(0, 1.0, (3072, 256)).astype(np.float32)))
+    ref = a @ b
+    bar = 2.0 ** -8 * np.abs(ref).max()
+    terms = np.abs(a[7, :] * b[:, 9])
+    k = int(np.argsort(terms)[len(terms) // 2])   # the median-sized term of that output
+    got = ref.copy()
+    got[7, 9] -= a[7, k] * b[k, 9]
+    assert got[7, 9] != ref[7, 9] and bar_accepts(got, ref, 2.0 ** -8)
+    assert (terms <= bar).mean() >= 0.5   # and so do most of its terms
+
+
+@pytest.mark.parametrize("T,nh,nkv,hd,draw", [(130, 2, 2, 64, 2), (300, 4, 2, 128, 8)])
+def test_one_wrong_mask_decision_changes_the_bits(T, nh, nkv, hd, draw):
+    """exact families: a future key admitted at ONE row (ramp: it takes the whole row), the diagonal dropped at one row (code: a row whose target it is) -- dq, dk and dv
+    all change.  And the record: on random peaked inputs (q scaled by 4) a future key admitted at one row in 32 changes hundreds of output values, and whether the
+    2^-7 max / 2^-9 rms bars notice depends on the draw -- on whether an admitted key happens to score near its row's maximum.  Of the draws 0 .. 11 of this generator
+    the error passes both bars on 2 and 6 at (T 130, hd 64) and on 8 at (T 300, hd 128), by a factor of up to 6; on others it misses them by up to 90 x.  The
+    draws pinned here pass."""
+    causal = np.tril(np.ones((T, T), bool))
+    for fam in ("ramp", "code"):
+        c = E.attn_case(fam, T, nh, nkv, hd, 1, seed=T)
+        q, k, v, o, dO = split_seq(c, 0)
+        want = E.closed_backward(c)
+        diag = [i for i in range(1, T) if (c["ta"][0, i] == i).any()]   # code: rows with a head whose target is the diagonal -- the ones nearest the seams
+        rows = [31, 32, 127, 128, T - 2] if fam == "ramp" else sorted({min(diag, key=lambda i: abs(i - at)) for at in (31, 32, 127, 128, T - 1)} | set(diag[::len(diag) // 4]))
+        assert len(rows) >= 3
+        for i in rows:
+            vis = causal.copy()
+            if fam == "ramp":
+                vis[i, i + 1] = True
+            else:
+                vis[i, i] = False
+            got = E.attn_backward_ref(q, k, v, o, dO, nh, nkv, hd, vis=vis, round_p=True)
+            for name in ("dq", "dk", "dv"):
+                assert not same_values(got[name], want[name]), (fam, i, name)
+    rng = np.random.default_rng(draw)
+    q, k, v, o, dO = (E.f64(O.f32_to_bf16((rng.normal(0, 1.0, (T, w * hd)) * g).astype(np.float32))) for w, g in ((nh, 4.0), (nkv, 1.0), (nkv, 1.0), (nh, 1.0), (nh, 1.0)))
+    vis = causal.copy()
+    for i in range(5, T - 1, 32):
+        vis[i, i + 1] = True
+    ref = E.attn_backward_ref(q, k, v, o, dO, nh, nkv, hd, round_p=True)
+    got = E.attn_backward_ref(q, k, v, o, dO, nh, nkv, hd, vis=vis, round_p=True)
+    for name in ("dq", "dk", "dv"):
+        assert not np.array_equal(got[name], ref[name])
+        assert bar_accepts(E.f64(got[name]), E.f64(ref[name]), 2.0 ** -7, 2.0 ** -9), name
