@@ -444,6 +444,48 @@ int kf_fused_classifier(kf_ctx* ctx, kf_bf16* logits, float* losses, kf_bf16* pr
  * (device int32, optional). */
 int kf_adamw(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, size_t n, int mv_type, float learning_rate, float beta1, float beta2,
              float beta1_correction, float beta2_correction, float eps, float weight_decay, float grad_scale, uint32_t seed, int32_t* d_status);
+/* kf_adamw with grad_scale read on the device: *d_grad_scale (one float, 4-byte aligned; loaded once per thread) in place of the by-value float -- there is no
+ * product of two scales.  Bit for bit kf_adamw with the same float.  The clip factors of kf_grad_norms are what it is made for: d_scale + i. */
+int kf_adamw_scaled(kf_ctx* ctx, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, size_t n, int mv_type, float learning_rate, float beta1, float beta2,
+                    float beta1_correction, float beta2_correction, float eps, float weight_decay, const float* d_grad_scale, uint32_t seed, int32_t* d_status);
+
+/* ---- gradient norms: the sum of squares of EVERY gradient tensor of a step in one launch, |g| and the clip factors left on the device (kf_gradnorm.hip,
+ * kf_gradnorm_plan.h).  The reference: GTensor::Length per tensor (huTensor.cu:665-704: memset, atomicAdd kernel, blocking read-back), grad_scale = gnorm > gclip ?
+ * gclip / gnorm : 1 formed on the host (Optimizer.cu:756-774), Optimizer::gClip over the whole gradient (Optimizer.cpp:276-308), g_step = sqrt(sum gnorm^2) printed
+ * with the loss.  Here nothing is read back and no sum depends on scheduling.
+ *
+ * The table: n_tensors pairs (grads[i], n[i]); n[i] a positive multiple of 8, grads[i] 16-byte aligned.  Tensor i is cut into ceil(n[i] / 4096) chunks of 4096
+ * elements (512 threads x 8 bf16, kf_adamw's geometry); it owns the workgroups [wg0[i], wg0[i + 1]), wg0[0] = 0.  kf_grad_norms_plan writes {pointer, n, wg0,
+ * no_clip} once into the caller's scratch (device memory, 256-byte aligned, kf_grad_norms_scratch_bytes long: the table, then one fp64 partial per chunk) with one
+ * blocking copy -- outside the step -- and the context remembers the layout under the scratch's address; kf_grad_norms refuses a scratch it has not planned.  The
+ * gradient tensors and the scratch must stay where they are, and the table untouched, while the plan is in use; kf_grad_norms rewrites the partials inside the
+ * scratch.  Each plan carries a stamp, in the table and on the host: a scratch whose memory was given back and handed out again since (same address, other contents)
+ * makes kf_grad_norms a no-op that reports NaN sums and norms and unit scales -- the pointers of a table that is not the planned one are never followed.
+ *
+ * The summation order, complete (every addition fp64; the product of two bf16 values is exact in fp64, so only the additions round):
+ *   1. thread t of chunk k holds elements 4096 k + 8 t .. + 7 of the tensor: ss = 0; ss = fma(x, x, ss) for the 8 elements in element order (elements at or past n
+ *      are not loaded: such a thread holds 0);
+ *   2. the 64 lanes of a wave: six pairwise levels, level j adding the sums of adjacent blocks of 2^j lanes ((l0 + l1) + (l2 + l3) ...); the 8 waves of the
+ *      workgroup: 0 + w0 + w1 + ... + w7 in wave order.  One partial per chunk;
+ *   3. a tensor's np partials: per = ceil(np / 256); run r = partials [r per, min((r + 1) per, np)) added in order from 0; then the 256 runs in order from 0;
+ *   4. the total: the per-tensor sums in tensor order from 0.
+ * Outputs, all on the device: d_sumsq fp64 [n_tensors + 1] (the last entry: the total), d_gnorm float [n_tensors + 1] = (float)sqrt(sumsq) (the root in fp64,
+ * narrowed once), d_scale float [n_tensors]; with c = gclip and the division in fp32:
+ *   KF_CLIP_REPORT  every scale 1.0f
+ *   KF_CLIP_TENSOR  scale[i] = gnorm[i] > c ? c / gnorm[i] : 1.0f
+ *   KF_CLIP_GLOBAL  scale[i] = gnorm[n_tensors] > c ? c / gnorm[n_tensors] : 1.0f
+ * and 1.0f in every mode for a tensor whose no_clip byte was set at plan time (it still counts in the total).  A non-finite sum needs no special case: a NaN
+ * norm compares false and gives 1.0f, +inf gives 0.0f, and kf_adamw's own non-finite guard does the rest.
+ * kf_grad_norms_forget drops what the context remembers of a scratch (before the scratch is freed: its address may be handed out again); unknown: KF_OK.
+ * n_tensors is at most 4096: the total is one thread's serial chain over the per-tensor sums (measured at 580 tensors; microseconds at the cap).
+ * Refusals are KF_INVALID_ARGS, launch nothing, and kf_last_error names the cause: a null pointer; n_tensors < 1 or above 4096; an n that is not a positive multiple of 8; a
+ * misaligned pointer; a scratch that is missing, not 256-byte aligned, too short, or (kf_grad_norms) not planned for n_tensors on this context; an unknown mode;
+ * gclip not finite or <= 0 in a clipping mode.  kf_grad_norms_scratch_bytes is 0 for a list the entries refuse. */
+enum kf_clip_mode { KF_CLIP_REPORT = 1, KF_CLIP_TENSOR = 2, KF_CLIP_GLOBAL = 3 };
+size_t kf_grad_norms_scratch_bytes(int n_tensors, const long long* n);
+int kf_grad_norms_plan(kf_ctx* ctx, int n_tensors, const kf_bf16* const* grads, const long long* n, const uint8_t* no_clip_or_null, void* scratch, size_t scratch_bytes);
+int kf_grad_norms(kf_ctx* ctx, const void* scratch, int n_tensors, int mode, float gclip, double* d_sumsq, float* d_gnorm, float* d_scale);
+int kf_grad_norms_forget(kf_ctx* ctx, const void* scratch);
 
 /* ---- Muon, the reference's default optimiser (CLI_params.hpp:627), for a hidden matrix W [ne0 = out][ne1 = in] with ne0 >= ne1: PIPE_Muon::CU_core
  * (src/Device/CUDA/Optimizer.cu:498-583; set up by PIPE_Muon::Update, src/Device/Pipe.cpp:16-57).  The reference's column-major X (m = ne1, n = ne0) is W^T, its

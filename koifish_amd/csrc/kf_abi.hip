@@ -18,6 +18,7 @@
 #include "kf_gemv_plan.h"
 #include "kf_score_plan.h"
 #include "kf_gama_plan.h"
+#include "kf_gradnorm_plan.h"
 
 struct kf_ctx {
     int device;
@@ -40,6 +41,12 @@ struct kf_ctx {
     void* arena;
     size_t arena_bytes, arena_used;
     std::vector<DeqCopy> copies;
+    // the tables kf_grad_norms_plan has written, by the address of the scratch that holds them: kf_grad_norms launches what is remembered here and nothing else
+    struct GradNormSlot {
+        const void* scratch;
+        kf::GradNormPlan plan;
+    };
+    std::vector<GradNormSlot> gn_plans;
 };
 struct kf_graph {
     hipGraph_t graph;
@@ -1226,7 +1233,86 @@ int kf_adamw(kf_ctx* c, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, siz
     RET(kf::adamw_launch(c->stream, params, grads, gm, gv, n, mv_type == KF_BF16, learning_rate, beta1, beta2, beta1_correction, beta2_correction, eps,
                          weight_decay, grad_scale, seed, d_status));
 }
+int kf_adamw_scaled(kf_ctx* c, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, size_t n, int mv_type, float learning_rate, float beta1, float beta2,
+                    float beta1_correction, float beta2_correction, float eps, float weight_decay, const float* d_grad_scale, uint32_t seed, int32_t* d_status) {
+    CHKCTX(c);
+    if (!params || !grads || !gm || !gv || !d_grad_scale) return fail(KF_INVALID_ARGS, "kf_adamw_scaled: null pointer");
+    if (mv_type != KF_BF16 && mv_type != KF_F32) return fail(KF_UNSUPPORTED_DATATYPE, "kf_adamw_scaled: moments must be bf16 or f32 (got %d)", mv_type);
+    if (n == 0 || n % 8) return fail(KF_INVALID_ARGS, "kf_adamw_scaled: n = %zu is not a positive multiple of 8", n);
+    if (!al16(params) || !al16(grads) || !al16(gm) || !al16(gv) || (((uintptr_t)d_grad_scale) & 3)) return fail(KF_BLAS_UNALIGN, "kf_adamw_scaled: tensors must be 16-byte aligned, the scale 4-byte");
+    RET(kf::adamw_launch(c->stream, params, grads, gm, gv, n, mv_type == KF_BF16, learning_rate, beta1, beta2, beta1_correction, beta2_correction, eps,
+                         weight_decay, 1.0f, seed, d_status, d_grad_scale));
+}
 
+// ---- gradient norms (kf_gradnorm.hip): every launch figure is kf::gradnorm_plan's
+size_t kf_grad_norms_scratch_bytes(int n_tensors, const long long* n) {
+    const kf::GradNormPlan p = kf::gradnorm_plan(n_tensors, n);
+    return p.status == KF_OK ? p.bytes : 0;
+}
+int kf_grad_norms_plan(kf_ctx* c, int n_tensors, const kf_bf16* const* grads, const long long* n, const uint8_t* no_clip, void* scratch, size_t scratch_bytes) {
+    CHKCTX(c);
+    if (n_tensors < 1 || n_tensors > kf::GN_MAX_TENSORS) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: n_tensors = %d outside [1, %d]", n_tensors, kf::GN_MAX_TENSORS);
+    if (!grads || !n) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: null pointer");
+    kf::GradNormPlan p = kf::gradnorm_plan(n_tensors, n);
+    if (p.status != KF_OK) {
+        if (p.bad >= 0 && (n[p.bad] < 8 || (n[p.bad] & 7))) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: n[%d] = %lld is not a positive multiple of 8", p.bad, n[p.bad]);
+        return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: the list is too long (tensor %d: more than 2^40 elements, or more than 2^31 - 1 chunks in all)", p.bad);
+    }
+    for (int i = 0; i < n_tensors; i++) {
+        if (!grads[i]) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: grads[%d] is null", i);
+        if (!al16(grads[i])) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: grads[%d] is not 16-byte aligned", i);
+    }
+    if (!scratch || (((uintptr_t)scratch) & 255)) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: scratch is missing or not 256-byte aligned");
+    if (scratch_bytes < p.bytes) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: scratch of %zu bytes, kf_grad_norms_scratch_bytes = %zu", scratch_bytes, p.bytes);
+    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_grad_norms_plan: not inside a graph capture (it copies the table with a blocking copy)");
+    std::vector<kf::GradNormEntry> tab((size_t)n_tensors + 1);
+    std::vector<int> wg0((size_t)n_tensors + 1);
+    kf::gradnorm_wg0(n_tensors, n, wg0.data());
+    for (int i = 0; i <= n_tensors; i++) {
+        kf::GradNormEntry& e = tab[i];
+        memset(&e, 0, sizeof(e));
+        e.wg0 = wg0[i];
+        if (i < n_tensors) e.g = (const uint16_t*)grads[i], e.n = n[i], e.no_clip = no_clip && no_clip[i];
+    }
+    static std::mutex mu;
+    static unsigned long long counter = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        p.stamp = kf::GN_STAMP0 + ++counter;
+    }
+    tab[n_tensors].n = (long long)p.stamp;
+    // every remembered layout whose bytes this scratch overlaps is forgotten first (the same scratch planned again, or memory that was freed and handed out anew),
+    // so that a failed copy leaves no stale layout behind
+    for (size_t k = c->gn_plans.size(); k-- > 0;) {
+        const char *a0 = (const char*)c->gn_plans[k].scratch, *a1 = a0 + c->gn_plans[k].plan.bytes, *b0 = (const char*)scratch, *b1 = b0 + p.bytes;
+        if (a0 < b1 && b0 < a1) c->gn_plans.erase(c->gn_plans.begin() + k);
+    }
+    HIPCHK(hipMemcpyAsync((char*)scratch + p.off_table, tab.data(), sizeof(kf::GradNormEntry) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->gn_plans.push_back(kf_ctx::GradNormSlot{scratch, p});
+    return KF_OK;
+}
+int kf_grad_norms_forget(kf_ctx* c, const void* scratch) {
+    CHKCTX(c);
+    for (size_t k = c->gn_plans.size(); k-- > 0;)
+        if (c->gn_plans[k].scratch == scratch) c->gn_plans.erase(c->gn_plans.begin() + k);
+    return KF_OK;
+}
+int kf_grad_norms(kf_ctx* c, const void* scratch, int n_tensors, int mode, float gclip, double* d_sumsq, float* d_gnorm, float* d_scale) {
+    CHKCTX(c);
+    if (!scratch || !d_sumsq || !d_gnorm || !d_scale) return fail(KF_INVALID_ARGS, "kf_grad_norms: null pointer");
+    if (n_tensors < 1) return fail(KF_INVALID_ARGS, "kf_grad_norms: n_tensors = %d", n_tensors);
+    if (((uintptr_t)scratch) & 255) return fail(KF_INVALID_ARGS, "kf_grad_norms: scratch is not 256-byte aligned");
+    if ((((uintptr_t)d_sumsq) & 7) || (((uintptr_t)d_gnorm) & 3) || (((uintptr_t)d_scale) & 3)) return fail(KF_INVALID_ARGS, "kf_grad_norms: a misaligned output (fp64 sums 8-byte, floats 4-byte)");
+    if (mode != KF_CLIP_REPORT && mode != KF_CLIP_TENSOR && mode != KF_CLIP_GLOBAL) return fail(KF_INVALID_ARGS, "kf_grad_norms: unknown mode %d", mode);
+    if (mode != KF_CLIP_REPORT && !(isfinite(gclip) && gclip > 0.0f)) return fail(KF_INVALID_ARGS, "kf_grad_norms: gclip = %g must be finite and > 0 in a clipping mode", (double)gclip);
+    const kf::GradNormPlan* p = nullptr;
+    for (const kf_ctx::GradNormSlot& s : c->gn_plans)
+        if (s.scratch == scratch) p = &s.plan;
+    if (!p) return fail(KF_INVALID_ARGS, "kf_grad_norms: this scratch holds no table of this context (kf_grad_norms_plan first)");
+    if (p->n_tensors != n_tensors) return fail(KF_INVALID_ARGS, "kf_grad_norms: n_tensors = %d, the scratch was planned for %d", n_tensors, p->n_tensors);
+    RET(kf::grad_norms_launch(c->stream, scratch, *p, mode, gclip, d_sumsq, d_gnorm, d_scale));
+}
 
 // ---- Muon (PIPE_Muon::CU_core, Optimizer.cu:498-583): kf_muon.hip
 static bool muon_dims_ok(int ne0, int ne1) { return ne1 >= 64 && ne0 >= ne1 && !(ne0 % 64) && !(ne1 % 64); }
@@ -1595,6 +1681,20 @@ int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
 int kfdbg_a8_plan(const kf::A8Problem* P, kf::A8Plan* out) {
     if (!P || !out) return -1;
     *out = kf::a8_plan(*P);
+    return 0;
+}
+// the table kf::gradnorm_plan lays out for a list of tensor lengths (no HIP call): wg0_out [n_tensors + 1], and for every workgroup the tensor gradnorm_find gives it
+// (owner_out [total_wg], may be NULL): tests/test_gradnorm_cpu.py
+int kfdbg_gradnorm_plan(int n_tensors, const long long* n, kf::GradNormPlan* out, int* wg0_out, int* owner_out) {
+    if (!out) return -1;
+    *out = kf::gradnorm_plan(n_tensors, n);
+    if (out->status != KF_OK || !wg0_out) return 0;
+    kf::gradnorm_wg0(n_tensors, n, wg0_out);
+    if (owner_out) {
+        std::vector<kf::GradNormEntry> tab((size_t)n_tensors + 1);
+        for (int i = 0; i <= n_tensors; i++) tab[i].wg0 = wg0_out[i];
+        for (int wg = 0; wg < out->total_wg; wg++) owner_out[wg] = kf::gradnorm_find(tab.data(), n_tensors, wg);
+    }
     return 0;
 }
 // the plan kf::a8_tile_plan makes for the same product on MFMA tiles (no HIP call): tests/test_a8_tiles_cpu.py

@@ -150,6 +150,35 @@ __device__ __forceinline__ double wave_sum_f64_fast(double v) {
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) { return wave_sum_f64_fast(v); }
+// The two fixed-order fp64 sums behind every deterministic sum of squares (kf_muon.hip, kf_gradnorm.hip): ONE body each, so the orders cannot drift apart.
+// A workgroup of NT threads (every thread calls): butterfly inside each wave, then the NT / 64 waves in wave order from 0; thread 0 stores the sum to *out.
+template <int NT>
+__device__ __forceinline__ void block_sum_f64(double ss, double* __restrict__ out) {
+    __shared__ double red[NT / 64];
+    ss = wave_sum_f64(ss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; w++) tot += red[w];
+        *out = tot;
+    }
+}
+// partials[0 .. np) by a workgroup of 256 threads: thread t adds its contiguous run of ceil(np / 256) in order from 0, thread 0 adds the 256 runs in order from 0;
+// the return value is the sum in thread 0 (only there)
+__device__ __forceinline__ double runs_sum_f64(const double* __restrict__ partials, int np) {
+    __shared__ double red[256];
+    const int per = (np + 255) / 256, b = threadIdx.x * per, e = b + per < np ? b + per : np;
+    double s = 0.0;
+    for (int i = b; i < e; i++) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    double tot = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 256; i++) tot += red[i];
+    return tot;
+}
 // fp32 sum / max over the whole wave, VALU only (no LDS round trips): DPP inside the rows, row swaps across them
 __device__ __forceinline__ float wave_sum(float v) {
     v += dpp_f<0xB1>(v);

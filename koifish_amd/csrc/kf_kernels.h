@@ -214,7 +214,7 @@ int embed_launch(hipStream_t st, const kf_weight* w, int token, const int32_t* d
                  uint16_t* out, int n_tok = 1);
 int dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out, int ilv_n = 1, int ilv_i = 0); /* ilv_n > 1: rows interleaved with ilv_n - 1 other matrices in blocks of 16 (kf_ops.hip) */
 int adamw_launch(hipStream_t st, uint16_t* params, uint16_t* grads, void* gm, void* gv, size_t n, int mv_bf16, float lr, float beta1, float beta2, float b1c,
-                 float b2c, float eps, float wd, float grad_scale, unsigned int seed, int* status);
+                 float b2c, float eps, float wd, float grad_scale, unsigned int seed, int* status, const float* d_grad_scale = nullptr); /* d_grad_scale != NULL: *d_grad_scale replaces grad_scale */
 // ---- Muon (kf_muon.hip): PIPE_Muon::CU_core.  One scratch per tensor shape: A, B [ne1][ne1] bf16, two X buffers [ne0][ne1] bf16, one fp64 partial per 4096 elements, two doubles
 struct MuonLayout {
     size_t A, B, X0, X1, part, dbl, bytes; /* byte offsets, each a multiple of 256 */

@@ -19,32 +19,12 @@ namespace kf {
 
 constexpr int MUON_T = 512, MUON_EPT = 8, MUON_PER_WG = MUON_T * MUON_EPT; /* TASKA_1p1 (packedN.cuh:612-643): 512 threads x 8 bf16, as adamw_kernel */
 
-// the workgroup's fp64 sum in a fixed order: butterfly inside each wave, then the 8 waves in wave order
-__device__ __forceinline__ void muon_block_sum(double ss, double* __restrict__ partials) {
-    __shared__ double red[MUON_T / 64];
-    ss = wave_sum_f64(ss);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-#pragma unroll
-        for (int w = 0; w < MUON_T / 64; w++) tot += red[w];
-        partials[blockIdx.x] = tot;
-    }
-}
-// partials[0 .. np) added in workgroup order: thread t adds its contiguous run in order, thread 0 adds the 256 runs in order
+// the workgroup's fp64 sum in a fixed order: butterfly inside each wave, then the 8 waves in wave order (block_sum_f64, kf_device.h)
+__device__ __forceinline__ void muon_block_sum(double ss, double* __restrict__ partials) { block_sum_f64<MUON_T>(ss, partials + blockIdx.x); }
+// partials[0 .. np) added in workgroup order: thread t adds its contiguous run in order, thread 0 adds the 256 runs in order (runs_sum_f64, kf_device.h)
 __global__ void __launch_bounds__(256) muon_sum_kernel(const double* __restrict__ partials, int np, double* __restrict__ out) {
-    __shared__ double red[256];
-    const int per = (np + 255) / 256, b = threadIdx.x * per, e = b + per < np ? b + per : np;
-    double s = 0.0;
-    for (int i = b; i < e; i++) s += partials[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int i = 0; i < 256; i++) tot += red[i];
-        *out = tot;
-    }
+    const double tot = runs_sum_f64(partials, np);
+    if (threadIdx.x == 0) *out = tot;
 }
 
 __global__ void __launch_bounds__(MUON_T) muon_momentum_kernel(uint16_t* __restrict__ mG, const uint16_t* __restrict__ grads, uint16_t* __restrict__ X, size_t n, float one_minus_mu,

@@ -859,9 +859,10 @@ int quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src, int
 template <bool MV_BF16>
 __global__ void __launch_bounds__(512) adamw_kernel(uint16_t* __restrict__ params, uint16_t* __restrict__ grads, void* __restrict__ gm_, void* __restrict__ gv_, size_t n,
                                                     float lr, float beta1, float beta2, float b1c, float b2c, float eps, float wd, float grad_scale, unsigned int seed,
-                                                    int* __restrict__ status) {
+                                                    int* __restrict__ status, const float* __restrict__ d_grad_scale) {
     const size_t idx = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     if (idx >= n) return;
+    if (d_grad_scale) grad_scale = *d_grad_scale; /* kf_adamw_scaled: the scale read on the device (a clip factor of kf_grad_norms), in place of the by-value float */
     const unsigned int thr = squirrel5(threadIdx.x + 198491317u * (blockIdx.x * blockDim.x), seed) & 0xFFFFu;
     const u32x4 P = *reinterpret_cast<const u32x4*>(params + idx), G = *reinterpret_cast<const u32x4*>(grads + idx);
     const uint32_t pw[4] = {P.x, P.y, P.z, P.w}, gw[4] = {G.x, G.y, G.z, G.w};
@@ -917,14 +918,14 @@ __global__ void __launch_bounds__(512) adamw_kernel(uint16_t* __restrict__ param
     }
 }
 int adamw_launch(hipStream_t st, uint16_t* params, uint16_t* grads, void* gm, void* gv, size_t n, int mv_bf16, float lr, float beta1, float beta2, float b1c,
-                 float b2c, float eps, float wd, float grad_scale, unsigned int seed, int* status) {
+                 float b2c, float eps, float wd, float grad_scale, unsigned int seed, int* status, const float* d_grad_scale) {
     if (n == 0 || n % 8) return KF_INVALID_ARGS;
     const size_t nthread = n / 8;
     const unsigned blocks = (unsigned)((nthread + 511) / 512);
     if (mv_bf16)
-        hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(512), 0, st, params, grads, gm, gv, n, lr, beta1, beta2, b1c, b2c, eps, wd, grad_scale, seed, status);
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(512), 0, st, params, grads, gm, gv, n, lr, beta1, beta2, b1c, b2c, eps, wd, grad_scale, seed, status, d_grad_scale);
     else
-        hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(512), 0, st, params, grads, gm, gv, n, lr, beta1, beta2, b1c, b2c, eps, wd, grad_scale, seed, status);
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(512), 0, st, params, grads, gm, gv, n, lr, beta1, beta2, b1c, b2c, eps, wd, grad_scale, seed, status, d_grad_scale);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

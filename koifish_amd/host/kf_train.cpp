@@ -295,5 +295,7 @@ int kfh_gpt2_eval(void* h, const int32_t* d_ids, const int32_t* d_tgt, int mode,
     koifish::g_train_err.clear();
     return Gpt2(h)->Eval(d_ids, d_tgt, mode, branch, d_loss_out);
 }
+// gradient norms and clipping: TrainerCore::SetGradClip / GradClipScratchBytes / GradNorms (kf_train_common.hpp)
+KFH_GRAD_CLIP_ENTRIES(gpt2, koifish::g_train_err)
 const char* kfh_gpt2_last_error(void) { return koifish::g_train_err.c_str(); }
 }

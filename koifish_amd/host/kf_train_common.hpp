@@ -2,10 +2,12 @@
 // table of trained tensors, its registration in both forms (shadow weights / "train_target": "gama"), SLP::Back for one matrix, the optimiser switch and the update loop
 // with its seed rule -- and the step around them: Update, Step, the head product + fused classifier that ends every Forward (HeadLoss), the head's backward that starts
 // every Backward (HeadBack).  A trainer adds its own activations, Ready, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
+// Gradient norms and clipping (SetGradClip) live here too: one kf_grad_norms call at the head of the update, the clip factors read on the device by kf_adamw_scaled.
 // The handle behind the C ABI of both families is the TrainerCore*: the entries the families share call through it (Core), a family's own cast down from it.
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "kf_host.hpp"
@@ -40,8 +42,18 @@ struct TrainerCore {
     size_t sc_muon_bytes = 0;
     void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (SetGamaScratch)
     size_t sc_gama_bytes = 0;
+    // gradient norms and clipping (SetGradClip): CLIP_REPORT / _TENSOR / _GLOBAL are kf_clip_mode's values.  The caller's scratch holds kf_grad_norms' table and
+    // partials, then d_sumsq [n + 1] fp64, d_gnorm [n + 1] float, d_scale [n] float (each part rounded up to 256 bytes); n = params.size()
+    enum { CLIP_OFF = 0, CLIP_REPORT = KF_CLIP_REPORT, CLIP_TENSOR = KF_CLIP_TENSOR, CLIP_GLOBAL = KF_CLIP_GLOBAL };
+    int clip_mode = CLIP_OFF;
+    float gclip = 1.0f;
+    bool clip_stale = false;   // a tensor was registered again, or the optimiser switched, after SetGradClip: the table or its Muon mask no longer holds
+    bool norms_valid = false;  // an update has filled d_gnorm since SetGradClip
+    void* sc_clip = nullptr;
+    double* d_sumsq = nullptr;
+    float *d_gnorm = nullptr, *d_scale = nullptr;
 
-    virtual ~TrainerCore() {}
+    virtual ~TrainerCore() {}  // touches no context (it may be gone already): the owner of a clip scratch switches clipping off before it frees the scratch
     virtual bool InSection(size_t) const { return true; }  // Update leaves a tensor outside the active section alone (EOE)
     virtual int Ready() const = 0;  // everything registered that a step reads (ParamsReady + the trainer's own activations and buffers)
     virtual int Forward(const int32_t* d_ids, const int32_t* d_tgt) = 0;
@@ -71,8 +83,62 @@ struct TrainerCore {
             method = keep;
             if (!ok || scratch_bytes < need) return KF_INVALID_ARGS;
         }
+        if (clip_mode != CLIP_OFF && method_ != method) clip_stale = true; /* the table masks the Muon tensors */
         method = method_, lr_scale = lr_scale_, mui = mui_, eps_muon = eps_muon_, tp_decay = tp_decay_, sc_muon = scratch, sc_muon_bytes = scratch_bytes;
         return KF_OK;
+    }
+    // ---- gradient norms and clipping.  The reference: a norm per tensor with a blocking read-back (GTensor::Length), grad_scale = gnorm > gclip ? gclip / gnorm : 1
+    // on the host (Optimizer.cu:756-774), Optimizer::gClip over the whole gradient (Optimizer.cpp:276-308), |g| = sqrt(sum gnorm^2) printed with the loss.
+    static size_t Up256(size_t v) { return (v + 255) & ~(size_t)255; }
+    bool AllRegistered() const {
+        for (const TrainTensor& e : params)
+            if (!e.p || !e.g || !e.m || !e.v || e.n < 8 || (e.n & 7)) return false;
+        return !params.empty();
+    }
+    // the table and partials of kf_grad_norms over the registered lengths, then the three output arrays; 0 before every tensor is registered
+    size_t GradClipScratchBytes() const {
+        if (!AllRegistered()) return 0;
+        std::vector<long long> n(params.size());
+        for (size_t i = 0; i < params.size(); i++) n[i] = params[i].n;
+        const size_t tab = kf_grad_norms_scratch_bytes((int)n.size(), n.data());
+        return tab ? tab + Up256(8 * (n.size() + 1)) + Up256(4 * (n.size() + 1)) + Up256(4 * n.size()) : 0;
+    }
+    // mode CLIP_OFF: nothing is launched by the update (the default; scratch is not looked at).  Otherwise the table over EVERY registered tensor's g / n is written
+    // to the caller's scratch (device memory, 256-byte aligned, at least GradClipScratchBytes()), the Muon tensors masked to 1.0f: the reference's Muon path reads the
+    // raw gradient.  They still count in the total, which is the reported |g|.  A refusal changes nothing; *why says which (empty: kf_last_error does).
+    int SetGradClip(int mode, float gclip_, void* scratch, size_t scratch_bytes, std::string* why) {
+        auto refuse = [why](const char* msg) {
+            if (why) *why = msg;
+            return (int)KF_INVALID_ARGS;
+        };
+        if (mode != CLIP_OFF && mode != CLIP_REPORT && mode != CLIP_TENSOR && mode != CLIP_GLOBAL) return refuse("set_grad_clip: unknown mode (0 off, 1 report, 2 tensor, 3 global)");
+        if (mode == CLIP_OFF) {
+            if (sc_clip) (void)kf_grad_norms_forget(ctx, sc_clip);
+            clip_mode = CLIP_OFF, clip_stale = false, norms_valid = false, sc_clip = nullptr, d_sumsq = nullptr, d_gnorm = d_scale = nullptr;
+            return KF_OK;
+        }
+        if (mode != CLIP_REPORT && !(std::isfinite(gclip_) && gclip_ > 0.0f)) return refuse("set_grad_clip: gclip must be finite and > 0");
+        const size_t need = GradClipScratchBytes();
+        if (!need) return refuse("set_grad_clip: every tensor must be registered first");
+        if (!scratch || ((uintptr_t)scratch & 255)) return refuse("set_grad_clip: scratch is missing or not 256-byte aligned");
+        if (scratch_bytes < need) return refuse("set_grad_clip: scratch shorter than grad_clip_scratch_bytes");
+        const size_t nt = params.size();
+        std::vector<long long> n(nt);
+        std::vector<const kf_bf16*> g(nt);
+        std::vector<uint8_t> mask(nt);
+        for (size_t i = 0; i < nt; i++) n[i] = params[i].n, g[i] = params[i].g, mask[i] = IsMuon(i) ? 1 : 0;
+        const size_t tab = kf_grad_norms_scratch_bytes((int)nt, n.data());
+        KF_TRY(kf_grad_norms_plan(ctx, (int)nt, g.data(), n.data(), mask.data(), scratch, tab));
+        if (sc_clip && sc_clip != scratch) (void)kf_grad_norms_forget(ctx, sc_clip); /* the scratch this one replaces is the caller's to free from here on */
+        char* const sc = (char*)scratch;
+        sc_clip = scratch, d_sumsq = (double*)(sc + tab), d_gnorm = (float*)(sc + tab + Up256(8 * (nt + 1))), d_scale = (float*)(sc + tab + Up256(8 * (nt + 1)) + Up256(4 * (nt + 1)));
+        clip_mode = mode, gclip = mode == CLIP_REPORT ? 1.0f : gclip_, clip_stale = false, norms_valid = false;
+        return KF_OK;
+    }
+    // the one host read: d_gnorm of the last update, h_out [params.size() + 1] (registration order, then |g| of the whole gradient).  Never inside Update.
+    int GradNorms(float* h_out, int n) {
+        if (!h_out || clip_mode == CLIP_OFF || !norms_valid || n != (int)params.size() + 1) return KF_INVALID_ARGS;
+        return kf_d2h(ctx, h_out, d_gnorm, sizeof(float) * (size_t)n);
     }
     // blob: the descriptor of what the forward reads (null: the tensor is not multiplied as a weight); requant != 0: kf_quantize(blob, master) after every update
     int SetParam(int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
@@ -80,6 +146,7 @@ struct TrainerCore {
         TrainTensor& e = params[index];
         e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false;
         if (blob) e.blob = *blob;
+        if (clip_mode != CLIP_OFF) clip_stale = true;
         return KF_OK;
     }
     // "train_target": "gama" for one of a layer's weight matrices: blob a PackedQ group storage; the parameter is ITS [ZERO nGroup][STEP nGroup] slice
@@ -92,6 +159,7 @@ struct TrainerCore {
         e.blob = *blob;
         e.p = const_cast<kf_bf16*>(blob->gama) + blob->ne0 + blob->ne1, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = 2LL * blob->nGroup;
         e.decay = false, e.has_blob = true, e.requant = false, e.gama = true;
+        if (clip_mode != CLIP_OFF) clip_stale = true;
         return KF_OK;
     }
     // kf_gama_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_gama_backward_scratch_bytes of every gama tensor at the step's rows
@@ -100,8 +168,10 @@ struct TrainerCore {
         sc_gama = scratch, sc_gama_bytes = bytes;
         return KF_OK;
     }
-    // every tensor registered; every gama tensor a shape the entry takes, with scratch; no dequant arena beside a gama tensor
+    // every tensor registered; every gama tensor a shape the entry takes, with scratch; no dequant arena beside a gama tensor; the clip table, if any, still the
+    // registered tensors'
     int ParamsReady() const {
+        if (clip_stale) return KF_INVALID_ARGS;
         for (const TrainTensor& e : params)
             if (!e.p || !e.g || !e.m || !e.v || e.n < 8 || (e.n & 7)) return KF_INVALID_ARGS;
         for (size_t i = 0; i < params.size(); i++)
@@ -128,8 +198,14 @@ struct TrainerCore {
     // reference draws one per tensor update), then the re-quantisation of every quantised matrix from its updated master.  kf_adamw zeroes the gradients it has
     // consumed.  With the Muon switch a Muon tensor takes PIPE_Muon::CU_core instead (kf_muon: mG is its m buffer, v is not touched; lr x lr_scale, the weight decay
     // by tpDecay, Pipe.cpp:23-37; the same seed as its AdamW launch would have had).
+    // With SetGradClip: first ONE kf_grad_norms over every registered tensor (a tensor outside the active section holds a zero gradient and adds nothing), then
+    // every AdamW tensor -- gama tensors among them -- reads its clip factor on the device (kf_adamw_scaled); a Muon tensor is left as it is.  No host read.
     int UpdateParams(float lr, double beta1, double beta2, float eps, float wd, uint32_t seed) {
         t++;
+        if (clip_mode != CLIP_OFF) {
+            KF_TRY(kf_grad_norms(ctx, sc_clip, (int)params.size(), clip_mode, gclip, d_sumsq, d_gnorm, d_scale));
+            norms_valid = true;
+        }
         const float b1c = (float)(1.0 - std::pow(beta1, (double)t)), b2c = (float)(1.0 - std::pow(beta2, (double)t)); /* the bias corrections, in double like the host side of the reference */
         for (size_t i = 0; i < params.size(); i++) {
             if (!InSection(i)) continue; /* a tensor of another branch: not touched, its seed index skipped */
@@ -141,8 +217,12 @@ struct TrainerCore {
                 if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
                 continue;
             }
-            KF_TRY(kf_adamw(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f, 1.0f,
-                            sd, nullptr));
+            if (clip_mode != CLIP_OFF)
+                KF_TRY(kf_adamw_scaled(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f,
+                                       d_scale + i, sd, nullptr));
+            else
+                KF_TRY(kf_adamw(ctx, e.p, e.g, e.m, e.v, (size_t)e.n, KF_BF16, lr, (float)beta1, (float)beta2, b1c, b2c, eps, e.decay ? wd : 0.0f, 1.0f,
+                                sd, nullptr));
             if (e.requant) KF_TRY(kf_quantize(ctx, &e.blob, e.p, 0));
         }
         return KF_OK;
@@ -173,5 +253,20 @@ struct TrainerCore {
 };
 
 inline TrainerCore* Core(void* h) { return static_cast<TrainerCore*>(h); }  // the handle of kfh_gpt2_* / kfh_qwen3t_*
+
+// The gradient-clipping entries of a family, from one place: kfh_<fam>_set_grad_clip (mode 0 off, else kf_clip_mode; the reason of a refusal in the family's error
+// string `err`, which kfh_<fam>_last_error hands out), kfh_<fam>_grad_clip_scratch_bytes, kfh_<fam>_grad_norms (h_out: float [n_params + 1], the last one |g|).
+#define KFH_GRAD_CLIP_ENTRIES(fam, err)                                                                                         \
+    int kfh_##fam##_set_grad_clip(void* h, int mode, float gclip, void* scratch, size_t scratch_bytes) {                        \
+        (err).clear();                                                                                                          \
+        return koifish::Core(h)->SetGradClip(mode, gclip, scratch, scratch_bytes, &(err));                                      \
+    }                                                                                                                           \
+    size_t kfh_##fam##_grad_clip_scratch_bytes(void* h) { return koifish::Core(h)->GradClipScratchBytes(); }                    \
+    int kfh_##fam##_grad_norms(void* h, float* h_out, int n) {                                                                  \
+        (err).clear();                                                                                                          \
+        const int rc = koifish::Core(h)->GradNorms(h_out, n);                                                                   \
+        if (rc == KF_INVALID_ARGS) (err) = "grad_norms: needs set_grad_clip, an update since, and room for n_params + 1 floats"; \
+        return rc;                                                                                                              \
+    }
 
 }  // namespace koifish

@@ -197,5 +197,7 @@ int kfh_qwen3t_set_optimizer(void* h, int method, float lr_scale, float mui, flo
     return Core(h)->SetOptimizer(method, lr_scale, mui, eps_muon, tp_decay, scratch, scratch_bytes);
 }
 long long kfh_qwen3t_steps_taken(void* h) { return Core(h)->t; }
+// gradient norms and clipping: TrainerCore::SetGradClip / GradClipScratchBytes / GradNorms (kf_train_common.hpp)
+KFH_GRAD_CLIP_ENTRIES(qwen3t, koifish::g_q3t_err)
 const char* kfh_qwen3t_last_error(void) { return koifish::g_q3t_err.c_str(); }
 }

@@ -15,6 +15,8 @@ EVO_PSO, EVO_MIX, EVO_PSO_GA = 1, 2, 4   # enum kf_evo_algorithm = the live memb
 EVO_ALGORITHMS = {"pso": EVO_PSO, "mix": EVO_MIX, "pso_ga": EVO_PSO_GA}   # Fuyou_params::Algo2Name
 ENSEMBLE_AGGREGATION, ENSEMBLE_BRANCH = 0, 1   # kfh_gpt2_eval's mode
 QUANT_GROUP, QUANT_ROW_LUT, QUANT_ROW_RTN = 0, 1, 2  # kf_weight.quant
+CLIP_OFF, CLIP_REPORT, CLIP_TENSOR, CLIP_GLOBAL = 0, 1, 2, 3   # enum kf_clip_mode (0: the trainers' "off"; kf_grad_norms itself has no such mode)
+CLIP_MODES = {None: CLIP_OFF, "report": CLIP_REPORT, "tensor": CLIP_TENSOR, "global": CLIP_GLOBAL}
 NF4 = 1000  # not a typNUMBER: "Q4 with the normal-float quant card" (QUANT_MODE::RTNf) for the helpers that take a storage type
 
 # every symbol include/kf_abi.h declares (tests/test_abi_symbols.py checks the header against this list and the .so)
@@ -33,6 +35,7 @@ ABI_SYMBOLS = [
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
     "kf_evolve", "kf_loss_mean",
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
+    "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
 ]
 
 
@@ -44,6 +47,11 @@ class Weight(C.Structure):
     """struct kf_weight (include/kf_abi.h)"""
     _fields_ = [("data", C.c_void_p), ("gama", C.c_void_p), ("type", C.c_int32), ("ne0", C.c_int32), ("ne1", C.c_int32), ("nGroup", C.c_int32),
                 ("lGroup", C.c_int32), ("qMin", C.c_int32), ("qMax", C.c_int32), ("qBias", C.c_int32), ("qzeros", C.c_void_p), ("qscales", C.c_void_p), ("quant", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GradNormPlan(C.Structure):
+    """struct kf::GradNormPlan (csrc/kf_gradnorm_plan.h), as kfdbg_gradnorm_plan fills it"""
+    _fields_ = [("status", C.c_int), ("bad", C.c_int), ("n_tensors", C.c_int), ("total_wg", C.c_int), ("off_table", C.c_size_t), ("off_part", C.c_size_t), ("bytes", C.c_size_t), ("stamp", C.c_ulonglong)]
 
 
 # the entries of libkf_host.so that kfh_gpt2_* and kfh_qwen3t_* have with one signature: (name, argtypes, restype)
@@ -60,6 +68,9 @@ _TRAINER_ENTRIES = [
     ("step", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint32], C.c_int),
     ("set_optimizer", [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t], C.c_int),
     ("steps_taken", [C.c_void_p], C.c_longlong),
+    ("set_grad_clip", [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_size_t], C.c_int),
+    ("grad_clip_scratch_bytes", [C.c_void_p], C.c_size_t),
+    ("grad_norms", [C.c_void_p, C.c_void_p, C.c_int], C.c_int),
 ]
 _libs = None
 
@@ -91,6 +102,12 @@ def load():
         hip.kf_linear_multi_scratch_bytes.argtypes, hip.kf_linear_multi_scratch_bytes.restype = [C.c_int, C.c_void_p, C.c_int], C.c_size_t
         hip.kf_gateup_swiglu_batch.argtypes = [C.c_void_p, C.POINTER(Weight), C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_adamw.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_int] + [C.c_float] * 8 + [C.c_uint32, C.c_void_p]
+        hip.kf_adamw_scaled.argtypes = [C.c_void_p] * 5 + [C.c_size_t, C.c_int] + [C.c_float] * 7 + [C.c_void_p, C.c_uint32, C.c_void_p]
+        hip.kf_grad_norms_scratch_bytes.argtypes, hip.kf_grad_norms_scratch_bytes.restype = [C.c_int, C.c_void_p], C.c_size_t
+        hip.kf_grad_norms_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        hip.kf_grad_norms.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        hip.kf_grad_norms_forget.argtypes = [C.c_void_p, C.c_void_p]
+        hip.kfdbg_gradnorm_plan.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_muon_scratch_bytes.argtypes, hip.kf_muon_scratch_bytes.restype = [C.c_int, C.c_int], C.c_size_t
         hip.kf_muon_momentum.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_float, C.c_uint32, C.c_void_p]
         hip.kf_newton_schulz.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]

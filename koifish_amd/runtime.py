@@ -281,6 +281,33 @@ class Context:
         L.check(self.hip.kf_evolve(self.h, _ptr(x), _ptr(head), x.shape[0], x.shape[1], int(algorithm), alpha, social, t_crossover, seed & 0xFFFFFFFF), "kf_evolve")
         return x
 
+    def grad_norms_plan(self, grads, no_clip=None):
+        """kf_grad_norms_plan over a list of bf16 device tensors (each 16-byte aligned, a positive multiple of 8 elements; they must stay alive and in place): returns
+        the plan -- a dict that owns the scratch and the three device outputs `sumsq` fp64 [n + 1], `gnorm` fp32 [n + 1], `scale` fp32 [n] -- for grad_norms().
+        no_clip: optional list of flags, one per tensor: its scale is 1.0 in every mode."""
+        nt = len(grads)
+        n = (C.c_longlong * max(nt, 1))(*[g.numel() for g in grads])
+        ptrs = (C.c_void_p * max(nt, 1))(*[g.data_ptr() for g in grads])
+        mask = None if no_clip is None else (C.c_uint8 * max(nt, 1))(*[int(bool(f)) for f in no_clip])
+        need = self.hip.kf_grad_norms_scratch_bytes(nt, n)
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        sp = (ws.data_ptr() + 255) & ~255
+        L.check(self.hip.kf_grad_norms_plan(self.h, nt, ptrs, n, mask, C.c_void_p(sp), need), "kf_grad_norms_plan")
+        # (the plan dict keeps ws alive; a caller that drops a plan it will not use again may call kf_grad_norms_forget(ctx, scratch) first)
+        return dict(n=nt, ws=ws, scratch=sp, grads=list(grads), sumsq=torch.zeros(nt + 1, dtype=torch.float64, device=self.device),
+                    gnorm=torch.zeros(nt + 1, dtype=torch.float32, device=self.device), scale=torch.zeros(nt, dtype=torch.float32, device=self.device))
+
+    def grad_norms(self, plan, mode="report", gclip=1.0):
+        """kf_grad_norms: every tensor's sum of squares in one launch, fixed summation order, nothing read back.  mode "report" | "tensor" | "global" (or a kf_clip_mode
+        value).  Returns the plan's device tensors (sumsq, gnorm, scale); the last entry of sumsq / gnorm is the whole list's."""
+        if isinstance(mode, str):
+            if mode not in L.CLIP_MODES:
+                raise ValueError("grad_norms mode %r: 'report', 'tensor' or 'global'" % (mode,))
+            mode = L.CLIP_MODES[mode]
+        L.check(self.hip.kf_grad_norms(self.h, C.c_void_p(plan["scratch"]), plan["n"], int(mode), gclip, _ptr(plan["sumsq"]), _ptr(plan["gnorm"]), _ptr(plan["scale"])),
+                "kf_grad_norms")
+        return plan["sumsq"], plan["gnorm"], plan["scale"]
+
     def loss_mean(self, members):
         """kf_loss_mean over a list of fp32 [n] device tensors: ((m0 + m1) + m2 ...) / len(members) in fp32, one launch per member"""
         out = torch.empty_like(members[0])

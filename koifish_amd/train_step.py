@@ -50,6 +50,7 @@ class _TrainStep:
     _layer_noun = None     # what set_optimizer's refusal calls a layer matrix
     _reason_codes = None   # the return codes whose reason is in kfh_<_family>_last_error; None: every code
     optimizer = "adamw"
+    _clip = None           # (gclip, mode) of set_grad_clip, None: off
 
     def _begin(self, ctx, train_target, seed):
         """checks train_target before anything touches ctx; returns the device generator of the initial draws"""
@@ -157,9 +158,44 @@ class _TrainStep:
             sp = _align256(self._sc_muon.data_ptr())
         self._call("set_optimizer", int(method == "muon"), lr_scale, mui, eps, tp_decay, sp, nb)
         self.optimizer = method
+        if self._clip is not None:
+            self.set_grad_clip(*self._clip)   # the clip table masks the Muon tensors: written again for the new switch
+
+    def set_grad_clip(self, gclip=1.0, mode="tensor"):
+        """Gradient norms and clipping at the head of every update, on the device (kf_grad_norms: every tensor in one launch, a fixed summation order, no host read).
+        mode "tensor": each AdamW tensor's gradient is scaled by gclip / |g_i| where |g_i| > gclip (adam.gclip, the reference's per-tensor rule, Optimizer.cu:756-774);
+        "global": all by gclip / |g| of the whole gradient (Optimizer::gClip); "report": norms only, the update's bits are those of clipping off; None: off (the
+        default: nothing is launched).  Gama tensors are AdamW tensors; Muon tensors are never scaled (the reference's Muon path reads the raw gradient) and still
+        count in |g|.  Owns the scratch."""
+        if mode not in L.CLIP_MODES:
+            raise ValueError("grad clip mode %r: None, 'report', 'tensor' or 'global'" % (mode,))
+        sc, sp, nb = None, None, 0
+        if mode is not None:
+            nb = int(self._entry("grad_clip_scratch_bytes")(self.h))
+            sc = torch.empty(nb + 256, dtype=torch.uint8, device=self.ctx.device)
+            sp = _align256(sc.data_ptr())
+        self._call("set_grad_clip", L.CLIP_MODES[mode], gclip, sp, nb, check=self._check_host)
+        # only now: a refusal changes nothing in the trainer, which then still reads the scratch it had
+        self._sc_clip, self._clip = sc, (None if mode is None else (gclip, mode))
+
+    def grad_norms(self):
+        """|g_i| of every tensor at the last update, float32 numpy array in the order of self.params -- the one host read, made here and never inside update()"""
+        import numpy as np
+        out = np.empty(len(self.params) + 1, dtype=np.float32)
+        self._call("grad_norms", out.ctypes.data_as(C.c_void_p), out.size, check=self._check_host)
+        self._gnorm = float(out[-1])
+        return out[:-1]
+
+    def grad_norm(self):
+        """|g| of the whole gradient at the last update (the reference's g_step), Muon tensors included"""
+        self.grad_norms()
+        return self._gnorm
 
     def close(self):
         if getattr(self, "h", None):
+            if self._clip is not None and getattr(self.ctx, "h", None):
+                self._entry("set_grad_clip")(self.h, L.CLIP_OFF, 1.0, None, 0)   # the context forgets the scratch before it is freed
+                self._clip = None
             self._entry("destroy")(self.h)
             self.h = None
 
