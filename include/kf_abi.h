@@ -721,6 +721,35 @@ enum { KF_A8_TILE_MIN = 32 };
 int kf_linear_a8_tiles_status(const kf_weight* w, int nTok);
 int kf_linear_a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
 
+/* ---- int8 activations for 4-bit layers: W4 . A8, the integer form of KF_Q4 group storage.  Off unless called; the entries above keep refusing KF_Q4.
+ * THE DEFINITION (restated in numpy by tests/w4a8_restate.py):
+ *   activations: kf_act_quant_i8 above, unchanged -- q int8 [nTok][K], step_x fp32 [nTok].
+ *   product, per output row r and token t, groups g of 128 consecutive weights; code = the 4-bit value of the Packed128 stream (0 .. 15), qBias (0 or 8), ZERO[g], STEP[g]
+ *   from the blob (gama_T):
+ *     I_g = sum_{c in g} (code[c] - qBias) * q[t][c]  as int32;  |I_g| <= 128 * 15 * 127 = 243 840 < 2^24, so fp32(I_g) is exact;
+ *     S_g = sum_{c in g} q[t][c]                      as int32;  |S_g| <= 16 256;
+ *     p = fp32(STEP[g]) * fp32(I_g)   ONE IEEE fp32 multiply, one rounding: unlike the ternary case the product (8 + 18 significant bits) is NOT exact;
+ *     z = fp32(ZERO[g]) * fp32(S_g)   exact (8 + 14 significant bits);
+ *     c = p - z                       one fp32 subtract;
+ *     acc = 0;  acc = acc + c         for g = 0, 1, .. K/128 - 1: ONE ascending fp32 chain, one add per group.
+ *     The multiply, the subtract and the add are three separate roundings: no fused multiply-add stands in for any pair of them.  The order depends on K and g only --
+ *     never on lanes per row, tile, grid, chunk or nTok;
+ *     y = bf16_rn(step_x[t] * acc);  with bias: bf16_rn(step_x[t] * acc + bias[r]);  with residual: y = bf16(residual + bf16(..)), exactly as kf_linear_a8 writes it.
+ *   DEVIATIONS: (1) the weight is the affine STEP * (code - qBias) - ZERO WITHOUT the per-weight bf16 roundings of CU_Q128toX_ (bf16(bf16(step * (q - qBias)) - zero),
+ *   T.cu:274): the result differs from the bf16-activation route by more than the activation quantisation.  (2) the activation quantiser's deviation is the one stated
+ *   above (the absolute row maximum).
+ * kf_linear_w4a8: the mat-vec on v_dot4c_i32_i8; y [nTok][ne0], residual [nTok][ne0] may alias y.  Refusals (kf::w4a8_plan, csrc/kf_w4a8_plan.h), in kf_linear_a8's order and
+ * with its codes: any storage other than KF_Q4 in KF_QUANT_GROUP form (AutoAWQ included) KF_UNSUPPORTED_DATATYPE; lGroup != 128, no gama, or a qBias other than 0 / 8
+ * KF_QUANT_ERR; ne1 % 128 != 0, ne0 < 1, nTok < 1 KF_INVALID_ARGS; data not 16-byte aligned KF_BLAS_UNALIGN.
+ * kf_linear_w4a8_tiles: the same contract and the same bits on v_mfma_i32_16x16x64_i8, for token batches (any nTok >= 1 is served; token and row tails masked); the launch
+ * is kf::w4a8_tile_plan's, its refusals are kf::w4a8_plan's.  q need not be 16-byte aligned.
+ * kf_linear_w4a8_status / kf_linear_w4a8_tiles_status: what the entry would answer for this weight and nTok, without a launch: the served-storage rule for callers that
+ * route (Fish asks it per layer matrix while kfh_set_act_int8_q4 is on).  KF_A8_TILE_MIN is the default threshold of this family too. */
+int kf_linear_w4a8_status(const kf_weight* w, int nTok);
+int kf_linear_w4a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
+int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok);
+int kf_linear_w4a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
+
 #ifdef __cplusplus
 }
 #endif

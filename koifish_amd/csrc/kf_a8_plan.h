@@ -30,6 +30,18 @@ struct A8Plan {
     int grid_x, grid_y, block, lds;
 };
 
+// lanes per row (log2) of the integer mat-vecs (this plan and kf_w4a8_plan.h): the largest power of two <= 64 that divides the row's groups; a row without such a factor of
+// at least 8 gets min(8, groups) lanes rounded down to a power of two, the tail of the last step masked
+inline int a8_lanes_log2(int n_groups) {
+    int l = 6;
+    while (l > 0 && (n_groups % (1 << l)) != 0) l--;
+    if (l < A8_LPR_MIN_LOG2) {
+        l = A8_LPR_MIN_LOG2;
+        while ((1 << l) > n_groups) l--;
+    }
+    return l;
+}
+
 inline A8Plan a8_plan(const A8Problem& P) {
     A8Plan p = {};
     auto refuse = [&p](int status) {
@@ -44,12 +56,7 @@ inline A8Plan a8_plan(const A8Problem& P) {
     if (!(m.al & GM_DATA_AL)) return refuse(KF_BLAS_UNALIGN);
     p.bits = m.type == KF_T_SIGN ? 2 : 1;
     p.order = A8_ORDER_CHAIN, p.n_groups = m.K / A8_GROUP;
-    int l = 6;
-    while (l > 0 && (p.n_groups % (1 << l)) != 0) l--;
-    if (l < A8_LPR_MIN_LOG2) {
-        l = A8_LPR_MIN_LOG2;
-        while ((1 << l) > p.n_groups) l--;
-    }
+    const int l = a8_lanes_log2(p.n_groups);
     p.lpr_log2 = l, p.iters = (p.n_groups + (1 << l) - 1) >> l;
     p.rows_per_wave = 64 >> l, p.rows_per_wg = p.rows_per_wave * (A8_THREADS / 64);
     p.tok_tile = P.nTok > 1 ? A8_TOK_TILE : 1;

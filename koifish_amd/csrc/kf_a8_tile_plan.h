@@ -32,6 +32,14 @@ struct A8TilePlan {
     int min_tok;             /* A8T_MIN_TOK, for callers that route */
 };
 
+// 16-token MFMA tiles per wave of the int8 tile kernels (this plan and kf_w4a8_plan.h): the widest token tile that still leaves A8T_FILL workgroups, and no wider than the batch
+inline int a8t_mfma_tok(int M, int n) {
+    const long gx = (M + A8T_ROW_TILE - 1) / A8T_ROW_TILE;
+    int t = A8T_MAX_TOK_TILES;
+    while (t > 1 && ((t / 2) * A8T_TOK_PER_MFMA >= n || gx * ((n + t * A8T_TOK_PER_MFMA - 1) / (t * A8T_TOK_PER_MFMA)) < A8T_FILL)) t /= 2;
+    return t;
+}
+
 inline A8TilePlan a8_tile_plan(const A8Problem& P) {
     A8TilePlan p = {};
     const A8Plan v = a8_plan(P);
@@ -42,9 +50,7 @@ inline A8TilePlan a8_tile_plan(const A8Problem& P) {
     p.waves = A8T_WAVES, p.row_tile = A8T_ROW_TILE;
     /* the widest token tile (an unpacked weight operand serves 4, 2 or 1 MFMA tiles) that still leaves A8T_FILL workgroups, and no wider than the batch: a small launch is
        one serial walk over K per workgroup, so there the narrow tile (more workgroups, each a quarter of the work) is the faster one */
-    const long gx = (M + A8T_ROW_TILE - 1) / A8T_ROW_TILE;
-    p.mfma_tok = A8T_MAX_TOK_TILES;
-    while (p.mfma_tok > 1 && ((p.mfma_tok / 2) * A8T_TOK_PER_MFMA >= n || gx * ((n + p.mfma_tok * A8T_TOK_PER_MFMA - 1) / (p.mfma_tok * A8T_TOK_PER_MFMA)) < A8T_FILL)) p.mfma_tok /= 2;
+    p.mfma_tok = a8t_mfma_tok(M, n);
     p.tok_tile = p.mfma_tok * A8T_TOK_PER_MFMA;
     p.chunk = p.n_groups < A8T_CHUNK ? p.n_groups : A8T_CHUNK;
     p.lds = p.tok_tile * p.chunk * A8_GROUP_LDS + p.row_tile * p.chunk * 4; /* the staged activations (with each group's sum of q) + the chunk's weight steps as fp32 */

@@ -13,6 +13,7 @@
 
 #include "kf_a8_plan.h"
 #include "kf_a8_tile_plan.h"
+#include "kf_w4a8_plan.h"
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
@@ -1657,6 +1658,46 @@ int kf_linear_a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const flo
     if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_a8_tiles: weight data not 16-byte aligned");
     if (p.status != KF_OK) return fail(p.status, "kf_linear_a8_tiles: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
     RET(kf::a8_tiles_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+
+// ---- int8 activations for 4-bit layers (include/kf_abi.h): every launch decision is kf::w4a8_plan's / kf::w4a8_tile_plan's
+static kf::W4A8Problem w4a8_problem(const kf_weight* w, int nTok) { return kf::W4A8Problem{kf::mat_of(w), nTok, w->qBias}; }
+static int w4a8_refusal(const char* entry, int status, const kf_weight* w, int nTok) {
+    if (status == KF_UNSUPPORTED_DATATYPE)
+        return fail(status, "%s: weight type %d (quant mode %d%s) has no W4.A8 form: served is KF_Q4 (%d) in group storage", entry, w->type, w->quant,
+                    (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_Q4);
+    if (status == KF_QUANT_ERR) return fail(status, "%s: group size %d (must be 128), gama missing, or qBias %d (must be 0 or 8)", entry, w->lGroup, w->qBias);
+    if (status == KF_BLAS_UNALIGN) return fail(status, "%s: weight data not 16-byte aligned", entry);
+    return fail(status, "%s: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", entry, w->ne0, w->ne1, nTok);
+}
+int kf_linear_w4a8_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::w4a8_plan(w4a8_problem(w, nTok)).status : KF_INVALID_ARGS; }
+int kf_linear_w4a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_w4a8: null weight");
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_w4a8: null pointer");
+    const kf::W4A8Plan p = kf::w4a8_plan(w4a8_problem(w, nTok));
+    if (p.status != KF_OK) return w4a8_refusal("kf_linear_w4a8", p.status, w, nTok);
+    RET(kf::w4a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::w4a8_tile_plan(w4a8_problem(w, nTok)).status : KF_INVALID_ARGS; }
+int kf_linear_w4a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_w4a8_tiles: null weight");
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_w4a8_tiles: null pointer");
+    const kf::W4A8TilePlan p = kf::w4a8_tile_plan(w4a8_problem(w, nTok));
+    if (p.status != KF_OK) return w4a8_refusal("kf_linear_w4a8_tiles", p.status, w, nTok);
+    RET(kf::w4a8_tiles_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+// the plans kf::w4a8_plan / kf::w4a8_tile_plan make (no HIP call): tests/test_w4a8_cpu.py
+int kfdbg_w4a8_plan(const kf::W4A8Problem* P, kf::W4A8Plan* out) {
+    if (!P || !out) return -1;
+    *out = kf::w4a8_plan(*P);
+    return 0;
+}
+int kfdbg_w4a8_tile_plan(const kf::W4A8Problem* P, kf::W4A8TilePlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::w4a8_tile_plan(*P);
+    return 0;
 }
 
 // the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py

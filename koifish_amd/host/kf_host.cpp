@@ -399,10 +399,16 @@ int Fish::A8Ready(int rows) {
     a8_rows = rows;
     return KF_OK;
 }
+// where a matrix goes in a batch of n token rows while either switch is on: 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
+int Fish::A8Route(const kf_weight& w, int n) const {
+    if (act_int8_q4 && kf_linear_w4a8_status(&w, n) == KF_OK) return 2; /* asked with the batch's n: the plan's LDS bound depends on it, and a refused matrix keeps kf_linear */
+    return (act_int8_t && a8_type(w)) ? 1 : 0;
+}
 int Fish::A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
     bool any8 = false, other = false;
     kf_weight wd[3];
-    for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), (a8_type(wd[i]) ? any8 : other) = true;
+    int route[3];
+    for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), route[i] = A8Route(wd[i], n), (route[i] ? any8 : other) = true;
     if (any8) KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8_q, a8_step));
     const floatX* xb = x;
     if (other && norm_w) {
@@ -411,17 +417,24 @@ int Fish::A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int d
     }
     for (int i = 0; i < n_w; i++) {
         const floatX* b = s[i]->b ? ToX(s[i]->b) : nullptr;
-        if (a8_type(wd[i])) {
+        if (route[i]) {
             const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
-            if (tiles)
-                KF_TRY(kf_linear_a8_tiles(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
+            if (route[i] == 2)
+                KF_TRY((tiles ? kf_linear_w4a8_tiles : kf_linear_w4a8)(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
             else
-                KF_TRY(kf_linear_a8(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
+                KF_TRY((tiles ? kf_linear_a8_tiles : kf_linear_a8)(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
             a8_count[tiles ? 0 : 1]++;
         } else
             KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], b, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
     }
     return KF_OK;
+}
+void Fish::A8Switched(bool was) {
+    act_int8 = act_int8_t || act_int8_q4;
+    if (act_int8 != was) {
+        DropEngineTable(); /* the captured graphs and the engine belong to the other arithmetic */
+        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use */
+    }
 }
 int Fish::SetActInt8(bool on, std::string& why) {
     if (on) {
@@ -466,11 +479,44 @@ int Fish::SetActInt8(bool on, std::string& why) {
         KF_TRY(A8Ready(1));
         a8_count[0] = a8_count[1] = 0;
     }
-    if (on != act_int8) {
-        DropEngineTable(); /* the captured graphs and the engine belong to the other arithmetic */
-        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use */
-        act_int8 = on;
+    const bool was = act_int8;
+    act_int8_t = on;
+    A8Switched(was);
+    return KF_OK;
+}
+int Fish::SetActInt8Q4(bool on, std::string& why) {
+    if (on) {
+        if (tp.world > 1) {
+            why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
+        int n4 = 0;
+        for (int l = 0; l < config.nLayer; l++) {
+            SelfAttention* a = attn[l].get();
+            FFN* m = ffn[l].get();
+            if (m->n_hot >= 0) {
+                why = "a hot-row mask is set on layer " + std::to_string(l) + ": the sparse forward has no int8-activation form";
+                return KF_INVALID_ARGS;
+            }
+            for (SLP* s : {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down}) {
+                if (!s->w) {
+                    why = "a layer matrix is missing";
+                    return KF_INVALID_ARGS;
+                }
+                const kf_weight w = s->w->desc();
+                if (kf_linear_w4a8_status(&w, 1) == KF_OK) n4++; /* the group ZERO is part of this arithmetic: no zero check */
+            }
+        }
+        if (!n4) {
+            why = "no layer matrix is 4-bit group storage that kf_linear_w4a8 serves (KF_Q4, groups of 128 with gama, qBias 0 or 8): nothing would take int8 activations";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
+        KF_TRY(A8Ready(1));
+        a8_count[0] = a8_count[1] = 0;
     }
+    const bool was = act_int8;
+    act_int8_q4 = on;
+    A8Switched(was);
     return KF_OK;
 }
 
@@ -1570,13 +1616,19 @@ int kfh_set_act_int8(void* h, int on) {
     if (rc != KF_OK) g_host_err = "kfh_set_act_int8: " + g_host_err;
     return rc;
 }
+// the same for the 4-bit layer matrices (kf_linear_w4a8 / kf_linear_w4a8_tiles): a second switch, independent of kfh_set_act_int8
+int kfh_set_act_int8_q4(void* h, int on) {
+    const int rc = reinterpret_cast<Fish*>(h)->SetActInt8Q4(on != 0, g_host_err);
+    if (rc != KF_OK) g_host_err = "kfh_set_act_int8_q4: " + g_host_err;
+    return rc;
+}
 // the token count from which a token batch's ternary / 1-bit matrices take the int8 MFMA tiles (kf_linear_a8_tiles) instead of the mat-vec (kf_linear_a8): n >= 2 sets it,
 // 1 is treated as 2 (a single token always takes the mat-vec), 0 restores the default (KF_A8_TILE_MIN), n < 0 = never.  Both routes give the same bits.
 int kfh_set_a8_tile_min(void* h, int n) {
     reinterpret_cast<Fish*>(h)->a8_tile_min = n == 0 ? (int)KF_A8_TILE_MIN : n == 1 ? 2 : n < 0 ? -1 : n;
     return KF_OK;
 }
-// (kf_linear_a8_tiles launches, kf_linear_a8 launches) since the last switch-on of kfh_set_act_int8
+// (tile launches, mat-vec launches) of both integer families since the last switch-on of kfh_set_act_int8 / kfh_set_act_int8_q4
 int kfh_a8_route_counts(void* h, int64_t* out2) {
     if (!h || !out2) return KF_INVALID_ARGS;
     const Fish* f = reinterpret_cast<Fish*>(h);

@@ -315,7 +315,10 @@ struct Fish : SeqBuffers {
     // kf_linear_a8 -- q | k | v share one quantisation of the normed row (the norm prologue), gate | up one, o_proj and down_proj quantise their own inputs; matrices of
     // any other storage keep kf_rmsnorm + kf_linear; embedding, final norm and LM head are untouched.  Token-serial steps and token batches alike, on per-layer launches
     // with the position from the host: the persistent engines and the captured graphs are not used while it is on.
-    bool act_int8 = false;
+    // act_int8 is "either switch is on": what the per-layer bodies, the engines and the TP step ask.  act_int8_t is kfh_set_act_int8's own state (ternary / 1-bit
+    // matrices -> kf_linear_a8), act_int8_q4 kfh_set_act_int8_q4's (include/kf_abi.h "int8 activations for 4-bit layers": KF_Q4 group matrices that
+    // kf_linear_w4a8_status serves -> kf_linear_w4a8 / kf_linear_w4a8_tiles; their ZERO need not be 0, the dequant arena is not consulted for them).
+    bool act_int8 = false, act_int8_t = false, act_int8_q4 = false;
     int8_t* a8_q = nullptr;     // [a8_rows][max(q_dim, nEmbed, n_ff)]
     float* a8_step = nullptr;   // [a8_rows]
     int a8_rows = 0;
@@ -324,6 +327,9 @@ struct Fish : SeqBuffers {
     int a8_tile_min = KF_A8_TILE_MIN;
     int64_t a8_count[2] = {0, 0};
     int SetActInt8(bool on, std::string& why);  // the switch-on checks: a ternary / 1-bit layer matrix exists, every ZERO section of those is zero, no hot-row mask
+    int SetActInt8Q4(bool on, std::string& why);  // the switch-on checks: a 4-bit layer matrix that kf_linear_w4a8 serves exists, no hot-row mask
+    int A8Route(const kf_weight& w, int n) const;  // 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
+    void A8Switched(bool was);  // after either switch moved: act_int8 = either; a change of it drops the engine table and the captured graphs
     int A8Ready(int rows);
     // the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual` (may alias y[0]; n_w == 1) kf_linear's
     // residual epilogue.  normed: [n][dim] for the bf16 route of matrices that have no integer form.

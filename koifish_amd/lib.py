@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "kf_tp_recv_bytes", "kf_tp_push_bytes", "kf_tp_commit", "kf_tp_alloc", "kf_tp_ipc_export", "kf_tp_ipc_open", "kf_tp_ipc_close", "kf_linear_f32_push", "kf_tp_reduce_recv", "kf_tp_lm_head", "kf_tp_pick",
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
     "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status", "kf_linear_a8_tiles", "kf_linear_a8_tiles_status",
+    "kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
     "kf_evolve", "kf_loss_mean",
@@ -158,6 +159,10 @@ def load():
         hip.kf_linear_a8.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_linear_a8_tiles_status.argtypes = [C.POINTER(Weight), C.c_int]
         hip.kf_linear_a8_tiles.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        hip.kf_linear_w4a8_status.argtypes = [C.POINTER(Weight), C.c_int]
+        hip.kf_linear_w4a8.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        hip.kf_linear_w4a8_tiles_status.argtypes = [C.POINTER(Weight), C.c_int]
+        hip.kf_linear_w4a8_tiles.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_embed.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_int, C.c_void_p, C.c_void_p]
         hip.kf_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -230,6 +235,7 @@ def load():
         host.kfh_num_graphs.argtypes = [C.c_void_p]
         host.kfh_set_engine.argtypes = [C.c_void_p, C.c_int]
         host.kfh_set_act_int8.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_set_act_int8_q4.argtypes = [C.c_void_p, C.c_int]
         host.kfh_set_a8_tile_min.argtypes = [C.c_void_p, C.c_int]
         host.kfh_a8_route_counts.argtypes = [C.c_void_p, C.c_void_p]
         host.kfh_engine_steps.argtypes = [C.c_void_p]

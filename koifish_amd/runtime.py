@@ -344,6 +344,24 @@ class Context:
         L.check(self.hip.kf_linear_a8_tiles(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8_tiles")
         return y
 
+    def linear_w4a8(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_w4a8: a 4-bit group weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
+        n = 1 if q.dim() == 1 else q.shape[0]
+        if y is None:
+            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
+        d = w.desc()
+        L.check(self.hip.kf_linear_w4a8(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_w4a8")
+        return y
+
+    def linear_w4a8_tiles(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_w4a8_tiles: linear_w4a8's contract and bits on int8 MFMA tiles, for token batches (any nTok >= 1 is served); residual may be y"""
+        n = 1 if q.dim() == 1 else q.shape[0]
+        if y is None:
+            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
+        d = w.desc()
+        L.check(self.hip.kf_linear_w4a8_tiles(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_w4a8_tiles")
+        return y
+
     def rmsnorm(self, x, w, eps=1e-6):
         y = torch.empty_like(x)
         rows = 1 if x.dim() == 1 else x.shape[0]
@@ -571,7 +589,7 @@ class Qwen3:
             return
         a = np.ascontiguousarray(hot, dtype=np.int32)
         rc = self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size)
-        if rc != 0 and getattr(self, "_act_int8", False):   # the one refusal the host explains: a mask while int8 activations are on (the text is set on that path only)
+        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False)):   # the one refusal the host explains: a mask while int8 activations are on (the text is set on that path only)
             raise L.KFError("kfh_set_hot failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         L.check(rc, "kfh_set_hot")
         if not hasattr(self, "_hot"):
@@ -592,13 +610,23 @@ class Qwen3:
             raise L.KFError("set_act_int8 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         self._act_int8 = bool(on)
 
+    def set_act_int8_q4(self, on):
+        """int8 activations for every 4-bit (KF_Q4 group storage) layer matrix (kf_act_quant_i8 + kf_linear_w4a8 / kf_linear_w4a8_tiles; include/kf_abi.h "int8 activations
+        for 4-bit layers"), in forward, run_steps, generate, prefill, score and perplexity, on per-layer launches.  A second switch, independent of set_act_int8: a mixed
+        model with both on sends its ternary / 1-bit matrices to kf_linear_a8 and its 4-bit ones to kf_linear_w4a8.  Raises with the reason when no layer matrix is
+        served or a hot-row mask is set."""
+        rc = self.host.kfh_set_act_int8_q4(self.h, int(bool(on)))
+        if rc != 0:
+            raise L.KFError("set_act_int8_q4 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+        self._act_int8_q4 = bool(on)
+
     def set_a8_tile_min(self, n):
         """token batches of at least n rows send their ternary / 1-bit matrices to the int8 MFMA tiles (kf_linear_a8_tiles) while int8 activations are on, smaller ones and
         single tokens to the mat-vec (kf_linear_a8): n >= 2 sets the threshold (1 is treated as 2), 0 restores the default (32), n < 0 = never.  The bits are the same."""
         L.check(self.host.kfh_set_a8_tile_min(self.h, int(n)), "kfh_set_a8_tile_min")
 
     def a8_route_counts(self):
-        """(kf_linear_a8_tiles launches, kf_linear_a8 launches) since the last set_act_int8(True)"""
+        """(tile launches, mat-vec launches) of both integer families (kf_linear_a8*, kf_linear_w4a8*) since the last set_act_int8(True) / set_act_int8_q4(True)"""
         out = (C.c_int64 * 2)()
         L.check(self.host.kfh_a8_route_counts(self.h, out), "kfh_a8_route_counts")
         return int(out[0]), int(out[1])
