@@ -256,13 +256,16 @@ __device__ __forceinline__ void g3_collect(const G3SkArgs& s, int slot, f32x4 (&
     }
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rs = g3_rsrc(s.ws + (size_t)slot * (C::BM * C::BN), C::BM * C::BN * 4);
+    // up to 8 loads in flight at a time (the accumulators hold half the register file); the 64 x 64 tile has MT NT = 4 accumulators per lane: one group of 4
+    constexpr int NACC = C::MT * C::NT, CH = NACC < 8 ? NACC : 8;
+    static_assert(NACC % CH == 0, "the accumulators are collected in whole groups");
 #pragma unroll
-    for (int g = 0; g < C::MT * C::NT / 8; g++) { /* 8 loads in flight at a time: the accumulators hold half the register file */
-        f32x4 pv[8];
+    for (int g = 0; g < NACC / CH; g++) {
+        f32x4 pv[CH];
 #pragma unroll
-        for (int i = 0; i < 8; i++) pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ((g * 8 + i) * C::NTH + tid) * 16, 0, 16 /* sc1 */));
+        for (int i = 0; i < CH; i++) pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ((g * CH + i) * C::NTH + tid) * 16, 0, 16 /* sc1 */));
 #pragma unroll
-        for (int i = 0; i < 8; i++) acc[(g * 8 + i) / C::NT][(g * 8 + i) % C::NT] += pv[i];
+        for (int i = 0; i < CH; i++) acc[(g * CH + i) / C::NT][(g * CH + i) % C::NT] += pv[i];
         asm volatile("" ::: "memory");
     }
 }

@@ -8,6 +8,8 @@ output is bf16(exact) BIT FOR BIT and nothing is measured.  Two groups:
                           contraction indices placed on a seam of the form under test; small-integer prior values for the beta = 1 epilogues
   one-hot / two-hot attention   q, k built so that each row's softmax is exactly {1} or {1/2, 1/2} on chosen keys and exactly 0 elsewhere after the
                           kernels' own fp32 arithmetic (tests/test_exact_inputs_cpu.py emulates that arithmetic and asserts it)
+  exact weights per storage   bf16, f8e5m2, 4-bit groups and row codebooks, ternary and 1-bit weights built from CHOSEN codes and CHOSEN (zero, step) tables that differ
+                          from group to group, each dequantising to small integers: the forward token-batch GEMMs' operands, and their case table FORWARD_CASES
 
 Every helper ASSERTS its precondition on the fp64 values it returns, so a badly chosen density or target pattern fails on the CPU, not on the GPU."""
 import ctypes as C
@@ -459,3 +461,281 @@ FWD_TILE_LONG = dict(n=257, nh=64, nkv=8, hd=64, n_seq=3)   # and the unpaired t
 FWD_POS0 = 37       # kf_attn_prefill behind a prefix of cache rows
 BWD_T = [8, 31, 33, 64, 129, 257, 300]
 N_SEQ = [1, 3]
+
+
+# ---------------------------------------------------------------------------------------------------------------- forward token-batch GEMMs: exact weights per storage
+# storage name -> (kf type, row codebook, symmetric range (qBias 8), group size)
+STORAGES = {
+    "bf16": (O.BF16, False, False, 128), "f8": (O.F8E5M2, False, False, 128),
+    "q4": (O.Q4, False, False, 128), "q4s": (O.Q4, False, True, 128), "q4g64": (O.Q4, False, False, 64), "q4sg64": (O.Q4, False, True, 64), "q4g256": (O.Q4, False, False, 256),
+    "tern": (O.T_SIGN, False, False, 128), "bool1": (O.BOOL1, False, False, 128), "tbin": (O.T_BINARY, False, False, 128), "bool1g256": (O.BOOL1, False, False, 256),
+    "lut": (O.Q4, True, False, 0),
+}
+# (lowest code, highest code, codes that may dequantise to 0, qBias): the code q' of an element is what the stream holds minus qBias
+_RANGES = {(O.Q4, False): (0, 15, (2, 5), 0), (O.Q4, True): (-8, 7, (-3, 3), 8), (O.T_SIGN, False): (-1, 1, (-1, 1), 1), (O.BOOL1, False): (0, 1, (0, 1), 0),
+           (O.T_BINARY, False): (0, 1, (0, 1), 0)}
+
+
+def _group_weight(rng, type_, symmetric, lgroup, M, K, d, signs):
+    """a group-quantised weight built from CHOSEN codes and CHOSEN (zero, step) tables: group g has step s_g in {1, 2} and zero s_g q0_g, so code q' dequantises to
+    s_g (q' - q0_g), an integer, and q0_g to 0.  (s, q0) is drawn per group and never equals the previous group's: two distinct maps q' -> s q' - zero agree on at
+    most one code and every group holds at least two (sparse family), so a table read at the neighbouring group's index changes an integer.
+    sparse (signs None): a fraction d of the entries holds another code -- 4-bit: q0 +- 1, q0 +- 2; ternary / 1-bit: one of the other codes of the range -- and, 4-bit,
+    one entry per group ANY code of the range (all 16 nibbles occur).  signs [M, K] in {-1, 0, 1}: code q0 + sign (4-bit only)."""
+    lo, hi, (z_lo, z_hi), qbias = _RANGES[(type_, symmetric)]
+    nG = M * K // lgroup
+    combos = np.array([(s, q) for s in (1, 2) for q in range(z_lo, z_hi + 1)])
+    idx = (rng.integers(0, len(combos)) + np.concatenate([[0], np.cumsum(rng.integers(1, len(combos), size=nG - 1))])) % len(combos)
+    assert (idx[1:] != idx[:-1]).all()
+    step, q0 = combos[idx, 0][:, None], combos[idx, 1][:, None]
+    if signs is not None:
+        assert hi - lo == 15
+        q = q0 + signs.reshape(nG, lgroup).astype(np.int64)
+    else:
+        on = rng.random((nG, lgroup)) < d
+        on[np.arange(nG), rng.integers(0, lgroup, size=nG)] = True   # at least two distinct codes per group
+        if hi - lo == 15:
+            other = q0 + rng.choice([-2, -1, 1, 2], size=(nG, lgroup))
+        else:
+            other = lo + (q0 - lo + rng.integers(1, hi - lo + 1, size=(nG, lgroup))) % (hi - lo + 1)
+        q = np.where(on, other, q0)
+        if hi - lo == 15:
+            q[np.arange(nG), rng.integers(0, lgroup, size=nG)] = rng.integers(lo, hi + 1, size=nG)
+        assert (q.min(axis=1) != q.max(axis=1)).all()
+    assert q.min() >= lo and q.max() <= hi
+    W = (step * (q - q0)).astype(np.float64).reshape(M, K)
+    ow = O.QWeight(type_, M, K, O.pack(q + qbias, O.BITS[type_]), exact_bits(step * q0).reshape(-1), exact_bits(step).reshape(-1), lgroup, qbias)
+    return W, ow
+
+
+def _lut_weight(rng, M, K, d):
+    """4-bit row codebook: row r's table is its own permutation of -8 .. 7 (neighbouring rows differ); an entry is 0 with probability 1 - d, else +-1 or +-2, and one
+    entry in 128 holds any of the 16 codes; the stream is MSB first, element 2 i in the high nibble of byte i"""
+    table = np.stack([rng.permutation(16) - 8 for _ in range(M)])
+    for r in np.nonzero((table[1:] == table[:-1]).all(axis=1))[0]:
+        table[r + 1] = np.roll(table[r + 1], 1)
+    assert not (table[1:] == table[:-1]).all(axis=1).any()
+    W = ternary(rng, (M, K), d, twos=True)
+    any_code = rng.random((M, K)) < 1.0 / 128
+    W = np.where(any_code, rng.integers(-8, 8, size=(M, K)), W)
+    code = np.argsort(table, axis=1)[np.arange(M)[:, None], W.astype(np.int64) + 8]   # the place of value v in the row's table
+    assert np.array_equal(np.take_along_axis(table, code, axis=1), W)
+    data = (code[:, 0::2] << 4 | code[:, 1::2]).astype(np.uint8)
+    return W, O.LutWeight(M, K, data, exact_bits(table), 4)
+
+
+def exact_weight(storage, M, K, seed, signs=None, d=None):
+    """(W fp64 integers [M, K], the oracle weight that holds exactly W) for every storage the tile kernels unpack (STORAGES).  d: the fraction of non-zero entries
+    (default density(K) on the second moment of the storage's non-zero values); signs [M, K] in {-1, 0, 1}: the block family's pattern -- bf16, f8 and the row codebook
+    hold it as it is, a 4-bit group g holds s_g x signs.  Asserted on the CPU: O.dequant(ow) == W."""
+    type_, row_lut, symmetric, lgroup = STORAGES[storage]
+    rng = np.random.default_rng(seed)
+    if row_lut:
+        assert signs is None
+        W, ow = _lut_weight(rng, M, K, density(K, 2.5) if d is None else d)
+    elif type_ in (O.BF16, O.F8E5M2):
+        W = ternary(rng, (M, K), density(K, 2.5) if d is None else d, twos=True) if signs is None else signs.astype(np.float64)
+        ow = O.quantize(exact_bits(W), M, K, type_)
+    else:
+        assert K % lgroup == 0 or lgroup % K == 0
+        m = {15: 2.5 * 2.5, 2: 2.5 * 2.5, 1: 2.5}[_RANGES[(type_, symmetric)][1] - _RANGES[(type_, symmetric)][0]]   # E[s^2] = 2.5 times E[(q' - q0)^2]
+        W, ow = _group_weight(rng, type_, symmetric, lgroup, M, K, density(K, m) if d is None else d, signs)
+    assert np.array_equal(O.dequant(ow), exact_bits(W)), "storage %s does not hold the weight exactly" % storage
+    return W, ow
+
+
+ALPHA, BETA = 0.5, 2.0   # the epilogue case
+
+
+def linear_forward_case(M, K, n, storage, seed, family="sparse", at=(), epilogue=False):
+    """operands and exact results of y [n, M] = x [n, K] . W^T, everything in fp64:
+    family "sparse": W by exact_weight, x random {-1, 0, 1} at the density that keeps the sum of K products' variance K d_x mean(W^2) <= 400 (density()'s bound)
+    family "block":  dense +-1 blocks of 128 contraction indices at the positions `at` (block_rows): W is +-1 (4-bit group g: +-s_g) on the union of the blocks' columns
+                     and 0 elsewhere, token row t is +-1 on block t mod len(at) and 0 elsewhere -- every output is a 128-term dense sum, one per listed seam
+    epilogue: also y0, bias [M], residual (small integers) and y_epi = bits(f64(bits(ALPHA acc + BETA y0 + bias)) + residual), with every intermediate asserted a
+              multiple of 1/2 below 2^23 in gemm_epilogue's order (alpha, beta y, bias, store, residual add, store)"""
+    rng = np.random.default_rng(seed)
+    if family == "sparse":
+        W, ow = exact_weight(storage, M, K, seed + 1)
+        x = ternary(rng, (n, K), min(0.5, 400.0 / (K * (W * W).mean())))
+        kk = slice(None)
+    else:
+        assert family == "block" and len(at)
+        blocks = [block_rows(K, a) for a in at]
+        kk = np.unique(np.concatenate(blocks))
+        signs = np.zeros((M, K))
+        signs[:, kk] = rng.choice([-1.0, 1.0], size=(M, len(kk)))
+        W, ow = exact_weight(storage, M, K, seed + 1, signs=signs)
+        x = np.zeros((n, K))
+        for j, blk in enumerate(blocks):
+            x[j::len(blocks), blk[0]:blk[-1] + 1] = rng.choice([-1.0, 1.0], size=(len(x[j::len(blocks)]), len(blk)))
+    acc = exact_product(x[:, kk], np.ascontiguousarray(W[:, kk].T))
+    c = dict(M=M, K=K, n=n, storage=storage, W=W, ow=ow, x=exact_bits(x), y=exact_bits(acc), f64=dict(x=x, acc=acc))
+    if epilogue:
+        y0, bias, res = small_ints(rng, (n, M)), small_ints(rng, M), small_ints(rng, (n, M))
+        v = acc
+        for step in (lambda v: ALPHA * v, lambda v: v + BETA * y0, lambda v: v + bias):
+            v = step(v)
+            assert np.array_equal(2 * v, np.rint(2 * v)) and np.abs(v).max() < 2.0 ** 23
+        y1 = f64(bits(v))   # the store may round a half above 128: the fp32 value it rounds is exact, so the rounding is the kernel's
+        v = y1 + res
+        assert np.array_equal(2 * v, np.rint(2 * v)) and np.abs(v).max() < 2.0 ** 23
+        c.update(y0=exact_bits(y0), bias=exact_bits(bias), residual=exact_bits(res), y_epi=bits(v), f64_epi=dict(y0=y0, bias=bias, residual=res))
+    return c
+
+
+# ---- the plan behind the forward entries (kf_gemm_plan.h gemm_plan through kfdbg_gemm_plan), the problem filled as kf_abi.hip problem_of fills it
+GE = dict(linear=0, multi=1, gateup=2, rope=3, rope_seqs=3)
+FWD_ROUTES = {0: "MATVEC", 1: "AWQ", 2: "ROWFORM", 3: "RESIDENT", 4: "DEQ_TILE", 5: "TILE", 6: "STACKED", 7: "SWIGLU", 8: "ROPE", 9: "FUSED", 10: "SEPARATE"}
+FMTS = {0: "bf16", 1: "f8", 2: "q4", 3: "q2", 4: "q1", 6: "q4r"}
+DQ_NONE, DQ_SCRATCH, DQ_ARENA, DQ_RESIDENT = range(4)
+SK_WS_BYTES = 256 * 256 * 256 * 4 + 8192   # gemm3_sk_ws_bytes(), kf_resident_scratch_bytes()
+ARENA_ROOM = 1 << 30
+
+
+def storage_mat(storage, M, K):
+    """kf::mat_of of an uploaded weight of this storage: data and row tables 16-byte aligned, gama present on the quantised forms"""
+    type_, row_lut, _, lgroup = STORAGES[storage]
+    return _Mat(type_, 1 if row_lut else 0, 0, M, K, lgroup, int(O.BITS[type_] < 8), 3)
+
+
+def forward_plan(hip, entry, storage, Ms, K, n, scratch=0, arena=False, arena_hit=0, arena_free=ARENA_ROOM):
+    """the plan of kf_linear / kf_linear_multi / kf_gateup_swiglu_batch / kf_qkv_rope_batch(_seqs) for weights [Ms[i], K] of one storage at n token rows: x, act, q and k
+    aligned, head_dim 128 with whole heads, `scratch` bytes lent through kf_set_scratch, an arena set or not and the copy found in it or not"""
+    hip.kfdbg_gemm_plan.argtypes = [C.POINTER(_Problem), C.POINTER(_Plan)]
+    P = _Problem(entry=GE[entry], n_w=len(Ms), n=n, x_al=1, y_al=1, rope_ok=int(GE[entry] == 3), arena=int(arena), arena_hit=arena_hit,
+                 arena_free=arena_free if arena else 0, scratch=scratch)
+    for i, M in enumerate(Ms):
+        P.w[i] = storage_mat(storage, M, K)
+    out = _Plan()
+    assert hip.kfdbg_gemm_plan(C.byref(P), C.byref(out)) == 0 and out.status == 0
+    return out
+
+
+def forward_name(p):
+    """"TILE/DIRECT/32/q4", "TILE/STAGED/KS2/q2", "TILE/G2/f8", "RESIDENT/G3/TINY/S2", "RESIDENT/G3/SMALL/tails", "SWIGLU/G3/WIDE", "FUSED/PAIRED/q4", "MATVEC", ...: route,
+    family, form, then the format the kernel unpacks (the kf_gemm3.hip tiles read bf16 only) or its split-K cut"""
+    route, k = FWD_ROUTES[p.route], p.k
+    fam = FAMILIES[k.fam]
+    if fam == "NONE":
+        return route
+    if fam == "G3":
+        return "%s/G3/%s%s" % (route, G3_FORMS[k.form], "" if not k.sk else ("/S%d" % k.S if k.S >= 2 else "/tails"))
+    form = {"DIRECT": "%d/" % k.form, "STAGED": "KS%d/" % k.form}.get(fam, "")
+    return "%s/%s/%s%s" % (route, fam, form, FMTS[k.fmt])
+
+
+# ---- the cases tests/test_gpu_exact_linear_forward.py runs: (entry, storage, rows of each matrix, K, n, family, setting) -> the plan's name (forward_name), pinned by
+# tests/test_exact_inputs_cpu.py.  setting: "" nothing lent; "scratch": what kf_linear_scratch_bytes / kf_linear_multi_scratch_bytes asks for (2 bytes per weight);
+# "arena": a dequant arena set and gemm3_sk_ws_bytes() lent (run filling, then finding the resident copy); "epi": the epilogue case (alpha, beta, bias, residual).
+# The smallest shapes that reach each form, K 256 unless the case is about K: the form does not depend on K apart from % 64, % 128 and the split-K depth.
+FORWARD_CASES = {}
+_IN_REGISTER = ("q4", "q4s", "f8", "tern", "bool1", "bf16")
+
+
+def _cases(want, entry, storages, shapes, K=256, family="sparse", setting=""):
+    for st in storages:
+        for Ms, n in shapes:
+            Ms = (Ms,) if isinstance(Ms, int) else tuple(Ms)
+            key = (entry, st, Ms, K, n, family, setting)
+            assert key not in FORWARD_CASES
+            FORWARD_CASES[key] = want.replace("*", FMTS[{O.BF16: 0, O.F8E5M2: 1, O.Q4: 6 if STORAGES[st][1] else 2, O.T_SIGN: 3}.get(STORAGES[st][0], 4)])
+
+
+# kf_linear on the weight as stored.  40 x 129: ragged rows and a one-row last token tile; 96 x 8: the first batch past the mat-vec loop
+_cases("TILE/DIRECT/32/*", "linear", _IN_REGISTER + ("tbin", "lut", "q4g256", "bool1g256"), [(40, 129), (96, 8)])
+_cases("TILE/DIRECT/32/*", "linear", ("lut",), [(96, 64)])
+_cases("TILE/STAGED/KS2/*", "linear", ("q4", "q4s", "f8", "tern", "bool1", "lut"), [(2048, 641), (1056, 1281)])
+_cases("TILE/STAGED/KS2/*", "linear", ("tbin",), [(2048, 641)])
+# bf16 storage on the in-register kernels past the direct kernel's size: kf_gemm3.hip declines a side below 128, the producer / consumer kernel 255 tokens or fewer
+_cases("TILE/STAGED/KS2/*", "linear", ("bf16",), [(16384, 96), (96, 16384)])
+_cases("TILE/STAGED/KS1/*", "linear", ("bf16", "q4", "f8"), [(65536, 96)])                # 512 staged tiles of which none is a producer / consumer tile: n < 256
+_cases("TILE/G2/*", "linear", ("bf16", "q4"), [(96, 32768)])                             # one ragged row tile of 96, 128 token tiles
+_cases("TILE/STAGED/KS2/*", "linear", ("q4g256", "bool1g256"), [(2048, 641)])
+_cases("TILE/STAGED/KS1/*", "linear", ("tern", "bool1", "tbin", "lut"), [(4096, 2048)])  # from 256 tokens only the formats without a producer / consumer kernel get here
+_cases("TILE/G2/*", "linear", ("q4", "q4s", "f8"), [(4096, 1024), (16384, 256)])
+_cases("TILE/G3/TINY", "linear", ("bf16",), [(1024, 256), (1056, 1281)])                 # 1056 x 1281: ragged both ways
+_cases("TILE/G3/MID", "linear", ("bf16",), [(2048, 641), (6400, 224)])                   # 6400 x 224: n < 256 past the direct kernel's size
+_cases("TILE/G3/SMALL", "linear", ("bf16",), [(4096, 1024), (2048, 2304)])
+_cases("TILE/G3/BIG", "linear", ("bf16",), [(4096, 2560)])
+# K a multiple of 64 only: the half-empty last staged tile of 128 and the clamped address (4-bit in groups of 64)
+for _K in (1600, 192):
+    _cases("TILE/DIRECT/32/*", "linear", ("q4g64", "q4sg64", "f8", "bf16"), [(96, 40)], K=_K)
+_cases("TILE/STAGED/KS2/*", "linear", ("q4g64", "f8"), [(1056, 1281)], K=1600)
+_cases("TILE/G3/TINY", "linear", ("bf16",), [(1056, 1281)], K=1600)
+_cases("MATVEC", "linear", _IN_REGISTER + ("lut",), [(96, 7)])                           # below GEMM_MIN: the mat-vec loop, the same expected bits
+_cases("TILE/DIRECT/32/*", "linear", ("q4",), [(40, 129)], setting="epi")
+_cases("TILE/STAGED/KS2/*", "linear", ("q4",), [(2048, 641)], setting="epi")
+_cases("TILE/G2/*", "linear", ("q4",), [(4096, 1024)], setting="epi")
+_cases("TILE/G3/SMALL", "linear", ("bf16",), [(4096, 1024)], setting="epi")
+_cases("TILE/G3/BIG", "linear", ("bf16",), [(4096, 2560)], setting="epi")
+# kf_linear on a bf16 copy: dequantised into the caller's scratch; resident in the arena with the 64-row tiles in k pieces (S of them, or the owner / helper cut)
+_cases("DEQ_TILE/G3/SMALL", "linear", ("q4", "tern"), [(4096, 2048), (1024, 4096)], setting="scratch")
+_cases("DEQ_TILE/G3/BIG", "linear", ("q4", "tern"), [(4096, 2560)], setting="scratch")
+for _fam in ("sparse", "block"):
+    _cases("RESIDENT/G3/TINY/S2", "linear", ("q4",), [(1024, 320)], K=1024, family=_fam, setting="arena")
+    _cases("RESIDENT/G3/TINY/S6", "linear", ("q4",), [(1024, 512)], K=3072, family=_fam, setting="arena")
+    _cases("RESIDENT/G3/MID/S2", "linear", ("q4",), [(1024, 1536)], K=1024, family=_fam, setting="arena")
+    _cases("RESIDENT/G3/MID/tails", "linear", ("q4",), [(2048, 1664)], K=2048, family=_fam, setting="arena")   # 32 x 13 = 416 tiles of 64 x 128: between 1/2 and 4/5 of 768
+    _cases("RESIDENT/G3/TINY/S3", "linear", ("q4",), [(1024, 1281)], K=2048, family=_fam, setting="arena")   # 32 k tiles in three pieces: cuts at 10 and 21
+_cases("RESIDENT/G3/TINY/S2", "linear", ("tern",), [(1024, 320)], K=1024, setting="arena")
+_cases("RESIDENT/DIRECT/32/bf16", "linear", ("q4",), [(128, 320)], setting="arena")      # K 256 is too shallow to cut: the copy on the plain forms
+_cases("RESIDENT/G3/TINY", "linear", ("q4",), [(1024, 320)], setting="arena")
+_cases("RESIDENT/G3/MID", "linear", ("q4",), [(1024, 1536)], setting="arena")
+_cases("RESIDENT/G3/SMALL", "linear", ("q4",), [(4096, 1024)], setting="arena")
+_cases("RESIDENT/G3/BIG", "linear", ("q4",), [(4096, 2560)], setting="arena")
+# kf_linear_multi: a distinct weight per matrix
+_cases("FUSED/DIRECT/32/*", "multi", ("q4", "tern"), [((256, 128, 128), 40)])
+_cases("FUSED/DIRECT/64/*", "multi", ("q4", "bool1"), [((1024, 256, 256), 321)])
+_cases("STACKED/G3/SMALL", "multi", ("q4",), [((512, 256, 256), 1024)], setting="scratch")
+_cases("STACKED/G3/BIG", "multi", ("q4",), [((4096, 4096), 2560)], setting="scratch")
+# kf_gateup_swiglu_batch: rows = ffn, twice
+_cases("FUSED/PAIRED/*", "gateup", ("q4", "tern"), [((288, 288), 100)])                  # ragged
+_cases("FUSED/PAIRED/*", "gateup", ("q4",), [((3072, 3072), 672)])                       # the largest paired grid
+_cases("SWIGLU/G3/SMALL", "gateup", ("q4",), [((768, 768), 1024)], setting="scratch")
+_cases("SWIGLU/G3/WIDE", "gateup", ("q4",), [((3072, 3072), 1536)], setting="scratch")
+_cases("SWIGLU/G3/BIG", "gateup", ("q4",), [((2560, 2560), 2049)], setting="scratch")
+# kf_qkv_rope_batch / kf_qkv_rope_seqs: head_dim 128, 4 heads over 2 kv heads
+_cases("ROPE/G3/SMALL", "rope", ("q4",), [((512, 256, 256), 1024), ((512, 256, 256), 1280)], setting="scratch")
+_cases("ROPE/G3/SMALL", "rope_seqs", ("q4",), [((512, 256, 256), 1024), ((512, 256, 256), 1280)], setting="scratch")
+ROPE_SEQ_LEN = {1024: 64, 1280: 160}   # tokens per sequence at each n: sequences that begin inside a 128-token tile
+
+# what the rule cannot reach, and why (tile_plan, g3_plain, gemm_plan_linear).  Every in-register family is reachable on every format that has it: bf16 storage
+# leaves kf_gemm3.hip for the staged and producer / consumer kernels with a side below 128, 4-bit and f8 reach staged KS 1 below 256 tokens -- cases above.
+FORWARD_UNREACHABLE = {
+    "TILE/G2/q2": "the ternary, 1-bit and row-codebook formats have no producer / consumer form",
+    "TILE/G2/q1": "as TILE/G2/q2", "TILE/G2/q4r": "as TILE/G2/q2",
+    "TILE/G3/WIDE": "192 x 256 tiles are the SwiGLU epilogue's alone (swiglu_kern)",
+    "DEQ_TILE/G3/TINY": "the route asks for >= 128 tiles of 256 x 256 or >= 256 of 128 x 128: never fewer than 256 small tiles, so never the 64-row forms",
+    "DEQ_TILE/G3/MID": "as DEQ_TILE/G3/TINY",
+    "RESIDENT/G3/SMALL/S*": "g3_plain lends the workspace to the 64-row tiles only",
+    "RESIDENT/G3/BIG/S*": "as RESIDENT/G3/SMALL/S*",
+    "RESIDENT/G3/TINY/tails": "the owner / helper cut needs more than 640 of the 1280 resident 64 x 64 tiles, i.e. more than 320 tiles of 64 x 128: those are taken from 192",
+}
+
+
+def case_setting(key):
+    """(scratch bytes lent, arena set) of a case, as its GPU test sets them"""
+    entry, st, Ms, K, n, family, setting = key
+    if setting == "scratch":
+        return (sum(Ms) if entry != "linear" else Ms[0]) * K * 2, False
+    return (SK_WS_BYTES, True) if setting == "arena" else (0, False)
+
+
+def case_plan(hip, key, arena_hit=0):
+    scratch, arena = case_setting(key)
+    return forward_plan(hip, key[0], key[1], key[2], key[3], key[4], scratch=scratch, arena=arena, arena_hit=arena_hit)
+
+
+def forward_case(hip, key):
+    """the operands of a case: one linear_forward_case per matrix sharing x (a distinct weight each); the block family's blocks on the seams of the case's own plan"""
+    entry, st, Ms, K, n, family, setting = key
+    seed = sum(Ms) + 3 * K + 7 * n + len(family) + sum(map(ord, st))
+    at = seams(case_plan(hip, key), K) if family == "block" else ()
+    c = linear_forward_case(Ms[0], K, n, st, seed, family, at, epilogue=setting == "epi")
+    c["more"] = []
+    for i, M in enumerate(Ms[1:]):
+        W, ow = exact_weight(st, M, K, seed + 101 * (i + 1))
+        acc = exact_product(c["f64"]["x"], np.ascontiguousarray(W.T))
+        c["more"].append(dict(M=M, W=W, ow=ow, y=exact_bits(acc)))
+    return c

@@ -1,5 +1,5 @@
-"""Everything about the exact-arithmetic inputs (tests/exact_inputs.py) that can be settled without a GPU, for every case tests/test_gpu_exact_linear_backward.py and
-tests/test_gpu_exact_attention.py run:
+"""Everything about the exact-arithmetic inputs (tests/exact_inputs.py) that can be settled without a GPU, for every case tests/test_gpu_exact_linear_backward.py,
+tests/test_gpu_exact_linear_forward.py and tests/test_gpu_exact_attention.py run:
 
   preconditions   every operand is a bf16 value, every expected accumulator an integer (or half) inside the bound -- asserted by the helpers as the cases are built
   probabilities   an fp32 emulation of the softmax statistics AS THE KERNELS COMPUTE THEM (running maximum per key tile, exp2 of score x scale x log2 e - M,
@@ -7,6 +7,8 @@ tests/test_gpu_exact_attention.py run:
   references      the closed forms equal a plain fp64 softmax reference; that reference agrees with the oracle's attn_backward to a bf16 unit, bit for bit off the ties
   form coverage   the plan (kfdbg_gemm_plan / kfdbg_attn_plan) sends the case tables down every form the entry points have; what no small shape reaches is listed
   power           one term removed, doubled or moved, one key admitted or dropped, changes the expected BITS -- and passes the global-max bars used so far"""
+import fnmatch
+
 import numpy as np
 import pytest
 
@@ -383,3 +385,195 @@ def test_one_wrong_mask_decision_changes_the_bits(T, nh, nkv, hd, draw):
     for name in ("dq", "dk", "dv"):
         assert not np.array_equal(got[name], ref[name])
         assert bar_accepts(E.f64(got[name]), E.f64(ref[name]), 2.0 ** -7, 2.0 ** -9), name
+
+
+# ---------------------------------------------------------------------------------------------------------------- forward token-batch GEMMs: storages, cases, forms, power
+GROUP_STORAGES = [s for s, (t, lut, _, _) in E.STORAGES.items() if O.BITS[t] < 8 and not lut]
+
+
+def _whole_groups(storage, K):
+    """K is made of whole groups and (ternary, 1-bit) of whole 128-element tiles: the layouts the kernels take"""
+    type_, row_lut, _, lgroup = E.STORAGES[storage]
+    return row_lut or O.BITS[type_] >= 8 or (K % lgroup == 0 and (O.BITS[type_] == 4 or K % 128 == 0))
+
+
+@pytest.mark.parametrize("storage,M,K", [(s, M, K) for s in E.STORAGES for M, K in ((40, 256), (96, 1600), (64, 192)) if _whole_groups(s, K)])
+def test_exact_weight_holds_integers_in_every_storage(storage, M, K):
+    """exact_weight asserts O.dequant(ow) == W itself; here what makes a wrong read visible: step in {1, 2} and integer zeros that differ from each group to the next, at
+    least two codes per group, both qBias values of the 4-bit range, every nibble in use; a row codebook of 16 integers that differs from row to row"""
+    type_, row_lut, symmetric, lgroup = E.STORAGES[storage]
+    W, ow = E.exact_weight(storage, M, K, seed=M + K)
+    assert np.array_equal(W, np.rint(W)) and np.abs(W).max() <= 32 and (W != 0).any()
+    assert np.array_equal(E.f64(O.dequant(ow)), W)
+    if row_lut:
+        t = E.f64(ow.lut)
+        assert t.shape == (M, 16) and np.array_equal(t, np.rint(t)) and (np.sort(t, axis=1) == np.arange(-8, 8)).all()
+        assert (t[1:] != t[:-1]).any(axis=1).all()
+    elif storage in GROUP_STORAGES:
+        zero, step = E.f64(ow.zero), E.f64(ow.step)
+        assert set(np.unique(step)) == {1.0, 2.0} and np.array_equal(zero, np.rint(zero)) and len(np.unique(zero)) >= 3
+        assert ((zero[1:] != zero[:-1]) | (step[1:] != step[:-1])).all()
+        codes = O.unpack(ow.data, O.BITS[type_]).reshape(-1, lgroup)
+        assert (codes.min(axis=1) != codes.max(axis=1)).all()
+        assert ow.qBias == ((8 if symmetric else 0) if type_ == O.Q4 else (1 if type_ == O.T_SIGN else 0))
+        if type_ == O.Q4:
+            assert set(np.unique(codes)) == set(range(16))
+
+
+@pytest.fixture(scope="module")
+def forward_cases(hip):
+    """every case of the GPU module, built once: the helpers assert integer products inside the bound, term sums below 2^23, dequant == the integer weight, and the
+    epilogue's intermediates as they go"""
+    return {key: E.forward_case(hip, key) for key in E.FORWARD_CASES}
+
+
+def test_forward_case_preconditions(forward_cases):
+    for key, c in forward_cases.items():
+        for part in [c] + c["more"]:
+            y = E.f64(part["y"])
+            assert np.array_equal(y, np.rint(y)) and np.abs(y).max() <= E.BOUND and (y != 0).mean() > 0.5, key
+            assert np.array_equal(E.f64(O.dequant(part["ow"])), part["W"]), key
+        x = c["f64"]["x"]
+        assert set(np.unique(x)) == {-1.0, 0.0, 1.0}
+        assert (np.abs(x) @ np.abs(c["W"]).T).max() < 2.0 ** 23, key   # the sum of the terms' magnitudes: every partial sum in every order is an fp32 value
+        if key[5] == "block":   # every output a dense sum of 128 terms +-s: even
+            assert np.array_equal(E.f64(c["y"]) % 2, np.zeros(c["y"].shape)) and np.abs(E.f64(c["y"])).max() > 16, key
+            assert ((x != 0).sum(axis=1) == 128).all()
+        if key[6] == "epi":
+            e = c["f64_epi"]
+            y1 = E.f64(E.bits(E.ALPHA * c["f64"]["acc"] + E.BETA * e["y0"] + e["bias"]))
+            assert np.array_equal(c["y_epi"], E.bits(y1 + e["residual"])) and not np.array_equal(c["y_epi"], c["y"]), key
+        if len(c["more"]):   # a distinct weight per matrix
+            assert all(not np.array_equal(c["W"][:64], m["W"][:64]) for m in c["more"]), key
+
+
+# every name the rule can give a kf_linear call with nothing lent (every in-register family on every format that has it: the producer / consumer kernel exists for
+# bf16, f8 and 4-bit groups only), with the scratch kf_linear_scratch_bytes asks for, and on a resident copy whose k is too shallow to
+# cut (K 256) -- test_forward_forms_reached enumerates them; the table holds a case of each.  With a deeper k the resident 64-row tiles run in 2 .. 8 pieces of one
+# kernel: the table holds S 2, 3 and 6 and the owner / helper cut.
+LINEAR_NAMES = {
+    "": [fam + f for fam in ("TILE/DIRECT/32/", "TILE/STAGED/KS2/", "TILE/STAGED/KS1/") for f in ("bf16", "f8", "q4", "q2", "q1", "q4r")]
+        + ["TILE/G2/bf16", "TILE/G2/f8", "TILE/G2/q4"] + ["TILE/G3/" + f for f in ("TINY", "MID", "SMALL", "BIG")] + ["MATVEC"],
+    "scratch": ["DEQ_TILE/G3/SMALL", "DEQ_TILE/G3/BIG"],
+    "arena": ["RESIDENT/DIRECT/32/bf16"] + ["RESIDENT/G3/" + f for f in ("TINY", "MID", "SMALL", "BIG")],
+}
+SPLIT_NAMES = ["RESIDENT/G3/TINY/S2", "RESIDENT/G3/TINY/S3", "RESIDENT/G3/TINY/S6", "RESIDENT/G3/MID/S2", "RESIDENT/G3/MID/tails"]
+SHARED_NAMES = ["FUSED/DIRECT/32/q4", "FUSED/DIRECT/64/q4", "STACKED/G3/SMALL", "STACKED/G3/BIG", "FUSED/PAIRED/q4", "SWIGLU/G3/SMALL", "SWIGLU/G3/WIDE", "SWIGLU/G3/BIG",
+                "ROPE/G3/SMALL"]
+
+
+def test_forward_cases_are_pinned_against_the_plan(hip):
+    """the table names the plan of each case as kf_abi.hip's entry makes it (the same scratch bytes, the same arena state), and between them the cases reach every name"""
+    assert E.SK_WS_BYTES == hip.kf_resident_scratch_bytes()   # what the "arena" cases lend
+    got = set()
+    for key, want in E.FORWARD_CASES.items():
+        p = E.case_plan(hip, key)
+        assert E.forward_name(p) == want, key
+        got.add(want)
+        scratch, arena = E.case_setting(key)
+        assert p.deq == (E.DQ_ARENA if arena else (E.DQ_SCRATCH if scratch else E.DQ_NONE)), key
+        if arena:   # the second call finds the copy: the same kernel, nothing dequantised
+            p2 = E.case_plan(hip, key, arena_hit=1)
+            assert E.forward_name(p2) == want and p2.deq == E.DQ_RESIDENT and (p2.k.S, p2.k.kp, p2.k.R) == (p.k.S, p.k.kp, p.k.R), key
+        if p.k.sk and p.k.S >= 2:
+            S = int(want.rsplit("/S", 1)[1])
+            assert p.k.S == S and key[3] // 64 // S >= 8 and len(E.seams(p, key[3])) == S + 1, key   # pieces stay >= 512 deep
+        if want.endswith("/tails"):
+            assert p.k.kp > 0 and 64 * p.k.kp in E.seams(p, key[3]) and len(E.seams(p, key[3])) > 3, key
+        if key[1] in GROUP_STORAGES and p.k.fam in (1, 2, 3, 4) and p.deq == E.DQ_NONE:   # the in-register kernels index the group tables by block >> gshift
+            epb = {4: 32, 2: 64, 1: 128}[O.BITS[E.STORAGES[key[1]][0]]]
+            assert 1 << p.k.gshift == E.STORAGES[key[1]][3] // epb, key
+    assert set(sum(LINEAR_NAMES.values(), []) + SPLIT_NAMES + SHARED_NAMES) <= got
+    assert {(k[1], E.FORWARD_CASES[k].split("/")[1]) for k in E.FORWARD_CASES if k[6] == "epi"} == {("q4", "DIRECT"), ("q4", "STAGED"), ("q4", "G2"), ("bf16", "G3")}
+    gshifts = {(k[1][:2], E.case_plan(hip, k).k.gshift) for k in E.FORWARD_CASES if k[1] in GROUP_STORAGES and E.FORWARD_CASES[k].startswith("TILE")}
+    assert gshifts >= {("q4", 1), ("q4", 2), ("q4", 3), ("te", 1), ("bo", 0), ("bo", 1)}
+    for name in E.FORWARD_UNREACHABLE:
+        assert not any(fnmatch.fnmatchcase(g, name) for g in got), name
+
+
+def test_forward_forms_reached(hip):
+    """kf_linear over a grid of shapes (ragged and whole, 32 .. 65536 rows, 7 .. 65536 tokens, with a side below 128 against a very long one: where kf_gemm3.hip and
+    the producer / consumer kernel decline), every storage: the names reached are exactly LINEAR_NAMES -- the table misses none, and nothing listed as unreachable is
+    reached"""
+    Ms = [32, 40, 96, 127, 128, 256, 512, 1024, 1056, 2048, 4096, 6400, 8192, 16384, 32768, 65536]
+    ns = [7, 8, 64, 96, 127, 129, 224, 255, 256, 320, 512, 641, 1024, 1281, 1536, 1664, 2048, 2304, 2560, 4096, 8192, 16384, 32768, 65536]
+    for setting, storages in (("", ("q4", "q4s", "f8", "tern", "bool1", "tbin", "bf16", "lut")), ("scratch", ("q4", "tern")), ("arena", ("q4", "tern"))):
+        route = {"": ("TILE", "MATVEC"), "scratch": ("DEQ_TILE",), "arena": ("RESIDENT",)}[setting]
+        reached = set()
+        for st in storages:
+            for M in Ms:
+                for n in ns:
+                    scratch, arena = E.case_setting(("linear", st, (M,), 256, n, "sparse", setting))
+                    reached.add(E.forward_name(E.forward_plan(hip, "linear", st, (M,), 256, n, scratch=scratch, arena=arena)))
+        reached = {r for r in reached if r.split("/")[0] in route}
+        assert reached == set(LINEAR_NAMES[setting]), (setting, reached ^ set(LINEAR_NAMES[setting]))
+        assert not any(fnmatch.fnmatchcase(r, u) for r in reached for u in E.FORWARD_UNREACHABLE)
+    deep = {E.forward_name(E.forward_plan(hip, "linear", "q4", (M,), K, n, scratch=E.SK_WS_BYTES, arena=True)) for K in (1024, 2048, 3072, 4096) for M in Ms for n in ns}
+    cut = {d for d in deep if d.startswith("RESIDENT/G3/") and d.count("/") == 3}
+    assert set(SPLIT_NAMES) <= cut and {d.rsplit("/", 1)[0] for d in cut} == {"RESIDENT/G3/TINY", "RESIDENT/G3/MID"} and "RESIDENT/G3/TINY/tails" not in cut
+
+
+def _neighbours_table(ow, g):
+    """the weight dequantised with group g reading group g + 1's (zero, step): fp64 [M, K]"""
+    z, s = ow.zero.copy(), ow.step.copy()
+    z[g], s[g] = ow.zero[g + 1], ow.step[g + 1]
+    return E.f64(O.dequant_q128(ow.data, z, s, ow.lGroup, 4, ow.qBias)).reshape(ow.ne0, ow.ne1)
+
+
+def _gaussian(seed, M, K, n, lgroup=128, symmetric=False):
+    """operands of tests/test_gpu_gemm.py's scale: w ~ N(0, 0.02) through the 4-bit RTN, x ~ N(0, 1) -> (oracle weight, its dequantised values, x), fp64"""
+    rng = np.random.default_rng(seed)
+    w = O.f32_to_bf16(rng.normal(0, 0.02, (M, K)).astype(np.float32))
+    x = E.f64(O.f32_to_bf16(rng.normal(0, 1.0, (n, K)).astype(np.float32)))
+    ow = O.quantize(w, M, K, O.Q4, lGroup=lgroup, symmetric=symmetric)
+    return ow, E.f64(O.dequant(ow)), x
+
+
+def test_the_last_64_contraction_indices_dropped_for_one_row_block(forward_cases):
+    """K = 1600 (a half-empty last staged tile): the last 64 contraction indices lost for one block of 32 rows.  Exact inputs: two thirds of that block's outputs change
+    their bits, on the direct and on the staged case.  The record for the old bar, observed, not assumed: on Gaussian operands of the existing tests' scale this fault
+    is NOT subtle -- it moves an output by 0.17 .. 0.21 of max|exact| (draws 0 .. 3), 40 - 50 x the 2^-8 bar, which rejects it wherever a test runs such a K (none of
+    tests/test_gpu_gemm.py's shapes has K % 128 != 0)."""
+    for key in [k for k in E.FORWARD_CASES if k[3] == 1600 and k[1] == "q4g64"]:
+        c = forward_cases[key]
+        for rb in range(0, 96, 32):
+            Wm = c["W"].copy()
+            Wm[rb:rb + 32, 1536:] = 0
+            got = E.bits(c["f64"]["x"] @ Wm.T)
+            assert (got[:, rb:rb + 32] != c["y"][:, rb:rb + 32]).mean() > 0.5 and np.array_equal(np.delete(got, np.s_[rb:rb + 32], 1), np.delete(c["y"], np.s_[rb:rb + 32], 1))
+    for draw in range(4):
+        ow, deq, x = _gaussian(draw, 96, 1600, 40, lgroup=64)
+        ref = x @ deq.T
+        deq[32:64, 1536:] = 0
+        got = E.f64(E.bits(x @ deq.T))
+        assert 0.15 <= np.abs(got - ref).max() / np.abs(ref).max() <= 0.25 and not bar_accepts(got, ref, 2.0 ** -8)
+
+
+def test_one_groups_table_index_shifted_by_one(forward_cases):
+    """one 4-bit group reading its neighbour's (zero, step).  Exact inputs: all or nearly all of the group's 128 entries become other integers and the bits of most
+    outputs of that weight row change (at K 256 nearly all) -- which q4_grid_weight, with step 1 and zero -7 in every group, could not show.  The record for the old bar, observed: with
+    the asymmetric range (zero = -min of the group) the fault moves an output by 0.024 .. 0.56 of max|exact| on Gaussian operands and the 2^-8 bar rejects it on every
+    draw tried; with the symmetric range (zero = 0, neighbouring steps a few per cent apart) it depends on the draw: at 2048 x 1024 x 128 tokens the error was 0.0032
+    of max|exact| on draw 0 -- the bar ACCEPTED, with 86 output values changed -- and 0.0044 .. 0.092 on draws 1 .. 5 and 7, which it rejected (0.0044 by a hair).
+    That last outcome is a property of the draws, so it is recorded here and printed, not asserted; asserted is that the exact bits change on every draw."""
+    for key in (("linear", "q4", (40,), 256, 129, "sparse", ""), ("linear", "q4s", (40,), 256, 129, "sparse", ""), ("linear", "q4g64", (96,), 1600, 40, "sparse", "")):
+        c = forward_cases[key]
+        ow, K = c["ow"], key[3]
+        for g in (0, 5, 38, ow.zero.size - 2):
+            Wm = _neighbours_table(ow, g)
+            row = g * ow.lGroup // K
+            assert (Wm != c["W"]).sum() >= ow.lGroup * 3 // 4 and np.array_equal(np.delete(Wm, row, 0), np.delete(c["W"], row, 0))
+            got = E.bits(c["f64"]["x"] @ Wm.T)
+            assert (got[:, row] != c["y"][:, row]).mean() > 0.5, (key, g)
+    for draw in range(6):
+        for shape in ((40, 256, 129), (2048, 1024, 128)):
+            ow, deq, x = _gaussian(draw, *shape)
+            ref = x @ deq.T
+            got = E.f64(E.bits(x @ _neighbours_table(ow, 5).T))
+            assert not bar_accepts(got, ref, 2.0 ** -8) and np.abs(got - ref).max() >= 0.02 * np.abs(ref).max()
+        ow, deq, x = _gaussian(draw, 2048, 1024, 128, symmetric=True)
+        ref = x @ deq.T
+        got = E.bits(x @ _neighbours_table(ow, 5).T)
+        assert (got != E.bits(ref)).sum() >= 64
+        print("symmetric range, draw %d: max error %.4f of max|exact|, the 2^-8 bar %s" % (draw, np.abs(E.f64(got) - ref).max() / np.abs(ref).max(),
+                                                                                        "accepts" if bar_accepts(E.f64(got), ref, 2.0 ** -8) else "rejects"))
