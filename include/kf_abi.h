@@ -614,6 +614,20 @@ int kf_engine_set_embedding(kf_ctx* ctx, kf_engine* e, const kf_weight* embed_bf
  * KF_UNSUPPORTED_DATATYPE for other head storages (the caller keeps kf_norm_lm_head). */
 int kf_engine_set_head(kf_ctx* ctx, kf_engine* e, const kf_weight* head_bf16_or_null, const kf_bf16* final_norm_w, kf_bf16* logits, int32_t* d_tokens_out_or_null);
 int kf_engine_step_head(kf_ctx* ctx, kf_engine* e, const kf_bf16* x_in, kf_bf16* x_out, int32_t* d_state, int pos_bound, int pick);
+/* The int8 screen of the in-launch head.  In a kf_engine_steps_head launch only the LAST step's logits can be observed; on the steps before it the pick alone matters.  With a
+ * screen set those steps stream an int8 copy of the head (one scale per row, half the bytes), bound every row's logit by a rigorous per-row error bound, and re-compute from
+ * the bf16 head -- by the arithmetic of the full stream -- only the rows that can still be the first maximum: the picked ids are bit for bit what they are without a screen,
+ * those steps write no logits, and the last step of every launch (every single-step call) runs the full head unchanged.  buf: device memory, 256-byte aligned,
+ * kf_engine_head_screen_bytes(vocab, dim) bytes, owned by the caller, filled here (one launch on the context's stream) from the head that is set; it must stay valid, and the
+ * head's data unchanged, until the screen is switched off (buf == NULL), the head is set again (which drops the screen) or the engine is destroyed. */
+size_t kf_engine_head_screen_bytes(int vocab, int dim);
+int kf_engine_set_head_screen(kf_ctx* ctx, kf_engine* e, void* buf, size_t bytes);
+typedef struct kf_engine_screen_statistics { /* since creation / kf_engine_reset */
+    int64_t screened_steps; /* decode steps whose head phase streamed the screen */
+    int64_t rows_reranked;  /* rows re-computed from the bf16 head on those steps, all workgroups */
+    int64_t wg_fallbacks;   /* workgroup-steps whose candidate list overflowed: that workgroup streamed its bf16 rows instead */
+} kf_engine_screen_statistics;
+int kf_engine_screen_stats(kf_ctx* ctx, kf_engine* e, kf_engine_screen_statistics* out);
 /* n_steps consecutive greedy decode steps in ONE launch (Fish::ForwardOnRLS + Head4Token::cuInfer_1 + sample_argmax, n_steps times: GoPT.cpp:1155-1180): the step of
  * kf_engine_step_head(x_in = NULL, pick = 1) repeated inside the kernel -- the id a step picks reaches the next step's embedding read as a tagged granule instead of
  * through a launch boundary (~8 us per step).  Every position d_state[1] .. d_state[1] + n_steps - 1 must lie under pos_bound (the bound fixes the attention slicing of

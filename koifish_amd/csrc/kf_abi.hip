@@ -1440,6 +1440,24 @@ int kf_engine_set_head(kf_ctx* c, kf_engine* e, const kf_weight* head_or_null, c
     if (rc != KF_OK) return fail(rc, "kf_engine_set_head: the in-launch head takes a bf16 [vocab, dim] matrix of the engine's width, a norm weight and a logits buffer");
     return KF_OK;
 }
+size_t kf_engine_head_screen_bytes(int vocab, int dim) { return kf::head_screen_bytes(vocab, dim); }
+int kf_engine_set_head_screen(kf_ctx* c, kf_engine* e, void* buf, size_t bytes) {
+    CHKCTX(c);
+    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_set_head_screen: null engine");
+    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_set_head_screen: not while capturing");
+    const int rc = kf::engine_set_head_screen(e->h, buf, bytes, c->stream);
+    if (rc != KF_OK) return fail(rc, "kf_engine_set_head_screen: needs a head set by kf_engine_set_head and a 256-byte aligned buffer of kf_engine_head_screen_bytes(vocab, dim) bytes");
+    return KF_OK;
+}
+int kf_engine_screen_stats(kf_ctx* c, kf_engine* e, kf_engine_screen_statistics* out) {
+    CHKCTX(c);
+    if (!e || !e->h || !out) return fail(KF_INVALID_ARGS, "kf_engine_screen_stats: null argument");
+    long long w[3];
+    const int rc = kf::engine_screen_stats(e->h, c->stream, w);
+    if (rc != KF_OK) return fail(rc, "kf_engine_screen_stats: HIP failure");
+    out->screened_steps = w[0], out->rows_reranked = w[1], out->wg_fallbacks = w[2];
+    return KF_OK;
+}
 int kf_engine_reset(kf_ctx* c, kf_engine* e) {
     CHKCTX(c);
     if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_reset: null engine");

@@ -75,7 +75,7 @@ struct EngArgs {
     int emb_rows;
     uint16_t* x_out;        /* plain bf16 [dim]: the residual stream after the last layer */
     uint32_t* xch;          /* exchange area (EngXOff) */
-    int* ws;                /* [0] epoch, [1] error word */
+    int* ws;                /* [0] epoch, [1] error word, [8..14] hand-off statistics, [16..21] three 8-byte counters of the head screen */
     char* loc;              /* XCD-local area */
     int nsp, chunk, merge_e; /* attention slices of this launch's position bound; merge elements per workgroup */
     int kv_stride;
@@ -90,6 +90,9 @@ struct EngArgs {
     int32_t* d_state_w;      /* {token, pos}: advanced by the pick (NULL: logits only) */
     int32_t* d_tokens_out;
     int vocab, head_on;
+    // the int8 screen of the head (engine_set_head_screen; NULL: every step streams the bf16 head): biased bytes [vocab, dim] and {scale, E} per row (kf_head_screen.hip)
+    g_u32x4 screen_q;
+    const u32x2 KF_GLOBAL* screen_rows; /* float bits */
     unsigned long long* dbg; /* diagnostic instantiation only (KF_ENG_DEBUG): [layer][role][16] wall-clock stamps of workgroup dbg_wg */
     int dbg_wg;
 };
@@ -959,14 +962,34 @@ __device__ __forceinline__ void eng_compute_main(const EngArgs& a, const EngLds&
 }
 
 
+// ---- screened steps (engine_set_head_screen; the steps of a multi-step launch that are not its last: nobody can observe their logits, only the pick matters).  The
+// workgroup streams its rows of the int8 copy (half the bytes) in the same slot geometry, which gives every row an interval [L_r, U_r] that contains the fp32 value the
+// exact chain would leave in front of its bf16 store:  approx_r -+ B_r,  B_r = E_r * ||x||_2  (E_r: kf_head_screen.hip, which derives the bound; ||x||_2 rounded up).
+// With L* the workgroup's largest L_r, a row with bf16(U_r) < bf16(L*) can neither beat nor tie the workgroup's first maximum (f2bf is monotone: its stored logit is
+// <= bf16(U_r) < bf16(L*) <= the stored logit of the row that attains L*), so only the other rows -- the candidates -- are computed, from the bf16 head by the chain of
+// the full stream (head_row below: ONE implementation), and the workgroup publishes the same {value, row} as the full stream would.  More candidates than the list holds:
+// the workgroup runs the full exact stream over its rows (without the logit stores) and counts one fall-back.
+template <class C>
+struct HeadScreen {
+    static constexpr int HG = 4;                                                 /* row slots per batch of the exact stream */
+    static constexpr int nBlk8 = C::DIM / 16, IT8 = (nBlk8 + C::HLPR - 1) / C::HLPR; /* 16-byte pieces of an int8 row, pieces per lane */
+    static constexpr int HG8 = IT8 == 1 ? 8 : 4;                                 /* int8 row slots per batch: 16 loads per lane in flight, as the exact stream has */
+    static constexpr int CAP = C::NWV * C::HRPS * 2 * HG;                        /* candidates of a workgroup: what its waves hold in the exact stream's registers at once */
+    static constexpr int SCR = C::NWV * C::GQ * (C::HD + 2) * 8;                 /* bytes of the attention's wave sums (EngLds::comb), free in the head phase */
+    static constexpr int ROWS = (SCR - CAP * 4 - 64) / 4;                        /* rows of a workgroup whose U_r fit in front of the list */
+    static_assert(ROWS >= 512, "the screen's LDS scratch");
+};
+
 // ---- the LM head as trailing phases of the launch (Head4Token::cuInfer_1, NeuronFuse.cu:842-862: final RMSNorm, the [vocab, dim] mat-vec, first-maximum arg-max,
 // GoPT.cpp:602-612): what kf_norm_lm_head + argmax_finish_kernel do as two more launches.  All 8 waves stream: a wave owns the row slots wave, wave + 8, ... of the
 // workgroup's contiguous slot range, keeps HG slots (2 * HG 16-byte loads per lane) in flight, and holds its two x blocks in registers (a lane multiplies the same
 // block columns of every row).  The arithmetic is gemv_kernel<FMT_BF16>'s: same lanes per row, same per-lane chain, same tree, bf16 store, arg-max over the stored values.
 template <class C>
 __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L, int epoch, bool more_steps, int wg, int wave, int lane) {
-    constexpr int NWV = C::NWV, NWG = C::NWG, nBlk = C::HnBlk, LPR = C::HLPR, RPS = C::HRPS, ITERS = C::Hiters, HG = 4;
+    using HS = HeadScreen<C>;
+    constexpr int NWV = C::NWV, NWG = C::NWG, nBlk = C::HnBlk, LPR = C::HLPR, RPS = C::HRPS, ITERS = C::Hiters, HG = HS::HG;
     constexpr int ND = C::DIM / 256;
+    constexpr int nBlk8 = HS::nBlk8, IT8 = HS::IT8, HG8 = HS::HG8, CAP = HS::CAP;
     const int sub = lane >> C::Hlpr_log2, ll = lane & (LPR - 1);
     const int total = (a.vocab + RPS - 1) / RPS, spg = (total + NWG - 1) / NWG; /* slots in all, per workgroup */
     const int s_wg = wg * spg;
@@ -974,6 +997,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
     s_end = s_end < total ? s_end : total;
     const int nmine = s_end > s_wg + wave ? (s_end - s_wg - wave + NWV - 1) / NWV : 0; /* this wave's slots: s_wg + wave + NWV * i */
     const int nbatch = (nmine + HG - 1) / HG;
+    const bool screened = a.screen_q != nullptr && more_steps && spg * RPS <= HS::ROWS; /* uniform over the launch's workgroups and waves */
     u32x4 w[2][HG][ITERS];
     auto issue = [&](int b, int buf) {
 #pragma unroll
@@ -990,7 +1014,42 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
             }
         }
     };
-    issue(0, 0); /* ahead of the hand-off of x: the first rows' HBM latency runs under it */
+    // the int8 stream: the same slots, one 16-byte piece of 16 weights per lane and IT8
+    u32x4 w8[2][HG8][IT8];
+    const int nbatch8 = (nmine + HG8 - 1) / HG8;
+    auto issue8 = [&](int b, int buf) {
+#pragma unroll
+        for (int g = 0; g < HG8; g++) {
+            int i = b * HG8 + g;
+            i = i < nmine ? i : (nmine > 0 ? nmine - 1 : 0);
+            int row = (s_wg + wave + NWV * i) * RPS + sub;
+            row = row < a.vocab ? row : a.vocab - 1;
+#pragma unroll
+            for (int it = 0; it < IT8; it++) {
+                int col = it * LPR + ll;
+                col = col < nBlk8 ? col : nBlk8 - 1;
+                w8[buf][g][it] = __builtin_nontemporal_load(a.screen_q + (size_t)row * nBlk8 + col);
+            }
+        }
+    };
+    // {scale_r, E_r} (float bits) of the rows this THREAD bounds behind the stream: the workgroup's rows tid, tid + 512, ...; the first KP of them requested up here
+    constexpr int KP = 2;
+    const int row0 = s_wg * RPS, tid = (wave << 6) | lane;
+    int nrows = (s_end - s_wg) * RPS;
+    nrows = nrows < a.vocab - row0 ? nrows : a.vocab - row0; /* <= 0: a workgroup without rows */
+    u32x2 rinfo[KP];
+    /* ahead of the hand-off of x: the first rows' HBM latency runs under it */
+    if (screened) {
+        issue8(0, 0);
+#pragma unroll
+        for (int k = 0; k < KP; k++) {
+            const int r = row0 + tid + NWV * 64 * k;
+            rinfo[k] = a.screen_rows[r < a.vocab ? r : a.vocab - 1];
+        }
+        if (wave == 0 && lane == 0) *reinterpret_cast<int*>(reinterpret_cast<char*>(L.comb) + HS::ROWS * 4 + CAP * 4) = 0; /* the candidate count (the barrier below publishes it) */
+    } else {
+        issue(0, 0);
+    }
     const uint32_t gen = (uint32_t)(epoch + 1) * (uint32_t)a.n_layer, tag = gen & 0xffffu; /* the generation the last layer's down_proj published its rows with */
     if (wave == NWV - 1) {
         bool dead = false;
@@ -1001,49 +1060,173 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
     __syncthreads();
     float xf[ITERS][8]; /* this lane's block columns of the normed x, widened once: the lane multiplies the same columns of every row */
     uint32_t xp[ITERS][4]; /* the same as bf16 pairs (the v_dot2c form) */
+    auto load_x = [&]() {
 #pragma unroll
-    for (int it = 0; it < ITERS; it++) {
-        int col = it * LPR + ll;
-        col = col < nBlk ? col : nBlk - 1;
-        const u32x4 xv = L.xs[0][col];
-        const uint32_t x4[4] = {xv.x, xv.y, xv.z, xv.w};
+        for (int it = 0; it < ITERS; it++) {
+            int col = it * LPR + ll;
+            col = col < nBlk ? col : nBlk - 1;
+            const u32x4 xv = L.xs[0][col];
+            const uint32_t x4[4] = {xv.x, xv.y, xv.z, xv.w};
 #pragma unroll
-        for (int i = 0; i < 4; i++) xf[it][2 * i] = bf_lo(x4[i]), xf[it][2 * i + 1] = bf_hi(x4[i]), xp[it][i] = x4[i];
-    }
+            for (int i = 0; i < 4; i++) xf[it][2 * i] = bf_lo(x4[i]), xf[it][2 * i + 1] = bf_hi(x4[i]), xp[it][i] = x4[i];
+        }
+    };
     float best_v = -__builtin_inff();
     int best_i = 0x7fffffff;
-    auto compute = [&](int b, int buf) {
+    // one row slot of the exact head: the lane's chain over its blocks, the tree over the row's lanes -- the fp32 value in front of the bf16 store
+    auto head_row = [&](const u32x4* wr) -> float {
+        acc_t<C::CANON> acc{};
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) { /* BlockDot<FMT_BF16, CANON>: the block's 4 pairs in order (canonical: the even / odd chains, one v_pk_fma_f32 per pair) */
+            const uint32_t w4[4] = {wr[it].x, wr[it].y, wr[it].z, wr[it].w};
+            acc_t<C::CANON> r = acc;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if constexpr (C::CANON) r = pk_fma(f32x2_t{bf_lo(w4[i]), bf_hi(w4[i])}, f32x2_t{xf[it][2 * i], xf[it][2 * i + 1]}, r);
+                else r = dot2_bf16(w4[i], xp[it][i], r);
+            }
+            acc = acc_pick(it * LPR + ll < nBlk, r, acc);
+        }
+        return group_sum(acc_join(acc), C::Hlpr_log2);
+    };
+    auto take = [&](float v, int row) { /* the stored value and the first maximum over them */
+        const uint16_t o = f2bf(v);
+        const float fv = bf2f(o);
+        if (fv > best_v || (fv == best_v && row < best_i)) best_v = fv, best_i = row;
+        return o;
+    };
+    auto compute = [&](int b, int buf, auto store) {
 #pragma unroll
         for (int g = 0; g < HG; g++) {
             const int i = b * HG + g;
             const int row = (s_wg + wave + NWV * i) * RPS + sub;
-            acc_t<C::CANON> acc{};
-#pragma unroll
-            for (int it = 0; it < ITERS; it++) { /* BlockDot<FMT_BF16, CANON>: the block's 4 pairs in order (canonical: the even / odd chains, one v_pk_fma_f32 per pair) */
-                const uint32_t w4[4] = {w[buf][g][it].x, w[buf][g][it].y, w[buf][g][it].z, w[buf][g][it].w};
-                acc_t<C::CANON> r = acc;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if constexpr (C::CANON) r = pk_fma(f32x2_t{bf_lo(w4[i]), bf_hi(w4[i])}, f32x2_t{xf[it][2 * i], xf[it][2 * i + 1]}, r);
-                    else r = dot2_bf16(w4[i], xp[it][i], r);
-                }
-                acc = acc_pick(it * LPR + ll < nBlk, r, acc);
-            }
-            const float v = group_sum(acc_join(acc), C::Hlpr_log2);
+            const float v = head_row(w[buf][g]);
             if (ll == 0 && i < nmine && row < a.vocab) {
-                const uint16_t o = f2bf(v);
-                a.logits[row] = o;
-                const float fv = bf2f(o);
-                if (fv > best_v || (fv == best_v && row < best_i)) best_v = fv, best_i = row;
+                const uint16_t o = take(v, row);
+                if constexpr (decltype(store)::value) a.logits[row] = o;
             }
         }
     };
-    for (int b = 0; b < nbatch; b += 2) { /* two batches ping-pong: no register copies between steps */
-        issue(b + 1, 1);
-        compute(b, 0);
-        if (b + 1 >= nbatch) break;
-        issue(b + 2, 0);
-        compute(b + 1, 1);
+    auto stream = [&](auto store) { /* batch 0 is in flight */
+        for (int b = 0; b < nbatch; b += 2) { /* two batches ping-pong: no register copies between steps */
+            issue(b + 1, 1);
+            compute(b, 0, store);
+            if (b + 1 >= nbatch) break;
+            issue(b + 2, 0);
+            compute(b + 1, 1, store);
+        }
+    };
+    if (!screened) {
+        load_x();
+        stream(std::true_type{});
+    } else {
+        float* const U = reinterpret_cast<float*>(L.comb);       /* [ROWS] the rows' unscaled sums, then their U_r */
+        int* const cand = reinterpret_cast<int*>(U + HS::ROWS);   /* [CAP] candidate rows (workgroup-local), [1] their count, [NWV] the waves' largest L_r */
+        int* const ncand = cand + CAP;
+        float* const lmax = reinterpret_cast<float*>(ncand + 1);
+        // this lane's 16 * IT8 columns of x as float pairs, their sum (the bias of the stored bytes) and ||x||_2 (every lane group holds the whole vector between its lanes)
+        f32x2_t x8[IT8][8];
+        float sx = 0.f, ss = 0.f;
+#pragma unroll
+        for (int it = 0; it < IT8; it++) {
+            const int c8 = it * LPR + ll;
+            const bool ok = c8 < nBlk8;
+            const int c = ok ? c8 : nBlk8 - 1;
+            const u32x4 xa = L.xs[0][2 * c], xb = L.xs[0][2 * c + 1];
+            const uint32_t x4[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                x8[it][i] = f32x2_t{ok ? bf_lo(x4[i]) : 0.f, ok ? bf_hi(x4[i]) : 0.f}; /* a lane past the row's end multiplies zeros */
+                sx += x8[it][i].x, sx += x8[it][i].y;
+                ss = fmaf(x8[it][i].x, x8[it][i].x, ss), ss = fmaf(x8[it][i].y, x8[it][i].y, ss);
+            }
+        }
+        // ||x||_2 rounded up: the fp32 sum of <= 2048 squares is within 2^-12 of the true one, its root within 2^-13
+        const float xn = sqrtf(group_sum(ss, C::Hlpr_log2)) * (1.0f + 1.0f / 1024.0f);
+        auto compute8 = [&](int b, int buf) {
+#pragma unroll
+            for (int g = 0; g < HG8; g++) {
+                const int i = b * HG8 + g;
+                const int row = (s_wg + wave + NWV * i) * RPS + sub;
+                f32x2_t acc{};
+#pragma unroll
+                for (int it = 0; it < IT8; it++) {
+                    const uint32_t d4[4] = {w8[buf][g][it].x, w8[buf][g][it].y, w8[buf][g][it].z, w8[buf][g][it].w};
+#pragma unroll
+                    for (int d = 0; d < 4; d++) { /* bytes 0 | 1 and 2 | 3 of the dword: v_cvt_f32_ubyteK x 2 + one v_pk_fma_f32 (the even and the odd chain) */
+                        acc = pk_fma(f32x2_t{(float)(d4[d] & 0xffu), (float)((d4[d] >> 8) & 0xffu)}, x8[it][2 * d], acc);
+                        acc = pk_fma(f32x2_t{(float)((d4[d] >> 16) & 0xffu), (float)(d4[d] >> 24)}, x8[it][2 * d + 1], acc);
+                    }
+                }
+                const float v = group_sum(fmaf(-128.0f, sx, acc.x + acc.y), C::Hlpr_log2);
+                if (ll == 0 && i < nmine && row < a.vocab) U[row - row0] = v;
+            }
+        };
+        for (int b = 0; b < nbatch8; b += 2) {
+            issue8(b + 1, 1);
+            compute8(b, 0);
+            if (b + 1 >= nbatch8) break;
+            issue8(b + 2, 0);
+            compute8(b + 1, 1);
+        }
+        __syncthreads();
+        // every thread bounds its rows: approx_r = scale_r * sum, B_r, U_r, L_r with every rounding of these few operations pushed outwards (2^-20 on the product, 2^-22 of
+        // the sum on the sum: a sum is within 2^-24 of itself); U_r replaces the sum
+        float lm = -__builtin_inff();
+        auto bound = [&](int r, u32x2 info) {
+            const float ap = __uint_as_float(info.x) * U[r];
+            const float B = (__uint_as_float(info.y) * xn) * (1.0f + 1.0f / 1048576.0f);
+            float u = ap + B, lo = ap - B;
+            u += fabsf(u) * (1.0f / 4194304.0f), lo -= fabsf(lo) * (1.0f / 4194304.0f);
+            U[r] = u;
+            lm = fmaxf(lm, lo); /* a NaN never becomes L*: its row stays a candidate below (no compare with a NaN excludes) */
+        };
+#pragma unroll
+        for (int k = 0; k < KP; k++)
+            if (tid + NWV * 64 * k < nrows) bound(tid + NWV * 64 * k, rinfo[k]);
+        for (int r = tid + NWV * 64 * KP; r < nrows; r += NWV * 64) bound(r, a.screen_rows[row0 + r]);
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) lm = fmaxf(lm, __shfl_xor(lm, m, 64));
+        if (lane == 0) lmax[wave] = lm;
+        __syncthreads();
+        float ls = lmax[0];
+#pragma unroll
+        for (int k = 1; k < NWV; k++) ls = fmaxf(ls, lmax[k]);
+        const float lsb = round_bf16(ls);
+        for (int r = tid; r < nrows; r += NWV * 64) { /* the thread's own rows again */
+            if (!(round_bf16(U[r]) < lsb)) { /* excluded only when strictly below after the bf16 rounding: a tie with the winner stays in, so the lower row still wins it */
+                const int k = __hip_atomic_fetch_add(ncand, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (k < CAP) cand[k] = r;
+            }
+        }
+        __syncthreads();
+        const int nc = *ncand;
+        load_x();
+        if (nc > CAP) { /* the list overflowed: today's full exact stream over the workgroup's rows */
+            issue(0, 0);
+            stream(std::false_type{});
+            if (wave == 0 && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.ws + 16) + 2, 1ull);
+        } else if (nc > 0) { /* candidate c -> wave (c / RPS) % NWV, its slot (c / RPS) / NWV, lane group c % RPS: every load of the re-rank in flight together */
+#pragma unroll
+            for (int k = 0; k < 2 * HG; k++) {
+                const int c = (wave + NWV * k) * RPS + sub;
+                const int row = row0 + cand[c < nc ? c : 0];
+#pragma unroll
+                for (int it = 0; it < ITERS; it++) {
+                    int col = it * LPR + ll;
+                    col = col < nBlk ? col : nBlk - 1;
+                    w[k / HG][k % HG][it] = __builtin_nontemporal_load(a.head_w + (size_t)row * nBlk + col);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2 * HG; k++) {
+                const int c = (wave + NWV * k) * RPS + sub;
+                const float v = head_row(w[k / HG][k % HG]);
+                if (ll == 0 && c < nc) take(v, row0 + cand[c]);
+            }
+            if (wave == 0 && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.ws + 16) + 1, (unsigned long long)nc);
+        }
+        if (wg == 0 && wave == 0 && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.ws + 16), 1ull);
     }
     // first maximum over the workgroup's rows, published as one 8-byte granule {tag, bf16 value, row}; workgroup 0's poller picks over all of them
 #pragma unroll
@@ -1259,7 +1442,12 @@ __global__ void __launch_bounds__(C::NWV * 64) engine_kernel(const EngArgs a) {
             eng_poller_main<C>(a, L, S, epoch, step, wg, lane_s);
         else
             eng_compute_main<C>(a, L, S, epoch, wg, wave, lane_s);
-        if (a.head_on) eng_head_main<C>(a, L, epoch, step + 1 < nst, wg, wave, lane_s);
+        if (a.head_on) { /* stamped form: the head phase of the last layer's row, poller slots 12 / 13 (a full head) and 14 / 15 (a screened one) */
+            const int hs = (a.screen_q != nullptr && step + 1 < nst) ? 14 : 12;
+            if (C::DBG && wg == a.dbg_wg && tid == (NWV - 1) * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs] = __builtin_amdgcn_s_memrealtime();
+            eng_head_main<C>(a, L, epoch, step + 1 < nst, wg, wave, lane_s);
+            if (C::DBG && wg == a.dbg_wg && tid == (NWV - 1) * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs + 1] = __builtin_amdgcn_s_memrealtime();
+        }
     }
     // the next launch's generation (workgroup 0 owns rows of the last phase, so every workgroup has read the epoch long before)
     if (wg == 0 && tid == 0) {
@@ -1428,7 +1616,7 @@ static int engine_init_state(EngineHost* E, hipStream_t st) {
     char* const loc0 = a.loc;
     char* const end = reinterpret_cast<char*>(E->ws) + E->ws_bytes;
     if (hipMemsetAsync(loc0, 0xff, (size_t)(end - loc0), st) != hipSuccess) return KF_HIP_CHECK;
-    static const int init[16] = {1, 0}; /* epoch 1, no error, statistics (words 8 .. 14) zero */
+    static const int init[32] = {1, 0}; /* epoch 1, no error, statistics (words 8 .. 14) and the head screen's counters (16 .. 21) zero */
     if (hipMemsetAsync(a.loc, 0, 1024, st) != hipSuccess || hipMemcpyAsync(a.ws, init, sizeof(init), hipMemcpyHostToDevice, st) != hipSuccess) return KF_HIP_CHECK;
     return KF_OK;
 }
@@ -1578,6 +1766,7 @@ int engine_set_embedding(EngineHost* E, const kf_weight* w, const int32_t* d_for
 // The LM head (bf16 [vocab, dim]) + final norm as trailing phases of the launch (engine_step with_head); NULL removes it.
 int engine_set_head(EngineHost* E, const kf_weight* w, const uint16_t* norm_w, uint16_t* logits, int32_t* d_tokens_out) {
     EngArgs& a = E->args;
+    a.screen_q = nullptr, a.screen_rows = nullptr; /* a screen belongs to the head it was built from */
     if (!w) {
         a.head_w = nullptr, a.head_norm = nullptr, a.logits = nullptr, a.d_tokens_out = nullptr, a.vocab = 0;
         return KF_OK;
@@ -1587,6 +1776,28 @@ int engine_set_head(EngineHost* E, const kf_weight* w, const uint16_t* norm_w, u
     // the compile-time geometry of the head phases must be the mat-vec launcher's for this matrix (same lanes per row: same summation order)
     if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE;
     a.head_w = (g_u32x4)(uintptr_t)w->data, a.head_norm = (g_u16)(uintptr_t)norm_w, a.logits = logits, a.d_tokens_out = d_tokens_out, a.vocab = w->ne0;
+    return KF_OK;
+}
+// The int8 screen of the head that is set (kf_head_screen.hip): built here, once, into the caller's buffer; the steps of a multi-step launch that are not its last stream it
+// instead of the head and re-compute only the rows that can still be the first maximum (eng_head_main).  NULL: off.  The buffer must outlive the setting.
+int engine_set_head_screen(EngineHost* E, void* buf, size_t bytes, hipStream_t st) {
+    EngArgs& a = E->args;
+    a.screen_q = nullptr, a.screen_rows = nullptr;
+    if (!buf) return KF_OK;
+    if (!a.head_w) return KF_INVALID_ARGS;
+    const size_t need = head_screen_bytes(a.vocab, E->dim);
+    if (need == 0 || bytes < need || ((uintptr_t)buf & 255) != 0) return KF_INVALID_ARGS;
+    const int rc = head_screen_build(reinterpret_cast<const uint16_t*>((uintptr_t)a.head_w), a.vocab, E->dim, buf, bytes, st);
+    if (rc != KF_OK) return rc;
+    a.screen_q = (g_u32x4)(uintptr_t)buf;
+    a.screen_rows = (const u32x2 KF_GLOBAL*)((uintptr_t)buf + (((size_t)a.vocab * E->dim + 255) & ~(size_t)255));
+    return KF_OK;
+}
+// {screened steps, rows re-ranked, workgroup fall-backs} since creation / the last reset
+int engine_screen_stats(EngineHost* E, hipStream_t st, long long* out3) {
+    unsigned long long w[3];
+    if (hipMemcpyAsync(w, E->args.ws + 16, sizeof(w), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KF_HIP_CHECK;
+    for (int i = 0; i < 3; i++) out3[i] = (long long)w[i];
     return KF_OK;
 }
 int engine_error_word(EngineHost* E, hipStream_t st, int* h_err) {

@@ -143,6 +143,12 @@ int engine_stats(EngineHost* E, hipStream_t st, int pos_bound, int* out14);
 int engine_step(EngineHost* E, hipStream_t st, const uint16_t* x_in, uint16_t* x_out, const int32_t* d_state, int pos_bound, int with_head = 0, int n_steps = 1); /* 1: not served */
 int engine_set_head(EngineHost* E, const kf_weight* w, const uint16_t* norm_w, uint16_t* logits, int32_t* d_tokens_out);
 int engine_set_embedding(EngineHost* E, const kf_weight* w, const int32_t* d_forced);
+// the int8 screen of the in-launch head (kf_head_screen.hip): size of the caller's buffer, the build (one launch), the setter (buf == NULL: off; builds the copy from the head
+// that is set) and the counters since create / reset: {screened steps, rows re-ranked, workgroup fall-backs}
+size_t head_screen_bytes(int vocab, int dim);
+int head_screen_build(const uint16_t* head, int vocab, int dim, void* buf, size_t bytes, hipStream_t st);
+int engine_set_head_screen(EngineHost* E, void* buf, size_t bytes, hipStream_t st);
+int engine_screen_stats(EngineHost* E, hipStream_t st, long long* out3);
 int engine_error_word(EngineHost* E, hipStream_t st, int* h_err);
 void engine_set_canonical(EngineHost* E, int on); /* every phase: canonical order (1, the default) or the v_dot2c / fp32 forms */
 int engine_reset(EngineHost* E, hipStream_t st); /* after a timed-out poll: exchange state re-initialised, error word cleared */

@@ -296,6 +296,7 @@ Fish::~Fish() {
     if (ctx && deq_arena) kf_free(ctx, deq_arena);
     if (engine) kf_engine_destroy(engine);
     if (ctx && engine_ws) kf_free(ctx, engine_ws);
+    if (ctx && head_screen) kf_free(ctx, head_screen);
     if (ctx) {
         if (rope_table) kf_free(ctx, rope_table);
         FreeSeqs(ctx);
@@ -611,9 +612,33 @@ int Fish::EnsureEngine() {
     }
     return KF_OK;
 }
+// the int8 screen of the engine's head, under the caller's promise only; no room or a refusal is not an error: every step then streams the bf16 head
+void Fish::EnsureHeadScreen() {
+    if (head_screen || head_screen_tried || !prefill_resident || !engine || !engine_head) return;
+    head_screen_tried = true;
+    const kf_weight wh = head.proj.w->desc();
+    const size_t bytes = kf_engine_head_screen_bytes(wh.ne0, wh.ne1);
+    if (bytes == 0 || bytes + deq_arena_bytes > resident_max_bytes) return;
+    void* p = nullptr;
+    if (kf_malloc(ctx, bytes, &p) != KF_OK) return;
+    if (kf_engine_set_head_screen(ctx, engine, p, bytes) != KF_OK) {
+        kf_free(ctx, p);
+        return;
+    }
+    head_screen = p, head_screen_bytes = bytes;
+}
+void Fish::DropHeadScreen() {
+    if (head_screen) {
+        kf_sync(ctx);
+        if (engine) kf_engine_set_head_screen(ctx, engine, nullptr, 0);
+        kf_free(ctx, head_screen), head_screen = nullptr, head_screen_bytes = 0;
+    }
+    head_screen_tried = false;
+}
 void Fish::DropEngineTable() {
     for (auto& g : graphs)
         if (g) kf_graph_destroy(g), g = nullptr;
+    DropHeadScreen();
     if (engine) {
         kf_sync(ctx);
         kf_engine_destroy(engine);
@@ -649,7 +674,7 @@ int Fish::EnsureResident(int PC) {
         if (d.type != KF_BF16 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
     };
     for (int l = 0; l < config.nLayer; l++) add(attn[l]->Q), add(attn[l]->K), add(attn[l]->V), add(attn[l]->proj_cat), add(ffn[l]->gate), add(ffn[l]->up), add(ffn[l]->down);
-    if (total == 0 || total > resident_max_bytes) return KF_OK;
+    if (total == 0 || total + head_screen_bytes > resident_max_bytes) return KF_OK;
     KF_TRY(kf_sync(ctx));
     void* p = nullptr;
     if (kf_malloc(ctx, total, &p) != KF_OK) return KF_OK; /* no room: not an error, the scratch route serves */
@@ -855,6 +880,7 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
             int m = 1;
             while (i + m < n && m < kStepsPerLaunch && bucket_of(pos + i + m) == b) m++;
             tok_pos = p;
+            if (m > 1) EnsureHeadScreen();
             if (engine_autotune > 0 && engine_embed) { /* once per position bucket: the hand-off delays measured at the first step inside it */
                 if (bucket_tuned.empty()) bucket_tuned.assign((size_t)bucket_of(config.n_ctx - 1) + 1, 0);
                 if (!bucket_tuned[b]) {
@@ -1697,6 +1723,7 @@ int kfh_weights_changed(void* h) {
 int kfh_set_prefill_resident(void* h, int on, size_t max_bytes) {
     Fish* f = reinterpret_cast<Fish*>(h);
     f->DropResident();
+    if (!on) f->DropHeadScreen(); /* the promise is withdrawn: no derived copy of a weight stays */
     f->prefill_resident = on ? 1 : 0;
     if (max_bytes) f->resident_max_bytes = max_bytes;
     return KF_OK;
@@ -1719,6 +1746,16 @@ int kfh_engine_stats(void* h, int pos, int32_t* out14) {
     KF_TRY(kf_engine_stats(f->ctx, f->engine, f->pos_bound(), &s));
     for (int i = 0; i < 6; i++) out14[i] = s.sweeps[i], out14[7 + i] = s.delay[i];
     out14[6] = s.polls, out14[13] = s.tuned;
+    return KF_OK;
+}
+// the head screen's counters since the engine was built or reset: {screened steps, rows re-ranked, workgroup fall-backs}; zeros without an engine
+int kfh_engine_screen_stats(void* h, int64_t* out3) {
+    Fish* f = reinterpret_cast<Fish*>(h);
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!f->engine) return KF_OK;
+    kf_engine_screen_statistics s;
+    KF_TRY(kf_engine_screen_stats(f->ctx, f->engine, &s));
+    out3[0] = s.screened_steps, out3[1] = s.rows_reranked, out3[2] = s.wg_fallbacks;
     return KF_OK;
 }
 // n launches of the engine alone at the position d_state holds (bench.py times the kernel with events around this); the residual stream is

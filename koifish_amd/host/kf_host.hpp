@@ -249,6 +249,14 @@ struct Fish : SeqBuffers {
     unsigned weights_gen = 0;  // counts DropEngine calls (a weight set again, kfh_weights_changed): engines other objects built on this Fish compare it with their own copy
     bool engine_embed = false;  // the engine reads the (bf16) embedding row itself
     bool engine_head = false;   // ... and runs the final norm, the (bf16) LM head and the greedy pick as trailing phases of its launch
+    // The int8 screen of the in-launch head (kf_engine_set_head_screen): a derived copy of the head like the resident bf16 copies, so it is built only under the same promise
+    // (prefill_resident: "the quantised data does not change under me"), counts against resident_max_bytes, and is dropped with the engine's table (kfh_weights_changed, a
+    // weight set again) and when the promise is withdrawn.  The promise may arrive after the engine exists: RunSteps looks before every multi-step run.
+    void* head_screen = nullptr;
+    size_t head_screen_bytes = 0;
+    bool head_screen_tried = false;
+    void EnsureHeadScreen();
+    void DropHeadScreen();
     int masked_layers = 0;      // layers with a hot-row mask (kfh_set_hot): the engine walks dense FFNs only
     int EnsureEngine();
     // what the decode engines read of this model: one kf_engine_layer per layer -- the seven matrices (none with a bias), both norms, the q / k norms, the hot-row mask

@@ -671,6 +671,12 @@ class Qwen3:
         polls = max(int(w[6]), 1)
         return {"sweeps_per_poll": [round(int(w[i]) / polls, 3) for i in range(6)], "polls": int(w[6]), "delay": [int(w[7 + i]) for i in range(6)], "tuned": int(w[13])}
 
+    def engine_screen_stats(self):
+        """kf_engine_screen_stats: the head screen's counters since the engine was built or reset (zeros when there is none)"""
+        w = (C.c_int64 * 3)()
+        L.check(self.host.kfh_engine_screen_stats(self.h, w), "kfh_engine_screen_stats")
+        return {"screened_steps": int(w[0]), "rows_reranked": int(w[1]), "wg_fallbacks": int(w[2])}
+
     def engine_steps(self):
         """steps enqueued or captured through the engine so far (-1: the engine does not serve this model's shapes / storage)"""
         return int(self.host.kfh_engine_steps(self.h))

@@ -1,5 +1,6 @@
 """Per-phase wall-clock stamps of one workgroup of the persistent decode engine (the diagnostic instantiation of the kernel): where a layer's time goes.
-   STAMP_WG=77 [ENG_DELAY=16,8,12,16,16,16] python scratch/eng_stamps.py [pos]"""
+   STAMP_WG=77 [ENG_DELAY=16,8,12,16,16,16] [SCREEN=1] python scratch/eng_stamps.py [pos]
+   SCREEN=1: with the caller's promise (set_prefill_resident), so that the first three of the four steps stream the int8 screen of the head"""
 import ctypes as C
 import os
 import sys
@@ -22,6 +23,8 @@ if os.environ.get("ENG_DELAY"):
     d = (C.c_int * 6)(*[int(v) for v in os.environ["ENG_DELAY"].split(",")])
     assert m.host.kfh_engine_set_delays(m.h, d) == 0
 assert m.host.kfh_engine_stamps_enable(m.h, int(os.environ.get("STAMP_WG", "77"))) == 0
+if os.environ.get("SCREEN"):
+    m.set_prefill_resident(True)
 m.set_state(int(forced[pos - 4]), pos - 4)
 m.run_steps(pos - 4, 4, True)
 m.sync()
@@ -54,3 +57,7 @@ seg = np.diff(a[4:, 0, :8], axis=1) / 100.0
 print("poller segments, mean us:", "  ".join("%s %.2f" % (names_p[k + 1], seg[:, k].mean()) for k in range(7)))
 segc = np.diff(a[4:, 1, :10], axis=1) / 100.0
 print("wave-0 segments, mean us:", "  ".join("%s %.2f" % (names_c[k + 1], segc[:, k].mean()) for k in range(9)))
+# the head phase of workgroup STAMP_WG (poller wave: entry of eng_head_main to its return, i.e. hand-off of x, stream, workgroup maximum published; workgroup 0 adds the pick)
+hf, hs = (a[nl - 1, 0, 13] - a[nl - 1, 0, 12]) / 100.0, (a[nl - 1, 0, 15] - a[nl - 1, 0, 14]) / 100.0
+print("head phase (us): full stream %.2f%s" % (hf, "  screened %.2f" % hs if a[nl - 1, 0, 14] else "  (no screened step)"))
+print("head screen counters:", m.engine_screen_stats())
