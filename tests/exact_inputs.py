@@ -2,7 +2,7 @@
 
 A bar scaled by a tensor's largest element cannot see one wrong term of a long contraction.  With operands made of small integers (and halves) every
 product and every partial sum of a kernel's fp32 accumulation is representable, whatever the route, tile form, split-K cut or order, so the expected
-output is bf16(exact) BIT FOR BIT and nothing is measured.  Two groups:
+output is bf16(exact) BIT FOR BIT and nothing is measured.  The groups:
 
   integer GEMM operands   entries in {-1, 0, 1} (optionally +-2) with the density chosen per contraction length, or a dense +-1 block of 128 consecutive
                           contraction indices placed on a seam of the form under test; small-integer prior values for the beta = 1 epilogues
@@ -10,6 +10,8 @@ output is bf16(exact) BIT FOR BIT and nothing is measured.  Two groups:
                           kernels' own fp32 arithmetic (tests/test_exact_inputs_cpu.py emulates that arithmetic and asserts it)
   exact weights per storage   bf16, f8e5m2, 4-bit groups and row codebooks, ternary and 1-bit weights built from CHOSEN codes and CHOSEN (zero, step) tables that differ
                           from group to group, each dequantising to small integers: the forward token-batch GEMMs' operands, and their case table FORWARD_CASES
+  level logits            the scoring head: integer logits, 128 on a row's winners and within +-40 elsewhere, so that every exponential of the log-softmax fold is exactly
+                          0 or 1 and sum, maximum, first index and log-sum-exp are closed forms in every tile form, merge order and route (case table SCORE_CASES)
 
 Every helper ASSERTS its precondition on the fp64 values it returns, so a badly chosen density or target pattern fails on the CPU, not on the GPU."""
 import ctypes as C
@@ -198,8 +200,8 @@ def seams(p, K):
 
 
 # ---- the plan behind the attention entries (kf_attn_plan.h attn_plan through kfdbg_attn_plan): the forward's tile form or its paired form
-ATTN_PROMPT, ATTN_BATCH = 1, 2          # AttnProblem::entry: kf_attn_prefill, kf_attn_prefill_batch(_strided)
-ATTN_TILE, ATTN_PAIRED = 2, 3           # AttnPlan::route
+ATTN_DECODE, ATTN_PROMPT, ATTN_BATCH = 0, 1, 2   # AttnProblem::entry: kf_attn_decode, kf_attn_prefill, kf_attn_prefill_batch(_strided)
+ATTN_SLICED, ATTN_PER_TOKEN, ATTN_TILE, ATTN_PAIRED = 0, 1, 2, 3   # AttnPlan::route
 
 
 class _AttnProblem(C.Structure):
@@ -212,12 +214,18 @@ class _AttnPlan(C.Structure):
                 + [("grid", C.c_int * 3), ("grid_kv", C.c_int * 3), ("threads", C.c_int), ("lds", C.c_int), ("scratch", C.c_longlong)])
 
 
-def forward_route(hip, entry, nh, nkv, hd, n, n_seq=1, pos0=0):
-    """the route of a forward launch with aligned, dense rows"""
+def attn_plan(hip, entry, nh, nkv, hd, n, n_seq=1, pos0=0, canon=0, q_stride=None):
+    """the plan of a forward launch with aligned rows (dense unless q_stride is given)"""
     hip.kfdbg_attn_plan.argtypes = [C.POINTER(_AttnProblem), C.POINTER(_AttnPlan)]
     out = _AttnPlan()
-    assert hip.kfdbg_attn_plan(C.byref(_AttnProblem(entry, nh, nkv, hd, pos0, n, n_seq, 0, 3, nh * hd, 0, nkv * hd)), C.byref(out)) == 0 and out.status == 0
-    return out.route
+    P = _AttnProblem(entry, nh, nkv, hd, pos0, n, n_seq, canon, 3, nh * hd if q_stride is None else q_stride, 0, nkv * hd)
+    assert hip.kfdbg_attn_plan(C.byref(P), C.byref(out)) == 0 and out.status == 0
+    return out
+
+
+def forward_route(hip, entry, nh, nkv, hd, n, n_seq=1, pos0=0, q_stride=None):
+    """the route of a forward launch with aligned rows (dense unless q_stride is given)"""
+    return attn_plan(hip, entry, nh, nkv, hd, n, n_seq, pos0, 0, q_stride).route
 
 
 # ---------------------------------------------------------------------------------------------------------------- one-hot / two-hot attention
@@ -226,23 +234,27 @@ GAP_LOG2 = 160.0   # two scores that differ differ by at least this many powers 
 RAMP_G = 2048.0
 
 
-def code_gains(hd):
+GAIN_MAX = {9: 64.0, 11: 128.0}   # the largest q x k gain per code width (code_gains)
+
+
+def code_gains(hd, nbits=NBITS):
     """(gq, gk, rep): q = gq x code, k = gk x code, every code bit repeated rep times.  Two distinct keys differ in >= 1 bit, i.e. by >= 2 rep gq gk in the raw score,
     times scale log2(e) in the exponent: gq gk is the smallest power of two that makes that >= GAP_LOG2.  The gain sits mostly in k so that dk's accumulators (sums of
-    dS x q over many rows) stay small."""
-    rep = hd // NBITS
+    dS x q over many rows) stay small.  The bound on the gain: 64 at 9 bits, where the backward's accumulators carry it; 128 at 11 bits (head_dim 64 repeats a bit
+    only 5 times), which only forward cases use -- there the gain enters nothing but the score, an integer below 2^24 (asserted), and k = gk x +-1 stays a bf16 integer."""
+    rep = hd // nbits
     need = GAP_LOG2 / (2 * rep * np.log2(np.e) / np.sqrt(hd))
     g = 2.0 ** np.ceil(np.log2(need))
-    assert g <= 64
+    assert g <= GAIN_MAX[nbits] and g * nbits * rep < 2.0 ** 24
     return 2.0, g / 2.0, rep
 
 
-def codes(keys, hd, mask):
-    """+-1 code words of (key ^ mask), each of the NBITS bits repeated rep times, the remaining head_dim - NBITS rep entries 0"""
-    rep = hd // NBITS
-    b = ((np.asarray(keys)[:, None] ^ mask) >> np.arange(NBITS)[None, :]) & 1
+def codes(keys, hd, mask, nbits=NBITS):
+    """+-1 code words of (key ^ mask), each of the nbits bits repeated rep times, the remaining head_dim - nbits rep entries 0"""
+    rep = hd // nbits
+    b = ((np.asarray(keys)[:, None] ^ mask) >> np.arange(nbits)[None, :]) & 1
     c = np.zeros((len(keys), hd))
-    c[:, :NBITS * rep] = np.repeat(2.0 * b - 1.0, rep, axis=1)
+    c[:, :nbits * rep] = np.repeat(2.0 * b - 1.0, rep, axis=1)
     return c
 
 
@@ -281,29 +293,33 @@ def code_targets(T, pos0, nh, seq):
     return ta, tb
 
 
-def attn_case(family, T, nh, nkv, hd, n_seq=1, pos0=0, seed=0, vmax=1):
+def attn_case(family, T, nh, nkv, hd, n_seq=1, pos0=0, seed=0, vmax=1, vmin=None, nbits=NBITS, last=None):
     """q [n_seq T, nh hd], k / v [n_seq (pos0 + T), nkv hd], o / dO [n_seq T, nh hd] as fp64 small integers (each a bf16 value), and the targets ta / tb [n_seq, T, nh].
     family "code": k_j = gk x the code word of j (a different bit mask per kv head and sequence), q_i = gq x the code of the target, or gq / 2 x the sum of two codes
                    one bit apart -- the two scores are then equal and every other key's is lower by >= the gap.
     family "ramp": score(i, j) = RAMP_G (j - p_i): k_j = (hi, lo, 1, 1, 0 ...) with j = 16 hi + lo, q_i = RAMP_G (16, 1, -16 hi_p, -lo_p, 0 ...).  The diagonal scores 0 and
                    is the visible maximum; EVERY masked future key scores higher than any visible one, so one future key admitted takes the whole row.
-    o is NOT the forward's output: the backward takes it as an input, D = dO . o is an arbitrary integer."""
-    assert family in ("code", "ramp") and pos0 + T <= 1 << NBITS and nh % nkv == 0
+    o is NOT the forward's output: the backward takes it as an input, D = dO . o is an arbitrary integer.
+    vmin: v in [vmin, vmax] instead of [-vmax, vmax] (the decode kernels' cases: v > 0, see decode_case); nbits: the code width, 2^nbits keys at the most;
+    last = (ta [nh], tb [nh]): the code family's targets of the LAST row of every sequence, instead of code_targets' (decode_targets)."""
+    assert family in ("code", "ramp") and pos0 + T <= 1 << nbits and nh % nkv == 0
     rng = np.random.default_rng(seed)
     GQ, tot = nh // nkv, pos0 + T
     q, k = np.zeros((n_seq * T, nh * hd)), np.zeros((n_seq * tot, nkv * hd))
     ta, tb = np.zeros((n_seq, T, nh), np.int64), np.full((n_seq, T, nh), -1, np.int64)
-    gq, gk, _ = code_gains(hd)
+    gq, gk, _ = code_gains(hd, nbits)
     for s in range(n_seq):
         if family == "code":
             ta[s], tb[s] = code_targets(T, pos0, nh, s)
+            if last is not None:
+                ta[s, T - 1], tb[s, T - 1] = last
         else:
             ta[s] = (pos0 + np.arange(T))[:, None]
         for g in range(nkv):
             cols = slice(g * hd, (g + 1) * hd)
             if family == "code":
-                mask = (37 * g + 73 * s + 11) & ((1 << NBITS) - 1)
-                k[s * tot:(s + 1) * tot, cols] = gk * codes(np.arange(tot), hd, mask)
+                mask = (37 * g + 73 * s + 11) & ((1 << nbits) - 1)
+                k[s * tot:(s + 1) * tot, cols] = gk * codes(np.arange(tot), hd, mask, nbits)
             else:
                 j = np.arange(tot)
                 k[s * tot:(s + 1) * tot, g * hd + 0], k[s * tot:(s + 1) * tot, g * hd + 1] = j // 16, j % 16
@@ -311,15 +327,15 @@ def attn_case(family, T, nh, nkv, hd, n_seq=1, pos0=0, seed=0, vmax=1):
             for h in range(g * GQ, (g + 1) * GQ):
                 hc = slice(h * hd, (h + 1) * hd)
                 if family == "code":
-                    ca = codes(ta[s, :, h], hd, mask)
+                    ca = codes(ta[s, :, h], hd, mask, nbits)
                     two = tb[s, :, h] >= 0
-                    cb = codes(np.where(two, tb[s, :, h], 0), hd, mask)
+                    cb = codes(np.where(two, tb[s, :, h], 0), hd, mask, nbits)
                     q[s * T:(s + 1) * T, hc] = np.where(two[:, None], gq / 2 * (ca + cb), gq * ca)
                 else:
                     p = pos0 + np.arange(T)
                     q[s * T:(s + 1) * T, h * hd + 0], q[s * T:(s + 1) * T, h * hd + 1] = 16 * RAMP_G, RAMP_G
                     q[s * T:(s + 1) * T, h * hd + 2], q[s * T:(s + 1) * T, h * hd + 3] = -16 * RAMP_G * (p // 16), -RAMP_G * (p % 16)
-    v = rng.integers(-vmax, vmax + 1, size=(n_seq * tot, nkv * hd)).astype(np.float64)
+    v = rng.integers(-vmax if vmin is None else vmin, vmax + 1, size=(n_seq * tot, nkv * hd)).astype(np.float64)
     o = rng.integers(-1, 2, size=(n_seq * T, nh * hd)).astype(np.float64)
     dO = np.zeros((n_seq * T, nh, hd))
     for _ in range(2):   # two +-1 entries per (row, head) (where the two places coincide the row has one)
@@ -476,12 +492,13 @@ _RANGES = {(O.Q4, False): (0, 15, (2, 5), 0), (O.Q4, True): (-8, 7, (-3, 3), 8),
            (O.T_BINARY, False): (0, 1, (0, 1), 0)}
 
 
-def _group_weight(rng, type_, symmetric, lgroup, M, K, d, signs):
+def _group_weight(rng, type_, symmetric, lgroup, M, K, d, signs, edit=None):
     """a group-quantised weight built from CHOSEN codes and CHOSEN (zero, step) tables: group g has step s_g in {1, 2} and zero s_g q0_g, so code q' dequantises to
     s_g (q' - q0_g), an integer, and q0_g to 0.  (s, q0) is drawn per group and never equals the previous group's: two distinct maps q' -> s q' - zero agree on at
     most one code and every group holds at least two (sparse family), so a table read at the neighbouring group's index changes an integer.
     sparse (signs None): a fraction d of the entries holds another code -- 4-bit: q0 +- 1, q0 +- 2; ternary / 1-bit: one of the other codes of the range -- and, 4-bit,
-    one entry per group ANY code of the range (all 16 nibbles occur).  signs [M, K] in {-1, 0, 1}: code q0 + sign (4-bit only)."""
+    one entry per group ANY code of the range (all 16 nibbles occur).  signs [M, K] in {-1, 0, 1}: code q0 + sign (4-bit only).
+    edit(q, q0, step) -> q, all [M, K] integers: the caller's last word on the codes q' (the level family plants its channels), held to the same range."""
     lo, hi, (z_lo, z_hi), qbias = _RANGES[(type_, symmetric)]
     nG = M * K // lgroup
     combos = np.array([(s, q) for s in (1, 2) for q in range(z_lo, z_hi + 1)])
@@ -502,6 +519,8 @@ def _group_weight(rng, type_, symmetric, lgroup, M, K, d, signs):
         if hi - lo == 15:
             q[np.arange(nG), rng.integers(0, lgroup, size=nG)] = rng.integers(lo, hi + 1, size=nG)
         assert (q.min(axis=1) != q.max(axis=1)).all()
+    if edit is not None:
+        q = edit(q.reshape(M, K), np.broadcast_to(q0, q.shape).reshape(M, K), np.broadcast_to(step, q.shape).reshape(M, K)).reshape(nG, lgroup)
     assert q.min() >= lo and q.max() <= hi
     W = (step * (q - q0)).astype(np.float64).reshape(M, K)
     ow = O.QWeight(type_, M, K, O.pack(q + qbias, O.BITS[type_]), exact_bits(step * q0).reshape(-1), exact_bits(step).reshape(-1), lgroup, qbias)
@@ -524,22 +543,26 @@ def _lut_weight(rng, M, K, d):
     return W, O.LutWeight(M, K, data, exact_bits(table), 4)
 
 
-def exact_weight(storage, M, K, seed, signs=None, d=None):
+def exact_weight(storage, M, K, seed, signs=None, d=None, edit=None):
     """(W fp64 integers [M, K], the oracle weight that holds exactly W) for every storage the tile kernels unpack (STORAGES).  d: the fraction of non-zero entries
     (default density(K) on the second moment of the storage's non-zero values); signs [M, K] in {-1, 0, 1}: the block family's pattern -- bf16, f8 and the row codebook
-    hold it as it is, a 4-bit group g holds s_g x signs.  Asserted on the CPU: O.dequant(ow) == W."""
+    hold it as it is, a 4-bit group g holds s_g x signs.  edit(q, q0, step) -> q: see _group_weight; bf16 and f8 pass the values themselves with q0 = 0, step = 1.
+    Asserted on the CPU: O.dequant(ow) == W."""
     type_, row_lut, symmetric, lgroup = STORAGES[storage]
     rng = np.random.default_rng(seed)
     if row_lut:
-        assert signs is None
+        assert signs is None and edit is None
         W, ow = _lut_weight(rng, M, K, density(K, 2.5) if d is None else d)
     elif type_ in (O.BF16, O.F8E5M2):
         W = ternary(rng, (M, K), density(K, 2.5) if d is None else d, twos=True) if signs is None else signs.astype(np.float64)
-        ow = O.quantize(exact_bits(W), M, K, type_)
+        if edit is not None:
+            W = edit(W.astype(np.int64), np.zeros((M, K), np.int64), np.ones((M, K), np.int64)).astype(np.float64)
+        # (bf16 has no groups: the weight as O.quantize returns it, without its whole-groups precondition -- the level family's vocabulary is odd)
+        ow = O.QWeight(O.BF16, M, K, exact_bits(W).reshape(-1)) if type_ == O.BF16 else O.quantize(exact_bits(W), M, K, type_)
     else:
         assert K % lgroup == 0 or lgroup % K == 0
         m = {15: 2.5 * 2.5, 2: 2.5 * 2.5, 1: 2.5}[_RANGES[(type_, symmetric)][1] - _RANGES[(type_, symmetric)][0]]   # E[s^2] = 2.5 times E[(q' - q0)^2]
-        W, ow = _group_weight(rng, type_, symmetric, lgroup, M, K, density(K, m) if d is None else d, signs)
+        W, ow = _group_weight(rng, type_, symmetric, lgroup, M, K, density(K, m) if d is None else d, signs, edit)
     assert np.array_equal(O.dequant(ow), exact_bits(W)), "storage %s does not hold the weight exactly" % storage
     return W, ow
 
@@ -738,4 +761,284 @@ def forward_case(hip, key):
         W, ow = exact_weight(st, M, K, seed + 101 * (i + 1))
         acc = exact_product(c["f64"]["x"], np.ascontiguousarray(W.T))
         c["more"].append(dict(M=M, W=W, ow=ow, y=exact_bits(acc)))
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------- the scoring head: the "level" family
+# kf_head_logprob's fold has no fp32 sum of products to make exact -- its sums are of exponentials.  The level family makes every exponential 0 or 1: a row's logits are
+# exact integers, LEVEL_TOP on the row's winners and within +-LEVEL_FIELD everywhere else.  kf_expf(x) is exactly 0.0f for x < -87.33654 and kf_expf(0) exactly 1, so
+# whatever the tile form, the lane order, the merge order or the route:  max = 128, sum = the number of winners c, top1 = the lowest winner,
+#     lse = fl32(128 + logf(c))        logprob = fl32(fl32(t - 128) - logf(c))        (t: the target's integer logit; logf: the project's fixed kf_logf, from the oracle)
+# A partial whose own maximum is a field value holds some finite sum, and is multiplied by exactly 0 when it meets a winner's.  The second row kind, x = 0, has every
+# logit 0: sum = V (an integer below 2^24), top1 = 0, lse = logf(V) -- it counts every column exactly once.
+LEVEL_P = 16                             # channels: contraction indices that only a row's own winners answer
+LEVEL_TOP, LEVEL_FIELD = 128.0, 40.0     # the gap 88 > 87.33654
+ZERO_ROW_EVERY, ZERO_ROW_AT = 7, 3       # rows r with r % 7 == 3 are zero rows
+# storage -> (contraction indices per channel, the row's x on them).  A winner's weight on its channel: bf16 holds 16 (x 8); a 4-bit group of step s holds the code
+# q0 + 8 / s, i.e. 8 (x 16); a ternary group has no non-zero value common to every (zero, step) table, so a channel is TWO indices with x = (64, -64) and the winner holds
+# two codes whose values differ by 2: (1, -1) at step 1, (1, 0) at step 2.  Everybody else holds the code of 0 on every channel index.
+LEVEL_FORMS = {"bf16": (1, (8.0,)), "q4": (1, (16.0,)), "tern": (2, (64.0, -64.0))}
+
+
+def level_winners(V, bm):
+    """LEVEL_P winner sets (sorted column arrays), one per channel, for a vocabulary of V columns in tiles of bm (the fused route's G3 form; the panel route has no
+    tiles: 128).  Where the vocabulary has too few tiles for a set it falls back to a set that still exists; every set is asserted non-empty and inside [0, V)."""
+    n_vt, half = (V + bm - 1) // bm, bm // 2
+    full = max(V // bm - 1, 0)               # the last tile that is surely whole (tile 0 when the only tile is ragged: its columns are clipped below)
+    mid = min(n_vt // 2, full)
+
+    def tile(t):
+        return min(t, n_vt - 1) * bm
+    far = (1, 65) if n_vt > 65 else (0, n_vt - 1)
+    near = (2, 3) if n_vt > 3 else (0, n_vt - 1)
+    sets = [
+        [0],                                                         # 0  a single winner at column 0
+        [V - 1],                                                     # 1  ... at V - 1, inside the ragged last tile
+        [tile(1)],                                                   # 2  ... at the first column of a tile
+        [tile(mid) + bm - 1],                                        # 3  ... at the last column of a tile
+        [tile(mid) + half - 1, tile(mid) + half],                    # 4  either side of the wave-half seam (64 k - 1 | 64 k of 128 rows, 128 k - 1 | 128 k of 256)
+        [tile(n_vt // 3) + 7, tile(n_vt // 3) + 8],                  # 5  either side of a lane seam: 4 q4 + 3 | 4 q4 + 4
+        [tile(mid) + 15, tile(mid) + 16],                            # 6  ... 15 | 16: the last lane of one 16-row block, the first of the next
+        [tile(far[0]) + 5, tile(far[1]) + 70],                       # 7  tiles l and l + 64: the same merge lane folds both
+        [tile(near[0]) + 33, tile(near[1]) + 2],                     # 8  tiles that different merge lanes fold
+        [t * bm + (7 * t + 3) % min(bm, V - t * bm) for t in range(n_vt)],   # 9  one winner in every tile: c = n_vt
+        [V // 5, V // 2, V - 2],                                     # 10 three winners
+        list(np.linspace(0, V - 1, 64).astype(np.int64)),            # 11 64 winners spread out
+        [tile(mid) + half + 31, tile(mid) + half + 32],              # 12 a seam between two 16-row blocks of the second wave half
+        [tile(2) + 1, tile(66) + 1, tile(130) + 1],                  # 13 three tiles of one merge lane (131 tiles and more)
+        [V - 2, V - 1],                                              # 14 the last two columns
+        [0, V - 1],                                                  # 15 the first and the last
+    ]
+    out = []
+    for s in sets:
+        a = np.unique(np.minimum(np.asarray(s, np.int64), V - 1))
+        assert len(a) and a[0] >= 0 and a[-1] < V
+        out.append(a)
+    assert len(out) == LEVEL_P
+    return out
+
+
+def level_targets(n, V, bm, winners, logits):
+    """a target per row, dealt independently of the row's channel: a winner (the highest of the set: not top1 where there are several); a field column in the winner's
+    tile; one in another tile; column 0; column V - 1; the first and the last column of a tile; -1 (not scored).  A field column: nobody's winner, and where the tile
+    has one, a column whose logit in this row is not 0 (columns 0 and V - 1 and the tiles' corners are other channels' winners: they score 0)."""
+    n_vt = (V + bm - 1) // bm
+    tg = np.zeros(n, np.int32)
+    anybody = np.zeros(V, bool)
+    anybody[np.concatenate(winners)] = True
+
+    def field_in(r, t):
+        cols = np.arange(t * bm, min((t + 1) * bm, V))
+        cols = cols[~anybody[cols]]
+        assert len(cols), "no field column in tile %d" % t
+        nz = cols[logits[r, cols] != 0]
+        return int(nz[0] if len(nz) else cols[0])
+    for r in range(n):
+        tw = int(winners[r % LEVEL_P][0]) // bm
+        kind = (5 * r + r // 16) % 8
+        t = r % n_vt
+        tg[r] = [int(winners[r % LEVEL_P][-1]), field_in(r, tw), field_in(r, (tw + 1) % n_vt), 0, V - 1, t * bm, min((t + 1) * bm, V) - 1, -1][kind]
+    return tg
+
+
+def level_case(storage, V, K, n, bm, seed):
+    """head W [V, K] (exact_weight of the storage, channels planted through its edit hook), rows x [n + 2, K] (two poison rows behind row n that would score 4 x the
+    winners on every channel), targets, and the expected outputs as bit patterns: lp, lse (uint32 views of fp32) and top1 [n].  Asserted here on the fp64 product:
+    integer logits within +-256, every level row's set of columns at LEVEL_TOP equal to its winner set and every other logit within +-LEVEL_FIELD, every zero row all
+    0, the terms' magnitudes summing to < 2^23."""
+    width, xs = LEVEL_FORMS[storage]
+    nch = LEVEL_P * width
+    assert K > nch + 8 and V < 2 ** 24
+    winners = level_winners(V, bm)
+    rng = np.random.default_rng(seed)
+
+    def edit(q, q0, step):
+        q = q.copy()
+        q[:, :nch] = q0[:, :nch]                       # nobody but a winner answers a channel
+        for cols in winners:
+            q[cols] = q0[cols]                         # a winner: 0 on the field
+        for c, cols in enumerate(winners):
+            i = c * width
+            if storage == "bf16":
+                q[cols, i] = 16
+            elif storage == "q4":
+                q[cols, i] = q0[cols, i] + 8 // step[cols, i]
+            else:
+                q[cols, i], q[cols, i + 1] = 1, np.where(step[cols, i] == 1, -1, 0)
+        return q
+    W, ow = exact_weight(storage, V, K, seed + 1, edit=edit)
+    x = np.zeros((n + 2, K))
+    level = np.arange(n) % ZERO_ROW_EVERY != ZERO_ROW_AT
+    dx = 0.5
+    while True:   # the field's density: the largest that keeps the field within +-LEVEL_FIELD (asserted below either way)
+        xf = ternary(rng, (n, K - nch), dx) * level[:, None]
+        if np.abs(xf @ W[:, nch:].T).max() <= LEVEL_FIELD or dx < 1e-3:
+            break
+        dx /= 2
+    x[:n, nch:] = xf
+    for r in np.nonzero(level)[0]:
+        x[r, (r % LEVEL_P) * width:(r % LEVEL_P + 1) * width] = xs
+    x[n:, :nch] = np.tile(np.asarray(xs) * 4, LEVEL_P)
+    logits = x[:n] @ W.T
+    assert np.array_equal(logits, np.rint(logits)) and np.abs(logits).max() <= BOUND
+    assert (np.abs(x[:n]) @ np.abs(W).T).max() < 2.0 ** 23
+    assert (np.abs(xf) > 0).any() or n < 3
+    c = np.ones(n)
+    first = np.zeros(n, np.int32)
+    for r in range(n):
+        if level[r]:
+            win = winners[r % LEVEL_P]
+            assert np.array_equal(np.nonzero(logits[r] == LEVEL_TOP)[0], win), "row %d: the winner set" % r
+            assert np.abs(np.delete(logits[r], win)).max() <= LEVEL_FIELD, "row %d: field %g: lower the density" % (r, np.abs(np.delete(logits[r], win)).max())
+            c[r], first[r] = len(win), win[0]
+        else:
+            assert not logits[r].any()
+            c[r] = V
+    tg = level_targets(n, V, bm, winners, logits)
+    m = np.where(level, np.float32(LEVEL_TOP), np.float32(0.0)).astype(np.float32)
+    lg = O.logf(c.astype(np.float32)).astype(np.float32)
+    t = logits[np.arange(n), np.maximum(tg, 0)].astype(np.float32)
+    lp = np.where(tg >= 0, ((t - m).astype(np.float32) - lg).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    lse = (m + lg).astype(np.float32)
+    return dict(storage=storage, V=V, K=K, n=n, bm=bm, W=W, ow=ow, x=x, targets=tg, winners=winners, level=level, logits=logits, count=c,
+                lp=lp.view(np.uint32), lse=lse.view(np.uint32), top1=first)
+
+
+def level_fold(logits, targets, V, bm, mutate=None):
+    """a plain numpy restatement of the fold (per tile {max, sum exp, first index, target logit}, tiles merged in order) on exact logits, with kf_expf's two exact
+    values: exp(0) = 1, exp(d) = 0 for d < -87.33654 (the family's rows make no other difference).  mutate: one wrong decision --
+    ("drop", v) column v left out; ("twice", v) counted twice; ("admit",) column V read as a copy of column V - 1 (the tile loads clamp to the last row);
+    ("skip", t) tile t left out; ("tie_high",) ties of the maximum go to the higher index; ("neighbour",) the target's logit read from the next tile.
+    -> (lp, lse, top1) as level_case returns them"""
+    n = logits.shape[0]
+    kind = mutate[0] if mutate else None
+    lg = np.concatenate([logits, logits[:, -1:]], axis=1) if kind == "admit" else logits
+    cols = list(range(lg.shape[1]))
+    if kind == "drop":
+        cols.remove(mutate[1])
+    if kind == "twice":
+        cols.append(mutate[1])
+    if kind == "skip":
+        cols = [v for v in cols if v // bm != mutate[1]]
+    cols = np.asarray(cols)
+    lp, lse, top1 = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+    for r in range(n):
+        row = lg[r, cols]
+        m = row.max()
+        d = row - m
+        live = d[d >= -87.34]   # all 0 on the family's rows; a mutation that removes a row's only winner leaves the field, summed here in one of the possible orders
+        s = np.float32((d == 0).sum()) if not live.any() else np.float32(O.expf(live.astype(np.float32)).sum(dtype=np.float32))
+        at = cols[row == m]
+        top1[r] = at.max() if kind == "tie_high" else at.min()
+        lgs = O.logf(np.asarray([s], np.float32))[0]
+        tgt = int(targets[r])
+        if kind == "neighbour" and tgt >= 0:
+            tgt = min(tgt + bm, V - 1)
+        t = np.float32(logits[r, tgt]) if tgt >= 0 else np.float32(0)
+        lp[r] = (np.float32(t - np.float32(m)) - lgs) if tgt >= 0 else np.float32(0)
+        lse[r] = np.float32(m) + lgs
+    return lp.view(np.uint32), lse.view(np.uint32), top1
+
+
+# ---- the plan behind kf_head_logprob (kf_score_plan.h score_plan through kfdbg_score_plan), the problem filled as kf_abi.hip score_problem fills it
+SR_FUSED, SR_PANEL = 0, 1
+SCORE_BIG, SCORE_SMALL = 0, 1            # G3 forms; the "score_form" knob: < 0 the rule
+
+
+class _ScoreProblem(C.Structure):
+    _fields_ = [("w", _Mat), ("n", C.c_int), ("x_al", C.c_int), ("force", C.c_int), ("form", C.c_int)]
+
+
+class _ScorePlan(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("route", "status", "form", "n_vt", "n_rb", "gx", "block", "lds", "panel_rows")] + [("scratch", C.c_longlong)]
+
+
+def score_plan(hip, key):
+    storage, V, K, n, force, form = key
+    hip.kfdbg_score_plan.argtypes = [C.POINTER(_ScoreProblem), C.POINTER(_ScorePlan)]
+    out = _ScorePlan()
+    assert hip.kfdbg_score_plan(C.byref(_ScoreProblem(storage_mat(storage, V, K), n, 1, force, form)), C.byref(out)) == 0 and out.status == 0
+    return out
+
+
+def score_name(p):
+    """"FUSED/SMALL/33x2" (vocabulary tiles x row blocks), "PANEL/128" (rows per panel)"""
+    return "FUSED/%s/%dx%d" % ({SCORE_BIG: "BIG", SCORE_SMALL: "SMALL"}[p.form], p.n_vt, p.n_rb) if p.route == SR_FUSED else "PANEL/%d" % p.panel_rows
+
+
+# (storage, V, K, rows, "score_route" knob, "score_form" knob) -> the plan's name, pinned by tests/test_exact_inputs_cpu.py and asserted before every call.  The smallest
+# shapes that reach each path, K = 64 unless the case is about K.  4168 = 32.56 tiles of 128 = 16.28 of 256: ragged either way.
+SCORE_CASES = {}
+for _n in (1, 127, 128, 129, 257):
+    SCORE_CASES[("bf16", 4096 + 72, 64, _n, 0, -1)] = "FUSED/SMALL/33x%d" % ((_n + 127) // 128)
+SCORE_CASES.update({
+    ("bf16", 128, 64, 40, 0, -1): "FUSED/SMALL/1x1",                       # one tile
+    ("bf16", 128 * 130 + 5, 64, 40, 0, -1): "FUSED/SMALL/131x1",           # more than 64 partials per row, three for merge lanes 0 .. 2
+    ("bf16", 4096 + 72, 64, 513, 0, -1): "FUSED/BIG/17x3",                 # the 256-row tile by the rule
+    ("bf16", 4096 + 72, 64, 40, 0, SCORE_BIG): "FUSED/BIG/17x1",           # ... forced
+    ("bf16", 256 * 65 + 72, 64, 40, 0, SCORE_BIG): "FUSED/BIG/66x1",       # 66 partials per row
+    ("bf16", 4096 + 72, 192, 129, 0, -1): "FUSED/SMALL/33x2",              # three k steps
+    ("bf16", 4096 + 72, 1024, 129, 0, -1): "FUSED/SMALL/33x2",
+    ("bf16", 4096 + 72, 64, 130, 1, -1): "PANEL/128",                      # a bf16 head forced to the panel route: a panel of 128 rows and one of 2
+    ("bf16", 1000, 64, 9, 1, -1): "PANEL/9",                               # V no multiple of 256, the row kernel's thread stride
+    ("bf16", 1000, 200, 130, 0, -1): "PANEL/128",                          # dim 200: no multiple of the tile's k step
+    ("q4", 1000, 128, 130, 0, -1): "PANEL/128",
+    ("tern", 1000, 128, 33, 0, -1): "PANEL/33",
+})
+
+
+def score_case(hip, key):
+    storage, V, K, n, force, form = key
+    p = score_plan(hip, key)
+    bm = {SCORE_BIG: 256, SCORE_SMALL: 128}[p.form] if p.route == SR_FUSED else 128
+    return level_case(storage, V, K, n, bm, seed=V + 3 * K + 7 * n + 11 * force + form)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the decode kernels on the one-hot / two-hot families
+# kf_attn_decode (kf_attn.hip attn_kernel / attn_fast_kernel, route ATTN_SLICED) takes ONE query row: the last row of an attn_case with T = pos + 1.  Its v is drawn from
+# [1, 4]: the canonical order sums in fp64, where a weight of 2^-160 does NOT vanish -- it vanishes in the fp32 conversion of O / L, and where the exact output is 0 what
+# is left of it there is a signed zero whose sign is the leak's.  With v > 0 no output is 0 and (float)(O / L) is the closed form bit for bit in both orders
+# (tests/test_exact_inputs_cpu.py emulates both and shows the signed zero on the [-2, 2] draw).
+DECODE_POS = [0, 1, 63, 64, 128, 129, 191, 192, 193, 255, 256, 300, 511]   # 129 .. 191: one slice of > 128 keys (8 waves for GQ <= 2); 192 | 193 keys (positions 191 | 192): one slice | four
+DECODE_LONG = dict(pos=2046, nh=4, nkv=2, nbits=11)                        # 2047 keys: the largest slice count (KF_ATTN_MAX_SPLITS = 32)
+DECODE_BOUND, DECODE_BELOW = 300, 130                                      # a launch laid out for position 300 whose device position is 130
+DECODE_KINDS = 8
+DECODE_V = dict(vmin=1, vmax=4)
+PER_TOKEN_N = [1, 3, 7]                                                    # below ATTN_TILE_MIN_TOK
+PER_TOKEN_REFUSED = dict(n=33, pad=4)                                      # a q row stride of n_head head_dim + 4 elements: no multiple of 8, the tile kernel refuses it
+
+
+def decode_slices(pos_bound, nkv, gq, canon):
+    """kf_attn_plan.h attn_slices + attn_plan restated: (n_splits, chunk, nw, gq_split) of a kf_attn_decode launch laid out for positions up to pos_bound; asserted
+    against kfdbg_attn_plan before every call, so a moved threshold fails loudly"""
+    ln, nsp = pos_bound + 1, 1
+    if ln > 192:
+        nsp = min((ln + 63) // 64, 512 // nkv, 32)
+    chunk = (ln + nsp - 1) // nsp
+    return nsp, chunk, 8 if gq <= 2 and chunk > 128 else 4, gq // 2 if canon and gq > 2 else 1
+
+
+def decode_targets(pos, nh, chunk, shift):
+    """the last row's targets (ta [nh], tb [nh]) by kind (head + shift) % DECODE_KINDS: the diagonal; key 0; key pos - 1; the first key of a middle slice; the last key
+    of a slice; the first key of the slice that holds pos; two-hot {a, a - lowest set bit of a} with a the first key of a slice, so that the pair straddles two slices
+    (a = pos where the launch has one slice); two-hot on the diagonal.  chunk: keys per slice, as the plan reports it."""
+    ta, tb = np.full(nh, pos, np.int64), np.full(nh, -1, np.int64)
+    s_pos = pos // chunk
+    for h in range(nh):
+        kind = (h + shift) % DECODE_KINDS
+        a = [pos, 0, pos - 1, chunk * ((s_pos + 1) // 2), chunk * (s_pos // 2 + 1) - 1, chunk * s_pos, chunk * max(s_pos, 1) if s_pos else pos, pos][kind]
+        a = a if 0 <= a <= pos else pos
+        ta[h] = a
+        if kind >= 6 and a > 0:
+            tb[h] = a - (a & -a)
+    return ta, tb
+
+
+def decode_case(family, pos, nh, nkv, hd, chunk, shift=0, nbits=NBITS, T=None):
+    """an attn_case of T = pos + 1 rows (or more: rows behind pos stay in the cache) whose row `pos` is the query of a decode call, and that row's closed-form output
+    as bit patterns"""
+    T = pos + 1 if T is None else T
+    last = decode_targets(pos, nh, chunk, shift) if family == "code" and T == pos + 1 else None
+    c = attn_case(family, T, nh, nkv, hd, seed=pos + nh + hd, nbits=nbits, last=last, **DECODE_V)
+    c["want"] = bits(closed_forward(c)[pos])
     return c

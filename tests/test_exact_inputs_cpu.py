@@ -1,5 +1,5 @@
 """Everything about the exact-arithmetic inputs (tests/exact_inputs.py) that can be settled without a GPU, for every case tests/test_gpu_exact_linear_backward.py,
-tests/test_gpu_exact_linear_forward.py and tests/test_gpu_exact_attention.py run:
+tests/test_gpu_exact_linear_forward.py, tests/test_gpu_exact_attention.py, tests/test_gpu_exact_score.py and tests/test_gpu_exact_attention_decode.py run:
 
   preconditions   every operand is a bf16 value, every expected accumulator an integer (or half) inside the bound -- asserted by the helpers as the cases are built
   probabilities   an fp32 emulation of the softmax statistics AS THE KERNELS COMPUTE THEM (running maximum per key tile, exp2 of score x scale x log2 e - M,
@@ -577,3 +577,267 @@ def test_one_groups_table_index_shifted_by_one(forward_cases):
         assert (got != E.bits(ref)).sum() >= 64
         print("symmetric range, draw %d: max error %.4f of max|exact|, the 2^-8 bar %s" % (draw, np.abs(E.f64(got) - ref).max() / np.abs(ref).max(),
                                                                                         "accepts" if bar_accepts(E.f64(got), ref, 2.0 ** -8) else "rejects"))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the scoring head: the level family
+@pytest.fixture(scope="module")
+def score_cases(hip):
+    """every case of tests/test_gpu_exact_score.py, built once: level_case asserts integer logits within +-256, the winner sets, the gap and the zero rows as it goes"""
+    return {key: E.score_case(hip, key) for key in E.SCORE_CASES}
+
+
+def test_score_cases_are_pinned_against_the_plan(hip, score_cases):
+    """the table names the plan of each case (route, tile form, vocabulary tiles x row blocks, or the panel's rows), and between them the cases reach both tile forms by
+    the rule and by the knob, more than 64 and more than 128 partials per row, one k step and several, and the panel route for every reason it is taken"""
+    names = set()
+    for key, want in E.SCORE_CASES.items():
+        p = E.score_plan(hip, key)
+        assert E.score_name(p) == want, key
+        names.add(want.rsplit("/", 1)[0])
+        if p.route == E.SR_FUSED:
+            assert (p.n_vt, p.n_rb) == (-(-key[1] // score_cases[key]["bm"]), -(-key[3] // score_cases[key]["bm"]))
+    assert names == {"FUSED/SMALL", "FUSED/BIG", "PANEL"}
+    fused = [E.score_plan(hip, k) for k in E.SCORE_CASES if k[4] == 0 and k[0] == "bf16" and k[2] % 64 == 0]
+    assert {p.route for p in fused} == {E.SR_FUSED} and max(p.n_vt for p in fused if p.form == E.SCORE_SMALL) > 128 and max(p.n_vt for p in fused if p.form == E.SCORE_BIG) > 64
+    assert {k[2] for k in E.SCORE_CASES if E.SCORE_CASES[k].startswith("FUSED")} == {64, 192, 1024}
+    assert {k[0] for k in E.SCORE_CASES if E.SCORE_CASES[k].startswith("PANEL")} == {"bf16", "q4", "tern"}
+
+
+def test_level_case_preconditions(score_cases):
+    """what makes the closed form hold, and what makes a wrong fold visible, over every case: the gap to the winners is >= 88 > 87.33654 (kf_expf's exact zero), the
+    field is not empty, the targets take every kind, the winner sets sit on the seams the family is about, and the expectation equals a plain restatement of the fold"""
+    assert O.expf(np.float32([0.0]))[0] == 1.0 and O.expf(np.float32([-(E.LEVEL_TOP - E.LEVEL_FIELD)]))[0] == 0.0 and O.expf(np.float32([-87.3]))[0] > 0.0
+    for key, c in score_cases.items():
+        V, n, bm, lg = c["V"], c["n"], c["bm"], c["logits"]
+        assert np.array_equal(E.f64(O.dequant(c["ow"])), c["W"]), key
+        lev = c["level"]
+        assert lev[0] and (n < 4 or not lev[E.ZERO_ROW_AT])
+        field = np.where(lg == E.LEVEL_TOP, 0.0, lg)[lev]
+        assert np.abs(field).max() <= E.LEVEL_FIELD and (field != 0).mean() > 0.3, key
+        tg = c["targets"]
+        assert ((tg >= -1) & (tg < V)).all()
+        if n >= 16:
+            assert (tg == -1).any() and (tg == 0).any() and (tg == V - 1).any() and len(set(tg.tolist())) >= 6, key
+            t = lg[np.arange(n), np.maximum(tg, 0)]
+            assert (t[lev & (tg >= 0)] == E.LEVEL_TOP).any() and ((t != E.LEVEL_TOP) & (t != 0))[lev & (tg >= 0)].any(), key   # winners and non-zero field values are scored
+        w = c["winners"]
+        half = bm // 2
+        assert [len(s) for s in w[:4]] == [1, 1, 1, 1] and w[0][0] == 0 and w[1][0] == V - 1 and w[2][0] % bm == 0 and (w[3][0] % bm == bm - 1 or w[3][0] == V - 1)
+        if V > bm:
+            assert w[4][1] - w[4][0] == 1 and w[4][1] % bm == half and w[5][0] % 4 == 3 and w[5][1] - w[5][0] == 1 and w[6][0] % 16 == 15 and w[6][1] - w[6][0] == 1
+            assert len(w[9]) == -(-V // bm) and (np.diff(w[9] // bm) == 1).all() and len(w[11]) == 64 and len(w[10]) == 3
+            assert w[8][0] // bm != w[8][1] // bm and (w[8][0] // bm) % 64 != (w[8][1] // bm) % 64
+        if -(-V // bm) > 65:
+            assert w[7][1] // bm - w[7][0] // bm == 64
+        if -(-V // bm) > 130:
+            assert len(w[13]) == 3 and set(np.diff(w[13] // bm)) == {64}
+        got = E.level_fold(lg, tg, V, bm)
+        for a, b in zip(got, (c["lp"], c["lse"], c["top1"])):
+            assert np.array_equal(a, b), key
+
+
+MUTATION_KEYS = [("bf16", 4096 + 72, 64, 129, 0, -1), ("bf16", 128 * 130 + 5, 64, 40, 0, -1), ("bf16", 256 * 65 + 72, 64, 40, 0, E.SCORE_BIG), ("q4", 1000, 128, 130, 0, -1)]
+
+
+@pytest.mark.parametrize("key", MUTATION_KEYS)
+def test_one_wrong_fold_decision_changes_the_bits(score_cases, key):
+    """a numpy restatement of the fold with ONE wrong decision -- a column dropped, a column counted twice, column V admitted (the tile loads clamp to row V - 1, so it
+    reads as a copy of it), a tile left out (one that holds no winner of most rows: the zero rows and the rows with a winner in every tile see it), a tie sent to the higher index, the
+    target's logit read from the neighbouring tile: every one changes expected bits, in the outputs named below.
+
+    The record for the bar used so far (lse within d = 2^-7 max|logit| of the row, logprob within 2 d, top1 free within d), observed on the planted Gaussian rows of
+    tests/test_gpu_score.py (33 x 4096 x 1024, seed 4129, and 130 x 4168 x 1024, seed 4298; 2 d is about 0.16), with each fault applied to EVERY row -- a finding, not
+    an assertion:
+      a column that is not the winner dropped, or counted twice    lse moves by at most 0.011 d: passes on every row
+      a tile of 128 columns without the winner left out            lse moves by at most 0.48 d: passes on every row
+      column V admitted (a copy of column V - 1)                   passes on every row but the one whose winner is V - 1 (1 of 33, 1 of 130)
+      the winner dropped, counted twice, or its tile left out      lse moves by 7 .. 37 d: rejected on every row
+      the target's logit read from the neighbouring tile           logprob moves by |t - t'|, 2.7 on average: rejected on 26 of 28 and 101 of 111 scored rows, passes on the rest
+      a tie sent to the higher index                               invisible: the planted rows have no tie (one test holds ties, on 40 rows and two tiles)
+    So the old bar sees a fault of the fold only where it touches the row's winner or a scored target."""
+    c = score_cases[key]
+    V, n, bm, lg, tg, lev = c["V"], c["n"], c["bm"], c["logits"], c["targets"], c["level"]
+    want = (c["lp"], c["lse"], c["top1"])
+
+    def changed(mut):
+        got = E.level_fold(lg, tg, V, bm, mut)
+        return [np.nonzero(a != b)[0] for a, b in zip(got, want)]
+    zero = np.nonzero(~lev)[0]
+    assert len(zero)
+    for v in (0, V - 1, int(c["winners"][4][0]), int(c["winners"][9][len(c["winners"][9]) // 2])):
+        rows = np.nonzero(lg[:, v] == np.where(lev, E.LEVEL_TOP, 0.0))[0]   # the rows that count column v: its winners' rows and every zero row
+        assert set(zero) <= set(rows) and len(rows) > len(zero)
+        for mut in ("drop", "twice"):
+            lp, lse, top1 = changed((mut, v))
+            assert set(lse) == set(rows) and set(top1) <= set(rows) and set(lp) <= set(rows), (mut, v)   # every row that counts v, and no other
+    lp, lse, top1 = changed(("admit",))
+    assert set(zero) <= set(lse) and {r for r in range(n) if lev[r] and V - 1 in c["winners"][r % E.LEVEL_P]} <= set(lse) and len(lse) > len(zero)
+    t_skip = (c["winners"][9][-1] // bm) // 2 + 1 if V > bm else 0
+    lp, lse, top1 = changed(("skip", int(t_skip)))
+    assert set(zero) <= set(lse) and {r for r in range(n) if lev[r] and r % E.LEVEL_P == 9} <= set(lse)
+    lp, lse, top1 = changed(("tie_high",))
+    assert set(top1) == {r for r in range(n) if c["count"][r] > 1} and not len(lse) and not len(lp)
+    lp, lse, top1 = changed(("neighbour",))
+    assert len(lp) >= (1 if V <= bm else n // 4) and not len(lse) and not len(top1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the decode kernels on the one-hot / two-hot families
+def _decode_cases():
+    """(family, pos, nh, nkv, hd, shift, nbits) of every kf_attn_decode call of tests/test_gpu_exact_attention_decode.py with the device position at the bound"""
+    out = []
+    for pos in E.DECODE_POS:
+        for nh, nkv in E.HEADS:
+            for hd in E.HEAD_DIMS:
+                out += [("code", pos, nh, nkv, hd, sh, E.NBITS) for sh in range(0, E.DECODE_KINDS, nh)] + [("ramp", pos, nh, nkv, hd, 0, E.NBITS)]
+    t = E.DECODE_LONG
+    for hd in E.HEAD_DIMS:
+        out += [("code", t["pos"], t["nh"], t["nkv"], hd, sh, t["nbits"]) for sh in range(0, E.DECODE_KINDS, t["nh"])] + [("ramp", t["pos"], t["nh"], t["nkv"], hd, 0, t["nbits"])]
+    return out
+
+
+def test_decode_plans_are_pinned(hip):
+    """kfdbg_attn_plan against decode_slices (the rule restated) for every decode case in both orders, and the points the cases are about: one slice up to 192 keys with 8
+    waves from 129 keys for GQ <= 2, four slices at 193 keys, 32 slices of 64 at 2047 keys, five of 61 for the bound 300; the per-token route below 8 tokens and for a q
+    stride the tile kernel refuses.  Over the calls of a shape the targets take every kind; from two slices on they sit on the first and the last key of a slice and the
+    two-hot pair straddles two slices."""
+    for canon in (0, 1):
+        for pos in E.DECODE_POS + [E.DECODE_LONG["pos"], E.DECODE_BOUND]:
+            for nh, nkv in E.HEADS:
+                for hd in E.HEAD_DIMS:
+                    p = E.attn_plan(hip, E.ATTN_DECODE, nh, nkv, hd, 1, 1, pos, canon)
+                    assert (p.route, p.n_splits, p.chunk, p.nw, p.gq_split) == (E.ATTN_SLICED,) + E.decode_slices(pos, nkv, nh // nkv, canon), (pos, nh, nkv, canon)
+                    assert p.scratch == hip.kf_attn_scratch_bytes(nh, hd) and p.n_splits <= 32
+    S = E.decode_slices
+    assert [S(p, 2, 1, 0)[:3] for p in (128, 129, 191, 192, 193)] == [(1, 129, 8), (1, 130, 8), (1, 192, 8), (4, 49, 4), (4, 49, 4)]
+    assert S(127, 2, 1, 0)[:3] == (1, 128, 4) and S(191, 1, 4, 0)[:3] == (1, 192, 4) and S(191, 2, 1, 0)[0] == 1 and S(192, 2, 1, 0)[0] == 4
+    assert S(E.DECODE_LONG["pos"], E.DECODE_LONG["nkv"], 2, 0)[:2] == (32, 64) and S(E.DECODE_BOUND, 2, 2, 1)[:2] == (5, 61) and S(300, 1, 8, 1)[3] == 4
+    for nh, nkv in E.HEADS:
+        for hd in E.HEAD_DIMS:
+            for pos0 in (0, E.FWD_POS0):
+                for n in E.PER_TOKEN_N:
+                    assert E.forward_route(hip, E.ATTN_PROMPT, nh, nkv, hd, n, 1, pos0) == E.ATTN_PER_TOKEN
+                r = E.PER_TOKEN_REFUSED
+                assert E.forward_route(hip, E.ATTN_PROMPT, nh, nkv, hd, r["n"], 1, pos0) == E.ATTN_TILE
+                assert E.forward_route(hip, E.ATTN_PROMPT, nh, nkv, hd, r["n"], 1, pos0, q_stride=nh * hd + r["pad"]) == E.ATTN_PER_TOKEN
+            for pos in (300, 511):
+                nsp, chunk, _, _ = S(pos, nkv, nh // nkv, 0)
+                ta = np.concatenate([E.decode_targets(pos, nh, chunk, sh)[0] for sh in range(0, E.DECODE_KINDS, nh)])
+                tb = np.concatenate([E.decode_targets(pos, nh, chunk, sh)[1] for sh in range(0, E.DECODE_KINDS, nh)])
+                assert len(ta) == E.DECODE_KINDS and nsp > 2
+                assert (ta % chunk == 0).sum() >= 3 and (ta % chunk == chunk - 1).any() and 0 in ta and pos in ta and pos - 1 in ta
+                two = tb >= 0
+                assert two.sum() == 2 and (ta[two] // chunk != tb[two] // chunk).any() and (ta[two] % chunk == 0).any()
+                assert all(bin(a ^ b).count("1") == 1 for a, b in zip(ta[two], tb[two]))
+
+
+def kf_exp2_parts(y):
+    """kf_device.h kf_exp2_parts on fp32 y: n = the nearest integer, f = 2^(y - n) from the degree-7 polynomial (each fma emulated in fp64 and rounded once more to fp32:
+    the last bit of f may differ from the kernel's, which nothing below depends on)"""
+    y = y.astype(F32)
+    n = ((y + F32(12582912.0)).astype(F32) - F32(12582912.0)).astype(F32)
+    r = (y - n).astype(F32)
+    p = np.full(y.shape, F32(1.52527338e-5))
+    for coef in (1.54035304e-4, 1.33335581e-3, 9.61812911e-3, 5.55041087e-2, 2.40226507e-1, 6.93147181e-1, 1.0):
+        p = (p.astype(np.float64) * r.astype(np.float64) + np.float64(F32(coef))).astype(F32)
+    return p, n
+
+
+def _query_row(c, row):
+    """per head, for query row `row` (position pos0 + row) of a case: raw q . k over the visible keys (exact integers in fp32), the bf16 score both orders take, the
+    group's v [keys, hd], and which keys are the row's targets"""
+    nh, nkv, hd = c["nh"], c["nkv"], c["hd"]
+    GQ, ln = nh // nkv, c["pos0"] + row + 1
+    rden = E.kernel_scale(hd)
+    for h in range(nh):
+        q = c["q"][row, h * hd:(h + 1) * hd]
+        k = c["k"][:ln, (h // GQ) * hd:(h // GQ + 1) * hd]
+        assert (np.abs(k) @ np.abs(q)).max() < 2.0 ** 24
+        raw = (k @ q).astype(F32)
+        on = np.zeros(ln, bool)
+        on[c["ta"][0, row, h]] = True
+        if c["tb"][0, row, h] >= 0:
+            on[c["tb"][0, row, h]] = True
+        yield h, raw, E.f64(E.bits((raw * rden).astype(F32))).astype(F32), c["v"][:ln, (h // GQ) * hd:(h // GQ + 1) * hd], on
+
+
+def _canonical_out(s, v):
+    """the canonical order on one head: weights f 2^(n - m) in fp64 (a shift below -1022 is clamped: canon_shift), fp64 sums, one conversion to fp32, one bf16 store"""
+    f, n = kf_exp2_parts((s * LOG2E).astype(F32))
+    w = np.ldexp(f.astype(np.float64), np.maximum(n - n.max(), -1022.0).astype(np.int64))
+    return E.bits((w @ v / w.sum()).astype(F32)), w
+
+
+def _both_orders(c, row, nsp, chunk, nw, what):
+    """one query row through both orders' arithmetic -> (two-hot heads, slices that hold no target)"""
+    hd = c["hd"]
+    want = E.bits(E.closed_forward(c)[row])
+    batch = 4 * nw * (64 // (hd // 8))
+    n_two = n_without = 0
+    for h, raw, s, v, on in _query_row(c, row):
+        assert len(set(raw[on].tolist())) == 1 and len(set(s[on].tolist())) == 1, what                 # equal bit for bit
+        assert ((s[on][0] - s[~on]) * LOG2E >= 150).all() if (~on).any() else True, what                # exp2 of <= -150 is 0.0f
+        n_two += on.sum() == 2
+        # fast order
+        Ms, ls, Ps = [], [], []
+        for sp in range(nsp):
+            seg = s[None, sp * chunk:(sp + 1) * chunk]
+            if seg.shape[1] == 0:
+                continue   # a slice behind the position publishes a neutral partial: m = -inf, l = 0
+            M, l, P = walk(seg, range(-(-seg.shape[1] // batch)), batch, LOG2E)
+            Ms.append(M[0]), ls.append(l[0]), Ps.append(P[0])
+            n_without += not on[sp * chunk:(sp + 1) * chunk].any()
+        Mx = max(Ms)
+        sc = [exp2f(np.asarray([(m - Mx) * LOG2E], F32))[0] for m in Ms]
+        assert F32(sum(F32(l * a) for l, a in zip(ls, sc))) == on.sum(), what
+        assert np.array_equal(np.concatenate([P * a for P, a in zip(Ps, sc)]), on.astype(F32)), what
+        # canonical order
+        got, w = _canonical_out(s, v)
+        assert np.array_equal(got, want[h * hd:(h + 1) * hd]), what
+        if (~on).any() and c["family"] == "code":
+            assert (w[~on] > 0).all() and w[~on].max() / w[on][0] <= 2.0 ** -150, what                 # alive in fp64, gone after the two stores
+    return n_two, n_without
+
+
+def test_decode_probabilities_are_exact_in_both_orders(hip):
+    """kf_attn.hip on the query row of every call tests/test_gpu_exact_attention_decode.py makes: the decode cases, the position below the bound, the per-token route.
+    Both orders take score = bf16(fl32(q . k x fl32(1 / sqrt(hd)))); the two scores of a two-hot row are equal bit for bit, every other key's is lower by the gap.
+    fast order:      per slice of `chunk` keys and batch of 4 x waves x (64 / (hd / 8)) keys a running maximum, p = exp2(fl32((s - M) log2 e)), slices merged with
+                     exp2(fl32((M_slice - M) log2 e)): every target enters with exactly 1.0f, every other key and every slice without a target with exactly 0.0f
+    canonical order: p = f 2^(n - m) from kf_exp2_parts(fl32(s log2 e)), fp64 sums: a non-target's weight of 2^-150 and less is NOT zero, but
+                     bf16((float)(O / L)) is the closed form bit for bit -- because v > 0: on the [-2, 2] draw of the other modules the same emulation leaves -0.0
+                     (0x8000) where the closed form is +0, the sign of what leaked"""
+    n_two = n_without = 0
+    for fam, pos, nh, nkv, hd, shift, nbits in _decode_cases():
+        nsp, chunk, nw, _ = E.decode_slices(pos, nkv, nh // nkv, 0)
+        c = E.decode_case(fam, pos, nh, nkv, hd, chunk, shift, nbits)
+        a, b = _both_orders(c, pos, nsp, chunk, nw, (fam, pos, nh, hd, shift))
+        n_two, n_without = n_two + a, n_without + b
+        assert np.array_equal(c["want"], E.bits(E.closed_forward(c)[pos]))
+        if pos in (0, 193, 511):   # (the oracle's two modes restate these orders: they agree with the closed form too)
+            for mode in (O.ATTN_CANON, O.ATTN_FUSED):
+                assert np.array_equal(O.attn_decode(E.exact_bits(c["q"][pos]), E.exact_bits(c["k"]), E.exact_bits(c["v"]), pos, nh, nkv, hd, mode=mode), c["want"])
+    assert n_two > 50 and n_without > 1000
+    for nh, nkv in E.HEADS:
+        for hd in E.HEAD_DIMS:
+            nsp, chunk, nw, _ = E.decode_slices(E.DECODE_BOUND, nkv, nh // nkv, 0)   # the slices of the bound; the keys of the position
+            for fam in ("ramp", "code"):
+                c = E.decode_case(fam, E.DECODE_BELOW, nh, nkv, hd, chunk, T=E.DECODE_BOUND + 1)
+                _both_orders(c, E.DECODE_BELOW, nsp, chunk, nw, (fam, "below the bound", nh, hd))
+                if fam == "ramp":   # every row behind the position scores above every visible key
+                    q = c["q"][E.DECODE_BELOW, :hd]
+                    sc = c["k"][:, :hd] @ q
+                    assert sc[E.DECODE_BELOW + 1:].min() > sc[:E.DECODE_BELOW + 1].max()
+                for pos0 in (0, E.FWD_POS0):
+                    for n in E.PER_TOKEN_N + [E.PER_TOKEN_REFUSED["n"]]:
+                        c = E.attn_case(fam, n, nh, nkv, hd, 1, pos0, seed=n + nh + hd, **E.DECODE_V)
+                        for row in range(n):   # one slice per token: chunk = the launch's last position + 1
+                            _both_orders(c, row, 1, pos0 + n, 8 if nh // nkv <= 2 and pos0 + n > 128 else 4, (fam, "per token", n, pos0, nh, hd))
+    # the signed zero that v > 0 avoids
+    c = E.attn_case("code", 301, 4, 2, 64, seed=7, vmax=2)
+    neg = 0
+    for h, raw, s, v, _ in _query_row(c, 300):
+        got, _ = _canonical_out(s, v)
+        want = E.bits(E.closed_forward(c)[300, h * 64:(h + 1) * 64])
+        assert np.array_equal(E.f64(got), E.f64(want))
+        neg += int(((got == 0x8000) & (want == 0)).sum())
+    assert neg > 0
