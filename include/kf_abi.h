@@ -387,6 +387,28 @@ int kf_linear_backward(kf_ctx* ctx, const kf_weight* w, const kf_bf16* deltaIn, 
 size_t kf_gama_backward_scratch_bytes(int OC, int IC, int n);
 int kf_gama_backward(kf_ctx* ctx, const kf_weight* w, const kf_bf16* deltaIn, const kf_bf16* inp, kf_bf16* gGama, int n, float scale, void* scratch);
 
+/* The third way: the matrix W [OC, IC] stays frozen in whatever storage it has and a low-rank pair trains beside it -- the LORA branch of SLP::Forw / SLP::Back
+ * (NeuronFuse.cu:286-302, 343-358, 384-423, 453-468: HIERARCH_LorAB::Forw / Back; construction SparseNeuron.cpp:210-264).  a [r, IC], b [OC, r] bf16 row-major,
+ * x [n, IC], y [n, OC].  s is the reference's sAB and multiplies BOTH products of a direction, as there: the adapter's effective weight is s^2 b a -- on purpose, a
+ * caller who wants the usual alpha / r passes s = sqrt(alpha / r).
+ *   kf_lora_forward    ax [n, r]     = bf16(s x a^T)                     kept for the backward (the reference's Ax)
+ *                      y  [n, OC]    = bf16(y + s ax b^T)                in place, after the base product (kf_linear, epilogue included) has written y
+ *   kf_lora_backward   adelta [n, r] = bf16(s deltaIn b)                 at offset 0 of the scratch (the reference's Adelta)
+ *                      delta [n, IC] = bf16(delta + s adelta a)          ALWAYS on top of what kf_linear_backward(..., gW = NULL) of the base left there
+ *                      gB [OC, r]    = bf16(gB + s deltaIn^T ax)         g = [gA (r IC) | gB (OC r)], one vector
+ *                      gA [r, IC]    = bf16(gA + s adelta^T inp)
+ * Sums in fp32 (MFMA accumulation), bf16 roundings to nearest even exactly where written.  The gradients ACCUMULATE into g as gW and gGama do (kf_adamw zeroes what it
+ * consumed); the reference writes them with beta = 0, the same on a zeroed buffer.  Deterministic: no atomics; the weight side cuts n into slabs whose fp32 partials a
+ * finish launch adds in slab order; results do not depend on the scratch's contents.  Launches: forward one; backward four (transposed copies of a and b, the row side,
+ * both gradients' slabs, the finish) -- csrc/kf_lora_plan.h.
+ * Served: r 16, 32 or 64; OC and IC multiples of 64 and >= 128; n a multiple of 64 and >= 64.  Refusals launch nothing: no context, another shape or a null pointer:
+ * KF_INVALID_ARGS; an operand not 16-byte aligned or the scratch not 256-byte aligned: KF_BLAS_UNALIGN.  scratch: kf_lora_backward_scratch_bytes(r, OC, IC, n) bytes
+ * (0 for a refused shape), sized by the caller. */
+size_t kf_lora_backward_scratch_bytes(int r, int OC, int IC, int n);
+int kf_lora_forward(kf_ctx* ctx, const kf_bf16* a, const kf_bf16* b, int r, int OC, int IC, const kf_bf16* x, kf_bf16* y, kf_bf16* ax, int n, float s);
+int kf_lora_backward(kf_ctx* ctx, const kf_bf16* a, const kf_bf16* b, int r, int OC, int IC, const kf_bf16* deltaIn, const kf_bf16* inp, const kf_bf16* ax, kf_bf16* delta,
+                     kf_bf16* g, int n, float s, void* scratch);
+
 /* LayerNorm / RMSNorm backward (LayerNormal::cuFlow, backward branch, T.cu:605-646: layernorm_backward -> layernorm_backward_kernel10, layernorm.cuh:311-503;
  * RMS: CU_rms_back_llmc, layernorm.cuh:863-1051).  mean == NULL selects RMSNorm.  dinp (the residual-path gradient on entry) becomes
  * bf16(dinp + dL/dinp); dweight (and dbias, LayerNorm with a bias) accumulate the sums over the rows: bf16(sum + old).  rstd (and mean) are the forward's

@@ -19,6 +19,7 @@
 #include "kf_gemv_plan.h"
 #include "kf_score_plan.h"
 #include "kf_gama_plan.h"
+#include "kf_lora_plan.h"
 #include "kf_gradnorm_plan.h"
 
 struct kf_ctx {
@@ -1121,6 +1122,31 @@ int kf_gama_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, cons
     r = kf::gama_backward_launch(c->stream, p, (const unsigned char*)w->data, fmt, w->qBias, OC, IC, deltaIn, inp, n, gGama, scale, (float*)scratch);
     RET(r);
 }
+// ---- low-rank adapters beside a frozen matrix (SLP::Forw / SLP::Back, LORA branch -> HIERARCH_LorAB::Forw / Back): kf_lora.hip; the launches: kf_lora_plan.h
+size_t kf_lora_backward_scratch_bytes(int r, int OC, int IC, int n) {
+    const kf::LoraPlan p = kf::lora_plan(r, OC, IC, n);
+    return p.status == KF_OK ? (size_t)p.scratch : 0;
+}
+int kf_lora_forward(kf_ctx* c, const kf_bf16* a, const kf_bf16* b, int r, int OC, int IC, const kf_bf16* x, kf_bf16* y, kf_bf16* ax, int n, float s) {
+    CHKCTX(c);
+    if (!a || !b || !x || !y || !ax) return fail(KF_INVALID_ARGS, "kf_lora_forward: null a / b / x / y / ax");
+    const kf::LoraPlan p = kf::lora_plan(r, OC, IC, n);
+    if (p.status != KF_OK)
+        return fail(KF_INVALID_ARGS, "kf_lora_forward: needs rank 16, 32 or 64, OC and IC multiples of 64 and >= 128, n a multiple of 64 and >= 64 (got rank %d, %d x %d, n %d)", r, OC, IC, n);
+    if (!al16(a) || !al16(b) || !al16(x) || !al16(y) || !al16(ax)) return fail(KF_BLAS_UNALIGN, "kf_lora_forward: tensors must be 16-byte aligned");
+    RET(kf::lora_forward_launch(c->stream, p, a, b, r, OC, IC, x, y, ax, n, s));
+}
+int kf_lora_backward(kf_ctx* c, const kf_bf16* a, const kf_bf16* b, int r, int OC, int IC, const kf_bf16* deltaIn, const kf_bf16* inp, const kf_bf16* ax, kf_bf16* delta, kf_bf16* g,
+                     int n, float s, void* scratch) {
+    CHKCTX(c);
+    if (!a || !b || !deltaIn || !inp || !ax || !delta || !g || !scratch) return fail(KF_INVALID_ARGS, "kf_lora_backward: null a / b / deltaIn / inp / ax / delta / g / scratch");
+    const kf::LoraPlan p = kf::lora_plan(r, OC, IC, n);
+    if (p.status != KF_OK)
+        return fail(KF_INVALID_ARGS, "kf_lora_backward: needs rank 16, 32 or 64, OC and IC multiples of 64 and >= 128, n a multiple of 64 and >= 64 (got rank %d, %d x %d, n %d)", r, OC, IC, n);
+    if (!al16(a) || !al16(b) || !al16(deltaIn) || !al16(inp) || !al16(ax) || !al16(delta) || !al16(g) || ((uintptr_t)scratch & 255))
+        return fail(KF_BLAS_UNALIGN, "kf_lora_backward: tensors must be 16-byte aligned, scratch 256-byte aligned");
+    RET(kf::lora_backward_launch(c->stream, p, a, b, r, OC, IC, deltaIn, inp, ax, delta, g, n, s, (unsigned char*)scratch));
+}
 size_t kf_attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return kf::attn_backward_scratch_bytes(T, n_head, n_seq); }
 int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,
                      kf_bf16* dk, kf_bf16* dv, long long ld_d, int T, int n_head, int n_kv, int hd, int n_seq, void* scratch) {
@@ -1760,6 +1786,12 @@ int kfdbg_gradnorm_plan(int n_tensors, const long long* n, kf::GradNormPlan* out
 int kfdbg_a8_tile_plan(const kf::A8Problem* P, kf::A8TilePlan* out) {
     if (!P || !out) return -1;
     *out = kf::a8_tile_plan(*P);
+    return 0;
+}
+// the plan kf::lora_plan makes for an adapter (no HIP call): tests/test_lora_cpu.py
+int kfdbg_lora_plan(int r, int OC, int IC, int n, kf::LoraPlan* out) {
+    if (!out) return -1;
+    *out = kf::lora_plan(r, OC, IC, n);
     return 0;
 }
 // the plan kf::score_plan makes for a scoring problem (no HIP call): tests/test_score_cpu.py

@@ -1,5 +1,5 @@
 // kf_train_common.hpp -- what the training-step sequencers of libkf_host.so share (koifish::GPT2Trainer, kf_train.cpp; koifish::Qwen3Trainer, kf_train_qwen3.cpp): the
-// table of trained tensors, its registration in both forms (shadow weights / "train_target": "gama"), SLP::Back for one matrix, the optimiser switch and the update loop
+// table of trained tensors, its registration in its three forms (shadow weights / "train_target": "gama" / a low-rank adapter beside a frozen matrix), SLP::Back for one matrix, the optimiser switch and the update loop
 // with its seed rule -- and the step around them: Update, Step, the head product + fused classifier that ends every Forward (HeadLoss), the head's backward that starts
 // every Backward (HeadBack).  A trainer adds its own activations, Ready, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
 // Gradient norms and clipping (SetGradClip) live here too: one kf_grad_norms call at the head of the update, the clip factors read on the device by kf_adamw_scaled.
@@ -20,6 +20,10 @@ struct TrainTensor {
     long long n = 0;
     bool decay = false, has_blob = false, requant = false;
     bool gama = false;  // p is the blob's [ZERO][STEP] slice (n = 2 nGroup): SetParamGama
+    bool lora = false;  // blob is the frozen base; p / g / m / v are ONE vector [a (rank ne1) | b (ne0 rank)] (n = rank (ne1 + ne0)): SetParamLora
+    int rank = 0;       // of the adapter
+    float s = 1.0f;     // the reference's sAB: multiplies both products of a direction
+    kf_bf16* ax = nullptr;  // [N, rank], written by the forward and read by the backward (the reference's Ax)
     kf_weight blob;  // what the forward multiplies (f8e5m2 / 4-bit PackedQ / the bf16 master itself for a bf16 head)
 };
 
@@ -42,6 +46,8 @@ struct TrainerCore {
     size_t sc_muon_bytes = 0;
     void* sc_gama = nullptr;  // kf_gama_backward's slab partials, sized for the largest gama tensor (SetGamaScratch)
     size_t sc_gama_bytes = 0;
+    void* sc_lora = nullptr;  // kf_lora_backward's scratch, sized for the largest adapted matrix (SetLoraScratch)
+    size_t sc_lora_bytes = 0;
     // gradient norms and clipping (SetGradClip): CLIP_REPORT / _TENSOR / _GLOBAL are kf_clip_mode's values.  The caller's scratch holds kf_grad_norms' table and
     // partials, then d_sumsq [n + 1] fp64, d_gnorm [n + 1] float, d_scale [n] float (each part rounded up to 256 bytes); n = params.size()
     enum { CLIP_OFF = 0, CLIP_REPORT = KF_CLIP_REPORT, CLIP_TENSOR = KF_CLIP_TENSOR, CLIP_GLOBAL = KF_CLIP_GLOBAL };
@@ -60,11 +66,12 @@ struct TrainerCore {
     virtual int Backward() = 0;
 
     // MUON_params_::isAdamW restated: a Muon tensor is one of a layer's weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape) and a
-    // [ne0, ne1] bf16 master; embeddings, biases, norms, matrices with ne0 < ne1 and gama-trained tensors stay on AdamW
+    // [ne0, ne1] bf16 master; embeddings, biases, norms, matrices with ne0 < ne1 and gama-trained tensors stay on AdamW.  An adapter is never a Muon tensor: its
+    // parameter is the vector [a | b], not a matrix kf_muon could orthogonalise
     bool IsMuon(size_t i) const {
         if (method != OPT_MUON || i >= wmat.size() || !wmat[i]) return false;
         const TrainTensor& e = params[i];
-        return !e.gama && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
+        return !e.gama && !e.lora && e.has_blob && e.blob.ne0 >= e.blob.ne1 && (long long)e.blob.ne0 * e.blob.ne1 == e.n;
     }
     int SetOptimizer(int method_, float lr_scale_, float mui_, float eps_muon_, int tp_decay_, void* scratch, size_t scratch_bytes) {
         if (method_ != OPT_ADAMW && method_ != OPT_MUON) return KF_INVALID_ARGS;
@@ -144,7 +151,7 @@ struct TrainerCore {
     int SetParam(int index, void* p, void* g, void* m, void* v, long long n, int decay, const kf_weight* blob, int requant) {
         if (index < 0 || index >= (int)params.size() || !p || !g || !m || !v || n < 8 || (n & 7)) return KF_INVALID_ARGS;
         TrainTensor& e = params[index];
-        e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false;
+        e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = n, e.decay = decay != 0, e.has_blob = blob != nullptr, e.requant = blob && requant, e.gama = false, e.lora = false;
         if (blob) e.blob = *blob;
         if (clip_mode != CLIP_OFF) clip_stale = true;
         return KF_OK;
@@ -158,7 +165,7 @@ struct TrainerCore {
         TrainTensor& e = params[index];
         e.blob = *blob;
         e.p = const_cast<kf_bf16*>(blob->gama) + blob->ne0 + blob->ne1, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = 2LL * blob->nGroup;
-        e.decay = false, e.has_blob = true, e.requant = false, e.gama = true;
+        e.decay = false, e.has_blob = true, e.requant = false, e.gama = true, e.lora = false;
         if (clip_mode != CLIP_OFF) clip_stale = true;
         return KF_OK;
     }
@@ -166,6 +173,25 @@ struct TrainerCore {
     int SetGamaScratch(void* scratch, size_t bytes) {
         if (!scratch || ((uintptr_t)scratch & 255)) return KF_INVALID_ARGS;
         sc_gama = scratch, sc_gama_bytes = bytes;
+        return KF_OK;
+    }
+    // a low-rank adapter beside one of a layer's weight matrices (SLP's LORA branch): blob the frozen base in any storage kf_linear / kf_linear_backward serve, never
+    // re-quantised; p / g / m / v one vector [a (rank x ne1) | b (ne0 x rank)] each, so the update, the seed rule, the norms and the clipping see ONE tensor; decayed
+    // like any other 2-D tensor (the reference registers a and b as ordinary gensors); AdamW whatever the optimiser switch says.  ax: [N, rank] bf16, this tensor's own.
+    int SetParamLora(int index, void* p, void* g, void* m, void* v, int rank_, float s_, void* ax_, const kf_weight* blob) {
+        if (index < 0 || index >= (int)params.size() || !wmat[index] || !p || !g || !m || !v || !ax_ || !blob || !std::isfinite(s_)) return KF_INVALID_ARGS;
+        if (kf_lora_backward_scratch_bytes(rank_, blob->ne0, blob->ne1, 64) == 0) return KF_INVALID_ARGS; /* the rank or the matrix is none the entries take */
+        TrainTensor& e = params[index];
+        e.blob = *blob;
+        e.p = (kf_bf16*)p, e.g = (kf_bf16*)g, e.m = m, e.v = v, e.n = (long long)rank_ * ((long long)blob->ne0 + blob->ne1);
+        e.decay = true, e.has_blob = true, e.requant = false, e.gama = false, e.lora = true, e.rank = rank_, e.s = s_, e.ax = (kf_bf16*)ax_;
+        if (clip_mode != CLIP_OFF) clip_stale = true;
+        return KF_OK;
+    }
+    // kf_lora_backward's scratch (device memory, 256-byte aligned, the caller's): at least kf_lora_backward_scratch_bytes of every adapter at the step's rows
+    int SetLoraScratch(void* scratch, size_t bytes) {
+        if (!scratch || ((uintptr_t)scratch & 255)) return KF_INVALID_ARGS;
+        sc_lora = scratch, sc_lora_bytes = bytes;
         return KF_OK;
     }
     // every tensor registered; every gama tensor a shape the entry takes, with scratch; no dequant arena beside a gama tensor; the clip table, if any, still the
@@ -184,13 +210,28 @@ struct TrainerCore {
                 any_gama = true;
             }
         if (any_gama && kf_dequant_arena_bytes(ctx) > 0) return KF_INVALID_ARGS; /* resident dequantised copies would go stale with the first update */
+        for (const TrainTensor& e : params)
+            if (e.lora) { /* an adapter's base never changes: a dequant arena beside it stays valid and is not refused */
+                const size_t b = kf_lora_backward_scratch_bytes(e.rank, e.blob.ne0, e.blob.ne1, N);
+                if (b == 0 || !sc_lora || sc_lora_bytes < b) return KF_INVALID_ARGS;
+            }
         return KF_OK;
+    }
+    // SLP::Forw for one matrix: the base product with its epilogue, then -- LORA branch -- the adapter's two products on the same y (ax kept)
+    int LinForw(TrainTensor& w, const kf_bf16* x, kf_bf16* y, const kf_bf16* res) {
+        KF_TRY(kf_linear(ctx, &w.blob, x, y, nullptr, N, 1.0f, 0.0f, res ? 1u : 0u, res));
+        if (!w.lora) return KF_OK;
+        return kf_lora_forward(ctx, w.p, w.p + (size_t)w.rank * w.blob.ne1, w.rank, w.blob.ne0, w.blob.ne1, x, y, w.ax, N, w.s);
     }
     // SLP::Back (NeuronFuse.cu:495-563): weight / bias gradients into the tensors' own buffers, delta (accumulate: on top of what it holds) to the layer below
     int LinBack(TrainTensor& w, const kf_bf16* dIn, const kf_bf16* inp, kf_bf16* delta, TrainTensor* bias, int accumulate = 0) {
         if (w.gama) { /* the gama branch of SLP::Back: delta and the bias gradient as ever, no gW; then the (zero, step) gradients from the same two operands */
             KF_TRY(kf_linear_backward(ctx, &w.blob, dIn, inp, delta, nullptr, bias ? bias->g : nullptr, N, accumulate, sc_lin));
             return kf_gama_backward(ctx, &w.blob, dIn, inp, w.g, N, 1.0f, sc_gama);
+        }
+        if (w.lora) { /* the LORA branch: the frozen base gives delta (and the bias gradient) and no gW; the adapter then adds its share of delta and its two gradients */
+            KF_TRY(kf_linear_backward(ctx, &w.blob, dIn, inp, delta, nullptr, bias ? bias->g : nullptr, N, accumulate, sc_lin));
+            return kf_lora_backward(ctx, w.p, w.p + (size_t)w.rank * w.blob.ne1, w.rank, w.blob.ne0, w.blob.ne1, dIn, inp, w.ax, delta, w.g, N, w.s, sc_lora);
         }
         return kf_linear_backward(ctx, &w.blob, dIn, inp, delta, w.g, bias ? bias->g : nullptr, N, accumulate, sc_lin);
     }

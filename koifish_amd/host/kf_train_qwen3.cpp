@@ -18,7 +18,8 @@
 //
 // Options: the optimiser switch of the GPT-2 trainer ("muon": a layer matrix with ne0 >= ne1 and a bf16 master through kf_muon -- q, k, v, gate, up at the 0.6B shape; o,
 // down, norms, embeddings and every gama tensor on AdamW); "train_target": "gama" for any of the seven matrices (a context that holds a dequant arena is refused as soon
-// as one is registered).  EOE layer-section branches are NOT offered on this trainer.
+// as one is registered); a low-rank adapter beside any of the seven (kfh_qwen3t_set_param_lora: the base frozen, [a | b] one AdamW tensor, a dequant arena accepted).
+// EOE layer-section branches are NOT offered on this trainer.
 #include <cstring>
 #include <string>
 
@@ -59,7 +60,7 @@ struct Qwen3Trainer : TrainerCore {
         if (!params[(size_t)NL * PER_LAYER].has_blob || (!tied && !params[(size_t)NL * PER_LAYER + 2].has_blob)) return KF_INVALID_ARGS;
         return KF_OK;
     }
-    int Lin(TrainTensor& w, const kf_bf16* x, kf_bf16* y, const kf_bf16* res) { return kf_linear(ctx, &w.blob, x, y, nullptr, N, 1.0f, 0.0f, res ? 1u : 0u, res); }
+    int Lin(TrainTensor& w, const kf_bf16* x, kf_bf16* y, const kf_bf16* res) { return LinForw(w, x, y, res); }  // an adapted matrix: + kf_lora_forward on the same y
     int Rms(const kf_bf16* x, TrainTensor& w, kf_bf16* y, float* rstd) { return kf_rmsnorm(ctx, x, w.p, y, N, dim, eps, rstd); }
     // kf_norm_backward ADDS into dweight: the per-tensor gradients are zero here (kf_adamw zeroes what it consumed)
     int RmsBack(kf_bf16* dxx, const kf_bf16* dout, const kf_bf16* inp, TrainTensor& w, const float* rstd) {
@@ -163,6 +164,21 @@ int kfh_qwen3t_set_param_gama(void* h, int index, void* g, void* m, void* v, con
     return rc;
 }
 int kfh_qwen3t_set_gama_scratch(void* h, void* scratch, size_t bytes) { return Core(h)->SetGamaScratch(scratch, bytes); }
+// a low-rank adapter beside one of a layer's seven matrices (TrainerCore::SetParamLora): p / g / m / v are [a (rank x IC) | b (OC x rank)] bf16 each, ax [B T, rank] bf16
+int kfh_qwen3t_set_param_lora(void* h, int index, void* p, void* g, void* m, void* v, int rank, float s, void* ax, const kf_weight* blob) {
+    koifish::g_q3t_err.clear();
+    const int rc = Core(h)->SetParamLora(index, p, g, m, v, rank, s, ax, blob);
+    if (rc != KF_OK)
+        koifish::g_q3t_err = "kfh_qwen3t_set_param_lora: index " + std::to_string(index) + " is no layer matrix, a null pointer, a rank other than 16 / 32 / 64, or a matrix whose sides "
+                             "are not multiples of 64 and >= 128";
+    return rc;
+}
+int kfh_qwen3t_set_lora_scratch(void* h, void* scratch, size_t bytes) {
+    koifish::g_q3t_err.clear();
+    const int rc = Core(h)->SetLoraScratch(scratch, bytes);
+    if (rc != KF_OK) koifish::g_q3t_err = "kfh_qwen3t_set_lora_scratch: the scratch is missing or not 256-byte aligned";
+    return rc;
+}
 // ptrs: x h1 r1 qraw kraw qkv rq rk att x2 h2 r2 gate up act
 int kfh_qwen3t_set_layer_acts(void* h, int layer, void* const* ptrs) {
     Qwen3Trainer* t = Q3(h);

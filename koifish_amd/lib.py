@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
+    "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes",
     "kf_evolve", "kf_loss_mean",
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
     "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
@@ -48,6 +49,12 @@ class Weight(C.Structure):
     """struct kf_weight (include/kf_abi.h)"""
     _fields_ = [("data", C.c_void_p), ("gama", C.c_void_p), ("type", C.c_int32), ("ne0", C.c_int32), ("ne1", C.c_int32), ("nGroup", C.c_int32),
                 ("lGroup", C.c_int32), ("qMin", C.c_int32), ("qMax", C.c_int32), ("qBias", C.c_int32), ("qzeros", C.c_void_p), ("qscales", C.c_void_p), ("quant", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class LoraPlan(C.Structure):
+    """struct kf::LoraPlan (csrc/kf_lora_plan.h), as kfdbg_lora_plan fills it"""
+    _fields_ = ([(f, C.c_int) for f in ("status", "tm", "rows_gx", "rows_block", "rows_lds", "tr_gx", "SA", "SB", "tilesA", "tilesB", "w_gx", "w_block", "w_lds", "fin_gx")]
+                + [(f, C.c_longlong) for f in ("off_adelta", "off_aT", "off_bT", "off_partA", "off_partB", "scratch")])
 
 
 class GradNormPlan(C.Structure):
@@ -133,6 +140,10 @@ def load():
         hip.kf_linear_backward_scratch_bytes.argtypes, hip.kf_linear_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_gama_backward.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
         hip.kf_gama_backward_scratch_bytes.argtypes, hip.kf_gama_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
+        hip.kf_lora_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+        hip.kf_lora_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_void_p]
+        hip.kf_lora_backward_scratch_bytes.argtypes, hip.kf_lora_backward_scratch_bytes.restype = [C.c_int] * 4, C.c_size_t
+        hip.kfdbg_lora_plan.argtypes = [C.c_int] * 4 + [C.POINTER(LoraPlan)]
         hip.kf_norm_backward.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p]
         hip.kf_norm_backward_scratch_bytes.argtypes, hip.kf_norm_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_rope_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]
@@ -282,6 +293,9 @@ def load():
         host.kfh_qwen3t_create.restype = C.c_void_p
         host.kfh_qwen3t_create.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_float, C.c_int]
         host.kfh_qwen3t_last_error.restype = C.c_char_p
+        # a low-rank adapter beside a frozen layer matrix: the Qwen3 trainer only
+        host.kfh_qwen3t_set_param_lora.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        host.kfh_qwen3t_set_lora_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         # EOE: layer-section branches, the evolve step over the swarm, the ensemble evaluation
         host.kfh_gpt2_set_branches.argtypes = [C.c_void_p, C.c_int]
         host.kfh_gpt2_n_branches.argtypes = [C.c_void_p]

@@ -269,6 +269,34 @@ class Context:
         L.check(self.hip.kf_gama_backward(self.h, C.byref(d), _ptr(dIn), _ptr(inp), _ptr(g), n, scale, C.c_void_p((ws.data_ptr() + 255) & ~255)), "kf_gama_backward")
         return g
 
+    def lora_forward(self, a, b, x, y, s=1.0):
+        """kf_lora_forward beside a frozen matrix: a [r, IC], b [OC, r], x [n, IC] bf16; y [n, OC] bf16 already holds the base product and becomes
+        bf16(y + s ax b^T) in place, with ax = bf16(s x a^T) [n, r], which is returned for the backward.  s multiplies BOTH products (the reference's sAB): the adapter's
+        effective weight is s^2 b a."""
+        (r, IC), (OC, n) = a.shape, (b.shape[0], x.shape[0])
+        if b.shape != (OC, r) or x.shape != (n, IC) or y.shape != (n, OC):
+            raise L.KFError("lora_forward: a %s, b %s, x %s, y %s" % (tuple(a.shape), tuple(b.shape), tuple(x.shape), tuple(y.shape)))
+        ax = torch.empty(n, r, dtype=torch.bfloat16, device=self.device)
+        L.check(self.hip.kf_lora_forward(self.h, _ptr(a), _ptr(b), r, OC, IC, _ptr(x), _ptr(y), _ptr(ax), n, s), "kf_lora_forward")
+        return ax
+
+    def lora_backward(self, a, b, dIn, inp, ax, delta, g, s=1.0):
+        """kf_lora_backward: delta [n, IC] bf16 (what the base's kf_linear_backward left) += s adelta a with adelta = bf16(s dIn b); g = [gA (r IC) | gB (OC r)] bf16 +=
+        s adelta^T inp | s dIn^T ax.  Owns the scratch (kernels never allocate), sized with kf_lora_backward_scratch_bytes; returns adelta [n, r], a view of its head."""
+        (r, IC), (OC, n) = a.shape, (b.shape[0], dIn.shape[0])
+        need = self.hip.kf_lora_backward_scratch_bytes(r, OC, IC, n)
+        if b.shape != (OC, r) or dIn.shape != (n, OC) or inp.shape != (n, IC) or ax.shape != (n, r) or delta.shape != (n, IC) or g.numel() != r * (IC + OC) or not need:
+            raise L.KFError("lora_backward: a %s, b %s, dIn %s, inp %s, ax %s, delta %s, g %d" % (tuple(a.shape), tuple(b.shape), tuple(dIn.shape), tuple(inp.shape),
+                                                                                                 tuple(ax.shape), tuple(delta.shape), g.numel()))
+        ws = getattr(self, "_lora_ws", None)
+        if ws is None or ws.numel() < need + 256:
+            self.sync()   # earlier launches may still read the old buffer
+            ws = self._lora_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        off = ((ws.data_ptr() + 255) & ~255) - ws.data_ptr()
+        L.check(self.hip.kf_lora_backward(self.h, _ptr(a), _ptr(b), r, OC, IC, _ptr(dIn), _ptr(inp), _ptr(ax), _ptr(delta), _ptr(g), n, s, C.c_void_p(ws.data_ptr() + off)),
+                "kf_lora_backward")
+        return ws[off:off + n * r * 2].view(torch.bfloat16).view(n, r)
+
     def evolve(self, x, head, algorithm, alpha=0.9, social=2.0, t_crossover=0.6, seed=0):
         """kf_evolve (Fuyou::Exploitation): the follower matrix x [ne0, ne1] bf16 moves towards head [ne0, ne1] bf16, in place; algorithm "pso" | "pso_ga" | "mix"
         (Fuyou_params::Algo2Name) or a kf_evo_algorithm value; the defaults are Fuyou_params' (alpha 0.9, social 2, T_crossover 0.6).  Returns x."""

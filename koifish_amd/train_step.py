@@ -11,6 +11,10 @@ train_target="gama" is the reference's other way to train a quantised layer ("tr
 as a PackedQ group type keeps its packed integers frozen and trains each group's (zero, step) pair in place inside the blob -- no bf16 master, no [OC, IC] gradient, no
 moments of that size, no re-quantisation: per 128 weights two bf16 parameters, two gradients, four moments (kf_gama_backward + kf_adamw on the blob's gama slice).
 
+train_target="lora" (Qwen3Step only) is the third way, the LORA branch of SLP::Forw / SLP::Back: the quantised matrix stays frozen as it is and a low-rank pair a [r, IN],
+b [OUT, r] trains beside it (kf_lora_forward after the base product, kf_lora_backward after kf_linear_backward(gW = NULL)): no master, no [OUT, IN] gradient or moments,
+no weight-gradient GEMM and no re-quantisation.  [a | b] is ONE trained vector per matrix.
+
 layers_in_branch is the reference's EOE, "Evolutionary Optimization of Experts" (Fuyou_params::nLayerInBranch; RLSchedule::InitBranch, Fuyou::UpdateFollower,
 Fish::ForwardOnRLS): the NL layers are cut into NL / layers_in_branch sections; a section plus the shared embedding, final norm and head is a shallow model of its own
 (a "Fuyou").  set_branch(b) picks the one that forward / backward / update / step run; evolve(head) pulls the weight matrices of every other branch towards the head
@@ -49,13 +53,14 @@ class _TrainStep:
     _layer_prefix = None   # what the name of a layer's tensor starts with ("h3.fc.w", "l3.gate.w")
     _layer_noun = None     # what set_optimizer's refusal calls a layer matrix
     _reason_codes = None   # the return codes whose reason is in kfh_<_family>_last_error; None: every code
+    _targets = ("weights", "gama")   # the train_target values the family offers
     optimizer = "adamw"
     _clip = None           # (gclip, mode) of set_grad_clip, None: off
 
     def _begin(self, ctx, train_target, seed):
         """checks train_target before anything touches ctx; returns the device generator of the initial draws"""
-        if train_target not in ("weights", "gama"):
-            raise ValueError("train_target %r: 'weights' or 'gama'" % (train_target,))
+        if train_target not in self._targets:
+            raise ValueError("train_target %r: one of %s" % (train_target, ", ".join(repr(t_) for t_ in self._targets)))
         self.train_target, self.ctx = train_target, ctx
         self.params = []   # every trained tensor: dict(name, p (bf16 master), g (bf16 gradient), m, v (bf16 moments), wd (bool), blob (DevWeight or None), type)
         g = torch.Generator(device=ctx.device)
@@ -99,6 +104,15 @@ class _TrainStep:
         self.params.append(e)
         return e
 
+    def _reg_lora(self, name, W, type_, a, b):
+        """one of a layer's weight matrices with an adapter: the blob is quantised once from W, which is then dropped; the trained tensor is the vector [a | b]"""
+        blob = self.ctx.quantize(W.contiguous(), type_)
+        p = torch.cat([a.reshape(-1), b.reshape(-1)]).contiguous()
+        e = dict(name=name, p=p, g=torch.zeros_like(p), m=torch.zeros_like(p), v=torch.zeros_like(p), wd=True, blob=blob, type=type_, lora=True, rank=a.shape[0],
+                 s=self.lora_s, ax=torch.zeros(self.N, a.shape[0], dtype=torch.bfloat16, device=self.ctx.device))
+        self.params.append(e)
+        return e
+
     def _reg_matrix(self, name, W, type_):
         """one of a layer's weight matrices: its (zero, step) pairs under train_target="gama" when its storage is a PackedQ group type, its weights (decayed) otherwise"""
         if self.train_target == "gama" and type_ in GAMA_TYPES:
@@ -128,8 +142,17 @@ class _TrainStep:
                                 % (bad["name"], bad["blob"].ne0, bad["blob"].ne1, N))
             self._sc_gama = torch.empty(max(need) + 256, dtype=torch.uint8, device=self.ctx.device)
             self._call("set_gama_scratch", _align256(self._sc_gama.data_ptr()), max(need))
+        lora = [e for e in self.params if e.get("lora")]
+        if lora:
+            need = max(hip.kf_lora_backward_scratch_bytes(e["rank"], e["blob"].ne0, e["blob"].ne1, N) for e in lora)
+            self._sc_lora = torch.empty(need + 256, dtype=torch.uint8, device=self.ctx.device)
+            self._call("set_lora_scratch", _align256(self._sc_lora.data_ptr()), need, check=self._check_host)
         for i, e in enumerate(self.params):
             d = e["blob"].desc() if e["blob"] is not None else None
+            if e.get("lora"):
+                self._call("set_param_lora", i, e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), e["rank"], e["s"], e["ax"].data_ptr(), C.byref(d),
+                           check=self._check_host)
+                continue
             if e.get("gama"):
                 self._call("set_param_gama", i, e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), C.byref(d), check=self._check_host)
                 continue
@@ -144,12 +167,13 @@ class _TrainStep:
         """"adamw" (the default: every tensor) or "muon" (OPT_Muon, the reference's default): a layer's weight matrices with ne0 >= ne1 and a bf16 master (GPT-2: qkv, proj,
         fc; Qwen3 at its shapes: q, k, v, gate, up) take SGD-momentum + five Newton-Schulz steps (kf_muon: lr x lr_scale, weight decay by tp_decay as Pipe.cpp:23-37, mG =
         the tensor's m buffer); the other matrices (proj2; o, down), the embeddings, the head, biases and norms keep kf_adamw -- and so does every gama-trained tensor
-        (train_target="gama"): its parameter is a [2 nGroup] slice, never a matrix for kf_muon.  Owns the scratch, sized for the largest Muon tensor."""
+        (train_target="gama"): its parameter is a [2 nGroup] slice, never a matrix for kf_muon -- and every adapter (train_target="lora"): its parameter is the vector
+        [a | b].  Owns the scratch, sized for the largest Muon tensor."""
         if method not in ("adamw", "muon"):
             raise ValueError("optimizer %r: 'adamw' or 'muon'" % (method,))
         sp, nb = None, 0
         if method == "muon":
-            shapes = [tuple(e["p"].shape) for e in self.params if e["blob"] is not None and not e.get("gama") and e["name"].startswith(self._layer_prefix)
+            shapes = [tuple(e["p"].shape) for e in self.params if e["blob"] is not None and not e.get("gama") and not e.get("lora") and e["name"].startswith(self._layer_prefix)
                       and e["p"].dim() == 2 and e["p"].shape[0] >= e["p"].shape[1]]
             nb = max([self.ctx.hip.kf_muon_scratch_bytes(a, b) for a, b in shapes], default=256)   # no Muon tensor at all (every matrix gama-trained): a token scratch
             if nb == 0:
@@ -350,18 +374,62 @@ class Qwen3Step(_TrainStep):
     as_model(max_seq) hands out a Qwen3 decoder built ON these blobs and norm tensors (no copy): score, perplexity, generate, save_kun and the engines then work on the
     trained weights; every update() calls weights_changed() on each model still alive.
 
+    train_target="lora": every matrix named in lora_targets is quantised once and frozen, and a rank-r pair trains beside it (the LORA branch of SLP::Forw / SLP::Back):
+    lora_state() hands out the trained pairs, merged_masters() the masters of an equivalent plain model.  The decode path applies no adapters: as_model() refuses.
+
     Not offered on this trainer: EOE layer-section branches (GPT2Step's layers_in_branch)."""
 
+    _targets = ("weights", "gama", "lora")
     _family, _acts_entry, _layer_prefix, _layer_noun = "qwen3t", "set_layer_acts", "l", "layer"
     _act_keys = ("x", "h1", "r1", "qraw", "kraw", "qkv", "rq", "rk", "att", "x2", "h2", "r2", "gate", "up", "act")
 
-    def __init__(self, ctx, cfg, B, T, types=None, tied=True, seed=0, w_std=0.02, masters=None, train_target="weights"):
+    @staticmethod
+    def _mat_shapes(cfg):
+        dim, H, KV, hd, ffn = (cfg[k] for k in ("dim", "n_head", "n_kv", "head_dim", "ffn"))
+        return dict(q=(H * hd, dim), k=(KV * hd, dim), v=(KV * hd, dim), o=(dim, H * hd), gate=(ffn, dim), up=(ffn, dim), down=(dim, ffn))
+
+    @classmethod
+    def _check_lora_args(cls, cfg, B, T, lora_rank, lora_s, lora_targets, adapters):
+        """every argument error of train_target="lora", before anything touches a context"""
+        if lora_rank not in (16, 32, 64):
+            raise ValueError("lora_rank %r: 16, 32 or 64" % (lora_rank,))
+        if 2 * lora_rank >= cfg["dim"]:
+            raise ValueError("lora_rank %d: 2 x rank must stay below dim %d" % (lora_rank, cfg["dim"]))   # the reference's assertion (SparseNeuron.cpp)
+        if not (isinstance(lora_s, (int, float)) and lora_s == lora_s and abs(lora_s) != float("inf")):
+            raise ValueError("lora_s %r: a finite number" % (lora_s,))
+        targets = tuple(lora_targets)
+        bad = [k for k in targets if k not in Q3_MATS]
+        if bad or not targets or len(set(targets)) != len(targets):
+            raise ValueError("lora_targets %r: distinct names out of %s" % (lora_targets, Q3_MATS))
+        shapes, sb = cls._mat_shapes(cfg), L.load()[0].kf_lora_backward_scratch_bytes
+        for k in targets:
+            if not sb(lora_rank, shapes[k][0], shapes[k][1], B * T):
+                raise ValueError("train_target='lora': kf_lora_backward does not take %s [%d, %d] at %d rows (out- and in-features multiples of 64 and >= 128, rows a "
+                                 "multiple of 64)" % (k, shapes[k][0], shapes[k][1], B * T))
+        for name, ab in (adapters or {}).items():
+            l, _, k = name[1:].partition(".")
+            if not (name[:1] == "l" and l.isdigit() and int(l) < cfg["n_layer"] and k.endswith(".w") and k[:-2] in targets):
+                raise ValueError("adapters: %r is no adapted matrix (names are l<layer>.<target>.w)" % (name,))
+            OC, IC = shapes[k[:-2]]
+            if len(ab) != 2 or tuple(ab[0].shape) != (lora_rank, IC) or tuple(ab[1].shape) != (OC, lora_rank) or ab[0].dtype != torch.bfloat16 or ab[1].dtype != torch.bfloat16:
+                raise ValueError("adapters[%r]: (a [%d, %d], b [%d, %d]) bf16" % (name, lora_rank, IC, OC, lora_rank))
+        return targets
+
+    def __init__(self, ctx, cfg, B, T, types=None, tied=True, seed=0, w_std=0.02, masters=None, train_target="weights", lora_rank=16, lora_s=1.0, lora_targets=Q3_MATS,
+                 adapters=None):
         """cfg: the dict Qwen3 takes (dim, n_layer, n_head, n_kv, head_dim, ffn, vocab, theta, rms_eps).  types: storage per matrix name of Q3_MATS (default: 4-bit for
         all seven); the embedding / head are bf16.  The vocabulary is padded to a multiple of 64 rows (kf_linear_backward); the padded rows stay zero.
         masters: optional dict of host-provided bf16 torch tensors: 'wte' [V or Vp, dim], 'nf' [dim], 'head' [V or Vp, dim] (untied), 'layers': list of dicts
         {q .. down: W [out, in], n1, n2: [dim], qn, kn: [head_dim]}.  Otherwise N(0, w_std) draws on the device and unit norms.
         train_target: "weights" or "gama" (every layer matrix stored as a PackedQ group type trains its (zero, step) pairs in place, as GPT2Step); a context that holds a
-        dequant arena is refused."""
+        dequant arena is refused; or "lora": every matrix named in lora_targets is quantised once from its master, which is then dropped, and gets an adapter a [lora_rank,
+        in] ~ N(0, w_std), b [out, lora_rank] = 0 (the reference's isBZero), or the pair adapters[name] = (a, b) of bf16 host tensors (name "l<layer>.<target>.w").  lora_s is
+        the reference's sAB: it multiplies BOTH products of a direction, the adapter's effective weight is lora_s^2 b a.  [a | b] is one entry of self.params
+        (e["lora"] = True, decayed like any 2-D tensor, AdamW under every optimiser switch); everything else -- the matrices not named, norms, embedding, head -- trains as
+        under "weights".  Raised before anything touches ctx: a rank outside {16, 32, 64} or with 2 rank >= dim (the reference's assertion), an unknown target, a matrix
+        or row count kf_lora_backward does not take, a badly shaped adapter.  A dequant arena is accepted: the base never changes."""
+        self._lora_targets = self._check_lora_args(cfg, B, T, lora_rank, lora_s, lora_targets, adapters) if train_target == "lora" else ()
+        self.lora_rank, self.lora_s = int(lora_rank), float(lora_s)
         g = self._begin(ctx, train_target, seed)
         self.tied, self.cfg, self.B, self.T, self.N = bool(tied), dict(cfg), B, T, B * T
         dim, NL, H, KV, hd, ffn, V = (cfg[k] for k in ("dim", "n_layer", "n_head", "n_kv", "head_dim", "ffn", "vocab"))
@@ -374,7 +442,7 @@ class Qwen3Step(_TrainStep):
         z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
         rnd = lambda *s: (torch.randn(*s, device=dev, generator=g) * w_std).to(bf)
         ones = lambda n: torch.ones(n, device=dev, dtype=bf)
-        self.shapes = dict(q=(Cq, dim), k=(Ck, dim), v=(Ck, dim), o=(dim, Cq), gate=(ffn, dim), up=(ffn, dim), down=(dim, ffn))
+        self.shapes = self._mat_shapes(cfg)
         self.layers, self._models = [], []
         self._check_arena()
 
@@ -386,7 +454,14 @@ class Qwen3Step(_TrainStep):
             ly = {}
             for k in Q3_MATS:
                 Wm = ml[k].to(dev) if ml else rnd(*self.shapes[k])
-                ly[k] = self._reg_matrix("l%d.%s.w" % (l, k), Wm, self.types[k])
+                name = "l%d.%s.w" % (l, k)
+                if k in self._lora_targets:
+                    ab = adapters.get(name) if adapters else None
+                    a_ = ab[0].to(dev) if ab else rnd(self.lora_rank, self.shapes[k][1])
+                    b_ = ab[1].to(dev) if ab else z(self.shapes[k][0], self.lora_rank)
+                    ly[k] = self._reg_lora(name, Wm, self.types[k], a_, b_)
+                else:
+                    ly[k] = self._reg_matrix(name, Wm, self.types[k])
             for k in Q3_NORMS:
                 n_ = hd if k in ("qn", "kn") else dim
                 ly[k] = self._reg("l%d.%s" % (l, k), ml[k].to(dev) if ml else ones(n_), False)
@@ -422,6 +497,8 @@ class Qwen3Step(_TrainStep):
         The step keeps a weak reference and calls weights_changed() on it after every update; the model must not outlive this object's buffers."""
         import weakref
         from .runtime import DevWeight, Qwen3
+        if self.train_target == "lora":
+            raise L.KFError("as_model under train_target='lora': the decode path does not apply adapters -- build a plain model from merged_masters()")
         dim, V = self.cfg["dim"], self.V
         m = Qwen3(dict(self.cfg, max_seq=int(max_seq), rms_eps=self.eps, qk_eps=self.eps, theta=self.theta, tied=self.tied), device=self.ctx.device.index or 0)
         rows = lambda e: DevWeight(L.BF16, V, dim, e["blob"].blob[:V * dim * 2])   # the first V rows of the [Vp, dim] bf16 blob, the same memory
@@ -439,6 +516,29 @@ class Qwen3Step(_TrainStep):
         m._trainer = self   # the buffers live as long as the model does
         self._models.append(weakref.ref(m))
         return m
+
+    def _ab(self, e):
+        r, OC, IC = e["rank"], e["blob"].ne0, e["blob"].ne1
+        return e["p"][:r * IC].view(r, IC), e["p"][r * IC:].view(OC, r)
+
+    def lora_state(self):
+        """{name: (a [r, in], b [out, r])} of every adapted matrix: views of the trained vectors (what adapters= takes back)"""
+        return {e["name"]: self._ab(e) for e in self.params if e.get("lora")}
+
+    def merged_masters(self):
+        """a dict in the masters= layout (host bf16 tensors): every adapted matrix as bf16(dequant(W) + lora_s^2 b a), everything else as it stands -- what a plain bf16 or
+        re-quantised model of the trained weights is built from.  Export, not the step: plain torch."""
+        def mat(e):
+            if not e.get("lora"):
+                return e["p"].detach().cpu().clone()
+            a, b = self._ab(e)
+            W = self.ctx.dequant(e["blob"]).float() + (e["s"] * e["s"]) * (b.float() @ a.float())
+            return W.to(torch.bfloat16).cpu()
+        out = dict(wte=self.wte["p"].detach().cpu().clone(), nf=self.nf["p"].detach().cpu().clone(),
+                   layers=[{k: mat(ly[k]) for k in Q3_MATS + Q3_NORMS} for ly in self.layers])
+        if not self.tied:
+            out["head"] = self.head["p"].detach().cpu().clone()
+        return out
 
     def _weights_changed(self):
         live = []
