@@ -409,6 +409,26 @@ int kf_lora_forward(kf_ctx* ctx, const kf_bf16* a, const kf_bf16* b, int r, int 
 int kf_lora_backward(kf_ctx* ctx, const kf_bf16* a, const kf_bf16* b, int r, int OC, int IC, const kf_bf16* deltaIn, const kf_bf16* inp, const kf_bf16* ax, kf_bf16* delta,
                      kf_bf16* g, int n, float s, void* scratch);
 
+/* The same pair applied at inference: the reference runs its LORA branch inside SLP::Forw on every forward (NeuronFuse.cu:286-302), decode, prompt and scoring alike.
+ * Per row the arithmetic is kf_lora_forward's, unchanged:   ax [r] = bf16(s x a^T),   y [OC] = bf16(y + s ax b^T)   in place, after the base product (kf_linear,
+ * epilogue included) has written y.  Any n >= 1; the form follows from n alone (csrc/kf_lora_plan.h, kf::lora_apply_plan):
+ *   n >= 2   the tile form: kf_lora_forward's kernel with a row bound.  Rows >= n of the last 32-row tile load as zero and store nothing (neither y nor ax): every row
+ *            < n has the bits kf_lora_forward gives it on the input zero-padded to a multiple of 64 rows.  n_w must be 1.  ax [n, r] is written when given; NULL: not kept.
+ *   n == 1   the vector form: n_w <= 3 adapters that share the input row x (q | k | v, gate | up) in ONE launch; h_a / h_b / h_OC / h_y are HOST arrays of n_w entries
+ *            (device pointers a [r, IC], b [OC_i, r], y_i [OC_i]; the y_i are separate -- a V row lies inside the KV cache); r, IC, x and s are shared.  ax is ignored.
+ *            No workgroup waits for another: each recomputes the r dot products and owns 64 output rows of one adapter.  The order of every sum is FIXED:
+ *              ax_j   lane l (of 64) adds the products of the 8-element chunks l, l + 64, l + 128, ... of the contraction to one fp32 accumulator, chunks ascending,
+ *                     k ascending inside a chunk (fma; the product of two bf16 is exact in fp32, so fma and multiply-add agree); a lane without a chunk holds 0.  The 64
+ *                     lane sums p_l meet in a butterfly, six steps m = 32, 16, 8, 4, 2, 1, each p_l <- p_l + p_(l xor m) on all lanes at once.  ax_j = bf16(s p_0).
+ *              y_m    one fp32 chain over j = 0 .. r - 1 ascending of ax_j b [m, j] (fma), then bf16(y_m + s sum): the multiply by s and the addition round to fp32 each.
+ *            tests/lora_apply_restate.py restates this in numpy, bit for bit.  The two forms sum in different orders: equal on exact operands, within rounding otherwise.
+ * Deterministic, no atomics, no scratch.  Served: r 16, 32 or 64; OC_i and IC multiples of 64 and >= 128; n >= 1; 1 <= n_w <= 3, n_w > 1 only with n == 1 --
+ * kf_lora_apply_status(r, OC, IC, n, n_w) answers KF_OK or the refusal for ONE adapter of such a group without a device (a pure host function).  Refusals launch nothing:
+ * no context, another shape, a null pointer (ax excepted): KF_INVALID_ARGS; a, b, x, y or ax not 16-byte aligned: KF_BLAS_UNALIGN. */
+int kf_lora_apply_status(int r, int OC, int IC, int n, int n_w);
+int kf_lora_apply(kf_ctx* ctx, int n_w, const kf_bf16* const* h_a, const kf_bf16* const* h_b, int r, const int* h_OC, int IC, const kf_bf16* x, kf_bf16* const* h_y,
+                  kf_bf16* ax_or_null, int n, float s);
+
 /* LayerNorm / RMSNorm backward (LayerNormal::cuFlow, backward branch, T.cu:605-646: layernorm_backward -> layernorm_backward_kernel10, layernorm.cuh:311-503;
  * RMS: CU_rms_back_llmc, layernorm.cuh:863-1051).  mean == NULL selects RMSNorm.  dinp (the residual-path gradient on entry) becomes
  * bf16(dinp + dL/dinp); dweight (and dbias, LayerNorm with a bias) accumulate the sums over the rows: bf16(sum + old).  rstd (and mean) are the forward's

@@ -1147,6 +1147,24 @@ int kf_lora_backward(kf_ctx* c, const kf_bf16* a, const kf_bf16* b, int r, int O
         return fail(KF_BLAS_UNALIGN, "kf_lora_backward: tensors must be 16-byte aligned, scratch 256-byte aligned");
     RET(kf::lora_backward_launch(c->stream, p, a, b, r, OC, IC, deltaIn, inp, ax, delta, g, n, s, (unsigned char*)scratch));
 }
+// ---- the same pair at inference (kf_lora_apply.hip): the form and the geometry are kf::lora_apply_plan's
+int kf_lora_apply_status(int r, int OC, int IC, int n, int n_w) { return kf::lora_apply_plan(r, OC, IC, n, n_w).status; }
+int kf_lora_apply(kf_ctx* c, int n_w, const kf_bf16* const* h_a, const kf_bf16* const* h_b, int r, const int* h_OC, int IC, const kf_bf16* x, kf_bf16* const* h_y, kf_bf16* ax,
+                  int n, float s) {
+    CHKCTX(c);
+    if (!h_a || !h_b || !h_OC || !h_y || !x || n_w < 1 || n_w > kf::LORA_APPLY_MAX) return fail(KF_INVALID_ARGS, "kf_lora_apply: null h_a / h_b / h_OC / h_y / x, or n_w %d outside 1 .. 3", n_w);
+    kf::LoraApplyPlan p[kf::LORA_APPLY_MAX];
+    for (int i = 0; i < n_w; i++) {
+        if (!h_a[i] || !h_b[i] || !h_y[i]) return fail(KF_INVALID_ARGS, "kf_lora_apply: null a / b / y of adapter %d", i);
+        p[i] = kf::lora_apply_plan(r, h_OC[i], IC, n, n_w);
+        if (p[i].status != KF_OK)
+            return fail(KF_INVALID_ARGS, "kf_lora_apply: needs rank 16, 32 or 64, OC and IC multiples of 64 and >= 128, n >= 1, and n == 1 for more than one adapter (got rank %d, %d x %d, n %d, %d adapters)",
+                        r, h_OC[i], IC, n, n_w);
+        if (!al16(h_a[i]) || !al16(h_b[i]) || !al16(h_y[i])) return fail(KF_BLAS_UNALIGN, "kf_lora_apply: tensors must be 16-byte aligned");
+    }
+    if (!al16(x) || !al16(ax)) return fail(KF_BLAS_UNALIGN, "kf_lora_apply: tensors must be 16-byte aligned");
+    RET(kf::lora_apply_launch(c->stream, p, n_w, h_a, h_b, r, h_OC, IC, x, h_y, ax, n, s));
+}
 size_t kf_attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return kf::attn_backward_scratch_bytes(T, n_head, n_seq); }
 int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,
                      kf_bf16* dk, kf_bf16* dv, long long ld_d, int T, int n_head, int n_kv, int hd, int n_seq, void* scratch) {

@@ -77,7 +77,40 @@ inline LoraPlan lora_plan(int r, int OC, int IC, int n) {
     return p;
 }
 
-// ---- the launchers (kf_lora.hip): execute a plan, nothing else; KF_OK or KF_HIP_CHECK
+// ---- kf_lora_apply (inference: kf_lora_apply.hip): kf::lora_apply_plan, one pure host function, picks the form from n and returns ONE adapter's share of the launch
+//   * tile form, n >= 2: the rows kernel above with a row bound -- cdiv(n, LORA_TM) workgroups, rows >= n of the last tile load as zero and store nothing.
+//   * vector form, n == 1: up to LORA_APPLY_MAX adapters that share the input row in one launch.  A workgroup of LORA_VEC_WAVES waves owns LORA_VEC_ROWS output rows of
+//     one adapter (OC / LORA_VEC_ROWS workgroups per adapter, laid side by side in the grid); every workgroup recomputes the r dot products itself, so no workgroup waits
+//     for another.  Wave w takes the ranks w, w + 16, ...; r bf16 in LDS; then one lane of wave 0 per output row.
+constexpr int LORA_APPLY_MAX = 3;  /* adapters per vector-form launch: q | k | v */
+constexpr int LORA_VEC_WAVES = 16; /* 1024 threads: at most r / 16 ranks per wave, so that a wave's loads of a are few and the CU hides their latency with waves */
+constexpr int LORA_VEC_ROWS = 64;  /* output rows per vector-form workgroup: a lane of wave 0 each */
+enum { LORA_FORM_TILE = 0, LORA_FORM_VEC = 1 };
+
+struct LoraApplyPlan {
+    int status;         /* KF_OK, or KF_INVALID_ARGS for what the entry refuses */
+    int form;           /* LORA_FORM_TILE (n >= 2) or LORA_FORM_VEC (n == 1) */
+    int gx, block, lds; /* this adapter's workgroups (the vector form's grid is the sum over the launch's adapters), threads, dynamic LDS bytes */
+};
+
+inline LoraApplyPlan lora_apply_plan(int r, int OC, int IC, int n, int n_w) {
+    LoraApplyPlan p = {};
+    const bool shape = (r == 16 || r == 32 || r == 64) && OC >= 128 && OC % 64 == 0 && IC >= 128 && IC % 64 == 0;
+    if (!shape || n < 1 || n_w < 1 || n_w > LORA_APPLY_MAX || (n_w > 1 && n != 1)) {
+        p.status = KF_INVALID_ARGS;
+        return p;
+    }
+    if (n == 1)
+        p.form = LORA_FORM_VEC, p.gx = OC / LORA_VEC_ROWS, p.block = 64 * LORA_VEC_WAVES, p.lds = 0;
+    else
+        p.form = LORA_FORM_TILE, p.gx = (int)cdiv(n, LORA_TM), p.block = 64 * LORA_ROW_WAVES, p.lds = lora_rows_lds(r);
+    return p;
+}
+
+// ---- the launchers (kf_lora.hip, kf_lora_apply.hip): execute a plan, nothing else; KF_OK or KF_HIP_CHECK
+// p[i] is adapter i's plan (all of one form; the tile form has n_w == 1); a / b / OC / y per adapter, r, IC, x, n and s shared; ax (tile form only) may be NULL
+int lora_apply_launch(hipStream_t st, const LoraApplyPlan* p, int n_w, const uint16_t* const* a, const uint16_t* const* b, int r, const int* OC, int IC, const uint16_t* x,
+                      uint16_t* const* y, uint16_t* ax, int n, float s);
 int lora_forward_launch(hipStream_t st, const LoraPlan& p, const uint16_t* a, const uint16_t* b, int r, int OC, int IC, const uint16_t* x, uint16_t* y, uint16_t* ax, int n, float s);
 int lora_backward_launch(hipStream_t st, const LoraPlan& p, const uint16_t* a, const uint16_t* b, int r, int OC, int IC, const uint16_t* deltaIn, const uint16_t* inp,
                          const uint16_t* ax, uint16_t* delta, uint16_t* g, int n, float s, unsigned char* scratch);

@@ -125,18 +125,20 @@ hGTensor SelfAttention::cuInfer(hGTensor inpL, int) {
     f->gBUFF.residual = inpL;
     const int32_t* d_pos = f->graph_mode ? f->d_state + 1 : nullptr;
     const int bound = f->graph_mode ? f->pos_bound() : pos;
-    if (f->act_int8) {  // int8 activations: [norm + quantise] -> Q, K, V -> [q/k-norm + RoPE + attention] -> [quantise] -> proj_cat + residual; 7 launches
+    if (f->per_layer()) {  // int8 activations: [norm + quantise] -> Q, K, V -> [q/k-norm + RoPE + attention] -> [quantise] -> proj_cat + residual; 7 launches
+                           // adapters: norm -> Q, K, V -> their adapters (one launch, on the raw rows) -> [q/k-norm + RoPE + attention] -> proj_cat + residual -> its adapter; 8 launches
         if (f->graph_mode) return nullptr;  // cache rows are resolved on the host
+        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
         SLP* qkv[3] = {&Q, &K, &V};
         floatX* ys[3] = {ToX(Q.out), ToX(f->gBUFF.kraw), val_cache + (size_t)pos * kv_dim};
-        if (f->A8Group(ToX(inpL), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 3, qkv, ys, nullptr) != KF_OK) return nullptr;
+        if ((f->*group)(ToX(inpL), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 3, qkv, ys, nullptr) != KF_OK) return nullptr;
         if (kf_attn_block(c, ToX(Q.out), ToX(f->gBUFF.kraw), key_cache, val_cache, ToX(f->gBUFF.scratch), normQ.w ? ToX(normQ.w) : nullptr,
                           normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos, nullptr, n_head, n_head_kv, head_dim, kv_dim, normQ.rms_eps,
                           f->gBUFF.attn_ws->data) != KF_OK)
             return nullptr;
         SLP* o[1] = {&proj_cat};
         floatX* yo[1] = {ToX(out)};
-        if (f->A8Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, q_dim, nullptr, 1, o, yo, ToX(inpL)) != KF_OK) return nullptr;
+        if ((f->*group)(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, q_dim, nullptr, 1, o, yo, ToX(inpL)) != KF_OK) return nullptr;
         return out;
     }
     if (f->fuse_level == 0) {
@@ -171,14 +173,16 @@ hGTensor FFN::cuInfer(hGTensor hIn, int) {
     Fish* f = hFish;
     kf_ctx* c = f->ctx;
     f->gBUFF.residual = hIn;
-    if (f->act_int8) {  // int8 activations: [norm + quantise] -> gate, up -> SwiGLU -> [quantise] -> down + residual; 6 launches (no hot-row masks: refused at switch-on)
+    if (f->per_layer()) {  // int8 activations: [norm + quantise] -> gate, up -> SwiGLU -> [quantise] -> down + residual; 6 launches (no hot-row masks: refused at switch-on)
+                           // adapters: norm -> gate, up -> their adapters (one launch) -> SwiGLU -> down + residual -> its adapter; 7 launches (no hot-row masks either)
+        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
         SLP* gu[2] = {&gate, &up};
         floatX* ys[2] = {ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut)};
-        if (f->A8Group(ToX(hIn), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 2, gu, ys, nullptr) != KF_OK) return nullptr;
+        if ((f->*group)(ToX(hIn), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 2, gu, ys, nullptr) != KF_OK) return nullptr;
         if (kf_swiglu(c, ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut), ToX(f->gBUFF.scratch), latent) != KF_OK) return nullptr;
         SLP* d[1] = {&down};
         floatX* yd[1] = {ToX(out)};
-        if (f->A8Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, latent, nullptr, 1, d, yd, ToX(hIn)) != KF_OK) return nullptr;
+        if ((f->*group)(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, latent, nullptr, 1, d, yd, ToX(hIn)) != KF_OK) return nullptr;
         return out;
     }
     if (f->fuse_level == 0) {
@@ -219,17 +223,19 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
     floatX* vrows = val_cache + (size_t)pos0 * kv_dim;
     floatX *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn);
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
-    if (f->act_int8) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
-        KF_TRY(f->A8Ready(n));
+    if (f->per_layer()) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
+                           // adapters: kf_rmsnorm, kf_linear per matrix, kf_lora_apply per adapted matrix -- on the RAW k / v rows in the cache, before q/k-norm + RoPE, as the trainer's forward
+        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
+        if (f->act_int8) KF_TRY(f->A8Ready(n));
         SLP* qkv[3] = {&Q, &K, &V};
         floatX* ys[3] = {bq, krows, vrows};
-        KF_TRY(f->A8Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 3, qkv, ys, nullptr));
+        KF_TRY((f->*group)(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 3, qkv, ys, nullptr));
         KF_TRY(kf_qknorm_rope_batch(c, bq, krows, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n, q_dim, kv_dim, n_head, n_head_kv,
                                     head_dim, normQ.rms_eps));
         KF_TRY(kf_attn_prefill(c, bq, key_cache, val_cache, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
         SLP* o[1] = {&proj_cat};
         floatX* yo[1] = {bx};
-        return f->A8Group(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
+        return (f->*group)(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
     }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, krows, vrows, n, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv,
@@ -244,15 +250,16 @@ int FFN::cuFlow(floatX* bx, int n) {
     const int C = f->config.nEmbed;
     floatX *bn = ToX(f->gBUFF.bNorm), *bg = ToX(f->gBUFF.bGate), *bu = ToX(f->gBUFF.bUp);
     kf_weight wg = gate.w->desc(), wu = up.w->desc(), wd = down.w->desc();
-    if (f->act_int8) {
-        KF_TRY(f->A8Ready(n));
+    if (f->per_layer()) {
+        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
+        if (f->act_int8) KF_TRY(f->A8Ready(n));
         SLP* gu[2] = {&gate, &up};
         floatX* ys[2] = {bg, bu};
-        KF_TRY(f->A8Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
+        KF_TRY((f->*group)(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
         KF_TRY(kf_swiglu(c, bg, bu, bg, n * latent));
         SLP* d[1] = {&down};
         floatX* yd[1] = {bx};
-        return f->A8Group(bg, nullptr, 0.0f, n, latent, nullptr, 1, d, yd, bx);
+        return (f->*group)(bg, nullptr, 0.0f, n, latent, nullptr, 1, d, yd, bx);
     }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_gateup_swiglu_batch(c, &wg, &wu, bn, bg, bu, n));
@@ -443,6 +450,10 @@ int Fish::SetActInt8(bool on, std::string& why) {
             why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
             return KF_UNSUPPORTED_DATATYPE;
         }
+        if (n_adapters > 0) {
+            why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
+            return KF_INVALID_ARGS;
+        }
         int n8 = 0;
         std::vector<uint16_t> zero;
         for (int l = 0; l < config.nLayer; l++) {
@@ -491,6 +502,10 @@ int Fish::SetActInt8Q4(bool on, std::string& why) {
             why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
             return KF_UNSUPPORTED_DATATYPE;
         }
+        if (n_adapters > 0) {
+            why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
+            return KF_INVALID_ARGS;
+        }
         int n4 = 0;
         for (int l = 0; l < config.nLayer; l++) {
             SelfAttention* a = attn[l].get();
@@ -518,6 +533,86 @@ int Fish::SetActInt8Q4(bool on, std::string& why) {
     const bool was = act_int8;
     act_int8_q4 = on;
     A8Switched(was);
+    return KF_OK;
+}
+
+// ---- low-rank adapters at inference (kfh_set_adapter / kfh_clear_adapters)
+SLP* Fish::LayerMatrix(int layer, int slot) {
+    if (layer < 0 || layer >= config.nLayer) return nullptr;
+    SelfAttention* a = attn[layer].get();
+    FFN* m = ffn[layer].get();
+    SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
+    return slot >= 0 && slot < 7 ? s[slot] : nullptr;
+}
+int Fish::SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why) {
+    SLP* m = LayerMatrix(layer, slot);
+    if (!m || !m->w || !a || !b) {
+        why = "adapters: no such layer matrix (layer " + std::to_string(layer) + ", slot " + std::to_string(slot) + "), its weight is not set, or a null pointer";
+        return KF_INVALID_ARGS;
+    }
+    if (tp.world > 1) {
+        why = "adapters: this Fish is a tensor-parallel rank and the TP step applies no adapters";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
+    if (act_int8) {
+        why = "adapters: int8 activations are on and their products apply no adapters: switch kfh_set_act_int8 / kfh_set_act_int8_q4 off first";
+        return KF_INVALID_ARGS;
+    }
+    if (masked_layers > 0) {
+        why = "adapters: a hot-row mask is set and the sparse forward applies no adapters: clear it first";
+        return KF_INVALID_ARGS;
+    }
+    if (!std::isfinite(s)) {
+        why = "adapters: s is not finite";
+        return KF_INVALID_ARGS;
+    }
+    if (n_adapters - (m->lora_a ? 1 : 0) > 0 && (r != lora_r || s != lora_s)) { /* another matrix carries one already */
+        why = "adapters: one rank and one s per model (attached: rank " + std::to_string(lora_r) + ")";
+        return KF_INVALID_ARGS;
+    }
+    if (const int st = kf_lora_apply_status(r, m->nOut, m->nIn, 1, 1)) {
+        why = "adapters: kf_lora_apply refuses rank " + std::to_string(r) + " beside a " + std::to_string(m->nOut) + " x " + std::to_string(m->nIn) +
+              " matrix (rank 16, 32 or 64; sides multiples of 64 and >= 128)";
+        return st;
+    }
+    if (((uintptr_t)a | (uintptr_t)b) & 15) {
+        why = "adapters: a and b must be 16-byte aligned";
+        return KF_BLAS_UNALIGN;
+    }
+    if (!m->lora_a) n_adapters++;
+    m->lora_a = a, m->lora_b = b, lora_r = r, lora_s = s;
+    DropEngineTable(); /* as A8Switched: the captured graphs and the engine belong to the model without adapters */
+    weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use, and refuse */
+    return KF_OK;
+}
+void Fish::ClearAdapters() {
+    if (!n_adapters) return;
+    for (int l = 0; l < config.nLayer; l++)
+        for (int j = 0; j < 7; j++) {
+            SLP* m = LayerMatrix(l, j);
+            m->lora_a = m->lora_b = nullptr;
+        }
+    n_adapters = 0, lora_r = 0, lora_s = 0.0f;
+    DropEngineTable();
+    weights_gen++;
+}
+int Fish::LoraGroup(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
+    const floatX* xb = x;
+    if (norm_w) {
+        KF_TRY(kf_rmsnorm(ctx, x, norm_w, normed, n, dim, eps, nullptr));
+        xb = normed;
+    }
+    const floatX *a[3], *b[3];
+    floatX* ya[3];
+    int OC[3], na = 0;
+    for (int i = 0; i < n_w; i++) {
+        const kf_weight wd = s[i]->w->desc();
+        KF_TRY(kf_linear(ctx, &wd, xb, y[i], s[i]->b ? ToX(s[i]->b) : nullptr, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
+        if (s[i]->lora_a) a[na] = s[i]->lora_a, b[na] = s[i]->lora_b, ya[na] = y[i], OC[na] = wd.ne0, na++;
+    }
+    if (na == 0) return KF_OK;
+    if (n == 1) return kf_lora_apply(ctx, na, a, b, lora_r, OC, dim, xb, ya, nullptr, 1, lora_s); /* the group's adapters share the row: one launch */
+    for (int i = 0; i < na; i++) KF_TRY(kf_lora_apply(ctx, 1, a + i, b + i, lora_r, OC + i, dim, xb, ya + i, nullptr, n, lora_s));
     return KF_OK;
 }
 
@@ -581,6 +676,10 @@ int Fish::EnsureEngine() {
     engine_state = -1;
     if (act_int8) {
         engine_why = "int8 activations run on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
+    if (n_adapters > 0) {
+        engine_why = "low-rank adapters are attached: they run on the per-layer launches";
         return KF_ENGINE_NOT_SERVED;
     }
     std::vector<kf_engine_layer> L;
@@ -700,6 +799,10 @@ int Fish::TPInit(int rank, int world, int vocab_row0) {
         g_host_err = "kfh_tp_init: int8 activations are on and the tensor-parallel step has no int8-activation form: switch kfh_set_act_int8 off first";
         return KF_UNSUPPORTED_DATATYPE;
     }
+    if (n_adapters > 0) { /* nor one that applies adapters */
+        g_host_err = "kfh_tp_init: low-rank adapters are attached and the tensor-parallel step applies no adapters: clear the adapters first";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
     std::memset(&tp.comm, 0, sizeof(tp.comm));
     tp.rank = rank, tp.world = world, tp.vocab_row0 = vocab_row0;
     tp.comm.rank = rank, tp.comm.world = world, tp.comm.n_max = config.nEmbed, tp.comm.per_step = 2u * (uint32_t)config.nLayer + 1u;
@@ -784,7 +887,7 @@ static int tp_group_enqueue(Fish** fs, int R) {
 
 int Fish::EnqueueStep(int bound) {
     if (tp.world > 1) return EnqueueStepTP(); /* never with int8 activations: SetActInt8 refuses a TP rank, TPInit refuses while the switch is on */
-    if (act_int8 && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
+    if (per_layer() && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
     if (use_engine && fuse_level >= 1 && engine_state > 0 && engine_embed && (graph_mode || state_tokens)) { /* embedding row read inside the launch */
         if (engine_head) { /* ... and the final norm, the LM head and the greedy pick: ONE launch per token */
             const int rc = kf_engine_step_head(ctx, engine, nullptr, ToX(x), d_state, bound, samp_params.greedy() ? 1 : 0);
@@ -872,7 +975,7 @@ bool Fish::OneLaunchStep() {
 int Fish::RunSteps(int pos, int n, bool use_graph) {
     if (pos < 0 || pos + n > config.n_ctx) return KF_INVALID_ARGS;
     KF_TRY(TPCommit());
-    if (use_graph && n > 1 && !act_int8 && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
+    if (use_graph && n > 1 && !per_layer() && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
         constexpr int kStepsPerLaunch = 16;
         int i = 0;
         while (i < n) {
@@ -904,7 +1007,7 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
     }
     for (int i = 0; i < n; i++) {
         const int p = pos + i;
-        if (fuse_level == 0 || act_int8) {  // per-kernel launches only (AutoAWQ weights; int8 activations): eager, position from the host, token from the device state
+        if (fuse_level == 0 || per_layer()) {  // per-kernel launches only (AutoAWQ weights; int8 activations; adapters): eager, position from the host, token from the device state
             tok_pos = p;
             graph_mode = false, state_tokens = true;
             int rc = EnqueueStep(pos_bound());
@@ -1159,6 +1262,10 @@ int XcdReplicas::MakeEngine(bool allocate) {
     kf_engine_desc d;
     if (f->act_int8) {
         why = "int8 activations run on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
+    if (f->n_adapters > 0) {
+        why = "low-rank adapters are attached: the XCD engines apply no adapters";
         return KF_ENGINE_NOT_SERVED;
     }
     KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
@@ -1501,6 +1608,10 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "int8 activations run on the per-layer launches";
             return KF_ENGINE_NOT_SERVED;
         }
+        if (f->n_adapters > 0) {
+            why = "low-rank adapters are attached: the XCD engines apply no adapters";
+            return KF_ENGINE_NOT_SERVED;
+        }
         KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
         ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
         dp[r] = &ds[r];
@@ -1605,6 +1716,10 @@ int kfh_set_hot(void* h, int layer, const int32_t* h_hot, int n) {
         g_host_err = "kfh_set_hot: int8 activations are on and the sparse forward has no int8-activation form: switch kfh_set_act_int8 off first";
         return KF_INVALID_ARGS;
     }
+    if (h_hot && f->n_adapters > 0) { /* nor a form that applies adapters */
+        g_host_err = "kfh_set_hot: low-rank adapters are attached and the sparse forward applies no adapters: clear the adapters first";
+        return KF_INVALID_ARGS;
+    }
     f->DropEngineTable(); /* the engine's layer table (and the captured graphs) hold the masks: rebuilt on the next step; the resident bf16 copies and the measured delays do not
                              depend on them and stay */
     f->weights_gen++;     /* an XcdReplicas built on this Fish holds the masks' addresses in its layer table too: its next use re-creates the engine */
@@ -1648,6 +1763,19 @@ int kfh_set_act_int8_q4(void* h, int on) {
     if (rc != KF_OK) g_host_err = "kfh_set_act_int8_q4: " + g_host_err;
     return rc;
 }
+// a low-rank adapter beside layer matrix `slot` (0 q, 1 k, 2 v, 3 o, 4 gate, 5 up, 6 down): a [r, in], b [out, r] bf16 DEVICE pointers, no copy (the caller keeps them alive and
+// may update them in place: every launch reads them); s multiplies both products, one rank and one s per model.  While any is attached decode, prefill, score and perplexity
+// apply it (Fish::LoraGroup) on per-layer launches.  A refusal changes nothing; kfh_host_error says why.
+int kfh_set_adapter(void* h, int layer, int slot, const void* a, const void* b, int r, float s) {
+    const int rc = reinterpret_cast<Fish*>(h)->SetAdapter(layer, slot, reinterpret_cast<const floatX*>(a), reinterpret_cast<const floatX*>(b), r, s, g_host_err);
+    if (rc != KF_OK) g_host_err = "kfh_set_adapter: " + g_host_err;
+    return rc;
+}
+int kfh_clear_adapters(void* h) {
+    reinterpret_cast<Fish*>(h)->ClearAdapters();
+    return KF_OK;
+}
+int kfh_n_adapters(void* h) { return reinterpret_cast<Fish*>(h)->n_adapters; }
 // the token count from which a token batch's ternary / 1-bit matrices take the int8 MFMA tiles (kf_linear_a8_tiles) instead of the mat-vec (kf_linear_a8): n >= 2 sets it,
 // 1 is treated as 2 (a single token always takes the mat-vec), 0 restores the default (KF_A8_TILE_MIN), n < 0 = never.  Both routes give the same bits.
 int kfh_set_a8_tile_min(void* h, int n) {
@@ -1781,19 +1909,7 @@ int kfh_engine_check(void* h) {
 
 static SLP* slot_of(Fish* f, int layer, int slot) {
     if (layer < 0) return slot == 1 ? &f->head.proj : nullptr;
-    if (layer >= f->config.nLayer) return nullptr;
-    SelfAttention* a = f->attn[layer].get();
-    FFN* m = f->ffn[layer].get();
-    switch (slot) {
-        case 0: return &a->Q;
-        case 1: return &a->K;
-        case 2: return &a->V;
-        case 3: return &a->proj_cat;
-        case 4: return &m->gate;
-        case 5: return &m->up;
-        case 6: return &m->down;
-    }
-    return nullptr;
+    return f->LayerMatrix(layer, slot);
 }
 
 // slot: 0 q,1 k,2 v,3 o,4 gate,5 up,6 down (layer >= 0); layer = -1: slot 0 embed_tokens, 1 lm_head.
@@ -1829,6 +1945,10 @@ static int set_weight_impl(void* h, int layer, int slot, int type, int ne0, int 
     }
     SLP* s = slot_of(f, layer, slot);
     if (!s) return KF_INVALID_ARGS;
+    if (s->lora_a) { /* the pair beside it was checked against the old matrix's sides */
+        g_host_err = "kfh_set_weight: the matrix carries a low-rank adapter: clear the adapters first";
+        return KF_INVALID_ARGS;
+    }
     s->w = t, s->nOut = ne0, s->nIn = ne1;
     return f->EnsureLinearScratch(t->desc(), f->prefill_chunk); /* load time: the launches themselves never allocate */
 }

@@ -93,6 +93,7 @@ struct Relu : GeNeuron {
 struct SLP : GeNeuron {
     hGTensor w, b, out;
     int nIn = 0, nOut = 0;
+    const floatX *lora_a = nullptr, *lora_b = nullptr;  // a [r, nIn], b [nOut, r] of a low-rank adapter beside w (Fish::SetAdapter: the caller's device memory), or none
     bool Empty() const { return !w; }
     // rhs = W.lhs (+b);  returns 0 or -1 like the reference (NeuronFuse.cu:305-381)
     int Forw(hGTensor rhs, hGTensor lhs, hGTensor toGelu = nullptr, Relu* hRelu = nullptr, int flag = 0);
@@ -342,6 +343,20 @@ struct Fish : SeqBuffers {
     // the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual` (may alias y[0]; n_w == 1) kf_linear's
     // residual epilogue.  normed: [n][dim] for the bf16 route of matrices that have no integer form.
     int A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
+    // low-rank adapters at inference (kfh_set_adapter; include/kf_abi.h kf_lora_apply; the LORA branch of SLP::Forw): any subset of the layers' seven matrices carries a
+    // trained pair a [r, in], b [out, r] -- device pointers of the caller's, no copy, read at every launch (a trainer's later step is seen) -- with ONE rank and ONE s for
+    // the model.  While any is attached the layer bodies take the unfused sequence LoraGroup (modelled on A8Group) on per-layer launches with the position from the host:
+    // the persistent engines, the XCD objects and the captured graphs are not used, exactly as under act_int8.  Refused with a reason: a TP rank, int8 activations, a
+    // hot-row mask (and each of those while an adapter is attached), save_kun, a rank or shape kf_lora_apply_status refuses.
+    int n_adapters = 0, lora_r = 0;
+    float lora_s = 0.0f;
+    bool per_layer() const { return act_int8 || n_adapters > 0; }  // what the step sequencing asks: eager per-layer launches, no engine, no graphs
+    SLP* LayerMatrix(int layer, int slot);  // q k v o gate up down = 0 .. 6, or NULL
+    int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);
+    void ClearAdapters();
+    // A8Group's contract with kf_rmsnorm + kf_linear for every matrix, then kf_lora_apply on the same y for those that carry an adapter: one vector-form launch for the
+    // group when n == 1, a tile-form launch per adapted matrix otherwise
+    int LoraGroup(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
 };
 
 // What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their

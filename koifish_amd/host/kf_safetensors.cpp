@@ -1309,6 +1309,10 @@ void* kfh_load_hf(const char* dir, int device, void* stream, int layer_type, int
 // Fish -> file; 0 or a negative code with kfh_last_error() set
 int kfh_save_kun(void* h, const char* path) {
     std::string err;
+    if (reinterpret_cast<Fish*>(h)->n_adapters > 0) { /* the container has no place for a low-rank pair, and the blobs alone are not the model that is running */
+        g_st_err = "kfh_save_kun: low-rank adapters are attached and a .kun file holds none: clear the adapters, or save a model built from merged_masters()";
+        return KF_INVALID_ARGS;
+    }
     const int rc = SaveKun(reinterpret_cast<Fish*>(h), path, err);
     if (rc != KF_OK) g_st_err = err;
     return rc;

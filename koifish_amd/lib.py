@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
-    "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes",
+    "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes", "kf_lora_apply", "kf_lora_apply_status",
     "kf_evolve", "kf_loss_mean",
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
     "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
@@ -144,6 +144,8 @@ def load():
         hip.kf_lora_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_void_p]
         hip.kf_lora_backward_scratch_bytes.argtypes, hip.kf_lora_backward_scratch_bytes.restype = [C.c_int] * 4, C.c_size_t
         hip.kfdbg_lora_plan.argtypes = [C.c_int] * 4 + [C.POINTER(LoraPlan)]
+        hip.kf_lora_apply_status.argtypes = [C.c_int] * 5
+        hip.kf_lora_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         hip.kf_norm_backward.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p]
         hip.kf_norm_backward_scratch_bytes.argtypes, hip.kf_norm_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_rope_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]
@@ -247,6 +249,9 @@ def load():
         host.kfh_set_engine.argtypes = [C.c_void_p, C.c_int]
         host.kfh_set_act_int8.argtypes = [C.c_void_p, C.c_int]
         host.kfh_set_act_int8_q4.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_set_adapter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+        host.kfh_clear_adapters.argtypes = [C.c_void_p]
+        host.kfh_n_adapters.argtypes = [C.c_void_p]
         host.kfh_set_a8_tile_min.argtypes = [C.c_void_p, C.c_int]
         host.kfh_a8_route_counts.argtypes = [C.c_void_p, C.c_void_p]
         host.kfh_engine_steps.argtypes = [C.c_void_p]

@@ -280,6 +280,24 @@ class Context:
         L.check(self.hip.kf_lora_forward(self.h, _ptr(a), _ptr(b), r, OC, IC, _ptr(x), _ptr(y), _ptr(ax), n, s), "kf_lora_forward")
         return ax
 
+    def lora_apply(self, a, b, x, y, s=1.0, keep_ax=False):
+        """kf_lora_apply, the adapter at inference.  One adapter: a [r, IC], b [OC, r], x [n, IC] (or [IC]), y [n, OC] (or [OC]) bf16, any n >= 1; y becomes
+        bf16(y + s ax b^T) in place; keep_ax (n >= 2 only): ax [n, r] is kept and returned.  Up to three adapters that share ONE input row (n == 1, the vector form, one
+        launch): a, b and y are tuples of tensors, the y's separate and of their own lengths."""
+        many = isinstance(a, (tuple, list))
+        a_, b_, y_ = (list(a), list(b), list(y)) if many else ([a], [b], [y])
+        n_w, (r, IC) = len(a_), a_[0].shape
+        n = 1 if x.dim() == 1 else x.shape[0]
+        OC = [t.shape[0] for t in b_]
+        if len(b_) != n_w or len(y_) != n_w or x.numel() != n * IC or any(tuple(a_[i].shape) != (r, IC) or tuple(b_[i].shape) != (OC[i], r) or y_[i].numel() != n * OC[i]
+                                                                            for i in range(n_w)):
+            raise L.KFError("lora_apply: a %s, b %s, x %s, y %s" % ([tuple(t.shape) for t in a_], [tuple(t.shape) for t in b_], tuple(x.shape), [tuple(t.shape) for t in y_]))
+        ax = torch.empty(n, r, dtype=torch.bfloat16, device=self.device) if keep_ax and n > 1 else None
+        ptrs = lambda ts: (C.c_void_p * n_w)(*[t.data_ptr() for t in ts])
+        L.check(self.hip.kf_lora_apply(self.h, n_w, ptrs(a_), ptrs(b_), r, (C.c_int * n_w)(*OC), IC, _ptr(x), ptrs(y_), _ptr(ax), n, s),
+                "kf_lora_apply")
+        return ax
+
     def lora_backward(self, a, b, dIn, inp, ax, delta, g, s=1.0):
         """kf_lora_backward: delta [n, IC] bf16 (what the base's kf_linear_backward left) += s adelta a with adelta = bf16(s dIn b); g = [gA (r IC) | gB (OC r)] bf16 +=
         s adelta^T inp | s dIn^T ax.  Owns the scratch (kernels never allocate), sized with kf_lora_backward_scratch_bytes; returns adelta [n, r], a view of its head."""
@@ -617,7 +635,7 @@ class Qwen3:
             return
         a = np.ascontiguousarray(hot, dtype=np.int32)
         rc = self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size)
-        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False)):   # the one refusal the host explains: a mask while int8 activations are on (the text is set on that path only)
+        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False) or getattr(self, "_adapters", None)):   # the refusals the host explains: a mask while int8 activations are on or adapters are attached (the text is set on those paths only)
             raise L.KFError("kfh_set_hot failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         L.check(rc, "kfh_set_hot")
         if not hasattr(self, "_hot"):
@@ -647,6 +665,64 @@ class Qwen3:
         if rc != 0:
             raise L.KFError("set_act_int8_q4 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         self._act_int8_q4 = bool(on)
+
+    @classmethod
+    def check_adapters(cls, cfg, adapters, lora_s):
+        """every argument error of set_adapters as a ValueError, without a device: names "l<layer>.<target>.w" with target out of q k v o gate up down, (a [r, in],
+        b [out, r]) bf16 tensors of ONE rank 16 / 32 / 64, a finite lora_s.  Returns [(layer, slot, a, b)] and the rank."""
+        if not (isinstance(lora_s, (int, float)) and lora_s == lora_s and abs(lora_s) != float("inf")):
+            raise ValueError("lora_s %r: a finite number" % (lora_s,))
+        if not adapters:
+            raise ValueError("adapters: an empty dict (clear_adapters() detaches)")
+        dim, H, KV, hd, ffn = (cfg[k] for k in ("dim", "n_head", "n_kv", "head_dim", "ffn"))
+        shapes = dict(q=(H * hd, dim), k=(KV * hd, dim), v=(KV * hd, dim), o=(dim, H * hd), gate=(ffn, dim), up=(ffn, dim), down=(dim, ffn))
+        out, rank = [], None
+        for name, ab in adapters.items():
+            l, _, k = name[1:].partition(".")
+            if not (name[:1] == "l" and l.isdigit() and int(l) < cfg["n_layer"] and k.endswith(".w") and k[:-2] in SLOTS):
+                raise ValueError("adapters: %r is no layer matrix (names are l<layer>.<target>.w, target out of %s)" % (name, SLOTS))
+            OC, IC = shapes[k[:-2]]
+            if len(ab) != 2 or any(not torch.is_tensor(t) or t.dim() != 2 for t in ab):
+                raise ValueError("adapters[%r]: a pair of 2-D tensors (a [r, %d], b [%d, r])" % (name, IC, OC))
+            a, b = ab
+            if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+                raise ValueError("adapters[%r]: bf16 tensors (got %s, %s)" % (name, a.dtype, b.dtype))
+            r = a.shape[0]
+            if r not in (16, 32, 64) or tuple(a.shape) != (r, IC) or tuple(b.shape) != (OC, r):
+                raise ValueError("adapters[%r]: a [r, %d], b [%d, r] with r 16, 32 or 64 (got %s, %s)" % (name, IC, OC, tuple(a.shape), tuple(b.shape)))
+            if rank is not None and r != rank:
+                raise ValueError("adapters[%r]: rank %d beside rank %d -- one rank per model" % (name, r, rank))
+            rank = r
+            out.append((int(l), SLOTS.index(k[:-2]), a, b))
+        return out, rank
+
+    def set_adapters(self, adapters, lora_s=1.0):
+        """Attach trained low-rank pairs (Qwen3Step.lora_state()'s layout): {"l<layer>.<target>.w": (a [r, in], b [out, r])} of bf16 DEVICE tensors, any subset of the
+        layers' seven matrices, one rank; lora_s multiplies both products (effective weight lora_s^2 b a).  No copy: the model keeps the tensors alive and reads them at
+        every launch, so an in-place update is seen.  forward, run_steps, generate, prefill, score and perplexity then apply them (kf_lora_apply after each base product)
+        on per-layer launches -- engine_why() says so; the packed base stays byte for byte.  Replaces whatever was attached.  ValueError for a bad argument (before
+        anything touches the device); KFError when the model refuses: a TP rank, int8 activations on, a hot-row mask set, a shape kf_lora_apply does not serve."""
+        items, rank = self.check_adapters(self.cfg, adapters, lora_s)
+        for _, _, a, b in items:
+            if a.device != self.device or b.device != self.device or not a.is_contiguous() or not b.is_contiguous():
+                raise ValueError("adapters: contiguous tensors on %s" % (self.device,))
+        self.clear_adapters()
+        for layer, slot, a, b in items:
+            rc = self.host.kfh_set_adapter(self.h, layer, slot, _ptr(a), _ptr(b), rank, float(lora_s))
+            if rc != 0:
+                why = self.host.kfh_host_error().decode()
+                self.clear_adapters()
+                raise L.KFError("set_adapters failed with %d: %s" % (rc, why))
+        self._adapters, self._lora_s = {name: tuple(ab) for name, ab in adapters.items()}, float(lora_s)
+
+    def clear_adapters(self):
+        """detach every adapter: the fused launches, the engines and the captured graphs serve the model again, bit for bit as before set_adapters"""
+        L.check(self.host.kfh_clear_adapters(self.h), "kfh_clear_adapters")
+        self._adapters = {}
+
+    def adapters(self):
+        """{name: (a, b)} of what is attached (the tensors themselves)"""
+        return dict(getattr(self, "_adapters", {}))
 
     def set_a8_tile_min(self, n):
         """token batches of at least n rows send their ternary / 1-bit matrices to the int8 MFMA tiles (kf_linear_a8_tiles) while int8 activations are on, smaller ones and

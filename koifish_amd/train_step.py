@@ -375,7 +375,8 @@ class Qwen3Step(_TrainStep):
     trained weights; every update() calls weights_changed() on each model still alive.
 
     train_target="lora": every matrix named in lora_targets is quantised once and frozen, and a rank-r pair trains beside it (the LORA branch of SLP::Forw / SLP::Back):
-    lora_state() hands out the trained pairs, merged_masters() the masters of an equivalent plain model.  The decode path applies no adapters: as_model() refuses.
+    lora_state() hands out the trained pairs, merged_masters() the masters of an equivalent plain model, as_model(max_seq, adapters=True) a decoder on the packed base
+    with the pairs attached (kf_lora_apply); plain as_model(max_seq) refuses.
 
     Not offered on this trainer: EOE layer-section branches (GPT2Step's layers_in_branch)."""
 
@@ -492,13 +493,18 @@ class Qwen3Step(_TrainStep):
         bufs = (self.xf, self.hf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.dact, self.dgate, self.vtmp, self.dqr, self.dkr, self.dvd, self.table)
         self._attach(bufs, (self._sc_ln, self._sc_at, self._sc_qk))
 
-    def as_model(self, max_seq):
+    def as_model(self, max_seq, adapters=False):
         """a Qwen3 decoder on the trainer's OWN blobs and norm tensors (set_weight / set_norm / tie_head with device pointers: no copy), vocabulary = the unpadded one.
-        The step keeps a weak reference and calls weights_changed() on it after every update; the model must not outlive this object's buffers."""
+        The step keeps a weak reference and calls weights_changed() on it after every update; the model must not outlive this object's buffers.
+        adapters=True (train_target="lora" only): lora_state()'s VIEWS are attached (Qwen3.set_adapters, no copy), so the model scores, generates and measures perplexity
+        with what has been trained so far, and a later step() is seen without attaching again.  Without it a "lora" trainer refuses: the frozen base alone is not the model."""
         import weakref
         from .runtime import DevWeight, Qwen3
-        if self.train_target == "lora":
-            raise L.KFError("as_model under train_target='lora': the decode path does not apply adapters -- build a plain model from merged_masters()")
+        if adapters and self.train_target != "lora":
+            raise L.KFError("as_model(adapters=True) under train_target=%r: only a 'lora' trainer has adapters" % (self.train_target,))
+        if self.train_target == "lora" and not adapters:
+            raise L.KFError("as_model under train_target='lora': the decode path does not apply adapters unless asked -- as_model(max_seq, adapters=True), or build a "
+                            "plain model from merged_masters()")
         dim, V = self.cfg["dim"], self.V
         m = Qwen3(dict(self.cfg, max_seq=int(max_seq), rms_eps=self.eps, qk_eps=self.eps, theta=self.theta, tied=self.tied), device=self.ctx.device.index or 0)
         rows = lambda e: DevWeight(L.BF16, V, dim, e["blob"].blob[:V * dim * 2])   # the first V rows of the [Vp, dim] bf16 blob, the same memory
@@ -513,6 +519,8 @@ class Qwen3Step(_TrainStep):
                 m.set_weight(li, si, ly[k]["blob"])
             for si, k in enumerate(Q3_NORMS):
                 m.set_norm(li, si, ly[k]["p"])
+        if adapters:
+            m.set_adapters(self.lora_state(), self.lora_s)
         m._trainer = self   # the buffers live as long as the model does
         self._models.append(weakref.ref(m))
         return m
