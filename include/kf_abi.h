@@ -476,6 +476,42 @@ int kf_swiglu_backward(kf_ctx* ctx, kf_bf16* delta_in_out, kf_bf16* delta_gate, 
 int kf_fused_classifier(kf_ctx* ctx, kf_bf16* logits, float* losses, kf_bf16* probs_or_null, float dloss, const int32_t* targets, int B, int T, int V, int P,
                         const int32_t* mask_or_null, int write_dlogits);
 
+/* Distilling classifier: the fused classifier with a teacher's logits beside the hard labels (logit distillation as BitNet-style training of low-bit students
+ * uses it).  The reference states the intent only (src/Fuzi/Distillation.hpp is a stub, src/Device/CUDA/Distill.cu an attention-relation loss, not built here),
+ * so the contract is this comment.  Per row of logits [B*T, P] (z: V valid bf16 entries) and of teacher [B*T, teacher_ld] (u), tau = temperature,
+ * it = 1 / tau (fp32), a = ce_weight, b = kd_weight, m_z / m_u the row maxima:
+ *     p_i  = exp(z_i - m_z) / S1            S1 = sum exp(z_i - m_z)
+ *     pt_i = exp((z_i - m_z) it) / St       St = sum exp((z_i - m_z) it)
+ *     qt_i = exp((u_i - m_u) it) / Ut       Ut = sum exp((u_i - m_u) it)
+ *     A    = sum exp((u_i - m_u) it) ((u_i - m_u) - (z_i - m_z)) it
+ *     KL   = A / Ut - log Ut + log St       = KL(qt || pt), not clamped
+ *     CE   = -log p[target]
+ *     losses[row] += a CE + b tau^2 KL      (accumulates, as the fused classifier's)
+ *     kd[row]      = KL                     (kd may be NULL; written, not accumulated; only when b != 0)
+ *     dlogit_i     = bf16((a (p_i - [i == target]) + b tau (pt_i - qt_i)) dloss)   over the logits, when write_dlogits != 0
+ * Rows whose mask word has bit 0x10000 are skipped entirely; the columns [V, P) and [V, teacher_ld) are never read or written; the teacher is never written.
+ * With a == 0 the targets are not read (NULL is accepted), with b == 0 neither teacher nor kd is (NULL is accepted).
+ *
+ * Order of operations (fp32; exp / log the fixed recipes of the fused classifier; no fma except where one is named; tests/distill_restate.py is this in numpy).
+ * One workgroup of 1024 threads per row.  Thread t owns the 8-element vectors i = ceil(V/8) + t - 1024, i - 1024, ... >= 0 and visits them in that order, highest
+ * first, the elements of a vector ascending.  "Block max / sum" is the fused classifier's reduction: an xor butterfly (offsets 16, 8, 4, 2, 1) inside each group
+ * of 32 consecutive threads, then the same butterfly over the 32 group results.
+ *   1. As the fused classifier: per thread a running (max, sum) over its z -- on a new maximum sum *= exp(old - new), then sum += exp(z - max) --; m_z = block max;
+ *      sum_t *= exp(max_t - m_z); S1 = block sum; r1 = 1 / S1.  In the same sweep, b != 0: the thread's maximum of u; m_u = block max.
+ *   2. b != 0.  Per thread, from 0, over its elements in the visiting order:  dz = z - m_z;  du = u - m_u;  st = st + exp(dz it);  eu = exp(du it);  ut = ut + eu;
+ *      at = fma(eu, (du - dz) it, at).  St, Ut, A = the block sums of st, ut, at.  KL = (A / Ut - log Ut) + log St;  rt = 1 / St;  ru = 1 / Ut.
+ *      The z and the u sums run through one chain and one tree, so u == z gives Ut == St bit for bit, A == 0 and KL == 0.0 at any temperature.
+ *   3. c = a (-log(exp(z[target] - m_z) r1)) when a != 0;  w = (b tau) tau;  c = fma(w, KL, c) when both weights are set, c = w KL when a == 0;  losses[row] += c.
+ *   4. write_dlogits: per element  g = a (exp(dz) r1 - [i == target]) when a != 0, else 0;  b != 0:  g = fma(b tau, exp(dz it) rt - exp(du it) ru, g);
+ *      dlogit = bf16(g dloss).
+ * a = 1, b = 0 is the fused classifier bit for bit (1 x is exact); u == z adds exactly nothing to a gradient.
+ * KF_INVALID_ARGS, nothing launched: NULL logits or losses; NULL teacher with b != 0; NULL targets with a != 0; a weight negative or not finite, or both zero;
+ * a temperature not finite or <= 0; P < V or teacher_ld < V; teacher rows that overlap the logits' rows.  KF_BLAS_UNALIGN: P or teacher_ld no multiple of 8,
+ * logits or teacher not 16-byte aligned. */
+int kf_distill_classifier(kf_ctx* ctx, kf_bf16* logits, const kf_bf16* teacher_or_null, int64_t teacher_ld, float* losses, float* kd_or_null, float dloss,
+                          const int32_t* targets_or_null, int B, int T, int V, int P, const int32_t* mask_or_null, float ce_weight, float kd_weight, float temperature,
+                          int write_dlogits);
+
 /* ---- training kernel path (BASELINE config 3), first piece: the AdamW parameter update CU_adamw_p (src/Device/CUDA/Optimizer.cu:393-442)
  * as PIPE_Adamw::Update launches it (Optimizer.cu:630-646; TASKA_1p1, packedN.cuh:612-643: 512 threads x 8 bf16 per thread).
  * params / grads bf16 [n] (grads are zeroed), gm / gv: first and second moments, mv_type KF_BF16 (floatMV = bf16) or KF_F32.

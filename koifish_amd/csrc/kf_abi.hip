@@ -1268,6 +1268,27 @@ int kf_fused_classifier(kf_ctx* c, kf_bf16* logits, float* losses, kf_bf16* prob
         return fail(KF_BLAS_UNALIGN, "kf_fused_classifier: rows must be 16-byte aligned (P = %d a multiple of 8, like the reference's padded vocabulary)", P);
     RET(kf::fused_classifier_launch(c->stream, logits, losses, probs, dloss, targets, (long)B * T, V, P, mask, write_dlogits));
 }
+int kf_distill_classifier(kf_ctx* c, kf_bf16* logits, const kf_bf16* teacher, int64_t teacher_ld, float* losses, float* kd, float dloss, const int32_t* targets, int B, int T,
+                          int V, int P, const int32_t* mask, float ce_weight, float kd_weight, float temperature, int write_dlogits) {
+    CHKCTX(c);
+    if (!logits || !losses) return fail(KF_INVALID_ARGS, "kf_distill_classifier: null logits or losses");
+    if (!isfinite(ce_weight) || !isfinite(kd_weight) || ce_weight < 0.0f || kd_weight < 0.0f || (ce_weight == 0.0f && kd_weight == 0.0f))
+        return fail(KF_INVALID_ARGS, "kf_distill_classifier: ce_weight and kd_weight must be finite and >= 0, and not both zero (got %g, %g)", (double)ce_weight, (double)kd_weight);
+    if (!isfinite(temperature) || !(temperature > 0.0f)) return fail(KF_INVALID_ARGS, "kf_distill_classifier: the temperature must be finite and > 0 (got %g)", (double)temperature);
+    if (kd_weight != 0.0f && !teacher) return fail(KF_INVALID_ARGS, "kf_distill_classifier: kd_weight != 0 needs a teacher");
+    if (ce_weight != 0.0f && !targets) return fail(KF_INVALID_ARGS, "kf_distill_classifier: ce_weight != 0 needs targets");
+    if (B < 1 || T < 1 || V < 1 || P < V) return fail(KF_INVALID_ARGS, "kf_distill_classifier: needs B, T, V >= 1 and P >= V (got %d %d %d %d)", B, T, V, P);
+    if (teacher && teacher_ld < V) return fail(KF_INVALID_ARGS, "kf_distill_classifier: teacher_ld %lld is below V = %d", (long long)teacher_ld, V);
+    if ((P % 8) != 0 || !al16(logits) || (teacher && ((teacher_ld % 8) != 0 || !al16(teacher))))
+        return fail(KF_BLAS_UNALIGN, "kf_distill_classifier: rows must be 16-byte aligned (P = %d and teacher_ld = %lld multiples of 8)", P, (long long)teacher_ld);
+    if (teacher) { /* the rows' own extents: the last row ends at its V-th element */
+        const long long rows = (long long)B * T;
+        const uintptr_t z0 = (uintptr_t)logits, z1 = z0 + (size_t)((rows - 1) * P + V) * 2, u0 = (uintptr_t)teacher, u1 = u0 + (size_t)((rows - 1) * teacher_ld + V) * 2;
+        if (z0 < u1 && u0 < z1) return fail(KF_INVALID_ARGS, "kf_distill_classifier: the teacher's rows overlap the logits");
+    }
+    RET(kf::distill_classifier_launch(c->stream, logits, teacher, (long)teacher_ld, losses, kd, dloss, targets, (long)B * T, V, P, mask, ce_weight, kd_weight, temperature,
+                                      write_dlogits));
+}
 int kf_adamw(kf_ctx* c, kf_bf16* params, kf_bf16* grads, void* gm, void* gv, size_t n, int mv_type, float learning_rate, float beta1, float beta2,
              float beta1_correction, float beta2_correction, float eps, float weight_decay, float grad_scale, uint32_t seed, int32_t* d_status) {
     CHKCTX(c);

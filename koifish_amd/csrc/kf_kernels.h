@@ -214,6 +214,9 @@ int embed_backward_launch(hipStream_t st, uint16_t* dwte, long long ldw, uint16_
 // fused classifier (kf_loss.hip): cross-entropy loss per row + logit gradient in place
 int fused_classifier_launch(hipStream_t st, uint16_t* logits, float* losses, uint16_t* probs, float dloss, const int* targets, long rows, int V, int P,
                             const int* mask, int write_dlogits);
+// distilling classifier (kf_distill.hip): a CE + b tau^2 KL(teacher || student) per row + its logit gradient in place; kd_weight == 0: no teacher is read
+int distill_classifier_launch(hipStream_t st, uint16_t* logits, const uint16_t* teacher, long teacher_ld, float* losses, float* kd, float dloss, const int* targets,
+                              long rows, int V, int P, const int* mask, float ce_weight, float kd_weight, float temperature, int write_dlogits);
 int swiglu_launch(hipStream_t st, const uint16_t* gate, const uint16_t* up, uint16_t* out, int n);
 int add_launch(hipStream_t st, const uint16_t* a, const uint16_t* b, uint16_t* out, int n);
 int embed_launch(hipStream_t st, const kf_weight* w, int token, const int32_t* d_token, const int32_t* d_state, const int32_t* d_forced,

@@ -27,6 +27,9 @@
 // (ExploreOptimization, Scheduler.cpp:430-486): the head branch pulls the four weight matrices (isWMAT) of every layer of every other branch towards its own with
 // kf_evolve, and every follower blob is re-quantised.  Eval is the evaluation half of Fish::ForwardOnRLS (gLLM.cpp:722-787): one branch, or the mean over all of
 // them.  Which branch trains when, and which one is the head, is the caller's loop.  One branch (the default) is the code above, bit for bit.
+//
+// Distillation from a teacher's logits (kfh_gpt2_set_distill / _forward_logits) is TrainerCore's (SetDistill, ForwardLogits): with a teacher set the forward ends in
+// kf_distill_classifier.  It and the layer sections exclude each other: Eval shares the one `losses` buffer with the step.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -84,10 +87,10 @@ struct GPT2Trainer : TrainerCore {
     }
 
     // TokenEmbed, NL x [LayerNorm, qkv, causal attention, proj + residual, LayerNorm, fc, GELU, proj2 + residual], LayerNorm, tied head, fused classifier:
-    // per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
-    int Forward(const int32_t* d_ids, const int32_t* d_tgt) override {
-        KF_TRY(Ready());
-        if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
+    // (TrainerCore::Forward: per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`).  Trunk: up to hf, the final LayerNorm's output
+    TrainTensor& HeadTensor() override { return Wte(); }
+    bool Sectioned() const override { return LIS != NL; }
+    int Trunk(const int32_t* d_ids) override {
         KF_TRY(kf_embed_pos(ctx, Wte().p, C, Wpe().p, d_ids, B, T, C, Vp, acts[l0].x));
         for (int l = l0; l < l1; l++) {
             BlockActs& a = acts[l];
@@ -100,8 +103,7 @@ struct GPT2Trainer : TrainerCore {
             KF_TRY(kf_gelu(ctx, a.f, a.g, (size_t)N * 4 * C));
             KF_TRY(Lin(P(l, PROJ2_W), a.g, l + 1 < l1 ? acts[l + 1].x : xf, &P(l, PROJ2_B), a.x2));
         }
-        KF_TRY(LN(xf, LnfW(), LnfB(), hf, mf, rf));
-        return HeadLoss(Wte(), d_ids, d_tgt);
+        return LN(xf, LnfW(), LnfB(), hf, mf, rf);
     }
     int Backward() override {
         KF_TRY(Ready());
@@ -125,6 +127,10 @@ struct GPT2Trainer : TrainerCore {
         if (layers_in_branch == 0) layers_in_branch = NL;
         if (layers_in_branch < 0 || layers_in_branch > NL || NL % layers_in_branch) {
             g_train_err = "kfh_gpt2_set_branches: " + std::to_string(NL) + " layers do not divide into sections of " + std::to_string(layers_in_branch);
+            return KF_INVALID_ARGS;
+        }
+        if (teacher && layers_in_branch != NL) {
+            g_train_err = "kfh_gpt2_set_branches: the trainer distils from a teacher (set_distill), which layer sections do not offer -- switch distillation off first";
             return KF_INVALID_ARGS;
         }
         LIS = layers_in_branch;
@@ -183,6 +189,10 @@ struct GPT2Trainer : TrainerCore {
     int Eval(const int32_t* d_ids, const int32_t* d_tgt, int mode, int b, float* d_out) {
         KF_TRY(Ready());
         if (!d_out || d_out == losses) return KF_INVALID_ARGS;
+        if (teacher) {
+            g_train_err = "kfh_gpt2_eval: not offered while the trainer distils from a teacher (set_distill): switch distillation off first";
+            return KF_INVALID_ARGS;
+        }
         if (mode != ENSEMBLE_AGGREGATION && mode != ENSEMBLE_BRANCH) {
             g_train_err = "kfh_gpt2_eval: unknown ensemble mode " + std::to_string(mode);
             return KF_INVALID_ARGS;
@@ -297,5 +307,7 @@ int kfh_gpt2_eval(void* h, const int32_t* d_ids, const int32_t* d_tgt, int mode,
 }
 // gradient norms and clipping: TrainerCore::SetGradClip / GradClipScratchBytes / GradNorms (kf_train_common.hpp)
 KFH_GRAD_CLIP_ENTRIES(gpt2, koifish::g_train_err)
+// distillation against a teacher's logits: TrainerCore::SetDistill / ForwardLogits
+KFH_DISTILL_ENTRIES(gpt2, koifish::g_train_err)
 const char* kfh_gpt2_last_error(void) { return koifish::g_train_err.c_str(); }
 }

@@ -2,6 +2,7 @@
 // table of trained tensors, its registration in its three forms (shadow weights / "train_target": "gama" / a low-rank adapter beside a frozen matrix), SLP::Back for one matrix, the optimiser switch and the update loop
 // with its seed rule -- and the step around them: Update, Step, the head product + fused classifier that ends every Forward (HeadLoss), the head's backward that starts
 // every Backward (HeadBack).  A trainer adds its own activations, Ready, Forward and Backward, and says which registered indices are layer weight matrices (wmat).
+// Distillation lives here as well (SetDistill, ForwardLogits): a teacher's logits beside the hard labels, kf_distill_classifier in HeadLoss's place of kf_fused_classifier.
 // Gradient norms and clipping (SetGradClip) live here too: one kf_grad_norms call at the head of the update, the clip factors read on the device by kf_adamw_scaled.
 // The handle behind the C ABI of both families is the TrainerCore*: the entries the families share call through it (Core), a family's own cast down from it.
 #pragma once
@@ -58,12 +59,61 @@ struct TrainerCore {
     void* sc_clip = nullptr;
     double* d_sumsq = nullptr;
     float *d_gnorm = nullptr, *d_scale = nullptr;
+    // distillation (SetDistill): with a teacher set, HeadLoss ends in kf_distill_classifier instead of kf_fused_classifier.  The teacher's logits [N, teacher_ld] bf16
+    // and the KL rows [N] fp32 are the caller's; who fills the teacher's rows before a Forward is the caller's business too (another trainer's ForwardLogits)
+    const kf_bf16* teacher = nullptr;
+    long long teacher_ld = 0;
+    float ce_weight = 1.0f, kd_weight = 0.0f, temperature = 1.0f;
+    float* kd_rows = nullptr;
 
     virtual ~TrainerCore() {}  // touches no context (it may be gone already): the owner of a clip scratch switches clipping off before it frees the scratch
     virtual bool InSection(size_t) const { return true; }  // Update leaves a tensor outside the active section alone (EOE)
     virtual int Ready() const = 0;  // everything registered that a step reads (ParamsReady + the trainer's own activations and buffers)
-    virtual int Forward(const int32_t* d_ids, const int32_t* d_tgt) = 0;
+    virtual int Trunk(const int32_t* d_ids) = 0;  // the family's forward up to hf, the final norm's output: the embedding and the layer loop, written once
+    virtual TrainTensor& HeadTensor() = 0;        // what the head product multiplies
+    virtual bool Sectioned() const { return false; }  // EOE layer sections are set (GPT-2 only)
     virtual int Backward() = 0;
+    // per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
+    int Forward(const int32_t* d_ids, const int32_t* d_tgt) {
+        KF_TRY(Ready());
+        if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
+        KF_TRY(Trunk(d_ids));
+        return HeadLoss(HeadTensor(), d_ids, d_tgt);
+    }
+    // the forward through the head product only: raw logits in `logits`, no classifier, nothing a Backward could start from (ids is cleared: HeadBack refuses)
+    int ForwardLogits(const int32_t* d_ids, std::string* why) {
+        if (Ready() != KF_OK || !d_ids) {
+            if (why) *why = "forward_logits: every tensor and buffer must be registered, and ids must not be NULL";
+            return KF_INVALID_ARGS;
+        }
+        ids = nullptr;
+        KF_TRY(Trunk(d_ids));
+        return kf_linear(ctx, &HeadTensor().blob, hf, logits, nullptr, N, 1.0f, 0.0f, 0u, nullptr);
+    }
+    // teacher_logits == NULL: distillation off, the plain path bit for bit.  Otherwise every Forward from here on ends in kf_distill_classifier over (logits, teacher):
+    // losses[row] = ce_weight CE + kd_weight temperature^2 KL, kd_rows[row] (may be NULL) = KL, the gradient of their mean in `logits`.  A refusal changes nothing;
+    // *why says which.  Eval shares the one `losses` buffer with the step and is not defined under distillation: a trainer with EOE sections is refused.
+    int SetDistill(const kf_bf16* teacher_logits, long long ld, float ce_w, float kd_w, float tau, float* kd_out, std::string* why) {
+        auto refuse = [why](const char* msg) {
+            if (why) *why = msg;
+            return (int)KF_INVALID_ARGS;
+        };
+        if (!teacher_logits) {
+            teacher = nullptr, teacher_ld = 0, kd_rows = nullptr, ce_weight = 1.0f, kd_weight = 0.0f, temperature = 1.0f;
+            return KF_OK;
+        }
+        if (Ready() != KF_OK) return refuse("set_distill: every tensor and buffer must be registered first");
+        if (Sectioned()) return refuse("set_distill: a trainer with EOE layer sections (layers_in_branch) is not distilled: eval shares the step's loss buffer");
+        if (!(std::isfinite(ce_w) && std::isfinite(kd_w) && ce_w >= 0.0f && kd_w >= 0.0f) || (ce_w == 0.0f && kd_w == 0.0f))
+            return refuse("set_distill: ce_weight and kd_weight must be finite and >= 0, and not both zero");
+        if (!(std::isfinite(tau) && tau > 0.0f)) return refuse("set_distill: the temperature must be finite and > 0");
+        if (ld < V || (ld & 7) || ((uintptr_t)teacher_logits & 15)) return refuse("set_distill: teacher rows must be 16-byte aligned, teacher_ld >= V a multiple of 8");
+        const uintptr_t z0 = (uintptr_t)logits, z1 = z0 + (size_t)N * Vp * 2, u0 = (uintptr_t)teacher_logits, u1 = u0 + (size_t)N * (size_t)ld * 2;
+        if (z0 < u1 && u0 < z1) return refuse("set_distill: the teacher's logits overlap the trainer's own (a trainer cannot be its own teacher)");
+        if (kd_out && ((uintptr_t)kd_out & 3)) return refuse("set_distill: kd_rows is not 4-byte aligned");
+        teacher = teacher_logits, teacher_ld = ld, ce_weight = ce_w, kd_weight = kd_w, temperature = tau, kd_rows = kd_out;
+        return KF_OK;
+    }
 
     // MUON_params_::isAdamW restated: a Muon tensor is one of a layer's weight matrices with ne0 >= ne1 (the registered blob descriptor carries the shape) and a
     // [ne0, ne1] bf16 master; embeddings, biases, norms, matrices with ne0 < ne1 and gama-trained tensors stay on AdamW.  An adapter is never a Muon tensor: its
@@ -277,11 +327,15 @@ struct TrainerCore {
         KF_TRY(Backward());
         return Update(lr, beta1, beta2, eps, wd, seed);
     }
-    // the end of every Forward: logits = hf . head^T, then the fused classifier: per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
+    // the end of every Forward: logits = hf . head^T, then the fused classifier -- the distilling one under SetDistill --: per-row losses in `losses`, the logit gradients
+    // of the MEAN loss in `logits`
     int HeadLoss(TrainTensor& head, const int32_t* d_ids, const int32_t* d_tgt) {
         KF_TRY(kf_linear(ctx, &head.blob, hf, logits, nullptr, N, 1.0f, 0.0f, 0u, nullptr));
         KF_TRY(kf_memset(ctx, losses, 0, (size_t)N * 4));
-        KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
+        if (teacher)
+            KF_TRY(kf_distill_classifier(ctx, logits, teacher, teacher_ld, losses, kd_rows, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, ce_weight, kd_weight, temperature, 1));
+        else
+            KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
         ids = d_ids;
         return KF_OK;
     }
@@ -294,6 +348,18 @@ struct TrainerCore {
 };
 
 inline TrainerCore* Core(void* h) { return static_cast<TrainerCore*>(h); }  // the handle of kfh_gpt2_* / kfh_qwen3t_*
+
+// The distillation entries of a family, from one place: kfh_<fam>_set_distill (teacher_logits NULL: off; the reason of a refusal in the family's error string, which
+// kfh_<fam>_last_error hands out) and kfh_<fam>_forward_logits (a refusal of a kf_* entry underneath: kf_last_error).
+#define KFH_DISTILL_ENTRIES(fam, err)                                                                                                                         \
+    int kfh_##fam##_set_distill(void* h, const void* teacher_logits, int64_t teacher_ld, float ce_weight, float kd_weight, float temperature, void* kd_rows) { \
+        (err).clear();                                                                                                                                        \
+        return koifish::Core(h)->SetDistill((const kf_bf16*)teacher_logits, teacher_ld, ce_weight, kd_weight, temperature, (float*)kd_rows, &(err));          \
+    }                                                                                                                                                         \
+    int kfh_##fam##_forward_logits(void* h, const int32_t* d_ids) {                                                                                           \
+        (err).clear();                                                                                                                                        \
+        return koifish::Core(h)->ForwardLogits(d_ids, &(err));                                                                                                \
+    }
 
 // The gradient-clipping entries of a family, from one place: kfh_<fam>_set_grad_clip (mode 0 off, else kf_clip_mode; the reason of a refusal in the family's error
 // string `err`, which kfh_<fam>_last_error hands out), kfh_<fam>_grad_clip_scratch_bytes, kfh_<fam>_grad_norms (h_out: float [n_params + 1], the last one |g|).

@@ -11,7 +11,8 @@
 // Forward, per layer: RMSNorm (rstd kept) -> q, k, v products, each dense; q and k ARE the kept pre-norm copies -> the three blocks copied into the fused q | k | v rows
 // (kf_d2d_rows: kf_attn_backward takes ONE row stride for q, k and v, and GQA makes the blocks differ in width) -> kf_qknorm_rope_train in place on the fused rows
 // (rstd_q / rstd_k kept) -> kf_attn_prefill_batch_strided -> o_proj + residual -> RMSNorm -> gate, up -> kf_swiglu (gate and up kept) -> down + residual.  Then the final
-// RMSNorm, the head product and kf_fused_classifier with dloss = 1 / N.
+// RMSNorm, the head product and kf_fused_classifier with dloss = 1 / N (kf_distill_classifier under kfh_qwen3t_set_distill; kfh_qwen3t_forward_logits stops after the
+// head product: TrainerCore::SetDistill / ForwardLogits).
 // Backward, the reverse: every matrix through LinBack (a gama-registered one takes the gama branch); gate's and up's input gradients accumulate into one dh, q's, k's and
 // v's into one dh (accumulate_delta); dq | dk | dv of kf_attn_backward go through ONE kf_qknorm_rope_backward (RoPE^T + q/k-norm backward + the dense copies); the
 // embedding backward last, with no position table.
@@ -67,10 +68,9 @@ struct Qwen3Trainer : TrainerCore {
         return kf_norm_backward(ctx, dxx, w.g, nullptr, dout, inp, w.p, nullptr, rstd, N, dim, sc_ln);
     }
 
-    // per-row losses in `losses`, the logit gradients of the MEAN loss in `logits`
-    int Forward(const int32_t* d_ids, const int32_t* d_tgt) override {
-        KF_TRY(Ready());
-        if (!d_ids || !d_tgt) return KF_INVALID_ARGS;
+    TrainTensor& HeadTensor() override { return Head(); }
+    // the embedding, the layers and the final RMSNorm: hf.  TrainerCore::Forward and ForwardLogits go on from there
+    int Trunk(const int32_t* d_ids) override {
         KF_TRY(kf_embed_batch(ctx, &Wte().blob, d_ids, N, acts[0].x));
         for (int l = 0; l < NL; l++) {
             Q3Acts& a = acts[l];
@@ -90,8 +90,7 @@ struct Qwen3Trainer : TrainerCore {
             KF_TRY(kf_swiglu(ctx, a.gate, a.up, a.act, N * ffn));
             KF_TRY(Lin(P(l, DOWN_W), a.act, l + 1 < NL ? acts[l + 1].x : xf, a.x2));
         }
-        KF_TRY(Rms(xf, Nf(), hf, rf));
-        return HeadLoss(Head(), d_ids, d_tgt);
+        return Rms(xf, Nf(), hf, rf);
     }
     int Backward() override {
         KF_TRY(Ready());
@@ -215,5 +214,7 @@ int kfh_qwen3t_set_optimizer(void* h, int method, float lr_scale, float mui, flo
 long long kfh_qwen3t_steps_taken(void* h) { return Core(h)->t; }
 // gradient norms and clipping: TrainerCore::SetGradClip / GradClipScratchBytes / GradNorms (kf_train_common.hpp)
 KFH_GRAD_CLIP_ENTRIES(qwen3t, koifish::g_q3t_err)
+// distillation against a teacher's logits: TrainerCore::SetDistill / ForwardLogits
+KFH_DISTILL_ENTRIES(qwen3t, koifish::g_q3t_err)
 const char* kfh_qwen3t_last_error(void) { return koifish::g_q3t_err.c_str(); }
 }

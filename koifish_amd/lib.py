@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
     "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes", "kf_lora_apply", "kf_lora_apply_status",
-    "kf_evolve", "kf_loss_mean",
+    "kf_evolve", "kf_loss_mean", "kf_distill_classifier",
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
     "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
 ]
@@ -79,6 +79,8 @@ _TRAINER_ENTRIES = [
     ("set_grad_clip", [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_size_t], C.c_int),
     ("grad_clip_scratch_bytes", [C.c_void_p], C.c_size_t),
     ("grad_norms", [C.c_void_p, C.c_void_p, C.c_int], C.c_int),
+    ("set_distill", [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p], C.c_int),
+    ("forward_logits", [C.c_void_p, C.c_void_p], C.c_int),
 ]
 _libs = None
 
@@ -155,6 +157,8 @@ def load():
         hip.kf_gelu_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         hip.kf_swiglu_backward.argtypes = [C.c_void_p] * 5 + [C.c_size_t]
         hip.kf_fused_classifier.argtypes = [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        hip.kf_distill_classifier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int]
         hip.kf_gelu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         hip.kf_embed_batch.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int, C.c_void_p]
         hip.kf_qknorm_rope_batch.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]

@@ -21,6 +21,10 @@ Fish::ForwardOnRLS): the NL layers are cut into NL / layers_in_branch sections; 
 branch's (kf_evolve: particle swarm, particle swarm + genetic crossover, or a fixed mix) and re-quantises them; eval_loss scores one branch or the mean of all.  The
 schedule -- which branch trains when, which one is the head -- is the caller's loop over set_branch / step / evolve.
 
+set_distill(teacher, kd_weight, ce_weight, temperature) on either class turns the objective into ce_weight CE + kd_weight temperature^2 KL(teacher || student) on the
+logits (kf_distill_classifier in the fused classifier's place); the teacher is another trainer, whose forward_logits then runs first in every forward / step, or a
+tensor of logits the caller refills.
+
 The step keeps every activation (no recomputation).  Python here OWNS the device buffers (torch tensors: setup, outside any timed region) and registers them with
 koifish::GPT2Trainer (koifish_amd/host/kf_train.cpp, libkf_host.so), which sequences the step: forward / backward / update are one C call each, step() is ONE call,
 and nothing in them is a torch op (the embedding gather + add is kf_embed_pos, the attention reads q out of the fused rows, the zero fills are kf_memset / kf_memset2d).
@@ -56,6 +60,9 @@ class _TrainStep:
     _targets = ("weights", "gama")   # the train_target values the family offers
     optimizer = "adamw"
     _clip = None           # (gclip, mode) of set_grad_clip, None: off
+    _distill = None        # (teacher, "trainer" | "tensor") of set_distill, None: off
+    _kd = None             # the KL rows kf_distill_classifier writes, fp32 [B * T]
+    _n_sections = 1        # EOE layer sections (GPT2Step's layers_in_branch)
 
     def _begin(self, ctx, train_target, seed):
         """checks train_target before anything touches ctx; returns the device generator of the initial draws"""
@@ -215,6 +222,82 @@ class _TrainStep:
         self.grad_norms()
         return self._gnorm
 
+    # ---- distillation: the objective of every forward becomes ce_weight CE + kd_weight temperature^2 KL(teacher || student) (kf_distill_classifier)
+    @classmethod
+    def check_distill(cls, student, teacher, kd_weight=0.5, ce_weight=0.5, temperature=1.0):
+        """every argument error of set_distill as a ValueError, without a device.  student: the trainer (anything with ctx, B, T, N, V, Vp); teacher: another trainer of
+        any family on the same Context with equal B, T, V, Vp, or a bf16 tensor [B * T, >= V] on the student's device whose rows are 16-byte aligned (row stride a
+        multiple of 8, unit column stride).  Returns ("trainer" | "tensor", the teacher's row stride in elements)."""
+        for name, w in (("kd_weight", kd_weight), ("ce_weight", ce_weight), ("temperature", temperature)):
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or w != w or abs(w) == float("inf"):
+                raise ValueError("%s %r: a finite number" % (name, w))
+        if kd_weight < 0 or ce_weight < 0 or (kd_weight == 0 and ce_weight == 0):
+            raise ValueError("kd_weight %r, ce_weight %r: both >= 0 and not both zero" % (kd_weight, ce_weight))
+        if temperature <= 0:
+            raise ValueError("temperature %r: > 0" % (temperature,))
+        if teacher is student:
+            raise ValueError("set_distill: a trainer cannot be its own teacher (its logits buffer is where the gradient is written)")
+        if getattr(student, "_n_sections", 1) > 1:
+            raise ValueError("set_distill: a trainer with EOE layer sections (layers_in_branch) is not distilled: eval_loss shares the step's loss buffer")
+        if isinstance(teacher, _TrainStep):
+            if teacher.ctx is not student.ctx:
+                raise ValueError("set_distill: the teacher lives on another Context: both must share one (one device, one stream)")
+            for k in ("B", "T", "V", "Vp"):
+                if getattr(teacher, k) != getattr(student, k):
+                    raise ValueError("set_distill: the teacher's %s = %d, the student's %d" % (k, getattr(teacher, k), getattr(student, k)))
+            return "trainer", teacher.Vp
+        if not torch.is_tensor(teacher):
+            raise ValueError("set_distill: teacher %r is neither a trainer nor a tensor (None switches distillation off)" % (type(teacher).__name__,))
+        if teacher.dtype != torch.bfloat16 or teacher.dim() != 2:
+            raise ValueError("set_distill: teacher logits must be a 2-D bf16 tensor (got %s, %d-D)" % (teacher.dtype, teacher.dim()))
+        if teacher.shape[0] != student.N or teacher.shape[1] < student.V:
+            raise ValueError("set_distill: teacher logits %s: [%d, >= %d] wanted" % (tuple(teacher.shape), student.N, student.V))
+        if teacher.device != student.ctx.device:
+            raise ValueError("set_distill: teacher logits on %s, the trainer on %s" % (teacher.device, student.ctx.device))
+        ld = teacher.stride(0) if teacher.shape[0] > 1 else teacher.shape[1]
+        if teacher.stride(1) != 1 or ld < teacher.shape[1] or ld % 8 or teacher.data_ptr() % 16:
+            raise ValueError("set_distill: teacher rows must be 16-byte aligned: unit column stride, a row stride that is a multiple of 8 (got strides %s)" % (tuple(teacher.stride()),))
+        return "tensor", ld
+
+    def set_distill(self, teacher, kd_weight=0.5, ce_weight=0.5, temperature=1.0):
+        """Distil from a teacher's logits: every forward / step from here on ends in kf_distill_classifier, losses = ce_weight CE + kd_weight temperature^2
+        KL(softmax(teacher / temperature) || softmax(student / temperature)) per row, and the backward starts from that sum's gradient.  teacher: another trainer of
+        either family on the same Context with equal B, T, V, Vp -- its forward_logits(ids) then runs first in every forward / step, on the same stream; it is never
+        updated, and the gradient and moment buffers it carries are simply unused (an accepted cost: build the teacher with the cheapest storage that holds its weights)
+        -- or a bf16 device tensor [B * T, ld >= V] that the caller refills before every forward.  None switches distillation off: the plain path, bit for bit.
+        eval_loss is not offered under distillation, and a trainer with EOE layer sections is refused."""
+        if teacher is None:
+            self._call("set_distill", None, 0, 1.0, 0.0, 1.0, None, check=self._check_host)
+            self._distill = self._kd = None
+            return
+        kind, ld = self.check_distill(self, teacher, kd_weight, ce_weight, temperature)
+        rows = teacher.logits if kind == "trainer" else teacher
+        kd = torch.zeros(self.N, dtype=torch.float32, device=self.ctx.device)
+        self._call("set_distill", rows.data_ptr(), ld, ce_weight, kd_weight, temperature, kd.data_ptr(), check=self._check_host)
+        # only now: a refusal changes nothing in the trainer
+        self._distill, self._kd = (teacher, kind), kd
+
+    def forward_logits(self, ids):
+        """the forward through the head product only: raw bf16 logits in self.logits ([B * T, Vp]; the columns from V on are the padded vocabulary rows' products), no
+        loss, no gradient.  A backward after it is refused: it needs a forward."""
+        self._check_arena()
+        self._call("forward_logits", ids.data_ptr(), check=self._check_host)
+
+    def _teach(self, ids):
+        """a trainer as teacher: its logits of this batch, on the same stream, before the student's forward reads them"""
+        if self._distill is not None and self._distill[1] == "trainer":
+            self._distill[0].forward_logits(ids)
+
+    def kd_losses(self):
+        """KL(teacher || student) at the temperature of set_distill, per row of the last forward: fp32 [B * T] device tensor (a copy)"""
+        if self._distill is None:
+            raise L.KFError("kd_losses: no teacher is set (set_distill)")
+        return self._kd.clone()
+
+    def kd_loss(self):
+        """the mean of kd_losses() -- the one host read, made here and never inside forward / step"""
+        return float(self.kd_losses().mean())
+
     def close(self):
         if getattr(self, "h", None):
             if self._clip is not None and getattr(self.ctx, "h", None):
@@ -235,6 +318,7 @@ class _TrainStep:
         """ids, tgt: int32 [B * T] on the device.  Leaves the per-row losses in self.losses and the logit gradients (of the MEAN loss) in self.logits."""
         self._ids = ids   # kept alive: the backward reads them
         self._check_arena()
+        self._teach(ids)
         self._call("forward", ids.data_ptr(), tgt.data_ptr())
 
     def backward(self):
@@ -253,6 +337,7 @@ class _TrainStep:
         """forward + loss, backward, update + re-quantisation: ONE call into the host library"""
         self._ids = ids
         self._check_arena()
+        self._teach(ids)
         self._call("step", ids.data_ptr(), tgt.data_ptr(), lr, beta1, beta2, eps, wd, seed & 0xFFFFFFFF)
         self._after_update()
 
@@ -318,6 +403,7 @@ class GPT2Step(_TrainStep):
         self._attach((self.xf, self.hf, self.mf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.d4), (self._sc_ln, self._sc_at))
         if layers_in_branch:
             self._check_host(ctx.host.kfh_gpt2_set_branches(self.h, int(layers_in_branch)), "kfh_gpt2_set_branches")
+            self._n_sections = NL // int(layers_in_branch)
 
     # ---- EOE: layer-section branches
     @property
