@@ -842,6 +842,42 @@ int kf_linear_w4a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float
 int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok);
 int kf_linear_w4a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
 
+/* ---- int8 KV cache: quantised K / V rows and a decode attention whose scores are exact integer dots (the reference's switch DEBUG.T_kvcache_quant, QKV.cu:664, has a
+ * stub behind it).  Off unless called; the bf16 entries above are untouched.
+ * THE DEFINITION (restated in numpy by tests/kv8_restate.py):
+ *   storage, per layer: K8, V8 int8 [n_ctx][kv_stride] (kv_stride >= n_kv * hd bytes, a multiple of 16); KS, VS fp32 [n_ctx][n_kv]: one step per row and kv-head.  The
+ *     caller zero-fills all four at allocation: rows past the position are then finite, which is what the d_pos contract (kf_attn_block) asks of the bf16 cache too.
+ *   row quantiser, per token and kv-head over its hd elements: kf_act_quant_i8's arithmetic, unchanged -- amax = max_i |x_i|; step = amax / 127.0f (correctly rounded fp32
+ *     division); q_i = clamp(round_half_away(x_i / step), -127, 127); amax == 0: step = 0 and every q_i = 0.  K rows are quantised after q/k-norm + RoPE and their rounding
+ *     to bf16; V rows as the projection stores them (bf16).
+ *   decode attention, for query head h of kv-head kvh at position pos, keys t = 0 .. pos:
+ *     query    (q8, sq) = the row quantiser on the normed, roped bf16 query head;
+ *     integer  I_t = sum_i q8_i * k8[t][i] as int32;  |I_t| <= 128 * 127^2 < 2^24, so fp32(I_t) is exact;
+ *     score    c = sq * KS[t][kvh];  d = fp32(I_t) * c;  s_t = bf16_rn(d * rden), rden = 1.0f / sqrtf(hd) as the bf16 kernel's score multiplies by it: THREE separate fp32
+ *              multiplies, none fused with another;
+ *     weight   (f_t, n_t) = kf_exp2_parts(s_t * log2 e), p_t = f_t * 2^(n_t - m), m ANY integer >= every n it meets -- the canonical order of kf_attn_block;
+ *     value    g_t = f_t * VS[t][kvh]: ONE fp32 multiply, taken before the power-of-two scaling, so that it does not depend on m;
+ *     sums     fp64: L = sum_t p_t;  O[d] = sum_t ldexp((double)g_t * (double)v8[t][d], n_t - m): every term is exact (24 + 7 significant bits);
+ *     out      bf16_rn((float)(O[d] / L)).
+ *     The new row is quantised FIRST and attended in its quantised form like every other key.  There is ONE arithmetic: kf_set_canonical 0 and 1 give the same bits.
+ *   dequantised row (token batches): bf16_rn(fp32(q8) * step): one fp32 multiply, one rounding.
+ * kf_attn_block_kv8: kf_attn_block's contract on this cache in one launch -- q/k-norm + RoPE of the raw q [n_head * hd] and raw new key [n_kv * hd], the new K row and the
+ * raw new V row [n_kv * hd] quantised and written with their steps at the position, then the attention over keys 0 .. position; pos is the launch bound, d_pos (or NULL)
+ * the device word that holds the position (<= pos); scratch: kf_attn_scratch_bytes(), zero-filled once, shared with kf_attn_block (the counters return to zero).  The
+ * launch is the ATTN_DECODE_KV8 entry of kf::attn_plan (csrc/kf_attn_plan.h).  Refusals: a null pointer KF_INVALID_ARGS; query heads per kv-head other than 1, 2, 4, 8 or
+ * hd other than 64, 128 KF_INVALID_ARGS; K8 / V8 not 16-byte aligned or kv_stride % 16 != 0 KF_BLAS_UNALIGN.
+ * kf_attn_block_kv8_status: what the entry would answer for a shape, without a launch.
+ * kf_kv8_quant_rows: n bf16 K rows and n bf16 V rows [n_kv * hd], ld elements apart -> rows pos0 .. pos0 + n - 1 of K8 / V8 / KS / VS.
+ * kf_kv8_dequant_rows: rows 0 .. n - 1 of K8 / V8 -> bf16 kout / vout [n][n_kv * hd], ld_out elements apart. */
+int kf_attn_block_kv8_status(int n_head, int n_kv, int hd);
+int kf_attn_block_kv8(kf_ctx* ctx, const kf_bf16* q_raw, const kf_bf16* k_raw, const kf_bf16* v_raw, int8_t* k8, int8_t* v8, float* ks, float* vs, kf_bf16* out,
+                      const kf_bf16* wq_norm_or_null, const kf_bf16* wk_norm_or_null, const float* rope_table, int pos, const int32_t* d_pos_or_null, int n_head, int n_kv,
+                      int hd, int kv_stride, float eps, void* scratch);
+int kf_kv8_quant_rows(kf_ctx* ctx, const kf_bf16* k, const kf_bf16* v, int64_t ld, int n, int n_kv, int hd, int8_t* k8, int8_t* v8, float* ks, float* vs, int pos0,
+                      int kv_stride);
+int kf_kv8_dequant_rows(kf_ctx* ctx, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, kf_bf16* kout,
+                        kf_bf16* vout, int64_t ld_out);
+
 #ifdef __cplusplus
 }
 #endif

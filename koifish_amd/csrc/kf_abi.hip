@@ -743,6 +743,50 @@ int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16
     RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q_raw, out, 0, 0, 0))));
 }
 
+// ---- int8 KV cache (include/kf_abi.h): every launch decision is kf::attn_plan's ATTN_DECODE_KV8 entry
+static kf::AttnProblem kv8_problem(int n_head, int n_kv, int hd, int pos, long long kv_stride) {
+    return kf::AttnProblem{kf::ATTN_DECODE_KV8, n_head, n_kv, hd, pos, 1, 1, 1, 0, 0, 0, kv_stride};
+}
+int kf_attn_block_kv8_status(int n_head, int n_kv, int hd) { return kf::attn_plan(kv8_problem(n_head, n_kv, hd, 0, 0)).status; }
+int kf_attn_block_kv8(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, const kf_bf16* v_raw, int8_t* k8, int8_t* v8, float* ks, float* vs, kf_bf16* out,
+                      const kf_bf16* wq, const kf_bf16* wk, const float* table, int pos, const int32_t* d_pos, int n_head, int n_kv, int hd, int kv_stride, float eps,
+                      void* scratch) {
+    CHKCTX(c);
+    if (!q_raw || !k_raw || !v_raw || !k8 || !v8 || !ks || !vs || !out || !scratch || !table) return fail(KF_INVALID_ARGS, "kf_attn_block_kv8: null pointer");
+    if (!al16(k8) || !al16(v8)) return fail(KF_BLAS_UNALIGN, "kf_attn_block_kv8: cache not 16-byte aligned");
+    const kf::AttnPlan p = kf::attn_plan(kv8_problem(n_head, n_kv, hd, pos, kv_stride));
+    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_attn_block_kv8: kv_stride %d is not a multiple of 16", kv_stride);
+    if (p.status != KF_OK || kv_stride < n_kv * hd)
+        return fail(KF_INVALID_ARGS, "kf_attn_block_kv8: %d / %d heads x %d, pos %d, kv_stride %d: query heads per kv-head 1, 2, 4 or 8, head_dim 64 or 128, pos >= 0", n_head, n_kv,
+                    hd, pos, kv_stride);
+    kf::AttnKv8Args a;
+    memset(&a, 0, sizeof(a));
+    a.q = q_raw, a.k_raw = k_raw, a.v_raw = v_raw, a.k8 = k8, a.v8 = v8, a.ks = ks, a.vs = vs, a.out = out;
+    a.wq_norm = wq, a.wk_norm = wk, a.rope_table = table, a.eps = eps;
+    a.pos = pos, a.d_pos = d_pos, a.n_kv = n_kv, a.kv_stride = kv_stride;
+    a.counters = (int*)scratch, a.part = (double*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
+    RET(kf::attn_kv8_launch(c->stream, a, p));
+}
+static int kv8_rows_check(const char* entry, int n, int n_kv, int hd, int kv_stride) {
+    if (n < 1 || n_kv < 1 || (hd != 64 && hd != 128) || kv_stride < n_kv * hd) return fail(KF_INVALID_ARGS, "%s: n=%d n_kv=%d hd=%d kv_stride=%d", entry, n, n_kv, hd, kv_stride);
+    return KF_OK;
+}
+int kf_kv8_quant_rows(kf_ctx* c, const kf_bf16* k, const kf_bf16* v, int64_t ld, int n, int n_kv, int hd, int8_t* k8, int8_t* v8, float* ks, float* vs, int pos0, int kv_stride) {
+    CHKCTX(c);
+    if (!k || !v || !k8 || !v8 || !ks || !vs) return fail(KF_INVALID_ARGS, "kf_kv8_quant_rows: null pointer");
+    if (const int r = kv8_rows_check("kf_kv8_quant_rows", n, n_kv, hd, kv_stride)) return r;
+    if (pos0 < 0 || ld < (int64_t)n_kv * hd) return fail(KF_INVALID_ARGS, "kf_kv8_quant_rows: pos0=%d ld=%lld", pos0, (long long)ld);
+    RET(kf::kv8_quant_rows_launch(c->stream, k, v, ld, n, n_kv, hd, k8, v8, ks, vs, pos0, kv_stride));
+}
+int kf_kv8_dequant_rows(kf_ctx* c, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, kf_bf16* kout, kf_bf16* vout,
+                        int64_t ld_out) {
+    CHKCTX(c);
+    if (!k8 || !v8 || !ks || !vs || !kout || !vout) return fail(KF_INVALID_ARGS, "kf_kv8_dequant_rows: null pointer");
+    if (const int r = kv8_rows_check("kf_kv8_dequant_rows", n, n_kv, hd, kv_stride)) return r;
+    if (ld_out < (int64_t)n_kv * hd) return fail(KF_INVALID_ARGS, "kf_kv8_dequant_rows: ld_out=%lld", (long long)ld_out);
+    RET(kf::kv8_dequant_rows_launch(c->stream, k8, v8, ks, vs, n, n_kv, hd, kv_stride, kout, vout, ld_out));
+}
+
 int kf_swiglu(kf_ctx* c, const kf_bf16* gate, const kf_bf16* up, kf_bf16* out, int n) {
     CHKCTX(c);
     if (!gate || !up || !out || n <= 0) return fail(KF_INVALID_ARGS, "kf_swiglu: bad args");
@@ -1799,6 +1843,12 @@ int kfdbg_gemv_plan(const kf::GemvProblem* P, kf::GemvPlan* out) {
 int kfdbg_attn_plan(const kf::AttnProblem* P, kf::AttnPlan* out) {
     if (!P || !out) return -1;
     *out = kf::attn_plan(*P);
+    return 0;
+}
+// the plan of kf_attn_block_kv8 (the ATTN_DECODE_KV8 entry of kf::attn_plan; no HIP call): tests/test_kv8_cpu.py
+int kfdbg_kv8_plan(int n_head, int n_kv, int hd, int pos, int kv_stride, kf::AttnPlan* out) {
+    if (!out) return -1;
+    *out = kf::attn_plan(kv8_problem(n_head, n_kv, hd, pos, kv_stride));
     return 0;
 }
 // the plan kf::a8_plan makes for an integer mat-vec (no HIP call): tests/test_a8_plan_cpu.py

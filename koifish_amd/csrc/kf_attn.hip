@@ -132,72 +132,13 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
         // ---- the wave's key groups summed (reduce-scatter by row swaps), the waves through LDS: exact rescales to the slice's maximum exponent
         canon_wave_to_lds<GQ, LPK>(A, comb + (size_t)wave * GQ * PS, hd, lane, d0);
         __syncthreads();
-        for (int i = tid; i < GQ * hd; i += blockDim.x) {
-            const int hq = i >> hd_log2, d = i & (hd - 1);
-            float ms = -__builtin_inff();
-#pragma unroll
-            for (int sl = 0; sl < NW; sl++) ms = fmaxf(ms, (float)comb[((size_t)sl * GQ + hq) * PS + hd + 1]);
-            double o = 0.0, L = 0.0;
-#pragma unroll
-            for (int sl = 0; sl < NW; sl++) {
-                const double* c = comb + ((size_t)sl * GQ + hq) * PS;
-                const int e = canon_shift((float)c[hd + 1] - ms);
-                o += ldexp_d(c[d], e);
-                L += ldexp_d(c[hd], e);
-            }
-            if (nsp == 1) {
-                odst[(size_t)(h0 + hq) * hd + d] = f2bf((float)(o / L));
-            } else {
-                double* dst = part + ((size_t)(h0 + hq) * nsp + split) * PS;
-                __hip_atomic_store(dst + d, o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (d == 0) __hip_atomic_store(dst + hd, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_store(dst + hd + 1, (double)ms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        canon_slice_publish<GQ, NW, HD>(comb, part, odst, h0, nsp, split);
     } else if (nsp > 1) { /* empty slice: neutral partial, but it still arrives */
-        for (int i = tid; i < GQ * hd; i += blockDim.x) {
-            const int hq = i >> hd_log2, d = i & (hd - 1);
-            double* dst = part + ((size_t)(h0 + hq) * nsp + split) * PS;
-            __hip_atomic_store(dst + d, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (d == 0) __hip_atomic_store(dst + hd, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_store(dst + hd + 1, -(double)__builtin_inff(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        canon_slice_publish_empty<GQ, HD>(part, h0, nsp, split);
     }
     if (nsp == 1) return;
-
-    // ---- arrival; the last workgroup of this kv-head merges
-    int* const counter = a.counters + (int)blockIdx.y * a.cnt_stride; /* per (kv-head, part): its slices' workgroups meet here */
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        flag[0] = (old == nsp - 1);
-    }
-    __syncthreads();
-    if (!flag[0]) return;
-
-    // Every thread merges its output elements over the slices: the head is the same for the whole wave (64 | hd), lane sp of the wave fetches (m, L) of slice sp,
-    // the maximum exponent and the rescaled L are formed in registers; the element's own chain walks the slices in order (fp64: the order does not matter).
-    constexpr int NT = NW * 64;
-    constexpr int NV = (GQ * 128 + NT - 1) / NT; /* output elements per thread (hd <= 128) */
-#pragma unroll
-    for (int e = 0; e < NV; e++) {
-        const int i = tid + e * NT;
-        const bool in = i < GQ * hd;
-        const int hq = in ? (i >> hd_log2) : 0, d = i & (hd - 1);
-        const double* p = part + (size_t)(h0 + hq) * nsp * PS;
-        const bool mine = in && lane < nsp;
-        const float ms = mine ? (float)__hip_atomic_load(p + (size_t)lane * PS + hd + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -__builtin_inff();
-        const double ls = mine ? __hip_atomic_load(p + (size_t)lane * PS + hd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-        const float Mx = wave_max(ms);
-        const int sh = canon_shift(ms - Mx);
-        const double L = wave_sum_f64_fast(ldexp_d(ls, sh));
-        double o = 0.0;
-        for (int sp = 0; sp < nsp; sp++) {
-            const double v = in ? __hip_atomic_load(p + (size_t)sp * PS + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            o += ldexp_d(v, __builtin_amdgcn_readlane(sh, sp));
-        }
-        if (in) odst[(size_t)(h0 + hq) * hd + d] = f2bf((float)(o / L));
-    }
-    if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // ---- arrival; the last workgroup of this kv-head merges (kf_attn_common.h)
+    canon_arrive_and_merge<GQ, NW, HD>(part, a.counters + (int)blockIdx.y * a.cnt_stride, flag, odst, h0, nsp); /* per (kv-head, part): its slices' workgroups meet here */
 }
 
 // ---- the fp32 form of rounds 1-2 (kf_set_canonical(ctx, 0), the default): scores by v_dot2c_f32_bf16, exp by v_exp_f32(x * log2 e), a workgroup-wide running

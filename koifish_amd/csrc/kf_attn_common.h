@@ -292,6 +292,86 @@ __device__ __forceinline__ void canon_wave_to_lds(const CanonAcc<GQ>& A, double*
     }
 }
 
+// ---- the canonical order's slice bookkeeping behind canon_wave_to_lds, shared by attn_kernel (kf_attn.hip) and attn_kv8_kernel (kf_attn_kv8.hip): ONE body each, so the
+// hand-off cannot drift apart between them.  PS = hd + 2 doubles {O[hd], L, m} per (head, slice); h0 = the workgroup's first head; odst = the token's output row.
+// the waves' partials in LDS (comb [NW][GQ][PS], behind a barrier) rescaled exactly to the slice's maximum exponent and summed: the output itself when there is one slice,
+// else this slice's partial, written with agent-scope relaxed atomic stores
+template <int GQ, int NW, int HD>
+__device__ __forceinline__ void canon_slice_publish(const double* comb, double* part, uint16_t* odst, int h0, int nsp, int split) {
+    constexpr int hd = HD, hd_log2 = HD == 128 ? 7 : 6, PS = hd + 2;
+    for (int i = threadIdx.x; i < GQ * hd; i += blockDim.x) {
+        const int hq = i >> hd_log2, d = i & (hd - 1);
+        float ms = -__builtin_inff();
+#pragma unroll
+        for (int sl = 0; sl < NW; sl++) ms = fmaxf(ms, (float)comb[((size_t)sl * GQ + hq) * PS + hd + 1]);
+        double o = 0.0, L = 0.0;
+#pragma unroll
+        for (int sl = 0; sl < NW; sl++) {
+            const double* c = comb + ((size_t)sl * GQ + hq) * PS;
+            const int e = canon_shift((float)c[hd + 1] - ms);
+            o += ldexp_d(c[d], e);
+            L += ldexp_d(c[hd], e);
+        }
+        if (nsp == 1) {
+            odst[(size_t)(h0 + hq) * hd + d] = f2bf((float)(o / L));
+        } else {
+            double* dst = part + ((size_t)(h0 + hq) * nsp + split) * PS;
+            __hip_atomic_store(dst + d, o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (d == 0) __hip_atomic_store(dst + hd, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_store(dst + hd + 1, (double)ms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+// a slice behind the position: a neutral partial (it still arrives)
+template <int GQ, int HD>
+__device__ __forceinline__ void canon_slice_publish_empty(double* part, int h0, int nsp, int split) {
+    constexpr int hd = HD, hd_log2 = HD == 128 ? 7 : 6, PS = hd + 2;
+    for (int i = threadIdx.x; i < GQ * hd; i += blockDim.x) {
+        const int hq = i >> hd_log2, d = i & (hd - 1);
+        double* dst = part + ((size_t)(h0 + hq) * nsp + split) * PS;
+        __hip_atomic_store(dst + d, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (d == 0) __hip_atomic_store(dst + hd, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_store(dst + hd + 1, -(double)__builtin_inff(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// arrival, and the merge by the workgroup that arrives last for its (kv-head, part): every storing wave drains vmcnt, the workgroup barriers, ONE lane adds to the counter
+// (agent scope); the workgroup whose add returned nsp - 1 reads every partial with agent-scope relaxed atomic loads behind a barrier and re-zeroes the counter.  Every thread
+// merges its output elements over the slices: the head is the same for the whole wave (64 | hd), lane sp of the wave fetches (m, L) of slice sp, the maximum exponent and the
+// rescaled L are formed in registers; the element's own chain walks the slices in order (fp64: the order does not matter).
+template <int GQ, int NW, int HD>
+__device__ __forceinline__ void canon_arrive_and_merge(const double* part, int* counter, int* flag, uint16_t* odst, int h0, int nsp) {
+    constexpr int hd = HD, hd_log2 = HD == 128 ? 7 : 6, PS = hd + 2;
+    const int tid = threadIdx.x, lane = tid & 63;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        flag[0] = (old == nsp - 1);
+    }
+    __syncthreads();
+    if (!flag[0]) return;
+    constexpr int NT = NW * 64;
+    constexpr int NV = (GQ * 128 + NT - 1) / NT; /* output elements per thread (hd <= 128) */
+#pragma unroll
+    for (int e = 0; e < NV; e++) {
+        const int i = tid + e * NT;
+        const bool in = i < GQ * hd;
+        const int hq = in ? (i >> hd_log2) : 0, d = i & (hd - 1);
+        const double* p = part + (size_t)(h0 + hq) * nsp * PS;
+        const bool mine = in && lane < nsp;
+        const float ms = mine ? (float)__hip_atomic_load(p + (size_t)lane * PS + hd + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -__builtin_inff();
+        const double ls = mine ? __hip_atomic_load(p + (size_t)lane * PS + hd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        const float Mx = wave_max(ms);
+        const int sh = canon_shift(ms - Mx);
+        const double L = wave_sum_f64_fast(ldexp_d(ls, sh));
+        double o = 0.0;
+        for (int sp = 0; sp < nsp; sp++) {
+            const double v = in ? __hip_atomic_load(p + (size_t)sp * PS + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            o += ldexp_d(v, __builtin_amdgcn_readlane(sh, sp));
+        }
+        if (in) odst[(size_t)(h0 + hq) * hd + d] = f2bf((float)(o / L));
+    }
+    if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------------------------------ the same slice bookkeeping in fp32 (the engine's default mode)
 // Scores on packed bf16 pairs (v_dot2c_f32_bf16), weights p = v_exp_f32(s * log2 e - m) against an INTEGER reference exponent m (the ceiling of the wave's largest
 // s * log2 e), fp32 sums.  Integer exponents keep every rescale an exact power of two, so a wave's (O, L, m) meets the other waves' -- and the slices' in the fp64

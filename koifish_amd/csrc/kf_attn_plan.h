@@ -1,6 +1,6 @@
 // kf_attn_plan.h -- how attention is launched: kf::attn_plan, one pure host function, picks the route, kernel form, slices, grid, threads, LDS and scratch of every
-// attention launch (kf_attn_decode / kf_attn_block, kf_attn_prefill, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
-// kf_attn_prefill.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
+// attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
+// kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
 #pragma once
 #include "kf_kernels.h"
 
@@ -25,6 +25,9 @@ constexpr long ATTN_PAIR_MAX_WGS = 320;
 constexpr int ATTN_PAIR_MIN_TOK = 256;
 constexpr int AP_KT = 32, AP_KT_LONG = 64; /* keys per staged tile: tile kernel, paired form */
 constexpr int AP_VPAD = 32;                /* V row padding, elements (64 B): rows 4 apart in a transposing read land on distinct 16-bank groups (K rows: 8) */
+// the int8 cache (kf_attn_kv8.hip): a lane holds 16 elements of a key, so a key takes hd / 16 lanes and a wave step twice the keys of the bf16 kernel; the slices are
+// attn_slices' (one rule), 4 waves always, ATTN_KV8_U tiles in flight per wave: one 64-key slice of hd = 128 is one batch of the workgroup (4 waves x 8 keys x 2 tiles)
+constexpr int ATTN_KV8_NW = 4, ATTN_KV8_U = 2;
 
 // ---- the slice rule: slices, keys per slice and waves of the decode kernel for keys 0 .. pos_bound (one_slice: the per-token form)
 struct AttnSlices {
@@ -46,7 +49,7 @@ constexpr size_t attn_decode_scratch_bytes(int n_head, int hd) { return sizeof(d
 constexpr size_t attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return (T < 1 || n_head < 1 || n_seq < 1) ? 0 : sizeof(float) * 2 * (size_t)T * n_head * n_seq; }
 
 // ---- the problem
-enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3 };
+enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4 };
 enum { ATTN_Q_AL = 1, ATTN_OUT_AL = 2 }; /* q 16-byte aligned, out 8-byte aligned */
 struct AttnProblem {
     int entry, n_head, n_kv, hd;
@@ -59,7 +62,8 @@ struct AttnProblem {
 //   ATTN_PER_TOKEN  the same kernels on (1, n_kv * gq_split, n_tok), no scratch
 //   ATTN_TILE / ATTN_PAIRED  attn_prefill_kernel<hd, gq, kh, kt> on (blocks, n_kv, n_seq); kh = 2: a block from the front and one from the back per workgroup
 //   ATTN_BWD        attn_bwd_dq_mfma_kernel<hd> on grid, then attn_bwd_dkv_mfma_kernel<hd> on grid_kv
-enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4 };
+//   ATTN_SLICED_KV8 attn_kv8_kernel<gq, hd> on (n_splits, n_kv * gq_split, 1), ATTN_KV8_NW waves; slices, counters and scratch as ATTN_SLICED in the canonical order
+enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4, ATTN_SLICED_KV8 = 5 };
 struct AttnPlan {
     int status, route;             /* KF_OK or the refusal; the route (of a refusal: the one that refused) */
     int canon, gq, nw, hd, kh, kt; /* the kernel form; gq = query heads per workgroup */
@@ -80,6 +84,22 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         if (!hd_ok || !kv_ok) return refuse(KF_UNSUPPORTED_DATATYPE);
         p.grid[0] = p.grid_kv[0] = (P.n_tok + ATTN_TILE_COLS - 1) / ATTN_TILE_COLS, p.grid[1] = P.n_head, p.grid_kv[1] = P.n_kv, p.grid[2] = p.grid_kv[2] = P.n_seq;
         p.threads = 256, p.scratch = (long long)attn_backward_scratch_bytes(P.n_tok, P.n_head, P.n_seq);
+        return p;
+    }
+    if (P.entry == ATTN_DECODE_KV8) { /* one token against the int8 cache: ONE arithmetic (P.canon is not read), the canonical order's two query heads per workgroup */
+        p.route = ATTN_SLICED_KV8;
+        if (!hd_ok || !kv_ok || !gq_ok || P.pos < 0) return refuse(KF_INVALID_ARGS);
+        if (P.kv_stride & 15) return refuse(KF_BLAS_UNALIGN);
+        const AttnSlices s = attn_slices(P.pos, P.n_kv, GQ);
+        p.canon = 1, p.gq_split = GQ > ATTN_CANON_GQ_WG ? GQ / ATTN_CANON_GQ_WG : 1;
+        p.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (P.n_kv * p.gq_split);
+        if (p.cnt_stride > ATTN_CNT_STRIDE_MAX) p.cnt_stride = ATTN_CNT_STRIDE_MAX;
+        if (p.cnt_stride < 1) return refuse(KF_INVALID_ARGS);
+        p.gq = GQ / p.gq_split, p.nw = ATTN_KV8_NW, p.n_splits = s.n_splits, p.chunk = s.chunk, p.threads = 64 * ATTN_KV8_NW;
+        p.grid[0] = s.n_splits, p.grid[1] = P.n_kv * p.gq_split, p.grid[2] = 1;
+        // the waves' {O[hd], L, m} doubles; prepared q heads + the new key (bf16); their int8 codes + the new K and V rows' codes; the gq + 2 steps and the flag
+        p.lds = (int)(sizeof(double) * ((size_t)ATTN_KV8_NW * p.gq * (P.hd + 2)) + sizeof(uint16_t) * ((size_t)p.gq * P.hd + P.hd) + ((size_t)p.gq * P.hd + 2 * P.hd) + 4 * (p.gq + 2) + 16);
+        p.scratch = (long long)attn_decode_scratch_bytes(P.n_head, P.hd);
         return p;
     }
     // the tile kernel: 16-byte q and K / V rows, 8-byte out rows
@@ -121,5 +141,29 @@ int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* 
 int attn_backward_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o,
                               const uint16_t* dO, long long ld_o, uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, int T, float* scratch, long long ld_kv,
                               long long ld_dkv); /* kf_attn_bwd_mfma.hip, ATTN_BWD */
+// the int8 cache (kf_attn_kv8.hip): ATTN_SLICED_KV8, and the two row kernels (no plan: one wave per (row, kv-head), one workgroup per row)
+struct AttnKv8Args {
+    const uint16_t* q;     /* raw q [n_head * hd] */
+    const uint16_t* k_raw; /* raw new key [n_kv * hd] */
+    const uint16_t* v_raw; /* new value row [n_kv * hd] */
+    int8_t* k8;
+    int8_t* v8;
+    float* ks;
+    float* vs;
+    const uint16_t* wq_norm;
+    const uint16_t* wk_norm;
+    const float* rope_table;
+    double* part;  /* [n_head][n_splits][hd + 2] fp64 partials {O, L, m} */
+    int* counters; /* per (kv-head, part), zero between launches */
+    uint16_t* out;
+    const int* d_pos;
+    int pos, n_kv, kv_stride, n_splits, chunk, cnt_stride, gq_split;
+    float eps, inv_sqrt_hd_den;
+};
+int attn_kv8_launch(hipStream_t st, AttnKv8Args& a, const AttnPlan& p);
+int kv8_quant_rows_launch(hipStream_t st, const uint16_t* k, const uint16_t* v, long long ld, int n, int n_kv, int hd, int8_t* k8, int8_t* v8, float* ks, float* vs, int pos0,
+                          int kv_stride);
+int kv8_dequant_rows_launch(hipStream_t st, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, uint16_t* kout,
+                            uint16_t* vout, long long ld_out);
 
 }  // namespace kf

@@ -53,6 +53,24 @@ int KVCache::Init(kf_ctx* c, int nl, int ms, int kvd) {
     val = GT(c, "kv.val", typNUMBER::BF16, nl * ms, kvd);
     return (key && val) ? KF_OK : KF_OUTOF_GPUMEMORY;
 }
+static hGTensor gt_bytes(kf_ctx* c, const std::string& name, typNUMBER tp, int n0, int n1, size_t bytes) { /* a zero-filled tensor of a type GT does not size */
+    auto t = std::make_shared<GTensor>();
+    t->name = name, t->type = tp, t->ne[0] = n0, t->ne[1] = n1, t->szData = bytes;
+    if (t->Alloc(c, bytes) != KF_OK) return nullptr;
+    kf_memset(c, t->data, 0, bytes);
+    return t;
+}
+int KVCache::Init8(kf_ctx* c, int nkv) {
+    if (k8) return KF_OK;
+    n_kv = nkv;
+    const int rows = n_layer * max_seq_len;
+    hGTensor a = gt_bytes(c, "kv.k8", typNUMBER::I8, rows, kv_dim, (size_t)rows * kv_dim), b = gt_bytes(c, "kv.v8", typNUMBER::I8, rows, kv_dim, (size_t)rows * kv_dim);
+    hGTensor sa = GT(c, "kv.ks", typNUMBER::F32, rows, nkv), sb = GT(c, "kv.vs", typNUMBER::F32, rows, nkv);
+    hGTensor ta = GT(c, "kv.stage_k", typNUMBER::BF16, max_seq_len, kv_dim), tb = GT(c, "kv.stage_v", typNUMBER::BF16, max_seq_len, kv_dim);
+    if (!a || !b || !sa || !sb || !ta || !tb) return KF_OUTOF_GPUMEMORY;
+    k8 = a, v8 = b, ks = sa, vs = sb, stage_k = ta, stage_v = tb;
+    return KF_OK;
+}
 void* KVCache::Get(CTYPE type, int layer, int pos) const {
     floatX* base = ToX(type == KV_KEY ? key : val);
     return base + ((size_t)layer * max_seq_len + pos) * kv_dim;
@@ -158,6 +176,19 @@ hGTensor SelfAttention::cuInfer(hGTensor inpL, int) {
     // fused: [norm + Q,K,V] -> [q/k-norm + RoPE + attention] -> [proj_cat + residual]
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
     const kf_weight* ws[3] = {&wq, &wk, &wv};
+    if (f->kv_int8) {  // int8 KV cache: q, the raw k and the raw v into scratch rows (no row of the cache is aliased), then [q/k-norm + RoPE + quantise the new rows +
+                       // integer-score attention] in one launch; graph mode works as below: the position comes from d_pos, the bound fixes the slices
+        kf_bf16* y8[3] = {ToX(Q.out), ToX(f->gBUFF.kraw), ToX(f->gBUFF.vraw)};
+        const int64_t none[3] = {0, 0, 0};
+        if (kf_norm_linear(c, ToX(inpL), ToX(norm.w), norm.rms_eps, 3, ws, y8, none, bound, d_pos) != KF_OK) return nullptr;
+        if (kf_attn_block_kv8(c, ToX(Q.out), ToX(f->gBUFF.kraw), ToX(f->gBUFF.vraw), hCache->Codes(KVCache::KV_KEY, L), hCache->Codes(KVCache::KV_VAL, L),
+                              hCache->Steps(KVCache::KV_KEY, L), hCache->Steps(KVCache::KV_VAL, L), ToX(f->gBUFF.scratch), normQ.w ? ToX(normQ.w) : nullptr,
+                              normK.w ? ToX(normK.w) : nullptr, f->rope_table, bound, d_pos, n_head, n_head_kv, head_dim, kv_dim, normQ.rms_eps,
+                              f->gBUFF.attn_ws->data) != KF_OK)
+            return nullptr;
+        if (kf_linear(c, &wo, ToX(f->gBUFF.scratch), ToX(out), nullptr, 1, 1.0f, 0.0f, KF_EPI_RESIDUAL, ToX(inpL)) != KF_OK) return nullptr;
+        return out;
+    }
     kf_bf16* ys[3] = {ToX(Q.out), ToX(f->gBUFF.kraw), val_cache};
     const int64_t strides[3] = {0, 0, (int64_t)kv_dim};
     if (kf_norm_linear(c, ToX(inpL), ToX(norm.w), norm.rms_eps, 3, ws, ys, strides, bound, d_pos) != KF_OK) return nullptr;
@@ -238,6 +269,18 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
         return (f->*group)(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
     }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
+    if (f->kv_int8) {  // int8 KV cache: the batch's K / V rows into the staging pair, quantised into the cache, then rows 0 .. pos0 + n - 1 dequantised over the staging
+                       // pair -- every key, the batch's own included, is attended in its dequantised form -- and the existing prompt attention on the staging pair
+        floatX *sk = ToX(hCache->stage_k), *sv = ToX(hCache->stage_v);
+        int8_t *k8 = hCache->Codes(KVCache::KV_KEY, L), *v8 = hCache->Codes(KVCache::KV_VAL, L);
+        float *ks = hCache->Steps(KVCache::KV_KEY, L), *vs = hCache->Steps(KVCache::KV_VAL, L);
+        KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, sk + (size_t)pos0 * kv_dim, sv + (size_t)pos0 * kv_dim, n, normQ.w ? ToX(normQ.w) : nullptr,
+                                 normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv, head_dim, normQ.rms_eps));
+        KF_TRY(kf_kv8_quant_rows(c, sk + (size_t)pos0 * kv_dim, sv + (size_t)pos0 * kv_dim, kv_dim, n, n_head_kv, head_dim, k8, v8, ks, vs, pos0, kv_dim));
+        KF_TRY(kf_kv8_dequant_rows(c, k8, v8, ks, vs, pos0 + n, n_head_kv, head_dim, kv_dim, sk, sv, kv_dim));
+        KF_TRY(kf_attn_prefill(c, bq, sk, sv, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
+        return kf_linear(c, &wo, ba, bx, nullptr, n, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx);
+    }
     KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, krows, vrows, n, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv,
                              head_dim, normQ.rms_eps));
     KF_TRY(kf_attn_prefill(c, bq, key_cache, val_cache, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
@@ -454,6 +497,10 @@ int Fish::SetActInt8(bool on, std::string& why) {
             why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
             return KF_INVALID_ARGS;
         }
+        if (kv_int8) {
+            why = "the int8 KV cache is on and its layer body has no int8-activation form: switch kfh_set_kv_int8 off first";
+            return KF_INVALID_ARGS;
+        }
         int n8 = 0;
         std::vector<uint16_t> zero;
         for (int l = 0; l < config.nLayer; l++) {
@@ -506,6 +553,10 @@ int Fish::SetActInt8Q4(bool on, std::string& why) {
             why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
             return KF_INVALID_ARGS;
         }
+        if (kv_int8) {
+            why = "the int8 KV cache is on and its layer body has no int8-activation form: switch kfh_set_kv_int8 off first";
+            return KF_INVALID_ARGS;
+        }
         int n4 = 0;
         for (int l = 0; l < config.nLayer; l++) {
             SelfAttention* a = attn[l].get();
@@ -536,6 +587,46 @@ int Fish::SetActInt8Q4(bool on, std::string& why) {
     return KF_OK;
 }
 
+// ---- int8 KV cache (kfh_set_kv_int8)
+int Fish::SetKVInt8(bool on, std::string& why) {
+    if (on) {
+        if (tp.world > 1) {
+            why = "this Fish is a tensor-parallel rank: the TP step has no int8 KV cache form";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
+        if (act_int8) {
+            why = "int8 activations are on and their layer body has no int8 KV cache form: switch kfh_set_act_int8 / kfh_set_act_int8_q4 off first";
+            return KF_INVALID_ARGS;
+        }
+        if (n_adapters > 0) {
+            why = "low-rank adapters are attached and their layer body has no int8 KV cache form: clear the adapters first";
+            return KF_INVALID_ARGS;
+        }
+        if (masked_layers > 0) {
+            why = "a hot-row mask is set: the sparse forward has no int8 KV cache form";
+            return KF_INVALID_ARGS;
+        }
+        if (fuse_level == 0) {
+            why = "fuse_level 0 (one launch per reference kernel) has no int8 KV cache form: kfh_set_fuse_level(1) first";
+            return KF_INVALID_ARGS;
+        }
+        if (const int st = kf_attn_block_kv8_status(config.n_head, config.n_head_kv, config.head_dim)) {
+            why = "kf_attn_block_kv8 refuses " + std::to_string(config.n_head) + " / " + std::to_string(config.n_head_kv) + " heads x " + std::to_string(config.head_dim);
+            return st;
+        }
+        if (!cache.k8) KF_TRY(kf_sync(ctx)); /* never inside a launch sequence */
+        KF_TRY(cache.Init8(ctx, config.n_head_kv));
+        if (!gBUFF.vraw) gBUFF.vraw = GT(ctx, "vraw", typNUMBER::BF16, config.n_head_kv * config.head_dim);
+        if (!gBUFF.vraw) return KF_OUTOF_GPUMEMORY;
+    }
+    if (kv_int8 != on) {
+        kv_int8 = on;
+        DropEngineTable(); /* as A8Switched: the captured graphs and the engine belong to the other cache */
+        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use, and refuse */
+    }
+    return KF_OK;
+}
+
 // ---- low-rank adapters at inference (kfh_set_adapter / kfh_clear_adapters)
 SLP* Fish::LayerMatrix(int layer, int slot) {
     if (layer < 0 || layer >= config.nLayer) return nullptr;
@@ -560,6 +651,10 @@ int Fish::SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int 
     }
     if (masked_layers > 0) {
         why = "adapters: a hot-row mask is set and the sparse forward applies no adapters: clear it first";
+        return KF_INVALID_ARGS;
+    }
+    if (kv_int8) {
+        why = "adapters: the int8 KV cache is on and its layer body applies no adapters: switch kfh_set_kv_int8 off first";
         return KF_INVALID_ARGS;
     }
     if (!std::isfinite(s)) {
@@ -682,6 +777,10 @@ int Fish::EnsureEngine() {
         engine_why = "low-rank adapters are attached: they run on the per-layer launches";
         return KF_ENGINE_NOT_SERVED;
     }
+    if (kv_int8) {
+        engine_why = "int8 KV cache runs on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
     KF_TRY(EngineTable(ToX(cache.key), ToX(cache.val), true, engine_why, L, d));
@@ -801,6 +900,10 @@ int Fish::TPInit(int rank, int world, int vocab_row0) {
     }
     if (n_adapters > 0) { /* nor one that applies adapters */
         g_host_err = "kfh_tp_init: low-rank adapters are attached and the tensor-parallel step applies no adapters: clear the adapters first";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
+    if (kv_int8) { /* nor one on the int8 cache */
+        g_host_err = "kfh_tp_init: the int8 KV cache is on and the tensor-parallel step has no int8 KV cache form: switch kfh_set_kv_int8 off first";
         return KF_UNSUPPORTED_DATATYPE;
     }
     std::memset(&tp.comm, 0, sizeof(tp.comm));
@@ -1268,6 +1371,10 @@ int XcdReplicas::MakeEngine(bool allocate) {
         why = "low-rank adapters are attached: the XCD engines apply no adapters";
         return KF_ENGINE_NOT_SERVED;
     }
+    if (f->kv_int8) {
+        why = "int8 KV cache runs on the per-layer launches";
+        return KF_ENGINE_NOT_SERVED;
+    }
     KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
     {
         char w[320];
@@ -1319,7 +1426,9 @@ int XcdReplicas::Fresh() {
         KF_TRY(kf_sync(ctx));
         kf_xengine_destroy(engine), engine = nullptr;
     }
-    return MakeEngine(false); /* caches, states, forced ids and ids out stay: the sequences go on where they stand, on the new weights */
+    const int rc = MakeEngine(false); /* caches, states, forced ids and ids out stay: the sequences go on where they stand, on the new weights */
+    if (rc != KF_OK) g_host_err = "XcdReplicas: " + why; /* a switch moved on the Fish since the engine was built (int8 activations, adapters, the int8 KV cache): kfh_host_error says which */
+    return rc;
 }
 int XcdReplicas::SetForced(int seq, const int32_t* ids, int n) {
     if (seq < 0 || seq >= n_seq || n < 0 || n > hFish->config.n_ctx) return KF_INVALID_ARGS;
@@ -1612,6 +1721,10 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "low-rank adapters are attached: the XCD engines apply no adapters";
             return KF_ENGINE_NOT_SERVED;
         }
+        if (f->kv_int8) {
+            why = "int8 KV cache runs on the per-layer launches";
+            return KF_ENGINE_NOT_SERVED;
+        }
         KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
         ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
         dp[r] = &ds[r];
@@ -1703,7 +1816,12 @@ void kfh_destroy(void* h) { delete reinterpret_cast<Fish*>(h); }
 const char* kfh_host_error(void) { return g_host_err.c_str(); } /* why the last kfh_create failed */
 void* kfh_ctx(void* h) { return reinterpret_cast<Fish*>(h)->ctx; }
 int kfh_set_fuse_level(void* h, int lvl) {
-    reinterpret_cast<Fish*>(h)->fuse_level = lvl;
+    Fish* f = reinterpret_cast<Fish*>(h);
+    if (lvl == 0 && f->kv_int8) { /* the per-kernel sequence has no int8 KV cache form */
+        g_host_err = "kfh_set_fuse_level: the int8 KV cache is on and fuse_level 0 has no int8 KV cache form: switch kfh_set_kv_int8 off first";
+        return KF_INVALID_ARGS;
+    }
+    f->fuse_level = lvl;
     return KF_OK;
 }
 // sparse forward: h_hot[ffn] (1 = hot, CS_Picker::hot) for one layer's FFN, NULL = dense again.  The mask becomes a device row list here (load time).
@@ -1718,6 +1836,10 @@ int kfh_set_hot(void* h, int layer, const int32_t* h_hot, int n) {
     }
     if (h_hot && f->n_adapters > 0) { /* nor a form that applies adapters */
         g_host_err = "kfh_set_hot: low-rank adapters are attached and the sparse forward applies no adapters: clear the adapters first";
+        return KF_INVALID_ARGS;
+    }
+    if (h_hot && f->kv_int8) { /* nor one on the int8 cache */
+        g_host_err = "kfh_set_hot: the int8 KV cache is on and the sparse forward has no int8 KV cache form: switch kfh_set_kv_int8 off first";
         return KF_INVALID_ARGS;
     }
     f->DropEngineTable(); /* the engine's layer table (and the captured graphs) hold the masks: rebuilt on the next step; the resident bf16 copies and the measured delays do not
@@ -1762,6 +1884,22 @@ int kfh_set_act_int8_q4(void* h, int on) {
     const int rc = reinterpret_cast<Fish*>(h)->SetActInt8Q4(on != 0, g_host_err);
     if (rc != KF_OK) g_host_err = "kfh_set_act_int8_q4: " + g_host_err;
     return rc;
+}
+// the int8 KV cache: on / off (off: today's routes on the bf16 cache, bit for bit).  The two caches are independent -- switching converts nothing, the caller prefills again.
+// A refusal leaves the switch as it was; kfh_host_error says why.  kfh_kv8_*: the int8 pair and its steps on the device (NULL before the first switch-on).
+int kfh_set_kv_int8(void* h, int on) {
+    const int rc = reinterpret_cast<Fish*>(h)->SetKVInt8(on != 0, g_host_err);
+    if (rc != KF_OK) g_host_err = "kfh_set_kv_int8: " + g_host_err;
+    return rc;
+}
+int kfh_kv_int8(void* h) { return reinterpret_cast<Fish*>(h)->kv_int8 ? 1 : 0; }
+void* kfh_kv8_codes(void* h, int val) {
+    const KVCache& kc = reinterpret_cast<Fish*>(h)->cache;
+    return kc.k8 ? (val ? kc.v8 : kc.k8)->data : nullptr;
+}
+void* kfh_kv8_steps(void* h, int val) {
+    const KVCache& kc = reinterpret_cast<Fish*>(h)->cache;
+    return kc.k8 ? (val ? kc.vs : kc.ks)->data : nullptr;
 }
 // a low-rank adapter beside layer matrix `slot` (0 q, 1 k, 2 v, 3 o, 4 gate, 5 up, 6 down): a [r, in], b [out, r] bf16 DEVICE pointers, no copy (the caller keeps them alive and
 // may update them in place: every launch reads them); s multiplies both products, one rank and one s per model.  While any is attached decode, prefill, score and perplexity

@@ -70,6 +70,14 @@ struct KVCache {
     int n_layer = 0, max_seq_len = 0, kv_dim = 0;
     int Init(kf_ctx* c, int n_layer, int max_seq, int kv_dim);
     void* Get(CTYPE type, int layer, int pos) const;  // Cache.cpp:42-57
+    // the int8 pair (include/kf_abi.h "int8 KV cache"; the reference's DEBUG.T_kvcache_quant, QKV.cu:664): k8 / v8 int8 [n_layer, max_seq, kv_dim], ks / vs fp32
+    // [n_layer, max_seq, n_kv], zero-filled; stage_k / stage_v bf16 [max_seq, kv_dim]: the rows a token batch attends to (its own rows, then every row dequantised).
+    // Allocated by the first switch-on (Fish::SetKVInt8) and kept; the bf16 pair above stays allocated beside it (engine tables and captured graphs hold its addresses).
+    hGTensor k8, v8, ks, vs, stage_k, stage_v;
+    int n_kv = 0;
+    int Init8(kf_ctx* c, int n_kv);
+    int8_t* Codes(CTYPE type, int layer) const { return reinterpret_cast<int8_t*>((type == KV_KEY ? k8 : v8)->data) + (size_t)layer * max_seq_len * kv_dim; }
+    float* Steps(CTYPE type, int layer) const { return reinterpret_cast<float*>((type == KV_KEY ? ks : vs)->data) + (size_t)layer * max_seq_len * n_kv; }
 };
 
 struct GeNeuron {
@@ -156,6 +164,7 @@ struct MODEL_CARD {  // the fields of CLI_params / MODEL_CARD this path reads (C
 struct MemBuffer {
     hGTensor tmpFF1;    // Q.out
     hGTensor kraw;      // new key before norm/rope (fused path)
+    hGTensor vraw;      // new value row before it is quantised (int8 KV cache; allocated by the first switch-on)
     hGTensor scratch;   // proj_cat out / gate-act
     hGTensor delta;     // down out
     hGTensor upOut;     // up out (unfused path)
@@ -350,6 +359,13 @@ struct Fish : SeqBuffers {
     // hot-row mask (and each of those while an adapter is attached), save_kun, a rank or shape kf_lora_apply_status refuses.
     int n_adapters = 0, lora_r = 0;
     float lora_s = 0.0f;
+    // int8 KV cache (kfh_set_kv_int8; include/kf_abi.h "int8 KV cache"): K / V rows live as int8 codes with one fp32 step per row and kv-head; a decode step runs
+    // kf_norm_linear (q, raw k, raw v into scratch rows) -> kf_attn_block_kv8 -> kf_linear per layer -- still 5 launches with the FFN's two, eager or on captured graphs
+    // (d_pos, position buckets) like any model the engine does not serve; token batches quantise their rows into the cache and attend to the dequantised rows of the
+    // staging pair (kf_kv8_quant_rows, kf_kv8_dequant_rows, then the existing kf_attn_prefill).  The two caches are independent: switching converts nothing, the caller
+    // prefills again.  Refused with a reason, in both directions: a TP rank, the XCD objects, int8 activations, adapters, hot-row masks, fuse_level 0.
+    bool kv_int8 = false;
+    int SetKVInt8(bool on, std::string& why);
     bool per_layer() const { return act_int8 || n_adapters > 0; }  // what the step sequencing asks: eager per-layer launches, no engine, no graphs
     SLP* LayerMatrix(int layer, int slot);  // q k v o gate up down = 0 .. 6, or NULL
     int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);

@@ -372,6 +372,27 @@ class Context:
         L.check(self.hip.kf_act_quant_i8(self.h, _ptr(x), ldx, _ptr(norm_w), eps, rows, dim, _ptr(q), _ptr(step)), "kf_act_quant_i8")
         return q, step
 
+    def kv8_quant_rows(self, k, v, k8, v8, ks, vs, pos0, n_kv, hd):
+        """kf_kv8_quant_rows: k, v bf16 [n, n_kv * hd] (a row stride larger than that is honoured) -> rows pos0 .. pos0 + n - 1 of k8 / v8 int8 [n_ctx, kv_stride] and of
+        ks / vs fp32 [n_ctx, n_kv], in place"""
+        assert k.dim() == 2 and k.stride(1) == 1 and k.stride() == v.stride() and k.dtype == v.dtype == torch.bfloat16
+        L.check(self.hip.kf_kv8_quant_rows(self.h, _ptr(k), _ptr(v), k.stride(0), k.shape[0], n_kv, hd, _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), pos0, k8.stride(0)),
+                "kf_kv8_quant_rows")
+
+    def kv8_dequant_rows(self, k8, v8, ks, vs, n, n_kv, hd, kout, vout):
+        """kf_kv8_dequant_rows: rows 0 .. n - 1 of the int8 pair -> kout, vout bf16 [n, n_kv * hd] (their row stride is honoured), in place"""
+        assert kout.stride() == vout.stride() and kout.stride(1) == 1
+        L.check(self.hip.kf_kv8_dequant_rows(self.h, _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), n, n_kv, hd, k8.stride(0), _ptr(kout), _ptr(vout), kout.stride(0)),
+                "kf_kv8_dequant_rows")
+
+    def attn_block_kv8(self, q_raw, k_raw, v_raw, k8, v8, ks, vs, wq, wk, table, pos, n_head, n_kv, hd, eps=1e-6, d_pos=None, ws=None):
+        """kf_attn_block_kv8: kf_attn_block's contract on the int8 cache -- the new K / V rows are quantised and written (with their steps) at the position; pos is the
+        launch bound when d_pos (an int32 device tensor holding the position) is given"""
+        out = torch.empty(n_head * hd, dtype=torch.bfloat16, device=self.device)
+        L.check(self.hip.kf_attn_block_kv8(self.h, _ptr(q_raw), _ptr(k_raw), _ptr(v_raw), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(out), _ptr(wq), _ptr(wk), _ptr(table),
+                                           pos, _ptr(d_pos), n_head, n_kv, hd, k8.stride(0), eps, _ptr(ws if ws is not None else self._ws(n_head, hd))), "kf_attn_block_kv8")
+        return out
+
     def linear_a8(self, w, q, step, bias=None, residual=None, y=None):
         """kf_linear_a8: a ternary / 1-bit weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
         n = 1 if q.dim() == 1 else q.shape[0]
@@ -625,7 +646,9 @@ class Qwen3:
         L.check(self.host.kfh_set_norm(self.h, layer, slot, C.c_void_p(w_bf16.data_ptr()), w_bf16.numel(), 1), "kfh_set_norm")
 
     def set_fuse_level(self, lvl):
-        self.host.kfh_set_fuse_level(self.h, lvl)
+        rc = self.host.kfh_set_fuse_level(self.h, lvl)
+        if rc != 0:   # refused only while the int8 KV cache is on
+            raise L.KFError("set_fuse_level failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
 
     def set_hot(self, layer, hot):
         """sparse forward (D_matmul_sparse / CS_Picker::hot): hot[ffn] int32 host array, 1 = the FFN row of gate / up is computed; None = dense"""
@@ -635,7 +658,7 @@ class Qwen3:
             return
         a = np.ascontiguousarray(hot, dtype=np.int32)
         rc = self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size)
-        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False) or getattr(self, "_adapters", None)):   # the refusals the host explains: a mask while int8 activations are on or adapters are attached (the text is set on those paths only)
+        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False) or getattr(self, "_adapters", None) or self.kv_int8()):   # the refusals the host explains: a mask while int8 activations are on or adapters are attached (the text is set on those paths only)
             raise L.KFError("kfh_set_hot failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         L.check(rc, "kfh_set_hot")
         if not hasattr(self, "_hot"):
@@ -665,6 +688,33 @@ class Qwen3:
         if rc != 0:
             raise L.KFError("set_act_int8_q4 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         self._act_int8_q4 = bool(on)
+
+    def set_kv_int8(self, on):
+        """The int8 KV cache (include/kf_abi.h "int8 KV cache"): K / V rows as int8 codes with one fp32 step per row and kv-head, decode attention on exact integer scores
+        (kf_attn_block_kv8), token batches on the dequantised rows; forward, run_steps, generate (graphs included), prefill, score and perplexity, on per-layer launches
+        (engine_why() says so).  The two caches are independent: switching converts nothing, prefill again.  Raises with the reason on a TP rank, with int8 activations,
+        adapters, a hot-row mask or fuse_level 0."""
+        rc = self.host.kfh_set_kv_int8(self.h, int(bool(on)))
+        if rc != 0:
+            raise L.KFError("set_kv_int8 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+
+    def kv_int8(self):
+        return bool(self.host.kfh_kv_int8(self.h))
+
+    def kv8_to_host(self):
+        """the int8 cache copied to the host: (k8 int8 [n_layer, max_seq, kv_dim], ks fp32 [n_layer, max_seq, n_kv], v8, vs); allocated by the first set_kv_int8(True)"""
+        c = self.cfg
+        kvd, rows = c["n_kv"] * c["head_dim"], c["n_layer"] * c["max_seq"]
+        ctx = C.c_void_p(self.host.kfh_ctx(self.h))
+        out = []
+        for val in (0, 1):
+            codes, steps = np.zeros(rows * kvd, dtype=np.int8), np.zeros(rows * c["n_kv"], dtype=np.float32)
+            for a, p in ((codes, self.host.kfh_kv8_codes(self.h, val)), (steps, self.host.kfh_kv8_steps(self.h, val))):
+                if not p:
+                    raise L.KFError("kv8_to_host: the int8 cache is allocated by the first set_kv_int8(True)")
+                L.check(self.hip.kf_d2h(ctx, a.ctypes.data_as(C.c_void_p), C.c_void_p(p), C.c_size_t(a.nbytes)), "kf_d2h")
+            out += [codes.reshape(c["n_layer"], c["max_seq"], kvd), steps.reshape(c["n_layer"], c["max_seq"], c["n_kv"])]
+        return tuple(out)
 
     @classmethod
     def check_adapters(cls, cfg, adapters, lora_s):
