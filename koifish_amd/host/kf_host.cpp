@@ -143,20 +143,19 @@ hGTensor SelfAttention::cuInfer(hGTensor inpL, int) {
     f->gBUFF.residual = inpL;
     const int32_t* d_pos = f->graph_mode ? f->d_state + 1 : nullptr;
     const int bound = f->graph_mode ? f->pos_bound() : pos;
-    if (f->per_layer()) {  // int8 activations: [norm + quantise] -> Q, K, V -> [q/k-norm + RoPE + attention] -> [quantise] -> proj_cat + residual; 7 launches
+    if (f->EagerOnly()) {  // int8 activations: [norm + quantise] -> Q, K, V -> [q/k-norm + RoPE + attention] -> [quantise] -> proj_cat + residual; 7 launches
                            // adapters: norm -> Q, K, V -> their adapters (one launch, on the raw rows) -> [q/k-norm + RoPE + attention] -> proj_cat + residual -> its adapter; 8 launches
         if (f->graph_mode) return nullptr;  // cache rows are resolved on the host
-        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
         SLP* qkv[3] = {&Q, &K, &V};
         floatX* ys[3] = {ToX(Q.out), ToX(f->gBUFF.kraw), val_cache + (size_t)pos * kv_dim};
-        if ((f->*group)(ToX(inpL), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 3, qkv, ys, nullptr) != KF_OK) return nullptr;
+        if (f->Group(ToX(inpL), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 3, qkv, ys, nullptr) != KF_OK) return nullptr;
         if (kf_attn_block(c, ToX(Q.out), ToX(f->gBUFF.kraw), key_cache, val_cache, ToX(f->gBUFF.scratch), normQ.w ? ToX(normQ.w) : nullptr,
                           normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos, nullptr, n_head, n_head_kv, head_dim, kv_dim, normQ.rms_eps,
                           f->gBUFF.attn_ws->data) != KF_OK)
             return nullptr;
         SLP* o[1] = {&proj_cat};
         floatX* yo[1] = {ToX(out)};
-        if ((f->*group)(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, q_dim, nullptr, 1, o, yo, ToX(inpL)) != KF_OK) return nullptr;
+        if (f->Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, q_dim, nullptr, 1, o, yo, ToX(inpL)) != KF_OK) return nullptr;
         return out;
     }
     if (f->fuse_level == 0) {
@@ -204,16 +203,15 @@ hGTensor FFN::cuInfer(hGTensor hIn, int) {
     Fish* f = hFish;
     kf_ctx* c = f->ctx;
     f->gBUFF.residual = hIn;
-    if (f->per_layer()) {  // int8 activations: [norm + quantise] -> gate, up -> SwiGLU -> [quantise] -> down + residual; 6 launches (no hot-row masks: refused at switch-on)
+    if (f->EagerOnly()) {  // int8 activations: [norm + quantise] -> gate, up -> SwiGLU -> [quantise] -> down + residual; 6 launches (no hot-row masks: the modes exclude them)
                            // adapters: norm -> gate, up -> their adapters (one launch) -> SwiGLU -> down + residual -> its adapter; 7 launches (no hot-row masks either)
-        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
         SLP* gu[2] = {&gate, &up};
         floatX* ys[2] = {ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut)};
-        if ((f->*group)(ToX(hIn), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 2, gu, ys, nullptr) != KF_OK) return nullptr;
+        if (f->Group(ToX(hIn), ToX(norm.w), norm.rms_eps, 1, f->config.nEmbed, ToX(f->gBUFF.normed), 2, gu, ys, nullptr) != KF_OK) return nullptr;
         if (kf_swiglu(c, ToX(f->gBUFF.scratch), ToX(f->gBUFF.upOut), ToX(f->gBUFF.scratch), latent) != KF_OK) return nullptr;
         SLP* d[1] = {&down};
         floatX* yd[1] = {ToX(out)};
-        if ((f->*group)(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, latent, nullptr, 1, d, yd, ToX(hIn)) != KF_OK) return nullptr;
+        if (f->Group(ToX(f->gBUFF.scratch), nullptr, 0.0f, 1, latent, nullptr, 1, d, yd, ToX(hIn)) != KF_OK) return nullptr;
         return out;
     }
     if (f->fuse_level == 0) {
@@ -254,19 +252,17 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
     floatX* vrows = val_cache + (size_t)pos0 * kv_dim;
     floatX *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn);
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
-    if (f->per_layer()) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
+    if (f->EagerOnly()) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
                            // adapters: kf_rmsnorm, kf_linear per matrix, kf_lora_apply per adapted matrix -- on the RAW k / v rows in the cache, before q/k-norm + RoPE, as the trainer's forward
-        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
-        if (f->act_int8) KF_TRY(f->A8Ready(n));
         SLP* qkv[3] = {&Q, &K, &V};
         floatX* ys[3] = {bq, krows, vrows};
-        KF_TRY((f->*group)(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 3, qkv, ys, nullptr));
+        KF_TRY(f->Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 3, qkv, ys, nullptr));
         KF_TRY(kf_qknorm_rope_batch(c, bq, krows, normQ.w ? ToX(normQ.w) : nullptr, normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n, q_dim, kv_dim, n_head, n_head_kv,
                                     head_dim, normQ.rms_eps));
         KF_TRY(kf_attn_prefill(c, bq, key_cache, val_cache, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
         SLP* o[1] = {&proj_cat};
         floatX* yo[1] = {bx};
-        return (f->*group)(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
+        return f->Group(ba, nullptr, 0.0f, n, q_dim, nullptr, 1, o, yo, bx);
     }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     if (f->kv_int8) {  // int8 KV cache: the batch's K / V rows into the staging pair, quantised into the cache, then rows 0 .. pos0 + n - 1 dequantised over the staging
@@ -293,16 +289,14 @@ int FFN::cuFlow(floatX* bx, int n) {
     const int C = f->config.nEmbed;
     floatX *bn = ToX(f->gBUFF.bNorm), *bg = ToX(f->gBUFF.bGate), *bu = ToX(f->gBUFF.bUp);
     kf_weight wg = gate.w->desc(), wu = up.w->desc(), wd = down.w->desc();
-    if (f->per_layer()) {
-        const auto group = f->act_int8 ? &Fish::A8Group : &Fish::LoraGroup;
-        if (f->act_int8) KF_TRY(f->A8Ready(n));
+    if (f->EagerOnly()) {
         SLP* gu[2] = {&gate, &up};
         floatX* ys[2] = {bg, bu};
-        KF_TRY((f->*group)(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
+        KF_TRY(f->Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
         KF_TRY(kf_swiglu(c, bg, bu, bg, n * latent));
         SLP* d[1] = {&down};
         floatX* yd[1] = {bx};
-        return (f->*group)(bg, nullptr, 0.0f, n, latent, nullptr, 1, d, yd, bx);
+        return f->Group(bg, nullptr, 0.0f, n, latent, nullptr, 1, d, yd, bx);
     }
     KF_TRY(kf_rmsnorm(c, bx, ToX(norm.w), bn, n, C, norm.rms_eps, nullptr));
     KF_TRY(kf_gateup_swiglu_batch(c, &wg, &wu, bn, bg, bu, n));
@@ -433,7 +427,28 @@ int Fish::Build(const MODEL_CARD& card, int device, void* stream) {
     return head.preLogits ? KF_OK : KF_OUTOF_GPUMEMORY;
 }
 
-// ---- int8 activations (kfh_set_act_int8)
+// ---- the modes (kf_host_modes.hpp)
+unsigned Fish::Modes() const {
+    return (tp.world > 1 ? mode_bit(MODE_TP) : 0u) | (act_int8 ? mode_bit(MODE_ACT_INT8) : 0u) | (n_adapters > 0 ? mode_bit(MODE_ADAPTERS) : 0u) |
+           (kv_int8 ? mode_bit(MODE_KV_INT8) : 0u) | (masked_layers > 0 ? mode_bit(MODE_HOT_MASK) : 0u) | (fuse_level == 0 ? mode_bit(MODE_FUSE0) : 0u);
+}
+void Fish::ModeChanged() {
+    DropEngineTable(); /* the captured graphs and the engine's table belong to the other arithmetic (or hold the old masks) */
+    weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use */
+}
+// a setter's own refusal: "<entry>: <msg>" into why, rc back
+static int refused(std::string& why, const char* entry, int rc, const std::string& msg) {
+    why = std::string(entry) + ": " + msg;
+    return rc;
+}
+std::array<SLP*, 7> Fish::LayerMatrices(int l) const {
+    SelfAttention* a = attn[l].get();
+    FFN* m = ffn[l].get();
+    return {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
+}
+SLP* Fish::LayerMatrix(int layer, int slot) const { return layer >= 0 && layer < config.nLayer && slot >= 0 && slot < 7 ? LayerMatrices(layer)[slot] : nullptr; }
+
+// ---- int8 activations (kfh_set_act_int8, kfh_set_act_int8_q4)
 static const char* kf_last_error_hint(int st) {
     return st == KF_QUANT_ERR ? "groups of 128 weights with their gama are required" : st == KF_BLAS_UNALIGN ? "data not 16-byte aligned" : "rows must be whole 128-weight groups";
 }
@@ -450,250 +465,22 @@ int Fish::A8Ready(int rows) {
     a8_rows = rows;
     return KF_OK;
 }
-// where a matrix goes in a batch of n token rows while either switch is on: 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
+// where a matrix goes in a batch of n token rows: 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear (every matrix while both switches are off)
 int Fish::A8Route(const kf_weight& w, int n) const {
     if (act_int8_q4 && kf_linear_w4a8_status(&w, n) == KF_OK) return 2; /* asked with the batch's n: the plan's LDS bound depends on it, and a refused matrix keeps kf_linear */
     return (act_int8_t && a8_type(w)) ? 1 : 0;
 }
-int Fish::A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
+int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
     bool any8 = false, other = false;
     kf_weight wd[3];
     int route[3];
     for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), route[i] = A8Route(wd[i], n), (route[i] ? any8 : other) = true;
-    if (any8) KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8_q, a8_step));
+    if (any8) {
+        KF_TRY(A8Ready(n));
+        KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8_q, a8_step));
+    }
     const floatX* xb = x;
     if (other && norm_w) {
-        KF_TRY(kf_rmsnorm(ctx, x, norm_w, normed, n, dim, eps, nullptr));
-        xb = normed;
-    }
-    for (int i = 0; i < n_w; i++) {
-        const floatX* b = s[i]->b ? ToX(s[i]->b) : nullptr;
-        if (route[i]) {
-            const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
-            if (route[i] == 2)
-                KF_TRY((tiles ? kf_linear_w4a8_tiles : kf_linear_w4a8)(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
-            else
-                KF_TRY((tiles ? kf_linear_a8_tiles : kf_linear_a8)(ctx, &wd[i], a8_q, a8_step, y[i], b, residual, n));
-            a8_count[tiles ? 0 : 1]++;
-        } else
-            KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], b, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
-    }
-    return KF_OK;
-}
-void Fish::A8Switched(bool was) {
-    act_int8 = act_int8_t || act_int8_q4;
-    if (act_int8 != was) {
-        DropEngineTable(); /* the captured graphs and the engine belong to the other arithmetic */
-        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use */
-    }
-}
-int Fish::SetActInt8(bool on, std::string& why) {
-    if (on) {
-        if (tp.world > 1) {
-            why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        if (n_adapters > 0) {
-            why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
-            return KF_INVALID_ARGS;
-        }
-        if (kv_int8) {
-            why = "the int8 KV cache is on and its layer body has no int8-activation form: switch kfh_set_kv_int8 off first";
-            return KF_INVALID_ARGS;
-        }
-        int n8 = 0;
-        std::vector<uint16_t> zero;
-        for (int l = 0; l < config.nLayer; l++) {
-            SelfAttention* a = attn[l].get();
-            FFN* m = ffn[l].get();
-            if (m->n_hot >= 0) {
-                why = "a hot-row mask is set on layer " + std::to_string(l) + ": the sparse forward has no int8-activation form";
-                return KF_INVALID_ARGS;
-            }
-            for (SLP* s : {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down}) {
-                if (!s->w) {
-                    why = "a layer matrix is missing";
-                    return KF_INVALID_ARGS;
-                }
-                const kf_weight w = s->w->desc();
-                if (!a8_type(w)) continue;
-                if (const int st = kf_linear_a8_status(&w, 1)) {
-                    why = "layer " + std::to_string(l) + ": kf_linear_a8 refuses a ternary / 1-bit matrix with " + std::to_string(st) + " (" + kf_last_error_hint(st) + ")";
-                    return st;
-                }
-                zero.resize(w.nGroup);
-                KF_TRY(kf_d2h(ctx, zero.data(), w.gama + w.ne0 + w.ne1, (size_t)w.nGroup * 2)); /* gama_T(ZERO) */
-                for (uint16_t z : zero)
-                    if (z & 0x7fff) {
-                        why = "layer " + std::to_string(l) + ": a group zero is not 0 -- the integer product has no zero point (YinYang and the symmetric quantiser write 0)";
-                        return KF_QUANT_ERR;
-                    }
-                n8++;
-            }
-        }
-        if (!n8) {
-            why = "no layer matrix is ternary (KF_T_SIGN) or 1-bit (KF_BOOL1 / KF_T_BINARY): nothing would take int8 activations";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        KF_TRY(A8Ready(1));
-        a8_count[0] = a8_count[1] = 0;
-    }
-    const bool was = act_int8;
-    act_int8_t = on;
-    A8Switched(was);
-    return KF_OK;
-}
-int Fish::SetActInt8Q4(bool on, std::string& why) {
-    if (on) {
-        if (tp.world > 1) {
-            why = "this Fish is a tensor-parallel rank: the TP step has no int8-activation form";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        if (n_adapters > 0) {
-            why = "low-rank adapters are attached and the integer products apply no adapters: clear the adapters first";
-            return KF_INVALID_ARGS;
-        }
-        if (kv_int8) {
-            why = "the int8 KV cache is on and its layer body has no int8-activation form: switch kfh_set_kv_int8 off first";
-            return KF_INVALID_ARGS;
-        }
-        int n4 = 0;
-        for (int l = 0; l < config.nLayer; l++) {
-            SelfAttention* a = attn[l].get();
-            FFN* m = ffn[l].get();
-            if (m->n_hot >= 0) {
-                why = "a hot-row mask is set on layer " + std::to_string(l) + ": the sparse forward has no int8-activation form";
-                return KF_INVALID_ARGS;
-            }
-            for (SLP* s : {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down}) {
-                if (!s->w) {
-                    why = "a layer matrix is missing";
-                    return KF_INVALID_ARGS;
-                }
-                const kf_weight w = s->w->desc();
-                if (kf_linear_w4a8_status(&w, 1) == KF_OK) n4++; /* the group ZERO is part of this arithmetic: no zero check */
-            }
-        }
-        if (!n4) {
-            why = "no layer matrix is 4-bit group storage that kf_linear_w4a8 serves (KF_Q4, groups of 128 with gama, qBias 0 or 8): nothing would take int8 activations";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        KF_TRY(A8Ready(1));
-        a8_count[0] = a8_count[1] = 0;
-    }
-    const bool was = act_int8;
-    act_int8_q4 = on;
-    A8Switched(was);
-    return KF_OK;
-}
-
-// ---- int8 KV cache (kfh_set_kv_int8)
-int Fish::SetKVInt8(bool on, std::string& why) {
-    if (on) {
-        if (tp.world > 1) {
-            why = "this Fish is a tensor-parallel rank: the TP step has no int8 KV cache form";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        if (act_int8) {
-            why = "int8 activations are on and their layer body has no int8 KV cache form: switch kfh_set_act_int8 / kfh_set_act_int8_q4 off first";
-            return KF_INVALID_ARGS;
-        }
-        if (n_adapters > 0) {
-            why = "low-rank adapters are attached and their layer body has no int8 KV cache form: clear the adapters first";
-            return KF_INVALID_ARGS;
-        }
-        if (masked_layers > 0) {
-            why = "a hot-row mask is set: the sparse forward has no int8 KV cache form";
-            return KF_INVALID_ARGS;
-        }
-        if (fuse_level == 0) {
-            why = "fuse_level 0 (one launch per reference kernel) has no int8 KV cache form: kfh_set_fuse_level(1) first";
-            return KF_INVALID_ARGS;
-        }
-        if (const int st = kf_attn_block_kv8_status(config.n_head, config.n_head_kv, config.head_dim)) {
-            why = "kf_attn_block_kv8 refuses " + std::to_string(config.n_head) + " / " + std::to_string(config.n_head_kv) + " heads x " + std::to_string(config.head_dim);
-            return st;
-        }
-        if (!cache.k8) KF_TRY(kf_sync(ctx)); /* never inside a launch sequence */
-        KF_TRY(cache.Init8(ctx, config.n_head_kv));
-        if (!gBUFF.vraw) gBUFF.vraw = GT(ctx, "vraw", typNUMBER::BF16, config.n_head_kv * config.head_dim);
-        if (!gBUFF.vraw) return KF_OUTOF_GPUMEMORY;
-    }
-    if (kv_int8 != on) {
-        kv_int8 = on;
-        DropEngineTable(); /* as A8Switched: the captured graphs and the engine belong to the other cache */
-        weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use, and refuse */
-    }
-    return KF_OK;
-}
-
-// ---- low-rank adapters at inference (kfh_set_adapter / kfh_clear_adapters)
-SLP* Fish::LayerMatrix(int layer, int slot) {
-    if (layer < 0 || layer >= config.nLayer) return nullptr;
-    SelfAttention* a = attn[layer].get();
-    FFN* m = ffn[layer].get();
-    SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
-    return slot >= 0 && slot < 7 ? s[slot] : nullptr;
-}
-int Fish::SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why) {
-    SLP* m = LayerMatrix(layer, slot);
-    if (!m || !m->w || !a || !b) {
-        why = "adapters: no such layer matrix (layer " + std::to_string(layer) + ", slot " + std::to_string(slot) + "), its weight is not set, or a null pointer";
-        return KF_INVALID_ARGS;
-    }
-    if (tp.world > 1) {
-        why = "adapters: this Fish is a tensor-parallel rank and the TP step applies no adapters";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    if (act_int8) {
-        why = "adapters: int8 activations are on and their products apply no adapters: switch kfh_set_act_int8 / kfh_set_act_int8_q4 off first";
-        return KF_INVALID_ARGS;
-    }
-    if (masked_layers > 0) {
-        why = "adapters: a hot-row mask is set and the sparse forward applies no adapters: clear it first";
-        return KF_INVALID_ARGS;
-    }
-    if (kv_int8) {
-        why = "adapters: the int8 KV cache is on and its layer body applies no adapters: switch kfh_set_kv_int8 off first";
-        return KF_INVALID_ARGS;
-    }
-    if (!std::isfinite(s)) {
-        why = "adapters: s is not finite";
-        return KF_INVALID_ARGS;
-    }
-    if (n_adapters - (m->lora_a ? 1 : 0) > 0 && (r != lora_r || s != lora_s)) { /* another matrix carries one already */
-        why = "adapters: one rank and one s per model (attached: rank " + std::to_string(lora_r) + ")";
-        return KF_INVALID_ARGS;
-    }
-    if (const int st = kf_lora_apply_status(r, m->nOut, m->nIn, 1, 1)) {
-        why = "adapters: kf_lora_apply refuses rank " + std::to_string(r) + " beside a " + std::to_string(m->nOut) + " x " + std::to_string(m->nIn) +
-              " matrix (rank 16, 32 or 64; sides multiples of 64 and >= 128)";
-        return st;
-    }
-    if (((uintptr_t)a | (uintptr_t)b) & 15) {
-        why = "adapters: a and b must be 16-byte aligned";
-        return KF_BLAS_UNALIGN;
-    }
-    if (!m->lora_a) n_adapters++;
-    m->lora_a = a, m->lora_b = b, lora_r = r, lora_s = s;
-    DropEngineTable(); /* as A8Switched: the captured graphs and the engine belong to the model without adapters */
-    weights_gen++;     /* XcdReplicas / XcdTP built on this Fish re-check at their next use, and refuse */
-    return KF_OK;
-}
-void Fish::ClearAdapters() {
-    if (!n_adapters) return;
-    for (int l = 0; l < config.nLayer; l++)
-        for (int j = 0; j < 7; j++) {
-            SLP* m = LayerMatrix(l, j);
-            m->lora_a = m->lora_b = nullptr;
-        }
-    n_adapters = 0, lora_r = 0, lora_s = 0.0f;
-    DropEngineTable();
-    weights_gen++;
-}
-int Fish::LoraGroup(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
-    const floatX* xb = x;
-    if (norm_w) {
         KF_TRY(kf_rmsnorm(ctx, x, norm_w, normed, n, dim, eps, nullptr));
         xb = normed;
     }
@@ -701,14 +488,107 @@ int Fish::LoraGroup(const floatX* x, const floatX* norm_w, float eps, int n, int
     floatX* ya[3];
     int OC[3], na = 0;
     for (int i = 0; i < n_w; i++) {
-        const kf_weight wd = s[i]->w->desc();
-        KF_TRY(kf_linear(ctx, &wd, xb, y[i], s[i]->b ? ToX(s[i]->b) : nullptr, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
-        if (s[i]->lora_a) a[na] = s[i]->lora_a, b[na] = s[i]->lora_b, ya[na] = y[i], OC[na] = wd.ne0, na++;
+        const floatX* bias = s[i]->b ? ToX(s[i]->b) : nullptr;
+        if (route[i]) {
+            const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
+            if (route[i] == 2)
+                KF_TRY((tiles ? kf_linear_w4a8_tiles : kf_linear_w4a8)(ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
+            else
+                KF_TRY((tiles ? kf_linear_a8_tiles : kf_linear_a8)(ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
+            a8_count[tiles ? 0 : 1]++;
+        } else
+            KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], bias, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
+        if (s[i]->lora_a) a[na] = s[i]->lora_a, b[na] = s[i]->lora_b, ya[na] = y[i], OC[na] = wd[i].ne0, na++;
     }
     if (na == 0) return KF_OK;
     if (n == 1) return kf_lora_apply(ctx, na, a, b, lora_r, OC, dim, xb, ya, nullptr, 1, lora_s); /* the group's adapters share the row: one launch */
     for (int i = 0; i < na; i++) KF_TRY(kf_lora_apply(ctx, 1, a + i, b + i, lora_r, OC + i, dim, xb, ya + i, nullptr, n, lora_s));
     return KF_OK;
+}
+int Fish::SetActInt8(bool q4, bool on, std::string& why) {
+    const char* entry = q4 ? "kfh_set_act_int8_q4" : "kfh_set_act_int8";
+    if (on) {
+        KF_TRY(Admit(MODE_ACT_INT8, entry, why));
+        int served = 0;
+        std::vector<uint16_t> zero;
+        for (int l = 0; l < config.nLayer; l++)
+            for (SLP* s : LayerMatrices(l)) {
+                if (!s->w) return refused(why, entry, KF_INVALID_ARGS, "a layer matrix is missing");
+                const kf_weight w = s->w->desc();
+                if (q4) { /* the group ZERO is part of this arithmetic: no zero check */
+                    served += kf_linear_w4a8_status(&w, 1) == KF_OK;
+                    continue;
+                }
+                if (!a8_type(w)) continue;
+                if (const int st = kf_linear_a8_status(&w, 1))
+                    return refused(why, entry, st, "layer " + std::to_string(l) + ": kf_linear_a8 refuses a ternary / 1-bit matrix with " + std::to_string(st) + " (" + kf_last_error_hint(st) + ")");
+                zero.resize(w.nGroup);
+                KF_TRY(kf_d2h(ctx, zero.data(), w.gama + w.ne0 + w.ne1, (size_t)w.nGroup * 2)); /* gama_T(ZERO) */
+                for (uint16_t z : zero)
+                    if (z & 0x7fff)
+                        return refused(why, entry, KF_QUANT_ERR, "layer " + std::to_string(l) + ": a group zero is not 0 -- the integer product has no zero point (YinYang and the symmetric quantiser write 0)");
+                served++;
+            }
+        if (!served)
+            return refused(why, entry, KF_UNSUPPORTED_DATATYPE,
+                           q4 ? "no layer matrix is 4-bit group storage that kf_linear_w4a8 serves (KF_Q4, groups of 128 with gama, qBias 0 or 8): nothing would take int8 activations"
+                              : "no layer matrix is ternary (KF_T_SIGN) or 1-bit (KF_BOOL1 / KF_T_BINARY): nothing would take int8 activations");
+        KF_TRY(A8Ready(1));
+        a8_count[0] = a8_count[1] = 0;
+    }
+    const bool was = act_int8;
+    (q4 ? act_int8_q4 : act_int8_t) = on;
+    act_int8 = act_int8_t || act_int8_q4;
+    if (act_int8 != was) ModeChanged();
+    return KF_OK;
+}
+
+// ---- int8 KV cache (kfh_set_kv_int8)
+int Fish::SetKVInt8(bool on, std::string& why) {
+    if (on) {
+        KF_TRY(Admit(MODE_KV_INT8, "kfh_set_kv_int8", why));
+        if (const int st = kf_attn_block_kv8_status(config.n_head, config.n_head_kv, config.head_dim))
+            return refused(why, "kfh_set_kv_int8", st,
+                           "kf_attn_block_kv8 refuses " + std::to_string(config.n_head) + " / " + std::to_string(config.n_head_kv) + " heads x " + std::to_string(config.head_dim));
+        if (!cache.k8) KF_TRY(kf_sync(ctx)); /* never inside a launch sequence */
+        KF_TRY(cache.Init8(ctx, config.n_head_kv));
+        if (!gBUFF.vraw) gBUFF.vraw = GT(ctx, "vraw", typNUMBER::BF16, config.n_head_kv * config.head_dim);
+        if (!gBUFF.vraw) return KF_OUTOF_GPUMEMORY;
+    }
+    if (kv_int8 != on) {
+        kv_int8 = on;
+        ModeChanged();
+    }
+    return KF_OK;
+}
+
+// ---- low-rank adapters at inference (kfh_set_adapter / kfh_clear_adapters)
+int Fish::SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why) {
+    const char* entry = "kfh_set_adapter";
+    SLP* m = LayerMatrix(layer, slot);
+    if (!m || !m->w || !a || !b)
+        return refused(why, entry, KF_INVALID_ARGS,
+                       "adapters: no such layer matrix (layer " + std::to_string(layer) + ", slot " + std::to_string(slot) + "), its weight is not set, or a null pointer");
+    KF_TRY(Admit(MODE_ADAPTERS, entry, why));
+    if (!std::isfinite(s)) return refused(why, entry, KF_INVALID_ARGS, "adapters: s is not finite");
+    if (n_adapters - (m->lora_a ? 1 : 0) > 0 && (r != lora_r || s != lora_s)) /* another matrix carries one already */
+        return refused(why, entry, KF_INVALID_ARGS, "adapters: one rank and one s per model (attached: rank " + std::to_string(lora_r) + ")");
+    if (const int st = kf_lora_apply_status(r, m->nOut, m->nIn, 1, 1))
+        return refused(why, entry, st,
+                       "adapters: kf_lora_apply refuses rank " + std::to_string(r) + " beside a " + std::to_string(m->nOut) + " x " + std::to_string(m->nIn) +
+                           " matrix (rank 16, 32 or 64; sides multiples of 64 and >= 128)");
+    if (((uintptr_t)a | (uintptr_t)b) & 15) return refused(why, entry, KF_BLAS_UNALIGN, "adapters: a and b must be 16-byte aligned");
+    if (!m->lora_a) n_adapters++;
+    m->lora_a = a, m->lora_b = b, lora_r = r, lora_s = s;
+    ModeChanged();
+    return KF_OK;
+}
+void Fish::ClearAdapters() {
+    if (!n_adapters) return;
+    for (int l = 0; l < config.nLayer; l++)
+        for (SLP* m : LayerMatrices(l)) m->lora_a = m->lora_b = nullptr;
+    n_adapters = 0, lora_r = 0, lora_s = 0.0f;
+    ModeChanged();
 }
 
 // position buckets: one captured graph each; the bound fixes the attention slice count of that graph
@@ -740,7 +620,7 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
     for (int l = 0; l < config.nLayer; l++) {
         SelfAttention* a = attn[l].get();
         FFN* m = ffn[l].get();
-        SLP* s[7] = {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
+        const auto s = LayerMatrices(l);
         for (int j = 0; j < 7; j++) {
             if (!s[j]->w || s[j]->b) {
                 why = "a layer matrix is missing or carries a bias";
@@ -769,18 +649,7 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
 int Fish::EnsureEngine() {
     if (engine_state != 0) return engine_state > 0 ? KF_OK : KF_ENGINE_NOT_SERVED;
     engine_state = -1;
-    if (act_int8) {
-        engine_why = "int8 activations run on the per-layer launches";
-        return KF_ENGINE_NOT_SERVED;
-    }
-    if (n_adapters > 0) {
-        engine_why = "low-rank adapters are attached: they run on the per-layer launches";
-        return KF_ENGINE_NOT_SERVED;
-    }
-    if (kv_int8) {
-        engine_why = "int8 KV cache runs on the per-layer launches";
-        return KF_ENGINE_NOT_SERVED;
-    }
+    KF_TRY(engine_refusal(Modes(), engine_why));
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
     KF_TRY(EngineTable(ToX(cache.key), ToX(cache.val), true, engine_why, L, d));
@@ -866,12 +735,12 @@ int Fish::EnsureResident(int PC) {
     if (deq_arena || resident_tried || !prefill_resident || PC < 1024) return KF_OK;
     resident_tried = true;
     size_t total = 0;
-    auto add = [&](const SLP& s) {
-        if (!s.w) return;
-        const kf_weight d = s.w->desc();
-        if (d.type != KF_BF16 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
-    };
-    for (int l = 0; l < config.nLayer; l++) add(attn[l]->Q), add(attn[l]->K), add(attn[l]->V), add(attn[l]->proj_cat), add(ffn[l]->gate), add(ffn[l]->up), add(ffn[l]->down);
+    for (int l = 0; l < config.nLayer; l++)
+        for (const SLP* s : LayerMatrices(l)) {
+            if (!s->w) continue;
+            const kf_weight d = s->w->desc();
+            if (d.type != KF_BF16 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
+        }
     if (total == 0 || total + head_screen_bytes > resident_max_bytes) return KF_OK;
     KF_TRY(kf_sync(ctx));
     void* p = nullptr;
@@ -894,18 +763,7 @@ int Fish::EngineCheck() {
 // ------------------------------------------------------------------------------------------------ tensor parallel
 int Fish::TPInit(int rank, int world, int vocab_row0) {
     if (world < 2 || world > 8 || rank < 0 || rank >= world) return KF_INVALID_ARGS;
-    if (act_int8) { /* the TP step has no int8-activation form: switch it off first */
-        g_host_err = "kfh_tp_init: int8 activations are on and the tensor-parallel step has no int8-activation form: switch kfh_set_act_int8 off first";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    if (n_adapters > 0) { /* nor one that applies adapters */
-        g_host_err = "kfh_tp_init: low-rank adapters are attached and the tensor-parallel step applies no adapters: clear the adapters first";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    if (kv_int8) { /* nor one on the int8 cache */
-        g_host_err = "kfh_tp_init: the int8 KV cache is on and the tensor-parallel step has no int8 KV cache form: switch kfh_set_kv_int8 off first";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
+    KF_TRY(Admit(MODE_TP, "kfh_tp_init", g_host_err));
     std::memset(&tp.comm, 0, sizeof(tp.comm));
     tp.rank = rank, tp.world = world, tp.vocab_row0 = vocab_row0;
     tp.comm.rank = rank, tp.comm.world = world, tp.comm.n_max = config.nEmbed, tp.comm.per_step = 2u * (uint32_t)config.nLayer + 1u;
@@ -988,9 +846,17 @@ static int tp_group_enqueue(Fish** fs, int R) {
     return KF_OK;
 }
 
+int Fish::LayersAndHead(hGTensor cur) {
+    for (int l = 0; l < config.nLayer && cur; l++) {
+        cur = attn[l]->cuInfer(cur);
+        if (cur) cur = ffn[l]->cuInfer(cur);
+    }
+    return cur && head.cuInfer_1(cur) ? KF_OK : KF_INTERNAL_ERR;
+}
+
 int Fish::EnqueueStep(int bound) {
-    if (tp.world > 1) return EnqueueStepTP(); /* never with int8 activations: SetActInt8 refuses a TP rank, TPInit refuses while the switch is on */
-    if (per_layer() && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
+    if (tp.world > 1) return EnqueueStepTP(); /* never an eager-only mode: both exclude a TP rank */
+    if (EagerOnly() && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
     if (use_engine && fuse_level >= 1 && engine_state > 0 && engine_embed && (graph_mode || state_tokens)) { /* embedding row read inside the launch */
         if (engine_head) { /* ... and the final norm, the LM head and the greedy pick: ONE launch per token */
             const int rc = kf_engine_step_head(ctx, engine, nullptr, ToX(x), d_state, bound, samp_params.greedy() ? 1 : 0);
@@ -1019,13 +885,7 @@ int Fish::EnqueueStep(int bound) {
             return head.cuInfer_1(x) ? KF_OK : KF_INTERNAL_ERR;
         }
     }
-    for (int l = 0; l < config.nLayer; l++) {
-        cur = attn[l]->cuInfer(cur);
-        if (!cur) return KF_INTERNAL_ERR;
-        cur = ffn[l]->cuInfer(cur);
-        if (!cur) return KF_INTERNAL_ERR;
-    }
-    return head.cuInfer_1(cur) ? KF_OK : KF_INTERNAL_ERR;
+    return LayersAndHead(cur);
 }
 
 int Fish::ForwardOnRLS(int token, int pos) {
@@ -1033,15 +893,7 @@ int Fish::ForwardOnRLS(int token, int pos) {
     tok_pos = pos;
     graph_mode = false;
     KF_TRY(kf_set_state(ctx, d_state, token, pos));
-    hGTensor cur = embed.cuInfer(token);
-    if (!cur) return KF_INTERNAL_ERR;
-    for (int l = 0; l < config.nLayer; l++) {
-        cur = attn[l]->cuInfer(cur);
-        if (!cur) return KF_INTERNAL_ERR;
-        cur = ffn[l]->cuInfer(cur);
-        if (!cur) return KF_INTERNAL_ERR;
-    }
-    return head.cuInfer_1(cur) ? KF_OK : KF_INTERNAL_ERR;
+    return LayersAndHead(embed.cuInfer(token));
 }
 
 int Fish::SetState(int token, int pos) { return kf_set_state(ctx, d_state, token, pos); }
@@ -1078,7 +930,7 @@ bool Fish::OneLaunchStep() {
 int Fish::RunSteps(int pos, int n, bool use_graph) {
     if (pos < 0 || pos + n > config.n_ctx) return KF_INVALID_ARGS;
     KF_TRY(TPCommit());
-    if (use_graph && n > 1 && !per_layer() && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
+    if (use_graph && n > 1 && !EagerOnly() && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
         constexpr int kStepsPerLaunch = 16;
         int i = 0;
         while (i < n) {
@@ -1110,7 +962,7 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
     }
     for (int i = 0; i < n; i++) {
         const int p = pos + i;
-        if (fuse_level == 0 || per_layer()) {  // per-kernel launches only (AutoAWQ weights; int8 activations; adapters): eager, position from the host, token from the device state
+        if (fuse_level == 0 || EagerOnly()) {  // per-kernel launches only (AutoAWQ weights; the eager-only modes): eager, position from the host, token from the device state
             tok_pos = p;
             graph_mode = false, state_tokens = true;
             int rc = EnqueueStep(pos_bound());
@@ -1139,24 +991,32 @@ int Fish::Prefill(const int* tokens, int n, int pos0) {
     if (n < 1 || pos0 < 0 || pos0 + n > config.n_ctx) return KF_INVALID_ARGS;
     for (int i = 0; i < n; i++)
         if (tokens[i] < 0 || tokens[i] >= config.vocab) return KF_INVALID_ARGS;
-    const int PC = prefill_chunk < config.n_ctx ? prefill_chunk : config.n_ctx, C = config.nEmbed;
+    const int PC = prefill_chunk < config.n_ctx ? prefill_chunk : config.n_ctx;
     KF_TRY(PrefillReady());
-    floatX* bx = ToX(gBUFF.bX);
-    kf_weight we = embed.w->desc();
     int m = 0;
     for (int c0 = 0; c0 < n; c0 += PC) {
         m = n - c0 < PC ? n - c0 : PC;
-        KF_TRY(kf_h2d(ctx, gBUFF.d_ptok, tokens + c0, (size_t)m * 4));
-        KF_TRY(kf_embed_batch(ctx, &we, gBUFF.d_ptok, m, bx));
-        for (int l = 0; l < config.nLayer; l++) {
-            KF_TRY(attn[l]->cuFlow(bx, pos0 + c0, m));
-            KF_TRY(ffn[l]->cuFlow(bx, m));
-        }
+        KF_TRY(FlowChunk(tokens + c0, m, pos0 + c0));
     }
-    // head on the last token; the state update leaves {next token, pos0 + n}
-    KF_TRY(kf_d2d(ctx, x->data, bx + (size_t)(m - 1) * C, (size_t)C * 2));
-    KF_TRY(SetState(tokens[n - 1], pos0 + n - 1));
-    tok_pos = pos0 + n - 1;
+    return FlowEnd(m - 1, tokens[n - 1], pos0 + n - 1);
+}
+int Fish::FlowChunk(const int* tokens, int m, int pos) {
+    floatX* bx = ToX(gBUFF.bX);
+    const kf_weight we = embed.w->desc();
+    KF_TRY(kf_h2d(ctx, gBUFF.d_ptok, tokens, (size_t)m * 4));
+    KF_TRY(kf_embed_batch(ctx, &we, gBUFF.d_ptok, m, bx));
+    for (int l = 0; l < config.nLayer; l++) {
+        KF_TRY(attn[l]->cuFlow(bx, pos, m));
+        KF_TRY(ffn[l]->cuFlow(bx, m));
+    }
+    return KF_OK;
+}
+// head on the last token (row `last` of the batch buffer, `token` at `pos`); the state update leaves {next token, pos + 1}
+int Fish::FlowEnd(int last, int token, int pos) {
+    const int C = config.nEmbed;
+    KF_TRY(kf_d2d(ctx, x->data, ToX(gBUFF.bX) + (size_t)last * C, (size_t)C * 2));
+    KF_TRY(SetState(token, pos));
+    tok_pos = pos;
     return HeadAndPick(ToX(x));
 }
 
@@ -1189,17 +1049,12 @@ int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top
     const int PC = prefill_chunk < config.n_ctx ? prefill_chunk : config.n_ctx, C = config.nEmbed;
     KF_TRY(ScoreReady());
     floatX* bx = ToX(gBUFF.bX);
-    kf_weight we = embed.w->desc(), wh = head.proj.w->desc();
+    const kf_weight wh = head.proj.w->desc();
     std::vector<int32_t> tgt(PC);
     int m = 0;
     for (int c0 = 0; c0 < n; c0 += PC) {
         m = n - c0 < PC ? n - c0 : PC;
-        KF_TRY(kf_h2d(ctx, gBUFF.d_ptok, tokens + c0, (size_t)m * 4));
-        KF_TRY(kf_embed_batch(ctx, &we, gBUFF.d_ptok, m, bx));
-        for (int l = 0; l < config.nLayer; l++) {
-            KF_TRY(attn[l]->cuFlow(bx, pos0 + c0, m));
-            KF_TRY(ffn[l]->cuFlow(bx, m));
-        }
+        KF_TRY(FlowChunk(tokens + c0, m, pos0 + c0));
         // row i of the chunk predicts token c0 + i + 1: the first token of the next chunk for the chunk's last row, nothing for the last row of all
         const int ns = c0 + m < n ? m : m - 1;
         if (ns < 1) continue;
@@ -1210,11 +1065,7 @@ int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top
         KF_TRY(kf_d2h(ctx, logprob_out + c0, gBUFF.d_slp, (size_t)ns * 4));
         if (top1_out) KF_TRY(kf_d2h(ctx, top1_out + c0, gBUFF.d_stop1, (size_t)ns * 4));
     }
-    // from here on Prefill's own ending: the head on the last token, the state update leaves {next token, pos0 + n}
-    KF_TRY(kf_d2d(ctx, x->data, bx + (size_t)(m - 1) * C, (size_t)C * 2));
-    KF_TRY(SetState(tokens[n - 1], pos0 + n - 1));
-    tok_pos = pos0 + n - 1;
-    return HeadAndPick(ToX(x));
+    return FlowEnd(m - 1, tokens[n - 1], pos0 + n - 1); /* Prefill's own ending */
 }
 
 int Fish::EvalPPL(const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored) {
@@ -1363,18 +1214,7 @@ int XcdReplicas::MakeEngine(bool allocate) {
     const int kvd = c.n_head_kv * c.head_dim;
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
-    if (f->act_int8) {
-        why = "int8 activations run on the per-layer launches";
-        return KF_ENGINE_NOT_SERVED;
-    }
-    if (f->n_adapters > 0) {
-        why = "low-rank adapters are attached: the XCD engines apply no adapters";
-        return KF_ENGINE_NOT_SERVED;
-    }
-    if (f->kv_int8) {
-        why = "int8 KV cache runs on the per-layer launches";
-        return KF_ENGINE_NOT_SERVED;
-    }
+    KF_TRY(engine_refusal(f->Modes(), why));
     KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
     {
         char w[320];
@@ -1713,18 +1553,7 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "the ranks' cards disagree";
             return KF_INVALID_ARGS;
         }
-        if (f->act_int8) {
-            why = "int8 activations run on the per-layer launches";
-            return KF_ENGINE_NOT_SERVED;
-        }
-        if (f->n_adapters > 0) {
-            why = "low-rank adapters are attached: the XCD engines apply no adapters";
-            return KF_ENGINE_NOT_SERVED;
-        }
-        if (f->kv_int8) {
-            why = "int8 KV cache runs on the per-layer launches";
-            return KF_ENGINE_NOT_SERVED;
-        }
+        KF_TRY(engine_refusal(f->Modes(), why));
         KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
         ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
         dp[r] = &ds[r];
@@ -1817,10 +1646,7 @@ const char* kfh_host_error(void) { return g_host_err.c_str(); } /* why the last 
 void* kfh_ctx(void* h) { return reinterpret_cast<Fish*>(h)->ctx; }
 int kfh_set_fuse_level(void* h, int lvl) {
     Fish* f = reinterpret_cast<Fish*>(h);
-    if (lvl == 0 && f->kv_int8) { /* the per-kernel sequence has no int8 KV cache form */
-        g_host_err = "kfh_set_fuse_level: the int8 KV cache is on and fuse_level 0 has no int8 KV cache form: switch kfh_set_kv_int8 off first";
-        return KF_INVALID_ARGS;
-    }
+    if (lvl == 0) KF_TRY(f->Admit(MODE_FUSE0, "kfh_set_fuse_level", g_host_err));
     f->fuse_level = lvl;
     return KF_OK;
 }
@@ -1830,21 +1656,9 @@ int kfh_set_hot(void* h, int layer, const int32_t* h_hot, int n) {
     if (layer < 0 || layer >= f->config.nLayer) return KF_INVALID_ARGS;
     FFN* m = f->ffn[layer].get();
     if (h_hot && n != f->config.n_ff) return KF_INVALID_ARGS; /* arguments first: a rejected call changes nothing */
-    if (h_hot && f->act_int8) { /* the sparse forward has no int8-activation form */
-        g_host_err = "kfh_set_hot: int8 activations are on and the sparse forward has no int8-activation form: switch kfh_set_act_int8 off first";
-        return KF_INVALID_ARGS;
-    }
-    if (h_hot && f->n_adapters > 0) { /* nor a form that applies adapters */
-        g_host_err = "kfh_set_hot: low-rank adapters are attached and the sparse forward applies no adapters: clear the adapters first";
-        return KF_INVALID_ARGS;
-    }
-    if (h_hot && f->kv_int8) { /* nor one on the int8 cache */
-        g_host_err = "kfh_set_hot: the int8 KV cache is on and the sparse forward has no int8 KV cache form: switch kfh_set_kv_int8 off first";
-        return KF_INVALID_ARGS;
-    }
-    f->DropEngineTable(); /* the engine's layer table (and the captured graphs) hold the masks: rebuilt on the next step; the resident bf16 copies and the measured delays do not
-                             depend on them and stay */
-    f->weights_gen++;     /* an XcdReplicas built on this Fish holds the masks' addresses in its layer table too: its next use re-creates the engine */
+    if (h_hot) KF_TRY(f->Admit(MODE_HOT_MASK, "kfh_set_hot", g_host_err)); /* clearing is never refused */
+    f->ModeChanged(); /* the engine's layer table, the captured graphs and an XcdReplicas' table hold the masks: rebuilt at their next use; the resident bf16 copies and the
+                         measured delays do not depend on them and stay */
     if (!h_hot) {
         if (m->n_hot >= 0) f->masked_layers--;
         m->n_hot = -1, m->hot_rows.reset(), m->hot_mask.reset();
@@ -1874,24 +1688,12 @@ int kfh_set_engine(void* h, int on) {
     return KF_OK;
 }
 // int8 activations for the ternary / 1-bit layer matrices: on / off (off: today's routes, bit for bit).  A refusal leaves the switch as it was; kfh_host_error says why.
-int kfh_set_act_int8(void* h, int on) {
-    const int rc = reinterpret_cast<Fish*>(h)->SetActInt8(on != 0, g_host_err);
-    if (rc != KF_OK) g_host_err = "kfh_set_act_int8: " + g_host_err;
-    return rc;
-}
+int kfh_set_act_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(false, on != 0, g_host_err); }
 // the same for the 4-bit layer matrices (kf_linear_w4a8 / kf_linear_w4a8_tiles): a second switch, independent of kfh_set_act_int8
-int kfh_set_act_int8_q4(void* h, int on) {
-    const int rc = reinterpret_cast<Fish*>(h)->SetActInt8Q4(on != 0, g_host_err);
-    if (rc != KF_OK) g_host_err = "kfh_set_act_int8_q4: " + g_host_err;
-    return rc;
-}
+int kfh_set_act_int8_q4(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(true, on != 0, g_host_err); }
 // the int8 KV cache: on / off (off: today's routes on the bf16 cache, bit for bit).  The two caches are independent -- switching converts nothing, the caller prefills again.
 // A refusal leaves the switch as it was; kfh_host_error says why.  kfh_kv8_*: the int8 pair and its steps on the device (NULL before the first switch-on).
-int kfh_set_kv_int8(void* h, int on) {
-    const int rc = reinterpret_cast<Fish*>(h)->SetKVInt8(on != 0, g_host_err);
-    if (rc != KF_OK) g_host_err = "kfh_set_kv_int8: " + g_host_err;
-    return rc;
-}
+int kfh_set_kv_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetKVInt8(on != 0, g_host_err); }
 int kfh_kv_int8(void* h) { return reinterpret_cast<Fish*>(h)->kv_int8 ? 1 : 0; }
 void* kfh_kv8_codes(void* h, int val) {
     const KVCache& kc = reinterpret_cast<Fish*>(h)->cache;
@@ -1903,11 +1705,9 @@ void* kfh_kv8_steps(void* h, int val) {
 }
 // a low-rank adapter beside layer matrix `slot` (0 q, 1 k, 2 v, 3 o, 4 gate, 5 up, 6 down): a [r, in], b [out, r] bf16 DEVICE pointers, no copy (the caller keeps them alive and
 // may update them in place: every launch reads them); s multiplies both products, one rank and one s per model.  While any is attached decode, prefill, score and perplexity
-// apply it (Fish::LoraGroup) on per-layer launches.  A refusal changes nothing; kfh_host_error says why.
+// apply it (Fish::Group) on per-layer launches.  A refusal changes nothing; kfh_host_error says why.
 int kfh_set_adapter(void* h, int layer, int slot, const void* a, const void* b, int r, float s) {
-    const int rc = reinterpret_cast<Fish*>(h)->SetAdapter(layer, slot, reinterpret_cast<const floatX*>(a), reinterpret_cast<const floatX*>(b), r, s, g_host_err);
-    if (rc != KF_OK) g_host_err = "kfh_set_adapter: " + g_host_err;
-    return rc;
+    return reinterpret_cast<Fish*>(h)->SetAdapter(layer, slot, reinterpret_cast<const floatX*>(a), reinterpret_cast<const floatX*>(b), r, s, g_host_err);
 }
 int kfh_clear_adapters(void* h) {
     reinterpret_cast<Fish*>(h)->ClearAdapters();
@@ -2045,10 +1845,22 @@ int kfh_engine_check(void* h) {
     return f->EngineCheck();
 }
 
-static SLP* slot_of(Fish* f, int layer, int slot) {
-    if (layer < 0) return slot == 1 ? &f->head.proj : nullptr;
-    return f->LayerMatrix(layer, slot);
+static SLP* slot_of(Fish* f, int layer, int slot) { return layer >= 0 ? f->LayerMatrix(layer, slot) : slot == 1 ? &f->head.proj : nullptr; }
+// the mode table without a device (tests/test_host_modes_cpu.py): mode_refusal / engine_refusal / eager_only for any set of active modes
+static int why_out(int rc, const std::string& why, char* out, size_t n) {
+    if (out && n) std::snprintf(out, n, "%s", rc != KF_OK ? why.c_str() : "");
+    return rc;
 }
+int kfhdbg_mode_refusal(unsigned active, int asked, char* why, size_t n) {
+    if (asked < 0 || asked >= N_MODES) return why_out(KF_INVALID_ARGS, "kfhdbg: no such mode", why, n);
+    std::string w;
+    return why_out(mode_refusal(active, (Mode)asked, "kfhdbg", w), w, why, n);
+}
+int kfhdbg_engine_refusal(unsigned active, char* why, size_t n) {
+    std::string w;
+    return why_out(engine_refusal(active, w), w, why, n);
+}
+int kfhdbg_eager_only(unsigned active) { return eager_only(active) ? 1 : 0; }
 
 // slot: 0 q,1 k,2 v,3 o,4 gate,5 up,6 down (layer >= 0); layer = -1: slot 0 embed_tokens, 1 lm_head.
 // Either a host blob (`data||gama`, copied to a fresh device allocation) or an existing device pointer.

@@ -13,12 +13,14 @@
 //   Fish::ForwardOnRLS / Chat  src/Manifold/gLLM.cpp:722-787, src/Manifold/GoPT.cpp:1111-1235
 // No HIP headers here: device memory and launches go through the kf_* C ABI only (plain g++ builds this file).
 #pragma once
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/kf_abi.h"
+#include "kf_host_modes.hpp"
 
 namespace koifish {
 
@@ -222,6 +224,14 @@ struct TPState {
 
 struct Fish : SeqBuffers {
     MODEL_CARD config;
+    // The ways a layer can run (kf_host_modes.hpp: the one table of modes, of the pairs that do not combine and of what a refusal says).  Modes() is derived from the state
+    // below, never stored; every entry that switches a mode ON asks Admit first (after its argument checks: a rejected call changes nothing), switching off is never
+    // refused; ModeChanged() follows every switch that moved: the engine's table and the captured graphs belong to the other arithmetic, and XcdReplicas / XcdTP objects
+    // built on this Fish re-check at their next use (weights_gen).
+    unsigned Modes() const;
+    int Admit(Mode asked, const char* entry, std::string& why) const { return mode_refusal(Modes(), asked, entry, why); }
+    bool EagerOnly() const { return eager_only(Modes()); }  // what the step sequencing asks: eager per-layer launches, position from the host, no engine, no graphs
+    void ModeChanged();
     TPState tp;
     int TPInit(int rank, int world, int vocab_row0);  // allocates this rank's receive area; peers are set afterwards
     int TPSetPeer(int r, void* area);
@@ -256,7 +266,7 @@ struct Fish : SeqBuffers {
     kf_engine* engine = nullptr;
     void* engine_ws = nullptr;
     int engine_state = 0;  // 0 not tried, 1 built, -1 not served
-    unsigned weights_gen = 0;  // counts DropEngine calls (a weight set again, kfh_weights_changed): engines other objects built on this Fish compare it with their own copy
+    unsigned weights_gen = 0;  // counts DropEngine (a weight set again, kfh_weights_changed) and ModeChanged calls: engines other objects built on this Fish compare it with their own copy
     bool engine_embed = false;  // the engine reads the (bf16) embedding row itself
     bool engine_head = false;   // ... and runs the final norm, the (bf16) LM head and the greedy pick as trailing phases of its launch
     // The int8 screen of the in-launch head (kf_engine_set_head_screen): a derived copy of the head like the resident bf16 copies, so it is built only under the same promise
@@ -329,13 +339,13 @@ struct Fish : SeqBuffers {
     // 8191 tokens 92.3 / 53.9 / 42.7 / 36.6 ms at 1024 / 2048 / 4096 / 8192 (scratch/prefill_chunk.py): the tile kernels want many rows per launch.
     int prefill_chunk = 8192;
     int prefill_mode = 0;  // Generate: 0 token-serial prefill like the reference, 1 batched
+    // ---- the modes.  Which of them combine, and every refusal's text: kf_host_modes.hpp.  Each setter keeps only the checks that are its mode's own.
     // int8 activations (kfh_set_act_int8; include/kf_abi.h "int8 activations"): every layer matrix stored ternary or 1-bit takes its input through kf_act_quant_i8 and
     // kf_linear_a8 -- q | k | v share one quantisation of the normed row (the norm prologue), gate | up one, o_proj and down_proj quantise their own inputs; matrices of
-    // any other storage keep kf_rmsnorm + kf_linear; embedding, final norm and LM head are untouched.  Token-serial steps and token batches alike, on per-layer launches
-    // with the position from the host: the persistent engines and the captured graphs are not used while it is on.
-    // act_int8 is "either switch is on": what the per-layer bodies, the engines and the TP step ask.  act_int8_t is kfh_set_act_int8's own state (ternary / 1-bit
-    // matrices -> kf_linear_a8), act_int8_q4 kfh_set_act_int8_q4's (include/kf_abi.h "int8 activations for 4-bit layers": KF_Q4 group matrices that
-    // kf_linear_w4a8_status serves -> kf_linear_w4a8 / kf_linear_w4a8_tiles; their ZERO need not be 0, the dequant arena is not consulted for them).
+    // any other storage keep kf_rmsnorm + kf_linear; embedding, final norm and LM head are untouched.  Token-serial steps and token batches alike (an eager-only mode).
+    // act_int8 is "either switch is on".  act_int8_t is kfh_set_act_int8's own state (ternary / 1-bit matrices -> kf_linear_a8), act_int8_q4 kfh_set_act_int8_q4's
+    // (include/kf_abi.h "int8 activations for 4-bit layers": KF_Q4 group matrices that kf_linear_w4a8_status serves -> kf_linear_w4a8 / kf_linear_w4a8_tiles; their ZERO
+    // need not be 0, the dequant arena is not consulted for them).
     bool act_int8 = false, act_int8_t = false, act_int8_q4 = false;
     int8_t* a8_q = nullptr;     // [a8_rows][max(q_dim, nEmbed, n_ff)]
     float* a8_step = nullptr;   // [a8_rows]
@@ -344,35 +354,37 @@ struct Fish : SeqBuffers {
     // kf_linear_a8; < 0: never.  kfh_set_a8_tile_min; the default is the tile plan's KF_A8_TILE_MIN.  a8_count: (tile, mat-vec) launches since the last switch-on.
     int a8_tile_min = KF_A8_TILE_MIN;
     int64_t a8_count[2] = {0, 0};
-    int SetActInt8(bool on, std::string& why);  // the switch-on checks: a ternary / 1-bit layer matrix exists, every ZERO section of those is zero, no hot-row mask
-    int SetActInt8Q4(bool on, std::string& why);  // the switch-on checks: a 4-bit layer matrix that kf_linear_w4a8 serves exists, no hot-row mask
+    // one switch per family; its own switch-on checks: a layer matrix of the family exists (q4: one kf_linear_w4a8 serves; otherwise: ternary / 1-bit, kf_linear_a8
+    // accepts each, every ZERO section of those is zero)
+    int SetActInt8(bool q4, bool on, std::string& why);
     int A8Route(const kf_weight& w, int n) const;  // 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
-    void A8Switched(bool was);  // after either switch moved: act_int8 = either; a change of it drops the engine table and the captured graphs
     int A8Ready(int rows);
-    // the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual` (may alias y[0]; n_w == 1) kf_linear's
-    // residual epilogue.  normed: [n][dim] for the bf16 route of matrices that have no integer form.
-    int A8Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
     // low-rank adapters at inference (kfh_set_adapter; include/kf_abi.h kf_lora_apply; the LORA branch of SLP::Forw): any subset of the layers' seven matrices carries a
     // trained pair a [r, in], b [out, r] -- device pointers of the caller's, no copy, read at every launch (a trainer's later step is seen) -- with ONE rank and ONE s for
-    // the model.  While any is attached the layer bodies take the unfused sequence LoraGroup (modelled on A8Group) on per-layer launches with the position from the host:
-    // the persistent engines, the XCD objects and the captured graphs are not used, exactly as under act_int8.  Refused with a reason: a TP rank, int8 activations, a
-    // hot-row mask (and each of those while an adapter is attached), save_kun, a rank or shape kf_lora_apply_status refuses.
+    // the model (an eager-only mode).  Its own checks: s finite, one rank and one s, a rank and shape kf_lora_apply_status serves, 16-byte alignment.
     int n_adapters = 0, lora_r = 0;
     float lora_s = 0.0f;
+    std::array<SLP*, 7> LayerMatrices(int layer) const;  // q k v o gate up down, the order of kf_engine_layer.w and of the C entries' slots
+    SLP* LayerMatrix(int layer, int slot) const;  // one of them, or NULL
+    int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);
+    void ClearAdapters();
+    // What the eager-only layer bodies run for the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual`
+    // (may alias y[0]; n_w == 1) the products' residual epilogue; normed: [n][dim] for the bf16 route.  One quantisation (kf_act_quant_i8) when a matrix takes an integer
+    // route, one kf_rmsnorm when a matrix takes kf_linear, the product per matrix, then kf_lora_apply on the same y for the matrices that carry an adapter: one
+    // vector-form launch for the group when n == 1, a tile-form launch per adapted matrix otherwise.
+    int Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
     // int8 KV cache (kfh_set_kv_int8; include/kf_abi.h "int8 KV cache"): K / V rows live as int8 codes with one fp32 step per row and kv-head; a decode step runs
     // kf_norm_linear (q, raw k, raw v into scratch rows) -> kf_attn_block_kv8 -> kf_linear per layer -- still 5 launches with the FFN's two, eager or on captured graphs
     // (d_pos, position buckets) like any model the engine does not serve; token batches quantise their rows into the cache and attend to the dequantised rows of the
     // staging pair (kf_kv8_quant_rows, kf_kv8_dequant_rows, then the existing kf_attn_prefill).  The two caches are independent: switching converts nothing, the caller
-    // prefills again.  Refused with a reason, in both directions: a TP rank, the XCD objects, int8 activations, adapters, hot-row masks, fuse_level 0.
+    // prefills again.  Its own check: kf_attn_block_kv8_status.
     bool kv_int8 = false;
     int SetKVInt8(bool on, std::string& why);
-    bool per_layer() const { return act_int8 || n_adapters > 0; }  // what the step sequencing asks: eager per-layer launches, no engine, no graphs
-    SLP* LayerMatrix(int layer, int slot);  // q k v o gate up down = 0 .. 6, or NULL
-    int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);
-    void ClearAdapters();
-    // A8Group's contract with kf_rmsnorm + kf_linear for every matrix, then kf_lora_apply on the same y for those that carry an adapter: one vector-form launch for the
-    // group when n == 1, a tile-form launch per adapted matrix otherwise
-    int LoraGroup(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual);
+    // what Prefill and Score share: m tokens at positions pos.. as one token batch through the embedding and every layer (rows in gBUFF.bX); the ending -- the head on row
+    // `last` of the batch buffer, the state update leaves {next token, pos + 1}
+    int FlowChunk(const int* tokens, int m, int pos);
+    int FlowEnd(int last, int token, int pos);
+    int LayersAndHead(hGTensor cur);  // what EnqueueStep and ForwardOnRLS share: the embedded row through every layer's cuInfer, then the head
 };
 
 // What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their

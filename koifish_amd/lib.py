@@ -17,6 +17,7 @@ ENSEMBLE_AGGREGATION, ENSEMBLE_BRANCH = 0, 1   # kfh_gpt2_eval's mode
 QUANT_GROUP, QUANT_ROW_LUT, QUANT_ROW_RTN = 0, 1, 2  # kf_weight.quant
 CLIP_OFF, CLIP_REPORT, CLIP_TENSOR, CLIP_GLOBAL = 0, 1, 2, 3   # enum kf_clip_mode (0: the trainers' "off"; kf_grad_norms itself has no such mode)
 CLIP_MODES = {None: CLIP_OFF, "report": CLIP_REPORT, "tensor": CLIP_TENSOR, "global": CLIP_GLOBAL}
+MODES = ("TP", "ACT_INT8", "ADAPTERS", "KV_INT8", "HOT_MASK", "FUSE0")  # enum koifish::Mode (host/kf_host_modes.hpp), in precedence order
 NF4 = 1000  # not a typNUMBER: "Q4 with the normal-float quant card" (QUANT_MODE::RTNf) for the helpers that take a storage type
 
 # every symbol include/kf_abi.h declares (tests/test_abi_symbols.py checks the header against this list and the .so)
@@ -264,6 +265,10 @@ def load():
         for f in ("kfh_kv8_codes", "kfh_kv8_steps"):
             getattr(host, f).restype = C.c_void_p
             getattr(host, f).argtypes = [C.c_void_p, C.c_int]
+        # the mode table (host/kf_host_modes.hpp) without a device: bit m of `active` = mode m of MODES is on
+        host.kfhdbg_mode_refusal.argtypes = [C.c_uint, C.c_int, C.c_char_p, C.c_size_t]
+        host.kfhdbg_engine_refusal.argtypes = [C.c_uint, C.c_char_p, C.c_size_t]
+        host.kfhdbg_eager_only.argtypes = [C.c_uint]
         host.kfh_set_adapter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         host.kfh_clear_adapters.argtypes = [C.c_void_p]
         host.kfh_n_adapters.argtypes = [C.c_void_p]
