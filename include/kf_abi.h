@@ -792,7 +792,7 @@ int kf_xengine_set_head_tp(kf_ctx* ctx, kf_xengine* e, const kf_weight* const* h
  *     y = bf16_rn(step_x[t] * acc);  with bias: bf16_rn(step_x[t] * acc + bias[r]);  with residual: y = bf16(residual + bf16(..)), kf_linear's epilogue.
  *   The group ZERO is not part of this arithmetic: YinYang and the symmetric quantiser write zero = 0 (GeQuant.cpp:536-628); callers check it (Fish, at switch-on).
  * kf_act_quant_i8: x rows of dim bf16, ldx elements apart (ldx >= dim) -> q int8 [rows][dim], step fp32 [rows].
- * kf_linear_a8: y [nTok][ne0] as kf_linear writes it; residual [nTok][ne0] may alias y.  Refusals (kf::a8_plan, csrc/kf_a8_plan.h): any storage other than KF_T_SIGN /
+ * kf_linear_a8: y [nTok][ne0] as kf_linear writes it; residual [nTok][ne0] may alias y.  Refusals (kf::a8_plan, csrc/kf_a8.h): any storage other than KF_T_SIGN /
  * KF_BOOL1 / KF_T_BINARY in KF_QUANT_GROUP form KF_UNSUPPORTED_DATATYPE; lGroup != 128 or no gama KF_QUANT_ERR; ne1 % 128 != 0, ne0 < 1, nTok < 1 KF_INVALID_ARGS; data not
  * 16-byte aligned KF_BLAS_UNALIGN.  nTok > 1 runs the same kernel on tiles of token rows: the bits of nTok = 1.
  * With norm_w the prologue refuses what kf_rmsnorm refuses (an odd dim: KF_RMS_PARAMS).
@@ -805,8 +805,8 @@ int kf_linear_a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* 
  * [nTok] as kf_act_quant_i8 writes them, y bf16 [nTok][ne0], y = bf16(step_x * acc [+ bias]) then bf16(residual + bf16(y)); residual [nTok][ne0] may alias y (every
  * output element is read and written by one lane).  Any nTok >= 1 is served; token and row tails are masked.  Per 128-weight group an int32 accumulator starts from
  * zero and takes exactly that group (two MFMA steps); the lane that holds an output element folds I_g into its fp32 chain in ascending g: the definition above, so the
- * result equals kf_linear_a8's bit for bit whatever the tile, the grid or nTok.  The launch is kf::a8_tile_plan's (csrc/kf_a8_tile_plan.h); its refusals are
- * kf::a8_plan's, the ones listed above.
+ * result equals kf_linear_a8's bit for bit whatever the tile, the grid or nTok.  The launch is the tile route of kf::a8_plan (csrc/kf_a8.h); its refusals are
+ * the mat-vec route's, the ones listed above.
  * kf_linear_a8_tiles_status: what kf_linear_a8_tiles would answer for this weight and nTok, without a launch.
  * KF_A8_TILE_MIN: the token count from which callers that route (Fish::A8Group) send a batch to the tiles by default; below it, and for nTok = 1 always, kf_linear_a8. */
 enum { KF_A8_TILE_MIN = 32 };
@@ -830,11 +830,11 @@ int kf_linear_a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const f
  *   DEVIATIONS: (1) the weight is the affine STEP * (code - qBias) - ZERO WITHOUT the per-weight bf16 roundings of CU_Q128toX_ (bf16(bf16(step * (q - qBias)) - zero),
  *   T.cu:274): the result differs from the bf16-activation route by more than the activation quantisation.  (2) the activation quantiser's deviation is the one stated
  *   above (the absolute row maximum).
- * kf_linear_w4a8: the mat-vec on v_dot4c_i32_i8; y [nTok][ne0], residual [nTok][ne0] may alias y.  Refusals (kf::w4a8_plan, csrc/kf_w4a8_plan.h), in kf_linear_a8's order and
+ * kf_linear_w4a8: the mat-vec on v_dot4c_i32_i8; y [nTok][ne0], residual [nTok][ne0] may alias y.  Refusals (kf::a8_plan, csrc/kf_a8.h), in kf_linear_a8's order and
  * with its codes: any storage other than KF_Q4 in KF_QUANT_GROUP form (AutoAWQ included) KF_UNSUPPORTED_DATATYPE; lGroup != 128, no gama, or a qBias other than 0 / 8
  * KF_QUANT_ERR; ne1 % 128 != 0, ne0 < 1, nTok < 1 KF_INVALID_ARGS; data not 16-byte aligned KF_BLAS_UNALIGN.
  * kf_linear_w4a8_tiles: the same contract and the same bits on v_mfma_i32_16x16x64_i8, for token batches (any nTok >= 1 is served; token and row tails masked); the launch
- * is kf::w4a8_tile_plan's, its refusals are kf::w4a8_plan's.  q need not be 16-byte aligned.
+ * is the tile route of kf::a8_plan, its refusals are the mat-vec route's.  q need not be 16-byte aligned.
  * kf_linear_w4a8_status / kf_linear_w4a8_tiles_status: what the entry would answer for this weight and nTok, without a launch: the served-storage rule for callers that
  * route (Fish asks it per layer matrix while kfh_set_act_int8_q4 is on).  KF_A8_TILE_MIN is the default threshold of this family too. */
 int kf_linear_w4a8_status(const kf_weight* w, int nTok);

@@ -11,9 +11,7 @@
 
 #include <vector>
 
-#include "kf_a8_plan.h"
-#include "kf_a8_tile_plan.h"
-#include "kf_w4a8_plan.h"
+#include "kf_a8.h"
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
@@ -1749,7 +1747,7 @@ int kfdbg_engine_set_delays(kf_engine* e, const int* d6) {
     kf::engine_set_delays(e->h, d6);
     return 0;
 }
-// ---- int8 activations for 1-bit / ternary weights (include/kf_abi.h): the quantiser and the integer mat-vec; every launch decision is kf::a8_plan's
+// ---- int8 activations (include/kf_abi.h "int8 activations", "int8 activations for 4-bit layers"): the quantiser, then the products
 int kf_act_quant_i8(kf_ctx* c, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w, float eps, int rows, int dim, int8_t* q, float* step) {
     CHKCTX(c);
     if (!x || !q || !step) return fail(KF_INVALID_ARGS, "kf_act_quant_i8: null pointer");
@@ -1757,75 +1755,91 @@ int kf_act_quant_i8(kf_ctx* c, const kf_bf16* x, int64_t ldx, const kf_bf16* nor
     if (norm_w && dim % 2 != 0) return fail(KF_RMS_PARAMS, "kf_act_quant_i8: rmsnorm dim %d is not divisible by 2", dim); /* what kf_rmsnorm refuses, the prologue refuses */
     RET(kf::act_quant_launch(c->stream, x, ldx, norm_w, eps, rows, dim, q, step));
 }
-int kf_linear_a8_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::a8_plan(kf::A8Problem{kf::mat_of(w), nTok}).status : KF_INVALID_ARGS; }
-int kf_linear_a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
-    CHKCTX(c);
-    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_a8: null weight");
-    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_a8: null pointer");
-    const kf::A8Plan p = kf::a8_plan(kf::A8Problem{kf::mat_of(w), nTok});
-    if (p.status == KF_UNSUPPORTED_DATATYPE)
-        return fail(p.status, "kf_linear_a8: weight type %d (quant mode %d%s) has no integer form: served are KF_T_SIGN (%d), KF_BOOL1 (%d), KF_T_BINARY (%d) in group storage", w->type,
-                    w->quant, (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_T_SIGN, KF_BOOL1, KF_T_BINARY);
-    if (p.status == KF_QUANT_ERR) return fail(p.status, "kf_linear_a8: group size %d (must be 128) or gama missing", w->lGroup);
-    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_a8: weight data not 16-byte aligned");
-    if (p.status != KF_OK) return fail(p.status, "kf_linear_a8: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
-    RET(kf::a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+// the products of the two families (1-bit / ternary: kf_linear_a8*, 4-bit: kf_linear_w4a8*) on the two routes: every launch decision is kf::a8_plan's (kf_a8.h).  An entry
+// serves its own family: the other family's storage has no form there, whatever else is wrong with it
+static kf::A8Plan a8_family_plan(int family, const kf::A8Problem& P) {
+    kf::A8Plan p = kf::a8_plan(P);
+    if (p.family != family) p = kf::A8Plan{}, p.status = KF_UNSUPPORTED_DATATYPE;
+    return p;
 }
-// the same product on int8 MFMA tiles: every launch decision is kf::a8_tile_plan's, whose refusals are kf::a8_plan's
-int kf_linear_a8_tiles_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::a8_tile_plan(kf::A8Problem{kf::mat_of(w), nTok}).status : KF_INVALID_ARGS; }
-int kf_linear_a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
-    CHKCTX(c);
-    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_a8_tiles: null weight");
-    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_a8_tiles: null pointer");
-    const kf::A8TilePlan p = kf::a8_tile_plan(kf::A8Problem{kf::mat_of(w), nTok});
-    if (p.status == KF_UNSUPPORTED_DATATYPE)
-        return fail(p.status, "kf_linear_a8_tiles: weight type %d (quant mode %d%s) has no integer form: served are KF_T_SIGN (%d), KF_BOOL1 (%d), KF_T_BINARY (%d) in group storage",
-                    w->type, w->quant, (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_T_SIGN, KF_BOOL1, KF_T_BINARY);
-    if (p.status == KF_QUANT_ERR) return fail(p.status, "kf_linear_a8_tiles: group size %d (must be 128) or gama missing", w->lGroup);
-    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_a8_tiles: weight data not 16-byte aligned");
-    if (p.status != KF_OK) return fail(p.status, "kf_linear_a8_tiles: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", w->ne0, w->ne1, nTok);
-    RET(kf::a8_tiles_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
-}
-
-// ---- int8 activations for 4-bit layers (include/kf_abi.h): every launch decision is kf::w4a8_plan's / kf::w4a8_tile_plan's
-static kf::W4A8Problem w4a8_problem(const kf_weight* w, int nTok) { return kf::W4A8Problem{kf::mat_of(w), nTok, w->qBias}; }
-static int w4a8_refusal(const char* entry, int status, const kf_weight* w, int nTok) {
+static kf::A8Plan a8_entry_plan(int family, int route, const kf_weight* w, int nTok) { return a8_family_plan(family, kf::A8Problem{kf::mat_of(w), nTok, w->qBias, route}); }
+static int a8_status(int family, int route, const kf_weight* w, int nTok) { return (w && w->data) ? a8_entry_plan(family, route, w, nTok).status : KF_INVALID_ARGS; }
+static int a8_refusal(const char* entry, int family, int status, const kf_weight* w, int nTok) {
+    const bool q4 = family == kf::A8_Q4;
+    const char* awq = (w->qzeros || w->qscales) ? ", AutoAWQ" : "";
+    if (status == KF_UNSUPPORTED_DATATYPE && q4)
+        return fail(status, "%s: weight type %d (quant mode %d%s) has no W4.A8 form: served is KF_Q4 (%d) in group storage", entry, w->type, w->quant, awq, KF_Q4);
     if (status == KF_UNSUPPORTED_DATATYPE)
-        return fail(status, "%s: weight type %d (quant mode %d%s) has no W4.A8 form: served is KF_Q4 (%d) in group storage", entry, w->type, w->quant,
-                    (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_Q4);
-    if (status == KF_QUANT_ERR) return fail(status, "%s: group size %d (must be 128), gama missing, or qBias %d (must be 0 or 8)", entry, w->lGroup, w->qBias);
+        return fail(status, "%s: weight type %d (quant mode %d%s) has no integer form: served are KF_T_SIGN (%d), KF_BOOL1 (%d), KF_T_BINARY (%d) in group storage", entry, w->type,
+                    w->quant, awq, KF_T_SIGN, KF_BOOL1, KF_T_BINARY);
+    if (status == KF_QUANT_ERR && q4) return fail(status, "%s: group size %d (must be 128), gama missing, or qBias %d (must be 0 or 8)", entry, w->lGroup, w->qBias);
+    if (status == KF_QUANT_ERR) return fail(status, "%s: group size %d (must be 128) or gama missing", entry, w->lGroup);
     if (status == KF_BLAS_UNALIGN) return fail(status, "%s: weight data not 16-byte aligned", entry);
     return fail(status, "%s: %d x %d, nTok=%d: rows of whole 128-weight groups, at least one row and one token", entry, w->ne0, w->ne1, nTok);
 }
-int kf_linear_w4a8_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::w4a8_plan(w4a8_problem(w, nTok)).status : KF_INVALID_ARGS; }
+static int a8_entry(const char* entry, int family, int route, kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias,
+                    const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "%s: null weight", entry);
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "%s: null pointer", entry);
+    const kf::A8Plan p = a8_entry_plan(family, route, w, nTok);
+    if (p.status != KF_OK) return a8_refusal(entry, family, p.status, w, nTok);
+    RET(kf::a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+int kf_linear_a8_status(const kf_weight* w, int nTok) { return a8_status(kf::A8_LOWBIT, kf::A8_MATVEC, w, nTok); }
+int kf_linear_a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    return a8_entry("kf_linear_a8", kf::A8_LOWBIT, kf::A8_MATVEC, c, w, q, step, y, bias, residual, nTok);
+}
+int kf_linear_a8_tiles_status(const kf_weight* w, int nTok) { return a8_status(kf::A8_LOWBIT, kf::A8_TILES, w, nTok); }
+int kf_linear_a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    return a8_entry("kf_linear_a8_tiles", kf::A8_LOWBIT, kf::A8_TILES, c, w, q, step, y, bias, residual, nTok);
+}
+int kf_linear_w4a8_status(const kf_weight* w, int nTok) { return a8_status(kf::A8_Q4, kf::A8_MATVEC, w, nTok); }
 int kf_linear_w4a8(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
-    CHKCTX(c);
-    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_w4a8: null weight");
-    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_w4a8: null pointer");
-    const kf::W4A8Plan p = kf::w4a8_plan(w4a8_problem(w, nTok));
-    if (p.status != KF_OK) return w4a8_refusal("kf_linear_w4a8", p.status, w, nTok);
-    RET(kf::w4a8_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+    return a8_entry("kf_linear_w4a8", kf::A8_Q4, kf::A8_MATVEC, c, w, q, step, y, bias, residual, nTok);
 }
-int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::w4a8_tile_plan(w4a8_problem(w, nTok)).status : KF_INVALID_ARGS; }
+int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok) { return a8_status(kf::A8_Q4, kf::A8_TILES, w, nTok); }
 int kf_linear_w4a8_tiles(kf_ctx* c, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
-    CHKCTX(c);
-    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_w4a8_tiles: null weight");
-    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_w4a8_tiles: null pointer");
-    const kf::W4A8TilePlan p = kf::w4a8_tile_plan(w4a8_problem(w, nTok));
-    if (p.status != KF_OK) return w4a8_refusal("kf_linear_w4a8_tiles", p.status, w, nTok);
-    RET(kf::w4a8_tiles_launch(c->stream, p, w, q, step, y, bias, residual, nTok));
+    return a8_entry("kf_linear_w4a8_tiles", kf::A8_Q4, kf::A8_TILES, c, w, q, step, y, bias, residual, nTok);
 }
-// the plans kf::w4a8_plan / kf::w4a8_tile_plan make (no HIP call): tests/test_w4a8_cpu.py
-int kfdbg_w4a8_plan(const kf::W4A8Problem* P, kf::W4A8Plan* out) {
+// the plan kf::a8_plan makes for a problem, either family, either route (no HIP call): tests/a8_plan_mirror.py
+int kfdbg_a8_route_plan(const kf::A8Problem* P, kf::A8Plan* out) {
     if (!P || !out) return -1;
-    *out = kf::w4a8_plan(*P);
+    *out = kf::a8_plan(*P);
     return 0;
 }
-int kfdbg_w4a8_tile_plan(const kf::W4A8Problem* P, kf::W4A8TilePlan* out) {
-    if (!P || !out) return -1;
-    *out = kf::w4a8_tile_plan(*P);
+// the four per-entry exports of earlier versions keep their names and layouts for callers built against them (tests/a8_plan_mirror.py check_views).  Each is a view of
+// the one plan for an entry's problem: a route's figures only; the second word is `bits` for the low-bit family and `qbias` for q4, whose problem carries it
+struct A8DbgProblem {
+    kf::GemmMat w;
+    int nTok;
+};
+struct W4A8DbgProblem {
+    kf::GemmMat w;
+    int nTok, qbias;
+};
+struct A8DbgMatvec {
+    int status, bits_or_qbias, order, n_groups, lpr_log2, iters, rows_per_wave, rows_per_wg, tok_tile, tok_tiles, grid_x, grid_y, block, lds;
+};
+struct A8DbgTiles {
+    int status, bits_or_qbias, order, n_groups, row_tile, tok_tile, waves, mfma_tok, chunk, grid_x, grid_y, block, lds, min_tok;
+};
+static int a8_dbg_matvec(int family, const kf::GemmMat& w, int nTok, int qbias, A8DbgMatvec* out) {
+    const kf::A8Plan p = a8_family_plan(family, kf::A8Problem{w, nTok, qbias, kf::A8_MATVEC});
+    *out = {p.status, family == kf::A8_Q4 ? p.qbias : p.bits, p.order, p.n_groups, p.lpr_log2, p.iters, p.rows_per_wave, p.rows_per_wg,
+            p.tok_tile, p.tok_tiles, p.grid_x, p.grid_y, p.block, p.lds};
     return 0;
 }
+static int a8_dbg_tiles(int family, const kf::GemmMat& w, int nTok, int qbias, A8DbgTiles* out) {
+    const kf::A8Plan p = a8_family_plan(family, kf::A8Problem{w, nTok, qbias, kf::A8_TILES});
+    *out = {p.status, family == kf::A8_Q4 ? p.qbias : p.bits, p.order, p.n_groups, p.row_tile, p.tok_tile, p.waves, p.mfma_tok, p.chunk,
+            p.grid_x, p.grid_y, p.block, p.lds, kf::A8T_MIN_TOK};
+    return 0;
+}
+int kfdbg_a8_plan(const A8DbgProblem* P, A8DbgMatvec* out) { return (P && out) ? a8_dbg_matvec(kf::A8_LOWBIT, P->w, P->nTok, 0, out) : -1; }
+int kfdbg_a8_tile_plan(const A8DbgProblem* P, A8DbgTiles* out) { return (P && out) ? a8_dbg_tiles(kf::A8_LOWBIT, P->w, P->nTok, 0, out) : -1; }
+int kfdbg_w4a8_plan(const W4A8DbgProblem* P, A8DbgMatvec* out) { return (P && out) ? a8_dbg_matvec(kf::A8_Q4, P->w, P->nTok, P->qbias, out) : -1; }
+int kfdbg_w4a8_tile_plan(const W4A8DbgProblem* P, A8DbgTiles* out) { return (P && out) ? a8_dbg_tiles(kf::A8_Q4, P->w, P->nTok, P->qbias, out) : -1; }
 
 // the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py
 int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
@@ -1851,12 +1865,6 @@ int kfdbg_kv8_plan(int n_head, int n_kv, int hd, int pos, int kv_stride, kf::Att
     *out = kf::attn_plan(kv8_problem(n_head, n_kv, hd, pos, kv_stride));
     return 0;
 }
-// the plan kf::a8_plan makes for an integer mat-vec (no HIP call): tests/test_a8_plan_cpu.py
-int kfdbg_a8_plan(const kf::A8Problem* P, kf::A8Plan* out) {
-    if (!P || !out) return -1;
-    *out = kf::a8_plan(*P);
-    return 0;
-}
 // the table kf::gradnorm_plan lays out for a list of tensor lengths (no HIP call): wg0_out [n_tensors + 1], and for every workgroup the tensor gradnorm_find gives it
 // (owner_out [total_wg], may be NULL): tests/test_gradnorm_cpu.py
 int kfdbg_gradnorm_plan(int n_tensors, const long long* n, kf::GradNormPlan* out, int* wg0_out, int* owner_out) {
@@ -1869,12 +1877,6 @@ int kfdbg_gradnorm_plan(int n_tensors, const long long* n, kf::GradNormPlan* out
         for (int i = 0; i <= n_tensors; i++) tab[i].wg0 = wg0_out[i];
         for (int wg = 0; wg < out->total_wg; wg++) owner_out[wg] = kf::gradnorm_find(tab.data(), n_tensors, wg);
     }
-    return 0;
-}
-// the plan kf::a8_tile_plan makes for the same product on MFMA tiles (no HIP call): tests/test_a8_tiles_cpu.py
-int kfdbg_a8_tile_plan(const kf::A8Problem* P, kf::A8TilePlan* out) {
-    if (!P || !out) return -1;
-    *out = kf::a8_tile_plan(*P);
     return 0;
 }
 // the plan kf::lora_plan makes for an adapter (no HIP call): tests/test_lora_cpu.py

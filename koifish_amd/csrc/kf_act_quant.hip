@@ -1,7 +1,7 @@
 // kf_act_quant.hip -- kf_act_quant_i8: the per-token symmetric int8 activation quantiser in front of the integer mat-vec (huTensor::Quant4A -> CU_X2A8_, T.cu:24-102,
 // with the ABSOLUTE row maximum: include/kf_abi.h "int8 activations").  One workgroup per row; an optional RMSNorm prologue norms the row and rounds it to bf16 exactly
 // as kf_rmsnorm stores it (rmsnorm_kernel, kf_ops.hip) before it is quantised, so q | k | v and gate | up share one launch for norm + quantise.
-#include "kf_a8_plan.h"
+#include "kf_a8.h"
 
 namespace kf {
 

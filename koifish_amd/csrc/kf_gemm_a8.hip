@@ -1,18 +1,18 @@
 // kf_gemm_a8.hip -- kf_linear_a8_tiles: 1-bit / ternary weights times int8 activations of a token batch on v_mfma_i32_16x16x64_i8 (include/kf_abi.h "int8 activations";
-// the launch is kf::a8_tile_plan's).  The arithmetic is kf_linear_a8's (kf_gemv_a8.hip), bit for bit:
+// the launch is kf::a8_plan's tile route, kf_a8.h).  The arithmetic is kf_linear_a8's (kf_gemv_a8.hip), bit for bit:
 //   * a wave owns 16 output rows -- the A operand -- and NT tiles of 16 tokens -- the B operands; a 128-weight group is TWO MFMA steps of K = 64 into an int32x4 accumulator
 //     that starts from zero, so I_g is that group's exact integer sum and nothing else.  No accumulator runs across a group boundary.
 //   * the lane that holds output element (row, token) of the C tile (col = lane & 15 = the token, row = 4 * (lane >> 4) + register) folds I_g into ITS fp32 chain
 //     acc = acc + step_w[g] * I_g, groups ascending (A8_ORDER_CHAIN): one lane, one chain per output element, no split-K, no hand-over between lanes or waves.
 //   * operands: inside a group any pairing of codes and activations gives the same I_g, so all that matters is that lane quarter h = lane >> 4 of A and of B carry the SAME
-//     16 elements in the same order in each step.  Quarter h, step s takes the staged dwords 8h + 4s .. 8h + 4s + 3 of the group (staged order: a8t_elem, the order the masks
+//     16 elements in the same order in each step.  Quarter h, step s takes the staged dwords 8h + 4s .. 8h + 4s + 3 of the group (staged order: a8_elem, the order the masks
 //     (D >> s) & 0x01010101 and (D >> 2c) & 0x03030303 leave codes in -- kf_gemv_a8.hip): of a 1-bit block that is dword h, bits 4s .. 4s + 3; of a 2-bit group block
 //     h >> 1, dword 2 (h & 1) + s, codes 0 .. 3.  A lane loads 4 (1-bit) or 8 (2-bit) bytes of weights per group and makes its eight operand dwords with a shift and a mask each.
 //   * codes are multiplied as they are stored; the ternary bias comes off as qBias * sum(q of the group), formed once at staging (exact, as kf_gemv_a8.hip).
 //   * activations: staged per chunk of at most A8T_CHUNK groups for every token of the workgroup's tile, 36 dwords per (group, token) -- 32 staged dwords, the sum, pad --
 //     so that the 16 tokens of a B read sit on distinct banks.  A thread stages whole groups: eight 16-byte loads, 4 x 4 byte transposes on v_perm_b32.  The loads of
 //     chunk c + 1 (activations and the lane's weight dwords) are issued before chunk c is multiplied and land in registers meanwhile.
-#include "kf_a8_tile_plan.h"
+#include "kf_a8.h"
 
 namespace kf {
 
@@ -29,14 +29,6 @@ struct A8TArgs {
     int M, K, G, nTok, chunk, qBias, q_al;
 };
 
-constexpr int A8T_GDW = A8_GROUP_LDS / 4; /* dwords of LDS per group and token row; dword 32 = qBias * the group's sum of q */
-
-// element (inside its group) whose activation sits in byte b of staged dword j (kf_gemv_a8.hip a8_elem: the same order)
-template <int BITS>
-__device__ __forceinline__ int a8t_elem(int j, int b) {
-    if (BITS == 1) return (3 - (j >> 3)) * 32 + 31 - 8 * b - (j & 7);
-    return (j >> 4) * 64 + (3 - ((j >> 2) & 3)) * 16 + 15 - 4 * b - (j & 3);
-}
 // o[v] = { byte 3 - v of s0, of s1, of s2, of s3 } (bytes 0 .. 3)
 __device__ __forceinline__ void a8t_tr4(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t* o) {
     const uint32_t ah = __builtin_amdgcn_perm(s1, s0, 0x06020703u), bh = __builtin_amdgcn_perm(s3, s2, 0x06020703u); /* {s0.3, s1.3, s0.2, s1.2} */
@@ -52,9 +44,9 @@ __global__ void __launch_bounds__(A8T_THREADS) a8_tiles_kernel(A8TArgs a) {
     constexpr int TT = NT * A8T_TOK_PER_MFMA;
     constexpr int U = (TT * A8T_CHUNK + A8T_THREADS - 1) / A8T_THREADS; /* (group, token) units a thread stages per chunk */
     constexpr int WDW = BITS;                                           /* weight dwords a lane loads per group */
-    extern __shared__ __align__(16) uint32_t lds[]; /* qs [chunk][TT][A8T_GDW], then sws [A8T_ROW_TILE][chunk] fp32 */
+    extern __shared__ __align__(16) uint32_t lds[]; /* qs [chunk][TT][A8_GDW], then sws [A8T_ROW_TILE][chunk] fp32 */
     uint32_t* qs = lds;
-    float* sws = reinterpret_cast<float*>(lds + a.chunk * TT * A8T_GDW);
+    float* sws = reinterpret_cast<float*>(lds + a.chunk * TT * A8_GDW);
     const int G = a.G, tok0 = blockIdx.y * TT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 4, c16 = lane & 15;
     const long wg_row0 = (long)blockIdx.x * A8T_ROW_TILE;
@@ -106,7 +98,7 @@ __global__ void __launch_bounds__(A8T_THREADS) a8_tiles_kernel(A8TArgs a) {
         for (int uu = 0; uu < U; uu++) {
             const int u = threadIdx.x + uu * A8T_THREADS;
             if (u >= gc * TT) continue;
-            uint32_t* dst = qs + (size_t)u * A8T_GDW; /* u = gl * TT + t */
+            uint32_t* dst = qs + (size_t)u * A8_GDW; /* u = gl * TT + t */
             uint32_t o[32];
             int s = 0;
             if (a.q_al) {
@@ -139,7 +131,7 @@ __global__ void __launch_bounds__(A8T_THREADS) a8_tiles_kernel(A8TArgs a) {
                     uint32_t v = 0;
                     if (live) {
 #pragma unroll
-                        for (int b = 0; b < 4; b++) v |= (uint32_t)qb[a8t_elem<BITS>(j, b)] << (8 * b);
+                        for (int b = 0; b < 4; b++) v |= (uint32_t)qb[a8_elem<BITS>(j, b)] << (8 * b);
                     }
                     o[j] = v;
                     s = __builtin_amdgcn_sdot4(0x01010101, (int)v, s, false);
@@ -173,7 +165,7 @@ __global__ void __launch_bounds__(A8T_THREADS) a8_tiles_kernel(A8TArgs a) {
             for (int r = 0; r < 4; r++) sw[r] = sws[(wave * A8T_ROWS_PER_WAVE + 4 * h + r) * a.chunk + gl];
 #pragma unroll
             for (int t = 0; t < NT; t++) {
-                const uint32_t* qg = qs + (size_t)(gl * TT + t * A8T_TOK_PER_MFMA + c16) * A8T_GDW;
+                const uint32_t* qg = qs + (size_t)(gl * TT + t * A8T_TOK_PER_MFMA + c16) * A8_GDW;
                 const u32x4 b0 = *reinterpret_cast<const u32x4*>(qg + 8 * h), b1 = *reinterpret_cast<const u32x4*>(qg + 8 * h + 4);
                 i32x4 I = {0, 0, 0, 0};
                 I = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], __builtin_bit_cast(i32x4, b0), I, 0, 0, 0);
@@ -195,41 +187,26 @@ __global__ void __launch_bounds__(A8T_THREADS) a8_tiles_kernel(A8TArgs a) {
         for (int r = 0; r < 4; r++) {
             const long row = orow0 + r;
             if (row >= a.M) break;
-            const size_t o = (size_t)tok * a.M + row;
-            float v = sx * acc[t][r];
-            if (a.bias) v = v + bf2f(a.bias[row]);
-            uint16_t y = f2bf(v);
-            if (a.residual) y = f2bf(bf2f(a.residual[o]) + bf2f(y)); /* CU_add3: bf16(x + bf16(W.x)), as kf_linear; read and written by this lane alone (residual may be y) */
-            a.y[o] = y;
+            a8_store(a.y, a.bias, a.residual, sx, acc[t][r], row, (size_t)tok * a.M + row);
         }
     }
 }
 
-int a8_tiles_launch(hipStream_t st, const A8TilePlan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual,
-                    int nTok) {
-    if (p.status != KF_OK) return p.status;
+int a8_tiles_run(hipStream_t st, const A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
     A8TArgs a;
     a.w = reinterpret_cast<const uint32_t*>(w->data);
     a.stepw = w->gama + w->ne0 + w->ne1 + (size_t)w->ne0 * w->ne1 / w->lGroup; /* gama_T(STEP), GTensor.cpp:456-510 */
     a.q = q, a.stepx = step, a.y = y, a.bias = bias, a.residual = residual;
-    a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.chunk = p.chunk, a.qBias = w->qBias;
+    a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.chunk = p.chunk, a.qBias = p.qbias;
     a.q_al = ((uintptr_t)q & 15) == 0; /* K is a multiple of 128: every row and group then starts 16-byte aligned */
-    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kern) {
-        if (p.lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, grid, block, p.lds, st, a);
-    };
     if (p.bits == 1) {
-        if (p.mfma_tok == 1) go(a8_tiles_kernel<1, 1>);
-        else if (p.mfma_tok == 2) go(a8_tiles_kernel<1, 2>);
-        else go(a8_tiles_kernel<1, 4>);
-    } else {
-        if (p.mfma_tok == 1) go(a8_tiles_kernel<2, 1>);
-        else if (p.mfma_tok == 2) go(a8_tiles_kernel<2, 2>);
-        else go(a8_tiles_kernel<2, 4>);
+        if (p.mfma_tok == 1) return a8_go(a8_tiles_kernel<1, 1>, p, st, a);
+        if (p.mfma_tok == 2) return a8_go(a8_tiles_kernel<1, 2>, p, st, a);
+        return a8_go(a8_tiles_kernel<1, 4>, p, st, a);
     }
-    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? KF_OK : KF_HIP_CHECK;
+    if (p.mfma_tok == 1) return a8_go(a8_tiles_kernel<2, 1>, p, st, a);
+    if (p.mfma_tok == 2) return a8_go(a8_tiles_kernel<2, 2>, p, st, a);
+    return a8_go(a8_tiles_kernel<2, 4>, p, st, a);
 }
 
 }  // namespace kf

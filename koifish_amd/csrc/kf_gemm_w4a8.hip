@@ -1,5 +1,5 @@
 // kf_gemm_w4a8.hip -- kf_linear_w4a8_tiles: 4-bit group weights times int8 activations of a token batch on v_mfma_i32_16x16x64_i8 (include/kf_abi.h "int8 activations
-// for 4-bit layers"; the launch is kf::w4a8_tile_plan's).  The arithmetic is kf_linear_w4a8's (kf_gemv_w4a8.hip), bit for bit; the shape is kf_gemm_a8.hip's:
+// for 4-bit layers"; the launch is kf::a8_plan's tile route, kf_a8.h).  The arithmetic is kf_linear_w4a8's (kf_gemv_w4a8.hip), bit for bit; the shape is kf_gemm_a8.hip's:
 //   * a wave owns 16 output rows -- the A operand -- and NT tiles of 16 tokens -- the B operands; a 128-weight group is TWO MFMA steps of K = 64 into an int32x4 accumulator
 //     that starts from zero, so it holds that group's exact sum of code * q and nothing else.  No accumulator runs across a group boundary.
 //   * the lane that holds output element (row, token) of the C tile (col = lane & 15 = the token, row = 4 * (lane >> 4) + register) takes qBias * S_g off, computes
@@ -13,7 +13,7 @@
 //     so that the 16 tokens of a B read sit on distinct banks.  A thread stages whole groups: eight 16-byte loads, two v_perm_b32 per eight elements.  The loads of chunk
 //     c + 1 (activations and the lane's weight blocks) are issued before chunk c is multiplied and land in registers meanwhile.  STEP and ZERO of the workgroup's rows are
 //     staged per chunk as fp32.
-#include "kf_w4a8_plan.h"
+#include "kf_a8.h"
 
 namespace kf {
 
@@ -31,15 +31,13 @@ struct W4A8TArgs {
     int M, K, G, nTok, chunk, qBias, q_al;
 };
 
-constexpr int W4A8T_GDW = A8_GROUP_LDS / 4; /* dwords of LDS per group and token row; dword 32 = the group's sum of q */
-
 template <int NT>
 __global__ void __launch_bounds__(A8T_THREADS) w4a8_tiles_kernel(W4A8TArgs a) {
     constexpr int TT = NT * A8T_TOK_PER_MFMA;
     constexpr int U = (TT * A8T_CHUNK + A8T_THREADS - 1) / A8T_THREADS; /* (group, token) units a thread stages per chunk */
-    extern __shared__ __align__(16) uint32_t lds[]; /* qs [chunk][TT][W4A8T_GDW], then sws, zws [A8T_ROW_TILE][chunk] fp32 */
+    extern __shared__ __align__(16) uint32_t lds[]; /* qs [chunk][TT][A8_GDW], then sws, zws [A8T_ROW_TILE][chunk] fp32 */
     uint32_t* qs = lds;
-    float* sws = reinterpret_cast<float*>(lds + a.chunk * TT * W4A8T_GDW);
+    float* sws = reinterpret_cast<float*>(lds + a.chunk * TT * A8_GDW);
     float* zws = sws + A8T_ROW_TILE * a.chunk;
     const int G = a.G, tok0 = blockIdx.y * TT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 4, c16 = lane & 15;
@@ -86,7 +84,7 @@ __global__ void __launch_bounds__(A8T_THREADS) w4a8_tiles_kernel(W4A8TArgs a) {
         for (int uu = 0; uu < U; uu++) {
             const int u = threadIdx.x + uu * A8T_THREADS;
             if (u >= gc * TT) continue;
-            uint32_t* dst = qs + (size_t)u * W4A8T_GDW; /* u = gl * TT + t */
+            uint32_t* dst = qs + (size_t)u * A8_GDW; /* u = gl * TT + t */
             uint32_t o[32];
             int s = 0;
             if (a.q_al) {
@@ -146,7 +144,7 @@ __global__ void __launch_bounds__(A8T_THREADS) w4a8_tiles_kernel(W4A8TArgs a) {
             }
 #pragma unroll
             for (int t = 0; t < NT; t++) {
-                const uint32_t* qg = qs + (size_t)(gl * TT + t * A8T_TOK_PER_MFMA + c16) * W4A8T_GDW;
+                const uint32_t* qg = qs + (size_t)(gl * TT + t * A8T_TOK_PER_MFMA + c16) * A8_GDW;
                 const u32x4 b0 = *reinterpret_cast<const u32x4*>(qg + 8 * h), b1 = *reinterpret_cast<const u32x4*>(qg + 8 * h + 4);
                 i32x4 I = {0, 0, 0, 0};
                 I = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0], __builtin_bit_cast(i32x4, b0), I, 0, 0, 0);
@@ -175,19 +173,12 @@ __global__ void __launch_bounds__(A8T_THREADS) w4a8_tiles_kernel(W4A8TArgs a) {
         for (int r = 0; r < 4; r++) {
             const long row = orow0 + r;
             if (row >= a.M) break;
-            const size_t o = (size_t)tok * a.M + row;
-            float v = sx * acc[t][r];
-            if (a.bias) v = v + bf2f(a.bias[row]);
-            uint16_t y = f2bf(v);
-            if (a.residual) y = f2bf(bf2f(a.residual[o]) + bf2f(y)); /* CU_add3: bf16(x + bf16(W.x)), as kf_linear; read and written by this lane alone (residual may be y) */
-            a.y[o] = y;
+            a8_store(a.y, a.bias, a.residual, sx, acc[t][r], row, (size_t)tok * a.M + row);
         }
     }
 }
 
-int w4a8_tiles_launch(hipStream_t st, const W4A8TilePlan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual,
-                      int nTok) {
-    if (p.status != KF_OK) return p.status;
+int w4a8_tiles_run(hipStream_t st, const A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
     W4A8TArgs a;
     a.w = reinterpret_cast<const u32x4*>(w->data);
     a.zerow = w->gama + w->ne0 + w->ne1;                     /* gama_T(ZERO), GTensor.cpp:456-510 */
@@ -195,16 +186,9 @@ int w4a8_tiles_launch(hipStream_t st, const W4A8TilePlan& p, const kf_weight* w,
     a.q = q, a.stepx = step, a.y = y, a.bias = bias, a.residual = residual;
     a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.chunk = p.chunk, a.qBias = p.qbias;
     a.q_al = ((uintptr_t)q & 15) == 0; /* K is a multiple of 128: every row and group then starts 16-byte aligned */
-    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kern) {
-        if (p.lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, grid, block, p.lds, st, a);
-    };
-    if (p.mfma_tok == 1) go(w4a8_tiles_kernel<1>);
-    else if (p.mfma_tok == 2) go(w4a8_tiles_kernel<2>);
-    else go(w4a8_tiles_kernel<4>);
-    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? KF_OK : KF_HIP_CHECK;
+    if (p.mfma_tok == 1) return a8_go(w4a8_tiles_kernel<1>, p, st, a);
+    if (p.mfma_tok == 2) return a8_go(w4a8_tiles_kernel<2>, p, st, a);
+    return a8_go(w4a8_tiles_kernel<4>, p, st, a);
 }
 
 }  // namespace kf

@@ -2,12 +2,12 @@
 //   * a lane owns one 128-weight group per step: one 16-byte Packed128 block of 1-bit codes, two of 2-bit codes (PackedQ.hpp:200-239), streamed with 16-byte loads.
 //   * the codes become packed int8 weights with a shift and a mask per FOUR weights -- (D >> s) & 0x01010101 picks bit s of every byte of a dword, (D >> 2k) & 0x03030303
 //     every byte's k-th 2-bit code -- and go straight into v_dot4c_i32_i8.  Which four elements that is follows from the blocks' most-significant-first order; the
-//     activations are staged in LDS ONCE per workgroup in exactly that order (a8_elem), so the loop holds no per-weight reversal.
+//     activations are staged in LDS ONCE per workgroup in exactly that order (kf_a8.h a8_elem), so the loop holds no per-weight reversal.
 //   * codes are dotted as they are stored; the bias (ternary: code - 1) comes off as qBias * sum(q of the group), a sum formed once at staging.
 //   * an unpacked block is dotted against every token row of the pass (TT rows: the XCfg::NB idea); token tiles are grid.y.
 //   * order: I_g is an exact int32 whatever lanes form it; the row's fp32 products step_w[g] * I_g are added in ONE ascending chain over g (A8_ORDER_CHAIN): each step the
 //     lanes of a row hand their products round and every lane adds them in lane = group order.  Lanes per row, grid and TT never touch a bit.
-#include "kf_a8_plan.h"
+#include "kf_a8.h"
 
 namespace kf {
 
@@ -21,15 +21,6 @@ struct A8Args {
     const uint16_t* residual;
     int M, K, G, nTok, lpr_log2, iters, qBias;
 };
-
-constexpr int A8_GDW = A8_GROUP_LDS / 4; /* dwords of LDS per group and token row; dword 32 = the group's sum of q */
-
-// element (inside its group) whose activation sits in byte b of staged dword j: the element whose code the mask of (dword, shift) j leaves in byte b
-template <int BITS>
-__device__ __forceinline__ int a8_elem(int j, int b) {
-    if (BITS == 1) return (3 - (j >> 3)) * 32 + 31 - 8 * b - (j & 7);                   /* j = dword * 8 + bit */
-    return (j >> 4) * 64 + (3 - ((j >> 2) & 3)) * 16 + 15 - 4 * b - (j & 3);            /* j = block * 16 + dword * 4 + code */
-}
 
 template <int BITS, int TT>
 __global__ void __launch_bounds__(A8_THREADS) a8_kernel(A8Args a) {
@@ -109,34 +100,21 @@ __global__ void __launch_bounds__(A8_THREADS) a8_kernel(A8Args a) {
 #pragma unroll
         for (int t = 0; t < TT; t++) {
             if (tok0 + t >= a.nTok) break;
-            const size_t o = (size_t)(tok0 + t) * a.M + row;
-            float v = a.stepx[tok0 + t] * acc[t];
-            if (a.bias) v = v + bf2f(a.bias[row]);
-            uint16_t r = f2bf(v);
-            if (a.residual) r = f2bf(bf2f(a.residual[o]) + bf2f(r)); /* CU_add3: bf16(x + bf16(W.x)), as kf_linear */
-            a.y[o] = r;
+            a8_store(a.y, a.bias, a.residual, a.stepx[tok0 + t], acc[t], row, (size_t)(tok0 + t) * a.M + row);
         }
     }
 }
 
-int a8_launch(hipStream_t st, const A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
-    if (p.status != KF_OK) return p.status;
+int a8_matvec_run(hipStream_t st, const A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
     A8Args a;
     a.w = reinterpret_cast<const u32x4*>(w->data);
     a.stepw = w->gama + w->ne0 + w->ne1 + (size_t)w->ne0 * w->ne1 / w->lGroup; /* gama_T(STEP), GTensor.cpp:456-510 */
     a.q = q, a.stepx = step, a.y = y, a.bias = bias, a.residual = residual;
-    a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.lpr_log2 = p.lpr_log2, a.iters = p.iters, a.qBias = w->qBias;
-    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kern) {
-        if (p.lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, grid, block, p.lds, st, a);
-    };
-    if (p.bits == 1 && p.tok_tile == 1) go(a8_kernel<1, 1>);
-    else if (p.bits == 1) go(a8_kernel<1, A8_TOK_TILE>);
-    else if (p.tok_tile == 1) go(a8_kernel<2, 1>);
-    else go(a8_kernel<2, A8_TOK_TILE>);
-    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? KF_OK : KF_HIP_CHECK;
+    a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.lpr_log2 = p.lpr_log2, a.iters = p.iters, a.qBias = p.qbias;
+    if (p.bits == 1 && p.tok_tile == 1) return a8_go(a8_kernel<1, 1>, p, st, a);
+    if (p.bits == 1) return a8_go(a8_kernel<1, A8_TOK_TILE>, p, st, a);
+    if (p.tok_tile == 1) return a8_go(a8_kernel<2, 1>, p, st, a);
+    return a8_go(a8_kernel<2, A8_TOK_TILE>, p, st, a);
 }
 
 }  // namespace kf

@@ -1,5 +1,5 @@
 // kf_gemv_w4a8.hip -- kf_linear_w4a8: 4-bit group weights times int8 activations on v_dot4c_i32_i8 (include/kf_abi.h "int8 activations for 4-bit layers"; the launch is
-// kf::w4a8_plan's).  The shape is kf_gemv_a8.hip's:
+// kf::a8_plan's, kf_a8.h).  The shape is kf_gemv_a8.hip's:
 //   * a lane owns one 128-weight group per step: four 16-byte Packed128 blocks of 32 codes (PackedQ.hpp:99-183), streamed with non-temporal 16-byte loads.
 //   * the codes become packed int8 operands with a shift and a mask per FOUR weights: (D >> 4c) & 0x0F0F0F0F, c = 0, 1, picks the low (c = 0) or high nibble of every byte
 //     of a dword.  A block's dword 3 holds elements 0 .. 7 with element 0 in bits 28 .. 31 (kf_gemv_blocks.h dot_q4_dword), so byte b of dword d holds element
@@ -10,7 +10,7 @@
 //     once (8 + 18 significant bits), ZERO * S_g is exact (8 + 14), the subtract rounds once -- and the row's terms are added in ONE ascending chain over g
 //     (A8_ORDER_CHAIN): each step the lanes of a row hand their c round and every lane adds them in lane = group order.  Lanes per row, grid and TT never touch a bit.
 //     The file is built with -ffp-contract=off (build.py): the multiply, the subtract and the add below stay three instructions.
-#include "kf_w4a8_plan.h"
+#include "kf_a8.h"
 
 namespace kf {
 
@@ -26,11 +26,9 @@ struct W4A8Args {
     int M, K, G, nTok, lpr_log2, iters, qBias;
 };
 
-constexpr int W4A8_GDW = A8_GROUP_LDS / 4; /* dwords of LDS per group and token row; dword 32 = the group's sum of q */
-
 template <int TT>
 __global__ void __launch_bounds__(A8_THREADS) w4a8_kernel(W4A8Args a) {
-    extern __shared__ __align__(16) uint32_t qs[]; /* [TT][G][W4A8_GDW] */
+    extern __shared__ __align__(16) uint32_t qs[]; /* [TT][G][A8_GDW] */
     const int G = a.G, tok0 = blockIdx.y * TT;
     for (int i = threadIdx.x; i < TT * G * 32; i += A8_THREADS) {
         const int tg = i >> 5, j = i & 31, t = tg / G, g = tg - t * G;
@@ -40,13 +38,13 @@ __global__ void __launch_bounds__(A8_THREADS) w4a8_kernel(W4A8Args a) {
 #pragma unroll
             for (int b = 0; b < 4; b++) v |= (uint32_t)qr[w4a8_elem(j, b)] << (8 * b);
         }
-        qs[tg * W4A8_GDW + j] = v;
+        qs[tg * A8_GDW + j] = v;
     }
     __syncthreads();
     for (int tg = threadIdx.x; tg < TT * G; tg += A8_THREADS) {
         int s = 0;
-        for (int j = 0; j < 32; j++) s = __builtin_amdgcn_sdot4(0x01010101, (int)qs[tg * W4A8_GDW + j], s, false);
-        qs[tg * W4A8_GDW + 32] = (uint32_t)s;
+        for (int j = 0; j < 32; j++) s = __builtin_amdgcn_sdot4(0x01010101, (int)qs[tg * A8_GDW + j], s, false);
+        qs[tg * A8_GDW + 32] = (uint32_t)s;
     }
     __syncthreads();
 
@@ -71,7 +69,7 @@ __global__ void __launch_bounds__(A8_THREADS) w4a8_kernel(W4A8Args a) {
             for (int k = 0; k < W4A8_BLOCKS; k++) W[k] = ld_nt(a.w + gi * W4A8_BLOCKS + k);
 #pragma unroll
             for (int t = 0; t < TT; t++) {
-                const uint32_t* qg = qs + (t * G + g) * W4A8_GDW;
+                const uint32_t* qg = qs + (t * G + g) * A8_GDW;
                 const u32x4* qv = reinterpret_cast<const u32x4*>(qg);
                 int s = 0;
 #pragma unroll
@@ -102,33 +100,19 @@ __global__ void __launch_bounds__(A8_THREADS) w4a8_kernel(W4A8Args a) {
 #pragma unroll
         for (int t = 0; t < TT; t++) {
             if (tok0 + t >= a.nTok) break;
-            const size_t o = (size_t)(tok0 + t) * a.M + row;
-            float v = a.stepx[tok0 + t] * acc[t];
-            if (a.bias) v = v + bf2f(a.bias[row]);
-            uint16_t r = f2bf(v);
-            if (a.residual) r = f2bf(bf2f(a.residual[o]) + bf2f(r)); /* CU_add3: bf16(x + bf16(W.x)), as kf_linear */
-            a.y[o] = r;
+            a8_store(a.y, a.bias, a.residual, a.stepx[tok0 + t], acc[t], row, (size_t)(tok0 + t) * a.M + row);
         }
     }
 }
 
-int w4a8_launch(hipStream_t st, const W4A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
-    if (p.status != KF_OK) return p.status;
+int w4a8_matvec_run(hipStream_t st, const A8Plan& p, const kf_weight* w, const int8_t* q, const float* step, uint16_t* y, const uint16_t* bias, const uint16_t* residual, int nTok) {
     W4A8Args a;
     a.w = reinterpret_cast<const u32x4*>(w->data);
     a.zerow = w->gama + w->ne0 + w->ne1;                        /* gama_T(ZERO), GTensor.cpp:456-510 */
     a.stepw = a.zerow + (size_t)w->ne0 * w->ne1 / w->lGroup;    /* gama_T(STEP) */
     a.q = q, a.stepx = step, a.y = y, a.bias = bias, a.residual = residual;
     a.M = w->ne0, a.K = w->ne1, a.G = p.n_groups, a.nTok = nTok, a.lpr_log2 = p.lpr_log2, a.iters = p.iters, a.qBias = p.qbias;
-    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kern) {
-        if (p.lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, grid, block, p.lds, st, a);
-    };
-    if (p.tok_tile == 1) go(w4a8_kernel<1>);
-    else go(w4a8_kernel<A8_TOK_TILE>);
-    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? KF_OK : KF_HIP_CHECK;
+    return p.tok_tile == 1 ? a8_go(w4a8_kernel<1>, p, st, a) : a8_go(w4a8_kernel<A8_TOK_TILE>, p, st, a);
 }
 
 }  // namespace kf

@@ -491,10 +491,8 @@ int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim
         const floatX* bias = s[i]->b ? ToX(s[i]->b) : nullptr;
         if (route[i]) {
             const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
-            if (route[i] == 2)
-                KF_TRY((tiles ? kf_linear_w4a8_tiles : kf_linear_w4a8)(ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
-            else
-                KF_TRY((tiles ? kf_linear_a8_tiles : kf_linear_a8)(ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
+            static constexpr decltype(&kf_linear_a8) entry[2][2] = {{kf_linear_a8, kf_linear_a8_tiles}, {kf_linear_w4a8, kf_linear_w4a8_tiles}}; /* [A8Route - 1][tiles] */
+            KF_TRY(entry[route[i] - 1][tiles](ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
             a8_count[tiles ? 0 : 1]++;
         } else
             KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], bias, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));

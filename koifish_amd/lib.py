@@ -174,14 +174,9 @@ def load():
         hip.kf_head_logprob.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_head_logprob_scratch_bytes.argtypes, hip.kf_head_logprob_scratch_bytes.restype = [C.POINTER(Weight), C.c_int], C.c_size_t
         hip.kf_act_quant_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        hip.kf_linear_a8_status.argtypes = [C.POINTER(Weight), C.c_int]
-        hip.kf_linear_a8.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        hip.kf_linear_a8_tiles_status.argtypes = [C.POINTER(Weight), C.c_int]
-        hip.kf_linear_a8_tiles.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        hip.kf_linear_w4a8_status.argtypes = [C.POINTER(Weight), C.c_int]
-        hip.kf_linear_w4a8.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        hip.kf_linear_w4a8_tiles_status.argtypes = [C.POINTER(Weight), C.c_int]
-        hip.kf_linear_w4a8_tiles.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        for f in ("kf_linear_a8", "kf_linear_a8_tiles", "kf_linear_w4a8", "kf_linear_w4a8_tiles"):
+            getattr(hip, f + "_status").argtypes = [C.POINTER(Weight), C.c_int]
+            getattr(hip, f).argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_attn_block_kv8_status.argtypes = [C.c_int, C.c_int, C.c_int]
         hip.kf_attn_block_kv8.argtypes = [C.c_void_p] * 12 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
         hip.kf_kv8_quant_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int]

@@ -393,41 +393,30 @@ class Context:
                                            pos, _ptr(d_pos), n_head, n_kv, hd, k8.stride(0), eps, _ptr(ws if ws is not None else self._ws(n_head, hd))), "kf_attn_block_kv8")
         return out
 
-    def linear_a8(self, w, q, step, bias=None, residual=None, y=None):
-        """kf_linear_a8: a ternary / 1-bit weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
+    def _linear_a8(self, entry, w, q, step, bias, residual, y):
+        """the four int8-activation products share one calling convention: entry is the ABI function's name"""
         n = 1 if q.dim() == 1 else q.shape[0]
         if y is None:
             y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
         d = w.desc()
-        L.check(self.hip.kf_linear_a8(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8")
+        L.check(getattr(self.hip, entry)(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), entry)
         return y
+
+    def linear_a8(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_a8: a ternary / 1-bit weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
+        return self._linear_a8("kf_linear_a8", w, q, step, bias, residual, y)
 
     def linear_a8_tiles(self, w, q, step, bias=None, residual=None, y=None):
         """kf_linear_a8_tiles: linear_a8's contract and bits on int8 MFMA tiles, for token batches (any nTok >= 1 is served); residual may be y"""
-        n = 1 if q.dim() == 1 else q.shape[0]
-        if y is None:
-            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
-        d = w.desc()
-        L.check(self.hip.kf_linear_a8_tiles(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_a8_tiles")
-        return y
+        return self._linear_a8("kf_linear_a8_tiles", w, q, step, bias, residual, y)
 
     def linear_w4a8(self, w, q, step, bias=None, residual=None, y=None):
         """kf_linear_w4a8: a 4-bit group weight times int8 activations q [ne1] or [nTok, ne1] with their steps [nTok] -> y bf16 [ne0] or [nTok, ne0]"""
-        n = 1 if q.dim() == 1 else q.shape[0]
-        if y is None:
-            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
-        d = w.desc()
-        L.check(self.hip.kf_linear_w4a8(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_w4a8")
-        return y
+        return self._linear_a8("kf_linear_w4a8", w, q, step, bias, residual, y)
 
     def linear_w4a8_tiles(self, w, q, step, bias=None, residual=None, y=None):
         """kf_linear_w4a8_tiles: linear_w4a8's contract and bits on int8 MFMA tiles, for token batches (any nTok >= 1 is served); residual may be y"""
-        n = 1 if q.dim() == 1 else q.shape[0]
-        if y is None:
-            y = torch.zeros((n, w.ne0) if q.dim() == 2 else (w.ne0,), dtype=torch.bfloat16, device=self.device)
-        d = w.desc()
-        L.check(self.hip.kf_linear_w4a8_tiles(self.h, C.byref(d), _ptr(q), _ptr(step), _ptr(y), _ptr(bias), _ptr(residual), n), "kf_linear_w4a8_tiles")
-        return y
+        return self._linear_a8("kf_linear_w4a8_tiles", w, q, step, bias, residual, y)
 
     def rmsnorm(self, x, w, eps=1e-6):
         y = torch.empty_like(x)

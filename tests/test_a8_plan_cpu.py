@@ -1,45 +1,17 @@
-"""The int8-activation mat-vec plan without a GPU: kf::a8_plan (through kfdbg_a8_plan) is the one rule behind kf_linear_a8 -- the refusals, the lanes per row, the token
-rows per weight pass, grid and LDS -- pinned on each side of every boundary.  The per-row summation order (one ascending chain over the K / 128 groups) is a function of K
+"""The int8-activation mat-vec plan without a GPU: the mat-vec route of kf::a8_plan (through kfdbg_a8_route_plan, tests/a8_plan_mirror.py) is the one rule behind kf_linear_a8
+-- the refusals, the lanes per row, the token rows per weight pass, grid and LDS -- pinned on each side of every boundary.  The per-row summation order (one ascending chain over the K / 128 groups) is a function of K
 alone: the fields that carry it may not move with nTok or M."""
-import ctypes as C
-
 import pytest
 
-from koifish_amd import lib as L
-
-BF16, F8, Q4, Q2, T_SIGN, BOOL1, T_BINARY = 3, 4, 14, 16, 17, 19, 20   # kf_dtype
-GROUP, ROW_LUT, ROW_RTN = 0, 1, 2                                      # quant forms
-OK, INVALID_ARGS, QUANT_ERR, UNSUPPORTED, UNALIGN = 0, -20, -701, -1000, -2000
-ORDER_CHAIN, TOK_TILE, GROUP_LDS, LDS_MAX = 1, 4, 144, 160 * 1024      # kf_a8_plan.h
-
-
-class Mat(C.Structure):   # kf::GemmMat
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):
-    _fields_ = [("w", Mat), ("nTok", C.c_int)]
-
-
-class Plan(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("status", "bits", "order", "n_groups", "lpr_log2", "iters", "rows_per_wave", "rows_per_wg", "tok_tile", "tok_tiles", "grid_x", "grid_y",
-                                       "block", "lds")]
-
-
-def mat(M, K, type=T_SIGN, quant=GROUP, lgroup=128, gama=1, al=3, awq=0):
-    return Mat(type, quant, awq, M, K, lgroup, gama, al)
+from a8_plan_mirror import (BF16, BOOL1, F8, GROUP_LDS, INVALID_ARGS, LDS_MAX, LOWBIT, MATVEC, OK, ORDER_CHAIN, Q2, Q4, QUANT_ERR, ROW_LUT, ROW_RTN, T_BINARY, T_SIGN, TOK_TILE,  # noqa: F401
+                            UNALIGN, UNSUPPORTED, mat)
+from a8_plan_mirror import check_views
+from a8_plan_mirror import plan as a8_plan
 
 
 @pytest.fixture(scope="module")
 def plan():
-    hip = L.load()[0]
-    hip.kfdbg_a8_plan.argtypes = [C.POINTER(Problem), C.POINTER(Plan)]
-
-    def f(m, nTok=1):
-        out = Plan()
-        assert hip.kfdbg_a8_plan(C.byref(Problem(m, nTok)), C.byref(out)) == 0
-        return out
-    return f
+    return lambda m, nTok=1: a8_plan(LOWBIT, MATVEC, m, nTok)
 
 
 @pytest.mark.parametrize("m,nTok,want", [
@@ -120,3 +92,7 @@ def test_order_depends_on_K_only(plan, K, type_):
         for nTok in (1, 2, 5, 9):
             p = plan(mat(M, K, type=type_), nTok)
             assert (p.order, p.n_groups) == (ref.order, ref.n_groups) == (ORDER_CHAIN, K // 128)
+
+
+def test_the_earlier_exports_are_views_of_this_plan():
+    check_views()

@@ -1,19 +1,13 @@
-"""The int8 MFMA tile plan without a GPU: kf::a8_tile_plan (through kfdbg_a8_tile_plan) is the one rule behind kf_linear_a8_tiles.  Its refusals are kf::a8_plan's -- one
-rule, asked twice: the refusal table of tests/test_a8_plan_cpu.py gives the same status through either -- and its tiles cover M x nTok with no empty workgroup inside
+"""The int8 MFMA tile plan without a GPU: the tile route of kf::a8_plan (through kfdbg_a8_route_plan) is the one rule behind kf_linear_a8_tiles.  Its refusals are the mat-vec
+route's -- one rule, asked twice: the refusal table of tests/test_a8_plan_cpu.py gives the same status through either -- and its tiles cover M x nTok with no empty workgroup inside
 160 KB of LDS.  The per-row summation order (one ascending chain over the K / 128 groups) is a function of K alone: the fields that carry it may not move with M or nTok."""
 import ctypes as C
 
 import pytest
 
 import test_a8_plan_cpu as P1
+from a8_plan_mirror import LOWBIT, MATVEC, TILE_MIN, TILES, plan
 from koifish_amd import lib as L
-
-TILE_MIN = 32   # KF_A8_TILE_MIN (include/kf_abi.h)
-
-
-class TilePlan(C.Structure):   # kf::A8TilePlan
-    _fields_ = [(f, C.c_int) for f in ("status", "bits", "order", "n_groups", "row_tile", "tok_tile", "waves", "mfma_tok", "chunk", "grid_x", "grid_y", "block", "lds",
-                                       "min_tok")]
 
 
 @pytest.fixture(scope="module")
@@ -22,19 +16,13 @@ def hip():
 
 
 @pytest.fixture(scope="module")
-def tile_plan(hip):
-    hip.kfdbg_a8_tile_plan.argtypes = [C.POINTER(P1.Problem), C.POINTER(TilePlan)]
-
-    def f(m, nTok=1):
-        out = TilePlan()
-        assert hip.kfdbg_a8_tile_plan(C.byref(P1.Problem(m, nTok)), C.byref(out)) == 0
-        return out
-    return f
+def tile_plan():
+    return lambda m, nTok=1: plan(LOWBIT, TILES, m, nTok)
 
 
 def test_symbols():
     hip, host = L.load()
-    for f in ("kf_linear_a8_tiles", "kf_linear_a8_tiles_status", "kfdbg_a8_tile_plan", "kf_linear_a8", "kfdbg_a8_plan"):
+    for f in ("kf_linear_a8_tiles", "kf_linear_a8_tiles_status", "kfdbg_a8_tile_plan", "kf_linear_a8", "kfdbg_a8_plan", "kfdbg_a8_route_plan"):
         assert hasattr(hip, f), f
     for f in ("kfh_set_a8_tile_min", "kfh_a8_route_counts"):
         assert hasattr(host, f), f
@@ -51,15 +39,12 @@ def test_the_refusal_table_is_the_other_file_s():
 
 
 @pytest.mark.parametrize("m,nTok,want", REFUSALS)
-def test_one_rule_asked_twice(hip, tile_plan, m, nTok, want):
-    hip.kfdbg_a8_plan.argtypes = [C.POINTER(P1.Problem), C.POINTER(P1.Plan)]
-    ref = P1.Plan()
-    assert hip.kfdbg_a8_plan(C.byref(P1.Problem(m, nTok)), C.byref(ref)) == 0
-    assert tile_plan(m, nTok).status == ref.status == want
+def test_one_rule_asked_twice(tile_plan, m, nTok, want):
+    assert tile_plan(m, nTok).status == plan(LOWBIT, MATVEC, m, nTok).status == want
 
 
 def test_lds_refusal_is_a8_plan_s(tile_plan):
-    """a row a8_plan refuses for its own LDS (tests/test_a8_plan_cpu.py test_lds_bound_refuses) is refused here with the same status: the status is taken, not re-derived"""
+    """a row the mat-vec route refuses for its own LDS (tests/test_a8_plan_cpu.py test_lds_bound_refuses) is refused here with the same status"""
     assert tile_plan(P1.mat(8, 36352), 2).status == P1.OK
     assert tile_plan(P1.mat(8, 36480), 2).status == P1.INVALID_ARGS
 
@@ -103,5 +88,6 @@ def test_status_entry(hip):
     assert [both(t, n) for t in (L.T_SIGN, L.BOOL1, L.T_BINARY) for n in (1, 70)] == [0] * 6
     assert [both(t, 70, gama=(t == L.Q4)) for t in (L.Q4, L.BF16, L.F8E5M2)] == [-1000] * 3
     assert both(L.T_SIGN, quant=L.QUANT_ROW_LUT) == -1000
+    assert both(L.Q4, lGroup=64, gama=False, off=8) == -1000   # the other family's storage is refused as storage, whatever else is wrong with it
     assert both(L.T_SIGN, lGroup=64) == -701 and both(L.BOOL1, gama=False) == -701
     assert both(L.T_SIGN, ne1=192) == -20 and both(L.T_SIGN, 0) == -20 and both(L.T_SIGN, off=8) == -2000

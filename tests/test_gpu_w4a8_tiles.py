@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from a8_plan_mirror import weight_tile_plan as tile_plan
 from koifish_amd import lib as L
 from oracle import oracle as O
 from w4a8_cases import FILL, SHAPES, IntW4, case, large_sum_case, linear_w4a8, run, saturating, t_bf16, u16, upload
@@ -24,17 +25,6 @@ def test_product_bit_for_bit(ctx, M, K, qBias):
         assert not (got == FILL).any(), "nTok = %d: an output element kept the fill value" % n
         assert np.array_equal(got, ref[:n]), "nTok = %d: %d of %d outputs differ from the restatement" % (n, int((got != ref[:n]).sum()), got.size)
         assert np.array_equal(got, run(ctx, "linear_w4a8", dw, q[:n], s[:n])), "nTok = %d: differs from kf_linear_w4a8" % n
-
-
-def tile_plan(dw, n):
-    """kf::w4a8_tile_plan's answer for this weight and nTok (tests/test_w4a8_cpu.py mirrors the structs)"""
-    import ctypes as C
-    from test_w4a8_cpu import Mat, Problem, TilePlan
-    hip = L.load()[0]
-    hip.kfdbg_w4a8_tile_plan.argtypes = [C.POINTER(Problem), C.POINTER(TilePlan)]
-    out = TilePlan()
-    assert hip.kfdbg_w4a8_tile_plan(C.byref(Problem(Mat(L.Q4, 0, 0, dw.ne0, dw.ne1, 128, 1, 3), n, dw.qBias)), C.byref(out)) == 0 and out.status == 0
-    return out
 
 
 WIDE = (1000, 1280)   # 16 row tiles, the last 40 rows; 10 groups: a chunk of 8, where a thread of the 64-token form stages two (group, token) units, and one of 2

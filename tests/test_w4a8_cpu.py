@@ -1,4 +1,4 @@
-"""W4.A8 without a GPU: kf::w4a8_plan and kf::w4a8_tile_plan (through kfdbg_w4a8_plan / kfdbg_w4a8_tile_plan) are the one rule behind kf_linear_w4a8 and
+"""W4.A8 without a GPU: the two routes of kf::a8_plan (through kfdbg_a8_route_plan, tests/a8_plan_mirror.py) are the one rule behind kf_linear_w4a8 and
 kf_linear_w4a8_tiles -- refusals, lanes per row, tiles, grid, LDS -- and the numpy restatement (tests/w4a8_restate.py) of the definition (include/kf_abi.h "int8
 activations for 4-bit layers") is held against exact rational arithmetic with one rounding per operation."""
 import ctypes as C
@@ -8,35 +8,15 @@ import numpy as np
 import pytest
 
 import w4a8_restate as R
+from a8_plan_mirror import (BF16, BOOL1, F8, GROUP_LDS, INVALID_ARGS, LDS_MAX, MATVEC, OK, ORDER_CHAIN, Q2, Q3, Q4, Q4_FAMILY, QUANT_ERR, ROW_LUT, ROW_RTN, T_BINARY, T_SIGN,
+                            TILE_MIN, TILES, TOK_TILE, UNALIGN, UNSUPPORTED, plan)
+from a8_plan_mirror import mat as any_mat
 from koifish_amd import lib as L
 from oracle import oracle as O
 
-BF16, F8, Q4, Q3, Q2, T_SIGN, BOOL1, T_BINARY = 3, 4, 14, 15, 16, 17, 19, 20   # kf_dtype
-GROUP, ROW_LUT, ROW_RTN = 0, 1, 2                                              # quant forms
-OK, INVALID_ARGS, QUANT_ERR, UNSUPPORTED, UNALIGN = 0, -20, -701, -1000, -2000
-ORDER_CHAIN, TOK_TILE, GROUP_LDS, LDS_MAX, TILE_MIN = 1, 4, 144, 160 * 1024, 32
 
-
-class Mat(C.Structure):   # kf::GemmMat
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):   # kf::W4A8Problem
-    _fields_ = [("w", Mat), ("nTok", C.c_int), ("qbias", C.c_int)]
-
-
-class Plan(C.Structure):   # kf::W4A8Plan
-    _fields_ = [(f, C.c_int) for f in ("status", "qbias", "order", "n_groups", "lpr_log2", "iters", "rows_per_wave", "rows_per_wg", "tok_tile", "tok_tiles", "grid_x",
-                                       "grid_y", "block", "lds")]
-
-
-class TilePlan(C.Structure):   # kf::W4A8TilePlan
-    _fields_ = [(f, C.c_int) for f in ("status", "qbias", "order", "n_groups", "row_tile", "tok_tile", "waves", "mfma_tok", "chunk", "grid_x", "grid_y", "block", "lds",
-                                       "min_tok")]
-
-
-def mat(M, K, type=Q4, quant=GROUP, lgroup=128, gama=1, al=3, awq=0):
-    return Mat(type, quant, awq, M, K, lgroup, gama, al)
+def mat(M, K, type=Q4, **kw):
+    return any_mat(M, K, type=type, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -45,21 +25,13 @@ def hip():
 
 
 @pytest.fixture(scope="module")
-def plans(hip):
-    hip.kfdbg_w4a8_plan.argtypes = [C.POINTER(Problem), C.POINTER(Plan)]
-    hip.kfdbg_w4a8_tile_plan.argtypes = [C.POINTER(Problem), C.POINTER(TilePlan)]
-
-    def f(m, nTok=1, qbias=0):
-        a, b = Plan(), TilePlan()
-        P = Problem(m, nTok, qbias)
-        assert hip.kfdbg_w4a8_plan(C.byref(P), C.byref(a)) == 0 and hip.kfdbg_w4a8_tile_plan(C.byref(P), C.byref(b)) == 0
-        return a, b
-    return f
+def plans():
+    return lambda m, nTok=1, qbias=0: (plan(Q4_FAMILY, MATVEC, m, nTok, qbias), plan(Q4_FAMILY, TILES, m, nTok, qbias))
 
 
 def test_symbols():
     hip, host = L.load()
-    for f in ("kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status", "kfdbg_w4a8_plan", "kfdbg_w4a8_tile_plan"):
+    for f in ("kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status", "kfdbg_w4a8_plan", "kfdbg_w4a8_tile_plan", "kfdbg_a8_route_plan"):
         assert hasattr(hip, f), f
         assert not f.startswith("kf_") or f in L.ABI_SYMBOLS
     assert hasattr(host, "kfh_set_act_int8_q4")
@@ -67,7 +39,7 @@ def test_symbols():
     assert hasattr(Context, "linear_w4a8") and hasattr(Context, "linear_w4a8_tiles") and hasattr(Qwen3, "set_act_int8_q4")
 
 
-# ---------------------------------------------------------------- 1. the refusals: a8_plan's order and codes
+# ---------------------------------------------------------------- 1. the refusals: the low-bit family's order and codes
 @pytest.mark.parametrize("m,nTok,qbias,want", [
     (mat(64, 1024, type=BF16, gama=0), 1, 0, UNSUPPORTED),
     (mat(64, 1024, type=F8, gama=0), 1, 0, UNSUPPORTED),
@@ -173,6 +145,7 @@ def test_status_entries(hip):
     others = (L.F32, L.F16, L.BF16, L.F8E5M2, L.F8E4M3, L.I8, L.Q3, L.Q2, L.T_SIGN, L.T_SEQ, L.BOOL1, L.T_BINARY, L.T_BINARY_3, L.T_BINARY_TILE)
     assert [both(t, 70) for t in others] == [UNSUPPORTED] * len(others)
     assert both(L.Q4, quant=L.QUANT_ROW_LUT) == UNSUPPORTED and both(L.Q4, quant=L.QUANT_ROW_RTN) == UNSUPPORTED and both(L.Q4, awq=True) == UNSUPPORTED
+    assert both(L.T_SIGN, lGroup=64, gama=False, off=8) == UNSUPPORTED   # the other family's storage is refused as storage, whatever else is wrong with it
     assert both(L.Q4, lGroup=64) == QUANT_ERR and both(L.Q4, gama=False) == QUANT_ERR and both(L.Q4, qBias=4) == QUANT_ERR
     assert both(L.Q4, ne1=192) == INVALID_ARGS and both(L.Q4, 0) == INVALID_ARGS and both(L.Q4, off=8) == UNALIGN
     # the existing entries keep refusing 4-bit storage
