@@ -877,6 +877,34 @@ int kf_kv8_quant_rows(kf_ctx* ctx, const kf_bf16* k, const kf_bf16* v, int64_t l
                       int kv_stride);
 int kf_kv8_dequant_rows(kf_ctx* ctx, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, kf_bf16* kout,
                         kf_bf16* vout, int64_t ld_out);
+/* ---- int8 KV cache, the prompt form: attention of a token batch on the int8 rows themselves (restated in numpy by tests/kv8_prefill_restate.py).
+ * THE DEFINITION, for row r of the batch at position p = pos0 + r, query head h of kv-head kvh, keys t = 0 .. p.  Up to the weight it IS the decode definition above, bit
+ * for bit: (q8, sq) the row quantiser on the prepared bf16 query head; I_t the exact int32 dot (here on v_mfma_i32_16x16x64_i8); c = sq * KS[t][kvh], d = fp32(I_t) * c,
+ * s_t = bf16_rn(d * rden): three separate fp32 multiplies; (f_t, n_t) = kf_exp2_parts(s_t * log2 e); p_t = f_t * 2^(n_t - m), m any integer >= every n met so far (moving
+ * m multiplies by a power of two: exact); g_t = f_t * VS[t][kvh], one fp32 multiply.  So a prompt row's scores and weights are the ones kf_attn_block_kv8 computes there.
+ *   The tail is this form's own:
+ *     operand  gb_t = bf16_rn(g_t); the P.V product runs on bf16 MFMA, its V operand is bf16(v8[t][d]) (exact);
+ *     sums     fp32: O[d] = sum_t (gb_t * 2^(n_t - m)) * v8[t][d], L = sum_t p_t.  Every product is exact (8 + 7 significant bits); the additions round, and their order
+ *              inside an MFMA accumulator is the hardware's, not ours to state.  (A product scaled below the fp32 normal range, n_t - m < about -120, may be flushed: it is
+ *              below 2^-120 of the largest weight.)
+ *     out      bf16_rn(fl32(O[d] / L)): ONE correctly rounded fp32 division per element (not a reciprocal and a multiply), then the bf16 store.
+ *   Hence the tail is held to a DERIVED bound, not to bit equality.  With N = p + 1 keys, unit roundoff u = 2^-23 (which covers an accumulator that truncates as well as
+ *   one that rounds to nearest), A[d] = sum_t |gb_t * v8[t][d]| * 2^(n_t - M) and O, L the exact sums against one M: any-order fp32 summation gives |O~ - O| <= N u A and
+ *   |L~ - L| <= N u L to first order, so |out - O / L| <= 2^-8 |O / L| (the bf16 store) + 2^-24 |O / L| (the division) + 2 N u (A + |O|) / L.  With ONE key nothing is
+ *   summed and out is exact: bf16_rn(fl32(gb_0 * v8[0][d] / f_0)).
+ *   EXACT, whatever the launch: a row's output bits depend only on its position, its q row and the cache -- not on pos0, n_tok, the rows beside it or the grid.  (Key tiles
+ *   are anchored at key 0, a key's place in the walk is a function of its index, a column's m after a tile is the largest n among its keys so far; there is no split
+ *   over keys and no merge.)  There is ONE arithmetic: kf_set_canonical 0 and 1 give the same bits.
+ *   Against the decode form at the same position the result differs by the gb rounding (<= 2^-8 A / L) and the fp32 sums; the two are NOT bit-equal.
+ * kf_attn_prefill_kv8: kf_attn_prefill's contract on the int8 cache -- q the prepared bf16 queries [n_tok][q_stride] as kf_qkv_rope_batch leaves them, rows
+ * pos0 .. pos0 + n_tok - 1 of K8 / V8 / KS / VS already written by kf_kv8_quant_rows; out [n_tok][q_stride].  No scratch.  The launch is the ATTN_PROMPT_KV8 entry of
+ * kf::attn_plan: one form for any n_tok >= 1 and pos0 >= 0.  Refusals, as kf_attn_block_kv8: a null pointer KF_INVALID_ARGS; query heads per kv-head other than 1, 2, 4, 8,
+ * hd other than 64, 128, pos0 < 0, n_tok < 1, or a row stride shorter than the row KF_INVALID_ARGS; K8 / V8 or q not 16-byte aligned, out not 8-byte aligned,
+ * kv_stride % 16 != 0 or q_stride % 8 != 0 KF_BLAS_UNALIGN.
+ * kf_attn_prefill_kv8_status: what the entry would answer for a shape and n_tok, without a launch. */
+int kf_attn_prefill_kv8_status(int n_head, int n_kv, int hd, int n_tok);
+int kf_attn_prefill_kv8(kf_ctx* ctx, const kf_bf16* q, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, kf_bf16* out, int pos0, int n_tok,
+                        int64_t q_stride, int n_head, int n_kv, int hd, int kv_stride);
 
 #ifdef __cplusplus
 }

@@ -784,6 +784,31 @@ int kf_kv8_dequant_rows(kf_ctx* c, const int8_t* k8, const int8_t* v8, const flo
     if (ld_out < (int64_t)n_kv * hd) return fail(KF_INVALID_ARGS, "kf_kv8_dequant_rows: ld_out=%lld", (long long)ld_out);
     RET(kf::kv8_dequant_rows_launch(c->stream, k8, v8, ks, vs, n, n_kv, hd, kv_stride, kout, vout, ld_out));
 }
+// the prompt form: every launch decision is kf::attn_plan's ATTN_PROMPT_KV8 entry
+static kf::AttnProblem kv8_prefill_problem(int n_head, int n_kv, int hd, int pos0, int n_tok, int al, long long q_stride, long long kv_stride) {
+    return kf::AttnProblem{kf::ATTN_PROMPT_KV8, n_head, n_kv, hd, pos0, n_tok, 1, 1, al, q_stride, 0, kv_stride};
+}
+int kf_attn_prefill_kv8_status(int n_head, int n_kv, int hd, int n_tok) {
+    return kf::attn_plan(kv8_prefill_problem(n_head, n_kv, hd, 0, n_tok, kf::ATTN_Q_AL | kf::ATTN_OUT_AL, 0, 0)).status;
+}
+int kf_attn_prefill_kv8(kf_ctx* c, const kf_bf16* q, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, kf_bf16* out, int pos0, int n_tok, int64_t q_stride,
+                        int n_head, int n_kv, int hd, int kv_stride) {
+    CHKCTX(c);
+    if (!q || !k8 || !v8 || !ks || !vs || !out) return fail(KF_INVALID_ARGS, "kf_attn_prefill_kv8: null pointer");
+    if (!al16(k8) || !al16(v8)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill_kv8: cache not 16-byte aligned");
+    const int al = (al16(q) ? kf::ATTN_Q_AL : 0) | (((uintptr_t)out & 7) == 0 ? kf::ATTN_OUT_AL : 0);
+    const kf::AttnPlan p = kf::attn_plan(kv8_prefill_problem(n_head, n_kv, hd, pos0, n_tok, al, q_stride, kv_stride));
+    if (p.status == KF_BLAS_UNALIGN)
+        return fail(p.status, "kf_attn_prefill_kv8: kv_stride %d is not a multiple of 16, q_stride %lld not a multiple of 8, q not 16-byte or out not 8-byte aligned", kv_stride,
+                    (long long)q_stride);
+    if (p.status != KF_OK)
+        return fail(KF_INVALID_ARGS, "kf_attn_prefill_kv8: %d / %d heads x %d, pos0 %d, n_tok %d: query heads per kv-head 1, 2, 4 or 8, head_dim 64 or 128, pos0 >= 0, n_tok >= 1",
+                    n_head, n_kv, hd, pos0, n_tok);
+    if (q_stride < (int64_t)n_head * hd || kv_stride < n_kv * hd) return fail(KF_INVALID_ARGS, "kf_attn_prefill_kv8: q_stride=%lld kv_stride=%d", (long long)q_stride, kv_stride);
+    kf::AttnPrefillKv8Args a;
+    a.q = q, a.k8 = k8, a.v8 = v8, a.ks = ks, a.vs = vs, a.out = out, a.pos0 = pos0, a.n_tok = n_tok, a.n_kv = n_kv, a.kv_stride = kv_stride, a.q_stride = q_stride, a.rden = 0.0f;
+    RET(kf::attn_prefill_kv8_launch(c->stream, a, p));
+}
 
 int kf_swiglu(kf_ctx* c, const kf_bf16* gate, const kf_bf16* up, kf_bf16* out, int n) {
     CHKCTX(c);

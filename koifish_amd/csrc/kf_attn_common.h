@@ -470,4 +470,26 @@ __device__ __forceinline__ void fast_wave_to_lds(const FastAcc<GQ>& A, float* co
 __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// ---- the int8 KV cache's row quantiser, shared by attn_kv8_kernel / kv8_quant_rows_kernel (kf_attn_kv8.hip) and attn_prefill_kv8_kernel (kf_attn_prefill_kv8.hip)
+// the row quantiser (kf_act_quant_i8's arithmetic) on one head held by one wave as load_head / prep_head deal it: lane j < hd / 2 holds elements j and j + hd / 2
+__device__ __forceinline__ void quant_head(float x0, float x1, int hd, int8_t* dst, float* step_out) {
+    const int j = threadIdx.x & 63, half = hd >> 1;
+    const bool act = j < half;
+    const float amax = wave_max(act ? fmaxf(fabsf(x0), fabsf(x1)) : 0.0f);
+    const float s = __fdiv_rn(amax, 127.0f);
+    float r0 = 0.0f, r1 = 0.0f;
+    if (amax != 0.0f) {
+        r0 = fminf(fmaxf(roundf(__fdiv_rn(x0, s)), -127.0f), 127.0f);
+        r1 = fminf(fmaxf(roundf(__fdiv_rn(x1, s)), -127.0f), 127.0f);
+    }
+    if (act) dst[j] = (int8_t)(int)r0, dst[j + half] = (int8_t)(int)r1;
+    if (j == 0) *step_out = s;
+}
+// ... on a bf16 head this wave has just written to LDS (prep_head: the lane reads back its own two elements)
+__device__ __forceinline__ void quant_head_lds(const uint16_t* src, int hd, int8_t* dst, float* step_out) {
+    const int j = threadIdx.x & 63, half = hd >> 1;
+    const bool act = j < half; /* the lanes past hd / 2 read nothing: no lane depends on another lane's LDS store */
+    quant_head(act ? bf2f(src[j]) : 0.0f, act ? bf2f(src[j + half]) : 0.0f, hd, dst, step_out);
+}
+
 }  // namespace kf

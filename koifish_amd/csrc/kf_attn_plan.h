@@ -1,6 +1,6 @@
 // kf_attn_plan.h -- how attention is launched: kf::attn_plan, one pure host function, picks the route, kernel form, slices, grid, threads, LDS and scratch of every
-// attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
-// kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
+// attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_kv8, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
+// kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_prefill_kv8.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
 #pragma once
 #include "kf_kernels.h"
 
@@ -28,6 +28,9 @@ constexpr int AP_VPAD = 32;                /* V row padding, elements (64 B): ro
 // the int8 cache (kf_attn_kv8.hip): a lane holds 16 elements of a key, so a key takes hd / 16 lanes and a wave step twice the keys of the bf16 kernel; the slices are
 // attn_slices' (one rule), 4 waves always, ATTN_KV8_U tiles in flight per wave: one 64-key slice of hd = 128 is one batch of the workgroup (4 waves x 8 keys x 2 tiles)
 constexpr int ATTN_KV8_NW = 4, ATTN_KV8_U = 2;
+// prompts on the int8 cache (kf_attn_prefill_kv8.hip): 64 (token, query head) columns per workgroup, 16 per wave (the N of v_mfma_i32_16x16x64_i8); key tiles of 64
+// anchored at key 0; K8 rows 16 bytes apart from a multiple of 128 (the 16 rows of an A read on distinct banks), bf16 V rows 32 bytes (the 8 rows of a transposing pass)
+constexpr int APK8_COLS = 64, APK8_KT = 64, APK8_KPAD = 16, APK8_VPAD = 16;
 
 // ---- the slice rule: slices, keys per slice and waves of the decode kernel for keys 0 .. pos_bound (one_slice: the per-token form)
 struct AttnSlices {
@@ -49,7 +52,7 @@ constexpr size_t attn_decode_scratch_bytes(int n_head, int hd) { return sizeof(d
 constexpr size_t attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return (T < 1 || n_head < 1 || n_seq < 1) ? 0 : sizeof(float) * 2 * (size_t)T * n_head * n_seq; }
 
 // ---- the problem
-enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4 };
+enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5 };
 enum { ATTN_Q_AL = 1, ATTN_OUT_AL = 2 }; /* q 16-byte aligned, out 8-byte aligned */
 struct AttnProblem {
     int entry, n_head, n_kv, hd;
@@ -63,7 +66,8 @@ struct AttnProblem {
 //   ATTN_TILE / ATTN_PAIRED  attn_prefill_kernel<hd, gq, kh, kt> on (blocks, n_kv, n_seq); kh = 2: a block from the front and one from the back per workgroup
 //   ATTN_BWD        attn_bwd_dq_mfma_kernel<hd> on grid, then attn_bwd_dkv_mfma_kernel<hd> on grid_kv
 //   ATTN_SLICED_KV8 attn_kv8_kernel<gq, hd> on (n_splits, n_kv * gq_split, 1), ATTN_KV8_NW waves; slices, counters and scratch as ATTN_SLICED in the canonical order
-enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4, ATTN_SLICED_KV8 = 5 };
+//   ATTN_TILE_KV8   attn_prefill_kv8_kernel<hd, gq> on (blocks of 64 / gq tokens, n_kv, 1), four waves, no scratch; gq = the query heads of a kv-head, any n_tok >= 1
+enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4, ATTN_SLICED_KV8 = 5, ATTN_TILE_KV8 = 6 };
 struct AttnPlan {
     int status, route;             /* KF_OK or the refusal; the route (of a refusal: the one that refused) */
     int canon, gq, nw, hd, kh, kt; /* the kernel form; gq = query heads per workgroup */
@@ -100,6 +104,17 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         // the waves' {O[hd], L, m} doubles; prepared q heads + the new key (bf16); their int8 codes + the new K and V rows' codes; the gq + 2 steps and the flag
         p.lds = (int)(sizeof(double) * ((size_t)ATTN_KV8_NW * p.gq * (P.hd + 2)) + sizeof(uint16_t) * ((size_t)p.gq * P.hd + P.hd) + ((size_t)p.gq * P.hd + 2 * P.hd) + 4 * (p.gq + 2) + 16);
         p.scratch = (long long)attn_decode_scratch_bytes(P.n_head, P.hd);
+        return p;
+    }
+    if (P.entry == ATTN_PROMPT_KV8) { /* a token batch against the int8 cache: ONE arithmetic and ONE form for every n_tok >= 1 (P.canon is not read) */
+        p.route = ATTN_TILE_KV8;
+        if (!hd_ok || !kv_ok || !gq_ok || P.pos < 0 || P.n_tok < 1) return refuse(KF_INVALID_ARGS);
+        if ((P.kv_stride & 15) || (P.q_stride & 7) || !(P.al & ATTN_Q_AL) || !(P.al & ATTN_OUT_AL)) return refuse(KF_BLAS_UNALIGN); /* 16-byte q and K8 / V8 rows, 8-byte out rows */
+        const int TQ = APK8_COLS / GQ;
+        p.canon = 1, p.kh = 1, p.kt = APK8_KT, p.threads = 256;
+        p.grid[0] = (P.n_tok + TQ - 1) / TQ, p.grid[1] = P.n_kv, p.grid[2] = 1;
+        // the K8 tile, the bf16 V tile (the prologue's bf16 query heads lie in it), the rows' two steps, the query codes and their steps
+        p.lds = APK8_KT * (P.hd + APK8_KPAD) + (int)sizeof(uint16_t) * APK8_KT * (P.hd + APK8_VPAD) + 4 * 2 * APK8_KT + APK8_COLS * P.hd + 4 * APK8_COLS;
         return p;
     }
     // the tile kernel: 16-byte q and K / V rows, 8-byte out rows
@@ -161,6 +176,18 @@ struct AttnKv8Args {
     float eps, inv_sqrt_hd_den;
 };
 int attn_kv8_launch(hipStream_t st, AttnKv8Args& a, const AttnPlan& p);
+struct AttnPrefillKv8Args { /* kf_attn_prefill_kv8.hip, ATTN_TILE_KV8 */
+    const uint16_t* q; /* prepared bf16 query rows */
+    const int8_t* k8;
+    const int8_t* v8;
+    const float* ks;
+    const float* vs;
+    uint16_t* out;
+    int pos0, n_tok, n_kv, kv_stride;
+    long long q_stride; /* of q and of out */
+    float rden;
+};
+int attn_prefill_kv8_launch(hipStream_t st, AttnPrefillKv8Args& a, const AttnPlan& p);
 int kv8_quant_rows_launch(hipStream_t st, const uint16_t* k, const uint16_t* v, long long ld, int n, int n_kv, int hd, int8_t* k8, int8_t* v8, float* ks, float* vs, int pos0,
                           int kv_stride);
 int kv8_dequant_rows_launch(hipStream_t st, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, uint16_t* kout,

@@ -273,6 +273,11 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
         KF_TRY(kf_qkv_rope_batch(c, &wq, &wk, &wv, bn, bq, sk + (size_t)pos0 * kv_dim, sv + (size_t)pos0 * kv_dim, n, normQ.w ? ToX(normQ.w) : nullptr,
                                  normK.w ? ToX(normK.w) : nullptr, f->rope_table, pos0, n_head, n_head_kv, head_dim, normQ.rms_eps));
         KF_TRY(kf_kv8_quant_rows(c, sk + (size_t)pos0 * kv_dim, sv + (size_t)pos0 * kv_dim, kv_dim, n, n_head_kv, head_dim, k8, v8, ks, vs, pos0, kv_dim));
+        f->kv8_count[f->kv_int8_prefill ? 0 : 1]++;
+        if (f->kv_int8_prefill) {  // the prompt form: the int8 rows themselves, integer scores as the decode kernel's; nothing is dequantised, no earlier row is rewritten
+            KF_TRY(kf_attn_prefill_kv8(c, bq, k8, v8, ks, vs, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
+            return kf_linear(c, &wo, ba, bx, nullptr, n, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx);
+        }
         KF_TRY(kf_kv8_dequant_rows(c, k8, v8, ks, vs, pos0 + n, n_head_kv, head_dim, kv_dim, sk, sv, kv_dim));
         KF_TRY(kf_attn_prefill(c, bq, sk, sv, ba, pos0, n, q_dim, n_head, n_head_kv, head_dim, kv_dim));
         return kf_linear(c, &wo, ba, bx, nullptr, n, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx);
@@ -555,7 +560,22 @@ int Fish::SetKVInt8(bool on, std::string& why) {
     }
     if (kv_int8 != on) {
         kv_int8 = on;
+        if (!on) kv_int8_prefill = false; /* the sub-setting goes with the cache */
         ModeChanged();
+    }
+    return KF_OK;
+}
+int Fish::SetKVInt8Prefill(bool on, std::string& why) {
+    if (on) {
+        if (!kv_int8)
+            return refused(why, "kfh_set_kv_int8_prefill", KF_INVALID_ARGS, "the int8 prompt attention is a sub-setting of the int8 KV cache: switch kfh_set_kv_int8 on first");
+        if (const int st = kf_attn_prefill_kv8_status(config.n_head, config.n_head_kv, config.head_dim, 1))
+            return refused(why, "kfh_set_kv_int8_prefill", st,
+                           "kf_attn_prefill_kv8 refuses " + std::to_string(config.n_head) + " / " + std::to_string(config.n_head_kv) + " heads x " + std::to_string(config.head_dim));
+    }
+    if (kv_int8_prefill != on) {
+        kv_int8_prefill = on;
+        ModeChanged(); /* as kfh_set_kv_int8: captured graphs dropped, XcdReplicas / XcdTP built on this Fish re-check */
     }
     return KF_OK;
 }
@@ -647,7 +667,7 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
 int Fish::EnsureEngine() {
     if (engine_state != 0) return engine_state > 0 ? KF_OK : KF_ENGINE_NOT_SERVED;
     engine_state = -1;
-    KF_TRY(engine_refusal(Modes(), engine_why));
+    KF_TRY(EngineRefusal(engine_why));
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
     KF_TRY(EngineTable(ToX(cache.key), ToX(cache.val), true, engine_why, L, d));
@@ -1212,7 +1232,7 @@ int XcdReplicas::MakeEngine(bool allocate) {
     const int kvd = c.n_head_kv * c.head_dim;
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
-    KF_TRY(engine_refusal(f->Modes(), why));
+    KF_TRY(f->EngineRefusal(why));
     KF_TRY(f->EngineTable(ToX(f->cache.key), ToX(f->cache.val), true, why, L, d)); /* the Fish's own K / V rows stand in for the validation below: a refused model allocates nothing */
     {
         char w[320];
@@ -1551,7 +1571,7 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "the ranks' cards disagree";
             return KF_INVALID_ARGS;
         }
-        KF_TRY(engine_refusal(f->Modes(), why));
+        KF_TRY(f->EngineRefusal(why));
         KF_TRY(f->EngineTable(ToX(key) + r * rank_elems, ToX(val) + r * rank_elems, false, why, Ls[r], ds[r])); /* no hot-row masks: the TP form has no sparse FFN */
         ds[r].rope_table = f0->rope_table; /* every rank's descriptor: rank 0's table (n_layer, max_seq and kv_stride agree, checked above) */
         dp[r] = &ds[r];
@@ -1693,6 +1713,18 @@ int kfh_set_act_int8_q4(void* h, int on) { return reinterpret_cast<Fish*>(h)->Se
 // A refusal leaves the switch as it was; kfh_host_error says why.  kfh_kv8_*: the int8 pair and its steps on the device (NULL before the first switch-on).
 int kfh_set_kv_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetKVInt8(on != 0, g_host_err); }
 int kfh_kv_int8(void* h) { return reinterpret_cast<Fish*>(h)->kv_int8 ? 1 : 0; }
+// the int8 prompt attention, a sub-setting of the int8 KV cache: off by default, refused (with the reason) unless kfh_set_kv_int8 is on, switched off with it.  On: token
+// batches run kf_attn_prefill_kv8 on the int8 rows; off: the dequantise route, bit for bit.
+int kfh_set_kv_int8_prefill(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetKVInt8Prefill(on != 0, g_host_err); }
+int kfh_kv_int8_prefill(void* h) { return reinterpret_cast<Fish*>(h)->kv_int8_prefill ? 1 : 0; }
+// (kf_attn_prefill_kv8 launches, dequantise-route launches) of the token batches since the last reset; reset != 0 zeroes them after the read
+int kfh_kv8_route_counts(void* h, int64_t* out2, int reset) {
+    if (!h || !out2) return KF_INVALID_ARGS;
+    Fish* f = reinterpret_cast<Fish*>(h);
+    out2[0] = f->kv8_count[0], out2[1] = f->kv8_count[1];
+    if (reset) f->kv8_count[0] = f->kv8_count[1] = 0;
+    return KF_OK;
+}
 void* kfh_kv8_codes(void* h, int val) {
     const KVCache& kc = reinterpret_cast<Fish*>(h)->cache;
     return kc.k8 ? (val ? kc.v8 : kc.k8)->data : nullptr;

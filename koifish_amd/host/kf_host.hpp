@@ -229,7 +229,20 @@ struct Fish : SeqBuffers {
     // refused; ModeChanged() follows every switch that moved: the engine's table and the captured graphs belong to the other arithmetic, and XcdReplicas / XcdTP objects
     // built on this Fish re-check at their next use (weights_gen).
     unsigned Modes() const;
-    int Admit(Mode asked, const char* entry, std::string& why) const { return mode_refusal(Modes(), asked, entry, why); }
+    // a refusal that names the int8 KV cache names its sub-setting too while that is on
+    void Kv8Note(std::string& why) const {
+        if (kv_int8 && kv_int8_prefill && why.find("int8 KV cache") != std::string::npos) why += " (its int8 prompt attention, kfh_set_kv_int8_prefill, is on too)";
+    }
+    int Admit(Mode asked, const char* entry, std::string& why) const {
+        const int rc = mode_refusal(Modes(), asked, entry, why);
+        if (rc != KF_OK) Kv8Note(why);
+        return rc;
+    }
+    int EngineRefusal(std::string& why) const {  // engine_refusal for this Fish's modes
+        const int rc = engine_refusal(Modes(), why);
+        if (rc != KF_OK) Kv8Note(why);
+        return rc;
+    }
     bool EagerOnly() const { return eager_only(Modes()); }  // what the step sequencing asks: eager per-layer launches, position from the host, no engine, no graphs
     void ModeChanged();
     TPState tp;
@@ -380,6 +393,14 @@ struct Fish : SeqBuffers {
     // prefills again.  Its own check: kf_attn_block_kv8_status.
     bool kv_int8 = false;
     int SetKVInt8(bool on, std::string& why);
+    // ... and its sub-setting (kfh_set_kv_int8_prefill; include/kf_abi.h "int8 KV cache, the prompt form"): token batches attend to the int8 rows themselves --
+    // kf_qkv_rope_batch into the chunk's rows of the staging pair, kf_kv8_quant_rows, kf_attn_prefill_kv8: no kf_kv8_dequant_rows, no bf16 kf_attn_prefill, and the scores
+    // of a prompt row are the decode kernel's.  A field beside kv_int8, not a mode: it is refused unless kv_int8 is on, excludes what MODE_KV_INT8 excludes through that
+    // row, and is switched off with kv_int8.  Off by default.  Its own check: kf_attn_prefill_kv8_status.  kv8_count: (int8, dequantise-route) prompt-attention launches
+    // since the last kfh_kv8_route_counts reset.
+    bool kv_int8_prefill = false;
+    int64_t kv8_count[2] = {0, 0};
+    int SetKVInt8Prefill(bool on, std::string& why);
     // what Prefill and Score share: m tokens at positions pos.. as one token batch through the embedding and every layer (rows in gBUFF.bX); the ending -- the head on row
     // `last` of the batch buffer, the state update leaves {next token, pos + 1}
     int FlowChunk(const int* tokens, int m, int pos);

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
     "kf_act_quant_i8", "kf_linear_a8", "kf_linear_a8_status", "kf_linear_a8_tiles", "kf_linear_a8_tiles_status",
     "kf_linear_w4a8", "kf_linear_w4a8_status", "kf_linear_w4a8_tiles", "kf_linear_w4a8_tiles_status",
-    "kf_attn_block_kv8", "kf_attn_block_kv8_status", "kf_kv8_quant_rows", "kf_kv8_dequant_rows",
+    "kf_attn_block_kv8", "kf_attn_block_kv8_status", "kf_kv8_quant_rows", "kf_kv8_dequant_rows", "kf_attn_prefill_kv8", "kf_attn_prefill_kv8_status",
     "kf_muon_scratch_bytes", "kf_muon_momentum", "kf_newton_schulz", "kf_muon_apply", "kf_muon",
     "kf_gama_backward", "kf_gama_backward_scratch_bytes", "kf_dequant_arena_bytes",
     "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes", "kf_lora_apply", "kf_lora_apply_status",
@@ -182,6 +182,8 @@ def load():
         hip.kf_kv8_quant_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int]
         hip.kf_kv8_dequant_rows.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
         hip.kfdbg_kv8_plan.argtypes = [C.c_int] * 5 + [C.c_void_p]
+        hip.kf_attn_prefill_kv8_status.argtypes = [C.c_int] * 4
+        hip.kf_attn_prefill_kv8.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
         hip.kf_embed.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_int, C.c_void_p, C.c_void_p]
         hip.kf_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -257,6 +259,9 @@ def load():
         host.kfh_set_act_int8_q4.argtypes = [C.c_void_p, C.c_int]
         host.kfh_set_kv_int8.argtypes = [C.c_void_p, C.c_int]
         host.kfh_kv_int8.argtypes = [C.c_void_p]
+        host.kfh_set_kv_int8_prefill.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_kv_int8_prefill.argtypes = [C.c_void_p]
+        host.kfh_kv8_route_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         for f in ("kfh_kv8_codes", "kfh_kv8_steps"):
             getattr(host, f).restype = C.c_void_p
             getattr(host, f).argtypes = [C.c_void_p, C.c_int]

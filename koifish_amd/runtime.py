@@ -385,6 +385,16 @@ class Context:
         L.check(self.hip.kf_kv8_dequant_rows(self.h, _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), n, n_kv, hd, k8.stride(0), _ptr(kout), _ptr(vout), kout.stride(0)),
                 "kf_kv8_dequant_rows")
 
+    def attn_prefill_kv8(self, q, k8, v8, ks, vs, pos0, n_head, n_kv, hd, out=None):
+        """kf_attn_prefill_kv8: kf_attn_prefill's contract on the int8 cache -- q the prepared bf16 queries [n, n_head * hd] (a larger row stride is honoured, out's must
+        equal it), rows pos0 .. pos0 + n - 1 of k8 / v8 / ks / vs already written (kv8_quant_rows) -> out [n, n_head * hd]"""
+        if out is None:   # rows as far apart as q's: the entry has one row stride for both
+            out = torch.empty((q.shape[0], q.stride(0)), dtype=q.dtype, device=q.device)[:, :q.shape[1]]
+        assert out.stride(0) == q.stride(0) and q.stride(1) == 1 and out.stride(1) == 1
+        L.check(self.hip.kf_attn_prefill_kv8(self.h, _ptr(q), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), _ptr(out), pos0, q.shape[0], q.stride(0), n_head, n_kv, hd,
+                                             k8.stride(0)), "kf_attn_prefill_kv8")
+        return out
+
     def attn_block_kv8(self, q_raw, k_raw, v_raw, k8, v8, ks, vs, wq, wk, table, pos, n_head, n_kv, hd, eps=1e-6, d_pos=None, ws=None):
         """kf_attn_block_kv8: kf_attn_block's contract on the int8 cache -- the new K / V rows are quantised and written (with their steps) at the position; pos is the
         launch bound when d_pos (an int32 device tensor holding the position) is given"""
@@ -680,7 +690,7 @@ class Qwen3:
 
     def set_kv_int8(self, on):
         """The int8 KV cache (include/kf_abi.h "int8 KV cache"): K / V rows as int8 codes with one fp32 step per row and kv-head, decode attention on exact integer scores
-        (kf_attn_block_kv8), token batches on the dequantised rows; forward, run_steps, generate (graphs included), prefill, score and perplexity, on per-layer launches
+        (kf_attn_block_kv8), token batches on the dequantised rows (or, with set_kv_int8_prefill, on the int8 rows); forward, run_steps, generate (graphs included), prefill, score and perplexity, on per-layer launches
         (engine_why() says so).  The two caches are independent: switching converts nothing, prefill again.  Raises with the reason on a TP rank, with int8 activations,
         adapters, a hot-row mask or fuse_level 0."""
         rc = self.host.kfh_set_kv_int8(self.h, int(bool(on)))
@@ -689,6 +699,25 @@ class Qwen3:
 
     def kv_int8(self):
         return bool(self.host.kfh_kv_int8(self.h))
+
+    def set_kv_int8_prefill(self, on):
+        """The int8 prompt attention, a sub-setting of the int8 KV cache (include/kf_abi.h "int8 KV cache, the prompt form"): prefill, score, perplexity and every
+        chunk of them attend to the int8 rows themselves (kf_attn_prefill_kv8: integer scores, the decode kernel's score and weight arithmetic) instead of the
+        dequantised staging pair.  Off by default; off: the dequantise route, bit for bit.  Raises with the reason unless set_kv_int8(True) came first;
+        set_kv_int8(False) switches it off too.  Captured graphs are dropped at the switch."""
+        rc = self.host.kfh_set_kv_int8_prefill(self.h, int(bool(on)))
+        if rc != 0:
+            raise L.KFError("set_kv_int8_prefill failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+
+    def kv_int8_prefill(self):
+        return bool(self.host.kfh_kv_int8_prefill(self.h))
+
+    def kv8_route_counts(self, reset=False):
+        """prompt-attention launches of the token batches on the int8 cache since the last reset: {"prefill_int8": kf_attn_prefill_kv8, "prefill_dequant": the
+        dequantise route}; reset=True zeroes them after the read"""
+        out = (C.c_int64 * 2)()
+        L.check(self.host.kfh_kv8_route_counts(self.h, out, int(bool(reset))), "kfh_kv8_route_counts")
+        return {"prefill_int8": int(out[0]), "prefill_dequant": int(out[1])}
 
     def kv8_to_host(self):
         """the int8 cache copied to the host: (k8 int8 [n_layer, max_seq, kv_dim], ks fp32 [n_layer, max_seq, n_kv], v8, vs); allocated by the first set_kv_int8(True)"""
