@@ -707,9 +707,22 @@ int kf_qknorm_rope(kf_ctx* c, kf_bf16* q, kf_bf16* k, const kf_bf16* wq, const k
 }
 
 size_t kf_attn_scratch_bytes(int n_head, int hd) { return kf::attn_decode_scratch_bytes(n_head, hd); }
+// q 16-byte and out 8-byte aligned: the tile kernels' rows
+static int attn_al(const void* q, const void* out) { return (al16(q) ? kf::ATTN_Q_AL : 0) | (((uintptr_t)out & 7) == 0 ? kf::ATTN_OUT_AL : 0); }
 static kf::AttnProblem attn_problem(int entry, kf_ctx* c, int n_head, int n_kv, int hd, int pos, int n_tok, int n_seq, const void* q, const void* out, long long q_stride,
-                                    long long out_stride, long long kv_stride) { /* q 16-byte and out 8-byte aligned: the tile kernel's rows */
-    return kf::AttnProblem{entry, n_head, n_kv, hd, pos, n_tok, n_seq, c->canonical, (al16(q) ? kf::ATTN_Q_AL : 0) | (((uintptr_t)out & 7) == 0 ? kf::ATTN_OUT_AL : 0), q_stride, out_stride, kv_stride};
+                                    long long out_stride, long long kv_stride) {
+    return kf::AttnProblem{entry, n_head, n_kv, hd, pos, n_tok, n_seq, c->canonical, attn_al(q, out), q_stride, out_stride, kv_stride};
+}
+// the decode kernel's arguments of kf_attn_decode, kf_attn_block and kf_attn_prefill's per-token route: what is not named stays 0 (no new key, q prepared, no scratch)
+static kf::AttnArgs attn_args(kf_ctx* c, const kf_bf16* q, kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, int pos, const int32_t* d_pos, int n_head, int n_kv, int hd,
+                              int kv_stride, void* scratch) {
+    kf::AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.canon = c->canonical, a.q = q, a.kcache = kc, a.vcache = vc, a.out = out;
+    a.pos = pos, a.d_pos = d_pos, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
+    if (scratch) /* the first KF_ATTN_CNT_BYTES: arrival counters (fixed place whatever the shape); the partials behind them */
+        a.counters = (int*)scratch, a.part = (float*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
+    return a;
 }
 
 int kf_attn_decode(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, int pos, const int32_t* d_pos, int n_head, int n_kv, int hd,
@@ -717,12 +730,7 @@ int kf_attn_decode(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf16
     CHKCTX(c);
     if (!q || !kc || !vc || !out || !scratch) return fail(KF_INVALID_ARGS, "kf_attn_decode: null pointer");
     if (!al16(kc) || !al16(vc) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_decode: cache not 16-byte aligned");
-    kf::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.canon = c->canonical;
-    a.q = q, a.kcache = const_cast<kf_bf16*>(kc), a.vcache = vc, a.out = out, a.part = (float*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
-    a.pos = pos, a.d_pos = d_pos, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
-    a.counters = (int*)scratch; /* the first KF_ATTN_CNT_BYTES: arrival counters (fixed place whatever the shape) */
+    kf::AttnArgs a = attn_args(c, q, const_cast<kf_bf16*>(kc), vc, out, pos, d_pos, n_head, n_kv, hd, kv_stride, scratch);
     RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q, out, 0, 0, 0))));
 }
 
@@ -731,13 +739,8 @@ int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16
     CHKCTX(c);
     if (!q_raw || !k_raw || !kc || !vc || !out || !scratch || !table) return fail(KF_INVALID_ARGS, "kf_attn_block: null pointer");
     if (!al16(kc) || !al16(vc) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_block: cache not 16-byte aligned");
-    kf::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.canon = c->canonical;
-    a.q = q_raw, a.k_raw = k_raw, a.kcache = kc, a.vcache = vc, a.out = out, a.part = (float*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
-    a.wq_norm = wq, a.wk_norm = wk, a.rope_table = table, a.eps = eps;
-    a.pos = pos, a.d_pos = d_pos, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
-    a.counters = (int*)scratch;
+    kf::AttnArgs a = attn_args(c, q_raw, kc, vc, out, pos, d_pos, n_head, n_kv, hd, kv_stride, scratch);
+    a.k_raw = k_raw, a.wq_norm = wq, a.wk_norm = wk, a.rope_table = table, a.eps = eps;
     RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q_raw, out, 0, 0, 0))));
 }
 
@@ -796,8 +799,7 @@ int kf_attn_prefill_kv8(kf_ctx* c, const kf_bf16* q, const int8_t* k8, const int
     CHKCTX(c);
     if (!q || !k8 || !v8 || !ks || !vs || !out) return fail(KF_INVALID_ARGS, "kf_attn_prefill_kv8: null pointer");
     if (!al16(k8) || !al16(v8)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill_kv8: cache not 16-byte aligned");
-    const int al = (al16(q) ? kf::ATTN_Q_AL : 0) | (((uintptr_t)out & 7) == 0 ? kf::ATTN_OUT_AL : 0);
-    const kf::AttnPlan p = kf::attn_plan(kv8_prefill_problem(n_head, n_kv, hd, pos0, n_tok, al, q_stride, kv_stride));
+    const kf::AttnPlan p = kf::attn_plan(kv8_prefill_problem(n_head, n_kv, hd, pos0, n_tok, attn_al(q, out), q_stride, kv_stride));
     if (p.status == KF_BLAS_UNALIGN)
         return fail(p.status, "kf_attn_prefill_kv8: kv_stride %d is not a multiple of 16, q_stride %lld not a multiple of 8, q not 16-byte or out not 8-byte aligned", kv_stride,
                     (long long)q_stride);
@@ -991,11 +993,7 @@ int kf_attn_prefill(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf1
         if (rc != KF_OK) return fail(rc, "kf_attn_prefill: launch failed (%d)", rc);
         return KF_OK;
     }
-    kf::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.canon = c->canonical;
-    a.q = q, a.kcache = const_cast<kf_bf16*>(kc), a.vcache = vc, a.out = out;
-    a.pos = pos0, a.n_head = n_head, a.n_kv = n_kv, a.hd = hd, a.kv_stride = kv_stride;
+    kf::AttnArgs a = attn_args(c, q, const_cast<kf_bf16*>(kc), vc, out, pos0, nullptr, n_head, n_kv, hd, kv_stride, nullptr);
     a.q_stride = q_stride, a.one_slice = 1;
     RET(kf::attn_launch(c->stream, a, p));
 }

@@ -31,28 +31,24 @@ namespace kf {
 template <int GQ, int NW, int HD>
 __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int hd = HD, hd_log2 = HD == 128 ? 7 : 6; /* head_dim 64 or 128: compile-time, so that the lane-group reductions are straight-line code */
+    using Slice = AttnSlice<GQ, NW, HD, 8>; /* the shell (kf_attn_common.h): 8 dims of a key per lane */
+    constexpr int hd = HD, LPK = Slice::LPK, KPW = Slice::KPW, lpk_log2 = Slice::lpk_log2, tstride = Slice::tstride, NQ = Slice::NQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int PS = hd + 2; /* {O[hd], L, m} as doubles */
-    double* comb = reinterpret_cast<double*>(smem_raw);        // [NW][GQ][PS]
-    uint16_t* qb = reinterpret_cast<uint16_t*>(comb + NW * GQ * PS);  // [GQ][hd] prepared q, bf16 bits
-    uint16_t* knew = qb + GQ * hd;                         // [hd]
-    int* flag = reinterpret_cast<int*>(knew + hd);
+    constexpr AttnCanonLds lds(GQ, NW, HD);
+    static_assert(lds.fits(), "LDS");
+    double* comb = reinterpret_cast<double*>(smem_raw + lds.comb);
+    uint16_t* qb = reinterpret_cast<uint16_t*>(smem_raw + lds.qb);
+    uint16_t* knew = reinterpret_cast<uint16_t*>(smem_raw + lds.knew);
+    int* flag = reinterpret_cast<int*>(smem_raw + lds.flag);
 
-    const int split = blockIdx.x, kvh = (int)blockIdx.y / a.gq_split, gpart = (int)blockIdx.y - kvh * a.gq_split, nsp = a.n_splits;
+    const Slice sl(a.gq_split, a.chunk);
     // token batch (prefill): blockIdx.z = token, one slice per kv-head, position pos0 + token, q / out rows q_stride apart
-    const int pos_l = a.pos + (int)blockIdx.z;
+    const int pos_l = a.pos + (int)blockIdx.z, nsp = a.n_splits;
     const uint16_t* const qsrc = a.q + (size_t)blockIdx.z * a.q_stride;
     uint16_t* const odst = a.out + (size_t)blockIdx.z * a.q_stride;
-    const int chunk = a.chunk; /* keys per slice, fixed by the launch bound so that the K/V stream can start before pos is known */
-    const int t0 = split * chunk;
-    const int h0 = (kvh * a.gq_split + gpart) * GQ; /* GQ = the heads of THIS workgroup */
-
-    // LPK lanes per key (8 dims each), KPW keys per wave step, the waves interleaved over the slice
-    constexpr int LPK = hd >> 3, KPW = 64 / LPK, lpk_log2 = hd_log2 - 3;
-    const int grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 8;
+    const int h0 = sl.h0(), grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 8, tstart = sl.tstart(wave, grp);
     const bool has_new = a.k_raw != nullptr;
-    const int tstart = t0 + wave * KPW + grp, tstride = NW * KPW;
 
     // ---- issue the first K/V tiles before anything else: they depend neither on the position (read from device memory in
     // graph replay) nor on the previous kernel's q.  Rows up to the launch bound exist in the cache; rows past the real position
@@ -64,19 +60,14 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
             const int t = tb + u * tstride;
             kk[u] = u32x4{0, 0, 0, 0}, vv[u] = u32x4{0, 0, 0, 0};
             if (t < tend) {
-                const size_t off = (size_t)t * a.kv_stride + (size_t)kvh * hd + d0;
+                const size_t off = (size_t)t * a.kv_stride + (size_t)sl.kvh * hd + d0;
                 kk[u] = *reinterpret_cast<const u32x4*>(a.kcache + off);
                 vv[u] = *reinterpret_cast<const u32x4*>(a.vcache + off);
             }
         }
     };
-    {
-        int tb_end = t0 + chunk;
-        if (tb_end > pos_l + 1) tb_end = pos_l + 1; /* a.pos is the launch bound here */
-        issue(tstart, tb_end);
-    }
+    issue(tstart, sl.end(pos_l)); /* a.pos is the launch bound here */
     // ... and the q heads (+ the raw new key) this wave will prepare: they do not depend on the position either
-    constexpr int NQ = (GQ + NW - 1) / NW;
     const bool qnorm = a.rope_table && a.wq_norm;
     HeadRaw qraw[NQ];
 #pragma unroll
@@ -84,13 +75,9 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
         const int hq = wave + i * NW;
         qraw[i] = load_head(qsrc + (size_t)(h0 + (hq < GQ ? hq : 0)) * hd, qnorm ? a.wq_norm : nullptr, hd);
     }
-    const HeadRaw kraw = load_head(has_new ? a.k_raw + (size_t)kvh * hd : qsrc, a.wk_norm, hd);
+    const HeadRaw kraw = load_head(has_new ? a.k_raw + (size_t)sl.kvh * hd : qsrc, a.wk_norm, hd);
 
-    const int pos = a.d_pos ? *a.d_pos : pos_l;
-    const int len = pos + 1;
-    int t1 = t0 + chunk;
-    if (t1 > len) t1 = len;
-    const bool empty = t0 >= len;
+    const auto [pos, t1, empty] = sl.at(a.d_pos, pos_l);
     double* const part = reinterpret_cast<double*>(a.part); /* [n_head][n_splits][PS] doubles */
 
     if (!empty) {
@@ -99,11 +86,11 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
 #pragma unroll
         for (int i = 0; i < NQ; i++)
             if (wave + i * NW < GQ) prep_head(qraw[i], qnorm, tab_pos, hd, a.eps, qb + (wave + i * NW) * hd);
-        const bool own_new = has_new && (pos >= t0) && (pos < t1);
+        const bool own_new = has_new && sl.holds(pos, t1);
         if (own_new && wave == (GQ % NW)) prep_head(kraw, a.wk_norm != nullptr, tab_pos, hd, a.eps, knew);
         __syncthreads();
-        if (own_new && gpart == 0) {
-            uint16_t* krow = a.kcache + (size_t)pos * a.kv_stride + (size_t)kvh * hd;
+        if (own_new && sl.gpart == 0) { /* every part of the kv-head holds the same row: one writes it */
+            uint16_t* krow = a.kcache + (size_t)pos * a.kv_stride + (size_t)sl.kvh * hd;
             for (int i = tid; i < hd; i += blockDim.x) krow[i] = knew[i];
         }
         float qf[GQ][8]; /* this lane's 8 dims of every q head */
@@ -132,9 +119,9 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
         // ---- the wave's key groups summed (reduce-scatter by row swaps), the waves through LDS: exact rescales to the slice's maximum exponent
         canon_wave_to_lds<GQ, LPK>(A, comb + (size_t)wave * GQ * PS, hd, lane, d0);
         __syncthreads();
-        canon_slice_publish<GQ, NW, HD>(comb, part, odst, h0, nsp, split);
+        canon_slice_publish<GQ, NW, HD>(comb, part, odst, h0, nsp, sl.split);
     } else if (nsp > 1) { /* empty slice: neutral partial, but it still arrives */
-        canon_slice_publish_empty<GQ, HD>(part, h0, nsp, split);
+        canon_slice_publish_empty<GQ, HD>(part, h0, nsp, sl.split);
     }
     if (nsp == 1) return;
     // ---- arrival; the last workgroup of this kv-head merges (kf_attn_common.h)
@@ -147,33 +134,26 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
 template <int GQ, int NW, int HD>
 __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int hd = HD, hd_log2 = HD == 128 ? 7 : 6; /* head_dim 64 or 128: compile-time, so that the lane-group reductions are straight-line code */
+    using Slice = AttnSlice<GQ, NW, HD, 8>;
+    constexpr int hd = HD, hd_log2 = Slice::hd_log2, LPK = Slice::LPK, KPW = Slice::KPW, lpk_log2 = Slice::lpk_log2, tstride = Slice::tstride, NQ = Slice::NQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int PS = hd + 4; /* {acc[hd], m, l, pad, pad} */
-    uint16_t* qb = reinterpret_cast<uint16_t*>(smem_raw);  // [GQ][hd] prepared q, bf16 bits
-    uint16_t* knew = qb + GQ * hd;                         // [hd]
-    float* wmax = reinterpret_cast<float*>(knew + hd);     // [NW][GQ]
-    int* flag = reinterpret_cast<int*>(wmax + NW * GQ);
-    float* comb = reinterpret_cast<float*>(flag + 4);  // [NW][GQ][PS]
+    constexpr AttnFastLds lds(GQ, NW, HD);
+    static_assert(lds.fits(), "LDS");
+    uint16_t* qb = reinterpret_cast<uint16_t*>(smem_raw + lds.qb);
+    uint16_t* knew = reinterpret_cast<uint16_t*>(smem_raw + lds.knew);
+    float* wmax = reinterpret_cast<float*>(smem_raw + lds.wmax);
+    int* flag = reinterpret_cast<int*>(smem_raw + lds.flag);
+    float* comb = reinterpret_cast<float*>(smem_raw + lds.comb);
 
-    const int split = blockIdx.x, kvh = (int)blockIdx.y / a.gq_split, gpart = (int)blockIdx.y - kvh * a.gq_split, nsp = a.n_splits;
-    // token batch (prefill): blockIdx.z = token, one slice per kv-head, position pos0 + token, q / out rows q_stride apart
-    const int pos_l = a.pos + (int)blockIdx.z;
+    // the shell, as in attn_kernel
+    const Slice sl(a.gq_split, a.chunk);
+    const int pos_l = a.pos + (int)blockIdx.z, nsp = a.n_splits;
     const uint16_t* const qsrc = a.q + (size_t)blockIdx.z * a.q_stride;
     uint16_t* const odst = a.out + (size_t)blockIdx.z * a.q_stride;
-    const int chunk = a.chunk; /* keys per slice, fixed by the launch bound so that the K/V stream can start before pos is known */
-    const int t0 = split * chunk;
-    const int h0 = (kvh * a.gq_split + gpart) * GQ; /* GQ = the heads of THIS workgroup */
-
-    // LPK lanes per key (8 dims each), KPW keys per wave step, the waves interleaved over the slice
-    constexpr int LPK = hd >> 3, KPW = 64 / LPK, lpk_log2 = hd_log2 - 3;
-    const int grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 8;
+    const int h0 = sl.h0(), grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 8, tstart = sl.tstart(wave, grp);
     const bool has_new = a.k_raw != nullptr;
-    const int tstart = t0 + wave * KPW + grp, tstride = NW * KPW;
 
-    // ---- issue the first K/V tiles before anything else: they depend neither on the position (read from device memory in
-    // graph replay) nor on the previous kernel's q.  Rows up to the launch bound exist in the cache; rows past the real position
-    // are masked later, and the row AT the position is replaced by the freshly normed+roped key.
     u32x4 kk[ATTN_U], vv[ATTN_U];
     auto issue = [&](int tb, int tend) {
 #pragma unroll
@@ -181,19 +161,13 @@ __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
             const int t = tb + u * tstride;
             kk[u] = u32x4{0, 0, 0, 0}, vv[u] = u32x4{0, 0, 0, 0};
             if (t < tend) {
-                const size_t off = (size_t)t * a.kv_stride + (size_t)kvh * hd + d0;
+                const size_t off = (size_t)t * a.kv_stride + (size_t)sl.kvh * hd + d0;
                 kk[u] = *reinterpret_cast<const u32x4*>(a.kcache + off);
                 vv[u] = *reinterpret_cast<const u32x4*>(a.vcache + off);
             }
         }
     };
-    {
-        int tb_end = t0 + chunk;
-        if (tb_end > pos_l + 1) tb_end = pos_l + 1; /* a.pos is the launch bound here */
-        issue(tstart, tb_end);
-    }
-    // ... and the q heads (+ the raw new key) this wave will prepare: they do not depend on the position either
-    constexpr int NQ = (GQ + NW - 1) / NW;
+    issue(tstart, sl.end(pos_l));
     const bool qnorm = a.rope_table && a.wq_norm;
     HeadRaw qraw[NQ];
 #pragma unroll
@@ -201,25 +175,20 @@ __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
         const int hq = wave + i * NW;
         qraw[i] = load_head(qsrc + (size_t)(h0 + (hq < GQ ? hq : 0)) * hd, qnorm ? a.wq_norm : nullptr, hd);
     }
-    const HeadRaw kraw = load_head(has_new ? a.k_raw + (size_t)kvh * hd : qsrc, a.wk_norm, hd);
+    const HeadRaw kraw = load_head(has_new ? a.k_raw + (size_t)sl.kvh * hd : qsrc, a.wk_norm, hd);
 
-    const int pos = a.d_pos ? *a.d_pos : pos_l;
-    const int len = pos + 1;
-    int t1 = t0 + chunk;
-    if (t1 > len) t1 = len;
-    const bool empty = t0 >= len;
+    const auto [pos, t1, empty] = sl.at(a.d_pos, pos_l);
 
     if (!empty) {
-        // ---- prologue: q heads of this group, and the new key when it lies in this slice
         const float* tab_pos = a.rope_table ? a.rope_table + (size_t)pos * hd : nullptr;
 #pragma unroll
         for (int i = 0; i < NQ; i++)
             if (wave + i * NW < GQ) prep_head(qraw[i], qnorm, tab_pos, hd, a.eps, qb + (wave + i * NW) * hd);
-        const bool own_new = has_new && (pos >= t0) && (pos < t1);
+        const bool own_new = has_new && sl.holds(pos, t1);
         if (own_new && wave == (GQ % NW)) prep_head(kraw, a.wk_norm != nullptr, tab_pos, hd, a.eps, knew);
         __syncthreads();
-        if (own_new && gpart == 0) {
-            uint16_t* krow = a.kcache + (size_t)pos * a.kv_stride + (size_t)kvh * hd;
+        if (own_new && sl.gpart == 0) { /* every part of the kv-head holds the same row: one writes it */
+            uint16_t* krow = a.kcache + (size_t)pos * a.kv_stride + (size_t)sl.kvh * hd;
             for (int i = tid; i < hd; i += blockDim.x) krow[i] = knew[i];
         }
         u32x4 qreg[GQ]; /* this lane's 8 dims of every q head, packed bf16 */
@@ -342,7 +311,7 @@ __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
                 float Mh = M[0];
 #pragma unroll
                 for (int q2 = 1; q2 < GQ; q2++) Mh = (hq == q2) ? M[q2] : Mh;
-                float* dst = a.part + ((size_t)(h0 + hq) * nsp + split) * PS;
+                float* dst = a.part + ((size_t)(h0 + hq) * nsp + sl.split) * PS;
                 st_sc1(dst + d, o);
                 if (d == 0) st_sc1(dst + hd, Mh), st_sc1(dst + hd + 1, L);
             }
@@ -350,7 +319,7 @@ __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
     } else if (nsp > 1) { /* empty slice: neutral partial, but it still arrives */
         for (int i = tid; i < GQ * hd; i += blockDim.x) {
             const int hq = i >> hd_log2, d = i & (hd - 1);
-            float* dst = a.part + ((size_t)(h0 + hq) * nsp + split) * PS;
+            float* dst = a.part + ((size_t)(h0 + hq) * nsp + sl.split) * PS;
             st_sc1(dst + d, 0.f);
             if (d == 0) st_sc1(dst + hd, -__builtin_inff()), st_sc1(dst + hd + 1, 0.f);
         }

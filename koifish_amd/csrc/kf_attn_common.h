@@ -1,5 +1,6 @@
-// kf_attn_common.h -- pieces of the decode attention shared by kf_attn.hip and the persistent decode engine (kf_engine.hip):
-// per-head q/k RMSNorm + rotate-half RoPE (ROPE::cuInfer, rope.cu:645-672), the hardware-exp2 softmax exponent, sc1 accessors.
+// kf_attn_common.h -- pieces of the decode attention shared by kf_attn.hip, kf_attn_kv8.hip and the persistent decode engines (kf_engine.hip, kf_xengine*.hip):
+// per-head q/k RMSNorm + rotate-half RoPE (ROPE::cuInfer, rope.cu:645-672), the hardware-exp2 softmax exponent, sc1 accessors; the decode slice shell (AttnSlice: grid
+// decode, lane geometry and slice ends of the three decode kernels), the canonical order's batch, publish and merge, the int8 cache's row quantiser.
 #pragma once
 #include "kf_kernels.h"
 
@@ -62,6 +63,36 @@ __device__ __forceinline__ void prep_head(const HeadRaw r, bool norm, const floa
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269502162933349609375f); }
 
 constexpr int ATTN_U = 4; /* key tiles kept in flight per wave */
+
+// ------------------------------------------------------------------------------------------------ the decode slice shell
+// What attn_kernel, attn_fast_kernel (kf_attn.hip) and attn_kv8_kernel (kf_attn_kv8.hip) share in front of their arithmetic: which slice of which kv-head and which of
+// its parts a workgroup is (blockIdx = (slice, kv-head * gq_split + part)), the lane geometry, where a run of tiles ends, what the position makes of the slice.
+// EL = the elements of a key one lane holds: 8 (bf16 rows) or 16 (int8 rows).  The q heads' load / prepare loops, the batch loop's two bounds, the issue of the tiles
+// and the lane's grp / d0 are NOT here: shared, they changed the compiler's output, so each kernel spells them out.
+struct AttnAt { int pos, t1; bool empty; }; /* the position, the slice's end against it, the slice lies wholly behind it */
+template <int GQ, int NW, int HD, int EL>
+struct AttnSlice {
+    static constexpr int hd_log2 = HD == 128 ? 7 : 6; /* head_dim 64 or 128: compile-time, so that the lane-group reductions are straight-line code */
+    // LPK lanes per key (EL elements each), KPW keys per wave step, the waves interleaved over the slice; NQ q heads a wave loads and prepares
+    static constexpr int LPK = HD / EL, KPW = 64 / LPK, lpk_log2 = hd_log2 - (EL == 16 ? 4 : 3), tstride = NW * KPW, NQ = (GQ + NW - 1) / NW;
+    // chunk = keys per slice, fixed by the launch bound so that the K/V stream can start before pos is known; t0 its first key
+    const int gq_split, split, kvh, gpart, chunk, t0;
+    __device__ __forceinline__ AttnSlice(int gq_split_, int chunk_)
+        : gq_split(gq_split_), split(blockIdx.x), kvh((int)blockIdx.y / gq_split), gpart((int)blockIdx.y - kvh * gq_split), chunk(chunk_), t0(split * chunk) {}
+    __device__ __forceinline__ int h0() const { return (kvh * gq_split + gpart) * GQ; } /* the first of the GQ heads of THIS workgroup */
+    __device__ __forceinline__ int tstart(int wave, int grp) const { return t0 + wave * KPW + grp; } /* the first key a lane walks (then every tstride-th) */
+    __device__ __forceinline__ int end(int last) const { /* of the slice's keys among 0 .. last */
+        int t = t0 + chunk;
+        if (t > last + 1) t = last + 1;
+        return t;
+    }
+    __device__ __forceinline__ AttnAt at(const int* d_pos, int pos_bound) const { /* the position: read from device memory in graph replay, else the launch bound */
+        const int pos = d_pos ? *d_pos : pos_bound, len = pos + 1;
+        return AttnAt{pos, end(pos), t0 >= len};
+    }
+    // the new row lies in this slice: the wave behind the q heads' waves prepares it (a second row: the wave behind that), part 0 of the kv-head writes it
+    __device__ __forceinline__ bool holds(int pos, int t1) const { return (pos >= t0) && (pos < t1); }
+};
 
 // ------------------------------------------------------------------------------------------------ canonical decode attention
 // The order kernels and oracle share (oracle/kf_oracle.c section 6, mode CANON), free of launch geometry:

@@ -94,27 +94,24 @@ __device__ __forceinline__ void kv8_batch(Kv8Acc<GQ>& A, const u32x4 (&q8)[GQ], 
 template <int GQ, int HD>
 __global__ void __launch_bounds__(ATTN_KV8_NW * 64) attn_kv8_kernel(const AttnKv8Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int NW = ATTN_KV8_NW, U = ATTN_KV8_U, hd = HD, hd_log2 = HD == 128 ? 7 : 6;
+    constexpr int NW = ATTN_KV8_NW, U = ATTN_KV8_U, hd = HD;
+    using Slice = AttnSlice<GQ, NW, HD, 16>; /* the shell (kf_attn_common.h): 16 codes of a key per lane */
+    constexpr int LPK = Slice::LPK, KPW = Slice::KPW, lpk_log2 = Slice::lpk_log2, tstride = Slice::tstride, NQ = Slice::NQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int PS = hd + 2; /* {O[hd], L, m} as doubles */
-    double* comb = reinterpret_cast<double*>(smem_raw);               // [NW][GQ][PS]
-    uint16_t* qb = reinterpret_cast<uint16_t*>(comb + NW * GQ * PS);  // [GQ][hd] prepared q, bf16 bits
-    uint16_t* knew = qb + GQ * hd;                                    // [hd] prepared new key, bf16 bits
-    int8_t* q8 = reinterpret_cast<int8_t*>(knew + hd);                // [GQ][hd] the q heads' codes
-    int8_t* k8n = q8 + GQ * hd;                                       // [hd] the new K row's codes
-    int8_t* v8n = k8n + hd;                                           // [hd] the new V row's codes
-    float* stp = reinterpret_cast<float*>(v8n + hd);                  // [GQ] q steps, then the new K row's and the new V row's
-    int* flag = reinterpret_cast<int*>(stp + GQ + 2);
+    constexpr AttnKv8Lds lds(GQ, HD);
+    static_assert(lds.fits(), "LDS");
+    double* comb = reinterpret_cast<double*>(smem_raw + lds.comb);
+    uint16_t* qb = reinterpret_cast<uint16_t*>(smem_raw + lds.qb);
+    uint16_t* knew = reinterpret_cast<uint16_t*>(smem_raw + lds.knew);
+    int8_t* q8 = reinterpret_cast<int8_t*>(smem_raw + lds.q8);
+    int8_t* k8n = reinterpret_cast<int8_t*>(smem_raw + lds.k8n);
+    int8_t* v8n = reinterpret_cast<int8_t*>(smem_raw + lds.v8n);
+    float* stp = reinterpret_cast<float*>(smem_raw + lds.stp);
+    int* flag = reinterpret_cast<int*>(smem_raw + lds.flag);
 
-    const int split = blockIdx.x, kvh = (int)blockIdx.y / a.gq_split, gpart = (int)blockIdx.y - kvh * a.gq_split, nsp = a.n_splits;
-    const int chunk = a.chunk; /* keys per slice, fixed by the launch bound so that the K/V stream can start before pos is known */
-    const int t0 = split * chunk;
-    const int h0 = (kvh * a.gq_split + gpart) * GQ; /* GQ = the heads of THIS workgroup */
-
-    // LPK lanes per key (16 codes each), KPW keys per wave step, the waves interleaved over the slice
-    constexpr int LPK = hd >> 4, KPW = 64 / LPK, lpk_log2 = hd_log2 - 4;
-    const int grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 16;
-    const int tstart = t0 + wave * KPW + grp, tstride = NW * KPW;
+    const Slice sl(a.gq_split, a.chunk);
+    const int nsp = a.n_splits, h0 = sl.h0(), grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 16, tstart = sl.tstart(wave, grp);
 
     // ---- the first K/V tiles and their steps before anything else: rows up to the launch bound exist in the cache (zero-filled at allocation: finite); rows past the
     // real position are masked later, and the row AT the position is replaced by the freshly quantised one
@@ -126,21 +123,16 @@ __global__ void __launch_bounds__(ATTN_KV8_NW * 64) attn_kv8_kernel(const AttnKv
             const int t = tb + u * tstride;
             kk[u] = u32x4{0, 0, 0, 0}, vv[u] = u32x4{0, 0, 0, 0}, ksr[u] = 0.0f, vsr[u] = 0.0f;
             if (t < tend) {
-                const size_t off = (size_t)t * a.kv_stride + (size_t)kvh * hd + d0;
+                const size_t off = (size_t)t * a.kv_stride + (size_t)sl.kvh * hd + d0;
                 kk[u] = *reinterpret_cast<const u32x4*>(a.k8 + off);
                 vv[u] = *reinterpret_cast<const u32x4*>(a.v8 + off);
-                ksr[u] = a.ks[(size_t)t * a.n_kv + kvh];
-                vsr[u] = a.vs[(size_t)t * a.n_kv + kvh];
+                ksr[u] = a.ks[(size_t)t * a.n_kv + sl.kvh];
+                vsr[u] = a.vs[(size_t)t * a.n_kv + sl.kvh];
             }
         }
     };
-    {
-        int tb_end = t0 + chunk;
-        if (tb_end > a.pos + 1) tb_end = a.pos + 1; /* a.pos is the launch bound here */
-        issue(tstart, tb_end);
-    }
+    issue(tstart, sl.end(a.pos)); /* a.pos is the launch bound here */
     // ... and the q heads, the raw new key and the new value row this wave will prepare: they do not depend on the position either
-    constexpr int NQ = (GQ + NW - 1) / NW;
     const bool qnorm = a.wq_norm != nullptr;
     HeadRaw qraw[NQ];
 #pragma unroll
@@ -148,14 +140,10 @@ __global__ void __launch_bounds__(ATTN_KV8_NW * 64) attn_kv8_kernel(const AttnKv
         const int hq = wave + i * NW;
         qraw[i] = load_head(a.q + (size_t)(h0 + (hq < GQ ? hq : 0)) * hd, a.wq_norm, hd);
     }
-    const HeadRaw kraw = load_head(a.k_raw + (size_t)kvh * hd, a.wk_norm, hd);
-    const HeadRaw vraw = load_head(a.v_raw + (size_t)kvh * hd, nullptr, hd);
+    const HeadRaw kraw = load_head(a.k_raw + (size_t)sl.kvh * hd, a.wk_norm, hd);
+    const HeadRaw vraw = load_head(a.v_raw + (size_t)sl.kvh * hd, nullptr, hd);
 
-    const int pos = a.d_pos ? *a.d_pos : a.pos;
-    const int len = pos + 1;
-    int t1 = t0 + chunk;
-    if (t1 > len) t1 = len;
-    const bool empty = t0 >= len;
+    const auto [pos, t1, empty] = sl.at(a.d_pos, a.pos);
     double* const part = a.part; /* [n_head][n_splits][PS] doubles */
 
     if (!empty) {
@@ -168,18 +156,18 @@ __global__ void __launch_bounds__(ATTN_KV8_NW * 64) attn_kv8_kernel(const AttnKv
                 prep_head(qraw[i], qnorm, tab_pos, hd, a.eps, qb + hq * hd);
                 quant_head_lds(qb + hq * hd, hd, q8 + hq * hd, stp + hq);
             }
-        const bool own_new = (pos >= t0) && (pos < t1);
+        const bool own_new = sl.holds(pos, t1);
         if (own_new && wave == (GQ % NW)) {
             prep_head(kraw, a.wk_norm != nullptr, tab_pos, hd, a.eps, knew);
             quant_head_lds(knew, hd, k8n, stp + GQ);
         }
         if (own_new && wave == ((GQ + 1) % NW)) quant_head(bf2f(vraw.x0), bf2f(vraw.x1), hd, v8n, stp + GQ + 1);
         __syncthreads();
-        if (own_new && gpart == 0) { /* every part of the kv-head holds the same row: one writes it */
-            int8_t* krow = a.k8 + (size_t)pos * a.kv_stride + (size_t)kvh * hd;
-            int8_t* vrow = a.v8 + (size_t)pos * a.kv_stride + (size_t)kvh * hd;
+        if (own_new && sl.gpart == 0) { /* every part of the kv-head holds the same row: one writes it */
+            int8_t* krow = a.k8 + (size_t)pos * a.kv_stride + (size_t)sl.kvh * hd;
+            int8_t* vrow = a.v8 + (size_t)pos * a.kv_stride + (size_t)sl.kvh * hd;
             for (int i = tid; i < hd; i += blockDim.x) krow[i] = k8n[i], vrow[i] = v8n[i];
-            if (tid == 0) a.ks[(size_t)pos * a.n_kv + kvh] = stp[GQ], a.vs[(size_t)pos * a.n_kv + kvh] = stp[GQ + 1];
+            if (tid == 0) a.ks[(size_t)pos * a.n_kv + sl.kvh] = stp[GQ], a.vs[(size_t)pos * a.n_kv + sl.kvh] = stp[GQ + 1];
         }
         u32x4 qreg[GQ]; /* this lane's 16 codes of every q head */
         float sq[GQ];
@@ -220,9 +208,9 @@ __global__ void __launch_bounds__(ATTN_KV8_NW * 64) attn_kv8_kernel(const AttnKv
         canon_wave_to_lds<GQ, 8>(A.lo, comb + (size_t)wave * GQ * PS, hd, lane, d0);
         canon_wave_to_lds<GQ, 8>(A.hi, comb + (size_t)wave * GQ * PS, hd, lane, d0 + 8);
         __syncthreads();
-        canon_slice_publish<GQ, NW, HD>(comb, part, a.out, h0, nsp, split);
+        canon_slice_publish<GQ, NW, HD>(comb, part, a.out, h0, nsp, sl.split);
     } else if (nsp > 1) {
-        canon_slice_publish_empty<GQ, HD>(part, h0, nsp, split);
+        canon_slice_publish_empty<GQ, HD>(part, h0, nsp, sl.split);
     }
     if (nsp == 1) return;
     canon_arrive_and_merge<GQ, NW, HD>(part, a.counters + (int)blockIdx.y * a.cnt_stride, flag, a.out, h0, nsp); /* per (kv-head, part): its slices' workgroups meet here */

@@ -1,6 +1,7 @@
 // kf_attn_plan.h -- how attention is launched: kf::attn_plan, one pure host function, picks the route, kernel form, slices, grid, threads, LDS and scratch of every
 // attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_kv8, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
 // kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_prefill_kv8.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
+// The Attn*Lds layouts are the ONE statement of every attention kernel's dynamic LDS: the plan's size and the kernels' pointers both come from them.
 #pragma once
 #include "kf_kernels.h"
 
@@ -24,7 +25,7 @@ constexpr int ATTN_TILE_MIN_TOK = 8, ATTN_TILE_COLS = 128;
 constexpr long ATTN_PAIR_MAX_WGS = 320;
 constexpr int ATTN_PAIR_MIN_TOK = 256;
 constexpr int AP_KT = 32, AP_KT_LONG = 64; /* keys per staged tile: tile kernel, paired form */
-constexpr int AP_VPAD = 32;                /* V row padding, elements (64 B): rows 4 apart in a transposing read land on distinct 16-bank groups (K rows: 8) */
+constexpr int AP_KPAD = 8, AP_VPAD = 32;   /* K and V row padding, elements (16 B; 64 B: rows 4 apart in a transposing read land on distinct 16-bank groups) */
 // the int8 cache (kf_attn_kv8.hip): a lane holds 16 elements of a key, so a key takes hd / 16 lanes and a wave step twice the keys of the bf16 kernel; the slices are
 // attn_slices' (one rule), 4 waves always, ATTN_KV8_U tiles in flight per wave: one 64-key slice of hd = 128 is one batch of the workgroup (4 waves x 8 keys x 2 tiles)
 constexpr int ATTN_KV8_NW = 4, ATTN_KV8_U = 2;
@@ -50,6 +51,50 @@ constexpr AttnSlices attn_slices(int pos_bound, int n_kv, int gq, bool one_slice
 // scratch: the decode kernel's {O[hd], L, m} fp64 partials per (head, slice) behind the counters; the backward's L and D per (sequence, head, row)
 constexpr size_t attn_decode_scratch_bytes(int n_head, int hd) { return sizeof(double) * (size_t)n_head * KF_ATTN_MAX_SPLITS * (hd + 2) + KF_ATTN_CNT_BYTES; }
 constexpr size_t attn_backward_scratch_bytes(int T, int n_head, int n_seq) { return (T < 1 || n_head < 1 || n_seq < 1) ? 0 : sizeof(float) * 2 * (size_t)T * n_head * n_seq; }
+
+// ---- the LDS layouts, ONE statement per kernel: every buffer's byte offset in the dynamic LDS and the total.  attn_plan takes p.lds from `bytes`, the kernel its
+// pointers from the offsets and asserts fits() for the form it is.  take() hands out the buffers back to back in the order of the members and notes whether each starts
+// on its alignment: 8 for the fp64 partials (and the rows stored as float2), 4 for floats and ints, 16 for the rows read or written with 128-bit LDS accesses.
+constexpr int ATTN_LDS_MAX = 64 * 1024, ATTN_TILE_LDS_MAX = 160 * 1024; /* what a launcher can ask for; attn_prefill_mfma_launch raises the tile kernel to the second */
+struct AttnLds {
+    int bytes = 0;
+    bool sound = true; /* every buffer aligned, every alias inside what it lies over */
+    constexpr int take(int n, int align) { return sound = sound && bytes % align == 0, bytes += n, bytes - n; }
+    constexpr bool fits(int max = ATTN_LDS_MAX) const { return sound && bytes <= max; }
+};
+struct AttnCanonLds : AttnLds { /* attn_kernel<gq, nw, hd> */
+    int comb, qb, knew, flag;   /* [nw][gq][hd + 2] the waves' {O[hd], L, m} doubles; [gq][hd] prepared q heads and [hd] the new key, bf16 bits; the merge flag */
+    constexpr AttnCanonLds(int gq, int nw, int hd) : comb(take(8 * nw * gq * (hd + 2), 8)), qb(take(2 * gq * hd, 16)), knew(take(2 * hd, 16)), flag(take(16, 4)) {}
+};
+struct AttnFastLds : AttnLds { /* attn_fast_kernel<gq, nw, hd> */
+    int qb, knew, wmax, flag, comb; /* q heads and new key as above; [nw][gq] the waves' batch maxima; the flag; [nw][gq][hd + 4] floats {acc[hd], m, l, pad, pad} */
+    constexpr AttnFastLds(int gq, int nw, int hd)
+        : qb(take(2 * gq * hd, 16)), knew(take(2 * hd, 16)), wmax(take(4 * nw * gq, 4)), flag(take(16, 4)), comb(take(4 * nw * gq * (hd + 4), 8)) {}
+};
+struct AttnKv8Lds : AttnLds { /* attn_kv8_kernel<gq, hd>, ATTN_KV8_NW waves */
+    int comb, qb, knew;              /* as attn_kernel's */
+    int q8, k8n, v8n, stp, flag;     /* [gq][hd] the q heads' codes, [hd] the new K row's, [hd] the new V row's; [gq] q steps, then the new K and V rows'; the merge flag */
+    constexpr AttnKv8Lds(int gq, int hd)
+        : comb(take(8 * ATTN_KV8_NW * gq * (hd + 2), 8)), qb(take(2 * gq * hd, 16)), knew(take(2 * hd, 16)), q8(take(gq * hd, 16)), k8n(take(hd, 16)), v8n(take(hd, 16)),
+          stp(take(4 * (gq + 2), 4)), flag(take(16, 4)) {}
+};
+struct AttnTileLds : AttnLds { /* attn_prefill_kernel<hd, gq, kh, kt> */
+    int ks, vt, half; /* 2 x [kt][hd + AP_KPAD] K tiles and 2 x [kt][hd + AP_VPAD] V tiles of key half 0, bf16; key half 1: the same, `half` bytes on */
+    int ex, ex_rows;  /* kh = 2, after the key walk: the odd half's (O, M, l), ex_rows rows of 256 floats, OVER the tiles from the start of the buffer */
+    constexpr AttnTileLds(int hd, int kh, int kt) : ks(take(2 * 2 * kt * (hd + AP_KPAD), 16)), vt(take(2 * 2 * kt * (hd + AP_VPAD), 16)), half(bytes), ex(0), ex_rows(hd / 2 + 2) {
+        bytes = kh * half;
+        sound = sound && half % 16 == 0 && (kh == 1 || ex + 4 * ex_rows * 256 <= bytes);
+    }
+};
+struct AttnTileKv8Lds : AttnLds { /* attn_prefill_kv8_kernel<hd, gq> */
+    int kt8, vt, kst, vst; /* [KT][hd + KPAD] the K8 tile; [KT][hd + VPAD] the V tile, bf16 bits; [KT] K steps and, right behind them (one store fills both), [KT] V steps */
+    int q8, sqs, qb;       /* [COLS][hd] query codes, [COLS] query steps; prologue only: [COLS][hd] bf16 query heads IN the V tile, which is not staged yet */
+    constexpr AttnTileKv8Lds(int hd)
+        : kt8(take(APK8_KT * (hd + APK8_KPAD), 16)), vt(take(2 * APK8_KT * (hd + APK8_VPAD), 16)), kst(take(4 * APK8_KT, 16)), vst(take(4 * APK8_KT, 16)),
+          q8(take(APK8_COLS * hd, 16)), sqs(take(4 * APK8_COLS, 4)), qb(vt) {
+        sound = sound && qb + 2 * APK8_COLS * hd <= kst;
+    }
+};
 
 // ---- the problem
 enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5 };
@@ -83,6 +128,18 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
     const int GQ = kv_ok ? P.n_head / P.n_kv : 0;
     const bool gq_ok = GQ == 1 || GQ == 2 || GQ == 4 || GQ == 8;
     p.hd = P.hd, p.gq = GQ;
+    // the sliced geometry of the decode kernels (s: the slices, nw waves, n_tok tokens on grid z): the canonical order's query heads dealt to workgroups of
+    // ATTN_CANON_GQ_WG, the counter stride (refused below 1), grid, threads, and the hand-off's scratch; false: refused
+    auto sliced = [&](bool canon, const AttnSlices& s, int nw, int n_tok, bool hand_off) {
+        p.canon = canon, p.gq_split = canon && GQ > ATTN_CANON_GQ_WG ? GQ / ATTN_CANON_GQ_WG : 1;
+        p.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (P.n_kv * p.gq_split);
+        if (p.cnt_stride > ATTN_CNT_STRIDE_MAX) p.cnt_stride = ATTN_CNT_STRIDE_MAX;
+        if (p.cnt_stride < 1) return refuse(KF_INVALID_ARGS), false;
+        p.gq = GQ / p.gq_split, p.nw = nw, p.n_splits = s.n_splits, p.chunk = s.chunk, p.threads = 64 * nw;
+        p.grid[0] = s.n_splits, p.grid[1] = P.n_kv * p.gq_split, p.grid[2] = n_tok;
+        p.scratch = hand_off ? (long long)attn_decode_scratch_bytes(P.n_head, P.hd) : 0;
+        return true;
+    };
     if (P.entry == ATTN_BACKWARD) {
         p.route = ATTN_BWD;
         if (!hd_ok || !kv_ok) return refuse(KF_UNSUPPORTED_DATATYPE);
@@ -94,16 +151,8 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         p.route = ATTN_SLICED_KV8;
         if (!hd_ok || !kv_ok || !gq_ok || P.pos < 0) return refuse(KF_INVALID_ARGS);
         if (P.kv_stride & 15) return refuse(KF_BLAS_UNALIGN);
-        const AttnSlices s = attn_slices(P.pos, P.n_kv, GQ);
-        p.canon = 1, p.gq_split = GQ > ATTN_CANON_GQ_WG ? GQ / ATTN_CANON_GQ_WG : 1;
-        p.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (P.n_kv * p.gq_split);
-        if (p.cnt_stride > ATTN_CNT_STRIDE_MAX) p.cnt_stride = ATTN_CNT_STRIDE_MAX;
-        if (p.cnt_stride < 1) return refuse(KF_INVALID_ARGS);
-        p.gq = GQ / p.gq_split, p.nw = ATTN_KV8_NW, p.n_splits = s.n_splits, p.chunk = s.chunk, p.threads = 64 * ATTN_KV8_NW;
-        p.grid[0] = s.n_splits, p.grid[1] = P.n_kv * p.gq_split, p.grid[2] = 1;
-        // the waves' {O[hd], L, m} doubles; prepared q heads + the new key (bf16); their int8 codes + the new K and V rows' codes; the gq + 2 steps and the flag
-        p.lds = (int)(sizeof(double) * ((size_t)ATTN_KV8_NW * p.gq * (P.hd + 2)) + sizeof(uint16_t) * ((size_t)p.gq * P.hd + P.hd) + ((size_t)p.gq * P.hd + 2 * P.hd) + 4 * (p.gq + 2) + 16);
-        p.scratch = (long long)attn_decode_scratch_bytes(P.n_head, P.hd);
+        if (!sliced(true, attn_slices(P.pos, P.n_kv, GQ), ATTN_KV8_NW, 1, true)) return p;
+        p.lds = AttnKv8Lds(p.gq, P.hd).bytes;
         return p;
     }
     if (P.entry == ATTN_PROMPT_KV8) { /* a token batch against the int8 cache: ONE arithmetic and ONE form for every n_tok >= 1 (P.canon is not read) */
@@ -113,8 +162,7 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         const int TQ = APK8_COLS / GQ;
         p.canon = 1, p.kh = 1, p.kt = APK8_KT, p.threads = 256;
         p.grid[0] = (P.n_tok + TQ - 1) / TQ, p.grid[1] = P.n_kv, p.grid[2] = 1;
-        // the K8 tile, the bf16 V tile (the prologue's bf16 query heads lie in it), the rows' two steps, the query codes and their steps
-        p.lds = APK8_KT * (P.hd + APK8_KPAD) + (int)sizeof(uint16_t) * APK8_KT * (P.hd + APK8_VPAD) + 4 * 2 * APK8_KT + APK8_COLS * P.hd + 4 * APK8_COLS;
+        p.lds = AttnTileKv8Lds(P.hd).bytes;
         return p;
     }
     // the tile kernel: 16-byte q and K / V rows, 8-byte out rows
@@ -128,7 +176,7 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         if ((long)p.grid[0] * P.n_kv * P.n_seq <= ATTN_PAIR_MAX_WGS && P.n_tok >= ATTN_PAIR_MIN_TOK)
             p.route = ATTN_PAIRED, p.grid[0] = ((P.n_tok + TQ / 2 - 1) / (TQ / 2) + 1) / 2; /* half blocks of TQ / 2 tokens, two per workgroup */
         p.kh = p.route == ATTN_PAIRED ? 2 : 1, p.kt = p.kh == 2 ? AP_KT_LONG : AP_KT, p.threads = 256 * p.kh;
-        p.lds = (int)sizeof(uint16_t) * p.kh * (2 * p.kt * (P.hd + 8) + 2 * p.kt * (P.hd + AP_VPAD));
+        p.lds = AttnTileLds(P.hd, p.kh, p.kt).bytes;
         return p;
     }
     // the decode kernel: sliced (one token), or one slice per token (a prompt the tile kernel does not take)
@@ -137,15 +185,8 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
     if (!hd_ok || !kv_ok || !gq_ok) return refuse(KF_INVALID_ARGS);
     const int n_tok = per_token ? P.n_tok : 1;
     const AttnSlices s = attn_slices(P.pos + n_tok - 1, P.n_kv, GQ, per_token);
-    p.canon = P.canon != 0, p.gq_split = p.canon && GQ > ATTN_CANON_GQ_WG ? GQ / ATTN_CANON_GQ_WG : 1;
-    p.cnt_stride = KF_ATTN_CNT_BYTES / 4 / (P.n_kv * p.gq_split);
-    if (p.cnt_stride > ATTN_CNT_STRIDE_MAX) p.cnt_stride = ATTN_CNT_STRIDE_MAX;
-    if (p.cnt_stride < 1) return refuse(KF_INVALID_ARGS);
-    p.gq = GQ / p.gq_split, p.nw = s.nw, p.n_splits = s.n_splits, p.chunk = s.chunk, p.threads = 64 * s.nw;
-    p.grid[0] = s.n_splits, p.grid[1] = P.n_kv * p.gq_split, p.grid[2] = n_tok;
-    const size_t q_lds = sizeof(uint16_t) * ((size_t)p.gq * P.hd + P.hd); /* prepared q heads + the new key */
-    p.lds = (int)(p.canon ? sizeof(double) * ((size_t)s.nw * p.gq * (P.hd + 2)) + q_lds + 16 : q_lds + sizeof(float) * (s.nw * p.gq + 4 + (size_t)s.nw * p.gq * (P.hd + 4)));
-    p.scratch = per_token ? 0 : (long long)attn_decode_scratch_bytes(P.n_head, P.hd);
+    if (!sliced(P.canon != 0, s, s.nw, n_tok, !per_token)) return p;
+    p.lds = p.canon ? AttnCanonLds(p.gq, p.nw, P.hd).bytes : AttnFastLds(p.gq, p.nw, P.hd).bytes;
     return p;
 }
 

@@ -69,17 +69,18 @@ __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefil
     constexpr int NSUB = KT / 32; /* 32-key sub-tiles per staged tile */
     constexpr int NS = HD / 16;   /* MFMA steps over d for S^T */
     constexpr int NDB = HD / 32;  /* 32-row blocks of O^T */
-    constexpr int KS = HD + 8;    /* padded K row, elements */
+    constexpr int KS = HD + AP_KPAD; /* padded K row, elements */
     constexpr int TQ = 128 / GQ;  /* tokens per workgroup */
     constexpr int KCH = KT * HD / 8; /* 16-byte chunks per K (or V) tile */
     constexpr int CPT = KCH / 256;      /* chunks per thread */
     static_assert(KCH % 256 == 0, "tile chunks must divide among 256 threads");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int VS = HD + AP_VPAD; /* V row stride, elements */
-    constexpr int HALF_EL = 2 * KT * KS + 2 * KT * VS; /* one key-half's buffers, elements */
+    constexpr AttnTileLds lds(HD, KH, KT);
+    static_assert(lds.fits(ATTN_TILE_LDS_MAX), "LDS");
     const int kh = KH == 2 ? (int)(threadIdx.x >> 8) : 0; /* which key tiles this wave walks: t = kh, kh + KH, ... */
-    uint16_t* ks = reinterpret_cast<uint16_t*>(smem_raw) + (size_t)kh * HALF_EL;  // 2 x [KT][KS]
-    uint16_t* vt = ks + 2 * KT * KS;                                           // 2 x [KT][VS]
+    uint16_t* ks = reinterpret_cast<uint16_t*>(smem_raw + (size_t)kh * lds.half + lds.ks);  // 2 x [KT][KS]
+    uint16_t* vt = reinterpret_cast<uint16_t*>(smem_raw + (size_t)kh * lds.half + lds.vt);  // 2 x [KT][VS]
 
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -303,8 +304,9 @@ __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefil
     }
 #endif
     if (KH == 2) { /* the odd half hands (O, M, l) over, register-major rows of 256 lanes; the even half merges and finishes */
-        float* ex = reinterpret_cast<float*>(smem_raw);
-        constexpr int NR = NDB * 16;
+        float* ex = reinterpret_cast<float*>(smem_raw + lds.ex); /* over the tiles: the walk is done */
+        constexpr int NR = lds.ex_rows - 2; /* the rows of O; M and l behind them */
+        static_assert(NR == NDB * 16, "the hand-over holds every row of O");
         if (kh == 1) {
             const int et = PAIR ? tid ^ 128 : tid; /* the even half's thread that holds the same column (paired form: its wave number differs in bit 1) */
 #pragma unroll
@@ -347,7 +349,6 @@ template <int I, int HD = I / APF_HD ? 128 : 64, int GQ = 1 << (I / APF_GQ % 4),
 constexpr ApKernel ap_form() {
     static_assert(ap_form_index(HD, GQ, KH) == I, "ap_form_index");
     constexpr int KT = KH == 2 ? AP_KT_LONG : AP_KT;
-    static_assert(sizeof(uint16_t) * KH * (2 * KT * (HD + 8) + 2 * KT * (HD + AP_VPAD)) <= 160 * 1024, "LDS");
     return attn_prefill_kernel<HD, GQ, KH, KT>;
 }
 template <int... I>
@@ -360,7 +361,7 @@ int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* 
     static constexpr std::array<ApKernel, AP_FORMS> forms = ap_forms(std::make_integer_sequence<int, AP_FORMS>());
     static bool lds_set[AP_FORMS] = {};
     const int f = ap_form_index(p.hd, p.gq, p.kh);
-    if (!lds_set[f] && p.lds > 64 * 1024) {
+    if (!lds_set[f] && p.lds > ATTN_LDS_MAX) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(forms[f]), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds) != hipSuccess) return KF_HIP_CHECK;
         lds_set[f] = true;
     }

@@ -46,14 +46,15 @@ __global__ void __launch_bounds__(256) attn_prefill_kv8_kernel(const AttnPrefill
     constexpr int CPT = KT * CPR / 256;   /* chunks per thread and tile */
     static_assert(KT == 64 && COLS == 64 && KT * CPR % 256 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    int8_t* kt8 = reinterpret_cast<int8_t*>(smem_raw);                    // [KT][KSB]
-    uint16_t* vt = reinterpret_cast<uint16_t*>(smem_raw + KT * KSB);      // [KT][VSE] bf16 bits
-    float* kst = reinterpret_cast<float*>(vt + KT * VSE);                 // [KT] K steps, [KT] V steps
-    float* vst = kst + KT;
-    int8_t* q8 = reinterpret_cast<int8_t*>(vst + KT);                     // [COLS][HD] query codes
-    float* sqs = reinterpret_cast<float*>(q8 + COLS * HD);                // [COLS] query steps
-    uint16_t* qb = vt;                                                    // prologue only: [COLS][HD] bf16 query heads (the V tile is not staged yet)
-    static_assert(COLS * HD <= KT * VSE, "the bf16 query heads fit the V tile");
+    constexpr AttnTileKv8Lds lds(HD);
+    static_assert(lds.fits(), "LDS");
+    int8_t* kt8 = reinterpret_cast<int8_t*>(smem_raw + lds.kt8);          // [KT][KSB]
+    uint16_t* vt = reinterpret_cast<uint16_t*>(smem_raw + lds.vt);        // [KT][VSE] bf16 bits
+    float* kst = reinterpret_cast<float*>(smem_raw + lds.kst);            // [KT] K steps, [KT] V steps behind them
+    float* vst = reinterpret_cast<float*>(smem_raw + lds.vst);
+    int8_t* q8 = reinterpret_cast<int8_t*>(smem_raw + lds.q8);            // [COLS][HD] query codes
+    float* sqs = reinterpret_cast<float*>(smem_raw + lds.sqs);            // [COLS] query steps
+    uint16_t* qb = reinterpret_cast<uint16_t*>(smem_raw + lds.qb);        // prologue only: [COLS][HD] bf16 query heads, in the V tile
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, h = lane >> 4;
     const int kvh = blockIdx.y, blk = (int)gridDim.x - 1 - (int)blockIdx.x; /* the blocks with the most keys first */

@@ -18,6 +18,7 @@ import ctypes as C
 
 import numpy as np
 
+import attn_plan_mirror as APM
 from oracle import oracle as O
 
 BOUND = 256.0   # every integer of magnitude <= 256 is a bf16 value: the bf16 store of an exact result within the bound is that result
@@ -200,26 +201,14 @@ def seams(p, K):
 
 
 # ---- the plan behind the attention entries (kf_attn_plan.h attn_plan through kfdbg_attn_plan): the forward's tile form or its paired form
-ATTN_DECODE, ATTN_PROMPT, ATTN_BATCH = 0, 1, 2   # AttnProblem::entry: kf_attn_decode, kf_attn_prefill, kf_attn_prefill_batch(_strided)
-ATTN_SLICED, ATTN_PER_TOKEN, ATTN_TILE, ATTN_PAIRED = 0, 1, 2, 3   # AttnPlan::route
-
-
-class _AttnProblem(C.Structure):
-    _fields_ = ([(f, C.c_int) for f in ("entry", "n_head", "n_kv", "hd", "pos", "n_tok", "n_seq", "canon", "al")]
-                + [(f, C.c_longlong) for f in ("q_stride", "out_stride", "kv_stride")])
-
-
-class _AttnPlan(C.Structure):
-    _fields_ = ([(f, C.c_int) for f in ("status", "route", "canon", "gq", "nw", "hd", "kh", "kt", "gq_split", "n_splits", "chunk", "cnt_stride")]
-                + [("grid", C.c_int * 3), ("grid_kv", C.c_int * 3), ("threads", C.c_int), ("lds", C.c_int), ("scratch", C.c_longlong)])
+ATTN_DECODE, ATTN_PROMPT, ATTN_BATCH = APM.DECODE, APM.PROMPT, APM.BATCH   # AttnProblem::entry: kf_attn_decode, kf_attn_prefill, kf_attn_prefill_batch(_strided)
+ATTN_SLICED, ATTN_PER_TOKEN, ATTN_TILE, ATTN_PAIRED = APM.SLICED, APM.PER_TOKEN, APM.TILE, APM.PAIRED   # AttnPlan::route
 
 
 def attn_plan(hip, entry, nh, nkv, hd, n, n_seq=1, pos0=0, canon=0, q_stride=None):
     """the plan of a forward launch with aligned rows (dense unless q_stride is given)"""
-    hip.kfdbg_attn_plan.argtypes = [C.POINTER(_AttnProblem), C.POINTER(_AttnPlan)]
-    out = _AttnPlan()
-    P = _AttnProblem(entry, nh, nkv, hd, pos0, n, n_seq, canon, 3, nh * hd if q_stride is None else q_stride, 0, nkv * hd)
-    assert hip.kfdbg_attn_plan(C.byref(P), C.byref(out)) == 0 and out.status == 0
+    out = APM.plan(hip, entry, nh, nkv, hd, pos0, n, n_seq, canon, q_stride=q_stride)
+    assert out.status == 0
     return out
 
 

@@ -4,25 +4,15 @@ backward: the route, the kernel form, the slices, the counter stride, grid, thre
 value is what the launchers chose before the rule (attn_launch with attn_splits and the KF_ATTN_GO ladder, attn_prefill_mfma_launch with ap_launch_gq, and
 kf_attn_prefill's try-the-tile-kernel-then-fall-back) for the same inputs, at the knobs' shipped values."""
 import ctypes as C
+import functools
 
 import pytest
 
+import attn_plan_mirror as A
+from attn_plan_mirror import BACKWARD, BATCH, BWD, DECODE, OUT_AL, PAIRED, PER_TOKEN, PROMPT, Q_AL, SLICED, TILE
 from koifish_amd import lib as L
 
 OK, INVALID_ARGS, UNSUPPORTED = 0, -20, -1000
-DECODE, PROMPT, BATCH, BACKWARD = range(4)          # AttnProblem::entry
-SLICED, PER_TOKEN, TILE, PAIRED, BWD = range(5)     # AttnPlan::route
-Q_AL, OUT_AL = 1, 2
-
-
-class Problem(C.Structure):   # kf::AttnProblem
-    _fields_ = ([(f, C.c_int) for f in ("entry", "n_head", "n_kv", "hd", "pos", "n_tok", "n_seq", "canon", "al")]
-                + [(f, C.c_longlong) for f in ("q_stride", "out_stride", "kv_stride")])
-
-
-class Plan(C.Structure):      # kf::AttnPlan
-    _fields_ = ([(f, C.c_int) for f in ("status", "route", "canon", "gq", "nw", "hd", "kh", "kt", "gq_split", "n_splits", "chunk", "cnt_stride")]
-                + [("grid", C.c_int * 3), ("grid_kv", C.c_int * 3), ("threads", C.c_int), ("lds", C.c_int), ("scratch", C.c_longlong)])
 
 
 @pytest.fixture(scope="module")
@@ -32,15 +22,7 @@ def hip():
 
 @pytest.fixture(scope="module")
 def plan(hip):
-    hip.kfdbg_attn_plan.argtypes = [C.POINTER(Problem), C.POINTER(Plan)]
-
-    def f(entry, n_head, n_kv, hd=128, pos=0, n_tok=1, n_seq=1, canon=0, al=Q_AL | OUT_AL, q_stride=None, out_stride=0, kv_stride=None):
-        q_stride = n_head * hd if q_stride is None else q_stride
-        kv_stride = n_kv * hd if kv_stride is None else kv_stride
-        out = Plan()
-        assert hip.kfdbg_attn_plan(C.byref(Problem(entry, n_head, n_kv, hd, pos, n_tok, n_seq, canon, al, q_stride, out_stride, kv_stride)), C.byref(out)) == 0
-        return out
-    return f
+    return functools.partial(A.plan, hip)
 
 
 def dec(p):

@@ -9,6 +9,7 @@ import pytest
 import exact_inputs as E
 import kv8_restate as R
 from a8_restate import quant_rows
+from attn_plan_mirror import kv8_plan
 from koifish_amd import lib as L
 from oracle import oracle as O
 
@@ -122,12 +123,6 @@ def test_accuracy_against_the_unquantised_attention():
                 worst = max(worst, err)
     print("largest: %.5f (recorded: %.5f)" % (worst, MEASURED_MAX_ERR))
     assert worst <= 2 * MEASURED_MAX_ERR
-
-
-def kv8_plan(hip, nh, nkv, hd, pos, kv_stride=None):
-    out = E._AttnPlan()
-    assert hip.kfdbg_kv8_plan(nh, nkv, hd, pos, nkv * hd if kv_stride is None else kv_stride, C.byref(out)) == 0
-    return out
 
 
 def test_plan_is_pinned(hip):

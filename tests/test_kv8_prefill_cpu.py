@@ -17,11 +17,10 @@ None of the constants comes from a run.
 
 AGAINST THE DECODE FORM at the same position the only differences are gb = bf16_rn(g) in place of g (|gb - g| <= 2^-8 |g|, so the exact quotients differ by at most
 2^-8 A / L to first order) and the two stores: decode's fl32 + bf16 store of its exact quotient, and this form's bf16 store -- 2^-8 of each value."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import attn_plan_mirror as APM
 import exact_inputs as E
 import kv8_prefill_restate as P
 import kv8_restate as R
@@ -148,14 +147,10 @@ def test_plan_and_status():
     """the ATTN_PROMPT_KV8 entry of kf::attn_plan: one form for every n_tok, 64 / gq tokens per workgroup, no scratch; the refusals and kf_attn_prefill_kv8_status"""
     from koifish_amd import lib as L
     hip, _ = L.load()
-    hip.kfdbg_attn_plan.argtypes = [C.POINTER(E._AttnProblem), C.POINTER(E._AttnPlan)]
-    PROMPT_KV8, TILE_KV8 = 5, 6
+    TILE_KV8 = APM.TILE_KV8
 
     def plan(nh, nkv, hd, pos0, n, al=3, q_stride=None, kv_stride=None):
-        out = E._AttnPlan()
-        pr = E._AttnProblem(PROMPT_KV8, nh, nkv, hd, pos0, n, 1, 1, al, nh * hd if q_stride is None else q_stride, 0, nkv * hd if kv_stride is None else kv_stride)
-        assert hip.kfdbg_attn_plan(C.byref(pr), C.byref(out)) == 0
-        return out
+        return APM.plan(hip, APM.PROMPT_KV8, nh, nkv, hd, pos0, n, al=al, q_stride=q_stride, kv_stride=kv_stride)
 
     for nh, nkv in E.HEADS:
         for hd in E.HEAD_DIMS:
