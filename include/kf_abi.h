@@ -286,6 +286,45 @@ int kf_set_state(kf_ctx* ctx, int32_t* d_state, int token, int pos);
 /* embed lookup driven by device state: token = (d_forced && d_forced[pos] >= 0) ? d_forced[pos] : d_state[0] */
 int kf_embed_state(kf_ctx* ctx, const kf_weight* w, const int32_t* d_state, const int32_t* d_forced, kf_bf16* out);
 
+/* ---- row siblings of the fused mat-vec entries: n_rows = 1 .. 8 activation rows against ONE pass over the weights (no counterpart in the reference).  The use is
+ * the verify pass of speculative decoding: a token and up to seven drafted continuations of one sequence, whose rows are consecutive positions pos0 .. pos0 +
+ * n_rows - 1.  Row r is x + r * x_stride (elements; a multiple of 8); the pass is eager and the host knows the position, so there is no d_pos form.
+ * In the canonical order (kf_set_canonical 1, the default) row r carries EVERY BIT of the one-token entry called on row r at position pos0 + r -- kf_linear
+ * with nTok = 1, kf_norm_linear, kf_norm_gateup_swiglu, kf_norm_lm_head: the lanes per weight row come from the same rule with the same arguments, and with them
+ * the per-lane chains, the lane tree, the RMSNorm sums and the epilogue arithmetic.
+ * Sharing: for 4-bit group weights (PackedQ, qBias 0 or 8) and bf16 weights in the canonical order, from two rows up, every 16-byte weight block is loaded and
+ * dequantised once and multiplied into one accumulator pair per row; rows whose activations do not fit 80 KiB of LDS together are cut into panels of equal size, one
+ * weight pass per panel.  Everything else -- the v_dot2c order, f8 / 2-bit / 1-bit / row-codebook weights, one row, rows longer than 40 832 elements -- runs the
+ * one-token launch row by row inside the same entry: the same results, no sharing.  kf_rows_route_counts says how many rows took which route since kf_init.
+ * AutoAWQ-layout weights, sparse forms, bias, alpha / beta: not served (KF_UNSUPPORTED_DATATYPE for AWQ as the one-token entries; the others have no argument).
+ * Refusals are the one-token entries' own, plus KF_INVALID_ARGS for n_rows outside 1 .. 8 and KF_BLAS_UNALIGN for an x_stride that is not a multiple of 8. */
+/* y[r] = W . x[r] (+ residual[r]); row r of y / residual at r * y_stride / r * residual_stride elements; `residual` MAY alias `y` (with equal strides) */
+int kf_linear_rows(kf_ctx* ctx, const kf_weight* w, const kf_bf16* x, int64_t x_stride, kf_bf16* y, int64_t y_stride, int n_rows, uint32_t epilogue,
+                   const kf_bf16* residual, int64_t residual_stride);
+/* [RMSNorm per row] -> up to 3 projections; row r of projection i goes to y[i] + r * y_row_stride[i] + (pos0 + r) * y_pos_stride[i]: K.out / V.out land in the
+ * cache rows pos0 .. pos0 + n_rows - 1 with y_row_stride 0 and y_pos_stride = the cache's row stride (y_pos_stride NULL: all zero) */
+int kf_norm_linear_rows(kf_ctx* ctx, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w_or_null, float eps, int n_w, const kf_weight* const* w,
+                        kf_bf16* const* y, const int64_t* y_row_stride, const int64_t* y_pos_stride_or_null, int pos0, int n_rows);
+/* [RMSNorm per row] -> gate & up -> SwiGLU -> act[r] at r * act_stride */
+int kf_norm_gateup_swiglu_rows(kf_ctx* ctx, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w_or_null, float eps, const kf_weight* gate, const kf_weight* up,
+                               kf_bf16* act, int64_t act_stride, int n_rows);
+/* [final RMSNorm per row] + LM head + greedy pick per row: d_top1[r] = the first maximum of row r's bf16 logits (ties to the lower id), always; the logits
+ * themselves to logits + r * logits_stride when logits != NULL.  No decode-state update.  scratch: kf_head_rows_scratch_bytes(w) bytes, 16-byte aligned. */
+int kf_norm_lm_head_rows(kf_ctx* ctx, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w_or_null, float eps, const kf_weight* w, kf_bf16* logits_or_null,
+                         int64_t logits_stride, int32_t* d_top1, int n_rows, void* scratch);
+size_t kf_head_rows_scratch_bytes(const kf_weight* w);
+/* kf_attn_decode for n_rows = 1 .. 8 consecutive queries of one sequence in ONE launch: query r (prepared: normed + roped, at q + r * row_stride) sits at position
+ * pos0 + r and attends to keys 0 .. pos0 + r; out row r at out + r * row_stride.  The K / V rows of the whole batch, positions pos0 .. pos0 + n_rows - 1, must be in
+ * the cache before the call (kf_norm_linear_rows into the cache rows, then kf_qknorm_rope_batch on the K rows in place): query r reads the keys of rows 0 .. r.
+ * Canonical order: each row equals kf_attn_decode at its position bit for bit -- every query cuts its keys into kf_attn_decode's slices at its own position and owns
+ * its arrival counters and partials.  The v_dot2c order: the one-token launch per row.  scratch: kf_attn_rows_scratch_bytes(n_head, hd, n_rows) bytes, 16-byte
+ * aligned, zero-filled ONCE by the caller (the counters return to zero). */
+int kf_attn_decode_rows(kf_ctx* ctx, const kf_bf16* q, int64_t row_stride, const kf_bf16* kcache, const kf_bf16* vcache, kf_bf16* out, int pos0, int n_rows,
+                        int n_head, int n_kv, int hd, int kv_stride, void* scratch);
+size_t kf_attn_rows_scratch_bytes(int n_head, int hd, int n_rows);
+/* out2[0]: activation rows served with the shared unpack, out2[1]: rows served by one-token launches, by the four entries above since kf_init */
+int kf_rows_route_counts(kf_ctx* ctx, int64_t* out2);
+
 /* GeneratOnPrompt::Sample, non-greedy branch (GoPT.cpp:614-630; LogitsInfo::TopK / UpdateLogits / TopP / Qu_FlipCoin, GoPT.cpp:632-790):
  * picks the next token from bf16 logits[n] on the device -- candidate set exactly as TOPK_heap::Select builds it (indices
  * 0..k-2 plus the first maximum over i >= k-1), softmax with temperature, top-p cut, xorshift64* coin.  d_rng_state: one uint64 in device

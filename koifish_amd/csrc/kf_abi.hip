@@ -15,6 +15,7 @@
 #include "kf_attn_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
+#include "kf_gemv_rows_plan.h"
 #include "kf_score_plan.h"
 #include "kf_gama_plan.h"
 #include "kf_lora_plan.h"
@@ -29,6 +30,7 @@ struct kf_ctx {
     int* amax_idx;
     double* muon_part; /* per-workgroup partial sums of squares of kf_muon_momentum / kf_muon_apply (those entries take no scratch) */
     int canonical;    /* 1: the decode kernels sum in the canonical order of oracle/kf_oracle.c sections 4c / 6 (bit-exact against the oracle; the default); 0: v_dot2c / fp32 forms */
+    long long rows_shared, rows_single; /* activation rows the kf_*_rows entries served with the shared unpack / with one-token launches (kf_rows_route_counts) */
     void* scratch;    /* caller-owned workspace of kf_linear (kf_set_scratch): AWQ slice partials, or a weight dequantised to bf16 */
     size_t scratch_bytes;
     // resident GetDataX copies for token batches (kf_set_dequant_arena): caller-owned memory, filled on first use, keyed by the data pointers of the matrices a route
@@ -638,6 +640,125 @@ int kf_norm_gateup_swiglu(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, fl
     RET(kf::gemv_launch(c->stream, L));
 }
 
+// ---- the row siblings of the fused decode entries: R = 1 .. 8 activation rows against one pass over the weights (kf_gemv_rows_plan.h decides; kf_gemv_rows.hip).
+// A plan that does not share (the v_dot2c order, another storage, one row) is carried out here as the one-token launch row by row: the same bits either way
+struct RowsCall {
+    int n_w, mode, n_rows;
+    const kf_weight* w[3];
+    kf_bf16* y[3];
+    int64_t y_row_stride[3], y_pos_stride[3];
+    const kf_bf16 *x, *norm_w, *residual;
+    int64_t x_stride, res_stride;
+    float eps;
+    int pos0;
+    float* amax_val; /* GEMV_ARGMAX: [n_rows][KF_MAX_ARGMAX_PARTIALS] */
+    int* amax_idx;
+    int32_t* d_top1;
+    kf_bf16* logits_row; /* GEMV_ARGMAX row by row without a logits matrix: one row to write them to */
+};
+static kf::GemvRowsLaunch rows_launch_of(const RowsCall& q) {
+    kf::GemvRowsLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.n = q.n_w, L.mode = q.mode, L.n_rows = q.n_rows;
+    for (int j = 0; j < q.n_w; j++) L.w[j] = q.w[j], L.args.job[j].y = q.y[j], L.args.job[j].y_pos_stride = q.y_pos_stride[j], L.args.y_row_stride[j] = q.y_row_stride[j];
+    L.args.x = q.x, L.args.x_stride = q.x_stride, L.args.norm_w = q.norm_w, L.args.eps = q.eps;
+    L.args.residual = q.residual, L.args.res_stride = q.res_stride, L.args.pos0 = q.pos0;
+    L.args.amax_val = q.amax_val, L.args.amax_idx = q.amax_idx;
+    return L;
+}
+static int rows_run(kf_ctx* c, const RowsCall& q, const char* who) {
+    if (q.n_rows < 1 || q.n_rows > kf::GEMV_ROWS_MAX) return fail(KF_INVALID_ARGS, "%s: n_rows=%d outside 1 .. %d", who, q.n_rows, kf::GEMV_ROWS_MAX);
+    if (!q.x || !al16(q.x) || (q.x_stride & 7) || (q.norm_w && !al16(q.norm_w))) return fail(KF_BLAS_UNALIGN, "%s: x / norm_w null or not 16-byte aligned, or x_stride not a multiple of 8", who);
+    for (int j = 0; j < q.n_w; j++) {
+        const int r = check_weight(q.w[j], who);
+        if (r) return r;
+    }
+    kf::GemvRowsLaunch L = rows_launch_of(q);
+    const kf::GemvRowsPlan p = kf::gemv_rows_plan(kf::gemv_rows_problem(L, c->canonical));
+    if (p.status) return fail(p.status, "%s: refused with %d", who, p.status);
+    c->rows_shared += p.shared ? q.n_rows : 0, c->rows_single += p.shared ? 0 : q.n_rows;
+    if (p.shared) {
+        int rc = kf::gemv_rows_launch(c->stream, L, p);
+        if (rc == KF_OK && q.mode == kf::GEMV_ARGMAX) {
+            kf::argmax_rows_finish_launch(c->stream, q.amax_val, q.amax_idx, p.grid, q.n_rows, q.d_top1);
+            rc = hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+        }
+        return rc ? fail(rc, "%s: launch failed with %d", who, rc) : KF_OK;
+    }
+    kf::GemvLaunch G;
+    init_args(c, G);
+    G.n = q.n_w, G.mode = q.mode;
+    for (int j = 0; j < q.n_w; j++) G.w[j] = q.w[j];
+    G.args.norm_w = q.norm_w, G.args.eps = q.eps;
+    const kf::GemvPlan g = kf::gemv_plan(kf::gemv_problem(G));
+    for (int r = 0; r < q.n_rows; r++) {
+        G.args.x = q.x + (size_t)r * q.x_stride, G.args.pos = q.pos0 + r;
+        G.args.residual = q.residual ? q.residual + (size_t)r * q.res_stride : nullptr;
+        for (int j = 0; j < q.n_w; j++) G.args.job[j].y = q.y[j] ? q.y[j] + (size_t)r * q.y_row_stride[j] : q.logits_row, G.args.job[j].y_pos_stride = q.y_pos_stride[j];
+        G.args.amax_val = q.amax_val, G.args.amax_idx = q.amax_idx;
+        int rc = kf::gemv_launch(c->stream, G, g);
+        if (rc == KF_OK && q.mode == kf::GEMV_ARGMAX) {
+            kf::argmax_finish_launch(c->stream, q.amax_val, q.amax_idx, G.blocks, q.d_top1 + r, nullptr, nullptr);
+            rc = hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+        }
+        if (rc != KF_OK) return fail(rc, "%s: row %d failed with %d", who, r, rc);
+    }
+    return KF_OK;
+}
+int kf_linear_rows(kf_ctx* c, const kf_weight* w, const kf_bf16* x, int64_t x_stride, kf_bf16* y, int64_t y_stride, int n_rows, uint32_t epilogue,
+                   const kf_bf16* residual, int64_t residual_stride) {
+    CHKCTX(c);
+    if (!y) return fail(KF_INVALID_ARGS, "kf_linear_rows: y null");
+    if ((epilogue & KF_EPI_RESIDUAL) && !residual) return fail(KF_INVALID_ARGS, "kf_linear_rows: residual epilogue without residual");
+    RowsCall q = {};
+    q.n_w = 1, q.mode = kf::GEMV_PLAIN, q.n_rows = n_rows, q.w[0] = w, q.y[0] = y, q.y_row_stride[0] = y_stride;
+    q.x = x, q.x_stride = x_stride;
+    if (epilogue & KF_EPI_RESIDUAL) q.residual = residual, q.res_stride = residual_stride;
+    return rows_run(c, q, "kf_linear_rows");
+}
+int kf_norm_linear_rows(kf_ctx* c, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w, float eps, int n_w, const kf_weight* const* w, kf_bf16* const* y,
+                        const int64_t* y_row_stride, const int64_t* y_pos_stride, int pos0, int n_rows) {
+    CHKCTX(c);
+    if (n_w < 1 || n_w > 3 || !w || !y || !y_row_stride || pos0 < 0) return fail(KF_INVALID_ARGS, "kf_norm_linear_rows: n_w=%d, pos0=%d, or w / y / y_row_stride null", n_w, pos0);
+    RowsCall q = {};
+    q.n_w = n_w, q.mode = kf::GEMV_PLAIN, q.n_rows = n_rows;
+    for (int i = 0; i < n_w; i++) {
+        if (!y[i]) return fail(KF_INVALID_ARGS, "kf_norm_linear_rows: y[%d] null", i);
+        q.w[i] = w[i], q.y[i] = y[i], q.y_row_stride[i] = y_row_stride[i], q.y_pos_stride[i] = y_pos_stride ? y_pos_stride[i] : 0;
+    }
+    q.x = x, q.x_stride = x_stride, q.norm_w = norm_w, q.eps = eps, q.pos0 = pos0;
+    return rows_run(c, q, "kf_norm_linear_rows");
+}
+int kf_norm_gateup_swiglu_rows(kf_ctx* c, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w, float eps, const kf_weight* gate, const kf_weight* up, kf_bf16* act,
+                               int64_t act_stride, int n_rows) {
+    CHKCTX(c);
+    if (!act) return fail(KF_INVALID_ARGS, "kf_norm_gateup_swiglu_rows: act null");
+    RowsCall q = {};
+    q.n_w = 2, q.mode = kf::GEMV_PAIRED, q.n_rows = n_rows, q.w[0] = gate, q.w[1] = up, q.y[0] = act, q.y_row_stride[0] = act_stride;
+    q.x = x, q.x_stride = x_stride, q.norm_w = norm_w, q.eps = eps;
+    return rows_run(c, q, "kf_norm_gateup_swiglu_rows");
+}
+size_t kf_head_rows_scratch_bytes(const kf_weight* w) {
+    return w ? (size_t)kf::GEMV_ROWS_MAX * kf_head_scratch_bytes() + (((size_t)w->ne0 * 2 + 15) & ~(size_t)15) : 0;
+}
+int kf_norm_lm_head_rows(kf_ctx* c, const kf_bf16* x, int64_t x_stride, const kf_bf16* norm_w, float eps, const kf_weight* w, kf_bf16* logits, int64_t logits_stride,
+                         int32_t* d_top1, int n_rows, void* scratch) {
+    CHKCTX(c);
+    if (!d_top1 || !scratch || !al16(scratch)) return fail(KF_INVALID_ARGS, "kf_norm_lm_head_rows: top1 / scratch null, or scratch not 16-byte aligned");
+    RowsCall q = {};
+    q.n_w = 1, q.mode = kf::GEMV_ARGMAX, q.n_rows = n_rows, q.w[0] = w, q.y[0] = logits, q.y_row_stride[0] = logits_stride;
+    q.x = x, q.x_stride = x_stride, q.norm_w = norm_w, q.eps = eps;
+    const size_t parts = (size_t)kf::GEMV_ROWS_MAX * kf::KF_MAX_ARGMAX_PARTIALS;
+    q.amax_val = (float*)scratch, q.amax_idx = (int*)(q.amax_val + parts), q.logits_row = (kf_bf16*)(q.amax_idx + parts), q.d_top1 = d_top1;
+    return rows_run(c, q, "kf_norm_lm_head_rows");
+}
+int kf_rows_route_counts(kf_ctx* c, int64_t* out2) {
+    CHKCTX(c);
+    if (!out2) return fail(KF_INVALID_ARGS, "kf_rows_route_counts: out null");
+    out2[0] = c->rows_shared, out2[1] = c->rows_single;
+    return KF_OK;
+}
+
 // ---- sparse forward (hot rows)
 int kf_hot_rows(kf_ctx* c, const int32_t* d_hot, int n, int32_t* d_rows, int32_t* d_count) {
     CHKCTX(c);
@@ -732,6 +853,28 @@ int kf_attn_decode(kf_ctx* c, const kf_bf16* q, const kf_bf16* kc, const kf_bf16
     if (!al16(kc) || !al16(vc) || (kv_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_decode: cache not 16-byte aligned");
     kf::AttnArgs a = attn_args(c, q, const_cast<kf_bf16*>(kc), vc, out, pos, d_pos, n_head, n_kv, hd, kv_stride, scratch);
     RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q, out, 0, 0, 0))));
+}
+
+// R consecutive queries of one sequence in one launch (the ATTN_VERIFY entry of kf::attn_plan); the v_dot2c order: the one-token launch per row on row 0's scratch
+size_t kf_attn_rows_scratch_bytes(int n_head, int hd, int n_rows) { return n_rows < 1 ? 0 : (size_t)n_rows * kf::attn_decode_scratch_bytes(n_head, hd); }
+int kf_attn_decode_rows(kf_ctx* c, const kf_bf16* q, int64_t row_stride, const kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, int pos0, int n_rows, int n_head, int n_kv,
+                        int hd, int kv_stride, void* scratch) {
+    CHKCTX(c);
+    if (!q || !kc || !vc || !out || !scratch || pos0 < 0) return fail(KF_INVALID_ARGS, "kf_attn_decode_rows: null pointer or pos0 < 0");
+    if (n_rows < 1 || n_rows > kf::ATTN_VERIFY_MAX) return fail(KF_INVALID_ARGS, "kf_attn_decode_rows: n_rows=%d outside 1 .. %d", n_rows, kf::ATTN_VERIFY_MAX);
+    if (!al16(kc) || !al16(vc) || (kv_stride % 8) || !al16(scratch)) return fail(KF_BLAS_UNALIGN, "kf_attn_decode_rows: cache / scratch not 16-byte aligned");
+    if (row_stride < (int64_t)n_head * hd) return fail(KF_INVALID_ARGS, "kf_attn_decode_rows: row_stride below n_head * hd");
+    if (!c->canonical) {
+        for (int r = 0; r < n_rows; r++) {
+            kf::AttnArgs a = attn_args(c, q + (size_t)r * row_stride, const_cast<kf_bf16*>(kc), vc, out + (size_t)r * row_stride, pos0 + r, nullptr, n_head, n_kv, hd, kv_stride, scratch);
+            const int rc = kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos0 + r, 1, 1, q, out, 0, 0, 0)));
+            if (rc != KF_OK) return fail(rc, "kf_attn_decode_rows: row %d failed with %d", r, rc);
+        }
+        return KF_OK;
+    }
+    kf::AttnArgs a = attn_args(c, q, const_cast<kf_bf16*>(kc), vc, out, pos0, nullptr, n_head, n_kv, hd, kv_stride, scratch);
+    a.q_stride = row_stride;
+    RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_VERIFY, c, n_head, n_kv, hd, pos0, n_rows, 1, q, out, row_stride, 0, kv_stride)), true));
 }
 
 int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16* kc, const kf_bf16* vc, kf_bf16* out, const kf_bf16* wq, const kf_bf16* wk,
@@ -1874,6 +2017,12 @@ int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
 int kfdbg_gemv_plan(const kf::GemvProblem* P, kf::GemvPlan* out) {
     if (!P || !out) return -1;
     *out = kf::gemv_plan(*P);
+    return 0;
+}
+// the plan kf::gemv_rows_plan makes for R activation rows over one weight pass (no HIP call): tests/test_gemv_rows_plan_cpu.py
+int kfdbg_gemv_rows_plan(const kf::GemvRowsProblem* P, kf::GemvRowsPlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::gemv_rows_plan(*P);
     return 0;
 }
 // the plan kf::attn_plan makes for an attention problem (no HIP call): tests/test_attn_plan_cpu.py

@@ -28,7 +28,11 @@
 
 namespace kf {
 
-template <int GQ, int NW, int HD>
+// ROWS (kf_attn_decode_rows: the verify pass of speculative decoding, R consecutive queries of one sequence on grid z): query z sits at position a.pos + z and
+// attends to keys 0 .. a.pos + z.  Every z cuts its keys by attn_slices at its OWN position -- the slices kf_attn_decode would take there; the grid's x is the last
+// row's count, workgroups past a row's own count leave at once -- and owns its arrival counters and partials: row z's scratch lies z * attn_decode_scratch_bytes
+// behind row 0's.  The waves per workgroup are the launch's (the last row's): the canonical order does not depend on them.
+template <int GQ, int NW, int HD, bool ROWS = false>
 __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     using Slice = AttnSlice<GQ, NW, HD, 8>; /* the shell (kf_attn_common.h): 8 dims of a key per lane */
@@ -42,9 +46,15 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
     uint16_t* knew = reinterpret_cast<uint16_t*>(smem_raw + lds.knew);
     int* flag = reinterpret_cast<int*>(smem_raw + lds.flag);
 
-    const Slice sl(a.gq_split, a.chunk);
     // token batch (prefill): blockIdx.z = token, one slice per kv-head, position pos0 + token, q / out rows q_stride apart
-    const int pos_l = a.pos + (int)blockIdx.z, nsp = a.n_splits;
+    const int pos_l = a.pos + (int)blockIdx.z;
+    int nsp = a.n_splits, chunk = a.chunk;
+    if constexpr (ROWS) {
+        const AttnSlices s = attn_slices(pos_l, a.n_kv, GQ * a.gq_split);
+        nsp = s.n_splits, chunk = s.chunk;
+        if ((int)blockIdx.x >= nsp) return; /* workgroup-uniform */
+    }
+    const Slice sl(a.gq_split, chunk);
     const uint16_t* const qsrc = a.q + (size_t)blockIdx.z * a.q_stride;
     uint16_t* const odst = a.out + (size_t)blockIdx.z * a.q_stride;
     const int h0 = sl.h0(), grp = lane >> lpk_log2, d0 = (lane & (LPK - 1)) * 8, tstart = sl.tstart(wave, grp);
@@ -78,7 +88,8 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
     const HeadRaw kraw = load_head(has_new ? a.k_raw + (size_t)sl.kvh * hd : qsrc, a.wk_norm, hd);
 
     const auto [pos, t1, empty] = sl.at(a.d_pos, pos_l);
-    double* const part = reinterpret_cast<double*>(a.part); /* [n_head][n_splits][PS] doubles */
+    const size_t row_scratch = ROWS ? (size_t)blockIdx.z * attn_decode_scratch_bytes(a.n_head, HD) : 0; /* bytes from row 0's counters / partials to this row's */
+    double* const part = reinterpret_cast<double*>(a.part) + row_scratch / sizeof(double); /* [n_head][n_splits][PS] doubles */
 
     if (!empty) {
         // ---- prologue: q heads of this group, and the new key when it lies in this slice
@@ -125,7 +136,7 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnArgs a) {
     }
     if (nsp == 1) return;
     // ---- arrival; the last workgroup of this kv-head merges (kf_attn_common.h)
-    canon_arrive_and_merge<GQ, NW, HD>(part, a.counters + (int)blockIdx.y * a.cnt_stride, flag, odst, h0, nsp); /* per (kv-head, part): its slices' workgroups meet here */
+    canon_arrive_and_merge<GQ, NW, HD>(part, a.counters + row_scratch / sizeof(int) + (int)blockIdx.y * a.cnt_stride, flag, odst, h0, nsp); /* per (kv-head, part): its slices' workgroups meet here */
 }
 
 // ---- the fp32 form of rounds 1-2 (kf_set_canonical(ctx, 0), the default): scores by v_dot2c_f32_bf16, exp by v_exp_f32(x * log2 e), a workgroup-wide running
@@ -402,10 +413,23 @@ constexpr std::array<AttnKernel, ATTN_FORMS> attn_forms(std::integer_sequence<in
     return {{attn_form<I>()...}};
 }
 
-int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p) {
+// the ROWS instantiations of the canonical kernel, by the same index (its canonical half)
+template <int I, int GQ = 1 << (I / AF_GQ % 4), int NW = I / AF_NW % 2 ? 8 : 4, int HD = I % 2 ? 128 : 64>
+constexpr AttnKernel attn_rows_form() {
+    if constexpr ((NW == 8 && GQ > ATTN_NW8_GQ) || GQ > ATTN_CANON_GQ_WG) return nullptr;
+    else return attn_kernel<GQ, NW, HD, true>;
+}
+template <int... I>
+constexpr std::array<AttnKernel, AF_CANON> attn_rows_forms(std::integer_sequence<int, I...>) {
+    return {{attn_rows_form<I>()...}};
+}
+
+int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p, bool rows) {
     static constexpr std::array<AttnKernel, ATTN_FORMS> forms = attn_forms(std::make_integer_sequence<int, ATTN_FORMS>());
+    static constexpr std::array<AttnKernel, AF_CANON> rows_forms = attn_rows_forms(std::make_integer_sequence<int, AF_CANON>());
     if (p.status != KF_OK) return p.status;
-    const AttnKernel k = forms[attn_form_index(p.canon, p.gq, p.nw, p.hd)];
+    if (rows && !p.canon) return KF_INTERNAL_ERR;
+    const AttnKernel k = rows ? rows_forms[attn_form_index(false, p.gq, p.nw, p.hd)] : forms[attn_form_index(p.canon, p.gq, p.nw, p.hd)];
     if (!k) return KF_INTERNAL_ERR; /* a form attn_plan never names */
     a.n_tok = p.grid[2], a.n_splits = p.n_splits, a.chunk = p.chunk, a.gq_split = p.gq_split, a.cnt_stride = p.cnt_stride;
     a.inv_sqrt_hd_den = sqrtf((float)p.hd);

@@ -16,6 +16,7 @@ constexpr int ATTN_SLICE_KEYS = 64, ATTN_ONE_SLICE_KEYS = 192, ATTN_SLICE_WGS = 
 constexpr int ATTN_NW8_KEYS = 128, ATTN_NW8_GQ = 2;
 // the canonical order deals the query heads of GQA-4 / GQA-8 to workgroups of two: 8 heads in one workgroup need 411 registers (one wave per SIMD), 2 need 224
 constexpr int ATTN_CANON_GQ_WG = 2;
+constexpr int ATTN_VERIFY_MAX = 8; /* queries of one verify launch (kf_attn_decode_rows): the rows of kf_gemv_rows_plan.h */
 // arrival counters at the head of the decode scratch, at most 64 ints apart: the counters of two (kv-head, part) on different cache lines (atomics on one line serialise)
 constexpr int KF_ATTN_CNT_BYTES = 16384, ATTN_CNT_STRIDE_MAX = 64;
 // prompts: the MFMA tile kernel (128 (token, query head) columns per workgroup, as in the backward) from 8 tokens; fewer: one slice of the decode kernel per token
@@ -97,7 +98,7 @@ struct AttnTileKv8Lds : AttnLds { /* attn_prefill_kv8_kernel<hd, gq> */
 };
 
 // ---- the problem
-enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5 };
+enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5, ATTN_VERIFY = 6 };
 enum { ATTN_Q_AL = 1, ATTN_OUT_AL = 2 }; /* q 16-byte aligned, out 8-byte aligned */
 struct AttnProblem {
     int entry, n_head, n_kv, hd;
@@ -107,6 +108,7 @@ struct AttnProblem {
 };
 // ---- the plan, by route:
 //   ATTN_SLICED     attn_kernel (canon) / attn_fast_kernel <gq, nw, hd> on (n_splits, n_kv * gq_split, 1); the last workgroup of a (kv-head, part) merges the slices
+//                   (ATTN_VERIFY: the canonical kernel's ROWS form on (n_splits of the last query, n_kv * gq_split, n_tok), scratch per query)
 //   ATTN_PER_TOKEN  the same kernels on (1, n_kv * gq_split, n_tok), no scratch
 //   ATTN_TILE / ATTN_PAIRED  attn_prefill_kernel<hd, gq, kh, kt> on (blocks, n_kv, n_seq); kh = 2: a block from the front and one from the back per workgroup
 //   ATTN_BWD        attn_bwd_dq_mfma_kernel<hd> on grid, then attn_bwd_dkv_mfma_kernel<hd> on grid_kv
@@ -165,6 +167,17 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         p.lds = AttnTileKv8Lds(P.hd).bytes;
         return p;
     }
+    if (P.entry == ATTN_VERIFY) { /* n_tok consecutive queries of one sequence, query r at pos + r against keys 0 .. pos + r: the sliced decode kernel with the query on
+                                     grid z.  Canonical order only: every z takes attn_slices at its own position inside the kernel, the grid's x and the waves are
+                                     the last row's (the slice count never falls as the position grows), the hand-off scratch is one decode scratch per row */
+        p.route = ATTN_SLICED;
+        if (!hd_ok || !kv_ok || !gq_ok || P.pos < 0 || P.n_tok < 1 || P.n_tok > ATTN_VERIFY_MAX || !P.canon) return refuse(KF_INVALID_ARGS);
+        const AttnSlices s = attn_slices(P.pos + P.n_tok - 1, P.n_kv, GQ);
+        if (!sliced(true, s, s.nw, P.n_tok, true)) return p;
+        p.scratch *= P.n_tok;
+        p.lds = AttnCanonLds(p.gq, p.nw, P.hd).bytes;
+        return p;
+    }
     // the tile kernel: 16-byte q and K / V rows, 8-byte out rows
     const long long out_stride = P.out_stride > 0 ? P.out_stride : P.q_stride;
     const bool tile_ok = !(out_stride & 3) && hd_ok && kv_ok && !(P.q_stride & 7) && !(P.kv_stride & 7) && (P.al & ATTN_Q_AL) && (P.al & ATTN_OUT_AL) && gq_ok;
@@ -191,7 +204,7 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
 }
 
 // ---- the launchers carry out a plan with status KF_OK: KF_OK, KF_INTERNAL_ERR (a form the plan never names) or KF_HIP_CHECK
-int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p); /* kf_attn.hip, ATTN_SLICED / ATTN_PER_TOKEN (returns p.status when not KF_OK); a's geometry from p */
+int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p, bool rows = false); /* kf_attn.hip, ATTN_SLICED / ATTN_PER_TOKEN (returns p.status when not KF_OK); a's geometry from p; rows: an ATTN_VERIFY plan */
 int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, int pos0, int n_tok,
                              long long q_stride, int n_kv, int kv_stride, int n_seq, long long out_stride); /* kf_attn_prefill.hip, ATTN_TILE / ATTN_PAIRED */
 int attn_backward_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o,

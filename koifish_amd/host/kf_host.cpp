@@ -352,7 +352,9 @@ Fish::~Fish() {
         if (gBUFF.d_ptok) kf_free(ctx, gBUFF.d_ptok);
         FreeScore();
         if (d_rng) kf_free(ctx, d_rng);
+        if (d_vtok) kf_free(ctx, d_vtok);
     }
+    vX.reset(), vQ.reset(), vAttn.reset(), vGate.reset(), vLogits.reset(), v_attn_ws.reset(), v_head_ws.reset();
     attn.clear(), ffn.clear();
     embed = TokenEmbed(), head = Head4Token(), final_norm = LayerNormal();
     gBUFF = MemBuffer(), cache = KVCache(), x.reset();
@@ -1179,6 +1181,142 @@ int Fish::Generate(const int* prompt, int n_prompt, int n_new, int* out, bool us
     return KF_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ speculative decoding: the verify pass and the rounds
+int Fish::VerifyReady(bool logits) {
+    const int R = KF_SPEC_MAX_K + 1, C = config.nEmbed, qd = config.n_head * config.head_dim;
+    if (!vX) {
+        const kf_weight wh = head.proj.w->desc();
+        vX = GT(ctx, "vX", typNUMBER::BF16, C, R), vQ = GT(ctx, "vQ", typNUMBER::BF16, qd, R), vAttn = GT(ctx, "vAttn", typNUMBER::BF16, qd, R);
+        vGate = GT(ctx, "vGate", typNUMBER::BF16, config.n_ff, R);
+        v_attn_ws = GT(ctx, "v_attn_ws", typNUMBER::F32, (int)((kf_attn_rows_scratch_bytes(config.n_head, config.head_dim, R) + 3) / 4)); /* zero-filled once */
+        v_head_ws = GT(ctx, "v_head_ws", typNUMBER::F32, (int)((kf_head_rows_scratch_bytes(&wh) + 3) / 4));
+        if (!vX || !vQ || !vAttn || !vGate || !v_attn_ws || !v_head_ws) return vX.reset(), KF_OUTOF_GPUMEMORY;
+        KF_TRY(kf_malloc(ctx, (size_t)2 * R * 4, (void**)&d_vtok));
+    }
+    if (logits && !vLogits && !(vLogits = GT(ctx, "vLogits", typNUMBER::BF16, config.vocab, R))) return KF_OUTOF_GPUMEMORY;
+    return KF_OK;
+}
+
+int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, std::string& why) {
+    if (!tokens || !top1 || n < 1 || n > KF_SPEC_MAX_K + 1 || pos0 < 0 || pos0 + n > config.n_ctx)
+        return refused(why, "kfh_verify", KF_INVALID_ARGS, "1 .. 8 tokens at positions inside the context, and a place for their ids");
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= config.vocab) return refused(why, "kfh_verify", KF_INVALID_ARGS, "a token id outside the vocabulary");
+    if (!embed.w || !head.proj.w) return refused(why, "kfh_verify", KF_INVALID_ARGS, "the model has no weights yet");
+    const int rcm = verify_refusal(Modes(), samp_params.greedy(), "kfh_verify", why);
+    if (rcm != KF_OK) return Kv8Note(why), rcm;
+    KF_TRY(VerifyReady(logits != nullptr));
+    const int C = config.nEmbed, hd = config.head_dim, nh = config.n_head, nkv = config.n_head_kv, qd = nh * hd, kvd = nkv * hd, F = config.n_ff;
+    floatX *bx = ToX(vX), *bq = ToX(vQ), *ba = ToX(vAttn), *bg = ToX(vGate);
+    int32_t* d_top1 = d_vtok + KF_SPEC_MAX_K + 1;
+    int64_t before[2], after[2];
+    KF_TRY(kf_rows_route_counts(ctx, before));
+    const kf_weight we = embed.w->desc();
+    KF_TRY(kf_h2d(ctx, d_vtok, tokens, (size_t)n * 4));
+    KF_TRY(kf_embed_batch(ctx, &we, d_vtok, n, bx));
+    for (int l = 0; l < config.nLayer; l++) {
+        SelfAttention* a = attn[l].get();
+        FFN* m = ffn[l].get();
+        floatX* kc = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_KEY, l, 0));
+        floatX* vc = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_VAL, l, 0));
+        const kf_weight wq = a->Q.w->desc(), wk = a->K.w->desc(), wv = a->V.w->desc(), wo = a->proj_cat.w->desc();
+        const kf_weight wg = m->gate.w->desc(), wu = m->up.w->desc(), wd = m->down.w->desc();
+        const kf_weight* qkv[3] = {&wq, &wk, &wv};
+        kf_bf16* ys[3] = {bq, kc, vc}; /* the raw K rows and the V rows straight into cache rows pos0 + r */
+        const int64_t row_stride[3] = {qd, 0, 0}, pos_stride[3] = {0, kvd, kvd};
+        KF_TRY(kf_norm_linear_rows(ctx, bx, C, ToX(a->norm.w), a->norm.rms_eps, 3, qkv, ys, row_stride, pos_stride, pos0, n));
+        // every K row of the batch normed and rotated in place BEFORE the attention: query r reads the keys of rows 0 .. r - 1
+        KF_TRY(kf_qknorm_rope_batch(ctx, bq, kc + (size_t)pos0 * kvd, a->normQ.w ? ToX(a->normQ.w) : nullptr, a->normK.w ? ToX(a->normK.w) : nullptr, rope_table, pos0, n, qd, kvd,
+                                    nh, nkv, hd, a->normQ.rms_eps));
+        KF_TRY(kf_attn_decode_rows(ctx, bq, qd, kc, vc, ba, pos0, n, nh, nkv, hd, kvd, v_attn_ws->data));
+        KF_TRY(kf_linear_rows(ctx, &wo, ba, qd, bx, C, n, KF_EPI_RESIDUAL, bx, C));
+        KF_TRY(kf_norm_gateup_swiglu_rows(ctx, bx, C, ToX(m->norm.w), m->norm.rms_eps, &wg, &wu, bg, F, n));
+        KF_TRY(kf_linear_rows(ctx, &wd, bg, F, bx, C, n, KF_EPI_RESIDUAL, bx, C));
+    }
+    const kf_weight wh = head.proj.w->desc();
+    KF_TRY(kf_norm_lm_head_rows(ctx, bx, C, ToX(final_norm.w), final_norm.rms_eps, &wh, logits ? ToX(vLogits) : nullptr, config.vocab, d_top1, n, v_head_ws->data));
+    KF_TRY(kf_d2h(ctx, top1, d_top1, (size_t)n * 4)); /* the round's one read */
+    if (logits) KF_TRY(kf_d2h(ctx, logits, vLogits->data, (size_t)n * config.vocab * 2));
+    KF_TRY(kf_rows_route_counts(ctx, after));
+    verify_rows[0] += after[0] - before[0], verify_rows[1] += after[1] - before[1];
+    return KF_OK;
+}
+
+int SpecDecoder::Propose(const std::vector<int>& ids, int kk, int* out) {
+    const int n = (int)ids.size();
+    if (kk < 1) return 0;
+    if (kind == 0) return spec_lookup(ids.data(), n, ngram, kk, out);
+    if (kind == 2) {
+        const int m = fn ? fn(ids.data(), n, kk, out, user) : 0;
+        return m < 0 ? 0 : m > kk ? kk : m;
+    }
+    // another Fish: the ids it has not consumed yet are teacher-forced (rows draft_rows .. n - 1), then kk - 1 free-running steps; the step at row p gives the id of
+    // row p + 1, so rows n - 1 .. n + kk - 2 give the kk proposals.  Rows past the accepted ones are rewritten by a later round before anything reads them
+    Fish* d = draft;
+    const int p0 = draft_rows, steps = n - p0 + kk - 1;
+    if (kf_h2d(d->ctx, d->d_forced + p0, ids.data() + p0, (size_t)(n - p0) * 4) != KF_OK) return -1;
+    if (d->SetState(ids[p0], p0) != KF_OK || d->RunSteps(p0, steps, true) != KF_OK) return -1;
+    if (kf_d2h(d->ctx, out, d->d_tokens_out + (n - 1), (size_t)kk * 4) != KF_OK || d->EngineCheck() != KF_OK) return -1;
+    return kk;
+}
+
+int SpecDecoder::Generate(const int* prompt, int n_prompt, int n_new, int* out, std::string& why) {
+    Fish* f = target;
+    if (!f || !prompt || !out || n_prompt < 1 || n_new < 1 || n_prompt + n_new - 1 > f->config.n_ctx)
+        return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "a prompt and a number of new ids that fit the context");
+    if (k < 1 || k > KF_SPEC_MAX_K) return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "k outside 1 .. 7");
+    for (int i = 0; i < n_prompt; i++)
+        if (prompt[i] < 0 || prompt[i] >= f->config.vocab) return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "a prompt id outside the vocabulary");
+    int n_ctx = f->config.n_ctx;
+    if (kind == 1) {
+        if (!draft || draft == f || draft->config.vocab != f->config.vocab) return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "the drafter is another Fish with the target's vocabulary");
+        if (!draft->samp_params.greedy()) return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "the drafter proposes greedy ids: kfh_set_sampler with temperature 0 on it first");
+        if (draft->config.n_ctx < n_ctx) n_ctx = draft->config.n_ctx; /* rounds stop drafting where the drafter's cache ends */
+        std::vector<int32_t> free_run((size_t)draft->config.n_ctx, -1);
+        KF_TRY(kf_h2d(draft->ctx, draft->d_forced, free_run.data(), free_run.size() * 4));
+        draft_rows = 0;
+    }
+    const int rcm = verify_refusal(f->Modes(), f->samp_params.greedy(), "kfh_spec_generate", why); /* before the prompt runs: a refused call changes nothing */
+    if (rcm != KF_OK) return f->Kv8Note(why), rcm;
+    // the prompt, as Generate runs it: the ids forced, token-serial steps up to the last prompt token (prefill_mode 1: the token batch, which also gives the first new id)
+    std::vector<int32_t> forced(f->config.n_ctx, -1);
+    for (int i = 0; i < n_prompt; i++) forced[i] = prompt[i];
+    KF_TRY(kf_h2d(f->ctx, f->d_forced, forced.data(), forced.size() * 4));
+    std::vector<int> ids(prompt, prompt + n_prompt); /* the context: every id that is settled; the last one is not in the caches yet */
+    int n_out = 0;
+    if (f->prefill_mode == 1 && n_prompt > 1) {
+        KF_TRY(f->Prefill(prompt, n_prompt, 0));
+        int32_t st[4];
+        KF_TRY(kf_d2h(f->ctx, st, f->d_state, 16));
+        ids.push_back(st[0]), out[n_out++] = st[0];
+    } else if (n_prompt > 1) {
+        KF_TRY(f->SetState(prompt[0], 0));
+        KF_TRY(f->RunSteps(0, n_prompt - 1, true));
+    }
+    int drafts[KF_SPEC_MAX_K + 1], rows[KF_SPEC_MAX_K + 1], top1[KF_SPEC_MAX_K + 1];
+    while (n_out < n_new) {
+        const int pos = (int)ids.size() - 1; /* the row of the last settled id */
+        const int kk = spec_clip_k(k, n_new - n_out, pos, n_ctx);
+        const int m = Propose(ids, kk, drafts);
+        if (m < 0) return refused(why, "kfh_spec_generate", KF_INTERNAL_ERR, "the drafter's steps failed");
+        rows[0] = ids.back();
+        for (int i = 0; i < m; i++) {
+            if (drafts[i] < 0 || drafts[i] >= f->config.vocab) return refused(why, "kfh_spec_generate", KF_INVALID_ARGS, "the drafter proposed an id outside the vocabulary");
+            rows[1 + i] = drafts[i];
+        }
+        KF_TRY(f->Verify(rows, m + 1, pos, top1, nullptr, why));
+        const int n_acc = spec_accept(drafts, m, top1);
+        for (int i = 0; i <= n_acc; i++) ids.push_back(top1[i]), out[n_out++] = top1[i];
+        rounds++, proposed += m, accepted += n_acc;
+        if (kind == 1 && m > 0) draft_rows = n_acc + 1 < m ? pos + n_acc + 1 : pos + m; /* its steps took rows up to pos + m - 1: those whose input was a kept id stay */
+    }
+    // behind the last id, as Generate leaves the target: the ids in d_tokens_out (the id produced at each position), the state on the last of them
+    const int last = (int)ids.size() - 1;
+    KF_TRY(kf_h2d(f->ctx, f->d_tokens_out + (n_prompt - 1), out, (size_t)n_new * 4));
+    KF_TRY(f->SetState(ids[last], last));
+    return f->EngineCheck();
+}
+
 // ------------------------------------------------------------------------------------------------ XCD engines
 XcdEngine::~XcdEngine() {
     if (!ctx) return;
@@ -1981,6 +2119,58 @@ int kfh_forward(void* h, int token, int pos, uint16_t* h_logits) {
         if (rc != KF_OK) return rc;
     }
     return f->fuse_level == 0 ? st[2] : st[0];
+}
+// the verify pass (Fish::Verify): n = 1 .. 8 tokens at positions pos0 .., top1_out [n] int32, logits_out [n][vocab] bf16 or NULL.  A refusal: kfh_host_error says why
+int kfh_verify(void* h, const int* tokens, int n, int pos0, int* top1_out, uint16_t* logits_out) {
+    return reinterpret_cast<Fish*>(h)->Verify(tokens, n, pos0, top1_out, reinterpret_cast<floatX*>(logits_out), g_host_err);
+}
+// speculative decoding (koifish::SpecDecoder): handles are SpecDecoder*.  The drafter is the lookup drafter until one of the setters names another
+void* kfh_spec_create(void* target, int k) {
+    if (!target || k < 1 || k > KF_SPEC_MAX_K) {
+        g_host_err = "kfh_spec_create: a target and k in 1 .. 7";
+        return nullptr;
+    }
+    SpecDecoder* s = new SpecDecoder();
+    s->target = reinterpret_cast<Fish*>(target), s->k = k;
+    s->rows_shared = -s->target->verify_rows[0], s->rows_single = -s->target->verify_rows[1]; /* the target's counts when the decoder began */
+    return s;
+}
+void kfh_spec_destroy(void* s) { delete reinterpret_cast<SpecDecoder*>(s); }
+int kfh_spec_set_lookup(void* s, int ngram) {
+    if (!s || ngram < 1) return KF_INVALID_ARGS;
+    SpecDecoder* d = reinterpret_cast<SpecDecoder*>(s);
+    d->kind = 0, d->ngram = ngram;
+    return KF_OK;
+}
+int kfh_spec_set_draft_model(void* s, void* fish) {
+    if (!s || !fish) return KF_INVALID_ARGS;
+    SpecDecoder* d = reinterpret_cast<SpecDecoder*>(s);
+    d->kind = 1, d->draft = reinterpret_cast<Fish*>(fish);
+    return KF_OK;
+}
+int kfh_spec_set_callback(void* s, SpecDecoder::DraftFn fn, void* user) {
+    if (!s || !fn) return KF_INVALID_ARGS;
+    SpecDecoder* d = reinterpret_cast<SpecDecoder*>(s);
+    d->kind = 2, d->fn = fn, d->user = user;
+    return KF_OK;
+}
+int kfh_spec_generate(void* s, const int* prompt, int n_prompt, int n_new, int* out) {
+    return s ? reinterpret_cast<SpecDecoder*>(s)->Generate(prompt, n_prompt, n_new, out, g_host_err) : KF_INVALID_ARGS;
+}
+// {rounds, ids proposed, ids accepted, activation rows of the verify passes served with the shared unpack, ... served row by row}, since the decoder exists
+int kfh_spec_stats(void* s, int64_t* out5) {
+    if (!s || !out5) return KF_INVALID_ARGS;
+    const SpecDecoder* d = reinterpret_cast<SpecDecoder*>(s);
+    out5[0] = d->rounds, out5[1] = d->proposed, out5[2] = d->accepted, out5[3] = d->rows_shared + d->target->verify_rows[0], out5[4] = d->rows_single + d->target->verify_rows[1];
+    return KF_OK;
+}
+// the rules of kf_spec.hpp without a device (tests/test_spec_cpu.py)
+int kfhdbg_spec_clip_k(int k, int n_left, int pos, int n_ctx) { return spec_clip_k(k, n_left, pos, n_ctx); }
+int kfhdbg_spec_accept(const int* drafts, int k, const int* top1) { return spec_accept(drafts, k, top1); }
+int kfhdbg_spec_lookup(const int* ids, int n, int ngram, int k, int* out) { return spec_lookup(ids, n, ngram, k, out); }
+int kfhdbg_verify_refusal(unsigned active, int greedy, char* why, size_t n) {
+    std::string w;
+    return why_out(verify_refusal(active, greedy != 0, "kfhdbg", w), w, why, n);
 }
 int kfh_generate(void* h, const int* prompt, int n_prompt, int n_new, int* out, int use_graph) {
     return reinterpret_cast<Fish*>(h)->Generate(prompt, n_prompt, n_new, out, use_graph != 0);

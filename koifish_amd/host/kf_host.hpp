@@ -21,6 +21,7 @@
 
 #include "../../include/kf_abi.h"
 #include "kf_host_modes.hpp"
+#include "kf_spec.hpp"
 
 namespace koifish {
 
@@ -406,6 +407,38 @@ struct Fish : SeqBuffers {
     int FlowChunk(const int* tokens, int m, int pos);
     int FlowEnd(int last, int token, int pos);
     int LayersAndHead(hGTensor cur);  // what EnqueueStep and ForwardOnRLS share: the embedded row through every layer's cuInfer, then the head
+    // ---- the verify pass of speculative decoding (include/kf_abi.h "row siblings"): n = 1 .. 8 tokens at positions pos0 .. pos0 + n - 1 -- a token and its drafted
+    // continuations -- through every layer with ONE pass over the weights: per layer [norm + q | k | v rows] -> q/k-norm + RoPE rows -> attention rows -> [o_proj +
+    // residual rows] -> [norm + gate | up + SwiGLU rows] -> [down + residual rows], then [final norm + head + pick per row]: six launches per layer whatever n is.
+    // top1[i] = the greedy id behind row i; logits_or_null [n][vocab].  Row i carries every bit (id, logits, K / V rows pos0 + i) of ForwardOnRLS(tokens[i], pos0 + i)
+    // run one after the other on the fused per-layer launches (canonical order; in the v_dot2c order and for storages the row kernel does not take the entries run the
+    // one-token launches row by row: still the plain step's bits).  Eager, the position from the host; K / V rows pos0 .. pos0 + n - 1 are (re)written, d_state, the
+    // residual row x and the logits row of the plain step are not touched.  Not a mode: it reads Modes() and refuses while any is on, and a sampler that is not greedy
+    // (verify_refusal, kf_spec.hpp).  One device-to-host read (the n ids; the logits when asked for).
+    hGTensor vX, vQ, vAttn, vGate, vLogits, v_attn_ws, v_head_ws;  // [8][.] activation rows of the pass and its scratch, allocated by the first Verify
+    int32_t* d_vtok = nullptr;  // [8] the pass's ids, then [8] its greedy ids
+    int VerifyReady(bool logits);
+    int Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits_or_null, std::string& why);
+    int64_t verify_rows[2] = {0, 0};  // activation rows of the Verify passes' mat-vec entries served with the shared unpack / row by row (kf_rows_route_counts deltas)
+};
+
+// Speculative decoding on a target Fish (greedy): rounds of "propose k ids, verify them in one pass, keep the longest agreed prefix" (kf_spec.hpp).  The ids it emits
+// are Fish::Generate's, id for id: every kept id is the target's own greedy id behind a context of kept ids.
+struct SpecDecoder {
+    typedef int (*DraftFn)(const int* ids, int n, int k, int* out, void* user);  // a host drafter: the context ids [0, n) -> up to k proposals in out, their number back
+    Fish* target = nullptr;    // not owned
+    int k = 4;                 // drafts per round, 1 .. KF_SPEC_MAX_K
+    int kind = 0;              // 0 lookup, 1 another Fish, 2 callback
+    int ngram = 3;
+    Fish* draft = nullptr;     // not owned; the same device, an equal vocabulary; its greedy steps run through RunSteps (whatever serves it, the engine included)
+    int draft_rows = 0;        // the drafter's cache rows [0, draft_rows) belong to accepted tokens
+    DraftFn fn = nullptr;
+    void* user = nullptr;
+    int64_t rounds = 0, proposed = 0, accepted = 0;
+    int64_t rows_shared = 0, rows_single = 0;  // minus the target's verify_rows when the decoder began: kfh_spec_stats adds the target's current counts
+    int Propose(const std::vector<int>& ids, int kk, int* out);  // up to kk proposals behind ids (the last of them the token not yet in the caches)
+    // prompt [n_prompt] -> out [n_new], Generate's ids; leaves the target behind the last id: d_state = {last id, its position}, d_tokens_out as Generate leaves it
+    int Generate(const int* prompt, int n_prompt, int n_new, int* out, std::string& why);
 };
 
 // What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their

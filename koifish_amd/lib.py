@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "kf_lora_forward", "kf_lora_backward", "kf_lora_backward_scratch_bytes", "kf_lora_apply", "kf_lora_apply_status",
     "kf_evolve", "kf_loss_mean", "kf_distill_classifier",
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
+    "kf_linear_rows", "kf_norm_linear_rows", "kf_norm_gateup_swiglu_rows", "kf_norm_lm_head_rows", "kf_head_rows_scratch_bytes", "kf_rows_route_counts", "kf_attn_decode_rows", "kf_attn_rows_scratch_bytes",
     "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
 ]
 
@@ -84,6 +85,8 @@ _TRAINER_ENTRIES = [
     ("set_distill", [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p], C.c_int),
     ("forward_logits", [C.c_void_p, C.c_void_p], C.c_int),
 ]
+# a host drafter of generate_speculative: (ids, n, k, out, user) -> the number of ids proposed (koifish::SpecDecoder::DraftFn)
+SPEC_DRAFT_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p)
 _libs = None
 
 
@@ -170,6 +173,16 @@ def load():
         hip.kf_norm_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         hip.kf_norm_gateup_swiglu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Weight), C.POINTER(Weight), C.c_void_p]
         hip.kf_norm_lm_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # the row siblings (R = 1 .. 8 activation rows over one weight pass)
+        hip.kf_linear_rows.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_void_p, C.c_int64]
+        hip.kf_norm_linear_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        hip.kf_norm_gateup_swiglu_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.POINTER(Weight), C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_int]
+        hip.kf_norm_lm_head_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        hip.kf_head_rows_scratch_bytes.argtypes, hip.kf_head_rows_scratch_bytes.restype = [C.POINTER(Weight)], C.c_size_t
+        hip.kf_rows_route_counts.argtypes = [C.c_void_p, C.c_void_p]
+        hip.kf_attn_decode_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
+        hip.kf_attn_rows_scratch_bytes.argtypes, hip.kf_attn_rows_scratch_bytes.restype = [C.c_int] * 3, C.c_size_t
+        hip.kfdbg_gemv_rows_plan.argtypes = [C.c_void_p, C.c_void_p]
         hip.kf_lm_head.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_head_logprob.argtypes = [C.c_void_p, C.POINTER(Weight), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         hip.kf_head_logprob_scratch_bytes.argtypes, hip.kf_head_logprob_scratch_bytes.restype = [C.POINTER(Weight), C.c_int], C.c_size_t
@@ -210,6 +223,20 @@ def load():
         host.kfh_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         host.kfh_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         host.kfh_set_forced.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        # speculative decoding: the verify pass, the decoder, and its pure rules (host/kf_spec.hpp) without a device
+        host.kfh_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        host.kfh_spec_create.restype = C.c_void_p
+        host.kfh_spec_create.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_spec_destroy.argtypes, host.kfh_spec_destroy.restype = [C.c_void_p], None
+        host.kfh_spec_set_lookup.argtypes = [C.c_void_p, C.c_int]
+        host.kfh_spec_set_draft_model.argtypes = [C.c_void_p, C.c_void_p]
+        host.kfh_spec_set_callback.argtypes = [C.c_void_p, SPEC_DRAFT_FN, C.c_void_p]
+        host.kfh_spec_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        host.kfh_spec_stats.argtypes = [C.c_void_p, C.c_void_p]
+        host.kfhdbg_spec_clip_k.argtypes = [C.c_int] * 4
+        host.kfhdbg_spec_accept.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        host.kfhdbg_spec_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        host.kfhdbg_verify_refusal.argtypes = [C.c_uint, C.c_int, C.c_char_p, C.c_size_t]
         host.kfh_set_state.argtypes = [C.c_void_p, C.c_int, C.c_int]
         host.kfh_last_error.restype = C.c_char_p
         host.kfh_host_error.restype = C.c_char_p

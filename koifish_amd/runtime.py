@@ -498,6 +498,68 @@ class Context:
         L.check(self.hip.kf_norm_gateup_swiglu(self.h, _ptr(x), _ptr(norm_w), eps, C.byref(dg), C.byref(du), _ptr(act)), "kf_norm_gateup_swiglu")
         return act
 
+    # ---- the row siblings: x [R, ne1] (R = 1 .. 8 consecutive positions of one sequence) against one pass over the weights; thin mirrors for the op tests
+    def linear_rows(self, w, x, residual=None, y=None):
+        """kf_linear_rows: y [R, ne0] = x . W^T (+ residual); y may be the residual tensor itself (the in-place form)"""
+        R = x.shape[0]
+        y = torch.zeros(R, w.ne0, dtype=torch.bfloat16, device=self.device) if y is None else y
+        d = w.desc()
+        epi = L.KF_EPI_RESIDUAL if residual is not None else 0
+        L.check(self.hip.kf_linear_rows(self.h, C.byref(d), _ptr(x), x.stride(0), _ptr(y), y.stride(0), R, epi, _ptr(residual),
+                                        residual.stride(0) if residual is not None else 0), "kf_linear_rows")
+        return y
+
+    def norm_linear_rows(self, x, norm_w, ws, eps=1e-6, ys=None, y_row_stride=None, y_pos_stride=None, pos0=0):
+        """kf_norm_linear_rows: row r of projection i at ys[i] + r * y_row_stride[i] + (pos0 + r) * y_pos_stride[i] (default: fresh [R, ne0] tensors)"""
+        R = x.shape[0]
+        if ys is None:
+            ys = [torch.zeros(R, w.ne0, dtype=torch.bfloat16, device=self.device) for w in ws]
+            y_row_stride, y_pos_stride = [y.stride(0) for y in ys], [0] * len(ws)
+        descs = [w.desc() for w in ws]
+        wp = (C.c_void_p * len(ws))(*[C.addressof(d) for d in descs])
+        yp = (C.c_void_p * len(ws))(*[y.data_ptr() for y in ys])
+        rs, ps = (C.c_int64 * len(ws))(*y_row_stride), (C.c_int64 * len(ws))(*y_pos_stride)
+        L.check(self.hip.kf_norm_linear_rows(self.h, _ptr(x), x.stride(0), _ptr(norm_w), eps, len(ws), wp, yp, rs, ps, int(pos0), R), "kf_norm_linear_rows")
+        return ys
+
+    def norm_gateup_swiglu_rows(self, x, norm_w, gate, up, eps=1e-6):
+        R = x.shape[0]
+        act = torch.zeros(R, gate.ne0, dtype=torch.bfloat16, device=self.device)
+        dg, du = gate.desc(), up.desc()
+        L.check(self.hip.kf_norm_gateup_swiglu_rows(self.h, _ptr(x), x.stride(0), _ptr(norm_w), eps, C.byref(dg), C.byref(du), _ptr(act), act.stride(0), R),
+                "kf_norm_gateup_swiglu_rows")
+        return act
+
+    def norm_lm_head_rows(self, w, x, norm_w=None, eps=1e-6, want_logits=True):
+        """kf_norm_lm_head_rows -> (logits [R, ne0] or None, top1 [R] as a list of ints)"""
+        R = x.shape[0]
+        d = w.desc()
+        ws = torch.empty(self.hip.kf_head_rows_scratch_bytes(C.byref(d)), dtype=torch.uint8, device=self.device)
+        logits = torch.zeros(R, w.ne0, dtype=torch.bfloat16, device=self.device) if want_logits else None
+        top1 = torch.full((R,), -1, dtype=torch.int32, device=self.device)
+        L.check(self.hip.kf_norm_lm_head_rows(self.h, _ptr(x), x.stride(0), _ptr(norm_w), eps, C.byref(d), _ptr(logits), w.ne0 if want_logits else 0, _ptr(top1), R,
+                                              _ptr(ws)), "kf_norm_lm_head_rows")
+        self.sync()   # ws is this call's own
+        return logits, top1.tolist()
+
+    def attn_decode_rows(self, q, kc, vc, pos0, n_head, n_kv, hd, kv_stride=None, scratch=None):
+        """kf_attn_decode_rows: q [R, n_head * hd] prepared queries at positions pos0 .. pos0 + R - 1 -> out [R, n_head * hd]; scratch: a zero-filled uint8 tensor
+        of kf_attn_rows_scratch_bytes the caller keeps between calls (default: a fresh one)"""
+        q = q.contiguous()   # q and out rows lie one stride apart
+        R = q.shape[0]
+        out = torch.empty(R, n_head * hd, dtype=torch.bfloat16, device=self.device)
+        if scratch is None:
+            scratch = torch.zeros(self.hip.kf_attn_rows_scratch_bytes(n_head, hd, R), dtype=torch.uint8, device=self.device)
+        L.check(self.hip.kf_attn_decode_rows(self.h, _ptr(q), q.stride(0), _ptr(kc), _ptr(vc), _ptr(out), int(pos0), R, n_head, n_kv, hd, kv_stride or n_kv * hd,
+                                             _ptr(scratch)), "kf_attn_decode_rows")
+        return out
+
+    def rows_route_counts(self):
+        """(activation rows served with the shared unpack, rows served by one-token launches) by the *_rows entries of this context"""
+        out = (C.c_int64 * 2)()
+        L.check(self.hip.kf_rows_route_counts(self.h, out), "kf_rows_route_counts")
+        return int(out[0]), int(out[1])
+
     # ---- HIP events on the ctx stream
     def event(self):
         e = C.c_void_p()
@@ -877,6 +939,63 @@ class Qwen3:
         out = np.zeros(n_new, dtype=np.int32)
         L.check(self.host.kfh_generate(self.h, p.ctypes.data_as(C.c_void_p), p.size, n_new, out.ctypes.data_as(C.c_void_p), int(use_graph)), "kfh_generate")
         return out.tolist()
+
+    # ---- speculative decoding (host/kf_spec.hpp, Fish::Verify, koifish::SpecDecoder)
+    def _host_check(self, rc, what):
+        if rc != 0:
+            why = self.host.kfh_host_error().decode()
+            raise L.KFError("%s failed with %d: %s" % (what, rc, why or self.hip.kf_last_error().decode()))
+
+    def verify(self, tokens, pos0, want_logits=False):
+        """The verify pass: R = len(tokens) <= 8 tokens at positions pos0 .. pos0 + R - 1 -- a token and its drafted continuations -- through every layer with ONE pass
+        over the weights.  Returns top1 [R] (the greedy id behind each row), and with want_logits the rows' logits as uint16 [R, vocab].  In the canonical order row i
+        carries every bit (id, logits, K / V rows pos0 + i) of forward(tokens[i], pos0 + i) called one after the other.  The decode state is not touched.  Raises with
+        the reason while a mode is on (TP, int8 activations, adapters, int8 KV cache, hot-row masks, fuse_level 0) or a sampler is set."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        top1 = np.zeros(t.size, dtype=np.int32)
+        logits = np.zeros((t.size, self.cfg["vocab"]), dtype=np.uint16) if want_logits else None
+        self._host_check(self.host.kfh_verify(self.h, t.ctypes.data_as(C.c_void_p), t.size, int(pos0), top1.ctypes.data_as(C.c_void_p),
+                                              None if logits is None else logits.ctypes.data_as(C.c_void_p)), "kfh_verify")
+        return (top1, logits) if want_logits else top1
+
+    def generate_speculative(self, prompt, n_new, draft="lookup", k=4, ngram=3):
+        """generate()'s ids -- id for id -- by rounds of "propose k ids, verify them in one pass over the weights, keep the longest prefix the model agrees with".
+        draft: another Qwen3 on this device with this vocabulary (its greedy steps, the engine included), "lookup" (the longest suffix of the context, up to `ngram`
+        ids, found earlier in the context proposes what followed it: no model), or a callable (ids, k) -> up to k proposed ids.  k = 1 .. 7.  spec_stats() counts."""
+        p = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.zeros(n_new, dtype=np.int32)
+        s = self.host.kfh_spec_create(self.h, int(k))
+        if not s:
+            raise L.KFError("kfh_spec_create: %s" % self.host.kfh_host_error().decode())
+        keep = None
+        try:
+            if isinstance(draft, Qwen3):
+                L.check(self.host.kfh_spec_set_draft_model(s, draft.h), "kfh_spec_set_draft_model")
+            elif draft == "lookup":
+                L.check(self.host.kfh_spec_set_lookup(s, int(ngram)), "kfh_spec_set_lookup")
+            elif callable(draft):
+                def cb(ids, n, kk, outp, _user):
+                    got = list(draft([ids[i] for i in range(n)], kk))[:kk]
+                    for i, g in enumerate(got):
+                        outp[i] = int(g)
+                    return len(got)
+                keep = L.SPEC_DRAFT_FN(cb)
+                L.check(self.host.kfh_spec_set_callback(s, keep, None), "kfh_spec_set_callback")
+            else:
+                raise L.KFError("generate_speculative: draft is a Qwen3, \"lookup\" or a callable")
+            rc = self.host.kfh_spec_generate(s, p.ctypes.data_as(C.c_void_p), p.size, int(n_new), out.ctypes.data_as(C.c_void_p))
+            st = (C.c_int64 * 5)()
+            self.host.kfh_spec_stats(s, st)
+            self._spec = {"rounds": int(st[0]), "proposed": int(st[1]), "accepted": int(st[2]), "rows_shared": int(st[3]), "rows_row_by_row": int(st[4])}
+            self._host_check(rc, "kfh_spec_generate")
+        finally:
+            self.host.kfh_spec_destroy(s)
+        return out.tolist()
+
+    def spec_stats(self):
+        """the last generate_speculative: rounds, ids proposed, ids accepted, and the activation rows its verify passes' mat-vec entries served with the shared unpack
+        (rows_shared) and with one-token launches (rows_row_by_row: the v_dot2c order, storages the row kernel does not take, one-row rounds)"""
+        return dict(getattr(self, "_spec", {"rounds": 0, "proposed": 0, "accepted": 0, "rows_shared": 0, "rows_row_by_row": 0}))
 
     def set_sampler(self, temperature=0.0, top_p=0.95, top_k=50, seed=42, true_topk=False):
         """CHAT_SAMPLER: temperature 0 (or top_k 1) = greedy; otherwise GeneratOnPrompt::Sample on the device, rng reseeded here.
