@@ -155,7 +155,7 @@ __device__ __forceinline__ void a8_store(uint16_t* y, const uint16_t* bias, cons
     float v = sx * acc;
     if (bias) v = v + bf2f(bias[row]);
     uint16_t r = f2bf(v);
-    if (residual) r = f2bf(bf2f(residual[o]) + bf2f(r));
+    if (residual) r = add_bf16(residual[o], r);
     y[o] = r;
 }
 

@@ -14,7 +14,7 @@ __global__ void __launch_bounds__(256) act_quant_kernel(const uint16_t* __restri
     float mul = 1.0f;
     if (norm_w) {
         const double ss = block_sumsq_bf16(xr, dim, red);
-        mul = 1.0f / sqrtf(fmaf((float)ss, inv_dim, eps));
+        mul = rms_scale((float)ss, inv_dim, eps);
     }
     auto value = [&](int i) { return norm_w ? round_bf16((bf2f(xr[i]) * mul) * bf2f(norm_w[i])) : bf2f(xr[i]); };
     float m = 0.0f;

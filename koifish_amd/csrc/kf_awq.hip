@@ -78,7 +78,7 @@ __global__ void awq_finish_kernel(const float* __restrict__ partial, int nslice,
     if (beta != 0.0f) v = v + beta * bf2f(y[o]);
     if (bias) v = v + bf2f(bias[o]);
     uint16_t r = f2bf(v);
-    if (residual) r = f2bf(bf2f(residual[o]) + bf2f(r));
+    if (residual) r = add_bf16(residual[o], r);
     y[o] = r;
 }
 

@@ -205,6 +205,60 @@ __device__ __forceinline__ float wave_max(float v) {
     return xmax32(xmax16(v));
 }
 
+// ---- The small rules that oracle/kf_oracle.c pins bit for bit, ONE body each like the fp64 sums above: every kernel that ends a mat-vec or picks a token calls
+// these, so no copy can drift ("rules stated once").
+// First maximum, ties to the lower index (sample_argmax, GoPT.cpp:602-612; oracle section 7).  The empty pick never wins.
+constexpr float FIRST_MAX_NONE_V = -__builtin_inff();
+constexpr int FIRST_MAX_NONE_I = 0x7fffffff;
+// The rule is stated once and applied to a candidate in registers or, by address, in memory (there the index is read only when the values tie, as the
+// hand-written copies read it: the per-wave picks in LDS, the per-workgroup partials)
+#define KF_FIRST_MAX_RULE(v, i) \
+    if ((v) > bv || ((v) == bv && (i) < bi)) bv = (v), bi = (i)
+__device__ __forceinline__ void first_max(float& bv, int& bi, float v, int i) { KF_FIRST_MAX_RULE(v, i); }
+__device__ __forceinline__ void first_max(float& bv, int& bi, const float* v, const int* i) { KF_FIRST_MAX_RULE(*v, *i); }
+#undef KF_FIRST_MAX_RULE
+// the pick over aligned groups of WIDTH lanes (xor butterfly from WIDTH / 2 down to 1): every lane of a group ends with the group's pick
+template <int WIDTH = 64>
+__device__ __forceinline__ void wave_first_max(float& bv, int& bi) {
+#pragma unroll
+    for (int m = WIDTH / 2; m > 0; m >>= 1) {
+        const float ov = __shfl_xor(bv, m, 64);
+        const int oi = __shfl_xor(bi, m, 64);
+        first_max(bv, bi, ov, oi);
+    }
+}
+// per-wave picks rv / ri [w0 .. nw) folded into (bv, bi) in wave order
+__device__ __forceinline__ void waves_first_max(float& bv, int& bi, const float* rv, const int* ri, int w0, int nw) {
+    for (int w = w0; w < nw; w++) first_max(bv, bi, rv + w, ri + w);
+}
+// a workgroup of 256 threads (every thread calls with its own candidate): the workgroup's pick, valid in thread 0 only
+__device__ __forceinline__ void block_first_max_256(float& bv, int& bi) {
+    wave_first_max(bv, bi);
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
+    __syncthreads();
+    if (threadIdx.x == 0) waves_first_max(bv, bi, sv, si, 1, 4);
+}
+// the decode state after a pick (argmax_finish_kernel's graph-replay update): the id is the next step's input, the position moves on; the id is also
+// recorded at the old position when the caller keeps a token list
+__device__ __forceinline__ void advance_decode_state(int32_t* st, int32_t* tokens_out, int id) {
+    const int p = st[1];
+    if (tokens_out) tokens_out[p] = id;
+    st[0] = id;
+    st[1] = p + 1;
+}
+// SwiGLU of two projections that are bf16 values already (CU_swiglu_v0, Activation.cu:85-93; oracle section 5): bf16((g * u) / (1 + exp(-g)))
+__device__ __forceinline__ uint16_t swiglu_bf16(float gt, float up) { return f2bf((gt * up) / (1.0f + kf_expf(-gt))); }
+// the residual epilogue CU_add3: bf16(x + bf16(W.x)), both operands bf16 already
+__device__ __forceinline__ uint16_t add_bf16(uint16_t res, uint16_t o) { return f2bf(bf2f(res) + bf2f(o)); }
+// RMSNorm (rms_norm_kernel, layernorm.cuh:800-847; oracle section 3): the multiplier from the fp64 sum of squares, and one normalised bf16 pair (x * mul) * w
+__device__ __forceinline__ float rms_scale(float tot, float inv_dim, float eps) { return 1.0f / sqrtf(fmaf(tot, inv_dim, eps)); }
+__device__ __forceinline__ uint32_t rms_pair(uint32_t x, uint32_t w, float mul) { return pack_bf16x2((bf_lo(x) * mul) * bf_lo(w), (bf_hi(x) * mul) * bf_hi(w)); }
+// four bf16 (two pair words) widened to one fp32 chunk of four, element order kept: exact.  The fp32 staging of the canonical 4-bit mat-vecs (XF) and of the engines
+// (F32X) writes a bf16 chunk of eight as two of these.
+__device__ __forceinline__ u32x4 widen_bf16x4(uint32_t p0, uint32_t p1) { return u32x4{p0 << 16, p0 & 0xffff0000u, p1 << 16, p1 & 0xffff0000u}; }
+
 // Sum of squares of a bf16 vector in fp64 over a whole workgroup (nthreads a multiple of 64, <= 1024).
 // fp64 keeps the result independent of the reduction tree (products of bf16 values are exact, the fp64 sum of
 // <= 2^16 of them is exact or correctly rounded to far below an fp32 ulp), which is what lets the oracle and the

@@ -139,7 +139,7 @@ __device__ __forceinline__ void eng_poll_stage_part(const uint32_t* gsrc, uint32
         const uint32_t o0 = (g[i].x & 0xffffu) | (g[i].y << 16), o1 = (g[i].z & 0xffffu) | (g[i].w << 16);
         if (F32X) {
             const int q = e0 >> 2, c = q / XCH, j = q - c * XCH;
-            xs[j * NBLK + c] = u32x4{o0 << 16, o0 & 0xffff0000u, o1 << 16, o1 & 0xffff0000u};
+            xs[j * NBLK + c] = widen_bf16x4(o0, o1);
         } else {
             const int q = e0 >> 3, c = q / XCH, j = q - c * XCH;
             reinterpret_cast<u32x2*>(xs + j * NBLK + c)[(e0 >> 2) & 1] = u32x2{o0, o1};
@@ -924,7 +924,7 @@ __device__ __forceinline__ void eng_compute_main(const EngArgs& a, const EngLds&
         mv_prefetch<P5, NCW, FMT, S5>(ly.m[4], ly.m[5], wg * P5::spg, wave, lane_m, P5::M0, r5, hot5);
         w4.run(wg * P4::spg, wave, lane_m, P4::M0, L.xs[1], 0xffffffffu, r4, [&](int row, float v, float) {
             const uint16_t o = f2bf(v);
-            L.outb[row - wg * P4::R] = (tag << 16) | (uint32_t)f2bf(bf2f(L.xrawA[row]) + bf2f(o)); /* CU_add3: bf16(x + bf16(W.x)) */
+            L.outb[row - wg * P4::R] = (tag << 16) | (uint32_t)add_bf16(L.xrawA[row], o);
         });
         if (has4 && wave < NWP4) wg_publish(L, 1, a.xch + C::xB, wg * P4::R, P4::R, NWP4, lane_m);
         // ================= P5: RMSNorm + gate/up + SwiGLU -> act
@@ -935,8 +935,7 @@ __device__ __forceinline__ void eng_compute_main(const EngArgs& a, const EngLds&
         if (wave == 0) ENG_STAMP(1, 6);
         mv_prefetch<P6, NCW, FMT, S6>(ly.m[6], ly.m[6], wg * P6::spg, wave, lane_m, P6::M0, r6);
         w5.run(wg * P5::spg, wave, lane_m, P5::M0, L.xs[0], L.hotbits[l], r5, [&](int row, float v, float v2) {
-            const float gt = round_bf16(v), up = round_bf16(v2); /* CU_swiglu_v0 on the two bf16-rounded projections */
-            L.outb[row - wg * P5::R] = (tag << 16) | (uint32_t)f2bf((gt * up) / (1.0f + kf_expf(-gt)));
+            L.outb[row - wg * P5::R] = (tag << 16) | (uint32_t)swiglu_bf16(round_bf16(v), round_bf16(v2)); /* on the two bf16-rounded projections */
         });
         if (has5 && wave < NWP5) wg_publish(L, 2, a.xch + C::act, wg * P5::R, P5::R, NWP5, lane_m);
         // ================= P6: down_proj + residual -> x of the next layer
@@ -952,7 +951,7 @@ __device__ __forceinline__ void eng_compute_main(const EngArgs& a, const EngLds&
         mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, wave, lane_m, S.M1, r1);
         w6.run(wg * P6::spg, wave, lane_m, P6::M0, L.xs[1], 0xffffffffu, r6, [&](int row, float v, float) {
             const uint16_t o = f2bf(v);
-            const uint16_t y = f2bf(bf2f(L.xrawB[row]) + bf2f(o));
+            const uint16_t y = add_bf16(L.xrawB[row], o);
             if (last) a.x_out[row] = y;
             L.outb[row - wg * P6::R] = (tag_next << 16) | (uint32_t)y;
         });
@@ -1091,8 +1090,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
     };
     auto take = [&](float v, int row) { /* the stored value and the first maximum over them */
         const uint16_t o = f2bf(v);
-        const float fv = bf2f(o);
-        if (fv > best_v || (fv == best_v && row < best_i)) best_v = fv, best_i = row;
+        first_max(best_v, best_i, bf2f(o), row);
         return o;
     };
     auto compute = [&](int b, int buf, auto store) {
@@ -1230,10 +1228,10 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
     }
     // first maximum over the workgroup's rows, published as one 8-byte granule {tag, bf16 value, row}; workgroup 0's poller picks over all of them
 #pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
+    for (int m = 32; m > 0; m >>= 1) { /* wave_first_max spelled out: through the helper the compiler schedules this kernel differently ("rules stated once") */
         const float ov = __shfl_xor(best_v, m, 64);
         const int oi = __shfl_xor(best_i, m, 64);
-        if (ov > best_v || (ov == best_v && oi < best_i)) best_v = ov, best_i = oi;
+        first_max(best_v, best_i, ov, oi);
     }
     float* rv = L.wmax; /* [NWV] values, [NWV] rows behind them (the attention scratch is free now) */
     int* ri = reinterpret_cast<int*>(L.wmax + NWV);
@@ -1241,8 +1239,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
     __syncthreads();
     unsigned long long* hb = reinterpret_cast<unsigned long long*>(a.xch + C::hbest);
     if (wave == 0 && lane == 0) {
-        for (int k = 1; k < NWV; k++)
-            if (rv[k] > best_v || (rv[k] == best_v && ri[k] < best_i)) best_v = rv[k], best_i = ri[k];
+        for (int k = 1; k < NWV; k++) first_max(best_v, best_i, rv + k, ri + k);
         /* a workgroup without rows publishes (-inf, 0x7fffffff): it never wins */
         const unsigned long long gr = ((unsigned long long)((tag << 16) | (uint32_t)f2bf(best_v)) << 32) | (unsigned long long)(uint32_t)best_i;
         __hip_atomic_store(hb + wg, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1263,28 +1260,21 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
             }
             __builtin_amdgcn_s_sleep(1);
         }
-        float bv = -__builtin_inff();
-        int bi = 0x7fffffff;
+        float bv = FIRST_MAX_NONE_V;
+        int bi = FIRST_MAX_NONE_I;
         const uint32_t hv[4] = {g0.y, g0.w, g1.y, g1.w}, hi[4] = {g0.x, g0.z, g1.x, g1.z};
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float fv = bf2f((uint16_t)(hv[k] & 0xffffu));
-            const int ix = (int)hi[k];
-            if (fv > bv || (fv == bv && ix < bi)) bv = fv, bi = ix;
-        }
+        for (int k = 0; k < 4; k++) first_max(bv, bi, bf2f((uint16_t)(hv[k] & 0xffffu)), (int)hi[k]);
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1) {
             const float ov = __shfl_xor(bv, m, 64);
             const int oi = __shfl_xor(bi, m, 64);
-            if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+            first_max(bv, bi, ov, oi);
         }
         if (lane == 0) {
             const int err = __hip_atomic_load(a.ws + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (ok && err == 0 && bi >= 0 && bi < a.vocab) { /* never advance the decode state on a timed-out hand-off */
-                const int p = a.d_state_w[1];
-                if (a.d_tokens_out) a.d_tokens_out[p] = bi;
-                a.d_state_w[0] = bi;
-                a.d_state_w[1] = p + 1;
+                advance_decode_state(a.d_state_w, a.d_tokens_out, bi);
                 if (more_steps) /* the next step of this launch starts from this id */
                     __builtin_amdgcn_raw_buffer_store_b64(u32x2{(uint32_t)bi, (uint32_t)(epoch + 1)}, eng_rsrc(a.xch + C::tokg, 8u), 0, 0, 16 /* sc1 */);
             } else if (err == 0) {

@@ -145,7 +145,7 @@ __device__ __forceinline__ void eng_poll_stage(const uint32_t* gsrc, const uint1
             ss = fma(a, a, ss), ss = fma(b, b, ss), ss = fma(c, c, ss), ss = fma(d, d, ss);
         }
         const double tot = wave_sum_f64_fast(ss);
-        mul = 1.0f / sqrtf(fmaf((float)tot, 1.0f / (float)n, eps));
+        mul = rms_scale((float)tot, 1.0f / (float)n, eps);
     }
 #pragma unroll
     for (int r = 0; r < NLD; r++) {
@@ -153,12 +153,12 @@ __device__ __forceinline__ void eng_poll_stage(const uint32_t* gsrc, const uint1
         uint32_t o0 = p0[r], o1 = p1[r];
         if (xraw) *reinterpret_cast<u32x2*>(xraw + e0) = u32x2{o0, o1};
         if (NORM) {
-            o0 = pack_bf16x2((bf_lo(o0) * mul) * bf_lo(w0[r]), (bf_hi(o0) * mul) * bf_hi(w0[r]));
-            o1 = pack_bf16x2((bf_lo(o1) * mul) * bf_lo(w1[r]), (bf_hi(o1) * mul) * bf_hi(w1[r]));
+            o0 = rms_pair(o0, w0[r], mul);
+            o1 = rms_pair(o1, w1[r], mul);
         }
         if (F32X) { /* the mat-vec phases multiply fp32 activations (BlockDotF): chunk = these 4 elements as floats, [XCH chunks per block][NBLK] */
             const int q = e0 >> 2, c = q / XCH, j = q - c * XCH;
-            xs[j * NBLK + c] = u32x4{o0 << 16, o0 & 0xffff0000u, o1 << 16, o1 & 0xffff0000u};
+            xs[j * NBLK + c] = widen_bf16x4(o0, o1);
         } else {
             const int q = e0 >> 3, c = q / XCH, j = q - c * XCH;
             reinterpret_cast<u32x2*>(xs + j * NBLK + c)[(e0 >> 2) & 1] = u32x2{o0, o1};
@@ -196,7 +196,7 @@ __device__ __forceinline__ void eng_poll_stage_long(const uint32_t* gsrc, uint32
         for (int r = 0; r < NP; r++) {
             const int e0 = 4 * ((R0 + r) * 64 + lane), q = e0 >> 2, c = q / XCH, j = q - c * XCH;
             const uint32_t o0 = (g[r].x & 0xffffu) | (g[r].y << 16), o1 = (g[r].z & 0xffffu) | (g[r].w << 16);
-            xs[j * NBLK + c] = u32x4{o0 << 16, o0 & 0xffff0000u, o1 << 16, o1 & 0xffff0000u};
+            xs[j * NBLK + c] = widen_bf16x4(o0, o1);
         }
         eng_poll_stage_long<XCH, NLD, NBLK, PIECE, R0 + NP>(gsrc, tag, xs, lane, ws, dead, nsweeps);
     }
@@ -255,17 +255,16 @@ __device__ __forceinline__ void eng_poll_stage_norm_long(const uint32_t* gsrc, c
     double ss = 0.0;
     eng_norm_long_pass1<XCH, NLD, NBLK, PLAIN, F32X, PIECE>(gsrc, plain, tag, xraw, lane, ws, dead, ss);
     const double tot = wave_sum_f64_fast(ss);
-    const float mul = 1.0f / sqrtf(fmaf((float)tot, 1.0f / (float)n, eps));
+    const float mul = rms_scale((float)tot, 1.0f / (float)n, eps);
 #pragma unroll
     for (int r = 0; r < NLD; r++) {
         const int e0 = 4 * (r * 64 + lane);
         const u32x2 raw = *reinterpret_cast<const u32x2*>(xraw + e0); /* this lane's own words of pass 1 */
         const u32x2 w = wn[r];
-        const uint32_t o0 = pack_bf16x2((bf_lo(raw.x) * mul) * bf_lo(w.x), (bf_hi(raw.x) * mul) * bf_hi(w.x));
-        const uint32_t o1 = pack_bf16x2((bf_lo(raw.y) * mul) * bf_lo(w.y), (bf_hi(raw.y) * mul) * bf_hi(w.y));
+        const uint32_t o0 = rms_pair(raw.x, w.x, mul), o1 = rms_pair(raw.y, w.y, mul);
         if (F32X) {
             const int q = e0 >> 2, c = q / XCH, j = q - c * XCH;
-            xs[j * NBLK + c] = u32x4{o0 << 16, o0 & 0xffff0000u, o1 << 16, o1 & 0xffff0000u};
+            xs[j * NBLK + c] = widen_bf16x4(o0, o1);
         } else {
             const int q = e0 >> 3, c = q / XCH, j = q - c * XCH;
             reinterpret_cast<u32x2*>(xs + j * NBLK + c)[(e0 >> 2) & 1] = u32x2{o0, o1};

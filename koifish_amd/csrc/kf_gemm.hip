@@ -456,11 +456,11 @@ __global__ void __launch_bounds__(NW * 64) gemm_direct_kernel(const GemmArgs a0)
                     if (a.beta != 0.0f) x = x + a.beta * bf2f(yp[j]);
                     if (a.bias) x = x + bf2f(a.bias[rg + j]);
                     uint16_t qv = f2bf(x);
-                    if (a.residual) qv = f2bf(bf2f(a.residual[(size_t)tok * a.ldr + rg + j]) + bf2f(qv));
+                    if (a.residual) qv = add_bf16(a.residual[(size_t)tok * a.ldr + rg + j], qv);
                     o[j] = qv;
                 } else { /* act = silu(gate) * up on the bf16-rounded gate / up (Relu::Forw SWIG, Activation.cu:85-93; the expression of kf_swiglu) */
                     const float g = round_bf16(v[j]), u = round_bf16(v2[j]);
-                    o[j] = f2bf((g * u) / (1.0f + kf_expf(-g)));
+                    o[j] = swiglu_bf16(g, u);
                 }
             }
             if (((a.ldy & 1) == 0) && ((reinterpret_cast<uintptr_t>(a.y) & 3) == 0) && rg + 1 < a.M) {

@@ -130,7 +130,7 @@ __device__ __forceinline__ void g3_epilogue(const GemmArgs& a, int m0, int t0, c
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float g = round_bf16(gv[j]), u = round_bf16(uv[j]);
-                    o[j] = f2bf((g * u) / (1.0f + kf_expf(-g)));
+                    o[j] = swiglu_bf16(g, u);
                 }
                 uint16_t* yp = a.y + (size_t)tok * a.ldy + f;
                 if (f + 3 < F && ((a.ldy & 3) == 0)) {
@@ -182,7 +182,7 @@ __device__ __forceinline__ void g3_epilogue(const GemmArgs& a, int m0, int t0, c
                     if (a.beta != 0.0f) v = v + a.beta * bf2f(yp[j]);
                     if (a.bias) v = v + bf2f(a.bias[m + j]);
                     uint16_t qv = f2bf(v);
-                    if (!AKM && a.residual) qv = f2bf(bf2f(a.residual[(size_t)tok * a.ldr + m + j]) + bf2f(qv));
+                    if (!AKM && a.residual) qv = add_bf16(a.residual[(size_t)tok * a.ldr + m + j], qv);
                     o[j] = qv;
                 }
             }

@@ -130,7 +130,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TB], const Gem
                     if (a.beta != 0.0f) v = v + a.beta * bf2f(yp[j]);
                     if (a.bias) v = v + bf2f(a.bias[rg + j]);
                     uint16_t q = f2bf(v);
-                    if (a.residual) q = f2bf(bf2f(a.residual[(size_t)tok * a.ldr + rg + j]) + bf2f(q));
+                    if (a.residual) q = add_bf16(a.residual[(size_t)tok * a.ldr + rg + j], q);
                     o[j] = q;
                 } else {
                     o[j] = 0;

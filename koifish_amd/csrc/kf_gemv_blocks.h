@@ -526,4 +526,65 @@ __device__ __forceinline__ float group_sum(float v, int lg) {
     return v;
 }
 
+// ---- parts of gemv_kernel (kf_gemv_kernel.h) and gemv_rows_kernel (kf_gemv_rows.hip) that both carry: one body each
+// Every wave works inside ONE job (the plan pads each job's slot range to a multiple of spw), so the job's fields are selected once, with constant indices into
+// the kernel arguments (SGPRs), and stay scalar for the whole loop.  Indexing a.job[] with a run-time value inside the loop would turn each access into a load from
+// the kernarg segment whose wait serialises the weight stream.  ONEJOB: job 0 by name, the descriptors of jobs 1 and 2 are never read.
+struct GemvJobSel {
+    int jx; /* the job, wave-uniform */
+    const u32x4* w;
+    const uint16_t *step, *zero;
+    uint16_t* y;
+    long long y_pos_stride;
+    int M, slot0;
+    float qb;
+};
+template <class T>
+__device__ __forceinline__ T gemv_job_pick(int jx, T f0, T f1, T f2) {
+    return jx == 0 ? f0 : (jx == 1 ? f1 : f2);
+}
+template <bool ONEJOB, class Args>
+__device__ __forceinline__ GemvJobSel gemv_job_sel(const Args& a, long s_begin) {
+    GemvJobSel s;
+    s.jx = 0;
+    if constexpr (!ONEJOB) {
+        if (a.njobs > 1 && s_begin >= a.job[1].slot0) s.jx = 1;
+        if (a.njobs > 2 && s_begin >= a.job[2].slot0) s.jx = 2;
+        s.jx = __builtin_amdgcn_readfirstlane(s.jx);
+    }
+#define JF(f) (ONEJOB ? a.job[0].f : gemv_job_pick(s.jx, a.job[0].f, a.job[1].f, a.job[2].f))
+    s.w = reinterpret_cast<const u32x4*>(JF(w));
+    s.step = JF(step), s.zero = JF(zero);
+    s.y = JF(y), s.y_pos_stride = JF(y_pos_stride);
+    s.M = JF(M), s.slot0 = JF(slot0);
+    s.qb = (float)JF(qBias);
+#undef JF
+    return s;
+}
+// a thread's share of the fp64 sum of squares of a vector of <= 4096 elements held as two chunks of 8 per thread (h0 / h1: the chunk is the thread's own; a clamped
+// lane holds a copy of chunk 0)
+__device__ __forceinline__ double sumsq_2chunks(u32x4 r0, u32x4 r1, bool h0, bool h1) {
+    const uint32_t rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+    double ss0 = 0.0, ss1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const double lo = (double)bf_lo(rw[k]), hi = (double)bf_hi(rw[k]), lo1 = (double)bf_lo(rw[4 + k]), hi1 = (double)bf_hi(rw[4 + k]);
+        ss0 = fma(lo, lo, ss0), ss0 = fma(hi, hi, ss0);
+        ss1 = fma(lo1, lo1, ss1), ss1 = fma(hi1, hi1, ss1);
+    }
+    return (h0 ? ss0 : 0.0) + (h1 ? ss1 : 0.0);
+}
+// host side of both launchers: the jobs of a launch from its weights and the plan's rows / first slots
+inline void gemv_fill_jobs(GemvJob* job, const int* slot0, const int* M, const kf_weight* const* w, int n, int fmt) {
+    for (int j = 0; j < 3; j++) {
+        GemvJob& jb = job[j];
+        jb.slot0 = slot0[j];
+        if (j >= n) continue;
+        jb.w = w[j]->data, jb.M = M[j], jb.qBias = w[j]->qBias;
+        jb.zero = jb.step = nullptr;
+        if (fmt >= FMT_Q4) jb.zero = w[j]->gama + w[j]->ne0 + w[j]->ne1; /* gama_T(ZERO), GTensor.cpp:456-510; FMT_Q4R: the row codebooks, 16 entries per row */
+        if (fmt >= FMT_Q4 && fmt != FMT_Q4R) jb.step = jb.zero + (size_t)w[j]->ne0 * w[j]->ne1 / w[j]->lGroup;
+    }
+}
+
 }  // namespace kf

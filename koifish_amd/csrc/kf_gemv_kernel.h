@@ -81,26 +81,15 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     const int nbatch = s_end > s_begin ? (int)((s_end - s_begin + G - 1) / G) : 0;
     const int nsteps = nbatch * iters;
 
-    // Every wave works inside ONE job (the launcher pads each job's slot range to a multiple of spw), so the job's fields are
-    // selected once, with constant indices into the kernel arguments (SGPRs), and stay scalar for the whole loop.  Indexing
-    // a.job[] with a run-time value inside the loop would turn each access into a load from the kernarg segment whose wait
-    // serialises the weight stream.
-    int jx = 0;
-    if constexpr (!ONEJOB) {
-        if (a.njobs > 1 && s_begin >= a.job[1].slot0) jx = 1;
-        if (a.njobs > 2 && s_begin >= a.job[2].slot0) jx = 2;
-        jx = __builtin_amdgcn_readfirstlane(jx);
-    }
-#define JF(f) (ONEJOB ? a.job[0].f : (jx == 0 ? a.job[0].f : (jx == 1 ? a.job[1].f : a.job[2].f)))
-    const u32x4* const jw = reinterpret_cast<const u32x4*>(JF(w));
+    const GemvJobSel js = gemv_job_sel<ONEJOB>(a, s_begin); /* the wave's job, scalar for the whole loop (kf_gemv_blocks.h) */
+    const u32x4* const jw = js.w;
     const u32x4* const jw2 = reinterpret_cast<const u32x4*>(a.job[1].w);
-    const uint16_t* const jstep = JF(step);
-    const uint16_t* const jzero = JF(zero);
-    uint16_t* const jy = JF(y);
-    const long long jystride = JF(y_pos_stride);
-    const int jM = JF(M), jslot0 = JF(slot0);
-    const float jqb = (float)JF(qBias), jqb2 = (float)a.job[1].qBias;
-#undef JF
+    const uint16_t* const jstep = js.step;
+    const uint16_t* const jzero = js.zero;
+    uint16_t* const jy = js.y;
+    const long long jystride = js.y_pos_stride;
+    const int jM = js.M, jslot0 = js.slot0;
+    const float jqb = js.qb, jqb2 = (float)a.job[1].qBias;
     const int gshift = a.gshift;
     auto slot = [&](long s, int& row) -> bool {
         row = (int)(s - jslot0) * RPS + sub;
@@ -226,8 +215,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
         constexpr int XCH = BD::XCH;
         auto put = [&](int c, int j, u32x4 o) {
             if constexpr (XF) {
-                xs[(2 * j) * wcols + c] = u32x4{o.x << 16, o.x & 0xffff0000u, o.y << 16, o.y & 0xffff0000u};
-                xs[(2 * j + 1) * wcols + c] = u32x4{o.z << 16, o.z & 0xffff0000u, o.w << 16, o.w & 0xffff0000u};
+                xs[(2 * j) * wcols + c] = widen_bf16x4(o.x, o.y);
+                xs[(2 * j + 1) * wcols + c] = widen_bf16x4(o.z, o.w);
             } else {
                 xs[j * nBlk + c] = o;
             }
@@ -239,24 +228,13 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
             uint32_t ow[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
             if (has_norm) {
                 const uint32_t ww[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
-                double ss0 = 0.0, ss1 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double lo = (double)bf_lo(rw[k]), hi = (double)bf_hi(rw[k]), lo1 = (double)bf_lo(rw[4 + k]), hi1 = (double)bf_hi(rw[4 + k]);
-                    ss0 = fma(lo, lo, ss0), ss0 = fma(hi, hi, ss0);
-                    ss1 = fma(lo1, lo1, ss1), ss1 = fma(hi1, hi1, ss1);
-                }
-                double ss = (h0 ? ss0 : 0.0) + (h1 ? ss1 : 0.0); /* clamped lanes hold a copy of chunk 0 */
-                ss = wave_sum_f64_fast(ss);
+                const double ss = wave_sum_f64_fast(sumsq_2chunks(r0, r1, h0, h1));
                 if (lane == 0) red[wave_in_blk] = ss;
                 __syncthreads();
                 const double tot = (red[0] + red[1]) + (red[2] + red[3]);
-                const float mul = 1.0f / sqrtf(fmaf((float)tot, a.inv_dim, a.eps));
+                const float mul = rms_scale((float)tot, a.inv_dim, a.eps);
 #pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const float v0 = (bf_lo(rw[k]) * mul) * bf_lo(ww[k]), v1 = (bf_hi(rw[k]) * mul) * bf_hi(ww[k]);
-                    ow[k] = pack_bf16x2(v0, v1);
-                }
+                for (int k = 0; k < 8; k++) ow[k] = rms_pair(rw[k], ww[k], mul);
             }
             if (h0) {
                 const int c = tid / XCH, j = tid - c * XCH;
@@ -269,9 +247,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
         } else {
             float mul = 1.0f;
             if (a.norm_w) { /* large K: two passes */
-                double ss = block_sumsq_bf16(a.x, a.K, red);
-                float val = fmaf((float)ss, a.inv_dim, a.eps);
-                mul = 1.0f / sqrtf(val);
+                mul = rms_scale((float)block_sumsq_bf16(a.x, a.K, red), a.inv_dim, a.eps);
             }
             // element e of block column c, chunk j (e = c*EPB + j*8 + i)  ->  LDS chunk (j*nBlk + c)
             const int nch_w = XF2 ? wcol0 * XCH : nch; /* XF2: the first window (the launcher takes this form only without a norm) */
@@ -284,10 +260,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                     const uint32_t rw[4] = {raw.x, raw.y, raw.z, raw.w}, ww[4] = {nw.x, nw.y, nw.z, nw.w};
                     uint32_t ow[4];
 #pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        float v0 = (bf_lo(rw[k]) * mul) * bf_lo(ww[k]), v1 = (bf_hi(rw[k]) * mul) * bf_hi(ww[k]);
-                        ow[k] = pack_bf16x2(v0, v1);
-                    }
+                    for (int k = 0; k < 4; k++) ow[k] = rms_pair(rw[k], ww[k], mul);
                     o.x = ow[0], o.y = ow[1], o.z = ow[2], o.w = ow[3];
                 }
                 put(c, j, o);
@@ -297,8 +270,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     }
 
     // ---- main: pipelined over (batch, iteration) steps
-    float best_v = -__builtin_inff();
-    int best_i = 0x7fffffff;
+    float best_v = FIRST_MAX_NONE_V;
+    int best_i = FIRST_MAX_NONE_I;
     using Acc = typename BD::Acc;
     Acc acc[G], acc2[PAIRED ? G : 1]; /* per-lane chains (canonical: an even and an odd one; four such pairs for 1-bit blocks) */
     float sum[G], sum2[PAIRED ? G : 1];
@@ -359,9 +332,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                     uint16_t* y = jy + (size_t)pos * jystride;
                     float v = sum[g];
                     if (PAIRED) {
-                        // SwiGLU of the two bf16-rounded projections (CU_swiglu_v0, Activation.cu:85-93)
-                        const float gt = round_bf16(v), up = round_bf16(sum2[g]);
-                        y[r] = f2bf((gt * up) / (1.0f + kf_expf(-gt)));
+                        y[r] = swiglu_bf16(round_bf16(v), round_bf16(sum2[g])); /* of the two bf16-rounded projections */
                         continue;
                     }
                     if (a.tp) { /* tensor-parallel push: one 8-byte {value | tag} granule into this rank's slot of every rank's receive area (kf_tp.hip) */
@@ -378,11 +349,10 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                     if (a.beta != 0.0f) v = v + a.beta * bf2f(y[r]);
                     if (a.bias) v = v + bf2f(a.bias[r]);
                     uint16_t o = f2bf(v);
-                    if (a.residual) o = f2bf(bf2f(a.residual[r]) + bf2f(o)); /* CU_add3: bf16(x + bf16(W.x)) */
+                    if (a.residual) o = add_bf16(a.residual[r], o);
                     y[r] = o;
                     if (MODE == GEMV_ARGMAX) {
-                        const float fv = bf2f(o);
-                        if (fv > best_v || (fv == best_v && r < best_i)) best_v = fv, best_i = r;
+                        first_max(best_v, best_i, bf2f(o), r);
                     }
                 }
             }
@@ -420,8 +390,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
             for (int e8 = wcol0 * XCH + tid; e8 < nch; e8 += blockDim.x) {
                 const int c = e8 / XCH - wcol0, j = e8 % XCH;
                 const u32x4 o = *reinterpret_cast<const u32x4*>(a.x + (size_t)e8 * 8);
-                xs[(2 * j) * wcols + c] = u32x4{o.x << 16, o.x & 0xffff0000u, o.y << 16, o.y & 0xffff0000u};
-                xs[(2 * j + 1) * wcols + c] = u32x4{o.z << 16, o.z & 0xffff0000u, o.w << 16, o.w & 0xffff0000u};
+                xs[(2 * j) * wcols + c] = widen_bf16x4(o.x, o.y);
+                xs[(2 * j + 1) * wcols + c] = widen_bf16x4(o.z, o.w);
             }
         }
         __syncthreads();
@@ -438,21 +408,20 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     }
 
     if (MODE == GEMV_ARGMAX) {
-        // first-maximum over this workgroup's rows (sample_argmax, GoPT.cpp:602-612)
+        // the first maximum over this workgroup's rows (first_max, kf_device.h)
 #pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            float ov = __shfl_xor(best_v, m, 64);
-            int oi = __shfl_xor(best_i, m, 64);
-            if (ov > best_v || (ov == best_v && oi < best_i)) best_v = ov, best_i = oi;
+        for (int m = 32; m > 0; m >>= 1) { /* wave_first_max spelled out: through the helper the compiler schedules this kernel differently ("rules stated once") */
+            const float ov = __shfl_xor(best_v, m, 64);
+            const int oi = __shfl_xor(best_i, m, 64);
+            first_max(best_v, best_i, ov, oi);
         }
         float* rv = reinterpret_cast<float*>(red);
         int* ri = reinterpret_cast<int*>(rv + 16);
         __syncthreads();
         if (lane == 0) rv[wave_in_blk] = best_v, ri[wave_in_blk] = best_i;
         __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-                if (rv[w] > best_v || (rv[w] == best_v && ri[w] < best_i)) best_v = rv[w], best_i = ri[w];
+        if (tid == 0) { /* waves_first_max spelled out, for the same reason */
+            for (int w = 1; w < (int)(blockDim.x >> 6); w++) first_max(best_v, best_i, rv + w, ri + w);
             a.amax_val[blockIdx.x] = best_v;
             a.amax_idx[blockIdx.x] = best_i;
         }

@@ -1,11 +1,9 @@
 // kf_gemv_rows.hip -- the canonical mat-vec of up to eight activation rows against ONE pass over the packed weights (the verify pass of speculative decoding: a
-// token and its drafted continuations), gfx950 / wave64.  A sibling of gemv_kernel (kf_gemv_kernel.h): the same data mapping -- LPR lanes walk a weight row, 64 / LPR
-// weight rows side by side per wave slot, ITERS loads per row, the lanes per row from kf::gemv_lpr_log2 -- the same even / odd chain pair per lane, the same lane tree
-// and the same epilogue arithmetic, so activation row r of a launch carries every bit of the one-token launch on that row (kf_gemv_rows_plan.h takes those figures
-// from the one-token plan).  What is shared is the weight side: a 16-byte block is loaded once and dequantised once into its 16 bf16 pair words (BlockPrep, the
-// persistent engine's "dequantise ahead" form, kf_gemv_blocks.h), then multiplied into one accumulator pair per activation row.
-// LDS: the rows' activations, row after row, each laid out as the one-token kernel lays out its one ([chunk j of block][block column], bf16 chunks of 8 or, XF, fp32
-// chunks of 4) | 256 B reduction scratch.
+// token and its drafted continuations), gfx950 / wave64.  The sibling of gemv_kernel (kf_gemv_kernel.h) with the same data mapping; what makes activation row r carry
+// every bit of the one-token launch on that row is shared by construction: the plan's figures (kf_gemv_rows_plan.h takes them from the one-token plan), the job
+// selection, the two-chunk sum of squares, the block dots and the lane tree (kf_gemv_blocks.h), the epilogue rules and the pick (kf_device.h), the job fill on the host.
+// Its own: a 16-byte block is loaded once and dequantised once into its 16 bf16 pair words (BlockPrep), then multiplied into one accumulator pair per activation row.
+// LDS: the rows' activations, row after row, each laid out as the one-token kernel lays out its one | 256 B reduction scratch.
 #include "kf_gemv_blocks.h"
 #include "kf_gemv_rows_plan.h"
 
@@ -68,22 +66,16 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
     if (s_end > a.total_slots) s_end = a.total_slots;
     const int nsteps = s_end > s_begin ? (int)(s_end - s_begin) * iters : 0;
 
-    // a wave works inside one job (the plan pads each job's slot range to whole waves): its fields are picked once and stay scalar (gemv_kernel)
-    int jx = 0;
-    if (a.njobs > 1 && s_begin >= a.job[1].slot0) jx = 1;
-    if (a.njobs > 2 && s_begin >= a.job[2].slot0) jx = 2;
-    jx = __builtin_amdgcn_readfirstlane(jx);
-#define JF(f) (jx == 0 ? a.job[0].f : (jx == 1 ? a.job[1].f : a.job[2].f))
-    const u32x4* const jw = reinterpret_cast<const u32x4*>(JF(w));
+    const GemvJobSel js = gemv_job_sel<false>(a, s_begin); /* the wave's job, scalar for the whole loop */
+    const u32x4* const jw = js.w;
     const u32x4* const jw2 = reinterpret_cast<const u32x4*>(a.job[1].w);
-    const uint16_t* const jstep = JF(step);
-    const uint16_t* const jzero = JF(zero);
-    uint16_t* const jy = JF(y);
-    const long long jystride = JF(y_pos_stride);
-    const long long jyrow = jx == 0 ? a.y_row_stride[0] : (jx == 1 ? a.y_row_stride[1] : a.y_row_stride[2]);
-    const int jM = JF(M), jslot0 = JF(slot0);
-    const float jqb = (float)JF(qBias), jqb2 = (float)a.job[1].qBias;
-#undef JF
+    const uint16_t* const jstep = js.step;
+    const uint16_t* const jzero = js.zero;
+    uint16_t* const jy = js.y;
+    const long long jystride = js.y_pos_stride;
+    const long long jyrow = js.jx == 0 ? a.y_row_stride[0] : (js.jx == 1 ? a.y_row_stride[1] : a.y_row_stride[2]);
+    const int jM = js.M, jslot0 = js.slot0;
+    const float jqb = js.qb, jqb2 = (float)a.job[1].qBias;
     const int gshift = a.gshift;
 
     // unconditional loads from a clamped (row, column): a lane outside the matrix re-reads a valid block and is masked when the block is multiplied (gemv_kernel, LAT)
@@ -116,15 +108,7 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
             if (a.norm_regs) {
                 const bool h0 = tid < nch, h1 = tid + 256 < nch;
                 const u32x4 r0 = *reinterpret_cast<const u32x4*>(xr + (size_t)(h0 ? tid : 0) * 8), r1 = *reinterpret_cast<const u32x4*>(xr + (size_t)(h1 ? tid + 256 : 0) * 8);
-                const uint32_t rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                double ss0 = 0.0, ss1 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double lo = (double)bf_lo(rw[k]), hi = (double)bf_hi(rw[k]), lo1 = (double)bf_lo(rw[4 + k]), hi1 = (double)bf_hi(rw[4 + k]);
-                    ss0 = fma(lo, lo, ss0), ss0 = fma(hi, hi, ss0);
-                    ss1 = fma(lo1, lo1, ss1), ss1 = fma(hi1, hi1, ss1);
-                }
-                ss = (h0 ? ss0 : 0.0) + (h1 ? ss1 : 0.0);
+                ss = sumsq_2chunks(r0, r1, h0, h1);
             } else {
                 ss = 0.0;
                 for (int i = tid; i < a.K; i += 256) {
@@ -144,20 +128,20 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
         if (has_norm) {
             const double* rr = red + r * 4;
             const double tot = a.norm_regs ? (rr[0] + rr[1]) + (rr[2] + rr[3]) : (((0.0 + rr[0]) + rr[1]) + rr[2]) + rr[3];
-            const float mul = 1.0f / sqrtf(fmaf((float)tot, a.inv_dim, a.eps));
+            const float mul = rms_scale((float)tot, a.inv_dim, a.eps);
             const u32x4 nw = *reinterpret_cast<const u32x4*>(a.norm_w + (size_t)e8 * 8);
             const uint32_t rw[4] = {raw.x, raw.y, raw.z, raw.w}, ww[4] = {nw.x, nw.y, nw.z, nw.w};
             uint32_t ow[4];
 #pragma unroll
-            for (int k = 0; k < 4; k++) ow[k] = pack_bf16x2((bf_lo(rw[k]) * mul) * bf_lo(ww[k]), (bf_hi(rw[k]) * mul) * bf_hi(ww[k]));
+            for (int k = 0; k < 4; k++) ow[k] = rms_pair(rw[k], ww[k], mul);
             o = u32x4{ow[0], ow[1], ow[2], ow[3]};
         }
         // element e of block column c, chunk j (e = c * EPB + j * 8 + i) -> the row's LDS chunk j * nBlk + c (XF: the two fp32 chunks 2 j, 2 j + 1)
         const int c = e8 / XCH, j = e8 - c * XCH;
         u32x4* xr = xs + (size_t)r * row_chunks;
         if constexpr (XF) {
-            xr[(2 * j) * nBlk + c] = u32x4{o.x << 16, o.x & 0xffff0000u, o.y << 16, o.y & 0xffff0000u};
-            xr[(2 * j + 1) * nBlk + c] = u32x4{o.z << 16, o.z & 0xffff0000u, o.w << 16, o.w & 0xffff0000u};
+            xr[(2 * j) * nBlk + c] = widen_bf16x4(o.x, o.y);
+            xr[(2 * j + 1) * nBlk + c] = widen_bf16x4(o.z, o.w);
         } else {
             xr[j * nBlk + c] = o;
         }
@@ -170,7 +154,7 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
     int best_i[MODE == GEMV_ARGMAX ? NR : 1];
     if constexpr (MODE == GEMV_ARGMAX) {
 #pragma unroll
-        for (int r = 0; r < NR; r++) best_v[r] = -__builtin_inff(), best_i[r] = 0x7fffffff;
+        for (int r = 0; r < NR; r++) best_v[r] = FIRST_MAX_NONE_V, best_i[r] = FIRST_MAX_NONE_I;
     }
     int bi = 0, it = 0, nbi = 0, nit = 0;
     for (int k = 0; k < nsteps; k++) {
@@ -214,17 +198,13 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
                 if constexpr (PAIRED) v2 = group_sum(acc_join(acc2[r]), a.lpr_log2);
                 if (ll == 0 && row < jM) {
                     uint16_t* y = jy ? jy + (size_t)r * jyrow + (size_t)(a.pos0 + r) * jystride : nullptr;
-                    if constexpr (PAIRED) { /* SwiGLU of the two bf16-rounded projections (gemv_kernel) */
-                        const float gt = round_bf16(v), up = round_bf16(v2);
-                        y[row] = f2bf((gt * up) / (1.0f + kf_expf(-gt)));
+                    if constexpr (PAIRED) {
+                        y[row] = swiglu_bf16(round_bf16(v), round_bf16(v2));
                     } else {
                         uint16_t o = f2bf(v);
-                        if (a.residual) o = f2bf(bf2f(a.residual[(size_t)r * a.res_stride + row]) + bf2f(o)); /* read before the store: residual may alias y */
+                        if (a.residual) o = add_bf16(a.residual[(size_t)r * a.res_stride + row], o); /* read before the store: residual may alias y */
                         if (y) y[row] = o;
-                        if constexpr (MODE == GEMV_ARGMAX) {
-                            const float fv = bf2f(o);
-                            if (fv > best_v[r] || (fv == best_v[r] && row < best_i[r])) best_v[r] = fv, best_i[r] = row;
-                        }
+                        if constexpr (MODE == GEMV_ARGMAX) first_max(best_v[r], best_i[r], bf2f(o), row);
                     }
                 }
             }
@@ -242,20 +222,14 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
             if (r >= nr) break;
             float bv = best_v[r];
             int bx = best_i[r];
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) {
-                const float ov = __shfl_xor(bv, m, 64);
-                const int oi = __shfl_xor(bx, m, 64);
-                if (ov > bv || (ov == bv && oi < bx)) bv = ov, bx = oi;
-            }
+            wave_first_max(bv, bx);
             if (lane == 0) rv[r * 4 + wave_in_blk] = bv, ri[r * 4 + wave_in_blk] = bx;
         }
         __syncthreads();
-        if (tid < nr) {
+        if (tid < nr) { /* thread r folds row r's four waves in order */
             float bv = rv[tid * 4];
             int bx = ri[tid * 4];
-            for (int w = 1; w < 4; w++)
-                if (rv[tid * 4 + w] > bv || (rv[tid * 4 + w] == bv && ri[tid * 4 + w] < bx)) bv = rv[tid * 4 + w], bx = ri[tid * 4 + w];
+            waves_first_max(bv, bx, rv + tid * 4, ri + tid * 4, 1, 4);
             a.amax_val[(size_t)tid * gridDim.x + blockIdx.x] = bv;
             a.amax_idx[(size_t)tid * gridDim.x + blockIdx.x] = bx;
         }
@@ -266,25 +240,11 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
 __global__ void __launch_bounds__(256) argmax_rows_finish_kernel(const float* val, const int* idx, int n, int32_t* d_top1) {
     const float* v = val + (size_t)blockIdx.x * n;
     const int* ix = idx + (size_t)blockIdx.x * n;
-    float bv = -__builtin_inff();
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 256)
-        if (v[i] > bv || (v[i] == bv && ix[i] < bi)) bv = v[i], bi = ix[i];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const float ov = __shfl_xor(bv, m, 64);
-        const int oi = __shfl_xor(bi, m, 64);
-        if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
-    }
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++)
-            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) bv = sv[w], bi = si[w];
-        d_top1[blockIdx.x] = bi;
-    }
+    float bv = FIRST_MAX_NONE_V;
+    int bi = FIRST_MAX_NONE_I;
+    for (int i = threadIdx.x; i < n; i += 256) first_max(bv, bi, v + i, ix + i);
+    block_first_max_256(bv, bi);
+    if (threadIdx.x == 0) d_top1[blockIdx.x] = bi;
 }
 void argmax_rows_finish_launch(hipStream_t st, const float* val, const int* idx, int n, int n_rows, int32_t* d_top1) {
     hipLaunchKernelGGL(argmax_rows_finish_kernel, dim3(n_rows), dim3(256), 0, st, val, idx, n, d_top1);
@@ -327,15 +287,7 @@ int gemv_rows_launch(hipStream_t st, GemvRowsLaunch& L, const GemvRowsPlan& p) {
     a.njobs = p.njobs, a.K = p.K, a.nBlk = p.nBlk, a.lpr_log2 = p.lpr_log2, a.iters = p.iters, a.gshift = p.gshift;
     a.spw = p.spw, a.total_slots = p.total_slots, a.norm_regs = p.norm_regs;
     a.inv_dim = 1.0f / (float)p.K;
-    for (int j = 0; j < 3; j++) {
-        GemvJob& jb = a.job[j];
-        jb.slot0 = p.slot0[j];
-        if (j >= L.n) continue;
-        const kf_weight* w = L.w[j];
-        jb.w = w->data, jb.M = p.M[j], jb.qBias = w->qBias;
-        jb.zero = jb.step = nullptr;
-        if (p.fmt != FMT_BF16) jb.zero = w->gama + w->ne0 + w->ne1, jb.step = jb.zero + (size_t)w->ne0 * w->ne1 / w->lGroup; /* gemv_launch */
-    }
+    gemv_fill_jobs(a.job, p.slot0, p.M, L.w, L.n, p.fmt);
     if (p.lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds) != hipSuccess) return KF_HIP_CHECK;
     for (int r0 = 0; r0 < L.n_rows; r0 += p.panel_rows) {
         GemvRowsArgs b = a;

@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) norm_rows_kernel(const uint16_t* __restri
         sq = wave_sum_f64_fast(sq);
         s = 1.0f / sqrtf((float)sq / (float)dim + eps);
     } else {
-        s = 1.0f / sqrtf(fmaf((float)acc, 1.0f / (float)dim, eps));
+        s = rms_scale((float)acc, 1.0f / (float)dim, eps);
     }
     uint16_t* yr = y + (size_t)row * dim;
 #pragma unroll
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) rmsnorm_kernel(const uint16_t* __restrict
     const uint16_t* xr = x + (size_t)blockIdx.x * dim;
     uint16_t* yr = y + (size_t)blockIdx.x * dim;
     const double ss = block_sumsq_bf16(xr, dim, red);
-    const float mul = 1.0f / sqrtf(fmaf((float)ss, inv_dim, eps));
+    const float mul = rms_scale((float)ss, inv_dim, eps);
     for (int i = threadIdx.x; i < dim; i += blockDim.x) yr[i] = f2bf((bf2f(xr[i]) * mul) * bf2f(w[i]));
     if (rstd && threadIdx.x == 0) rstd[blockIdx.x] = mul;
 }
@@ -289,7 +289,7 @@ __global__ void swiglu_kernel(const uint16_t* __restrict__ gate, const uint16_t*
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const float g = bf2f(gate[i]), u = bf2f(up[i]);
-        out[i] = f2bf((g * u) / (1.0f + kf_expf(-g)));
+        out[i] = swiglu_bf16(g, u);
     }
 }
 int swiglu_launch(hipStream_t st, const uint16_t* gate, const uint16_t* up, uint16_t* out, int n) {
@@ -298,7 +298,7 @@ int swiglu_launch(hipStream_t st, const uint16_t* gate, const uint16_t* up, uint
 }
 __global__ void add_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b, uint16_t* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = f2bf(bf2f(a[i]) + bf2f(b[i]));
+    if (i < n) out[i] = add_bf16(a[i], b[i]);
 }
 int add_launch(hipStream_t st, const uint16_t* a, const uint16_t* b, uint16_t* out, int n) {
     hipLaunchKernelGGL(add_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, b, out, n);
@@ -481,18 +481,14 @@ __global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict
         const int p = d_state[1];
         if (p + 1 < n_forced && d_forced[p + 1] >= 0) {
             __syncthreads();
-            if (tid == 0) {
-                if (d_tokens_out) d_tokens_out[p] = d_forced[p + 1];
-                d_state[0] = d_forced[p + 1];
-                d_state[1] = p + 1;
-            }
+            if (tid == 0) advance_decode_state(d_state, d_tokens_out, d_forced[p + 1]);
             return;
         }
     }
     if constexpr (!TRUE_TOPK) {
         // first maximum over i >= k-1
-        float bv = -__builtin_inff();
-        int bi = 0x7fffffff;
+        float bv = FIRST_MAX_NONE_V;
+        int bi = FIRST_MAX_NONE_I;
         for (int i = k - 1 + tid; i < n; i += blockDim.x) {
             const float v = bf2f(logits[i]);
             if (v > bv) bv = v, bi = i;
@@ -503,7 +499,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict
             if (tid < m) {
                 const float ov = sv[tid + m];
                 const int oi = si[tid + m];
-                if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) sv[tid] = ov, si[tid] = oi;
+                first_max(sv[tid], si[tid], ov, oi);
             }
             __syncthreads();
         }
@@ -646,12 +642,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(const uint16_t* __restrict
             }
         }
         if (d_token) *d_token = qu;
-        if (d_state) {
-            const int p = d_state[1];
-            if (d_tokens_out) d_tokens_out[p] = qu;
-            d_state[0] = qu;
-            d_state[1] = p + 1;
-        }
+        if (d_state) advance_decode_state(d_state, d_tokens_out, qu);
     }
 }
 int sample_launch(hipStream_t st, const uint16_t* logits, int n, int top_k, float temperature, float top_p, unsigned long long* rng, int32_t* d_token,
@@ -768,28 +759,19 @@ __global__ void __launch_bounds__(1024) argmax_rows_state_kernel(const uint16_t*
     __shared__ float sv[16];
     __shared__ int si[16];
     const uint16_t* row = logits + (size_t)blockIdx.x * ld;
-    float best = -__builtin_inff();
-    int bi = 0x7fffffff;
+    float best = FIRST_MAX_NONE_V;
+    int bi = FIRST_MAX_NONE_I;
     for (int i = threadIdx.x; i < n; i += 1024) { /* ascending i per thread: a strict > keeps the thread's first maximum */
         const float v = bf2f(row[i]);
-        if (v > best || bi == 0x7fffffff) best = v, bi = i;
+        if (v > best || bi == FIRST_MAX_NONE_I) best = v, bi = i;
     }
-    auto better = [](float v, int i, float bv, int bi2) { return v > bv || (v == bv && i < bi2); };
-    for (int m = 32; m > 0; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const int oi = __shfl_xor(bi, m, 64);
-        if (better(ov, oi, best, bi)) best = ov, bi = oi;
-    }
+    wave_first_max(best, bi);
     if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = best, si[threadIdx.x >> 6] = bi;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++)
-            if (better(sv[w], si[w], best, bi)) best = sv[w], bi = si[w];
+        waves_first_max(best, bi, sv, si, 1, 16);
         const int seq = d_seq[blockIdx.x];
-        int32_t* st = states + 4 * (size_t)seq;
-        const int p = st[1];
-        if (tokens_out) tokens_out[(size_t)seq * tokens_stride + p] = bi;
-        st[0] = bi, st[1] = p + 1;
+        advance_decode_state(states + 4 * (size_t)seq, tokens_out ? tokens_out + (size_t)seq * tokens_stride : nullptr, bi);
     }
 }
 int argmax_rows_state_launch(hipStream_t st, const uint16_t* logits, long long ld, int n, int n_rows, const int* d_seq, int32_t* states, int32_t* tokens_out, int tokens_stride) {
@@ -937,7 +919,7 @@ __global__ void tp_reduce_kernel(const float* __restrict__ partials, int R, int 
     float tot = partials[i];
     for (int r = 1; r < R; r++) tot = tot + partials[(size_t)r * n + i];
     uint16_t o = f2bf(tot);
-    if (residual) o = f2bf(bf2f(residual[i]) + bf2f(o));
+    if (residual) o = add_bf16(residual[i], o);
     out[i] = o;
 }
 int tp_reduce_launch(hipStream_t st, const float* partials, int R, int n, const uint16_t* residual, uint16_t* out) {

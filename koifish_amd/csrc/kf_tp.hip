@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) tp_reduce_recv_kernel(const unsigned long
         tot = r == 0 ? p : tot + p;
     }
     uint16_t o = f2bf(tot);
-    if (residual) o = f2bf(bf2f(residual[i]) + bf2f(o));
+    if (residual) o = add_bf16(residual[i], o);
     out[i] = o;
 }
 
@@ -59,26 +59,16 @@ struct TpPeers {
 };
 __global__ void __launch_bounds__(256) tp_argmax_push_kernel(const float* __restrict__ val, const int* __restrict__ idx, int n, int row0, TpPeers peers, int R,
                                                              const unsigned* __restrict__ d_step, unsigned per_step, unsigned index) {
-    float bv = -__builtin_inff();
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float w = val[i];
-        const int jx = idx[i];
-        if (w > bv || (w == bv && jx < bi)) bv = w, bi = jx;
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const float ov = __shfl_xor(bv, m, 64);
-        const int oi = __shfl_xor(bi, m, 64);
-        if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
-    }
-    __shared__ float sv[4];
+    float bv = FIRST_MAX_NONE_V;
+    int bi = FIRST_MAX_NONE_I;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) first_max(bv, bi, val[i], idx[i]);
+    wave_first_max(bv, bi);
+    __shared__ float sv[4]; /* block_first_max_256 with the result in threads 0 .. R - 1: each folds all four waves */
     __shared__ int si[4];
     if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
     __syncthreads();
     if (threadIdx.x < R) {
-        for (int w = 0; w < 4; w++)
-            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) bv = sv[w], bi = si[w];
+        waves_first_max(bv, bi, sv, si, 0, 4);
         const unsigned long long tag = (unsigned long long)(*d_step * per_step + index + 1u) << 32;
         unsigned long long* dst = peers.p[threadIdx.x];
         __hip_atomic_store(dst, tag | __float_as_uint(bv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -99,8 +89,8 @@ __global__ void tp_pick_kernel(const unsigned long long* __restrict__ pairs, int
                                int32_t* __restrict__ d_state, int32_t* __restrict__ d_tokens_out, int* __restrict__ d_err, int vocab) {
     if (threadIdx.x != 0) return;
     const unsigned tag = *d_step * per_step + index + 1u;
-    float bv = -__builtin_inff();
-    int bi = 0x7fffffff;
+    float bv = FIRST_MAX_NONE_V;
+    int bi = FIRST_MAX_NONE_I;
     for (int r = 0; r < R; r++) {
         unsigned long long g[2];
         for (int k = 0; k < 2; k++) {
@@ -114,19 +104,14 @@ __global__ void tp_pick_kernel(const unsigned long long* __restrict__ pairs, int
                 g[k] = tp_load(pairs + 2 * r + k);
             }
         }
-        const float v = __uint_as_float((unsigned)g[0]);
-        const int i = (int)(unsigned)g[1];
-        if (v > bv || (v == bv && i < bi)) bv = v, bi = i;
+        first_max(bv, bi, __uint_as_float((unsigned)g[0]), (int)(unsigned)g[1]);
     }
     // A timed-out exchange (this poll or an earlier one of the step: d_err is set) leaves stale pairs: the decode state is NOT advanced with them -- the id would
     // feed the next step's embedding lookup -- and an index outside the vocabulary is refused the same way.  The generation word still advances, so that every
     // rank keeps forming the same tags; the host sees the error word at its next check (kfh_tp_check) and the ids behind it are void.
     const int err = __hip_atomic_load(d_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (err == 0 && bi >= 0 && bi < vocab) {
-        const int p = d_state[1];
-        if (d_tokens_out) d_tokens_out[p] = bi;
-        d_state[0] = bi;
-        d_state[1] = p + 1;
+        advance_decode_state(d_state, d_tokens_out, bi);
         d_state[2] = bi;
     } else if (err == 0) {
         atomicExch(d_err, 201);

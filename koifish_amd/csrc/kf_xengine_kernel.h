@@ -550,7 +550,7 @@ __device__ __forceinline__ void xe_publish(const XLds& L, int phase, uint32_t ta
                 const uint32_t pr = ob[i];
                 const float gt = bf_lo(pr), up = bf_hi(pr);
                 const bool cold = hot != nullptr && hot[i] != 1; /* (the single-sequence engine and the masked launches publish the same zero) */
-                ob[i] = (tag << 16) | (cold ? 0u : (uint32_t)f2bf((gt * up) / (1.0f + kf_expf(-gt))));
+                ob[i] = (tag << 16) | (cold ? 0u : (uint32_t)swiglu_bf16(gt, up));
             }
         }
         for (int i = 4 * lane; i < nrows; i += 256) {
@@ -598,7 +598,7 @@ __device__ __forceinline__ void xe_tp_reduce(const XArgs& a, const XSeq& S, int 
             float tot = __uint_as_float(g[0][k].x);
 #pragma unroll
             for (int s = 1; s < XE_NXCD; s++) tot = tot + __uint_as_float(g[s][k].x);
-            const uint16_t o = f2bf(bf2f(resid[row0 + i]) + bf2f(f2bf(tot)));
+            const uint16_t o = f2bf(bf2f(resid[row0 + i]) + bf2f(f2bf(tot))); /* add_bf16 spelled out, here and in the two mat-vec epilogues below ("rules stated once") */
             dst_local[i] = (tag16 << 16) | (uint32_t)o;
             if (plain) plain[row0 + i] = o;
         }
@@ -790,7 +790,7 @@ __device__ __forceinline__ void xe_coop_norm_stage(const XArgs& a, const XLds& L
     double tot = 0.0;
 #pragma unroll
     for (int w = 0; w < NWV; w++) tot += L.msc[w];
-    const float mul = 1.0f / sqrtf(fmaf((float)tot, 1.0f / (float)C::DIM, a.eps));
+    const float mul = rms_scale((float)tot, 1.0f / (float)C::DIM, a.eps);
 #pragma unroll
     for (int k = 0; k < NR; k++) {
         const int r = wave + k * NWV;
@@ -798,7 +798,7 @@ __device__ __forceinline__ void xe_coop_norm_stage(const XArgs& a, const XLds& L
             const int e0 = 4 * (r * 64 + lane), q = e0 >> 2, c = q / XCH, j = q - c * XCH;
             const uint32_t o0 = pack_bf16x2((bf_lo(p0[k]) * mul) * bf_lo(wn[k].x), (bf_hi(p0[k]) * mul) * bf_hi(wn[k].x));
             const uint32_t o1 = pack_bf16x2((bf_lo(p1[k]) * mul) * bf_lo(wn[k].y), (bf_hi(p1[k]) * mul) * bf_hi(wn[k].y));
-            xs[j * NBLK + c] = u32x4{o0 << 16, o0 & 0xffff0000u, o1 << 16, o1 & 0xffff0000u};
+            xs[j * NBLK + c] = widen_bf16x4(o0, o1);
         }
     }
 }
@@ -1287,8 +1287,7 @@ __device__ __forceinline__ void xe_head_main(const XArgs& a, const XLds& L, cons
                 if (ll == 0 && i < nmine && row < vocab && (NB == 1 || SS[b].act)) {
                     const uint16_t o = f2bf(v);
                     logits[(size_t)b * XE_NXCD * vocab + row] = o;
-                    const float fv = bf2f(o);
-                    if (fv > best_v[b] || (fv == best_v[b] && row < best_i[b])) best_v[b] = fv, best_i[b] = row;
+                    first_max(best_v[b], best_i[b], bf2f(o), row);
                 }
             }
         }
@@ -1303,10 +1302,10 @@ __device__ __forceinline__ void xe_head_main(const XArgs& a, const XLds& L, cons
 #pragma unroll
     for (int b = 0; b < NB; b++) {
 #pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
+        for (int m = 32; m > 0; m >>= 1) { /* wave_first_max spelled out: through the helper the compiler schedules this kernel differently ("rules stated once") */
             const float ov = __shfl_xor(best_v[b], m, 64);
             const int oi = __shfl_xor(best_i[b], m, 64);
-            if (ov > best_v[b] || (ov == best_v[b] && oi < best_i[b])) best_v[b] = ov, best_i[b] = oi;
+            first_max(best_v[b], best_i[b], ov, oi);
         }
         const XLds Lb = xe_lds_view<C>(L, b);
         float* rv = Lb.wmax;
@@ -1326,8 +1325,7 @@ __device__ __forceinline__ void xe_head_main(const XArgs& a, const XLds& L, cons
         if (wave == 0 && lane == 0) {
             float bv0 = best_v[b];
             int bi0 = best_i[b];
-            for (int k = 1; k < NWV; k++)
-                if (rv[k] > bv0 || (rv[k] == bv0 && ri[k] < bi0)) bv0 = rv[k], bi0 = ri[k];
+            for (int k = 1; k < NWV; k++) first_max(bv0, bi0, rv + k, ri + k);
             hb[wg] = ((unsigned long long)((tag << 16) | (uint32_t)f2bf(bv0)) << 32) | (unsigned long long)(uint32_t)bi0;
         }
         if (wg == 0 && wave == C::NCW + b % C::NP && a.pick) { /* the pick over the decoder's 32 workgroup maxima (sequence b's poller): two granules per lane */
@@ -1344,22 +1342,18 @@ __device__ __forceinline__ void xe_head_main(const XArgs& a, const XLds& L, cons
                 }
                 __builtin_amdgcn_s_sleep(KF_SWEEP_SLEEP);
             }
-            float bv = -__builtin_inff();
-            int bi = 0x7fffffff;
+            float bv = FIRST_MAX_NONE_V;
+            int bi = FIRST_MAX_NONE_I;
             if (mine) {
                 const uint32_t hv[2] = {g0.y, g0.w}, hi[2] = {g0.x, g0.z};
 #pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const float fv = bf2f((uint16_t)(hv[k] & 0xffffu));
-                    const int ix = (int)hi[k];
-                    if (fv > bv || (fv == bv && ix < bi)) bv = fv, bi = ix;
-                }
+                for (int k = 0; k < 2; k++) first_max(bv, bi, bf2f((uint16_t)(hv[k] & 0xffffu)), (int)hi[k]);
             }
 #pragma unroll
             for (int m = 32; m > 0; m >>= 1) {
                 const float ov = __shfl_xor(bv, m, 64);
                 const int oi = __shfl_xor(bi, m, 64);
-                if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+                first_max(bv, bi, ov, oi);
             }
             int vocab_all = vocab;
             if constexpr (C::TP) { /* the rank's maximum (GLOBAL row) to every rank; then the first maximum over the ranks (tp_pick_kernel, kf_tp.hip: lowest row among equals) */
@@ -1383,19 +1377,19 @@ __device__ __forceinline__ void xe_head_main(const XArgs& a, const XLds& L, cons
                     __builtin_amdgcn_s_sleep(KF_SWEEP_SLEEP);
                 }
                 ok = ok && ok2;
-                bv = src ? bf2f((uint16_t)(gb.y & 0xffffu)) : -__builtin_inff(), bi = src ? (int)gb.x : 0x7fffffff;
+                bv = src ? bf2f((uint16_t)(gb.y & 0xffffu)) : FIRST_MAX_NONE_V, bi = src ? (int)gb.x : FIRST_MAX_NONE_I;
 #pragma unroll
                 for (int m = 4; m > 0; m >>= 1) {
                     const float ov = __shfl_xor(bv, m, 64);
                     const int oi = __shfl_xor(bi, m, 64);
-                    if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+                    first_max(bv, bi, ov, oi);
                 }
             }
             if (lane == 0) {
                 const int err = __hip_atomic_load(a.ws + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (ok && err == 0 && bi >= 0 && bi < vocab_all) { /* never advance the decode state on a timed-out hand-off */
                     if (!C::TP || S.seq == 0) { /* TP: every rank knows the id (its next embedding row); rank 0 keeps the books */
-                        int32_t* st = a.d_state + Sb.sq * 4;
+                        int32_t* st = a.d_state + Sb.sq * 4; /* advance_decode_state spelled out: through the helper the compiler lays this kernel out differently ("rules stated once") */
                         const int p = st[1];
                         if (a.d_tokens_out) a.d_tokens_out[(size_t)Sb.sq * a.tokens_stride + p] = bi;
                         st[0] = bi, st[1] = p + 1;
