@@ -69,9 +69,12 @@ typedef struct kf_weight {
      * lGroup / nGroup / qMin / qMax / qBias are not used.  ne1 must be a multiple of 32.
      * The same mode with type = KF_Q3 / KF_Q2 is the 8- / 4-entry form (CU_Q32X_NF3 / CU_Q32X_ / CU_Q22X_, quantizer.cu:690-792): a 3- / 2-bit stream,
      * most significant bit first, 8 weights per 3 / 2 bytes, [LUT ne0 x 8] / [LUT ne0 x 4]; ne1 a multiple of 8.  KF_QUANT_ROW_RTN (type = KF_Q2) is
-     * CU_Q22X_RTN (quantizer.cu:655-688): gama = [R][C][(zero, step) x ne0], weight = bf16(zero + bf16(step * id)).  These three are served the way the
-     * reference serves them -- kf_dequant (GetDataX), and kf_linear as dequant + the bf16 product; kf_quantize builds the 3-bit normal-float form
-     * (RT_NormalF asserts bits == 4 || 3).  CU_Q32X_RTN is not restated: it reads every row from row 0's stream (quantizer.cu:802, no row offset). */
+     * CU_Q22X_RTN (quantizer.cu:655-688): gama = [R][C][(zero, step) x ne0], weight = bf16(zero + bf16(step * id)).  By default these three are served the
+     * way the reference serves them -- kf_dequant (GetDataX), and kf_linear as dequant + the bf16 product; kf_quantize builds the 3-bit normal-float form
+     * (RT_NormalF asserts bits == 4 || 3).  CU_Q32X_RTN is not restated: it reads every row from row 0's stream (quantizer.cu:802, no row offset).
+     * With kf_set_row_unpack they are multiplied from the packed stream (below): STORAGE UNITS -- a row is cut into units of 32 weights, 12 bytes at 3 bits and
+     * 8 bytes at 2; with V = the unit's bytes read as one big-endian integer, weight i (0 .. 31) has id (V >> (93 - 3 i)) & 7, resp. (V >> (62 - 2 i)) & 3
+     * (BIT_SET_k order, no un-biasing), and the value lut[row][id], resp. bf16(zero + bf16(step * id)) formed once per row into a 4-entry table. */
     int32_t quant;
     int32_t reserved_;
 } kf_weight;
@@ -146,6 +149,17 @@ int kf_quantize(kf_ctx* ctx, const kf_weight* w, const kf_bf16* src, int symmetr
  * The reference's own order is cuBLASLt's and unspecified (gemm.cu:126).  Not while capturing. */
 int kf_set_canonical(kf_ctx* ctx, int on);
 int kf_get_canonical(kf_ctx* ctx);
+/* The 3- / 2-bit row forms (KF_QUANT_ROW_LUT with KF_Q3 / KF_Q2, KF_QUANT_ROW_RTN with KF_Q2) unpacked in registers.  0 (the default): every entry treats them as
+ * before -- kf_linear dequantises into the scratch and multiplies the bf16 copy, the fused decode entries refuse them.  1: kf_linear (one token and token batches,
+ * every epilogue), kf_norm_linear (1-3 matrices of one form), kf_norm_gateup_swiglu, kf_linear_multi, kf_qkv_rope_batch / _seqs and kf_gateup_swiglu_batch read
+ * the packed stream once: a lane owns units of 32 weights (kf_weight.quant above), looks four ids up with one v_perm_b32 per byte plane of the row's table, and
+ * sums EXACTLY as it would over the 4-bit row codebook holding the same values (the same ids as nibbles, a 16-entry table whose first 8 / 4 entries are the
+ * row's own): that "4-bit twin" gives the same bits through every one of these entries, in both summation orders, and it is how the launch is planned.
+ * Shape rule: ne1 a multiple of 128, the row tables aligned to their own size (16 / 8 / 4 bytes).  Where it fails kf_linear keeps the dequantise route and the
+ * fused entries refuse with KF_BLAS_UNALIGN.  Not served in either setting: kf_lm_head / kf_norm_lm_head, kf_embed* (TokenEmbed::cuInfer asserts on Q3), the
+ * masked (hot-row) forms, the *_rows entries, the engines.  kf_linear_scratch_bytes does not change.  Not while capturing. */
+int kf_set_row_unpack(kf_ctx* ctx, int on);
+int kf_get_row_unpack(kf_ctx* ctx);
 size_t kf_linear_scratch_bytes(const kf_weight* w, int nTok);
 int kf_set_scratch(kf_ctx* ctx, void* scratch, size_t bytes);
 /* RESIDENT dequantised copies for token batches (prompt prefill).  The reference dequantises a quantised weight in front of EVERY token-batch product

@@ -20,6 +20,7 @@
 #include "kf_gama_plan.h"
 #include "kf_lora_plan.h"
 #include "kf_gradnorm_plan.h"
+#include "kf_rowq.h"
 
 struct kf_ctx {
     int device;
@@ -30,6 +31,7 @@ struct kf_ctx {
     int* amax_idx;
     double* muon_part; /* per-workgroup partial sums of squares of kf_muon_momentum / kf_muon_apply (those entries take no scratch) */
     int canonical;    /* 1: the decode kernels sum in the canonical order of oracle/kf_oracle.c sections 4c / 6 (bit-exact against the oracle; the default); 0: v_dot2c / fp32 forms */
+    int row_unpack;   /* kf_set_row_unpack: 1: the 3- / 2-bit row forms unpack in registers where their 4-bit stand-in (kf_rowq.h) is served; 0 (the default): dequant + bf16 product */
     long long rows_shared, rows_single; /* activation rows the kf_*_rows entries served with the shared unpack / with one-token launches (kf_rows_route_counts) */
     void* scratch;    /* caller-owned workspace of kf_linear (kf_set_scratch): AWQ slice partials, or a weight dequantised to bf16 */
     size_t scratch_bytes;
@@ -106,6 +108,7 @@ int kf_init(int device, void* stream, kf_ctx** out) {
     c->scratch = nullptr, c->scratch_bytes = 0;
     c->arena = nullptr, c->arena_bytes = c->arena_used = 0;
     c->canonical = 1;
+    c->row_unpack = 0;
     *out = c;
     return KF_OK;
 }
@@ -150,6 +153,9 @@ static kf::GemmProblem problem_of(const kf_ctx* c, int entry, int n_w, const kf_
     memset(&P, 0, sizeof(P));
     P.entry = entry, P.n_w = n_w, P.n = n, P.x_al = al16(x);
     for (int i = 0; i < n_w; i++) P.w[i] = kf::mat_of(w[i]);
+    // kf_set_row_unpack: matrices of one 3- / 2-bit row form, every one of them runnable in registers, are planned as the 4-bit row codebooks of their shapes;
+    // otherwise as they are stored (kf_linear's dequantise route, the shared entries' one kf_linear per matrix)
+    if (c->row_unpack) (void)kf::rowq_standins(n_w, w, P.w, true);
     P.scratch = c->scratch ? (long long)c->scratch_bytes : 0;
     P.arena = c->arena != nullptr, P.capturing = c->capturing, P.arena_free = (long long)(c->arena_bytes - c->arena_used);
     for (int f = kf::DEQ_STACK; f <= kf::DEQ_ILV; f++)
@@ -291,7 +297,8 @@ static int check_weight(const kf_weight* w, const char* who) {
         return KF_OK;
     }
     if ((w->quant == KF_QUANT_ROW_LUT && (w->type == KF_Q3 || w->type == KF_Q2)) || (w->quant == KF_QUANT_ROW_RTN && w->type == KF_Q2)) {
-        /* 3- / 2-bit row forms: dequant-only storage (kf_dequant, kf_linear through it, kf_quantize for NF3) */
+        /* 3- / 2-bit row forms: kf_dequant, kf_quantize for NF3, kf_linear through the dequantised copy -- or, with kf_set_row_unpack, unpacked in registers by kf_linear,
+           kf_norm_linear, kf_norm_gateup_swiglu and the token-batch entries (kf_rowq.h) */
         if (!w->gama) return fail(KF_QUANT_ERR, "%s: row-quantised weight without gama", who);
         if (w->ne1 % 8) return fail(KF_BLAS_UNALIGN, "%s: rows of %d weights are not whole 8-weight units", who, w->ne1);
         return KF_OK;
@@ -349,6 +356,13 @@ int kf_set_canonical(kf_ctx* c, int on) {
     return KF_OK;
 }
 int kf_get_canonical(kf_ctx* c) { return c ? c->canonical : 0; }
+int kf_set_row_unpack(kf_ctx* c, int on) {
+    CHKCTX(c);
+    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_set_row_unpack: not while capturing");
+    c->row_unpack = on ? 1 : 0;
+    return KF_OK;
+}
+int kf_get_row_unpack(kf_ctx* c) { return c ? c->row_unpack : 0; }
 int kf_set_dequant_arena(kf_ctx* c, void* arena, size_t bytes) {
     CHKCTX(c);
     if (arena && !al16(arena)) return fail(KF_BLAS_UNALIGN, "kf_set_dequant_arena: unaligned");
@@ -372,7 +386,7 @@ int kf_set_scratch(kf_ctx* c, void* scratch, size_t bytes) {
 static int linear_rows(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta, const kf_bf16* residual) {
     kf::GemvLaunch L;
     init_args(c, L);
-    L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN;
+    L.n = 1, L.w[0] = w, L.mode = kf::GEMV_PLAIN, L.row_unpack = c->row_unpack;
     L.args.bias = bias, L.args.alpha = alpha, L.args.beta = beta;
     const kf::GemvPlan p = kf::gemv_plan(kf::gemv_problem(L));
     for (int t = 0; t < nTok; t++) {
@@ -409,7 +423,8 @@ int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const
     }
     if (p.route == kf::GR_MATVEC) return linear_rows(c, w, x, y, bias, nTok, alpha, beta, res);
     if (p.route == kf::GR_TILE) {
-        const int rc = p.status ? p.status : kf::gemm_launch(c->stream, p.k, kf::gm_operand(w, p.k), x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, res, w->ne0);
+        const kf::GemmKern k = kf::rowq_kern(p.k, c->row_unpack ? kf::rowq_fmt(w) : -1); /* a row form planned as its 4-bit stand-in: the weight's own unpack */
+        const int rc = p.status ? p.status : kf::gemm_launch(c->stream, k, kf::gm_operand(w, k), x, w->ne1, nTok, y, w->ne0, bias, alpha, beta, res, w->ne0);
         return rc ? fail(rc, "kf_linear (token-batch GEMM) failed with %d", rc) : KF_OK;
     }
     // on a bf16 copy: a row form's GetDataX into the scratch, the resident copy (kf_set_dequant_arena), a large batch's dequantise into the scratch
@@ -613,7 +628,7 @@ int kf_norm_linear(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, float eps
     if (!x || !al16(x) || (norm_w && !al16(norm_w))) return fail(KF_BLAS_UNALIGN, "kf_norm_linear: x/norm_w null or unaligned");
     kf::GemvLaunch L;
     init_args(c, L);
-    L.n = n_w, L.mode = kf::GEMV_PLAIN;
+    L.n = n_w, L.mode = kf::GEMV_PLAIN, L.row_unpack = c->row_unpack;
     for (int i = 0; i < n_w; i++) {
         int r = check_weight(w[i], "kf_norm_linear");
         if (r) return r;
@@ -635,7 +650,7 @@ int kf_norm_gateup_swiglu(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, fl
     if (!x || !act || !al16(x)) return fail(KF_BLAS_UNALIGN, "kf_norm_gateup_swiglu: x/act");
     kf::GemvLaunch L;
     init_args(c, L);
-    L.n = 2, L.w[0] = gate, L.w[1] = up, L.mode = kf::GEMV_PAIRED;
+    L.n = 2, L.w[0] = gate, L.w[1] = up, L.mode = kf::GEMV_PAIRED, L.row_unpack = c->row_unpack;
     L.args.x = x, L.args.norm_w = norm_w, L.args.eps = eps, L.args.job[0].y = act;
     RET(kf::gemv_launch(c->stream, L));
 }
@@ -1016,9 +1031,10 @@ static int stacked_launch(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_we
 // GR_FUSED: the direct kernel over the matrices as they are stored
 static int fused_launch(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight* const* w, const kf_bf16* x, int nTok, kf_bf16* const* y) {
     if (p.status) return p.status;
+    const kf::GemmKern k = kf::rowq_kern(p.k, c->row_unpack ? kf::rowq_fmt(w[0]) : -1); /* row forms planned as their 4-bit stand-ins (problem_of): all of one format */
     kf::GmWeight g[3];
-    for (int i = 0; i < n_w; i++) g[i] = kf::gm_operand(w[i], p.k);
-    return kf::gemm_multi_launch(c->stream, p.k, n_w, g, x, w[0]->ne1, nTok, y);
+    for (int i = 0; i < n_w; i++) g[i] = kf::gm_operand(w[i], k);
+    return kf::gemm_multi_launch(c->stream, k, n_w, g, x, w[0]->ne1, nTok, y);
 }
 int kf_qkv_rope_batch(kf_ctx* c, const kf_weight* wq, const kf_weight* wk, const kf_weight* wv, const kf_bf16* x, kf_bf16* q, kf_bf16* k, kf_bf16* v, int nTok, const kf_bf16* wq_norm,
                       const kf_bf16* wk_norm, const float* rope_table, int pos0, int n_head, int n_kv, int hd, float eps) {
@@ -2011,6 +2027,16 @@ int kfdbg_w4a8_tile_plan(const W4A8DbgProblem* P, A8DbgTiles* out) { return (P &
 int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {
     if (!P || !out) return -1;
     *out = kf::gemm_plan(*P);
+    return 0;
+}
+// the 4-bit stand-in kf::rowq_standin plans a 3- / 2-bit row form as (no HIP call): out[8] = status, real format, then the stand-in's type, quant, M, K, gama, al;
+// tests/test_rowq_cpu.py
+int kfdbg_rowq_standin(const kf_weight* w, int* out) {
+    if (!w || !out) return -1;
+    kf::GemmMat m = {};
+    int fmt = -1;
+    out[0] = kf::rowq_standin(w, &m, &fmt), out[1] = fmt;
+    out[2] = m.type, out[3] = m.quant, out[4] = m.M, out[5] = m.K, out[6] = m.gama, out[7] = m.al;
     return 0;
 }
 // the plan kf::gemv_plan makes for a one-token mat-vec problem (no HIP call): tests/test_gemv_plan_cpu.py

@@ -408,6 +408,68 @@ __device__ __forceinline__ u32x4 perm_x_order(u32x4 o) {
                  __builtin_amdgcn_perm(o.w, o.z, 0x07060302u)};
 }
 
+// ---- 8- / 4-entry bf16 row tables in registers (the 3- / 2-bit row forms, include/kf_abi.h "storage units"): a low-byte and a high-byte plane of NE / 4 dwords
+// each, so ONE v_perm_b32 per plane looks four weights up (the 16-entry lookup above needs two and a select).  The pair words come out as perm_dot_dword_nat forms
+// them -- (e0, e1), (e2, e3), ... in index order -- so a product over them sums exactly as the 4-bit row codebook holding the same values.
+struct RowTab {
+    uint32_t tl[2], th[2];
+};
+// p: the table's entries as pair words (entries 2i, 2i + 1 in word i); NE = 8: p.x .. p.w, NE = 4: p.x, p.y
+template <int NE>
+__device__ __forceinline__ RowTab row_tab(u32x4 p) {
+    RowTab t;
+    t.tl[0] = __builtin_amdgcn_perm(p.y, p.x, 0x06040200u), t.th[0] = __builtin_amdgcn_perm(p.y, p.x, 0x07050301u);
+    t.tl[1] = NE == 8 ? __builtin_amdgcn_perm(p.w, p.z, 0x06040200u) : 0u, t.th[1] = NE == 8 ? __builtin_amdgcn_perm(p.w, p.z, 0x07050301u) : 0u;
+    return t;
+}
+// row RTN (CU_Q22X_RTN): zs = {zero | step << 16}; entry id = bf16(zero + bf16(step * id)), every operator a bf16 operator (row_dequant_kernel<2, true>, kf_lut.hip)
+__device__ __forceinline__ RowTab row_tab_rtn(uint32_t zs) {
+    const float zero = bf_lo(zs), step = bf_hi(zs);
+    const uint32_t m01 = pack_bf16x2(step * 0.0f, step * 1.0f), m23 = pack_bf16x2(step * 2.0f, step * 3.0f);
+    return row_tab<4>(u32x4{pack_bf16x2(zero + bf_lo(m01), zero + bf_hi(m01)), pack_bf16x2(zero + bf_lo(m23), zero + bf_hi(m23)), 0u, 0u});
+}
+// v: eight ids of BITS bits, most significant first, in the low 8 * BITS bits -> the four pair words of the eight weights
+template <int BITS>
+__device__ __forceinline__ u32x4 row_pairs8(uint32_t v, const RowTab& t) {
+    constexpr uint32_t m = (1u << BITS) - 1u;
+    u32x4 o;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const int e0 = 4 * half; /* index bytes 0..3 = elements e0 .. e0 + 3 */
+        const uint32_t s = ((v >> (BITS * (7 - e0))) & m) | (((v >> (BITS * (6 - e0))) & m) << 8) | (((v >> (BITS * (5 - e0))) & m) << 16) | (((v >> (BITS * (4 - e0))) & m) << 24);
+        const uint32_t lo = __builtin_amdgcn_perm(t.tl[1], t.tl[0], s), hi = __builtin_amdgcn_perm(t.th[1], t.th[0], s);
+        const uint32_t p0 = __builtin_amdgcn_perm(hi, lo, 0x05010400u), p1 = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+        if (half == 0) o.x = p0, o.y = p1;
+        else o.z = p0, o.w = p1;
+    }
+    return o;
+}
+// weights 8 c .. 8 c + 7 of a unit of 32 (b: its 12 / 8 bytes as little-endian dwords; the unit is one big-endian integer, weight 0 on top): their ids for row_pairs8
+template <int BITS>
+__device__ __forceinline__ uint32_t row_unit_ids8(u32x4 b, int c) {
+    if constexpr (BITS == 3) /* bytes 3 c .. 3 c + 2, first byte on top */
+        return c == 0 ? __builtin_amdgcn_perm(b.y, b.x, 0x0c000102u) : (c == 1 ? __builtin_amdgcn_perm(b.y, b.x, 0x0c030405u) : (c == 2 ? __builtin_amdgcn_perm(b.z, b.y, 0x0c020304u) : __builtin_amdgcn_perm(0u, b.z, 0x0c010203u)));
+    else /* bytes 2 c, 2 c + 1 */
+        return c == 0 ? __builtin_amdgcn_perm(0u, b.x, 0x0c0c0001u) : (c == 1 ? __builtin_amdgcn_perm(0u, b.x, 0x0c0c0203u) : (c == 2 ? __builtin_amdgcn_perm(0u, b.y, 0x0c0c0001u) : __builtin_amdgcn_perm(0u, b.y, 0x0c0c0203u)));
+}
+// a unit of 12 / 8 bytes, 4-byte aligned, streamed once
+struct __attribute__((packed, aligned(4))) U32x3A4 {
+    uint32_t x, y, z;
+};
+struct __attribute__((packed, aligned(4))) U32x2A4 {
+    uint32_t x, y;
+};
+template <int BYTES>
+__device__ __forceinline__ u32x4 ld_unit(const unsigned char* p) {
+    if constexpr (BYTES == 12) {
+        const U32x3A4 v = *reinterpret_cast<const U32x3A4*>(p);
+        return u32x4{v.x, v.y, v.z, 0u};
+    } else {
+        const U32x2A4 v = *reinterpret_cast<const U32x2A4*>(p);
+        return u32x4{v.x, v.y, 0u, 0u};
+    }
+}
+
 // quad broadcast (DPP quad_perm k,k,k,k): every lane of an aligned group of 4 gets lane k's value
 template <int K>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {

@@ -87,6 +87,44 @@ struct WTile<FMT_Q4R, KS> {
         return u32x4{o.x & keep, o.y & keep, o.z & keep, o.w & keep};
     }
 };
+// 3- / 2-bit row forms (kf_set_row_unpack): the units of 32 weights take the place of the 4-bit row codebook's blocks -- the same element ranges per lane, the same
+// fragments as frag_q4r forms from the nibble stream of the same ids -- in 12 / 8 bytes each; the row's 8 / 4 entries (row RTN: its (zero, step)) ride along
+template <int FMT, int KS>
+struct WTileRowQ {
+    static constexpr int NP = 2 / KS, BITS = FMT == FMT_Q3R ? 3 : 2, UB = rowq_unit_bytes(FMT);
+    u32x4 b[NP];
+    u32x4 ta;
+    bool in[NP];
+    __device__ __forceinline__ void load(const GemmArgs& a, int row, int it, int h, int ks) {
+        if constexpr (FMT == FMT_Q3R) ta = reinterpret_cast<const u32x4*>(a.zero)[row]; /* a.zero carries the table base */
+        else if constexpr (FMT == FMT_Q2R) {
+            const u32x2 v = reinterpret_cast<const u32x2*>(a.zero)[row];
+            ta = u32x4{v.x, v.y, 0u, 0u};
+        } else ta = u32x4{reinterpret_cast<const uint32_t*>(a.zero)[row], 0u, 0u, 0u};
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            int bi = it * 4 + 2 * (ks * NP + p) + h;
+            const bool in_row = bi < a.nBlk;
+            if (!in_row) bi = a.nBlk - 1;
+            b[p] = ld_unit<UB>(a.w + ((size_t)row * (size_t)a.nBlk + (size_t)bi) * UB);
+            in[p] = in_row;
+        }
+    }
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&) const {
+        const int p = sl >> 2, c = sl & 3;
+        const RowTab t = FMT == FMT_Q2N ? row_tab_rtn(ta.x) : row_tab<(1 << BITS)>(ta);
+        const u32x4 o = row_pairs8<BITS>(row_unit_ids8<BITS>(b[p], c), t);
+        const uint32_t keep = in[p] ? 0xffffffffu : 0u;
+        return u32x4{o.x & keep, o.y & keep, o.z & keep, o.w & keep};
+    }
+};
+template <int KS>
+struct WTile<FMT_Q3R, KS> : WTileRowQ<FMT_Q3R, KS> {};
+template <int KS>
+struct WTile<FMT_Q2R, KS> : WTileRowQ<FMT_Q2R, KS> {};
+template <int KS>
+struct WTile<FMT_Q2N, KS> : WTileRowQ<FMT_Q2N, KS> {};
 template <int KS>
 struct WTile<FMT_BF16, KS> {
     static constexpr int NP = 2 / KS;
@@ -497,6 +535,9 @@ static int gemm_run(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* 
         case FMT_Q4: gm_launch<FMT_Q4>(k, a, st); break;
         case FMT_Q2: gm_launch<FMT_Q2>(k, a, st); break;
         case FMT_Q4R: gm_launch<FMT_Q4R>(k, a, st); break;
+        case FMT_Q3R: gm_launch<FMT_Q3R>(k, a, st); break;
+        case FMT_Q2R: gm_launch<FMT_Q2R>(k, a, st); break;
+        case FMT_Q2N: gm_launch<FMT_Q2N>(k, a, st); break;
         default: gm_launch<FMT_Q1>(k, a, st); break;
     }
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
@@ -505,7 +546,7 @@ static int gemm_run(hipStream_t st, const GemmKern& k, const GemmArgs& a, void* 
 GmWeight gm_operand(const kf_weight* w, const GemmKern& k) {
     GmWeight g = gm_bf16(w->data, w->ne0, w->ne1);
     g.qBias = (float)w->qBias;
-    if (k.fmt == FMT_Q4R) {
+    if (k.fmt == FMT_Q4R || fmt_rowq(k.fmt)) {
         g.zero = w->gama + w->ne0 + w->ne1; /* the rows' tables */
     } else if (k.fmt >= FMT_Q4) {
         g.zero = w->gama + w->ne0 + w->ne1;
@@ -516,7 +557,7 @@ GmWeight gm_operand(const kf_weight* w, const GemmKern& k) {
 static void gm_base(GemmArgs& a, const GemmKern& k, const GmWeight& g, const uint16_t* x, long long ldx, int n, uint16_t* y, long long ldy) {
     memset(&a, 0, sizeof(a));
     a.w = g.w, a.zero = g.zero, a.step = g.step, a.qBias = g.qBias;
-    a.M = g.M, a.K = g.K, a.nBlk = g.K / GM_EPB[k.fmt], a.gshift = k.gshift;
+    a.M = g.M, a.K = g.K, a.nBlk = g.K / (fmt_rowq(k.fmt) ? 32 : GM_EPB[k.fmt]), a.gshift = k.gshift;
     a.x = x, a.ldx = ldx, a.n = n, a.y = y, a.ldy = ldy, a.alpha = 1.0f, a.njobs = 1;
     a.rb_end[0] = a.rb_end[1] = a.rb_end[2] = (g.M + 31) / 32;
 }

@@ -1,6 +1,7 @@
 // kf_gemv.hip -- the one-token mat-vec launcher: a GemvLaunch becomes a problem, kf::gemv_plan (kf_gemv_plan.h) decides, this file carries the plan out with the
 // v_dot2c_f32_bf16 instantiations of gemv_kernel (kf_gemv_kernel.h) or, in the canonical order, with kf_gemv_canon.hip's; and the arg-max pick behind the LM head.
 #include "kf_gemv_kernel.h"
+#include "kf_rowq.h"
 
 namespace kf {
 
@@ -42,6 +43,9 @@ GemvProblem gemv_problem(const GemvLaunch& L) {
     GemvProblem P = {};
     P.mode = L.mode, P.n_w = L.n;
     for (int j = 0; j < L.n; j++) P.w[j] = mat_of(L.w[j]);
+    // the 3- / 2-bit row forms behind kf_set_row_unpack: planned as 4-bit row codebooks of their shape (plain and paired launches; the arg-max and sparse forms refuse
+    // them as they are)
+    if (L.row_unpack && L.mode != GEMV_ARGMAX && !L.args.row_map) (void)rowq_standins(L.n, L.w, P.w, false);
     P.sparse = L.args.row_map != nullptr, P.n_hot = L.n_hot;
     P.norm = L.args.norm_w != nullptr, P.canon = L.canon != 0;
     P.q4_perm = g_knobs.q4_perm != 0, P.q2_tab = g_knobs.q2_tab != 0, P.q1_tab = g_knobs.q1_tab != 0, P.xf2 = g_knobs.gemv_xf2 != 0;
@@ -50,13 +54,15 @@ GemvProblem gemv_problem(const GemvLaunch& L) {
 
 int gemv_launch(hipStream_t st, GemvLaunch& L, const GemvPlan& p) {
     if (p.status) return p.status;
+    GemvPlan q = p;
+    if (L.row_unpack && p.fmt == FMT_Q4R && rowq_fmt(L.w[0]) >= 0) q.fmt = rowq_fmt(L.w[0]); /* the stand-in's plan, the weight's own unpack */
     GemvArgs& a = L.args;
     a.njobs = p.njobs, a.K = p.K, a.nBlk = p.nBlk, a.lpr_log2 = p.lpr_log2, a.iters = p.iters, a.lGroup = p.lgroup, a.gshift = p.gshift;
     a.spw = p.spw, a.total_slots = p.total_slots, a.stream_ok = p.stream_ok;
     a.inv_dim = 1.0f / (float)p.K;
-    gemv_fill_jobs(a.job, p.slot0, p.M, L.w, L.n, p.fmt);
+    gemv_fill_jobs(a.job, p.slot0, p.M, L.w, L.n, q.fmt);
     L.blocks = p.grid;
-    return p.canon ? gemv_dispatch_canon(p, a, st) : gemv_dispatch_dot2(p, a, st);
+    return p.canon ? gemv_dispatch_canon(q, a, st) : gemv_dispatch_dot2(q, a, st);
 }
 
 }  // namespace kf

@@ -179,6 +179,36 @@ struct BlockDot<FMT_Q4R, CANON> {
     }
 };
 
+// 3- / 2-bit row forms (CU_Q32X_NF3 / CU_Q32X_ / CU_Q22X_ / CU_Q22X_RTN, quantizer.cu:690-792; kf_set_row_unpack): a "block" is a unit of 32 weights -- 12 / 8 bytes of
+// the most-significant-bit-first stream, in w.x .. w.z / w.x, w.y -- and the row's 8 / 4 entries (row RTN: its (zero, step)) ride in ta.  Same x chunks, same pair
+// words in the same order as BlockDot<FMT_Q4R> on the nibble stream of the same ids: every output bit is that form's (kf_device.h row_pairs8).
+template <int FMT, bool CANON>
+struct BlockDotRowQ {
+    static constexpr int EPB = 32, XCH = 4, BITS = FMT == FMT_Q3R ? 3 : 2;
+    static constexpr bool HAS_GAMA = false;
+    using Acc = acc_t<CANON>;
+    __device__ static __forceinline__ acc_t<CANON> run(u32x4, const u32x4*, int, int, float, float, float, acc_t<CANON> acc) { return acc; }
+    __device__ static __forceinline__ RowTab table(u32x4 ta) { return FMT == FMT_Q2N ? row_tab_rtn(ta.x) : row_tab<(1 << BITS)>(ta); }
+    __device__ static __forceinline__ acc_t<CANON> run_lut(u32x4 w, const u32x4* xs, int col, int nBlk, u32x4 ta, u32x4, acc_t<CANON> acc) {
+        const RowTab t = table(ta);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const u32x4 p = row_pairs8<BITS>(row_unit_ids8<BITS>(w, c), t), X = xs[c * nBlk + col];
+            acc = dotp<CANON>(p.x, X.x, acc);
+            acc = dotp<CANON>(p.y, X.y, acc);
+            acc = dotp<CANON>(p.z, X.z, acc);
+            acc = dotp<CANON>(p.w, X.w, acc);
+        }
+        return acc;
+    }
+};
+template <bool CANON>
+struct BlockDot<FMT_Q3R, CANON> : BlockDotRowQ<FMT_Q3R, CANON> {};
+template <bool CANON>
+struct BlockDot<FMT_Q2R, CANON> : BlockDotRowQ<FMT_Q2R, CANON> {};
+template <bool CANON>
+struct BlockDot<FMT_Q2N, CANON> : BlockDotRowQ<FMT_Q2N, CANON> {};
+
 // 2-bit (T_SIGN ternary / generic CU_Q128toX_<T,64>): element i < 32 at high >> (62-2i) (PackedQ.hpp:185-226):
 // dword3 -> elements 0..15 (element 0 in bits 30..31), dword2 -> 16..31, dword1 -> 32..47, dword0 -> 48..63.
 template <bool CANON>
@@ -582,8 +612,8 @@ inline void gemv_fill_jobs(GemvJob* job, const int* slot0, const int* M, const k
         if (j >= n) continue;
         jb.w = w[j]->data, jb.M = M[j], jb.qBias = w[j]->qBias;
         jb.zero = jb.step = nullptr;
-        if (fmt >= FMT_Q4) jb.zero = w[j]->gama + w[j]->ne0 + w[j]->ne1; /* gama_T(ZERO), GTensor.cpp:456-510; FMT_Q4R: the row codebooks, 16 entries per row */
-        if (fmt >= FMT_Q4 && fmt != FMT_Q4R) jb.step = jb.zero + (size_t)w[j]->ne0 * w[j]->ne1 / w[j]->lGroup;
+        if (fmt >= FMT_Q4) jb.zero = w[j]->gama + w[j]->ne0 + w[j]->ne1; /* gama_T(ZERO), GTensor.cpp:456-510; FMT_Q4R: the row codebooks, 16 entries per row; the 3- / 2-bit row forms: 8 / 4 / 2 */
+        if (fmt >= FMT_Q4 && fmt != FMT_Q4R && !fmt_rowq(fmt)) jb.step = jb.zero + (size_t)w[j]->ne0 * w[j]->ne1 / w[j]->lGroup;
     }
 }
 

@@ -24,12 +24,12 @@
 
 namespace kf {
 
-template <int G, bool PAIRED, bool LUT>
+template <int G, bool PAIRED, bool LUT, bool LUT16 = LUT>
 struct Batch {
     u32x4 w[G];
     u32x4 w2[PAIRED ? G : 1];
-    u32x4 ta[LUT ? G : 1], tb[LUT ? G : 1];                       /* row codebook (FMT_Q4R) */
-    u32x4 ta2[LUT && PAIRED ? G : 1], tb2[LUT && PAIRED ? G : 1];
+    u32x4 ta[LUT ? G : 1], tb[LUT16 ? G : 1];                     /* row codebook (FMT_Q4R: 16 entries in ta | tb; the 3- / 2-bit row forms: ta alone) */
+    u32x4 ta2[LUT && PAIRED ? G : 1], tb2[LUT16 && PAIRED ? G : 1];
     // zero / step stay raw bf16 bits until the block is multiplied: converted when loaded, the shift makes the wave wait for the loads it has
     // just issued (s_waitcnt vmcnt right behind the prefetch) instead of overlapping them with the current batch's arithmetic
     uint16_t st[G], ze[G];
@@ -48,7 +48,8 @@ struct Batch {
 template <int FMT, int G, int MODE, bool SPARSE, bool ONEJOB, bool CANON, bool XF_ = false, bool XF2_ = false>
 __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     using BD = BlockDot<FMT, CANON>;
-    constexpr bool PAIRED = (MODE == GEMV_PAIRED), LUT = (FMT == FMT_Q4R), XF = XF_ && CANON && (FMT == FMT_Q4 || FMT == FMT_Q4P);
+    constexpr bool PAIRED = (MODE == GEMV_PAIRED), ROWQ = fmt_rowq(FMT), LUT16 = (FMT == FMT_Q4R), LUT = LUT16 || ROWQ, XF = XF_ && CANON && (FMT == FMT_Q4 || FMT == FMT_Q4P);
+    using BatchT = Batch<G, PAIRED, LUT, LUT16>;
     constexpr bool XF2 = XF2_ && XF && G == 1 && !PAIRED && !SPARSE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* xs = reinterpret_cast<u32x4*>(smem_raw);
@@ -101,7 +102,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     // wait for x, which is requested FIRST so that its staging overlaps the weights' HBM latency.  Long launches (G > 1) are bound by
     // the dequant arithmetic and hide latency with resident waves: they keep the masked loads (no per-step mask arithmetic).
     constexpr bool LAT = (G == 1);
-    auto load = [&](int bi, int it, Batch<G, PAIRED, LUT>& b) {
+    auto load = [&](int bi, int it, BatchT& b) {
         const long s0 = s_begin + (long)bi * G;
         int col = it * LPR + ll;
         const bool col_ok = col < nBlk;
@@ -118,22 +119,43 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                 b.st[g] = b.ze[g] = 0;
                 if (PAIRED) b.w2[g] = u32x4{0, 0, 0, 0}, b.st2[g] = b.ze2[g] = 0;
                 if constexpr (LUT) {
-                    b.ta[g] = b.tb[g] = u32x4{0, 0, 0, 0};
-                    if constexpr (PAIRED) b.ta2[g] = b.tb2[g] = u32x4{0, 0, 0, 0};
+                    b.ta[g] = u32x4{0, 0, 0, 0};
+                    if constexpr (PAIRED) b.ta2[g] = u32x4{0, 0, 0, 0};
+                }
+                if constexpr (LUT16) {
+                    b.tb[g] = u32x4{0, 0, 0, 0};
+                    if constexpr (PAIRED) b.tb2[g] = u32x4{0, 0, 0, 0};
                 }
             }
             if (LAT || ok) {
                 if constexpr (SPARSE) row = a.row_map[row]; /* sparse forward: the slot's row is the row-th hot row (one dependent, wave-uniform-per-group load).  A template
                                                               parameter: as a run-time branch its join carried an s_waitcnt vmcnt(0) that drained the weight stream of every launch */
                 const uint32_t bidx = (uint32_t)row * (uint32_t)nBlk + (uint32_t)col; /* < 2^32 blocks = 64 GiB per tensor */
-                b.w[g] = ld_nt(jw + bidx);
-                if (PAIRED) b.w2[g] = ld_nt(jw2 + bidx);
+                if constexpr (ROWQ) { /* a unit of 12 / 8 bytes; consecutive lanes read consecutive units (rows start 16-byte aligned: K a multiple of 128) */
+                    constexpr int UB = rowq_unit_bytes(FMT);
+                    b.w[g] = ld_unit<UB>(reinterpret_cast<const unsigned char*>(jw) + (size_t)bidx * UB);
+                    if constexpr (PAIRED) b.w2[g] = ld_unit<UB>(reinterpret_cast<const unsigned char*>(jw2) + (size_t)bidx * UB);
+                } else {
+                    b.w[g] = ld_nt(jw + bidx);
+                    if (PAIRED) b.w2[g] = ld_nt(jw2 + bidx);
+                }
                 if (BD::HAS_GAMA) {
                     const uint32_t gi = bidx >> gshift; /* group = element / lGroup, lGroup / EPB a power of two */
                     b.st[g] = jstep[gi], b.ze[g] = jzero[gi];
                     if (PAIRED) b.st2[g] = a.job[1].step[gi], b.ze2[g] = a.job[1].zero[gi];
                 }
-                if constexpr (LUT) { /* job.zero carries the table base: 16 bf16 per row */
+                if constexpr (ROWQ) { /* job.zero carries the table base: 8 / 4 / 2 bf16 per row, aligned to their size */
+                    auto tab = [&](const uint16_t* base) -> u32x4 {
+                        if constexpr (FMT == FMT_Q3R) return reinterpret_cast<const u32x4*>(base)[row];
+                        else if constexpr (FMT == FMT_Q2R) {
+                            const u32x2 v = reinterpret_cast<const u32x2*>(base)[row];
+                            return u32x4{v.x, v.y, 0u, 0u};
+                        } else return u32x4{reinterpret_cast<const uint32_t*>(base)[row], 0u, 0u, 0u};
+                    };
+                    b.ta[g] = tab(jzero);
+                    if constexpr (PAIRED) b.ta2[g] = tab(a.job[1].zero);
+                }
+                if constexpr (LUT16) { /* job.zero carries the table base: 16 bf16 per row */
                     const u32x4* lt = reinterpret_cast<const u32x4*>(jzero) + 2 * (size_t)row;
                     b.ta[g] = lt[0], b.tb[g] = lt[1];
                     if constexpr (PAIRED) {
@@ -166,7 +188,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
             }
         }
     }
-    auto sload = [&](int bi, int it, Batch<G, PAIRED, LUT>& b) {
+    auto sload = [&](int bi, int it, BatchT& b) {
         if constexpr (STREAM) {
             const int col = it * LPR + ll;
             const uint32_t row0 = (uint32_t)((int)(s_begin - jslot0) + bi * G) * (uint32_t)RPS + (uint32_t)sub;
@@ -198,8 +220,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
         if (has_norm) n0 = *reinterpret_cast<const u32x4*>(a.norm_w + c0 * 8), n1 = *reinterpret_cast<const u32x4*>(a.norm_w + c1 * 8);
     }
 
-    Batch<G, PAIRED, LUT> cur, nxt;
-    [[maybe_unused]] Batch<G, PAIRED, LUT> ring[XF2 ? RD : 1];
+    BatchT cur, nxt;
+    [[maybe_unused]] BatchT ring[XF2 ? RD : 1];
     if constexpr (XF2) {
 #pragma unroll
         for (int d = 0; d < RD; d++) load(0, d < iters ? d : iters - 1, ring[d]);
@@ -277,7 +299,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     float sum[G], sum2[PAIRED ? G : 1];
     int bi = 0, it = 0;       // the step being computed
     int nbi = 0, nit = 0;     // the step being loaded
-    auto compute = [&](const Batch<G, PAIRED, LUT>& bt) {
+    auto compute = [&](const BatchT& bt) {
         if (it == 0) {
 #pragma unroll
             for (int g = 0; g < G; g++) {
@@ -294,10 +316,10 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                 int row;
                 const bool ok = !LAT || (slot(s_begin + (long)bi * G + g, row) && col_ok); /* masked loads carry zero weights */
                 if constexpr (LUT) {
-                    const Acc r = BD::run_lut(bt.w[g], xs, col, nBlk, bt.ta[g], bt.tb[g], acc[g]);
+                    const Acc r = BD::run_lut(bt.w[g], xs, col, nBlk, bt.ta[g], bt.tb[LUT16 ? g : 0], acc[g]);
                     acc[g] = acc_pick(ok, r, acc[g]);
                     if constexpr (PAIRED) {
-                        const Acc r2 = BD::run_lut(bt.w2[g], xs, col, nBlk, bt.ta2[g], bt.tb2[g], acc2[g]);
+                        const Acc r2 = BD::run_lut(bt.w2[g], xs, col, nBlk, bt.ta2[g], bt.tb2[LUT16 ? g : 0], acc2[g]);
                         acc2[g] = acc_pick(ok, r2, acc2[g]);
                     }
                 } else {
@@ -432,13 +454,14 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
 // arg-max, the sparse plain and paired forms); XF for the canonical 4-bit forms, XF2 for their plain one-matrix G = 1 launches
 constexpr bool gemv_form_exists(bool canon, int fmt, int G, int mode, bool sparse, bool onejob, bool xf, bool xf2) {
     if (sparse && mode == GEMV_ARGMAX) return false;
+    if (fmt_rowq(fmt) && (sparse || mode == GEMV_ARGMAX || xf)) return false; /* the 3- / 2-bit row forms: plain (1-3 matrices) and paired launches only */
     if (mode == GEMV_PAIRED ? onejob : (!onejob && (mode == GEMV_ARGMAX || sparse))) return false; /* paired: job 1 by name; arg-max and sparse: one matrix */
     if (xf && !(canon && (fmt == FMT_Q4 || fmt == FMT_Q4P))) return false;
     return !xf2 || (xf && mode == GEMV_PLAIN && !sparse && onejob && G == 1);
 }
-// the table index: one digit per template parameter, its stride named below -- fmt (9 FMT_*) x G (1 / 2 / 4 as 0 / 1 / 2) x mode (3) x sparse x onejob x xf x xf2;
+// the table index: one digit per template parameter, its stride named below -- fmt (12 FMT_*) x G (1 / 2 / 4 as 0 / 1 / 2) x mode (3) x sparse x onejob x xf x xf2;
 // gemv_form_index composes an index from a plan, gemv_form's defaults take one apart with the same strides
-constexpr int GF_XF2 = 1, GF_XF = 2, GF_ONEJOB = 4, GF_SPARSE = 8, GF_MODE = 16, GF_G = 3 * GF_MODE, GF_FMT = 3 * GF_G, GEMV_FORMS = 9 * GF_FMT;
+constexpr int GF_XF2 = 1, GF_XF = 2, GF_ONEJOB = 4, GF_SPARSE = 8, GF_MODE = 16, GF_G = 3 * GF_MODE, GF_FMT = 3 * GF_G, GEMV_FORMS = 12 * GF_FMT;
 constexpr int gemv_form_index(int fmt, int G, int mode, bool sparse, bool onejob, bool xf, bool xf2) {
     return fmt * GF_FMT + (G >> 1) * GF_G + mode * GF_MODE + sparse * GF_SPARSE + onejob * GF_ONEJOB + xf * GF_XF + xf2 * GF_XF2;
 }

@@ -189,6 +189,7 @@ struct GemvLaunch {
     int mode;
     int n_hot;  /* args.row_map != NULL: number of entries */
     int canon;  /* the canonical summation order (one v_pk_fma_f32 per weight pair: an even and an odd chain per lane; oracle/kf_oracle.c section 4c) instead of v_dot2c_f32_bf16 */
+    int row_unpack; /* kf_set_row_unpack: 3- / 2-bit row forms are planned as their 4-bit stand-in (kf_rowq.h) and run in registers; 0: refused as ever */
     int blocks; /* out */
 };
 GemvProblem gemv_problem(const GemvLaunch& L); /* what L asks for, with the process's knobs */

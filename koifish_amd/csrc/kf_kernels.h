@@ -10,9 +10,17 @@ enum {
     FMT_Q4P = 5, /* 4-bit through the register-table lookup (mat-vec only) */
     FMT_Q4R = 6, /* 4-bit row codebook (KF_QUANT_ROW_LUT): byte-packed nibbles + 16 bf16 table entries per row */
     FMT_Q1T = 7, /* 1-bit through an LDS table of v_perm selectors (mat-vec only; bit-identical to FMT_Q1) */
-    FMT_Q2T = 8  /* 2-bit, the same way (bit-identical to FMT_Q2) */
+    FMT_Q2T = 8, /* 2-bit, the same way (bit-identical to FMT_Q2) */
+    // 3- / 2-bit row forms unpacked in registers (kf_set_row_unpack; units of 32 weights, include/kf_abi.h): never named by a plan -- an entry plans the weight as the
+    // 4-bit row codebook of its shape (kf_rowq.h) and launches the FMT_Q4R form's kernel in one of these
+    FMT_Q3R = 9,  /* 8-entry row codebook (KF_Q3 + KF_QUANT_ROW_LUT): 12 bytes per unit */
+    FMT_Q2R = 10, /* 4-entry row codebook (KF_Q2 + KF_QUANT_ROW_LUT): 8 bytes per unit */
+    FMT_Q2N = 11  /* 2-bit row RTN (KF_Q2 + KF_QUANT_ROW_RTN): the row's (zero, step) becomes a 4-entry table when it is loaded */
 };
-inline bool is_row_lut(const kf_weight* w) { return w->quant != KF_QUANT_GROUP; } /* any row-wise card (kf_lut.hip); the mat-vec kernel takes Q4 + ROW_LUT only */
+constexpr bool fmt_rowq(int fmt) { return fmt >= FMT_Q3R && fmt <= FMT_Q2N; }
+constexpr int rowq_unit_bytes(int fmt) { return fmt == FMT_Q3R ? 12 : 8; }                     /* a unit of 32 weights in the stream */
+constexpr int rowq_tab_elems(int fmt) { return fmt == FMT_Q3R ? 8 : (fmt == FMT_Q2R ? 4 : 2); } /* bf16 elements of a row's table */
+inline bool is_row_lut(const kf_weight* w) { return w->quant != KF_QUANT_GROUP; } /* any row-wise card (kf_lut.hip); the mat-vec kernel takes Q4 + ROW_LUT, and the 3- / 2-bit forms behind kf_set_row_unpack */
 enum { GEMV_PLAIN = 0, GEMV_PAIRED = 1, GEMV_ARGMAX = 2 };
 constexpr int KF_MAX_ARGMAX_PARTIALS = 4096;
 constexpr int KF_ATTN_MAX_SPLITS = 32;

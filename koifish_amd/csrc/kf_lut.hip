@@ -131,7 +131,9 @@ __global__ void __launch_bounds__(256) lut_dequant_kernel(const uint32_t* __rest
     const size_t row = i / (size_t)words_per_row;
     *reinterpret_cast<u32x4*>(out + i * 8) = lut_unpack8(data[i], lut + row * 16);
 }
-// 3- and 2-bit row forms (CU_Q32X_NF3 / CU_Q32X_ / CU_Q22X_ / CU_Q22X_RTN): one thread per 8 weights = BITS bytes of the stream, most significant bit first
+// 3- and 2-bit row forms (CU_Q32X_NF3 / CU_Q32X_ / CU_Q22X_ / CU_Q22X_RTN): one thread per 8 weights = BITS bytes of the stream, most significant bit first.  GetDataX of
+// these storages; the products over them read the same stream in registers with kf_set_row_unpack (kf_device.h row_unit_ids8 / row_pairs8 restate this unpack per unit of
+// 32 weights, and row_tab_rtn the RTN arithmetic below)
 template <int BITS, bool RTN>
 __global__ void __launch_bounds__(256) row_dequant_kernel(const unsigned char* __restrict__ data, const uint16_t* __restrict__ tab, int units_per_row, size_t nunits,
                                                           uint16_t* __restrict__ out) {

@@ -453,6 +453,14 @@ std::array<SLP*, 7> Fish::LayerMatrices(int l) const {
     FFN* m = ffn[l].get();
     return {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
 }
+static bool is_row3(const hGTensor& t) { return t && t->quant.isNormalFloat && t->type == typNUMBER::Q3; }
+static const char* kRow3Why = "a layer matrix is a 3-bit row codebook (NF3): such layers run on the per-layer launches (kf_set_row_unpack), not in this path";
+bool Fish::HasRow3() const {
+    for (int l = 0; l < config.nLayer; l++)
+        for (const SLP* s : LayerMatrices(l))
+            if (is_row3(s->w)) return true;
+    return false;
+}
 SLP* Fish::LayerMatrix(int layer, int slot) const { return layer >= 0 && layer < config.nLayer && slot >= 0 && slot < 7 ? LayerMatrices(layer)[slot] : nullptr; }
 
 // ---- int8 activations (kfh_set_act_int8, kfh_set_act_int8_q4)
@@ -644,6 +652,10 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
         for (int j = 0; j < 7; j++) {
             if (!s[j]->w || s[j]->b) {
                 why = "a layer matrix is missing or carries a bias";
+                return KF_ENGINE_NOT_SERVED;
+            }
+            if (is_row3(s[j]->w)) { /* the engines (persistent and XCD) serve group-quantised storage */
+                why = kRow3Why;
                 return KF_ENGINE_NOT_SERVED;
             }
             L[l].w[j] = s[j]->w->desc();
@@ -1203,6 +1215,7 @@ int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, 
     for (int i = 0; i < n; i++)
         if (tokens[i] < 0 || tokens[i] >= config.vocab) return refused(why, "kfh_verify", KF_INVALID_ARGS, "a token id outside the vocabulary");
     if (!embed.w || !head.proj.w) return refused(why, "kfh_verify", KF_INVALID_ARGS, "the model has no weights yet");
+    if (HasRow3()) return refused(why, "kfh_verify", KF_UNSUPPORTED_DATATYPE, kRow3Why); /* the row entries (kf_*_rows) do not unpack the 3-bit stream */
     const int rcm = verify_refusal(Modes(), samp_params.greedy(), "kfh_verify", why);
     if (rcm != KF_OK) return Kv8Note(why), rcm;
     KF_TRY(VerifyReady(logits != nullptr));
@@ -2041,6 +2054,27 @@ int kfh_set_weight(void* h, int layer, int slot, int type, int ne0, int ne1, con
 // the same for a tensor whose quant card says isNormalFloat (QUANT_MODE::RTNf): Q4 nibble stream || gama with a 16-entry table per row
 int kfh_set_weight_lut(void* h, int layer, int slot, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device) {
     return set_weight_impl(h, layer, slot, (int)typNUMBER::Q4, ne0, ne1, blob, blob_bytes, szData, is_device, 0, 0, 15, 0, true);
+}
+// ... at `bits` per weight: 4 as above; 3 (RT_NormalF with bits == 3: an 8-entry table per row) for layer matrices only -- TokenEmbed::cuInfer asserts on Q3 and the LM
+// head forms do not unpack it.  A Fish holding such a matrix multiplies it from the packed stream: kf_set_row_unpack goes on for its own context (there is no earlier
+// behaviour to keep: the fused decode entries refused the storage)
+int kfh_set_weight_lut_bits(void* h, int layer, int slot, int bits, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device) {
+    if (bits == 4) return kfh_set_weight_lut(h, layer, slot, ne0, ne1, blob, blob_bytes, szData, is_device);
+    if (bits != 3) {
+        g_host_err = "kfh_set_weight_lut_bits: normal-float row codebooks exist at 4 and 3 bits (RT_NormalF)";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
+    if (layer < 0) {
+        g_host_err = "kfh_set_weight_lut_bits: the embedding and the LM head stay bf16 or 4-bit (TokenEmbed::cuInfer asserts on Q3; no 3-bit head mat-vec): NF3 is for layer matrices";
+        return KF_UNSUPPORTED_DATATYPE;
+    }
+    if (ne1 % 128 != 0 || ne0 % 8 != 0) {
+        g_host_err = "kfh_set_weight_lut_bits: a 3-bit layer matrix needs ne1 % 128 == 0 and ne0 % 8 == 0 (whole 32-weight units per lane, 16-byte aligned row tables)";
+        return KF_BLAS_UNALIGN;
+    }
+    Fish* f = reinterpret_cast<Fish*>(h);
+    const int rc = set_weight_impl(h, layer, slot, (int)typNUMBER::Q3, ne0, ne1, blob, blob_bytes, szData, is_device, 0, 0, 7, 0, true);
+    return rc != KF_OK ? rc : kf_set_row_unpack(f->ctx, 1);
 }
 static int set_weight_impl(void* h, int layer, int slot, int type, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device, int lGroup,
                            int qMin, int qMax, int qBias, bool normal_float) {

@@ -379,6 +379,7 @@ struct Fish : SeqBuffers {
     int n_adapters = 0, lora_r = 0;
     float lora_s = 0.0f;
     std::array<SLP*, 7> LayerMatrices(int layer) const;  // q k v o gate up down, the order of kf_engine_layer.w and of the C entries' slots
+    bool HasRow3() const;  // a layer matrix is a 3-bit row codebook (NF3): per-layer launches with kf_set_row_unpack on; no engine, no XCD decoders, no Verify
     SLP* LayerMatrix(int layer, int slot) const;  // one of them, or NULL
     int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);
     void ClearAdapters();

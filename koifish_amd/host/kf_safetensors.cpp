@@ -787,6 +787,7 @@ void quant_range(typNUMBER t, bool symmetric, QuantCard& q) {  // GeQuant ctor (
     q.qMin = q.qMax = q.qBias = 0, q.bits = 16;
     switch (t) {
         case typNUMBER::Q4: q.bits = 4; if (symmetric) q.qMin = -8, q.qMax = 7, q.qBias = 8; else q.qMin = 0, q.qMax = 15; break;
+        case typNUMBER::Q3: q.bits = 3, q.qMin = 0, q.qMax = 7; break; /* the normal-float row form only (RT_NormalF with bits == 3) */
         case typNUMBER::T_SIGN: q.bits = 2, q.qMin = -1, q.qMax = 1, q.qBias = 1; break;
         case typNUMBER::BOOL1: case typNUMBER::T_BINARY: q.bits = 1, q.qMin = 0, q.qMax = 1; break;
         case typNUMBER::F8E5M2: q.bits = 8; break;
@@ -858,12 +859,15 @@ struct Loader {
             KF_TRY(t->Alloc(f->ctx, t->szData));
             kf_weight d = t->desc();
             KF_TRY(kf_quantize(f->ctx, &d, d_src, 0));
-        } else if (tp == typNUMBER::Q4 && lGroup == 0) {
-            // quant card with isNormalFloat (QUANT_MODE::RTNf): GeQuant::RT_NormalF on the device -> nibble stream || [R][C][LUT ne0 x 16]
-            if ((ne1 % 32) || (ne0 % 8)) return fail(KF_QUANT_ERR, "tensor '" + name + "': the normal-float row form needs in % 32 == 0 and out % 8 == 0");
+        } else if ((tp == typNUMBER::Q4 || tp == typNUMBER::Q3) && lGroup == 0) {
+            // quant card with isNormalFloat (QUANT_MODE::RTNf): GeQuant::RT_NormalF on the device -> nibble (3-bit) stream || [R][C][LUT ne0 x 16 (8)]
+            const int bits = t->quant.bits;
+            if (bits == 4 && ((ne1 % 32) || (ne0 % 8))) return fail(KF_QUANT_ERR, "tensor '" + name + "': the normal-float row form needs in % 32 == 0 and out % 8 == 0");
+            if (bits == 3 && ((ne1 % 128) || (ne0 % 8)))
+                return fail(KF_QUANT_ERR, "tensor '" + name + "': the 3-bit normal-float row form needs in % 128 == 0 and out % 8 == 0 (whole 32-weight units, aligned row tables)");
             t->quant.isNormalFloat = true;
-            t->szData = n / 2;
-            t->szGama = ((size_t)ne0 + ne1 + 16 * (size_t)ne0) * 2;
+            t->szData = n * bits / 8;
+            t->szGama = ((size_t)ne0 + ne1 + ((size_t)ne0 << bits)) * 2;
             KF_TRY(t->Alloc(f->ctx, t->szData + t->szGama));
             std::vector<uint16_t> ones((size_t)ne0 + ne1, 0x3F80);
             KF_TRY(kf_h2d(f->ctx, t->gama_T(), ones.data(), ones.size() * 2));
@@ -1012,6 +1016,7 @@ Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_t
             return bail(rc, err);
     }
     if (any_awq) f->fuse_level = 0;  // the AutoAWQ layout has its own mat-vec (kf_linear only): one launch per reference kernel
+    if (f->HasRow3() && (rc = kf_set_row_unpack(f->ctx, 1)) != KF_OK) return bail(rc, "kf_set_row_unpack failed"); /* 3-bit layers are multiplied from the packed stream */
     if (rc_out) *rc_out = KF_OK;
     return f.release();
 }
@@ -1186,7 +1191,7 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
                 if (kv.second.kind == JSON::OBJ && !kv.first.empty() && kv.first[0] != '#' && name.find(kv.first) != std::string::npos) sec = &kv.second;
         quant_range(t->type, sec && sec->bool_or("symmetric", false), t->quant);
         t->quant.T_group = sec ? (int)sec->number_or("group_size", group_dflt) : group_dflt;
-        if (sec && t->type == typNUMBER::Q4) {
+        if (sec && (t->type == typNUMBER::Q4 || t->type == typNUMBER::Q3)) {
             const JSON* m = sec->get("quant_method");
             const std::string ms = m && m->kind == JSON::STR ? m->str : "";
             t->quant.isNormalFloat = ms.find("RTN") == std::string::npos && ms.find("AWQ") == std::string::npos && ms.find("yyang") == std::string::npos &&
@@ -1194,11 +1199,15 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
         }
         const size_t n = (size_t)ne0 * ne1;
         size_t want_data = n * 2, want_gama = 0;
+        if (t->type == typNUMBER::Q3 && (!t->quant.isNormalFloat || name.find("layers.") == std::string::npos || (ne1 % 128) || (ne0 % 8))) {
+            err = "tensor '" + name + "': Q<3> is served as the normal-float row form (quant_method \"NF\") of a layer matrix with in % 128 == 0 and out % 8 == 0";
+            return KF_UNSUPPORTED_DATATYPE;
+        }
         if (is_quant_type(t->type)) {
             want_data = n * t->quant.bits / 8;
             if (t->quant.isNormalFloat) {
                 t->quant.T_group = 0;
-                want_gama = ((size_t)ne0 + ne1 + 16 * (size_t)ne0) * 2;
+                want_gama = ((size_t)ne0 + ne1 + ((size_t)ne0 << t->quant.bits)) * 2;
             } else {
                 if (t->quant.T_group <= 0 || n % (size_t)t->quant.T_group) {
                     err = "tensor '" + name + "': group size " + std::to_string(t->quant.T_group);
@@ -1248,6 +1257,7 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
             !ok(linear(p + "mlp.down_proj.weight", C, card.n_ff, &m->down)))
             return bail(rc, err);
     }
+    if (f->HasRow3() && (rc = kf_set_row_unpack(f->ctx, 1)) != KF_OK) return bail(rc, "kf_set_row_unpack failed"); /* 3-bit layers are multiplied from the packed stream */
     if (rc_out) *rc_out = KF_OK;
     return f.release();
 }
@@ -1298,9 +1308,14 @@ int kfh_st_read(void* h, const char* name, void* out, uint64_t nbytes) {
 // HF directory (config.json + model.safetensors[.index.json]) -> Fish handle usable with every kfh_* entry; NULL + *rc on failure
 void* kfh_load_hf(const char* dir, int device, void* stream, int layer_type, int head_type, int lGroup, int max_seq, int* rc) {
     std::string err;
-    // 1000 (koifish_amd.lib.NF4) is not a typNUMBER: "Q4 with the normal-float quant card" (QUANT_MODE::RTNf)
-    const bool lnf = layer_type == 1000, hnf = head_type == 1000;
-    Fish* f = LoadHF(dir, device, stream, lnf ? typNUMBER::Q4 : (typNUMBER)layer_type, hnf ? typNUMBER::Q4 : (typNUMBER)head_type, lGroup > 0 ? lGroup : 128, max_seq, rc, err,
+    // 1000 / 1001 (koifish_amd.lib.NF4 / NF3) are not typNUMBERs: "Q4 / Q3 with the normal-float quant card" (QUANT_MODE::RTNf); NF3 is for layer matrices only
+    if (head_type == 1001) {
+        g_st_err = "kfh_load_hf: the embedding and the LM head stay bf16 or 4-bit (TokenEmbed::cuInfer asserts on Q3): NF3 is a layer storage";
+        if (rc) *rc = KF_UNSUPPORTED_DATATYPE;
+        return nullptr;
+    }
+    const bool lnf = layer_type == 1000 || layer_type == 1001, hnf = head_type == 1000;
+    Fish* f = LoadHF(dir, device, stream, layer_type == 1001 ? typNUMBER::Q3 : lnf ? typNUMBER::Q4 : (typNUMBER)layer_type, hnf ? typNUMBER::Q4 : (typNUMBER)head_type, lGroup > 0 ? lGroup : 128, max_seq, rc, err,
                      lnf, hnf);
     if (!f) g_st_err = err;
     return f;

@@ -19,6 +19,8 @@ CLIP_OFF, CLIP_REPORT, CLIP_TENSOR, CLIP_GLOBAL = 0, 1, 2, 3   # enum kf_clip_mo
 CLIP_MODES = {None: CLIP_OFF, "report": CLIP_REPORT, "tensor": CLIP_TENSOR, "global": CLIP_GLOBAL}
 MODES = ("TP", "ACT_INT8", "ADAPTERS", "KV_INT8", "HOT_MASK", "FUSE0")  # enum koifish::Mode (host/kf_host_modes.hpp), in precedence order
 NF4 = 1000  # not a typNUMBER: "Q4 with the normal-float quant card" (QUANT_MODE::RTNf) for the helpers that take a storage type
+NF3 = 1001  # the same card at 3 bits (RT_NormalF with bits == 3): layer matrices only, multiplied from the packed stream with kf_set_row_unpack
+FMT_Q3R, FMT_Q2R, FMT_Q2N = 9, 10, 11   # kf_kernels.h: the kernel formats of the 3- / 2-bit row forms (kfdbg_rowq_standin)
 
 # every symbol include/kf_abi.h declares (tests/test_abi_symbols.py checks the header against this list and the .so)
 ABI_SYMBOLS = [
@@ -27,7 +29,7 @@ ABI_SYMBOLS = [
     "kf_event_destroy", "kf_dequant", "kf_quantize", "kf_linear", "kf_rmsnorm", "kf_qknorm_rope", "kf_rope_table_host", "kf_attn_decode",
     "kf_attn_scratch_bytes", "kf_linear_f32", "kf_tp_reduce", "kf_swiglu", "kf_add", "kf_embed", "kf_lm_head", "kf_head_scratch_bytes", "kf_norm_linear",
     "kf_norm_gateup_swiglu", "kf_attn_block", "kf_norm_lm_head", "kf_set_state", "kf_embed_state", "kf_embed_batch", "kf_qknorm_rope_batch", "kf_attn_prefill", "kf_sample", "kf_linear_multi", "kf_linear_multi_scratch_bytes", "kf_gateup_swiglu_batch", "kf_adamw", "kf_layernorm", "kf_gelu", "kf_sample_topk", "kf_fused_classifier", "kf_gelu_backward", "kf_swiglu_backward", "kf_rope_backward", "kf_norm_backward", "kf_norm_backward_scratch_bytes", "kf_linear_backward", "kf_linear_backward_scratch_bytes", "kf_embed_backward", "kf_attn_backward", "kf_attn_backward_scratch_bytes", "kf_attn_prefill_batch", "kf_attn_prefill_batch_strided", "kf_embed_pos", "kf_memset2d", "kf_copy_blocks", "kf_argmax_rows_state", "kf_qknorm_rope_train",
-    "kf_hot_rows", "kf_linear_masked", "kf_zero_cold_columns", "kf_norm_gateup_swiglu_masked", "kf_linear_scratch_bytes", "kf_set_scratch", "kf_engine_workspace_bytes", "kf_engine_create", "kf_engine_step", "kf_engine_check", "kf_engine_destroy", "kf_engine_set_embedding", "kf_engine_set_head", "kf_engine_step_head", "kf_engine_steps_head", "kf_engine_reset", "kf_set_canonical", "kf_get_canonical", "kf_engine_served", "kf_engine_tune", "kf_engine_stats", "kf_engine_head_screen_bytes", "kf_engine_set_head_screen", "kf_engine_screen_stats", "kf_qkv_rope_batch", "kf_qkv_rope_seqs", "kf_set_dequant_arena", "kf_dequant_arena_used", "kf_resident_scratch_bytes",
+    "kf_hot_rows", "kf_linear_masked", "kf_zero_cold_columns", "kf_norm_gateup_swiglu_masked", "kf_linear_scratch_bytes", "kf_set_scratch", "kf_engine_workspace_bytes", "kf_engine_create", "kf_engine_step", "kf_engine_check", "kf_engine_destroy", "kf_engine_set_embedding", "kf_engine_set_head", "kf_engine_step_head", "kf_engine_steps_head", "kf_engine_reset", "kf_set_canonical", "kf_get_canonical", "kf_set_row_unpack", "kf_get_row_unpack", "kf_engine_served", "kf_engine_tune", "kf_engine_stats", "kf_engine_head_screen_bytes", "kf_engine_set_head_screen", "kf_engine_screen_stats", "kf_qkv_rope_batch", "kf_qkv_rope_seqs", "kf_set_dequant_arena", "kf_dequant_arena_used", "kf_resident_scratch_bytes",
     "kf_xengine_workspace_bytes", "kf_xengine_create", "kf_xengine_served", "kf_xengine_set_embedding", "kf_xengine_set_head", "kf_xengine_steps", "kf_xengine_check", "kf_xengine_reset", "kf_xengine_destroy", "kf_xengine_workspace_bytes_tp", "kf_xengine_create_tp", "kf_xengine_set_head_tp",
     "kf_tp_recv_bytes", "kf_tp_push_bytes", "kf_tp_commit", "kf_tp_alloc", "kf_tp_ipc_export", "kf_tp_ipc_open", "kf_tp_ipc_close", "kf_linear_f32_push", "kf_tp_reduce_recv", "kf_tp_lm_head", "kf_tp_pick",
     "kf_head_logprob", "kf_head_logprob_scratch_bytes",
@@ -218,6 +220,7 @@ def load():
         host.kfh_set_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_int]
         host.kfh_set_weight_lut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
+        host.kfh_set_weight_lut_bits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
         host.kfh_tie_head.argtypes = [C.c_void_p]
         host.kfh_set_norm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
         host.kfh_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -332,6 +335,8 @@ def load():
         host.kfh_engine_screen_stats.argtypes = [C.c_void_p, C.c_void_p]
         hip.kf_set_canonical.argtypes = [C.c_void_p, C.c_int]
         hip.kf_get_canonical.argtypes = [C.c_void_p]
+        hip.kf_set_row_unpack.argtypes = [C.c_void_p, C.c_int]
+        hip.kf_get_row_unpack.argtypes = [C.c_void_p]
         hip.kf_engine_destroy.argtypes = [C.c_void_p]
         # the training steps' sequencers: koifish::GPT2Trainer (host/kf_train.cpp, kfh_gpt2_*) and koifish::Qwen3Trainer (host/kf_train_qwen3.cpp, kfh_qwen3t_*), the
         # entries both families have from one table (_TRAINER_ENTRIES); getattr raises on a name the library lacks

@@ -86,7 +86,7 @@ class DevWeight:
 
 class LutDevWeight:
     """Row-codebook weight in HBM (KF_QUANT_ROW_LUT; GeQuant::RT_NormalF): blob = MSB-first `bits`-wide stream [ne0*ne1*bits/8] ‖ bf16 gama
-    [ne0 + ne1 + (2^bits)*ne0]; bits 4 (the mat-vec format), 3 or 2 (dequant-only); rtn=True (bits 2): (zero, step) per row, KF_QUANT_ROW_RTN."""
+    [ne0 + ne1 + (2^bits)*ne0]; bits 4 (the mat-vec format), 3 or 2 (dequantised in front of a product, or multiplied from the stream with Context.set_row_unpack); rtn=True (bits 2): (zero, step) per row, KF_QUANT_ROW_RTN."""
 
     def __init__(self, ne0, ne1, blob, bits=4, rtn=False):
         self.type, self.ne0, self.ne1, self.blob, self.lGroup = {4: L.Q4, 3: L.Q3, 2: L.Q2}[bits], ne0, ne1, blob, 0
@@ -187,6 +187,11 @@ class Context:
         """1 (the library default): the decode kernels sum in the canonical order the CPU oracle shares (bit-exact); 0: the v_dot2c / fp32 forms"""
         L.check(self.hip.kf_set_canonical(self.h, int(bool(on))), "kf_set_canonical")
 
+    def set_row_unpack(self, on):
+        """1: the 3- / 2-bit row forms are multiplied from the packed stream (kf_set_row_unpack: one token, the fused decode entries, token batches -- the bits of the
+        4-bit row codebook holding the same values); 0 (the library default): dequantise + bf16 product, and the fused entries refuse them"""
+        L.check(self.hip.kf_set_row_unpack(self.h, int(bool(on))), "kf_set_row_unpack")
+
     # ---- weights
     def upload_blob(self, type_, ne0, ne1, blob_np, lGroup=128, symmetric=False):
         t = torch.from_numpy(np.ascontiguousarray(blob_np).view(np.uint8).reshape(-1).copy()).to(self.device)
@@ -196,6 +201,8 @@ class Context:
         """w_bf16: torch.bfloat16 [ne0, ne1] on the GPU -> DevWeight (kf_quantize: GeQuant::RTN_x / YinYang on device)."""
         if type_ == L.NF4:
             return self.quantize_nf4(w_bf16)
+        if type_ == L.NF3:
+            return self.quantize_nf4(w_bf16, bits=3)
         ne0, ne1 = w_bf16.shape
         w_bf16 = w_bf16.contiguous()
         if type_ == L.BF16:
@@ -237,7 +244,8 @@ class Context:
         return out
 
     def linear_scratch(self, w, n_tok=1):
-        """kernels never allocate: storages served by dequantise-then-multiply (AWQ, 3- / 2-bit row forms, row-codebook batches) get their workspace here"""
+        """kernels never allocate: storages served by dequantise-then-multiply (AWQ, 3- / 2-bit row forms unless set_row_unpack serves them from the stream, row-codebook
+        batches) get their workspace here"""
         d = w.desc() if not isinstance(w, L.Weight) else w
         need = self.hip.kf_linear_scratch_bytes(C.byref(d), int(n_tok))
         if need and (self._lin_ws is None or self._lin_ws.numel() < need):
@@ -689,6 +697,13 @@ class Qwen3:
         """w: DevWeight (already in HBM)."""
         self._keep.append(w)
         self.weights[(layer, slot)] = w
+        if isinstance(w, LutDevWeight) and w.bits != 4:   # NF3 layer matrices (the host refuses other widths, the embedding and the head, with a reason)
+            if w.rtn:
+                raise L.KFError("set_weight: the 2-bit row forms are operator-level storage (the reference has no quantiser for them)")
+            rc = self.host.kfh_set_weight_lut_bits(self.h, layer, slot, w.bits, w.ne0, w.ne1, C.c_void_p(w.blob.data_ptr()), C.c_size_t(w.blob.numel()), C.c_size_t(w.szData), 1)
+            if rc != 0:
+                raise L.KFError("kfh_set_weight_lut_bits failed: code %d: %s" % (rc, self.host.kfh_host_error().decode()))
+            return
         if isinstance(w, LutDevWeight):
             L.check(self.host.kfh_set_weight_lut(self.h, layer, slot, w.ne0, w.ne1, C.c_void_p(w.blob.data_ptr()), C.c_size_t(w.blob.numel()), C.c_size_t(w.szData), 1),
                     "kfh_set_weight_lut")
