@@ -152,11 +152,7 @@ __device__ __forceinline__ int w4a8_elem(int j, int b) { return (j >> 3) * 32 + 
 // the epilogue of one output element o = tok * M + row: y = bf16(step_x * acc (+ bias)), then CU_add3: bf16(x + bf16(W.x)), as kf_linear.  The element is read and written
 // by this lane alone (residual may be y).
 __device__ __forceinline__ void a8_store(uint16_t* y, const uint16_t* bias, const uint16_t* residual, float sx, float acc, long row, size_t o) {
-    float v = sx * acc;
-    if (bias) v = v + bf2f(bias[row]);
-    uint16_t r = f2bf(v);
-    if (residual) r = add_bf16(residual[o], r);
-    y[o] = r;
+    y[o] = linear_out_bf16(sx * acc, /* alpha */ 1.0f, /* beta, y */ 0.0f, nullptr, 0, bias, row, residual, o);
 }
 
 }  // namespace kf

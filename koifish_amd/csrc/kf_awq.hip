@@ -74,6 +74,7 @@ __global__ void awq_finish_kernel(const float* __restrict__ partial, int nslice,
     if (o >= n_out) return;
     float v = partial[o];
     for (int s = 1; s < nslice; s++) v = v + partial[(size_t)s * n_out + o];
+    /* linear_out_bf16 (kf_device.h), written out: through the helper the beta branch is laid out the other way round */
     if (alpha != 1.0f) v = alpha * v;
     if (beta != 0.0f) v = v + beta * bf2f(y[o]);
     if (bias) v = v + bf2f(bias[o]);

@@ -252,6 +252,17 @@ __device__ __forceinline__ void advance_decode_state(int32_t* st, int32_t* token
 __device__ __forceinline__ uint16_t swiglu_bf16(float gt, float up) { return f2bf((gt * up) / (1.0f + kf_expf(-gt))); }
 // the residual epilogue CU_add3: bf16(x + bf16(W.x)), both operands bf16 already
 __device__ __forceinline__ uint16_t add_bf16(uint16_t res, uint16_t o) { return f2bf(bf2f(res) + bf2f(o)); }
+// the end of every linear product (the mat-vec, the token-batch GEMMs, AWQ; oracle `linear`): alpha, beta * y, bias, ONE bf16 rounding, then the residual add on the
+// rounded value.  Each operand vector comes as (base, index of the element): y is read only when beta != 0, bias and res only when their base is not null -- the
+// bases are tested, so the tests stay scalar, and an element's address is formed only where it is read
+__device__ __forceinline__ uint16_t linear_out_bf16(float v, float alpha, float beta, const uint16_t* y, size_t yi, const uint16_t* bias, size_t bi, const uint16_t* res, size_t ri) {
+    if (alpha != 1.0f) v = alpha * v;
+    if (beta != 0.0f) v = v + beta * bf2f(y[yi]);
+    if (bias) v = v + bf2f(bias[bi]);
+    uint16_t o = f2bf(v);
+    if (res) o = add_bf16(res[ri], o);
+    return o;
+}
 // RMSNorm (rms_norm_kernel, layernorm.cuh:800-847; oracle section 3): the multiplier from the fp64 sum of squares, and one normalised bf16 pair (x * mul) * w
 __device__ __forceinline__ float rms_scale(float tot, float inv_dim, float eps) { return 1.0f / sqrtf(fmaf(tot, inv_dim, eps)); }
 __device__ __forceinline__ uint32_t rms_pair(uint32_t x, uint32_t w, float mul) { return pack_bf16x2((bf_lo(x) * mul) * bf_lo(w), (bf_hi(x) * mul) * bf_hi(w)); }

@@ -16,8 +16,10 @@
 //
 // Workgroup = 4 waves = RBW row blocks of 32 output rows x KS halves of the staged k tile (KS = 1: 128 rows; KS = 2: 64 rows, each k
 // half on its own wave, partial sums combined through LDS in a fixed order).  Grid = (row tiles, 128-token tiles).
-// fp32 accumulation inside the MFMA, one bf16 round-to-nearest store; epilogue order as the mat-vec (alpha, beta*y, bias, store,
-// residual add + store).  Differs from the token-serial mat-vec only in fp32 summation order.
+// fp32 accumulation inside the MFMA, one bf16 round-to-nearest store; the epilogue is linear_out_bf16 (kf_device.h: alpha, beta*y, bias, store,
+// residual add + store), called by gemm_epilogue and by the direct kernel's reduce tail.  Differs from the token-serial mat-vec only in fp32 summation order.
+// Every storage format has its own WTile body (load, frag(sl, a, ks)) over one of two element ranges, koff_unit / koff_half; a common load shell for the five
+// unit formats was tried and is not here: DESIGN.md section 4.0.
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,8 +31,13 @@ namespace kf {
 // step sl of wave-half ks: elements [koff, koff + 8) of the 128-wide tile
 template <int FMT, int KS>
 struct WTile;
+// the two element ranges, stated once.  Unit formats (32 weights per unit: 4-bit, the row forms, bf16, f8): pair P = ks * NP + p (NP = 2 / KS), lane half h owns
+// elements (2P + h) * 32 .. + 32.  2-bit / 1-bit (blocks of 64 / 128): lane half h owns 64 elements, global step s = ks * NS + sl covers its elements 8s .. 8s + 7
+template <int KS>
+__device__ __forceinline__ int koff_unit(int sl, int h, int ks) { return (2 * (ks * (2 / KS) + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
+template <int KS>
+__device__ __forceinline__ int koff_half(int sl, int h, int ks) { return 64 * h + 8 * (ks * (8 / KS) + sl); }
 
-// 4-bit, bf16, f8 share the element ranges: pair P = ks * NP + p (NP = 2 / KS), lane half h owns elements (2P + h) * 32 .. + 32
 template <int KS>
 struct WTile<FMT_Q4, KS> {
     static constexpr int NP = 2 / KS;
@@ -51,8 +58,8 @@ struct WTile<FMT_Q4, KS> {
             st[p] = a.step[gi], ze[p] = a.zero[gi], in[p] = in_row;
         }
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
-    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs& a) const {
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_unit<KS>(sl, h, ks); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs& a, int) const {
         const int p = sl >> 2, c = sl & 3;
         const uint32_t D = c == 0 ? b[p].w : (c == 1 ? b[p].z : (c == 2 ? b[p].y : b[p].x));
         const float s = in[p] ? bf2f(st[p]) : 0.f, z = in[p] ? bf2f(ze[p]) : 0.f;
@@ -78,8 +85,8 @@ struct WTile<FMT_Q4R, KS> {
             in[p] = in_row;
         }
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
-    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&) const {
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_unit<KS>(sl, h, ks); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&, int) const {
         const int p = sl >> 2, c = sl & 3;
         const uint32_t D = c == 0 ? b[p].x : (c == 1 ? b[p].y : (c == 2 ? b[p].z : b[p].w)); /* stream order: dword 0 holds elements 0..7 */
         const u32x4 o = frag_q4r(D, ta, tb);
@@ -110,8 +117,8 @@ struct WTileRowQ {
             in[p] = in_row;
         }
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
-    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&) const {
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_unit<KS>(sl, h, ks); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&, int) const {
         const int p = sl >> 2, c = sl & 3;
         const RowTab t = FMT == FMT_Q2N ? row_tab_rtn(ta.x) : row_tab<(1 << BITS)>(ta);
         const u32x4 o = row_pairs8<BITS>(row_unit_ids8<BITS>(b[p], c), t);
@@ -143,8 +150,8 @@ struct WTile<FMT_BF16, KS> {
             }
         }
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
-    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&) const { return b[sl >> 2][sl & 3]; }
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_unit<KS>(sl, h, ks); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&, int) const { return b[sl >> 2][sl & 3]; }
 };
 template <int KS>
 struct WTile<FMT_F8, KS> {
@@ -164,17 +171,16 @@ struct WTile<FMT_F8, KS> {
             }
         }
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return (2 * (ks * NP + (sl >> 2)) + h) * 32 + 8 * (sl & 3); }
-    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&) const {
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_unit<KS>(sl, h, ks); }
+    __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs&, int) const {
         const int p = sl >> 2, c = sl & 3;
         const u32x4 v = b[p][c >> 1];
         return (c & 1) ? frag_f8(v.z, v.w) : frag_f8(v.x, v.y);
     }
 };
-// 2-bit: the staged tile is two 64-element blocks, lane half h owns block h; global step s = ks * NS + sl covers elements 8s..8s+7
+// 2-bit: the staged tile is two 64-element blocks, lane half h owns block h
 template <int KS>
 struct WTile<FMT_Q2, KS> {
-    static constexpr int NS = 8 / KS;
     u32x4 b;
     uint16_t st, ze;
     __device__ __forceinline__ void load(const GemmArgs& a, int row, int it, int h, int) {
@@ -183,7 +189,7 @@ struct WTile<FMT_Q2, KS> {
         const uint32_t gi = bidx >> a.gshift;
         st = a.step[gi], ze = a.zero[gi];
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return 64 * h + 8 * (ks * NS + sl); }
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_half<KS>(sl, h, ks); }
     __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs& a, int ks) const {
         const uint32_t dw[4] = {b.w, b.z, b.y, b.x}; /* dword3 holds elements 0..15 */
         uint32_t D = dw[sl >> 1];
@@ -196,7 +202,6 @@ struct WTile<FMT_Q2, KS> {
 // 1-bit: the staged tile is one 128-element block, lane half h owns its 8-byte half (elements 64h .. 64h+63)
 template <int KS>
 struct WTile<FMT_Q1, KS> {
-    static constexpr int NS = 8 / KS;
     u32x2 b; /* b.y: first 32 elements of the half, b.x: next 32 */
     uint16_t st, ze;
     __device__ __forceinline__ void load(const GemmArgs& a, int row, int it, int h, int) {
@@ -205,7 +210,7 @@ struct WTile<FMT_Q1, KS> {
         const uint32_t gi = bidx >> a.gshift;
         st = a.step[gi], ze = a.zero[gi];
     }
-    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return 64 * h + 8 * (ks * NS + sl); }
+    static __device__ __forceinline__ int koff(int sl, int h, int ks) { return koff_half<KS>(sl, h, ks); }
     __device__ __forceinline__ u32x4 frag(int sl, const GemmArgs& a, int ks) const {
         const uint32_t D = (KS == 2) ? (ks ? b.x : b.y) : ((sl >> 2) ? b.x : b.y);
         const uint32_t byte = (D >> (24 - 8 * (sl & 3))) & 0xffu;
@@ -215,14 +220,6 @@ struct WTile<FMT_Q1, KS> {
         return frag_q1(byte, ww & 0xffffu, ww >> 16);
     }
 };
-
-template <int FMT, int KS>
-__device__ __forceinline__ u32x4 get_frag(const WTile<FMT, KS>& t, int sl, const GemmArgs& a, int ks) {
-    if constexpr (FMT == FMT_Q2 || FMT == FMT_Q1)
-        return t.frag(sl, a, ks);
-    else
-        return t.frag(sl, a);
-}
 
 template <int FMT, int KS>
 __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs a) {
@@ -313,7 +310,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs a) {
                 for (int tb = 0; tb < 4; tb++) Bn[tb] = *reinterpret_cast<const u32x4*>(xb + (tb * 32 + r) * GM_XS + ko);
             }
             __builtin_amdgcn_sched_barrier(0); /* keep the reads up here: left alone, the scheduler sinks each one next to its MFMA */
-            const bf16x8 A = __builtin_bit_cast(bf16x8, get_frag<FMT, KS>(wc, sl, a, ks));
+            const bf16x8 A = __builtin_bit_cast(bf16x8, wc.frag(sl, a, ks));
 #pragma unroll
             for (int tb = 0; tb < 4; tb++) acc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(bf16x8, Bc[tb]), acc[tb], 0, 0, 0);
 #pragma unroll
@@ -435,12 +432,12 @@ __global__ void __launch_bounds__(NW * 64) gemm_direct_kernel(const GemmArgs a0)
             if (u0 + j < nunit) {
 #pragma unroll
                 for (int sl = 0; sl < 4; sl++) {
-                    const bf16x8 A = __builtin_bit_cast(bf16x8, get_frag<FMT, 2>(gc.w[j], sl, a, (u0 + j) & 1));
+                    const bf16x8 A = __builtin_bit_cast(bf16x8, gc.w[j].frag(sl, a, (u0 + j) & 1));
 #pragma unroll
                     for (int tb = 0; tb < TB; tb++)
                         acc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(bf16x8, gc.x[j][sl][tb]), acc[tb], 0, 0, 0);
                     if (PAIRED) {
-                        const bf16x8 A2 = __builtin_bit_cast(bf16x8, get_frag<FMT, 2>(gc.w2[j], sl, b, (u0 + j) & 1));
+                        const bf16x8 A2 = __builtin_bit_cast(bf16x8, gc.w2[j].frag(sl, b, (u0 + j) & 1));
 #pragma unroll
                         for (int tb = 0; tb < TB; tb++)
                             acc2[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, __builtin_bit_cast(bf16x8, gc.x[j][sl][tb]), acc2[tb], 0, 0, 0);
@@ -488,14 +485,8 @@ __global__ void __launch_bounds__(NW * 64) gemm_direct_kernel(const GemmArgs a0)
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 if (rg + j >= a.M) continue;
-                if (!PAIRED) { /* gemm_epilogue's expression */
-                    float x = v[j];
-                    if (a.alpha != 1.0f) x = a.alpha * x;
-                    if (a.beta != 0.0f) x = x + a.beta * bf2f(yp[j]);
-                    if (a.bias) x = x + bf2f(a.bias[rg + j]);
-                    uint16_t qv = f2bf(x);
-                    if (a.residual) qv = add_bf16(a.residual[(size_t)tok * a.ldr + rg + j], qv);
-                    o[j] = qv;
+                if (!PAIRED) {
+                    o[j] = linear_out_bf16(v[j], a.alpha, a.beta, yp, j, a.bias, rg + j, a.residual, (size_t)tok * a.ldr + rg + j);
                 } else { /* act = silu(gate) * up on the bf16-rounded gate / up (Relu::Forw SWIG, Activation.cu:85-93; the expression of kf_swiglu) */
                     const float g = round_bf16(v[j]), u = round_bf16(v2[j]);
                     o[j] = swiglu_bf16(g, u);

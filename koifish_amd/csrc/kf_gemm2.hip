@@ -152,23 +152,17 @@ __global__ void __launch_bounds__(512) gemm2_kernel(const GemmArgs a) {
 }
 
 // tiles of G2_BM rows x G2_BN tokens (kf_gemm_plan.h tile_plan: 4-bit, bf16, f8; K a multiple of G2_BK, >= G2_BN rows)
+template <int FMT>
+static void g2_launch(hipStream_t st, const GemmKern& k, const GemmArgs& a) {
+    static bool raised = false; /* the dynamic-LDS limit: once per kernel */
+    if (!raised) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds), raised = true;
+    hipLaunchKernelGGL(gemm2_kernel<FMT>, dim3(k.gx, k.gy), dim3(512), (size_t)k.lds, st, a);
+}
 int gemm2_run(hipStream_t st, const GemmKern& k, const GemmArgs& a) {
-    const dim3 grid(k.gx, k.gy);
-    const size_t smem = k.lds;
-    static bool raised[3] = {false, false, false};
     switch (k.fmt) {
-        case FMT_Q4:
-            if (!raised[0]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<FMT_Q4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), raised[0] = true;
-            hipLaunchKernelGGL(gemm2_kernel<FMT_Q4>, grid, dim3(512), smem, st, a);
-            break;
-        case FMT_BF16:
-            if (!raised[1]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<FMT_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), raised[1] = true;
-            hipLaunchKernelGGL(gemm2_kernel<FMT_BF16>, grid, dim3(512), smem, st, a);
-            break;
-        default:
-            if (!raised[2]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<FMT_F8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem), raised[2] = true;
-            hipLaunchKernelGGL(gemm2_kernel<FMT_F8>, grid, dim3(512), smem, st, a);
-            break;
+        case FMT_Q4: g2_launch<FMT_Q4>(st, k, a); break;
+        case FMT_BF16: g2_launch<FMT_BF16>(st, k, a); break;
+        default: g2_launch<FMT_F8>(st, k, a); break;
     }
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }

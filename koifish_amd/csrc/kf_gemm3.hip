@@ -177,7 +177,7 @@ __device__ __forceinline__ void g3_epilogue(const GemmArgs& a, int m0, int t0, c
             for (int j = 0; j < 4; j++) {
                 float v = vv[j];
                 o[j] = 0;
-                if (m + j < Mlim) {
+                if (m + j < Mlim) { /* linear_out_bf16 (kf_device.h), written out: through the helper the k-major forms' branches are laid out differently */
                     if (a.alpha != 1.0f) v = a.alpha * v;
                     if (a.beta != 0.0f) v = v + a.beta * bf2f(yp[j]);
                     if (a.bias) v = v + bf2f(a.bias[m + j]);

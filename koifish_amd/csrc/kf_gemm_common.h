@@ -124,17 +124,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TB], const Gem
             uint16_t o[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                float v = acc[tb][4 * g + j];
-                if (rg + j < a.M) {
-                    if (a.alpha != 1.0f) v = a.alpha * v;
-                    if (a.beta != 0.0f) v = v + a.beta * bf2f(yp[j]);
-                    if (a.bias) v = v + bf2f(a.bias[rg + j]);
-                    uint16_t q = f2bf(v);
-                    if (a.residual) q = add_bf16(a.residual[(size_t)tok * a.ldr + rg + j], q);
-                    o[j] = q;
-                } else {
-                    o[j] = 0;
-                }
+                o[j] = rg + j < a.M ? linear_out_bf16(acc[tb][4 * g + j], a.alpha, a.beta, yp, j, a.bias, rg + j, a.residual, (size_t)tok * a.ldr + rg + j) : (uint16_t)0;
             }
             if (vec_ok && rg + 3 < a.M) {
                 *reinterpret_cast<u32x2*>(yp) = u32x2{(uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16)};

@@ -367,6 +367,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                         a.yf[r] = v;
                         continue;
                     }
+                    /* linear_out_bf16 (kf_device.h), written out: through the helper the compiler forms y's address once in front of the branches */
                     if (a.alpha != 1.0f) v = a.alpha * v;
                     if (a.beta != 0.0f) v = v + a.beta * bf2f(y[r]);
                     if (a.bias) v = v + bf2f(a.bias[r]);

@@ -201,8 +201,8 @@ __global__ void __launch_bounds__(256) gemv_rows_kernel(const GemvRowsArgs a) {
                     if constexpr (PAIRED) {
                         y[row] = swiglu_bf16(round_bf16(v), round_bf16(v2));
                     } else {
-                        uint16_t o = f2bf(v);
-                        if (a.residual) o = add_bf16(a.residual[(size_t)r * a.res_stride + row], o); /* read before the store: residual may alias y */
+                        /* alpha = 1, beta = 0, no bias; the residual is read before the store: it may alias y */
+                        const uint16_t o = linear_out_bf16(v, 1.0f, 0.0f, nullptr, 0, nullptr, 0, a.residual, (size_t)r * a.res_stride + row);
                         if (y) y[row] = o;
                         if constexpr (MODE == GEMV_ARGMAX) first_max(best_v[r], best_i[r], bf2f(o), row);
                     }

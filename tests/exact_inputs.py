@@ -672,8 +672,8 @@ _cases("TILE/G3/SMALL", "linear", ("bf16",), [(4096, 1024), (2048, 2304)])
 _cases("TILE/G3/BIG", "linear", ("bf16",), [(4096, 2560)])
 # K a multiple of 64 only: the half-empty last staged tile of 128 and the clamped address (4-bit in groups of 64)
 for _K in (1600, 192):
-    _cases("TILE/DIRECT/32/*", "linear", ("q4g64", "q4sg64", "f8", "bf16"), [(96, 40)], K=_K)
-_cases("TILE/STAGED/KS2/*", "linear", ("q4g64", "f8"), [(1056, 1281)], K=1600)
+    _cases("TILE/DIRECT/32/*", "linear", ("q4g64", "q4sg64", "f8", "bf16", "lut"), [(96, 40)], K=_K)   # "lut": the clamped unit is zeroed by masking the fragment
+_cases("TILE/STAGED/KS2/*", "linear", ("q4g64", "f8", "lut"), [(1056, 1281)], K=1600)
 _cases("TILE/G3/TINY", "linear", ("bf16",), [(1056, 1281)], K=1600)
 _cases("MATVEC", "linear", _IN_REGISTER + ("lut",), [(96, 7)])                           # below GEMM_MIN: the mat-vec loop, the same expected bits
 _cases("TILE/DIRECT/32/*", "linear", ("q4",), [(40, 129)], setting="epi")

@@ -319,6 +319,13 @@ def test_awq_layout_dequant_and_linear(ctx, O, shape):
     res = O.f32_to_bf16(rng.normal(0, 0.5, size=n_out).astype(np.float32))
     y2 = u16(ctx.linear(dw, bf16_t(x, ctx.device), residual=bf16_t(res, ctx.device)))
     assert close_bf16(y2, O.add(res, ref)).all()
+    if shape == (256, 64):   # the whole epilogue of the finish kernel: alpha, beta on a prior y, bias, then all of them under the residual add
+        b, y0 = O.f32_to_bf16(rng.normal(0, 0.1, size=n_out).astype(np.float32)), O.f32_to_bf16(rng.normal(0, 0.5, size=n_out).astype(np.float32))
+        ref3 = O.linear(ow, x, bias=b, alpha=0.5, beta=2.0, y=y0)
+        for r_np, want in ((None, ref3), (res, O.add(res, ref3))):
+            got = u16(ctx.linear(dw, bf16_t(x, ctx.device), bias=bf16_t(b, ctx.device), alpha=0.5, beta=2.0, y=bf16_t(y0, ctx.device),
+                                 residual=None if r_np is None else bf16_t(r_np, ctx.device)))
+            assert close_bf16(got, want).all(), "residual" if r_np is not None else "alpha, beta, bias"
     # the fused entry points refuse this layout instead of misreading it
     import ctypes as C
     d = dw.desc()
