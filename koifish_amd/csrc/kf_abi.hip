@@ -21,6 +21,7 @@
 #include "kf_lora_plan.h"
 #include "kf_gradnorm_plan.h"
 #include "kf_rowq.h"
+#include "kf_engine_host.h"
 
 struct kf_ctx {
     int device;
@@ -1678,229 +1679,193 @@ int kf_loss_mean(kf_ctx* c, float* acc, const float* losses, size_t n, int index
     RET(kf::loss_mean_launch(c->stream, acc, losses, n, index, count));
 }
 
-// ---- persistent decode engine
+// ---- the decode engines (kf_engine_*, kf_xengine_*, kfdbg_*engine*).  What the entries share, stated once.  The opening: the context, then the handles the entry cannot do
+// without (`what` names them: "engine" / "argument"), then, where the entry changes what a captured launch holds, ENG_NOT_CAPTURING.  The tails: ENG_HIP for a call that
+// can only fail in HIP, ok_or for one fixed refusal text, ENG_WRAP for a create (the refusal, or the host object h wrapped into *out), eng_served for the *_served answers.
+#define ENG_ENTER(c, ok, what) \
+    CHKCTX(c);                 \
+    if (!(ok)) return fail(KF_INVALID_ARGS, "%s: null " what, __func__)
+#define ENG_NOT_CAPTURING(c) \
+    if ((c)->capturing) return fail(KF_INVALID_ARGS, "%s: not while capturing", __func__)
+#define ENG_HIP(expr) \
+    if (const int rc_ = (expr)) return fail(rc_, "%s: HIP failure", __func__)
+#define ENG_WRAP(E, rc, why, h, out) ((rc) != KF_OK ? fail(rc, "%s: %s", __func__, why) : (*(out) = new E{h}, KF_OK))
+static int ok_or(int rc, const char* refusal) { return rc == KF_OK ? KF_OK : fail(rc, "%s", refusal); }
 struct kf_engine {
     kf::EngineHost* h;
 };
+struct kf_xengine {
+    kf::XEngineHost* h;
+};
+static int eng_served(int rc, const char* fn, const char* w, char* why, size_t why_bytes) {
+    if (why && why_bytes > 0) snprintf(why, why_bytes, "%s", w);
+    if (rc == KF_OK) return KF_OK;
+    return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : fail(rc, "%s: %s", fn, w);
+}
+
+// ---- persistent decode engine
 size_t kf_engine_workspace_bytes(const kf_engine_desc* d) { return d ? kf::engine_ws_bytes(d) : 0; }
 int kf_engine_create(kf_ctx* c, const kf_engine_desc* d, void* ws, size_t ws_bytes, kf_engine** out) {
-    CHKCTX(c);
-    if (!d || !ws || !out) return fail(KF_INVALID_ARGS, "kf_engine_create: null argument");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_create: not while capturing");
+    ENG_ENTER(c, d && ws && out, "argument");
+    ENG_NOT_CAPTURING(c);
     kf::EngineHost* h = nullptr;
     const char* why = "";
     const int rc = kf::engine_build(d, ws, ws_bytes, c->stream, &h, &why);
-    if (rc != KF_OK) return fail(rc, "kf_engine_create: %s", why);
-    kf_engine* e = new kf_engine();
-    e->h = h;
-    *out = e;
-    return KF_OK;
+    return ENG_WRAP(kf_engine, rc, why, h, out);
 }
 int kf_engine_step(kf_ctx* c, kf_engine* e, const kf_bf16* x_in, kf_bf16* x_out, const int32_t* d_state, int pos_bound) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_step: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     kf::engine_set_canonical(e->h, c->canonical);
     const int rc = kf::engine_step(e->h, c->stream, x_in, x_out, d_state, pos_bound);
-    if (rc < 0) return fail(rc, "kf_engine_step failed with %d", rc);
-    return rc;
+    return rc < 0 ? fail(rc, "kf_engine_step failed with %d", rc) : rc;
 }
 int kf_engine_step_head(kf_ctx* c, kf_engine* e, const kf_bf16* x_in, kf_bf16* x_out, int32_t* d_state, int pos_bound, int pick) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_step_head: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     kf::engine_set_canonical(e->h, c->canonical);
     const int rc = kf::engine_step(e->h, c->stream, x_in, x_out, d_state, pos_bound, pick ? 2 : 1);
-    if (rc < 0) return fail(rc, "kf_engine_step_head failed with %d (no head set?)", rc);
-    return rc;
+    return rc < 0 ? fail(rc, "kf_engine_step_head failed with %d (no head set?)", rc) : rc;
 }
 int kf_engine_steps_head(kf_ctx* c, kf_engine* e, kf_bf16* x_out, int32_t* d_state, int pos_bound, int n_steps) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_steps_head: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     if (n_steps < 1) return fail(KF_INVALID_ARGS, "kf_engine_steps_head: n_steps %d", n_steps);
     kf::engine_set_canonical(e->h, c->canonical);
     const int rc = kf::engine_step(e->h, c->stream, nullptr, x_out, d_state, pos_bound, 2, n_steps);
-    if (rc < 0) return fail(rc, "kf_engine_steps_head failed with %d (no head / embedding set?)", rc);
-    return rc;
+    return rc < 0 ? fail(rc, "kf_engine_steps_head failed with %d (no head / embedding set?)", rc) : rc;
 }
 int kf_engine_set_head(kf_ctx* c, kf_engine* e, const kf_weight* head_or_null, const kf_bf16* final_norm_w, kf_bf16* logits, int32_t* d_tokens_out) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_set_head: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_set_head: not while capturing");
-    const int rc = kf::engine_set_head(e->h, head_or_null, final_norm_w, logits, d_tokens_out);
-    if (rc != KF_OK) return fail(rc, "kf_engine_set_head: the in-launch head takes a bf16 [vocab, dim] matrix of the engine's width, a norm weight and a logits buffer");
-    return KF_OK;
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
+    return ok_or(kf::engine_set_head(e->h, head_or_null, final_norm_w, logits, d_tokens_out),
+                 "kf_engine_set_head: the in-launch head takes a bf16 [vocab, dim] matrix of the engine's width, a norm weight and a logits buffer");
 }
 size_t kf_engine_head_screen_bytes(int vocab, int dim) { return kf::head_screen_bytes(vocab, dim); }
 int kf_engine_set_head_screen(kf_ctx* c, kf_engine* e, void* buf, size_t bytes) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_set_head_screen: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_set_head_screen: not while capturing");
-    const int rc = kf::engine_set_head_screen(e->h, buf, bytes, c->stream);
-    if (rc != KF_OK) return fail(rc, "kf_engine_set_head_screen: needs a head set by kf_engine_set_head and a 256-byte aligned buffer of kf_engine_head_screen_bytes(vocab, dim) bytes");
-    return KF_OK;
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
+    return ok_or(kf::engine_set_head_screen(e->h, buf, bytes, c->stream),
+                 "kf_engine_set_head_screen: needs a head set by kf_engine_set_head and a 256-byte aligned buffer of kf_engine_head_screen_bytes(vocab, dim) bytes");
 }
 int kf_engine_screen_stats(kf_ctx* c, kf_engine* e, kf_engine_screen_statistics* out) {
-    CHKCTX(c);
-    if (!e || !e->h || !out) return fail(KF_INVALID_ARGS, "kf_engine_screen_stats: null argument");
+    ENG_ENTER(c, e && e->h && out, "argument");
     long long w[3];
-    const int rc = kf::engine_screen_stats(e->h, c->stream, w);
-    if (rc != KF_OK) return fail(rc, "kf_engine_screen_stats: HIP failure");
+    ENG_HIP(kf::engine_screen_stats(e->h, c->stream, w));
     out->screened_steps = w[0], out->rows_reranked = w[1], out->wg_fallbacks = w[2];
     return KF_OK;
 }
 int kf_engine_reset(kf_ctx* c, kf_engine* e) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_reset: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_reset: not while capturing");
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(KF_HIP_CHECK, "kf_engine_reset: HIP failure");
-    const int rc = kf::engine_reset(e->h, c->stream);
-    if (rc != KF_OK) return fail(rc, "kf_engine_reset: HIP failure");
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
+    ENG_HIP(kf::eng_then_sync(KF_OK, c->stream));
+    ENG_HIP(kf::engine_reset(e->h, c->stream));
     return KF_OK;
 }
 int kf_engine_set_embedding(kf_ctx* c, kf_engine* e, const kf_weight* embed_or_null, const int32_t* d_forced) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_set_embedding: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_set_embedding: not while capturing");
-    const int rc = kf::engine_set_embedding(e->h, embed_or_null, d_forced);
-    if (rc != KF_OK) return fail(rc, "kf_engine_set_embedding: the fused row read takes a bf16 table of the engine's width (other storages keep kf_embed_state)");
-    return KF_OK;
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
+    return ok_or(kf::engine_set_embedding(e->h, embed_or_null, d_forced),
+                 "kf_engine_set_embedding: the fused row read takes a bf16 table of the engine's width (other storages keep kf_embed_state)");
 }
 int kf_engine_served(kf_ctx* c, const kf_engine_desc* d, char* why, size_t why_bytes) {
     CHKCTX(c);
     const char* w = "";
-    const int rc = kf::engine_build(d, nullptr, 0, c->stream, nullptr, &w, true);
-    if (why && why_bytes > 0) snprintf(why, why_bytes, "%s", w);
-    if (rc == KF_OK) return KF_OK;
-    return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : fail(rc, "kf_engine_served: %s", w);
+    const int rc = kf::engine_build(d, nullptr, 0, c->stream, nullptr, &w, kf::ENG_DRY);
+    return eng_served(rc, __func__, w, why, why_bytes);
 }
 int kf_engine_tune(kf_ctx* c, kf_engine* e, kf_bf16* x_out, const int32_t* d_state, int pos_bound, int passes, float* us_before, float* us_after) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_tune: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_engine_tune: not while capturing");
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
     kf::engine_set_canonical(e->h, c->canonical);
     const int rc = kf::engine_tune(e->h, c->stream, x_out, d_state, pos_bound, passes, us_before, us_after);
-    if (rc < 0) return fail(rc, "kf_engine_tune failed with %d (no embedding table set, or a poll timed out)", rc);
-    return rc;
+    return rc < 0 ? fail(rc, "kf_engine_tune failed with %d (no embedding table set, or a poll timed out)", rc) : rc;
 }
 int kf_engine_stats(kf_ctx* c, kf_engine* e, int pos_bound, kf_engine_statistics* out) {
-    CHKCTX(c);
-    if (!e || !e->h || !out) return fail(KF_INVALID_ARGS, "kf_engine_stats: null argument");
+    ENG_ENTER(c, e && e->h && out, "argument");
     int w[14];
-    const int rc = kf::engine_stats(e->h, c->stream, pos_bound, w);
-    if (rc != KF_OK) return fail(rc, "kf_engine_stats: HIP failure");
+    ENG_HIP(kf::engine_stats(e->h, c->stream, pos_bound, w));
     for (int i = 0; i < 6; i++) out->sweeps[i] = w[i], out->delay[i] = w[7 + i];
     out->polls = w[6], out->tuned = w[13];
     return KF_OK;
 }
 int kf_engine_check(kf_ctx* c, kf_engine* e) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_engine_check: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     int err = 0;
-    const int rc = kf::engine_error_word(e->h, c->stream, &err);
-    if (rc != KF_OK) return fail(rc, "kf_engine_check: HIP failure");
+    ENG_HIP(kf::engine_error_word(e->h, c->stream, &err));
     if (err) return fail(KF_INTERNAL_ERR, "kf_engine: a hand-off poll timed out (error word 0x%x): the launch was not fully resident", err);
     return KF_OK;
 }
 // ---- XCD-confined decode engines (kf_xengine.hip)
-struct kf_xengine {
-    kf::XEngineHost* h;
-};
 size_t kf_xengine_workspace_bytes(const kf_engine_desc* d) { return d ? kf::xengine_ws_bytes(d) : 0; }
 int kf_xengine_create(kf_ctx* c, const kf_engine_desc* d, int n_seq, int64_t kv_seq_stride, void* ws, size_t ws_bytes, kf_xengine** out) {
-    CHKCTX(c);
-    if (!d || !ws || !out) return fail(KF_INVALID_ARGS, "kf_xengine_create: null argument");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_xengine_create: not while capturing");
+    ENG_ENTER(c, d && ws && out, "argument");
+    ENG_NOT_CAPTURING(c);
     if (n_seq < 1 || n_seq > KF_XENGINE_MAX_SEQ) return fail(KF_INVALID_ARGS, "kf_xengine_create: n_seq %d outside 1 .. %d (up to four sequences per XCD)", n_seq, KF_XENGINE_MAX_SEQ);
     kf::XEngineHost* h = nullptr;
     const char* why = "";
     const int rc = kf::xengine_build(d, n_seq, (long long)kv_seq_stride, ws, ws_bytes, c->stream, &h, &why);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_create: %s", why);
-    kf_xengine* e = new kf_xengine();
-    e->h = h;
-    *out = e;
-    return KF_OK;
+    return ENG_WRAP(kf_xengine, rc, why, h, out);
 }
 size_t kf_xengine_workspace_bytes_tp(const kf_engine_desc* d) { return d ? kf::xengine_ws_bytes_tp(d) : 0; }
 int kf_xengine_create_tp(kf_ctx* c, const kf_engine_desc* const* ds, int world, void* ws, size_t ws_bytes, kf_xengine** out) {
-    CHKCTX(c);
-    if (!ds || !ws || !out) return fail(KF_INVALID_ARGS, "kf_xengine_create_tp: null argument");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_xengine_create_tp: not while capturing");
+    ENG_ENTER(c, ds && ws && out, "argument");
+    ENG_NOT_CAPTURING(c);
     kf::XEngineHost* h = nullptr;
     const char* why = "";
     const int rc = kf::xengine_build_tp(ds, world, ws, ws_bytes, c->stream, &h, &why);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_create_tp: %s", why);
-    kf_xengine* e = new kf_xengine();
-    e->h = h;
-    *out = e;
-    return KF_OK;
+    return ENG_WRAP(kf_xengine, rc, why, h, out);
 }
 int kf_xengine_set_head_tp(kf_ctx* c, kf_xengine* e, const kf_weight* const* shards, const int32_t* row0, const kf_bf16* final_norm_w, kf_bf16* logits, int32_t* d_tokens_out, int tokens_stride) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_xengine_set_head_tp: null engine");
-    const int rc = kf::xengine_set_head_tp(e->h, shards, row0, final_norm_w, logits, d_tokens_out, tokens_stride);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_set_head_tp: eight bf16 [rows, dim] vocabulary shards in rank order (row0 = the rows before), a norm weight and a logits buffer");
-    return KF_OK;
+    ENG_ENTER(c, e && e->h, "engine");
+    return ok_or(kf::xengine_set_head_tp(e->h, shards, row0, final_norm_w, logits, d_tokens_out, tokens_stride),
+                 "kf_xengine_set_head_tp: eight bf16 [rows, dim] vocabulary shards in rank order (row0 = the rows before), a norm weight and a logits buffer");
 }
 int kf_xengine_served(kf_ctx* c, const kf_engine_desc* d, char* why, size_t why_bytes) {
     CHKCTX(c);
     if (!d) return fail(KF_INVALID_ARGS, "kf_xengine_served: null descriptor");
     const char* w = "";
-    const int rc = kf::xengine_build(d, 1, 0, nullptr, 0, c->stream, nullptr, &w, true);
-    if (why && why_bytes) snprintf(why, why_bytes, "%s", w);
-    if (rc == KF_OK) return KF_OK;
-    return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : fail(rc, "kf_xengine_served: %s", w);
+    const int rc = kf::xengine_build(d, 1, 0, nullptr, 0, c->stream, nullptr, &w, kf::ENG_DRY);
+    return eng_served(rc, __func__, w, why, why_bytes);
 }
 int kf_xengine_set_embedding(kf_ctx* c, kf_xengine* e, const kf_weight* embed, const int32_t* d_forced, int forced_stride) {
-    CHKCTX(c);
-    if (!e || !e->h || !embed) return fail(KF_INVALID_ARGS, "kf_xengine_set_embedding: null argument");
+    ENG_ENTER(c, e && e->h && embed, "argument");
     if (d_forced && forced_stride < 1) return fail(KF_INVALID_ARGS, "kf_xengine_set_embedding: forced_stride %d", forced_stride);
-    const int rc = kf::xengine_set_embedding(e->h, embed, d_forced, forced_stride);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_set_embedding: the row read inside the launch takes a bf16 table of the engine's width");
-    return KF_OK;
+    return ok_or(kf::xengine_set_embedding(e->h, embed, d_forced, forced_stride), "kf_xengine_set_embedding: the row read inside the launch takes a bf16 table of the engine's width");
 }
 int kf_xengine_set_head(kf_ctx* c, kf_xengine* e, const kf_weight* head_or_null, const kf_bf16* final_norm_w, kf_bf16* logits, int32_t* d_tokens_out, int tokens_stride) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_xengine_set_head: null engine");
-    const int rc = kf::xengine_set_head(e->h, head_or_null, final_norm_w, logits, d_tokens_out, tokens_stride);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_set_head: the in-launch head takes a bf16 [vocab, dim] matrix of the engine's width, a norm weight and a logits buffer");
-    return KF_OK;
+    ENG_ENTER(c, e && e->h, "engine");
+    return ok_or(kf::xengine_set_head(e->h, head_or_null, final_norm_w, logits, d_tokens_out, tokens_stride),
+                 "kf_xengine_set_head: the in-launch head takes a bf16 [vocab, dim] matrix of the engine's width, a norm weight and a logits buffer");
 }
 int kf_xengine_steps(kf_ctx* c, kf_xengine* e, kf_bf16* x_out, int32_t* d_state, int n_steps, int pick) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_xengine_steps: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     if (!c->canonical) return fail(KF_UNSUPPORTED_DATATYPE, "kf_xengine_steps: the XCD-confined engines run the canonical summation order only (kf_set_canonical(ctx, 1))");
     if (n_steps < 1 || (n_steps > 1 && !pick)) return fail(KF_INVALID_ARGS, "kf_xengine_steps: n_steps %d (several steps per launch need the pick inside)", n_steps);
     if (c->capturing) return fail(KF_INVALID_ARGS, "kf_xengine_steps: not while capturing (the launch's generation is a kernel argument the host counts: a replayed launch would repeat it)");
     const int rc = kf::xengine_steps(e->h, c->stream, d_state, x_out, pick ? 2 : 1, n_steps);
     if (rc == KF_UNSUPPORTED_DATATYPE) return fail(rc, "kf_xengine_steps: the form for this many sequences does not fit the LDS at this depth");
-    if (rc != KF_OK) return fail(rc, "kf_xengine_steps failed with %d (no embedding / head set?)", rc);
-    return KF_OK;
+    return rc == KF_OK ? KF_OK : fail(rc, "kf_xengine_steps failed with %d (no embedding / head set?)", rc);
 }
 int kf_xengine_check(kf_ctx* c, kf_xengine* e) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_xengine_check: null engine");
+    ENG_ENTER(c, e && e->h, "engine");
     int err = 0;
-    const int rc = kf::xengine_error_word(e->h, c->stream, &err);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_check: HIP failure");
+    ENG_HIP(kf::xengine_error_word(e->h, c->stream, &err));
     if (err) return fail(KF_INTERNAL_ERR, "kf_xengine: error word 0x%x (8: an XCD did not get 32 workgroups; 64: a position beyond the cache rows (TP form); others: a hand-off poll timed out -- the launch was not fully resident)", err);
     return KF_OK;
 }
 int kf_xengine_reset(kf_ctx* c, kf_xengine* e) {
-    CHKCTX(c);
-    if (!e || !e->h) return fail(KF_INVALID_ARGS, "kf_xengine_reset: null engine");
-    if (c->capturing) return fail(KF_INVALID_ARGS, "kf_xengine_reset: not while capturing");
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(KF_HIP_CHECK, "kf_xengine_reset: HIP failure");
-    const int rc = kf::xengine_reset(e->h, c->stream);
-    if (rc != KF_OK) return fail(rc, "kf_xengine_reset: HIP failure");
+    ENG_ENTER(c, e && e->h, "engine");
+    ENG_NOT_CAPTURING(c);
+    ENG_HIP(kf::eng_then_sync(KF_OK, c->stream));
+    ENG_HIP(kf::xengine_reset(e->h, c->stream));
     return KF_OK;
 }
 int kf_xengine_destroy(kf_xengine* e) {
-    if (e) {
-        kf::xengine_free(e->h);
-        delete e;
-    }
+    if (e) kf::xengine_free(e->h);
+    delete e;
     return KF_OK;
 }
-int kfdbg_xengine_variant(kf_xengine* e, int nwv, int depth) { return (e && e->h) ? kf::xengine_set_variant(e->h, nwv, depth) : -1; }
+// ---- diagnostics (NOT part of the ABI header; tests and scratch/ only): -1 = no engine / refused
+#define ENG_DBG(e, call) ((e) && (e)->h ? (call) : -1)
+int kfdbg_xengine_variant(kf_xengine* e, int nwv, int depth) { return ENG_DBG(e, kf::xengine_set_variant(e->h, nwv, depth)); }
 // the form the engines pick (kf::xengine_form, no HIP call) for a shape class (1 Qwen3-0.6B, 2 the 256-wide test shape, 3 1.7B, 4 4B, 5 8B, 6 the 8-on-1 test shape, 7 / 8 / 9
 // the TP ranks of 32B / 8B / 4B), a storage (kf::FMT_Q4P / FMT_Q1T / FMT_Q2T) and the hooks: out[5] = waves, ring depth, decoders per XCD, sequences per decoder, stamps;
 // -1: refused
@@ -1918,17 +1883,26 @@ int kfdbg_engine_form(int shape_class, int fmt, int canon, int stamps, int n_lay
     out[0] = f->shape_class, out[1] = f->fmt, out[2] = f->canon, out[3] = f->dbg, out[4] = (int)f->smem(n_layer);
     return 0;
 }
-int kfdbg_xengine_stamps_enable(kf_xengine* e, int seq, int wg, int max_steps) { return (e && e->h) ? kf::xengine_debug_enable(e->h, seq, wg, max_steps) : -1; }
-int kfdbg_xengine_stamps(kf_xengine* e, unsigned long long* h_out, int n_words) { return (e && e->h) ? kf::xengine_debug_read(e->h, h_out, n_words) : -1; }
-// ---- diagnostics (NOT part of the ABI header; tests and scratch/ only)
-// the per-phase stamps of one workgroup of the engine: enable (the diagnostic instantiation of the kernel serves the next launches), read
-int kfdbg_engine_stamps_enable(kf_engine* e, int wg) { return (e && e->h) ? kf::engine_debug_enable(e->h, wg) : -1; }
-int kfdbg_engine_stamps(kf_engine* e, unsigned long long* h_out, int n_words) { return (e && e->h) ? kf::engine_debug_read(e->h, h_out, n_words) : -1; }
-int kfdbg_engine_set_delays(kf_engine* e, const int* d6) {
-    if (!e || !e->h || !d6) return -1;
-    kf::engine_set_delays(e->h, d6);
-    return 0;
+// what a build answers for a descriptor, and why, without a device (kf::ENG_DRY_NO_DEVICE: every check of create but the CU count, in create's order; no device pointer is
+// dereferenced).  family: 0 the persistent engine, 1 the XCD-confined engines with n_seq sequences
+int kfdbg_engine_desc_refusal(int family, const kf_engine_desc* d, int n_seq, char* why, size_t n) {
+    const char* w = "";
+    const int rc = family == 0 ? kf::engine_build(d, nullptr, 0, nullptr, nullptr, &w, kf::ENG_DRY_NO_DEVICE)
+                               : kf::xengine_build(d, n_seq, 0, nullptr, 0, nullptr, nullptr, &w, kf::ENG_DRY_NO_DEVICE);
+    if (why && n > 0) snprintf(why, n, "%s", w);
+    return rc;
 }
+// what the setters answer for an operand of an engine `dim` wide (kf_engine_host.h): kind 0 the in-launch head (has_norm_and_logits: both given), 1 the embedding table
+int kfdbg_engine_operand_rule(int kind, const kf_weight* w, int dim, int has_norm_and_logits) {
+    const void* given = has_norm_and_logits ? (const void*)w : nullptr;
+    return kind == 0 ? kf::eng_head_rule(w, dim, given, given) : kf::eng_embed_rule(w, dim);
+}
+int kfdbg_xengine_stamps_enable(kf_xengine* e, int seq, int wg, int max_steps) { return ENG_DBG(e, kf::xengine_debug_enable(e->h, seq, wg, max_steps)); }
+int kfdbg_xengine_stamps(kf_xengine* e, unsigned long long* h_out, int n_words) { return ENG_DBG(e, kf::xengine_debug_read(e->h, h_out, n_words)); }
+// the per-phase stamps of one workgroup of the engine: enable (the diagnostic instantiation of the kernel serves the next launches), read
+int kfdbg_engine_stamps_enable(kf_engine* e, int wg) { return ENG_DBG(e, kf::engine_debug_enable(e->h, wg)); }
+int kfdbg_engine_stamps(kf_engine* e, unsigned long long* h_out, int n_words) { return ENG_DBG(e, kf::engine_debug_read(e->h, h_out, n_words)); }
+int kfdbg_engine_set_delays(kf_engine* e, const int* d6) { return ENG_DBG(e, d6 ? (kf::engine_set_delays(e->h, d6), 0) : -1); }
 // ---- int8 activations (include/kf_abi.h "int8 activations", "int8 activations for 4-bit layers"): the quantiser, then the products
 int kf_act_quant_i8(kf_ctx* c, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w, float eps, int rows, int dim, int8_t* q, float* step) {
     CHKCTX(c);
@@ -2104,10 +2078,8 @@ int kfdbg_set_knob(const char* name, long value) {
     return 0;
 }
 int kf_engine_destroy(kf_engine* e) {
-    if (e) {
-        kf::engine_free(e->h);
-        delete e;
-    }
+    if (e) kf::engine_free(e->h);
+    delete e;
     return KF_OK;
 }
 

@@ -40,6 +40,7 @@
 
 #include "kf_attn_plan.h"
 #include "kf_engine_common.h"
+#include "kf_engine_host.h"
 
 namespace kf {
 
@@ -1451,9 +1452,8 @@ __global__ void __launch_bounds__(C::NWV * 64) engine_kernel(const EngArgs a) {
 struct EngineHost {
     EngArgs args;
     const EngForm* form; /* what engine_step launches: engine_form of the model's shape, storage and depth, the order (form->canon) and the stamps */
-    int GQ, hd;
-    int dim, q_dim, kv_dim, ffn, n_kv, n_head;
-    int n_cu;
+    EngDims dm;
+    int GQ, n_cu;
     void* xmem;     /* the hand-off vectors every CU sweeps: device memory that is cached nowhere (hipDeviceMallocUncached), owned by the engine */
     size_t xbytes;
     void* ws;
@@ -1478,11 +1478,7 @@ static size_t eng_smem(int n_layer) {
 }
 template <class C>
 static int engine_go(EngineHost* E, hipStream_t st) {
-    static bool attr = false; /* the LDS ceiling of this instantiation, set at its first launch */
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)engine_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return KF_HIP_CHECK;
-        attr = true;
-    }
+    if (eng_raise_lds<C>(engine_kernel<C>) != KF_OK) return KF_HIP_CHECK;
     hipLaunchKernelGGL((engine_kernel<C>), dim3(C::NWG), dim3(C::NWV * 64), eng_smem<C>(E->args.n_layer), st, E->args);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
@@ -1504,16 +1500,17 @@ using EC3 = EngCfg<FMT, 2, 128, ENG_NWV, 2048, 2048, 1024, 6144, ENG_NWG, true, 
 
 // ---- the table of shapes: one row per shape class, read off a form of the shape
 struct EngShapeRow {
-    int sc, hd, dim, q_dim, kv_dim, ffn;
+    int sc;
+    EngDims dm;
 };
 template <class C>
 constexpr EngShapeRow eng_shape(int sc) {
-    return EngShapeRow{sc, C::HD, C::DIM, C::QD, C::KVD, C::FFN};
+    return EngShapeRow{sc, eng_dims_c<C>()};
 }
 static const EngShapeRow eng_shapes[] = {eng_shape<EC1<FMT_Q4P, false, true>>(1), eng_shape<EC2<FMT_Q4P, false, true>>(2), eng_shape<EC3<FMT_Q4P, false, true>>(3)};
 static const EngShapeRow* eng_shape_of(const kf_engine_desc* d) { /* nullptr: not instantiated */
     for (const EngShapeRow& s : eng_shapes)
-        if (d->head_dim == s.hd && d->dim == s.dim && d->n_head * d->head_dim == s.q_dim && d->n_kv * d->head_dim == s.kv_dim && d->ffn == s.ffn) return &s;
+        if (eng_dims_match(s.dm, eng_dims_of(d))) return &s;
     return nullptr;
 }
 
@@ -1549,38 +1546,6 @@ static bool eng_plans_match(const EngForm* f, const kf_engine_desc* d) {
     return true;
 }
 
-// one model's (one TP rank's) layer table out of its descriptor, for both engine families; qbias: the seven matrices' zero points of layer 0 (every layer, every rank: the
-// same).  *fmt_io: the storage every matrix of the model carries (0 on entry = not known yet): FMT_Q4P, FMT_Q1T or FMT_Q2T; NULL: 4-bit only
-int eng_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool qbias_set, bool& q4p_ok, int* fmt_io, bool allow_hot) {
-    const int hd = d->head_dim, q_dim = d->n_head * hd, kv_dim = d->n_kv * hd;
-    const int Ks[7] = {d->dim, d->dim, d->dim, q_dim, d->dim, d->dim, d->ffn}, Ms[7] = {q_dim, kv_dim, kv_dim, d->dim, d->ffn, d->ffn, d->dim};
-    for (int l = 0; l < d->n_layer; l++) {
-        const kf_engine_layer& Ly = d->layers[l];
-        if (Ly.hot_ffn && !allow_hot) return KF_UNSUPPORTED_DATATYPE;
-        if (!Ly.norm_in || !Ly.norm_post || !Ly.kcache || !Ly.vcache || (((uintptr_t)Ly.kcache | (uintptr_t)Ly.vcache) & 15) != 0) return KF_UNSUPPORTED_DATATYPE;
-        for (int j = 0; j < 7; j++) {
-            const kf_weight& w = Ly.w[j];
-            const int wf = gemv_fmt(mat_of(&w)), ef = wf == FMT_Q4 ? FMT_Q4P : (wf == FMT_Q1 ? FMT_Q1T : (wf == FMT_Q2 ? FMT_Q2T : -1));
-            if (ef < 0 || (!fmt_io && ef != FMT_Q4P) || (fmt_io && *fmt_io != 0 && *fmt_io != ef)) return KF_UNSUPPORTED_DATATYPE;
-            if (fmt_io) *fmt_io = ef;
-            if (w.ne0 != Ms[j] || w.ne1 != Ks[j] || w.qzeros || w.qscales || !w.gama || w.lGroup != 128 || (Ks[j] % 128) != 0 || ((uintptr_t)w.data & 15) != 0)
-                return KF_UNSUPPORTED_DATATYPE;
-            const long rows = j < 3 ? (long)q_dim + 2 * kv_dim : (j == 4 || j == 5 ? (long)d->ffn : (long)Ms[j]);
-            if (gemv_lpr_log2(32, Ks[j], rows) < 2) q4p_ok = false; /* the register-table form needs a group's four blocks in one aligned lane quad (1-bit: the four dwords of a block in one) */
-            tab[l].m[j].w = (g_u32x4)(uintptr_t)w.data;
-            tab[l].m[j].zero = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1);
-            tab[l].m[j].step = (g_u16)(uintptr_t)(w.gama + w.ne0 + w.ne1 + (size_t)w.ne0 * w.ne1 / w.lGroup);
-            if (l == 0 && !qbias_set) qbias[j] = (float)w.qBias;
-            else if (qbias[j] != (float)w.qBias) return KF_UNSUPPORTED_DATATYPE;
-        }
-        tab[l].norm_in = (g_u16)(uintptr_t)Ly.norm_in, tab[l].norm_post = (g_u16)(uintptr_t)Ly.norm_post;
-        tab[l].norm_q = (g_u16)(uintptr_t)Ly.q_norm, tab[l].norm_k = (g_u16)(uintptr_t)Ly.k_norm;
-        tab[l].kcache = (g_u16w)(uintptr_t)Ly.kcache, tab[l].vcache = (g_u16w)(uintptr_t)Ly.vcache;
-        tab[l].hot = (g_i32)(uintptr_t)Ly.hot_ffn; /* sparse forward: CS_Picker's hot[ffn] on the device (kf_abi.h kf_engine_layer::hot_ffn); NULL: dense */
-    }
-    return KF_OK;
-}
-
 // caller's workspace (cached device memory): [ws words 256 B] [EngLayer table] [XCD-local area: tickets | lqkv | lpart] [room for the exchange vectors, used
 // only when the uncached allocation is refused]
 size_t engine_ws_bytes(const kf_engine_desc* d) {
@@ -1591,7 +1556,7 @@ size_t engine_ws_bytes(const kf_engine_desc* d) {
     return b;
 }
 
-static void engine_release(EngineHost* E) {
+void engine_free(EngineHost* E) {
     if (!E) return;
     if (E->args.dbg) (void)hipFree(E->args.dbg);
     if (E->xmem) (void)hipFree(E->xmem);
@@ -1611,26 +1576,25 @@ static int engine_init_state(EngineHost* E, hipStream_t st) {
     return KF_OK;
 }
 
-// why != NULL: *why names the reason of a refusal; dry: validation only (kf_engine_served) -- nothing is allocated, ws may be NULL
-int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t st, EngineHost** out, const char** why, bool dry) {
-    const char* dummy;
-    if (!why) why = &dummy;
+// *why names the reason of a refusal; mode ENG_DRY: validation only (kf_engine_served) -- nothing is allocated, ws may be NULL; ENG_DRY_NO_DEVICE: the same without the
+// question to the device
+int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t st, EngineHost** out, const char** why, int mode) {
+    const bool dry = mode != ENG_BUILD;
     *why = "bad arguments";
     if (!d || (!dry && (!ws || !out)) || d->n_layer < 1 || !d->layers) return KF_INVALID_ARGS;
     if (!dry && (ws_bytes < engine_ws_bytes(d) || ((uintptr_t)ws & 255) != 0)) return KF_INVALID_ARGS;
-    const int hd = d->head_dim;
     *why = "head_dim must be 64 or 128 and n_head a multiple of n_kv";
-    if ((hd != 64 && hd != 128) || d->n_kv <= 0 || d->n_head % d->n_kv != 0) return KF_UNSUPPORTED_DATATYPE;
+    if (!eng_desc_heads_ok(d)) return KF_UNSUPPORTED_DATATYPE;
     const EngShapeRow* sh = eng_shape_of(d);
     *why = "model shape not instantiated: the engine's phase plans are compile-time types; built for Qwen3-0.6B (dim 1024, 16/8 heads of 128, ffn 3072), Qwen3-1.7B (dim 2048, same heads, ffn 6144; 4-bit layers) and the 256-wide test shape (dim 256, 4/2 heads of 64, ffn 512)";
     if (!sh) return KF_UNSUPPORTED_DATATYPE; /* not one of the instantiated model shapes: the per-layer launches remain */
-    int dev = 0, n_cu = 0;
+    int n_cu = ENG_NWG;
     *why = "HIP failure";
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) return KF_HIP_CHECK;
+    if (mode != ENG_DRY_NO_DEVICE && (eng_device_cus(&n_cu) != KF_OK || n_cu < 1)) return KF_HIP_CHECK;
     *why = "the device has fewer than 256 compute units: one resident workgroup per CU is the engine's premise";
     if (n_cu < ENG_NWG) return KF_UNSUPPORTED_DATATYPE; /* one resident workgroup per CU is the engine's premise */
     *why = "rope_table missing, kv_stride not a multiple of 8, or max_seq < 1";
-    if (!d->rope_table || (d->kv_stride % 8) != 0 || d->max_seq < 1) return KF_INVALID_ARGS;
+    if (!eng_desc_cache_ok(d)) return KF_INVALID_ARGS;
     *why = "layer storage not served: the engine is instantiated for 4-bit (RTN), 2-bit and 1-bit PackedQ layers in groups of 128 with 16-byte aligned blocks, every matrix the "
            "same storage, every layer the same shapes and zero points, norm weights and 16-byte aligned caches present; other storages keep the per-layer launches";
     std::vector<EngLayer> tab(d->n_layer);
@@ -1653,8 +1617,8 @@ int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t
     memset(E, 0, sizeof(*E));
     EngArgs& a = E->args;
     E->form = f;
-    E->GQ = d->n_head / d->n_kv, E->hd = hd, E->n_cu = ENG_NWG;
-    E->dim = d->dim, E->n_head = d->n_head, E->n_kv = d->n_kv, E->q_dim = d->n_head * hd, E->kv_dim = d->n_kv * hd, E->ffn = d->ffn;
+    const EngDims& dm = E->dm = eng_dims_of(d);
+    E->GQ = dm.n_head / dm.n_kv, E->n_cu = ENG_NWG;
     a.n_layer = d->n_layer;
     a.kv_stride = d->kv_stride;
     a.max_seq = d->max_seq;
@@ -1665,7 +1629,7 @@ int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t
     E->ws = ws, E->ws_bytes = ws_bytes;
     a.ws = reinterpret_cast<int*>(p), p += 256;
     a.layers = reinterpret_cast<const EngLayer*>(p), p += ((size_t)d->n_layer * sizeof(EngLayer) + 255) & ~(size_t)255;
-    a.loc = p, p += (eng_loc_bytes(E->GQ, hd) + 255) & ~(size_t)255;
+    a.loc = p, p += (eng_loc_bytes(E->GQ, dm.hd) + 255) & ~(size_t)255;
     {
         /* s_sleep units (one trip of the wait loop ~ 40 ns) behind the own publish: x, q|k|v, slice partials, ao, xB, act.  Tuned on the 0.6B shape at 2 k keys
            (scratch/eng_ab.py): after the drains were removed 12,8,12,12,12,12 0.455 ms/step, 16,8,12,16,16,16 0.452, 20,12,16,20,20,20 0.464, 24,12,16,24,24,24 0.474 */
@@ -1676,36 +1640,26 @@ int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t
     }
     // The vectors that cross XCDs live in uncached device memory: an sc1 sweep of a cached (hipMalloc) line costs 75 ns per KB and CU, of an uncached one 43
     // (scratch/ub_handoff3.hip).  The XCD-local vectors (lqkv, lpart) stay in the caller's cached workspace: they are meant to live in that XCD's L2.
-    E->xbytes = (size_t)eng_xoff(E->dim, E->q_dim, E->kv_dim, E->ffn, hd).end * 4;
+    E->xbytes = (size_t)eng_xoff(dm.dim, dm.q_dim, dm.kv_dim, dm.ffn, dm.hd).end * 4;
     E->xmem = nullptr;
     if (hipExtMallocWithFlags(&E->xmem, E->xbytes, hipDeviceMallocUncached) != hipSuccess) {
         (void)hipGetLastError();
         E->xmem = nullptr; /* the cached workspace serves (slower sweeps, same protocol) */
     }
     a.xch = reinterpret_cast<uint32_t*>(E->xmem ? E->xmem : (void*)p);
-    if (engine_init_state(E, st) != KF_OK ||
-        hipMemcpyAsync(const_cast<EngLayer*>(a.layers), tab.data(), tab.size() * sizeof(EngLayer), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        engine_release(E);
-        *why = "HIP failure while initialising the workspace";
+    if (eng_upload_layers(engine_init_state(E, st), a.layers, tab, st, why) != KF_OK) {
+        engine_free(E);
         return KF_HIP_CHECK;
     }
     *out = E;
-    *why = "";
     return KF_OK;
 }
-void engine_free(EngineHost* E) { engine_release(E); }
 // the form for another order or the stamps: the model's shape, storage and depth, which create found a form for (every twin has the same plans and LDS)
 static void engine_repick(EngineHost* E, bool canon) { E->form = engine_form(E->form->shape_class, E->form->fmt, canon, E->args.dbg != nullptr, E->args.n_layer); }
 // diagnostic runs: per-phase wall-clock stamps of one workgroup (the DBG instantiation of the kernel)
 int engine_debug_enable(EngineHost* E, int wg) {
     EngArgs& a = E->args;
-    if (!a.dbg) {
-        if (hipMalloc(&a.dbg, (size_t)a.n_layer * 2 * 16 * 8) != hipSuccess) {
-            a.dbg = nullptr;
-            return KF_HIP_CHECK;
-        }
-    }
-    (void)hipMemset(a.dbg, 0, (size_t)a.n_layer * 2 * 16 * 8);
+    if (eng_stamps_zeroed(&a.dbg, (size_t)a.n_layer * 2 * 16 * 8) != KF_OK) return KF_HIP_CHECK;
     a.dbg_wg = wg;
     engine_repick(E, E->form->canon);
     return KF_OK;
@@ -1715,11 +1669,8 @@ void engine_set_delays(EngineHost* E, const int* d6) { /* every slice count */
         for (int i = 0; i < 6; i++) E->delay_tab[n][i] = d6[i];
 }
 int engine_debug_read(EngineHost* E, unsigned long long* h_out, int n_words) {
-    if (!E->args.dbg) return 0;
     const int have = E->args.n_layer * 2 * 16;
-    const int n = n_words < have ? n_words : have;
-    if (hipMemcpy(h_out, E->args.dbg, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return n;
+    return eng_stamps_read(E->args.dbg, h_out, n_words < have ? n_words : have);
 }
 
 // 1: this position bound is outside what the engine serves (the caller runs the multi-launch path), < 0 error
@@ -1731,14 +1682,14 @@ int engine_step(EngineHost* E, hipStream_t st, const uint16_t* x_in, uint16_t* x
     a.n_steps = n_steps;
     a.head_on = with_head ? 1 : 0;
     a.d_state_w = with_head == 2 ? const_cast<int32_t*>(d_state) : nullptr; /* 2: head + greedy pick + state update; 1: logits only */
-    const AttnSlices sl = attn_slices(pos_bound, E->n_kv, E->GQ);
+    const AttnSlices sl = attn_slices(pos_bound, E->dm.n_kv, E->GQ);
     const int nsp = sl.n_splits;
-    if (sl.nw != 4 || E->n_kv * nsp > E->n_cu) return 1; /* the 8-wave slice form and more slices than workgroups are not restated here */
+    if (sl.nw != 4 || E->dm.n_kv * nsp > E->n_cu) return 1; /* the 8-wave slice form and more slices than workgroups are not restated here */
     a.nsp = nsp, a.chunk = sl.chunk;
     for (int i = 0; i < 6; i++) a.delay[i] = E->delay_tab[nsp][i];
-    int e = (E->n_head * E->hd + E->n_cu - 1) / E->n_cu, me = 1;
+    int e = (E->dm.n_head * E->dm.hd + E->n_cu - 1) / E->n_cu, me = 1;
     while (me < e) me <<= 1;
-    if (me > E->hd || me > 64) return 1;
+    if (me > E->dm.hd || me > 64) return 1;
     a.merge_e = me; /* = EngCfg::ME of the instantiated shapes (whole workgroups: q_dim / n_cu) */
     a.x_in = x_in, a.x_out = x_out, a.d_state = d_state;
     return E->form->go(E, st);
@@ -1749,7 +1700,7 @@ int engine_set_embedding(EngineHost* E, const kf_weight* w, const int32_t* d_for
         E->args.emb = nullptr, E->args.d_forced = nullptr, E->args.emb_rows = 0;
         return KF_OK;
     }
-    if (w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data) return KF_UNSUPPORTED_DATATYPE;
+    if (eng_embed_rule(w, E->dm.dim) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
     E->args.emb = reinterpret_cast<const uint16_t*>(w->data), E->args.d_forced = d_forced, E->args.emb_rows = w->ne0;
     return KF_OK;
 }
@@ -1761,10 +1712,7 @@ int engine_set_head(EngineHost* E, const kf_weight* w, const uint16_t* norm_w, u
         a.head_w = nullptr, a.head_norm = nullptr, a.logits = nullptr, a.d_tokens_out = nullptr, a.vocab = 0;
         return KF_OK;
     }
-    if (w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || !norm_w || !logits || w->ne0 < 64)
-        return KF_UNSUPPORTED_DATATYPE;
-    // the compile-time geometry of the head phases must be the mat-vec launcher's for this matrix (same lanes per row: same summation order)
-    if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE;
+    if (eng_head_rule(w, E->dm.dim, norm_w, logits) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
     a.head_w = (g_u32x4)(uintptr_t)w->data, a.head_norm = (g_u16)(uintptr_t)norm_w, a.logits = logits, a.d_tokens_out = d_tokens_out, a.vocab = w->ne0;
     return KF_OK;
 }
@@ -1775,12 +1723,12 @@ int engine_set_head_screen(EngineHost* E, void* buf, size_t bytes, hipStream_t s
     a.screen_q = nullptr, a.screen_rows = nullptr;
     if (!buf) return KF_OK;
     if (!a.head_w) return KF_INVALID_ARGS;
-    const size_t need = head_screen_bytes(a.vocab, E->dim);
+    const size_t need = head_screen_bytes(a.vocab, E->dm.dim);
     if (need == 0 || bytes < need || ((uintptr_t)buf & 255) != 0) return KF_INVALID_ARGS;
-    const int rc = head_screen_build(reinterpret_cast<const uint16_t*>((uintptr_t)a.head_w), a.vocab, E->dim, buf, bytes, st);
+    const int rc = head_screen_build(reinterpret_cast<const uint16_t*>((uintptr_t)a.head_w), a.vocab, E->dm.dim, buf, bytes, st);
     if (rc != KF_OK) return rc;
     a.screen_q = (g_u32x4)(uintptr_t)buf;
-    a.screen_rows = (const u32x2 KF_GLOBAL*)((uintptr_t)buf + (((size_t)a.vocab * E->dim + 255) & ~(size_t)255));
+    a.screen_rows = (const u32x2 KF_GLOBAL*)((uintptr_t)buf + (((size_t)a.vocab * E->dm.dim + 255) & ~(size_t)255));
     return KF_OK;
 }
 // {screened steps, rows re-ranked, workgroup fall-backs} since creation / the last reset
@@ -1790,12 +1738,7 @@ int engine_screen_stats(EngineHost* E, hipStream_t st, long long* out3) {
     for (int i = 0; i < 3; i++) out3[i] = (long long)w[i];
     return KF_OK;
 }
-int engine_error_word(EngineHost* E, hipStream_t st, int* h_err) {
-    int v[2] = {0, 0};
-    if (hipMemcpyAsync(v, E->args.ws, sizeof(v), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KF_HIP_CHECK;
-    *h_err = v[1];
-    return KF_OK;
-}
+int engine_error_word(EngineHost* E, hipStream_t st, int* h_err) { return eng_read_error_word(E->args.ws, st, h_err); }
 void engine_set_canonical(EngineHost* E, int on) { engine_repick(E, on != 0); }
 
 // ---- self-calibration of the first-sweep delays.  The hand-off protocol is correct for ANY delay -- a sweep that comes too early is repeated -- but a
@@ -1812,7 +1755,7 @@ static float eng_time_launches(EngineHost* E, hipStream_t st, uint16_t* x_out, c
 }
 int engine_tune(EngineHost* E, hipStream_t st, uint16_t* x_out, const int32_t* d_state, int pos_bound, int passes, float* us_before, float* us_after) {
     if (!E->args.emb || !x_out || !d_state || pos_bound < 0 || pos_bound >= E->args.max_seq) return KF_INVALID_ARGS;
-    const int nsp = attn_slices(pos_bound, E->n_kv, E->GQ).n_splits; /* 1 .. KF_ATTN_MAX_SPLITS */
+    const int nsp = attn_slices(pos_bound, E->dm.n_kv, E->GQ).n_splits; /* 1 .. KF_ATTN_MAX_SPLITS */
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess) return KF_HIP_CHECK;
     if (hipEventCreate(&e1) != hipSuccess) {
@@ -1869,16 +1812,12 @@ int engine_stats(EngineHost* E, hipStream_t st, int pos_bound, int* out14) {
     int w[16];
     if (hipMemcpyAsync(w, E->args.ws, sizeof(w), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KF_HIP_CHECK;
     for (int i = 0; i < 7; i++) out14[i] = w[8 + i];
-    const int nsp = attn_slices(pos_bound < 0 ? 0 : pos_bound, E->n_kv, E->GQ).n_splits;
+    const int nsp = attn_slices(pos_bound < 0 ? 0 : pos_bound, E->dm.n_kv, E->GQ).n_splits;
     for (int i = 0; i < 6; i++) out14[7 + i] = E->delay_tab[nsp][i];
     out14[13] = E->tuned[nsp];
     return KF_OK;
 }
 // after a timed-out poll (the error word latches and every later launch returns at once): all granules back to "not written", epoch 1, error word cleared
-int engine_reset(EngineHost* E, hipStream_t st) {
-    const int rc = engine_init_state(E, st);
-    if (rc != KF_OK) return rc;
-    return hipStreamSynchronize(st) == hipSuccess ? KF_OK : KF_HIP_CHECK;
-}
+int engine_reset(EngineHost* E, hipStream_t st) { return eng_then_sync(engine_init_state(E, st), st); }
 
 }  // namespace kf

@@ -1,7 +1,8 @@
 // kf_engine_common.h -- what the two persistent decode engines share: kf_engine.hip (one sequence on all 256 CUs, weights in registers ahead of every hand-off) and
 // kf_xengine.hip (round 5: eight independent sequences, one per XCD, every hand-off through that XCD's L2, weights streamed): the device tables, the tagged-granule
 // accessors, and the mat-vec phase geometry as compile-time types (the lanes per row of the mat-vec rule, gemv_lpr_log2, for the same matrices, and the rows per wave step and
-// steps per row that follow: the canonical summation order is a property of the matrix shape, not of how many workgroups share the rows).
+// steps per row that follow: the canonical summation order is a property of the matrix shape, not of how many workgroups share the rows).  Device code and the tables it
+// reads; what the two host sides share is kf_engine_host.h.
 #pragma once
 #include <stdint.h>
 
@@ -36,8 +37,6 @@ struct EngLayer {
     g_u16w kcache, vcache; /* layer base */
     g_i32 hot;             /* sparse forward: CS_Picker's hot[ffn] (1 = the gate / up row is computed, D_matmul_sparse); NULL: dense */
 };
-// one model's (one TP rank's) layer table out of its descriptor, validated for both engine families (kf_engine.hip)
-int eng_fill_layers(const kf_engine_desc* d, EngLayer* tab, float* qbias, bool qbias_set, bool& q4p_ok, int* fmt_io = nullptr, bool allow_hot = false);
 
 constexpr int eng_gran_dw(int n) { return ((n * 4 + 255) & ~255) / 4; }
 constexpr int pow2_ceil(int v) {

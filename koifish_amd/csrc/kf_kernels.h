@@ -129,6 +129,9 @@ struct Knobs {
     int score_form = -1;  /* kf_head_logprob's fused route: >= 0 the tile form (G3_BIG / G3_SMALL) instead of the rule's (scratch/ub_score.py measures both) */
 };
 extern Knobs g_knobs;
+// ---- the decode engines.  Two families, two kernels, each with its own host side below; the host rules both state -- served descriptors, heads and embedding tables, the
+// layer table, the error word, the per-device LDS ceiling -- are kf_engine_host.h
+enum { ENG_BUILD = 0, ENG_DRY = 1, ENG_DRY_NO_DEVICE = 2 }; /* engine_build / xengine_build: create; validate only; validate without asking the device for its CUs */
 // ---- the persistent decode engine: one sequence on every CU (kf_engine.hip)
 struct EngineHost;
 struct CPlan { /* one mat-vec phase of an engine, a compile-time figure of its model shape (kf_engine_common.h c_plan, PlanT) */
@@ -145,7 +148,7 @@ struct EngForm {
 // THE choice of form, at create and when the order or the stamps change (no HIP call): nullptr = refused (no form for this shape and storage, or its LDS does not fit)
 const EngForm* engine_form(int shape_class, int fmt, bool canon, bool stamps, int n_layer);
 size_t engine_ws_bytes(const kf_engine_desc* d);
-int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t st, EngineHost** out, const char** why = nullptr, bool dry = false);
+int engine_build(const kf_engine_desc* d, void* ws, size_t ws_bytes, hipStream_t st, EngineHost** out, const char** why, int mode = ENG_BUILD);
 int engine_tune(EngineHost* E, hipStream_t st, uint16_t* x_out, const int32_t* d_state, int pos_bound, int passes, float* us_before, float* us_after);
 int engine_stats(EngineHost* E, hipStream_t st, int pos_bound, int* out14);
 int engine_step(EngineHost* E, hipStream_t st, const uint16_t* x_in, uint16_t* x_out, const int32_t* d_state, int pos_bound, int with_head = 0, int n_steps = 1); /* 1: not served */
@@ -178,10 +181,10 @@ struct XForm {
 // THE choice of form, at create and at every launch (no HIP call): nullptr = refused (no form for this shape, storage and count, or none fits the LDS at this depth)
 const XForm* xengine_form(int shape_class, int fmt, int n_seq, int n_layer, bool stamps, bool two_wpc);
 size_t xengine_ws_bytes(const kf_engine_desc* d);
-int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why = nullptr, bool dry = false);
+int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why, int mode = ENG_BUILD);
 int xengine_steps(XEngineHost* E, hipStream_t st, int32_t* d_state, uint16_t* x_out, int with_head, int n_steps);
 size_t xengine_ws_bytes_tp(const kf_engine_desc* rank0);                                /* tensor parallel over the XCDs: one sequence, rank r on XCD r */
-int xengine_build_tp(const kf_engine_desc* const* ranks, int world, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why = nullptr);
+int xengine_build_tp(const kf_engine_desc* const* ranks, int world, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why);
 int xengine_set_head_tp(XEngineHost* E, const kf_weight* const* shards, const int* row0, const uint16_t* norm_w, uint16_t* logits, int32_t* d_tokens_out, int tokens_stride);
 int xengine_set_embedding(XEngineHost* E, const kf_weight* w, const int32_t* d_forced, int forced_stride);
 int xengine_set_head(XEngineHost* E, const kf_weight* w, const uint16_t* norm_w, uint16_t* logits, int32_t* d_tokens_out, int tokens_stride);

@@ -35,7 +35,8 @@ static_assert(XC7::FUSED && XC8::FUSED && XC9::FUSED, "the TP forms multiply q |
 
 // ---- the table of shapes: one row per shape class, read off a form of the shape (the dimensions, TP, the fused q | k | v copy and the exchange area are the same in every form)
 struct XShape {
-    int sc, hd, dim, q_dim, kv_dim, ffn;
+    int sc;
+    EngDims dm;
     bool tp, fused;
     int loc_dw;  /* a decoder's XCD-local exchange area (dwords) */
     int max_seq; /* the most sequences served */
@@ -43,7 +44,7 @@ struct XShape {
 };
 template <class C>
 constexpr XShape xe_shape(int sc, int max_seq, bool lowbit) {
-    return XShape{sc, C::HD, C::DIM, C::QD, C::KVD, C::FFN, C::TP, C::FUSED, C::loc_dw, max_seq, lowbit};
+    return XShape{sc, eng_dims_c<C>(), C::TP, C::FUSED, C::loc_dw, max_seq, lowbit};
 }
 // more than 8 sequences: two or four per decoder (XCfg::NB) for the 16 / 8-head shapes; the GQA-4 / GQA-8 shapes would need two workgroups per CU, 2 x 78 KB (2 x 98 KB) of
 // activations in LDS
@@ -52,7 +53,7 @@ static const XShape xe_shapes[] = {xe_shape<XC1<12, 2, false, 1>>(1, XE_MAXSEQ, 
                                    xe_shape<XC7>(7, XE_NXCD, false), xe_shape<XC8>(8, XE_NXCD, false), xe_shape<XC9>(9, XE_NXCD, false)};
 static const XShape* xe_shape_of(const kf_engine_desc* d, bool tp) { /* nullptr: not instantiated */
     for (const XShape& s : xe_shapes)
-        if (s.tp == tp && d->head_dim == s.hd && d->dim == s.dim && d->n_head * d->head_dim == s.q_dim && d->n_kv * d->head_dim == s.kv_dim && d->ffn == s.ffn) return &s;
+        if (s.tp == tp && eng_dims_match(s.dm, eng_dims_of(d))) return &s;
     return nullptr;
 }
 
@@ -166,8 +167,7 @@ static int xe_make(const kf_engine_desc* const* ds, const XShape* sh, int fmt, i
     XEngineHost* E = new XEngineHost();
     memset(E, 0, sizeof(*E));
     XArgs& a = E->args;
-    E->shape_class = sh->sc, E->fmt = fmt, E->dim = d->dim, E->q_dim = d->n_head * d->head_dim, E->kv_dim = d->n_kv * d->head_dim, E->ffn = d->ffn, E->n_head = d->n_head,
-    E->n_kv = d->n_kv, E->hd = d->head_dim;
+    E->shape_class = sh->sc, E->fmt = fmt, E->dm = eng_dims_of(d);
     a.n_layer = d->n_layer, a.n_seq = n_seq, a.kv_seq_stride = kv_seq_stride, a.kv_stride = d->kv_stride, a.max_seq = d->max_seq;
     a.eps = d->rms_eps, a.qk_eps = d->qk_eps, a.rope_table = d->rope_table;
     for (int j = 0; j < 7; j++) a.qbias[j] = qbias[j];
@@ -194,24 +194,19 @@ static int xe_make(const kf_engine_desc* const* ds, const XShape* sh, int fmt, i
             }
         }
     }
-    if (xengine_init_state(E, st) != KF_OK || hipMemcpyAsync(const_cast<EngLayer*>(a.layers), tab.data(), tab.size() * sizeof(EngLayer), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
+    if (eng_upload_layers(xengine_init_state(E, st), a.layers, tab, st, why) != KF_OK) {
         xengine_free(E);
-        *why = "HIP failure while initialising the workspace";
         return KF_HIP_CHECK;
     }
     *out = E;
-    *why = "";
     return KF_OK;
 }
-int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why, bool dry) {
-    const char* dummy;
-    if (!why) why = &dummy;
+int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why, int mode) {
+    const bool dry = mode != ENG_BUILD; /* ENG_DRY: validation only, nothing allocated, ws may be NULL; ENG_DRY_NO_DEVICE: the same without the question to the device */
     *why = "bad arguments";
     if (!d || (!dry && (!ws || !out)) || d->n_layer < 1 || !d->layers || n_seq < 1 || n_seq > XE_MAXSEQ || kv_seq_stride < 0) return KF_INVALID_ARGS;
-    const int hd = d->head_dim;
     *why = "head_dim must be 64 or 128 and n_head a multiple of n_kv";
-    if ((hd != 64 && hd != 128) || d->n_kv <= 0 || d->n_head % d->n_kv != 0) return KF_UNSUPPORTED_DATATYPE;
+    if (!eng_desc_heads_ok(d)) return KF_UNSUPPORTED_DATATYPE;
     const XShape* sh = xe_shape_of(d, false);
     *why = "model shape not instantiated for the XCD-confined engine: built for Qwen3-0.6B (dim 1024, 16/8 heads of 128, ffn 3072), Qwen3-1.7B (dim 2048, same heads, ffn 6144), Qwen3-4B "
            "(dim 2560, 32/8 heads, ffn 9728), Qwen3-8B (dim 4096, 32/8 heads, ffn 12288) and the 256-wide test shape";
@@ -223,13 +218,13 @@ int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, v
         *why = "workspace too small or not 256-byte aligned";
         return KF_INVALID_ARGS;
     }
-    int dev = 0, n_cu = 0;
+    int n_cu = XE_GRID;
     *why = "HIP failure";
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return KF_HIP_CHECK;
+    if (mode != ENG_DRY_NO_DEVICE && eng_device_cus(&n_cu) != KF_OK) return KF_HIP_CHECK;
     *why = "the device does not show 256 compute units (8 XCDs of 32): one resident workgroup per CU, 32 per XCD, is the premise";
     if (n_cu != XE_GRID) return KF_UNSUPPORTED_DATATYPE;
     *why = "rope_table missing, kv_stride not a multiple of 8, or max_seq < 1";
-    if (!d->rope_table || (d->kv_stride % 8) != 0 || d->max_seq < 1) return KF_INVALID_ARGS;
+    if (!eng_desc_cache_ok(d)) return KF_INVALID_ARGS;
     *why = "layer storage not served: 4-bit (RTN), 2-bit or 1-bit (YinYang) PackedQ layers in groups of 128 with 16-byte aligned blocks, every matrix the same storage, every layer the same shapes (FFN dense or with a hot-row mask)";
     std::vector<EngLayer> tab(d->n_layer);
     float qbias[7] = {0};
@@ -248,8 +243,6 @@ int xengine_build(const kf_engine_desc* d, int n_seq, long long kv_seq_stride, v
     return xe_make(&d, sh, fmt, n_seq, kv_seq_stride, tab, qbias, ws, ws_bytes, st, out, why);
 }
 int xengine_build_tp(const kf_engine_desc* const* ds, int world, void* ws, size_t ws_bytes, hipStream_t st, XEngineHost** out, const char** why) {
-    const char* dummy;
-    if (!why) why = &dummy;
     *why = "bad arguments";
     if (!ds || !ws || !out || world < 1) return KF_INVALID_ARGS;
     *why = "tensor parallel over the XCDs: exactly 8 ranks (one per XCD)";
@@ -266,14 +259,14 @@ int xengine_build_tp(const kf_engine_desc* const* ds, int world, void* ws, size_
         *why = "workspace too small or not 256-byte aligned";
         return KF_INVALID_ARGS;
     }
-    int dev = 0, n_cu = 0;
+    int n_cu = 0;
     *why = "HIP failure";
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return KF_HIP_CHECK;
+    if (eng_device_cus(&n_cu) != KF_OK) return KF_HIP_CHECK;
     *why = "the device does not show 256 compute units (8 XCDs of 32): one resident workgroup per CU, 32 per XCD, is the premise";
     if (n_cu != XE_GRID) return KF_UNSUPPORTED_DATATYPE;
     *why = "rope_table missing, kv_stride not a multiple of 8, max_seq < 1, or the ranks disagree";
     for (int r = 0; r < world; r++)
-        if (!ds[r]->rope_table || (ds[r]->kv_stride % 8) != 0 || ds[r]->max_seq < 1 || ds[r]->max_seq != d->max_seq || ds[r]->kv_stride != d->kv_stride || ds[r]->rms_eps != d->rms_eps ||
+        if (!eng_desc_cache_ok(ds[r]) || ds[r]->max_seq != d->max_seq || ds[r]->kv_stride != d->kv_stride || ds[r]->rms_eps != d->rms_eps ||
             ds[r]->qk_eps != d->qk_eps)
             return KF_INVALID_ARGS;
     *why = "layer storage not served: 4-bit PackedQ (RTN) layers in groups of 128 with 16-byte aligned blocks, dense FFN, every layer and rank the same shapes";
@@ -292,8 +285,7 @@ int xengine_set_head_tp(XEngineHost* E, const kf_weight* const* ws, const int* r
     long at = 0;
     for (int r = 0; r < XE_NXCD; r++) {
         const kf_weight* w = ws[r];
-        if (!w || w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || w->ne0 < 64 || row0[r] != at) return KF_UNSUPPORTED_DATATYPE;
-        if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
+        if (eng_head_rule(w, E->dm.dim, norm_w, logits) != KF_OK || row0[r] != at) return KF_UNSUPPORTED_DATATYPE;
         a.head_w_r[r] = (g_u32x4)(uintptr_t)w->data, a.logits_r[r] = logits + at, a.vocab_r[r] = w->ne0, a.row0_r[r] = row0[r];
         at += w->ne0;
     }
@@ -317,7 +309,7 @@ int xengine_steps(XEngineHost* E, hipStream_t st, int32_t* d_state, uint16_t* x_
     return rc;
 }
 int xengine_set_embedding(XEngineHost* E, const kf_weight* w, const int32_t* d_forced, int forced_stride) {
-    if (!w || w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data) return KF_UNSUPPORTED_DATATYPE;
+    if (eng_embed_rule(w, E->dm.dim) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
     E->args.emb = reinterpret_cast<const uint16_t*>(w->data), E->args.emb_rows = w->ne0, E->args.d_forced = d_forced, E->args.forced_stride = forced_stride;
     return KF_OK;
 }
@@ -328,23 +320,12 @@ int xengine_set_head(XEngineHost* E, const kf_weight* w, const uint16_t* norm_w,
         a.head_w = nullptr, a.head_norm = nullptr, a.logits = nullptr, a.d_tokens_out = nullptr, a.vocab = 0;
         return KF_OK;
     }
-    if (w->type != KF_BF16 || w->quant != KF_QUANT_GROUP || w->qzeros || w->ne1 != E->dim || !w->data || ((uintptr_t)w->data & 15) != 0 || !norm_w || !logits || w->ne0 < 64)
-        return KF_UNSUPPORTED_DATATYPE;
-    if (gemv_lpr_log2(8, E->dim, w->ne0) != gemv_lpr_log2(8, E->dim, 1L << 20)) return KF_UNSUPPORTED_DATATYPE; /* same lanes per row as the mat-vec launcher: same summation order */
+    if (eng_head_rule(w, E->dm.dim, norm_w, logits) != KF_OK) return KF_UNSUPPORTED_DATATYPE;
     a.head_w = (g_u32x4)(uintptr_t)w->data, a.head_norm = (g_u16)(uintptr_t)norm_w, a.logits = logits, a.d_tokens_out = d_tokens_out, a.tokens_stride = tokens_stride, a.vocab = w->ne0;
     return KF_OK;
 }
-int xengine_error_word(XEngineHost* E, hipStream_t st, int* h_err) {
-    int v[2] = {0, 0};
-    if (hipMemcpyAsync(v, E->args.ws, sizeof(v), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KF_HIP_CHECK;
-    *h_err = v[1];
-    return KF_OK;
-}
-int xengine_reset(XEngineHost* E, hipStream_t st) {
-    const int rc = xengine_init_state(E, st);
-    if (rc != KF_OK) return rc;
-    return hipStreamSynchronize(st) == hipSuccess ? KF_OK : KF_HIP_CHECK;
-}
+int xengine_error_word(XEngineHost* E, hipStream_t st, int* h_err) { return eng_read_error_word(E->args.ws, st, h_err); }
+int xengine_reset(XEngineHost* E, hipStream_t st) { return eng_then_sync(xengine_init_state(E, st), st); }
 int xengine_set_variant(XEngineHost* E, int nwv, int depth) {
     if (nwv != -2) return -1;
     E->two_wpc = depth != 0; /* A/B hook: depth != 0 = 9 .. 16 sequences through the round-5 form (two decoders per XCD) instead of the batched one */
@@ -355,18 +336,10 @@ int xengine_debug_enable(XEngineHost* E, int seq, int wg, int max_steps) {
     const size_t bytes = (size_t)max_steps * a.n_layer * 64 * 8;
     if (a.dbg) (void)hipFree(a.dbg), a.dbg = nullptr;
     if (seq < 0) return KF_OK;
-    if (hipMalloc(&a.dbg, bytes) != hipSuccess) {
-        a.dbg = nullptr;
-        return KF_HIP_CHECK;
-    }
-    (void)hipMemset(a.dbg, 0, bytes);
+    if (eng_stamps_zeroed(&a.dbg, bytes) != KF_OK) return KF_HIP_CHECK;
     a.dbg_seq = seq, a.dbg_wg = wg, a.dbg_steps = max_steps;
     return KF_OK;
 }
-int xengine_debug_read(XEngineHost* E, unsigned long long* h_out, int n_words) {
-    if (!E->args.dbg) return 0;
-    if (hipMemcpy(h_out, E->args.dbg, (size_t)n_words * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return n_words;
-}
+int xengine_debug_read(XEngineHost* E, unsigned long long* h_out, int n_words) { return eng_stamps_read(E->args.dbg, h_out, n_words); }
 
 }  // namespace kf

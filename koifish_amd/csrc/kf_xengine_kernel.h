@@ -28,10 +28,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
 #pragma once
 #include "kf_engine_common.h"
+#include "kf_engine_host.h"
 
 namespace kf {
 
@@ -1584,7 +1583,7 @@ __global__ void __launch_bounds__(C::NWV * 64, (C::NWV * C::WPC + 3) / 4 /* wave
 struct XEngineHost {
     XArgs args;
     int shape_class, fmt;
-    int dim, q_dim, kv_dim, ffn, n_head, n_kv, hd;
+    EngDims dm;
     size_t loc_stride;
     void* ws;
     size_t ws_bytes;
@@ -1605,13 +1604,7 @@ static size_t xe_launch_smem(int n_layer) {
 }
 template <class C>
 static int xengine_go(XEngineHost* E, hipStream_t st) {
-    static unsigned long long ready = 0; /* bit d: the attribute is set on device d (it is per device: ADVICE r05) */
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return KF_HIP_CHECK;
-    if (dev < 0 || dev >= 64 || !((ready >> dev) & 1ull)) {
-        if (hipFuncSetAttribute((const void*)xengine_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return KF_HIP_CHECK;
-        if (dev >= 0 && dev < 64) ready |= 1ull << dev;
-    }
+    if (eng_raise_lds<C>(xengine_kernel<C>) != KF_OK) return KF_HIP_CHECK;
     const size_t smem = xe_launch_smem<C>(E->args.n_layer);
     if (smem * C::WPC > 160 * 1024) return KF_UNSUPPORTED_DATATYPE;
     E->args.deal_wl = C::WPC > 1 ? 14 : (C::NCW == 7 ? 11 : 16); /* xe_deal: the share of the compute wave beside the poller (two decoders per XCD) */

@@ -303,3 +303,25 @@ def test_qwen3_1p7b_shape_engine_equals_per_layer_launches_bit_for_bit():
         ids[per_launch] = np.asarray(m.tokens_out(cfg["max_seq"])[1985:2040]).copy()
     assert np.array_equal(ids[1], ids[16])
     m.close()
+
+
+def test_engine_on_a_second_device():
+    """The 160 KB ceiling of a kernel's dynamic LDS is an attribute per device, raised before an engine form's first launch on each (kf::eng_raise_lds): the same weights
+    built on device 0 and then on device 1 in this process give the same ids through the engine, and the error word stays clear on both."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one device visible")
+    cfg = _cfg("small", 64)
+    raw = synth.raw_weights_numpy(cfg, 1234, w_std=0.1)
+    prompt = prompt_ids(cfg, 8)
+    ids = []
+    try:
+        for device in (0, 1):
+            m = synth.build_from_raw(cfg, raw, L.Q4, L.BF16, device=device)
+            ids.append(m.generate(prompt, 8, use_graph=True))
+            assert m.engine_steps() > 0, "device %d: the engine was not used (%s)" % (device, m.engine_why())
+            m.engine_check()
+            m.close()
+    finally:
+        torch.cuda.set_device(0)
+    assert ids[0] == ids[1], "greedy ids on device 1 %s differ from device 0's %s" % (ids[1], ids[0])
