@@ -514,6 +514,51 @@ int kf_qknorm_rope_backward(kf_ctx* ctx, const kf_bf16* dq, const kf_bf16* dk, c
                             const float* rope_table, int n_tok, int seq_len, int n_head, int n_kv, int head_dim, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out_or_null,
                             kf_bf16* dwq, kf_bf16* dwk, void* scratch);
 
+/* ---- Packed documents (supervised fine-tuning: the reference's P_SFT phase -- BATCH_INPUT::UpdatePadMask, TokenSet/DataLoader.cpp:1560-1630, and SelfAttention
+ * with isVarLen, Manifold/TGraph.cpp:97 -- which pads one sample per batch row; here any number of documents share the rows of a batch).
+ * THE LAYOUT: a batch is n_rows rows.  Document d owns rows [row0[d], row0[d] + len[d]); documents are ascending and do not overlap; 1 <= len[d] <= max_len (the
+ * rope table's length); a document may start at any row.  A row in no document is a GAP ROW.  Row r of document d stands at position r - row0[d] and attends
+ * causally to its own document's rows only; a gap row stands at position 0, attends to nothing and receives nothing: the forward writes zeros to its output row,
+ * the backward zeros to its dq | dk | dv rows -- with launches whose writes for gap rows are proportional to their number.
+ * kf_attn_docs_plan (host only, no device or context needed) writes the workgroup tables of the launches below to h_table: a kf_attn_docs_header, then three
+ * tables of kf_attn_docs_entry, one entry per tile of a document (forward: ATTN_TILE_COLS / (n_head / n_kv) = 128 / GQ tokens; the two backward launches: 128
+ * rows), longest key range first, then the gap rows as entries with gap = 1.  The caller copies the whole table to the device once and hands both to the
+ * launches: the header on the host (read at the call), the copy on the device (16-byte aligned).  kf_attn_docs_table_bytes: the table's size, 0 for a layout
+ * the plan refuses.  Refusals (KF_INVALID_ARGS, nothing written): a null pointer, n_doc < 1, a length outside [1, max_len], overlapping or descending
+ * documents, a document past n_rows, a head geometry kf_attn_prefill_batch or kf_attn_backward refuse, table_bytes too small. */
+#define KF_ATTN_DOCS_MAGIC 0x53434F44
+typedef struct kf_attn_docs_header {
+    int32_t magic, n_rows, n_head, n_kv, head_dim, n_doc, max_len;
+    int32_t off[3], n[3]; /* forward, dQ launch, dK/dV launch: first entry (in 16-byte units from the table's start) and entry count */
+    int32_t doc_rows, gap_rows, reserved_;
+} kf_attn_docs_header;
+typedef struct kf_attn_docs_entry {
+    int32_t row0, len, tile, gap; /* the document's first row and length (gap = 1: a run of gap rows), this entry's tile inside it */
+} kf_attn_docs_entry;
+size_t kf_attn_docs_table_bytes(const int32_t* row0, const int32_t* len, int n_doc, int n_rows, int max_len, int n_head, int n_kv, int head_dim);
+int kf_attn_docs_plan(const int32_t* row0, const int32_t* len, int n_doc, int n_rows, int max_len, int n_head, int n_kv, int head_dim, void* h_table, size_t table_bytes);
+/* kf_attn_prefill_batch_strided on a table: the tile kernel in its one-key-half form for every document length (never the paired form); the output rows of a
+ * document are bit for bit what kf_attn_prefill_batch_strided writes for that document alone (n_seq = 1, n_tok = len) on its tile route; gap rows of out are
+ * written as zero.  Refusals launch nothing: a null pointer or a header that is not this geometry's: KF_INVALID_ARGS; misaligned rows or table: KF_BLAS_UNALIGN. */
+int kf_attn_prefill_docs(kf_ctx* ctx, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, kf_bf16* out, const kf_attn_docs_header* h_header, const void* d_table,
+                         int64_t q_stride, int64_t out_stride, int n_head, int n_kv, int head_dim, int kv_stride);
+/* kf_attn_backward on a table: dq, dk, dv rows of a document are bit for bit kf_attn_backward on that document alone (n_seq = 1, T = len); gap rows of dq | dk | dv
+ * are written as zero.  scratch: kf_attn_backward_docs_scratch_bytes(n_rows, n_head) bytes (log-sum-exp and dO.O, indexed by global row). */
+size_t kf_attn_backward_docs_scratch_bytes(int n_rows, int n_head);
+int kf_attn_backward_docs(kf_ctx* ctx, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,
+                          kf_bf16* dk, kf_bf16* dv, long long ld_d, const kf_attn_docs_header* h_header, const void* d_table, int n_head, int n_kv, int head_dim, void* scratch);
+/* kf_qknorm_rope_train / kf_qknorm_rope_backward with the position of every row given: pos [n_tok] int32 on the device, each in [0, the rope table's length),
+ * in place of t % seq_len.  The bits are the plain entries' at equal positions (dwq / dwk: the same fixed summation order over the n_tok rows). */
+int kf_qknorm_rope_train_pos(kf_ctx* ctx, kf_bf16* q, kf_bf16* k, const kf_bf16* wq_norm, const kf_bf16* wk_norm, const float* rope_table, int n_tok, const int32_t* pos,
+                             int64_t q_stride, int64_t k_stride, int n_head, int n_kv, int head_dim, float eps, float* rstd_q_or_null, float* rstd_k_or_null);
+int kf_qknorm_rope_backward_pos(kf_ctx* ctx, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv_or_null, long long ld_d, const kf_bf16* q_raw, long long ld_qraw,
+                                const kf_bf16* k_raw, long long ld_kraw, const kf_bf16* wq_norm, const kf_bf16* wk_norm, const float* rstd_q, const float* rstd_k,
+                                const float* rope_table, int n_tok, const int32_t* pos, int n_head, int n_kv, int head_dim, kf_bf16* dq_raw, kf_bf16* dk_raw,
+                                kf_bf16* dv_out_or_null, kf_bf16* dwq, kf_bf16* dwk, void* scratch);
+/* After kf_fused_classifier with a mask: the rows it skipped (mask word has 0x10000, F_IGNORE_LOSS) still hold raw logits where every other row holds a gradient.
+ * This writes zeros to exactly those rows of buf [n_rows, P] (P a multiple of 8, 16-byte aligned) and touches no other row. */
+int kf_zero_ignored_rows(kf_ctx* ctx, kf_bf16* buf, int n_rows, int P, const int32_t* mask);
+
 /* Activation backward (Relu::Back, Activation.cu:283-320).  GELU, in place on the incoming gradient (Activation_backward_inplace ->
  * gelu_backward_inplace_kernel, Activation.cu:42-78): d = bf16(gelu'(x) * d) with x the pre-activation.  SwiGLU (CU_swiglu_back_v0,
  * Activation.cu:245-260): delta_gate = bf16(delta * up * sig * (1 + gate * (1 - sig))), delta_in_out = bf16(delta * gate * sig), sig = sigmoid(gate). */

@@ -13,6 +13,7 @@
 
 #include "kf_a8.h"
 #include "kf_attn_plan.h"
+#include "kf_attn_docs_plan.h"
 #include "kf_gemm_plan.h"
 #include "kf_gemv_plan.h"
 #include "kf_gemv_rows_plan.h"
@@ -1403,6 +1404,63 @@ int kf_attn_backward(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf1
     if (p.status != KF_OK) return fail(p.status, "kf_attn_backward: head_dim %d not covered (64, 128)", hd);
     RET(kf::attn_backward_mfma_launch(c->stream, p, q, k, v, ld_qkv, o, dO, ld_o, dq, dk, dv, ld_d, T, (float*)scratch, ld_qkv, ld_d));
 }
+// ---- packed documents (kf_attn_docs_plan.h): the plan on the host, the three launches and the row-position forms of the q/k-norm + RoPE entries
+size_t kf_attn_docs_table_bytes(const int32_t* row0, const int32_t* len, int n_doc, int n_rows, int max_len, int n_head, int n_kv, int hd) {
+    const kf::AttnDocsPlan p = kf::attn_docs_plan(row0, len, n_doc, n_rows, max_len, n_head, n_kv, hd);
+    return p.status == KF_OK ? p.bytes() : 0;
+}
+int kf_attn_docs_plan(const int32_t* row0, const int32_t* len, int n_doc, int n_rows, int max_len, int n_head, int n_kv, int hd, void* h_table, size_t table_bytes) {
+    if (!h_table) return fail(KF_INVALID_ARGS, "kf_attn_docs_plan: null table");
+    const kf::AttnDocsPlan p = kf::attn_docs_plan(row0, len, n_doc, n_rows, max_len, n_head, n_kv, hd);
+    if (p.status != KF_OK)
+        return fail(KF_INVALID_ARGS, "kf_attn_docs_plan: needs n_doc >= 1 ascending, non-overlapping documents of 1 .. max_len rows inside n_rows, and a head geometry the "
+                                     "attention entries take (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8)");
+    if (table_bytes < p.bytes()) return fail(KF_INVALID_ARGS, "kf_attn_docs_plan: the table needs %zu bytes (kf_attn_docs_table_bytes), got %zu", p.bytes(), table_bytes);
+    memcpy(h_table, &p.hdr, sizeof(p.hdr));
+    memcpy((char*)h_table + sizeof(p.hdr), p.entries.data(), p.entries.size() * sizeof(kf_attn_docs_entry));
+    return KF_OK;
+}
+int kf_attn_prefill_docs(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, kf_bf16* out, const kf_attn_docs_header* h, const void* d_table, int64_t q_stride,
+                         int64_t out_stride, int n_head, int n_kv, int hd, int kv_stride) {
+    CHKCTX(c);
+    if (!q || !k || !v || !out || !h || !d_table || out_stride < (int64_t)n_head * hd) return fail(KF_INVALID_ARGS, "kf_attn_prefill_docs: null pointer or out_stride below n_head * head_dim");
+    if (!al16(k) || !al16(v) || (kv_stride % 8) || !al16(d_table)) return fail(KF_BLAS_UNALIGN, "kf_attn_prefill_docs: k / v rows and the table must be 16-byte aligned");
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_BATCH, c, n_head, n_kv, hd, 0, 1, 1, q, out, q_stride, out_stride, kv_stride));
+    if (p.status != KF_OK) { /* as kf_attn_prefill_batch_strided; a q or out the tile kernel cannot read is an alignment refusal here */
+        const bool unal = (((uintptr_t)q) & 15) || (((uintptr_t)out) & 7) || (q_stride & 7) || (out_stride & 3);
+        return fail(unal ? KF_BLAS_UNALIGN : KF_INVALID_ARGS, "kf_attn_prefill_docs: shape not covered by the tile kernel (head_dim 64 / 128, n_head / n_kv in 1, 2, 4, 8, 16-byte aligned rows)");
+    }
+    if (!kf::attn_docs_header_ok(h, n_head, n_kv, hd)) return fail(KF_INVALID_ARGS, "kf_attn_prefill_docs: the table's header is not kf_attn_docs_plan's for %d / %d heads of %d", n_head, n_kv, hd);
+    RET(kf::attn_prefill_docs_launch(c->stream, p, *h, d_table, q, k, v, out, q_stride, n_kv, kv_stride, out_stride));
+}
+size_t kf_attn_backward_docs_scratch_bytes(int n_rows, int n_head) { return kf::attn_backward_docs_scratch_bytes(n_rows, n_head); }
+int kf_attn_backward_docs(kf_ctx* c, const kf_bf16* q, const kf_bf16* k, const kf_bf16* v, long long ld_qkv, const kf_bf16* o, const kf_bf16* dO, long long ld_o, kf_bf16* dq,
+                          kf_bf16* dk, kf_bf16* dv, long long ld_d, const kf_attn_docs_header* h, const void* d_table, int n_head, int n_kv, int hd, void* scratch) {
+    CHKCTX(c);
+    if (!q || !k || !v || !o || !dO || !dq || !dk || !dv || !scratch || !h || !d_table || n_kv < 1 || n_head < 1 || n_head % n_kv)
+        return fail(KF_INVALID_ARGS, "kf_attn_backward_docs: null pointer or n_head not a multiple of n_kv");
+    if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(dO) || !al16(dq) || !al16(dk) || !al16(dv) || (ld_qkv % 8) || (ld_o % 8) || (ld_d % 8) || ((uintptr_t)scratch & 3) ||
+        !al16(d_table))
+        return fail(KF_BLAS_UNALIGN, "kf_attn_backward_docs: rows and the table must be 16-byte aligned");
+    if (ld_qkv < (long long)n_head * hd || ld_o < (long long)n_head * hd || ld_d < (long long)n_head * hd) return fail(KF_INVALID_ARGS, "kf_attn_backward_docs: row stride below n_head * head_dim");
+    const kf::AttnPlan p = kf::attn_plan(attn_problem(kf::ATTN_BACKWARD, c, n_head, n_kv, hd, 0, 1, 1, q, dq, 0, 0, 0));
+    if (p.status != KF_OK) return fail(p.status, "kf_attn_backward_docs: head_dim %d not covered (64, 128)", hd);
+    if (!kf::attn_docs_header_ok(h, n_head, n_kv, hd)) return fail(KF_INVALID_ARGS, "kf_attn_backward_docs: the table's header is not kf_attn_docs_plan's for %d / %d heads of %d", n_head, n_kv, hd);
+    RET(kf::attn_backward_docs_launch(c->stream, p, *h, d_table, q, k, v, ld_qkv, o, dO, ld_o, dq, dk, dv, ld_d, (float*)scratch));
+}
+int kf_qknorm_rope_train_pos(kf_ctx* c, kf_bf16* q, kf_bf16* k, const kf_bf16* wq, const kf_bf16* wk, const float* table, int n_tok, const int32_t* pos, int64_t q_stride,
+                             int64_t k_stride, int n_head, int n_kv, int hd, float eps, float* rstd_q, float* rstd_k) {
+    CHKCTX(c);
+    if (!q || n_tok < 1 || !pos) return fail(KF_INVALID_ARGS, "kf_qknorm_rope_train_pos: bad args");
+    if (hd % 2) return fail(KF_RMS_PARAMS, "head_dim %d is not divisible by 2", hd);
+    RET(kf::qknorm_rope_pos_launch(c->stream, q, k, wq, wk, table, pos, n_head, n_kv, hd, eps, n_tok, q_stride, k_stride, rstd_q, rstd_k));
+}
+int kf_zero_ignored_rows(kf_ctx* c, kf_bf16* buf, int n_rows, int P, const int32_t* mask) {
+    CHKCTX(c);
+    if (!buf || !mask || n_rows < 1 || P < 8) return fail(KF_INVALID_ARGS, "kf_zero_ignored_rows: null pointer, n_rows < 1 or P < 8");
+    if ((P % 8) != 0 || !al16(buf)) return fail(KF_BLAS_UNALIGN, "kf_zero_ignored_rows: rows must be 16-byte aligned (P = %d a multiple of 8)", P);
+    RET(kf::zero_ignored_rows_launch(c->stream, buf, n_rows, P, mask));
+}
 int kf_embed_pos(kf_ctx* c, const kf_bf16* wte, long long ldw, const kf_bf16* wpe, const int32_t* tokens, int B, int T, int C, int V, kf_bf16* out) {
     CHKCTX(c);
     if (!wte || !wpe || !tokens || !out) return fail(KF_INVALID_ARGS, "kf_embed_pos: null pointer");
@@ -1457,10 +1515,10 @@ int kf_rope_backward(kf_ctx* c, kf_bf16* d, const float* rope_table, int pos0, i
     RET(kf::rope_backward_launch(c->stream, d, rope_table, pos0, n_tok, seq_len, stride, n_head, hd));
 }
 size_t kf_qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int hd) { return kf::qknorm_rope_backward_scratch_bytes(n_tok, n_head, n_kv, hd); }
-int kf_qknorm_rope_backward(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv, long long ld_d, const kf_bf16* q_raw, long long ld_qraw, const kf_bf16* k_raw,
-                            long long ld_kraw, const kf_bf16* wq, const kf_bf16* wk, const float* rstd_q, const float* rstd_k, const float* table, int n_tok, int seq_len,
-                            int n_head, int n_kv, int hd, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out, kf_bf16* dwq, kf_bf16* dwk, void* scratch) {
-    CHKCTX(c);
+// kf_qknorm_rope_backward (pos NULL: row t at t % seq_len) and kf_qknorm_rope_backward_pos (row t at pos[t]; seq_len is passed as 1): one set of refusals
+static int qknorm_rope_backward_impl(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv, long long ld_d, const kf_bf16* q_raw, long long ld_qraw, const kf_bf16* k_raw,
+                                     long long ld_kraw, const kf_bf16* wq, const kf_bf16* wk, const float* rstd_q, const float* rstd_k, const float* table, int n_tok, int seq_len,
+                                     const int32_t* pos, int n_head, int n_kv, int hd, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out, kf_bf16* dwq, kf_bf16* dwk, void* scratch) {
     if (!dq || !dk || !q_raw || !k_raw || !wq || !wk || !rstd_q || !rstd_k || !table || !dq_raw || !dk_raw || !dwq || !dwk || !scratch || (!dv) != (!dv_out))
         return fail(KF_INVALID_ARGS, "kf_qknorm_rope_backward: null pointer (dv and dv_out go together)");
     if (n_tok < 1 || seq_len < 1 || n_tok % seq_len || n_head < 1 || n_kv < 1 || n_head % n_kv)
@@ -1472,7 +1530,22 @@ int kf_qknorm_rope_backward(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, con
         (dv_out && !al16(dv_out)) || ((uintptr_t)rstd_q & 3) || ((uintptr_t)rstd_k & 3) || ((uintptr_t)dwq & 1) || ((uintptr_t)dwk & 1) || ((uintptr_t)scratch & 7))
         return fail(KF_BLAS_UNALIGN, "kf_qknorm_rope_backward: tensors and the table must be 16-byte aligned, the scratch 8-byte aligned");
     RET(kf::qknorm_rope_backward_launch(c->stream, dq, dk, dv, ld_d, q_raw, ld_qraw, k_raw, ld_kraw, wq, wk, rstd_q, rstd_k, table, n_tok, seq_len, n_head, n_kv, hd, dq_raw, dk_raw,
-                                        dv_out, dwq, dwk, (double*)scratch));
+                                        dv_out, dwq, dwk, (double*)scratch, pos));
+}
+int kf_qknorm_rope_backward(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv, long long ld_d, const kf_bf16* q_raw, long long ld_qraw, const kf_bf16* k_raw,
+                            long long ld_kraw, const kf_bf16* wq, const kf_bf16* wk, const float* rstd_q, const float* rstd_k, const float* table, int n_tok, int seq_len,
+                            int n_head, int n_kv, int hd, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out, kf_bf16* dwq, kf_bf16* dwk, void* scratch) {
+    CHKCTX(c);
+    return qknorm_rope_backward_impl(c, dq, dk, dv, ld_d, q_raw, ld_qraw, k_raw, ld_kraw, wq, wk, rstd_q, rstd_k, table, n_tok, seq_len, nullptr, n_head, n_kv, hd, dq_raw, dk_raw,
+                                     dv_out, dwq, dwk, scratch);
+}
+int kf_qknorm_rope_backward_pos(kf_ctx* c, const kf_bf16* dq, const kf_bf16* dk, const kf_bf16* dv, long long ld_d, const kf_bf16* q_raw, long long ld_qraw, const kf_bf16* k_raw,
+                                long long ld_kraw, const kf_bf16* wq, const kf_bf16* wk, const float* rstd_q, const float* rstd_k, const float* table, int n_tok,
+                                const int32_t* pos, int n_head, int n_kv, int hd, kf_bf16* dq_raw, kf_bf16* dk_raw, kf_bf16* dv_out, kf_bf16* dwq, kf_bf16* dwk, void* scratch) {
+    CHKCTX(c);
+    if (!pos || ((uintptr_t)pos & 3)) return fail(KF_INVALID_ARGS, "kf_qknorm_rope_backward_pos: pos is null or not 4-byte aligned");
+    return qknorm_rope_backward_impl(c, dq, dk, dv, ld_d, q_raw, ld_qraw, k_raw, ld_kraw, wq, wk, rstd_q, rstd_k, table, n_tok, 1, pos, n_head, n_kv, hd, dq_raw, dk_raw, dv_out,
+                                     dwq, dwk, scratch);
 }
 int kf_gelu_backward(kf_ctx* c, kf_bf16* d_in_out, const kf_bf16* x, size_t n) {
     CHKCTX(c);

@@ -380,13 +380,14 @@ __global__ void __launch_bounds__(NW * 64) attn_fast_kernel(const AttnArgs a) {
     if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// standalone ROPE::cuInfer: grid = n_head + n_kv, one wave each
+// standalone ROPE::cuInfer: grid = n_head + n_kv, one wave each.  ROWPOS: d_pos is an array, one position per token (packed documents)
+template <bool ROWPOS>
 __global__ void __launch_bounds__(64) qknorm_rope_kernel(uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, int pos_,
                                                          const int* d_pos, int n_head, int n_kv, int hd, float eps, long long q_stride, long long k_stride, int seq_len, float* rstd_q,
                                                          float* rstd_k) {
     __shared__ uint16_t buf[256];
     /* blockIdx.y = token of a batch; seq_len > 0: sequences of seq_len tokens back to back, positions restart at pos_ in each */
-    const int pos = (d_pos ? *d_pos : pos_) + (seq_len > 0 ? (int)blockIdx.y % seq_len : (int)blockIdx.y);
+    const int pos = ROWPOS ? d_pos[blockIdx.y] : (d_pos ? *d_pos : pos_) + (seq_len > 0 ? (int)blockIdx.y % seq_len : (int)blockIdx.y);
     const int b = blockIdx.x;
     uint16_t* src = b < n_head ? q + (size_t)blockIdx.y * q_stride + (size_t)b * hd : k + (size_t)blockIdx.y * k_stride + (size_t)(b - n_head) * hd;
     const uint16_t* wn = b < n_head ? wq : wk;
@@ -441,8 +442,16 @@ int attn_launch(hipStream_t st, AttnArgs& a, const AttnPlan& p, bool rows) {
 int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, int pos,
                        const int* d_pos, int n_head, int n_kv, int hd, float eps, int n_tok, long long q_stride, long long k_stride, int seq_len, float* rstd_q, float* rstd_k) {
     if (hd < 64 || hd > 128 || (hd & (hd - 1)) != 0 || n_tok < 1) return KF_INVALID_ARGS;
-    hipLaunchKernelGGL(qknorm_rope_kernel, dim3(n_head + (k ? n_kv : 0), n_tok), dim3(64), 0, st, q, k, wq, wk, table, pos, d_pos, n_head, n_kv, hd, eps,
+    hipLaunchKernelGGL(qknorm_rope_kernel<false>, dim3(n_head + (k ? n_kv : 0), n_tok), dim3(64), 0, st, q, k, wq, wk, table, pos, d_pos, n_head, n_kv, hd, eps,
                        q_stride, k_stride, seq_len, rstd_q, rstd_k);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+// the same with row_pos [n_tok]: token t at position row_pos[t]
+int qknorm_rope_pos_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, const int* row_pos, int n_head, int n_kv, int hd,
+                           float eps, int n_tok, long long q_stride, long long k_stride, float* rstd_q, float* rstd_k) {
+    if (hd < 64 || hd > 128 || (hd & (hd - 1)) != 0 || n_tok < 1 || !row_pos) return KF_INVALID_ARGS;
+    hipLaunchKernelGGL(qknorm_rope_kernel<true>, dim3(n_head + (k ? n_kv : 0), n_tok), dim3(64), 0, st, q, k, wq, wk, table, 0, row_pos, n_head, n_kv, hd, eps, q_stride,
+                       k_stride, 0, rstd_q, rstd_k);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

@@ -11,7 +11,7 @@
 //              P = exp(scale S - L_q), dS = P o (dP - D_q)  L, D per accumulator ROW: four ds_read_b128 each
 //              dV^T[d][key] += dO^T[d][q] . P[q][key],  dK^T[d][key] += Q^T[d][q] . dS[q][key]
 // P and dS enter their products as single bf16 values (gradients are compared at 2^-7 of scale); everything else fp32.
-#include "kf_attn_plan.h"
+#include "kf_attn_docs_plan.h"
 
 namespace kf {
 
@@ -79,15 +79,40 @@ __device__ __forceinline__ u32x4 ab_tfrag(const uint16_t* rows2, int db, int s2,
     return __builtin_bit_cast(u32x4, bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
 }
 
+// a gap entry of a packed-documents table: zeros to rows [row0 + 128 tile, ..) of this run, HD columns from p on
 template <int HD>
+__device__ __forceinline__ void ab_zero_gap(uint16_t* p, long long ld, const kf_attn_docs_entry& e) {
+    const int first = e.tile * 128, nrow = e.len - first < 128 ? e.len - first : 128;
+    for (int i = threadIdx.x; i < nrow * (HD / 8); i += 256) {
+        const int rr = i / (HD / 8), c = i - rr * (HD / 8);
+        *reinterpret_cast<u32x4*>(p + (size_t)(e.row0 + first + rr) * ld + c * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+// DOCS (both kernels): packed documents.  The sequence origin, T and the block of 128 come from the workgroup's table entry (blockIdx.x) instead of blockIdx;
+// Lbuf / Dbuf are [head][n_rows], indexed by global row.  The arithmetic is the plain form's.
+template <int HD, bool DOCS = false>
 __global__ void __launch_bounds__(256) attn_bwd_dq_mfma_kernel(const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* o, const uint16_t* dO, long long ld_o,
-                                                               uint16_t* dq, long long ld_d, float* Lbuf, float* Dbuf, int T, float scale, int gq, long long ld_kv) {
+                                                               uint16_t* dq, long long ld_d, float* Lbuf, float* Dbuf, int T, float scale, int gq, long long ld_kv,
+                                                               const kf_attn_docs_entry* docs, int n_rows) {
     constexpr int NS = HD / 16, NDB = HD / 32, KS = HD + 8;
     __shared__ __attribute__((aligned(16))) uint16_t ks[AB_T * KS], vs[AB_T * KS], kt[AB_T * (HD + AB_PAD2)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int head = blockIdx.y, tok0 = (gridDim.x - 1 - blockIdx.x) * 128; /* the longest columns first */
+    const int head = blockIdx.y;
+    int tok0 = (gridDim.x - 1 - blockIdx.x) * 128; /* the longest columns first */
     const size_t hoff = (size_t)head * HD, hoff_kv = (size_t)(head / gq) * HD; /* GQA: gq query heads share a kv head */
-    { /* sequence blockIdx.z: T rows further on in every tensor */
+    int LT = T; /* rows per head of Lbuf / Dbuf */
+    if constexpr (DOCS) {
+        const kf_attn_docs_entry e = docs[blockIdx.x]; /* workgroup-uniform */
+        if (e.gap) {
+            ab_zero_gap<HD>(dq + hoff, ld_d, e);
+            return;
+        }
+        const size_t ro = (size_t)e.row0;
+        T = e.len, tok0 = e.tile * 128, LT = n_rows;
+        q += ro * ld_qkv, k += ro * ld_kv, v += ro * ld_kv, o += ro * ld_o, dO += ro * ld_o, dq += ro * ld_d;
+        Lbuf += ro, Dbuf += ro;
+    } else { /* sequence blockIdx.z: T rows further on in every tensor */
         const size_t ro = (size_t)blockIdx.z * T;
         q += ro * ld_qkv, k += ro * ld_kv, v += ro * ld_kv, o += ro * ld_o, dO += ro * ld_o, dq += ro * ld_d;
         Lbuf += (size_t)blockIdx.z * gridDim.y * T, Dbuf += (size_t)blockIdx.z * gridDim.y * T;
@@ -144,7 +169,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_mfma_kernel(const uint16_t* q
     }
     l += __shfl_xor(l, 32, 64);
     const float L = (M + __log2f(l)) * 0.693147182464599609375f; /* back to natural units: log-sum-exp of the scaled scores */
-    if (col_ok && h == 0) Lbuf[(size_t)head * T + tok] = L, Dbuf[(size_t)head * T + tok] = D;
+    if (col_ok && h == 0) Lbuf[(size_t)head * LT + tok] = L, Dbuf[(size_t)head * LT + tok] = D;
 
     // ---- pass B: dQ^T
     f32x16 acc[NDB];
@@ -209,16 +234,30 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_mfma_kernel(const uint16_t* q
         }
 }
 
-template <int HD>
+template <int HD, bool DOCS = false>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_mfma_kernel(const uint16_t* q, const uint16_t* k, const uint16_t* v, long long ld_qkv, const uint16_t* dO, long long ld_o, uint16_t* dk,
-                                                                uint16_t* dv, long long ld_d, const float* Lbuf, const float* Dbuf, int T, float scale, int gq, long long ld_kv, long long ld_dkv) {
+                                                                uint16_t* dv, long long ld_d, const float* Lbuf, const float* Dbuf, int T, float scale, int gq, long long ld_kv, long long ld_dkv,
+                                                                const kf_attn_docs_entry* docs, int n_rows) {
     constexpr int NS = HD / 16, NDB = HD / 32, KS = HD + 8;
     __shared__ __attribute__((aligned(16))) uint16_t qs[AB_T * KS], os[AB_T * KS], qt[AB_T * (HD + AB_PAD2)], ot[AB_T * (HD + AB_PAD2)];
     __shared__ __attribute__((aligned(16))) float Ls[AB_T], Ds[AB_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int kvh = blockIdx.y, key0 = blockIdx.x * 128; /* blockIdx.y = kv head; the first key columns see the most query tiles: already first */
+    const int kvh = blockIdx.y; /* blockIdx.y = kv head */
+    int key0 = blockIdx.x * 128; /* the first key columns see the most query tiles: already first */
     const size_t hoff = (size_t)kvh * HD;
-    {
+    int LT = T; /* rows per head of Lbuf / Dbuf */
+    if constexpr (DOCS) {
+        const kf_attn_docs_entry e = docs[blockIdx.x]; /* workgroup-uniform */
+        if (e.gap) {
+            ab_zero_gap<HD>(dk + hoff, ld_dkv, e);
+            ab_zero_gap<HD>(dv + hoff, ld_dkv, e);
+            return;
+        }
+        const size_t ro = (size_t)e.row0;
+        T = e.len, key0 = e.tile * 128, LT = n_rows;
+        q += ro * ld_qkv, k += ro * ld_kv, v += ro * ld_kv, dO += ro * ld_o, dk += ro * ld_dkv, dv += ro * ld_dkv;
+        Lbuf += ro, Dbuf += ro;
+    } else {
         const size_t ro = (size_t)blockIdx.z * T;
         q += ro * ld_qkv, k += ro * ld_kv, v += ro * ld_kv, dO += ro * ld_o, dk += ro * ld_dkv, dv += ro * ld_dkv;
         Lbuf += (size_t)blockIdx.z * gridDim.y * gq * T, Dbuf += (size_t)blockIdx.z * gridDim.y * gq * T;
@@ -249,7 +288,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_mfma_kernel(const uint16_t* 
         ab_load<HD>(dO, ld_o, (size_t)head * HD, t * AB_T, T, oreg);
         if (tid < AB_T) {
             const int qi = t * AB_T + tid;
-            lreg = qi < T ? Lbuf[(size_t)head * T + qi] * AB_LOG2E : 0.f, dreg = qi < T ? Dbuf[(size_t)head * T + qi] : 0.f;
+            lreg = qi < T ? Lbuf[(size_t)head * LT + qi] * AB_LOG2E : 0.f, dreg = qi < T ? Dbuf[(size_t)head * LT + qi] : 0.f;
         }
     };
     auto put = [&]() {
@@ -325,8 +364,25 @@ int attn_backward_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t*
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), grid_kv(p.grid_kv[0], p.grid_kv[1], p.grid_kv[2]);
     const auto dq_k = p.hd == 128 ? attn_bwd_dq_mfma_kernel<128> : attn_bwd_dq_mfma_kernel<64>;
     const auto dkv_k = p.hd == 128 ? attn_bwd_dkv_mfma_kernel<128> : attn_bwd_dkv_mfma_kernel<64>;
-    hipLaunchKernelGGL(dq_k, grid, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, T, scale, p.gq, ld_kv);
-    hipLaunchKernelGGL(dkv_k, grid_kv, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, T, scale, p.gq, ld_kv, ld_dkv);
+    hipLaunchKernelGGL(dq_k, grid, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, T, scale, p.gq, ld_kv, nullptr, 0);
+    hipLaunchKernelGGL(dkv_k, grid_kv, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, T, scale, p.gq, ld_kv, ld_dkv, nullptr, 0);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
+// packed documents: the same two launches on the dQ and dK/dV tables, one workgroup per (entry, head) / (entry, kv-head); q | k | v share ld_qkv, dq | dk | dv ld_d
+int attn_backward_docs_launch(hipStream_t st, const AttnPlan& p, const kf_attn_docs_header& h, const void* d_table, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                              long long ld_qkv, const uint16_t* o, const uint16_t* dO, long long ld_o, uint16_t* dq, uint16_t* dk, uint16_t* dv, long long ld_d, float* scratch) {
+    if (p.status != KF_OK || p.route != ATTN_BWD) return KF_INTERNAL_ERR;
+    const float scale = 1.0f / sqrtf((float)p.hd);
+    float* Lb = scratch;
+    float* Db = scratch + (size_t)h.n_rows * h.n_head;
+    const kf_attn_docs_entry* tab = reinterpret_cast<const kf_attn_docs_entry*>(d_table);
+    const dim3 grid(h.n[ATTN_DOCS_DQ], h.n_head, 1), grid_kv(h.n[ATTN_DOCS_DKV], h.n_kv, 1);
+    const auto dq_k = p.hd == 128 ? attn_bwd_dq_mfma_kernel<128, true> : attn_bwd_dq_mfma_kernel<64, true>;
+    const auto dkv_k = p.hd == 128 ? attn_bwd_dkv_mfma_kernel<128, true> : attn_bwd_dkv_mfma_kernel<64, true>;
+    hipLaunchKernelGGL(dq_k, grid, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, o, dO, ld_o, dq, ld_d, Lb, Db, 0, scale, p.gq, ld_qkv, tab + h.off[ATTN_DOCS_DQ], h.n_rows);
+    hipLaunchKernelGGL(dkv_k, grid_kv, dim3(p.threads), p.lds, st, q, k, v, ld_qkv, dO, ld_o, dk, dv, ld_d, Lb, Db, 0, scale, p.gq, ld_qkv, ld_d, tab + h.off[ATTN_DOCS_DKV],
+                       h.n_rows);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

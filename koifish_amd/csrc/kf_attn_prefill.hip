@@ -21,7 +21,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "kf_attn_plan.h"
+#include "kf_attn_docs_plan.h"
 
 namespace kf {
 #ifdef AP_STAMP /* scratch/build_variant.py ... -DAP_STAMP: cycles per segment of the key walk, summed by wave 2 of workgroup (0, 0) -- a long walk of the even key half */
@@ -51,6 +51,7 @@ struct AttnPrefillArgs {
     long long q_stride;
     long long out_stride; /* row stride of out (a training step reads q out of the fused [rows, 3C] buffer and writes a dense [rows, C] out) */
     float rden;
+    const kf_attn_docs_entry* docs; /* the DOCS form: the forward table of kf_attn_docs_plan.h, one entry per (workgroup / n_kv) */
 };
 
 __device__ __forceinline__ float ap_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -64,8 +65,11 @@ constexpr bool PSPLIT = true; /* probabilities enter P.V as bf16 high + bf16 rem
 // key walk, not its column count, and the second workgroup of a heavy block does not land on an idle CU.  Cutting the late blocks' KEY ranges into pieces for other
 // workgroups -- partial (O, max, sum) through memory, owners dispatched last and merging in key order -- was built and measured as well: 70.7 us in the 2047-token
 // prefill against 67 us without, so it is not in the tree; the launch behaves throughput-bound at ~250 TFLOP/s of causal flops rather than tail-bound.)
-template <int HD, int GQ, int KH, int KT>
+// DOCS (KH = 1 only): packed documents.  The workgroup's sequence origin, sequence length and block come from its table entry instead of blockIdx; the arithmetic
+// is the plain form's, so a document's rows carry the bits of a launch on that document alone.  An entry over gap rows: zeros to its rows, nothing else.
+template <int HD, int GQ, int KH, int KT, bool DOCS = false>
 __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefillArgs a) {
+    static_assert(!DOCS || KH == 1, "packed documents take the one-key-half form");
     constexpr int NSUB = KT / 32; /* 32-key sub-tiles per staged tile */
     constexpr int NS = HD / 16;   /* MFMA steps over d for S^T */
     constexpr int NDB = HD / 32;  /* 32-row blocks of O^T */
@@ -88,7 +92,23 @@ __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefil
     // rows (1 MB at 2047 tokens) then stay in that XCD's 4 MB L2 instead of every XCD streaming all heads' rows through the fabric (199 MB per launch at 2047 tokens)
     const int wg_id = (int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y;
     const int g = wg_id % a.n_kv, bx = wg_id / a.n_kv;
-    const size_t seq_row = (size_t)blockIdx.z * a.n_tok;
+    size_t seq_row;
+    int n_tok, doc_tile = 0;
+    if constexpr (DOCS) {
+        const kf_attn_docs_entry e = a.docs[bx]; /* workgroup-uniform */
+        seq_row = (size_t)e.row0, n_tok = e.len, doc_tile = e.tile;
+        if (e.gap) { /* gap rows [row0 + tile TQ, ..) of this run: this kv-head's GQ query heads of out, zero */
+            const int first = e.tile * TQ, nrow = e.len - first < TQ ? e.len - first : TQ;
+            constexpr int VPR = GQ * HD / 4; /* 8-byte stores per row */
+            for (int i = (int)threadIdx.x; i < nrow * VPR; i += 256) {
+                const int rr = i / VPR, c = i - rr * VPR;
+                *reinterpret_cast<u32x2*>(a.out + (seq_row + first + rr) * a.out_stride + (size_t)g * GQ * HD + c * 4) = u32x2{0u, 0u};
+            }
+            return;
+        }
+    } else {
+        seq_row = (size_t)blockIdx.z * a.n_tok, n_tok = a.n_tok;
+    }
     // Which tokens a wave's 32 columns are.  KH = 1: the workgroup is TQ consecutive tokens, the blocks with the most keys dispatched first.  KH = 2 (about one workgroup per
     // CU: the launch lasts as long as its heaviest workgroup, and under the causal mask the last query block walks twice the keys of the average one -- measured at 2047 tokens:
     // matrix + vector pipe time of the average SIMD 25 us, of the last block's 57 us, launch 65 us): the workgroup is TWO half blocks of TQ / 2 tokens, number x from the front
@@ -102,31 +122,31 @@ __global__ void __launch_bounds__(256 * KH) attn_prefill_kernel(const AttnPrefil
     if constexpr (PAIR) {
         // (SIMD = wave % 4 holds wave w of the even key half and wave w of the odd one: the back half block -- the long walk -- sits on waves 2-3 of the even half and on
         // waves 0-1 of the odd half, so that every SIMD runs one long and one short walk; with both long walks on SIMDs 2-3 the launch took what it took unpaired.)
-        const int nsb = (a.n_tok + HT - 1) / HT, lo = bx, hi = nsb - 1 - bx, half = ((wave >> 1) ^ kh) & 1;
+        const int nsb = (n_tok + HT - 1) / HT, lo = bx, hi = nsb - 1 - bx, half = ((wave >> 1) ^ kh) & 1;
         sb_first = (half ? hi : lo) * HT, sb_tokens = HT, col_in = (wave & 1) * 32;
         half_ok = half || lo != hi; /* an odd count's middle block belongs to the back half's waves alone */
         int last = hi * HT + HT - 1;
-        kmax = a.pos0 + (last < a.n_tok - 1 ? last : a.n_tok - 1);
+        kmax = a.pos0 + (last < n_tok - 1 ? last : n_tok - 1);
     } else {
-        sb_first = ((int)gridDim.x - 1 - bx) * TQ, sb_tokens = TQ, col_in = wave * 32;
+        sb_first = (DOCS ? doc_tile : (int)gridDim.x - 1 - bx) * TQ, sb_tokens = TQ, col_in = wave * 32;
         int last = sb_first + TQ - 1;
-        kmax = a.pos0 + (last < a.n_tok - 1 ? last : a.n_tok - 1);
+        kmax = a.pos0 + (last < n_tok - 1 ? last : n_tok - 1);
     }
     const int colh = col_in + r;
     const int tq = colh / GQ, hq = colh - tq * GQ;
     int tok = sb_first + tq;
-    const bool col_ok = half_ok && tok < a.n_tok;
-    if (tok >= a.n_tok) tok = a.n_tok - 1;
+    const bool col_ok = half_ok && tok < n_tok;
+    if (tok >= n_tok) tok = n_tok - 1;
     const int pos_q = a.pos0 + tok; /* last key this column attends to */
     const int ntile = kmax / KT + 1;
     int ntile_w = ntile; /* tiles this wave multiplies */
     if constexpr (PAIR) {
         int last = sb_first + sb_tokens - 1;
-        last = last < a.n_tok - 1 ? last : a.n_tok - 1;
+        last = last < n_tok - 1 ? last : n_tok - 1;
         ntile_w = half_ok ? (a.pos0 + last) / KT + 1 : 0;
     }
     const int wave_tok0 = sb_first + col_in / GQ; /* the first token among this wave's columns */
-    const bool block_whole = sb_first + sb_tokens <= a.n_tok;
+    const bool block_whole = sb_first + sb_tokens <= n_tok;
 
     // Q fragments: B operand of S^T, lane (col, h) holds Q[col][16 s + 8 h .. + 8]
     u32x4 qf[NS];
@@ -369,9 +389,35 @@ int attn_prefill_mfma_launch(hipStream_t st, const AttnPlan& p, const uint16_t* 
     a.q = q, a.kcache = kc, a.vcache = vc, a.out = out, a.pos0 = pos0, a.n_tok = n_tok, a.n_kv = n_kv, a.kv_stride = kv_stride, a.q_stride = q_stride;
     a.out_stride = out_stride > 0 ? out_stride : q_stride;
     a.rden = 1.0f / sqrtf((float)p.hd);
-    a.n_seq = n_seq;
+    a.n_seq = n_seq, a.docs = nullptr;
     void* args[] = {&a};
     (void)hipLaunchKernel(reinterpret_cast<const void*>(forms[f]), dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.threads), args, (size_t)p.lds, st);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
+// packed documents: the DOCS instantiations by (hd, query heads per workgroup), the ATTN_TILE form of plan p (planned for ONE row: the form does not depend on
+// the length) on one workgroup per (forward-table entry, kv-head)
+template <int I>
+constexpr ApKernel ap_docs_form() {
+    return attn_prefill_kernel<I / 4 ? 128 : 64, 1 << (I % 4), 1, AP_KT, true>;
+}
+template <int... I>
+constexpr std::array<ApKernel, 8> ap_docs_forms(std::integer_sequence<int, I...>) {
+    return {{ap_docs_form<I>()...}};
+}
+int attn_prefill_docs_launch(hipStream_t st, const AttnPlan& p, const kf_attn_docs_header& h, const void* d_table, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                             uint16_t* out, long long q_stride, int n_kv, int kv_stride, long long out_stride) {
+    static constexpr std::array<ApKernel, 8> forms = ap_docs_forms(std::make_integer_sequence<int, 8>());
+    if (p.status != KF_OK || p.route != ATTN_TILE || p.kh != 1 || p.kt != AP_KT || p.lds > ATTN_LDS_MAX) return KF_INTERNAL_ERR;
+    const long long wgs = (long long)h.n[ATTN_DOCS_FWD] * n_kv;
+    if (wgs < 1 || wgs > 0x7fffffffLL) return KF_INVALID_ARGS;
+    AttnPrefillArgs a;
+    a.q = q, a.kcache = k, a.vcache = v, a.out = out, a.pos0 = 0, a.n_tok = 0, a.n_kv = n_kv, a.kv_stride = kv_stride, a.q_stride = q_stride;
+    a.out_stride = out_stride > 0 ? out_stride : q_stride;
+    a.rden = 1.0f / sqrtf((float)p.hd);
+    a.n_seq = 1, a.docs = reinterpret_cast<const kf_attn_docs_entry*>(d_table) + h.off[ATTN_DOCS_FWD];
+    void* args[] = {&a};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(forms[(p.hd == 128) * 4 + __builtin_ctz(p.gq)]), dim3((unsigned)wgs), dim3(p.threads), args, (size_t)p.lds, st);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

@@ -117,6 +117,8 @@ struct AttnArgs {
 int qknorm_rope_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, int pos,
                        const int* d_pos, int n_head, int n_kv, int hd, float eps, int n_tok = 1, long long q_stride = 0, long long k_stride = 0, int seq_len = 0,
                        float* rstd_q = nullptr, float* rstd_k = nullptr);
+int qknorm_rope_pos_launch(hipStream_t st, uint16_t* q, uint16_t* k, const uint16_t* wq, const uint16_t* wk, const float* table, const int* row_pos, int n_head, int n_kv, int hd,
+                           float eps, int n_tok, long long q_stride, long long k_stride, float* rstd_q, float* rstd_k); /* token t at position row_pos[t] */
 
 // Development knobs (process-wide, default = the product's choice).  Not part of the ABI and never read from the environment: tests and the scripts under
 // scratch/ set them through kfdbg_set_knob (kf_abi.hip) to compare a kernel form with the form it replaces inside one process.
@@ -212,7 +214,7 @@ size_t qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int h
 int qknorm_rope_backward_launch(hipStream_t st, const uint16_t* dq, const uint16_t* dk, const uint16_t* dv, long long ld_d, const uint16_t* q_raw, long long ld_qraw,
                                 const uint16_t* k_raw, long long ld_kraw, const uint16_t* wq, const uint16_t* wk, const float* rstd_q, const float* rstd_k, const float* table,
                                 int n_tok, int seq_len, int n_head, int n_kv, int hd, uint16_t* dq_raw, uint16_t* dk_raw, uint16_t* dv_out, uint16_t* dwq, uint16_t* dwk,
-                                double* scratch);
+                                double* scratch, const int* pos = nullptr);
 int bias_residual_launch(hipStream_t st, uint16_t* y, const uint16_t* bias, const uint16_t* residual, size_t n, int M); /* kf_ops.hip */
 // linear backward helpers (kf_linear_bwd.hip)
 int transpose_bf16_launch(hipStream_t st, const uint16_t* in, uint16_t* out, int R, int C);
@@ -225,6 +227,7 @@ int embed_backward_launch(hipStream_t st, uint16_t* dwte, long long ldw, uint16_
 // fused classifier (kf_loss.hip): cross-entropy loss per row + logit gradient in place
 int fused_classifier_launch(hipStream_t st, uint16_t* logits, float* losses, uint16_t* probs, float dloss, const int* targets, long rows, int V, int P,
                             const int* mask, int write_dlogits);
+int zero_ignored_rows_launch(hipStream_t st, uint16_t* buf, long rows, int P, const int* mask); /* zeros to the rows the classifier skipped, and to no other */
 // distilling classifier (kf_distill.hip): a CE + b tau^2 KL(teacher || student) per row + its logit gradient in place; kd_weight == 0: no teacher is read
 int distill_classifier_launch(hipStream_t st, uint16_t* logits, const uint16_t* teacher, long teacher_ld, float* losses, float* kd, float dloss, const int* targets,
                               long rows, int V, int P, const int* mask, float ce_weight, float kd_weight, float temperature, int write_dlogits);

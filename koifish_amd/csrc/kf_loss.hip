@@ -112,4 +112,17 @@ int fused_classifier_launch(hipStream_t st, uint16_t* logits, float* losses, uin
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 
+// The rows the classifier skipped (F_IGNORE_LOSS) still hold raw logits where the backward reads a gradient: zeros to exactly those rows.  One workgroup per
+// row; the workgroup of a counted row reads its mask word and ends.
+__global__ void __launch_bounds__(256) zero_ignored_rows_kernel(uint16_t* __restrict__ buf, int P, const int* __restrict__ mask) {
+    if (!(mask[blockIdx.x] & 0x10000)) return;
+    uint16_t* const row = buf + (size_t)blockIdx.x * P;
+    for (int v8 = threadIdx.x; v8 < P / 8; v8 += 256) *reinterpret_cast<u32x4*>(row + (size_t)v8 * 8) = u32x4{0u, 0u, 0u, 0u};
+}
+int zero_ignored_rows_launch(hipStream_t st, uint16_t* buf, long rows, int P, const int* mask) {
+    if (rows < 1 || rows > 0x7fffffffL || P < 8 || (P % 8) != 0 || !mask) return KF_INVALID_ARGS;
+    hipLaunchKernelGGL(zero_ignored_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, buf, P, mask);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
 }  // namespace kf

@@ -38,10 +38,11 @@ struct QkbArgs {
     double *part[2];            /* [G][hd] column partials */
     long long ld_d, ld_raw[2];
     const float *table;
+    const int *pos;             /* POS form: [n_tok] the rows' positions, in place of t % seq_len */
     int n_tok, seq_len, nh[2], G[2], Gv;
 };
 
-template <int HD>
+template <int HD, bool POS = false>
 __global__ void __launch_bounds__(256) qknorm_rope_backward_kernel(QkbArgs a) {
     constexpr int LPR = HD / 16, RPW = 64 / LPR, NSLOT = 4 * RPW, HALF = HD / 2;
     const int tid = threadIdx.x, which = blockIdx.y;
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(256) qknorm_rope_backward_kernel(QkbArgs a) {
         const size_t od = (size_t)t * a.ld_d + (size_t)h * HD + ll * 8, orw = (size_t)t * ld_raw + (size_t)h * HD + ll * 8;
         const u32x4 d0 = *reinterpret_cast<const u32x4*>(dsrc + od), d1 = *reinterpret_cast<const u32x4*>(dsrc + od + HALF);
         const u32x4 x0 = *reinterpret_cast<const u32x4*>(raw + orw), x1 = *reinterpret_cast<const u32x4*>(raw + orw + HALF);
-        const float* cs = a.table + ((size_t)(t % a.seq_len) * HALF + ll * 8) * 2;
+        const float* cs = a.table + ((size_t)(POS ? a.pos[t] : (int)(t % a.seq_len)) * HALF + ll * 8) * 2;
         f32x4 tb[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) tb[k] = *reinterpret_cast<const f32x4*>(cs + 4 * k); /* (c, s) of columns 2k, 2k + 1 */
@@ -158,19 +159,20 @@ size_t qknorm_rope_backward_scratch_bytes(int n_tok, int n_head, int n_kv, int h
 int qknorm_rope_backward_launch(hipStream_t st, const uint16_t* dq, const uint16_t* dk, const uint16_t* dv, long long ld_d, const uint16_t* q_raw, long long ld_qraw,
                                 const uint16_t* k_raw, long long ld_kraw, const uint16_t* wq, const uint16_t* wk, const float* rstd_q, const float* rstd_k, const float* table,
                                 int n_tok, int seq_len, int n_head, int n_kv, int hd, uint16_t* dq_raw, uint16_t* dk_raw, uint16_t* dv_out, uint16_t* dwq, uint16_t* dwk,
-                                double* scratch) {
-    if (qknorm_rope_backward_scratch_bytes(n_tok, n_head, n_kv, hd) == 0 || seq_len < 1 || n_tok % seq_len) return KF_INVALID_ARGS;
+                                double* scratch, const int* pos) { /* pos != NULL: the POS form, seq_len is not read */
+    if (qknorm_rope_backward_scratch_bytes(n_tok, n_head, n_kv, hd) == 0 || (!pos && (seq_len < 1 || n_tok % seq_len))) return KF_INVALID_ARGS;
     QkbArgs a;
     a.d[0] = dq, a.d[1] = dk, a.d[2] = dv, a.raw[0] = q_raw, a.raw[1] = k_raw, a.w[0] = wq, a.w[1] = wk, a.rstd[0] = rstd_q, a.rstd[1] = rstd_k;
     a.out[0] = dq_raw, a.out[1] = dk_raw, a.out[2] = dv_out;
-    a.ld_d = ld_d, a.ld_raw[0] = ld_qraw, a.ld_raw[1] = ld_kraw, a.table = table, a.n_tok = n_tok, a.seq_len = seq_len, a.nh[0] = n_head, a.nh[1] = n_kv;
+    a.ld_d = ld_d, a.ld_raw[0] = ld_qraw, a.ld_raw[1] = ld_kraw, a.table = table, a.pos = pos, a.n_tok = n_tok, a.seq_len = pos ? 1 : seq_len, a.nh[0] = n_head, a.nh[1] = n_kv;
     a.G[0] = qknorm_rope_backward_groups((long long)n_tok * n_head, hd), a.G[1] = qknorm_rope_backward_groups((long long)n_tok * n_kv, hd);
     a.part[0] = scratch, a.part[1] = scratch + (size_t)a.G[0] * hd;
     const long long vvec = (long long)n_tok * n_kv * (hd / 8);
     a.Gv = dv ? (int)((vvec + 255) / 256 > QKB_MAX_GROUPS ? QKB_MAX_GROUPS : (vvec + 255) / 256) : 0;
     const int gx = a.G[0] > a.Gv ? a.G[0] : a.Gv; /* G[1] <= G[0]: n_kv <= n_head */
-    if (hd == 64) hipLaunchKernelGGL(qknorm_rope_backward_kernel<64>, dim3(gx, dv ? 3 : 2), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(qknorm_rope_backward_kernel<128>, dim3(gx, dv ? 3 : 2), dim3(256), 0, st, a);
+    const auto kern = pos ? (hd == 64 ? qknorm_rope_backward_kernel<64, true> : qknorm_rope_backward_kernel<128, true>)
+                          : (hd == 64 ? qknorm_rope_backward_kernel<64, false> : qknorm_rope_backward_kernel<128, false>);
+    hipLaunchKernelGGL(kern, dim3(gx, dv ? 3 : 2), dim3(256), 0, st, a);
     if (hipGetLastError() != hipSuccess) return KF_HIP_CHECK;
     int rc = norm_backward_reduce_launch(st, dwq, a.part[0], a.G[0], hd);
     if (rc == KF_OK) rc = norm_backward_reduce_launch(st, dwk, a.part[1], a.G[1], hd);

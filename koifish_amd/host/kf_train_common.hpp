@@ -65,6 +65,10 @@ struct TrainerCore {
     long long teacher_ld = 0;
     float ce_weight = 1.0f, kd_weight = 0.0f, temperature = 1.0f;
     float* kd_rows = nullptr;
+    // packed documents (Qwen3Trainer::SetDocuments): the mask words of the step's rows (bit 0x10000, F_IGNORE_LOSS: the row's target does not count) and the number
+    // of rows that count.  With a mask HeadLoss takes the mean over n_valid rows and leaves exact zeros in the ignored rows of `logits`
+    const int32_t* loss_mask = nullptr;
+    int n_valid = 0;
 
     virtual ~TrainerCore() {}  // touches no context (it may be gone already): the owner of a clip scratch switches clipping off before it frees the scratch
     virtual bool InSection(size_t) const { return true; }  // Update leaves a tensor outside the active section alone (EOE)
@@ -102,6 +106,7 @@ struct TrainerCore {
             teacher = nullptr, teacher_ld = 0, kd_rows = nullptr, ce_weight = 1.0f, kd_weight = 0.0f, temperature = 1.0f;
             return KF_OK;
         }
+        if (loss_mask) return refuse("set_distill: documents are set (set_documents): the teacher's forward would need the same layout -- switch them off first");
         if (Ready() != KF_OK) return refuse("set_distill: every tensor and buffer must be registered first");
         if (Sectioned()) return refuse("set_distill: a trainer with EOE layer sections (layers_in_branch) is not distilled: eval shares the step's loss buffer");
         if (!(std::isfinite(ce_w) && std::isfinite(kd_w) && ce_w >= 0.0f && kd_w >= 0.0f) || (ce_w == 0.0f && kd_w == 0.0f))
@@ -334,7 +339,10 @@ struct TrainerCore {
         KF_TRY(kf_memset(ctx, losses, 0, (size_t)N * 4));
         if (teacher)
             KF_TRY(kf_distill_classifier(ctx, logits, teacher, teacher_ld, losses, kd_rows, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, ce_weight, kd_weight, temperature, 1));
-        else
+        else if (loss_mask) { /* the classifier skips an ignored row entirely: its raw logits would be read as a gradient by HeadBack */
+            KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)n_valid, d_tgt, B, T, V, Vp, loss_mask, 1));
+            KF_TRY(kf_zero_ignored_rows(ctx, logits, N, Vp, loss_mask));
+        } else
             KF_TRY(kf_fused_classifier(ctx, logits, losses, nullptr, 1.0f / (float)N, d_tgt, B, T, V, Vp, nullptr, 1));
         ids = d_ids;
         return KF_OK;

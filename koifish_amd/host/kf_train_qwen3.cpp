@@ -12,7 +12,8 @@
 // (kf_d2d_rows: kf_attn_backward takes ONE row stride for q, k and v, and GQA makes the blocks differ in width) -> kf_qknorm_rope_train in place on the fused rows
 // (rstd_q / rstd_k kept) -> kf_attn_prefill_batch_strided -> o_proj + residual -> RMSNorm -> gate, up -> kf_swiglu (gate and up kept) -> down + residual.  Then the final
 // RMSNorm, the head product and kf_fused_classifier with dloss = 1 / N (kf_distill_classifier under kfh_qwen3t_set_distill; kfh_qwen3t_forward_logits stops after the
-// head product: TrainerCore::SetDistill / ForwardLogits).
+// head product: TrainerCore::SetDistill / ForwardLogits).  Under kfh_qwen3t_set_documents (supervised fine-tuning on packed documents) the q/k-norm + RoPE and the
+// attention, forward and backward, are their _pos / _docs forms and the loss is the mean over the rows that count; every other operator is row-wise and unchanged.
 // Backward, the reverse: every matrix through LinBack (a gama-registered one takes the gama branch); gate's and up's input gradients accumulate into one dh, q's, k's and
 // v's into one dh (accumulate_delta); dq | dk | dv of kf_attn_backward go through ONE kf_qknorm_rope_backward (RoPE^T + q/k-norm backward + the dense copies); the
 // embedding backward last, with no position table.
@@ -45,6 +46,10 @@ struct Qwen3Trainer : TrainerCore {
     float* rf = nullptr;
     const float* table = nullptr;  // kf_rope_table_host layout, T positions
     void *sc_ln = nullptr, *sc_at = nullptr, *sc_qk = nullptr;
+    // packed documents (SetDocuments; the layout: include/kf_abi.h): the header of kf_attn_docs_plan's table (a copy), the table's device copy and the rows' positions
+    kf_attn_docs_header doc_hdr = {};
+    const void* doc_tab = nullptr;
+    const int32_t* doc_pos = nullptr;
 
     enum { Q_W = 0, K_W, V_W, O_W, GATE_W, UP_W, DOWN_W, N1, N2, QN, KN, PER_LAYER };
     TrainTensor& P(int l, int k) { return params[(size_t)l * PER_LAYER + k]; }
@@ -59,6 +64,27 @@ struct Qwen3Trainer : TrainerCore {
         if (!xf || !hf || !logits || !dx || !dh || !dqkv || !datt || !dact || !dgate || !vtmp || !dqr || !dkr || !dvd || !rf || !losses || !table || !sc_lin || !sc_ln || !sc_at || !sc_qk)
             return KF_INVALID_ARGS;
         if (!params[(size_t)NL * PER_LAYER].has_blob || (!tied && !params[(size_t)NL * PER_LAYER + 2].has_blob)) return KF_INVALID_ARGS;
+        return KF_OK;
+    }
+    // d_table == NULL: back to B sequences of T rows, the plain step bit for bit with no extra launch.  Otherwise Forward / Backward call kf_attn_prefill_docs,
+    // kf_attn_backward_docs and the _pos forms of the q/k-norm + RoPE entries, and the loss is the mean over the n_valid rows whose mask word lacks 0x10000.
+    // h_header: the head of the host table (copied); d_table, d_pos [N], d_mask [N]: device memory the caller keeps alive.  A refusal changes nothing.
+    int SetDocuments(const kf_attn_docs_header* h_header, const void* d_table, const int32_t* d_pos, const int32_t* d_mask, int n_valid_, std::string* why) {
+        auto refuse = [why](const char* msg) {
+            if (why) *why = msg;
+            return (int)KF_INVALID_ARGS;
+        };
+        if (!d_table) {
+            doc_tab = nullptr, doc_pos = nullptr, loss_mask = nullptr, n_valid = 0, doc_hdr = kf_attn_docs_header{};
+            return KF_OK;
+        }
+        if (teacher) return refuse("set_documents: a teacher is set (set_distill): its forward would need the same layout -- switch distillation off first");
+        if (!h_header || !d_pos || !d_mask) return refuse("set_documents: the header, the positions and the mask words must not be NULL");
+        if (((uintptr_t)d_table & 15) || ((uintptr_t)d_pos & 3) || ((uintptr_t)d_mask & 3)) return refuse("set_documents: the table must be 16-byte aligned, positions and mask words 4-byte aligned");
+        if (h_header->magic != KF_ATTN_DOCS_MAGIC || h_header->n_rows != N || h_header->n_head != H || h_header->n_kv != KV || h_header->head_dim != hd || h_header->max_len > T)
+            return refuse("set_documents: the table was not planned (kf_attn_docs_plan) for this trainer's rows, heads and rope table");
+        if (n_valid_ < 1 || n_valid_ > h_header->doc_rows) return refuse("set_documents: n_valid must be between 1 and the number of document rows");
+        doc_hdr = *h_header, doc_tab = d_table, doc_pos = d_pos, loss_mask = d_mask, n_valid = n_valid_;
         return KF_OK;
     }
     int Lin(TrainTensor& w, const kf_bf16* x, kf_bf16* y, const kf_bf16* res) { return LinForw(w, x, y, res); }  // an adapted matrix: + kf_lora_forward on the same y
@@ -81,8 +107,13 @@ struct Qwen3Trainer : TrainerCore {
             KF_TRY(kf_d2d_rows(ctx, a.qkv, (size_t)W * 2, a.qraw, (size_t)Cq * 2, (size_t)Cq * 2, (size_t)N)); /* q | k | v: column blocks of the fused rows */
             KF_TRY(kf_d2d_rows(ctx, a.qkv + Cq, (size_t)W * 2, a.kraw, (size_t)Ck * 2, (size_t)Ck * 2, (size_t)N));
             KF_TRY(kf_d2d_rows(ctx, a.qkv + Cq + Ck, (size_t)W * 2, vtmp, (size_t)Ck * 2, (size_t)Ck * 2, (size_t)N));
-            KF_TRY(kf_qknorm_rope_train(ctx, a.qkv, a.qkv + Cq, P(l, QN).p, P(l, KN).p, table, N, T, W, W, H, KV, hd, eps, a.rq, a.rk));
-            KF_TRY(kf_attn_prefill_batch_strided(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, a.att, T, W, Cq, H, KV, hd, W, B));
+            if (doc_tab) { /* packed documents: a row's position and the rows it attends to are data */
+                KF_TRY(kf_qknorm_rope_train_pos(ctx, a.qkv, a.qkv + Cq, P(l, QN).p, P(l, KN).p, table, N, doc_pos, W, W, H, KV, hd, eps, a.rq, a.rk));
+                KF_TRY(kf_attn_prefill_docs(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, a.att, &doc_hdr, doc_tab, W, Cq, H, KV, hd, W));
+            } else {
+                KF_TRY(kf_qknorm_rope_train(ctx, a.qkv, a.qkv + Cq, P(l, QN).p, P(l, KN).p, table, N, T, W, W, H, KV, hd, eps, a.rq, a.rk));
+                KF_TRY(kf_attn_prefill_batch_strided(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, a.att, T, W, Cq, H, KV, hd, W, B));
+            }
             KF_TRY(Lin(P(l, O_W), a.att, a.x2, a.x));
             KF_TRY(Rms(a.x2, P(l, N2), a.h2, a.r2));
             KF_TRY(Lin(P(l, GATE_W), a.h2, a.gate, nullptr));
@@ -105,9 +136,15 @@ struct Qwen3Trainer : TrainerCore {
             KF_TRY(LinBack(P(l, GATE_W), dgate, a.h2, dh, nullptr, 1));
             KF_TRY(RmsBack(dx, dh, a.x2, P(l, N2), a.r2));
             KF_TRY(LinBack(P(l, O_W), dx, a.att, datt, nullptr));
-            KF_TRY(kf_attn_backward(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, W, a.att, datt, Cq, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, T, H, KV, hd, B, sc_at));
-            KF_TRY(kf_qknorm_rope_backward(ctx, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, a.qraw, Cq, a.kraw, Ck, P(l, QN).p, P(l, KN).p, a.rq, a.rk, table, N, T, H, KV, hd, dqr, dkr,
-                                           dvd, P(l, QN).g, P(l, KN).g, sc_qk));
+            if (doc_tab) { /* sc_at: kf_attn_backward_docs_scratch_bytes(N, H) = kf_attn_backward_scratch_bytes(T, H, B) */
+                KF_TRY(kf_attn_backward_docs(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, W, a.att, datt, Cq, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, &doc_hdr, doc_tab, H, KV, hd, sc_at));
+                KF_TRY(kf_qknorm_rope_backward_pos(ctx, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, a.qraw, Cq, a.kraw, Ck, P(l, QN).p, P(l, KN).p, a.rq, a.rk, table, N, doc_pos, H, KV, hd,
+                                                   dqr, dkr, dvd, P(l, QN).g, P(l, KN).g, sc_qk));
+            } else {
+                KF_TRY(kf_attn_backward(ctx, a.qkv, a.qkv + Cq, a.qkv + Cq + Ck, W, a.att, datt, Cq, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, T, H, KV, hd, B, sc_at));
+                KF_TRY(kf_qknorm_rope_backward(ctx, dqkv, dqkv + Cq, dqkv + Cq + Ck, W, a.qraw, Cq, a.kraw, Ck, P(l, QN).p, P(l, KN).p, a.rq, a.rk, table, N, T, H, KV, hd, dqr,
+                                               dkr, dvd, P(l, QN).g, P(l, KN).g, sc_qk));
+            }
             KF_TRY(LinBack(P(l, Q_W), dqr, a.h1, dh, nullptr));
             KF_TRY(LinBack(P(l, K_W), dkr, a.h1, dh, nullptr, 1));
             KF_TRY(LinBack(P(l, V_W), dvd, a.h1, dh, nullptr, 1));
@@ -216,5 +253,10 @@ long long kfh_qwen3t_steps_taken(void* h) { return Core(h)->t; }
 KFH_GRAD_CLIP_ENTRIES(qwen3t, koifish::g_q3t_err)
 // distillation against a teacher's logits: TrainerCore::SetDistill / ForwardLogits
 KFH_DISTILL_ENTRIES(qwen3t, koifish::g_q3t_err)
+// packed documents: Qwen3Trainer::SetDocuments (d_table NULL: off).  The GPT-2 trainer has no such entry: its positions are learned
+int kfh_qwen3t_set_documents(void* h, const void* h_header, const void* d_table, const int32_t* d_pos, const int32_t* d_mask, int n_valid) {
+    koifish::g_q3t_err.clear();
+    return Q3(h)->SetDocuments((const kf_attn_docs_header*)h_header, d_table, d_pos, d_mask, n_valid, &koifish::g_q3t_err);
+}
 const char* kfh_qwen3t_last_error(void) { return koifish::g_q3t_err.c_str(); }
 }

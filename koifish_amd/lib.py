@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "kf_qknorm_rope_backward", "kf_qknorm_rope_backward_scratch_bytes", "kf_d2d_rows",
     "kf_linear_rows", "kf_norm_linear_rows", "kf_norm_gateup_swiglu_rows", "kf_norm_lm_head_rows", "kf_head_rows_scratch_bytes", "kf_rows_route_counts", "kf_attn_decode_rows", "kf_attn_rows_scratch_bytes",
     "kf_adamw_scaled", "kf_grad_norms_scratch_bytes", "kf_grad_norms_plan", "kf_grad_norms", "kf_grad_norms_forget",
+    "kf_attn_docs_table_bytes", "kf_attn_docs_plan", "kf_attn_prefill_docs", "kf_attn_backward_docs", "kf_attn_backward_docs_scratch_bytes", "kf_qknorm_rope_train_pos",
+    "kf_qknorm_rope_backward_pos", "kf_zero_ignored_rows",
 ]
 
 
@@ -54,6 +56,16 @@ class Weight(C.Structure):
     """struct kf_weight (include/kf_abi.h)"""
     _fields_ = [("data", C.c_void_p), ("gama", C.c_void_p), ("type", C.c_int32), ("ne0", C.c_int32), ("ne1", C.c_int32), ("nGroup", C.c_int32),
                 ("lGroup", C.c_int32), ("qMin", C.c_int32), ("qMax", C.c_int32), ("qBias", C.c_int32), ("qzeros", C.c_void_p), ("qscales", C.c_void_p), ("quant", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class AttnDocsHeader(C.Structure):
+    """struct kf_attn_docs_header (include/kf_abi.h): the first 64 bytes of a table kf_attn_docs_plan wrote; off / n: the forward, dQ and dK/dV tables in entries"""
+    _fields_ = ([(f, C.c_int32) for f in ("magic", "n_rows", "n_head", "n_kv", "head_dim", "n_doc", "max_len")] + [("off", C.c_int32 * 3), ("n", C.c_int32 * 3)]
+                + [(f, C.c_int32) for f in ("doc_rows", "gap_rows", "reserved_")])
+
+
+ATTN_DOCS_MAGIC = 0x53434F44
+F_IGNORE_LOSS = 0x10000   # MASK_FLAG::F_IGNORE_LOSS: the mask word of a row whose target does not count
 
 
 class LoraPlan(C.Structure):
@@ -139,6 +151,18 @@ def load():
         hip.kf_attn_backward.argtypes = [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         hip.kf_attn_backward_scratch_bytes.argtypes, hip.kf_attn_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
         hip.kf_attn_prefill_batch_strided.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        # packed documents: the host plan, its three launches, the row-position forms of the q/k-norm + RoPE entries
+        docs_layout = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        hip.kf_attn_docs_table_bytes.argtypes, hip.kf_attn_docs_table_bytes.restype = docs_layout, C.c_size_t
+        hip.kf_attn_docs_plan.argtypes = docs_layout + [C.c_void_p, C.c_size_t]
+        hip.kf_attn_prefill_docs.argtypes = [C.c_void_p] * 7 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+        hip.kf_attn_backward_docs_scratch_bytes.argtypes, hip.kf_attn_backward_docs_scratch_bytes.restype = [C.c_int, C.c_int], C.c_size_t
+        hip.kf_attn_backward_docs.argtypes = [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        hip.kf_qknorm_rope_train_pos.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        hip.kf_qknorm_rope_backward_pos.argtypes = ([C.c_void_p] * 4 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+                                                    + [C.c_int] * 3 + [C.c_void_p] * 6)
+        hip.kf_zero_ignored_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         hip.kf_embed_pos.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         hip.kf_argmax_rows_state.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         hip.kf_memset32.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t]
@@ -353,6 +377,8 @@ def load():
         # a low-rank adapter beside a frozen layer matrix: the Qwen3 trainer only
         host.kfh_qwen3t_set_param_lora.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         host.kfh_qwen3t_set_lora_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        # packed documents: (header on the host, table / positions / mask words on the device, n_valid); the Qwen3 trainer only
+        host.kfh_qwen3t_set_documents.argtypes = [C.c_void_p] * 5 + [C.c_int]
         # EOE: layer-section branches, the evolve step over the swarm, the ensemble evaluation
         host.kfh_gpt2_set_branches.argtypes = [C.c_void_p, C.c_int]
         host.kfh_gpt2_n_branches.argtypes = [C.c_void_p]

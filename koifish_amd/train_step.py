@@ -464,6 +464,10 @@ class Qwen3Step(_TrainStep):
     lora_state() hands out the trained pairs, merged_masters() the masters of an equivalent plain model, as_model(max_seq, adapters=True) a decoder on the packed base
     with the pairs attached (kf_lora_apply); plain as_model(max_seq) refuses.
 
+    set_documents(doc_lens, doc_rows, loss_mask): supervised fine-tuning on packed documents -- any number of documents share the B * T rows, each at its own positions
+    and attending to itself only, the loss over the rows that count (sft_loss()); the attention and the q/k-norm + RoPE, forward and backward, then run their _docs /
+    _pos entries, everything else is row-wise and unchanged.
+
     Not offered on this trainer: EOE layer-section branches (GPT2Step's layers_in_branch)."""
 
     _targets = ("weights", "gama", "lora")
@@ -578,6 +582,92 @@ class Qwen3Step(_TrainStep):
             raise L.KFError("kfh_qwen3t_create refused the shape: %s" % host.kfh_qwen3t_last_error().decode())
         bufs = (self.xf, self.hf, self.rf, self.logits, self.losses, self.dx, self.dh, self.dqkv, self.datt, self.dact, self.dgate, self.vtmp, self.dqr, self.dkr, self.dvd, self.table)
         self._attach(bufs, (self._sc_ln, self._sc_at, self._sc_qk))
+
+    # ---- supervised fine-tuning on packed documents (the layout: include/kf_abi.h; the reference's P_SFT phase pads one sample per batch row instead)
+    _docs = None   # the active layout: dict(lens, rows, n_valid, and the device tensors the trainer reads), None: B sequences of T rows
+
+    @classmethod
+    def check_documents(cls, cfg, B, T, doc_lens, doc_rows=None, loss_mask=None):
+        """every argument error of set_documents as a ValueError, without a device.  doc_lens: the documents' lengths, each in 1 .. T; doc_rows: their first rows in
+        the B * T rows of a step, ascending and not overlapping (None: back to back from row 0); loss_mask: bool [B * T], True = this row's target counts (None: every
+        document row).  A gap row -- a row in no document -- never counts.  Returns dict(lens, rows: int32 [n_doc]; pos: int32 [N], a row's position in its document, 0 in
+        a gap; mask: int32 [N], 0x10000 (F_IGNORE_LOSS) on every row that does not count; n_valid: the rows that count)."""
+        import numpy as np
+        N = B * T
+        try:
+            lens = [int(x) for x in doc_lens]
+            rows = None if doc_rows is None else [int(x) for x in doc_rows]
+            if any(a != b for a, b in zip(lens, doc_lens)) or (rows is not None and any(a != b for a, b in zip(rows, doc_rows))):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError("set_documents: doc_lens and doc_rows must be sequences of ints") from None
+        if not lens:
+            raise ValueError("set_documents: at least one document (None switches documents off)")
+        if rows is None:
+            rows = [sum(lens[:d]) for d in range(len(lens))]
+        if len(rows) != len(lens):
+            raise ValueError("set_documents: %d lengths but %d first rows" % (len(lens), len(rows)))
+        at = 0
+        for d, (r, n) in enumerate(zip(rows, lens)):
+            if not 1 <= n <= T:
+                raise ValueError("set_documents: document %d has %d rows: 1 .. %d (the rope table's length)" % (d, n, T))
+            if r < at:
+                raise ValueError("set_documents: document %d starts at row %d, before row %d where the one before it ends: ascending, no overlap" % (d, r, at))
+            if r + n > N:
+                raise ValueError("set_documents: document %d ends at row %d, past the step's %d rows" % (d, r + n, N))
+            at = r + n
+        lens_a, rows_a = np.asarray(lens, dtype=np.int32), np.asarray(rows, dtype=np.int32)
+        H, KV, hd = cfg["n_head"], cfg["n_kv"], cfg["head_dim"]
+        if not L.load()[0].kf_attn_docs_table_bytes(rows_a.ctypes.data_as(C.c_void_p), lens_a.ctypes.data_as(C.c_void_p), len(lens), N, T, H, KV, hd):
+            raise ValueError("set_documents: the attention entries do not take %d / %d heads of %d (head_dim 64 or 128, n_head / n_kv in 1, 2, 4, 8)" % (H, KV, hd))
+        pos, in_doc = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=bool)
+        for r, n in zip(rows, lens):
+            pos[r:r + n], in_doc[r:r + n] = np.arange(n, dtype=np.int32), True
+        if loss_mask is None:
+            counts = in_doc
+        else:
+            counts = np.asarray(loss_mask.cpu() if torch.is_tensor(loss_mask) else loss_mask)
+            if counts.dtype != np.bool_ or counts.shape != (N,):
+                raise ValueError("set_documents: loss_mask must be bool [%d] (got %s %s)" % (N, counts.dtype, tuple(counts.shape)))
+            counts = counts & in_doc
+        n_valid = int(counts.sum())
+        if n_valid == 0:
+            raise ValueError("set_documents: no row counts in the loss (the mask selects no document row): the mean over zero rows is undefined")
+        return dict(lens=lens_a, rows=rows_a, pos=pos, mask=np.where(counts, 0, L.F_IGNORE_LOSS).astype(np.int32), n_valid=n_valid)
+
+    def set_documents(self, doc_lens, doc_rows=None, loss_mask=None):
+        """Train on packed documents from here on (kept until changed, like set_distill): document d owns rows [doc_rows[d], doc_rows[d] + doc_lens[d]) of the B * T rows
+        of ids / tgt, a row stands at its position inside its document and attends causally to its own document only, and the loss is the mean over the rows of
+        loss_mask (None: every document row; a gap row never counts) -- sft_loss().  Documents may start at any row and cross the B row boundaries; rows in no document
+        cost their share of the GEMMs and nothing else (their ids must still be valid token ids).  Plans on the host (kf_attn_docs_plan), uploads once; forward /
+        backward then run kf_attn_prefill_docs, kf_attn_backward_docs and the _pos forms of the q/k-norm + RoPE entries.  Everything else -- train_target, Muon,
+        clipping, as_model -- is row-wise and works unchanged; set_distill is refused while documents are set, and the other way round.  set_documents(None): back to B
+        sequences of T rows, the plain step bit for bit."""
+        import numpy as np
+        if doc_lens is None:
+            self._call("set_documents", None, None, None, None, 0, check=self._check_host)
+            self._docs = None
+            return
+        d = self.check_documents(self.cfg, self.B, self.T, doc_lens, doc_rows, loss_mask)
+        hip, cfg = self.ctx.hip, self.cfg
+        geom = (len(d["lens"]), self.N, self.T, cfg["n_head"], cfg["n_kv"], cfg["head_dim"])
+        lp, rp = d["lens"].ctypes.data_as(C.c_void_p), d["rows"].ctypes.data_as(C.c_void_p)
+        table = np.zeros(hip.kf_attn_docs_table_bytes(rp, lp, *geom), dtype=np.uint8)
+        L.check(hip.kf_attn_docs_plan(rp, lp, *geom, table.ctypes.data_as(C.c_void_p), table.size), "kf_attn_docs_plan")
+        dev = {k: torch.from_numpy(v).to(self.ctx.device) for k, v in (("table", table), ("pos", d["pos"]), ("mask", d["mask"]))}
+        self._call("set_documents", table.ctypes.data_as(C.c_void_p), dev["table"].data_ptr(), dev["pos"].data_ptr(), dev["mask"].data_ptr(), d["n_valid"], check=self._check_host)
+        # only now: a refusal changes nothing in the trainer, which then still reads the tensors it had
+        self._docs = dict(d, dev=dev)
+
+    def documents(self):
+        """the active layout: dict(lens, rows: int32 numpy [n_doc]; n_valid), or None"""
+        return None if self._docs is None else {k: self._docs[k] for k in ("lens", "rows", "n_valid")}
+
+    def sft_loss(self):
+        """the mean loss of the last forward over the rows that count: losses.sum() / n_valid -- the one host read, made here and never inside forward / step"""
+        if self._docs is None:
+            raise L.KFError("sft_loss: no documents are set (set_documents)")
+        return float(self.losses.sum()) / self._docs["n_valid"]
 
     def as_model(self, max_seq, adapters=False):
         """a Qwen3 decoder on the trainer's OWN blobs and norm tensors (set_weight / set_norm / tie_head with device pointers: no copy), vocabulary = the unpadded one.
