@@ -19,6 +19,8 @@
 //     so the FIRST sweep of a hand-off is issued a fixed delay behind the moment this workgroup's own rows of the feeding phase were
 //     published (all workgroups do the same work in step): scratch/ub_handoff3.hip, 1.2 us per edge instead of 2.1-2.3.
 //     The vectors that cross XCDs live in uncached device memory (an sc1 sweep costs 43 ns per KB there, 75 in cached memory).
+//     Being the youngest wave it loses VALU issue to its SIMD partner's ahead-of-phase dequantisation at equal priority, so it runs the step's serial chains --
+//     sweep + RMSNorm + staging of x and xB, the slice merge -- at s_setprio ENG_POLLER_PRIO and everything else at 0 (ENG_PRIO_UP / ENG_PRIO_DOWN).
 //   * waves 0..6 hold the phase's 16-byte weight blocks in registers -- requested one phase ahead, unconditionally, so HBM latency is
 //     off the chain and every wait is a counted s_waitcnt vmcnt(N) -- and multiply when the barrier behind the poller's staging opens.
 //     The arithmetic is the mat-vec kernel's (kf_gemv_blocks.h: same lanes per row, same per-lane chain, same DPP tree) and the
@@ -97,6 +99,16 @@ struct EngArgs {
     unsigned long long* dbg; /* diagnostic instantiation only (KF_ENG_DEBUG): [layer][role][16] wall-clock stamps of workgroup dbg_wg */
     int dbg_wg;
 };
+// the poller's priority over one serial chain (ENG_POLLER_PRIO, kf_engine_common.h): s_setprio is a scalar instruction that ignores EXEC, so only inside the poller's
+// arm of the (scalar) role branch
+#define ENG_PRIO_UP()                                                                          \
+    do {                                                                                       \
+        if constexpr (ENG_POLLER_PRIO != 0) __builtin_amdgcn_s_setprio(ENG_POLLER_PRIO);        \
+    } while (0)
+#define ENG_PRIO_DOWN()                                                     \
+    do {                                                                    \
+        if constexpr (ENG_POLLER_PRIO != 0) __builtin_amdgcn_s_setprio(0);  \
+    } while (0)
 #define ENG_STAMP(role, k)                                                                                                           \
     do {                                                                                                                         \
         if (DBG && wg == a.dbg_wg && lane == 0) a.dbg[((size_t)l * 2 + (role)) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
@@ -594,7 +606,8 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
     constexpr int XCH = C::XCH, hd = HD, hd_log2 = HD == 128 ? 7 : 6;
     bool dead = false;
     const bool has1 = XMAP ? true : wg * P1::spg < P1::total, has4 = wg * P4::spg < P4::total, has5 = wg * P5::spg < P5::total, has6 = wg * P6::spg < P6::total;
-    // the poller's share of P1 (virtual compute wave NWV - 1)
+    // the poller's share of P1 and its part of the all-wave phases: its role index, the last (virtual) compute wave
+    constexpr int PW = eng_poller_role<NWV>();
     constexpr int NCW1 = ENG_P1_SHARE ? NWV : NWV - 1, S1 = c_maxs<P1, NCW1>(), NWP1 = P1::spg < NCW1 ? P1::spg : NCW1;
     constexpr bool P1_SHARE = ENG_P1_SHARE && P1::spg >= NWV; /* the poller owns a slot */
     const float qb1 = S.j1 == 0 ? a.qbias[0] : (S.j1 == 1 ? a.qbias[1] : a.qbias[2]);
@@ -603,22 +616,23 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
     auto mat1 = [&](int l) { /* the matrix of this workgroup's P1 rows in layer l */
         return L.lay[l].m[S.j1];
     };
-    if (P1_SHARE) mv_prefetch<P1, NCW1, FMT, S1>(mat1(0), mat1(0), S.s1, NWV - 1, lane, S.M1, r1);
+    if (P1_SHARE) mv_prefetch<P1, NCW1, FMT, S1>(mat1(0), mat1(0), S.s1, PW, lane, S.M1, r1);
     EngAttnState<C> T;
 #pragma unroll
     for (int u = 0; u < EngAttnState<C>::U; u++) T.kk[u] = T.vv[u] = u32x4{0, 0, 0, 0};
     eng_attn_rope<C>(a, S, lane, T);
-    if (S.has_unit && !S.empty) eng_attn_issue<C>(a, L.lay[0], S, NWV - 1, lane, T, 0);
+    if (S.has_unit && !S.empty) eng_attn_issue<C>(a, L.lay[0], S, PW, lane, T, 0);
     int sw[4] = {0, 0, 0, 0};
     int swt[6] = {0, 0, 0, 0, 0, 0}; /* this step's sweeps of the poller per hand-off (x, q|k|v, slice partials, ao, xB, act): workgroup 0 adds them to the engine's statistics */
     for (int l = 0; l < a.n_layer; l++) {
         const EngLayer& ly = L.lay[l];
         const uint32_t gen = (uint32_t)epoch * (uint32_t)a.n_layer + (uint32_t)l, tag = gen & 0xffffu;
-        if (S.has_unit && !S.empty) eng_attn_normw<C>(ly, NWV - 1, lane, T);
+        if (S.has_unit && !S.empty) eng_attn_normw<C>(ly, PW, lane, T);
         MvPhase<C, P1, NCW1, S1> w1;
-        if (P1_SHARE) w1.ahead(qb1, 0.f, NWV - 1, lane, r1, L.q1tab); /* its blocks were requested behind the previous layer's attention phase */
+        if (P1_SHARE) w1.ahead(qb1, 0.f, PW, lane, r1, L.q1tab); /* its blocks were requested behind the previous layer's attention phase */
         // P1 (P4 adds this x as the residual)
         ENG_STAMP(0, 0);
+        ENG_PRIO_UP();
         if (has1 || has4) {
             if (l == 0) {
                 const uint16_t* x0 = a.x_in;
@@ -653,10 +667,11 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
                                                                a.delay[0]);
             }
         }
+        ENG_PRIO_DOWN();
         ENG_STAMP(0, 1);
         __syncthreads();
         if (P1_SHARE && has1) { /* this wave's P1 rows, then the workgroup's publish like every other owner */
-            w1.run(S.s1, NWV - 1, lane, S.M1, L.xs[0], 0xffffffffu, r1, [&](int row, float v, float) { L.outb[row - row0_1] = (tag << 16) | (uint32_t)f2bf(v); });
+            w1.run(S.s1, PW, lane, S.M1, L.xs[0], 0xffffffffu, r1, [&](int row, float v, float) { L.outb[row - row0_1] = (tag << 16) | (uint32_t)f2bf(v); });
             if (XMAP)
                 wg_publish(L, 0, eng_lqkv<C>(a, S.xcc), S.q_out0, P1::R, NWP1, lane, true);
             else
@@ -703,16 +718,16 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
             if (P1_SHARE) { /* the next layer's P1 blocks of this wave: unconditional (the last layer requests its own again), and HERE -- loads return in order, so a
                                request in front of a poll holds that poll's sweep back by an HBM latency; the attention phase waits for nothing younger than its tiles */
                 const int ln = l + 1 < a.n_layer ? l + 1 : l;
-                mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, NWV - 1, lane, S.M1, r1);
+                mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, PW, lane, S.M1, r1);
             }
-            eng_attn_phase<C>(a, L, S, ly, gen, tag, NWV - 1, lane, T, l, wg);
+            eng_attn_phase<C>(a, L, S, ly, gen, tag, PW, lane, T, l, wg);
             /* the next layer's tiles (the last layer asks for its own again).  Round 4 moved this request of the poller behind the merge's sweep (loads return in order: the sweep's
                answer might wait for these sixteen HBM lines) and, with a second register set, in front of the attention phase: 387 / 392 us per launch against 383 / 390 here --
                the ao store then queues behind the tile requests, and the earlier sweep mostly comes too early */
-            if (!S.empty) eng_attn_issue<C>(a, L.lay[l + 1 < a.n_layer ? l + 1 : l], S, NWV - 1, lane, T, 0);
+            if (!S.empty) eng_attn_issue<C>(a, L.lay[l + 1 < a.n_layer ? l + 1 : l], S, PW, lane, T, 0);
         } else if (P1_SHARE) { /* a workgroup without an attention slice at this position: the same request, nothing to poll in front of it */
             const int ln = l + 1 < a.n_layer ? l + 1 : l;
-            mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, NWV - 1, lane, S.M1, r1);
+            mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, PW, lane, S.M1, r1);
         }
         // P3: merge the slices of this workgroup's output elements: exact rescales to the largest exponent, fp64 sums, one division (kf_attn_common.h)
         ENG_STAMP(0, 3);
@@ -727,6 +742,7 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
             const bool mine = lane < nsp;
             eng_wait_pub(nullptr, 0, a.delay[2], dead);
             ENG_STAMP(0, 9);
+            ENG_PRIO_UP();
             int msw = 0;
             for (int spins = 0;; spins++) {
                 uint32_t bad = 0;
@@ -795,27 +811,30 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
             } else if (holder) {
                 __hip_atomic_store(ao_dst + he, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            ENG_PRIO_DOWN();
         }
         // P4, P5 (P6 adds that x as the residual), P6
         ENG_STAMP(0, 4);
         if (ENG_COOP) { /* the ao vector: timed by this wave, swept by all eight */
             if (has4) eng_wait_pub(nullptr, 0, a.delay[3], dead);
             __syncthreads();
-            if (has4) eng_poll_stage_part<XCH, NQD, P4::nBlk, NWV, C::F32X>(a.xch + C::ao, tag, L.xs[1], NWV - 1, lane, a.ws, dead, &sw[1]);
+            if (has4) eng_poll_stage_part<XCH, NQD, P4::nBlk, NWV, C::F32X>(a.xch + C::ao, tag, L.xs[1], PW, lane, a.ws, dead, &sw[1]);
         } else if (has4) {
             eng_poll_stage<XCH, NQD, P4::nBlk, false, false, C::F32X>(a.xch + C::ao, nullptr, tag, nullptr, 0.f, L.xs[1], nullptr, lane, a.ws, dead, &sw[1], nullptr, 0, a.delay[3]);
         }
         ENG_STAMP(0, 5);
         __syncthreads();
+        ENG_PRIO_UP();
         if (has5 || has6)
             eng_poll_stage<XCH, ND, P5::nBlk, true, false, C::F32X>(a.xch + C::xB, nullptr, tag, ly.norm_post, a.eps, L.xs[0], L.xrawB, lane, a.ws, dead, &sw[2], has4 ? L.pub + 1 : nullptr, l + 1,
                                                            a.delay[4]);
+        ENG_PRIO_DOWN();
         ENG_STAMP(0, 6);
         __syncthreads();
         if (ENG_COOP) {
             if (has6) eng_wait_pub(has5 ? L.pub + 2 : nullptr, l + 1, a.delay[5], dead);
             __syncthreads();
-            if (has6) eng_poll_stage_part<XCH, NF, P6::nBlk, NWV, C::F32X>(a.xch + C::act, tag, L.xs[1], NWV - 1, lane, a.ws, dead, &sw[3]);
+            if (has6) eng_poll_stage_part<XCH, NF, P6::nBlk, NWV, C::F32X>(a.xch + C::act, tag, L.xs[1], PW, lane, a.ws, dead, &sw[3]);
         } else if (has6) {
             eng_poll_stage<XCH, NF, P6::nBlk, false, false, C::F32X>(a.xch + C::act, nullptr, tag, nullptr, 0.f, L.xs[1], nullptr, lane, a.ws, dead, &sw[3], has5 ? L.pub + 2 : nullptr, l + 1, a.delay[5]);
         }
@@ -988,7 +1007,7 @@ template <class C>
 __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L, int epoch, bool more_steps, int wg, int wave, int lane) {
     using HS = HeadScreen<C>;
     constexpr int NWV = C::NWV, NWG = C::NWG, nBlk = C::HnBlk, LPR = C::HLPR, RPS = C::HRPS, ITERS = C::Hiters, HG = HS::HG;
-    constexpr int ND = C::DIM / 256;
+    constexpr int ND = C::DIM / 256, PW = eng_poller_role<NWV>();
     constexpr int nBlk8 = HS::nBlk8, IT8 = HS::IT8, HG8 = HS::HG8, CAP = HS::CAP;
     const int sub = lane >> C::Hlpr_log2, ll = lane & (LPR - 1);
     const int total = (a.vocab + RPS - 1) / RPS, spg = (total + NWG - 1) / NWG; /* slots in all, per workgroup */
@@ -1051,7 +1070,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
         issue(0, 0);
     }
     const uint32_t gen = (uint32_t)(epoch + 1) * (uint32_t)a.n_layer, tag = gen & 0xffffu; /* the generation the last layer's down_proj published its rows with */
-    if (wave == NWV - 1) {
+    if (wave == PW) {
         bool dead = false;
         const bool has6 = wg * C::SH::P6::spg < C::SH::P6::total;
         eng_poll_stage<1, ND, nBlk, true, false, false>(a.xch + C::xA, nullptr, tag, a.head_norm, a.eps, L.xs[0], nullptr, lane, a.ws, dead, nullptr, has6 ? L.pub + 3 : nullptr, a.n_layer,
@@ -1245,7 +1264,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
         const unsigned long long gr = ((unsigned long long)((tag << 16) | (uint32_t)f2bf(best_v)) << 32) | (unsigned long long)(uint32_t)best_i;
         __hip_atomic_store(hb + wg, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (wg == 0 && wave == NWV - 1 && a.d_state_w) { /* the pick (argmax_finish_kernel): NWG granules, 4 per lane */
+    if (wg == 0 && wave == PW && a.d_state_w) { /* the pick (argmax_finish_kernel): NWG granules, 4 per lane */
         static_assert(NWG == 256, "four granules per lane");
         const __amdgpu_buffer_rsrc_t rs = eng_rsrc(hb, NWG * 8u);
         u32x4 g0, g1;
@@ -1288,7 +1307,7 @@ __device__ __forceinline__ void eng_head_main(const EngArgs& a, const EngLds& L,
 // DIM, QD, KVD, FFN: the model's dim, q_dim, kv_dim, ffn; NWG: the grid (= CUs): sweeps and mat-vec geometry are straight-line code
 template <class C>
 __global__ void __launch_bounds__(C::NWV * 64) engine_kernel(const EngArgs a) {
-    constexpr int hd = C::HD, GQ = C::GQ, NWV = C::NWV;
+    constexpr int hd = C::HD, GQ = C::GQ, NWV = C::NWV, PW = eng_poller_role<NWV>();
     constexpr bool XMAP = C::XMAP;
     using P1 = typename C::SH::P1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1429,15 +1448,15 @@ __global__ void __launch_bounds__(C::NWV * 64) engine_kernel(const EngArgs a) {
         int sz; /* as inside the layer loop: nothing derived from the lane id is to be hoisted out of the step loop and held in registers across a whole step */
         asm volatile("s_mov_b32 %0, 0" : "=s"(sz));
         const int lane_s = lane + sz;
-        if (wave == NWV - 1)
+        if (wave == PW)
             eng_poller_main<C>(a, L, S, epoch, step, wg, lane_s);
         else
             eng_compute_main<C>(a, L, S, epoch, wg, wave, lane_s);
         if (a.head_on) { /* stamped form: the head phase of the last layer's row, poller slots 12 / 13 (a full head) and 14 / 15 (a screened one) */
             const int hs = (a.screen_q != nullptr && step + 1 < nst) ? 14 : 12;
-            if (C::DBG && wg == a.dbg_wg && tid == (NWV - 1) * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs] = __builtin_amdgcn_s_memrealtime();
+            if (C::DBG && wg == a.dbg_wg && tid == PW * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs] = __builtin_amdgcn_s_memrealtime();
             eng_head_main<C>(a, L, epoch, step + 1 < nst, wg, wave, lane_s);
-            if (C::DBG && wg == a.dbg_wg && tid == (NWV - 1) * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs + 1] = __builtin_amdgcn_s_memrealtime();
+            if (C::DBG && wg == a.dbg_wg && tid == PW * 64) a.dbg[((size_t)(a.n_layer - 1) * 2) * 16 + hs + 1] = __builtin_amdgcn_s_memrealtime();
         }
     }
     // the next launch's generation (workgroup 0 owns rows of the last phase, so every workgroup has read the epoch long before)
@@ -1664,9 +1683,11 @@ int engine_debug_enable(EngineHost* E, int wg) {
     engine_repick(E, E->form->canon);
     return KF_OK;
 }
-void engine_set_delays(EngineHost* E, const int* d6) { /* every slice count */
-    for (int n = 0; n <= KF_ATTN_MAX_SPLITS; n++)
+void engine_set_delays(EngineHost* E, const int* d6) { /* every slice count; no row counts as measured any more (kf_engine_stats out[13]) */
+    for (int n = 0; n <= KF_ATTN_MAX_SPLITS; n++) {
         for (int i = 0; i < 6; i++) E->delay_tab[n][i] = d6[i];
+        E->tuned[n] = 0;
+    }
 }
 int engine_debug_read(EngineHost* E, unsigned long long* h_out, int n_words) {
     const int have = E->args.n_layer * 2 * 16;

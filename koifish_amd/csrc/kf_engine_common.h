@@ -19,6 +19,18 @@ constexpr int ENG_NWG = 256, ENG_NWV = 8; /* MI355X: 256 CUs, one 8-wave workgro
 #endif
 constexpr int ENG_SPIN_MAX = 1 << 17;     /* sweeps before a poll gives up (~0.1 s): sets the error word, never hangs */
 
+// ---- the roles of the persistent engine's waves, stated once.  Roles 0 .. NWV - 2 are the compute waves; role NWV - 1 is the poller and, where a phase is shared with
+// it, the last "virtual" compute wave.  A wave is the poller where its index equals the CONSTANT `constexpr int PW = eng_poller_role<NWV>()` (behind a function call
+// in the condition the same test no longer compiles to the same kernel text).
+template <int NWV>
+constexpr int eng_poller_role() { return NWV - 1; }
+// The poller is the youngest wave of the workgroup, and between the two waves of a SIMD the VALU issues by priority, then by age: at equal priority its serial chains
+// (sweep, RMSNorm, staging; the slice merge) lose every contested slot to the weight dequantisation its partner runs ahead of the next phase.  It therefore raises its
+// priority to ENG_POLLER_PRIO over exactly those chains and lowers it behind them (0: no s_setprio is emitted -- the A/B build of scratch/build_variant.py).
+#ifndef ENG_POLLER_PRIO
+#define ENG_POLLER_PRIO 1
+#endif
+
 // device tables hold GLOBAL pointers (address space 1): read back from LDS they would otherwise be generic, and every access through them a
 // flat_load, which the hardware returns out of order, so every wait behind one is a drain (vmcnt(0) + lgkmcnt(0))
 #define KF_GLOBAL __attribute__((address_space(1)))
