@@ -66,7 +66,7 @@ def build_hip(force=False, verbose=False):
 def _host_inputs():
     """the host library's translation units, and everything a change to which makes it stale"""
     srcs = [os.path.join(HOST, s) for s in HOST_SOURCES]
-    return srcs, srcs + [os.path.join(HOST, d) for d in HOST_DEPS] + [os.path.join(HERE, "..", "include", "kf_abi.h"), LIB_HIP]
+    return srcs, srcs + [os.path.join(HOST, d) for d in HOST_DEPS] + [os.path.join(HERE, "..", "include", h) for h in ("kf_abi.h", "kf_host_abi.h")] + [LIB_HIP]
 
 
 def build_host(force=False, verbose=False):

@@ -1,5 +1,6 @@
 // kf_host.cpp -- see kf_host.hpp.  Plain C++17, no HIP headers; every device action is a kf_* ABI call.
 #include "kf_host.hpp"
+#include "../../include/kf_host_abi.h"
 
 #include <cassert>
 #include <cmath>

@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "kf_host.hpp"
+#include "../../include/kf_host_abi.h"
 
 namespace koifish {
 

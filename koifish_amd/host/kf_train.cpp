@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "kf_train_common.hpp"
+#include "../../include/kf_host_abi.h"
 
 namespace koifish {
 

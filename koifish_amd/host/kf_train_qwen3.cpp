@@ -26,6 +26,7 @@
 #include <string>
 
 #include "kf_train_common.hpp"
+#include "../../include/kf_host_abi.h"
 
 namespace koifish {
 

@@ -1,7 +1,8 @@
-"""The ctypes mirror of kf::GemmMat / kf::A8Problem / kf::A8Plan (csrc/kf_a8.h) and the call of kfdbg_a8_route_plan, once, for every test of the int8-activation products."""
+"""The ctypes mirror of kf::A8Problem / kf::A8Plan (csrc/kf_a8.h; kf::GemmMat: plan_structs.py) and the call of kfdbg_a8_route_plan, once, for every test of the int8-activation products."""
 import ctypes as C
 
 from koifish_amd import lib as L
+from plan_structs import GemmMat as Mat
 
 BF16, F8, Q4, Q3, Q2, T_SIGN, BOOL1, T_BINARY = 3, 4, 14, 15, 16, 17, 19, 20   # kf_dtype
 GROUP, ROW_LUT, ROW_RTN = 0, 1, 2                                              # quant forms
@@ -9,10 +10,6 @@ OK, INVALID_ARGS, QUANT_ERR, UNSUPPORTED, UNALIGN = 0, -20, -701, -1000, -2000
 ORDER_CHAIN, TOK_TILE, GROUP_LDS, LDS_MAX, TILE_MIN = 1, 4, 144, 160 * 1024, 32   # kf_a8.h; TILE_MIN = KF_A8_TILE_MIN (include/kf_abi.h)
 LOWBIT, Q4_FAMILY = 1, 2                                                       # A8Plan::family
 MATVEC, TILES = 0, 1                                                           # A8Problem::route
-
-
-class Mat(C.Structure):   # kf::GemmMat
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
 
 
 class Problem(C.Structure):   # kf::A8Problem

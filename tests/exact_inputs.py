@@ -20,6 +20,7 @@ import numpy as np
 
 import attn_plan_mirror as APM
 from oracle import oracle as O
+from plan_structs import GemmMat as _Mat, GemmPlan as _Plan, GemmProblem as _Problem, ScorePlan as _ScorePlan, ScoreProblem as _ScoreProblem
 
 BOUND = 256.0   # every integer of magnitude <= 256 is a bf16 value: the bf16 store of an exact result within the bound is that result
 
@@ -139,23 +140,6 @@ BF16_T, BWD_DX, BWD_DW = 3, 4, 5
 ROUTES = {11: "KMAJOR", 12: "TRANSPOSE"}
 FAMILIES = {0: "NONE", 1: "DIRECT", 2: "PAIRED", 3: "STAGED", 4: "G2", 5: "G3"}
 G3_FORMS = {0: "BIG", 1: "SMALL", 2: "MID", 3: "TINY", 4: "WIDE"}
-
-
-class _Mat(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class _Problem(C.Structure):
-    _fields_ = [("entry", C.c_int), ("n_w", C.c_int), ("w", _Mat * 3), ("n", C.c_int), ("x_al", C.c_int), ("y_al", C.c_int), ("rope_ok", C.c_int), ("arena", C.c_int),
-                ("capturing", C.c_int), ("arena_hit", C.c_int), ("arena_free", C.c_longlong), ("scratch", C.c_longlong)]
-
-
-class _Kern(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("fam", "fmt", "gshift", "form", "akm", "bkm", "gx", "gy", "block", "lds", "sk", "P", "S", "kp", "R")]
-
-
-class _Plan(C.Structure):
-    _fields_ = [("route", C.c_int), ("status", C.c_int), ("deq", C.c_int), ("deq_form", C.c_int), ("deq_bytes", C.c_longlong), ("ws_bytes", C.c_longlong), ("k", _Kern)]
 
 
 def _up256(v):
@@ -932,14 +916,6 @@ def level_fold(logits, targets, V, bm, mutate=None):
 # ---- the plan behind kf_head_logprob (kf_score_plan.h score_plan through kfdbg_score_plan), the problem filled as kf_abi.hip score_problem fills it
 SR_FUSED, SR_PANEL = 0, 1
 SCORE_BIG, SCORE_SMALL = 0, 1            # G3 forms; the "score_form" knob: < 0 the rule
-
-
-class _ScoreProblem(C.Structure):
-    _fields_ = [("w", _Mat), ("n", C.c_int), ("x_al", C.c_int), ("force", C.c_int), ("form", C.c_int)]
-
-
-class _ScorePlan(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("route", "status", "form", "n_vt", "n_rb", "gx", "block", "lds", "panel_rows")] + [("scratch", C.c_longlong)]
 
 
 def score_plan(hip, key):

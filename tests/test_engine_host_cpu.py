@@ -6,23 +6,12 @@ import ctypes as C
 import pytest
 
 from koifish_amd import lib as L
+from plan_structs import EngineDesc, EngineLayer
 
 OK, INVALID_ARGS, UNSUPPORTED = 0, -20, -1000   # kf_abi.h
 PERSISTENT, XCD = 0, 1
 HEAD, EMBEDDING = 0, 1
 ADDR = 0x7f0000001000   # "device" addresses: never read
-
-
-class EngineLayer(C.Structure):
-    """struct kf_engine_layer (include/kf_abi.h)"""
-    _fields_ = [("w", L.Weight * 7), ("norm_in", C.c_void_p), ("norm_post", C.c_void_p), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p), ("kcache", C.c_void_p),
-                ("vcache", C.c_void_p), ("hot_ffn", C.c_void_p)]
-
-
-class EngineDesc(C.Structure):
-    """struct kf_engine_desc (include/kf_abi.h)"""
-    _fields_ = [(f, C.c_int32) for f in ("n_layer", "dim", "n_head", "n_kv", "head_dim", "ffn", "kv_stride", "max_seq")] + [
-        ("rms_eps", C.c_float), ("qk_eps", C.c_float), ("rope_table", C.c_void_p), ("layers", C.POINTER(EngineLayer))]
 
 
 @pytest.fixture(scope="module")

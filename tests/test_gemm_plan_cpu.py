@@ -7,6 +7,7 @@ import ctypes as C
 import pytest
 
 from koifish_amd import lib as L
+from plan_structs import GemmKern as Kern, GemmMat as Mat, GemmPlan as Plan, GemmProblem as Problem
 
 BF16, F8, Q4, Q3, T_SIGN = 3, 4, 14, 15, 17             # kf_dtype
 GROUP, ROW_LUT = 0, 1                                     # quant forms
@@ -19,23 +20,6 @@ BIG, SMALL, MID, TINY, WIDE = range(5)                    # G3 forms
 STACK, ILV = 0, 1
 SK_BYTES = 256 * 256 * 256 * 4 + 8192                     # gemm3_sk_ws_bytes()
 LOTS = 1 << 30
-
-
-class Mat(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):
-    _fields_ = [("entry", C.c_int), ("n_w", C.c_int), ("w", Mat * 3), ("n", C.c_int), ("x_al", C.c_int), ("y_al", C.c_int), ("rope_ok", C.c_int), ("arena", C.c_int),
-                ("capturing", C.c_int), ("arena_hit", C.c_int), ("arena_free", C.c_longlong), ("scratch", C.c_longlong)]
-
-
-class Kern(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("fam", "fmt", "gshift", "form", "akm", "bkm", "gx", "gy", "block", "lds", "sk", "P", "S", "kp", "R")]
-
-
-class Plan(C.Structure):
-    _fields_ = [("route", C.c_int), ("status", C.c_int), ("deq", C.c_int), ("deq_form", C.c_int), ("deq_bytes", C.c_longlong), ("ws_bytes", C.c_longlong), ("k", Kern)]
 
 
 def mat(M, K, type=Q4, quant=GROUP, lgroup=128, al=3, awq=0):

@@ -9,6 +9,7 @@ import pytest
 
 from koifish_amd import lib as L
 from oracle import oracle as O
+from plan_structs import GemmMat as Mat, GemvPlan as Plan, GemvProblem as Problem
 
 BF16, F8, Q4, Q3, Q2, T_SIGN, BOOL1, T_BINARY = 3, 4, 14, 15, 16, 17, 19, 20   # kf_dtype
 GROUP, ROW_LUT, ROW_RTN = 0, 1, 2                                              # quant forms
@@ -16,19 +17,6 @@ FMT_BF16, FMT_F8, FMT_Q4, FMT_Q2, FMT_Q1, FMT_Q4P, FMT_Q4R, FMT_Q1T, FMT_Q2T = r
 PLAIN, PAIRED, ARGMAX = range(3)                                               # GEMV_*
 OK, INTERNAL_ERR, INVALID_ARGS, QUANT_ERR, UNSUPPORTED, UNALIGN = 0, -11, -20, -701, -1000, -2000
 NONE = 0x7fffffff                                                              # slot0 of a job the launch does not have
-
-
-class Mat(C.Structure):   # kf::GemmMat
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):
-    _fields_ = [("mode", C.c_int), ("n_w", C.c_int), ("w", Mat * 3)] + [(f, C.c_int) for f in ("sparse", "n_hot", "norm", "canon", "q4_perm", "q2_tab", "q1_tab", "xf2")]
-
-
-class Plan(C.Structure):
-    _fields_ = ([(f, C.c_int) for f in ("status", "fmt", "G", "mode", "sparse", "onejob", "canon", "xf", "xf2", "K", "nBlk", "lpr_log2", "iters", "lgroup", "gshift", "njobs")]
-                + [("M", C.c_int * 3), ("slot0", C.c_int * 3)] + [(f, C.c_int) for f in ("spw", "total_slots", "stream_ok", "grid", "lds")])
 
 
 def mat(M, K, type=Q4, quant=GROUP, lgroup=128, gama=1, al=3, awq=0):

@@ -7,6 +7,7 @@ import ctypes as C
 import pytest
 
 from koifish_amd import lib as L
+from plan_structs import GemmMat as Mat, GemvPlan as Plan, GemvProblem as Problem, GemvRowsPlan as RowsPlan, GemvRowsProblem as RowsProblem
 
 BF16, F8, Q4, Q3, T_SIGN, BOOL1 = 3, 4, 14, 15, 17, 19                          # kf_dtype
 GROUP, ROW_LUT = 0, 1
@@ -14,28 +15,6 @@ FMT_BF16, FMT_F8, FMT_Q4, FMT_Q2, FMT_Q1, FMT_Q4P, FMT_Q4R, FMT_Q1T, FMT_Q2T = r
 PLAIN, PAIRED, ARGMAX = range(3)
 OK, INVALID_ARGS, QUANT_ERR, UNSUPPORTED, UNALIGN = 0, -20, -701, -1000, -2000
 LDS_MAX, XF_LDS_MAX, RED = 80 * 1024, 53 * 1024, 256                             # GEMV_ROWS_LDS_MAX, GEMV_ROWS_XF_LDS_MAX, GEMV_RED_BYTES
-
-
-class Mat(C.Structure):   # kf::GemmMat
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):   # kf::GemvProblem
-    _fields_ = [("mode", C.c_int), ("n_w", C.c_int), ("w", Mat * 3)] + [(f, C.c_int) for f in ("sparse", "n_hot", "norm", "canon", "q4_perm", "q2_tab", "q1_tab", "xf2")]
-
-
-class Plan(C.Structure):   # kf::GemvPlan
-    _fields_ = ([(f, C.c_int) for f in ("status", "fmt", "G", "mode", "sparse", "onejob", "canon", "xf", "xf2", "K", "nBlk", "lpr_log2", "iters", "lgroup", "gshift", "njobs")]
-                + [("M", C.c_int * 3), ("slot0", C.c_int * 3)] + [(f, C.c_int) for f in ("spw", "total_slots", "stream_ok", "grid", "lds")])
-
-
-class RowsProblem(C.Structure):   # kf::GemvRowsProblem
-    _fields_ = [("one", Problem), ("n_rows", C.c_int)]
-
-
-class RowsPlan(C.Structure):   # kf::GemvRowsPlan
-    _fields_ = ([(f, C.c_int) for f in ("status", "shared", "fmt", "mode", "xf", "NR", "K", "nBlk", "lpr_log2", "iters", "lgroup", "gshift", "norm_regs", "njobs")]
-                + [("M", C.c_int * 3), ("slot0", C.c_int * 3)] + [(f, C.c_int) for f in ("spw", "total_slots", "n_panels", "panel_rows", "grid", "lds")])
 
 
 def mat(M, K, type=Q4, quant=GROUP, lgroup=128, gama=1, al=3, awq=0):

@@ -7,6 +7,7 @@ import pytest
 
 from koifish_amd import lib as L
 from koifish_amd.runtime import perplexity_from_logprobs
+from plan_structs import GemmMat as Mat, ScorePlan as Plan, ScoreProblem as Problem
 
 BF16, Q4 = 3, 14                 # kf_dtype
 GROUP, ROW_LUT = 0, 1            # quant forms
@@ -15,18 +16,6 @@ BIG, SMALL = 0, 1                # G3 forms
 V = 151936
 QWEN3_DIMS = (1024, 2048, 2560, 4096, 5120)
 ROWS = (1, 7, 128, 2047, 8192)
-
-
-class Mat(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("type", "quant", "awq", "M", "K", "lgroup", "gama", "al")]
-
-
-class Problem(C.Structure):
-    _fields_ = [("w", Mat), ("n", C.c_int), ("x_al", C.c_int), ("force", C.c_int), ("form", C.c_int)]
-
-
-class Plan(C.Structure):
-    _fields_ = [(f, C.c_int) for f in ("route", "status", "form", "n_vt", "n_rb", "gx", "block", "lds", "panel_rows")] + [("scratch", C.c_longlong)]
 
 
 @pytest.fixture(scope="module")
