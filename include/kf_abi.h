@@ -825,7 +825,7 @@ typedef struct kf_engine_statistics {
     int32_t tuned;     /* 1: measured by kf_engine_tune on this device, 0: the built-in defaults */
 } kf_engine_statistics;
 int kf_engine_stats(kf_ctx* ctx, kf_engine* e, int pos_bound, kf_engine_statistics* out);
-int kf_engine_check(kf_ctx* ctx, kf_engine* e); /* synchronises; KF_INTERNAL_ERR when a hand-off poll has timed out since creation or the last kf_engine_reset */
+int kf_engine_check(kf_ctx* ctx, kf_engine* e); /* synchronises; KF_INTERNAL_ERR when a hand-off poll has timed out since creation or the last kf_engine_reset, or (error word bit 128, canonical order) an attention score left the engine's fixed-exponent range: |round(s log2 e)| > 448 -- the per-layer launches serve such a model */
 /* After KF_INTERNAL_ERR from kf_engine_check: the error word latches and every later launch of the engine returns at once without output.  kf_engine_reset
  * synchronises, puts the hand-off state back to its initial one and clears the word; the steps since the failure have to be redone. */
 int kf_engine_reset(kf_ctx* ctx, kf_engine* e);

@@ -1863,6 +1863,8 @@ int kf_engine_check(kf_ctx* c, kf_engine* e) {
     ENG_ENTER(c, e && e->h, "engine");
     int err = 0;
     ENG_HIP(kf::engine_error_word(e->h, c->stream, &err));
+    if (err & 128) /* kf_attn_common.h, KF_CANON_FIX_LIM: an arithmetic flag of the canonical attention, no hand-off failed */
+        return fail(KF_INTERNAL_ERR, "kf_engine: attention scores outside the engine's fixed-exponent range (error word 0x%x): the per-layer launches serve such a model (set_engine(False))", err);
     if (err) return fail(KF_INTERNAL_ERR, "kf_engine: a hand-off poll timed out (error word 0x%x): the launch was not fully resident", err);
     return KF_OK;
 }

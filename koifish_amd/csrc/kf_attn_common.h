@@ -2,6 +2,8 @@
 // per-head q/k RMSNorm + rotate-half RoPE (ROPE::cuInfer, rope.cu:645-672), the hardware-exp2 softmax exponent, sc1 accessors; the decode slice shell (AttnSlice: grid
 // decode, lane geometry and slice ends of the three decode kernels), the canonical order's batch, publish and merge, the int8 cache's row quantiser.
 #pragma once
+#include <type_traits>
+
 #include "kf_kernels.h"
 
 namespace kf {
@@ -101,7 +103,19 @@ struct AttnSlice {
 //   weight  p = f * 2^(n - m), (f, n) = kf_exp2_parts(s * log2 e); m = ANY integer >= every n it is compared with: a power of two rescales exactly, so every
 //           lane / wave / slice works against a maximum of its own and the partial sums are rescaled when they meet;
 //   sums    fp64 (every term p and p * v is exact in fp64: the sums do not depend on their order to far below an fp32 ulp), out = bf16((float)(O / L)).
+// The fixed reference exponent (canon_batch_fixed; the persistent engine's canonical forms): m = 0 for every lane, wave and slice, p = f * 2^n, and every partial sum at
+// every level is a plain addend -- no maximum is formed or exchanged, nothing is rescaled.  The result is the one above bit for bit while |n| <= KF_CANON_FIX_LIM for
+// every valid key: an fp64 addition, fma and division commute with a common power-of-two factor as long as no operand or result leaves the range where fp64 holds it
+// exactly as the scaled twin, so the sums against m = 0 are the sums against m = max n times 2^(max n) at every step, and O / L is the same quotient.  The range:
+//   f lies in [2^-1/2, 2^1/2] with 24 significant bits (lowest bit >= 2^-24), v is bf16 (lowest bit of the smallest subnormal 2^-133, |v| < 2^128);
+//   the definition's own terms: n - m >= -2 LIM, the lowest bit of f * 2^(n - m) * v is >= 2^(-24 - 2 LIM - 133): a multiple of fp64's quantum 2^-1074 -- so exact,
+//     and every sum of such terms exact or rounded as its scaled twin -- while 2 LIM <= 917, LIM <= 458.  THIS bounds the limit: beyond it the definition itself (the
+//     oracle, the per-layer kernels) would round a tail term in the subnormal range and the two forms could part;
+//   the fixed form's terms: lowest bit >= 2^(-157 - LIM) (LIM <= 917), the largest sum < 2^11 keys * 2^(1/2 + LIM) * 2^128 < 2^1024 (LIM <= 884): both far inside.
+// LIM = 448 = 7 * 64, the multiple of 64 below 458: scores up to |s| = 448 / log2 e = 310, where an fp32 softmax has long overflowed.  A lane that meets a valid key
+// outside the range sets a sticky flag (NaN-safe: !(|n| <= LIM)); what becomes of the flag is the caller's (the engine latches bit 128 of its error word).
 constexpr float KF_LOG2E = 1.44269502162933349609375f;
+constexpr float KF_CANON_FIX_LIM = 448.0f;
 __device__ __forceinline__ float canon_score(const float (&q)[8], u32x4 kw, int lpk_log2, float rden) {
     const uint32_t k4[4] = {kw.x, kw.y, kw.z, kw.w};
     float d = 0.f;
@@ -301,9 +315,53 @@ __device__ __forceinline__ void canon_batch(CanonAcc<GQ>& A, const float (&qf)[G
         }
     }
 }
+// ---- the same batch against the fixed reference exponent m = 0 (the rule and its range: the comment block above canon_score): no batch maximum, no cross-lane
+// exchange between the exponentials and the P.V chains, no rescale, p = f * 2^n; `oob`: this lane has met a valid key with |n| > KF_CANON_FIX_LIM (sticky)
+template <int GQ>
+struct CanonAccFixed {
+    double o[GQ][8], l[GQ];
+    bool oob;
+    __device__ __forceinline__ void init() {
+        oob = false;
+#pragma unroll
+        for (int hq = 0; hq < GQ; hq++) {
+            l[hq] = 0.0;
+#pragma unroll
+            for (int i = 0; i < 8; i++) o[hq][i] = 0.0;
+        }
+    }
+};
+template <int GQ, int LPK, int U = ATTN_U>
+__device__ __forceinline__ void canon_batch_fixed(CanonAccFixed<GQ>& A, const float (&qf)[GQ][8], const u32x4 (&kk)[U], const u32x4 (&vv)[U], const bool (&valid)[U], int lpk_log2, float rden) {
+    float f[U][GQ], n[U][GQ];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+#pragma unroll
+        for (int hq = 0; hq < GQ; hq++) {
+            const float s = canon_score(qf[hq], kk[u], lpk_log2, rden);
+            kf_exp2_parts(s * KF_LOG2E, f[u][hq], n[u][hq]);
+            A.oob |= valid[u] && !(fabsf(n[u][hq]) <= KF_CANON_FIX_LIM);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t vw[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+        double vd[8];
+#pragma unroll
+        for (int i = 0; i < 4; i++) vd[2 * i] = (double)bf_lo(vw[i]), vd[2 * i + 1] = (double)bf_hi(vw[i]);
+#pragma unroll
+        for (int hq = 0; hq < GQ; hq++) {
+            const double p = valid[u] ? ldexp_d((double)f[u][hq], (int)n[u][hq]) : 0.0;
+            A.l[hq] += p;
+#pragma unroll
+            for (int i = 0; i < 8; i++) A.o[hq][i] = fma(p, vd[i], A.o[hq][i]);
+        }
+    }
+}
 // sums over the wave's key groups, left in LDS: c[d] for d < hd, c[hd] = l, c[hd + 1] = m (as a double); c = this wave's [hq] row of hd + 2 doubles
-template <int GQ, int LPK>
-__device__ __forceinline__ void canon_wave_to_lds(const CanonAcc<GQ>& A, double* comb_wave /* [GQ][hd + 2] */, int hd, int lane, int d0) {
+// (CanonAccFixed: the same rows without an exponent -- c[hd + 1] is not written)
+template <int GQ, int LPK, class Acc>
+__device__ __forceinline__ void canon_wave_to_lds(const Acc& A, double* comb_wave /* [GQ][hd + 2] */, int hd, int lane, int d0) {
     const int row = lane >> 4;
 #pragma unroll
     for (int hq = 0; hq < GQ; hq++) {
@@ -319,7 +377,11 @@ __device__ __forceinline__ void canon_wave_to_lds(const CanonAcc<GQ>& A, double*
         if (LPK < 16) lt += dpp_d<0x128>(lt);
         double* c = comb_wave + (size_t)hq * (hd + 2);
         if (LPK == 16 || (lane & 8) == 0) c[d0 + 2 * row] = r2[0], c[d0 + 2 * row + 1] = r2[1];
-        if (lane == 0) c[hd] = lt, c[hd + 1] = (double)A.m[hq];
+        if constexpr (std::is_same_v<Acc, CanonAccFixed<GQ>>) {
+            if (lane == 0) c[hd] = lt;
+        } else {
+            if (lane == 0) c[hd] = lt, c[hd + 1] = (double)A.m[hq];
+        }
     }
 }
 

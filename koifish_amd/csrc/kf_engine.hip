@@ -389,7 +389,8 @@ struct EngCfg {
     static constexpr int lq_stride = eng_lq_stride(GQ_, HD_), lp_stride = eng_lp_stride(GQ_, HD_);
     // slice merge: every workgroup merges ME consecutive elements of one head (ME = the power of two >= q_dim / NWG).  A head's slice partials (fp64 sums of the
     // canonical softmax, kf_attn_common.h) lie as [hd / ME element groups][KF_ATTN_MAX_SPLITS slices][ME] values, a value = two 8-byte {32 bits, generation}
-    // granules (low word, high word), then [KF_ATTN_MAX_SPLITS][4] granules {m, L low, L high, unused}: what a workgroup merges is contiguous
+    // granules (low word, high word), then [KF_ATTN_MAX_SPLITS][4] granules {m, L low, L high, unused} (canonical order, whose exponent is fixed: {L low, L high,
+    // unused, unused} -- one 16-byte value, the strides kept): what a workgroup merges is contiguous
     static constexpr int ME = pow2_ceil((QD_ + NWG_ - 1) / NWG_), PSH = KF_ATTN_MAX_SPLITS * (2 * HD_ + 4), NLM = (KF_ATTN_MAX_SPLITS * ME * 2 + 127) / 128;
     static_assert(ME <= 64 && ME <= HD_, "merge elements per workgroup");
 };
@@ -401,7 +402,7 @@ __device__ __forceinline__ unsigned long long* eng_lpart(const EngArgs& a, int x
 }
 
 // ---- P2 for one wave: q/k-norm + RoPE + the canonical attention over this workgroup's slice, run by ALL 8 waves of the workgroup (the poller too: it has nothing
-// to wait for between the staging of the raw heads and the slice partials).  The canonical softmax sums in fp64 against per-wave exponents (kf_attn_common.h), so
+// to wait for between the staging of the raw heads and the slice partials).  The canonical softmax sums in fp64 against one fixed exponent (kf_attn_common.h), so
 // how the keys are dealt to waves and lanes does not show in the result: wave w takes the keys t0 + w * KPW + group + 8 * KPW * u.
 template <class C>
 struct EngAttnState { /* the wave's K / V tiles of the slice, requested a layer ahead */
@@ -488,8 +489,9 @@ __device__ __forceinline__ void eng_attn_phase(const EngArgs& a, const EngLds& L
             }
         }
         // the slice's sums: canonical (fp64 sums of exact weights: bit-exact against the oracle) when the mat-vec phases are, else the decode kernel's default arithmetic
-        // (v_dot2c scores, v_exp_f32, fp32 sums); both keep integer reference exponents, so the combine below and the merge treat them alike
-        using Acc = std::conditional_t<C::CANON, CanonAcc<GQ>, FastAcc<GQ>>;
+        // (v_dot2c scores, v_exp_f32, fp32 sums).  The canonical sums stand against the FIXED reference exponent 0 (canon_batch_fixed, kf_attn_common.h): the waves', the
+        // slices' and the merge's partials are plain addends; the fp32 sums keep a running integer exponent per wave, which the combine below and the merge rescale by
+        using Acc = std::conditional_t<C::CANON, CanonAccFixed<GQ>, FastAcc<GQ>>;
         using Sum = std::conditional_t<C::CANON, double, float>;
         Acc A;
         A.init();
@@ -516,8 +518,11 @@ __device__ __forceinline__ void eng_attn_phase(const EngArgs& a, const EngLds& L
                 if (valid[u] && t == pos) ck[u] = *reinterpret_cast<const u32x4*>(L.knew + d0), cv[u] = *reinterpret_cast<const u32x4*>(L.vraw + d0);
             }
             if (b + 1 < nbatch) eng_attn_issue<C>(a, ly, S, wave, lane, T, b + 1);
-            if constexpr (C::CANON) canon_batch<GQ, LPK, U>(A, qf, ck, cv, valid, lpk_log2, rden);
+            if constexpr (C::CANON) canon_batch_fixed<GQ, LPK, U>(A, qf, ck, cv, valid, lpk_log2, rden);
             else fast_batch<GQ, LPK, U>(A, qp, ck, cv, valid, lpk_log2, rden);
+        }
+        if constexpr (C::CANON) { /* a valid key outside the fixed exponent's range: the error word latches (an arithmetic flag: every hand-off of the step still arrives) */
+            if (__builtin_amdgcn_ballot_w64(A.oob) != 0 && lane == 0) atomicOr(a.ws + 1, 128);
         }
         if (wave == 0) ENG_STAMP(1, 12);
         Sum* const comb = reinterpret_cast<Sum*>(L.comb);
@@ -530,19 +535,18 @@ __device__ __forceinline__ void eng_attn_phase(const EngArgs& a, const EngLds& L
         for (int i = tid; i < GQ * hd; i += NWA * 64) { /* (two or four threads per element with DPP joins was measured: slower, 378 vs 370 us per step) */
             const int hq = i >> hd_log2, d = i & (hd - 1);
             float ms = -__builtin_inff();
-#pragma unroll
-            for (int sl = 0; sl < NWA; sl++) ms = fmaxf(ms, (float)comb[((size_t)sl * GQ + hq) * PSD + hd + 1]);
             double o, Ls;
-            if constexpr (C::CANON) {
+            if constexpr (C::CANON) { /* plain sums of the waves' O; their L where it is used (one slice: every thread divides; else the thread that stores it) */
                 o = 0.0, Ls = 0.0;
 #pragma unroll
-                for (int sl = 0; sl < NWA; sl++) {
-                    const double* c = L.comb + ((size_t)sl * GQ + hq) * PSD;
-                    const int e = canon_shift((float)c[hd + 1] - ms);
-                    o += ldexp_d(c[d], e);
-                    Ls += ldexp_d(c[hd], e);
+                for (int sl = 0; sl < NWA; sl++) o += L.comb[((size_t)sl * GQ + hq) * PSD + d];
+                if (nsp == 1 || d == 0) {
+#pragma unroll
+                    for (int sl = 0; sl < NWA; sl++) Ls += L.comb[((size_t)sl * GQ + hq) * PSD + hd];
                 }
             } else {
+#pragma unroll
+                for (int sl = 0; sl < NWA; sl++) ms = fmaxf(ms, (float)comb[((size_t)sl * GQ + hq) * PSD + hd + 1]);
                 float of = 0.f, lf = 0.f;
 #pragma unroll
                 for (int sl = 0; sl < NWA; sl++) {
@@ -562,18 +566,24 @@ __device__ __forceinline__ void eng_attn_phase(const EngArgs& a, const EngLds& L
                 if (XMAP) { /* plain stores into this XCD's partial buffer: a value = two {32 bits, generation} granules */
                     unsigned long long* dst = eng_lpart<C>(a, S.xcc) + (size_t)hq * C::PSH;
                     *reinterpret_cast<ulonglong2*>(dst + oi) = ulonglong2{gg | (ob & 0xffffffffull), gg | (ob >> 32)};
-                    if (d == 0) {
+                    if constexpr (C::CANON) { /* L as one 16-byte {low, high} value; no exponent granule (the strides of the buffer are the fp32 form's) */
+                        if (d == 0) *reinterpret_cast<ulonglong2*>(dst + mi) = ulonglong2{gg | (lb & 0xffffffffull), gg | (lb >> 32)};
+                    } else if (d == 0) {
                         *reinterpret_cast<ulonglong2*>(dst + mi) = ulonglong2{gg | __float_as_uint(ms), gg | (lb & 0xffffffffull)};
                         dst[mi + 2] = gg | (lb >> 32);
                     }
                 } else {
                     unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.xch + C::part) + (size_t)(h0 + hq) * C::PSH;
                     st_gran64(dst + oi, gen, __uint_as_float((uint32_t)ob)), st_gran64(dst + oi + 1, gen, __uint_as_float((uint32_t)(ob >> 32)));
-                    if (d == 0) st_gran64(dst + mi, gen, ms), st_gran64(dst + mi + 1, gen, __uint_as_float((uint32_t)lb)), st_gran64(dst + mi + 2, gen, __uint_as_float((uint32_t)(lb >> 32)));
+                    if constexpr (C::CANON) {
+                        if (d == 0) st_gran64(dst + mi, gen, __uint_as_float((uint32_t)lb)), st_gran64(dst + mi + 1, gen, __uint_as_float((uint32_t)(lb >> 32)));
+                    } else if (d == 0) {
+                        st_gran64(dst + mi, gen, ms), st_gran64(dst + mi + 1, gen, __uint_as_float((uint32_t)lb)), st_gran64(dst + mi + 2, gen, __uint_as_float((uint32_t)(lb >> 32)));
+                    }
                 }
             }
         }
-    } else if (nsp > 1) { /* empty slice: neutral partial (sums 0, exponent -inf) */
+    } else if (nsp > 1) { /* empty slice: neutral partial (sums 0; the fp32 form: exponent -inf) */
         for (int i = tid; i < GQ * hd; i += NWA * 64) {
             const int hq = i >> hd_log2, d = i & (hd - 1);
             constexpr int ME = C::ME, MAXSP = KF_ATTN_MAX_SPLITS;
@@ -582,11 +592,19 @@ __device__ __forceinline__ void eng_attn_phase(const EngArgs& a, const EngLds& L
             if (XMAP) {
                 unsigned long long* dst = eng_lpart<C>(a, S.xcc) + (size_t)hq * C::PSH;
                 dst[oi] = gg, dst[oi + 1] = gg;
-                if (d == 0) dst[mi] = gg | 0xff800000u, dst[mi + 1] = gg, dst[mi + 2] = gg;
+                if constexpr (C::CANON) {
+                    if (d == 0) dst[mi] = gg, dst[mi + 1] = gg;
+                } else if (d == 0) {
+                    dst[mi] = gg | 0xff800000u, dst[mi + 1] = gg, dst[mi + 2] = gg;
+                }
             } else {
                 unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.xch + C::part) + (size_t)(h0 + hq) * C::PSH;
                 st_gran64(dst + oi, gen, 0.f), st_gran64(dst + oi + 1, gen, 0.f);
-                if (d == 0) st_gran64(dst + mi, gen, -__builtin_inff()), st_gran64(dst + mi + 1, gen, 0.f), st_gran64(dst + mi + 2, gen, 0.f);
+                if constexpr (C::CANON) {
+                    if (d == 0) st_gran64(dst + mi, gen, 0.f), st_gran64(dst + mi + 1, gen, 0.f);
+                } else if (d == 0) {
+                    st_gran64(dst + mi, gen, -__builtin_inff()), st_gran64(dst + mi + 1, gen, 0.f), st_gran64(dst + mi + 2, gen, 0.f);
+                }
             }
         }
     }
@@ -729,7 +747,8 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
             const int ln = l + 1 < a.n_layer ? l + 1 : l;
             mv_prefetch<P1, NCW1, FMT, S1>(mat1(ln), mat1(ln), S.s1, PW, lane, S.M1, r1);
         }
-        // P3: merge the slices of this workgroup's output elements: exact rescales to the largest exponent, fp64 sums, one division (kf_attn_common.h)
+        // P3: merge the slices of this workgroup's output elements: fp64 sums (canonical order: plain, against the fixed exponent; else behind exact rescales to the largest
+        // exponent), one division (kf_attn_common.h)
         ENG_STAMP(0, 3);
         if (S.has_merge) {
             constexpr int ME = C::ME, NLM = C::NLM, MAXSP = KF_ATTN_MAX_SPLITS;
@@ -750,10 +769,11 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
 #pragma unroll
                 for (int r = 0; r < NLM; r++) go[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_o, (r * 64 + lane) * 16, 0, 16 /* sc1 */));
                 gm0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ml, (mine ? lane : 0) * 32, 0, 16));
-                gm1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ml, (mine ? lane : 0) * 32 + 16, 0, 16));
+                if constexpr (!C::CANON) gm1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ml, (mine ? lane : 0) * 32 + 16, 0, 16));
 #pragma unroll
                 for (int r = 0; r < NLM; r++) bad |= (r * 64 + lane) < cnt ? ((go[r].y ^ gen) | (go[r].w ^ gen)) : 0u;
-                bad |= mine ? ((gm0.y ^ gen) | (gm0.w ^ gen) | (gm1.y ^ gen)) : 0u;
+                if constexpr (C::CANON) bad |= mine ? ((gm0.y ^ gen) | (gm0.w ^ gen)) : 0u; /* the slice's L: one 16-byte {low, high} value */
+                else bad |= mine ? ((gm0.y ^ gen) | (gm0.w ^ gen) | (gm1.y ^ gen)) : 0u;
                 if (all_good(bad)) break;
                 if (dead || spins > ENG_SPIN_MAX) {
                     if (!dead && lane == 0) atomicOr(a.ws + 1, 4);
@@ -774,29 +794,50 @@ __device__ __forceinline__ void eng_poller_main(const EngArgs& a, const EngLds& 
                     L.msc[e * MAXSP + sp] = vi < cnt ? __builtin_bit_cast(double, ((unsigned long long)go[r].z << 32) | go[r].x) : 0.0;
                 }
             }
-            const float ms = mine ? __uint_as_float(gm0.x) : -__builtin_inff();
-            const double ls = mine ? __builtin_bit_cast(double, ((unsigned long long)gm1.x << 32) | gm0.z) : 0.0;
-            const float Mx = wave_max(ms);
-            const int sh = canon_shift(ms - Mx);
-            const double Lt = wave_sum_f64_fast(ldexp_d(ls, sh));
-            // element e's sum over the slices by FOUR lanes (lane = 4 e + quarter: 8 slices each, then two quad adds): fp64 sums do not depend on their order
-            int* shl = reinterpret_cast<int*>(L.msc + ME * MAXSP + 32); /* the slices' shifts, for lanes that walk other slices than their own */
-            if (lane < MAXSP) shl[lane] = sh;
-            double o = 0.0;
-            {
+            double o, Lt;
+            if constexpr (C::CANON) { /* the fixed reference exponent: every slice's L and O are plain addends (kf_attn_common.h) */
+                const double ls = mine ? __builtin_bit_cast(double, ((unsigned long long)gm0.z << 32) | gm0.x) : 0.0;
+                Lt = wave_sum_f64_fast(ls);
+                // element e's sum over the slices by FOUR lanes (lane = 4 e + quarter: 8 slices each, then two quad adds): fp64 sums do not depend on their order
+                o = 0.0;
                 constexpr int QS = MAXSP / 4;
                 const int e = (4 * ME <= 64) ? (lane >> 2) : lane, qq = (4 * ME <= 64) ? (lane & 3) : 0;
                 const bool on = e < ME;
                 const double* mv = L.msc + (on ? e : 0) * MAXSP + qq * QS;
-                const int* sv = shl + qq * QS;
                 if (4 * ME <= 64) {
 #pragma unroll
-                    for (int k = 0; k < QS; k++) o += ldexp_d(mv[k], sv[k]);
+                    for (int k = 0; k < QS; k++) o += mv[k];
                     o += dpp_d<0xB1>(o); /* quad_perm xor 1 */
                     o += dpp_d<0x4E>(o); /* quad_perm xor 2 */
                 } else {
 #pragma unroll
-                    for (int k = 0; k < MAXSP; k++) o += ldexp_d(mv[k], shl[k]);
+                    for (int k = 0; k < MAXSP; k++) o += mv[k];
+                }
+            } else { /* the fp32 sums' integer exponents: exact rescales to the largest */
+                const float ms = mine ? __uint_as_float(gm0.x) : -__builtin_inff();
+                const double ls = mine ? __builtin_bit_cast(double, ((unsigned long long)gm1.x << 32) | gm0.z) : 0.0;
+                const float Mx = wave_max(ms);
+                const int sh = canon_shift(ms - Mx);
+                Lt = wave_sum_f64_fast(ldexp_d(ls, sh));
+                // element e's sum over the slices by FOUR lanes (lane = 4 e + quarter: 8 slices each, then two quad adds): fp64 sums do not depend on their order
+                int* shl = reinterpret_cast<int*>(L.msc + ME * MAXSP + 32); /* the slices' shifts, for lanes that walk other slices than their own */
+                if (lane < MAXSP) shl[lane] = sh;
+                o = 0.0;
+                {
+                    constexpr int QS = MAXSP / 4;
+                    const int e = (4 * ME <= 64) ? (lane >> 2) : lane, qq = (4 * ME <= 64) ? (lane & 3) : 0;
+                    const bool on = e < ME;
+                    const double* mv = L.msc + (on ? e : 0) * MAXSP + qq * QS;
+                    const int* sv = shl + qq * QS;
+                    if (4 * ME <= 64) {
+#pragma unroll
+                        for (int k = 0; k < QS; k++) o += ldexp_d(mv[k], sv[k]);
+                        o += dpp_d<0xB1>(o); /* quad_perm xor 1 */
+                        o += dpp_d<0x4E>(o); /* quad_perm xor 2 */
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < MAXSP; k++) o += ldexp_d(mv[k], shl[k]);
+                    }
                 }
             }
             const uint32_t gr = (tag << 16) | (uint32_t)f2bf((float)(o / Lt));
