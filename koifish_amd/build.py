@@ -15,7 +15,7 @@ HOST = os.path.join(HERE, "host")
 HIP_SOURCES = ["kf_gemv.hip", "kf_gemv_canon.hip", "kf_gemv_rows.hip", "kf_gemv_a8.hip", "kf_gemm_a8.hip", "kf_gemv_w4a8.hip", "kf_gemm_w4a8.hip", "kf_act_quant.hip", "kf_gemm.hip", "kf_gemm2.hip", "kf_gemm3.hip", "kf_head_score.hip", "kf_head_screen.hip", "kf_attn.hip", "kf_attn_kv8.hip", "kf_engine.hip", "kf_xengine.hip", "kf_xengine_q1.hip", "kf_attn_prefill.hip", "kf_attn_prefill_kv8.hip", "kf_ops.hip", "kf_muon.hip", "kf_gradnorm.hip", "kf_evo.hip", "kf_lut.hip", "kf_loss.hip", "kf_distill.hip", "kf_norm_bwd.hip", "kf_qknorm_rope_bwd.hip", "kf_linear_bwd.hip", "kf_gama_bwd.hip", "kf_lora.hip", "kf_lora_apply.hip", "kf_embed_bwd.hip", "kf_attn_bwd_mfma.hip", "kf_awq.hip", "kf_tp.hip", "kf_abi.hip"]
 HIP_DEPS = ["kf_device.h", "kf_kernels.h", "kf_gemm_common.h", "kf_gemm_plan.h", "kf_gemm3_tile.h", "kf_score_plan.h", "kf_gama_plan.h", "kf_lora_plan.h", "kf_gradnorm_plan.h", "kf_gemv_plan.h", "kf_gemv_rows_plan.h", "kf_a8.h", "kf_attn_plan.h", "kf_attn_docs_plan.h", "kf_gemv_kernel.h", "kf_gemv_blocks.h", "kf_rowq.h", "kf_attn_common.h", "kf_engine_common.h", "kf_engine_host.h", "kf_xengine_kernel.h"]
 HOST_SOURCES = ["kf_host.cpp", "kf_safetensors.cpp", "kf_train.cpp", "kf_train_qwen3.cpp"]
-HOST_DEPS = ["kf_train_common.hpp", "kf_safetensors.hpp", "kf_host.hpp", "kf_host_modes.hpp", "kf_spec.hpp"]
+HOST_DEPS = ["kf_train_common.hpp", "kf_safetensors.hpp", "kf_host.hpp", "kf_devbuf.hpp", "kf_host_modes.hpp", "kf_spec.hpp"]
 LIB_HIP = os.path.join(HERE, "libkf_hip.so")
 LIB_HOST = os.path.join(HERE, "libkf_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -5,6 +5,7 @@
 #include <string.h>
 
 
+#include <atomic>
 #include <mutex>
 #include <math.h>
 #include <stdlib.h>
@@ -179,16 +180,23 @@ int kf_sync(kf_ctx* c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     return KF_OK;
 }
+// blocks handed out by kf_malloc / kf_tp_alloc and not yet given back to kf_free (kfdbg_live_allocations: tests/test_gpu_host_lifetimes.py); nothing on a launch path reads it
+static std::atomic<long long> g_live_allocations{0};
+long long kfdbg_live_allocations(void) { return g_live_allocations.load(); }
 int kf_malloc(kf_ctx* c, size_t bytes, void** out) {
     CHKCTX(c);
     if (!out) return fail(KF_INVALID_ARGS, "kf_malloc: out is null");
     hipError_t e = hipMalloc(out, bytes ? bytes : 16);
     if (e != hipSuccess) return fail(KF_OUTOF_GPUMEMORY, "kf_malloc(%zu): %s", bytes, hipGetErrorString(e));
+    g_live_allocations++;
     return KF_OK;
 }
 int kf_free(kf_ctx* c, void* p) {
     CHKCTX(c);
-    if (p) HIPCHK(hipFree(p));
+    if (p) {
+        HIPCHK(hipFree(p));
+        g_live_allocations--;
+    }
     return KF_OK;
 }
 int kf_memset(kf_ctx* c, void* p, int v, size_t bytes) {
@@ -551,6 +559,7 @@ int kf_tp_alloc(kf_ctx* c, size_t bytes, void** out) {
         return fail(KF_OUTOF_GPUMEMORY, "kf_tp_alloc(%zu): uncached device memory refused (%s); a cached allocation cannot serve as a receive area", bytes, hipGetErrorString(e));
     }
     HIPCHK(hipMemset(*out, 0, bytes));
+    g_live_allocations++;
     return KF_OK;
 }
 int kf_tp_ipc_export(kf_ctx* c, void* p, unsigned char handle[64]) {

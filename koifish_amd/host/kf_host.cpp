@@ -10,9 +10,6 @@
 namespace koifish {
 
 // ------------------------------------------------------------------------------------------------ GTensor
-GTensor::~GTensor() {
-    if (owned && data && ctx) kf_free(ctx, data);
-}
 kf_weight GTensor::desc() const {
     kf_weight w;
     std::memset(&w, 0, sizeof(w));
@@ -29,18 +26,23 @@ kf_weight GTensor::desc() const {
 }
 int GTensor::Alloc(kf_ctx* c, size_t nbytes) {
     ctx = c;
-    KF_TRY(kf_malloc(c, nbytes, &data));
-    owned = true;
-    return KF_OK;
+    const int rc = mem.Alloc(c, nbytes);
+    data = mem; /* the view follows the block: NULL when refused */
+    return rc;
 }
 int GTensor::LoadBlob(kf_ctx* c, const void* h_blob, size_t nbytes) {
     KF_TRY(Alloc(c, nbytes));
     return kf_h2d(c, data, h_blob, nbytes);
 }
+static size_t type_bytes(typNUMBER tp) { /* F32 .. I64 in typNUMBER's order; 0: a packed type behind them, sized by its quant card, not here */
+    static const uint8_t kBytes[] = {4, 8, 2, 2, 1, 1, 1, 1, 2, 2, 4, 4, 8, 8};
+    return (size_t)tp < sizeof(kBytes) ? kBytes[(size_t)tp] : 0;
+}
 hGTensor GT(kf_ctx* c, const std::string& name, typNUMBER tp, int n0, int n1) {
     auto t = std::make_shared<GTensor>();
     t->name = name, t->type = tp, t->ne[0] = n0, t->ne[1] = n1;
-    size_t bytes = (size_t)n0 * n1 * (tp == typNUMBER::F32 || tp == typNUMBER::I32 ? 4 : 2);
+    if (!type_bytes(tp)) return nullptr;
+    const size_t bytes = (size_t)n0 * n1 * type_bytes(tp);
     t->szData = bytes;
     if (t->Alloc(c, bytes) != KF_OK) return nullptr;
     kf_memset(c, t->data, 0, bytes);
@@ -54,18 +56,11 @@ int KVCache::Init(kf_ctx* c, int nl, int ms, int kvd) {
     val = GT(c, "kv.val", typNUMBER::BF16, nl * ms, kvd);
     return (key && val) ? KF_OK : KF_OUTOF_GPUMEMORY;
 }
-static hGTensor gt_bytes(kf_ctx* c, const std::string& name, typNUMBER tp, int n0, int n1, size_t bytes) { /* a zero-filled tensor of a type GT does not size */
-    auto t = std::make_shared<GTensor>();
-    t->name = name, t->type = tp, t->ne[0] = n0, t->ne[1] = n1, t->szData = bytes;
-    if (t->Alloc(c, bytes) != KF_OK) return nullptr;
-    kf_memset(c, t->data, 0, bytes);
-    return t;
-}
 int KVCache::Init8(kf_ctx* c, int nkv) {
     if (k8) return KF_OK;
     n_kv = nkv;
     const int rows = n_layer * max_seq_len;
-    hGTensor a = gt_bytes(c, "kv.k8", typNUMBER::I8, rows, kv_dim, (size_t)rows * kv_dim), b = gt_bytes(c, "kv.v8", typNUMBER::I8, rows, kv_dim, (size_t)rows * kv_dim);
+    hGTensor a = GT(c, "kv.k8", typNUMBER::I8, rows, kv_dim), b = GT(c, "kv.v8", typNUMBER::I8, rows, kv_dim);
     hGTensor sa = GT(c, "kv.ks", typNUMBER::F32, rows, nkv), sb = GT(c, "kv.vs", typNUMBER::F32, rows, nkv);
     hGTensor ta = GT(c, "kv.stage_k", typNUMBER::BF16, max_seq_len, kv_dim), tb = GT(c, "kv.stage_v", typNUMBER::BF16, max_seq_len, kv_dim);
     if (!a || !b || !sa || !sb || !ta || !tb) return KF_OUTOF_GPUMEMORY;
@@ -93,17 +88,31 @@ int CHAT_SAMPLER::Draw(kf_ctx* c, const floatX* logits, int vocab, uint64_t* rng
     return (true_topk ? kf_sample_topk : kf_sample)(c, logits, vocab, top_k, temperature, top_p, rng, nullptr, state, ids, forced, n_ctx);
 }
 
-int SeqBuffers::AllocSeqs(kf_ctx* c, int n, int n_ctx, int tokens_fill) {
-    KF_TRY(kf_malloc(c, (size_t)n * 16, (void**)&d_state));
-    KF_TRY(kf_malloc(c, (size_t)n * n_ctx * 4, (void**)&d_forced));
-    KF_TRY(kf_malloc(c, (size_t)n * n_ctx * 4, (void**)&d_tokens_out));
-    KF_TRY(kf_memset(c, d_state, 0, (size_t)n * 16));
-    KF_TRY(kf_memset(c, d_forced, 0xff, (size_t)n * n_ctx * 4));
-    return kf_memset(c, d_tokens_out, tokens_fill, (size_t)n * n_ctx * 4);
+// ---- the sets.  A set commits whole or not at all: its Alloc fills a FRESH object, moved over the held one only after every allocation succeeded
+template <class Set, class... A>
+static int Commit(Set& held, A&&... a) {
+    Set fresh;
+    KF_TRY(fresh.Alloc(a...));
+    held = std::move(fresh);
+    return KF_OK;
 }
-void SeqBuffers::FreeSeqs(kf_ctx* c) {
-    kf_free(c, d_state), kf_free(c, d_forced), kf_free(c, d_tokens_out);
-    d_state = d_forced = d_tokens_out = nullptr;
+int TokenBatch::Alloc(kf_ctx* c, int n, int dim, int q_dim, int ffn) {
+    bX = GT(c, "bX", typNUMBER::BF16, dim, n), bNorm = GT(c, "bNorm", typNUMBER::BF16, dim, n);
+    bQ = GT(c, "bQ", typNUMBER::BF16, q_dim, n), bAttn = GT(c, "bAttn", typNUMBER::BF16, q_dim, n);
+    bGate = GT(c, "bGate", typNUMBER::BF16, ffn, n), bUp = GT(c, "bUp", typNUMBER::BF16, ffn, n);
+    if (!bX || !bNorm || !bQ || !bAttn || !bGate || !bUp) return KF_OUTOF_GPUMEMORY;
+    KF_TRY(d_ptok.Alloc(c, (size_t)n * 4));
+    rows = n;
+    return KF_OK;
+}
+int VerifyRows::Alloc(kf_ctx* c, const MODEL_CARD& card, const kf_weight& head) {
+    const int R = KF_SPEC_MAX_K + 1, qd = card.n_head * card.head_dim;
+    vX = GT(c, "vX", typNUMBER::BF16, card.nEmbed, R), vQ = GT(c, "vQ", typNUMBER::BF16, qd, R), vAttn = GT(c, "vAttn", typNUMBER::BF16, qd, R);
+    vGate = GT(c, "vGate", typNUMBER::BF16, card.n_ff, R);
+    v_attn_ws = GT(c, "v_attn_ws", typNUMBER::F32, (int)((kf_attn_rows_scratch_bytes(card.n_head, card.head_dim, R) + 3) / 4)); /* zero-filled once */
+    v_head_ws = GT(c, "v_head_ws", typNUMBER::F32, (int)((kf_head_rows_scratch_bytes(&head) + 3) / 4));
+    if (!vX || !vQ || !vAttn || !vGate || !v_attn_ws || !v_head_ws) return KF_OUTOF_GPUMEMORY;
+    return d_vtok.Alloc(c, (size_t)2 * R * 4);
 }
 
 // ------------------------------------------------------------------------------------------------ neurons
@@ -332,34 +341,11 @@ hGTensor Head4Token::cuInfer_1(hGTensor inp_, int) {
 }
 
 // ------------------------------------------------------------------------------------------------ Fish
+// Only what has an order: graphs and engine before the workspace and head screen they point into; the IPC mappings (no allocations) closed.  The context goes last.
 Fish::~Fish() {
-    for (auto g : graphs) kf_graph_destroy(g);
-    for (auto g : tp.group_graphs)
-        if (g) kf_graph_destroy(g);
-    if (ctx) {
+    DropGraphs(), tp.group_graphs.clear(), engine.reset();
+    if (ctx)
         for (void* p : tp.opened) kf_tp_ipc_close(ctx, p);
-        if (tp.area) kf_free(ctx, tp.area);
-    }
-    if (ctx && lin_scratch) kf_free(ctx, lin_scratch);
-    if (ctx && a8_q) kf_free(ctx, a8_q);
-    if (ctx && a8_step) kf_free(ctx, a8_step);
-    if (ctx && deq_arena) kf_free(ctx, deq_arena);
-    if (engine) kf_engine_destroy(engine);
-    if (ctx && engine_ws) kf_free(ctx, engine_ws);
-    if (ctx && head_screen) kf_free(ctx, head_screen);
-    if (ctx) {
-        if (rope_table) kf_free(ctx, rope_table);
-        FreeSeqs(ctx);
-        if (gBUFF.d_ptok) kf_free(ctx, gBUFF.d_ptok);
-        FreeScore();
-        if (d_rng) kf_free(ctx, d_rng);
-        if (d_vtok) kf_free(ctx, d_vtok);
-    }
-    vX.reset(), vQ.reset(), vAttn.reset(), vGate.reset(), vLogits.reset(), v_attn_ws.reset(), v_head_ws.reset();
-    attn.clear(), ffn.clear();
-    embed = TokenEmbed(), head = Head4Token(), final_norm = LayerNormal();
-    gBUFF = MemBuffer(), cache = KVCache(), x.reset();
-    if (ctx) kf_destroy(ctx);
 }
 
 bool Fish::ShapeServed(const MODEL_CARD& c, std::string& why) {
@@ -403,10 +389,10 @@ int Fish::Build(const MODEL_CARD& card, int device, void* stream) {
     {
         std::vector<float> tab((size_t)card.n_ctx * hd);
         KF_TRY(kf_rope_table_host(tab.data(), card.n_ctx, hd, card.rope_theta));
-        KF_TRY(kf_malloc(ctx, tab.size() * 4, (void**)&rope_table));
+        KF_TRY(rope_table.Alloc(ctx, tab.size() * 4));
         KF_TRY(kf_h2d(ctx, rope_table, tab.data(), tab.size() * 4));
     }
-    KF_TRY(AllocSeqs(ctx, 1, card.n_ctx, 0xff));
+    KF_TRY(Commit<SeqBuffers>(*this, ctx, 1, card.n_ctx, 0xff));
 
     embed.hFish = this, embed.name = "embed_tokens", embed.out = x;
     for (int l = 0; l < card.nLayer; l++) {
@@ -471,15 +457,10 @@ static const char* kf_last_error_hint(int st) {
 // a matrix takes int8 activations unless kf::a8_plan (asked through kf_linear_a8_status: the one served-storage rule) says its storage has no integer form
 static bool a8_type(const kf_weight& w) { return kf_linear_a8_status(&w, 1) != KF_UNSUPPORTED_DATATYPE; }
 int Fish::A8Ready(int rows) {
-    if (a8_q && a8_rows >= rows) return KF_OK;
+    if (a8.q && a8.rows >= rows) return KF_OK;
     KF_TRY(kf_sync(ctx));
-    if (a8_q) kf_free(ctx, a8_q), a8_q = nullptr;
-    if (a8_step) kf_free(ctx, a8_step), a8_step = nullptr;
-    const size_t wide = (size_t)std::max(std::max(config.n_head * config.head_dim, config.nEmbed), config.n_ff);
-    KF_TRY(kf_malloc(ctx, wide * rows, (void**)&a8_q));
-    KF_TRY(kf_malloc(ctx, (size_t)rows * 4, (void**)&a8_step));
-    a8_rows = rows;
-    return KF_OK;
+    a8 = A8Rows(); /* the old rows go first (they can be large): a refusal below leaves the set empty, rows 0 */
+    return Commit(a8, ctx, rows, (size_t)std::max(std::max(config.n_head * config.head_dim, config.nEmbed), config.n_ff));
 }
 // where a matrix goes in a batch of n token rows: 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear (every matrix while both switches are off)
 int Fish::A8Route(const kf_weight& w, int n) const {
@@ -493,7 +474,7 @@ int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim
     for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), route[i] = A8Route(wd[i], n), (route[i] ? any8 : other) = true;
     if (any8) {
         KF_TRY(A8Ready(n));
-        KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8_q, a8_step));
+        KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8.q, a8.step));
     }
     const floatX* xb = x;
     if (other && norm_w) {
@@ -508,7 +489,7 @@ int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim
         if (route[i]) {
             const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
             static constexpr decltype(&kf_linear_a8) entry[2][2] = {{kf_linear_a8, kf_linear_a8_tiles}, {kf_linear_w4a8, kf_linear_w4a8_tiles}}; /* [A8Route - 1][tiles] */
-            KF_TRY(entry[route[i] - 1][tiles](ctx, &wd[i], a8_q, a8_step, y[i], bias, residual, n));
+            KF_TRY(entry[route[i] - 1][tiles](ctx, &wd[i], a8.q, a8.step, y[i], bias, residual, n));
             a8_count[tiles ? 0 : 1]++;
         } else
             KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], bias, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
@@ -633,13 +614,12 @@ int Fish::pos_bound() const {
 }
 
 int Fish::GrowScratch(size_t need) {
-    if (need <= lin_scratch_bytes) return KF_OK;
+    if (need <= lin_scratch.bytes()) return KF_OK;
     KF_TRY(kf_sync(ctx));
-    void* p = nullptr;
-    KF_TRY(kf_malloc(ctx, need, &p));
+    DevBuf<> p; /* the old block stays the context's scratch until the new one is accepted */
+    KF_TRY(p.Alloc(ctx, need));
     KF_TRY(kf_set_scratch(ctx, p, need));
-    if (lin_scratch) kf_free(ctx, lin_scratch);
-    lin_scratch = p, lin_scratch_bytes = need;
+    lin_scratch = std::move(p);
     return KF_OK;
 }
 
@@ -694,21 +674,20 @@ int Fish::EnsureEngine() {
         if (served != KF_OK) return KF_ENGINE_NOT_SERVED;
     }
     const size_t bytes = kf_engine_workspace_bytes(&d);
-    if (kf_malloc(ctx, bytes, &engine_ws) != KF_OK) return KF_OUTOF_GPUMEMORY;
-    if (kf_engine_create(ctx, &d, engine_ws, bytes, &engine) != KF_OK) {
-        kf_free(ctx, engine_ws);
-        engine_ws = nullptr, engine = nullptr;
-        return KF_ENGINE_NOT_SERVED;
-    }
+    DevBuf<> ws;
+    kf_engine* e = nullptr;
+    if (ws.Alloc(ctx, bytes) != KF_OK) return KF_OUTOF_GPUMEMORY;
+    if (kf_engine_create(ctx, &d, ws, bytes, &e) != KF_OK) return KF_ENGINE_NOT_SERVED;
+    engine.reset(e), engine_ws = std::move(ws);
     engine_state = 1;
     // a bf16 embedding table is read inside the launch (graph-mode steps): one launch less per token; other storages keep kf_embed_state
     kf_weight we = embed.w->desc();
-    engine_embed = kf_engine_set_embedding(ctx, engine, &we, d_forced) == KF_OK;
+    engine_embed = kf_engine_set_embedding(ctx, engine.get(), &we, d_forced) == KF_OK;
     // final norm + bf16 LM head + greedy pick as trailing phases of the same launch (other head storages keep kf_norm_lm_head)
     engine_head = false;
     if (head.proj.w && final_norm.w && head.preLogits && final_norm.rms_eps == config.rms_eps) {
         kf_weight wh = head.proj.w->desc();
-        engine_head = kf_engine_set_head(ctx, engine, &wh, ToX(final_norm.w), ToX(head.preLogits), d_tokens_out) == KF_OK;
+        engine_head = kf_engine_set_head(ctx, engine.get(), &wh, ToX(final_norm.w), ToX(head.preLogits), d_tokens_out) == KF_OK;
     }
     return KF_OK;
 }
@@ -718,33 +697,27 @@ void Fish::EnsureHeadScreen() {
     head_screen_tried = true;
     const kf_weight wh = head.proj.w->desc();
     const size_t bytes = kf_engine_head_screen_bytes(wh.ne0, wh.ne1);
-    if (bytes == 0 || bytes + deq_arena_bytes > resident_max_bytes) return;
-    void* p = nullptr;
-    if (kf_malloc(ctx, bytes, &p) != KF_OK) return;
-    if (kf_engine_set_head_screen(ctx, engine, p, bytes) != KF_OK) {
-        kf_free(ctx, p);
-        return;
-    }
-    head_screen = p, head_screen_bytes = bytes;
+    if (bytes == 0 || bytes + deq_arena.bytes() > resident_max_bytes) return;
+    DevBuf<> p;
+    if (p.Alloc(ctx, bytes) != KF_OK || kf_engine_set_head_screen(ctx, engine.get(), p, bytes) != KF_OK) return;
+    head_screen = std::move(p);
 }
 void Fish::DropHeadScreen() {
     if (head_screen) {
         kf_sync(ctx);
-        if (engine) kf_engine_set_head_screen(ctx, engine, nullptr, 0);
-        kf_free(ctx, head_screen), head_screen = nullptr, head_screen_bytes = 0;
+        if (engine) kf_engine_set_head_screen(ctx, engine.get(), nullptr, 0);
+        head_screen.Free();
     }
     head_screen_tried = false;
 }
 void Fish::DropEngineTable() {
-    for (auto& g : graphs)
-        if (g) kf_graph_destroy(g), g = nullptr;
+    DropGraphs();
     DropHeadScreen();
     if (engine) {
-        kf_sync(ctx);
-        kf_engine_destroy(engine);
-        engine = nullptr;
+        kf_sync(ctx); /* the deleter does not: a launch may still be running */
+        engine.reset();
     }
-    if (engine_ws) kf_free(ctx, engine_ws), engine_ws = nullptr;
+    engine_ws.Free();
     engine_state = 0, engine_embed = engine_head = false;
 }
 void Fish::DropEngine() {
@@ -757,7 +730,7 @@ void Fish::DropResident() {
     if (deq_arena) {
         kf_sync(ctx);
         kf_set_dequant_arena(ctx, nullptr, 0);
-        kf_free(ctx, deq_arena), deq_arena = nullptr, deq_arena_bytes = 0;
+        deq_arena.Free();
     }
     resident_tried = false;
 }
@@ -774,21 +747,20 @@ int Fish::EnsureResident(int PC) {
             const kf_weight d = s->w->desc();
             if (d.type != KF_BF16 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
         }
-    if (total == 0 || total + head_screen_bytes > resident_max_bytes) return KF_OK;
+    if (total == 0 || total + head_screen.bytes() > resident_max_bytes) return KF_OK;
     KF_TRY(kf_sync(ctx));
-    void* p = nullptr;
-    if (kf_malloc(ctx, total, &p) != KF_OK) return KF_OK; /* no room: not an error, the scratch route serves */
-    deq_arena = p, deq_arena_bytes = total;
+    DevBuf<> p;
+    if (p.Alloc(ctx, total) != KF_OK) return KF_OK; /* no room: not an error, the scratch route serves */
     KF_TRY(kf_set_dequant_arena(ctx, p, total));
+    deq_arena = std::move(p);
     return GrowScratch(kf_resident_scratch_bytes()); /* the scratch holds no dequantised copy any more: it lends the small tile kernels their split-K slots */
 }
 int Fish::EngineCheck() {
     if (!engine || engine_steps == 0) return KF_OK;
-    const int rc = kf_engine_check(ctx, engine);
+    const int rc = kf_engine_check(ctx, engine.get());
     if (rc == KF_INTERNAL_ERR) { /* the word latches: every launch since the failure was a no-op.  Report it once, start over from a clean hand-off state */
-        for (auto& g : graphs)
-            if (g) kf_graph_destroy(g), g = nullptr;
-        kf_engine_reset(ctx, engine);
+        DropGraphs();
+        kf_engine_reset(ctx, engine.get());
     }
     return rc;
 }
@@ -802,11 +774,11 @@ int Fish::TPInit(int rank, int world, int vocab_row0) {
     tp.comm.rank = rank, tp.comm.world = world, tp.comm.n_max = config.nEmbed, tp.comm.per_step = 2u * (uint32_t)config.nLayer + 1u;
     const size_t bytes = kf_tp_recv_bytes(world, config.nEmbed);
     const size_t pbytes = kf_tp_push_bytes(tp.comm.per_step);
-    KF_TRY(kf_tp_alloc(ctx, bytes + 64 + pbytes, &tp.area)); /* + the generation and error words and the push descriptors behind the area */
-    tp.comm.d_push = reinterpret_cast<uint8_t*>(tp.area) + bytes + 64;
+    KF_TRY(tp.area.AllocUncached(ctx, bytes + 64 + pbytes)); /* + the generation and error words and the push descriptors behind the area */
+    tp.comm.d_push = tp.area + bytes + 64;
     tp.comm.recv = tp.area, tp.comm.peer[rank] = tp.area;
-    tp.comm.d_step = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(tp.area) + bytes);
-    tp.comm.d_err = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(tp.area) + bytes + 32);
+    tp.comm.d_step = reinterpret_cast<uint32_t*>(tp.area + bytes);
+    tp.comm.d_err = reinterpret_cast<int32_t*>(tp.area + bytes + 32);
     use_engine = false; /* the persistent engine serves whole layers of one GPU */
     return KF_OK;
 }
@@ -892,7 +864,7 @@ int Fish::EnqueueStep(int bound) {
     if (EagerOnly() && engine_state == 0) EnsureEngine(); /* records why the engine is not used: engine_state < 0 below */
     if (use_engine && fuse_level >= 1 && engine_state > 0 && engine_embed && (graph_mode || state_tokens)) { /* embedding row read inside the launch */
         if (engine_head) { /* ... and the final norm, the LM head and the greedy pick: ONE launch per token */
-            const int rc = kf_engine_step_head(ctx, engine, nullptr, ToX(x), d_state, bound, samp_params.greedy() ? 1 : 0);
+            const int rc = kf_engine_step_head(ctx, engine.get(), nullptr, ToX(x), d_state, bound, samp_params.greedy() ? 1 : 0);
             if (rc < 0) return rc;
             if (rc == KF_OK) {
                 engine_steps++;
@@ -900,7 +872,7 @@ int Fish::EnqueueStep(int bound) {
                 return samp_params.Draw(ctx, ToX(head.preLogits), config.vocab, d_rng, d_state, d_tokens_out, d_forced, config.n_ctx);
             }
         } else {
-            const int rc = kf_engine_step(ctx, engine, nullptr, ToX(x), d_state, bound);
+            const int rc = kf_engine_step(ctx, engine.get(), nullptr, ToX(x), d_state, bound);
             if (rc < 0) return rc;
             if (rc == KF_OK) {
                 engine_steps++;
@@ -911,7 +883,7 @@ int Fish::EnqueueStep(int bound) {
     hGTensor cur = embed.cuInfer(-1);
     if (!cur) return KF_INTERNAL_ERR;
     if (use_engine && fuse_level >= 1 && engine_state > 0 && !(engine_embed && (graph_mode || state_tokens))) {
-        const int rc = kf_engine_step(ctx, engine, ToX(cur), ToX(x), d_state, bound);
+        const int rc = kf_engine_step(ctx, engine.get(), ToX(cur), ToX(x), d_state, bound);
         if (rc < 0) return rc;
         if (rc == KF_OK) {
             engine_steps++;
@@ -931,25 +903,32 @@ int Fish::ForwardOnRLS(int token, int pos) {
 
 int Fish::SetState(int token, int pos) { return kf_set_state(ctx, d_state, token, pos); }
 
+// one launch sequence captured into `out`: `enqueue` runs between kf_graph_begin and kf_graph_end; the first refusal's code back, and then no graph is kept
+template <class F>
+static int Capture(kf_ctx* c, hGraph& out, F enqueue) {
+    KF_TRY(kf_graph_begin(c));
+    int rc = enqueue();
+    kf_graph* g = nullptr;
+    const int rc2 = kf_graph_end(c, &g);
+    hGraph captured(g);
+    if (rc == KF_OK && (rc = rc2) == KF_OK) out = std::move(captured);
+    return rc;
+}
 kf_graph* Fish::GraphFor(int pos) {
     const int b = bucket_of(pos);
-    if ((int)graphs.size() <= b) graphs.resize(b + 1, nullptr), graph_bound.resize(b + 1, 0);
+    if ((int)graphs.size() <= b) graphs.resize(b + 1);
     if (!graphs[b]) {
         if (use_engine && engine_state == 0) EnsureEngine(); /* not while capturing */
         tok_pos = pos;
         graph_mode = true;
         const int save = fuse_level;
         fuse_level = 1;
-        if (kf_graph_begin(ctx) != KF_OK) return nullptr;
-        int rc = EnqueueStep(pos_bound());
-        kf_graph* g = nullptr;
-        int rc2 = kf_graph_end(ctx, &g);
+        const int rc = Capture(ctx, graphs[b], [&] { return EnqueueStep(pos_bound()); });
         fuse_level = save;
         graph_mode = false;
-        if (rc != KF_OK || rc2 != KF_OK) return nullptr;
-        graphs[b] = g, graph_bound[b] = pos_bound();
+        if (rc != KF_OK) return nullptr;
     }
-    return graphs[b];
+    return graphs[b].get();
 }
 
 // A step that is ONE kernel launch (the engine with the embedding row, the LM head and the greedy pick inside) gains nothing from a captured graph: replaying a
@@ -976,15 +955,15 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
                 if (bucket_tuned.empty()) bucket_tuned.assign((size_t)bucket_of(config.n_ctx - 1) + 1, 0);
                 if (!bucket_tuned[b]) {
                     bucket_tuned[b] = 1;
-                    const int trc = kf_engine_tune(ctx, engine, ToX(x), d_state, pos_bound(), engine_autotune, nullptr, nullptr);
+                    const int trc = kf_engine_tune(ctx, engine.get(), ToX(x), d_state, pos_bound(), engine_autotune, nullptr, nullptr);
                     if (trc < 0) { /* a tuning problem (a poll timed out while a delay was being tried) is not a decode error: the built-in delays stay (kf_engine_tune restored
                                       them), the latched error word is cleared, and the step below runs */
-                        if (kf_engine_reset(ctx, engine) != KF_OK) return trc;
+                        if (kf_engine_reset(ctx, engine.get()) != KF_OK) return trc;
                         engine_autotune = 0;
                     }
                 }
             }
-            const int rc = kf_engine_steps_head(ctx, engine, ToX(x), d_state, pos_bound(), m);
+            const int rc = kf_engine_steps_head(ctx, engine.get(), ToX(x), d_state, pos_bound(), m);
             if (rc < 0) return rc;
             if (rc != KF_OK) break; /* not served at this position: the per-step path below takes the rest */
             engine_steps += m;
@@ -1053,26 +1032,14 @@ int Fish::FlowEnd(int last, int token, int pos) {
     return HeadAndPick(ToX(x));
 }
 
-void Fish::FreeScore() {
-    if (gBUFF.d_stgt) kf_free(ctx, gBUFF.d_stgt), gBUFF.d_stgt = nullptr;
-    if (gBUFF.d_slp) kf_free(ctx, gBUFF.d_slp), gBUFF.d_slp = nullptr;
-    if (gBUFF.d_stop1) kf_free(ctx, gBUFF.d_stop1), gBUFF.d_stop1 = nullptr;
-    if (gBUFF.score_ws) kf_free(ctx, gBUFF.score_ws), gBUFF.score_ws = nullptr;
-    gBUFF.score_rows = 0;
-}
 int Fish::ScoreReady() {
     KF_TRY(PrefillReady());
     const int R = gBUFF.rows;
     if (gBUFF.score_rows >= R) return KF_OK;
     KF_TRY(kf_sync(ctx));
-    FreeScore();
+    static_cast<ScoreBuffers&>(gBUFF) = ScoreBuffers(); /* the old set goes first, as it always did */
     kf_weight wh = head.proj.w->desc();
-    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_stgt));
-    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_slp));
-    KF_TRY(kf_malloc(ctx, (size_t)R * 4, (void**)&gBUFF.d_stop1));
-    KF_TRY(kf_malloc(ctx, kf_head_logprob_scratch_bytes(&wh, R), &gBUFF.score_ws));
-    gBUFF.score_rows = R;
-    return KF_OK;
+    return Commit<ScoreBuffers>(gBUFF, ctx, R, kf_head_logprob_scratch_bytes(&wh, R));
 }
 
 int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) {
@@ -1094,7 +1061,7 @@ int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top
         for (int i = 0; i < m; i++) tgt[i] = i < ns ? tokens[c0 + i + 1] : -1;
         KF_TRY(kf_h2d(ctx, gBUFF.d_stgt, tgt.data(), (size_t)m * 4));
         KF_TRY(kf_rmsnorm(ctx, bx, ToX(final_norm.w), ToX(gBUFF.bNorm), ns, C, final_norm.rms_eps, nullptr));
-        KF_TRY(kf_head_logprob(ctx, &wh, ToX(gBUFF.bNorm), C, ns, gBUFF.d_stgt, gBUFF.d_slp, nullptr, top1_out ? gBUFF.d_stop1 : nullptr, gBUFF.score_ws));
+        KF_TRY(kf_head_logprob(ctx, &wh, ToX(gBUFF.bNorm), C, ns, gBUFF.d_stgt, gBUFF.d_slp, nullptr, top1_out ? gBUFF.d_stop1.get() : nullptr, gBUFF.score_ws));
         KF_TRY(kf_d2h(ctx, logprob_out + c0, gBUFF.d_slp, (size_t)ns * 4));
         if (top1_out) KF_TRY(kf_d2h(ctx, top1_out + c0, gBUFF.d_stop1, (size_t)ns * 4));
     }
@@ -1127,22 +1094,14 @@ int Fish::PrefillReady(int min_rows) {
     PC = min_rows > PC ? min_rows : PC;
     if (gBUFF.bX && gBUFF.rows < PC) { /* a later, larger batch: the buffers grow once (never inside a captured region: prefill launches are eager) */
         KF_TRY(kf_sync(ctx));
-        gBUFF.bX.reset(), gBUFF.bNorm.reset(), gBUFF.bQ.reset(), gBUFF.bAttn.reset(), gBUFF.bGate.reset(), gBUFF.bUp.reset();
-        kf_free(ctx, gBUFF.d_ptok), gBUFF.d_ptok = nullptr;
+        static_cast<TokenBatch&>(gBUFF) = TokenBatch(); /* the old set goes first (it can be large): a refusal below leaves it empty, rows 0 */
         if (!deq_arena) resident_tried = false; /* the larger batch may be one the resident bf16 copies serve (>= 1024 rows) */
     }
     if (!gBUFF.bX) {
-        gBUFF.rows = PC;
-        gBUFF.bX = GT(ctx, "bX", typNUMBER::BF16, C, PC);
-        gBUFF.bNorm = GT(ctx, "bNorm", typNUMBER::BF16, C, PC);
-        gBUFF.bQ = GT(ctx, "bQ", typNUMBER::BF16, qd, PC);
-        gBUFF.bAttn = GT(ctx, "bAttn", typNUMBER::BF16, qd, PC);
-        gBUFF.bGate = GT(ctx, "bGate", typNUMBER::BF16, config.n_ff, PC);
-        gBUFF.bUp = GT(ctx, "bUp", typNUMBER::BF16, config.n_ff, PC);
-        if (!gBUFF.bX || !gBUFF.bNorm || !gBUFF.bQ || !gBUFF.bAttn || !gBUFF.bGate || !gBUFF.bUp) return KF_OUTOF_GPUMEMORY;
-        KF_TRY(kf_malloc(ctx, (size_t)PC * 4, (void**)&gBUFF.d_ptok));
+        TokenBatch fresh;
+        KF_TRY(fresh.Alloc(ctx, PC, C, qd, config.n_ff));
         // the stacked large-batch routes (Q | K | V and gate | up dequantised back to back, one tile-GEMM launch each): their workspace, sized here -- the first
-        // Prefill allocates the batch buffers anyway; the launches themselves never allocate
+        // Prefill allocates the batch buffers anyway; the launches themselves never allocate.  The set is committed behind it: rows are never held without their scratch
         for (int l = 0; l < config.nLayer; l++) {
             kf_weight wq = attn[l]->Q.w->desc(), wk = attn[l]->K.w->desc(), wv = attn[l]->V.w->desc(), wg = ffn[l]->gate.w->desc(), wu = ffn[l]->up.w->desc();
             const kf_weight* qkv[3] = {&wq, &wk, &wv};
@@ -1150,6 +1109,7 @@ int Fish::PrefillReady(int min_rows) {
             const size_t need = kf_linear_multi_scratch_bytes(3, qkv, PC), need2 = kf_linear_multi_scratch_bytes(2, gu, PC);
             KF_TRY(GrowScratch(need > need2 ? need : need2));
         }
+        static_cast<TokenBatch&>(gBUFF) = std::move(fresh);
     }
     return EnsureResident(gBUFF.rows);
 }
@@ -1166,11 +1126,8 @@ int Fish::SetSampler(const CHAT_SAMPLER& s) {
     if (!s.Valid(config.vocab)) return KF_INVALID_ARGS;
     const bool was_greedy = samp_params.greedy();
     samp_params = s;
-    if (!was_greedy || !s.greedy()) { /* the captured step graphs end in a different pick, or hold the old sampler arguments */
-        for (auto& g : graphs)
-            if (g) kf_graph_destroy(g), g = nullptr;
-    }
-    if (!d_rng) KF_TRY(kf_malloc(ctx, 8, (void**)&d_rng));
+    if (!was_greedy || !s.greedy()) DropGraphs(); /* the captured step graphs end in a different pick, or hold the old sampler arguments */
+    if (!d_rng) KF_TRY(d_rng.Alloc(ctx, 8));
     return kf_h2d(ctx, d_rng, &samp_params.seed, 8);
 }
 
@@ -1195,21 +1152,6 @@ int Fish::Generate(const int* prompt, int n_prompt, int n_new, int* out, bool us
 }
 
 // ------------------------------------------------------------------------------------------------ speculative decoding: the verify pass and the rounds
-int Fish::VerifyReady(bool logits) {
-    const int R = KF_SPEC_MAX_K + 1, C = config.nEmbed, qd = config.n_head * config.head_dim;
-    if (!vX) {
-        const kf_weight wh = head.proj.w->desc();
-        vX = GT(ctx, "vX", typNUMBER::BF16, C, R), vQ = GT(ctx, "vQ", typNUMBER::BF16, qd, R), vAttn = GT(ctx, "vAttn", typNUMBER::BF16, qd, R);
-        vGate = GT(ctx, "vGate", typNUMBER::BF16, config.n_ff, R);
-        v_attn_ws = GT(ctx, "v_attn_ws", typNUMBER::F32, (int)((kf_attn_rows_scratch_bytes(config.n_head, config.head_dim, R) + 3) / 4)); /* zero-filled once */
-        v_head_ws = GT(ctx, "v_head_ws", typNUMBER::F32, (int)((kf_head_rows_scratch_bytes(&wh) + 3) / 4));
-        if (!vX || !vQ || !vAttn || !vGate || !v_attn_ws || !v_head_ws) return vX.reset(), KF_OUTOF_GPUMEMORY;
-        KF_TRY(kf_malloc(ctx, (size_t)2 * R * 4, (void**)&d_vtok));
-    }
-    if (logits && !vLogits && !(vLogits = GT(ctx, "vLogits", typNUMBER::BF16, config.vocab, R))) return KF_OUTOF_GPUMEMORY;
-    return KF_OK;
-}
-
 int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, std::string& why) {
     if (!tokens || !top1 || n < 1 || n > KF_SPEC_MAX_K + 1 || pos0 < 0 || pos0 + n > config.n_ctx)
         return refused(why, "kfh_verify", KF_INVALID_ARGS, "1 .. 8 tokens at positions inside the context, and a place for their ids");
@@ -1219,10 +1161,11 @@ int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, 
     if (HasRow3()) return refused(why, "kfh_verify", KF_UNSUPPORTED_DATATYPE, kRow3Why); /* the row entries (kf_*_rows) do not unpack the 3-bit stream */
     const int rcm = verify_refusal(Modes(), samp_params.greedy(), "kfh_verify", why);
     if (rcm != KF_OK) return Kv8Note(why), rcm;
-    KF_TRY(VerifyReady(logits != nullptr));
+    if (!vrows.vX) KF_TRY(Commit(vrows, ctx, config, head.proj.w->desc())); /* allocated by the first Verify */
+    if (logits && !vLogits && !(vLogits = GT(ctx, "vLogits", typNUMBER::BF16, config.vocab, KF_SPEC_MAX_K + 1))) return KF_OUTOF_GPUMEMORY;
     const int C = config.nEmbed, hd = config.head_dim, nh = config.n_head, nkv = config.n_head_kv, qd = nh * hd, kvd = nkv * hd, F = config.n_ff;
-    floatX *bx = ToX(vX), *bq = ToX(vQ), *ba = ToX(vAttn), *bg = ToX(vGate);
-    int32_t* d_top1 = d_vtok + KF_SPEC_MAX_K + 1;
+    floatX *bx = ToX(vrows.vX), *bq = ToX(vrows.vQ), *ba = ToX(vrows.vAttn), *bg = ToX(vrows.vGate);
+    int32_t *d_vtok = vrows.d_vtok, *d_top1 = d_vtok + KF_SPEC_MAX_K + 1;
     int64_t before[2], after[2];
     KF_TRY(kf_rows_route_counts(ctx, before));
     const kf_weight we = embed.w->desc();
@@ -1242,13 +1185,13 @@ int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, 
         // every K row of the batch normed and rotated in place BEFORE the attention: query r reads the keys of rows 0 .. r - 1
         KF_TRY(kf_qknorm_rope_batch(ctx, bq, kc + (size_t)pos0 * kvd, a->normQ.w ? ToX(a->normQ.w) : nullptr, a->normK.w ? ToX(a->normK.w) : nullptr, rope_table, pos0, n, qd, kvd,
                                     nh, nkv, hd, a->normQ.rms_eps));
-        KF_TRY(kf_attn_decode_rows(ctx, bq, qd, kc, vc, ba, pos0, n, nh, nkv, hd, kvd, v_attn_ws->data));
+        KF_TRY(kf_attn_decode_rows(ctx, bq, qd, kc, vc, ba, pos0, n, nh, nkv, hd, kvd, vrows.v_attn_ws->data));
         KF_TRY(kf_linear_rows(ctx, &wo, ba, qd, bx, C, n, KF_EPI_RESIDUAL, bx, C));
         KF_TRY(kf_norm_gateup_swiglu_rows(ctx, bx, C, ToX(m->norm.w), m->norm.rms_eps, &wg, &wu, bg, F, n));
         KF_TRY(kf_linear_rows(ctx, &wd, bg, F, bx, C, n, KF_EPI_RESIDUAL, bx, C));
     }
     const kf_weight wh = head.proj.w->desc();
-    KF_TRY(kf_norm_lm_head_rows(ctx, bx, C, ToX(final_norm.w), final_norm.rms_eps, &wh, logits ? ToX(vLogits) : nullptr, config.vocab, d_top1, n, v_head_ws->data));
+    KF_TRY(kf_norm_lm_head_rows(ctx, bx, C, ToX(final_norm.w), final_norm.rms_eps, &wh, logits ? ToX(vLogits) : nullptr, config.vocab, d_top1, n, vrows.v_head_ws->data));
     KF_TRY(kf_d2h(ctx, top1, d_top1, (size_t)n * 4)); /* the round's one read */
     if (logits) KF_TRY(kf_d2h(ctx, logits, vLogits->data, (size_t)n * config.vocab * 2));
     KF_TRY(kf_rows_route_counts(ctx, after));
@@ -1332,24 +1275,29 @@ int SpecDecoder::Generate(const int* prompt, int n_prompt, int n_new, int* out, 
 }
 
 // ------------------------------------------------------------------------------------------------ XCD engines
-XcdEngine::~XcdEngine() {
-    if (!ctx) return;
-    kf_sync(ctx);
-    if (engine) kf_xengine_destroy(engine);
-    kf_free(ctx, engine_ws);
-    FreeSeqs(ctx);
+// n_kv K / V caches of the card's layout (XcdReplicas: one per sequence; XcdTP: one per rank), then per sequence: logits, residual stream, state, forced ids, ids out
+int XcdSeqs::Alloc(kf_ctx* c, const MODEL_CARD& card, int n_kv, int n_seq, int vocab) {
+    const int kvd = card.n_head_kv * card.head_dim;
+    key = GT(c, "xcd.key", typNUMBER::BF16, kvd, card.n_ctx * card.nLayer * n_kv);
+    val = GT(c, "xcd.val", typNUMBER::BF16, kvd, card.n_ctx * card.nLayer * n_kv);
+    logits = GT(c, "xcd.logits", typNUMBER::BF16, vocab, n_seq);
+    x = GT(c, "xcd.x", typNUMBER::BF16, card.nEmbed, n_seq);
+    if (!key || !val || !logits || !x) return KF_OUTOF_GPUMEMORY;
+    KF_TRY(kf_memset(c, key->data, 0, key->szData));
+    KF_TRY(kf_memset(c, val->data, 0, val->szData));
+    return SeqBuffers::Alloc(c, n_seq, card.n_ctx, 0);
 }
-int XcdEngine::EnsureWorkspace(size_t bytes) {
-    if (engine_ws && bytes <= engine_ws_bytes) return KF_OK;
-    if (engine_ws) kf_free(ctx, engine_ws), engine_ws = nullptr;
-    KF_TRY(kf_malloc(ctx, bytes, &engine_ws));
-    engine_ws_bytes = bytes;
-    return KF_OK;
+int XcdReplicas::BatchRows::Alloc(kf_ctx* c, int kv_dim, int rows, int vocab, int n_seq) {
+    bK = GT(c, "xr.bK", typNUMBER::BF16, kv_dim, rows), bV = GT(c, "xr.bV", typNUMBER::BF16, kv_dim, rows);
+    if (!bK || !bV) return KF_OUTOF_GPUMEMORY;
+    KF_TRY(d_dst.Alloc(c, (size_t)3 * n_seq * sizeof(void*) + (size_t)n_seq * 4)); /* three tables of destinations (K, V, logits) + the slots */
+    bL = GT(c, "xr.bL", typNUMBER::BF16, vocab, n_seq);
+    return bL ? KF_OK : KF_OUTOF_GPUMEMORY;
 }
 int XcdEngine::LaunchSteps(int n) {
     for (int i = 0; i < n;) {
         const int m = n - i < steps_per_launch ? n - i : steps_per_launch;
-        KF_TRY(kf_xengine_steps(ctx, engine, ToX(x), d_state, m, 1));
+        KF_TRY(kf_xengine_steps(ctx, engine.get(), ToX(x), d_state, m, 1));
         i += m;
     }
     return KF_OK;
@@ -1361,17 +1309,12 @@ int XcdEngine::SetStepsPerLaunch(int n) {
 }
 int XcdEngine::Check() {
     if (!engine) return KF_OK;
-    const int rc = kf_xengine_check(ctx, engine);
-    if (rc == KF_INTERNAL_ERR) kf_xengine_reset(ctx, engine);
+    const int rc = kf_xengine_check(ctx, engine.get());
+    if (rc == KF_INTERNAL_ERR) kf_xengine_reset(ctx, engine.get());
     return rc;
 }
 
 // ---- XCD-confined replicas
-XcdReplicas::~XcdReplicas() {
-    if (!ctx) return;
-    kf_free(ctx, d_rng);
-    kf_free(ctx, d_dst);
-}
 size_t XcdReplicas::kv_seq_elems() const {
     const MODEL_CARD& c = hFish->config;
     return (size_t)c.nLayer * c.n_ctx * c.n_head_kv * c.head_dim;
@@ -1381,7 +1324,6 @@ size_t XcdReplicas::kv_seq_elems() const {
 int XcdReplicas::MakeEngine(bool allocate) {
     Fish* f = hFish;
     const MODEL_CARD& c = f->config;
-    const int kvd = c.n_head_kv * c.head_dim;
     std::vector<kf_engine_layer> L;
     kf_engine_desc d;
     KF_TRY(f->EngineRefusal(why));
@@ -1397,27 +1339,19 @@ int XcdReplicas::MakeEngine(bool allocate) {
         why = "embedding / head / final norm missing";
         return KF_ENGINE_NOT_SERVED;
     }
-    const size_t seq_elems = kv_seq_elems();
-    if (allocate) { // per sequence: K / V cache, state {token, pos, parked, status}, forced ids, ids out, logits, residual stream
-        key = GT(ctx, "xr.key", typNUMBER::BF16, kvd, c.n_ctx * c.nLayer * n_seq);
-        val = GT(ctx, "xr.val", typNUMBER::BF16, kvd, c.n_ctx * c.nLayer * n_seq);
-        logits = GT(ctx, "xr.logits", typNUMBER::BF16, c.vocab, n_seq);
-        x = GT(ctx, "xr.x", typNUMBER::BF16, c.nEmbed, n_seq);
-        if (!key || !val || !logits || !x) return KF_OUTOF_GPUMEMORY;
-        KF_TRY(kf_memset(ctx, key->data, 0, seq_elems * n_seq * 2));
-        KF_TRY(kf_memset(ctx, val->data, 0, seq_elems * n_seq * 2));
-        KF_TRY(AllocSeqs(ctx, n_seq, c.n_ctx, 0));
-    }
+    if (allocate) KF_TRY(Commit<XcdSeqs>(*this, ctx, c, n_seq, n_seq, c.vocab));
     KF_TRY(f->EngineTable(ToX(key), ToX(val), true, why, L, d)); /* the table again, on this object's rows */
     KF_TRY(EnsureWorkspace(kf_xengine_workspace_bytes(&d)));
-    int rc = kf_xengine_create(ctx, &d, n_seq, (int64_t)seq_elems, engine_ws, engine_ws_bytes, &engine);
+    kf_xengine* e = nullptr;
+    int rc = kf_xengine_create(ctx, &d, n_seq, (int64_t)kv_seq_elems(), engine_ws, engine_ws.bytes(), &e);
     if (rc != KF_OK) {
         why = kf_last_error();
         return rc;
     }
+    engine.reset(e);
     kf_weight we = f->embed.w->desc(), wh = f->head.proj.w->desc();
-    rc = kf_xengine_set_embedding(ctx, engine, &we, d_forced, c.n_ctx);
-    if (rc == KF_OK) rc = kf_xengine_set_head(ctx, engine, &wh, ToX(f->final_norm.w), ToX(logits), d_tokens_out, c.n_ctx);
+    rc = kf_xengine_set_embedding(ctx, engine.get(), &we, d_forced, c.n_ctx);
+    if (rc == KF_OK) rc = kf_xengine_set_head(ctx, engine.get(), &wh, ToX(f->final_norm.w), ToX(logits), d_tokens_out, c.n_ctx);
     if (rc != KF_OK) {
         why = "the embedding table and the LM head must be bf16 (read inside the launch)";
         return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : rc;
@@ -1433,8 +1367,8 @@ int XcdReplicas::Build(Fish* f, int n_seq_) {
 int XcdReplicas::Fresh() {
     if (engine && built_gen == hFish->weights_gen) return KF_OK;
     if (engine) {
-        KF_TRY(kf_sync(ctx));
-        kf_xengine_destroy(engine), engine = nullptr;
+        KF_TRY(kf_sync(ctx)); /* the deleter does not */
+        engine.reset();
     }
     const int rc = MakeEngine(false); /* caches, states, forced ids and ids out stay: the sequences go on where they stand, on the new weights */
     if (rc != KF_OK) g_host_err = "XcdReplicas: " + why; /* a switch moved on the Fish since the engine was built (int8 activations, adapters, the int8 KV cache): kfh_host_error says which */
@@ -1454,7 +1388,7 @@ int XcdReplicas::SetState(int seq, int token, int pos) {
 // CHAT_SAMPLER for Chat (greedy by default): one rng word per sequence, seeded per request
 int XcdReplicas::SetSampler(const CHAT_SAMPLER& sp) {
     if (!sp.Valid(hFish->config.vocab)) return KF_INVALID_ARGS;
-    if (!sp.greedy() && !d_rng) KF_TRY(kf_malloc(ctx, (size_t)n_seq * 8, (void**)&d_rng));
+    if (!sp.greedy() && !d_rng) KF_TRY(d_rng.Alloc(ctx, (size_t)n_seq * 8));
     samp_params = sp;
     return KF_OK;
 }
@@ -1508,14 +1442,9 @@ int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int
     if (T >= c.n_ctx || R > f->prefill_chunk) return KF_INVALID_ARGS;
     KF_TRY(Fresh());
     KF_TRY(f->PrefillReady(R));
-    if (!bK || bK->ne[1] < R) {
+    if (!pb.bK || pb.bK->ne[1] < R) {
         KF_TRY(kf_sync(ctx));
-        const int rows = f->gBUFF.rows;
-        bK = GT(ctx, "xr.bK", typNUMBER::BF16, kvd, rows), bV = GT(ctx, "xr.bV", typNUMBER::BF16, kvd, rows);
-        if (!bK || !bV) return KF_OUTOF_GPUMEMORY;
-        if (!d_dst) KF_TRY(kf_malloc(ctx, (size_t)3 * n_seq * sizeof(void*) + (size_t)n_seq * 4, (void**)&d_dst)); /* three tables of destinations (K, V, logits) + the slots */
-        if (!bL) bL = GT(ctx, "xr.bL", typNUMBER::BF16, c.vocab, n_seq);
-        if (!bL) return KF_OUTOF_GPUMEMORY;
+        KF_TRY(Commit(pb, ctx, kvd, f->gBUFF.rows, c.vocab, n_seq));
     }
     std::vector<int32_t> rows((size_t)R, 0);
     std::vector<void*> dst((size_t)3 * n_seq + (n_seq + 1) / 2, nullptr); /* the slots ride behind the pointer tables as int32 */
@@ -1526,10 +1455,10 @@ int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int
         dst[2 * n_seq + i] = ToX(logits) + (size_t)slots[i] * c.vocab;
         h_slots[i] = slots[i];
     }
-    const int32_t* d_slots = reinterpret_cast<const int32_t*>(d_dst + (size_t)3 * n_seq);
+    const int32_t* d_slots = reinterpret_cast<const int32_t*>(pb.d_dst + (size_t)3 * n_seq);
     KF_TRY(kf_h2d(ctx, f->gBUFF.d_ptok, rows.data(), (size_t)R * 4));
-    KF_TRY(kf_h2d(ctx, d_dst, dst.data(), (size_t)3 * n_seq * sizeof(void*) + (size_t)n_seq * 4));
-    floatX *bx = ToX(f->gBUFF.bX), *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn), *bk = ToX(bK), *bv = ToX(bV);
+    KF_TRY(kf_h2d(ctx, pb.d_dst, dst.data(), (size_t)3 * n_seq * sizeof(void*) + (size_t)n_seq * 4));
+    floatX *bx = ToX(f->gBUFF.bX), *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn), *bk = ToX(pb.bK), *bv = ToX(pb.bV);
     kf_weight we = f->embed.w->desc();
     KF_TRY(kf_embed_batch(ctx, &we, f->gBUFF.d_ptok, R, bx));
     for (int l = 0; l < c.nLayer; l++) {
@@ -1540,8 +1469,8 @@ int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int
                                 c.n_head_kv, c.head_dim, a.normQ.rms_eps)); /* positions restart with every prompt */
         KF_TRY(kf_attn_prefill_batch(ctx, bq, bk, bv, ba, T, qd, c.n_head, c.n_head_kv, c.head_dim, kvd, S)); /* the rows of a prompt see that prompt's keys only */
         const size_t off = (size_t)l * c.n_ctx * kvd * 2, blk = (size_t)T * kvd * 2;
-        KF_TRY(kf_copy_blocks(ctx, d_dst, off, bk, blk, blk, S));
-        KF_TRY(kf_copy_blocks(ctx, d_dst + n_seq, off, bv, blk, blk, S));
+        KF_TRY(kf_copy_blocks(ctx, pb.d_dst, off, bk, blk, blk, S));
+        KF_TRY(kf_copy_blocks(ctx, pb.d_dst + n_seq, off, bv, blk, blk, S));
         KF_TRY(kf_linear(ctx, &wo, ba, bx, nullptr, R, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx));
         KF_TRY(f->ffn[l]->cuFlow(bx, R));
     }
@@ -1560,9 +1489,9 @@ int XcdReplicas::PrefillBatch(const int* slots, const int32_t* tokens, const int
                                    d_tokens_out + (size_t)s * c.n_ctx, f->gBUFF.head_ws->data));
     }
     if (together) {
-        KF_TRY(kf_linear(ctx, &wh, bn, ToX(bL), nullptr, S, 1.0f, 0.0f, 0u, nullptr));
-        KF_TRY(kf_argmax_rows_state(ctx, ToX(bL), c.vocab, c.vocab, S, d_slots, d_state, d_tokens_out, c.n_ctx));
-        KF_TRY(kf_copy_blocks(ctx, d_dst + 2 * n_seq, 0, ToX(bL), (size_t)c.vocab * 2, (size_t)c.vocab * 2, S));
+        KF_TRY(kf_linear(ctx, &wh, bn, ToX(pb.bL), nullptr, S, 1.0f, 0.0f, 0u, nullptr));
+        KF_TRY(kf_argmax_rows_state(ctx, ToX(pb.bL), c.vocab, c.vocab, S, d_slots, d_state, d_tokens_out, c.n_ctx));
+        KF_TRY(kf_copy_blocks(ctx, pb.d_dst + 2 * n_seq, 0, ToX(pb.bL), (size_t)c.vocab * 2, (size_t)c.vocab * 2, S));
     }
     return KF_OK;
 }
@@ -1663,7 +1592,7 @@ int XcdReplicas::Chat(const int32_t* prompts, const int32_t* prompt_len, int n_r
             for (int s = 0; s < n_seq; s++)
                 if (slot[s].req >= 0) active++, k = slot[s].want - slot[s].have < k ? slot[s].want - slot[s].have : k;
             if (!active) continue;
-            KF_TRY(kf_xengine_steps(ctx, engine, ToX(x), d_state, k, sampled ? 0 : 1));
+            KF_TRY(kf_xengine_steps(ctx, engine.get(), ToX(x), d_state, k, sampled ? 0 : 1));
             if (sampled)
                 for (int s = 0; s < n_seq; s++)
                     if (slot[s].req >= 0) KF_TRY(draw(s));
@@ -1704,19 +1633,16 @@ int XcdTP::Build(Fish** fs, int world) {
     const MODEL_CARD& c = f0->config;
     const int kvd = c.n_head_kv * c.head_dim;
     const size_t rank_elems = (size_t)c.nLayer * c.n_ctx * kvd;
-    key = GT(ctx, "xtp.key", typNUMBER::BF16, kvd, c.n_ctx * c.nLayer * world);
-    val = GT(ctx, "xtp.val", typNUMBER::BF16, kvd, c.n_ctx * c.nLayer * world);
-    if (!key || !val) return KF_OUTOF_GPUMEMORY;
-    KF_TRY(kf_memset(ctx, key->data, 0, rank_elems * world * 2));
-    KF_TRY(kf_memset(ctx, val->data, 0, rank_elems * world * 2));
+    vocab = 0;
+    for (int r = 0; r < world; r++) vocab += fs[r]->config.vocab; /* the logits vector: the shards in rank order */
+    KF_TRY(Commit<XcdSeqs>(*this, ctx, c, world, 1, vocab));
     std::vector<std::vector<kf_engine_layer>> Ls(world);
     std::vector<kf_engine_desc> ds(world);
     std::vector<const kf_engine_desc*> dp(world);
     std::vector<kf_weight> heads(world);
     std::vector<const kf_weight*> hp(world);
     std::vector<int32_t> row0(world);
-    vocab = 0;
-    for (int r = 0; r < world; r++) {
+    for (int r = 0, v0 = 0; r < world; v0 += fs[r++]->config.vocab) {
         Fish* f = fs[r];
         const MODEL_CARD& cr = f->config;
         if (cr.nLayer != c.nLayer || cr.n_ctx != c.n_ctx || cr.nEmbed != c.nEmbed || cr.n_head_kv * cr.head_dim != kvd) {
@@ -1731,22 +1657,19 @@ int XcdTP::Build(Fish** fs, int world) {
             why = "embedding / head / final norm missing";
             return KF_ENGINE_NOT_SERVED;
         }
-        heads[r] = f->head.proj.w->desc(), hp[r] = &heads[r], row0[r] = vocab;
-        vocab += cr.vocab;
+        heads[r] = f->head.proj.w->desc(), hp[r] = &heads[r], row0[r] = v0;
     }
-    logits = GT(ctx, "xtp.logits", typNUMBER::BF16, vocab, 1);
-    x = GT(ctx, "xtp.x", typNUMBER::BF16, c.nEmbed, 1);
-    if (!logits || !x) return KF_OUTOF_GPUMEMORY;
-    KF_TRY(AllocSeqs(ctx, 1, c.n_ctx, 0));
     KF_TRY(EnsureWorkspace(kf_xengine_workspace_bytes_tp(dp[0])));
-    int rc = kf_xengine_create_tp(ctx, dp.data(), world, engine_ws, engine_ws_bytes, &engine);
+    kf_xengine* e = nullptr;
+    int rc = kf_xengine_create_tp(ctx, dp.data(), world, engine_ws, engine_ws.bytes(), &e);
     if (rc != KF_OK) {
         why = kf_last_error();
         return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : rc;
     }
+    engine.reset(e);
     kf_weight we = f0->embed.w->desc();
-    rc = kf_xengine_set_embedding(ctx, engine, &we, d_forced, c.n_ctx);
-    if (rc == KF_OK) rc = kf_xengine_set_head_tp(ctx, engine, hp.data(), row0.data(), ToX(f0->final_norm.w), ToX(logits), d_tokens_out, c.n_ctx);
+    rc = kf_xengine_set_embedding(ctx, engine.get(), &we, d_forced, c.n_ctx);
+    if (rc == KF_OK) rc = kf_xengine_set_head_tp(ctx, engine.get(), hp.data(), row0.data(), ToX(f0->final_norm.w), ToX(logits), d_tokens_out, c.n_ctx);
     if (rc != KF_OK) {
         why = kf_last_error();
         return rc == KF_UNSUPPORTED_DATATYPE ? KF_ENGINE_NOT_SERVED : rc;
@@ -1853,8 +1776,7 @@ int kfh_n_hot(void* h, int layer) {
 int kfh_set_engine(void* h, int on) {
     Fish* f = reinterpret_cast<Fish*>(h);
     f->use_engine = on != 0;
-    for (auto& g : f->graphs)
-        if (g) kf_graph_destroy(g), g = nullptr;
+    f->DropGraphs();
     return KF_OK;
 }
 // int8 activations for the ternary / 1-bit layer matrices: on / off (off: today's routes, bit for bit).  A refusal leaves the switch as it was; kfh_host_error says why.
@@ -1912,8 +1834,7 @@ int kfh_a8_route_counts(void* h, int64_t* out2) {
 // summation order of the decode kernels (kf_set_canonical): 1 (default) the canonical order shared with the CPU oracle, 0 the v_dot2c forms; captured graphs are dropped
 int kfh_set_canonical(void* h, int on) {
     Fish* f = reinterpret_cast<Fish*>(h);
-    for (auto& g : f->graphs)
-        if (g) kf_graph_destroy(g), g = nullptr;
+    f->DropGraphs();
     return kf_set_canonical(f->ctx, on);
 }
 // steps enqueued (or captured) through the engine so far; -1: the engine does not serve this model
@@ -1927,21 +1848,19 @@ extern "C" int kfdbg_engine_stamps_enable(kf_engine* e, int wg);
 extern "C" int kfdbg_engine_set_delays(kf_engine* e, const int* d6);
 int kfh_engine_stamps(void* h, unsigned long long* out, int n) {
     Fish* f = reinterpret_cast<Fish*>(h);
-    return f->engine ? kfdbg_engine_stamps(f->engine, out, n) : -1;
+    return f->engine ? kfdbg_engine_stamps(f->engine.get(), out, n) : -1;
 }
 int kfh_engine_stamps_enable(void* h, int wg) {
     Fish* f = reinterpret_cast<Fish*>(h);
     if (f->engine_state == 0) f->EnsureEngine();
-    for (auto& g : f->graphs)
-        if (g) kf_graph_destroy(g), g = nullptr; /* captured launches hold the product instantiation */
-    return f->engine ? kfdbg_engine_stamps_enable(f->engine, wg) : -1;
+    f->DropGraphs(); /* captured launches hold the product instantiation */
+    return f->engine ? kfdbg_engine_stamps_enable(f->engine.get(), wg) : -1;
 }
 int kfh_engine_set_delays(void* h, const int* d6) {
     Fish* f = reinterpret_cast<Fish*>(h);
     if (f->engine_state == 0) f->EnsureEngine();
-    for (auto& g : f->graphs)
-        if (g) kf_graph_destroy(g), g = nullptr;
-    return f->engine ? kfdbg_engine_set_delays(f->engine, d6) : -1;
+    f->DropGraphs();
+    return f->engine ? kfdbg_engine_set_delays(f->engine.get(), d6) : -1;
 }
 // why the engine does not serve this model ("" when it does; valid once a step has been tried or kfh_engine_stamps_enable / kfh_engine_only forced the build)
 const char* kfh_engine_why(void* h) {
@@ -1958,7 +1877,7 @@ int kfh_engine_tune(void* h, int passes, float* us2) {
     KF_TRY(kf_d2h(f->ctx, st, f->d_state, 16));
     f->tok_pos = st[1];
     float b = 0.f, a = 0.f;
-    const int rc = kf_engine_tune(f->ctx, f->engine, ToX(f->x), f->d_state, f->pos_bound(), passes, &b, &a);
+    const int rc = kf_engine_tune(f->ctx, f->engine.get(), ToX(f->x), f->d_state, f->pos_bound(), passes, &b, &a);
     if (us2) us2[0] = b, us2[1] = a;
     return rc;
 }
@@ -1991,7 +1910,7 @@ int kfh_engine_stats(void* h, int pos, int32_t* out14) {
     if (!f->engine) return KF_ENGINE_NOT_SERVED;
     kf_engine_statistics s;
     f->tok_pos = pos;
-    KF_TRY(kf_engine_stats(f->ctx, f->engine, f->pos_bound(), &s));
+    KF_TRY(kf_engine_stats(f->ctx, f->engine.get(), f->pos_bound(), &s));
     for (int i = 0; i < 6; i++) out14[i] = s.sweeps[i], out14[7 + i] = s.delay[i];
     out14[6] = s.polls, out14[13] = s.tuned;
     return KF_OK;
@@ -2002,7 +1921,7 @@ int kfh_engine_screen_stats(void* h, int64_t* out3) {
     out3[0] = out3[1] = out3[2] = 0;
     if (!f->engine) return KF_OK;
     kf_engine_screen_statistics s;
-    KF_TRY(kf_engine_screen_stats(f->ctx, f->engine, &s));
+    KF_TRY(kf_engine_screen_stats(f->ctx, f->engine.get(), &s));
     out3[0] = s.screened_steps, out3[1] = s.rows_reranked, out3[2] = s.wg_fallbacks;
     return KF_OK;
 }
@@ -2017,15 +1936,12 @@ int kfh_engine_only(void* h, int n) {
     f->tok_pos = st[1];
     f->graph_mode = true;
     int rc = KF_OK;
-    for (int i = 0; i < n && rc == KF_OK; i++) rc = kf_engine_step(f->ctx, f->engine, ToX(f->x), ToX(f->x), f->d_state, f->pos_bound());
+    for (int i = 0; i < n && rc == KF_OK; i++) rc = kf_engine_step(f->ctx, f->engine.get(), ToX(f->x), ToX(f->x), f->d_state, f->pos_bound());
     f->graph_mode = false;
     return rc;
 }
 // synchronises; KF_INTERNAL_ERR when one of the engine's hand-off polls has timed out
-int kfh_engine_check(void* h) {
-    Fish* f = reinterpret_cast<Fish*>(h);
-    return f->EngineCheck();
-}
+int kfh_engine_check(void* h) { return reinterpret_cast<Fish*>(h)->EngineCheck(); }
 
 static SLP* slot_of(Fish* f, int layer, int slot) { return layer >= 0 ? f->LayerMatrix(layer, slot) : slot == 1 ? &f->head.proj : nullptr; }
 // the mode table without a device (tests/test_host_modes_cpu.py): mode_refusal / engine_refusal / eager_only for any set of active modes
@@ -2085,12 +2001,7 @@ static int set_weight_impl(void* h, int layer, int slot, int type, int ne0, int 
     t->szData = szData, t->szGama = blob_bytes - szData;
     t->quant.T_group = lGroup, t->quant.qMin = qMin, t->quant.qMax = qMax, t->quant.qBias = qBias;
     t->quant.isNormalFloat = normal_float;
-    if (is_device) {
-        t->data = const_cast<void*>(blob), t->ctx = f->ctx, t->owned = false;
-    } else {
-        int rc = t->LoadBlob(f->ctx, blob, blob_bytes);
-        if (rc != KF_OK) return rc;
-    }
+    KF_TRY(t->Take(f->ctx, blob, blob_bytes, is_device != 0));
     f->DropEngine(); /* the engine's device table (and every captured graph) holds the old tensors' addresses */
     if (layer < 0 && slot == 0) {
         f->embed.w = t;
@@ -2118,12 +2029,7 @@ int kfh_set_norm(void* h, int layer, int slot, const void* w, int n, int is_devi
     Fish* f = reinterpret_cast<Fish*>(h);
     auto t = std::make_shared<GTensor>();
     t->type = typNUMBER::BF16, t->ne[0] = n, t->szData = (size_t)n * 2;
-    if (is_device) {
-        t->data = const_cast<void*>(w), t->ctx = f->ctx;
-    } else {
-        int rc = t->LoadBlob(f->ctx, w, (size_t)n * 2);
-        if (rc != KF_OK) return rc;
-    }
+    KF_TRY(t->Take(f->ctx, w, (size_t)n * 2, is_device != 0));
     f->DropEngine();
     if (layer < 0) {
         f->final_norm.w = t;
@@ -2245,7 +2151,7 @@ void* kfh_logits(void* h) { return reinterpret_cast<Fish*>(h)->head.preLogits->d
 void* kfh_hidden(void* h) { return reinterpret_cast<Fish*>(h)->x->data; }
 // ---- tensor parallel
 int kfh_tp_init(void* h, int rank, int world, int vocab_row0) { return reinterpret_cast<Fish*>(h)->TPInit(rank, world, vocab_row0); }
-void* kfh_tp_area(void* h) { return reinterpret_cast<Fish*>(h)->tp.area; }
+void* kfh_tp_area(void* h) { return reinterpret_cast<Fish*>(h)->tp.area.get(); }
 int kfh_tp_set_peer(void* h, int r, void* area) { return reinterpret_cast<Fish*>(h)->TPSetPeer(r, area); }
 int kfh_tp_export(void* h, unsigned char* handle64) {
     Fish* f = reinterpret_cast<Fish*>(h);
@@ -2283,18 +2189,9 @@ int kfh_tp_group_run(void** hs, int R, int pos, int n, int use_graph) {
         int rc = KF_OK;
         if (use_graph) {
             const int b = bucket_of(pos + i);
-            if ((int)graphs.size() <= b) graphs.resize(b + 1, nullptr);
-            if (!graphs[b]) {
-                rc = kf_graph_begin(fs[0]->ctx);
-                if (rc == KF_OK) {
-                    rc = tp_group_enqueue(fs, R);
-                    kf_graph* g = nullptr;
-                    const int rc2 = kf_graph_end(fs[0]->ctx, &g);
-                    if (rc == KF_OK) rc = rc2;
-                    if (rc == KF_OK) graphs[b] = g;
-                }
-            }
-            if (rc == KF_OK) rc = kf_graph_launch(fs[0]->ctx, graphs[b]);
+            if ((int)graphs.size() <= b) graphs.resize(b + 1);
+            if (!graphs[b]) rc = Capture(fs[0]->ctx, graphs[b], [&] { return tp_group_enqueue(fs, R); });
+            if (rc == KF_OK) rc = kf_graph_launch(fs[0]->ctx, graphs[b].get());
         } else {
             rc = tp_group_enqueue(fs, R);
         }
@@ -2381,15 +2278,15 @@ void* kfh_xtp_vcache(void* h) { return ToX(reinterpret_cast<XcdTP*>(h)->val); }
 extern "C" int kfdbg_xengine_variant(kf_xengine* e, int nwv, int depth);
 extern "C" int kfdbg_xengine_stamps_enable(kf_xengine* e, int seq, int wg, int max_steps);
 extern "C" int kfdbg_xengine_stamps(kf_xengine* e, unsigned long long* h_out, int n_words);
-int kfh_xtp_stamps_enable(void* h, int rank, int wg, int max_steps) { return kfdbg_xengine_stamps_enable(reinterpret_cast<XcdTP*>(h)->engine, rank, wg, max_steps); }
-int kfh_xtp_stamps(void* h, unsigned long long* out, int n) { return kfdbg_xengine_stamps(reinterpret_cast<XcdTP*>(h)->engine, out, n); }
-int kfh_xr_variant(void* h, int nwv, int depth) { return kfdbg_xengine_variant(reinterpret_cast<XcdReplicas*>(h)->engine, nwv, depth); }
-int kfh_xr_stamps_enable(void* h, int seq, int wg, int max_steps) { return kfdbg_xengine_stamps_enable(reinterpret_cast<XcdReplicas*>(h)->engine, seq, wg, max_steps); }
-int kfh_xr_stamps(void* h, unsigned long long* out, int n) { return kfdbg_xengine_stamps(reinterpret_cast<XcdReplicas*>(h)->engine, out, n); }
+int kfh_xtp_stamps_enable(void* h, int rank, int wg, int max_steps) { return kfdbg_xengine_stamps_enable(reinterpret_cast<XcdTP*>(h)->engine.get(), rank, wg, max_steps); }
+int kfh_xtp_stamps(void* h, unsigned long long* out, int n) { return kfdbg_xengine_stamps(reinterpret_cast<XcdTP*>(h)->engine.get(), out, n); }
+int kfh_xr_variant(void* h, int nwv, int depth) { return kfdbg_xengine_variant(reinterpret_cast<XcdReplicas*>(h)->engine.get(), nwv, depth); }
+int kfh_xr_stamps_enable(void* h, int seq, int wg, int max_steps) { return kfdbg_xengine_stamps_enable(reinterpret_cast<XcdReplicas*>(h)->engine.get(), seq, wg, max_steps); }
+int kfh_xr_stamps(void* h, unsigned long long* out, int n) { return kfdbg_xengine_stamps(reinterpret_cast<XcdReplicas*>(h)->engine.get(), out, n); }
 
 int kfh_num_graphs(void* h) {
     int n = 0;
-    for (auto g : reinterpret_cast<Fish*>(h)->graphs) n += g != nullptr;
+    for (const auto& g : reinterpret_cast<Fish*>(h)->graphs) n += g != nullptr;
     return n;
 }
 }

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/kf_abi.h"
+#include "kf_devbuf.hpp"
 #include "kf_host_modes.hpp"
 #include "kf_spec.hpp"
 
@@ -29,6 +30,16 @@ using floatX = kf_bf16;
 enum class typNUMBER : uint8_t { F32 = 0, F64, F16, BF16, F8E5M2, F8E4M3, U8, I8, U16, I16, U32, I32, U64, I64, Q4, Q3, Q2, T_SIGN, T_SEQ, BOOL1, T_BINARY };
 
 struct Fish;
+
+// kf_graph / kf_engine / kf_xengine handles: destroyed by these deleters only.  A deleter does not synchronise: where an engine may still run, kf_sync stands at that site.
+template <auto Destroy>
+struct HandleDel {
+    template <class H>
+    void operator()(H* h) const { Destroy(h); }
+};
+using hGraph = std::unique_ptr<kf_graph, HandleDel<kf_graph_destroy>>;
+using hEngine = std::unique_ptr<kf_engine, HandleDel<kf_engine_destroy>>;
+using hXEngine = std::unique_ptr<kf_xengine, HandleDel<kf_xengine_destroy>>;
 
 #define KF_TRY(expr)                 \
     do {                             \
@@ -45,16 +56,15 @@ struct QuantCard {
 // A device tensor: `data||gama` in one allocation, as huTensor::Alloc lays it out (GTensor.cpp:456-510).
 struct GTensor {
     std::string name;
-    void* data = nullptr;
+    DevBuf<> mem;          // the allocation, when this tensor owns one (Alloc / LoadBlob); empty for a caller's device pointer
+    void* data = nullptr;  // the view the kernels read: mem's block, a caller's pointer, or -- for the length of XcdReplicas::Prefill -- a sequence's rows
     size_t szData = 0, szGama = 0;
     typNUMBER type = typNUMBER::BF16;
     int ne[4] = {1, 1, 1, 1};
     QuantCard quant;
-    bool owned = false;
     kf_ctx* ctx = nullptr;
     std::shared_ptr<GTensor> qZero, qScale;  // vendor AutoAWQ tensors (GeQuant.cpp:410): data = qweight [in, out/8]; ne = {out, in}
 
-    ~GTensor();
     size_t size() const { return (size_t)ne[0] * ne[1] * ne[2] * ne[3]; }
     int nGroup() const { return (szGama && quant.T_group > 0) ? (int)(size() / quant.T_group) : 0; }
     floatX* gama_T() const { return szGama ? reinterpret_cast<floatX*>(reinterpret_cast<uint8_t*>(data) + szData) : nullptr; }
@@ -62,9 +72,12 @@ struct GTensor {
     // SerialGamaData H2D (huTensor.cu:413-458): allocate and copy a host `data||gama` blob
     int LoadBlob(kf_ctx* c, const void* h_blob, size_t nbytes);
     int Alloc(kf_ctx* c, size_t nbytes);
+    int Take(kf_ctx* c, const void* blob, size_t nbytes, bool is_device) {  // a caller's device pointer as the view (not owned), or LoadBlob of a host blob
+        return is_device ? (ctx = c, data = const_cast<void*>(blob), KF_OK) : LoadBlob(c, blob, nbytes);
+    }
 };
 using hGTensor = std::shared_ptr<GTensor>;
-hGTensor GT(kf_ctx* c, const std::string& name, typNUMBER tp, int n0, int n1 = 1);
+hGTensor GT(kf_ctx* c, const std::string& name, typNUMBER tp, int n0, int n1 = 1);  // zero-filled [n1][n0] of a whole-byte type; NULL when refused
 inline floatX* ToX(const hGTensor& t) { return t ? reinterpret_cast<floatX*>(t->data) : nullptr; }
 
 struct KVCache {
@@ -163,8 +176,29 @@ struct MODEL_CARD {  // the fields of CLI_params / MODEL_CARD this path reads (C
     bool tie_word_embeddings = true;
 };
 
-// Shared scratch, named after GST_MemBuffer's gBUFF members (GST_MemBuffer.hpp:46-48)
-struct MemBuffer {
+// token-batch (prefill) activations, [rows, .], allocated by the first Prefill and grown by a larger batch (Fish::PrefillReady)
+struct TokenBatch {
+    hGTensor bX, bNorm, bQ, bAttn, bGate, bUp;
+    DevBuf<int32_t> d_ptok;
+    int rows = 0;
+    int Alloc(kf_ctx* c, int n, int dim, int q_dim, int ffn);
+};
+// Fish::Score: a chunk's target ids, log-probs and greedy ids [score_rows], and kf_head_logprob's workspace; allocated by the first Score (ScoreReady)
+struct ScoreBuffers {
+    DevBuf<int32_t> d_stgt, d_stop1;
+    DevBuf<float> d_slp;
+    DevBuf<> score_ws;
+    int score_rows = 0;
+    int Alloc(kf_ctx* c, int n, size_t ws_bytes) {
+        KF_TRY(d_stgt.Alloc(c, (size_t)n * 4));
+        KF_TRY(d_slp.Alloc(c, (size_t)n * 4));
+        KF_TRY(d_stop1.Alloc(c, (size_t)n * 4));
+        KF_TRY(score_ws.Alloc(c, ws_bytes));
+        return score_rows = n, KF_OK;
+    }
+};
+// Shared scratch, named after GST_MemBuffer's gBUFF members (GST_MemBuffer.hpp:46-48).  The two sets above are bases: gBUFF.bX / gBUFF.d_stgt read as members, each set commits whole
+struct MemBuffer : TokenBatch, ScoreBuffers {
     hGTensor tmpFF1;    // Q.out
     hGTensor kraw;      // new key before norm/rope (fused path)
     hGTensor vraw;      // new value row before it is quantised (int8 KV cache; allocated by the first switch-on)
@@ -175,16 +209,6 @@ struct MemBuffer {
     hGTensor attn_ws;   // split-KV partials
     hGTensor head_ws;   // arg-max partials
     hGTensor residual;  // alias, not owned
-    // token-batch (prefill) activations, [prefill_chunk, .] rows, allocated by the first Prefill
-    hGTensor bX, bNorm, bQ, bAttn, bGate, bUp;
-    int32_t* d_ptok = nullptr;
-    int rows = 0;       // rows of the token-batch buffers
-    // Fish::Score: a chunk's target ids, log-probs and greedy ids [score_rows], and kf_head_logprob's workspace; allocated by the first Score (ScoreReady)
-    int32_t* d_stgt = nullptr;
-    float* d_slp = nullptr;
-    int32_t* d_stop1 = nullptr;
-    void* score_ws = nullptr;
-    int score_rows = 0;
 };
 
 // CHAT_SAMPLER (CLI_params.hpp:663-683): the fields GeneratOnPrompt::Sample reads.  temperature == 0 or top_k == 1 -> sample_argmax.
@@ -204,11 +228,14 @@ struct CHAT_SAMPLER {
 
 // The decode buffers of n sequences, allocated and filled together (Fish: one sequence; XcdReplicas: n_seq; XcdTP: its one sequence)
 struct SeqBuffers {
-    int32_t* d_state = nullptr;       // [n][4]: {token, pos, 0, 0} (XcdReplicas: {token, pos, parked, status})
-    int32_t* d_forced = nullptr;      // [n][n_ctx] teacher-forced ids, -1 = free running
-    int32_t* d_tokens_out = nullptr;  // [n][n_ctx] the id produced at each position
-    int AllocSeqs(kf_ctx* c, int n, int n_ctx, int tokens_fill);  // tokens_fill: the byte d_tokens_out starts as
-    void FreeSeqs(kf_ctx* c);
+    DevBuf<int32_t> d_state;       // [n][4]: {token, pos, 0, 0} (XcdReplicas: {token, pos, parked, status})
+    DevBuf<int32_t> d_forced;      // [n][n_ctx] teacher-forced ids, -1 = free running
+    DevBuf<int32_t> d_tokens_out;  // [n][n_ctx] the id produced at each position
+    int Alloc(kf_ctx* c, int n, int n_ctx, int tokens_fill) {  // tokens_fill: the byte d_tokens_out starts as
+        KF_TRY(d_state.AllocFilled(c, (size_t)n * 16, 0));
+        KF_TRY(d_forced.AllocFilled(c, (size_t)n * n_ctx * 4, 0xff));
+        return d_tokens_out.AllocFilled(c, (size_t)n * n_ctx * 4, tokens_fill);
+    }
 };
 
 // Tensor-parallel decode (no counterpart in the single-GPU reference, QKV.cu:503): this Fish holds ONE rank's shard -- the
@@ -217,13 +244,37 @@ struct SeqBuffers {
 struct TPState {
     int rank = 0, world = 1, vocab_row0 = 0;
     kf_tp_comm comm;
-    void* area = nullptr;
+    DevBuf<uint8_t> area;               // uncached (kf_tp_alloc): the receive area, the generation and error words, the push descriptors
     bool committed = false;             // kf_tp_commit done for the current peer set
     std::vector<void*> opened;          // IPC mappings of other processes' areas (closed with the Fish)
-    std::vector<kf_graph*> group_graphs;  // ranks of ONE process stepped in lock-step on one stream: rank 0 keeps the group's graphs, one per bucket
+    std::vector<hGraph> group_graphs;  // ranks of ONE process stepped in lock-step on one stream: rank 0 keeps the group's graphs, one per bucket
 };
 
-struct Fish : SeqBuffers {
+// the int8 activation rows (Fish::A8Ready): q [rows][max(q_dim, nEmbed, n_ff)], step [rows]
+struct A8Rows {
+    DevBuf<int8_t> q;
+    DevBuf<float> step;
+    int rows = 0;
+    int Alloc(kf_ctx* c, int n, size_t wide) {
+        KF_TRY(q.Alloc(c, wide * n));
+        KF_TRY(step.Alloc(c, (size_t)n * 4));
+        return rows = n, KF_OK;
+    }
+};
+// [8][.] activation rows of the verify pass and its scratch, allocated by the first Verify
+struct VerifyRows {
+    hGTensor vX, vQ, vAttn, vGate, v_attn_ws, v_head_ws;
+    DevBuf<int32_t> d_vtok;  // [8] the pass's ids, then [8] its greedy ids
+    int Alloc(kf_ctx* c, const MODEL_CARD& card, const kf_weight& head);
+};
+// The context: the FIRST base of Fish, so it is destroyed LAST -- after every member and base that frees device memory through it.
+struct CtxHolder {
+    kf_ctx* ctx = nullptr;
+    CtxHolder() = default;
+    CtxHolder(const CtxHolder&) = delete;
+    ~CtxHolder() { kf_destroy(ctx); }  // NULL (kf_init refused): nothing to do
+};
+struct Fish : CtxHolder, SeqBuffers {
     MODEL_CARD config;
     // The ways a layer can run (kf_host_modes.hpp: the one table of modes, of the pairs that do not combine and of what a refusal says).  Modes() is derived from the state
     // below, never stored; every entry that switches a mode ON asks Admit first (after its argument checks: a rejected call changes nothing), switching off is never
@@ -256,17 +307,15 @@ struct Fish : SeqBuffers {
     int TPPhase(int phase, int layer);
     int EnqueueStepTP();
     CHAT_SAMPLER samp_params;
-    uint64_t* d_rng = nullptr;  // LogitsInfo::rng_state on the device
+    DevBuf<uint64_t> d_rng;  // LogitsInfo::rng_state on the device
     int SetSampler(const CHAT_SAMPLER& s);  // also (re)seeds the device rng state
     int HeadAndPick(const floatX* x_last);  // [final norm + LM head] then arg-max or Sample, and the decode-state update
-    kf_ctx* ctx = nullptr;
     int fuse_level = 1;  // 0: one launch per reference kernel; 1: fused launches (5 per layer)
     // the layer loop of a decode step as one persistent launch (kf_engine_*): used by EnqueueStep when fuse_level >= 1, the model's shapes and
     // storage are served and the position bound is; otherwise the per-layer launches run.  Same arithmetic, bit for bit.
-    void* lin_scratch = nullptr;  // kf_set_scratch: workspace of the dequantise-then-multiply storages (AutoAWQ, row forms), sized when weights are set
-    size_t lin_scratch_bytes = 0;
-    void* deq_arena = nullptr;  // kf_set_dequant_arena: resident bf16 copies of the layers' quantised matrices for long prompts (EnsureResident)
-    size_t deq_arena_bytes = 0, resident_max_bytes = (size_t)16 << 30;
+    DevBuf<> lin_scratch;  // kf_set_scratch: workspace of the dequantise-then-multiply storages (AutoAWQ, row forms), sized when weights are set
+    DevBuf<> deq_arena;    // kf_set_dequant_arena: resident bf16 copies of the layers' quantised matrices for long prompts (EnsureResident)
+    size_t resident_max_bytes = (size_t)16 << 30;
     // OFF by default: the copies are keyed by the blobs' addresses, so a caller that hands weights over as device pointers (kfh_set_weight is_device = 1) and later
     // re-quantises or updates them IN PLACE would prefill on stale bf16 copies while the decode reads the live data.  kfh_set_prefill_resident opts in and takes that promise
     // ("the quantised data does not change under me"); kfh_weights_changed drops the copies (and the engine's table) after an in-place update.
@@ -277,8 +326,8 @@ struct Fish : SeqBuffers {
     int GrowScratch(size_t need);  // the kf_set_scratch workspace grown to `need` bytes (synchronises first; never shrinks)
     int EnsureLinearScratch(const kf_weight& w, int nTok) { return GrowScratch(kf_linear_scratch_bytes(&w, nTok)); }
     bool use_engine = true;
-    kf_engine* engine = nullptr;
-    void* engine_ws = nullptr;
+    hEngine engine;      // points into engine_ws and head_screen: ~Fish drops it (and the graphs) before the members go
+    DevBuf<> engine_ws;
     int engine_state = 0;  // 0 not tried, 1 built, -1 not served
     unsigned weights_gen = 0;  // counts DropEngine (a weight set again, kfh_weights_changed) and ModeChanged calls: engines other objects built on this Fish compare it with their own copy
     bool engine_embed = false;  // the engine reads the (bf16) embedding row itself
@@ -286,8 +335,7 @@ struct Fish : SeqBuffers {
     // The int8 screen of the in-launch head (kf_engine_set_head_screen): a derived copy of the head like the resident bf16 copies, so it is built only under the same promise
     // (prefill_resident: "the quantised data does not change under me"), counts against resident_max_bytes, and is dropped with the engine's table (kfh_weights_changed, a
     // weight set again) and when the promise is withdrawn.  The promise may arrive after the engine exists: RunSteps looks before every multi-step run.
-    void* head_screen = nullptr;
-    size_t head_screen_bytes = 0;
+    DevBuf<> head_screen;
     bool head_screen_tried = false;
     void EnsureHeadScreen();
     void DropHeadScreen();
@@ -311,12 +359,14 @@ struct Fish : SeqBuffers {
     std::vector<std::unique_ptr<FFN>> ffn;
     LayerNormal final_norm;
     Head4Token head;
-    float* rope_table = nullptr;  // device [n_ctx][hd/2][2]
+    DevBuf<float> rope_table;     // device [n_ctx][hd/2][2]
     int tok_pos = 0;              // hBatch->tok_pos
     bool graph_mode = false;      // launches take position/token from d_state
     bool state_tokens = false;    // eager per-kernel steps (fuse_level 0, e.g. AutoAWQ weights): position from the host, token from d_state
-    std::vector<kf_graph*> graphs;  // one per position bucket
-    std::vector<int> graph_bound;
+    std::vector<hGraph> graphs;   // one per position bucket
+    void DropGraphs() {           // every captured step graph (they hold the other arithmetic, pick, engine form or masks); the next step captures again
+        for (auto& g : graphs) g.reset();
+    }
     hGTensor x;                   // residual stream
 
     ~Fish();
@@ -344,7 +394,6 @@ struct Fish : SeqBuffers {
     // residual row are left exactly as Prefill(tokens, n, pos0) leaves them.  Argument checks and codes as Prefill's; n >= 2.
     int Score(const int* tokens, int n, int pos0, float* logprob_out, int* top1_out);
     int ScoreReady();  // PrefillReady + the scoring buffers, sized to the token-batch rows: allocated by the first Score, never inside a later one
-    void FreeScore();
     // the reference's perplexity loop: windows of at most `window` tokens (<= 0: n_ctx), each scored from position 0; sum, sum of squares and count of the log-probs in
     // fp64, ppl = exp(-sum / nz), pplerr = ppl * sqrt((ss - sum * sum / nz) / nz / nz) (Evaluate.cpp:64-80).  A trailing window of one token has no pair and is left out.
     int EvalPPL(const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored);
@@ -361,9 +410,7 @@ struct Fish : SeqBuffers {
     // (include/kf_abi.h "int8 activations for 4-bit layers": KF_Q4 group matrices that kf_linear_w4a8_status serves -> kf_linear_w4a8 / kf_linear_w4a8_tiles; their ZERO
     // need not be 0, the dequant arena is not consulted for them).
     bool act_int8 = false, act_int8_t = false, act_int8_q4 = false;
-    int8_t* a8_q = nullptr;     // [a8_rows][max(q_dim, nEmbed, n_ff)]
-    float* a8_step = nullptr;   // [a8_rows]
-    int a8_rows = 0;
+    A8Rows a8;
     // token batches of at least a8_tile_min rows send those matrices to kf_linear_a8_tiles (int8 MFMA tiles; the same bits), smaller ones and every single token to
     // kf_linear_a8; < 0: never.  kfh_set_a8_tile_min; the default is the tile plan's KF_A8_TILE_MIN.  a8_count: (tile, mat-vec) launches since the last switch-on.
     int a8_tile_min = KF_A8_TILE_MIN;
@@ -416,9 +463,8 @@ struct Fish : SeqBuffers {
     // one-token launches row by row: still the plain step's bits).  Eager, the position from the host; K / V rows pos0 .. pos0 + n - 1 are (re)written, d_state, the
     // residual row x and the logits row of the plain step are not touched.  Not a mode: it reads Modes() and refuses while any is on, and a sampler that is not greedy
     // (verify_refusal, kf_spec.hpp).  One device-to-host read (the n ids; the logits when asked for).
-    hGTensor vX, vQ, vAttn, vGate, vLogits, v_attn_ws, v_head_ws;  // [8][.] activation rows of the pass and its scratch, allocated by the first Verify
-    int32_t* d_vtok = nullptr;  // [8] the pass's ids, then [8] its greedy ids
-    int VerifyReady(bool logits);
+    VerifyRows vrows;
+    hGTensor vLogits;  // [8][vocab], allocated by the first Verify that asks for logits
     int Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits_or_null, std::string& why);
     int64_t verify_rows[2] = {0, 0};  // activation rows of the Verify passes' mat-vec entries served with the shared unpack / row by row (kf_rows_route_counts deltas)
 };
@@ -444,18 +490,20 @@ struct SpecDecoder {
 
 // What both XCD objects (XcdReplicas, XcdTP) own and do: the engine over the Fish's (ranks') weights and its workspace, the K / V rows, logits and residual streams of their
 // sequences, the sequences' buffers, the launches in runs of steps_per_launch, the check and the teardown.
-struct XcdEngine : SeqBuffers {
-    kf_ctx* ctx = nullptr;  // the (first) Fish's, not owned; set by Build
-    kf_xengine* engine = nullptr;
-    void* engine_ws = nullptr;
-    size_t engine_ws_bytes = 0;
+struct XcdSeqs : SeqBuffers {  // the K / V rows and per-sequence block of an XCD object: what XcdReplicas::MakeEngine(allocate) and XcdTP::Build make, all of it or none
     hGTensor key, val;      // [sequence or rank][n_layer][n_ctx][kv_dim] bf16
     hGTensor logits, x;     // [sequence][vocab], [sequence][nEmbed]
+    int Alloc(kf_ctx* c, const MODEL_CARD& card, int n_kv, int n_seq, int vocab);
+};
+struct XcdEngine : XcdSeqs {
+    kf_ctx* ctx = nullptr;  // the (first) Fish's, not owned; set by Build
+    DevBuf<> engine_ws;     // declared ahead of the engine that points into it: destroyed after it
+    hXEngine engine;
     std::string why;        // why the model is not served, "" when it is
     int steps_per_launch;
     explicit XcdEngine(int steps) : steps_per_launch(steps) {}
-    ~XcdEngine();
-    int EnsureWorkspace(size_t bytes);  // engine_ws of at least `bytes` (kept when large enough)
+    ~XcdEngine() { if (ctx) kf_sync(ctx); }  // a launch may still be running; then the engine, its workspace and the sequences' buffers go with the members, in that order
+    int EnsureWorkspace(size_t bytes) { return engine_ws && bytes <= engine_ws.bytes() ? KF_OK : engine_ws.Alloc(ctx, bytes); }  // kept when large enough; never while an engine points into it
     int LaunchSteps(int n);  // n greedy steps of every sequence, kf_xengine_steps in runs of at most steps_per_launch; no host sync
     int SetStepsPerLaunch(int n);
     int Check();          // synchronises; a timed-out hand-off is reported once (KF_INTERNAL_ERR) and the engine reset
@@ -471,7 +519,6 @@ struct XcdReplicas : XcdEngine {
     long long steps_run = 0;
     unsigned built_gen = 0;  // Fish::weights_gen the engine was built on
     XcdReplicas() : XcdEngine(32) {}
-    ~XcdReplicas();
     int Build(Fish* f, int n_seq_);
     int MakeEngine(bool allocate);
     int Fresh();          // re-creates the engine when the Fish's weights changed since it was built (kfh_weights_changed, a weight set again)
@@ -489,10 +536,13 @@ struct XcdReplicas : XcdEngine {
     // each prompt's last row.  What Fish::Chat's token-serial prefill loop (GoPT.cpp:1139-1146) does for one prompt, for S of them in the launches of one.
     int PrefillBatch(const int* slots, const int32_t* tokens, const int* lens, int S, int stride);
     int prefill_batch = 1;        // Chat: prompts prefilled together when several slots are free (1: one by one, the bits of Fish::Prefill)
-    hGTensor bK, bV, bL;          // [rows, kv_dim] K / V rows of a prompt batch before they are scattered; [n_seq, vocab] the batch's logits
-    void** d_dst = nullptr;       // [3][n_seq] device tables of the scatters' destinations (K, V, logits), then the batch's slots as int32
+    struct BatchRows {            // what PrefillBatch needs beside the Fish's token-batch buffers; regrown whole when a batch has more rows
+        hGTensor bK, bV, bL;      // [rows, kv_dim] K / V rows of a prompt batch before they are scattered; [n_seq, vocab] the batch's logits
+        DevBuf<void*> d_dst;      // [3][n_seq] device tables of the scatters' destinations (K, V, logits), then the batch's slots as int32
+        int Alloc(kf_ctx* c, int kv_dim, int rows, int vocab, int n_seq);
+    } pb;
     CHAT_SAMPLER samp_params;     // Chat's sampler (greedy by default); non-greedy: one launch per token, kf_sample per occupied slot
-    uint64_t* d_rng = nullptr;    // [n_seq] xorshift states, seeded per request (seed + request index)
+    DevBuf<uint64_t> d_rng;       // [n_seq] xorshift states, seeded per request (seed + request index)
     int SetSampler(const CHAT_SAMPLER& s);
     size_t kv_seq_elems() const;
 };

@@ -800,16 +800,12 @@ struct Loader {
     Fish* f;
     K_SafeTensors& st;
     std::string& err;
-    void* d_stage = nullptr;  // bf16 staging on the device, grown on demand
-    size_t stage_bytes = 0;
+    DevBuf<uint16_t> d_stage;  // bf16 staging on the device, grown on demand
     std::vector<uint16_t> h_conv;
 
     int fail(int code, const std::string& what) {
         err = what;
         return code;
-    }
-    ~Loader() {
-        if (d_stage) kf_free(f->ctx, d_stage);
     }
     // bf16 [ne0, ne1] of tensor `name` on the device (staging buffer); F16 / F32 sources are converted on the host
     int stage(const std::string& name, int ne0, int ne1, const uint16_t** d_out) {
@@ -832,14 +828,9 @@ struct Loader {
         } else if (t->dtype != "BF16") {
             return fail(KF_UNSUPPORTED_DATATYPE, "tensor '" + name + "': dtype " + t->dtype + " (BF16, F16 or F32 expected)");
         }
-        if (n * 2 > stage_bytes) {
-            if (d_stage) kf_free(f->ctx, d_stage);
-            d_stage = nullptr;
-            KF_TRY(kf_malloc(f->ctx, n * 2, &d_stage));
-            stage_bytes = n * 2;
-        }
+        if (n * 2 > d_stage.bytes()) KF_TRY(d_stage.Alloc(f->ctx, n * 2));
         KF_TRY(kf_h2d(f->ctx, d_stage, src, n * 2));
-        *d_out = reinterpret_cast<const uint16_t*>(d_stage);
+        *d_out = d_stage;
         return KF_OK;
     }
     // dense HF weight -> GTensor of type `tp` (quantise-on-load, GeQuant.cpp:144-200 -> RTN_x / YinYang on the device)
