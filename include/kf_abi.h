@@ -58,7 +58,10 @@ typedef struct kf_weight {
     int32_t qMin, qMax, qBias;
     /* Vendor AutoAWQ tensors (GTensor::qZero / qScale, GeQuant.cpp:410; CU_Q42X_awq quantizer.cu:131-156).  Both non-NULL select the
      * AWQ GEMM layout: type = KF_Q4, data = qweight int32 [ne1, ne0/8] (TRANSPOSED: input rows), qzeros int32 [ne1/128, ne0/8],
-     * qscales fp16 [ne1/128, ne0]; gama is unused.  Served by kf_linear and kf_dequant (which then writes [ne1, ne0], TransA = 0). */
+     * qscales fp16 [ne1/128, ne0]; gama is unused.  Served by kf_linear and kf_dequant (which then writes [ne1, ne0], TransA = 0).
+     * kf_linear from 16 token rows (16-byte aligned qweight, scales and x): one launch of MFMA tiles on the packed words, no scratch; the product sums in MFMA
+     * order, so a token-batch row equals the one-token entry within the token-batch bar, not bit for bit -- as for every other storage.  Fewer rows: the mat-vec
+     * per token row, which needs the scratch below. */
     const void* qzeros;
     const void* qscales;
     /* Quant card mode (QUANT_MODE, GeQuant.hpp).  0 = KF_QUANT_GROUP: everything above.  KF_QUANT_ROW_LUT: the row-codebook 4-bit storage of

@@ -420,7 +420,11 @@ int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const
     // otherwise one mat-vec launch per token row; which kernel, on which operand, is kf::gemm_plan's choice
     const kf_bf16* res = (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr;
     const kf::GemmPlan p = kf::gemm_plan(problem_of(c, kf::GE_LINEAR, 1, &w, nTok, x));
-    if (p.route == kf::GR_AWQ) { /* AutoAWQ layout: its own transposed mat-vec */
+    if (p.route == kf::GR_AWQ && p.k.fam == kf::GK_AWQ && !kf::g_knobs.awq_route) { /* AutoAWQ layout, a batch: one launch of its MFMA tiles, no scratch */
+        const int rc = kf::awq_tile_launch(c->stream, p.k, w, x, nTok, y, bias, alpha, beta, res);
+        return rc ? fail(rc, "kf_linear (AWQ token-batch tiles) failed with %d", rc) : KF_OK;
+    }
+    if (p.route == kf::GR_AWQ) { /* ... a few rows: its own transposed mat-vec, row by row */
         const size_t need = kf::awq_scratch_bytes(w);
         if (need > c->scratch_bytes || !c->scratch)
             return fail(KF_INVALID_ARGS, "kf_linear: the AWQ mat-vec needs %zu bytes of scratch (kf_linear_scratch_bytes), kf_set_scratch gave %zu", need, c->scratch_bytes);
@@ -2158,6 +2162,7 @@ int kfdbg_set_knob(const char* name, long value) {
     else if (!strcmp(name, "gemv_xf2")) k.gemv_xf2 = (int)value;
     else if (!strcmp(name, "score_route")) k.score_route = (int)value;
     else if (!strcmp(name, "score_form")) k.score_form = (int)value;
+    else if (!strcmp(name, "awq_route")) k.awq_route = (int)value;
     else return -1;
     return 0;
 }

@@ -102,7 +102,7 @@ __global__ void awq_dequant_kernel(const uint32_t* __restrict__ qweight, const u
     *reinterpret_cast<u32x4*>(out + (size_t)i * n_out + (size_t)wcol * 8) = u32x4{o[0], o[1], o[2], o[3]};
 }
 
-static int awq_check(const kf_weight* w) {
+int awq_check(const kf_weight* w) {
     if (!w->qzeros || !w->qscales || w->type != KF_Q4) return KF_QUANT_ERR;
     if (w->ne0 % 8 || w->ne1 % 128 || w->lGroup != 128) return KF_QUANT_ERR;
     return KF_OK;

@@ -39,12 +39,34 @@ struct G3Form {
 template <class C>
 constexpr G3Form g3_form() { return {C::BM, C::BN, C::NTH, 2 * C::STAGE, C::WGS_PER_CU}; }
 constexpr G3Form G3_FORMS[5] = {g3_form<G3Big>(), g3_form<G3Small>(), g3_form<G3Mid>(), g3_form<G3Tiny>(), g3_form<G3Wide>()};
+// kf_gemm_awq.hip: the AutoAWQ layout's tile, 8 WC word columns (outputs) x BT tokens over the whole of K, NW waves as WO (groups of WCU word columns) x WT (groups of TT
+// 16-token MFMA tiles) x WK (the 32-row k-steps of a stage of KS input rows, dealt round robin; > 1: summed through LDS in wave order).  A wave's MFMA step has 16 word
+// columns; a form with WCU < 16 leaves the others idle -- the narrow form trades them for workgroups over `out`.  LDS: two stages of raw words (rows padded by two words:
+// the four row octets of a step fall into different banks) and x rows (padded by 8 elements, as GM_XS), or the k-slices' partial sums.
+template <int WO_, int WT_, int WK_, int TT_, int WCU_, int KS_>
+struct AwqCfg {
+    static constexpr int WO = WO_, WT = WT_, WK = WK_, TT = TT_, WCU = WCU_, KS = KS_, NW = WO_ * WT_ * WK_, NTH = 64 * NW;
+    static constexpr int WC = WCU_ * WO_, BO = 8 * WC, BT = 16 * TT_ * WT_, WS = WC + 2, XS = KS_ + 8, VW = WC >= 4 ? 4 : WC; /* VW: words per load of a row segment */
+    static constexpr int W_BYTES = KS_ * WS * 4, STAGE = W_BYTES + BT * XS * 2, RED = (WK_ - 1) * WO_ * WT_ * 4 * WCU_ * 8 * TT_ * 4 * 4;
+    static constexpr int LDS = 2 * STAGE > RED ? 2 * STAGE : RED;
+    static_assert(KS_ % (32 * WK_) == 0 && 128 % KS_ == 0 && WC % VW == 0 && W_BYTES % 16 == 0 && (XS * 2) % 16 == 0, "AwqCfg");
+};
+using AwqNarrow = AwqCfg<1, 1, 4, 2, 2, 128>; /* 16 outputs x 32 tokens: a 1024-wide layer is 64 workgroups per token tile; four waves share a 128-row group */
+using AwqWide = AwqCfg<2, 2, 1, 4, 16, 64>;   /* 256 outputs (128 contiguous bytes of a qweight row) x 128 tokens; a wave: 128 x 64 */
+struct AwqForm {
+    int bo, bt, nth, lds;
+};
+template <class C>
+constexpr AwqForm awq_form() { return {C::BO, C::BT, C::NTH, C::LDS}; }
+constexpr AwqForm AWQ_NARROW = awq_form<AwqNarrow>(), AWQ_WIDE = awq_form<AwqWide>();
 constexpr size_t G3_SK_FLAG_BYTES = 8192; /* up to 2048 resident workgroups (64 x 64 tiles, eight per CU) */
 /* the split-K workspace: 256 partial 256 x 256 fp32 tiles + the flags in its last 8 KiB */
 constexpr size_t gemm3_sk_ws_bytes() { return (size_t)256 * G3_BM * G3_BN * 4 + G3_SK_FLAG_BYTES; }
 
 // ---- the route thresholds (token rows unless said otherwise)
 constexpr int GEMM_MIN = 8;             /* the MFMA tile kernels replace the per-token mat-vec loop */
+constexpr int AWQ_TILE_MIN = 16;        /* AutoAWQ layout: the kf_gemm_awq.hip tiles replace the per-row mat-vec loop (one MFMA token tile; above 8: an 8-token prompt keeps its bits) */
+constexpr int AWQ_WIDE_MIN = 128;       /* ... on 128-token tiles; below: 32-token tiles, as many workgroups over `out` as 16-output tiles give */
 constexpr int G3_FIRST = 256;           /* bf16 operands try the kf_gemm3.hip tiles before the 32 x 32 direct kernel (the direct kernel took 64 us for bf16 1024 x 2048 at 1024 rows) */
 constexpr int RESIDENT_MIN = 320;       /* with a dequant arena: the resident bf16 copies + the kf_gemm3.hip tiles (the 1024-row o_proj / down_proj of a long prompt) */
 constexpr int STACK_MIN = 1024;         /* without an arena: the stacked route, a dequantise per call */
@@ -78,7 +100,7 @@ struct GemmProblem {
 // ---- the plan: what the entry does
 enum GemmRoute {
     GR_MATVEC = 0,   /* one mat-vec launch per token row */
-    GR_AWQ,          /* the AutoAWQ mat-vec per token row */
+    GR_AWQ,          /* the AutoAWQ layout: k (GK_AWQ) on the packed words as they lie; k.fam == GK_NONE: its mat-vec per token row */
     GR_ROWFORM,      /* row forms: GetDataX into the scratch, then k on the copy (3- / 2-bit at any batch, k.fam == GK_NONE: the mat-vec loop on it; 4-bit row-LUT when
                         only the copy is tile-eligible) */
     GR_RESIDENT,     /* k on the weight's resident bf16 copy (kf_set_dequant_arena) */
@@ -92,13 +114,13 @@ enum GemmRoute {
     GR_KMAJOR,       /* backward: kf_gemm3.hip on the k-major operands as they lie */
     GR_TRANSPOSE     /* backward: the operands transposed into the scratch, then k */
 };
-enum GemmFamily { GK_NONE = 0, GK_DIRECT, GK_PAIRED, GK_STAGED, GK_G2, GK_G3 };
+enum GemmFamily { GK_NONE = 0, GK_DIRECT, GK_PAIRED, GK_STAGED, GK_G2, GK_G3, GK_AWQ };
 enum { DQ_NONE = 0, DQ_SCRATCH, DQ_ARENA, DQ_RESIDENT }; /* the copy: none, into the scratch, into the arena (kept), already in the arena */
 struct GemmKern {
     int fam;            /* GemmFamily; GK_NONE: no tile kernel takes the shape */
     int fmt;            /* FMT_* of the operand the kernel reads */
     int gshift;         /* log2(16-byte blocks per quantisation group) */
-    int form;           /* GK_DIRECT: 32- / 64-token tiles; GK_STAGED: KS 1 / 2; GK_G3: G3_BIG .. G3_WIDE */
+    int form;           /* GK_DIRECT: 32- / 64-token tiles; GK_STAGED: KS 1 / 2; GK_G3: G3_BIG .. G3_WIDE; GK_AWQ: 32- / 128-token tiles */
     int akm, bkm;       /* GK_G3: k-major A (weight) / B (token) operand */
     int gx, gy, block, lds;
     int sk;             /* GK_G3: the split-K form (gemm3_sk_kernel) with P tiles, S pieces, kp owner steps, R helper steps */
@@ -255,11 +277,21 @@ inline GemmPlan plan_of(int route, GemmKern k = GemmKern{}, int deq = DQ_NONE, l
     return p;
 }
 
+// the AutoAWQ tiles (kf_gemm_awq.hip) for qweight [K, M / 8] x n token rows: GK_NONE below AWQ_TILE_MIN rows, for operands that are not 16-byte aligned (data and scales:
+// mat_of) and for every shape awq_check refuses (the mat-vec route reports it)
+inline GemmKern awq_kern(const GemmMat& m, int n, bool x_al) {
+    GemmKern k = {};
+    if (n < AWQ_TILE_MIN || !x_al || !(m.al & GM_DATA_AL) || m.type != KF_Q4 || m.M < 8 || m.M % 8 || m.K < 128 || m.K % 128 || m.lgroup != 128) return k;
+    const AwqForm& f = n >= AWQ_WIDE_MIN ? AWQ_WIDE : AWQ_NARROW;
+    k.fam = GK_AWQ, k.fmt = FMT_Q4, k.form = f.bt, k.gx = (int)cdiv(m.M, f.bo), k.gy = (int)cdiv(n, f.bt), k.block = f.nth, k.lds = f.lds;
+    return k;
+}
+
 inline GemmPlan gemm_plan_linear(const GemmProblem& P) {
     const GemmMat& m = P.w[0];
     const long long bytes = (long long)m.M * m.K * 2;
     GemmKern k;
-    if (m.awq) return plan_of(GR_AWQ);
+    if (m.awq) return plan_of(GR_AWQ, awq_kern(m, P.n, P.x_al));
     if (m.quant != KF_QUANT_GROUP && m.type != KF_Q4) { /* 3- / 2-bit row forms: GetDataX into the scratch whatever the batch (the reference's own order) */
         if (P.n < GEMM_MIN || tile_plan(bf16_mat(m.M, m.K), P.n, P.x_al, 0, k) != 0) k = GemmKern{};
         return plan_of(GR_ROWFORM, k, DQ_SCRATCH, bytes);
@@ -419,5 +451,8 @@ int gemm3_swiglu_launch(hipStream_t st, const GemmKern& k, const uint16_t* Wilv,
 // GR_KMAJOR: y[n, M] = alpha * sum_k B(k, tok) A(k, m) + beta * y, A = w[K][lda] k-major, B = x[K][ldb] (k.bkm) or x[n][ldb]; ws lends the split-K slots
 int gemm3_km_launch(hipStream_t st, const GemmKern& k, const uint16_t* A, long long lda, const uint16_t* B, long long ldb, int n, int M, int K, uint16_t* y, long long ldy,
                     float alpha, float beta, void* ws);
+// GR_AWQ with k.fam == GK_AWQ (kf_gemm_awq.hip): y[n, ne0] from the AutoAWQ tensors as they are stored, x [n, ne1]; the layout's refusals are awq_check's
+int awq_tile_launch(hipStream_t st, const GemmKern& k, const kf_weight* w, const uint16_t* x, int n, uint16_t* y, const uint16_t* bias, float alpha, float beta,
+                    const uint16_t* residual);
 
 }  // namespace kf

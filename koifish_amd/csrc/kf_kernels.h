@@ -42,11 +42,12 @@ struct GemmMat {
     int type, quant, awq; /* kf_weight type and quant form; AutoAWQ layout (qzeros / qscales) */
     int M, K;             /* ne0, ne1 */
     int lgroup, gama;     /* group size; gama present */
-    int al;               /* GM_DATA_AL: data 16-byte aligned; GM_TAB_AL: the row tables (gama + ne0 + ne1) 16-byte aligned */
+    int al;               /* GM_DATA_AL: data (AutoAWQ layout: qweight and scales) 16-byte aligned; GM_TAB_AL: the row tables (gama + ne0 + ne1) 16-byte aligned */
 };
 inline GemmMat mat_of(const kf_weight* w) {
     const bool tab_al = w->gama && ((uintptr_t)(w->gama + w->ne0 + w->ne1) & 15) == 0;
-    return GemmMat{w->type, w->quant, w->qzeros || w->qscales, w->ne0, w->ne1, w->lGroup, w->gama != nullptr, (((uintptr_t)w->data & 15) == 0 ? GM_DATA_AL : 0) | (tab_al ? GM_TAB_AL : 0)};
+    const bool data_al = (((uintptr_t)w->data | (uintptr_t)w->qscales) & 15) == 0;
+    return GemmMat{w->type, w->quant, w->qzeros || w->qscales, w->ne0, w->ne1, w->lGroup, w->gama != nullptr, (data_al ? GM_DATA_AL : 0) | (tab_al ? GM_TAB_AL : 0)};
 }
 
 struct TpPushDev { /* one per (rank, exchange index), written once by kf_tp_commit */
@@ -128,6 +129,8 @@ struct Knobs {
     int q1_tab = 1;       /* 1-bit mat-vec through the LDS selector table (0: the per-bit select form; same bits) */
     int gemv_xf2 = 1;     /* canonical 4-bit rows too long for fp32 activations in 48 KiB of LDS: two windows of half the block columns (0: bf16 activations, widened per product) */
     int score_route = 0;  /* kf_head_logprob: 1 sends a head the fused route would take down the panel route (kf_score_plan.h; the two are compared by tests/test_gpu_score.py) */
+    int awq_route = 0;    /* kf_linear on the AutoAWQ layout: 1 sends a batch the tiles would take (kf_gemm_plan.h awq_kern) down the per-row mat-vec loop (compared by
+                             tests/test_gpu_awq_tiles.py, timed by scratch/ub_awq.py) */
     int score_form = -1;  /* kf_head_logprob's fused route: >= 0 the tile form (G3_BIG / G3_SMALL) instead of the rule's (scratch/ub_score.py measures both) */
 };
 extern Knobs g_knobs;
@@ -257,7 +260,8 @@ int quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src, int
 int lut_quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src);
 int lut_dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out);
 int lut_embed_launch(hipStream_t st, const kf_weight* w, int token, const int32_t* d_token, const int32_t* d_state, const int32_t* d_forced, uint16_t* out, int n_tok);
-// ---- AutoAWQ layout (kf_awq.hip)
+// ---- AutoAWQ layout (kf_awq.hip; the token-batch tiles: kf_gemm_awq.hip, launched through kf_gemm_plan.h)
+int awq_check(const kf_weight* w);
 size_t awq_scratch_bytes(const kf_weight* w);
 int awq_linear_launch(hipStream_t st, const kf_weight* w, const uint16_t* x, uint16_t* y, const uint16_t* bias, float alpha, float beta,
                       const uint16_t* residual, float* scratch);

@@ -255,11 +255,13 @@ class Context:
         return need
 
     def linear(self, w, x, bias=None, alpha=1.0, beta=0.0, residual=None, y=None):
-        y = torch.zeros(w.ne0, dtype=torch.bfloat16, device=self.device) if y is None else y
-        self.linear_scratch(w)
+        """x [in] -> y [out], or a token batch x [n, in] -> y [n, out] (kf_linear's nTok = n; residual and a prior y are [n, out] too)"""
+        n = 1 if x.dim() == 1 else x.shape[0]
+        y = torch.zeros(*((w.ne0,) if x.dim() == 1 else (n, w.ne0)), dtype=torch.bfloat16, device=self.device) if y is None else y
+        self.linear_scratch(w, n)
         d = w.desc()
         epi = L.KF_EPI_RESIDUAL if residual is not None else 0
-        L.check(self.hip.kf_linear(self.h, C.byref(d), _ptr(x), _ptr(y), _ptr(bias), 1, alpha, beta, epi, _ptr(residual)), "kf_linear")
+        L.check(self.hip.kf_linear(self.h, C.byref(d), _ptr(x), _ptr(y), _ptr(bias), n, alpha, beta, epi, _ptr(residual)), "kf_linear")
         return y
 
     def gama_backward(self, w, dIn, inp, g, scale=1.0):
