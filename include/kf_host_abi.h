@@ -68,6 +68,9 @@ int kfh_set_weight_lut(void* h, int layer, int slot, int ne0, int ne1, const voi
 int kfh_set_weight_lut_bits(void* h, int layer, int slot, int bits, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device);
 int kfh_tie_head(void* h);
 int kfh_set_norm(void* h, int layer, int slot, const void* w, int n, int is_device);
+int kfh_weight_layout(int type, int64_t ne0, int64_t ne1, int lGroup, int normal_float, int symmetric, int row_rtn, uint64_t* szData, uint64_t* szGama, int64_t* nGroup);
+int kfh_quant_card(int type, int symmetric, int normal_float, int* out4);
+int64_t kfhdbg_param_table(int dim, int n_layer, int n_head, int n_kv, int head_dim, int ffn, int vocab, int qk_norm, int tied, char* out, int64_t cap);
 int kfh_forward(void* h, int token, int pos, uint16_t* h_logits);
 int kfh_verify(void* h, const int* tokens, int n, int pos0, int* top1_out, uint16_t* logits_out);
 void* kfh_spec_create(void* target, int k);

@@ -370,7 +370,7 @@ int Fish::Build(const MODEL_CARD& card, int device, void* stream) {
         g_host_err = "Fish::Build: " + g_host_err;
         return KF_UNSUPPORTED_DATATYPE;
     }
-    config = card;
+    config = card, params = param_table(card);
     KF_TRY(kf_init(device, stream, &ctx));
     const int C = card.nEmbed, hd = card.head_dim, qd = card.n_head * hd, kvd = card.n_head_kv * hd;
     KF_TRY(cache.Init(ctx, card.nLayer, card.n_ctx, kvd));
@@ -449,6 +449,29 @@ bool Fish::HasRow3() const {
     return false;
 }
 SLP* Fish::LayerMatrix(int layer, int slot) const { return layer >= 0 && layer < config.nLayer && slot >= 0 && slot < 7 ? LayerMatrices(layer)[slot] : nullptr; }
+Fish::ParamRef Fish::Resolve(const Param& p) {
+    if (p.kind == P_EMBED) return {&embed.w, nullptr};
+    if (p.kind == P_HEAD) return {&head.proj.w, &head.proj};
+    if (p.kind == P_MATRIX) {
+        SLP* s = LayerMatrix(p.layer, p.slot);
+        return {&s->w, s};
+    }
+    if (p.layer < 0) return {&final_norm.w, nullptr};
+    SelfAttention* a = attn[p.layer].get();
+    LayerNormal* n[4] = {&a->norm, &ffn[p.layer]->norm, &a->normQ, &a->normK};
+    return {&n[p.slot]->w, nullptr};
+}
+int Fish::Install(const Param& p, const hGTensor& t, int scratch_rows) {
+    const ParamRef r = Resolve(p);
+    *r.t = t;
+    if (!r.slp) return KF_OK;
+    r.slp->nOut = t->ne[0], r.slp->nIn = t->ne[1];
+    return scratch_rows > 0 ? EnsureLinearScratch(t->desc(), scratch_rows) : KF_OK;
+}
+int Fish::TieHead() {
+    if (!embed.w) return KF_INVALID_ARGS;
+    return Install(params.back(), embed.w, 0);
+}
 
 // ---- int8 activations (kfh_set_act_int8, kfh_set_act_int8_q4)
 static const char* kf_last_error_hint(int st) {
@@ -1943,7 +1966,6 @@ int kfh_engine_only(void* h, int n) {
 // synchronises; KF_INTERNAL_ERR when one of the engine's hand-off polls has timed out
 int kfh_engine_check(void* h) { return reinterpret_cast<Fish*>(h)->EngineCheck(); }
 
-static SLP* slot_of(Fish* f, int layer, int slot) { return layer >= 0 ? f->LayerMatrix(layer, slot) : slot == 1 ? &f->head.proj : nullptr; }
 // the mode table without a device (tests/test_host_modes_cpu.py): mode_refusal / engine_refusal / eager_only for any set of active modes
 static int why_out(int rc, const std::string& why, char* out, size_t n) {
     if (out && n) std::snprintf(out, n, "%s", rc != KF_OK ? why.c_str() : "");
@@ -1960,91 +1982,98 @@ int kfhdbg_engine_refusal(unsigned active, char* why, size_t n) {
 }
 int kfhdbg_eager_only(unsigned active) { return eager_only(active) ? 1 : 0; }
 
-// slot: 0 q,1 k,2 v,3 o,4 gate,5 up,6 down (layer >= 0); layer = -1: slot 0 embed_tokens, 1 lm_head.
-// Either a host blob (`data||gama`, copied to a fresh device allocation) or an existing device pointer.
-static int set_weight_impl(void* h, int layer, int slot, int type, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device, int lGroup,
-                           int qMin, int qMax, int qBias, bool normal_float);
+// ---- the weight setters.  (layer, slot) names an entry of the parameter table (kf_params.hpp); the blob is a host `data||gama` (copied to a fresh device allocation)
+// or an existing device pointer.  Every check stands in front of the first change: a refused call leaves the Fish, its engine table and its captured graphs as they were.
+static int set_refused(const char* entry, int rc, const std::string& msg) {
+    g_host_err = std::string(entry) + ": " + msg;
+    return rc;
+}
+static int set_weight_impl(const char* entry, void* h, int layer, int slot, typNUMBER type, QuantCard card, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData,
+                           int is_device) {
+    Fish* f = reinterpret_cast<Fish*>(h);
+    const Param* p = find_param(f->params, false, layer, slot);
+    if (!p) return set_refused(entry, KF_INVALID_ARGS, "no weight at layer " + std::to_string(layer) + ", slot " + std::to_string(slot));
+    if (type == typNUMBER::Q3 && p->kind != P_MATRIX)
+        return set_refused(entry, KF_UNSUPPORTED_DATATYPE, "the embedding and the LM head stay bf16 or 4-bit (TokenEmbed::cuInfer asserts on Q3; no 3-bit head mat-vec): NF3 is for layer matrices");
+    const Fish::ParamRef r = f->Resolve(*p);
+    if (r.slp && r.slp->lora_a) /* the pair beside it was checked against the old matrix's sides */
+        return set_refused(entry, KF_INVALID_ARGS, "the matrix carries a low-rank adapter: clear the adapters first");
+    Layout lay;
+    hGTensor t = make_tensor<GTensor>(p->name, type, card, ne0, ne1, lay);
+    if (!t) return set_refused(entry, lay.code(KF_BLAS_UNALIGN), lay.why);
+    if (!lay.fits(szData, blob_bytes))
+        return set_refused(entry, KF_INVALID_ARGS, "szData / blob_bytes " + std::to_string(szData) + " / " + std::to_string(blob_bytes) + " do not fit the type, shape and quant card (" +
+                                                       std::to_string(lay.szData) + " / " + std::to_string(lay.bytes()) + ")");
+    KF_TRY(t->Take(f->ctx, blob, blob_bytes, is_device != 0));
+    f->DropEngine(); /* the engine's device table (and every captured graph) holds the old tensors' addresses */
+    return f->Install(*p, t, f->prefill_chunk);
+}
 int kfh_set_weight(void* h, int layer, int slot, int type, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device, int lGroup,
                    int qMin, int qMax, int qBias) {
-    return set_weight_impl(h, layer, slot, type, ne0, ne1, blob, blob_bytes, szData, is_device, lGroup, qMin, qMax, qBias, false);
+    QuantCard card = card_of((typNUMBER)type, false, false, lGroup);
+    card.qMin = qMin, card.qMax = qMax, card.qBias = qBias; /* the caller's range (symmetric or not) */
+    return set_weight_impl("kfh_set_weight", h, layer, slot, (typNUMBER)type, card, ne0, ne1, blob, blob_bytes, szData, is_device);
 }
 // the same for a tensor whose quant card says isNormalFloat (QUANT_MODE::RTNf): Q4 nibble stream || gama with a 16-entry table per row
 int kfh_set_weight_lut(void* h, int layer, int slot, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device) {
-    return set_weight_impl(h, layer, slot, (int)typNUMBER::Q4, ne0, ne1, blob, blob_bytes, szData, is_device, 0, 0, 15, 0, true);
+    return set_weight_impl("kfh_set_weight_lut", h, layer, slot, typNUMBER::Q4, card_of(typNUMBER::Q4, false, true, 0), ne0, ne1, blob, blob_bytes, szData, is_device);
 }
-// ... at `bits` per weight: 4 as above; 3 (RT_NormalF with bits == 3: an 8-entry table per row) for layer matrices only -- TokenEmbed::cuInfer asserts on Q3 and the LM
-// head forms do not unpack it.  A Fish holding such a matrix multiplies it from the packed stream: kf_set_row_unpack goes on for its own context (there is no earlier
-// behaviour to keep: the fused decode entries refused the storage)
+// ... at `bits` per weight: 4 as above; 3 (RT_NormalF with bits == 3: an 8-entry table per row) for layer matrices only.  A Fish holding such a matrix multiplies it from
+// the packed stream: kf_set_row_unpack goes on for its own context (there is no earlier behaviour to keep: the fused decode entries refused the storage)
 int kfh_set_weight_lut_bits(void* h, int layer, int slot, int bits, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device) {
     if (bits == 4) return kfh_set_weight_lut(h, layer, slot, ne0, ne1, blob, blob_bytes, szData, is_device);
-    if (bits != 3) {
-        g_host_err = "kfh_set_weight_lut_bits: normal-float row codebooks exist at 4 and 3 bits (RT_NormalF)";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    if (layer < 0) {
-        g_host_err = "kfh_set_weight_lut_bits: the embedding and the LM head stay bf16 or 4-bit (TokenEmbed::cuInfer asserts on Q3; no 3-bit head mat-vec): NF3 is for layer matrices";
-        return KF_UNSUPPORTED_DATATYPE;
-    }
-    if (ne1 % 128 != 0 || ne0 % 8 != 0) {
-        g_host_err = "kfh_set_weight_lut_bits: a 3-bit layer matrix needs ne1 % 128 == 0 and ne0 % 8 == 0 (whole 32-weight units per lane, 16-byte aligned row tables)";
-        return KF_BLAS_UNALIGN;
-    }
-    Fish* f = reinterpret_cast<Fish*>(h);
-    const int rc = set_weight_impl(h, layer, slot, (int)typNUMBER::Q3, ne0, ne1, blob, blob_bytes, szData, is_device, 0, 0, 7, 0, true);
-    return rc != KF_OK ? rc : kf_set_row_unpack(f->ctx, 1);
+    if (bits != 3) return set_refused("kfh_set_weight_lut_bits", KF_UNSUPPORTED_DATATYPE, "normal-float row codebooks exist at 4 and 3 bits (RT_NormalF)");
+    const int rc = set_weight_impl("kfh_set_weight_lut_bits", h, layer, slot, typNUMBER::Q3, card_of(typNUMBER::Q3, false, true, 0), ne0, ne1, blob, blob_bytes, szData, is_device);
+    return rc != KF_OK ? rc : kf_set_row_unpack(reinterpret_cast<Fish*>(h)->ctx, 1);
 }
-static int set_weight_impl(void* h, int layer, int slot, int type, int ne0, int ne1, const void* blob, size_t blob_bytes, size_t szData, int is_device, int lGroup,
-                           int qMin, int qMax, int qBias, bool normal_float) {
-    Fish* f = reinterpret_cast<Fish*>(h);
-    auto t = std::make_shared<GTensor>();
-    t->type = (typNUMBER)type, t->ne[0] = ne0, t->ne[1] = ne1;
-    t->szData = szData, t->szGama = blob_bytes - szData;
-    t->quant.T_group = lGroup, t->quant.qMin = qMin, t->quant.qMax = qMax, t->quant.qBias = qBias;
-    t->quant.isNormalFloat = normal_float;
-    KF_TRY(t->Take(f->ctx, blob, blob_bytes, is_device != 0));
-    f->DropEngine(); /* the engine's device table (and every captured graph) holds the old tensors' addresses */
-    if (layer < 0 && slot == 0) {
-        f->embed.w = t;
-        return KF_OK;
-    }
-    SLP* s = slot_of(f, layer, slot);
-    if (!s) return KF_INVALID_ARGS;
-    if (s->lora_a) { /* the pair beside it was checked against the old matrix's sides */
-        g_host_err = "kfh_set_weight: the matrix carries a low-rank adapter: clear the adapters first";
-        return KF_INVALID_ARGS;
-    }
-    s->w = t, s->nOut = ne0, s->nIn = ne1;
-    return f->EnsureLinearScratch(t->desc(), f->prefill_chunk); /* load time: the launches themselves never allocate */
-}
-// tie_word_embeddings: lm_head shares embed_tokens' tensor (Neuron.cpp:349-356)
 int kfh_tie_head(void* h) {
     Fish* f = reinterpret_cast<Fish*>(h);
     if (!f->embed.w) return KF_INVALID_ARGS;
     f->DropEngine();
-    f->head.proj.w = f->embed.w, f->head.proj.nOut = f->embed.w->ne[0], f->head.proj.nIn = f->embed.w->ne[1];
-    return KF_OK;
+    return f->TieHead();
 }
-// slot: 0 input_layernorm, 1 post_attention_layernorm, 2 q_norm, 3 k_norm; layer = -1: final norm.  bf16 [n]
+// bf16 [n]
 int kfh_set_norm(void* h, int layer, int slot, const void* w, int n, int is_device) {
     Fish* f = reinterpret_cast<Fish*>(h);
-    auto t = std::make_shared<GTensor>();
-    t->type = typNUMBER::BF16, t->ne[0] = n, t->szData = (size_t)n * 2;
-    KF_TRY(t->Take(f->ctx, w, (size_t)n * 2, is_device != 0));
+    const Param* p = find_param(f->params, true, layer, slot);
+    if (!p) return set_refused("kfh_set_norm", KF_INVALID_ARGS, "no norm at layer " + std::to_string(layer) + ", slot " + std::to_string(slot));
+    Layout lay;
+    hGTensor t = make_tensor<GTensor>(p->name, typNUMBER::BF16, QuantCard(), n, 1, lay);
+    if (!t) return set_refused("kfh_set_norm", lay.status, lay.why);
+    KF_TRY(t->Take(f->ctx, w, lay.szData, is_device != 0));
     f->DropEngine();
-    if (layer < 0) {
-        f->final_norm.w = t;
-        return KF_OK;
-    }
-    if (layer >= f->config.nLayer) return KF_INVALID_ARGS;
-    SelfAttention* a = f->attn[layer].get();
-    switch (slot) {
-        case 0: a->norm.w = t; break;
-        case 1: f->ffn[layer]->norm.w = t; break;
-        case 2: a->normQ.w = t; break;
-        case 3: a->normK.w = t; break;
-        default: return KF_INVALID_ARGS;
-    }
+    return f->Install(*p, t, 0);
+}
+
+// ---- the storage rule and the parameter table without a device (kf_storage.hpp, kf_params.hpp): what Python sizes its blobs by, and what the tests pin
+// type: a typNUMBER; normal_float: the row codebook of Q4 / Q3 / Q2; row_rtn (with normal_float, 2 bits): (zero, step) per row.  szData / szGama / nGroup are written
+// for KF_OK and for the row-shape refusal (KF_BLAS_UNALIGN: a stream the decode path does not multiply, operators may), zero otherwise; kfh_host_error says why
+int kfh_weight_layout(int type, int64_t ne0, int64_t ne1, int lGroup, int normal_float, int symmetric, int row_rtn, uint64_t* szData, uint64_t* szGama, int64_t* nGroup) {
+    QuantCard card = card_of((typNUMBER)type, symmetric != 0, normal_float != 0, lGroup);
+    card.isRowRTN = row_rtn != 0;
+    const Layout lay = layout_of(type < 0 || type > (int)typNUMBER::T_BINARY ? typNUMBER::T_SEQ : (typNUMBER)type, card, ne0, ne1); /* T_SEQ: served nowhere */
+    *szData = lay.szData, *szGama = lay.szGama, *nGroup = (int64_t)lay.nGroup;
+    return lay.status == KF_OK ? KF_OK : set_refused("kfh_weight_layout", lay.status, lay.why);
+}
+// out4: bits, qMin, qMax, qBias
+int kfh_quant_card(int type, int symmetric, int normal_float, int* out4) {
+    const QuantCard q = card_of((typNUMBER)type, symmetric != 0, normal_float != 0, 0);
+    out4[0] = q.bits, out4[1] = q.qMin, out4[2] = q.qMax, out4[3] = q.qBias;
     return KF_OK;
+}
+// the parameter table of a card as text, one line per entry a checkpoint of such a model stores: "name kind layer slot ne0 ne1 required"; qk_norm / tied: whether the
+// optional entries (q_norm / k_norm; lm_head) are there.  Returns the length needed (copy truncated to cap - 1)
+int64_t kfhdbg_param_table(int dim, int n_layer, int n_head, int n_kv, int head_dim, int ffn, int vocab, int qk_norm, int tied, char* out, int64_t cap) {
+    MODEL_CARD c;
+    c.nEmbed = dim, c.nLayer = n_layer, c.n_head = n_head, c.n_head_kv = n_kv, c.head_dim = head_dim, c.n_ff = ffn, c.vocab = vocab, c.tie_word_embeddings = tied != 0;
+    static const char* kKind[] = {"embed", "head", "norm", "matrix"};
+    std::string text;
+    for (const Param& p : param_table(c)) {
+        if (!p.required && (p.kind == P_HEAD ? head_is_tied(c, true) : !qk_norm)) continue;
+        text += p.name + " " + kKind[p.kind] + " " + std::to_string(p.layer) + " " + std::to_string(p.slot) + " " + std::to_string(p.ne0) + " " + std::to_string(p.ne1) + " " + (p.required ? "1" : "0") + "\n";
+    }
+    if (out && cap > 0) std::snprintf(out, (size_t)cap, "%s", text.c_str());
+    return (int64_t)text.size() + 1;
 }
 
 // one eager step; logits (bf16[vocab]) and hidden copied to host when non-null; returns the greedy id or < 0

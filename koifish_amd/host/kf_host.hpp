@@ -22,13 +22,13 @@
 #include "../../include/kf_abi.h"
 #include "kf_devbuf.hpp"
 #include "kf_host_modes.hpp"
+#include "kf_params.hpp"
 #include "kf_spec.hpp"
+#include "kf_storage.hpp"
 
 namespace koifish {
 
 using floatX = kf_bf16;
-enum class typNUMBER : uint8_t { F32 = 0, F64, F16, BF16, F8E5M2, F8E4M3, U8, I8, U16, I16, U32, I32, U64, I64, Q4, Q3, Q2, T_SIGN, T_SEQ, BOOL1, T_BINARY };
-
 struct Fish;
 
 // kf_graph / kf_engine / kf_xengine handles: destroyed by these deleters only.  A deleter does not synchronise: where an engine may still run, kf_sync stands at that site.
@@ -47,12 +47,6 @@ using hXEngine = std::unique_ptr<kf_xengine, HandleDel<kf_xengine_destroy>>;
         if (rc_ != KF_OK) return rc_; \
     } while (0)
 
-// Quant card fields that cross the kernel seam (QUANT_CARD / GeQuant, GeQuant.cpp:107-124)
-struct QuantCard {
-    int bits = 16, T_group = 128, qMin = 0, qMax = 0, qBias = 0;
-    bool isNormalFloat = false;  // QUANT_MODE::RTNf (GeQuant.cpp:853): row-codebook storage -> kf_weight.quant = KF_QUANT_ROW_LUT
-};
-
 // A device tensor: `data||gama` in one allocation, as huTensor::Alloc lays it out (GTensor.cpp:456-510).
 struct GTensor {
     std::string name;
@@ -66,7 +60,7 @@ struct GTensor {
     std::shared_ptr<GTensor> qZero, qScale;  // vendor AutoAWQ tensors (GeQuant.cpp:410): data = qweight [in, out/8]; ne = {out, in}
 
     size_t size() const { return (size_t)ne[0] * ne[1] * ne[2] * ne[3]; }
-    int nGroup() const { return (szGama && quant.T_group > 0) ? (int)(size() / quant.T_group) : 0; }
+    int nGroup() const { return szGama ? (int)group_count(quant, size()) : 0; }
     floatX* gama_T() const { return szGama ? reinterpret_cast<floatX*>(reinterpret_cast<uint8_t*>(data) + szData) : nullptr; }
     kf_weight desc() const;  // what TASKA_quant / TASKA_AxB hand to the kernels
     // SerialGamaData H2D (huTensor.cu:413-458): allocate and copy a host `data||gama` blob
@@ -168,12 +162,6 @@ struct Head4Token : GeNeuron {
     SLP proj;
     hGTensor preLogits;
     hGTensor cuInfer_1(hGTensor inp_, int flag = 0);
-};
-
-struct MODEL_CARD {  // the fields of CLI_params / MODEL_CARD this path reads (CLI_params.hpp, cases/qwen3/*.json)
-    int nEmbed = 0, nLayer = 0, n_head = 0, n_head_kv = 0, head_dim = 0, n_ff = 0, vocab = 0, n_ctx = 0;
-    float rms_eps = 1e-6f, qk_eps = 1e-6f, rope_theta = 1e6f;
-    bool tie_word_embeddings = true;
 };
 
 // token-batch (prefill) activations, [rows, .], allocated by the first Prefill and grown by a larger batch (Fish::PrefillReady)
@@ -428,6 +416,17 @@ struct Fish : CtxHolder, SeqBuffers {
     std::array<SLP*, 7> LayerMatrices(int layer) const;  // q k v o gate up down, the order of kf_engine_layer.w and of the C entries' slots
     bool HasRow3() const;  // a layer matrix is a 3-bit row codebook (NF3): per-layer launches with kf_set_row_unpack on; no engine, no XCD decoders, no Verify
     SLP* LayerMatrix(int layer, int slot) const;  // one of them, or NULL
+    // ---- the parameters (kf_params.hpp): the table of this model's card, and where an entry lives -- the tensor of a norm or the embedding, the SLP of a matrix or the head
+    std::vector<Param> params;
+    struct ParamRef {
+        hGTensor* t = nullptr;
+        SLP* slp = nullptr;
+    };
+    ParamRef Resolve(const Param& p);
+    // The one place a parameter enters the model.  A matrix or the head also takes its sides from the tensor and, with scratch_rows > 0, has the kf_set_scratch
+    // workspace grown to what kf_linear asks for that many token rows (load time: the launches themselves never allocate).  The callers drop the engine first.
+    int Install(const Param& p, const hGTensor& t, int scratch_rows);
+    int TieHead();  // lm_head shares embed_tokens' tensor
     int SetAdapter(int layer, int slot, const floatX* a, const floatX* b, int r, float s, std::string& why);
     void ClearAdapters();
     // What the eager-only layer bodies run for the matrices s[0 .. n_w) on the rows x [n][ldx = dim] (normed by norm_w first when given): y[i] [n][ne0], with `residual`

@@ -784,18 +784,6 @@ inline float half_to_f32(uint16_t h) {
     return f;
 }
 
-void quant_range(typNUMBER t, bool symmetric, QuantCard& q) {  // GeQuant ctor (GeQuant.cpp:107-124)
-    q.qMin = q.qMax = q.qBias = 0, q.bits = 16;
-    switch (t) {
-        case typNUMBER::Q4: q.bits = 4; if (symmetric) q.qMin = -8, q.qMax = 7, q.qBias = 8; else q.qMin = 0, q.qMax = 15; break;
-        case typNUMBER::Q3: q.bits = 3, q.qMin = 0, q.qMax = 7; break; /* the normal-float row form only (RT_NormalF with bits == 3) */
-        case typNUMBER::T_SIGN: q.bits = 2, q.qMin = -1, q.qMax = 1, q.qBias = 1; break;
-        case typNUMBER::BOOL1: case typNUMBER::T_BINARY: q.bits = 1, q.qMin = 0, q.qMax = 1; break;
-        case typNUMBER::F8E5M2: q.bits = 8; break;
-        default: break;
-    }
-}
-
 struct Loader {
     Fish* f;
     K_SafeTensors& st;
@@ -833,47 +821,21 @@ struct Loader {
         *d_out = d_stage;
         return KF_OK;
     }
-    // dense HF weight -> GTensor of type `tp` (quantise-on-load, GeQuant.cpp:144-200 -> RTN_x / YinYang on the device)
-    int dense(const std::string& name, int ne0, int ne1, typNUMBER tp, int lGroup, hGTensor* out) {
+    // dense HF weight -> GTensor of type `tp` with `card` (quantise-on-load, GeQuant.cpp:144-200 -> RTN_x / YinYang / RT_NormalF on the device)
+    int dense(const Param& p, typNUMBER tp, const QuantCard& card, hGTensor* out) {
         const uint16_t* d_src = nullptr;
-        KF_TRY(stage(name, ne0, ne1, &d_src));
-        auto t = std::make_shared<GTensor>();
-        t->name = name, t->type = tp, t->ne[0] = ne0, t->ne[1] = ne1;
-        quant_range(tp, false, t->quant);
-        t->quant.T_group = lGroup;
-        const size_t n = (size_t)ne0 * ne1;
+        KF_TRY(stage(p.name, p.ne0, p.ne1, &d_src));
+        Layout lay;
+        hGTensor t = make_tensor<GTensor>(p.name, tp, card, p.ne0, p.ne1, lay);
+        if (!t) return fail(lay.code(KF_QUANT_ERR), "tensor '" + p.name + "': " + lay.why);
+        KF_TRY(t->Alloc(f->ctx, lay.bytes()));
         if (tp == typNUMBER::BF16) {
-            t->szData = n * 2;
-            KF_TRY(t->Alloc(f->ctx, t->szData));
-            KF_TRY(kf_d2d(f->ctx, t->data, d_src, t->szData));
-        } else if (tp == typNUMBER::F8E5M2) {
-            t->szData = n;
-            KF_TRY(t->Alloc(f->ctx, t->szData));
-            kf_weight d = t->desc();
-            KF_TRY(kf_quantize(f->ctx, &d, d_src, 0));
-        } else if ((tp == typNUMBER::Q4 || tp == typNUMBER::Q3) && lGroup == 0) {
-            // quant card with isNormalFloat (QUANT_MODE::RTNf): GeQuant::RT_NormalF on the device -> nibble (3-bit) stream || [R][C][LUT ne0 x 16 (8)]
-            const int bits = t->quant.bits;
-            if (bits == 4 && ((ne1 % 32) || (ne0 % 8))) return fail(KF_QUANT_ERR, "tensor '" + name + "': the normal-float row form needs in % 32 == 0 and out % 8 == 0");
-            if (bits == 3 && ((ne1 % 128) || (ne0 % 8)))
-                return fail(KF_QUANT_ERR, "tensor '" + name + "': the 3-bit normal-float row form needs in % 128 == 0 and out % 8 == 0 (whole 32-weight units, aligned row tables)");
-            t->quant.isNormalFloat = true;
-            t->szData = n * bits / 8;
-            t->szGama = ((size_t)ne0 + ne1 + ((size_t)ne0 << bits)) * 2;
-            KF_TRY(t->Alloc(f->ctx, t->szData + t->szGama));
-            std::vector<uint16_t> ones((size_t)ne0 + ne1, 0x3F80);
-            KF_TRY(kf_h2d(f->ctx, t->gama_T(), ones.data(), ones.size() * 2));
-            kf_weight d = t->desc();
-            KF_TRY(kf_quantize(f->ctx, &d, d_src, 0));
+            KF_TRY(kf_d2d(f->ctx, t->data, d_src, lay.szData));
         } else {
-            if (lGroup <= 0) return fail(KF_QUANT_ERR, "tensor '" + name + "': group size " + std::to_string(lGroup));
-            if (n % (size_t)lGroup) return fail(KF_QUANT_ERR, "tensor '" + name + "': size is not a multiple of the group " + std::to_string(lGroup));
-            t->szData = n * t->quant.bits / 8;
-            const size_t nGroup = n / lGroup;
-            t->szGama = ((size_t)ne0 + ne1 + 2 * nGroup) * 2;
-            KF_TRY(t->Alloc(f->ctx, t->szData + t->szGama));
-            std::vector<uint16_t> ones((size_t)ne0 + ne1, 0x3F80);  // R_SCALE / C_SCALE = 1 (rc_normal = 0)
-            KF_TRY(kf_h2d(f->ctx, t->gama_T(), ones.data(), ones.size() * 2));
+            if (lay.szGama) { /* R_SCALE / C_SCALE = 1 (rc_normal = 0) */
+                std::vector<uint16_t> ones((size_t)p.ne0 + p.ne1, 0x3F80);
+                KF_TRY(kf_h2d(f->ctx, t->gama_T(), ones.data(), ones.size() * 2));
+            }
             kf_weight d = t->desc();
             KF_TRY(kf_quantize(f->ctx, &d, d_src, 0));
         }
@@ -900,27 +862,9 @@ struct Loader {
         KF_TRY(raw_copy(*qw, &t, typNUMBER::Q4));
         KF_TRY(raw_copy(*qz, &z, typNUMBER::I32));
         KF_TRY(raw_copy(*sc, &s, typNUMBER::F16));
-        t->ne[0] = n_out, t->ne[1] = n_in, t->quant.bits = 4, t->quant.T_group = 128, t->quant.qMin = 0, t->quant.qMax = 15, t->quant.qBias = 0;
+        t->ne[0] = n_out, t->ne[1] = n_in, t->quant = card_of(typNUMBER::Q4, false, false, 128);
         t->qZero = z, t->qScale = s;
         *out = t;
-        return KF_OK;
-    }
-    int linear(const std::string& prefix, int n_out, int n_in, typNUMBER tp, int lGroup, SLP* slot, bool* any_awq) {
-        hGTensor t;
-        if (st.Find(prefix + ".qweight")) {
-            KF_TRY(awq(prefix, n_out, n_in, &t));
-            *any_awq = true;
-        } else {
-            KF_TRY(dense(prefix + ".weight", n_out, n_in, tp, lGroup, &t));
-        }
-        slot->w = t, slot->nOut = n_out, slot->nIn = n_in;
-        return slot->hFish ? slot->hFish->EnsureLinearScratch(t->desc(), 1) : KF_OK; /* AutoAWQ tensors: the mat-vec's slice partials (one token, batches below 16 rows) live in caller-owned scratch */
-    }
-    int norm(const std::string& name, int n, LayerNormal* ln, bool required) {
-        if (!st.Find(name)) return required ? fail(KF_INVALID_ARGS, "tensor '" + name + "' not in the checkpoint") : KF_OK;
-        hGTensor t;
-        KF_TRY(dense(name, n, 1, typNUMBER::BF16, 128, &t));
-        ln->w = t;
         return KF_OK;
     }
 };
@@ -930,7 +874,6 @@ struct Loader {
 // HF directory -> Fish.  layer_type / head_type: what the dense matrices are quantised to on load (BF16 keeps them).
 Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_type, typNUMBER head_type, int lGroup, int max_seq, int* rc_out, std::string& err,
              bool layer_nf, bool head_nf) {
-    const int lGroupL = layer_nf ? 0 : lGroup, lGroupH = head_nf ? 0 : lGroup; /* 0: normal-float row codebooks (Loader::dense) */
     auto bail = [&](int rc, const std::string& what) -> Fish* {
         if (rc_out) *rc_out = rc;
         err = what;
@@ -977,35 +920,31 @@ Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_t
     rc = f->Build(card, device, stream);
     if (rc != KF_OK) return bail(rc, "Fish::Build failed");
     Loader L{f.get(), st, err};
-    const int C = card.nEmbed, qd = card.n_head * card.head_dim, kvd = card.n_head_kv * card.head_dim;
     bool any_awq = false;
-    auto check = [&](int r) { return r == KF_OK; };
-    hGTensor emb;
-    if (!check(rc = L.dense("model.embed_tokens.weight", card.vocab, C, head_type, lGroupH, &emb))) return bail(rc, err);
-    f->embed.w = emb;
-    if (card.tie_word_embeddings || !st.Find("lm_head.weight")) {
-        f->head.proj.w = emb, f->head.proj.nOut = card.vocab, f->head.proj.nIn = C;  // Neuron.cpp:349-356
-    } else {
-        hGTensor hw;
-        if (!check(rc = L.dense("lm_head.weight", card.vocab, C, head_type, lGroupH, &hw))) return bail(rc, err);
-        f->head.proj.w = hw, f->head.proj.nOut = card.vocab, f->head.proj.nIn = C;
-    }
-    if (!check(rc = L.norm("model.norm.weight", C, &f->final_norm, true))) return bail(rc, err);
-    for (int l = 0; l < card.nLayer; l++) {
-        const std::string p = "model.layers." + std::to_string(l) + ".";
-        SelfAttention* a = f->attn[l].get();
-        FFN* m = f->ffn[l].get();
-        if (!check(rc = L.norm(p + "input_layernorm.weight", C, &a->norm, true)) || !check(rc = L.norm(p + "post_attention_layernorm.weight", C, &m->norm, true)) ||
-            !check(rc = L.norm(p + "self_attn.q_norm.weight", card.head_dim, &a->normQ, false)) ||
-            !check(rc = L.norm(p + "self_attn.k_norm.weight", card.head_dim, &a->normK, false)) ||
-            !check(rc = L.linear(p + "self_attn.q_proj", qd, C, layer_type, lGroupL, &a->Q, &any_awq)) ||
-            !check(rc = L.linear(p + "self_attn.k_proj", kvd, C, layer_type, lGroupL, &a->K, &any_awq)) ||
-            !check(rc = L.linear(p + "self_attn.v_proj", kvd, C, layer_type, lGroupL, &a->V, &any_awq)) ||
-            !check(rc = L.linear(p + "self_attn.o_proj", C, qd, layer_type, lGroupL, &a->proj_cat, &any_awq)) ||
-            !check(rc = L.linear(p + "mlp.gate_proj", card.n_ff, C, layer_type, lGroupL, &m->gate, &any_awq)) ||
-            !check(rc = L.linear(p + "mlp.up_proj", card.n_ff, C, layer_type, lGroupL, &m->up, &any_awq)) ||
-            !check(rc = L.linear(p + "mlp.down_proj", C, card.n_ff, layer_type, lGroupL, &m->down, &any_awq)))
-            return bail(rc, err);
+    for (const Param& p : f->params) {
+        if (p.kind == P_HEAD && head_is_tied(card, st.Find(p.name))) {
+            f->TieHead();
+            continue;
+        }
+        if (!p.required && !st.Find(p.name)) continue;
+        const bool matrix = p.kind == P_MATRIX;
+        const std::string prefix = p.name.substr(0, p.name.size() - 7); /* without ".weight" */
+        hGTensor t;
+        if (p.kind == P_NORM) {
+            rc = L.dense(p, typNUMBER::BF16, card_of(typNUMBER::BF16, false, false, 128), &t);
+        } else if (matrix && st.Find(prefix + ".qweight")) { /* an AutoAWQ triple is taken as it is */
+            rc = L.awq(prefix, p.ne0, p.ne1, &t);
+            any_awq = true;
+        } else { /* quantise on load; the normal-float row codebooks have no groups */
+            const typNUMBER tp = matrix ? layer_type : head_type;
+            rc = L.dense(p, tp, card_of(tp, false, matrix ? layer_nf : head_nf, lGroup), &t);
+        }
+        // Scratch at load: the layer matrices for ONE row, the head for none -- what this loader has always asked for.  One row covers every need that does not depend
+        // on the batch (the AutoAWQ mat-vec's slice partials, the row forms' dequantised copy); the group forms' large-batch copy is lent by the stacked workspace
+        // Fish::PrefillReady sizes.  The scratch's size is an input of the GEMM plan (kf_gemm_plan.h: the copy target, the split-K slots), so asking for more here
+        // could move a route and with it the bits.
+        if (rc == KF_OK) rc = f->Install(p, t, matrix ? 1 : 0);
+        if (rc != KF_OK) return bail(rc, err);
     }
     if (any_awq) f->fuse_level = 0;  // the AutoAWQ layout has its own mat-vec (kf_linear only): one launch per reference kernel
     if (f->HasRow3() && (rc = kf_set_row_unpack(f->ctx, 1)) != KF_OK) return bail(rc, "kf_set_row_unpack failed"); /* 3-bit layers are multiplied from the packed stream */
@@ -1015,48 +954,17 @@ Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_t
 
 // ------------------------------------------------------------------------------------------------ Fish <-> .kun
 namespace {
-struct KunSlot {
-    std::string name;
-    hGTensor t;
-};
-// the parameters of the decode path under their Hugging Face names, in the order the neurons are built (embed, layers, final norm, head)
-std::vector<KunSlot> kun_params(Fish* f) {
-    std::vector<KunSlot> v;
-    v.push_back({"model.embed_tokens.weight", f->embed.w});
-    for (int l = 0; l < f->config.nLayer; l++) {
-        const std::string p = "model.layers." + std::to_string(l) + ".";
-        SelfAttention* a = f->attn[l].get();
-        FFN* m = f->ffn[l].get();
-        v.push_back({p + "input_layernorm.weight", a->norm.w});
-        v.push_back({p + "self_attn.q_proj.weight", a->Q.w});
-        v.push_back({p + "self_attn.k_proj.weight", a->K.w});
-        v.push_back({p + "self_attn.v_proj.weight", a->V.w});
-        if (a->normQ.w) v.push_back({p + "self_attn.q_norm.weight", a->normQ.w});
-        if (a->normK.w) v.push_back({p + "self_attn.k_norm.weight", a->normK.w});
-        v.push_back({p + "self_attn.o_proj.weight", a->proj_cat.w});
-        v.push_back({p + "post_attention_layernorm.weight", m->norm.w});
-        v.push_back({p + "mlp.gate_proj.weight", m->gate.w});
-        v.push_back({p + "mlp.up_proj.weight", m->up.w});
-        v.push_back({p + "mlp.down_proj.weight", m->down.w});
-    }
-    v.push_back({"model.norm.weight", f->final_norm.w});
-    if (f->head.proj.w && f->head.proj.w != f->embed.w) v.push_back({"lm_head.weight", f->head.proj.w});  // a tied head "isRefer" and is skipped (Serialize.cpp:936)
-    return v;
-}
 // "quantizer" section for one family of tensors (QUANT_CARD::Init, GeQuant.cpp:1231-1282: quant_method "RTN" -> RTN, "yyang" -> the ternary /
 // binary forms, anything else -> RTNf for 4 bits and F8Ex for 8)
 JSON quant_section(const GTensor& t) {
     JSON q = JSON::Object();
     const bool lowbit = t.type == typNUMBER::T_SIGN || t.type == typNUMBER::T_BINARY || t.type == typNUMBER::BOOL1;
     q["quant_method"] = JSON::Str(t.quant.isNormalFloat ? "NF" : lowbit ? "yyang" : t.type == typNUMBER::F8E5M2 ? "F8Ex" : "RTN");
-    QuantCard qc;
-    quant_range(t.type, false, qc);
-    q["bits"] = JSON::Int(qc.bits);
+    q["bits"] = JSON::Int(t.quant.bits);
     if (!t.quant.isNormalFloat && t.szGama) q["group_size"] = JSON::Int(t.quant.T_group);
     if (t.type == typNUMBER::Q4 && t.quant.qBias != 0) q["symmetric"] = JSON::Bool(true);  // ours: QUANT_CARD::isSymmetric is not a JSON key of the reference
     return q;
 }
-bool is_quant_type(typNUMBER t) { return t == typNUMBER::Q4 || t == typNUMBER::Q3 || t == typNUMBER::Q2 || t == typNUMBER::T_SIGN || t == typNUMBER::T_BINARY || t == typNUMBER::BOOL1; }
 }  // namespace
 
 // Fish -> `.kun` (the save branch of Fish::SAFETENSOR_Serialize, Serialize.cpp:911-963).  The config tensor carries what the reference's
@@ -1065,25 +973,28 @@ bool is_quant_type(typNUMBER t) { return t == typNUMBER::Q4 || t == typNUMBER::Q
 // reference takes from the Hugging Face card instead.
 int SaveKun(Fish* f, const std::string& path, std::string& err) {
     const MODEL_CARD& c = f->config;
-    std::vector<KunSlot> params = kun_params(f);
+    std::vector<hGTensor> saved;
     KunWriter w;
-    for (const auto& s : params) {
-        if (!s.t || !s.t->data) {
-            err = "tensor '" + s.name + "' is empty";  // "[ST_SERIALIZE] \"%s\" is empty!" (Serialize.cpp:634)
+    for (const Param& p : f->params) {
+        const hGTensor t = *f->Resolve(p).t;
+        if (!p.required && (!t || (p.kind == P_HEAD && t == f->embed.w))) continue;  // no q / k norm; a tied head "isRefer" and is skipped (Serialize.cpp:936)
+        if (!t || !t->data) {
+            err = "tensor '" + p.name + "' is empty";  // "[ST_SERIALIZE] \"%s\" is empty!" (Serialize.cpp:634)
             return KF_INVALID_ARGS;
         }
-        if (s.t->qZero || s.t->qScale) {
-            err = "tensor '" + s.name + "': vendor AutoAWQ tensors (explicit zeros / scales) are not written to .kun";
+        if (t->qZero || t->qScale) {
+            err = "tensor '" + p.name + "': vendor AutoAWQ tensors (explicit zeros / scales) are not written to .kun";
             return KF_UNSUPPORTED_DATATYPE;
         }
-        const char* dn = K_FLOATS_name((int)s.t->type);
+        const char* dn = K_FLOATS_name((int)t->type);
         if (!dn) {
-            err = "tensor '" + s.name + "': type has no K_FLOATS name";
+            err = "tensor '" + p.name + "': type has no K_FLOATS name";
             return KF_UNSUPPORTED_DATATYPE;
         }
-        std::vector<int64_t> shape = {s.t->ne[0]};
-        if (s.t->ne[1] > 1) shape.push_back(s.t->ne[1]);
-        w.Register(s.name, dn, shape, s.t->szData, s.t->szGama);
+        std::vector<int64_t> shape = {t->ne[0]};
+        if (t->ne[1] > 1) shape.push_back(t->ne[1]);
+        w.Register(p.name, dn, shape, t->szData, t->szGama);
+        saved.push_back(t);
     }
     JSON js = JSON::Object();
     js["vendor"] = JSON::Str("gruai");
@@ -1115,7 +1026,7 @@ int SaveKun(Fish* f, const std::string& path, std::string& err) {
     js["tokenizer"]["tokens"] = JSON::Str("");
     kf_ctx* ctx = f->ctx;
     KF_TRY(kf_sync(ctx));
-    return w.Save(path, js, [&](size_t i, void* dst, size_t n) { return kf_d2h(ctx, dst, params[i].t->data, n); }, err);  // SerialGamaData(toHost): data||gama in one copy
+    return w.Save(path, js, [&](size_t i, void* dst, size_t n) { return kf_d2h(ctx, dst, saved[i]->data, n); }, err);  // SerialGamaData(toHost): data||gama in one copy
 }
 
 // `.kun` -> Fish (SAFETENSOR2Gensors + SerialGamaData H2D, Serialize.cpp:965, huTensor.cu:413-458): the blobs go to the device as they are,
@@ -1147,8 +1058,9 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
     card.tie_word_embeddings = jp->bool_or("tie_word_embeddings", true);
     card.rope_theta = (float)jp->number_or("rope_theta", 1e6);
     card.rms_eps = card.qk_eps = (float)jp->number_or("rms_norm_eps", 1e-6);
-    const ST_Tensor* emb_t = st.Find("model.embed_tokens.weight");
-    if (!emb_t || emb_t->shape.size() != 2) return bail(KF_INVALID_ARGS, path + ": model.embed_tokens.weight missing");
+    const std::string emb_name = param_table(card).front().name; /* the embedding's rows give the vocabulary when the config does not */
+    const ST_Tensor* emb_t = st.Find(emb_name);
+    if (!emb_t || emb_t->shape.size() != 2) return bail(KF_INVALID_ARGS, path + ": " + emb_name + " missing");
     card.vocab = (int)cfg->path({"model"})->number_or("vocab_size", (double)emb_t->shape[0]);
     card.n_ctx = max_seq > 0 ? max_seq : ctx_len;
     if (card.nEmbed <= 0 || card.nLayer <= 0 || card.n_head <= 0 || card.n_head_kv <= 0 || card.head_dim <= 0 || card.n_ff <= 0 || card.vocab <= 0 || card.n_ctx <= 0)
@@ -1160,94 +1072,48 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
     rc = f->Build(card, device, stream);
     if (rc != KF_OK) return bail(rc, "Fish::Build failed");
     // one tensor: type from its K_FLOATS dtype, quant card from the quantizer section whose key its name contains (G_Has_, GeQuant.cpp:1231)
-    auto load = [&](const std::string& name, int ne0, int ne1, bool required, hGTensor* out) -> int {
-        const ST_Tensor* s = st.Find(name);
-        if (!s) {
-            if (!required) return KF_OK;
-            err = "tensor '" + name + "' not in " + path;
-            return KF_INVALID_ARGS;
-        }
+    auto load = [&](const Param& p, const ST_Tensor* s, hGTensor* out) -> int {
+        auto fail = [&](int code, const std::string& what) {
+            err = "tensor '" + p.name + "': " + what;
+            return code;
+        };
         const int tp = K_FLOATS_type(s->dtype);
-        const bool shape_ok = (s->shape.size() == 2 && s->shape[0] == ne0 && s->shape[1] == ne1) || (s->shape.size() == 1 && ne1 == 1 && s->shape[0] == ne0);
-        if (tp < 0 || !shape_ok) {
-            err = "tensor '" + name + "': unexpected dtype '" + s->dtype + "' or shape";
-            return KF_INVALID_ARGS;
-        }
-        auto t = std::make_shared<GTensor>();
-        t->name = name, t->type = (typNUMBER)tp, t->ne[0] = ne0, t->ne[1] = ne1;
-        t->szData = s->szData, t->szGama = s->szGama;
-        if (t->szData + t->szGama == 0) t->szData = s->end - s->begin;
+        const bool shape_ok = (s->shape.size() == 2 && s->shape[0] == p.ne0 && s->shape[1] == p.ne1) || (s->shape.size() == 1 && p.ne1 == 1 && s->shape[0] == p.ne0);
+        if (tp < 0 || !shape_ok) return fail(KF_INVALID_ARGS, "unexpected dtype '" + s->dtype + "' or shape");
+        const typNUMBER type = (typNUMBER)tp;
         const JSON* sec = nullptr;
         if (jq)
             for (const auto& kv : jq->obj)
-                if (kv.second.kind == JSON::OBJ && !kv.first.empty() && kv.first[0] != '#' && name.find(kv.first) != std::string::npos) sec = &kv.second;
-        quant_range(t->type, sec && sec->bool_or("symmetric", false), t->quant);
-        t->quant.T_group = sec ? (int)sec->number_or("group_size", group_dflt) : group_dflt;
-        if (sec && (t->type == typNUMBER::Q4 || t->type == typNUMBER::Q3)) {
+                if (kv.second.kind == JSON::OBJ && !kv.first.empty() && kv.first[0] != '#' && p.name.find(kv.first) != std::string::npos) sec = &kv.second;
+        bool nf = false;
+        if (sec && (type == typNUMBER::Q4 || type == typNUMBER::Q3)) {
             const JSON* m = sec->get("quant_method");
             const std::string ms = m && m->kind == JSON::STR ? m->str : "";
-            t->quant.isNormalFloat = ms.find("RTN") == std::string::npos && ms.find("AWQ") == std::string::npos && ms.find("yyang") == std::string::npos &&
-                                     ms.find("bitnet") == std::string::npos;  // GeQuant.cpp:1271-1279
+            nf = ms.find("RTN") == std::string::npos && ms.find("AWQ") == std::string::npos && ms.find("yyang") == std::string::npos && ms.find("bitnet") == std::string::npos;  // GeQuant.cpp:1271-1279
         }
-        const size_t n = (size_t)ne0 * ne1;
-        size_t want_data = n * 2, want_gama = 0;
-        if (t->type == typNUMBER::Q3 && (!t->quant.isNormalFloat || name.find("layers.") == std::string::npos || (ne1 % 128) || (ne0 % 8))) {
-            err = "tensor '" + name + "': Q<3> is served as the normal-float row form (quant_method \"NF\") of a layer matrix with in % 128 == 0 and out % 8 == 0";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        if (is_quant_type(t->type)) {
-            want_data = n * t->quant.bits / 8;
-            if (t->quant.isNormalFloat) {
-                t->quant.T_group = 0;
-                want_gama = ((size_t)ne0 + ne1 + ((size_t)ne0 << t->quant.bits)) * 2;
-            } else {
-                if (t->quant.T_group <= 0 || n % (size_t)t->quant.T_group) {
-                    err = "tensor '" + name + "': group size " + std::to_string(t->quant.T_group);
-                    return KF_QUANT_ERR;
-                }
-                want_gama = ((size_t)ne0 + ne1 + 2 * (n / t->quant.T_group)) * 2;
-            }
-        } else if (t->type == typNUMBER::F8E5M2) {
-            want_data = n;
-        } else if (t->type != typNUMBER::BF16) {
-            err = "tensor '" + name + "': dtype '" + s->dtype + "' is not served by the decode path";
-            return KF_UNSUPPORTED_DATATYPE;
-        }
-        if (t->szData != want_data || t->szGama != want_gama) {
-            err = "tensor '" + name + "': szData/szGama " + std::to_string(t->szData) + "/" + std::to_string(t->szGama) + " do not fit its type, shape and quant card (" +
-                  std::to_string(want_data) + "/" + std::to_string(want_gama) + ")";
-            return KF_INVALID_ARGS;
-        }
-        KF_TRY(t->LoadBlob(f->ctx, st.Data(*s), t->szData + t->szGama));
+        if (type == typNUMBER::Q3 && (!nf || p.kind != P_MATRIX)) return fail(KF_UNSUPPORTED_DATATYPE, "Q<3> is served as the normal-float row form (quant_method \"NF\") of a layer matrix");
+        const QuantCard card = card_of(type, sec && sec->bool_or("symmetric", false), nf, sec ? (int)sec->number_or("group_size", group_dflt) : group_dflt);
+        Layout lay;
+        hGTensor t = make_tensor<GTensor>(p.name, type, card, p.ne0, p.ne1, lay);
+        if (!t) return fail(lay.code(KF_UNSUPPORTED_DATATYPE), lay.why);
+        const size_t szData = s->szData + s->szGama ? s->szData : s->end - s->begin, szGama = s->szGama;
+        if (szData != lay.szData || szGama != lay.szGama)
+            return fail(KF_INVALID_ARGS, "szData/szGama " + std::to_string(szData) + "/" + std::to_string(szGama) + " do not fit its type, shape and quant card (" +
+                                             std::to_string(lay.szData) + "/" + std::to_string(lay.szGama) + ")");
+        KF_TRY(t->LoadBlob(f->ctx, st.Data(*s), lay.bytes()));
         *out = t;
         return KF_OK;
     };
-    auto linear = [&](const std::string& name, int n_out, int n_in, SLP* slot) -> int {
+    for (const Param& p : f->params) {
+        const ST_Tensor* s = st.Find(p.name);
+        if (p.kind == P_HEAD && head_is_tied(card, s)) {
+            f->TieHead();
+            continue;
+        }
+        if (!s && !p.required) continue;
+        if (!s) return bail(KF_INVALID_ARGS, "tensor '" + p.name + "' not in " + path);
         hGTensor t;
-        KF_TRY(load(name, n_out, n_in, true, &t));
-        slot->w = t, slot->nOut = n_out, slot->nIn = n_in;
-        return f->EnsureLinearScratch(t->desc(), f->prefill_chunk);
-    };
-    const int C = card.nEmbed, qd = card.n_head * card.head_dim, kvd = card.n_head_kv * card.head_dim;
-    auto ok = [&](int r) { return (rc = r) == KF_OK; };
-    if (!ok(load("model.embed_tokens.weight", card.vocab, C, true, &f->embed.w))) return bail(rc, err);
-    if (st.Find("lm_head.weight")) {
-        if (!ok(linear("lm_head.weight", card.vocab, C, &f->head.proj))) return bail(rc, err);
-    } else {
-        f->head.proj.w = f->embed.w, f->head.proj.nOut = card.vocab, f->head.proj.nIn = C;
-    }
-    if (!ok(load("model.norm.weight", C, 1, true, &f->final_norm.w))) return bail(rc, err);
-    for (int l = 0; l < card.nLayer; l++) {
-        const std::string p = "model.layers." + std::to_string(l) + ".";
-        SelfAttention* a = f->attn[l].get();
-        FFN* m = f->ffn[l].get();
-        if (!ok(load(p + "input_layernorm.weight", C, 1, true, &a->norm.w)) || !ok(load(p + "post_attention_layernorm.weight", C, 1, true, &m->norm.w)) ||
-            !ok(load(p + "self_attn.q_norm.weight", card.head_dim, 1, false, &a->normQ.w)) || !ok(load(p + "self_attn.k_norm.weight", card.head_dim, 1, false, &a->normK.w)) ||
-            !ok(linear(p + "self_attn.q_proj.weight", qd, C, &a->Q)) || !ok(linear(p + "self_attn.k_proj.weight", kvd, C, &a->K)) ||
-            !ok(linear(p + "self_attn.v_proj.weight", kvd, C, &a->V)) || !ok(linear(p + "self_attn.o_proj.weight", C, qd, &a->proj_cat)) ||
-            !ok(linear(p + "mlp.gate_proj.weight", card.n_ff, C, &m->gate)) || !ok(linear(p + "mlp.up_proj.weight", card.n_ff, C, &m->up)) ||
-            !ok(linear(p + "mlp.down_proj.weight", C, card.n_ff, &m->down)))
-            return bail(rc, err);
+        if ((rc = load(p, s, &t)) != KF_OK || (rc = f->Install(p, t, f->prefill_chunk)) != KF_OK) return bail(rc, err);
     }
     if (f->HasRow3() && (rc = kf_set_row_unpack(f->ctx, 1)) != KF_OK) return bail(rc, "kf_set_row_unpack failed"); /* 3-bit layers are multiplied from the packed stream */
     if (rc_out) *rc_out = KF_OK;

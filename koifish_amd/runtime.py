@@ -15,15 +15,22 @@ SLOTS = ("q", "k", "v", "o", "gate", "up", "down")
 NORMS = ("norm_in", "norm_post", "qn", "kn")
 
 
-def quant_range(type_, symmetric=False):
-    """qMin, qMax, qBias as the GeQuant ctor sets them (GeQuant.cpp:107-124)."""
-    if type_ == L.T_SIGN:
-        return -1, 1, 1
-    if type_ in (L.BOOL1, L.T_BINARY):
-        return 0, 1, 0
-    if type_ == L.Q4:
-        return (-8, 7, 8) if symmetric else (0, 15, 0)
-    return 0, 0, 0
+def quant_range(type_, symmetric=False, normal_float=False):
+    """qMin, qMax, qBias as the GeQuant ctor sets them (GeQuant.cpp:107-124): the library's card (kfh_quant_card)."""
+    v = (C.c_int * 4)()
+    L.check(L.load()[1].kfh_quant_card(int(type_), int(bool(symmetric)), int(bool(normal_float)), v), "kfh_quant_card")
+    return v[1], v[2], v[3]
+
+
+def weight_layout(type_, ne0, ne1, lGroup=0, normal_float=False, symmetric=False, row_rtn=False):
+    """(szData, szGama, nGroup) of a stored weight: the library's one storage rule (kfh_weight_layout; no device).  A row form whose shape the decode path refuses
+    (KF_BLAS_UNALIGN) still has its sizes: the operators take such a stream.  Any other refusal raises with the library's reason."""
+    host = L.load()[1]
+    d, g, n = C.c_uint64(), C.c_uint64(), C.c_int64()
+    rc = host.kfh_weight_layout(int(type_), int(ne0), int(ne1), int(lGroup), int(bool(normal_float)), int(bool(symmetric)), int(bool(row_rtn)), C.byref(d), C.byref(g), C.byref(n))
+    if rc not in (0, -2000):
+        raise L.KFError("kfh_weight_layout failed: code %d: %s" % (rc, host.kfh_host_error().decode()))
+    return d.value, g.value, n.value
 
 
 def perplexity_from_logprobs(logprobs):
@@ -43,21 +50,14 @@ class DevWeight:
 
     def __init__(self, type_, ne0, ne1, blob, lGroup=128, symmetric=False):
         self.type, self.ne0, self.ne1, self.blob, self.lGroup = type_, ne0, ne1, blob, lGroup
-        bits = L.BITS[type_]
-        self.szData = ne0 * ne1 * bits // 8
-        self.quantised = bits < 8
-        self.nGroup = ne0 * ne1 // lGroup if self.quantised else 0
-        self.szGama = (ne0 + ne1 + 2 * self.nGroup) * 2 if self.quantised else 0
+        self.szData, self.szGama, self.nGroup = weight_layout(type_, ne0, ne1, lGroup)
+        self.quantised = self.szGama > 0
         assert blob.numel() == self.szData + self.szGama, (blob.numel(), self.szData, self.szGama)
         self.qMin, self.qMax, self.qBias = quant_range(type_, symmetric)
 
     @staticmethod
     def blob_bytes(type_, ne0, ne1, lGroup=128):
-        bits = L.BITS[type_]
-        n = ne0 * ne1 * bits // 8
-        if bits < 8:
-            n += (ne0 + ne1 + 2 * (ne0 * ne1 // lGroup)) * 2
-        return n
+        return sum(weight_layout(type_, ne0, ne1, lGroup)[:2])
 
     def desc(self):
         p = self.blob.data_ptr()
@@ -91,17 +91,17 @@ class LutDevWeight:
     def __init__(self, ne0, ne1, blob, bits=4, rtn=False):
         self.type, self.ne0, self.ne1, self.blob, self.lGroup = {4: L.Q4, 3: L.Q3, 2: L.Q2}[bits], ne0, ne1, blob, 0
         self.bits, self.rtn = bits, rtn
-        self.szData = ne0 * ne1 * bits // 8
-        self.szGama = (ne0 + ne1 + (2 if rtn else 1 << bits) * ne0) * 2
+        self.szData, self.szGama, _ = weight_layout(self.type, ne0, ne1, normal_float=True, row_rtn=rtn)
+        self.qMin, self.qMax, self.qBias = quant_range(self.type, normal_float=True)
         assert blob.numel() == self.szData + self.szGama, (blob.numel(), self.szData, self.szGama)
 
     @staticmethod
     def blob_bytes(ne0, ne1, bits=4):
-        return ne0 * ne1 * bits // 8 + (ne0 + ne1 + (1 << bits) * ne0) * 2
+        return sum(weight_layout({4: L.Q4, 3: L.Q3, 2: L.Q2}[bits], ne0, ne1, normal_float=True)[:2])
 
     def desc(self):
         p = self.blob.data_ptr()
-        return L.Weight(p, p + self.szData, self.type, self.ne0, self.ne1, 0, 0, 0, (1 << self.bits) - 1, 0, None, None,
+        return L.Weight(p, p + self.szData, self.type, self.ne0, self.ne1, 0, 0, self.qMin, self.qMax, self.qBias, None, None,
                         L.QUANT_ROW_RTN if self.rtn else L.QUANT_ROW_LUT, 0)
 
     def algorithmic_bytes(self):
@@ -119,9 +119,10 @@ class AWQDevWeight:
     def __init__(self, n_out, n_in, qweight, qzeros, scales):
         self.type, self.ne0, self.ne1, self.lGroup = L.Q4, n_out, n_in, 128
         self.qweight, self.qzeros, self.scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+        self.qMin, self.qMax, self.qBias = quant_range(L.Q4)
 
     def desc(self):
-        return L.Weight(self.qweight.data_ptr(), None, L.Q4, self.ne0, self.ne1, self.ne0 * self.ne1 // 128, 128, 0, 15, 0, self.qzeros.data_ptr(),
+        return L.Weight(self.qweight.data_ptr(), None, L.Q4, self.ne0, self.ne1, self.ne0 * self.ne1 // 128, 128, self.qMin, self.qMax, self.qBias, self.qzeros.data_ptr(),
                         self.scales.data_ptr())
 
     def algorithmic_bytes(self):
