@@ -19,6 +19,7 @@
 #include "kf_gemv_plan.h"
 #include "kf_gemv_rows_plan.h"
 #include "kf_score_plan.h"
+#include "kf_linear_bwd_plan.h"
 #include "kf_gama_plan.h"
 #include "kf_lora_plan.h"
 #include "kf_gradnorm_plan.h"
@@ -115,7 +116,6 @@ int kf_init(int device, void* stream, kf_ctx** out) {
     *out = c;
     return KF_OK;
 }
-static size_t up256z(size_t v) { return (v + 255) & ~(size_t)255; }
 // the resident copy of n_w matrices in `form` (kf_set_dequant_arena), or NULL: a lookup, nothing is launched or filled
 static const uint16_t* arena_find(const kf_ctx* c, int n_w, const kf_weight* const* w, int form) {
     if (!c->arena) return nullptr;
@@ -138,7 +138,7 @@ static int deq_copies(kf_ctx* c, const kf::GemmPlan& p, int n_w, const kf_weight
     for (int i = 0; i < n_w; i++) {
         const int r = p.deq_form == kf::DEQ_ILV ? kf::dequant_launch(c->stream, w[i], (uint16_t*)dst, n_w, i) : kf::dequant_launch(c->stream, w[i], (uint16_t*)(dst + off));
         if (r != KF_OK) return r < 0 ? r : KF_HIP_CHECK;
-        off += up256z((size_t)w[i]->ne0 * w[i]->ne1 * 2);
+        off += (size_t)kf::up256((long long)w[i]->ne0 * w[i]->ne1 * 2);
     }
     if (p.deq == kf::DQ_ARENA) {
         kf_ctx::DeqCopy e;
@@ -1259,79 +1259,22 @@ int kf_gelu(kf_ctx* c, const kf_bf16* x, kf_bf16* y, size_t n) {
     if (!x || !y || n == 0) return fail(KF_INVALID_ARGS, "kf_gelu: bad args");
     RET(kf::gelu_launch(c->stream, x, y, n));
 }
-// scratch layout of kf_linear_backward: [W bf16 OC*IC][middle][bias slabs fp64 ceil(n/256)*OC], each 256-B aligned; the middle region is either the transposed copies
-// [W^T bf16 IC*OC][deltaIn^T bf16 OC*n][inp^T bf16 IC*n] of the small-shape path or the partial-tile slots of the large tile kernel's stream-K form (kf_gemm3.hip)
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-static size_t lbw_mid_bytes(int OC, int IC, int n) {
-    const size_t t = up256((size_t)OC * IC * 2) + up256((size_t)OC * n * 2) + up256((size_t)IC * n * 2), k = up256(kf::gemm3_sk_ws_bytes());
-    return t > k ? t : k;
-}
-size_t kf_linear_backward_scratch_bytes(int OC, int IC, int n) {
-    if (OC < 1 || IC < 1 || n < 1) return 0;
-    return up256((size_t)OC * IC * 2) + lbw_mid_bytes(OC, IC, n) + up256((size_t)((n + 255) / 256) * OC * 8);
-}
+// kf_linear_backward: the shapes served, the scratch regions and both products are kf::linear_bwd_plan's (kf_linear_bwd_plan.h); the launches: kf_linear_bwd.hip
+size_t kf_linear_backward_scratch_bytes(int OC, int IC, int n) { return (size_t)kf::linear_bwd_plan(kf::LinearBwdProblem{kf::bf16_mat(OC, IC), n, 1, 1, 1}).bytes; }
 int kf_linear_backward(kf_ctx* c, const kf_weight* w, const kf_bf16* deltaIn, const kf_bf16* inp, kf_bf16* delta, kf_bf16* gW, kf_bf16* gBias, int n, int accumulate_delta,
                        void* scratch) {
+    static const char* const refused[] = {"", "AutoAWQ-layout weights are inference-only", "nothing to compute",
+                                          "OC (and n, for the weight gradient) must be multiples of 64 and >= 128, IC a multiple of 8, n >= 1",
+                                          "input-gradient GEMM not covered", "weight-gradient GEMM not covered"}; /* by kf::LinearBwdRefusal */
     CHKCTX(c);
     int r = check_weight(w, "kf_linear_backward");
     if (r) return r;
-    if (w->qzeros) return fail(KF_UNSUPPORTED_DATATYPE, "kf_linear_backward: AutoAWQ-layout weights are inference-only");
-    if (!deltaIn || !scratch || n < 1) return fail(KF_INVALID_ARGS, "kf_linear_backward: null deltaIn / scratch or n < 1");
-    if ((gW && !inp) || (!delta && !gW && !gBias)) return fail(KF_INVALID_ARGS, "kf_linear_backward: gW needs inp; nothing to compute");
-    const int OC = w->ne0, IC = w->ne1;
-    // the MFMA kernels contract over multiples of 64 and want 16-byte aligned rows
-    if ((OC % 64) || OC < 128 || (IC % 8) || (gW && ((n % 64) || n < 128)))
-        return fail(KF_INVALID_ARGS, "kf_linear_backward: OC (and n, for the weight gradient) must be multiples of 64 and >= 128, IC a multiple of 8 (got %d %d %d)", OC, IC, n);
+    const kf::LinearBwdPlan p = kf::linear_bwd_plan(kf::LinearBwdProblem{kf::mat_of(w), n, delta != nullptr, gW != nullptr, gBias != nullptr});
+    if (p.status != KF_OK) return fail(p.status, "kf_linear_backward: %s (got %d x %d, n %d)", refused[p.refusal], w->ne0, w->ne1, n);
+    if (!deltaIn || !scratch || (gW && !inp)) return fail(KF_INVALID_ARGS, "kf_linear_backward: null deltaIn / scratch, or gW without inp");
     if (!al16(deltaIn) || (inp && !al16(inp)) || (delta && !al16(delta)) || (gW && !al16(gW)) || ((uintptr_t)scratch & 255))
         return fail(KF_BLAS_UNALIGN, "kf_linear_backward: tensors must be 16-byte aligned, scratch 256-byte aligned");
-    char* p = (char*)scratch;
-    uint16_t* Wd = (uint16_t*)p;    p += up256((size_t)OC * IC * 2);
-    uint16_t* WdT = (uint16_t*)p;   p += up256((size_t)OC * IC * 2);
-    uint16_t* dInT = (uint16_t*)p;  p += up256((size_t)OC * n * 2);
-    uint16_t* inpT = (uint16_t*)p;
-    double* slabs = (double*)((char*)scratch + up256((size_t)OC * IC * 2) + lbw_mid_bytes(OC, IC, n));
-    void* const sk_ws = WdT; /* the middle region: stream-K slots when the large tile kernel takes the shape, the transposed copies otherwise */
-    const size_t sk_bytes = lbw_mid_bytes(OC, IC, n);
-    if (gBias) {
-        r = kf::colsum_add_launch(c->stream, deltaIn, gBias, n, OC, slabs);
-        if (r != KF_OK) return fail(r, "kf_linear_backward: bias column sums failed with %d", r);
-    }
-    kf::GemmProblem P; /* the two products' plans (kf_gemm_plan.h gemm_plan_backward): the middle region lends the split-K slots */
-    memset(&P, 0, sizeof(P));
-    P.n_w = 1, P.w[0] = kf::mat_of(w), P.n = n, P.x_al = 1, P.scratch = (long long)sk_bytes;
-    if (delta) { /* delta [n, IC] (+)= deltaIn [n, OC] . W [OC, IC]: rows of W^T are contiguous in the contraction index OC */
-        P.entry = kf::GE_BWD_DX;
-        const kf::GemmPlan p = kf::gemm_plan(P);
-        const uint16_t* Wsrc = (const uint16_t*)w->data;
-        r = KF_OK;
-        if (w->type != KF_BF16) r = kf::dequant_launch(c->stream, w, Wd), Wsrc = Wd;
-        if (r != KF_OK) return fail(r, "kf_linear_backward: dequantise of the weight failed with %d", r);
-        if (p.route == kf::GR_KMAJOR) { /* large shapes: the tile kernel reads W as the K-MAJOR operand it already is (contraction over its OC rows): no transpose */
-            r = kf::gemm3_km_launch(c->stream, p.k, Wsrc, IC, deltaIn, OC, n, IC, OC, delta, IC, 1.0f, accumulate_delta ? 1.0f : 0.0f, sk_ws);
-            if (r) return fail(r, "kf_linear_backward: input-gradient GEMM failed with %d", r);
-        } else {
-            r = w->type == KF_BF16 ? kf::dequant_launch(c->stream, w, Wd) : KF_OK;
-            if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, Wd, WdT, OC, IC);
-            if (r != KF_OK) return fail(r, "kf_linear_backward: dequantise / transpose of the weight failed with %d", r);
-            r = p.k.fam ? kf::gemm_launch(c->stream, p.k, kf::gm_bf16(WdT, IC, OC), deltaIn, OC, n, delta, IC, nullptr, 1.0f, accumulate_delta ? 1.0f : 0.0f, nullptr, IC) : 1;
-            if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: input-gradient GEMM not covered (%d)", r);
-        }
-    }
-    if (gW) { /* both operands are k-major for the contraction over the n token rows: inp [n][IC] is the "weight" side, deltaIn [n][OC] the "token" side */
-        P.entry = kf::GE_BWD_DW;
-        const kf::GemmPlan p = kf::gemm_plan(P);
-        if (p.route == kf::GR_KMAJOR) {
-            r = kf::gemm3_km_launch(c->stream, p.k, inp, IC, deltaIn, OC, OC, IC, n, gW, IC, 1.0f, 1.0f, sk_ws);
-            if (r) return fail(r, "kf_linear_backward: weight-gradient GEMM failed with %d", r);
-        } else { /* gW [OC, IC] += deltaIn^T [OC, n] . inp [n, IC]: "weight" = inp^T [IC, n], "tokens" = the OC rows of deltaIn^T, contraction over n */
-            r = kf::transpose_bf16_launch(c->stream, deltaIn, dInT, n, OC);
-            if (r == KF_OK) r = kf::transpose_bf16_launch(c->stream, inp, inpT, n, IC);
-            if (r != KF_OK) return fail(r, "kf_linear_backward: operand transposes failed with %d", r);
-            r = p.k.fam ? kf::gemm_launch(c->stream, p.k, kf::gm_bf16(inpT, IC, n), dInT, n, OC, gW, IC, nullptr, 1.0f, 1.0f, nullptr, IC) : 1;
-            if (r != KF_OK) return fail(r < 0 ? r : KF_INVALID_ARGS, "kf_linear_backward: weight-gradient GEMM not covered (%d)", r);
-        }
-    }
-    return KF_OK;
+    RET(kf::linear_backward_launch(c->stream, p, w, deltaIn, inp, delta, gW, gBias, n, accumulate_delta, scratch));
 }
 // ---- "train_target": "gama" (SLP::Back's gama branch -> CU_GamaBack_2): the (zero, step) gradients of a group-quantised weight (kf_gama_bwd.hip; the launch: kf_gama_plan.h)
 size_t kf_gama_backward_scratch_bytes(int OC, int IC, int n) {
@@ -2099,6 +2042,12 @@ int kfdbg_rowq_standin(const kf_weight* w, int* out) {
     int fmt = -1;
     out[0] = kf::rowq_standin(w, &m, &fmt), out[1] = fmt;
     out[2] = m.type, out[3] = m.quant, out[4] = m.M, out[5] = m.K, out[6] = m.gama, out[7] = m.al;
+    return 0;
+}
+// the plan kf::linear_bwd_plan makes for kf_linear_backward (no HIP call): tests/test_linear_bwd_plan_cpu.py, tests/exact_inputs.py
+int kfdbg_linear_backward_plan(const kf::LinearBwdProblem* P, kf::LinearBwdPlan* out) {
+    if (!P || !out) return -1;
+    *out = kf::linear_bwd_plan(*P);
     return 0;
 }
 // the plan kf::gemv_plan makes for a one-token mat-vec problem (no HIP call): tests/test_gemv_plan_cpu.py

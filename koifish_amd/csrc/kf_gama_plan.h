@@ -8,7 +8,7 @@
 //   * slabs: S in 1 .. GAMA_MAX_SLABS, each at least GAMA_MIN_STEPS k-steps of G3_BK rows deep, chosen to fill the most of the last round of resident workgroups
 //     (tiles S / (rounds x resident)); ties go to the smaller S.  Slab s owns k-steps [nkt s / S, nkt (s + 1) / S).
 #pragma once
-#include "kf_gemm_plan.h"
+#include "kf_linear_bwd_plan.h"
 
 namespace kf {
 
@@ -27,8 +27,8 @@ struct GamaPlan {
     long long scratch;   /* bytes: S slabs of [2][nGroup] fp32 */
 };
 
-// the shapes served: IC whole groups, OC and n as kf_linear_backward's weight gradient wants them
-inline bool gama_shape_ok(int OC, int IC, int n) { return OC >= 128 && OC % 64 == 0 && IC >= GAMA_GROUP && IC % GAMA_GROUP == 0 && n >= G3_BK && n % G3_BK == 0; }
+// the shapes served: OC as kf_linear_backward wants it (linear_bwd_shape_ok), IC whole groups, n whole k-steps -- one step is enough here, the weight gradient wants two
+inline bool gama_shape_ok(int OC, int IC, int n) { return linear_bwd_shape_ok(OC, IC, n, false) && IC >= GAMA_GROUP && IC % GAMA_GROUP == 0 && n >= G3_BK && n % G3_BK == 0; }
 
 inline GamaPlan gama_plan(int OC, int IC, int n) {
     GamaPlan p = {};

@@ -391,8 +391,8 @@ inline GemmPlan gemm_plan_shared(const GemmProblem& P) { /* GE_MULTI, GE_GATEUP,
 }
 
 // backward (kf_linear_backward, W [OC = w[0].M][IC = w[0].K], n token rows): dX [n, IC] = dY [n, OC] . W, or dW [OC, IC] += dY^T . X -- kf_gemm3.hip on the k-major
-// operands as they lie (the scratch lends the split-K slots), else the transposed copies on the token-batch tiles.  IC % 8 == 0 and OC, n % 64 == 0 (the entry's checks)
-// keep every row stride a multiple of 8 elements.
+// operands as they lie (the scratch lends the split-K slots), else the transposed copies on the token-batch tiles.  The shapes that reach this rule have passed linear_bwd_shape_ok
+// (kf_linear_bwd_plan.h), which keeps every row stride a multiple of 8 elements.
 inline GemmPlan gemm_plan_backward(const GemmProblem& P) {
     const int OC = P.w[0].M, IC = P.w[0].K;
     const bool dx = P.entry == GE_BWD_DX;

@@ -5,8 +5,10 @@
 // Like the reference, the weight is first dequantised to bf16 (GetDataX); the three contractions then run on the token-batch MFMA kernels of
 // kf_gemm.hip / kf_gemm2.hip, which contract over the contiguous index of both operands -- so the operands are brought into that form by the
 // tiled bf16 transpose below: delta = gemm(W^T as [IC, OC] rows, deltaIn), gW = gemm(inp^T as [IC, n] rows, deltaIn^T [OC, n]) with beta = 1.
-// This file: the transpose, and the bias column sums (fp64 per 256-row slab, slabs in index order: oracle/kf_oracle.c kfo_colsum_add).
-#include "kf_kernels.h"
+// Shapes where the large tile kernel of kf_gemm3.hip reads both operands k-major as they lie skip the transposes (kf_gemm_plan.h gemm_plan_backward).
+// This file: the transpose, the bias column sums (fp64 per 256-row slab, slabs in index order: oracle/kf_oracle.c kfo_colsum_add), and the launcher that executes
+// kf::linear_bwd_plan (kf_linear_bwd_plan.h: the shapes served, the scratch regions, both products).
+#include "kf_linear_bwd_plan.h"
 
 namespace kf {
 
@@ -96,6 +98,36 @@ int colsum_add_launch(hipStream_t st, const uint16_t* x, uint16_t* dst, int n, i
         hipLaunchKernelGGL(colsum_part_scalar_kernel, dim3((C + 255) / 256, nslab), dim3(256), 0, st, x, scratch, n, C);
     hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, st, dst, scratch, nslab, C);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
+int linear_backward_launch(hipStream_t st, const LinearBwdPlan& p, const kf_weight* w, const uint16_t* deltaIn, const uint16_t* inp, uint16_t* delta, uint16_t* gW, uint16_t* gBias,
+                           int n, int accumulate, void* scratch) {
+    const int OC = w->ne0, IC = w->ne1;
+    char* const s = (char*)scratch;
+    uint16_t *const Wd = (uint16_t*)s, *const WdT = (uint16_t*)(s + p.off_mid), *const dInT = (uint16_t*)(s + p.off_dInT), *const inpT = (uint16_t*)(s + p.off_inpT);
+    void* const sk_ws = s + p.off_mid; /* the middle region: split-K slots on the k-major route, the transposed copies otherwise */
+    int r = KF_OK;
+    if (gBias) r = colsum_add_launch(st, deltaIn, gBias, n, OC, (double*)(s + p.off_slabs));
+    if (r == KF_OK && p.w_from != LBW_STORED) r = dequant_launch(st, w, Wd);
+    if (r == KF_OK && delta) { /* delta [n, IC] (+)= deltaIn [n, OC] . W [OC, IC] */
+        const float beta = accumulate ? 1.0f : 0.0f;
+        if (p.dx.route == GR_KMAJOR) { /* the tile kernel reads W as the k-major operand it already is (contraction over its OC rows): no transpose */
+            r = gemm3_km_launch(st, p.dx.k, p.w_from == LBW_STORED ? (const uint16_t*)w->data : Wd, IC, deltaIn, OC, n, IC, OC, delta, IC, 1.0f, beta, sk_ws);
+        } else { /* rows of W^T are contiguous in the contraction index OC */
+            r = transpose_bf16_launch(st, Wd, WdT, OC, IC);
+            if (r == KF_OK) r = gemm_launch(st, p.dx.k, gm_bf16(WdT, IC, OC), deltaIn, OC, n, delta, IC, nullptr, 1.0f, beta, nullptr, IC);
+        }
+    }
+    if (r == KF_OK && gW) { /* gW [OC, IC] += deltaIn^T [OC, n] . inp [n, IC], contraction over the n token rows: inp is the "weight" side, deltaIn the "token" side */
+        if (p.dw.route == GR_KMAJOR) { /* both operands are k-major as they lie */
+            r = gemm3_km_launch(st, p.dw.k, inp, IC, deltaIn, OC, OC, IC, n, gW, IC, 1.0f, 1.0f, sk_ws);
+        } else { /* "weight" = inp^T [IC, n], "tokens" = the OC rows of deltaIn^T */
+            r = transpose_bf16_launch(st, deltaIn, dInT, n, OC);
+            if (r == KF_OK) r = transpose_bf16_launch(st, inp, inpT, n, IC);
+            if (r == KF_OK) r = gemm_launch(st, p.dw.k, gm_bf16(inpT, IC, n), dInT, n, OC, gW, IC, nullptr, 1.0f, 1.0f, nullptr, IC);
+        }
+    }
+    return r;
 }
 
 }  // namespace kf

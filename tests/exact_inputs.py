@@ -20,7 +20,7 @@ import numpy as np
 
 import attn_plan_mirror as APM
 from oracle import oracle as O
-from plan_structs import GemmMat as _Mat, GemmPlan as _Plan, GemmProblem as _Problem, ScorePlan as _ScorePlan, ScoreProblem as _ScoreProblem
+from plan_structs import GemmMat as _Mat, GemmPlan as _Plan, GemmProblem as _Problem, LinearBwdPlan as _BwdPlan, LinearBwdProblem as _BwdProblem, ScorePlan as _ScorePlan, ScoreProblem as _ScoreProblem
 
 BOUND = 256.0   # every integer of magnitude <= 256 is a bf16 value: the bf16 store of an exact result within the bound is that result
 
@@ -135,27 +135,19 @@ def q4_grid_weight(OC, IC, seed):
     return w, ow
 
 
-# ---- the plan behind kf_linear_backward (kf_gemm_plan.h gemm_plan_backward through kfdbg_gemm_plan): which form a case runs, and where its k pieces meet
+# ---- the plan behind kf_linear_backward (kf_linear_bwd_plan.h; the products: kf_gemm_plan.h gemm_plan_backward): which form a case runs, and where its k pieces meet
 BF16_T, BWD_DX, BWD_DW = 3, 4, 5
 ROUTES = {11: "KMAJOR", 12: "TRANSPOSE"}
 FAMILIES = {0: "NONE", 1: "DIRECT", 2: "PAIRED", 3: "STAGED", 4: "G2", 5: "G3"}
 G3_FORMS = {0: "BIG", 1: "SMALL", 2: "MID", 3: "TINY", 4: "WIDE"}
 
 
-def _up256(v):
-    return (v + 255) & ~255
-
-
 def backward_plan(hip, entry, OC, IC, n):
-    """the plan kf_linear_backward makes for this product: the scratch it lends is the middle region of kf_linear_backward_scratch_bytes"""
-    hip.kfdbg_gemm_plan.argtypes = [C.POINTER(_Problem), C.POINTER(_Plan)]
-    hip.kf_linear_backward_scratch_bytes.argtypes, hip.kf_linear_backward_scratch_bytes.restype = [C.c_int, C.c_int, C.c_int], C.c_size_t
-    mid = hip.kf_linear_backward_scratch_bytes(OC, IC, n) - _up256(OC * IC * 2) - _up256((n + 255) // 256 * OC * 8)
-    P = _Problem(entry=entry, n_w=1, n=n, x_al=1, scratch=mid)
-    P.w[0] = _Mat(BF16_T, 0, 0, OC, IC, 0, 0, 3)
-    out = _Plan()
-    assert hip.kfdbg_gemm_plan(C.byref(P), C.byref(out)) == 0
-    return out
+    """the plan kf_linear_backward makes for this product of a bf16 weight with both gradients wanted (kf_linear_bwd_plan.h through kfdbg_linear_backward_plan)"""
+    hip.kfdbg_linear_backward_plan.argtypes = [C.POINTER(_BwdProblem), C.POINTER(_BwdPlan)]
+    out = _BwdPlan()
+    assert hip.kfdbg_linear_backward_plan(C.byref(_BwdProblem(_Mat(BF16_T, 0, 0, OC, IC, 0, 0, 3), n, 1, 1, 0)), C.byref(out)) == 0 and out.status == 0
+    return out.dx if entry == BWD_DX else out.dw
 
 
 def form_name(p):

@@ -22,6 +22,15 @@ class GemmPlan(C.Structure):   # kf::GemmPlan (csrc/kf_gemm_plan.h)
     _fields_ = [("route", C.c_int), ("status", C.c_int), ("deq", C.c_int), ("deq_form", C.c_int), ("deq_bytes", C.c_longlong), ("ws_bytes", C.c_longlong), ("k", GemmKern)]
 
 
+class LinearBwdProblem(C.Structure):   # kf::LinearBwdProblem (csrc/kf_linear_bwd_plan.h)
+    _fields_ = [("w", GemmMat)] + [(f, C.c_int) for f in ("n", "want_delta", "want_gw", "want_bias")]
+
+
+class LinearBwdPlan(C.Structure):   # kf::LinearBwdPlan (csrc/kf_linear_bwd_plan.h)
+    _fields_ = ([(f, C.c_int) for f in ("status", "refusal", "w_from")] + [(f, C.c_longlong) for f in ("off_mid", "off_dInT", "off_inpT", "off_slabs", "mid_bytes", "bytes")]
+                + [("dx", GemmPlan), ("dw", GemmPlan)])
+
+
 class ScoreProblem(C.Structure):   # kf::ScoreProblem (csrc/kf_score_plan.h)
     _fields_ = [("w", GemmMat), ("n", C.c_int), ("x_al", C.c_int), ("force", C.c_int), ("form", C.c_int)]
 

@@ -162,3 +162,17 @@ def test_linear_backward_rejects(ctx):
     scratch = torch.empty(1 << 20, dtype=torch.uint8, device=ctx.device)
     sp = (scratch.data_ptr() + 255) & ~255
     assert ctx.hip.kf_linear_backward(ctx.h, C.byref(desc), z.data_ptr(), z.data_ptr(), z.data_ptr(), None, None, 64, 0, sp) == -20   # OC = 96 is not a multiple of 64
+    # a refused call leaves its outputs as they were: 128 x 128 at n = 96 with gW and gBias wanted is refused for n
+    OC, IC, n = 128, 128, 96
+    rng = np.random.default_rng(96)
+    dw = ctx.upload_blob(L.BF16, OC, IC, O.quantize(O.f32_to_bf16(rng.normal(0, 0.05, (OC, IC)).astype(np.float32)), OC, IC, L.BF16).blob())
+    desc = dw.desc()
+    before = [O.f32_to_bf16(rng.normal(0, 1.0, s).astype(np.float32)) for s in ((n, IC), (OC, IC), OC)]
+    d_delta, d_gW, d_gb = (bf16_t(b, ctx.device) for b in before)
+    d_dIn, d_inp = bf16_t(O.f32_to_bf16(rng.normal(0, 1.0, (n, OC)).astype(np.float32)), ctx.device), bf16_t(O.f32_to_bf16(rng.normal(0, 1.0, (n, IC)).astype(np.float32)), ctx.device)
+    scratch = torch.empty(ctx.hip.kf_linear_backward_scratch_bytes(OC, IC, n) + 256, dtype=torch.uint8, device=ctx.device)
+    sp = (scratch.data_ptr() + 255) & ~255
+    assert ctx.hip.kf_linear_backward(ctx.h, C.byref(desc), d_dIn.data_ptr(), d_inp.data_ptr(), d_delta.data_ptr(), d_gW.data_ptr(), d_gb.data_ptr(), n, 0, sp) == -20
+    ctx.sync()
+    for d, b in zip((d_delta, d_gW, d_gb), before):
+        assert np.array_equal(u16(d), b)
