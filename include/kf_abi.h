@@ -944,6 +944,38 @@ int kf_linear_w4a8(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float
 int kf_linear_w4a8_tiles_status(const kf_weight* w, int nTok);
 int kf_linear_w4a8_tiles(kf_ctx* ctx, const kf_weight* w, const int8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
 
+/* ---- fp8 activations for f8e5m2 layers: W(e5m2) . A(e4m3) on the native fp8 matrix instruction, for token batches.  Off unless called; every entry above keeps
+ * its route for KF_F8E5M2 (bf16 conversion in registers, or the resident bf16 copy).
+ * THE DEFINITION (restated on the CPU by tests/f8a8_restate.py):
+ *   activations: kf_act_quant_f8.  The front is kf_act_quant_i8's, unchanged: bf16 rows ldx apart read as fp32; with norm_w first normed and rounded to bf16 exactly as
+ *   kf_rmsnorm stores it.  Per row:
+ *     amax = max_i |x_i|;  e = the smallest integer with amax * 2^-e <= 448 (the largest finite OCP e4m3fn value);  step = 2^e (fp32);
+ *     code_i = e4m3_rne(x_i * 2^-e): the scaling is exact, the convert (v_cvt_pk_fp8_f32, round to nearest even, OCP e4m3fn) is the only rounding, and no scaled
+ *     value exceeds 448;  amax == 0: step = 0 and every code = 0, as kf_act_quant_i8 treats a zero row.
+ *     So amax / step lies in (224, 448].  The scale is a power of two on purpose: the codes are floating point, so it costs no precision, and both the scaling and the
+ *     epilogue multiply are exact.
+ *   product, per weight row m and token t, W the stored bytes (an OCP e5m2 value each: the high byte of the half, kf_abi.h "KF_F8E5M2"):
+ *     acc = sum_k e4m3(q[t][k]) * e5m2(W[m][k])  in the fp32 accumulator of v_mfma_f32_16x16x128_f8f6f4 (A format fp8, B format bf8): ONE ascending chain of
+ *     ceil(K / 128) MFMA steps per output, element k always in slot k % 128 of step k / 128; a half last step (K % 128 == 64) is filled with zeros, which are exact.
+ *     No split-K, no second accumulator summed afterwards.  Every product is exact in fp32 (4 x 3 significand bits); the only unspecified rounding is the
+ *     instruction's own adder over the 128 products and the accumulator.
+ *     CONTRACT: the bits of y[t][m] are a function of weight row m and activation row t alone -- never of nTok, of the tile form, or of the row's place in the batch;
+ *     y = bf16_rn(step[t] * acc);  with bias: bf16_rn(step[t] * acc + bias[m]);  with residual: y = bf16(residual + bf16(..)), exactly as kf_linear_w4a8 writes it.
+ * kf_act_quant_f8: x rows of dim bf16, ldx elements apart (ldx >= dim) -> q uint8 [rows][dim], step fp32 [rows].  With norm_w an odd dim is KF_RMS_PARAMS.
+ * kf_linear_f8a8: q uint8 [nTok][ne1] and step fp32 [nTok] as kf_act_quant_f8 writes them; y bf16 [nTok][ne0]; residual [nTok][ne0] may alias y (every output element
+ * is read and written by one lane).  Any nTok >= 1 is served; row and token tails are masked.  Refusals (kf::f8a8_plan, csrc/kf_f8a8.h), in this order: any storage
+ * other than plain KF_F8E5M2 KF_UNSUPPORTED_DATATYPE; ne1 < 128, ne1 % 64 != 0, ne0 < 1, nTok < 1 KF_INVALID_ARGS; weight data or q not 16-byte aligned
+ * KF_BLAS_UNALIGN.  A refused call launches nothing.
+ * kf_linear_f8a8_status: what kf_linear_f8a8 would answer for this weight and nTok (with aligned q), without a launch: the served-storage rule for callers that route
+ * (Fish asks it per layer matrix while kfh_set_act_fp8 is on).
+ * KF_F8A8_TILE_MIN: the token count from which such callers send a batch here by default; below it, and for one token always, kf_linear: one token is bound by the
+ * weight bytes, and fp8 activations buy nothing there.  128 is the smallest batch timed at which the route won at the large layer shapes: at 32 rows
+ * the two launches cost more than kf_linear's one at nearly every shape. */
+enum { KF_F8A8_TILE_MIN = 128 };
+int kf_act_quant_f8(kf_ctx* ctx, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w_or_null, float eps, int rows, int dim, uint8_t* q, float* step);
+int kf_linear_f8a8_status(const kf_weight* w, int nTok);
+int kf_linear_f8a8(kf_ctx* ctx, const kf_weight* w, const uint8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias_or_null, const kf_bf16* residual_or_null, int nTok);
+
 /* ---- int8 KV cache: quantised K / V rows and a decode attention whose scores are exact integer dots (the reference's switch DEBUG.T_kvcache_quant, QKV.cu:664, has a
  * stub behind it).  Off unless called; the bf16 entries above are untouched.
  * THE DEFINITION (restated in numpy by tests/kv8_restate.py):

@@ -32,6 +32,7 @@ int kfh_n_hot(void* h, int layer);
 int kfh_set_engine(void* h, int on);
 int kfh_set_act_int8(void* h, int on);
 int kfh_set_act_int8_q4(void* h, int on);
+int kfh_set_act_fp8(void* h, int on);
 int kfh_set_kv_int8(void* h, int on);
 int kfh_kv_int8(void* h);
 int kfh_set_kv_int8_prefill(void* h, int on);
@@ -44,6 +45,8 @@ int kfh_clear_adapters(void* h);
 int kfh_n_adapters(void* h);
 int kfh_set_a8_tile_min(void* h, int n);
 int kfh_a8_route_counts(void* h, int64_t* out2);
+int kfh_set_f8a8_tile_min(void* h, int n);
+int kfh_f8a8_route_counts(void* h, int64_t* out2);
 int kfh_set_canonical(void* h, int on);
 int kfh_engine_steps(void* h);
 int kfh_engine_stamps(void* h, unsigned long long* out, int n);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kf_a8.h"
+#include "kf_f8a8.h"
 #include "kf_attn_plan.h"
 #include "kf_attn_docs_plan.h"
 #include "kf_gemm_plan.h"
@@ -2027,6 +2028,33 @@ int kfdbg_a8_plan(const A8DbgProblem* P, A8DbgMatvec* out) { return (P && out) ?
 int kfdbg_a8_tile_plan(const A8DbgProblem* P, A8DbgTiles* out) { return (P && out) ? a8_dbg_tiles(kf::A8_LOWBIT, P->w, P->nTok, 0, out) : -1; }
 int kfdbg_w4a8_plan(const W4A8DbgProblem* P, A8DbgMatvec* out) { return (P && out) ? a8_dbg_matvec(kf::A8_Q4, P->w, P->nTok, P->qbias, out) : -1; }
 int kfdbg_w4a8_tile_plan(const W4A8DbgProblem* P, A8DbgTiles* out) { return (P && out) ? a8_dbg_tiles(kf::A8_Q4, P->w, P->nTok, P->qbias, out) : -1; }
+
+// ---- fp8 activations for f8e5m2 layers (include/kf_abi.h): the quantiser, then the product; every launch decision is kf::f8a8_plan's (kf_f8a8.h)
+int kf_act_quant_f8(kf_ctx* c, const kf_bf16* x, int64_t ldx, const kf_bf16* norm_w, float eps, int rows, int dim, uint8_t* q, float* step) {
+    CHKCTX(c);
+    if (!x || !q || !step) return fail(KF_INVALID_ARGS, "kf_act_quant_f8: null pointer");
+    if (rows < 1 || dim < 1 || ldx < dim) return fail(KF_INVALID_ARGS, "kf_act_quant_f8: rows=%d dim=%d ldx=%lld", rows, dim, (long long)ldx);
+    if (norm_w && dim % 2 != 0) return fail(KF_RMS_PARAMS, "kf_act_quant_f8: rmsnorm dim %d is not divisible by 2", dim); /* what kf_rmsnorm refuses, the prologue refuses */
+    RET(kf::act_quant_f8_launch(c->stream, x, ldx, norm_w, eps, rows, dim, q, step));
+}
+int kf_linear_f8a8_status(const kf_weight* w, int nTok) { return (w && w->data) ? kf::f8a8_plan(kf::F8A8Problem{kf::mat_of(w), nTok, 1}).status : KF_INVALID_ARGS; }
+int kf_linear_f8a8(kf_ctx* c, const kf_weight* w, const uint8_t* q, const float* step, kf_bf16* y, const kf_bf16* bias, const kf_bf16* residual, int nTok) {
+    CHKCTX(c);
+    if (!w || !w->data) return fail(KF_INVALID_ARGS, "kf_linear_f8a8: null weight");
+    if (!q || !step || !y) return fail(KF_INVALID_ARGS, "kf_linear_f8a8: null pointer");
+    const kf::F8A8Plan p = kf::f8a8_plan(kf::F8A8Problem{kf::mat_of(w), nTok, ((uintptr_t)q & 15) == 0});
+    if (p.status == KF_UNSUPPORTED_DATATYPE)
+        return fail(p.status, "kf_linear_f8a8: weight type %d (quant mode %d%s) has no fp8 form: served is plain KF_F8E5M2 (%d)", w->type, w->quant, (w->qzeros || w->qscales) ? ", AutoAWQ" : "", KF_F8E5M2);
+    if (p.status == KF_BLAS_UNALIGN) return fail(p.status, "kf_linear_f8a8: weight data or activation codes not 16-byte aligned");
+    if (p.status != KF_OK) return fail(p.status, "kf_linear_f8a8: %d x %d, nTok=%d: rows of at least 128 bytes in multiples of 64, at least one row and one token", w->ne0, w->ne1, nTok);
+    RET(kf::f8a8_run(c->stream, p, w, q, step, y, bias, residual, nTok));
+}
+// the plan kf::f8a8_plan makes for a problem (no HIP call): tests/test_f8a8_cpu.py
+int kfdbg_f8a8_plan(const kf::F8A8Problem* P, kf::F8A8Plan* out) {
+    if (!P || !out) return -1;
+    *out = kf::f8a8_plan(*P);
+    return 0;
+}
 
 // the plan kf::gemm_plan makes for a problem (no HIP call): tests/test_gemm_plan_cpu.py
 int kfdbg_gemm_plan(const kf::GemmProblem* P, kf::GemmPlan* out) {

@@ -2,6 +2,7 @@
 // with the ABSOLUTE row maximum: include/kf_abi.h "int8 activations").  One workgroup per row; an optional RMSNorm prologue norms the row and rounds it to bf16 exactly
 // as kf_rmsnorm stores it (rmsnorm_kernel, kf_ops.hip) before it is quantised, so q | k | v and gate | up share one launch for norm + quantise.
 #include "kf_a8.h"
+#include "kf_f8a8.h"
 
 namespace kf {
 
@@ -34,6 +35,57 @@ __global__ void __launch_bounds__(256) act_quant_kernel(const uint16_t* __restri
 
 int act_quant_launch(hipStream_t st, const uint16_t* x, long long ldx, const uint16_t* norm_w, float eps, int rows, int dim, int8_t* q, float* step) {
     hipLaunchKernelGGL(act_quant_kernel, dim3(rows), dim3(256), 0, st, x, ldx, norm_w, eps, 1.0f / (float)dim, dim, q, step);
+    return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
+}
+
+// kf_act_quant_f8: the same front, then per row a power-of-two step and OCP e4m3 codes (include/kf_abi.h "fp8 activations for f8e5m2 layers").  One pass per row: amax,
+// the exponent e (the smallest with amax * 2^-e <= 448), step = 2^e, x * 2^-e by v_ldexp_f32 (exact), v_cvt_pk_fp8_f32 (round to nearest even; no scaled value exceeds 448,
+// so its saturation never acts), sixteen codes per 16-byte store where the row allows.
+constexpr float F8_E4M3_MAX_FRAC = 0.875f; /* the largest finite e4m3fn, 448, is 0.875 * 2^9 */
+constexpr int F8_E4M3_MAX_EXP = 9;
+__device__ __forceinline__ uint32_t f8_pack4(float a, float b, float c, float d) {
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+}
+__global__ void __launch_bounds__(256) act_quant_f8_kernel(const uint16_t* __restrict__ x, long long ldx, const uint16_t* __restrict__ norm_w, float eps, float inv_dim, int dim,
+                                                           uint8_t* __restrict__ q, float* __restrict__ step) {
+    __shared__ double red[16];
+    __shared__ float mx[4];
+    const uint16_t* xr = x + (size_t)blockIdx.x * ldx;
+    uint8_t* qr = q + (size_t)blockIdx.x * dim;
+    float mul = 1.0f;
+    if (norm_w) {
+        const double ss = block_sumsq_bf16(xr, dim, red);
+        mul = rms_scale((float)ss, inv_dim, eps);
+    }
+    auto value = [&](int i) { return norm_w ? round_bf16((bf2f(xr[i]) * mul) * bf2f(norm_w[i])) : bf2f(xr[i]); };
+    float m = 0.0f;
+    for (int i = threadIdx.x; i < dim; i += blockDim.x) m = fmaxf(m, fabsf(value(i)));
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) mx[threadIdx.x >> 6] = m;
+    __syncthreads();
+    const float amax = fmaxf(fmaxf(mx[0], mx[1]), fmaxf(mx[2], mx[3]));
+    int e = 0;
+    if (amax != 0.0f) {
+        int ex;
+        const float fr = frexpf(amax, &ex); /* amax = fr * 2^ex, fr in [0.5, 1) */
+        e = ex - (fr <= F8_E4M3_MAX_FRAC ? F8_E4M3_MAX_EXP : F8_E4M3_MAX_EXP - 1);
+    }
+    auto scaled = [&](int i) { return amax != 0.0f ? ldexpf(value(i), -e) : 0.0f; };
+    const bool vec = ((uintptr_t)qr & 15) == 0; /* this row's codes start 16-byte aligned */
+    const int n16 = vec ? dim >> 4 : 0;
+    for (int c = threadIdx.x; c < n16; c += blockDim.x) {
+        uint32_t o[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) o[j] = f8_pack4(scaled(16 * c + 4 * j), scaled(16 * c + 4 * j + 1), scaled(16 * c + 4 * j + 2), scaled(16 * c + 4 * j + 3));
+        reinterpret_cast<u32x4*>(qr)[c] = u32x4{o[0], o[1], o[2], o[3]};
+    }
+    for (int i = 16 * n16 + threadIdx.x; i < dim; i += blockDim.x) qr[i] = (uint8_t)(f8_pack4(scaled(i), 0.0f, 0.0f, 0.0f) & 0xffu);
+    if (threadIdx.x == 0) step[blockIdx.x] = amax != 0.0f ? ldexpf(1.0f, e) : 0.0f;
+}
+
+int act_quant_f8_launch(hipStream_t st, const uint16_t* x, long long ldx, const uint16_t* norm_w, float eps, int rows, int dim, uint8_t* q, float* step) {
+    hipLaunchKernelGGL(act_quant_f8_kernel, dim3(rows), dim3(256), 0, st, x, ldx, norm_w, eps, 1.0f / (float)dim, dim, q, step);
     return hipGetLastError() == hipSuccess ? KF_OK : KF_HIP_CHECK;
 }
 

@@ -479,25 +479,31 @@ static const char* kf_last_error_hint(int st) {
 }
 // a matrix takes int8 activations unless kf::a8_plan (asked through kf_linear_a8_status: the one served-storage rule) says its storage has no integer form
 static bool a8_type(const kf_weight& w) { return kf_linear_a8_status(&w, 1) != KF_UNSUPPORTED_DATATYPE; }
-int Fish::A8Ready(int rows) {
-    if (a8.q && a8.rows >= rows) return KF_OK;
+int Fish::A8Ready(A8Rows& r, int rows) {
+    if (r.q && r.rows >= rows) return KF_OK;
     KF_TRY(kf_sync(ctx));
-    a8 = A8Rows(); /* the old rows go first (they can be large): a refusal below leaves the set empty, rows 0 */
-    return Commit(a8, ctx, rows, (size_t)std::max(std::max(config.n_head * config.head_dim, config.nEmbed), config.n_ff));
+    r = A8Rows(); /* the old rows go first (they can be large): a refusal below leaves the set empty, rows 0 */
+    return Commit(r, ctx, rows, (size_t)std::max(std::max(config.n_head * config.head_dim, config.nEmbed), config.n_ff));
 }
-// where a matrix goes in a batch of n token rows: 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear (every matrix while both switches are off)
+// where a matrix goes in a batch of n token rows: 3 = kf_linear_f8a8 (token batches from f8a8_tile_min rows only), 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles),
+// 0 = kf_rmsnorm + kf_linear (every matrix while the switches are off)
 int Fish::A8Route(const kf_weight& w, int n) const {
+    if (act_fp8 && n > 1 && f8a8_tile_min >= 0 && n >= f8a8_tile_min && kf_linear_f8a8_status(&w, n) == KF_OK) return 3;
     if (act_int8_q4 && kf_linear_w4a8_status(&w, n) == KF_OK) return 2; /* asked with the batch's n: the plan's LDS bound depends on it, and a refused matrix keeps kf_linear */
     return (act_int8_t && a8_type(w)) ? 1 : 0;
 }
 int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim, floatX* normed, int n_w, SLP* const* s, floatX* const* y, const floatX* residual) {
-    bool any8 = false, other = false;
+    bool any8 = false, anyf8 = false, other = false;
     kf_weight wd[3];
     int route[3];
-    for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), route[i] = A8Route(wd[i], n), (route[i] ? any8 : other) = true;
+    for (int i = 0; i < n_w; i++) wd[i] = s[i]->w->desc(), route[i] = A8Route(wd[i], n), (route[i] == 3 ? anyf8 : route[i] ? any8 : other) = true;
     if (any8) {
-        KF_TRY(A8Ready(n));
+        KF_TRY(A8Ready(a8, n));
         KF_TRY(kf_act_quant_i8(ctx, x, dim, norm_w, eps, n, dim, a8.q, a8.step));
+    }
+    if (anyf8) {
+        KF_TRY(A8Ready(f8, n));
+        KF_TRY(kf_act_quant_f8(ctx, x, dim, norm_w, eps, n, dim, reinterpret_cast<uint8_t*>(f8.q.get()), f8.step));
     }
     const floatX* xb = x;
     if (other && norm_w) {
@@ -509,13 +515,18 @@ int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim
     int OC[3], na = 0;
     for (int i = 0; i < n_w; i++) {
         const floatX* bias = s[i]->b ? ToX(s[i]->b) : nullptr;
-        if (route[i]) {
+        if (route[i] == 3) {
+            KF_TRY(kf_linear_f8a8(ctx, &wd[i], reinterpret_cast<const uint8_t*>(f8.q.get()), f8.step, y[i], bias, residual, n));
+            f8a8_count[0]++;
+        } else if (route[i]) {
             const bool tiles = n > 1 && a8_tile_min >= 0 && n >= a8_tile_min; /* n = 1 (decode) always takes the mat-vec */
             static constexpr decltype(&kf_linear_a8) entry[2][2] = {{kf_linear_a8, kf_linear_a8_tiles}, {kf_linear_w4a8, kf_linear_w4a8_tiles}}; /* [A8Route - 1][tiles] */
             KF_TRY(entry[route[i] - 1][tiles](ctx, &wd[i], a8.q, a8.step, y[i], bias, residual, n));
             a8_count[tiles ? 0 : 1]++;
-        } else
+        } else {
             KF_TRY(kf_linear(ctx, &wd[i], xb, y[i], bias, n, 1.0f, 0.0f, residual ? KF_EPI_RESIDUAL : KF_EPI_NONE, residual));
+            if (act_fp8 && kf_linear_f8a8_status(&wd[i], n) == KF_OK) f8a8_count[1]++; /* an f8 matrix below the threshold */
+        }
         if (s[i]->lora_a) a[na] = s[i]->lora_a, b[na] = s[i]->lora_b, ya[na] = y[i], OC[na] = wd[i].ne0, na++;
     }
     if (na == 0) return KF_OK;
@@ -523,8 +534,9 @@ int Fish::Group(const floatX* x, const floatX* norm_w, float eps, int n, int dim
     for (int i = 0; i < na; i++) KF_TRY(kf_lora_apply(ctx, 1, a + i, b + i, lora_r, OC + i, dim, xb, ya + i, nullptr, n, lora_s));
     return KF_OK;
 }
-int Fish::SetActInt8(bool q4, bool on, std::string& why) {
-    const char* entry = q4 ? "kfh_set_act_int8_q4" : "kfh_set_act_int8";
+int Fish::SetActInt8(int family, bool on, std::string& why) {
+    const bool q4 = family == ACT_Q4, fp8 = family == ACT_FP8;
+    const char* entry = fp8 ? "kfh_set_act_fp8" : q4 ? "kfh_set_act_int8_q4" : "kfh_set_act_int8";
     if (on) {
         KF_TRY(Admit(MODE_ACT_INT8, entry, why));
         int served = 0;
@@ -533,6 +545,10 @@ int Fish::SetActInt8(bool q4, bool on, std::string& why) {
             for (SLP* s : LayerMatrices(l)) {
                 if (!s->w) return refused(why, entry, KF_INVALID_ARGS, "a layer matrix is missing");
                 const kf_weight w = s->w->desc();
+                if (fp8) {
+                    served += kf_linear_f8a8_status(&w, 1) == KF_OK;
+                    continue;
+                }
                 if (q4) { /* the group ZERO is part of this arithmetic: no zero check */
                     served += kf_linear_w4a8_status(&w, 1) == KF_OK;
                     continue;
@@ -549,14 +565,18 @@ int Fish::SetActInt8(bool q4, bool on, std::string& why) {
             }
         if (!served)
             return refused(why, entry, KF_UNSUPPORTED_DATATYPE,
-                           q4 ? "no layer matrix is 4-bit group storage that kf_linear_w4a8 serves (KF_Q4, groups of 128 with gama, qBias 0 or 8): nothing would take int8 activations"
+                           fp8 ? "no layer matrix is plain f8e5m2 storage that kf_linear_f8a8 serves (KF_F8E5M2, rows of at least 128 bytes in multiples of 64): nothing would take fp8 activations"
+                           : q4 ? "no layer matrix is 4-bit group storage that kf_linear_w4a8 serves (KF_Q4, groups of 128 with gama, qBias 0 or 8): nothing would take int8 activations"
                               : "no layer matrix is ternary (KF_T_SIGN) or 1-bit (KF_BOOL1 / KF_T_BINARY): nothing would take int8 activations");
-        KF_TRY(A8Ready(1));
-        a8_count[0] = a8_count[1] = 0;
+        if (fp8) f8a8_count[0] = f8a8_count[1] = 0; /* the rows f8 come with the first token batch */
+        else {
+            KF_TRY(A8Ready(a8, 1));
+            a8_count[0] = a8_count[1] = 0;
+        }
     }
     const bool was = act_int8;
-    (q4 ? act_int8_q4 : act_int8_t) = on;
-    act_int8 = act_int8_t || act_int8_q4;
+    (fp8 ? act_fp8 : q4 ? act_int8_q4 : act_int8_t) = on;
+    act_int8 = act_int8_t || act_int8_q4 || act_fp8;
     if (act_int8 != was) ModeChanged();
     return KF_OK;
 }
@@ -1803,9 +1823,24 @@ int kfh_set_engine(void* h, int on) {
     return KF_OK;
 }
 // int8 activations for the ternary / 1-bit layer matrices: on / off (off: today's routes, bit for bit).  A refusal leaves the switch as it was; kfh_host_error says why.
-int kfh_set_act_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(false, on != 0, g_host_err); }
+int kfh_set_act_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(Fish::ACT_TERNARY, on != 0, g_host_err); }
 // the same for the 4-bit layer matrices (kf_linear_w4a8 / kf_linear_w4a8_tiles): a second switch, independent of kfh_set_act_int8
-int kfh_set_act_int8_q4(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(true, on != 0, g_host_err); }
+int kfh_set_act_int8_q4(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(Fish::ACT_Q4, on != 0, g_host_err); }
+// fp8 activations for the plain f8e5m2 layer matrices of token batches (kf_act_quant_f8 + kf_linear_f8a8): a third switch of the same mode, independent of the other two
+int kfh_set_act_fp8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetActInt8(Fish::ACT_FP8, on != 0, g_host_err); }
+// the token count from which a token batch's f8e5m2 matrices take kf_linear_f8a8 while kfh_set_act_fp8 is on: n >= 2 sets it, 1 is treated as 2 (a single token always
+// keeps kf_linear), 0 restores the default (KF_F8A8_TILE_MIN), n < 0 = never
+int kfh_set_f8a8_tile_min(void* h, int n) {
+    reinterpret_cast<Fish*>(h)->f8a8_tile_min = n == 0 ? (int)KF_F8A8_TILE_MIN : n == 1 ? 2 : n < 0 ? -1 : n;
+    return KF_OK;
+}
+// (kf_linear_f8a8 launches, launches that kept a served f8e5m2 matrix on kf_linear) since the last switch-on of kfh_set_act_fp8
+int kfh_f8a8_route_counts(void* h, int64_t* out2) {
+    if (!h || !out2) return KF_INVALID_ARGS;
+    const Fish* f = reinterpret_cast<Fish*>(h);
+    out2[0] = f->f8a8_count[0], out2[1] = f->f8a8_count[1];
+    return KF_OK;
+}
 // the int8 KV cache: on / off (off: today's routes on the bf16 cache, bit for bit).  The two caches are independent -- switching converts nothing, the caller prefills again.
 // A refusal leaves the switch as it was; kfh_host_error says why.  kfh_kv8_*: the int8 pair and its steps on the device (NULL before the first switch-on).
 int kfh_set_kv_int8(void* h, int on) { return reinterpret_cast<Fish*>(h)->SetKVInt8(on != 0, g_host_err); }

@@ -397,17 +397,23 @@ struct Fish : CtxHolder, SeqBuffers {
     // act_int8 is "either switch is on".  act_int8_t is kfh_set_act_int8's own state (ternary / 1-bit matrices -> kf_linear_a8), act_int8_q4 kfh_set_act_int8_q4's
     // (include/kf_abi.h "int8 activations for 4-bit layers": KF_Q4 group matrices that kf_linear_w4a8_status serves -> kf_linear_w4a8 / kf_linear_w4a8_tiles; their ZERO
     // need not be 0, the dequant arena is not consulted for them).
-    bool act_int8 = false, act_int8_t = false, act_int8_q4 = false;
-    A8Rows a8;
+    // act_fp8 is kfh_set_act_fp8's (include/kf_abi.h "fp8 activations for f8e5m2 layers"): a third switch of the same mode.  While it is on, every plain KF_F8E5M2 layer
+    // matrix of a token batch of at least f8a8_tile_min rows takes its input through kf_act_quant_f8 (rows f8: e4m3 codes and their steps) and kf_linear_f8a8; smaller
+    // batches and single tokens keep kf_rmsnorm + kf_linear.  f8a8_count: (kf_linear_f8a8 launches, launches such a matrix kept on kf_linear) since the last switch-on.
+    bool act_int8 = false, act_int8_t = false, act_int8_q4 = false, act_fp8 = false;
+    A8Rows a8, f8;
+    int f8a8_tile_min = KF_F8A8_TILE_MIN;
+    int64_t f8a8_count[2] = {0, 0};
     // token batches of at least a8_tile_min rows send those matrices to kf_linear_a8_tiles (int8 MFMA tiles; the same bits), smaller ones and every single token to
     // kf_linear_a8; < 0: never.  kfh_set_a8_tile_min; the default is the tile plan's KF_A8_TILE_MIN.  a8_count: (tile, mat-vec) launches since the last switch-on.
     int a8_tile_min = KF_A8_TILE_MIN;
     int64_t a8_count[2] = {0, 0};
     // one switch per family; its own switch-on checks: a layer matrix of the family exists (q4: one kf_linear_w4a8 serves; otherwise: ternary / 1-bit, kf_linear_a8
-    // accepts each, every ZERO section of those is zero)
-    int SetActInt8(bool q4, bool on, std::string& why);
-    int A8Route(const kf_weight& w, int n) const;  // 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
-    int A8Ready(int rows);
+    // accepts each, every ZERO section of those is zero; fp8: one kf_linear_f8a8 serves)
+    enum { ACT_TERNARY = 0, ACT_Q4 = 1, ACT_FP8 = 2 };
+    int SetActInt8(int family, bool on, std::string& why);
+    int A8Route(const kf_weight& w, int n) const;  // 3 = kf_linear_f8a8, 2 = kf_linear_w4a8(_tiles), 1 = kf_linear_a8(_tiles), 0 = kf_rmsnorm + kf_linear
+    int A8Ready(A8Rows& r, int rows);
     // low-rank adapters at inference (kfh_set_adapter; include/kf_abi.h kf_lora_apply; the LORA branch of SLP::Forw): any subset of the layers' seven matrices carries a
     // trained pair a [r, in], b [out, r] -- device pointers of the caller's, no copy, read at every launch (a trainer's later step is seen) -- with ONE rank and ONE s for
     // the model (an eager-only mode).  Its own checks: s finite, one rank and one s, a rank and shape kf_lora_apply_status serves, 16-byte alignment.

@@ -383,6 +383,22 @@ class Context:
         L.check(self.hip.kf_act_quant_i8(self.h, _ptr(x), ldx, _ptr(norm_w), eps, rows, dim, _ptr(q), _ptr(step)), "kf_act_quant_i8")
         return q, step
 
+    def act_quant_f8(self, x, norm_w=None, eps=1e-6):
+        """kf_act_quant_f8: x bf16 [dim] or [rows, dim] (a row stride larger than dim is honoured) -> (q uint8 of x's shape: OCP e4m3 codes of x / step, step fp32 [rows]:
+        a power of two per row); with norm_w the rows are first RMS-normed and rounded to bf16 as kf_rmsnorm stores them"""
+        rows, dim = (1, x.shape[0]) if x.dim() == 1 else x.shape
+        ldx = dim if x.dim() == 1 else x.stride(0)
+        assert x.stride(-1) == 1 and x.dtype == torch.bfloat16
+        q = torch.empty((rows, dim) if x.dim() == 2 else (dim,), dtype=torch.uint8, device=self.device)
+        step = torch.empty(rows, dtype=torch.float32, device=self.device)
+        L.check(self.hip.kf_act_quant_f8(self.h, _ptr(x), ldx, _ptr(norm_w), eps, rows, dim, _ptr(q), _ptr(step)), "kf_act_quant_f8")
+        return q, step
+
+    def linear_f8a8(self, w, q, step, bias=None, residual=None, y=None):
+        """kf_linear_f8a8: a plain f8e5m2 weight times e4m3 activation codes q [ne1] or [nTok, ne1] with their steps [nTok] on the fp8 MFMA -> y bf16 [ne0] or
+        [nTok, ne0]; residual may be y"""
+        return self._linear_a8("kf_linear_f8a8", w, q, step, bias, residual, y)
+
     def kv8_quant_rows(self, k, v, k8, v8, ks, vs, pos0, n_kv, hd):
         """kf_kv8_quant_rows: k, v bf16 [n, n_kv * hd] (a row stride larger than that is honoured) -> rows pos0 .. pos0 + n - 1 of k8 / v8 int8 [n_ctx, kv_stride] and of
         ks / vs fp32 [n_ctx, n_kv], in place"""
@@ -737,7 +753,7 @@ class Qwen3:
             return
         a = np.ascontiguousarray(hot, dtype=np.int32)
         rc = self.host.kfh_set_hot(self.h, int(layer), a.ctypes.data_as(C.c_void_p), a.size)
-        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False) or getattr(self, "_adapters", None) or self.kv_int8()):   # the refusals the host explains: a mask while int8 activations are on or adapters are attached (the text is set on those paths only)
+        if rc != 0 and (getattr(self, "_act_int8", False) or getattr(self, "_act_int8_q4", False) or getattr(self, "_act_fp8", False) or getattr(self, "_adapters", None) or self.kv_int8()):   # the refusals the host explains: a mask while int8 activations are on or adapters are attached (the text is set on those paths only)
             raise L.KFError("kfh_set_hot failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         L.check(rc, "kfh_set_hot")
         if not hasattr(self, "_hot"):
@@ -767,6 +783,15 @@ class Qwen3:
         if rc != 0:
             raise L.KFError("set_act_int8_q4 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
         self._act_int8_q4 = bool(on)
+
+    def set_act_fp8(self, on):
+        """fp8 activations for every plain f8e5m2 layer matrix of a token batch (kf_act_quant_f8 + kf_linear_f8a8; include/kf_abi.h "fp8 activations for f8e5m2 layers"):
+        prefill, score and perplexity batches of at least set_f8a8_tile_min rows; smaller batches and single tokens keep kf_linear.  A third switch of the
+        int8-activation mode, independent of the other two, with that mode's exclusions.  Raises with the reason when no layer matrix is served or a hot-row mask is set."""
+        rc = self.host.kfh_set_act_fp8(self.h, int(bool(on)))
+        if rc != 0:
+            raise L.KFError("set_act_fp8 failed with %d: %s" % (rc, self.host.kfh_host_error().decode()))
+        self._act_fp8 = bool(on)
 
     def set_kv_int8(self, on):
         """The int8 KV cache (include/kf_abi.h "int8 KV cache"): K / V rows as int8 codes with one fp32 step per row and kv-head, decode attention on exact integer scores
@@ -881,6 +906,17 @@ class Qwen3:
         """(tile launches, mat-vec launches) of both integer families (kf_linear_a8*, kf_linear_w4a8*) since the last set_act_int8(True) / set_act_int8_q4(True)"""
         out = (C.c_int64 * 2)()
         L.check(self.host.kfh_a8_route_counts(self.h, out), "kfh_a8_route_counts")
+        return int(out[0]), int(out[1])
+
+    def set_f8a8_tile_min(self, n):
+        """token batches of at least n rows send their f8e5m2 matrices to kf_linear_f8a8 while set_act_fp8 is on, smaller ones and single tokens keep kf_linear:
+        n >= 2 sets the threshold (1 is treated as 2), 0 restores the default (128), n < 0 = never"""
+        L.check(self.host.kfh_set_f8a8_tile_min(self.h, int(n)), "kfh_set_f8a8_tile_min")
+
+    def f8a8_route_counts(self):
+        """(kf_linear_f8a8 launches, launches that kept a served f8e5m2 matrix on kf_linear) since the last set_act_fp8(True)"""
+        out = (C.c_int64 * 2)()
+        L.check(self.host.kfh_f8a8_route_counts(self.h, out), "kfh_f8a8_route_counts")
         return int(out[0]), int(out[1])
 
     def set_canonical(self, on):
