@@ -294,6 +294,35 @@ int kf_norm_gateup_swiglu(kf_ctx* ctx, const kf_bf16* x, const kf_bf16* norm_w_o
 int kf_attn_block(kf_ctx* ctx, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16* kcache, const kf_bf16* vcache, kf_bf16* out,
                   const kf_bf16* wq_norm, const kf_bf16* wk_norm, const float* rope_table, int pos, const int32_t* d_pos, int n_head, int n_kv,
                   int hd, int kv_stride, float eps, void* scratch);
+/* kf_attn_block for n_seq = 1 .. 32 INDEPENDENT sequences in ONE launch (batched decode: no counterpart in the reference).  Sequence s brings its raw q row at
+ * q_raw + s * q_stride, its raw new key at k_raw + s * k_stride and its new value row at v_raw + s * v_stride (V is passed RAW here: the launch writes it, since the row
+ * projections cannot aim each sequence's row at a cache row of its own), sits at position d_pos[s] and owns the cache rows from d_row0[s] on (both int32 device tables).
+ * For every sequence with d_pos[s] >= 0 the launch prepares the query heads and the key heads (per-head q/k RMSNorm + RoPE at d_pos[s]), writes the new K row and the V
+ * row to cache row d_row0[s] + d_pos[s], attends to cache rows d_row0[s] .. d_row0[s] + d_pos[s] and writes out + s * out_stride.
+ * DEFINITION: the output row of sequence s and the two cache rows it writes are BIT FOR BIT what kf_attn_block produces in the canonical order when called with
+ * kcache + d_row0[s] * kv_stride, vcache + d_row0[s] * kv_stride (the V row in place) and pos = d_pos[s] -- whatever the other sequences are: the canonical fp64 form
+ * does not depend on launch geometry.  There is ONE arithmetic, the canonical one, under both settings of kf_set_canonical (as kf_attn_block_kv8).
+ * d_pos[s] < 0: the sequence is PARKED -- nothing is read and nothing is written for it.
+ * h_pos [n_seq], HOST memory: the caller's mirror of d_pos, read during the call to size the grid and to deal the longest key walks first.  h_pos[s] >= d_pos[s] is
+ * required (a bound is enough: a sequence the device has parked may still be listed at its last position); h_pos[s] < 0 everywhere launches nothing (KF_OK).
+ * The sequences' row ranges must not overlap; rope_table covers every position.  Rows past a sequence's position are never read.
+ * Alignment (KF_BLAS_UNALIGN): kcache, vcache, v_raw and scratch 16-byte aligned; kv_stride, q_stride, v_stride, out_stride multiples of 8.  KF_INVALID_ARGS: a null
+ * pointer, n_seq outside 1 .. 32, query heads per kv-head other than 1, 2, 4, 8, hd other than 64 / 128, a stride shorter than its row.  A refusal launches nothing.
+ * scratch: kf_attn_seqs_scratch_bytes(n_head, hd, n_seq) bytes, zero-filled ONCE by the caller (the arrival counters return to zero) and kept to ONE (n_head, hd): the
+ * sequences' counters lie kf_attn_scratch_bytes(n_head, hd) apart, between their partials. */
+int kf_attn_block_seqs(kf_ctx* ctx, const kf_bf16* q_raw, int64_t q_stride, const kf_bf16* k_raw, int64_t k_stride, const kf_bf16* v_raw, int64_t v_stride,
+                       kf_bf16* kcache, kf_bf16* vcache, kf_bf16* out, int64_t out_stride, const kf_bf16* wq_norm, const kf_bf16* wk_norm, const float* rope_table,
+                       const int32_t* d_pos, const int32_t* d_row0, const int32_t* h_pos, int n_seq, int n_head, int n_kv, int hd, int kv_stride, float eps,
+                       void* scratch);
+size_t kf_attn_seqs_scratch_bytes(int n_head, int hd, int n_seq);
+/* The slots' bookkeeping between two steps of a batched decode, on the device (int32 tables of n_seq = 1 .. 32 entries): a sequence with d_pos[s] >= 0 takes the id
+ * d_top1[s] -- d_tok[s] = id, d_ids[s * ids_stride + d_count[s]] = id (dropped past ids_stride), d_count[s] += 1, d_pos[s] += 1 -- and PARKS (d_pos[s] = -1) when the id
+ * is `eos` (-1: none) or it was the sequence's max_new-th.  A parked sequence is left alone.  One small launch; nothing is read back. */
+/* The route of the linear parts of a batched decode step with n_seq = 1 .. 32 rows, for the n_w layer matrices w: 0 = the row entries (kf_*_rows: at most 8 sequences,
+ * the canonical order, every matrix 4-bit group storage or bf16 -- one unpack of every weight block, the one-token bits), 1 = the token-batch entries with n = n_seq rows
+ * (kf_linear, kf_gateup_swiglu_batch, kf_head_logprob: one pass over the weights, fp32 sums in MFMA order).  Negative: a refusal. */
+int kf_seqs_linear_route(kf_ctx* ctx, const kf_weight* const* w, int n_w, int n_seq);
+int kf_seqs_advance(kf_ctx* ctx, const int32_t* d_top1, int32_t* d_tok, int32_t* d_pos, int32_t* d_count, int32_t* d_ids, int ids_stride, int max_new, int eos, int n_seq);
 /* [final RMSNorm] + LM head + greedy pick; then state update for graph replay: d_state[0] = next token,
  * d_state[1] += 1 (position), d_tokens_out[old pos] = next token (when non-NULL).  d_state == NULL: logits only (kf_sample follows). */
 int kf_norm_lm_head(kf_ctx* ctx, const kf_bf16* x, const kf_bf16* norm_w_or_null, float eps, const kf_weight* w, kf_bf16* logits,

@@ -90,6 +90,31 @@ int kfhdbg_verify_refusal(unsigned active, int greedy, char* why, size_t n);
 int kfh_generate(void* h, const int* prompt, int n_prompt, int n_new, int* out, int use_graph);
 int kfh_set_forced(void* h, const int32_t* forced, int n);
 int kfh_prefill(void* h, const int* tokens, int n, int pos0);
+/* Batched decode: n_seq = 1 .. 32 independent greedy sequences on ONE model -- its bf16 KV cache [n_layer][n_ctx][kv_dim] cut into n_seq regions of n_ctx / n_seq rows
+ * (the longest context a sequence may reach: a prompt of n tokens and max_new ids need n + max_new - 1 rows; running past it is refused with a reason), one pass over
+ * the weights per step (kf_seqs_linear_route: the row entries up to 8 sequences on 4-bit group / bf16 layers in the canonical order, else the token-batch entries with
+ * n = n_seq rows) and ONE attention launch per layer for all of them (kf_attn_block_seqs).  kfh_seqs_prefill runs slot s's prompt through the
+ * batched prefill on its region (a one-token prompt waits for the first step); kfh_seqs_step runs up to n_steps greedy steps for every live slot -- ids and positions stay
+ * on the device, a slot parks on `eos` (-1: none) or with its max_new-th id, the call returns early once every slot has max_new ids; kfh_seqs_tokens reads a slot's ids
+ * (returns their number, at most cap; -1 on a refusal); kfh_seqs_end closes the regions.  On the row route a slot's ids are kfh_generate's (prefill mode 1) for its
+ * prompt, id for id; on the token-batch route the logits lie within the token-batch bar of the token-serial step's.  Greedy only, and refused -- in the words of the mode table -- while TP, int8 activations, adapters, the int8 KV cache, hot-row masks or fuse_level 0
+ * is on; while regions are open kfh_forward / kfh_generate / kfh_prefill / kfh_verify are refused (they share the cache).  Reasons: kfh_host_error.
+ * kfh_seqs_route_counts: out4 = {activation rows the row entries served with the shared unpack, rows they served by one-token launches, passes over every matrix, steps}
+ * since kfh_seqs_begin. */
+int kfh_seqs_begin(void* h, int n_seq, int max_new, int eos);
+int kfh_seqs_prefill(void* h, int s, const int* tokens, int n);
+int kfh_seqs_step(void* h, int n_steps);
+int kfh_seqs_tokens(void* h, int s, int* out, int cap);
+int kfh_seqs_end(void* h);
+int kfh_seqs_route_counts(void* h, int64_t* out4);
+/* kfh_seqs_route: the route the last kfh_seqs_step took for the linear parts (kf_seqs_linear_route: 0 row entries, 1 token-batch entries; -1 before the first step).
+ * Debug entries (tests and tools only; not part of a decode): kfhdbg_seqs_keep_logits(on) makes every later step leave the slots' logits rows, kfhdbg_seqs_logits reads slot s's [vocab] bf16 row of the last step,
+ * kfhdbg_seqs_force sets the next step's token of every slot (n_seq ids: teacher forcing).  On the token-batch route the kept logits are a product of their own
+ * (kf_linear on the normed rows) BESIDE the pick, which kf_head_logprob makes without a logit matrix: the ids a slot emitted are kfh_seqs_tokens'. */
+int kfh_seqs_route(void* h);
+int kfhdbg_seqs_keep_logits(void* h, int on);
+int kfhdbg_seqs_logits(void* h, int s, uint16_t* out);
+int kfhdbg_seqs_force(void* h, const int* tokens);
 int kfh_score(void* h, const int* tokens, int n, int pos0, float* logprob_out, int* top1_out);
 int kfh_eval_ppl(void* h, const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored);
 int kfh_set_prefill_mode(void* h, int mode, int chunk);

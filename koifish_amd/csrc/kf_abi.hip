@@ -918,6 +918,58 @@ int kf_attn_block(kf_ctx* c, const kf_bf16* q_raw, const kf_bf16* k_raw, kf_bf16
     RET(kf::attn_launch(c->stream, a, kf::attn_plan(attn_problem(kf::ATTN_DECODE, c, n_head, n_kv, hd, pos, 1, 1, q_raw, out, 0, 0, 0))));
 }
 
+// n_seq independent sequences in one launch (kf_attn_seqs.hip): every launch decision is kf::attn_plan's ATTN_DECODE_SEQS entry, asked with the largest mirrored position
+size_t kf_attn_seqs_scratch_bytes(int n_head, int hd, int n_seq) {
+    return (n_seq < 1 || n_seq > kf::ATTN_SEQS_MAX) ? 0 : (size_t)n_seq * kf::attn_decode_scratch_bytes(n_head, hd);
+}
+int kf_attn_block_seqs(kf_ctx* c, const kf_bf16* q_raw, int64_t q_stride, const kf_bf16* k_raw, int64_t k_stride, const kf_bf16* v_raw, int64_t v_stride, kf_bf16* kc,
+                       kf_bf16* vc, kf_bf16* out, int64_t out_stride, const kf_bf16* wq, const kf_bf16* wk, const float* table, const int32_t* d_pos, const int32_t* d_row0,
+                       const int32_t* h_pos, int n_seq, int n_head, int n_kv, int hd, int kv_stride, float eps, void* scratch) {
+    CHKCTX(c);
+    if (!q_raw || !k_raw || !v_raw || !kc || !vc || !out || !table || !d_pos || !d_row0 || !h_pos || !scratch) return fail(KF_INVALID_ARGS, "kf_attn_block_seqs: null pointer");
+    if (n_seq < 1 || n_seq > kf::ATTN_SEQS_MAX) return fail(KF_INVALID_ARGS, "kf_attn_block_seqs: n_seq=%d outside 1 .. %d", n_seq, kf::ATTN_SEQS_MAX);
+    if (!al16(kc) || !al16(vc) || !al16(v_raw) || !al16(scratch) || (v_stride % 8)) return fail(KF_BLAS_UNALIGN, "kf_attn_block_seqs: cache, v_raw or scratch not 16-byte aligned");
+    // the dispatch order (the longest key walks first: a stable insertion sort of the mirror) and the largest position, the plan's bound
+    int order[kf::ATTN_SEQS_MAX], pos_max = -1;
+    for (int s = 0; s < n_seq; s++) {
+        int i = s;
+        for (; i > 0 && h_pos[order[i - 1]] < h_pos[s]; i--) order[i] = order[i - 1];
+        order[i] = s;
+        if (h_pos[s] > pos_max) pos_max = h_pos[s];
+    }
+    kf::AttnProblem P = attn_problem(kf::ATTN_DECODE_SEQS, c, n_head, n_kv, hd, pos_max, 1, n_seq, q_raw, out, q_stride, out_stride, kv_stride);
+    const kf::AttnPlan p = kf::attn_plan(P);
+    if (p.status == KF_BLAS_UNALIGN)
+        return fail(p.status, "kf_attn_block_seqs: kv_stride %d, q_stride %lld or out_stride %lld is not a multiple of 8", kv_stride, (long long)q_stride, (long long)out_stride);
+    if (p.status != KF_OK || kv_stride < n_kv * hd || q_stride < (int64_t)n_head * hd || out_stride < (int64_t)n_head * hd || k_stride < (int64_t)n_kv * hd || v_stride < (int64_t)n_kv * hd)
+        return fail(KF_INVALID_ARGS, "kf_attn_block_seqs: %d / %d heads x %d, strides q %lld k %lld v %lld out %lld kv %d: query heads per kv-head 1, 2, 4 or 8, head_dim 64 or 128, no stride below its row",
+                    n_head, n_kv, hd, (long long)q_stride, (long long)k_stride, (long long)v_stride, (long long)out_stride, kv_stride);
+    kf::AttnSeqsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = q_raw, a.k_raw = k_raw, a.v_raw = v_raw, a.kcache = kc, a.vcache = vc, a.out = out, a.wq_norm = wq, a.wk_norm = wk, a.rope_table = table, a.eps = eps;
+    a.pos = d_pos, a.row0 = d_row0, a.q_stride = q_stride, a.k_stride = k_stride, a.v_stride = v_stride, a.out_stride = out_stride;
+    a.n_head = n_head, a.n_kv = n_kv, a.kv_stride = kv_stride;
+    for (int i = 0; i < n_seq; i++) a.order[i >> 3] |= (unsigned long long)order[i] << ((i & 7) * 8);
+    a.counters = (int*)scratch, a.part = (double*)((char*)scratch + kf::KF_ATTN_CNT_BYTES);
+    RET(kf::attn_seqs_launch(c->stream, a, p));
+}
+
+// the linear route of a batched decode step: kf::seqs_linear_route (kf_gemm_plan.h) asked with this context's order and the storage of the layer matrices
+int kf_seqs_linear_route(kf_ctx* c, const kf_weight* const* w, int n_w, int n_seq) {
+    CHKCTX(c);
+    if (!w || n_w < 1 || n_seq < 1 || n_seq > kf::ATTN_SEQS_MAX) return fail(KF_INVALID_ARGS, "kf_seqs_linear_route: no weights or n_seq=%d outside 1 .. %d", n_seq, kf::ATTN_SEQS_MAX);
+    bool shareable = true;
+    for (int i = 0; i < n_w; i++)
+        shareable = shareable && w[i] && (w[i]->type == KF_BF16 || (w[i]->type == KF_Q4 && w[i]->quant == KF_QUANT_GROUP && !w[i]->qzeros));
+    return kf::seqs_linear_route(n_seq, c->canonical != 0, shareable);
+}
+int kf_seqs_advance(kf_ctx* c, const int32_t* d_top1, int32_t* d_tok, int32_t* d_pos, int32_t* d_count, int32_t* d_ids, int ids_stride, int max_new, int eos, int n_seq) {
+    CHKCTX(c);
+    if (!d_top1 || !d_tok || !d_pos || !d_count || !d_ids || ids_stride < 1 || max_new < 1 || n_seq < 1 || n_seq > kf::ATTN_SEQS_MAX)
+        return fail(KF_INVALID_ARGS, "kf_seqs_advance: null pointer, ids_stride / max_new below 1 or n_seq=%d outside 1 .. %d", n_seq, kf::ATTN_SEQS_MAX);
+    RET(kf::seqs_advance_launch(c->stream, d_top1, d_tok, d_pos, d_count, d_ids, ids_stride, max_new, eos, n_seq));
+}
+
 // ---- int8 KV cache (include/kf_abi.h): every launch decision is kf::attn_plan's ATTN_DECODE_KV8 entry
 static kf::AttnProblem kv8_problem(int n_head, int n_kv, int hd, int pos, long long kv_stride) {
     return kf::AttnProblem{kf::ATTN_DECODE_KV8, n_head, n_kv, hd, pos, 1, 1, 1, 0, 0, 0, kv_stride};

@@ -81,6 +81,9 @@ struct AttnSlice {
     const int gq_split, split, kvh, gpart, chunk, t0;
     __device__ __forceinline__ AttnSlice(int gq_split_, int chunk_)
         : gq_split(gq_split_), split(blockIdx.x), kvh((int)blockIdx.y / gq_split), gpart((int)blockIdx.y - kvh * gq_split), chunk(chunk_), t0(split * chunk) {}
+    // the same with the (kv-head, part) index given: a launch whose grid y carries more than that (kf_attn_seqs.hip: the sequence in front)
+    __device__ __forceinline__ AttnSlice(int gq_split_, int chunk_, int y)
+        : gq_split(gq_split_), split(blockIdx.x), kvh(y / gq_split), gpart(y - kvh * gq_split), chunk(chunk_), t0(split * chunk) {}
     __device__ __forceinline__ int h0() const { return (kvh * gq_split + gpart) * GQ; } /* the first of the GQ heads of THIS workgroup */
     __device__ __forceinline__ int tstart(int wave, int grp) const { return t0 + wave * KPW + grp; } /* the first key a lane walks (then every tstride-th) */
     __device__ __forceinline__ int end(int last) const { /* of the slice's keys among 0 .. last */

@@ -1,6 +1,6 @@
 // kf_attn_plan.h -- how attention is launched: kf::attn_plan, one pure host function, picks the route, kernel form, slices, grid, threads, LDS and scratch of every
-// attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_kv8, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
-// kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_prefill_kv8.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
+// attention launch (kf_attn_decode / kf_attn_block, kf_attn_block_seqs, kf_attn_block_kv8, kf_attn_prefill, kf_attn_prefill_kv8, kf_attn_prefill_batch(_strided), kf_attn_backward); the launchers (kf_attn.hip,
+// kf_attn_seqs.hip, kf_attn_kv8.hip, kf_attn_prefill.hip, kf_attn_prefill_kv8.hip, kf_attn_bwd_mfma.hip) carry out what it returns and decide nothing.  attn_slices is the one slice rule: the decode engine reads it too.
 // The Attn*Lds layouts are the ONE statement of every attention kernel's dynamic LDS: the plan's size and the kernels' pointers both come from them.
 #pragma once
 #include "kf_kernels.h"
@@ -30,6 +30,9 @@ constexpr int AP_KPAD = 8, AP_VPAD = 32;   /* K and V row padding, elements (16 
 // the int8 cache (kf_attn_kv8.hip): a lane holds 16 elements of a key, so a key takes hd / 16 lanes and a wave step twice the keys of the bf16 kernel; the slices are
 // attn_slices' (one rule), 4 waves always, ATTN_KV8_U tiles in flight per wave: one 64-key slice of hd = 128 is one batch of the workgroup (4 waves x 8 keys x 2 tiles)
 constexpr int ATTN_KV8_NW = 4, ATTN_KV8_U = 2;
+// independent sequences in one launch (kf_attn_seqs.hip): at most ATTN_SEQS_MAX of them (the dispatch order travels in the kernel's arguments, a byte each); 4 waves
+// always -- the sequences fill the chip, so a slice never needs the second wave per SIMD that ATTN_NW8_KEYS buys a lone sequence
+constexpr int ATTN_SEQS_MAX = 32, ATTN_SEQS_NW = 4;
 // prompts on the int8 cache (kf_attn_prefill_kv8.hip): 64 (token, query head) columns per workgroup, 16 per wave (the N of v_mfma_i32_16x16x64_i8); key tiles of 64
 // anchored at key 0; K8 rows 16 bytes apart from a multiple of 128 (the 16 rows of an A read on distinct banks), bf16 V rows 32 bytes (the 8 rows of a transposing pass)
 constexpr int APK8_COLS = 64, APK8_KT = 64, APK8_KPAD = 16, APK8_VPAD = 16;
@@ -98,7 +101,7 @@ struct AttnTileKv8Lds : AttnLds { /* attn_prefill_kv8_kernel<hd, gq> */
 };
 
 // ---- the problem
-enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5, ATTN_VERIFY = 6 };
+enum { ATTN_DECODE = 0, ATTN_PROMPT = 1, ATTN_BATCH = 2, ATTN_BACKWARD = 3, ATTN_DECODE_KV8 = 4, ATTN_PROMPT_KV8 = 5, ATTN_VERIFY = 6, ATTN_DECODE_SEQS = 7 };
 enum { ATTN_Q_AL = 1, ATTN_OUT_AL = 2 }; /* q 16-byte aligned, out 8-byte aligned */
 struct AttnProblem {
     int entry, n_head, n_kv, hd;
@@ -114,7 +117,9 @@ struct AttnProblem {
 //   ATTN_BWD        attn_bwd_dq_mfma_kernel<hd> on grid, then attn_bwd_dkv_mfma_kernel<hd> on grid_kv
 //   ATTN_SLICED_KV8 attn_kv8_kernel<gq, hd> on (n_splits, n_kv * gq_split, 1), ATTN_KV8_NW waves; slices, counters and scratch as ATTN_SLICED in the canonical order
 //   ATTN_TILE_KV8   attn_prefill_kv8_kernel<hd, gq> on (blocks of 64 / gq tokens, n_kv, 1), four waves, no scratch; gq = the query heads of a kv-head, any n_tok >= 1
-enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4, ATTN_SLICED_KV8 = 5, ATTN_TILE_KV8 = 6 };
+//   ATTN_SLICED_SEQS attn_seqs_kernel<gq, hd> on (n_splits of the LONGEST sequence, n_seq * n_kv * gq_split, 1), ATTN_SEQS_NW waves: every sequence cuts its own keys by
+//                   attn_slices at its device position inside the kernel (its workgroups past that count leave at once), scratch = one decode scratch per sequence
+enum { ATTN_SLICED = 0, ATTN_PER_TOKEN = 1, ATTN_TILE = 2, ATTN_PAIRED = 3, ATTN_BWD = 4, ATTN_SLICED_KV8 = 5, ATTN_TILE_KV8 = 6, ATTN_SLICED_SEQS = 7 };
 struct AttnPlan {
     int status, route;             /* KF_OK or the refusal; the route (of a refusal: the one that refused) */
     int canon, gq, nw, hd, kh, kt; /* the kernel form; gq = query heads per workgroup */
@@ -165,6 +170,18 @@ inline AttnPlan attn_plan(const AttnProblem& P) {
         p.canon = 1, p.kh = 1, p.kt = APK8_KT, p.threads = 256;
         p.grid[0] = (P.n_tok + TQ - 1) / TQ, p.grid[1] = P.n_kv, p.grid[2] = 1;
         p.lds = AttnTileKv8Lds(P.hd).bytes;
+        return p;
+    }
+    if (P.entry == ATTN_DECODE_SEQS) { /* n_seq sequences, each one token at its own position of its own cache rows; P.pos = the LARGEST position (the host's mirror
+                                          of the device table, a bound), < 0: every sequence is parked and the grid is empty.  ONE arithmetic, the canonical one
+                                          (P.canon is not read); the grid's x is the longest sequence's slice count (the count never falls as the position grows) */
+        p.route = ATTN_SLICED_SEQS;
+        if (!hd_ok || !kv_ok || !gq_ok || P.n_seq < 1 || P.n_seq > ATTN_SEQS_MAX) return refuse(KF_INVALID_ARGS);
+        if ((P.kv_stride & 7) || (P.q_stride & 7) || (P.out_stride & 7)) return refuse(KF_BLAS_UNALIGN);
+        if (!sliced(true, attn_slices(P.pos < 0 ? 0 : P.pos, P.n_kv, GQ), ATTN_SEQS_NW, 1, true)) return p;
+        if (P.pos < 0) p.n_splits = p.grid[0] = 0;
+        p.grid[1] *= P.n_seq, p.scratch *= P.n_seq;
+        p.lds = AttnCanonLds(p.gq, p.nw, P.hd).bytes;
         return p;
     }
     if (P.entry == ATTN_VERIFY) { /* n_tok consecutive queries of one sequence, query r at pos + r against keys 0 .. pos + r: the sliced decode kernel with the query on
@@ -242,6 +259,27 @@ struct AttnPrefillKv8Args { /* kf_attn_prefill_kv8.hip, ATTN_TILE_KV8 */
     float rden;
 };
 int attn_prefill_kv8_launch(hipStream_t st, AttnPrefillKv8Args& a, const AttnPlan& p);
+struct AttnSeqsArgs { /* kf_attn_seqs.hip, ATTN_SLICED_SEQS: sequence s has its rows at s * the stride of each */
+    const uint16_t* q;     /* raw q rows [n_head * hd], q_stride apart */
+    const uint16_t* k_raw; /* raw new keys [n_kv * hd], k_stride apart */
+    const uint16_t* v_raw; /* new value rows [n_kv * hd], v_stride apart, 16-byte aligned rows */
+    uint16_t* kcache;
+    uint16_t* vcache;
+    const uint16_t* wq_norm;
+    const uint16_t* wk_norm;
+    const float* rope_table;
+    double* part;  /* sequence s: [n_head][its n_splits][hd + 2] fp64 partials, attn_decode_scratch_bytes * s behind sequence 0's */
+    int* counters; /* per (sequence, kv-head, part), zero between launches; the same distance apart */
+    uint16_t* out; /* out_stride apart */
+    const int* pos;  /* [n_seq] device: the position, < 0: parked */
+    const int* row0; /* [n_seq] device: the first cache row of the sequence */
+    long long q_stride, k_stride, v_stride, out_stride;
+    unsigned long long order[ATTN_SEQS_MAX / 8]; /* byte i: the sequence dispatched i-th (the longest walks first) */
+    int n_head, n_kv, kv_stride, gq_split, cnt_stride;
+    float eps, inv_sqrt_hd_den;
+};
+int attn_seqs_launch(hipStream_t st, AttnSeqsArgs& a, const AttnPlan& p);
+int seqs_advance_launch(hipStream_t st, const int* top1, int* tok, int* pos, int* count, int* ids, int ids_stride, int max_new, int eos, int n_seq); /* kf_attn_seqs.hip */
 int kv8_quant_rows_launch(hipStream_t st, const uint16_t* k, const uint16_t* v, long long ld, int n, int n_kv, int hd, int8_t* k8, int8_t* v8, float* ks, float* vs, int pos0,
                           int kv_stride);
 int kv8_dequant_rows_launch(hipStream_t st, const int8_t* k8, const int8_t* v8, const float* ks, const float* vs, int n, int n_kv, int hd, int kv_stride, uint16_t* kout,

@@ -70,6 +70,13 @@ constexpr int AWQ_WIDE_MIN = 128;       /* ... on 128-token tiles; below: 32-tok
 constexpr int G3_FIRST = 256;           /* bf16 operands try the kf_gemm3.hip tiles before the 32 x 32 direct kernel (the direct kernel took 64 us for bf16 1024 x 2048 at 1024 rows) */
 constexpr int RESIDENT_MIN = 320;       /* with a dequant arena: the resident bf16 copies + the kf_gemm3.hip tiles (the 1024-row o_proj / down_proj of a long prompt) */
 constexpr int STACK_MIN = 1024;         /* without an arena: the stacked route, a dequantise per call */
+// batched decode (Fish::SeqsStep: n_seq activation rows, one per independent sequence), chosen ONCE per call for every linear part of the step: the row entries
+// (kf_*_rows: one unpack of every weight block for up to GEMV_ROWS_MAX = 8 rows, the one-token bits) while they can share -- at most SEQS_ROWS_MAX sequences, the
+// canonical order, every layer matrix 4-bit group storage or bf16; anything else -- more sequences, the v_dot2c order, a row codebook, f8, 2- / 1-bit storage -- takes the
+// token-batch entries with n = n_seq rows (kf_linear from GEMM_MIN rows on the MFMA tiles, one pass over the weights whatever n_seq is; fp32 sums in MFMA order)
+constexpr int SEQS_ROWS_MAX = 8;
+enum { SEQS_ROUTE_ROWS = 0, SEQS_ROUTE_TILES = 1 };
+constexpr int seqs_linear_route(int n_seq, bool canonical, bool all_shareable) { return n_seq <= SEQS_ROWS_MAX && canonical && all_shareable ? SEQS_ROUTE_ROWS : SEQS_ROUTE_TILES; }
 constexpr int DEQ_TILE_MIN = 2048;      /* a quantised weight is dequantised into the scratch once for the bf16 tiles (a few % of the product at these sizes) */
 // prompt-sized batches on small matrices: the wave-independent direct kernel while its 32 x 32 workgroups fit ~2-3 rounds of the chip (measured crossover against
 // the staged tiles, scratch/ub_gemm.py: 1024 rows up to n ~ 1024, 2048 up to ~ 600, 3072 up to ~ 400)

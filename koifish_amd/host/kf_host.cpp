@@ -937,6 +937,7 @@ int Fish::EnqueueStep(int bound) {
 }
 
 int Fish::ForwardOnRLS(int token, int pos) {
+    KF_TRY(SeqsBusy("kfh_forward", g_host_err));
     if (pos < 0 || pos >= config.n_ctx || token < 0 || token >= config.vocab) return KF_INVALID_ARGS;
     tok_pos = pos;
     graph_mode = false;
@@ -983,6 +984,7 @@ bool Fish::OneLaunchStep() {
 }
 
 int Fish::RunSteps(int pos, int n, bool use_graph) {
+    KF_TRY(SeqsBusy("Fish::RunSteps", g_host_err));
     if (pos < 0 || pos + n > config.n_ctx) return KF_INVALID_ARGS;
     KF_TRY(TPCommit());
     if (use_graph && n > 1 && !EagerOnly() && OneLaunchStep()) { /* runs of steps inside one position bucket: ONE launch each (kf_engine_steps_head), at most kStepsPerLaunch steps */
@@ -1043,6 +1045,7 @@ int Fish::RunSteps(int pos, int n, bool use_graph) {
 }
 
 int Fish::Prefill(const int* tokens, int n, int pos0) {
+    if (!seqs.inside) KF_TRY(SeqsBusy("kfh_prefill", g_host_err)); /* SeqsPrefill runs this on a region of its own */
     if (n < 1 || pos0 < 0 || pos0 + n > config.n_ctx) return KF_INVALID_ARGS;
     for (int i = 0; i < n; i++)
         if (tokens[i] < 0 || tokens[i] >= config.vocab) return KF_INVALID_ARGS;
@@ -1086,6 +1089,7 @@ int Fish::ScoreReady() {
 }
 
 int Fish::Score(const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) {
+    KF_TRY(SeqsBusy("kfh_score", g_host_err));
     if (n < 2 || pos0 < 0 || pos0 + n > config.n_ctx || !tokens || !logprob_out) return KF_INVALID_ARGS;
     for (int i = 0; i < n; i++)
         if (tokens[i] < 0 || tokens[i] >= config.vocab) return KF_INVALID_ARGS;
@@ -1175,6 +1179,7 @@ int Fish::SetSampler(const CHAT_SAMPLER& s) {
 }
 
 int Fish::Generate(const int* prompt, int n_prompt, int n_new, int* out, bool use_graph) {
+    KF_TRY(SeqsBusy("kfh_generate", g_host_err));
     if (n_prompt < 1 || n_new < 1 || n_prompt + n_new - 1 > config.n_ctx) return KF_INVALID_ARGS;
     std::vector<int32_t> forced(config.n_ctx, -1);
     for (int i = 0; i < n_prompt; i++) forced[i] = prompt[i];
@@ -1196,6 +1201,7 @@ int Fish::Generate(const int* prompt, int n_prompt, int n_new, int* out, bool us
 
 // ------------------------------------------------------------------------------------------------ speculative decoding: the verify pass and the rounds
 int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, std::string& why) {
+    KF_TRY(SeqsBusy("kfh_verify", why));
     if (!tokens || !top1 || n < 1 || n > KF_SPEC_MAX_K + 1 || pos0 < 0 || pos0 + n > config.n_ctx)
         return refused(why, "kfh_verify", KF_INVALID_ARGS, "1 .. 8 tokens at positions inside the context, and a place for their ids");
     for (int i = 0; i < n; i++)
@@ -1239,6 +1245,204 @@ int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, 
     if (logits) KF_TRY(kf_d2h(ctx, logits, vLogits->data, (size_t)n * config.vocab * 2));
     KF_TRY(kf_rows_route_counts(ctx, after));
     verify_rows[0] += after[0] - before[0], verify_rows[1] += after[1] - before[1];
+    return KF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batched decode: regions of the one KV cache, one attention launch for all
+int SeqsRows::Alloc(kf_ctx* c, const MODEL_CARD& card, const kf_weight& head) {
+    const int R = KF_SEQS_MAX, qd = card.n_head * card.head_dim, kvd = card.n_head_kv * card.head_dim;
+    sX = GT(c, "sX", typNUMBER::BF16, card.nEmbed, R), sQ = GT(c, "sQ", typNUMBER::BF16, qd, R), sK = GT(c, "sK", typNUMBER::BF16, kvd, R), sV = GT(c, "sV", typNUMBER::BF16, kvd, R);
+    sAttn = GT(c, "sAttn", typNUMBER::BF16, qd, R), sGate = GT(c, "sGate", typNUMBER::BF16, card.n_ff, R);
+    s_attn_ws = GT(c, "s_attn_ws", typNUMBER::F32, (int)((kf_attn_seqs_scratch_bytes(card.n_head, card.head_dim, R) + 3) / 4)); /* zero-filled once */
+    s_head_ws = GT(c, "s_head_ws", typNUMBER::F32, (int)((kf_head_rows_scratch_bytes(&head) + 3) / 4));
+    if (!sX || !sQ || !sK || !sV || !sAttn || !sGate || !s_attn_ws || !s_head_ws) return KF_OUTOF_GPUMEMORY;
+    sNorm = GT(c, "sNorm", typNUMBER::BF16, card.nEmbed, R), sUp = GT(c, "sUp", typNUMBER::BF16, card.n_ff, R);
+    if (!sNorm || !sUp) return KF_OUTOF_GPUMEMORY;
+    KF_TRY(d_tab.AllocFilled(c, (size_t)5 * R * 4, 0));
+    KF_TRY(d_tgt.AllocFilled(c, (size_t)R * 4, 0xff));
+    KF_TRY(d_lp.Alloc(c, (size_t)R * 4));
+    KF_TRY(score_ws.Alloc(c, kf_head_logprob_scratch_bytes(&head, R)));
+    return d_ids.AllocFilled(c, (size_t)R * card.n_ctx * 4, 0);
+}
+int Fish::SeqsBusy(const char* entry, std::string& why) const {
+    if (seqs.n_seq == 0) return KF_OK;
+    return refused(why, entry, KF_INVALID_ARGS, "the KV cache is cut into " + std::to_string(seqs.n_seq) + " regions of a batched decode (kfh_seqs_begin) and this entry would write over them: kfh_seqs_end first");
+}
+int Fish::SeqsBegin(int n_seq, int max_new, int eos, std::string& why) {
+    const char* E = "kfh_seqs_begin";
+    if (seqs.n_seq) return refused(why, E, KF_INVALID_ARGS, "regions are open already: kfh_seqs_end first");
+    if (n_seq < 1 || n_seq > KF_SEQS_MAX || max_new < 1) return refused(why, E, KF_INVALID_ARGS, "1 .. 32 sequences and at least one new id each");
+    if (!embed.w || !head.proj.w) return refused(why, E, KF_INVALID_ARGS, "the model has no weights yet");
+    if (HasRow3()) return refused(why, E, KF_UNSUPPORTED_DATATYPE, kRow3Why);
+    for (int l = 0; l < config.nLayer; l++)
+        for (const SLP* m : LayerMatrices(l))
+            if (m->w->qZero) return refused(why, E, KF_UNSUPPORTED_DATATYPE, "a layer matrix is in the AutoAWQ layout, which batched decode has not been run on: such models decode one sequence at a time");
+    const int rcm = verify_refusal(Modes(), samp_params.greedy(), E, why, "batched decode");
+    if (rcm != KF_OK) return Kv8Note(why), rcm;
+    const int region = config.n_ctx / n_seq;
+    if (max_new > region) return refused(why, E, KF_INVALID_ARGS, std::to_string(max_new) + " new ids do not fit a region of " + std::to_string(region) + " rows (n_ctx / n_seq)");
+    if (!srows.sX) KF_TRY(Commit(srows, ctx, config, head.proj.w->desc())); /* allocated by the first SeqsBegin */
+    for (int l = 0; l < config.nLayer; l++) { /* the token-batch entries' workspace for KF_SEQS_MAX rows (storages that dequantise first): never inside a step */
+        for (const SLP* m : LayerMatrices(l)) KF_TRY(EnsureLinearScratch(m->w->desc(), KF_SEQS_MAX));
+        const kf_weight wg = ffn[l]->gate.w->desc(), wu = ffn[l]->up.w->desc();
+        const kf_weight* gu[2] = {&wg, &wu};
+        KF_TRY(GrowScratch(kf_linear_multi_scratch_bytes(2, gu, KF_SEQS_MAX)));
+    }
+    KF_TRY(EnsureLinearScratch(head.proj.w->desc(), KF_SEQS_MAX));
+    int32_t tab[5 * KF_SEQS_MAX] = {};
+    for (int s = 0; s < KF_SEQS_MAX; s++) tab[KF_SEQS_MAX + s] = -1, tab[2 * KF_SEQS_MAX + s] = s < n_seq ? s * region : 0; /* every slot parked until its prompt; row origins */
+    KF_TRY(kf_h2d(ctx, srows.d_tab, tab, sizeof(tab)));
+    seqs = SeqsState();
+    seqs.n_seq = n_seq, seqs.region = region, seqs.max_new = max_new, seqs.eos = eos;
+    seqs.pos.assign(n_seq, -1), seqs.count.assign(n_seq, 0);
+    return KF_OK;
+}
+int Fish::SeqsPrefill(int s, const int* tokens, int n, std::string& why) {
+    const char* E = "kfh_seqs_prefill";
+    if (!seqs.n_seq) return refused(why, E, KF_INVALID_ARGS, "no regions are open: kfh_seqs_begin first");
+    if (s < 0 || s >= seqs.n_seq || !tokens || n < 1) return refused(why, E, KF_INVALID_ARGS, "a slot of the open batch and a prompt of at least one token");
+    if (n + seqs.max_new - 1 > seqs.region)
+        return refused(why, E, KF_INVALID_ARGS, "a prompt of " + std::to_string(n) + " tokens and " + std::to_string(seqs.max_new) + " new ids run past the slot's region of " +
+                                                    std::to_string(seqs.region) + " rows (n_ctx / n_seq): fewer sequences, a shorter prompt or fewer new ids");
+    for (int i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= config.vocab) return refused(why, E, KF_INVALID_ARGS, "a prompt id outside the vocabulary");
+    const int S = KF_SEQS_MAX;
+    int32_t *d_tok = srows.d_tab, *d_pos = d_tok + S, *d_count = d_tok + 3 * S;
+    int32_t *ids = srows.d_ids + (size_t)s * config.n_ctx, zero = 0;
+    KF_TRY(kf_h2d(ctx, d_count + s, &zero, 4));
+    if (n == 1) { /* as Generate: a one-token prompt is the first step's token */
+        const int32_t tok = tokens[0];
+        KF_TRY(kf_h2d(ctx, d_tok + s, &tok, 4));
+        KF_TRY(kf_h2d(ctx, d_pos + s, &zero, 4));
+        seqs.pos[s] = 0, seqs.count[s] = 0;
+        return KF_OK;
+    }
+    {   /* for the length of the call the model's cache begins at the region's first row (as XcdReplicas::Prefill aims it): positions stay the tokens' own */
+        struct Aim {
+            KVCache& kc;
+            void *k0, *v0;
+            Aim(KVCache& c_, size_t off) : kc(c_), k0(c_.key->data), v0(c_.val->data) { kc.key->data = ToX(c_.key) + off, kc.val->data = ToX(c_.val) + off; }
+            ~Aim() { kc.key->data = k0, kc.val->data = v0; }
+        } aim(cache, (size_t)s * seqs.region * cache.kv_dim);
+        seqs.inside = true;
+        const int rc = Prefill(tokens, n, 0);
+        seqs.inside = false;
+        KF_TRY(rc);
+    }
+    // the id picked behind the prompt (d_state[0]) is the slot's first id: the slot stands at the prompt's last position and advances like after a step
+    const int32_t last = n - 1;
+    KF_TRY(kf_h2d(ctx, d_pos + s, &last, 4));
+    KF_TRY(kf_seqs_advance(ctx, d_state, d_tok + s, d_pos + s, d_count + s, ids, config.n_ctx, seqs.max_new, seqs.eos, 1));
+    seqs.count[s] = 1, seqs.pos[s] = seqs.max_new == 1 ? -1 : n;
+    return KF_OK;
+}
+int Fish::SeqsStep(int n_steps, std::string& why) {
+    const char* E = "kfh_seqs_step";
+    if (!seqs.n_seq) return refused(why, E, KF_INVALID_ARGS, "no regions are open: kfh_seqs_begin first");
+    if (n_steps < 1) return refused(why, E, KF_INVALID_ARGS, "at least one step");
+    const int rcm = verify_refusal(Modes(), samp_params.greedy(), E, why, "batched decode"); /* a switch may have moved since kfh_seqs_begin */
+    if (rcm != KF_OK) return Kv8Note(why), rcm;
+    const int S = KF_SEQS_MAX, N = seqs.n_seq, P = KF_SEQS_PANEL;
+    const int C = config.nEmbed, hd = config.head_dim, nh = config.n_head, nkv = config.n_head_kv, qd = nh * hd, kvd = nkv * hd, F = config.n_ff;
+    floatX *bx = ToX(srows.sX), *bq = ToX(srows.sQ), *bk = ToX(srows.sK), *bv = ToX(srows.sV), *ba = ToX(srows.sAttn), *bg = ToX(srows.sGate);
+    int32_t *d_tok = srows.d_tab, *d_pos = d_tok + S, *d_row0 = d_tok + 2 * S, *d_count = d_tok + 3 * S, *d_top1 = d_tok + 4 * S;
+    const kf_weight we = embed.w->desc(), wh = head.proj.w->desc();
+    floatX *bn = ToX(srows.sNorm), *bu = ToX(srows.sUp), *lg = seqs.keep_logits ? ToX(srows.sLogits) : nullptr;
+    {   /* the route of the linear parts, once per call: kf::seqs_linear_route asked with every layer matrix */
+        std::vector<kf_weight> descs;
+        for (int l = 0; l < config.nLayer; l++)
+            for (const SLP* m : LayerMatrices(l)) descs.push_back(m->w->desc());
+        std::vector<const kf_weight*> ptrs;
+        for (const kf_weight& d : descs) ptrs.push_back(&d);
+        seqs.route = kf_seqs_linear_route(ctx, ptrs.data(), (int)ptrs.size(), N);
+        if (seqs.route < 0) return seqs.route;
+    }
+    const bool tiles = seqs.route == 1;
+    int64_t before[2], after[2];
+    KF_TRY(kf_rows_route_counts(ctx, before));
+    for (int step = 0; step < n_steps; step++) {
+        bool live = false;
+        for (int s = 0; s < N; s++) live = live || seqs.pos[s] >= 0;
+        if (!live) break; /* every slot has its max_new ids (or no prompt) */
+        KF_TRY(kf_embed_batch(ctx, &we, d_tok, N, bx));
+        for (int l = 0; l < config.nLayer; l++) {
+            SelfAttention* a = attn[l].get();
+            FFN* m = ffn[l].get();
+            floatX* kc = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_KEY, l, 0));
+            floatX* vc = reinterpret_cast<floatX*>(cache.Get(KVCache::KV_VAL, l, 0));
+            const kf_weight wq = a->Q.w->desc(), wk = a->K.w->desc(), wv = a->V.w->desc(), wo = a->proj_cat.w->desc();
+            const kf_weight wg = m->gate.w->desc(), wu = m->up.w->desc(), wd = m->down.w->desc();
+            const kf_weight* qkv[3] = {&wq, &wk, &wv};
+            const int64_t row_stride[3] = {qd, kvd, kvd};
+            if (tiles) { /* n = N rows through the token-batch entries: ONE pass over every matrix */
+                KF_TRY(kf_rmsnorm(ctx, bx, ToX(a->norm.w), bn, N, C, a->norm.rms_eps, nullptr));
+                KF_TRY(kf_linear(ctx, &wq, bn, bq, nullptr, N, 1.0f, 0.0f, 0, nullptr));
+                KF_TRY(kf_linear(ctx, &wk, bn, bk, nullptr, N, 1.0f, 0.0f, 0, nullptr));
+                KF_TRY(kf_linear(ctx, &wv, bn, bv, nullptr, N, 1.0f, 0.0f, 0, nullptr));
+            }
+            for (int p0 = 0; p0 < N && !tiles; p0 += P) { /* the RAW q | k | v rows of a panel: one pass over the three matrices */
+                kf_bf16* ys[3] = {bq + (size_t)p0 * qd, bk + (size_t)p0 * kvd, bv + (size_t)p0 * kvd};
+                KF_TRY(kf_norm_linear_rows(ctx, bx + (size_t)p0 * C, C, ToX(a->norm.w), a->norm.rms_eps, 3, qkv, ys, row_stride, nullptr, 0, N - p0 < P ? N - p0 : P));
+            }
+            KF_TRY(kf_attn_block_seqs(ctx, bq, qd, bk, kvd, bv, kvd, kc, vc, ba, qd, a->normQ.w ? ToX(a->normQ.w) : nullptr, a->normK.w ? ToX(a->normK.w) : nullptr, rope_table, d_pos,
+                                      d_row0, seqs.pos.data(), N, nh, nkv, hd, kvd, a->normQ.rms_eps, srows.s_attn_ws->data));
+            if (tiles) {
+                KF_TRY(kf_linear(ctx, &wo, ba, bx, nullptr, N, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx));
+                KF_TRY(kf_rmsnorm(ctx, bx, ToX(m->norm.w), bn, N, C, m->norm.rms_eps, nullptr));
+                KF_TRY(kf_gateup_swiglu_batch(ctx, &wg, &wu, bn, bg, bu, N));
+                KF_TRY(kf_linear(ctx, &wd, bg, bx, nullptr, N, 1.0f, 0.0f, KF_EPI_RESIDUAL, bx));
+            }
+            for (int p0 = 0; p0 < N && !tiles; p0 += P) {
+                const int n = N - p0 < P ? N - p0 : P;
+                floatX* x = bx + (size_t)p0 * C;
+                KF_TRY(kf_linear_rows(ctx, &wo, ba + (size_t)p0 * qd, qd, x, C, n, KF_EPI_RESIDUAL, x, C));
+                KF_TRY(kf_norm_gateup_swiglu_rows(ctx, x, C, ToX(m->norm.w), m->norm.rms_eps, &wg, &wu, bg + (size_t)p0 * F, F, n));
+                KF_TRY(kf_linear_rows(ctx, &wd, bg + (size_t)p0 * F, F, x, C, n, KF_EPI_RESIDUAL, x, C));
+            }
+        }
+        if (tiles) { /* the row-batch head: the top-1 ids without the logit matrix (kf_head_logprob with nothing scored); the logits themselves only when asked for */
+            KF_TRY(kf_rmsnorm(ctx, bx, ToX(final_norm.w), bn, N, C, final_norm.rms_eps, nullptr));
+            KF_TRY(kf_head_logprob(ctx, &wh, bn, C, N, srows.d_tgt, srows.d_lp, nullptr, d_top1, srows.score_ws));
+            if (lg) KF_TRY(kf_linear(ctx, &wh, bn, lg, nullptr, N, 1.0f, 0.0f, 0, nullptr));
+        }
+        for (int p0 = 0; p0 < N && !tiles; p0 += P)
+            KF_TRY(kf_norm_lm_head_rows(ctx, bx + (size_t)p0 * C, C, ToX(final_norm.w), final_norm.rms_eps, &wh, lg ? lg + (size_t)p0 * config.vocab : nullptr, lg ? config.vocab : 0,
+                                        d_top1 + p0, N - p0 < P ? N - p0 : P, srows.s_head_ws->data));
+        KF_TRY(kf_seqs_advance(ctx, d_top1, d_tok, d_pos, d_count, srows.d_ids, config.n_ctx, seqs.max_new, seqs.eos, N));
+        for (int s = 0; s < N; s++) /* the mirror: a bound -- a slot the device parked on eos stays listed until its max_new */
+            if (seqs.pos[s] >= 0) seqs.pos[s] = ++seqs.count[s] >= seqs.max_new ? -1 : seqs.pos[s] + 1;
+        seqs.steps++, seqs.panels += tiles ? 1 : (N + P - 1) / P;
+    }
+    KF_TRY(kf_rows_route_counts(ctx, after));
+    seqs.rows[0] += after[0] - before[0], seqs.rows[1] += after[1] - before[1];
+    return KF_OK;
+}
+int Fish::SeqsTokens(int s, int* out, int cap, std::string& why) {
+    if (!seqs.n_seq || s < 0 || s >= seqs.n_seq || !out || cap < 0) return refused(why, "kfh_seqs_tokens", KF_INVALID_ARGS, "a slot of the open batch and a place for its ids"), -1;
+    int32_t n = 0;
+    if (kf_d2h(ctx, &n, srows.d_tab + 3 * KF_SEQS_MAX + s, 4) != KF_OK) return -1;
+    n = n < cap ? n : cap;
+    if (n > 0 && kf_d2h(ctx, out, srows.d_ids + (size_t)s * config.n_ctx, (size_t)n * 4) != KF_OK) return -1;
+    return n;
+}
+int Fish::SeqsKeepLogits(bool on) {
+    if (on && !srows.sLogits && !(srows.sLogits = GT(ctx, "sLogits", typNUMBER::BF16, config.vocab, KF_SEQS_MAX))) return KF_OUTOF_GPUMEMORY;
+    seqs.keep_logits = on;
+    return KF_OK;
+}
+int Fish::SeqsLogits(int s, floatX* out, std::string& why) {
+    if (!seqs.n_seq || s < 0 || s >= seqs.n_seq || !out || !seqs.keep_logits || !seqs.steps)
+        return refused(why, "kfhdbg_seqs_logits", KF_INVALID_ARGS, "a slot of the open batch, kfhdbg_seqs_keep_logits on, and a step behind it");
+    return kf_d2h(ctx, out, ToX(srows.sLogits) + (size_t)s * config.vocab, (size_t)config.vocab * 2);
+}
+int Fish::SeqsForce(const int* tokens, std::string& why) {
+    if (!seqs.n_seq || !tokens) return refused(why, "kfhdbg_seqs_force", KF_INVALID_ARGS, "no regions are open, or no ids");
+    for (int s = 0; s < seqs.n_seq; s++)
+        if (tokens[s] < 0 || tokens[s] >= config.vocab) return refused(why, "kfhdbg_seqs_force", KF_INVALID_ARGS, "an id outside the vocabulary");
+    return kf_h2d(ctx, srows.d_tab, tokens, (size_t)seqs.n_seq * 4);
+}
+int Fish::SeqsEnd() {
+    seqs.n_seq = 0; /* the counts stay readable (kfh_seqs_route_counts); the cache rows are whoever prefills next's */
     return KF_OK;
 }
 
@@ -2185,9 +2389,29 @@ int kfh_set_forced(void* h, const int32_t* forced, int n) {
     if (n > f->config.n_ctx) return KF_INVALID_ARGS;
     return kf_h2d(f->ctx, f->d_forced, forced, (size_t)n * 4);
 }
-int kfh_prefill(void* h, const int* tokens, int n, int pos0) { return reinterpret_cast<Fish*>(h)->Prefill(tokens, n, pos0); }
+int kfh_prefill(void* h, const int* tokens, int n, int pos0) {
+    return reinterpret_cast<Fish*>(h)->Prefill(tokens, n, pos0);
+}
+// batched decode (Fish::SeqsBegin .. SeqsEnd): refusals leave their reason in kfh_host_error
+int kfh_seqs_begin(void* h, int n_seq, int max_new, int eos) { return reinterpret_cast<Fish*>(h)->SeqsBegin(n_seq, max_new, eos, g_host_err); }
+int kfh_seqs_prefill(void* h, int s, const int* tokens, int n) { return reinterpret_cast<Fish*>(h)->SeqsPrefill(s, tokens, n, g_host_err); }
+int kfh_seqs_step(void* h, int n_steps) { return reinterpret_cast<Fish*>(h)->SeqsStep(n_steps, g_host_err); }
+int kfh_seqs_tokens(void* h, int s, int* out, int cap) { return reinterpret_cast<Fish*>(h)->SeqsTokens(s, out, cap, g_host_err); }
+int kfh_seqs_end(void* h) { return reinterpret_cast<Fish*>(h)->SeqsEnd(); }
+int kfh_seqs_route_counts(void* h, int64_t* out4) {
+    const Fish* f = reinterpret_cast<Fish*>(h);
+    if (!out4) return KF_INVALID_ARGS;
+    out4[0] = f->seqs.rows[0], out4[1] = f->seqs.rows[1], out4[2] = f->seqs.panels, out4[3] = f->seqs.steps;
+    return KF_OK;
+}
+int kfh_seqs_route(void* h) { return reinterpret_cast<Fish*>(h)->seqs.route; }
+int kfhdbg_seqs_keep_logits(void* h, int on) { return reinterpret_cast<Fish*>(h)->SeqsKeepLogits(on != 0); }
+int kfhdbg_seqs_logits(void* h, int s, uint16_t* out) { return reinterpret_cast<Fish*>(h)->SeqsLogits(s, reinterpret_cast<floatX*>(out), g_host_err); }
+int kfhdbg_seqs_force(void* h, const int* tokens) { return reinterpret_cast<Fish*>(h)->SeqsForce(tokens, g_host_err); }
 // Fish_ppl / Fish::Eval_ppl as a batch (Fish::Score, Fish::EvalPPL): logprob_out [n - 1] fp32, top1_out [n - 1] int32 or NULL
-int kfh_score(void* h, const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) { return reinterpret_cast<Fish*>(h)->Score(tokens, n, pos0, logprob_out, top1_out); }
+int kfh_score(void* h, const int* tokens, int n, int pos0, float* logprob_out, int* top1_out) {
+    return reinterpret_cast<Fish*>(h)->Score(tokens, n, pos0, logprob_out, top1_out);
+}
 int kfh_eval_ppl(void* h, const int* tokens, long long n, int window, double* ppl, double* pplerr, long long* n_scored) {
     return reinterpret_cast<Fish*>(h)->EvalPPL(tokens, n, window, ppl, pplerr, n_scored);
 }

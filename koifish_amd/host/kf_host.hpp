@@ -255,6 +255,17 @@ struct VerifyRows {
     DevBuf<int32_t> d_vtok;  // [8] the pass's ids, then [8] its greedy ids
     int Alloc(kf_ctx* c, const MODEL_CARD& card, const kf_weight& head);
 };
+// Batched decode (Fish::SeqsBegin .. SeqsEnd): the activation rows of up to KF_SEQS_MAX sequences, the attention and head scratch, the slots' device tables; allocated by the
+// first SeqsBegin.  d_tab: [tok | pos | row0 | count | top1][KF_SEQS_MAX] int32; d_ids: [KF_SEQS_MAX][n_ctx] the ids each slot produced
+constexpr int KF_SEQS_MAX = 32, KF_SEQS_PANEL = 8;  // kf_attn_block_seqs' sequences; the rows of one pass over the weights (kf_linear_rows)
+struct SeqsRows {
+    hGTensor sX, sQ, sK, sV, sAttn, sGate, s_attn_ws, s_head_ws;
+    hGTensor sNorm, sUp, sLogits;  // the token-batch route's normed rows and up rows; [KF_SEQS_MAX][vocab] logits (allocated by the first SeqsKeepLogits)
+    DevBuf<int32_t> d_tab, d_ids, d_tgt;  // d_tgt: [KF_SEQS_MAX] of -1, kf_head_logprob's "not scored"
+    DevBuf<float> d_lp;
+    DevBuf<> score_ws;
+    int Alloc(kf_ctx* c, const MODEL_CARD& card, const kf_weight& head);
+};
 // The context: the FIRST base of Fish, so it is destroyed LAST -- after every member and base that frees device memory through it.
 struct CtxHolder {
     kf_ctx* ctx = nullptr;
@@ -472,6 +483,35 @@ struct Fish : CtxHolder, SeqBuffers {
     hGTensor vLogits;  // [8][vocab], allocated by the first Verify that asks for logits
     int Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits_or_null, std::string& why);
     int64_t verify_rows[2] = {0, 0};  // activation rows of the Verify passes' mat-vec entries served with the shared unpack / row by row (kf_rows_route_counts deltas)
+    // ---- batched decode: n_seq = 1 .. KF_SEQS_MAX independent greedy sequences, one pass over the weights per step and ONE attention
+    // launch per layer for all of them (kf_attn_block_seqs).  SeqsBegin cuts the bf16 KV cache [n_layer][n_ctx][kv_dim] into n_seq regions of n_ctx / n_seq rows (nothing
+    // is allocated per token; a region is the longest context a sequence may reach); SeqsPrefill runs slot s's prompt through Prefill with the cache view moved to the
+    // region's first row (positions stay the tokens' own) -- a one-token prompt waits for the first step instead, as Generate runs it; SeqsStep runs greedy steps for every
+    // live slot.  The linear parts' route is chosen once per SeqsStep by kf_seqs_linear_route (the rule: kf_gemm_plan.h).  Row entries (at most 8 sequences, canonical
+    // order, 4-bit group / bf16 layers): kf_norm_linear_rows (raw q | k | v rows) -> kf_attn_block_seqs -> kf_linear_rows (+ residual) -> kf_norm_gateup_swiglu_rows ->
+    // kf_linear_rows (+ residual), then kf_norm_lm_head_rows.  Token-batch entries (everything else) with n = n_seq rows: kf_rmsnorm -> kf_linear x 3 (raw q | k | v) ->
+    // kf_attn_block_seqs -> kf_linear (+ residual) -> kf_rmsnorm -> kf_gateup_swiglu_batch -> kf_linear (+ residual), then kf_rmsnorm + kf_head_logprob (the top-1 ids).
+    // Then kf_seqs_advance.  Ids and positions stay on the device between steps; the host keeps a mirror of the positions that
+    // bounds them (a slot the device parked on eos stays listed until its max_new).  On the row route every id is Generate's (prefill_mode 1), id for id; on the token-batch route
+    // the logits lie within the token-batch bar of the token-serial step's.
+    // Not a mode: a call like Verify, refused while any mode is on or a sampler is set; while regions are open the entries that share the cache are refused (SeqsBusy).
+    SeqsRows srows;
+    struct SeqsState {
+        int n_seq = 0, region = 0, max_new = 0, eos = -1;  // n_seq 0: closed
+        int route = -1;                                     // of the last SeqsStep: kf_seqs_linear_route's answer (0 row entries, 1 token-batch entries)
+        bool keep_logits = false, inside = false;           // steps also leave every slot's logits row in sLogits; SeqsPrefill is running Prefill on a region
+        std::vector<int32_t> pos, count;                    // the host's mirror: pos[s] < 0 = parked or not admitted yet
+        int64_t rows[2] = {0, 0}, panels = 0, steps = 0;    // kf_rows_route_counts deltas of the steps, weight passes per matrix, steps
+    } seqs;
+    int SeqsBegin(int n_seq, int max_new, int eos, std::string& why);
+    int SeqsPrefill(int s, const int* tokens, int n, std::string& why);
+    int SeqsStep(int n_steps, std::string& why);
+    int SeqsTokens(int s, int* out, int cap, std::string& why);
+    int SeqsKeepLogits(bool on);                                 // from the next step on every step leaves the slots' logits rows (SeqsLogits reads one)
+    int SeqsLogits(int s, floatX* out, std::string& why);        // slot s's logits [vocab] of the last step
+    int SeqsForce(const int* tokens, std::string& why);          // teacher forcing: the next step's token of every slot (n_seq ids), instead of the id picked
+    int SeqsEnd();
+    int SeqsBusy(const char* entry, std::string& why) const;  // KF_OK, or the refusal of forward / generate / prefill / verify / score while regions are open
 };
 
 // Speculative decoding on a target Fish (greedy): rounds of "propose k ids, verify them in one pass, keep the longest agreed prefix" (kf_spec.hpp).  The ids it emits

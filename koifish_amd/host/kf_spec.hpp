@@ -50,14 +50,15 @@ inline int spec_lookup(const int* ids, int n, int ngram, int k, int* out) {
 // Fish::Verify runs the fused per-layer launches of the plain decode step, R rows at a time: every mode of the table changes what a layer runs, and the verify pass has
 // a form for none of them.  KF_OK, or the refusal in the table's own words, naming the first active mode: KF_UNSUPPORTED_DATATYPE for a tensor-parallel rank,
 // KF_INVALID_ARGS otherwise; a sampler that is not greedy is refused the same way (acceptance compares greedy ids; rejection sampling is not built)
-inline int verify_refusal(unsigned active, bool greedy, const char* entry, std::string& why) {
+// (`pass`: who refuses -- batched decode, Fish::SeqsBegin, runs the same row launches and refuses in the same words)
+inline int verify_refusal(unsigned active, bool greedy, const char* entry, std::string& why, const char* pass = "the verify pass") {
     for (int m = 0; m < N_MODES; m++) {
         if (!(active & mode_bit(m))) continue;
-        why = std::string(entry) + ": " + kModes[m].is_on + " and the verify pass has no " + kModes[m].form + " form: " + kModes[m].undo;
+        why = std::string(entry) + ": " + kModes[m].is_on + " and " + pass + " has no " + kModes[m].form + " form: " + kModes[m].undo;
         return m == MODE_TP ? KF_UNSUPPORTED_DATATYPE : KF_INVALID_ARGS;
     }
     if (!greedy) {
-        why = std::string(entry) + ": a sampler is set and the verify pass accepts greedy ids only: kfh_set_sampler with temperature 0 first";
+        why = std::string(entry) + ": a sampler is set and " + pass + " accepts greedy ids only: kfh_set_sampler with temperature 0 first";
         return KF_INVALID_ARGS;
     }
     return KF_OK;

@@ -581,6 +581,23 @@ class Context:
                                              _ptr(scratch)), "kf_attn_decode_rows")
         return out
 
+    def attn_block_seqs(self, q_raw, k_raw, v_raw, kc, vc, wq, wk, table, pos, row0, n_head, n_kv, hd, eps=1e-6, kv_stride=None, out=None, scratch=None, d_pos=None,
+                        d_row0=None):
+        """kf_attn_block_seqs: q_raw [S, >= n_head * hd], k_raw / v_raw [S, >= n_kv * hd], one row per independent sequence; pos / row0: the host lists (pos < 0:
+        parked), mirrored into int32 device tables unless d_pos / d_row0 are given (then pos only bounds d_pos).  Writes the new K / V rows at cache row
+        row0[s] + pos[s] and returns out [S, n_head * hd]; scratch: a zero-filled uint8 tensor of kf_attn_seqs_scratch_bytes kept between calls (default: a fresh one)"""
+        S = q_raw.shape[0]
+        out = torch.zeros(S, n_head * hd, dtype=torch.bfloat16, device=self.device) if out is None else out
+        if scratch is None:
+            scratch = torch.zeros(self.hip.kf_attn_seqs_scratch_bytes(n_head, hd, S), dtype=torch.uint8, device=self.device)
+        d_pos = torch.tensor(list(pos), dtype=torch.int32, device=self.device) if d_pos is None else d_pos
+        d_row0 = torch.tensor(list(row0), dtype=torch.int32, device=self.device) if d_row0 is None else d_row0
+        h_pos = (C.c_int32 * S)(*[int(p) for p in pos])
+        L.check(self.hip.kf_attn_block_seqs(self.h, _ptr(q_raw), q_raw.stride(0), _ptr(k_raw), k_raw.stride(0), _ptr(v_raw), v_raw.stride(0), _ptr(kc), _ptr(vc), _ptr(out),
+                                            out.stride(0), _ptr(wq), _ptr(wk), _ptr(table), _ptr(d_pos), _ptr(d_row0), h_pos, S, n_head, n_kv, hd, kv_stride or n_kv * hd, eps,
+                                            _ptr(scratch)), "kf_attn_block_seqs")
+        return out
+
     def rows_route_counts(self):
         """(activation rows served with the shared unpack, rows served by one-token launches) by the *_rows entries of this context"""
         out = (C.c_int64 * 2)()
@@ -991,7 +1008,7 @@ class Qwen3:
     def generate(self, prompt, n_new, use_graph=True):
         p = np.ascontiguousarray(prompt, dtype=np.int32)
         out = np.zeros(n_new, dtype=np.int32)
-        L.check(self.host.kfh_generate(self.h, p.ctypes.data_as(C.c_void_p), p.size, n_new, out.ctypes.data_as(C.c_void_p), int(use_graph)), "kfh_generate")
+        self._host_check(self.host.kfh_generate(self.h, p.ctypes.data_as(C.c_void_p), p.size, n_new, out.ctypes.data_as(C.c_void_p), int(use_graph)), "kfh_generate")
         return out.tolist()
 
     # ---- speculative decoding (host/kf_spec.hpp, Fish::Verify, koifish::SpecDecoder)
@@ -1011,6 +1028,38 @@ class Qwen3:
         self._host_check(self.host.kfh_verify(self.h, t.ctypes.data_as(C.c_void_p), t.size, int(pos0), top1.ctypes.data_as(C.c_void_p),
                                               None if logits is None else logits.ctypes.data_as(C.c_void_p)), "kfh_verify")
         return (top1, logits) if want_logits else top1
+
+    def generate_batch(self, prompts, n_new, eos=-1):
+        """Greedy decoding of len(prompts) = 1 .. 32 independent prompts on this one model: the KV cache cut into len(prompts) regions (a prompt and its new ids must fit
+        n_ctx // len(prompts) rows), every prompt through the batched prefill on its region, then steps that read the weights ONCE and run ONE attention launch per layer
+        for all of them (kf_attn_block_seqs).  Returns a list of id lists: n_new ids each, fewer for a sequence that met `eos` (its last id).  Up to 8 prompts on 4-bit
+        group / bf16 layers in the canonical order take the row entries and the ids are generate()'s with set_prefill_mode(1), id for id; anything else takes the
+        token-batch entries (MFMA tiles from 8 rows), whose logits lie within the token-batch bar of the token-serial step's (seqs_route_counts says which).  Raises with the reason while a mode is on or a sampler is set."""
+        self._host_check(self.host.kfh_seqs_begin(self.h, len(prompts), int(n_new), int(eos)), "kfh_seqs_begin")
+        try:
+            for s, prompt in enumerate(prompts):
+                t = np.ascontiguousarray(prompt, dtype=np.int32)
+                self._host_check(self.host.kfh_seqs_prefill(self.h, s, t.ctypes.data_as(C.c_void_p), t.size), "kfh_seqs_prefill")
+            self._host_check(self.host.kfh_seqs_step(self.h, int(n_new)), "kfh_seqs_step")
+            out = []
+            for s in range(len(prompts)):
+                ids = np.zeros(n_new, dtype=np.int32)
+                n = self.host.kfh_seqs_tokens(self.h, s, ids.ctypes.data_as(C.c_void_p), int(n_new))
+                self._host_check(0 if n >= 0 else -1, "kfh_seqs_tokens")
+                out.append(ids[:n].tolist())
+            return out
+        finally:
+            self.host.kfh_seqs_end(self.h)
+
+    def seqs_route_counts(self):
+        """of the last generate_batch (or the open one): "route": "rows" (the row entries: at most 8 sequences, canonical order, 4-bit group / bf16 layers) or "tiles" (the
+        token-batch entries with n = len(prompts) rows), chosen once per step call by kf_seqs_linear_route; "rows_shared" / "rows_single": activation rows the row entries
+        served with one unpack of every weight block / by one-token launches; "weight_passes": passes over every matrix; "steps": the decode steps run"""
+        out = (C.c_int64 * 4)()
+        L.check(self.host.kfh_seqs_route_counts(self.h, out), "kfh_seqs_route_counts")
+        r = dict(zip(("rows_shared", "rows_single", "weight_passes", "steps"), (int(v) for v in out)))
+        r["route"] = {0: "rows", 1: "tiles"}.get(self.host.kfh_seqs_route(self.h))
+        return r
 
     def generate_speculative(self, prompt, n_new, draft="lookup", k=4, ngram=3):
         """generate()'s ids -- id for id -- by rounds of "propose k ids, verify them in one pass over the weights, keep the longest prefix the model agrees with".
