@@ -50,7 +50,7 @@ enum kf_dtype {
 typedef struct kf_weight {
     const void* data;
     const kf_bf16* gama;
-    int32_t type;   /* kf_dtype: KF_BF16, KF_F8E5M2, KF_Q4, KF_T_SIGN, KF_BOOL1, KF_T_BINARY */
+    int32_t type;   /* kf_dtype: KF_BF16, KF_F8E5M2, KF_F8E4M3 (block-scaled, below), KF_Q4, KF_T_SIGN, KF_BOOL1, KF_T_BINARY */
     int32_t ne0;    /* rows  = out features (OC) */
     int32_t ne1;    /* cols  = in features  (IC) */
     int32_t nGroup; /* ne0*ne1/lGroup */
@@ -61,7 +61,23 @@ typedef struct kf_weight {
      * qscales fp16 [ne1/128, ne0]; gama is unused.  Served by kf_linear and kf_dequant (which then writes [ne1, ne0], TransA = 0).
      * kf_linear from 16 token rows (16-byte aligned qweight, scales and x): one launch of MFMA tiles on the packed words, no scratch; the product sums in MFMA
      * order, so a token-batch row equals the one-token entry within the token-batch bar, not bit for bit -- as for every other storage.  Fewer rows: the mat-vec
-     * per token row, which needs the scratch below. */
+     * per token row, which needs the scratch below.
+     * FP8 block-scaled layers (the FP8 releases of the Qwen3 family, the DeepSeek-style "weight" + "weight_scale_inv" pair): qscales non-NULL with qzeros NULL and
+     * type = KF_F8E4M3, quant = KF_QUANT_GROUP, lGroup = 128, gama = NULL.  data = OCP e4m3fn bytes [ne0, ne1] row-major, qscales = fp32 [ceil(ne0 / 128)][ne1 / 128]
+     * (4-byte aligned); a weight is scale[r / 128][k / 128] * e4m3(byte[r][k]) with ANY finite scale (checkpoints carry amax / 448).  Shape rule: ne1 % 128 == 0 and
+     * ne0 % 16 == 0 (a last scale row may cover fewer than 128 rows), else KF_BLAS_UNALIGN; qscales NULL, qzeros set, another lGroup or a gama: KF_QUANT_ERR.  Served by
+     * kf_linear, kf_norm_linear (1-3 matrices, all of this form), kf_norm_gateup_swiglu, kf_quantize and kf_dequant; every other entry answers
+     * KF_UNSUPPORTED_DATATYPE; no scratch (kf_linear_scratch_bytes = 0).  The scale never meets a single weight: an e4m3 x bf16 product is exact in fp32, a 128-wide
+     * k-block of a row is summed unscaled and its sum is multiplied once.
+     *   One token (kf_linear with nTok < 8 row by row, kf_norm_linear, kf_norm_gateup_swiglu -- ONE order, so the fused entries equal norm + kf_linear bit for bit):
+     *     a row is cut into pieces of 16 weights; lane l of a wave owns pieces l, l + 64, l + 128, ... in ascending order.  A piece is summed from +0 in two fma chains,
+     *     even k and odd k, each ascending, joined as even + odd; then acc = fma(scale of the piece's block, piece, acc).  The 64 lane sums are joined by the wave
+     *     butterfly of kf_device.h wave_sum (lanes ^1, ^2, row half mirror, row mirror, ^16, ^32).  A function of K alone: not of the launch plan, not of ne0.
+     *   Token batches (kf_linear, nTok >= 8): per 128-wide k-block four v_mfma_f32_16x16x32_bf16 steps fill a block accumulator from zero (the bytes widened to bf16,
+     *     exactly), then acc = fma(scale, block, acc), k-blocks ascending; equal to the one-token entry within the token-batch bar, not bit for bit.
+     * kf_quantize builds the form with power-of-two scales: per block amax, e = the smallest integer with amax * 2^-e <= 448, scale = 2^e (the rule of kf_act_quant_f8
+     * below), code = e4m3_rne(w * 2^-e) by v_cvt_pk_fp8_f32 -- the scaling is exact, the convert the only rounding; an all-zero block: scale 0, codes 0.  src 16-byte
+     * aligned.  kf_dequant writes bf16(scale * value), one rounding. */
     const void* qzeros;
     const void* qscales;
     /* Quant card mode (QUANT_MODE, GeQuant.hpp).  0 = KF_QUANT_GROUP: everything above.  KF_QUANT_ROW_LUT: the row-codebook 4-bit storage of

@@ -26,6 +26,7 @@
 #include "kf_gradnorm_plan.h"
 #include "kf_rowq.h"
 #include "kf_engine_host.h"
+#include "kf_f8b_plan.h"
 
 struct kf_ctx {
     int device;
@@ -302,6 +303,8 @@ static int check_weight(const kf_weight* w, const char* who) {
     if (!w || !w->data) return fail(KF_INVALID_ARGS, "%s: null weight", who);
     if (w->ne0 <= 0 || w->ne1 <= 0) return fail(KF_INVALID_ARGS, "%s: bad shape %d x %d", who, w->ne0, w->ne1);
     if (!al16(w->data)) return fail(KF_BLAS_UNALIGN, "%s: weight data not 16-byte aligned", who);
+    if (w->type == KF_F8E4M3 && !w->qzeros) /* the entries that serve the storage branch on it before they come here (check_f8b); with qzeros: the AutoAWQ test below, as ever */
+        return fail(KF_UNSUPPORTED_DATATYPE, "%s: e4m3 block-scaled weights are served by kf_linear, kf_norm_linear, kf_norm_gateup_swiglu, kf_quantize and kf_dequant", who);
     if (w->qzeros || w->qscales) { /* AutoAWQ layout */
         if (!w->qzeros || !w->qscales || w->type != KF_Q4 || w->lGroup != 128 || (w->ne0 % 8) || (w->ne1 % 128) || !al16(w->qscales))
             return fail(KF_QUANT_ERR, "%s: malformed AWQ weight (%d x %d, group %d)", who, w->ne0, w->ne1, w->lGroup);
@@ -333,19 +336,32 @@ static int check_weight(const kf_weight* w, const char* who) {
     return KF_OK;
 }
 
+// e4m3 bytes with one fp32 scale per 128 x 128 block (kf_f8b_plan.h states the form; kf_f8b.hip serves it): the entries that serve it ask here first
+static bool is_f8b(const kf_weight* w) { return w && w->type == KF_F8E4M3; }
+static int check_f8b(const kf_weight* w, const char* who) {
+    if (!w->data || w->ne0 <= 0 || w->ne1 <= 0) return fail(KF_INVALID_ARGS, "%s: null weight data or bad shape %d x %d", who, w->ne0, w->ne1);
+    const char* why;
+    const int r = kf::f8b_check(w, &why);
+    return r ? fail(r, "%s: %s (%d x %d)", who, why, w->ne0, w->ne1) : KF_OK;
+}
+
 int kf_dequant(kf_ctx* c, const kf_weight* w, kf_bf16* out) {
-    CHKCTX(c);
-    int r = check_weight(w, "kf_dequant");
+    int r = is_f8b(w) ? check_f8b(w, "kf_dequant") : KF_OK; /* the form is judged without a context */
     if (r) return r;
+    CHKCTX(c);
+    if (!is_f8b(w) && (r = check_weight(w, "kf_dequant"))) return r;
     if (!out || !al16(out)) return fail(KF_BLAS_UNALIGN, "kf_dequant: out null/unaligned");
+    if (is_f8b(w)) RET(kf::f8b_dequant_launch(c->stream, w, out));
     if (w->qzeros) RET(kf::awq_dequant_launch(c->stream, w, out));
     RET(kf::dequant_launch(c->stream, w, out));
 }
 int kf_quantize(kf_ctx* c, const kf_weight* w, const kf_bf16* src, int symmetric) {
-    CHKCTX(c);
-    int r = check_weight(w, "kf_quantize");
+    int r = is_f8b(w) ? check_f8b(w, "kf_quantize") : KF_OK;
     if (r) return r;
+    CHKCTX(c);
+    if (!is_f8b(w) && (r = check_weight(w, "kf_quantize"))) return r;
     if (!src) return fail(KF_INVALID_ARGS, "kf_quantize: null src");
+    if (is_f8b(w)) RET(kf::f8b_quantize_launch(c->stream, w, src));
     RET(kf::quantize_launch(c->stream, w, src, symmetric));
 }
 
@@ -355,7 +371,7 @@ static void init_args(kf_ctx* c, kf::GemvLaunch& L) { memset(&L, 0, sizeof(L)); 
 // change a route and with it the bits.  So it stays what it always was -- the row forms' GetDataX copy (the 4-bit row codebook's too), and the large-batch dequantise
 // route's shape even where that route's tile-count test then declines.
 size_t kf_linear_scratch_bytes(const kf_weight* w, int nTok) {
-    if (!w || nTok < 1) return 0;
+    if (!w || nTok < 1 || is_f8b(w)) return 0;
     if (w->qzeros) return kf::awq_scratch_bytes(w);
     const kf::GemmMat m = kf::mat_of(w);
     return m.quant != KF_QUANT_GROUP || kf::deq_tile_shape(m, nTok) ? (size_t)w->ne0 * w->ne1 * 2 : 0;
@@ -410,12 +426,26 @@ static int linear_rows(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16*
 }
 int kf_linear(kf_ctx* c, const kf_weight* w, const kf_bf16* x, kf_bf16* y, const kf_bf16* bias, int nTok, float alpha, float beta, uint32_t epilogue,
               const kf_bf16* residual) {
-    CHKCTX(c);
-    int r = check_weight(w, "kf_linear");
+    int r = is_f8b(w) ? check_f8b(w, "kf_linear") : KF_OK;
     if (r) return r;
+    CHKCTX(c);
+    if (!is_f8b(w) && (r = check_weight(w, "kf_linear"))) return r;
     if (nTok < 1) return fail(KF_INVALID_ARGS, "kf_linear: nTok=%d", nTok);
     if (!x || !y || !al16(x)) return fail(KF_BLAS_UNALIGN, "kf_linear: x/y null or x unaligned");
     if ((epilogue & KF_EPI_RESIDUAL) && !residual) return fail(KF_INVALID_ARGS, "kf_linear: residual epilogue without residual");
+    if (is_f8b(w)) { /* its own kernels: MFMA tiles from kf::F8B_TILE_MIN token rows, below that one mat-vec launch per row (ne1 % 128 == 0: every row of x is aligned) */
+        const kf_bf16* rs = (epilogue & KF_EPI_RESIDUAL) ? residual : nullptr;
+        if (nTok >= kf::F8B_TILE_MIN) {
+            r = kf::f8b_tile_launch(c->stream, w, x, nTok, y, bias, alpha, beta, rs);
+            return r ? fail(r, "kf_linear (e4m3 block-scaled tiles) failed with %d", r) : KF_OK;
+        }
+        for (int t = 0; t < nTok; t++) {
+            kf_bf16* yt = y + (size_t)t * w->ne0;
+            r = kf::f8b_vec_launch(c->stream, 1, &w, false, x + (size_t)t * w->ne1, nullptr, 0.0f, &yt, nullptr, 0, nullptr, bias, alpha, beta, rs ? rs + (size_t)t * w->ne0 : nullptr);
+            if (r) return fail(r, "kf_linear (e4m3 block-scaled mat-vec) failed with %d", r);
+        }
+        return KF_OK;
+    }
     if (nTok > 1 && ((w->ne1 * 2) % 16 != 0)) return fail(KF_BLAS_UNALIGN, "kf_linear: token rows of x are not 16-byte aligned");
     // nTok > 1 (SLP::Forw with a batch of tokens: x [nTok, ne1] row-major, y [nTok, ne0]): the MFMA tile kernels from kf::GEMM_MIN rows up when the shape is covered,
     // otherwise one mat-vec launch per token row; which kernel, on which operand, is kf::gemm_plan's choice
@@ -639,9 +669,24 @@ int kf_tp_pick(kf_ctx* c, const kf_tp_comm* t, int32_t* d_state, int32_t* d_toke
 
 int kf_norm_linear(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, float eps, int n_w, const kf_weight* const* w, kf_bf16* const* y,
                    const int64_t* y_pos_stride, int pos, const int32_t* d_pos) {
+    for (int i = 0; w && n_w <= 3 && i < n_w; i++) /* the e4m3 block-scaled form is judged without a context */
+        if (is_f8b(w[i])) {
+            const int r = check_f8b(w[i], "kf_norm_linear");
+            if (r) return r;
+        }
     CHKCTX(c);
     if (n_w < 1 || n_w > 3 || !w || !y) return fail(KF_INVALID_ARGS, "kf_norm_linear: n_w=%d", n_w);
     if (!x || !al16(x) || (norm_w && !al16(norm_w))) return fail(KF_BLAS_UNALIGN, "kf_norm_linear: x/norm_w null or unaligned");
+    int n_f8b = 0;
+    for (int i = 0; i < n_w; i++) n_f8b += is_f8b(w[i]);
+    if (n_f8b) { /* e4m3 block-scaled: one launch of its mat-vec over the 1 .. 3 matrices, the sums of kf_linear */
+        if (n_f8b != n_w) return fail(KF_UNSUPPORTED_DATATYPE, "kf_norm_linear: e4m3 block-scaled weights do not share a launch with another storage");
+        for (int i = 0; i < n_w; i++) {
+            if (!y[i]) return fail(KF_INVALID_ARGS, "kf_norm_linear: y[%d] null", i);
+            if (w[i]->ne1 != w[0]->ne1) return fail(KF_INVALID_ARGS, "kf_norm_linear: matrices of %d and %d inputs", w[0]->ne1, w[i]->ne1);
+        }
+        RET(kf::f8b_vec_launch(c->stream, n_w, w, false, x, norm_w, eps, y, y_pos_stride, pos, d_pos, nullptr, 1.0f, 0.0f, nullptr));
+    }
     kf::GemvLaunch L;
     init_args(c, L);
     L.n = n_w, L.mode = kf::GEMV_PLAIN, L.row_unpack = c->row_unpack;
@@ -658,6 +703,17 @@ int kf_norm_linear(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, float eps
 }
 
 int kf_norm_gateup_swiglu(kf_ctx* c, const kf_bf16* x, const kf_bf16* norm_w, float eps, const kf_weight* gate, const kf_weight* up, kf_bf16* act) {
+    if (is_f8b(gate) || is_f8b(up)) { /* e4m3 block-scaled: both rows of a pair in one wave, the SwiGLU of kf_device.h.  The form is judged without a context */
+        if (!is_f8b(gate) || !is_f8b(up)) return fail(KF_UNSUPPORTED_DATATYPE, "kf_norm_gateup_swiglu: e4m3 block-scaled gate and up come together");
+        int rf = check_f8b(gate, "kf_norm_gateup_swiglu");
+        if (!rf) rf = check_f8b(up, "kf_norm_gateup_swiglu");
+        if (rf) return rf;
+        CHKCTX(c);
+        if (gate->ne0 != up->ne0 || gate->ne1 != up->ne1) return fail(KF_INVALID_ARGS, "kf_norm_gateup_swiglu: gate %d x %d, up %d x %d", gate->ne0, gate->ne1, up->ne0, up->ne1);
+        if (!x || !act || !al16(x) || (norm_w && !al16(norm_w))) return fail(KF_BLAS_UNALIGN, "kf_norm_gateup_swiglu: x/act");
+        const kf_weight* gu[2] = {gate, up};
+        RET(kf::f8b_vec_launch(c->stream, 2, gu, true, x, norm_w, eps, &act, nullptr, 0, nullptr, nullptr, 1.0f, 0.0f, nullptr));
+    }
     CHKCTX(c);
     int r = check_weight(gate, "kf_norm_gateup_swiglu");
     if (r) return r;

@@ -266,6 +266,12 @@ size_t awq_scratch_bytes(const kf_weight* w);
 int awq_linear_launch(hipStream_t st, const kf_weight* w, const uint16_t* x, uint16_t* y, const uint16_t* bias, float alpha, float beta,
                       const uint16_t* residual, float* scratch);
 int awq_dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out);
+// ---- e4m3 bytes with one fp32 scale per 128 x 128 block (kf_f8b.hip; the shape rule and the launch plans: kf_f8b_plan.h).  Every weight has passed f8b_check
+int f8b_vec_launch(hipStream_t st, int n_w, const kf_weight* const* w, bool paired, const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* const* y,
+                   const int64_t* y_pos_stride, int pos, const int* d_pos, const uint16_t* bias, float alpha, float beta, const uint16_t* residual);
+int f8b_tile_launch(hipStream_t st, const kf_weight* w, const uint16_t* x, int n, uint16_t* y, const uint16_t* bias, float alpha, float beta, const uint16_t* residual);
+int f8b_quantize_launch(hipStream_t st, const kf_weight* w, const uint16_t* src);
+int f8b_dequant_launch(hipStream_t st, const kf_weight* w, uint16_t* out);
 
 int set_state_launch(hipStream_t st, int32_t* d_state, int token, int pos);
 int hot_rows_launch(hipStream_t st, const int32_t* hot, int n, int32_t* rows, int32_t* count);

@@ -22,6 +22,8 @@ kf_weight GTensor::desc() const {
     w.qMin = quant.qMin, w.qMax = quant.qMax, w.qBias = quant.qBias;
     if (quant.isNormalFloat) w.quant = KF_QUANT_ROW_LUT, w.nGroup = 0, w.lGroup = 0;
     if (qZero && qScale) w.qzeros = qZero->data, w.qscales = qScale->data, w.nGroup = (int)(size() / 128), w.gama = nullptr;
+    if (type == typNUMBER::F8E4M3) /* e4m3 bytes || fp32 block scales in ONE allocation (kf_storage.hpp): the scales are where gama lies for other types */
+        w.qscales = gama_T(), w.gama = nullptr, w.lGroup = 128, w.nGroup = (int)(szGama / 4);
     return w;
 }
 int GTensor::Alloc(kf_ctx* c, size_t nbytes) {
@@ -262,7 +264,8 @@ int SelfAttention::cuFlow(floatX* bx, int pos0, int n) {
     floatX* vrows = val_cache + (size_t)pos0 * kv_dim;
     floatX *bn = ToX(f->gBUFF.bNorm), *bq = ToX(f->gBUFF.bQ), *ba = ToX(f->gBUFF.bAttn);
     kf_weight wq = Q.w->desc(), wk = K.w->desc(), wv = V.w->desc(), wo = proj_cat.w->desc();
-    if (f->EagerOnly()) {  // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
+    if (f->EagerOnly() || wq.type == KF_F8E4M3 || wk.type == KF_F8E4M3 || wv.type == KF_F8E4M3) {  // e4m3 block-scaled layers: kf_rmsnorm, then kf_linear per matrix (its own MFMA tiles), as below
+                           // the unfused sequence: quantise, the integer products on tiles of token rows, then the existing q/k-norm + RoPE, prompt attention, residual epilogue
                            // adapters: kf_rmsnorm, kf_linear per matrix, kf_lora_apply per adapted matrix -- on the RAW k / v rows in the cache, before q/k-norm + RoPE, as the trainer's forward
         SLP* qkv[3] = {&Q, &K, &V};
         floatX* ys[3] = {bq, krows, vrows};
@@ -304,7 +307,7 @@ int FFN::cuFlow(floatX* bx, int n) {
     const int C = f->config.nEmbed;
     floatX *bn = ToX(f->gBUFF.bNorm), *bg = ToX(f->gBUFF.bGate), *bu = ToX(f->gBUFF.bUp);
     kf_weight wg = gate.w->desc(), wu = up.w->desc(), wd = down.w->desc();
-    if (f->EagerOnly()) {
+    if (f->EagerOnly() || wg.type == KF_F8E4M3 || wu.type == KF_F8E4M3) { /* e4m3 block-scaled layers: kf_rmsnorm, kf_linear per matrix, kf_swiglu */
         SLP* gu[2] = {&gate, &up};
         floatX* ys[2] = {bg, bu};
         KF_TRY(f->Group(bx, ToX(norm.w), norm.rms_eps, n, C, bn, 2, gu, ys, nullptr));
@@ -441,6 +444,15 @@ std::array<SLP*, 7> Fish::LayerMatrices(int l) const {
     return {&a->Q, &a->K, &a->V, &a->proj_cat, &m->gate, &m->up, &m->down};
 }
 static bool is_row3(const hGTensor& t) { return t && t->quant.isNormalFloat && t->type == typNUMBER::Q3; }
+static bool is_f8b(const hGTensor& t) { return t && t->type == typNUMBER::F8E4M3; }
+static const char* kF8bWhy = "a layer matrix is in the e4m3 block-scaled storage (FP8 checkpoints): such layers run on the per-layer launches (kf_norm_linear, kf_norm_gateup_swiglu, kf_linear), not in this path";
+bool Fish::HasF8Block() const {
+    for (int l = 0; l < config.nLayer; l++)
+        for (const SLP* s : LayerMatrices(l))
+            if (is_f8b(s->w)) return true;
+    return false;
+}
+const char* Fish::F8BlockWhy() { return kF8bWhy; }
 static const char* kRow3Why = "a layer matrix is a 3-bit row codebook (NF3): such layers run on the per-layer launches (kf_set_row_unpack), not in this path";
 bool Fish::HasRow3() const {
     for (int l = 0; l < config.nLayer; l++)
@@ -682,6 +694,10 @@ int Fish::EngineTable(floatX* kbase, floatX* vbase, bool masks, std::string& why
                 why = kRow3Why;
                 return KF_ENGINE_NOT_SERVED;
             }
+            if (is_f8b(s[j]->w)) {
+                why = kF8bWhy;
+                return KF_ENGINE_NOT_SERVED;
+            }
             L[l].w[j] = s[j]->w->desc();
         }
         if (!a->norm.w || !m->norm.w || (!masks && m->n_hot >= 0)) {
@@ -788,7 +804,7 @@ int Fish::EnsureResident(int PC) {
         for (const SLP* s : LayerMatrices(l)) {
             if (!s->w) continue;
             const kf_weight d = s->w->desc();
-            if (d.type != KF_BF16 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
+            if (d.type != KF_BF16 && d.type != KF_F8E4M3 && d.quant == KF_QUANT_GROUP && !d.qzeros) total += ((size_t)d.ne0 * d.ne1 * 2 + 255) & ~(size_t)255;
         }
     if (total == 0 || total + head_screen.bytes() > resident_max_bytes) return KF_OK;
     KF_TRY(kf_sync(ctx));
@@ -1149,7 +1165,7 @@ int Fish::PrefillReady(int min_rows) {
         KF_TRY(fresh.Alloc(ctx, PC, C, qd, config.n_ff));
         // the stacked large-batch routes (Q | K | V and gate | up dequantised back to back, one tile-GEMM launch each): their workspace, sized here -- the first
         // Prefill allocates the batch buffers anyway; the launches themselves never allocate.  The set is committed behind it: rows are never held without their scratch
-        for (int l = 0; l < config.nLayer; l++) {
+        for (int l = 0; l < config.nLayer && !HasF8Block(); l++) { /* e4m3 block-scaled layers go through kf_linear: no stacked route, no scratch */
             kf_weight wq = attn[l]->Q.w->desc(), wk = attn[l]->K.w->desc(), wv = attn[l]->V.w->desc(), wg = ffn[l]->gate.w->desc(), wu = ffn[l]->up.w->desc();
             const kf_weight* qkv[3] = {&wq, &wk, &wv};
             const kf_weight* gu[2] = {&wg, &wu};
@@ -1208,6 +1224,7 @@ int Fish::Verify(const int* tokens, int n, int pos0, int* top1, floatX* logits, 
         if (tokens[i] < 0 || tokens[i] >= config.vocab) return refused(why, "kfh_verify", KF_INVALID_ARGS, "a token id outside the vocabulary");
     if (!embed.w || !head.proj.w) return refused(why, "kfh_verify", KF_INVALID_ARGS, "the model has no weights yet");
     if (HasRow3()) return refused(why, "kfh_verify", KF_UNSUPPORTED_DATATYPE, kRow3Why); /* the row entries (kf_*_rows) do not unpack the 3-bit stream */
+    if (HasF8Block()) return refused(why, "kfh_verify", KF_UNSUPPORTED_DATATYPE, kF8bWhy);
     const int rcm = verify_refusal(Modes(), samp_params.greedy(), "kfh_verify", why);
     if (rcm != KF_OK) return Kv8Note(why), rcm;
     if (!vrows.vX) KF_TRY(Commit(vrows, ctx, config, head.proj.w->desc())); /* allocated by the first Verify */
@@ -1274,6 +1291,7 @@ int Fish::SeqsBegin(int n_seq, int max_new, int eos, std::string& why) {
     if (n_seq < 1 || n_seq > KF_SEQS_MAX || max_new < 1) return refused(why, E, KF_INVALID_ARGS, "1 .. 32 sequences and at least one new id each");
     if (!embed.w || !head.proj.w) return refused(why, E, KF_INVALID_ARGS, "the model has no weights yet");
     if (HasRow3()) return refused(why, E, KF_UNSUPPORTED_DATATYPE, kRow3Why);
+    if (HasF8Block()) return refused(why, E, KF_UNSUPPORTED_DATATYPE, kF8bWhy);
     for (int l = 0; l < config.nLayer; l++)
         for (const SLP* m : LayerMatrices(l))
             if (m->w->qZero) return refused(why, E, KF_UNSUPPORTED_DATATYPE, "a layer matrix is in the AutoAWQ layout, which batched decode has not been run on: such models decode one sequence at a time");
@@ -2237,6 +2255,10 @@ static int set_weight_impl(const char* entry, void* h, int layer, int slot, typN
     const Fish::ParamRef r = f->Resolve(*p);
     if (r.slp && r.slp->lora_a) /* the pair beside it was checked against the old matrix's sides */
         return set_refused(entry, KF_INVALID_ARGS, "the matrix carries a low-rank adapter: clear the adapters first");
+    if (type == typNUMBER::F8E4M3) { /* layer matrices of one storage family, in a model that runs no other mode (Fish::Admit refuses the modes afterwards) */
+        if (p->kind != P_MATRIX) return set_refused(entry, KF_UNSUPPORTED_DATATYPE, "the e4m3 block-scaled storage is for layer matrices: the embedding and the LM head have no kernel for it");
+        if (f->Modes() & ~mode_bit(MODE_FUSE0)) return set_refused(entry, KF_UNSUPPORTED_DATATYPE, std::string("a mode is on that does not serve it: ") + Fish::F8BlockWhy());
+    }
     Layout lay;
     hGTensor t = make_tensor<GTensor>(p->name, type, card, ne0, ne1, lay);
     if (!t) return set_refused(entry, lay.code(KF_BLAS_UNALIGN), lay.why);

@@ -285,6 +285,10 @@ struct Fish : CtxHolder, SeqBuffers {
         if (kv_int8 && kv_int8_prefill && why.find("int8 KV cache") != std::string::npos) why += " (its int8 prompt attention, kfh_set_kv_int8_prefill, is on too)";
     }
     int Admit(Mode asked, const char* entry, std::string& why) const {
+        if (asked != MODE_FUSE0 && HasF8Block()) { /* tensor parallel, int8 / fp8 activations, adapters, the int8 KV cache, hot-row masks: none reads the e4m3 block-scaled storage */
+            why = std::string(entry) + ": " + F8BlockWhy();
+            return KF_UNSUPPORTED_DATATYPE;
+        }
         const int rc = mode_refusal(Modes(), asked, entry, why);
         if (rc != KF_OK) Kv8Note(why);
         return rc;
@@ -431,6 +435,8 @@ struct Fish : CtxHolder, SeqBuffers {
     int n_adapters = 0, lora_r = 0;
     float lora_s = 0.0f;
     std::array<SLP*, 7> LayerMatrices(int layer) const;  // q k v o gate up down, the order of kf_engine_layer.w and of the C entries' slots
+    bool HasF8Block() const;  // a layer matrix is e4m3 bytes with block scales (FP8 checkpoints): per-layer launches, token batches through kf_linear; no engine, no XCD decoders, no Verify, no batched decode, no other mode
+    static const char* F8BlockWhy();
     bool HasRow3() const;  // a layer matrix is a 3-bit row codebook (NF3): per-layer launches with kf_set_row_unpack on; no engine, no XCD decoders, no Verify
     SLP* LayerMatrix(int layer, int slot) const;  // one of them, or NULL
     // ---- the parameters (kf_params.hpp): the table of this model's card, and where an entry lives -- the tensor of a norm or the embedding, the SLP of a matrix or the head

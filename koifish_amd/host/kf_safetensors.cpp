@@ -832,13 +832,42 @@ struct Loader {
         if (tp == typNUMBER::BF16) {
             KF_TRY(kf_d2d(f->ctx, t->data, d_src, lay.szData));
         } else {
-            if (lay.szGama) { /* R_SCALE / C_SCALE = 1 (rc_normal = 0) */
+            if (lay.szGama && tp != typNUMBER::F8E4M3) { /* R_SCALE / C_SCALE = 1 (rc_normal = 0); the e4m3 block-scaled form has fp32 scales there, written by kf_quantize */
                 std::vector<uint16_t> ones((size_t)p.ne0 + p.ne1, 0x3F80);
                 KF_TRY(kf_h2d(f->ctx, t->gama_T(), ones.data(), ones.size() * 2));
             }
             kf_weight d = t->desc();
             KF_TRY(kf_quantize(f->ctx, &d, d_src, 0));
         }
+        *out = t;
+        return KF_OK;
+    }
+    // FP8 checkpoint linear (quant_method "fp8", weight_block_size [128, 128]): <prefix>.weight F8_E4M3 [out, in] as it is, <prefix>.weight_scale_inv F32 or BF16
+    // [ceil(out / 128), in / 128] -> fp32 behind the bytes, one allocation (kf_storage.hpp; GTensor::desc points qscales there)
+    int fp8_block(const Param& p, const std::string& prefix, hGTensor* out) {
+        const ST_Tensor *w = st.Find(p.name), *sc = st.Find(prefix + ".weight_scale_inv");
+        if (st.Find(prefix + ".weight_scale")) return fail(KF_UNSUPPORTED_DATATYPE, prefix + ": a per-tensor weight_scale: served is one scale per 128 x 128 block (weight_scale_inv)");
+        if (!w || !sc) return fail(KF_INVALID_ARGS, prefix + ": weight / weight_scale_inv incomplete");
+        Layout lay;
+        hGTensor t = make_tensor<GTensor>(p.name, typNUMBER::F8E4M3, card_of(typNUMBER::F8E4M3, false, false, 128), p.ne0, p.ne1, lay);
+        if (!t) return fail(lay.code(KF_QUANT_ERR), "tensor '" + p.name + "': " + lay.why);
+        const int64_t sr = (p.ne0 + 127) / 128, scn = p.ne1 / 128;
+        const bool ok = w->dtype == "F8_E4M3" && w->shape.size() == 2 && w->shape[0] == p.ne0 && w->shape[1] == p.ne1 && (sc->dtype == "F32" || sc->dtype == "BF16") &&
+                        sc->shape.size() == 2 && sc->shape[0] == sr && sc->shape[1] == scn;
+        if (!ok) return fail(KF_QUANT_ERR, prefix + ": not F8_E4M3 [out, in] with F32 / BF16 weight_scale_inv [ceil(out / 128), in / 128]");
+        std::vector<float> scales((size_t)(sr * scn));
+        if (sc->dtype == "F32") {
+            memcpy(scales.data(), st.Data(*sc), scales.size() * 4);
+        } else {
+            const uint16_t* b = reinterpret_cast<const uint16_t*>(st.Data(*sc));
+            for (size_t i = 0; i < scales.size(); i++) {
+                const uint32_t u = (uint32_t)b[i] << 16;
+                memcpy(&scales[i], &u, 4);
+            }
+        }
+        KF_TRY(t->Alloc(f->ctx, lay.bytes()));
+        KF_TRY(kf_h2d(f->ctx, t->data, st.Data(*w), lay.szData));
+        KF_TRY(kf_h2d(f->ctx, t->gama_T(), scales.data(), lay.szGama));
         *out = t;
         return KF_OK;
     }
@@ -907,6 +936,21 @@ Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_t
         if (!Fish::ShapeServed(card, why)) return bail(KF_UNSUPPORTED_DATATYPE, "config.json: " + why); /* before any tensor is quantised */
     }
 
+    // "quantization_config": the FP8 releases' {"quant_method": "fp8", "weight_block_size": [128, 128]}; AutoAWQ directories are known by their tensors (below)
+    bool fp8 = false;
+    if (const JSON* qc = cfg.get("quantization_config")) {
+        const JSON* qm = qc->get("quant_method");
+        if (qm && qm->kind == JSON::STR && qm->str == "fp8") {
+            const JSON* bs = qc->get("weight_block_size");
+            if (!bs || bs->kind != JSON::ARR || bs->arr.size() != 2 || bs->arr[0].num != 128 || bs->arr[1].num != 128)
+                return bail(KF_UNSUPPORTED_DATATYPE, "config.json: quant_method fp8 is served with weight_block_size [128, 128] (one scale per 128 x 128 block), not " +
+                                                         (bs ? bs->Dump() : std::string("per-tensor scales")));
+            fp8 = true;
+        }
+    }
+    if (head_type == typNUMBER::F8E4M3)
+        return bail(KF_UNSUPPORTED_DATATYPE, "the e4m3 block-scaled storage is for layer matrices: the embedding and the LM head have no kernel for it");
+
     K_SafeTensors st;
     int rc = st.OpenDir(dir);
     if (rc != KF_OK) return bail(rc, st.err);
@@ -932,6 +976,10 @@ Fish* LoadHF(const std::string& dir, int device, void* stream, typNUMBER layer_t
         hGTensor t;
         if (p.kind == P_NORM) {
             rc = L.dense(p, typNUMBER::BF16, card_of(typNUMBER::BF16, false, false, 128), &t);
+        } else if (matrix && fp8 && st.Find(prefix + ".weight_scale_inv")) { /* an FP8 checkpoint's bytes and block scales are taken as they are */
+            rc = L.fp8_block(p, prefix, &t);
+        } else if (matrix && fp8 && st.Find(prefix + ".weight_scale")) {
+            rc = L.fp8_block(p, prefix, &t); /* refuses: per-tensor scale */
         } else if (matrix && st.Find(prefix + ".qweight")) { /* an AutoAWQ triple is taken as it is */
             rc = L.awq(prefix, p.ne0, p.ne1, &t);
             any_awq = true;
@@ -981,6 +1029,10 @@ int SaveKun(Fish* f, const std::string& path, std::string& err) {
         if (!t || !t->data) {
             err = "tensor '" + p.name + "' is empty";  // "[ST_SERIALIZE] \"%s\" is empty!" (Serialize.cpp:634)
             return KF_INVALID_ARGS;
+        }
+        if (t->type == typNUMBER::F8E4M3) {
+            err = "tensor '" + p.name + "': the e4m3 block-scaled storage (fp32 block scales) is not written to .kun";
+            return KF_UNSUPPORTED_DATATYPE;
         }
         if (t->qZero || t->qScale) {
             err = "tensor '" + p.name + "': vendor AutoAWQ tensors (explicit zeros / scales) are not written to .kun";
@@ -1091,6 +1143,7 @@ Fish* LoadKun(const std::string& path, int device, void* stream, int max_seq, in
             const std::string ms = m && m->kind == JSON::STR ? m->str : "";
             nf = ms.find("RTN") == std::string::npos && ms.find("AWQ") == std::string::npos && ms.find("yyang") == std::string::npos && ms.find("bitnet") == std::string::npos;  // GeQuant.cpp:1271-1279
         }
+        if (type == typNUMBER::F8E4M3) return fail(KF_UNSUPPORTED_DATATYPE, "the e4m3 block-scaled storage is not a .kun storage (kfh_save_kun refuses it)");
         if (type == typNUMBER::Q3 && (!nf || p.kind != P_MATRIX)) return fail(KF_UNSUPPORTED_DATATYPE, "Q<3> is served as the normal-float row form (quant_method \"NF\") of a layer matrix");
         const QuantCard card = card_of(type, sec && sec->bool_or("symmetric", false), nf, sec ? (int)sec->number_or("group_size", group_dflt) : group_dflt);
         Layout lay;

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/kf_abi.h"
+#include "../csrc/kf_f8b_plan.h" /* the e4m3 block-scaled form's shape rule, stated there (plain C++) */
 
 namespace koifish {
 
@@ -32,7 +33,7 @@ inline QuantCard card_of(typNUMBER t, bool symmetric, bool normal_float, int lGr
         case typNUMBER::Q2: q.bits = 2, q.qMax = 3; break;
         case typNUMBER::T_SIGN: q.bits = 2, q.qMin = -1, q.qMax = 1, q.qBias = 1; break;
         case typNUMBER::BOOL1: case typNUMBER::T_BINARY: q.bits = 1, q.qMax = 1; break;
-        case typNUMBER::F8E5M2: q.bits = 8; break;
+        case typNUMBER::F8E5M2: case typNUMBER::F8E4M3: q.bits = 8; break;
         default: break;
     }
     return q;
@@ -74,6 +75,9 @@ inline Layout layout_of(typNUMBER type, const QuantCard& q, int64_t ne0, int64_t
     const size_t r = (size_t)ne0, c = (size_t)ne1, n = mul(r, c), rc = add(r, c);
     if (type == typNUMBER::BF16 || type == typNUMBER::F8E5M2) {
         L.szData = type == typNUMBER::BF16 ? mul(n, 2) : n;
+    } else if (type == typNUMBER::F8E4M3) { /* a byte per weight || fp32 [ceil(ne0 / 128)][ne1 / 128] block scales (kf_weight.qscales); nGroup: their number */
+        if (!kf::f8b_shape_ok(ne0, ne1)) return refuse(KF_BLAS_UNALIGN, kf::f8b_shape_rule());
+        L.szData = n, L.nGroup = (size_t)kf::f8b_scale_count(ne0, ne1), L.szGama = mul(L.nGroup, 4);
     } else if (!is_quant_type(type) || (type == typNUMBER::Q3 && !q.isNormalFloat)) {
         return refuse(KF_UNSUPPORTED_DATATYPE, type == typNUMBER::Q3 ? "Q<3> is served as the normal-float row form only" : "type " + std::to_string((int)type) + " is not served by the decode path");
     } else if (q.isNormalFloat) { /* `bits`-wide stream || [R_SCALE ne0][C_SCALE ne1][LUT ne0 x 2^bits], or (zero, step) per row */

@@ -129,6 +129,37 @@ class AWQDevWeight:
         return self.qweight.numel() * 4 + self.qzeros.numel() * 4 + self.scales.numel() * 2
 
 
+class F8BlockDevWeight:
+    """e4m3 block-scaled weight in HBM (the FP8 checkpoints' form: kf_abi.h "FP8 block-scaled layers"): blob = e4m3fn bytes [ne0, ne1] ‖ fp32 scales
+    [ceil(ne0 / 128), ne1 / 128]; a weight is scale[r // 128][k // 128] * e4m3(byte).  in % 128 == 0 and out % 16 == 0."""
+
+    def __init__(self, ne0, ne1, blob):
+        self.type, self.ne0, self.ne1, self.blob, self.lGroup = L.F8E4M3, ne0, ne1, blob, 128
+        self.qMin = self.qMax = self.qBias = 0
+        self.szData, self.szGama, self.nGroup = weight_layout(L.F8E4M3, ne0, ne1, 128)
+        if self.szData == 0:
+            raise L.KFError("F8BlockDevWeight: %d x %d: %s" % (ne0, ne1, L.load()[1].kfh_host_error().decode()))
+        assert blob.numel() == self.szData + self.szGama, (blob.numel(), self.szData, self.szGama)
+
+    @staticmethod
+    def blob_bytes(ne0, ne1):
+        return sum(weight_layout(L.F8E4M3, ne0, ne1, 128)[:2])
+
+    def desc(self):
+        p = self.blob.data_ptr()
+        return L.Weight(p, None, L.F8E4M3, self.ne0, self.ne1, self.nGroup, 128, 0, 0, 0, None, p + self.szData)
+
+    def algorithmic_bytes(self):
+        """what a mat-vec has to read: the bytes + the block scales"""
+        return self.szData + self.szGama
+
+    def codes(self):
+        return self.blob[:self.szData].view(self.ne0, self.ne1)
+
+    def scales(self):
+        return self.blob[self.szData:].view(torch.float32).view(-1, self.ne1 // 128)
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -213,6 +244,11 @@ class Context:
             h = w_bf16.to(torch.float32).to(torch.float16).view(torch.int16)
             b = ((h.to(torch.int32) >> 8) & 0xFF).to(torch.uint8)
             return DevWeight(L.F8E5M2, ne0, ne1, b.reshape(-1).contiguous())
+        if type_ == L.F8E4M3:   # e4m3 codes with a power-of-two scale per 128 x 128 block: one workgroup per block on the device
+            fw = F8BlockDevWeight(ne0, ne1, torch.zeros(F8BlockDevWeight.blob_bytes(ne0, ne1), dtype=torch.uint8, device=self.device))
+            d = fw.desc()
+            L.check(self.hip.kf_quantize(self.h, C.byref(d), _ptr(w_bf16), 0), "kf_quantize")
+            return fw
         blob = torch.zeros(DevWeight.blob_bytes(type_, ne0, ne1, lGroup), dtype=torch.uint8, device=self.device)
         dw = DevWeight(type_, ne0, ne1, blob, lGroup, symmetric)
         g = blob[dw.szData:].view(torch.bfloat16)

@@ -43,6 +43,13 @@ MATS = ("qkv", "proj", "fc", "proj2")
 GAMA_TYPES = (L.Q4, L.T_SIGN, L.BOOL1)   # the PackedQ group storages kf_gama_backward serves
 
 
+def _trainable_types(types):
+    """the trainers' storage types: the e4m3 block-scaled storage is inference-only (kf_linear_backward has no form for it)"""
+    if L.F8E4M3 in types.values():
+        raise L.KFError("the e4m3 block-scaled storage (L.F8E4M3) is inference-only: the trainers' backward has no form for it")
+    return types
+
+
 def _align256(ptr):
     """a scratch the ABI wants 256-byte aligned is allocated 256 bytes longer and handed over from here"""
     return (ptr + 255) & ~255
@@ -361,7 +368,7 @@ class GPT2Step(_TrainStep):
         g = self._begin(ctx, train_target, seed)
         self.C, self.H, self.NL, self.V, self.Vp, self.B, self.T = C_, H, NL, V, Vp, B, T
         self.hd, self.N = C_ // H, B * T
-        self.types = dict(qkv=L.F8E5M2, proj=L.F8E5M2, fc=L.Q4, proj2=L.Q4) if types is None else dict(types)
+        self.types = _trainable_types(dict(qkv=L.F8E5M2, proj=L.F8E5M2, fc=L.Q4, proj2=L.Q4) if types is None else dict(types))
         dev, bf = ctx.device, torch.bfloat16
         z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
         rnd = lambda *s, std=w_std: (torch.randn(*s, device=dev, generator=g) * std).to(bf)
@@ -528,7 +535,7 @@ class Qwen3Step(_TrainStep):
         self.eps, self.theta = float(cfg.get("rms_eps", 1e-6)), float(cfg.get("theta", 1e6))
         Vp, N, Cq, Ck = self.Vp, self.N, H * hd, KV * hd
         W_ = Cq + 2 * Ck
-        self.types = dict({k: L.Q4 for k in Q3_MATS}, **(types or {}))
+        self.types = _trainable_types(dict({k: L.Q4 for k in Q3_MATS}, **(types or {})))
         dev, bf, f32 = ctx.device, torch.bfloat16, torch.float32
         z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)
         rnd = lambda *s: (torch.randn(*s, device=dev, generator=g) * w_std).to(bf)
